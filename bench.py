@@ -17,12 +17,15 @@ delivered frames that equal a transmitted BBFRAME is REPORTED (the reference's d
 reproduces bit for bit, lose frames at low SNR), and every delivered frame of every stream is compared on the device.
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full   the same, plus every check and secondary measurement (below)
     python bench.py --config mixed64 [--gpus N]            BASELINE config 4 (64 mixed-MODCOD transponders, strong scaling)
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = the LDPC decoder: hipEvent pairs around every launch INSIDE
-the timed steps, on the stream it runs on, plus a stand-alone launch), `cpu_baseline` (rank 0, N=1: the reference's own FEC code
-compiled into oracle/_ref when that build travelled, else the oracle port, plus the oracle front end) and `secondary` (configs
-2, 5, D and the mixed-MODCOD batch).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`,
+`stage_ms_per_step`: hipEvent pairs around every launch inside the timed steps).  `--dump-outputs DIR` writes what the last timed
+step delivered as DIR/*.npy (see last_step_outputs).  `--full` adds the frame check of the last timed step + the pipeline flush, the
+decoder self-check, `roofline` (dominant kernel = the LDPC decoder: the launches inside the timed steps plus stand-alone launches),
+`cpu_baseline` (rank 0, N=1: the reference's own FEC code compiled into oracle/_ref when that build travelled, else the oracle
+port, plus the oracle front end), `secondary` (configs 2, 5, D and the mixed-MODCOD batch) and the two config-4 lines.
 """
 import argparse
 import json
@@ -172,9 +175,9 @@ class S2Run:
         self.iq = self.out = None
 
 
-def time_steps(run, steps, warmup, barrier, pipelined, prove_decoder=False):
-    """preroll + warm-up (untimed), then `steps` timed steps between barriers; verifies the last timed step and the flush"""
-    import torch
+def time_steps(run, steps, warmup, barrier, pipelined, prove_decoder=False, full=True, dump=False):
+    """preroll + warm-up (untimed), then `steps` timed steps between barriers; with `full`, verifies the last timed step and the flush.
+    -> (seconds, stage times, checks (None unless full), outputs of the last timed step (None unless dump))"""
     eng = run.eng
     eng.set_pipelined(pipelined)
     for _ in range(max(1, -(-PREROLL_FRAMES // run.F))):
@@ -190,6 +193,10 @@ def time_steps(run, steps, warmup, barrier, pipelined, prove_decoder=False):
     barrier()
     dt = time.perf_counter() - t0
     stages = eng.stage_times()
+    outputs = last_step_outputs(run, nb) if dump else None      # (before the flush below writes into the same buffers)
+    if not full:
+        eng.set_pipelined(False)           # (drops the frames of the last timed step, which nobody collects here)
+        return dt, stages, None, outputs
     balancer = {k: eng.get_state(k) for k in ('g_prio_duty', 'g_prio_auto', 'g_prio_hold', 'stage_pipeline_on', 'fec_part_on')}
     acc = run.check(nb)
     proof = None
@@ -202,7 +209,40 @@ def time_steps(run, steps, warmup, barrier, pipelined, prove_decoder=False):
         eng.set_pipelined(False)
     acc['balancer'] = balancer
     acc['decoder_self_check'] = proof
-    return dt, stages, acc
+    return dt, stages, acc, outputs
+
+
+DUMP_BYTES = 48 << 20      # float32 bytes of the sampled output buffers (the whole dump stays under 64 MB)
+DUMP_SEED = 2024
+
+
+def last_step_outputs(run, nb):
+    """What a caller of the timed path holds after the last timed step, as float arrays (uint8 -> float32 is exact):
+      bytes_delivered   float64 [S]          byte counts the call returned, every stream
+      frame_byte_sums   float64 [S, cap]     sum of the bytes of every delivered BBFRAME slot, every stream (0 where nothing was delivered)
+      bbframes          float32 [n, cap*kb]  the output buffers of a fixed, seeded sample of n streams, bytes past the delivered count zeroed
+      sample_streams    float64 [n]          which streams those are"""
+    import torch
+    torch.cuda.synchronize()
+    S, cap, kb = run.S, run.cap, run.kb
+    nbt = torch.as_tensor(np.asarray(nb, dtype=np.int64), device=run.out.device)
+    valid = torch.arange(cap * kb, device=run.out.device)[None, :] < nbt[:, None]
+    sums = torch.empty((S, cap), dtype=torch.float64, device=run.out.device)
+    for a in range(0, S, 256):
+        fr = run.out[a:a + 256] * valid[a:a + 256]
+        sums[a:a + 256] = fr.view(-1, cap, kb).sum(-1, dtype=torch.int64).to(torch.float64)
+    n = min(S, max(1, DUMP_BYTES // (cap * kb * 4)))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(S, n, replace=False))
+    pt = torch.as_tensor(pick, device=run.out.device)
+    frames = (run.out[pt] * valid[pt]).to(torch.float32)
+    return {'bytes_delivered': np.asarray(nb, dtype=np.float64), 'frame_byte_sums': sums.cpu().numpy(),
+            'bbframes': frames.cpu().numpy(), 'sample_streams': pick.astype(np.float64)}
+
+
+def dump_outputs(outdir, outputs):
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
 
 
 def decoder_self_check(run, nb, valid, good, n_spread=40, n_odd=24):
@@ -401,7 +441,7 @@ def secondary_s2(eng, pkg, dev, name, modcod, rate, short, pilots, esn0_db, S, F
     # untimed steps first: the pipelined mode's balancer (wave-priority share of the timing loop, stage pipeline on / off; the FEC partition stream) starts from zero for every new
     # configuration (s2_demod.hip) and moves one notch per two consistent calls: a front-end-bound configuration needs these steps to reach ITS setting -- 8 where the decoder
     # is the critical path (the setting stays near zero), 20 in the plugin's mode (seven notches + the partition rule: 16 calls; a receiver runs for hours)
-    dt, stages, acc = time_steps(run, steps, 8 if force else 20, barrier, True)
+    dt, stages, acc, _ = time_steps(run, steps, 8 if force else 20, barrier, True)
     k = ldpc_alone(eng, run.info, rate, short, S * F, dev)
     bpf = ITERS * 4 * run.info['ldpc_edges'] + run.info['ldpc_n'] + run.info['kbch'] // 8
     if not force:
@@ -781,7 +821,12 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-secondary', action='store_true', help='skip configs 2, 5, D and the mixed-MODCOD batch')
     ap.add_argument('--no-pipeline', action='store_true', help='run the FEC inside the call that produced the frames (no overlap with the next front end)')
+    ap.add_argument('--full', action='store_true', help='besides the headline: frame check, decoder self-check, roofline, CPU baseline, secondary configs, config 4 lines '
+                    '(--no-cpu-baseline / --no-secondary leave parts of it out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed headline step delivered as DIR/<name>.npy (rank 0; see last_step_outputs)')
     args = ap.parse_args()
+    if args.dump_outputs and args.config != 'headline':
+        ap.error('--dump-outputs: only the headline configuration')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` on its own: start N ranks (one per GPU) as CHILD processes of this one, which has not touched the
@@ -858,13 +903,40 @@ def main():
     t_start = time.perf_counter()
     run = S2Run(eng, pkg, dev, MODCOD, SHORT, PILOTS, ESN0_DB, S, F, args.distinct, seed=rank, **(dict(iters=16, force=False) if args.plugin_mode else {}))
     t_setup = time.perf_counter() - t_start
-    dt, stages, acc = time_steps(run, args.steps, args.warmup, barrier, pipelined, prove_decoder=pipelined and rank == 0)
+    dt, stages, acc, outputs = time_steps(run, args.steps, args.warmup, barrier, pipelined, prove_decoder=args.full and pipelined and rank == 0,
+                                          full=args.full, dump=bool(args.dump_outputs) and rank == 0)
     dt = dd.max_over_ranks(dt)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     info, sym = run.info, run.sym
     block0 = run.blocks_host[0]
     iq_bytes = int(S) * run.nsamp * 8
     run.close()
     torch.cuda.empty_cache()
+
+    value = world * S * F * args.steps * sym / dt / 1e6
+    head = {
+        'metric': 'Msymbols/s demod+FEC, DVB-S2 8PSK 3/4 normal-frame @50 LDPC iters',
+        'value': round(value, 3), 'unit': 'Msymbols/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': round(dt / args.steps * 1e3, 4), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': 'int8 (FEC) / f32 (demod)', 'data': 'synthetic',
+        'config': {'workload': WORKLOAD,
+                   'streams_per_gpu': S, 'frames_per_stream_per_step': F, 'symbols_per_frame': sym, 'distinct_signal_blocks': min(args.distinct, S),
+                   'private_iq_copy_per_stream_bytes_total': iq_bytes,
+                   'parallelism': 'independent transponder streams sharded over GPUs, no data-path collective',
+                   'fec_pipelined_across_steps': pipelined,
+                   'setup_seconds_before_first_step': round(t_setup, 1),
+                   'ranks_seen_by_backend': (dist.get_world_size() if dist is not None else 1), 'backend': (backend if dist is not None else 'none')},
+        'stage_ms_per_step': {name: round(v[0] / args.steps, 3) for name, v in stages.items()},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        eng.close()
+        return
 
     nfr = S * F
     k = ldpc_alone(eng, info, RATE, SHORT, nfr, dev)
@@ -892,30 +964,20 @@ def main():
         traffic_current = tj.get('kernel_source_sha16') == ldpc_source_hash()
 
     if rank == 0:
-        value = world * S * F * args.steps * sym / dt / 1e6
         line = {
-            'metric': 'Msymbols/s demod+FEC, DVB-S2 8PSK 3/4 normal-frame @50 LDPC iters',
-            'value': round(value, 3), 'unit': 'Msymbols/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': round(dt / args.steps * 1e3, 4), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'int8 (FEC) / f32 (demod)', 'data': 'synthetic',
+            **head,
             # the same workload with the reference's check cadence (LDPCDecoder::operator(), layered_decoder.hh:121-133: bad() before EVERY iteration; the headline's forced mode
             # evaluates it once): `value` scaled by the decoder's own forced / normal time on input that never converges (all 50 iterations run), measured alone in this run
             'value_normal_mode': (round(value / (1.0 + (in_step_ms * l_n / (dt * 1e3)) * (k['normal'] / k['forced'] - 1.0)), 3) if k['normal_all_ran'] and l_n else None),
-            'config': {'workload': WORKLOAD,
-                       'streams_per_gpu': S, 'frames_per_stream_per_step': F, 'symbols_per_frame': sym, 'distinct_signal_blocks': min(args.distinct, S),
-                       'private_iq_copy_per_stream_bytes_total': iq_bytes,
-                       'parallelism': 'independent transponder streams sharded over GPUs, no data-path collective',
+            'config': {**head['config'],
                        'frames_delivered_checked': acc['delivered'], 'frames_equal_to_transmitted': acc['equal'],
                        'fraction_equal_to_transmitted': round(acc['equal'] / max(acc['delivered'], 1), 5),
                        'frames_out_of_sequence': acc['out_of_order'],
                        'check': 'every delivered frame of every stream, last timed step + pipeline flush, on the device (hash + full byte compare)',
                        'decoder_self_check': acc['decoder_self_check'],
-                       'fec_pipelined_across_steps': pipelined,
                        # where the pipelined mode's run-time balancer stood after the last timed step (s2_demod.hip: priority share of the timing loop 0..8, stage pipeline,
                        # decoder jobs on the 128-unit partition stream): two runs compare only at the same setting
-                       'balancer_final_state': acc['balancer'],
-                       'setup_seconds_before_first_step': round(t_setup, 1),
-                       'ranks_seen_by_backend': (dist.get_world_size() if dist is not None else 1), 'backend': (backend if dist is not None else 'none')},
+                       'balancer_final_state': acc['balancer']},
             'roofline': {'bound': 'hbm',
                          'bound_note': 'NOMINAL: algorithmic bytes against the 8 TB/s HBM peak, as the contract asks for a byte / integer path -- the state is on-chip and what bounds the kernel is vector issue -- its instructions are packed 16-bit / DPP / byte-permute forms, which a SIMD issues at HALF rate (valu_note) -- plus what the layers with shared bits cost beyond a plain row update (profiles/r06_ldpc_split_layers.txt); the layers with shared bits are SPECULATIVE since round 6: their time depends on how far the frame has converged (kernel_ms_alone: noise; kernel_ms_alone_on_the_steps_llrs: the step\'s own frames), their result does not',
                          'kernel': ('ldpc_split_kernel<%d>' % plan['max_deg']) if form == 2 else 'ldpc_decode_kernel<%d,%d,%s>' % (plan['max_deg'], plan['rec_dwords'], 'true' if plan.get('irregular') else 'false'),
@@ -938,7 +1000,6 @@ def main():
                          'syndrome_check': 'forced mode (the headline): evaluated once, after the last iteration; normal mode: before every iteration, as in the reference (bit-vector form, see DESIGN.md)',
                          'note': 'posteriors stay in LDS; the message records (132 MB live) bounce through the Infinity Cache, whose hits the fabric-side counters include',
                          'plan': plan},
-            'stage_ms_per_step': {name: round(v[0] / args.steps, 3) for name, v in stages.items()},
         }
         if world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(block0)

@@ -14,6 +14,9 @@ def pytest_configure(config):
 
 @pytest.fixture(scope='session')
 def pkg():
+    # torch before the library: torch links its own HIP runtime by the unversioned name libamdhip64.so, so a library loaded first would
+    # bring the system runtime in beside it, and in a run of the whole suite the GPU tests' library would then find no device
+    import torch  # noqa: F401
     import __graft_entry__ as g
     return g.load_package()
 

@@ -59,7 +59,7 @@ def test_bench_gpus_2_starts_two_ranks_by_itself():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--streams', '128', '--frames', '2',
-                        '--no-secondary', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=1200)
+                        '--full', '--no-secondary', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -10,6 +10,7 @@ F=$1; shift
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function"
 case "$F" in s2_rx_kernels|s2_demod|dvbs_demod) FLAGS="$FLAGS -ffp-contract=off";; esac
 OTHERS=$(ls $SRC/*.o | grep -v "/$F.o")
+BENCH_ARGS="--full ${BENCH_ARGS:-}"      # (the bench lines below read `roofline`, which only a --full run prints)
 for V in "$@"; do
   /opt/rocm/bin/hipcc $FLAGS $V -c $SRC/$F.hip -o /tmp/ab_variant.o
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/libdvbs2gpu_variant.so $OTHERS /tmp/ab_variant.o

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 for cfg in "$@"; do
   echo "== $cfg"
-  env $cfg python bench.py --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | tail -1 | python3 -c "
+  env $cfg python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('headline', d['value'], 'ms/step', round(d['ms_per_step'],1), d.get('stage_ms_per_step'))

@@ -13,7 +13,7 @@ from bench import ldpc_source_hash
 F, P = os.path.join(ROOT, 'gpurun_out', 'fin_' + tag), os.path.join(ROOT, 'profiles')
 rd = lambda n: open(os.path.join(F, n)).read()
 open(os.path.join(P, tag + '_bench.json'), 'w').write(rd('bench.json'))
-open(os.path.join(P, tag + '_bench_kernel_stats.csv'), 'w').write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary (tools/profile_run.sh)\n' + rd('kt.csv'))
+open(os.path.join(P, tag + '_bench_kernel_stats.csv'), 'w').write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary (tools/profile_run.sh)\n' + rd('kt.csv'))
 open(os.path.join(P, tag + '_bench_timeline.txt'), 'w').write('# start_ms end_ms duration_ms queue kernel -- dispatches >= 2 ms of the same run (tools/timeline.py); q=3: FEC stream, q=2: front-end stream\n' + rd('timeline.txt'))
 rows = [l.rstrip() for p in ('p1', 'p2', 'p3', 'p4') if os.path.exists(os.path.join(F, p + '.csv')) for l in open(os.path.join(F, p + '.csv')) if 'ldpc_decode_kernel' in l or 'ldpc_split_kernel' in l]
 get = lambda c: ([float(l.split(',')[-1]) for l in rows if '"' + c + '"' in l] or [float('nan')])[0]

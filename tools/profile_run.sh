@@ -7,9 +7,9 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/fin_$TAG
 rm -rf $O; mkdir -p $O
 cd $R
-timeout 900 python bench.py 2> $O/bench.err | tail -1 > $O/bench.json
+timeout 900 python bench.py --full 2> $O/bench.err | tail -1 > $O/bench.json
 cd /tmp; export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > $O/kt.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary > $O/kt.log 2>&1
 export FRAMES=4096 ITERS=50
 timeout 300 rocprofv3 --kernel-trace --stats --pmc FETCH_SIZE -d $O/p1 -- python3 $R/tools/pmc_ldpc.py 6 > $O/p1.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --pmc WRITE_SIZE -d $O/p2 -- python3 $R/tools/pmc_ldpc.py 6 > $O/p2.log 2>&1
