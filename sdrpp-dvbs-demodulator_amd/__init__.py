@@ -315,7 +315,7 @@ class Engine:
         self._check(self.lib.dvbs2gpu_set_option(self.h, str(name).encode(), int(value)))
 
     def get_state(self, name):
-        """read-only introspection (dvbs2gpu_get_state): 'kernel_launches', 'g_prio_duty', 'stage_pipeline_on', 'fec_part_on', ..."""
+        """read-only introspection (dvbs2gpu_get_state): 'kernel_launches', 'g_prio_duty', 'stage_pipeline_on', 'pipelined', ..."""
         v = C.c_longlong()
         self._check(self.lib.dvbs2gpu_get_state(self.h, str(name).encode(), C.byref(v)))
         return int(v.value)

@@ -65,7 +65,7 @@ int apply_option(dvbs2gpu_ctx* c, const char* name, int v) {
     }
     else if (n == "ldpc_split") { if (!in(0, 1)) return -1; c->ldpc_split = v; }       // (read at every launch)
     else if (n == "ldpc_split_fail_attempts") { if (!in(0, 1)) return -1; c->ldpc_split_fail_attempts = v; }       // (tests: the fall-back path of the half-row decoder's speculative layers)
-    else if (n == "gardner_form") { if (!(v == 0 || v == 1 || v == 2 || v == 4)) return -1; c->gardner_form = v; }
+    else if (n == "gardner_form") { if (!(v == 0 || v == 2 || v == 4)) return -1; c->gardner_form = v; }
     else if (n == "gardner_cand_skew") { c->gardner_cand_skew = v; }
     else if (n == "fe_slices") { if (!in(0, s2::S2_FE_MAX_SLICES)) return -1; c->fe_slices = v; }
     else if (n == "stage_pipeline") { if (!in(0, 2)) return -1; c->stage_pipeline = v; }
@@ -74,7 +74,6 @@ int apply_option(dvbs2gpu_ctx* c, const char* name, int v) {
     else if (n == "stage_min_duty") { if (!in(-1, 8)) return -1; c->stage_pipeline_min_duty = v; }
     else if (n == "loops_ahead") { if (!in(0, 1)) return -1; c->loops_ahead = v; }
     else if (n == "mixed_groups") { if (!in(0, 1)) return -1; c->mixed_groups = v; }
-    else if (n == "fec_part") { if (!in(-1, 1)) return -1; c->fec_part = v; c->fec_part_on = v == 1; c->fec_part_trend = 0; }
     else if (n == "mix_fec_streams") { if (!in(1, 8)) return -1; c->mix_fec_streams = v; }
     else if (n == "g_prio_duty") { if (!in(-1, 8)) return -1; if (v < 0) c->g_prio_auto = true; else { c->g_prio_duty = v; c->g_prio_auto = false; } }
     else if (n == "stage_loops_stream") { if (!in(0, 1)) return -1; c->stage_loops_stream = v; }
@@ -407,8 +406,7 @@ int dvbs2gpu_get_state(dvbs2gpu_ctx* ctx, const char* name, long long* value) {
     else if (n == "g_prio_auto") *value = ctx->g_prio_auto ? 1 : 0;
     else if (n == "g_prio_hold") *value = ctx->g_prio_hold;
     else if (n == "stage_pipeline_on") *value = ctx->last_call_staged ? 1 : 0;
-    else if (n == "fec_part_on") *value = ctx->fec_part_on ? 1 : 0;
-    else if (n == "fec_part") *value = ctx->fec_part;
+    else if (n == "fec_part_on") *value = 0;     // (the FEC partition stream is gone; the name stays for readers of the state)
     else if (n == "pipelined") *value = ctx->pipeline_fec;
     else if (n == "num_cus") *value = ctx->num_cus;
     else { g_err = std::string("unknown state name: ") + name; return DVBS2GPU_ERR_ARG; }
@@ -471,7 +469,6 @@ void dvbs2gpu_destroy(dvbs2gpu_ctx* ctx) {
     }
     if (ctx->fe_stream) (void)hipStreamDestroy(ctx->fe_stream);
     if (ctx->fec_stream) (void)hipStreamDestroy(ctx->fec_stream);
-    if (ctx->fec_part_stream) (void)hipStreamDestroy(ctx->fec_part_stream);
     if (ctx->ev_llr) (void)hipEventDestroy(ctx->ev_llr);
     if (ctx->ev_in) (void)hipEventDestroy(ctx->ev_in);
     for (int g = 0; g < dvbs2gpu_ctx::MAX_PIPE_GROUPS; ++g) {

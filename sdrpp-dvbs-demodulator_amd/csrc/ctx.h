@@ -149,20 +149,7 @@ struct dvbs2gpu_ctx {
     LastFecJob last_fec[MAX_PIPE_GROUPS];
     bool last_call_staged = false;            // the last CCM batch ran its post stages behind every front-end slice (the stage pipeline)
     hipEvent_t ev_fec[MAX_PIPE_GROUPS][2] = {};   // end of a group's FEC job, per job parity (the next job is enqueued before the previous one is delivered)
-    hipEvent_t ev_fec_t0[MAX_PIPE_GROUPS][2] = {};   // ... and its start (timing events: the job's duration feeds the rule below)
-    // THE PLUGIN'S MODE BY SPACE (s2_demod.hip, process_group): a second FEC stream confined to FEC_PART_CUS compute units.  A single-configuration batch whose decoder job is long
-    // done when the next call's front end is through AND would still fit into a call period on that many units gets its jobs there: the front end, which is that batch's critical
-    // path, then shares fewer units with decoder workgroups.  Jobs on the two streams never overlap (they share the FEC workspaces): fec_last_done / fec_last_stream.
-    hipStream_t fec_part_stream = nullptr;
-    hipEvent_t fec_last_done = nullptr;
-    hipStream_t fec_last_stream = nullptr;
-    // OFF BY DEFAULT since the third part of round 6: hipExtStreamCreateWithCUMask makes a BLOCKING stream, and every operation on the legacy null stream waits for the jobs on a
-    // blocking stream -- the host's own null-stream work did, and so does the event that orders a throughput-mode call behind the host's input producers
-    // (s2_demod.hip: ev_in): with the rule on, the front end of call k + 1 waited for the decoder job of call k (plugin's mode 118.7 -> 171.6 ms per step).  Without the rule
-    // the plugin's mode takes 122.5 ms (it bought 3 %); fec_part = -1 / 1 still select it for hosts that keep everything off the null stream and synchronise their inputs.
-    int fec_part = 0;                         // option fec_part: -1 by the rule, 0 never (default), 1 every big job of a single-configuration batch
-    bool fec_part_on = false;
-    int fec_part_trend = 0;
+    hipEvent_t ev_fec_t0[MAX_PIPE_GROUPS][2] = {};   // ... and its start (timing events: the job's duration feeds the priority balancer)
     std::chrono::steady_clock::time_point fec_last_entry{};
     // several groups of one pipelined batch run their MODCOD-dependent stages side by side (one host thread and HIP stream each)
     s2::Workspace ws_grp[MAX_PIPE_GROUPS][8];
@@ -179,7 +166,7 @@ struct dvbs2gpu_ctx {
     int loops_ahead = 1;                      // 0: frame loops only behind the PL sync (small banks)
     int mixed_groups = 0;                     // 1: small mixed batches through the per-group flow instead of process_mixed
     int mix_fec_streams = 4;                  // side streams for the FEC jobs of process_mixed (1..8)
-    int gardner_form = 0;                     // 1 / 2 / 4: one form of the timing recovery (0: chosen by bank size and balance)
+    int gardner_form = 0;                     // 2 / 4: one form of the timing recovery (0: chosen by bank size)
     int gardner_cand_skew = 0;                // tests only: skews the candidate form's arm prediction so that it leaves its tables
     int ldpc_wave = -1;                       // short frames: 0 / 1 = lane-per-row / wave-per-frame decoder (-1: per code)
     int ldpc_split_fail_attempts = 0;         // tests only: every attempt of the half-row decoder's layers with shared bits is made to fail (ldpc_split_kernel.hip: the long way must give the same bits)

@@ -82,21 +82,18 @@ __device__ __forceinline__ void atab_load(uint32_t (&pw)[NPW], const uint32_t* _
 #pragma unroll
     for (int i = 0; i < NPI; ++i) pw[2 * i] = w[i];
 }
-#ifndef LDPC_DIET
-#ifndef LDPC_OTHER_SUM
-#define LDPC_OTHER_SUM 1   // the other-minimum selection of the output phase as a sum minus a minimum (2 packed operations per link pair instead of 3).  Frames/s, 1024 frames x 50
-#endif                     // iterations, without -> with: normal 1/3 77 694 -> 82 151, 2/5 103 492 -> 104 048, 1/2 103 140 -> 106 015, 3/5 66 843 -> 67 977, 2/3 102 926 -> 106 170,
-                           // 4/5 80 950 -> 82 588, 5/6 73 178 -> 74 543, 8/9 97 007 -> 99 090, 9/10 83 223 -> 83 865, 1/4 118 119 -> 117 120; short 1/4 314 901 -> 335 881, the other
-                           // short codes within 1 %; the degree-12 kernel (3/4 normal, at the register cap: a different allocation eats it) 93 348 -> 90 917 -- it keeps the product form
-template <int MAXDEG, bool IRREG> constexpr bool ldpc_other_sum() { return LDPC_OTHER_SUM && MAXDEG != 12; }
-#define LDPC_DIET 1   // two cuts in a layer's per-wave instruction stream (what a layer costs): (1) the layer-ahead fetches -- message record, address / row words --
-                      // are issued unconditionally by every lane (idle lanes with a clamped row index; the records are cleared at the start of a frame, so the first sweep needs no "is
-                      // this the first sweep" either): no exec-mask juggling and, above all, no "fetched / not fetched" merge of the registers, which cost a copy of every prefetch register
-                      // at the top AND the bottom of the layer loop (20 v_mov); (2) the parity bits' LDS addresses follow the layer by one add instead of being rebuilt from the layer number.
-#endif
+// the other-minimum selection of the output phase as a sum minus a minimum (2 packed operations per link pair instead of 3).  Frames/s, 1024 frames x 50
+// iterations, without -> with: normal 1/3 77 694 -> 82 151, 2/5 103 492 -> 104 048, 1/2 103 140 -> 106 015, 3/5 66 843 -> 67 977, 2/3 102 926 -> 106 170,
+// 4/5 80 950 -> 82 588, 5/6 73 178 -> 74 543, 8/9 97 007 -> 99 090, 9/10 83 223 -> 83 865, 1/4 118 119 -> 117 120; short 1/4 314 901 -> 335 881, the other
+// short codes within 1 %; the degree-12 kernel (3/4 normal, at the register cap: a different allocation eats it) 93 348 -> 90 917 -- it keeps the product form
+template <int MAXDEG, bool IRREG> constexpr bool ldpc_other_sum() { return MAXDEG != 12; }
+// two cuts in a layer's per-wave instruction stream (what a layer costs): (1) the layer-ahead fetches -- message record, address / row words --
+// are issued unconditionally by every lane (idle lanes with a clamped row index; the records are cleared at the start of a frame, so the first sweep needs no "is
+// this the first sweep" either): no exec-mask juggling and, above all, no "fetched / not fetched" merge of the registers, which cost a copy of every prefetch register
+// at the top AND the bottom of the layer loop (20 v_mov); (2) the parity bits' LDS addresses follow the layer by one add instead of being rebuilt from the layer number.
 // Measured per kernel (1024 frames x 50 iterations, frames/s): degree 2 (1/4) 114 441 -> 118 196, degree 5 (1/2) 99 026 -> 102 814, degree 28 (9/10) 79 153 -> 83 527;
 // degree 8 (2/3) 102 711 -> 100 674 and degree 12 (3/4) 92 541 -> 91 892: the two kernels that sit AT the 128-register cap lose what they gain to a different allocation and keep the old form
-template <int MAXDEG, bool IRREG> constexpr bool ldpc_diet() { return LDPC_DIET && (IRREG || (MAXDEG != 8 && MAXDEG != 12)); }
+template <int MAXDEG, bool IRREG> constexpr bool ldpc_diet() { return IRREG || (MAXDEG != 8 && MAXDEG != 12); }
 #ifndef LDPC_WPE4_MAXDEG
 #define LDPC_WPE4_MAXDEG 28    // kernels up to this degree are held to 128 VGPRs (4 waves per SIMD: room for a front-end wave beside three decoder waves)
 #endif

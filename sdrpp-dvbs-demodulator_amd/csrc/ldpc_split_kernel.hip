@@ -30,21 +30,6 @@ namespace s2 {
 #ifndef LDPC_SPLIT_SKIP
 #define LDPC_SPLIT_SKIP 0           // development switch for counter experiments (results wrong): bit k set = the pseudo-layers of kind k do nothing
 #endif
-#ifndef LDPC_SPLIT_CHAIN_SPEC
-#define LDPC_SPLIT_CHAIN_SPEC 1    // chain layers try the plain row update where the previous chain layer changed no shared posterior (A/B switch)
-#endif
-#ifndef LDPC_SPLIT_SPEC_ATTEMPT
-#define LDPC_SPLIT_SPEC_ATTEMPT 1  // the same attempt ahead of the speculative passes (A/B switch)
-#endif
-#ifndef LDPC_SPLIT_DBG
-#define LDPC_SPLIT_DBG 0
-#endif
-#ifndef LDPC_SPLIT_BASE_PRIO
-#define LDPC_SPLIT_BASE_PRIO 0     // wave priority of the decoder outside its chain walks (A/B switch)
-#endif
-#ifndef LDPC_SPLIT_WPE
-#define LDPC_SPLIT_WPE 8          // waves per SIMD the register allocation aims at (6 = 80 VGPRs: two workgroups per compute unit; 8 = 64: room for a 128-register front-end wave beside them)
-#endif
 
 template <int MAXDEG>
 struct SplitShape {
@@ -153,7 +138,7 @@ struct RowState {
 // the totals where `late` is not zero (chain walk: 1, speculative passes: 2) -- V / G keep the values read
 // NOPREV: the pseudo-layer holds row 0 of layer 0, which has no previous parity bit (kind 7: a conflict-free layer; the plan refuses codes whose layer 0 has shared bits) --
 // a kind of its own, so that the other 44 layers of a sweep do not carry the test (r05: 7 vector instructions per wave and layer)
-template <int MAXDEG, int LATE, int NOPREV = 0>     // NOPREV 2: asked at run time (A/B builds, -DLDPC_SPLIT_NOPREV_RT)
+template <int MAXDEG, int LATE, int NOPREV = 0>     // NOPREV 2: asked at run time (noprev_rt: the chain / speculative layers of SplitShape::NOPREV_SHARED codes)
 __device__ __forceinline__ void row_input(RowState<MAXDEG>& R, const uint32_t late, const uint32_t noprev_t, const int t, int& M0, int& M1, int& SXs, const bool noprev_rt = false,
                                           uint32_t* x0 = nullptr /* [2]: the posteriors of slots 0 / 1 and 2 / 3 as read: bits 15:8 / 31:24 */, const int nx = 1) {
     using S = SplitShape<MAXDEG>;
@@ -356,7 +341,7 @@ __device__ __forceinline__ void chain_layer(RowState<MAXDEG>& R, uint32_t (&rec_
     // the previous chain layer's verdict: its word holds its number where some early slot changed (the words are cleared with the frame: the first chain layer does not try).
     // (Tried: two consistent layers in a row before an attempt -- slower where frames converge slowly, no faster on noise; the word read behind the layer's barrier and
     //  claimed at the top of the next pseudo-layer -- the bookkeeping in the layer loop cost more than the round trip here.)
-    const bool attempt = LDPC_SPLIT_CHAIN_SPEC && (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const lds_u1*)(uintptr_t)(flagb + 4u * ((cseq - 1u) & 1u))) != cseq - 1u;
+    const bool attempt = (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const lds_u1*)(uintptr_t)(flagb + 4u * ((cseq - 1u) & 1u))) != cseq - 1u;
     int M0, M1, SXs;
     uint32_t x0, pn0 = 0;
     SPLIT_MARK_DECL;
@@ -417,7 +402,7 @@ __device__ __forceinline__ void chain_layer(RowState<MAXDEG>& R, uint32_t (&rec_
         }
 #undef WALK_ROW
         if (t + T * chain_d < 360) LDS_I8(cwb + 8u * (uint32_t)(t + T * chain_d) + 7u) = (int8_t)x;
-        __builtin_amdgcn_s_setprio(LDPC_SPLIT_BASE_PRIO);
+        __builtin_amdgcn_s_setprio(0);
     }
     SPLIT_MARK(3);
     lds_barrier();
@@ -453,7 +438,7 @@ __device__ __forceinline__ void chain_layer(RowState<MAXDEG>& R, uint32_t (&rec_
         row_output<MAXDEG, 2>(R, M0, M1, SXs, early, rec_out, &pn0);
     }
     // the verdict for the next chain layer: did any slot a later row reads change?  (after a failed attempt the word is set already)
-    if (LDPC_SPLIT_CHAIN_SPEC && !attempt) {
+    if (!attempt) {
         const bool bad = ((pn0 ^ (x0 >> 8)) & emask) != 0;
         if (__builtin_amdgcn_ballot_w64(bad) != 0 && (t & 63) == 0) *(lds_u1*)(uintptr_t)my_flag = cseq;
     }
@@ -464,16 +449,8 @@ __device__ __forceinline__ void chain_layer(RowState<MAXDEG>& R, uint32_t (&rec_
 // 1 = "L"), the dependency chains walked by a few lanes; 6: quad walk (at most 4 shared links, deep and narrow level structure: one wave walks the rows of levels
 // >= 2, four lanes per row); 3: a barrier per level (at most 4 shared links).  The row word -- level | late << 8 | early << 12, zero for half 1 and idle lanes, so
 // every condition below is false there -- rides in the table.
-#ifndef LDPC_SPLIT_FIX
-#define LDPC_SPLIT_FIX 7
-#endif
-#if LDPC_SPLIT_FIX & 1
 typedef const __attribute__((address_space(4))) uint32_t* const_u32_ptr;
 typedef const __attribute__((address_space(4))) LdpcSplitLayer* const_layer_ptr;
-#else
-typedef const uint32_t* const_u32_ptr;
-typedef const LdpcSplitLayer* const_layer_ptr;
-#endif
 
 __device__ __forceinline__ LdpcSplitLayer layer_at(const_layer_ptr layers, int i) {      // (field by field: a struct in the constant address space has no copy constructor on the host pass)
     LdpcSplitLayer L;
@@ -525,7 +502,7 @@ __device__ __forceinline__ void spec_layer(RowState<MAXDEG>& R, uint32_t (&rec_o
     // the verdict words the layers with shared bits hand on (chain_layer): where the layer before changed no posterior a later row reads, this one first tries the plain row
     // update -- every input from its bit, slots 0..3 of the rows of level > 1 held back, one barrier, done if every such posterior got its value back -- and only else the passes
     const uint32_t my_flag = vflagb + 4u * (cseq & 1u);
-    const bool attempt = LDPC_SPLIT_CHAIN_SPEC && LDPC_SPLIT_SPEC_ATTEMPT && (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const lds_u1*)(uintptr_t)(vflagb + 4u * ((cseq - 1u) & 1u))) != cseq - 1u;
+    const bool attempt = (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const lds_u1*)(uintptr_t)(vflagb + 4u * ((cseq - 1u) & 1u))) != cseq - 1u;
     // (a copy of the side entry of its own for the attempt: a value fetched behind the compiler's back must have ONE place where it is claimed -- with two, the compiler
     //  moved the registers between them while the load was still on its way)
     u32x2 side_a = {0u, 0u};
@@ -542,15 +519,15 @@ __device__ __forceinline__ void spec_layer(RowState<MAXDEG>& R, uint32_t (&rec_o
     if (prof && blockIdx.x == 0 && t == 0) { prof[900] += 1; prof[901] += attempt; prof[910 + (cseq < 40 ? cseq : 40)] += attempt; }
 #endif
     if (attempt) {
-        if (!(LDPC_SPLIT_DBG & 2) || level == 1u) row_output<MAXDEG, 4>(R, M0, M1, SXs, spec ? 15u : 0u, rec_out, pn, 2);
+        row_output<MAXDEG, 4>(R, M0, M1, SXs, spec ? 15u : 0u, rec_out, pn, 2);
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(side_a) : : "memory");
         em0 = (((side_a.x >> 15) & 1u) ? 0xffu : 0u) | (((side_a.x >> 31) & 1u) ? 0xff0000u : 0u);
         em1 = (((side_a.y >> 15) & 1u) ? 0xffu : 0u) | (((side_a.y >> 31) & 1u) ? 0xff0000u : 0u);
-        const bool bad = (LDPC_SPLIT_DBG & 1) || fail_attempts || (!half1 && ((((pn[0] ^ (xr[0] >> 8)) & em0) | ((pn[1] ^ (xr[1] >> 8)) & em1)) != 0));
+        const bool bad = fail_attempts || (!half1 && ((((pn[0] ^ (xr[0] >> 8)) & em0) | ((pn[1] ^ (xr[1] >> 8)) & em1)) != 0));
         if (__builtin_amdgcn_ballot_w64(bad) != 0 && (t & 63) == 0) *(lds_u1*)(uintptr_t)my_flag = cseq;
-        if (!(LDPC_SPLIT_DBG & 8)) { lds_pairs_wait();
-        lds_barrier(); }
-        if (!(LDPC_SPLIT_DBG & 8) && (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const lds_u1*)(uintptr_t)my_flag) != cseq) {
+        lds_pairs_wait();
+        lds_barrier();
+        if ((uint32_t)__builtin_amdgcn_readfirstlane((int)*(const lds_u1*)(uintptr_t)my_flag) != cseq) {
 #if LDPC_SPLIT_SPEC_STATS
             if (prof && blockIdx.x == 0 && t == 0) prof[902] += 1;
 #endif
@@ -562,8 +539,7 @@ __device__ __forceinline__ void spec_layer(RowState<MAXDEG>& R, uint32_t (&rec_o
             }
             return;
         }
-        if (LDPC_SPLIT_DBG & 4) row_input<MAXDEG, -2, SplitShape<MAXDEG>::NOPREV_SHARED>(R, spec ? 1u : 0u, 1u, t, M0, M1, SXs, ((L.kind_nw >> 20) & 1u) != 0);
-        else row_totals<MAXDEG, -2>(R, spec ? 1u : 0u, M0, M1, SXs);          // the long way: the totals without slots 0..3 where the row has predecessors
+        row_totals<MAXDEG, -2>(R, spec ? 1u : 0u, M0, M1, SXs);          // the long way: the totals without slots 0..3 where the row has predecessors
     } else {
         if (level == 1u) row_output<MAXDEG, 0>(R, M0, M1, SXs, 0u, rec_out, pn, 2);
     }
@@ -656,7 +632,7 @@ __device__ __forceinline__ void spec_layer(RowState<MAXDEG>& R, uint32_t (&rec_o
         row_output<MAXDEG, 4>(R, M0, M1, SXs, half1 ? 0u : early, rec_out, pn, 2);          // (a slot a later row touches stays unwritten)
     }
     // the verdict for the next layer with shared bits (after a failed attempt the word is set already)
-    if (LDPC_SPLIT_CHAIN_SPEC && !attempt) {
+    if (!attempt) {
         em0 = (((side.x >> 15) & 1u) ? 0xffu : 0u) | (((side.x >> 31) & 1u) ? 0xff0000u : 0u);
         em1 = (((side.y >> 15) & 1u) ? 0xffu : 0u) | (((side.y >> 31) & 1u) ? 0xff0000u : 0u);
         const bool bad = !half1 && ((((pn[0] ^ (xr[0] >> 8)) & em0) | ((pn[1] ^ (xr[1] >> 8)) & em1)) != 0);
@@ -667,8 +643,9 @@ __device__ __forceinline__ void spec_layer(RowState<MAXDEG>& R, uint32_t (&rec_o
 #undef LINK_MG
 #undef LINK_SET
 
+// (waves_per_eu 8: the register allocation aims at 64 VGPRs -- room for a 128-register front-end wave beside the decoder; 6 = 80 VGPRs would leave two workgroups per compute unit)
 template <int MAXDEG>
-__global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(LDPC_SPLIT_WPE))) void ldpc_split_kernel(LdpcKernelParams read_through_ldpc_params) {
+__global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(8))) void ldpc_split_kernel(LdpcKernelParams read_through_ldpc_params) {
     // (the arguments are read section by section through ldpc_params(), ldpc_lane_common.h: this by-value structure must stay the kernel's FIRST AND ONLY parameter --
     // ldpc_params() reads it at offset 0 of the kernel-argument segment)
     using S = SplitShape<MAXDEG>;
@@ -677,7 +654,6 @@ __global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(LD
     const int t = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     int8_t* __restrict__ post = lds_all;
-    if (LDPC_SPLIT_BASE_PRIO) __builtin_amdgcn_s_setprio(LDPC_SPLIT_BASE_PRIO);
 
 #if defined(LDPC_PROF) && LDPC_PROF == 3
     if (blockIdx.x == 0) g_prof_dev = ldpc_params()->A.prof;      // (threads 0 and 384 of workgroup 0 are the only readers)
@@ -794,12 +770,6 @@ __global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(LD
                 if (LDPC_SPLIT_SKIP && ((LDPC_SPLIT_SKIP >> (L.kind_nw & 0xffu)) & 1)) {      // (timing / counter experiments: the layers of these kinds do nothing)
 #pragma unroll
                     for (int w = 0; w < REC; ++w) ro[w] = RS.rw;
-#ifdef LDPC_SPLIT_NOPREV_RT
-                } else if ((L.kind_nw & 0xffu) == 0 || (L.kind_nw & 0xffu) == 7) {
-                    int M0, M1, SXs;
-                    row_input<MAXDEG, 0, 2>(RS, 0u, L.aux, tt, M0, M1, SXs, (L.kind_nw >> 20) & 1u);
-                    row_output<MAXDEG, 0>(RS, M0, M1, SXs, 0u, ro);
-#endif
                 } else if ((L.kind_nw & 0xffu) == 0) {
                     int M0, M1, SXs;
                     row_input<MAXDEG, 0>(RS, 0u, 0u, tt, M0, M1, SXs);

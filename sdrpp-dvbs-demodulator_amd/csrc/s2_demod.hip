@@ -4,7 +4,7 @@
 // all streams in one launch and pools their frames for the FEC kernels.
 //
 // Call anatomy (process / process_batch), all on one HIP stream:
-//   1 front end (AGC+NCO, lane per stream; Gardner, 8 lanes per stream)    agc_pc_kernel, s2_gardner_kernel
+//   1 front end (AGC+NCO, lane per stream; Gardner, 8 lanes per stream)    agc_pc_kernel, s2_gardner2_kernel / s2_gardner_cand_kernel
 //   2 RRC on the kept samples + /2, append to the symbol FIFO               s2_rrc_decim_kernel
 //   3 PL sync: every stream's complete windows, correlation + the 2-state
 //     realign machine of S2PLSyncBlock (dvbs2_pl_sync.cpp:102-165)          s2_ccm_walk_kernel       -> D2H frame tables (sync 1)
@@ -309,7 +309,7 @@ int demod_configure(dvbs2gpu_demod* d) {
         last_error() = "loop gains must be finite"; return DVBS2GPU_ERR_ARG;
     }
     S2LoopCoefs& co = d->co;
-    co.g_prio_duty = 0; co.g_lane_form = 0; co.post_prio = 0;       // (scheduling hints: set per call by the pipelined mode's balancer)
+    co.g_prio_duty = 0; co.post_prio = 0;       // (scheduling hints: set per call by the pipelined mode's balancer)
     co.g_form = 0; co.g_cand_skew = 0;            // (context options, set per call)
     co.agc_rate = c.agc_rate;
     co.g_alpha = c.clock_mu_gain; co.g_beta = c.clock_omega_gain;
@@ -363,39 +363,9 @@ struct PendingFec {
     uint8_t** d_dst = nullptr;          // [nf] device table of the frames' destinations, filled by the delivery
     size_t n_results = 0;               // int32 words in d_trials (ACM/VCM)
     hipEvent_t done = nullptr;          // recorded on the FEC stream behind the job
-    hipEvent_t t0 = nullptr;            // ... and in front of it (big CCM jobs: the job's duration, for the partition rule)
-    bool on_part = false;               // the job ran on the partition stream
+    hipEvent_t t0 = nullptr;            // ... and in front of it (big CCM jobs: the job's duration, for the priority balancer)
     std::vector<hipEvent_t> done_more;  // (a job whose parts ran on several streams: one event per stream)
 };
-
-
-// FEC jobs of one context share its FEC workspaces: whichever FEC stream a job goes onto, it starts behind the job before it
-#ifndef FEC_PART_CUS_N
-#define FEC_PART_CUS_N 128
-#endif
-constexpr int FEC_PART_CUS = FEC_PART_CUS_N;
-static int fec_stream_enter(dvbs2gpu_ctx* ctx, hipStream_t sf) {
-    if (ctx->fec_last_done && ctx->fec_last_stream && ctx->fec_last_stream != sf) HIP_TRY(hipStreamWaitEvent(sf, ctx->fec_last_done, 0));
-    return 0;
-}
-static void fec_stream_leave(dvbs2gpu_ctx* ctx, hipStream_t sf, hipEvent_t done) { ctx->fec_last_done = done; ctx->fec_last_stream = sf; }
-// (hipExtStreamCreateWithCUMask has no flags argument: the stream it makes is a default-flag, BLOCKING stream -- work a host enqueues on the legacy null stream serialises with
-// the decoder jobs on it; INTEGRATION.md tells hosts to use explicit non-blocking streams beside the engine.  A driver that refuses the mask must not take the call down -- the
-// front end has advanced the streams' state by now: the rule is switched off for the context and the job goes onto the ordinary FEC stream.)
-static bool fec_part_stream(dvbs2gpu_ctx* ctx, hipStream_t* out) {
-    if (!ctx->fec_part_stream) {
-        uint32_t mask[8] = {};
-        for (int i = 0; i < FEC_PART_CUS && i < ctx->num_cus; ++i) mask[i >> 5] |= 1u << (i & 31);
-        if (hipExtStreamCreateWithCUMask(&ctx->fec_part_stream, 8, mask) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->fec_part_stream = nullptr;
-            ctx->fec_part = 0; ctx->fec_part_on = false; ctx->fec_part_trend = 0;
-            return false;
-        }
-    }
-    *out = ctx->fec_part_stream;
-    return true;
-}
 
 // the streams of the whole batch a pipelined call works on: a job is collected into the buffers of whichever of ITS streams are part of this batch
 // -- in any order, in any configuration group; frames of a stream that has left are dropped (collect them with a zero-count call before it leaves)
@@ -498,9 +468,6 @@ static int deliver_job(dvbs2gpu_ctx* ctx, PendingFec* job, hipStream_t st, Works
 #endif
 static int post_prio_wanted(const dvbs2gpu_ctx* ctx) { return ctx->pipeline_fec && ctx->g_prio_duty >= S2_POST_PRIO_MIN_DUTY ? 1 : 0; }
 static hipError_t create_stream(dvbs2gpu_ctx*, hipStream_t* out, int) { return hipStreamCreateWithFlags(out, hipStreamNonBlocking); }
-#ifndef S2_INPUT_EVENT
-#define S2_INPUT_EVENT 1      // (A/B switch, timing only: 0 = the throughput mode does not wait for the host's null-stream work -- the race of round 6)
-#endif
 #ifndef S2_MIN_SLICE_SAMPLES
 #define S2_MIN_SLICE_SAMPLES 1024     // a time slice holds at least this many samples per stream (a call of a few thousand samples is not cut into 32 slices of 133 launches)
 #endif
@@ -520,7 +487,6 @@ static hipError_t frontend_sliced(dvbs2gpu_ctx* ctx, const S2StreamWork* d_work,
     S2LoopCoefs cc = co;
     cc.g_prio_duty = ctx->pipeline_fec ? ctx->g_prio_duty : 0;
     cc.post_prio = post_prio_wanted(ctx);
-    cc.g_lane_form = 0;
     cc.g_form = ctx->gardner_form; cc.g_cand_skew = ctx->gardner_cand_skew;
     dvbs2gpu_ctx::FeAux* fa = nullptr;
     if (nsub > 1) {
@@ -847,11 +813,6 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
             job->done = ctx->ev_fec[slot][par];
         } else {
             std::lock_guard<std::mutex> fl(ctx->fec_mtx);
-            // (a single-configuration batch whose decoder has room to spare: onto the partition stream, ctx.h)
-            if (ctx->fec_part_on && !own_ws && !pre_nsym) {
-                job->on_part = fec_part_stream(ctx, &sf);
-            }
-            if ((rc = fec_stream_enter(ctx, sf))) return rc;
             HIP_TRY(hipStreamWaitEvent(sf, ev_llr, 0));
             if (!ctx->ev_fec_t0[slot][par]) HIP_TRY(hipEventCreate(&ctx->ev_fec_t0[slot][par]));
             HIP_TRY(hipEventRecord(ctx->ev_fec_t0[slot][par], sf));
@@ -861,7 +822,6 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
             HIP_TRY(hipEventRecord(ctx->ev_fec[slot][par], sf));
             job->done = ctx->ev_fec[slot][par];
             job->t0 = ctx->ev_fec_t0[slot][par];
-            fec_stream_leave(ctx, sf, job->done);
         }
         ctx->fec_parity[slot] ^= 1;
         hm.mark("fec_enqueued");
@@ -919,18 +879,7 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
                 ctx->g_prio_trend = held ? 0 : verdict;
                 if (ctx->g_prio_last_down > 0) --ctx->g_prio_last_down;
             }
-            // the partition rule (ctx.h)
-            if (ctx->fec_part < 0 && timed) {
-                if (sig_changed) { ctx->fec_part_on = false; ctx->fec_part_trend = 0; }
-                const double scale = prev->on_part ? 1.0 : 256.0 / FEC_PART_CUS;
-                const bool fits = job_was_done && job_ms * scale * 1.15 < period_ms;
-                const int want = fits ? +1 : -1;
-                if ((want > 0) != ctx->fec_part_on) {
-                    if (ctx->fec_part_trend == want) { ctx->fec_part_on = want > 0; ctx->fec_part_trend = 0; }
-                    else ctx->fec_part_trend = want;
-                } else ctx->fec_part_trend = 0;
-            }
-            if (hm.on) { char b[128]; snprintf(b, sizeof(b), " wait=%.2f call=%.1f duty=%d job=%.1f period=%.1f part=%d", wait_ms, call_ms, ctx->g_prio_duty, job_ms, period_ms, (int)ctx->fec_part_on); hm.line += b; }
+            if (hm.on) { char b[128]; snprintf(b, sizeof(b), " wait=%.2f call=%.1f duty=%d job=%.1f period=%.1f", wait_ms, call_ms, ctx->g_prio_duty, job_ms, period_ms); hm.line += b; }
         }
     }
     if (started) {
@@ -1146,13 +1095,11 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
             HIP_TRY(hipEventRecord(ctx->ev_llr, st));
             {
                 std::lock_guard<std::mutex> fl(ctx->fec_mtx);
-                if ((rc = fec_stream_enter(ctx, sf))) return rc;
                 HIP_TRY(hipStreamWaitEvent(sf, ctx->ev_llr, 0));
                 for (const Run& r : runs)
                     if ((rc = fec_run(ctx, r.f, r.llr, r.cnt, mt, force, r.bb, r.tr, r.tr + r.cnt, sf))) return rc;
                 if (!ctx->ev_fec[slot][par]) HIP_TRY(hipEventCreate(&ctx->ev_fec[slot][par]));
                 HIP_TRY(hipEventRecord(ctx->ev_fec[slot][par], sf));
-                fec_stream_leave(ctx, sf, ctx->ev_fec[slot][par]);
             }
             ctx->fec_parity[slot] ^= 1;
             HIP_TRY(hipMemcpyAsync(hstats.data(), d_stats, sizeof(S2FrameStats) * nf, hipMemcpyDeviceToHost, st));
@@ -1596,10 +1543,8 @@ static int release_streams(dvbs2gpu_ctx* ctx) {
         ctx->fe_aux.clear();
     }
     for (hipStream_t& sg : ctx->grp_stream) if (sg) { (void)hipStreamDestroy(sg); sg = nullptr; }
-    if (ctx->fec_part_stream) { (void)hipStreamDestroy(ctx->fec_part_stream); ctx->fec_part_stream = nullptr; }
     if (ctx->fec_stream) { (void)hipStreamDestroy(ctx->fec_stream); ctx->fec_stream = nullptr; }
     if (ctx->fe_stream) { (void)hipStreamDestroy(ctx->fe_stream); ctx->fe_stream = nullptr; }
-    ctx->fec_last_done = nullptr; ctx->fec_last_stream = nullptr;
     return 0;
 }
 int dvbs2gpu_set_pipelined(dvbs2gpu_ctx* ctx, int on) {
@@ -1615,7 +1560,6 @@ int dvbs2gpu_set_pipelined(dvbs2gpu_ctx* ctx, int on) {
     if (!on && ctx->fec_stream) {
         // frames of the last pipelined call that nobody collected are dropped (collect them with a zero-count call first)
         HIP_TRY(hipStreamSynchronize(ctx->fec_stream));
-        if (ctx->fec_part_stream) HIP_TRY(hipStreamSynchronize(ctx->fec_part_stream));
         for (hipStream_t sg : ctx->grp_stream) if (sg) HIP_TRY(hipStreamSynchronize(sg));      // (small jobs of mixed batches run on their group's stream)
         for (auto& pj : ctx->pending_fec) { delete (PendingFec*)pj; pj = nullptr; }
     }
@@ -1651,7 +1595,7 @@ int dvbs2gpu_demod_process_batch(dvbs2gpu_demod* const* demods, int n, const flo
     for (int i = 0; i < n; ++i) any_vcm = any_vcm || demods[i]->cfg.acm_vcm != 0;
     if (pipe && (int)groups.size() > dvbs2gpu_ctx::MAX_PIPE_GROUPS) { last_error() = "pipelined mode handles at most 16 configuration groups per batch"; return DVBS2GPU_ERR_ARG; }
     hipStream_t st = pipe ? ctx->fe_stream : nullptr;
-    if (pipe && S2_INPUT_EVENT) {
+    if (pipe) {
         // The synchronous mode runs on the legacy null stream: whatever the host has put there before the call -- the kernels or copies that FILL its input buffers -- lies in
         // front of the demodulator by itself.  The throughput mode's own stream is non-blocking: without this it READ INPUT THAT WAS STILL BEING WRITTEN whenever the host's
         // producer had not finished (round 6, tools/stress_pipelined.py on fresh streams: a frame of a busy call came out with LDPC trials -1 and two BCH corrections where

@@ -104,12 +104,12 @@ __device__ __forceinline__ cf32 phasor_hw(float x) { return phasor(x); }
 //   agc_pc_kernel      LANE = STREAM.  The AGC gain and NCO phase recurrences depend only on the input, are strictly serial in
 //                      time and ~40 instructions per sample: one lane runs one stream, a wave 64 streams, and the per-sample
 //                      (gain, phase) pairs go to the stream's scratch area; a second wave of the workgroup moves the tiles.
-//   s2_gardner_kernel  EIGHT LANES PER STREAM (polyphase arm x re/im), 8 streams per wave.  Tiles of 64 samples per stream are
-//                      staged through LDS by all 64 lanes -- y = x*gain, z = y*phasor(-phase), the parallel part of
-//                      FastAGC/FreqShift; the loads of the next tile stay in flight during the loop -- then every lane group
-//                      runs its stream's Gardner loop: one 8-tap polyphase dot product per lane in the reference's
-//                      accumulation order, DPP row shifts to bring the three arms together, a quad swap to add the re/im
-//                      halves of the timing error, two DPP broadcasts to hand it to the whole group.
+//   s2_gardner2_kernel EIGHT LANES PER STREAM (polyphase arm x re/im), 8 streams per resolver wave; a producer wave beside it
+//                      stages the samples -- y = x*gain, z = y*phasor(-phase), the parallel part of FastAGC/FreqShift -- and
+//                      computes the output values.  The resolver runs the streams' Gardner loops: one 8-tap polyphase dot
+//                      product per lane in the reference's accumulation order, DPP row shifts to bring the three arms together,
+//                      a quad swap to add the re/im halves of the timing error, two DPP broadcasts to hand it to the whole group.
+//   s2_gardner_cand_kernel  small banks: candidate tables (see there).
 // Many streams = many lanes: the batch fills the GPU, and nothing here is redundant across lanes (the first version ran the
 // serial chains once per wave, 64 lanes wide, and took 47 ms for 4096 x 43380 samples; this one ~4x less).
 // Wave priorities of the serial front-end kernels while the LDPC decoder of the previous call shares the SIMDs (pipelined mode; the
@@ -123,9 +123,6 @@ __device__ __forceinline__ cf32 phasor_hw(float x) { return phasor(x); }
 #ifndef G_PRIO
 #define G_PRIO 1      // (round 6, with every front-end kernel above the decoder's parallel phases: the front end of the headline step is through in 129 ms instead of 256 and the
                       //  step is the decoder again: 283.9 -> 274.2 ms; at 0 the timing recovery shared the decoder's level for (8 - share) of every 8 tiles)
-#endif
-#ifndef G_PRIO_DUTY
-#define G_PRIO_DUTY 0
 #endif
 #ifndef G_PRIO_HI
 #define G_PRIO_HI (G_PRIO + 1)   // the timing recovery's priority for `share` of every 8 tiles ...
@@ -151,7 +148,6 @@ __device__ __forceinline__ cf32 phasor_hw(float x) { return phasor(x); }
 #endif
 constexpr int G_TILE = 64;     // samples per stream per staging tile
 constexpr int G_SPW = 8;       // streams per wave (8 lanes each)
-constexpr int G_PITCH = G_TILE + 9;   // 7 history + tile, odd pitch spreads the rows over the LDS banks
 
 __device__ __forceinline__ size_t fe_scratch_offset(int n) { return (size_t)n + n / 16 + 128; }
 
@@ -306,138 +302,16 @@ __global__ __launch_bounds__(128) void agc_pc_kernel(const typename TR::Work* __
 }
 
 #define DPP_F(v, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (float)(v)), (ctrl), 0xf, 0xf, false))
-template <typename T>
-__device__ __forceinline__ T* readlane_ptr(T* p, int srclane) {
-    const unsigned long long v = (unsigned long long)p;
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, srclane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), srclane);
-    return (T*)(((unsigned long long)hi << 32) | lo);
-}
 
-__global__ __launch_bounds__(64) void s2_gardner_kernel(const S2StreamWork* __restrict__ work, int nstreams, S2LoopCoefs co,
-                                                        const float* __restrict__ bank_g, int sub, int nsub) {
-    __shared__ __attribute__((aligned(16))) float bank[GARDNER_PHASES * GARDNER_TAPS];
-    __shared__ float win[G_SPW * 2 * G_PITCH];          // [stream][re/im][7 history + tile]
-    const int lane = threadIdx.x, g = lane >> 3, r = lane & 7, arm = r >> 1, c = r & 1;   // arm 0/1/2 = phase-1 / phase / phase+1, 3 = spare
-    const int s0 = blockIdx.x * G_SPW, s = s0 + g;
-    const bool act = s < nstreams;
-    for (int i = lane; i < GARDNER_PHASES * GARDNER_TAPS; i += 64) bank[i] = bank_g[i];
-    S2StreamWork w = work[act ? s : 0];
-    int lo, hi;
-    fe_sub_range(act ? w.count : 0, sub, nsub, lo, hi);
-    const int n = hi - lo;
-    S2StreamState* st = w.st;
-    PclDev pcl{co.g_alpha, co.g_beta, st->g_phase, st->g_freq, co.g_min_freq, co.g_max_freq};
-    int offset = st->g_offset, spsctr = st->g_spsctr, outCount = sub ? st->n_fe_out : 0;   // (later slices append to the call's output)
-    float* row = &win[(g * 2 + c) * G_PITCH];           // aliases the staging writes below: no __restrict__
-    auto outc = as_global(reinterpret_cast<float*>(w.fe_out) + c);
-    const cf32* gpp = w.fe_out + fe_scratch_offset(w.count) + lo;
-    w.in += lo;
-    if (arm == 0)
-        for (int k = 0; k < GARDNER_TAPS - 1; ++k) row[k] = c ? st->g_hist[k].im : st->g_hist[k].re;
-    int nmax = n;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nmax = max(nmax, __shfl_xor(nmax, o));
-    // staging registers: sample `lane` of the next tile of each of the 8 streams (loads stay in flight during the Gardner loop)
-    cf32 px[G_SPW], pg[G_SPW];
-    auto issue = [&](int base) {
-#pragma unroll
-        for (int jj = 0; jj < G_SPW; ++jj) {
-            const cf32* inj = readlane_ptr(w.in, jj * 8);
-            const cf32* gpj = readlane_ptr(gpp, jj * 8);
-            const int cj = __builtin_amdgcn_readlane(n, jj * 8);
-            if (base + lane < cj) { px[jj] = ldg(inj + base + lane); pg[jj] = ldg(gpj + base + lane); }
-        }
-    };
-    auto commit = [&](int base) {
-#pragma unroll
-        for (int jj = 0; jj < G_SPW; ++jj) {
-            const int cj = __builtin_amdgcn_readlane(n, jj * 8);
-            if (base + lane < cj && lane < G_TILE) {
-                const cf32 z = cmul(cscale(px[jj], pg[jj].re), phasor_fast(-pg[jj].im));   // FastAGC scaling, FreqShift rotation
-                win[(jj * 2) * G_PITCH + GARDNER_TAPS - 1 + lane] = z.re;
-                win[(jj * 2 + 1) * G_PITCH + GARDNER_TAPS - 1 + lane] = z.im;
-            }
-        }
-    };
-    issue(0);
-    __syncthreads();
-    __builtin_amdgcn_s_setprio(G_PRIO);       // latency-critical serial loop (see agc_pc_kernel)
-    for (int base = 0; base < nmax; base += G_TILE) {
-        // co.g_prio_duty (+ the build's G_PRIO_DUTY) of every 8 tiles run one priority level up: the balance point between "this kernel yields to
-        // the decoder" (the front end becomes the critical path) and "it does not" (the decoder does) lies between two priority levels, and
-        // where it lies depends on the MODCOD -- the host moves it from call to call (s2_demod.hip)
-        if ((((unsigned)base / G_TILE) & 7u) < (unsigned)(co.g_prio_duty + G_PRIO_DUTY)) __builtin_amdgcn_s_setprio(G_PRIO_HI); else __builtin_amdgcn_s_setprio(G_PRIO_LO);
-        commit(base);
-        __syncthreads();
-        issue(base + G_TILE);
-        // ---- Gardner (common/dsp/demod/gardner.cpp:89-150): outputs whose 8-sample window starts inside this tile
-        const int m = max(0, min(G_TILE, n - base));
-        // (the trip count is bounded: a poisoned loop state -- NaN input -- must not hang the GPU)
-        for (int guard = 0; guard < 4 * G_TILE && __any(offset < base + m && offset >= base); ++guard) {
-            if (offset < base + m && offset >= base) {
-                int phase = (int)floorf(pcl.phase * 128.0f);
-                phase = phase < 0 ? 0 : (phase > 127 ? 127 : phase);
-                int my = phase;
-                if (arm == 0) my = phase > 0 ? phase - 1 : 0;
-                if (arm == 2) my = phase < 127 ? phase + 1 : 127;
-                const float* xw = row + (offset - base);
-                const float* t = &bank[my * 8];
-                float acc = 0.f;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) acc += xw[k] * t[k];
-                // arm-1 lanes (r = 2: re, 3: im) collect the neighbours' arms: row_shr:2 = lane-2 (phase-1), row_shl:2 = lane+2 (phase+1)
-                const float xm = DPP_F(acc, 0x112), xp = DPP_F(acc, 0x102), xo = acc;
-                if (arm == 1) outc[2 * outCount] = xo;
-                ++outCount;
-                // straight-line on purpose (streams of one wave differ in spsctr): the error of the off-symbol outputs is masked to 0
-                const float d = fsel(phase == 0, xp - xo, fsel(phase == 127, xo - xm, (xp - xm) * 0.5f));
-                const float e = (xo > 0 ? 1.0f : -1.0f) * d;                 // valid in lanes r = 2 (re half), 3 (im half)
-                const float eo = DPP_F(e, 0xB1);                             // quad_perm [1,0,3,2]: the other half
-                const float er = -(e + eo);                                  // -(re part + im part)
-                const float eq = DPP_F(er, 0xAA);                            // quad_perm [2,2,2,2]: r = 0..3 <- r = 2
-                const float eh = DPP_F(eq, 0x114);                           // row_shr:4: r = 4..7 <- r = 0..3
-                float error = spsctr == 0 ? (r < 4 ? eq : eh) : 0.f;
-                spsctr = spsctr >= 1 ? 0 : spsctr + 1;
-                error = clamp_med3(error, -1.0f, 1.0f);
-                pcl.advance(error);
-                const float delta = floorf(pcl.phase);
-                offset = (int)((float)offset + delta);
-                pcl.phase -= delta;
-            }
-        }
-        __syncthreads();
-        // ---- slide the 7-sample history (arm-0 lanes own the rows)
-        if (arm == 0) {
-            float h[GARDNER_TAPS - 1];
-#pragma unroll
-            for (int k = 0; k < GARDNER_TAPS - 1; ++k) h[k] = row[m + k];
-#pragma unroll
-            for (int k = 0; k < GARDNER_TAPS - 1; ++k) row[k] = h[k];
-        }
-        __syncthreads();
-    }
-    if (act && arm == 0) {
-        for (int k = 0; k < GARDNER_TAPS - 1; ++k) {
-            if (c) st->g_hist[k].im = row[k]; else st->g_hist[k].re = row[k];
-        }
-        if (c == 0) {
-            st->g_phase = pcl.phase; st->g_freq = pcl.freq; st->g_offset = offset - n; st->g_spsctr = spsctr;
-            st->n_fe_out = outCount;
-            st->n_fe_slice[sub & (S2_FE_MAX_SLICES - 1)] = outCount;
-        }
-    }
-}
-
-// ---- timing recovery, second form: the serial chain holds only what the recurrence needs ------------------------------------
+// ---- timing recovery, form 2: the serial chain holds only what the recurrence needs ------------------------------------
 // Of the reference loop's two outputs per symbol only the on-symbol one feeds the loop (gardner.cpp:100-131: the error of the
 // other is 0, so PCL::advance(0) moves the phase by the loop frequency alone), and an output VALUE never feeds anything: the chain is
 // "interpolate three arms at the on-symbol instant -> error -> advance; advance once more".  So the RESOLVER wave (8 lanes per stream,
-// 8 streams, as above) walks symbol by symbol -- on-symbol output, then its follower without any interpolation -- and leaves one word
+// 8 streams per wave) walks symbol by symbol -- on-symbol output, then its follower without any interpolation -- and leaves one word
 // (window slot, polyphase arm) per output in an LDS list; a PRODUCER wave of the same workgroup computes every output value from that
 // list one period later (the same 8-tap dot product in the reference's accumulation order, lane = output: coalesced stores instead of
 // a predicated store inside the chain), and stages the next samples (FastAGC scaling + FreqShift rotation).  Per symbol the chain is
-// ~125 instructions of one wave instead of ~230.  Streams of a wave start a period aligned on an on-symbol output (one single step
+// ~125 instructions of one wave instead of the ~230 of a loop that computes every output itself.  Streams of a wave start a period aligned on an on-symbol output (one single step
 // at the start of a slice where the state says otherwise); the last three sample positions of a slice go through single steps, so a
 // slice ends in exactly the state the reference's loop has after the same samples.
 // Samples live in a ring of 4 periods per stream and component (slot = buffer index mod ring; the first 8 slots are mirrored behind the
@@ -451,20 +325,11 @@ __global__ __launch_bounds__(64) void s2_gardner_kernel(const S2StreamWork* __re
 #ifndef G2_TILE_N
 #define G2_TILE_N 16
 #endif
-#ifndef G2_EXTRA_VALU
-#define G2_EXTRA_VALU 0     // sensitivity experiment: dead vector instructions per producer wave and period (how much does the decoder beside it pay per front-end instruction?)
-#endif
-#ifndef G2_FORCE_VGPRS
-#define G2_FORCE_VGPRS 0
-#endif
 #ifndef G2_PROD_PRIO
 #define G2_PROD_PRIO 1    // wave priority of the producer waves (A/B switch).  Round 6: at 0 -- the decoder's own level, one of seven waves of its SIMD -- the producer, not the resolver, paced a period beside the
                           // decoder; headline (driver's command, same call) 258.6 / 259.7 ms per step at 0, 255.1 / 252.6 at 1, 254.2 / 252.8 at 2; plugin's mode 126.9 / 124.7 / 123.9
 #endif
-#ifndef G2_PAIRS_N
-#define G2_PAIRS_N 2      // resolver + producer pairs per workgroup (A/B switch: 1 = round 5's 128-thread workgroups)
-#endif
-constexpr int G2_PAIRS = G2_PAIRS_N;
+constexpr int G2_PAIRS = 2;                   // resolver + producer pairs per workgroup
 constexpr int G2_TILE = G2_TILE_N;            // samples per stream and period
 constexpr int G2_RING = 4 * G2_TILE;
 constexpr int G2_PITCH = G2_RING + 8 + 1;     // ring + mirror of its first 8 slots; odd pitch
@@ -582,14 +447,6 @@ __global__ __launch_bounds__(64 * 2 * G2_PAIRS) void s2_gardner2_kernel(const S2
             if (!(G2_EXP & 2) && t + 1 < ntiles) commit(t + 1);
             if (t + 2 < ntiles) issue(t + 2);
             if (!(G2_EXP & 1) && t >= 1) produce(t - 1);
-#if G2_EXTRA_VALU
-            {   // (sensitivity experiment: dead vector instructions per period)
-                float dead = (float)t;
-#pragma unroll 8
-                for (int i = 0; i < G2_EXTRA_VALU; ++i) asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(dead));
-                asm volatile("" :: "v"(dead));
-            }
-#endif
             lds_only_barrier();
         }
         if (!(G2_EXP & 1) && ntiles > 0) produce(ntiles - 1);
@@ -640,13 +497,13 @@ __global__ __launch_bounds__(64 * 2 * G2_PAIRS) void s2_gardner2_kernel(const S2
         offset = (int)((float)offset + delta);
         pcl.phase -= delta;
     };
-#if G2_FORCE_VGPRS
-    asm volatile("" ::: "v123");             // (A/B: the register count the kernel had while its written-out loop named v100..v123)
-#endif
     lds_only_barrier();                       // period 0 is staged
     __builtin_amdgcn_s_setprio(G_PRIO);       // latency-critical serial loop (see agc_pc_kernel)
     for (int t = 0; t < ntiles; ++t) {
-        if ((((unsigned)t * G2_TILE / G_TILE) & 7u) < (unsigned)(co.g_prio_duty + G_PRIO_DUTY)) __builtin_amdgcn_s_setprio(G_PRIO_HI); else __builtin_amdgcn_s_setprio(G_PRIO_LO);
+        // co.g_prio_duty of every 8 tiles of G_TILE samples run one priority level up: the balance point between "this kernel yields to the decoder" (the front end
+        // becomes the critical path) and "it does not" (the decoder does) lies between two priority levels, and where it lies depends on the MODCOD -- the host moves
+        // it from call to call (s2_demod.hip)
+        if ((((unsigned)t * G2_TILE / G_TILE) & 7u) < (unsigned)co.g_prio_duty) __builtin_amdgcn_s_setprio(G_PRIO_HI); else __builtin_amdgcn_s_setprio(G_PRIO_LO);
         const int base = t * G2_TILE;
         const int lim = min(base + G2_TILE, n);            // outputs with offset < lim have their window staged
         lp = &list[t & 1][g][0];
@@ -815,8 +672,8 @@ __global__ __launch_bounds__(64 * 2 * G2_PAIRS) void s2_gardner2_kernel(const S2
 // (a third form -- lane = stream, 16 or 64 streams per workgroup: 102 instead of 185 ms of timing recovery per headline step, but the co-resident decoder 342 -> 366 ms and
 // no pipelined configuration where it beat the resolver + producer form -- was built in round 4 and deleted in round 5: profiles/r04_gardner_forms_ab.txt)
 
-// ---- timing recovery, fourth form: CANDIDATE TABLES for small banks -------------------------------------------------------
-// A small bank is bound by the length of ONE stream's chain, and ~100 of the ~135 instructions per symbol of the forms above are the
+// ---- timing recovery, form 4: CANDIDATE TABLES for small banks -------------------------------------------------------
+// A small bank is bound by the length of ONE stream's chain, and ~100 of the ~135 instructions per symbol of form 2 are the
 // four 8-tap dot products.  Which interpolants the loop will ask for is almost known in advance: an on-symbol output sits at a sample
 // offset of the current period, and the polyphase arm moves by alpha * error + (freq - 1) ~ 0.05 arms per symbol.  So two helper waves
 // compute, for the period AFTER the one being resolved, the interpolant of EVERY sample offset of that period with the 8 arms around the
@@ -1496,17 +1353,13 @@ __device__ __forceinline__ cf32 pll_payload_tile(const cf32 sym, const bool mine
 
 // SPEC: with the loops ahead of the PL sync (below) compiled in -- small banks only: the plain instantiation has to stay within 128 registers
 // (it shares its SIMDs with three decoder waves in the pipelined mode), and the extra state costs it 14
-#ifndef FL_WPB_MAX_N
-#define FL_WPB_MAX_N 1      // waves per workgroup of a big bank's frame loops (A/B switch).  Round 6, same call: 2 -> decoder in the step 247.8 -> 245.8 ms but frame loops 108-115 -> 123-132 and the step 264.4 -> 271.7: a two-wave workgroup needs two free 128-register places on one compute unit at once, and beside the decoder every SIMD has ONE
-#endif
-constexpr int FL_WPB_MAX = FL_WPB_MAX_N;
-// a bank of at least one single-wave workgroup per compute unit (256) goes out in workgroups of FL_WPB_MAX waves; smaller ones keep a workgroup -- a compute unit -- per wave
-static inline int frame_loops_wpb(int nstreams, int spw) { const int nb = (nstreams + spw - 1) / spw; return nb >= 256 ? FL_WPB_MAX : 1; }
-static inline int frame_loops_grid(int nstreams, int spw) { const int nb = (nstreams + spw - 1) / spw, w = frame_loops_wpb(nstreams, spw); return (nb + w - 1) / w; }
+// one wave per workgroup, whatever the bank (round 6, same call: a big bank in two-wave workgroups -> decoder in the step 247.8 -> 245.8 ms but frame loops 108-115 -> 123-132
+// and the step 264.4 -> 271.7: a two-wave workgroup needs two free 128-register places on one compute unit at once, and beside the decoder every SIMD has ONE)
+static inline int frame_loops_grid(int nstreams, int spw) { return (nstreams + spw - 1) / spw; }
 // what __syncthreads() is in a single-wave workgroup (the compiler drops its s_barrier there): a wave's LDS writes before its LDS reads -- the waves of these workgroups share nothing
 #define FL_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
 template <bool SPEC>
-__global__ __launch_bounds__(64 * FL_WPB_MAX) __attribute__((amdgpu_waves_per_eu(4, 4))) void s2_frame_loops_kernel(const S2StreamWork* __restrict__ work, int nstreams,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void s2_frame_loops_kernel(const S2StreamWork* __restrict__ work, int nstreams,
                                                             const S2FrameRef* __restrict__ frames, const int* __restrict__ first,
                                                             S2LoopCoefs co, S2PlTablesDev T, S2ConstelDev C, int pls_code, int slots,
                                                             int pilots, int pilot_blocks, int plframe, cf32* __restrict__ pllout,
@@ -1520,22 +1373,17 @@ __global__ __launch_bounds__(64 * FL_WPB_MAX) __attribute__((amdgpu_waves_per_eu
     // mixed batch: this workgroup's streams share the configuration of its first one (s2_demod.hip sees to that); `plframe` as passed is then the
     // stride of the PLL-output slots (the longest PLFRAME of the batch)
     const int slot_stride = plframe;
-    // WAVES of a workgroup are independent of one another (a big bank is launched with FL_WPB_MAX of them per workgroup for the sake of their PLACEMENT: the hardware spreads the
-    // waves of one workgroup over the SIMDs of its compute unit, single-wave workgroups land where they land -- tools/ubench/placement.hip); wave `wv` of workgroup b is what
-    // the single-wave workgroup b * waves + wv was: its own streams, its own tiles, no workgroup barrier anywhere (FL_SYNC orders a wave's own LDS traffic)
-    const int wv = threadIdx.x >> 6, vb = (int)blockIdx.x * ((int)blockDim.x >> 6) + wv;
+    // no workgroup barrier anywhere (FL_SYNC orders the wave's own LDS traffic)
+    const int vb = blockIdx.x;
     if (vb * spw >= nstreams) return;
     if (cfgs) {
         const S2StreamCfgDev* __restrict__ q = cfgs + min(vb * spw, nstreams - 1);
         C = q->con; pls_code = q->pls_code; slots = q->slots; pilots = q->pilots; pilot_blocks = q->pilot_blocks; plframe = q->plframe;
     }
-    __shared__ cf32 tiles_all[FL_WPB_MAX][FL_SPW][2 * FL_TILE]; // per wave and stream: [input tile | output tile]
-    __shared__ uint8_t rnt_all[FL_WPB_MAX][FL_TILE];
-    __shared__ cf32 s_pts_all[FL_WPB_MAX][32];                 // constellation points for the 32APSK phase-error search (the other constellations use the LUT)
-    cf32 (*const tiles)[2 * FL_TILE] = tiles_all[wv];
-    uint8_t* const rnt = rnt_all[wv];
-    cf32* const s_pts = s_pts_all[wv];
-    const int lane = threadIdx.x & 63, g = lane / FL_LPS, gl = lane % FL_LPS;
+    __shared__ cf32 tiles[FL_SPW][2 * FL_TILE];        // per stream: [input tile | output tile]
+    __shared__ uint8_t rnt[FL_TILE];
+    __shared__ cf32 s_pts[32];                          // constellation points for the 32APSK phase-error search (the other constellations use the LUT)
+    const int lane = threadIdx.x, g = lane / FL_LPS, gl = lane % FL_LPS;
     if (C.bits == 5 && lane < 32) s_pts[lane] = lane < C.states ? C.pts_g[lane] : cf32{0.f, 0.f};
     cf32* const tl = &tiles[g][0];                      // input tile (also a 36-symbol pilot block for the FED; with the output tile: the 90 header symbols)
     cf32* const ot = &tiles[g][FL_TILE];                // output tile
@@ -3401,7 +3249,7 @@ static hipError_t post_stages_launch(const S2StreamWork* d_work, int nstreams, c
                                    (const int*)nullptr, coefs, p.tabs, p.con, p.pls_code, p.slots, p.pilots, p.pilot_blocks, p.raw, p.d_pllout, p.d_stats,
                                    (const S2VcmFound*)p.d_found, p.maxf, spw, p.cfgs);
             else
-            hipLaunchKernelGGL(s2_frame_loops_kernel<false>, dim3(frame_loops_grid(nstreams, spw)), dim3(64 * frame_loops_wpb(nstreams, spw)), 0, s, d_work, nstreams, (const S2FrameRef*)nullptr,
+            hipLaunchKernelGGL(s2_frame_loops_kernel<false>, dim3(frame_loops_grid(nstreams, spw)), dim3(64), 0, s, d_work, nstreams, (const S2FrameRef*)nullptr,
                                (const int*)nullptr, coefs, p.tabs, p.con, p.pls_code, p.slots, p.pilots, p.pilot_blocks, p.raw, p.d_pllout, p.d_stats,
                                (const S2VcmFound*)p.d_found, p.maxf, spw, p.cfgs);
             if (p.spans) p.spans->end(3, s);
@@ -3412,45 +3260,24 @@ static hipError_t post_stages_launch(const S2StreamWork* d_work, int nstreams, c
 hipError_t s2_post_stages_launch(const S2StreamWork* d_work, int nstreams, const S2LoopCoefs& coefs, const S2PostStages& p, int c, int nsub, hipStream_t s) {
     return post_stages_launch(d_work, nstreams, coefs, p, c, nsub, s);
 }
-// Three forms of the timing recovery, all bit-identical (tests/test_gpu_gardner_forms.py runs every one): 1 = one wave, 8 lanes per stream
-// (s2_gardner_kernel); 2 = resolver + producer waves, 8 lanes per stream (s2_gardner2_kernel); 4 = candidate tables (s2_gardner_cand_kernel: the
-// shortest chain per stream -- what a small bank needs: one stream 3.68 -> 2.5 ms per 21 690-sample slice against form 2; 64 streams x 1 frame
-// 18.6 -> 16.7 ms per call, 256 x 4 frames 50.3 -> 47.2).  (Form 3, lane = stream, is gone: see above.)  Who wins where (round 4, MI355X, ms per
-// step, front end | decoder in the step | step):
-//   4096 streams x 8 frames 8PSK 3/4 (decoder critical):  form 1  185 | 342 | 363     form 2  147 | 345 | 363
-//   4096 streams x 8 frames QPSK 1/2 (front end critical): form 1  283 | 337 | 465     form 2  297 | 356 | 410
-//   1024 streams x 4 frames 8PSK 3/4:                      form 1   71 |  48 |  76     form 2   60 |  49 |  65
-//    384 streams x 4 frames:                               form 1   65 |  19 |  67     form 2   52 |  18 |  54     form 4  51 | 19 | 53
-// Default: form 4 up to S2_GARDNER_CAND_MAX streams; form 2 above (rounds 4-5: form 1 for big banks beside a decoder that is the critical path -- see gardner_form()).
-// The context option gardner_form = 1 | 2 | 4 forces one.
-#ifndef S2_GARDNER_BANK_MIN
-#define S2_GARDNER_BANK_MIN 512
-#endif
-#ifndef S2_GARDNER_LANE_MIN
-#define S2_GARDNER_LANE_MIN 2048
-#endif
+// Two forms of the timing recovery, bit-identical (tests/test_gpu_gardner_forms.py runs both): 2 = resolver + producer waves, 8 lanes per stream
+// (s2_gardner2_kernel); 4 = candidate tables (s2_gardner_cand_kernel: the shortest chain per stream -- what a small bank needs: one stream
+// 3.68 -> 2.5 ms per 21 690-sample slice against form 2; 64 streams x 1 frame 18.6 -> 16.7 ms per call, 256 x 4 frames 50.3 -> 47.2).
+// MI355X, ms per step, front end | decoder in the step | step:
+//    384 streams x 4 frames:                               form 2  52 | 18 | 54     form 4  51 | 19 | 53
+// Default: form 4 up to S2_GARDNER_CAND_MAX streams; form 2 above.  The context option gardner_form = 2 | 4 forces one.
 #ifndef S2_GARDNER_CAND_MAX
 #define S2_GARDNER_CAND_MAX 256
 #endif
-static int gardner_form(int nstreams, int prio_duty, int lane_form, int forced) {
-    if (forced == 1 || forced == 2 || forced == 4) return forced;      // (context option gardner_form: the parity tests run every form)
-    if (nstreams <= S2_GARDNER_CAND_MAX) return 4;
-    if (nstreams < S2_GARDNER_BANK_MIN) return 2;
-    // a big bank beside the decoder of the previous call: the one-wave form disturbs the decoder least; once the balancer of the pipelined
-    // mode (s2_demod.hip) has found the FRONT END to be the critical path (it raises the timing loop's priority share), the shorter forms win
-    // (round 6: form 2's workgroups of four waves spread evenly over a compute unit's SIMDs and its waves take 60 registers -- it now disturbs the decoder less than the one-wave
-    //  form everywhere: mixed 64-entry batch, whose shared front-end pass has no balancer, 206 -> 195.5 ms per step; the headline's balancer ends at a share >= 2 anyway)
-    (void)lane_form; (void)prio_duty;
-    return 2;
+static int gardner_form(int nstreams, int forced) {
+    if (forced == 2 || forced == 4) return forced;      // (context option gardner_form: the parity tests run both forms)
+    return nstreams <= S2_GARDNER_CAND_MAX ? 4 : 2;
 }
 static void gardner_launch(const S2StreamWork* d_work, int nstreams, const S2LoopCoefs& coefs, const float* d_bank, hipStream_t st, int c, int nsub) {
-    switch (gardner_form(nstreams, coefs.g_prio_duty, coefs.g_lane_form, coefs.g_form)) {
-        case 4:
-            hipLaunchKernelGGL(s2_gardner_cand_kernel, dim3((nstreams + GC_CS - 1) / GC_CS), dim3(192), 0, st, d_work, nstreams, coefs, d_bank, c, nsub, coefs.g_cand_skew);
-            break;
-        case 2: hipLaunchKernelGGL(s2_gardner2_kernel, dim3((nstreams + G2_PAIRS * G_SPW - 1) / (G2_PAIRS * G_SPW)), dim3(64 * 2 * G2_PAIRS), 0, st, d_work, nstreams, coefs, d_bank, c, nsub); break;
-        default: hipLaunchKernelGGL(s2_gardner_kernel, dim3((nstreams + G_SPW - 1) / G_SPW), dim3(64), 0, st, d_work, nstreams, coefs, d_bank, c, nsub); break;
-    }
+    if (gardner_form(nstreams, coefs.g_form) == 4)
+        hipLaunchKernelGGL(s2_gardner_cand_kernel, dim3((nstreams + GC_CS - 1) / GC_CS), dim3(192), 0, st, d_work, nstreams, coefs, d_bank, c, nsub, coefs.g_cand_skew);
+    else
+        hipLaunchKernelGGL(s2_gardner2_kernel, dim3((nstreams + G2_PAIRS * G_SPW - 1) / (G2_PAIRS * G_SPW)), dim3(64 * 2 * G2_PAIRS), 0, st, d_work, nstreams, coefs, d_bank, c, nsub);
 }
 #define GARDNER_LAUNCH(c_, n_) gardner_launch(d_work, nstreams, coefs, d_bank, st, (c_), (n_))
 hipError_t s2_frontend_launch(const S2StreamWork* d_work, int nstreams, S2LoopCoefs coefs, const float* d_bank, hipStream_t st, hipStream_t aux,
@@ -3462,7 +3289,7 @@ hipError_t s2_frontend_launch(const S2StreamWork* d_work, int nstreams, S2LoopCo
     // post_stream: a stream of their own for the post stages (synchronous mode: the FEC stream's hardware queue is free) -- on `aux` the
     // frame loops queue behind the AGC slices, and for a few streams that queue is the longest (AGC 4 x 7 + loops 4 x 10 ms against 47 ms of
     // timing recovery per 4-frame call)
-    const dim3 ga((nstreams + 63) / 64), gg((nstreams + G_SPW - 1) / G_SPW);
+    const dim3 ga((nstreams + 63) / 64);
     hipStream_t ps = post_stream ? post_stream : aux;
     if (nsub <= 1 || !aux || !ev || (post && !ev2)) {
         hipLaunchKernelGGL(agc_pc_kernel<AgcS2Traits>, ga, dim3(128), 0, st, d_work, nstreams, coefs, 0, 1);
@@ -3524,7 +3351,7 @@ hipError_t s2_frame_loops_launch(const S2StreamWork* d_work, int nstreams, const
                                  S2LoopCoefs coefs, S2PlTablesDev tabs, S2ConstelDev con, int pls_code, int slots, int pilots,
                                  int pilot_blocks, int plframe, cf32* d_pllout, S2FrameStats* d_stats, hipStream_t st) {
     const int spw = frame_loops_spw(nstreams);
-    hipLaunchKernelGGL(s2_frame_loops_kernel<false>, dim3(frame_loops_grid(nstreams, spw)), dim3(64 * frame_loops_wpb(nstreams, spw)), 0, st, d_work, nstreams, d_frames, d_first, coefs,
+    hipLaunchKernelGGL(s2_frame_loops_kernel<false>, dim3(frame_loops_grid(nstreams, spw)), dim3(64), 0, st, d_work, nstreams, d_frames, d_first, coefs,
                        tabs, con, pls_code, slots, pilots, pilot_blocks, plframe, d_pllout, d_stats, (const S2VcmFound*)nullptr, 0, spw, (const S2StreamCfgDev*)nullptr);
     return hipGetLastError();
 }

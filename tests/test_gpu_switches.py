@@ -15,8 +15,6 @@ CASES = [
     (dict(DVBS2GPU_OPTIONS='mixed_groups=1'), 'mixed'),
     # ... and the one-launch-per-stage flow with its FEC jobs in line on ONE side stream
     (dict(DVBS2GPU_OPTIONS='mix_fec_streams=1'), 'mixed'),
-    # the throughput mode's big FEC jobs on the partition stream (a subset of the compute units; by default a rule decides per batch), jobs of other flows on the plain FEC stream behind them
-    (dict(DVBS2GPU_OPTIONS='fec_part=1'), 'pipelined'),
     # all post stages of a slice on one stream (default for big banks: the frame loops on a stream of their own beside the next slice's RRC)
     (dict(DVBS2GPU_OPTIONS='stage_loops_stream=0'), 'pipelined'),
 ]
@@ -31,10 +29,9 @@ def test_alternative_flows_give_the_same_bytes(env, sel):
 
 
 @pytest.mark.gpu
-def test_partition_stream_beside_null_stream_work_of_the_host(pkg):
-    """the partition stream (hipExtStreamCreateWithCUMask) is a default-flag, BLOCKING stream: work the host enqueues on the legacy null stream serialises with the decoder
-    jobs on it (INTEGRATION.md tells hosts to keep to explicit non-blocking streams) -- but it must never change results: the same pipelined calls with fec_part = 1 and a
-    null-stream operation of the host (a torch default-stream kernel and a plain hipMemcpy-style copy) between every two calls deliver what the default flow delivers"""
+def test_null_stream_work_of_the_host_between_pipelined_calls(pkg):
+    """the throughput mode's streams are non-blocking, and each call starts behind the host's work on the legacy null stream: the same pipelined calls with a null-stream
+    operation of the host (a torch default-stream kernel and a plain hipMemcpy-style copy) between every two calls deliver what the calls without it deliver"""
     import numpy as np
     import torch
     import orc
@@ -43,8 +40,8 @@ def test_partition_stream_beside_null_stream_work_of_the_host(pkg):
     S, chunk = 6, 40000
     sigs = [orc.transmit(14, 1, 0, nframes=7, seed=90 + i, esn0_db=15.0, cfo=1e-4, timing=0.1 * i, phase0=0.2, lead_symbols=300 + 50 * i)[0] for i in range(S)]
     got = []
-    for opts, poke in (({}, False), ({'fec_part': 1}, True)):
-        eng = pkg.Engine(0, options=opts)
+    for poke in (False, True):
+        eng = pkg.Engine(0)
         cfg = eng.default_cfg(14, True, False, max_ldpc_trials=16)
         dms = [eng.demod(cfg, max_samples=chunk) for _ in range(S)]
         outs = [torch.zeros(1 << 18, dtype=torch.uint8, device='cuda') for _ in range(S)]
