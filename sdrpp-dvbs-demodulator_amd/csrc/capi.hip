@@ -69,15 +69,9 @@ int apply_option(dvbs2gpu_ctx* c, const char* name, int v) {
     else if (n == "gardner_cand_skew") { c->gardner_cand_skew = v; }
     else if (n == "fe_slices") { if (!in(0, s2::S2_FE_MAX_SLICES)) return -1; c->fe_slices = v; }
     else if (n == "stage_pipeline") { if (!in(0, 2)) return -1; c->stage_pipeline = v; }
-    else if (n == "stage_post_stream") { if (!in(0, 2)) return -1; c->stage_post_stream = v; }
     else if (n == "stage_loops") { if (!in(0, s2::S2_FE_MAX_SLICES)) return -1; c->stage_pipeline_launches = v; }
     else if (n == "stage_min_duty") { if (!in(-1, 8)) return -1; c->stage_pipeline_min_duty = v; }
-    else if (n == "loops_ahead") { if (!in(0, 1)) return -1; c->loops_ahead = v; }
-    else if (n == "mixed_groups") { if (!in(0, 1)) return -1; c->mixed_groups = v; }
-    else if (n == "mix_fec_streams") { if (!in(1, 8)) return -1; c->mix_fec_streams = v; }
     else if (n == "g_prio_duty") { if (!in(-1, 8)) return -1; if (v < 0) c->g_prio_auto = true; else { c->g_prio_duty = v; c->g_prio_auto = false; } }
-    else if (n == "stage_loops_stream") { if (!in(0, 1)) return -1; c->stage_loops_stream = v; }
-    else if (n == "g_prio_cap") { if (!in(0, 7)) return -1; c->g_prio_cap = v; }
     else if (n == "dvbs_fe_slices") { if (!in(1, s2::DVBS_FE_MAX_SLICES)) return -1; c->dvbs_fe_slices = v; }
     else if (n == "dvbs_bank_min") { if (v < 1) return -1; c->dvbs_bank_min = v; }
     else if (n == "dvbs_agc_stream") { if (!in(0, 1)) return -1; c->dvbs_agc_stream = v != 0; }
@@ -450,23 +444,14 @@ void dvbs2gpu_destroy(dvbs2gpu_ctx* ctx) {
     for (auto& kv : ctx->bandedge) if (kv.second) (void)hipFree(kv.second);
     if (ctx->d_vcm_mods) (void)hipFree(ctx->d_vcm_mods);
     if (ctx->d_vcm_cons) (void)hipFree(ctx->d_vcm_cons);
-    for (auto& w : ctx->ws_vcm) w.release();
-    for (auto& w : ctx->ws_mix) w.release();
+    ctx->ws_vcm.release();
+    ctx->ws_mix.release();
     for (auto& row : ctx->ev_mix) for (hipEvent_t& e : row) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     if (ctx->ev_ws) (void)hipEventDestroy(ctx->ev_ws);
     for (auto& sp : ctx->timers.pending) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (auto e : ctx->timers.pool) (void)hipEventDestroy(e);
     ctx->fws.release();
-    for (auto& kv : ctx->fe_aux) {
-        if (kv.second.aux) (void)hipStreamDestroy(kv.second.aux);
-        for (hipEvent_t e : kv.second.ev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : kv.second.ev2) if (e) (void)hipEventDestroy(e);
-        if (kv.second.aux2) (void)hipStreamDestroy(kv.second.aux2);
-        if (kv.second.aux3) (void)hipStreamDestroy(kv.second.aux3);
-        for (hipEvent_t e : kv.second.ev3) if (e) (void)hipEventDestroy(e);
-        for (hipStream_t a : kv.second.dvbs_aux) if (a) (void)hipStreamDestroy(a);
-        for (auto& row : kv.second.dvbs_ev) for (hipEvent_t e : row) if (e) (void)hipEventDestroy(e);
-    }
+    for (auto& kv : ctx->fe_aux) kv.second.release();
     if (ctx->fe_stream) (void)hipStreamDestroy(ctx->fe_stream);
     if (ctx->fec_stream) (void)hipStreamDestroy(ctx->fec_stream);
     if (ctx->ev_llr) (void)hipEventDestroy(ctx->ev_llr);
@@ -477,10 +462,10 @@ void dvbs2gpu_destroy(dvbs2gpu_ctx* ctx) {
         if (ctx->ev_llr_grp[g]) (void)hipEventDestroy(ctx->ev_llr_grp[g]);
         if (ctx->grp_stream[g]) (void)hipStreamDestroy(ctx->grp_stream[g]);
         ctx->fws_grp[g].release();
-        for (auto& w : ctx->ws_grp[g]) w.release();
-        for (auto& par : ctx->ws_fecbuf[g]) for (auto& w : par) w.release();
+        ctx->ws_grp[g].release();
+        for (auto& par : ctx->ws_fecbuf[g]) par.release();
     }
-    for (auto& w : ctx->ws_rx) w.release();
+    ctx->ws_rx.release();
     for (auto& w : ctx->ws_dvbs) w.release();
     delete ctx;
 }

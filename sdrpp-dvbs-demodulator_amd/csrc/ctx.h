@@ -87,6 +87,31 @@ struct StageSpan {
 
 // the FEC stage's scratch buffers: one set per context, and one per configuration group for jobs that run side by side (s2_demod.hip)
 struct FecWs { Workspace msg, hard, syn, misc; void release() { msg.release(); hard.release(); syn.release(); misc.release(); } };
+// per-call scratch of the S2 batch flows (s2_demod.hip), one struct per flow.  `deliver`: the destination table of a job's delivery
+struct GroupWs {        // a CCM group (process_group)
+    Workspace work,     // stream-work table + first[] + symbol counts + NCO + FIFO cur/fill
+              found,    // PL-sync frame tables + counts
+              frames,   // frame refs + stats + trials + corrections + slot indices
+              pll, llr, bb, deliver,
+              slot_stats;   // stage pipeline: per-slot frame stats
+    void release() { for (Workspace* w : {&work, &found, &frames, &pll, &llr, &bb, &deliver, &slot_stats}) w->release(); }
+};
+struct VcmWs {          // a group of ACM/VCM streams (process_vcm_group)
+    Workspace work,     // stream-work table + first[] + counts + FIFO cur/fill + symbol counts + NCO
+              found, frames /* frames + stats + destinations + index lists */, pll, llr,
+              fec_llr, fec_bb, fec_res,     // synchronous FEC parts: LLRs | BBFRAMEs | results + index lists + destinations
+              deliver;
+    void release() { for (Workspace* w : {&work, &found, &frames, &pll, &llr, &fec_llr, &fec_bb, &fec_res, &deliver}) w->release(); }
+};
+struct MixWs {          // a mixed CCM batch (process_mixed)
+    Workspace work,     // stream-work table + per-stream configurations + symbol counts + NCO + FIFO cur/fill
+              found, llr_of /* per-frame LLR pointers + slot indices */, pll, slot_stats,
+              fec_llr, fec_bb, fec_res,     // synchronous FEC parts, as VcmWs
+              deliver;
+    void release() { for (Workspace* w : {&work, &found, &llr_of, &pll, &slot_stats, &fec_llr, &fec_bb, &fec_res, &deliver}) w->release(); }
+};
+// the buffers of one pipelined FEC job (per slot and parity): LLRs | BBFRAMEs | frame refs + first[] + results (CCM), results + index lists + destinations (ACM/VCM, mixed)
+struct FecJobBufs { Workspace llr, bb, job; void release() { llr.release(); bb.release(); job.release(); } };
 
 struct ConstelTables {          // device tables of one constellation (type, gamma1, gamma2)
     S2ConstelDev dev;
@@ -121,16 +146,18 @@ struct dvbs2gpu_ctx {
     s2::S2PlTablesDev pl{};
     std::map<int, s2::ConstelTables> constel; // by modcod (gammas depend on it)
     std::map<int, float*> rrc;                // by ntaps*1000 + round(alpha*100) (Ts = 2)
-    s2::Workspace ws_rx[8];
+    // (ws_rx.slot_stats also holds frontend_prepass's work table -- a pre-passed group is never staged; ws_rx.deliver also collects the jobs left in slots without a group)
+    s2::GroupWs ws_rx;
     // ACM/VCM mode (s2_demod.hip): what every PLS code means + the constellations it points to, on the device; per-call scratch
     s2::S2VcmMod* d_vcm_mods = nullptr;
     s2::S2ConstelDev* d_vcm_cons = nullptr;
     std::vector<s2::S2VcmMod> h_vcm_mods;
     std::vector<s2::FecParams> h_vcm_fec;     // by PLS code
-    s2::Workspace ws_vcm[12];
+    s2::VcmWs ws_vcm;
     // mixed CCM batches through one launch per stage (s2_demod.hip, process_mixed): per-call scratch, and per FEC side stream and job parity the event behind its jobs
-    s2::Workspace ws_mix[12];
-    hipEvent_t ev_mix[8][2] = {};
+    s2::MixWs ws_mix;
+    static constexpr int MIX_FEC_STREAMS = 4;           // side streams (grp_stream[0..3]) of process_mixed's FEC parts
+    hipEvent_t ev_mix[MIX_FEC_STREAMS][2] = {};
     // pipelined FEC (s2_demod.hip): with pipeline_fec set, dvbs2gpu_demod_process_batch runs the FEC of call k on fec_stream
     // while call k+1's front end runs on fe_stream; BBFRAMEs of call k are delivered by call k+1
     int pipeline_fec = 0;
@@ -141,7 +168,7 @@ struct dvbs2gpu_ctx {
     // streams from call to call): the job in flight, its buffers (double-buffered) and the event that marks its completion
     static constexpr int MAX_PIPE_GROUPS = 16;
     void* pending_fec[MAX_PIPE_GROUPS] = {};              // s2::PendingFec*
-    s2::Workspace ws_fecbuf[MAX_PIPE_GROUPS][2][3];       // per parity: LLRs | BBFRAMEs | frame refs + first[] + trials + corrections
+    s2::FecJobBufs ws_fecbuf[MAX_PIPE_GROUPS][2];         // per parity
     int fec_parity[MAX_PIPE_GROUPS] = {};
     // what the bench's self-check reads back (dvbs2gpu_debug_last_fec_job): the pipelined CCM job a slot delivered last -- its LLR and BBFRAME buffers stay untouched until the
     // slot's next job of the same parity is started
@@ -152,7 +179,7 @@ struct dvbs2gpu_ctx {
     hipEvent_t ev_fec_t0[MAX_PIPE_GROUPS][2] = {};   // ... and its start (timing events: the job's duration feeds the priority balancer)
     std::chrono::steady_clock::time_point fec_last_entry{};
     // several groups of one pipelined batch run their MODCOD-dependent stages side by side (one host thread and HIP stream each)
-    s2::Workspace ws_grp[MAX_PIPE_GROUPS][8];
+    s2::GroupWs ws_grp[MAX_PIPE_GROUPS];
     hipStream_t grp_stream[MAX_PIPE_GROUPS] = {};
     hipEvent_t ev_llr_grp[MAX_PIPE_GROUPS] = {};
     std::mutex fec_mtx;                                   // FEC jobs on the shared stream are enqueued whole, one at a time (shared FEC workspaces)
@@ -160,12 +187,22 @@ struct dvbs2gpu_ctx {
     // SIDE BY SIDE instead: on the group's own stream (grp_stream) with a set of FEC workspaces per group
     s2::FecWs fws_grp[MAX_PIPE_GROUPS];
     // time-sliced front end (s2_rx_kernels.hip, s2_frontend_launch): per main stream one auxiliary stream + the slice events
-    struct FeAux { hipStream_t aux = nullptr, aux2 = nullptr, aux3 = nullptr; hipEvent_t ev[s2::S2_FE_MAX_SLICES + 1] = {}, ev2[s2::S2_FE_MAX_SLICES + 1] = {}, ev3[2 * (s2::S2_FE_MAX_SLICES + 1)] = {}; hipStream_t dvbs_aux[4] = {}; hipEvent_t dvbs_ev[4][s2::DVBS_FE_MAX_SLICES + 1] = {}; };   // (dvbs_*: the DVB-S receiver's stage streams: AGC, FLL, RRC, soft FIFO + Viterbi)
+    struct FeAux {      // (dvbs_*: the DVB-S receiver's stage streams: AGC, FLL, RRC, soft FIFO + Viterbi)
+        hipStream_t aux = nullptr, aux2 = nullptr, aux3 = nullptr;
+        hipEvent_t ev[s2::S2_FE_MAX_SLICES + 1] = {}, ev2[s2::S2_FE_MAX_SLICES + 1] = {}, ev3[2 * (s2::S2_FE_MAX_SLICES + 1)] = {};
+        hipStream_t dvbs_aux[4] = {};
+        hipEvent_t dvbs_ev[4][s2::DVBS_FE_MAX_SLICES + 1] = {};
+        void release() {    // destroys the streams and events (the entry is dropped afterwards)
+            for (hipStream_t s : {aux, aux2, aux3}) if (s) (void)hipStreamDestroy(s);
+            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+            for (hipEvent_t e : ev2) if (e) (void)hipEventDestroy(e);
+            for (hipEvent_t e : ev3) if (e) (void)hipEventDestroy(e);
+            for (hipStream_t s : dvbs_aux) if (s) (void)hipStreamDestroy(s);
+            for (auto& row : dvbs_ev) for (hipEvent_t e : row) if (e) (void)hipEventDestroy(e);
+        }
+    };
     std::map<hipStream_t, FeAux> fe_aux;
     // development / test options (dvbs2gpu_set_option, or DVBS2GPU_OPTIONS="name=value,..." in the environment when the context is created)
-    int loops_ahead = 1;                      // 0: frame loops only behind the PL sync (small banks)
-    int mixed_groups = 0;                     // 1: small mixed batches through the per-group flow instead of process_mixed
-    int mix_fec_streams = 4;                  // side streams for the FEC jobs of process_mixed (1..8)
     int gardner_form = 0;                     // 2 / 4: one form of the timing recovery (0: chosen by bank size)
     int gardner_cand_skew = 0;                // tests only: skews the candidate form's arm prediction so that it leaves its tables
     int ldpc_wave = -1;                       // short frames: 0 / 1 = lane-per-row / wave-per-frame decoder (-1: per code)
@@ -176,7 +213,6 @@ struct dvbs2gpu_ctx {
     int stage_pipeline_min_duty = 2;          // option stage_min_duty: pipelined mode uses the stage pipeline only above this balancer setting (-1: always).
                                               // 2: with the frame loops at the decoder's base priority the two streams of a headline step are 6 ms apart, a stray
                                               // verdict of the balancer must not tip the step into the other flow (which costs it 3 %)
-    int stage_post_stream = 1;                // option stage_post_stream: synchronous mode runs the post stages on a stream of their own (0: on the AGC's)
     unsigned stage_calls = 0;
     int stage_pipeline = 1;                   // option stage_pipeline: RRC, PL-sync walk and frame loops of a CCM call behind every timing-recovery slice (0: after the last one, frames pooled by the host first)
     int fe_slices = 0;                        // option fe_slices (0 = by mode: 4 pipelined, 8 synchronous; 1 = both stages back to back on the caller's stream)
@@ -185,8 +221,6 @@ struct dvbs2gpu_ctx {
     int g_prio_hold = 0, g_prio_last_down = 0;      // the balancer's damper: calls during which no step down is tried / calls since the last step down (s2_demod.hip)
     long long g_prio_sig = -1;                // what the balance was found for (streams, MODCOD, frame kind, iteration setting of the batch): another configuration starts from 0 again
     bool g_prio_auto = true;                  // option g_prio_duty fixes the value
-    int stage_loops_stream = 1;               // option stage_loops_stream: big banks run the frame loops of a slice on a stream of their own, beside the next slice's RRC (0: all post stages of a slice on one stream)
-    int g_prio_cap = 7;                       // option g_prio_cap: the highest share the balancer may reach (development aid)
     int dvbs_bank_min = 2048;                 // option dvbs_bank_min: carriers from which a bank uses the four-streams-per-wave FLL (measured crossover with the written-out wave-per-stream loop: 2048 carriers 74.2 vs 74.8 ms, 1024: 46.2 vs 54.8, 4096: 128.8 vs 111.4; tests: 1)
     int dvbs_agc_stream = 1;                  // option dvbs_agc_stream: the AGC slices of a bank below dvbs_bank_min carriers on a third auxiliary stream (0: on the Viterbi stream)
     int dvbs_fe_slices = 24;                 // option dvbs_fe_slices: time slices of a DVB-S call (dvbs_demod.hip)

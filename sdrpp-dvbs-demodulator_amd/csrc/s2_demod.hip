@@ -335,8 +335,6 @@ int demod_reset_state(dvbs2gpu_demod* d) {
     return 0;
 }
 
-// Runs one group of streams that share (modcod, shortframes, pilots) and loop coefficients.
-// FEC job launched by one pipelined call and delivered by the next
 // The FEC job of a pipelined call, collected by the next call (or by a later one, or dropped when the mode is switched off).
 // CCM groups: one job = one LDPC code, frames stream-major, every BBFRAME kb bytes.  ACM/VCM groups: one part per LDPC code present in the
 // call (frames of a part = pooled frame indices idx[]), BBFRAMEs of different sizes at per-frame byte offsets inside their stream's output.
@@ -463,6 +461,7 @@ static int deliver_job(dvbs2gpu_ctx* ctx, PendingFec* job, hipStream_t st, Works
 #ifndef S2_POST_PRIO_MIN_DUTY
 #define S2_POST_PRIO_MIN_DUTY 5
 #endif
+constexpr int S2_PRIO_MAX_DUTY = 7;       // the highest share the balancer may reach
 #ifndef S2_PRIO_START_DUTY
 #define S2_PRIO_START_DUTY 3      // (third part of round 6, headline at --warmup 2 | 5: start 2 -> 274.8, 254.4 | 252.3; 3 -> 253.0, 252.8, 252.5 | 252.7, 252.6; 4 -> 254.8, 255.6 | 256.0: from 4 the first verdicts take it to 5, post stages up, and the dead band keeps it there)
 #endif
@@ -507,7 +506,7 @@ static hipError_t frontend_sliced(dvbs2gpu_ctx* ctx, const S2StreamWork* d_work,
         if (e != hipSuccess) return e;
     }
     // (big banks: the frame loops on a third auxiliary stream, s2_frontend_launch)
-    const bool loops_own = fa && post && own_post_stream && ctx->stage_loops_stream && n > S2_SMALL_BANK && nsub > 1;
+    const bool loops_own = fa && post && own_post_stream && n > S2_SMALL_BANK && nsub > 1;
     if (loops_own && !fa->aux3) {
         std::lock_guard<std::mutex> l(ctx->mtx);
         hipError_t e = create_stream(ctx, &fa->aux3, +1);
@@ -530,14 +529,165 @@ struct HostMarks {
     ~HostMarks() { if (on) fprintf(stderr, "[dvbs2gpu host]%s\n", line.c_str()); }
 };
 
+// ---------------------------------------------------------------------------------------------------- steps every batch flow shares
+// What a flow clears of each handle's results of the last call.  Stats: not in the pipelined mode, where dvbs2gpu_demod_process_batch has cleared them (another group's
+// thread may be delivering this stream's frames).  frontend_prepass clears nothing: the group flow behind it does.
+enum : unsigned { CLR_FRAMES = 1, CLR_STATS = 2, CLR_VCM = 4 /* ACM/VCM: also the frame lengths and the taps */ };
+
+// The stream-work table of a call: checks every count against its handle's max_samples, fills S2StreamWork, clears the handle's per-call fields and uploads the
+// table to the front of `ws` (sized for the table + `extra` bytes).  `spec`: the frame loops run ahead of the PL sync (their buffer is allocated on first use).
+int upload_work(dvbs2gpu_demod* const* dm, int n, const cf32* const* d_iq, const int* counts, uint8_t* const* d_out, unsigned clear, bool spec,
+                Workspace& ws, size_t extra, hipStream_t st, int* max_count) {
+    std::vector<S2StreamWork> work(n);
+    *max_count = 0;
+    for (int i = 0; i < n; ++i) {
+        dvbs2gpu_demod* d = dm[i];
+        if (counts[i] < 0 || counts[i] > d->max_samples) { last_error() = "count exceeds max_samples"; return DVBS2GPU_ERR_ARG; }
+        if (spec && !d->d_spec) HIP_TRY(hipMalloc((void**)&d->d_spec, sizeof(cf32) * 33282));
+        work[i].in = d_iq[i]; work[i].count = counts[i]; work[i].fe_out = d->d_fe;
+        work[i].fifo = d->d_fifo[d->fifo_cur]; work[i].fifo_fill = d->fifo_fill; work[i].st = d->d_state;
+        work[i].fifo_next = d->d_fifo[d->fifo_cur ^ 1]; work[i].out = d_out[i]; work[i].spec_out = d->d_spec;
+        *max_count = std::max(*max_count, counts[i]);
+        if (clear & CLR_STATS) d->stats.clear();
+        if (clear & CLR_FRAMES) { d->frame_ptrs.clear(); d->frame_pos.clear(); }
+        if (clear & CLR_VCM) { d->frame_len.clear(); d->tap_pll = nullptr; d->tap_llr = nullptr; d->tap_pll_count = 0; d->tap_llr_count = 0; d->tap_pll_stride = 0; }
+    }
+    int rc;
+    if ((rc = ws.ensure(sizeof(S2StreamWork) * n + extra))) return rc;
+    HIP_TRY(hipMemcpyAsync(ws.p, work.data(), sizeof(S2StreamWork) * n, hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// ---- 7: the FIFO remainder behind the cur[i] symbols the call consumed to the spare buffer, the NCO frequency for the getter; then every handle's FIFO, symbol axis
+// and NCO frequency are committed
+int finish_call(dvbs2gpu_demod* const* dm, int n, const std::vector<int>& cur, const S2StreamWork* d_work, int* d_curfill, int* d_nsym, float* d_nco, hipStream_t st) {
+    std::vector<int> curfill(2 * n);
+    for (int i = 0; i < n; ++i) { curfill[2 * i] = cur[i]; curfill[2 * i + 1] = dm[i]->fifo_fill; }
+    HIP_TRY(hipMemcpyAsync(d_curfill, curfill.data(), sizeof(int) * 2 * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(s2_fifo_compact_launch(d_work, n, d_curfill, st));
+    std::vector<float> nco(n);
+    HIP_TRY(s2_collect_launch(d_work, n, d_nsym, d_nco, st));
+    HIP_TRY(hipMemcpyAsync(nco.data(), d_nco, sizeof(float) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) {
+        dvbs2gpu_demod* d = dm[i];
+        if (cur[i] > 0) { d->fifo_fill -= cur[i]; d->fifo_cur ^= 1; d->sym_base += cur[i]; }
+        d->nco_freq_host = nco[i];
+    }
+    return 0;
+}
+
+// per-stage timers of the stage pipeline
+struct Spans : S2SliceSpans {
+    StageTimers* T; std::unique_ptr<StageSpan> sp[4];
+    explicit Spans(StageTimers* t) : T(t) {}
+    void begin(int stage, hipStream_t s) override { sp[stage].reset(new StageSpan(*T, stage == 1 ? ST_RRC : (stage == 2 ? ST_PLSYNC : ST_LOOPS), s)); }
+    void end(int stage, hipStream_t) override { sp[stage].reset(); }
+};
+
+// The stage pipeline of a call (s2_frontend_launch): RRC, PL-sync walk and frame loops behind the timing-recovery slices, a stream's frames in its maxf slots of
+// `raw` symbols.  The frame loops run about once per frame a stream gets per call (a launch costs its longest stream's chain, 11 ms per frame, however few streams
+// have a frame ready; `raw_launch` is the PLFRAME length that counts), or as often as the option stage_loops says.  `spec` (small banks): ahead of the PL sync, behind
+// (nearly) every slice -- but a launch wants a few thousand symbols per stream to chew on: a bank of 64 spends 0.4 ms per launch on top of its symbols.
+// The caller fills in what the frame loops need of the configuration: con .. pilot_blocks for one MODCOD, cfgs for a mixed batch.
+S2PostStages post_stages(dvbs2gpu_ctx* ctx, Spans& spans, const dvbs2gpu_demod* d0, const float* d_taps, int max_count, int raw, int raw_launch, int maxf,
+                         S2VcmFound* d_found, int* d_counts, cf32* d_pll, S2FrameStats* d_stats, bool spec) {
+    int launches = std::min(S2_FE_MAX_SLICES, std::max(1, (max_count / 2) / raw_launch));
+    if (ctx->stage_pipeline_launches > 0) launches = ctx->stage_pipeline_launches;
+    S2PostStages post{d_taps, d0->cfg.rrc_taps, max_count + max_count / 32 + 8, raw, maxf, d_found, d_counts, ctx->pl, S2ConstelDev{}, 0,
+                      0, 0, 0, d_pll, d_stats, ctx->timers.on ? &spans : nullptr, launches};
+    if (spec) {
+        constexpr int sym_per_launch = 2700;
+        post.spec = 1;
+        post.loops_launches = std::min(S2_FE_MAX_SLICES, std::max(launches, (max_count / 2) / sym_per_launch));
+    }
+    return post;
+}
+
+// The pipelined hand-over of one slot: this call's FEC job is parked in ctx->pending_fec[slot] for the next call, and the job the previous call parked there is
+// delivered into this call's buffers, through the batch map (none given: a map of this call's streams, whose output counts and stats it clears).  Jobs of all
+// groups run in order on the FEC stream; each is followed by its own event, and the delivery (scatter into the caller's buffers) runs on the call's stream behind
+// that event, so it never queues behind a later group's decoder.
+struct SlotHandOver {
+    dvbs2gpu_ctx* ctx; int slot; hipStream_t st; Workspace& wo;
+    BatchMap bm_local; const BatchMap* bm;
+    std::unique_ptr<PendingFec> prev;     // the job the slot held (`take`): delivered by this call
+    SlotHandOver(dvbs2gpu_ctx* c, int slot_, hipStream_t st_, Workspace& wo_, const BatchMap* bm_, bool take,
+                 dvbs2gpu_demod* const* dm, int n, uint8_t* const* d_out, int out_cap, int* out_bytes) : ctx(c), slot(slot_), st(st_), wo(wo_), bm(bm_) {
+        if (!bm) {
+            for (int i = 0; i < n; ++i) { bm_local.pos[dm[i]] = i; out_bytes[i] = 0; dm[i]->stats.clear(); }
+            bm_local.d_out = d_out; bm_local.out_bytes = out_bytes; bm_local.out_cap = out_cap;
+            bm = &bm_local;
+        }
+        if (take) { prev.reset((PendingFec*)ctx->pending_fec[slot]); ctx->pending_fec[slot] = nullptr; }
+    }
+    int deliver(PendingFec* job) const { return deliver_job(ctx, job, st, wo, *bm); }
+    void park(std::unique_ptr<PendingFec> job) { if (job) ctx->pending_fec[slot] = job.release(); }
+    int park_and_deliver(std::unique_ptr<PendingFec> job) { park(std::move(job)); return prev ? deliver(prev.get()) : 0; }
+};
+
+// Balance of the two streams of the pipelined mode: did this call have to wait for the previous call's FEC job `prev` (the decoder is the critical path: the timing
+// loop should yield more) or was the job long done (the front end is: it should yield less)?  One step of the priority duty per two consistent calls.
+// `job_was_done`: asked before the delivery, which began at t_d0.
+void balance_priority(dvbs2gpu_ctx* ctx, const dvbs2gpu_demod* d0, int n, const PendingFec& prev, bool job_was_done,
+                      std::chrono::steady_clock::time_point t_entry, std::chrono::steady_clock::time_point t_d0, HostMarks& hm) {
+    // (the balance belongs to a configuration: what one batch settled at says nothing about the next one's -- a front-end-bound configuration that inherited the
+    //  headline's setting spent part of its steps in the wrong flow)
+    const long long sig = ((long long)n << 32) ^ ((long long)d0->cfg.modcod << 20) ^ ((long long)d0->cfg.shortframes << 19) ^ ((long long)d0->cfg.pilots << 18) ^
+                          ((long long)(d0->cfg.force_ldpc_iters & 0xff) << 8) ^ (long long)(d0->cfg.max_ldpc_trials & 0xff);
+    const bool sig_changed = sig != ctx->g_prio_sig;
+    // (a new configuration starts at share S2_PRIO_START_DUTY -- from 0 the headline's first four calls ran 55 ms long each, the front end being their critical path, and the
+    //  plugin's mode needed 14 calls to its share of 7; rounds 5-6 started at 2, where the decoder-bound configurations settled then; since the timing recovery's producers
+    //  run above the decoder they settle at 4: headline 4, config 5's stand-in 4, config 2 5, plugin's mode 7)
+    if (sig_changed) { ctx->g_prio_sig = sig; ctx->g_prio_duty = std::min(S2_PRIO_MAX_DUTY, S2_PRIO_START_DUTY); ctx->g_prio_trend = 0; ctx->g_prio_hold = 0; ctx->g_prio_last_down = 0; }
+    const auto t_d1 = std::chrono::steady_clock::now();
+    const double wait_ms = std::chrono::duration<double, std::milli>(t_d1 - t_d0).count();
+    const double call_ms = std::chrono::duration<double, std::milli>(t_d1 - t_entry).count();
+    // the job just delivered: how long did it run (timing events around it), and how far apart do this batch's calls come?
+    float job_ms = 0.f;
+    const double period_ms = std::chrono::duration<double, std::milli>(t_entry - ctx->fec_last_entry).count();
+    ctx->fec_last_entry = t_entry;
+    const bool timed = prev.t0 && prev.done && hipEventElapsedTime(&job_ms, prev.t0, prev.done) == hipSuccess && period_ms > 0.0 && period_ms < 5000.0;
+    const int verdict = job_was_done ? +1 : (wait_ms > 1.0 + 0.035 * call_ms ? -1 : 0);     // (3.5 %: the headline waits 2.2 % of its call at its best share, 2.9 % in the first calls of a run)
+    // a clear case moves the share at once: the job took less than 0.8 of the call (the front end is the critical path by a wide margin) / the call waited more
+    // than a twentieth of its time for the job; anything else needs two consistent calls
+    const bool clear = verdict > 0 ? (timed && job_ms < 0.8 * call_ms) : (verdict < 0 && wait_ms > 0.05 * call_ms);
+    // (no see-saw: a step down that the very next verdicts take back -- the lower share made the front end the critical path -- is not tried again for 64 calls;
+    //  the headline sat at share 2 with a wait right at the threshold and dipped to 1 every dozen calls, one 380 ms call each time)
+    if (ctx->g_prio_hold > 0) --ctx->g_prio_hold;
+    const bool held = verdict < 0 && ctx->g_prio_hold > 0;
+    if (verdict != 0 && !held && (clear || verdict == ctx->g_prio_trend)) {
+        const int before = ctx->g_prio_duty;
+        ctx->g_prio_duty = std::min(S2_PRIO_MAX_DUTY, std::max(0, ctx->g_prio_duty + verdict));
+        if (verdict > 0 && ctx->g_prio_last_down > 0 && ctx->g_prio_duty != before) ctx->g_prio_hold = 64;     // (up again right behind a step down)
+        ctx->g_prio_last_down = (verdict < 0 && ctx->g_prio_duty != before) ? 4 : 0;
+        ctx->g_prio_trend = 0;
+    } else {
+        ctx->g_prio_trend = held ? 0 : verdict;
+        if (ctx->g_prio_last_down > 0) --ctx->g_prio_last_down;
+    }
+    if (hm.on) { char b[128]; snprintf(b, sizeof(b), " wait=%.2f call=%.1f duty=%d job=%.1f period=%.1f", wait_ms, call_ms, ctx->g_prio_duty, job_ms, period_ms); hm.line += b; }
+}
+
+// how process_group runs a group of streams that share (modcod, shortframes, pilots) and loop coefficients
+struct GroupCall {
+    bool pipelined = false;         // the FEC job goes into slot `slot` (deliver_now: collected by this call, else by the next one)
+    int slot = 0;
+    const int* pre_nsym = nullptr;  // frontend_prepass has run the MODCOD-independent stages for the whole batch
+    bool own_ws = false;            // side by side with the batch's other groups: the group's own scratch (ws_grp[slot]), stream and, small jobs, FEC run
+    bool deliver_now = false;       // (a synchronous call's groups side by side)
+    const BatchMap* bm = nullptr;   // pipelined: the streams of the whole batch (null: this group's)
+};
+
 int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf32* const* d_iq, const int* counts,
-                  uint8_t* const* d_out, int out_cap, int* out_bytes, hipStream_t st, bool pipelined, int slot, const int* pre_nsym, bool own_ws, bool deliver_now,
-                  const BatchMap* bm = nullptr) {
+                  uint8_t* const* d_out, int out_cap, int* out_bytes, hipStream_t st, const GroupCall& gc) {
     HostMarks hm(ctx->host_timing != 0);
     const auto t_entry = std::chrono::steady_clock::now();
     dvbs2gpu_demod* d0 = dm[0];
-    Workspace* const W = own_ws ? ctx->ws_grp[slot] : ctx->ws_rx;      // per-call scratch: the group's own set when groups run side by side
-    const hipEvent_t ev_llr = own_ws ? ctx->ev_llr_grp[slot] : ctx->ev_llr;
+    const bool pipelined = gc.pipelined;
+    const int slot = gc.slot;
+    GroupWs& W = gc.own_ws ? ctx->ws_grp[slot] : ctx->ws_rx;      // per-call scratch: the group's own set when groups run side by side
+    const hipEvent_t ev_llr = gc.own_ws ? ctx->ev_llr_grp[slot] : ctx->ev_llr;
     const ModcodParams& mp = d0->mp;
     const int raw = mp.plframe, kb = mp.fec.kbch / 8, N = mp.fec.N;
     int rc;
@@ -550,34 +700,21 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     // ---- 1,2: front end + RRC
     // small banks (a workgroup per stream in the frame loops): the loops run behind EVERY slice and ahead of the PL sync (s2_frame_loops_kernel);
     // the window they are ahead in keeps its PLL output in a buffer of the stream's own (one PLFRAME of the longest kind)
-    const bool loops_ahead = ctx->loops_ahead != 0 && n <= S2_SMALL_BANK && !d0->cfg.pilot_aided && ctx->stage_pipeline_launches <= 0;     // (S2_SMALL_BANK = FL_SMALL_BANK of the kernels)
-    std::vector<S2StreamWork> work(n);
-    int max_count = 0;
-    for (int i = 0; i < n; ++i) {
-        dvbs2gpu_demod* d = dm[i];
-        if (counts[i] < 0 || counts[i] > d->max_samples) { last_error() = "count exceeds max_samples"; return DVBS2GPU_ERR_ARG; }
-        if (loops_ahead && !d->d_spec) HIP_TRY(hipMalloc((void**)&d->d_spec, sizeof(cf32) * 33282));
-        work[i].in = d_iq[i]; work[i].count = counts[i]; work[i].fe_out = d->d_fe;
-        work[i].fifo = d->d_fifo[d->fifo_cur]; work[i].fifo_fill = d->fifo_fill; work[i].st = d->d_state;
-        work[i].fifo_next = d->d_fifo[d->fifo_cur ^ 1]; work[i].out = d_out[i]; work[i].spec_out = d->d_spec;
-        max_count = std::max(max_count, counts[i]);
-        if (!pipelined) d->stats.clear();        // (pipelined: dvbs2gpu_demod_process_batch has cleared them -- another group's thread may be delivering this stream's frames)
-        d->frame_ptrs.clear(); d->frame_pos.clear();
-    }
-    Workspace& ws_work = W[0];
-    if ((rc = ws_work.ensure(sizeof(S2StreamWork) * n + sizeof(int) * (n + 1) + sizeof(int) * 4 * n + 64))) return rc;
-    S2StreamWork* d_work = (S2StreamWork*)ws_work.p;
-    int* d_nsym = (int*)((char*)ws_work.p + sizeof(S2StreamWork) * n + sizeof(int) * (n + 1));   // [n]
-    float* d_nco = (float*)(d_nsym + n);                                                          // [n]
-    int* d_curfill = (int*)(d_nco + n);                                                           // [2n]
-    HIP_TRY(hipMemcpyAsync(d_work, work.data(), sizeof(S2StreamWork) * n, hipMemcpyHostToDevice, st));
+    const bool spec_loops = n <= S2_SMALL_BANK && !d0->cfg.pilot_aided && ctx->stage_pipeline_launches <= 0;     // (S2_SMALL_BANK = FL_SMALL_BANK of the kernels)
+    int max_count;
+    if ((rc = upload_work(dm, n, d_iq, counts, d_out, CLR_FRAMES | (pipelined ? 0 : CLR_STATS), spec_loops, W.work,
+                          sizeof(int) * (n + 1) + sizeof(int) * 4 * n + 64, st, &max_count))) return rc;
+    S2StreamWork* d_work = (S2StreamWork*)W.work.p;
+    int* d_first = (int*)(d_work + n);        // [n + 1]
+    int* d_nsym = d_first + (n + 1);          // [n]
+    float* d_nco = (float*)(d_nsym + n);      // [n]
+    int* d_curfill = (int*)(d_nco + n);       // [2n]
     // ---- 3: PL sync.  The 2-state realign machine of S2PLSyncBlock runs on the device, one workgroup per stream walking its windows
     // in order (s2_ccm_walk_kernel); the host only pools the frame tables it gets back (ONE synchronisation for stages 1-3, or 1-4).
     int maxf = 0;
     for (int i = 0; i < n; ++i) maxf = std::max(maxf, dm[i]->fifo_cap / raw + 2);
-    Workspace& ws_win = W[1];
-    if ((rc = ws_win.ensure(sizeof(S2VcmFound) * (size_t)n * maxf + sizeof(int) * 4 * n + 64))) return rc;
-    S2VcmFound* d_found = (S2VcmFound*)ws_win.p;
+    if ((rc = W.found.ensure(sizeof(S2VcmFound) * (size_t)n * maxf + sizeof(int) * 4 * n + 64))) return rc;
+    S2VcmFound* d_found = (S2VcmFound*)W.found.p;
     int* d_counts = (int*)(d_found + (size_t)n * maxf);
     // Stage pipeline (calls of one configuration): RRC, walk and the frame loops run behind every timing-recovery slice on the auxiliary stream
     // (s2_frontend_launch); a stream's frames stay in its maxf slots of the PLL-output / statistics arrays until the host has pooled the tables.
@@ -585,42 +722,27 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     // share to its minimum): there the stages back to back leave the decoder more of the SIMDs (headline: 390 vs 394 ms per step).
     // (stage_pipeline == 2, for the tests: every other call, whatever the mode -- the two flows leave a stream in the same state)
     // (a small bank is a set of latency chains whatever the mode: always staged)
-    const bool staged = !pre_nsym && (ctx->stage_pipeline == 2 ? (ctx->stage_calls++ & 1) != 0 :
+    const bool staged = !gc.pre_nsym && (ctx->stage_pipeline == 2 ? (ctx->stage_calls++ & 1) != 0 :
         ctx->stage_pipeline && (n <= S2_SMALL_BANK || !(pipelined && ctx->g_prio_auto && ctx->g_prio_duty <= ctx->stage_pipeline_min_duty)));
     ctx->last_call_staged = staged;
-    Workspace& ws_pll = W[3];
-    Workspace& ws_slot = W[7];
     std::vector<S2FrameStats> slot_stats;
     if (staged) {
         const size_t nslot = (size_t)n * maxf;
-        if ((rc = ws_pll.ensure(nslot * raw * sizeof(cf32)))) return rc;
-        if ((rc = ws_slot.ensure(sizeof(S2FrameStats) * nslot + 64))) return rc;
-        struct Spans : S2SliceSpans {
-            StageTimers* T; std::unique_ptr<StageSpan> sp[4];
-            void begin(int stage, hipStream_t s) override { sp[stage].reset(new StageSpan(*T, stage == 1 ? ST_RRC : (stage == 2 ? ST_PLSYNC : ST_LOOPS), s)); }
-            void end(int stage, hipStream_t) override { sp[stage].reset(); }
-        } spans;
-        spans.T = &ctx->timers;
-        // how often the frame loops run inside the call: about once per frame a stream gets per call (a launch costs its longest stream's chain,
-        // 11 ms per frame, however few streams have a frame ready)
-        int launches = std::min(S2_FE_MAX_SLICES, std::max(1, (max_count / 2) / raw));
-        if (ctx->stage_pipeline_launches > 0) launches = ctx->stage_pipeline_launches;
-        S2PostStages post{d_taps, d0->cfg.rrc_taps, max_count + max_count / 32 + 8, raw, maxf, d_found, d_counts, ctx->pl, CT->dev, d0->pls_code,
-                          mp.slots, mp.pilots, mp.pilot_blocks, (cf32*)ws_pll.p, (S2FrameStats*)ws_slot.p, ctx->timers.on ? &spans : nullptr, launches};
-        if (loops_ahead) {
-            // behind (nearly) every slice -- but a launch wants a few thousand symbols per stream to chew on: a bank of 64 spends 0.4 ms per
-            // launch on top of its symbols
-            constexpr int sym_per_launch = 2700;
-            post.spec = 1;
-            post.loops_launches = std::min(S2_FE_MAX_SLICES, std::max(launches, (max_count / 2) / std::max(sym_per_launch, 1)));
-        }
-        { StageSpan sp(ctx->timers, ST_FRONTEND, st); HIP_TRY(frontend_sliced(ctx, d_work, n, d0->co, st, &post, ctx->stage_post_stream == 2 || ((!pipelined || n <= S2_SMALL_BANK || (ctx->g_prio_auto && ctx->g_prio_duty >= 4)) && ctx->stage_post_stream), nullptr, max_count)); }   // (a small bank is a set of latency chains in the throughput mode too: its post stages on the AGC's stream made one stream's 4-frame call 39.9 ms instead of 25;
+        if ((rc = W.pll.ensure(nslot * raw * sizeof(cf32)))) return rc;
+        if ((rc = W.slot_stats.ensure(sizeof(S2FrameStats) * nslot + 64))) return rc;
+        Spans spans(&ctx->timers);
+        S2PostStages post = post_stages(ctx, spans, d0, d_taps, max_count, raw, raw, maxf, d_found, d_counts, (cf32*)W.pll.p, (S2FrameStats*)W.slot_stats.p, spec_loops);
+        post.con = CT->dev; post.pls_code = d0->pls_code; post.slots = mp.slots; post.pilots = mp.pilots; post.pilot_blocks = mp.pilot_blocks;
+        // the post stages on a stream of their own, but for a big bank in the throughput mode beside a decoder that is the critical path
+        // (a small bank is a set of latency chains in the throughput mode too: its post stages on the AGC's stream made one stream's 4-frame call 39.9 ms instead of 25;
         //  a big bank whose FRONT END the balancer has found critical -- priority share 4 or more: the plugin's mode, QPSK -- likewise: AGC + RRC + walk + frame loops on one
         //  stream were 127 ms of launches per 140 ms step; beside a decoder that is the critical path the shared stream stays: headline 347 vs 361 ms per step)
+        const bool own_post_stream = !pipelined || n <= S2_SMALL_BANK || (ctx->g_prio_auto && ctx->g_prio_duty >= 4);
+        { StageSpan sp(ctx->timers, ST_FRONTEND, st); HIP_TRY(frontend_sliced(ctx, d_work, n, d0->co, st, &post, own_post_stream, nullptr, max_count)); }
         slot_stats.resize(nslot);
-        HIP_TRY(hipMemcpyAsync(slot_stats.data(), ws_slot.p, sizeof(S2FrameStats) * nslot, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(slot_stats.data(), W.slot_stats.p, sizeof(S2FrameStats) * nslot, hipMemcpyDeviceToHost, st));
     } else {
-        if (!pre_nsym) {
+        if (!gc.pre_nsym) {
             // (with pre_nsym the MODCOD-independent stages already ran for the whole batch: frontend_prepass)
             { StageSpan sp(ctx->timers, ST_FRONTEND, st); HIP_TRY(frontend_sliced(ctx, d_work, n, d0->co, st, nullptr, false, nullptr, max_count)); }
             { StageSpan sp(ctx->timers, ST_RRC, st); HIP_TRY(s2_rrc_decim_launch(d_work, n, max_count + max_count / 32 + 8, d_taps, d0->cfg.rrc_taps, st, post_prio_wanted(ctx))); }
@@ -663,34 +785,33 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     const int nf = (int)frames.size();
     std::vector<S2FrameStats> hstats(nf);
     std::vector<int32_t> trials(nf), corr(nf);
-    uint8_t* d_bb = nullptr;
+    const int force = d0->cfg.force_ldpc_iters > 0;
+    const int mt = force ? d0->cfg.force_ldpc_iters : d0->cfg.max_ldpc_trials;
+    const int par = ctx->fec_parity[slot];
+    FecJobBufs& jb = ctx->ws_fecbuf[slot][par];     // (pipelined: the FEC job's own buffers)
     if (nf > 0) {
-        Workspace& ws_fr = W[2];
-        if ((rc = ws_fr.ensure(sizeof(S2FrameRef) * nf + sizeof(S2FrameStats) * nf + sizeof(int32_t) * 3 * nf + 64))) return rc;
-        S2FrameRef* d_frames = (S2FrameRef*)ws_fr.p;
+        if ((rc = W.frames.ensure(sizeof(S2FrameRef) * nf + sizeof(S2FrameStats) * nf + sizeof(int32_t) * 3 * nf + 64))) return rc;
+        S2FrameRef* d_frames = (S2FrameRef*)W.frames.p;
         S2FrameStats* d_stats = (S2FrameStats*)(d_frames + nf);
         int32_t* d_trials = (int32_t*)(d_stats + nf);
         int32_t* d_corr = d_trials + nf;
         int* d_slot = (int*)(d_corr + nf);
-        int* d_first = (int*)((char*)ws_work.p + sizeof(S2StreamWork) * n);
-        const int par = ctx->fec_parity[slot];
-        Workspace &ws_llr = pipelined ? ctx->ws_fecbuf[slot][par][0] : W[4];
-        Workspace &ws_bb = pipelined ? ctx->ws_fecbuf[slot][par][1] : W[5];
+        Workspace& ws_llr = pipelined ? jb.llr : W.llr;
+        Workspace& ws_bb = pipelined ? jb.bb : W.bb;
         if (pipelined) {
-            // the FEC job keeps its own copy of the frame table and its result arrays (phase A of the next call reuses ws_rx[2])
-            Workspace& wj = ctx->ws_fecbuf[slot][par][2];
-            if ((rc = wj.ensure(sizeof(S2FrameRef) * nf + sizeof(int) * (n + 1) + sizeof(int32_t) * 2 * nf + 64))) return rc;
-            d_trials = (int32_t*)((char*)wj.p + sizeof(S2FrameRef) * nf + sizeof(int) * (n + 1));
+            // the FEC job keeps its own copy of the frame table and its result arrays (phase A of the next call reuses W.frames)
+            if ((rc = jb.job.ensure(sizeof(S2FrameRef) * nf + sizeof(int) * (n + 1) + sizeof(int32_t) * 2 * nf + 64))) return rc;
+            d_trials = (int32_t*)((char*)jb.job.p + sizeof(S2FrameRef) * nf + sizeof(int) * (n + 1));
             d_corr = d_trials + nf;
-            HIP_TRY(hipMemcpyAsync(wj.p, frames.data(), sizeof(S2FrameRef) * nf, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync((char*)wj.p + sizeof(S2FrameRef) * nf, first.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(jb.job.p, frames.data(), sizeof(S2FrameRef) * nf, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync((char*)jb.job.p + sizeof(S2FrameRef) * nf, first.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, st));
         }
-        if (!staged && (rc = ws_pll.ensure((size_t)nf * raw * sizeof(cf32)))) return rc;
+        if (!staged && (rc = W.pll.ensure((size_t)nf * raw * sizeof(cf32)))) return rc;
         if ((rc = ws_llr.ensure((size_t)nf * N))) return rc;
         if ((rc = ws_bb.ensure((size_t)nf * kb))) return rc;
-        cf32* d_pll = (cf32*)ws_pll.p;
+        cf32* d_pll = (cf32*)W.pll.p;
         int8_t* d_llr = (int8_t*)ws_llr.p;
-        d_bb = (uint8_t*)ws_bb.p;
+        uint8_t* d_bb = (uint8_t*)ws_bb.p;
         HIP_TRY(hipMemcpyAsync(d_frames, frames.data(), sizeof(S2FrameRef) * nf, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_first, first.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, st));
         if (staged) {
@@ -704,9 +825,6 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
                                           mp.pilot_blocks, raw, d_pll, d_stats, st));
         }
         { StageSpan sp(ctx->timers, ST_DEMAP, st); HIP_TRY(s2_demap_launch(CT->dev, mp.rate, mp.shortframe, mp.slots, mp.pilots, raw, d_pll, nf, d_llr, N, st, staged ? d_slot : nullptr, post_prio_wanted(ctx))); }
-        const int force = d0->cfg.force_ldpc_iters > 0;
-        const int mt = force ? d0->cfg.force_ldpc_iters : d0->cfg.max_ldpc_trials;
-        // keep a copy of the demapper output for the tap before LDPC consumes it? LDPC does not modify d_llr.
         if (!pipelined) {
             if ((rc = fec_run(ctx, mp.fec, d_llr, nf, mt, force, d_bb, d_trials, d_corr, st))) return rc;
             HIP_TRY(hipMemcpyAsync(trials.data(), d_trials, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, st));
@@ -729,21 +847,8 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         for (int i = 0; i < n; ++i) { out_bytes[i] = 0; dm[i]->tap_pll = nullptr; dm[i]->tap_llr = nullptr; }
     }
     hm.mark("loops_enqueued");
-    // ---- 7: FIFO remainder to the spare buffer, NCO frequency for the getter
-    std::vector<int> curfill(2 * n);
-    for (int i = 0; i < n; ++i) { curfill[2 * i] = cur[i]; curfill[2 * i + 1] = dm[i]->fifo_fill; }
-    HIP_TRY(hipMemcpyAsync(d_curfill, curfill.data(), sizeof(int) * 2 * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(s2_fifo_compact_launch(d_work, n, d_curfill, st));
-    std::vector<float> nco(n);
-    HIP_TRY(s2_collect_launch(d_work, n, d_nsym, d_nco, st));
-    HIP_TRY(hipMemcpyAsync(nco.data(), d_nco, sizeof(float) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = finish_call(dm, n, cur, d_work, d_curfill, d_nsym, d_nco, st))) return rc;
     hm.mark("frontend_all_done");
-    for (int i = 0; i < n; ++i) {
-        dvbs2gpu_demod* d = dm[i];
-        if (cur[i] > 0) { d->fifo_fill -= cur[i]; d->fifo_cur ^= 1; d->sym_base += cur[i]; }
-        d->nco_freq_host = nco[i];
-    }
     if (!pipelined) {
         for (int i = 0; i < n; ++i) {
             for (int f = first[i]; f < first[i + 1]; ++f) {
@@ -755,69 +860,53 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         }
         return 0;
     }
-    // ---- pipelined: deliver this group's job of the previous call into this call's output buffers, then start this call's job.
-    // Jobs of all groups run in order on the FEC stream; each is followed by its own event, and the delivery (scatter into the
-    // caller's buffers) runs on the front-end stream behind that event, so it never queues behind a later group's decoder.
-    hipStream_t sf = ctx->fec_stream;
+    // ---- pipelined: deliver this group's job of the previous call into this call's output buffers, start this call's job
     // (out_bytes of a pipelined call are written by the deliveries alone, through the batch map: the job a slot holds may belong to other streams of the batch)
-    BatchMap bm_local;
-    if (!bm) {
-        for (int i = 0; i < n; ++i) { bm_local.pos[dm[i]] = i; out_bytes[i] = 0; dm[i]->stats.clear(); }
-        bm_local.d_out = d_out; bm_local.out_bytes = out_bytes; bm_local.out_cap = out_cap;
-        bm = &bm_local;
-    }
-    auto deliver = [&](PendingFec* job) -> int { return deliver_job(ctx, job, st, W[6], *bm); };
-    PendingFec* prev = (PendingFec*)ctx->pending_fec[slot];
-    ctx->pending_fec[slot] = nullptr;
-    std::unique_ptr<PendingFec> prev_guard(prev);
+    SlotHandOver h(ctx, slot, st, W.deliver, gc.bm, true, dm, n, d_out, out_cap, out_bytes);
     // This call's job goes onto the FEC stream BEFORE the previous call's job is delivered: the stream then runs decoder launch after decoder
     // launch with no host in between (delivered first, a headline step left the FEC stream idle for ~5 ms: the scatter, its copies and the
     // synchronisation of the delivery).  The two jobs use the two halves of the double-buffered FEC workspaces and an event each.
     std::unique_ptr<PendingFec> started;
     // (a small job that runs on the group's own stream -- see below -- goes behind the previous job's delivery instead: that delivery ends with a
     //  synchronisation of this very stream)
-    const bool beside = own_ws && st && nf <= ctx->num_cus;
+    const bool beside = gc.own_ws && st && nf <= ctx->num_cus;
     bool prev_delivered = false;
-    if (beside && prev) {
-        if ((rc = deliver(prev))) return rc;
+    if (beside && h.prev) {
+        if ((rc = h.deliver(h.prev.get()))) return rc;
         hm.mark("prev_delivered");
         prev_delivered = true;
     }
     if (nf > 0) {
-        const int par = ctx->fec_parity[slot];
-        Workspace& wj = ctx->ws_fecbuf[slot][par][2];
-        S2FrameRef* j_frames = (S2FrameRef*)wj.p;
-        int* j_first = (int*)((char*)wj.p + sizeof(S2FrameRef) * nf);
-        int32_t* j_trials = (int32_t*)((char*)wj.p + sizeof(S2FrameRef) * nf + sizeof(int) * (n + 1));
+        S2FrameRef* j_frames = (S2FrameRef*)jb.job.p;
+        int* j_first = (int*)((char*)jb.job.p + sizeof(S2FrameRef) * nf);
+        int32_t* j_trials = (int32_t*)((char*)jb.job.p + sizeof(S2FrameRef) * nf + sizeof(int) * (n + 1));
         int32_t* j_corr = j_trials + nf;
+        const int8_t* j_llr = (const int8_t*)jb.llr.p;
+        uint8_t* j_bb = (uint8_t*)jb.bb.p;
         auto job = std::make_unique<PendingFec>();
         job->n = n; job->nf = nf; job->kb = kb;
         job->dm.assign(dm, dm + n);
         job->first = first; job->hstats = hstats; job->frame_bm = frame_bm;
-        job->d_frames = j_frames; job->d_first = j_first; job->d_bb = (const uint8_t*)ctx->ws_fecbuf[slot][par][1].p;
+        job->d_frames = j_frames; job->d_first = j_first; job->d_bb = j_bb;
         job->d_trials = j_trials; job->d_corr = j_corr;
-        const int force = d0->cfg.force_ldpc_iters > 0;
-        const int mt = force ? d0->cfg.force_ldpc_iters : d0->cfg.max_ldpc_trials;
-        job->d_llr = (const int8_t*)ctx->ws_fecbuf[slot][par][0].p; job->N = N; job->rate = mp.rate; job->shortframe = mp.shortframe; job->max_trials = mt; job->force = force; job->slot = slot;
+        job->d_llr = j_llr; job->N = N; job->rate = mp.rate; job->shortframe = mp.shortframe; job->max_trials = mt; job->force = force; job->slot = slot;
         // A group's job that cannot fill the device (fewer decoder workgroups than half the CUs: the groups of a 64-transponder batch -- a
         // handful of workgroups and 4-6 ms of decoder LATENCY each) runs beside the other groups' jobs: on the GROUP's stream, behind its
         // demapper, with the group's own FEC workspaces (the group's next call enqueues its stages a whole front-end pass later, so nothing
         // waits behind the job; more streams would only share the few hardware queues).  Big jobs queue up on the shared FEC stream as
         // before (two persistent decoders would only take turns).
         if (beside) {
-            if ((rc = fec_run(ctx, mp.fec, (const int8_t*)ctx->ws_fecbuf[slot][par][0].p, nf, mt, force, (uint8_t*)ctx->ws_fecbuf[slot][par][1].p, j_trials, j_corr, st,
-                              &ctx->fws_grp[slot])))
-                return rc;
+            if ((rc = fec_run(ctx, mp.fec, j_llr, nf, mt, force, j_bb, j_trials, j_corr, st, &ctx->fws_grp[slot]))) return rc;
             if (!ctx->ev_fec[slot][par]) HIP_TRY(hipEventCreate(&ctx->ev_fec[slot][par]));
             HIP_TRY(hipEventRecord(ctx->ev_fec[slot][par], st));
             job->done = ctx->ev_fec[slot][par];
         } else {
+            hipStream_t sf = ctx->fec_stream;
             std::lock_guard<std::mutex> fl(ctx->fec_mtx);
             HIP_TRY(hipStreamWaitEvent(sf, ev_llr, 0));
             if (!ctx->ev_fec_t0[slot][par]) HIP_TRY(hipEventCreate(&ctx->ev_fec_t0[slot][par]));
             HIP_TRY(hipEventRecord(ctx->ev_fec_t0[slot][par], sf));
-            if ((rc = fec_run(ctx, mp.fec, (const int8_t*)ctx->ws_fecbuf[slot][par][0].p, nf, mt, force, (uint8_t*)ctx->ws_fecbuf[slot][par][1].p, j_trials, j_corr, sf)))
-                return rc;
+            if ((rc = fec_run(ctx, mp.fec, j_llr, nf, mt, force, j_bb, j_trials, j_corr, sf))) return rc;
             if (!ctx->ev_fec[slot][par]) HIP_TRY(hipEventCreate(&ctx->ev_fec[slot][par]));
             HIP_TRY(hipEventRecord(ctx->ev_fec[slot][par], sf));
             job->done = ctx->ev_fec[slot][par];
@@ -827,68 +916,26 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         hm.mark("fec_enqueued");
         started = std::move(job);
     }
-    if (prev && !prev_delivered) {
+    if (h.prev && !prev_delivered) {
         // (asked BEFORE the delivery: had the previous call's FEC job already ended when this call's front end was through?  The delivery itself takes
         //  0.3-0.6 ms with the job long done -- copies, scatter, synchronisation --, which a fixed threshold on the waiting time mistook for "just in time")
-        const bool job_was_done = prev->done && hipEventQuery(prev->done) == hipSuccess;
+        const bool job_was_done = h.prev->done && hipEventQuery(h.prev->done) == hipSuccess;
         const auto t_d0 = std::chrono::steady_clock::now();
-        if ((rc = deliver(prev))) {               // FEC of the previous call (ran during this call's front end)
+        if ((rc = h.deliver(h.prev.get()))) {     // FEC of the previous call (ran during this call's front end)
             // this call's job is already on the device: it stays parked for the next call (or reset) to collect -- dropping it here would free
             // buffers its kernels are still using and lose the call's frames behind the previous job's error
-            if (started && !deliver_now) ctx->pending_fec[slot] = started.release();
+            if (started && !gc.deliver_now) h.park(std::move(started));
             else if (started) (void)hipDeviceSynchronize();     // (a job that would have been collected by this very call: let it end before its buffers go)
             return rc;
         }
         hm.mark("prev_delivered");
-        // Balance of the two streams: did this call have to wait for the previous call's FEC job (the decoder is the critical path: the timing
-        // loop should yield more) or was the job long done (the front end is: it should yield less)?  One step of the priority duty per two
-        // consistent calls; single-group batches only (the groups of a mixed batch share one front-end pass).
-        if (ctx->g_prio_auto && !own_ws && !pre_nsym) {
-            // (the balance belongs to a configuration: what one batch settled at says nothing about the next one's -- a front-end-bound configuration that inherited the
-            //  headline's setting spent part of its steps in the wrong flow)
-            const long long sig = ((long long)n << 32) ^ ((long long)d0->cfg.modcod << 20) ^ ((long long)d0->cfg.shortframes << 19) ^ ((long long)d0->cfg.pilots << 18) ^
-                                  ((long long)(d0->cfg.force_ldpc_iters & 0xff) << 8) ^ (long long)(d0->cfg.max_ldpc_trials & 0xff);
-            const bool sig_changed = sig != ctx->g_prio_sig;
-            // (a new configuration starts at share S2_PRIO_START_DUTY -- from 0 the headline's first four calls ran 55 ms long each, the front end being their critical path, and the
-            //  plugin's mode needed 14 calls to its share of 7; rounds 5-6 started at 2, where the decoder-bound configurations settled then; since the timing recovery's producers
-            //  run above the decoder they settle at 4: headline 4, config 5's stand-in 4, config 2 5, plugin's mode 7)
-            if (sig_changed) { ctx->g_prio_sig = sig; ctx->g_prio_duty = std::min(ctx->g_prio_cap, S2_PRIO_START_DUTY); ctx->g_prio_trend = 0; ctx->g_prio_hold = 0; ctx->g_prio_last_down = 0; }
-            const auto t_d1 = std::chrono::steady_clock::now();
-            const double wait_ms = std::chrono::duration<double, std::milli>(t_d1 - t_d0).count();
-            const double call_ms = std::chrono::duration<double, std::milli>(t_d1 - t_entry).count();
-            // the job just delivered: how long did it run (timing events around it), and how far apart do this batch's calls come?
-            float job_ms = 0.f;
-            const double period_ms = std::chrono::duration<double, std::milli>(t_entry - ctx->fec_last_entry).count();
-            ctx->fec_last_entry = t_entry;
-            const bool timed = prev->t0 && prev->done && hipEventElapsedTime(&job_ms, prev->t0, prev->done) == hipSuccess && period_ms > 0.0 && period_ms < 5000.0;
-            const int verdict = job_was_done ? +1 : (wait_ms > 1.0 + 0.035 * call_ms ? -1 : 0);     // (3.5 %: the headline waits 2.2 % of its call at its best share, 2.9 % in the first calls of a run)
-            // a clear case moves the share at once: the job took less than 0.8 of the call (the front end is the critical path by a wide margin) / the call waited more
-            // than a twentieth of its time for the job; anything else needs two consistent calls
-            const bool clear = verdict > 0 ? (timed && job_ms < 0.8 * call_ms) : (verdict < 0 && wait_ms > 0.05 * call_ms);
-            // (no see-saw: a step down that the very next verdicts take back -- the lower share made the front end the critical path -- is not tried again for 64 calls;
-            //  the headline sat at share 2 with a wait right at the threshold and dipped to 1 every dozen calls, one 380 ms call each time)
-            if (ctx->g_prio_hold > 0) --ctx->g_prio_hold;
-            const bool held = verdict < 0 && ctx->g_prio_hold > 0;
-            if (verdict != 0 && !held && (clear || verdict == ctx->g_prio_trend)) {
-                const int before = ctx->g_prio_duty;
-                ctx->g_prio_duty = std::min(ctx->g_prio_cap, std::max(0, ctx->g_prio_duty + verdict));
-                if (verdict > 0 && ctx->g_prio_last_down > 0 && ctx->g_prio_duty != before) ctx->g_prio_hold = 64;     // (up again right behind a step down)
-                ctx->g_prio_last_down = (verdict < 0 && ctx->g_prio_duty != before) ? 4 : 0;
-                ctx->g_prio_trend = 0;
-            } else {
-                ctx->g_prio_trend = held ? 0 : verdict;
-                if (ctx->g_prio_last_down > 0) --ctx->g_prio_last_down;
-            }
-            if (hm.on) { char b[128]; snprintf(b, sizeof(b), " wait=%.2f call=%.1f duty=%d job=%.1f period=%.1f", wait_ms, call_ms, ctx->g_prio_duty, job_ms, period_ms); hm.line += b; }
-        }
+        // (single-group batches only: the groups of a mixed batch share one front-end pass)
+        if (ctx->g_prio_auto && !gc.own_ws && !gc.pre_nsym) balance_priority(ctx, d0, n, *h.prev, job_was_done, t_entry, t_d0, hm);
     }
     if (started) {
-        if (deliver_now) {
-            // synchronous call with several groups side by side: the job is collected by the call that started it
-            if ((rc = deliver(started.get()))) return rc;
-        } else {
-            ctx->pending_fec[slot] = started.release();
-        }
+        // (synchronous call with several groups side by side: the job is collected by the call that started it)
+        if (gc.deliver_now) return h.deliver(started.get());
+        h.park(std::move(started));
     }
     return 0;
 }
@@ -942,31 +989,20 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
     if ((rc = get_rx_tables(ctx)) || (rc = get_vcm_tables(ctx))) return rc;
     float* d_taps;
     if ((rc = get_rrc(ctx, d0->cfg.rrc_taps, d0->cfg.rrc_alpha, d0->cfg.samplerate / d0->cfg.symbolrate, &d_taps))) return rc;
-    Workspace* const W = ctx->ws_vcm;
-    std::vector<S2StreamWork> work(n);
-    int max_count = 0, maxf = 0;
-    for (int i = 0; i < n; ++i) {
-        dvbs2gpu_demod* d = dm[i];
-        if (counts[i] < 0 || counts[i] > d->max_samples) { last_error() = "count exceeds max_samples"; return DVBS2GPU_ERR_ARG; }
-        work[i].in = d_iq[i]; work[i].count = counts[i]; work[i].fe_out = d->d_fe;
-        work[i].fifo = d->d_fifo[d->fifo_cur]; work[i].fifo_fill = d->fifo_fill; work[i].st = d->d_state;
-        work[i].fifo_next = d->d_fifo[d->fifo_cur ^ 1]; work[i].out = d_out[i]; work[i].spec_out = d->d_spec;
-        max_count = std::max(max_count, counts[i]);
-        maxf = std::max(maxf, d->fifo_cap / VCM_DUMMY_PLFRAME + 2);
-        if (!pipelined) d->stats.clear();
-        d->frame_ptrs.clear(); d->frame_pos.clear(); d->frame_len.clear();
-        d->tap_pll = nullptr; d->tap_llr = nullptr; d->tap_pll_count = 0; d->tap_llr_count = 0; d->tap_pll_stride = 0;
-    }
-    if ((rc = W[0].ensure(sizeof(S2StreamWork) * n + sizeof(int) * (n + 1) + sizeof(int) * 8 * n + sizeof(float) * n + 64))) return rc;
-    S2StreamWork* d_work = (S2StreamWork*)W[0].p;
-    int* d_first = (int*)((char*)W[0].p + sizeof(S2StreamWork) * n);
+    VcmWs& W = ctx->ws_vcm;
+    int max_count, maxf = 0;
+    for (int i = 0; i < n; ++i) maxf = std::max(maxf, dm[i]->fifo_cap / VCM_DUMMY_PLFRAME + 2);
+    if ((rc = W.found.ensure(sizeof(S2VcmFound) * (size_t)n * maxf))) return rc;
+    S2VcmFound* d_found = (S2VcmFound*)W.found.p;
+    // (the frames of a call differ in size: this flow also clears their lengths and the taps' element counts)
+    if ((rc = upload_work(dm, n, d_iq, counts, d_out, CLR_FRAMES | CLR_VCM | (pipelined ? 0 : CLR_STATS), false, W.work,
+                          sizeof(int) * (n + 1) + sizeof(int) * 8 * n + sizeof(float) * n + 64, st, &max_count))) return rc;
+    S2StreamWork* d_work = (S2StreamWork*)W.work.p;
+    int* d_first = (int*)(d_work + n);            // [n + 1]
     int* d_counts = d_first + (n + 1);            // [4n]
     int* d_curfill = d_counts + 4 * n;            // [2n]
     int* d_nsym = d_curfill + 2 * n;              // [n]
     float* d_nco = (float*)(d_nsym + n);          // [n]
-    if ((rc = W[1].ensure(sizeof(S2VcmFound) * (size_t)n * maxf))) return rc;
-    S2VcmFound* d_found = (S2VcmFound*)W[1].p;
-    HIP_TRY(hipMemcpyAsync(d_work, work.data(), sizeof(S2StreamWork) * n, hipMemcpyHostToDevice, st));
     { StageSpan sp(ctx->timers, ST_FRONTEND, st); HIP_TRY(frontend_sliced(ctx, d_work, n, d0->co, st)); }
     { StageSpan sp(ctx->timers, ST_RRC, st); HIP_TRY(s2_rrc_decim_launch(d_work, n, max_count + max_count / 32 + 8, d_taps, d0->cfg.rrc_taps, st)); }
     { StageSpan sp(ctx->timers, ST_PLSYNC, st); HIP_TRY(s2_vcm_walk_launch(d_work, n, ctx->pl, ctx->d_vcm_mods, d0->cfg.sof_threshold, maxf, d_found, d_counts, st)); }
@@ -1024,15 +1060,15 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
     std::vector<int32_t> trials(nf, 0), corr(nf, 0);
     std::unique_ptr<PendingFec> job_started;
     if (nf > 0) {
-        if ((rc = W[2].ensure(sizeof(S2VcmFrame) * nf + sizeof(S2FrameStats) * nf + sizeof(uint8_t*) * nf + sizeof(int) * nf + 64))) return rc;
-        S2VcmFrame* d_frames = (S2VcmFrame*)W[2].p;
+        if ((rc = W.frames.ensure(sizeof(S2VcmFrame) * nf + sizeof(S2FrameStats) * nf + sizeof(uint8_t*) * nf + sizeof(int) * nf + 64))) return rc;
+        S2VcmFrame* d_frames = (S2VcmFrame*)W.frames.p;
         S2FrameStats* d_stats = (S2FrameStats*)(d_frames + nf);
         uint8_t** d_dst = (uint8_t**)(d_stats + nf);
         int* d_idx = (int*)(d_dst + nf);
-        if ((rc = W[3].ensure((size_t)std::max<long long>(pll_off, 1) * sizeof(cf32)))) return rc;
-        if ((rc = W[4].ensure((size_t)std::max<long long>(llr_off, 4)))) return rc;
-        cf32* d_pll = (cf32*)W[3].p;
-        int8_t* d_llr = (int8_t*)W[4].p;
+        if ((rc = W.pll.ensure((size_t)std::max<long long>(pll_off, 1) * sizeof(cf32)))) return rc;
+        if ((rc = W.llr.ensure((size_t)std::max<long long>(llr_off, 4)))) return rc;
+        cf32* d_pll = (cf32*)W.pll.p;
+        int8_t* d_llr = (int8_t*)W.llr.p;
         HIP_TRY(hipMemcpyAsync(d_frames, frames.data(), sizeof(S2VcmFrame) * nf, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_first, first.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_dst, dst.data(), sizeof(uint8_t*) * nf, hipMemcpyHostToDevice, st));
@@ -1054,9 +1090,9 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
         // pipelined: the job's buffers are the slot's double-buffered FEC workspaces (the next call reuses ws_vcm while the job runs):
         // LLR groups | BBFRAME groups | results (trials ++ corrections per part) + the parts' frame index lists + the destination table
         const int par = pipelined ? ctx->fec_parity[slot] : 0;
-        Workspace& ws_gl = pipelined ? ctx->ws_fecbuf[slot][par][0] : W[5];
-        Workspace& ws_gb = pipelined ? ctx->ws_fecbuf[slot][par][1] : W[6];
-        Workspace& ws_gt = pipelined ? ctx->ws_fecbuf[slot][par][2] : W[7];
+        Workspace& ws_gl = pipelined ? ctx->ws_fecbuf[slot][par].llr : W.fec_llr;
+        Workspace& ws_gb = pipelined ? ctx->ws_fecbuf[slot][par].bb : W.fec_bb;
+        Workspace& ws_gt = pipelined ? ctx->ws_fecbuf[slot][par].job : W.fec_res;
         const size_t nall = all_idx.size();
         const size_t res_bytes = (sizeof(int32_t) * 2 * nall + 63) & ~(size_t)63, idx_bytes = (sizeof(int) * nall + 63) & ~(size_t)63;
         if ((rc = ws_gl.ensure(llr_need + 64)) || (rc = ws_gb.ensure(bb_need + 64)) || (rc = ws_gt.ensure(res_bytes + idx_bytes + sizeof(uint8_t*) * nf + 64))) return rc;
@@ -1116,14 +1152,14 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
             J.d_dst = (uint8_t**)((char*)ws_gt.p + res_bytes + idx_bytes);
             J.done = ctx->ev_fec[slot][par];
         } else {
-        std::vector<int32_t> tc(2 * all_idx.size());
-        HIP_TRY(hipMemcpyAsync(tc.data(), ws_gt.p, sizeof(int32_t) * tc.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(hstats.data(), d_stats, sizeof(S2FrameStats) * nf, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (const Out& o : outs) {
-            const std::vector<int>& idx = groups[o.code];
-            for (int k = 0; k < o.cnt; ++k) { trials[idx[k]] = tc[o.to + k]; corr[idx[k]] = tc[o.to + o.cnt + k]; }
-        }
+            std::vector<int32_t> tc(2 * all_idx.size());
+            HIP_TRY(hipMemcpyAsync(tc.data(), ws_gt.p, sizeof(int32_t) * tc.size(), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(hstats.data(), d_stats, sizeof(S2FrameStats) * nf, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (const Out& o : outs) {
+                const std::vector<int>& idx = groups[o.code];
+                for (int k = 0; k < o.cnt; ++k) { trials[idx[k]] = tc[o.to + k]; corr[idx[k]] = tc[o.to + o.cnt + k]; }
+            }
         }
         for (int i = 0; i < n; ++i)
             if (first[i + 1] > first[i]) {
@@ -1132,41 +1168,21 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
                     if (ctx->h_vcm_mods[frames[f].pls].valid == 1) { dm[i]->tap_pll = d_pll + frames[f].pll_off; dm[i]->tap_llr = d_llr + frames[f].llr_off; break; }
             }
     }
-    // ---- FIFO remainder to the spare buffer, NCO frequency for the getter
-    std::vector<int> curfill(2 * n);
-    for (int i = 0; i < n; ++i) { curfill[2 * i] = cnts[4 * i + 1]; curfill[2 * i + 1] = dm[i]->fifo_fill; }
-    HIP_TRY(hipMemcpyAsync(d_curfill, curfill.data(), sizeof(int) * 2 * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(s2_fifo_compact_launch(d_work, n, d_curfill, st));
-    std::vector<float> nco(n);
-    HIP_TRY(s2_collect_launch(d_work, n, d_nsym, d_nco, st));
-    HIP_TRY(hipMemcpyAsync(nco.data(), d_nco, sizeof(float) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<int> cur(n);
+    for (int i = 0; i < n; ++i) cur[i] = cnts[4 * i + 1];
+    if ((rc = finish_call(dm, n, cur, d_work, d_curfill, d_nsym, d_nco, st))) return rc;
     if (pipelined) {
-        for (int i = 0; i < n; ++i) {
-            dvbs2gpu_demod* d = dm[i];
-            const int cur = cnts[4 * i + 1];
-            if (cur > 0) { d->fifo_fill -= cur; d->fifo_cur ^= 1; d->sym_base += cur; }
-            d->nco_freq_host = nco[i];
-        }
         // the job of the previous call of this slot is collected AFTER this call's job has gone onto the FEC stream (process_group does the same)
-        PendingFec* prev = (PendingFec*)ctx->pending_fec[slot];
-        ctx->pending_fec[slot] = nullptr;
-        std::unique_ptr<PendingFec> prev_guard(prev);
-        if (job_started) { job_started->hstats = hstats; ctx->pending_fec[slot] = job_started.release(); }
-        if (prev && (rc = deliver_job(ctx, prev, st, W[8], *bm))) return rc;
-        return 0;
+        if (job_started) job_started->hstats = hstats;
+        SlotHandOver h(ctx, slot, st, W.deliver, bm, true, dm, n, d_out, out_cap, out_bytes);
+        return h.park_and_deliver(std::move(job_started));
     }
-    for (int i = 0; i < n; ++i) {
-        dvbs2gpu_demod* d = dm[i];
-        const int cur = cnts[4 * i + 1];
-        if (cur > 0) { d->fifo_fill -= cur; d->fifo_cur ^= 1; d->sym_base += cur; }
-        d->nco_freq_host = nco[i];
+    for (int i = 0; i < n; ++i)
         for (int f = first[i]; f < first[i + 1]; ++f) {
             S2FrameStats s = hstats[f];
             s.ldpc_trials = trials[f]; s.bch_corr = corr[f];
-            d->stats.push_back(s);
+            dm[i]->stats.push_back(s);
         }
-    }
     return 0;
 }
 
@@ -1176,72 +1192,50 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
 // behind a shared front-end pass.  Here the whole call is ONE stage pipeline: AGC / timing recovery / RRC are MODCOD-independent anyway, and the
 // PL-sync walk, the frame loops (ahead of the PL sync, as for a small bank of one configuration) and the demapper take what they otherwise get as
 // kernel arguments from a per-stream table (S2StreamCfgDev).  The FEC stays one job per LDPC code -- a handful of decoder workgroups each, a few
-// milliseconds of latency: they run side by side on up to four side streams (context option mix_fec_streams) -- and the BBFRAMEs go out through the per-frame
+// milliseconds of latency: they run side by side on up to four side streams (MIX_FEC_STREAMS) -- and the BBFRAMEs go out through the per-frame
 // destination table of the ACM/VCM jobs.  No host thread per group; the streams: the caller's, the front end's two auxiliary ones, the side streams.
 int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf32* const* d_iq, const int* counts, uint8_t* const* d_out,
                   int out_cap, int* out_bytes, hipStream_t st, bool pipelined, const BatchMap* bm) {
     dvbs2gpu_demod* d0 = dm[0];
-    Workspace* const W = ctx->ws_mix;
+    MixWs& W = ctx->ws_mix;
     int rc;
     if ((rc = get_rx_tables(ctx))) return rc;
     float* d_taps;
     if ((rc = get_rrc(ctx, d0->cfg.rrc_taps, d0->cfg.rrc_alpha, d0->cfg.samplerate / d0->cfg.symbolrate, &d_taps))) return rc;
-    const bool loops_ahead = ctx->loops_ahead != 0 && !d0->cfg.pilot_aided && ctx->stage_pipeline_launches <= 0;
-    std::vector<S2StreamWork> work(n);
+    const bool spec_loops = !d0->cfg.pilot_aided && ctx->stage_pipeline_launches <= 0;
     std::vector<S2StreamCfgDev> cfgs(n);
-    int max_count = 0, maxf = 0, raw_max = 0, raw_min = 1 << 30, max_slots = 0;
+    int max_count, maxf = 0, raw_max = 0, raw_min = 1 << 30, max_slots = 0;
     for (int i = 0; i < n; ++i) {
-        dvbs2gpu_demod* d = dm[i];
+        const dvbs2gpu_demod* d = dm[i];
         const ModcodParams& mp = d->mp;
-        if (counts[i] < 0 || counts[i] > d->max_samples) { last_error() = "count exceeds max_samples"; return DVBS2GPU_ERR_ARG; }
-        if (loops_ahead && !d->d_spec) HIP_TRY(hipMalloc((void**)&d->d_spec, sizeof(cf32) * 33282));
         ConstelTables* CT;
         if ((rc = get_constel(ctx, mp, &CT))) return rc;
-        work[i].in = d_iq[i]; work[i].count = counts[i]; work[i].fe_out = d->d_fe;
-        work[i].fifo = d->d_fifo[d->fifo_cur]; work[i].fifo_fill = d->fifo_fill; work[i].st = d->d_state;
-        work[i].fifo_next = d->d_fifo[d->fifo_cur ^ 1]; work[i].out = d_out[i]; work[i].spec_out = d->d_spec;
         S2StreamCfgDev& q = cfgs[i];
         q.con = CT->dev; q.pls_code = d->pls_code; q.slots = mp.slots; q.pilots = mp.pilots; q.pilot_blocks = mp.pilot_blocks; q.plframe = mp.plframe;
         q.rate = mp.rate; q.N = mp.fec.N;
-        max_count = std::max(max_count, counts[i]);
         maxf = std::max(maxf, d->fifo_cap / mp.plframe + 2);
         raw_max = std::max(raw_max, mp.plframe); raw_min = std::min(raw_min, mp.plframe); max_slots = std::max(max_slots, mp.slots);
-        if (!pipelined) d->stats.clear();
-        d->frame_ptrs.clear(); d->frame_pos.clear();
     }
-    if ((rc = W[0].ensure(sizeof(S2StreamWork) * n + sizeof(S2StreamCfgDev) * n + sizeof(int) * 4 * n + sizeof(float) * n + 256))) return rc;
-    S2StreamWork* d_work = (S2StreamWork*)W[0].p;
+    if ((rc = upload_work(dm, n, d_iq, counts, d_out, CLR_FRAMES | (pipelined ? 0 : CLR_STATS), spec_loops, W.work,
+                          sizeof(S2StreamCfgDev) * n + sizeof(int) * 4 * n + sizeof(float) * n + 256, st, &max_count))) return rc;
+    S2StreamWork* d_work = (S2StreamWork*)W.work.p;
     S2StreamCfgDev* d_cfgs = (S2StreamCfgDev*)(d_work + n);
     int* d_nsym = (int*)(d_cfgs + n);              // [n]
     float* d_nco = (float*)(d_nsym + n);           // [n]
     int* d_curfill = (int*)(d_nco + n);            // [2n]
-    HIP_TRY(hipMemcpyAsync(d_work, work.data(), sizeof(S2StreamWork) * n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_cfgs, cfgs.data(), sizeof(S2StreamCfgDev) * n, hipMemcpyHostToDevice, st));
     const size_t nslot = (size_t)n * maxf;
-    if ((rc = W[1].ensure(sizeof(S2VcmFound) * nslot + sizeof(int) * 4 * n + 64))) return rc;
-    S2VcmFound* d_found = (S2VcmFound*)W[1].p;
+    if ((rc = W.found.ensure(sizeof(S2VcmFound) * nslot + sizeof(int) * 4 * n + 64))) return rc;
+    S2VcmFound* d_found = (S2VcmFound*)W.found.p;
     int* d_counts = (int*)(d_found + nslot);
-    if ((rc = W[3].ensure(nslot * raw_max * sizeof(cf32)))) return rc;
-    if ((rc = W[7].ensure(sizeof(S2FrameStats) * nslot + 64))) return rc;
-    cf32* d_pll = (cf32*)W[3].p;
+    if ((rc = W.pll.ensure(nslot * raw_max * sizeof(cf32)))) return rc;
+    if ((rc = W.slot_stats.ensure(sizeof(S2FrameStats) * nslot + 64))) return rc;
+    cf32* d_pll = (cf32*)W.pll.p;
     // ---- front half: the stage pipeline of a small bank, every stage one launch per slice for ALL configurations
     {
-        struct Spans : S2SliceSpans {
-            StageTimers* T; std::unique_ptr<StageSpan> sp[4];
-            void begin(int stage, hipStream_t s) override { sp[stage].reset(new StageSpan(*T, stage == 1 ? ST_RRC : (stage == 2 ? ST_PLSYNC : ST_LOOPS), s)); }
-            void end(int stage, hipStream_t) override { sp[stage].reset(); }
-        } spans;
-        spans.T = &ctx->timers;
-        int launches = std::min(S2_FE_MAX_SLICES, std::max(1, (max_count / 2) / raw_min));
-        if (ctx->stage_pipeline_launches > 0) launches = ctx->stage_pipeline_launches;
-        S2PostStages post{d_taps, d0->cfg.rrc_taps, max_count + max_count / 32 + 8, raw_max, maxf, d_found, d_counts, ctx->pl, S2ConstelDev{}, 0,
-                          0, 0, 0, d_pll, (S2FrameStats*)W[7].p, ctx->timers.on ? &spans : nullptr, launches};
+        Spans spans(&ctx->timers);
+        S2PostStages post = post_stages(ctx, spans, d0, d_taps, max_count, raw_max, raw_min, maxf, d_found, d_counts, d_pll, (S2FrameStats*)W.slot_stats.p, spec_loops);
         post.cfgs = d_cfgs;
-        if (loops_ahead) {
-            constexpr int sym_per_launch = 2700;
-            post.spec = 1;
-            post.loops_launches = std::min(S2_FE_MAX_SLICES, std::max(launches, (max_count / 2) / std::max(sym_per_launch, 1)));
-        }
         StageSpan sp(ctx->timers, ST_FRONTEND, st);
         // (the post stages on a stream of their own in either mode: on the AGC's stream every slice's frame loops queue in front of the AGC slice the
         //  timing recovery waits for next -- 4.3 instead of 2.4 ms per slice)
@@ -1250,7 +1244,7 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     std::vector<S2FrameStats> slot_stats(nslot);
     std::vector<S2VcmFound> found(nslot);
     std::vector<int> cnts(4 * n);
-    HIP_TRY(hipMemcpyAsync(slot_stats.data(), W[7].p, sizeof(S2FrameStats) * nslot, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(slot_stats.data(), W.slot_stats.p, sizeof(S2FrameStats) * nslot, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(cnts.data(), d_counts, sizeof(int) * 4 * n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(found.data(), d_found, sizeof(S2VcmFound) * nslot, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1297,9 +1291,9 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     std::unique_ptr<PendingFec> job;
     if (nf > 0) {
         const int par = pipelined ? ctx->fec_parity[0] : 0;
-        Workspace& ws_gl = pipelined ? ctx->ws_fecbuf[0][par][0] : W[4];
-        Workspace& ws_gb = pipelined ? ctx->ws_fecbuf[0][par][1] : W[5];
-        Workspace& ws_gt = pipelined ? ctx->ws_fecbuf[0][par][2] : W[6];
+        Workspace& ws_gl = pipelined ? ctx->ws_fecbuf[0][par].llr : W.fec_llr;
+        Workspace& ws_gb = pipelined ? ctx->ws_fecbuf[0][par].bb : W.fec_bb;
+        Workspace& ws_gt = pipelined ? ctx->ws_fecbuf[0][par].job : W.fec_res;
         size_t lo = 0, bo = 0, to = 0;
         for (PartH& P : parts) {
             P.lo = lo; P.bo = bo; P.to = to;
@@ -1307,8 +1301,8 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         }
         const size_t res_bytes = (sizeof(int32_t) * to + 63) & ~(size_t)63, idx_bytes = (sizeof(int) * nf + 63) & ~(size_t)63;
         if ((rc = ws_gl.ensure(lo + 64)) || (rc = ws_gb.ensure(bo + 64)) || (rc = ws_gt.ensure(res_bytes + idx_bytes + sizeof(uint8_t*) * nf + 64))) return rc;
-        if ((rc = W[2].ensure(sizeof(int) * nf + sizeof(int8_t*) * nf + 64))) return rc;
-        int8_t** d_llr_of = (int8_t**)W[2].p;
+        if ((rc = W.llr_of.ensure(sizeof(int) * nf + sizeof(int8_t*) * nf + 64))) return rc;
+        int8_t** d_llr_of = (int8_t**)W.llr_of.p;
         int* d_slot = (int*)(d_llr_of + nf);
         int* j_idx = (int*)((char*)ws_gt.p + res_bytes);
         std::vector<int8_t*> llr_of(nf);
@@ -1331,7 +1325,7 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         J.frame_tr.assign(nf, -1); J.frame_co.assign(nf, -1);
         J.d_trials = (const int32_t*)ws_gt.p; J.n_results = to;
         J.d_dst = (uint8_t**)((char*)ws_gt.p + res_bytes + idx_bytes);
-        const int nside = std::min<int>((int)parts.size(), std::min(8, std::max(1, ctx->mix_fec_streams)));
+        const int nside = std::min<int>((int)parts.size(), dvbs2gpu_ctx::MIX_FEC_STREAMS);
         size_t off_idx = 0;
         for (size_t pi = 0; pi < parts.size(); ++pi) {
             const PartH& P = parts[pi];
@@ -1353,31 +1347,11 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         }
         if (pipelined) ctx->fec_parity[0] ^= 1;
     }
-    // ---- FIFO remainder to the spare buffer, NCO frequency for the getter
-    std::vector<int> curfill(2 * n);
-    for (int i = 0; i < n; ++i) { curfill[2 * i] = cur[i]; curfill[2 * i + 1] = dm[i]->fifo_fill; }
-    HIP_TRY(hipMemcpyAsync(d_curfill, curfill.data(), sizeof(int) * 2 * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(s2_fifo_compact_launch(d_work, n, d_curfill, st));
-    std::vector<float> nco(n);
-    HIP_TRY(s2_collect_launch(d_work, n, d_nsym, d_nco, st));
-    HIP_TRY(hipMemcpyAsync(nco.data(), d_nco, sizeof(float) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int i = 0; i < n; ++i) {
-        dvbs2gpu_demod* d = dm[i];
-        if (cur[i] > 0) { d->fifo_fill -= cur[i]; d->fifo_cur ^= 1; d->sym_base += cur[i]; }
-        d->nco_freq_host = nco[i];
-    }
-    BatchMap bm_local;
-    if (!bm) {
-        for (int i = 0; i < n; ++i) { bm_local.pos[dm[i]] = i; out_bytes[i] = 0; dm[i]->stats.clear(); }
-        bm_local.d_out = d_out; bm_local.out_bytes = out_bytes; bm_local.out_cap = out_cap;
-        bm = &bm_local;
-    }
-    if (!pipelined) return job ? deliver_job(ctx, job.get(), st, W[8], *bm) : 0;
-    PendingFec* prev = (PendingFec*)ctx->pending_fec[0];
-    ctx->pending_fec[0] = job.release();
-    std::unique_ptr<PendingFec> prev_guard(prev);
-    return prev ? deliver_job(ctx, prev, st, W[8], *bm) : 0;
+    if ((rc = finish_call(dm, n, cur, d_work, d_curfill, d_nsym, d_nco, st))) return rc;
+    // (synchronous: the job is collected by this call)
+    SlotHandOver h(ctx, 0, st, W.deliver, bm, pipelined, dm, n, d_out, out_cap, out_bytes);
+    if (!pipelined) return job ? h.deliver(job.get()) : 0;
+    return h.park_and_deliver(std::move(job));
 }
 
 // AGC, NCO, Gardner, RRC + decimation do not depend on the MODCOD: for a batch of several configuration groups whose loop
@@ -1390,22 +1364,12 @@ int frontend_prepass(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const 
     dvbs2gpu_demod* d0 = dm[0];
     float* d_taps;
     if ((rc = get_rrc(ctx, d0->cfg.rrc_taps, d0->cfg.rrc_alpha, d0->cfg.samplerate / d0->cfg.symbolrate, &d_taps))) return rc;
-    std::vector<S2StreamWork> work(n);
-    int max_count = 0;
-    for (int i = 0; i < n; ++i) {
-        dvbs2gpu_demod* d = dm[i];
-        if (counts[i] < 0 || counts[i] > d->max_samples) { last_error() = "count exceeds max_samples"; return DVBS2GPU_ERR_ARG; }
-        work[i].in = d_iq[i]; work[i].count = counts[i]; work[i].fe_out = d->d_fe;
-        work[i].fifo = d->d_fifo[d->fifo_cur]; work[i].fifo_fill = d->fifo_fill; work[i].st = d->d_state;
-        work[i].fifo_next = d->d_fifo[d->fifo_cur ^ 1]; work[i].out = d_out[i]; work[i].spec_out = d->d_spec;
-        max_count = std::max(max_count, counts[i]);
-    }
-    Workspace& ws = ctx->ws_rx[7];
-    if ((rc = ws.ensure(sizeof(S2StreamWork) * n + sizeof(int) * n + sizeof(float) * n + 64))) return rc;
+    Workspace& ws = ctx->ws_rx.slot_stats;      // (free: a pre-passed group is never staged)
+    int max_count;
+    if ((rc = upload_work(dm, n, d_iq, counts, d_out, 0, false, ws, sizeof(int) * n + sizeof(float) * n + 64, st, &max_count))) return rc;
     S2StreamWork* d_work = (S2StreamWork*)ws.p;
-    int* d_nsym = (int*)((char*)ws.p + sizeof(S2StreamWork) * n);
+    int* d_nsym = (int*)(d_work + n);
     float* d_nco = (float*)(d_nsym + n);
-    HIP_TRY(hipMemcpyAsync(d_work, work.data(), sizeof(S2StreamWork) * n, hipMemcpyHostToDevice, st));
     { StageSpan sp(ctx->timers, ST_FRONTEND, st); HIP_TRY(frontend_sliced(ctx, d_work, n, d0->co, st)); }
     { StageSpan sp(ctx->timers, ST_RRC, st); HIP_TRY(s2_rrc_decim_launch(d_work, n, max_count + max_count / 32 + 8, d_taps, d0->cfg.rrc_taps, st)); }
     nsym_out->assign(n, 0);
@@ -1422,6 +1386,25 @@ bool same_frontend(const dvbs2gpu_demod* a, const dvbs2gpu_demod* b) {
            a->cfg.rrc_taps == b->cfg.rrc_taps && a->cfg.rrc_alpha == b->cfg.rrc_alpha && a->cfg.samplerate == b->cfg.samplerate &&
            a->cfg.symbolrate == b->cfg.symbolrate;
 }
+
+// one configuration group of a batch: its streams' arguments in the group's order, how it runs, and (groups side by side) how it ended
+struct GroupJob {
+    std::vector<int> idx, gc, gb, gn;
+    std::vector<dvbs2gpu_demod*> g;
+    std::vector<const cf32*> gi;
+    std::vector<uint8_t*> go;
+    GroupCall call;
+    int rc = 0;
+    std::string err;
+    GroupJob(const std::vector<int>& idx_, dvbs2gpu_demod* const* demods, const float* const* d_iq, const int* counts, uint8_t* const* d_out)
+        : idx(idx_), gb(idx_.size(), 0) {
+        for (int k : idx) { g.push_back(demods[k]); gi.push_back((const cf32*)d_iq[k]); gc.push_back(counts[k]); go.push_back(d_out[k]); }
+    }
+    int run(dvbs2gpu_ctx* ctx, int out_cap, hipStream_t st) {
+        return process_group(ctx, g.data(), (int)g.size(), gi.data(), gc.data(), go.data(), out_cap, gb.data(), st, call);
+    }
+    void copy_out(int* out_bytes) const { for (size_t k = 0; k < idx.size(); ++k) out_bytes[idx[k]] = gb[k]; }
+};
 
 }  // namespace
 
@@ -1529,17 +1512,7 @@ static int release_streams(dvbs2gpu_ctx* ctx) {
     HIP_TRY(hipDeviceSynchronize());
     {
         std::lock_guard<std::mutex> l(ctx->mtx);
-        for (auto& kv : ctx->fe_aux) {
-            dvbs2gpu_ctx::FeAux& a = kv.second;
-            if (a.aux) (void)hipStreamDestroy(a.aux);
-            if (a.aux2) (void)hipStreamDestroy(a.aux2);
-            if (a.aux3) (void)hipStreamDestroy(a.aux3);
-            for (hipEvent_t e : a.ev) if (e) (void)hipEventDestroy(e);
-            for (hipEvent_t e : a.ev2) if (e) (void)hipEventDestroy(e);
-            for (hipEvent_t e : a.ev3) if (e) (void)hipEventDestroy(e);
-            for (hipStream_t d : a.dvbs_aux) if (d) (void)hipStreamDestroy(d);
-            for (auto& row : a.dvbs_ev) for (hipEvent_t e : row) if (e) (void)hipEventDestroy(e);
-        }
+        for (auto& kv : ctx->fe_aux) kv.second.release();
         ctx->fe_aux.clear();
     }
     for (hipStream_t& sg : ctx->grp_stream) if (sg) { (void)hipStreamDestroy(sg); sg = nullptr; }
@@ -1622,7 +1595,7 @@ int dvbs2gpu_demod_process_batch(dvbs2gpu_demod* const* demods, int n, const flo
             if (!job) continue;
             ctx->pending_fec[sl] = nullptr;
             std::unique_ptr<PendingFec> guard(job);
-            int rc = deliver_job(ctx, job, st, ctx->ws_rx[6], bmap);
+            int rc = deliver_job(ctx, job, st, ctx->ws_rx.deliver, bmap);
             if (rc) return rc;
         }
         return 0;
@@ -1632,24 +1605,19 @@ int dvbs2gpu_demod_process_batch(dvbs2gpu_demod* const* demods, int n, const flo
         // jobs run on the FEC stream beside the next call's front end and are collected by that call, like those of the CCM groups
         int slot = 0;
         for (const std::vector<int>& idx : groups) {
-            std::vector<dvbs2gpu_demod*> g;
-            std::vector<const cf32*> gi;
-            std::vector<int> gc, gb(idx.size());
-            std::vector<uint8_t*> go;
-            for (int k : idx) { g.push_back(demods[k]); gi.push_back((const cf32*)d_iq[k]); gc.push_back(counts[k]); go.push_back(d_out[k]); }
-            int rc = g[0]->cfg.acm_vcm ? process_vcm_group(ctx, g.data(), (int)g.size(), gi.data(), gc.data(), go.data(), out_cap, gb.data(), st, pipe, slot, pipe ? &bmap : nullptr)
-                                       : process_group(ctx, g.data(), (int)g.size(), gi.data(), gc.data(), go.data(), out_cap, gb.data(), st, pipe, slot, nullptr, false, false, pipe ? &bmap : nullptr);
+            GroupJob J(idx, demods, d_iq, counts, d_out);
+            J.call.pipelined = pipe; J.call.slot = slot; J.call.bm = pipe ? &bmap : nullptr;
+            int rc = J.g[0]->cfg.acm_vcm ? process_vcm_group(ctx, J.g.data(), (int)J.g.size(), J.gi.data(), J.gc.data(), J.go.data(), out_cap, J.gb.data(), st, pipe, slot, J.call.bm)
+                                         : J.run(ctx, out_cap, st);
             if (rc) return rc;
-            if (!pipe) for (size_t k = 0; k < idx.size(); ++k) out_bytes[idx[k]] = gb[k];
+            if (!pipe) J.copy_out(out_bytes);
             ++slot;
         }
         return pipe ? collect_leftovers(slot) : 0;
     }
-    // a small mixed batch with one front-end and loop configuration: ONE stage pipeline for all MODCODs (process_mixed); DVBS2GPU_MIXED_GROUPS=1
-    // keeps round 3's flow (a host thread and a HIP stream per configuration group behind a shared front-end pass), which bigger mixed batches use
+    // a small mixed batch with one front-end and loop configuration: ONE stage pipeline for all MODCODs (process_mixed)
     if (groups.size() > 1 && n <= S2_SMALL_BANK && ctx->stage_pipeline == 1) {
-        const bool by_groups = ctx->mixed_groups != 0;
-        bool one = !by_groups;
+        bool one = true;
         for (int i = 1; one && i < n; ++i) {
             const S2LoopCoefs &x = demods[0]->co, &y = demods[i]->co;
             one = same_frontend(demods[0], demods[i]) && x.pll_alpha == y.pll_alpha && x.pll_beta == y.pll_beta && x.hdr_alpha == y.hdr_alpha && x.hdr_beta == y.hdr_beta &&
@@ -1670,38 +1638,25 @@ int dvbs2gpu_demod_process_batch(dvbs2gpu_demod* const* demods, int n, const flo
         int rc = frontend_prepass(ctx, demods, n, (const cf32* const*)d_iq, counts, d_out, st, &pre_nsym);
         if (rc) return rc;
     }
-    struct GroupJob {
-        std::vector<int> idx, gc, gb, gn;
-        std::vector<dvbs2gpu_demod*> g;
-        std::vector<const cf32*> gi;
-        std::vector<uint8_t*> go;
-        int slot = 0, rc = 0;
-        std::string err;
-    };
     std::list<GroupJob> jobs;
     // (synchronous calls collect each group's FEC job before they return)
     const bool side_by_side = merged && (int)groups.size() <= dvbs2gpu_ctx::MAX_PIPE_GROUPS;
     int group_no = 0;
     for (const std::vector<int>& idx : groups) {
-        std::vector<dvbs2gpu_demod*> g;
-        std::vector<const cf32*> gi;
-        std::vector<int> gc, gb(idx.size()), gn;
-        std::vector<uint8_t*> go;
-        for (int k : idx) {
-            g.push_back(demods[k]); gi.push_back((const cf32*)d_iq[k]); gc.push_back(counts[k]); go.push_back(d_out[k]);
-            if (merged) gn.push_back(pre_nsym[k]);
-        }
+        jobs.emplace_back(idx, demods, d_iq, counts, d_out);
+        GroupJob& J = jobs.back();
+        if (merged) for (int k : idx) J.gn.push_back(pre_nsym[k]);
+        J.call.pre_nsym = merged ? J.gn.data() : nullptr;
+        J.call.bm = pipe ? &bmap : nullptr;
         if (side_by_side) {
-            jobs.emplace_back();
-            GroupJob& J = jobs.back();
-            J.idx = idx; J.g = std::move(g); J.gi = std::move(gi); J.gc = std::move(gc); J.go = std::move(go); J.gn = std::move(gn);
-            J.gb.assign(idx.size(), 0); J.slot = group_no++;
+            J.call.pipelined = true; J.call.slot = group_no++; J.call.own_ws = true; J.call.deliver_now = !pipe;
             continue;
         }
-        int rc = process_group(ctx, g.data(), (int)g.size(), gi.data(), gc.data(), go.data(), out_cap, gb.data(), st, pipe, pipe ? group_no : 0,
-                               merged ? gn.data() : nullptr, false, false, pipe ? &bmap : nullptr);
+        J.call.pipelined = pipe; J.call.slot = pipe ? group_no : 0;
+        int rc = J.run(ctx, out_cap, st);
         if (rc) return rc;
-        if (!pipe) for (size_t k = 0; k < idx.size(); ++k) out_bytes[idx[k]] = gb[k];
+        if (!pipe) J.copy_out(out_bytes);
+        jobs.pop_back();                // (run in order, here)
         ++group_no;
     }
     if (side_by_side) {
@@ -1713,53 +1668,40 @@ int dvbs2gpu_demod_process_batch(dvbs2gpu_demod* const* demods, int n, const flo
         // group, 110 with four queues).  Auxiliary streams other flows of this context left behind (time-sliced front ends on other main
         // streams, the DVB-S receiver's stage streams) are idle now -- one call at a time per context -- and given back first.
         bool need_streams = false;
-        for (GroupJob& J : jobs) need_streams = need_streams || !ctx->grp_stream[J.slot];
+        for (GroupJob& J : jobs) need_streams = need_streams || !ctx->grp_stream[J.call.slot];
         if (need_streams) {
             std::lock_guard<std::mutex> l(ctx->mtx);
             for (auto it = ctx->fe_aux.begin(); it != ctx->fe_aux.end();) {
                 if (it->first == st) { ++it; continue; }
-                dvbs2gpu_ctx::FeAux& a = it->second;
-                if (a.aux) (void)hipStreamDestroy(a.aux);
-                if (a.aux2) (void)hipStreamDestroy(a.aux2);
-                if (a.aux3) (void)hipStreamDestroy(a.aux3);
-                for (hipEvent_t e : a.ev) if (e) (void)hipEventDestroy(e);
-                for (hipEvent_t e : a.ev2) if (e) (void)hipEventDestroy(e);
-                for (hipEvent_t e : a.ev3) if (e) (void)hipEventDestroy(e);
-                for (hipStream_t d : a.dvbs_aux) if (d) (void)hipStreamDestroy(d);
-                for (auto& row : a.dvbs_ev) for (hipEvent_t e : row) if (e) (void)hipEventDestroy(e);
+                it->second.release();
                 it = ctx->fe_aux.erase(it);
             }
         }
         for (GroupJob& J : jobs) {
-            if (!ctx->grp_stream[J.slot]) HIP_TRY(hipStreamCreateWithFlags(&ctx->grp_stream[J.slot], hipStreamNonBlocking));
-            if (!ctx->ev_llr_grp[J.slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_llr_grp[J.slot], hipEventDisableTiming));
+            if (!ctx->grp_stream[J.call.slot]) HIP_TRY(hipStreamCreateWithFlags(&ctx->grp_stream[J.call.slot], hipStreamNonBlocking));
+            if (!ctx->ev_llr_grp[J.call.slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_llr_grp[J.call.slot], hipEventDisableTiming));
         }
+        auto run_on_own_stream = [ctx, out_cap](GroupJob& J) {
+            J.rc = J.run(ctx, out_cap, ctx->grp_stream[J.call.slot]);
+            if (J.rc) J.err = last_error();
+        };
         std::vector<std::thread> th;
         for (GroupJob& J : jobs) {
             if (&J == &jobs.back()) break;            // (the last group runs on the calling thread, below)
             try {
-                th.emplace_back([&J, ctx, out_cap, pipe, merged, &bmap]() {
+                th.emplace_back([&J, ctx, &run_on_own_stream]() {
                     if (hipSetDevice(ctx->device) != hipSuccess) { J.rc = DVBS2GPU_ERR_HIP; J.err = "hipSetDevice"; return; }
-                    J.rc = process_group(ctx, J.g.data(), (int)J.g.size(), J.gi.data(), J.gc.data(), J.go.data(), out_cap, J.gb.data(),
-                                         ctx->grp_stream[J.slot], true, J.slot, merged ? J.gn.data() : nullptr, true, !pipe, pipe ? &bmap : nullptr);
-                    if (J.rc) J.err = last_error();
+                    run_on_own_stream(J);
                 });
             } catch (...) {                           // no thread to be had: run the group here (no exception leaves the C ABI)
-                J.rc = process_group(ctx, J.g.data(), (int)J.g.size(), J.gi.data(), J.gc.data(), J.go.data(), out_cap, J.gb.data(),
-                                     ctx->grp_stream[J.slot], true, J.slot, merged ? J.gn.data() : nullptr, true, !pipe, pipe ? &bmap : nullptr);
-                if (J.rc) J.err = last_error();
+                run_on_own_stream(J);
             }
         }
-        {
-            GroupJob& J = jobs.back();
-            J.rc = process_group(ctx, J.g.data(), (int)J.g.size(), J.gi.data(), J.gc.data(), J.go.data(), out_cap, J.gb.data(),
-                                 ctx->grp_stream[J.slot], true, J.slot, merged ? J.gn.data() : nullptr, true, !pipe, pipe ? &bmap : nullptr);
-            if (J.rc) J.err = last_error();
-        }
+        run_on_own_stream(jobs.back());
         for (auto& t : th) t.join();
         for (GroupJob& J : jobs) {
             if (J.rc) { last_error() = J.err; return J.rc; }
-            if (!pipe) for (size_t k = 0; k < J.idx.size(); ++k) out_bytes[J.idx[k]] = J.gb[k];
+            if (!pipe) J.copy_out(out_bytes);
         }
     }
     return pipe ? collect_leftovers(group_no) : 0;
@@ -1788,7 +1730,7 @@ int dvbs2gpu_demod_process(dvbs2gpu_demod* d, int count, const float* h_iq, uint
         if (d->ctx->pipeline_fec) { last_error() = "ACM/VCM streams run in the synchronous mode (dvbs2gpu_set_pipelined(ctx, 0))"; return DVBS2GPU_ERR_ARG; }
         rc = process_vcm_group(d->ctx, &dd, 1, &in, &count, &dout, cap, &bytes, nullptr);
     } else
-    rc = process_group(d->ctx, &dd, 1, &in, &count, &dout, cap, &bytes, nullptr, false, 0, nullptr, false, false);
+    rc = process_group(d->ctx, &dd, 1, &in, &count, &dout, cap, &bytes, nullptr, GroupCall{});
     if (rc) return rc;
     if (bytes > out_cap) { last_error() = "output buffer too small"; return DVBS2GPU_ERR_CAPACITY; }
     if (bytes) HIP_TRY(hipMemcpy(h_out, d->d_out, bytes, hipMemcpyDeviceToHost));

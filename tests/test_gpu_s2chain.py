@@ -365,32 +365,35 @@ def test_pipelined_call_waits_for_inputs_the_host_is_still_writing_on_the_null_s
 
 def test_mixed_modcod_batch_matches_single(engine):
     """BASELINE config 4 shape: one process_batch call over transponders with DIFFERENT MODCODs (QPSK and 8PSK, normal and short
-    frames): streams are grouped per configuration inside the call; every stream == its own single-stream handle"""
+    frames): streams are grouped per configuration inside the call; every stream == its own single-stream handle.  With one loop setting the
+    batch runs as one stage pipeline (process_mixed); with one stream's loop_bw different, through the per-group flow (a shared front-end pass,
+    then each configuration group on a host thread and HIP stream of its own)"""
     import torch
     specs = [(4, 1, 0), (14, 1, 0), (6, 1, 0), (13, 0, 0), (4, 1, 0), (12, 1, 0), (14, 1, 0), (11, 0, 0)]
-    iqs, ref, dms = [], [], []
-    for s, (modcod, short, pilots) in enumerate(specs):
-        iq, bb, _ = orc.transmit(modcod, short, pilots, nframes=4 if short else 2, seed=700 + s, esn0_db=14.0, cfo=2e-4 * s, timing=0.07 * s,
-                                 phase0=0.05, lead_symbols=200 + 13 * s)
-        iqs.append(iq)
-        cfg = engine.default_cfg(modcod, bool(short), bool(pilots))
-        d = engine.demod(cfg, max_samples=iq.size)
-        ref.append(d.process(iq))
-        d.close()
-        dms.append(engine.demod(engine.default_cfg(modcod, bool(short), bool(pilots)), max_samples=iq.size))
-    tin = [torch.from_numpy(i).cuda() for i in iqs]
-    cap = max(d.info['kbch'] // 8 for d in dms) * 8
-    tout = [torch.zeros(cap, dtype=torch.uint8, device='cuda') for _ in specs]
-    nb = engine.process_batch(dms, tin, tout)
-    total = 0
-    for s, d in enumerate(dms):
-        kb = d.info['kbch'] // 8
-        got = tout[s][:nb[s]].cpu().numpy().reshape(-1, kb)
-        assert np.array_equal(got, ref[s]), (s, specs[s])
-        total += len(got)
-    assert total >= len(specs)             # frames did come out
-    for d in dms:
-        d.close()
+    for loop_bw in ({}, {2: 0.008}):
+        iqs, ref, dms = [], [], []
+        for s, (modcod, short, pilots) in enumerate(specs):
+            iq, bb, _ = orc.transmit(modcod, short, pilots, nframes=4 if short else 2, seed=700 + s, esn0_db=14.0, cfo=2e-4 * s, timing=0.07 * s,
+                                     phase0=0.05, lead_symbols=200 + 13 * s)
+            iqs.append(iq)
+            kw = {'loop_bw': loop_bw[s]} if s in loop_bw else {}
+            d = engine.demod(engine.default_cfg(modcod, bool(short), bool(pilots), **kw), max_samples=iq.size)
+            ref.append(d.process(iq))
+            d.close()
+            dms.append(engine.demod(engine.default_cfg(modcod, bool(short), bool(pilots), **kw), max_samples=iq.size))
+        tin = [torch.from_numpy(i).cuda() for i in iqs]
+        cap = max(d.info['kbch'] // 8 for d in dms) * 8
+        tout = [torch.zeros(cap, dtype=torch.uint8, device='cuda') for _ in specs]
+        nb = engine.process_batch(dms, tin, tout)
+        total = 0
+        for s, d in enumerate(dms):
+            kb = d.info['kbch'] // 8
+            got = tout[s][:nb[s]].cpu().numpy().reshape(-1, kb)
+            assert np.array_equal(got, ref[s]), (loop_bw, s, specs[s])
+            total += len(got)
+        assert total >= len(specs), loop_bw             # frames did come out
+        for d in dms:
+            d.close()
 
 
 def test_mixed_batch_of_all_four_constellations_with_and_without_pilots(engine):
@@ -1053,10 +1056,9 @@ def test_time_sliced_front_end_changes_nothing(engine, pkg):
     assert sum(x.size for x in ref[0] + ref[2] + ref[4]) > 0
     # ... and so do the later stages: with the stage pipeline (default) the RRC decimator, the PL-sync walk and the frame loops run behind
     # every timing-recovery slice, frames in per-stream slots; without it (context option stage_pipeline = 0) after the last slice on frames the host
-    # pooled; stage_loops fixes how many of the slices are followed by a frame-loop launch; stage_post_stream = 0 keeps
-    # them on the AGC's stream instead of a third one
+    # pooled; stage_loops fixes how many of the slices are followed by a frame-loop launch
     for opts in ({'fe_slices': 1}, {'fe_slices': 8}, {'stage_pipeline': 0}, {'stage_pipeline': 0, 'fe_slices': 1}, {'stage_loops': 4},
-                 {'stage_loops': 3, 'fe_slices': 8}, {'stage_loops': 1}, {'stage_post_stream': 0, 'fe_slices': 4}, {'fe_slices': 4}):
+                 {'stage_loops': 3, 'fe_slices': 8}, {'stage_loops': 1}, {'fe_slices': 4}):
         e2 = pkg.Engine(0, options=opts)
         got = run(e2)
         e2.close()
