@@ -295,6 +295,27 @@ int dvbs2gpu_demod_get_frame_positions(dvbs2gpu_demod* d, int64_t* h_out, int ca
  * Returns the element count; copies at most cap elements when h_dst != NULL. */
 int dvbs2gpu_demod_get_tap(dvbs2gpu_demod* d, int which, void* h_dst, int cap);
 
+/* Signal quality per frame (own extension; off by default).  With quality on, every frame the handle's front end
+ * completes gets one record, computed on the device from the frame's PLL output (tap 2).  Its known symbols (|a| = 1) form two runs: the 90
+ * header symbols (SOF + scrambled PLSC; they come from the header demodulator's own phase loop, whose phase is not the payload's) and, with
+ * pilots, the P pilot symbols ((1+j)/sqrt2); K = 90 + P.  Each run gets its own complex gain h_r = sum y conj(a) / count_r.
+ *   esn0_db          10 log10(g^2 / sigma^2), g^2 = (90 |h_hdr|^2 + P |h_pil|^2) / K, sigma^2 = sum over both runs of |y - h_r a|^2 / (K - runs)
+ *   gain             g
+ *   phase            arg h_pil; 0 without pilots (the payload is then referred to |h_hdr| at the PLL's own phase)
+ *   mer_db           ETSI TR 101 290 9.1 over the payload: z = y conj(h) / |h|^2 with h = h_pil (no pilots: |h_hdr|), against the nearest
+ *                    point d of the frame's constellation at unit mean energy, 10 log10(sum |d|^2 / sum |z - d|^2)
+ *   known_symbols    K;  payload_symbols: slots * 90
+ * A dummy PLFRAME (ACM/VCM) has no PLL output: every float is NaN and both counts are 0.
+ * get_quality: one record per dvbs2gpu_demod_get_stats record, in the same order (so in the throughput mode they arrive with their frames,
+ * one call late); 0 records while quality is off -- the setting in force when the frames' front end ran decides.  Returns the record count
+ * and copies at most cap records when h_out != NULL.  Null handles and a negative cap: DVBS2GPU_ERR_ARG. */
+typedef struct dvbs2gpu_frame_quality {
+    float esn0_db, mer_db, gain, phase;
+    int32_t known_symbols, payload_symbols;
+} dvbs2gpu_frame_quality;
+int dvbs2gpu_demod_set_quality(dvbs2gpu_demod* d, int on);
+int dvbs2gpu_demod_get_quality(dvbs2gpu_demod* d, dvbs2gpu_frame_quality* h_out, int cap);
+
 /* ------------------------------------------------------------------ fleet: the transponders of one host over several GPUs
  * The reference runs one independent DVBS2Demod instance per transponder (src/main.cpp:588,595: every plugin instance owns its demodulator and worker thread); nothing is
  * exchanged inside a frame or between streams.  A FLEET is what a C++ plugin host with several GPUs calls: `n` members -- one engine context + one worker thread per entry
@@ -432,6 +453,17 @@ int dvbs2gpu_dvbs_demod_get_stats(dvbs2gpu_dvbs_demod* d, dvbs2gpu_viterbi_stats
  * which 1: 8 floats of loop state (AGC gain, FLL phase/freq, timing phase/freq/offset, Costas phase/freq).  Returns the
  * element count; copies at most cap elements when h_dst != NULL. */
 int dvbs2gpu_dvbs_demod_get_tap(dvbs2gpu_dvbs_demod* d, int stream, int which, void* h_dst, int cap);
+/* Signal quality per stream and call (own extension; off by default), over the symbols after the Costas loop (tap 0):
+ *   esn0_db     blind M2M4: M2 = mean |y|^2, M4 = mean |y|^4, S = sqrt(2 M2^2 - M4), N = M2 - S, 10 log10(S / N); NaN where undefined
+ *   mer_db      QPSK decisions d = A (sgn Re y + j sgn Im y), 10 log10(sum |d|^2 / sum |y - d|^2)
+ *   amplitude   A = mean(|Re y| + |Im y|) / 2;  symbols: how many symbols the call produced
+ * get_quality: h_out [nstreams] of the last call; returns nstreams, or 0 when that call ran with quality off. */
+typedef struct dvbs2gpu_dvbs_quality {
+    float esn0_db, mer_db, amplitude;
+    int32_t symbols;
+} dvbs2gpu_dvbs_quality;
+int dvbs2gpu_dvbs_demod_set_quality(dvbs2gpu_dvbs_demod* d, int on);
+int dvbs2gpu_dvbs_demod_get_quality(dvbs2gpu_dvbs_demod* d, dvbs2gpu_dvbs_quality* h_out);
 
 /* ------------------------------------------------------------------ DVB-S segment receiver: ONE fast DVB-S carrier
  * The DVB-S counterpart of dvbs2gpu_segrx_*: one continuous IQ stream is cut into `nsegments` overlapping segments of `own_symbols`

@@ -19,6 +19,7 @@
 #include <dvbs2gpu.h>
 
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -83,8 +84,14 @@ public:
         cfg.sof_threshold = sof_thresold; cfg.max_ldpc_trials = max_ldpc_trials; cfg.force_ldpc_iters = 0;
         d_handler = handler; d_ctx = ctx;
         check(dvbs2gpu_demod_create(eng->ctx, &cfg, STREAM_BUFFER_SIZE, &h));
+        if (quality_on) check(dvbs2gpu_demod_set_quality(h, 1));
     }
     void reset() { check(dvbs2gpu_demod_reset(need())); }
+    /* per-frame Es/N0 and MER estimates (dvbs2gpu_demod_set_quality; an extension, off by default): esn0_db / mer_db and frameQuality() */
+    void setQualityEstimation(bool on) {
+        quality_on = on;
+        if (h) check(dvbs2gpu_demod_set_quality(h, on ? 1 : 0));
+    }
     void setDemodParams(int modcod, bool shortframes, bool pilots, float sof_thresold, int max_ldpc_trials) {
         check(dvbs2gpu_demod_set_params(need(), modcod, shortframes, pilots, sof_thresold, max_ldpc_trials));   // a bad MODCOD throws, old parameters stay
         cfg.modcod = modcod; cfg.shortframes = shortframes; cfg.pilots = pilots; cfg.sof_threshold = sof_thresold; cfg.max_ldpc_trials = max_ldpc_trials;
@@ -105,6 +112,13 @@ public:
             const dvbs2gpu_frame_stats& s = stats[(size_t)k - 1];
             detected_modcod = s.detected_modcod; detected_shortframes = s.detected_shortframes != 0; detected_pilots = s.detected_pilots != 0;
             pl_sync_best_match = s.pl_sync_best_match; ldpc_trials = (float)s.ldpc_trials; bch_corrections = (float)s.bch_corrections;
+        }
+        const int q = dvbs2gpu_demod_get_quality(h, nullptr, 0);
+        check(q);
+        quality.resize((size_t)q);
+        if (q > 0) {   // one record per frame above; the polled figures from the call's last frame
+            dvbs2gpu_demod_get_quality(h, quality.data(), q);
+            esn0_db = quality[(size_t)q - 1].esn0_db; mer_db = quality[(size_t)q - 1].mer_db;
         }
         if (d_handler && k > 0) {
             // module_dvbs2_demod.cpp:337: the handler is called once per PL frame, with that frame's header + payload (+ pilot) symbols behind the PLL.
@@ -127,6 +141,10 @@ public:
     float pl_sync_best_match = 0;
     float ldpc_trials = -1;
     float bch_corrections = -1;
+    float esn0_db = NAN;      // with setQualityEstimation(true): the last frame's estimates (NaN until then)
+    float mer_db = NAN;
+    /* the quality records of the frames the last process() call completed, one per frame, in frame order */
+    const std::vector<dvbs2gpu_frame_quality>& frameQuality() const { return quality; }
 
 private:
     dvbs2gpu_demod* need() {
@@ -139,6 +157,7 @@ private:
         check(dvbs2gpu_demod_create(eng->ctx, &cfg, STREAM_BUFFER_SIZE, &n));
         dvbs2gpu_demod_destroy(h);
         h = n;
+        if (quality_on) check(dvbs2gpu_demod_set_quality(h, 1));
     }
     void release() {
         if (h) dvbs2gpu_demod_destroy(h);
@@ -151,6 +170,8 @@ private:
     void* d_ctx = nullptr;
     std::vector<complex_t> tap;
     std::vector<dvbs2gpu_frame_stats> stats;
+    std::vector<dvbs2gpu_frame_quality> quality;
+    bool quality_on = false;
 };
 
 struct BBHeader {   // bbframe_ts_parser.h:36-66
@@ -229,6 +250,11 @@ public:
         check(dvbs2gpu_dvbs_demod_reset(need()));
         check(dvbs2gpu_dvbs_tail_reset(t));
     }
+    /* per-call Es/N0 (M2M4) and MER of the symbols after the Costas loop (dvbs2gpu_dvbs_demod_set_quality; an extension, off by default) */
+    void setQualityEstimation(bool on) {
+        quality_on = on;
+        if (h) check(dvbs2gpu_dvbs_demod_set_quality(h, on ? 1 : 0));
+    }
     void setSymbolrate(double symbolrate) { cfg.symbolrate = symbolrate; if (h) { release(); build(); } }
     void setSamplerate(double samplerate) { cfg.samplerate = samplerate; if (h) { release(); build(); } }
 
@@ -249,6 +275,10 @@ public:
             stats_rs_avg = (float)(sum / 8);   // (an integer mean in the reference too: int errors[8])
         }
         stats_deframer_err = std::min(ts[1], ts[2]);
+        dvbs2gpu_dvbs_quality q;
+        const int nq = dvbs2gpu_dvbs_demod_get_quality(h, &q);
+        check(nq);
+        if (nq > 0) { stats_esn0_db = q.esn0_db; stats_mer_db = q.mer_db; }
         if (d_handler) {
             const int ns = dvbs2gpu_dvbs_demod_get_tap(h, 0, 0, nullptr, 0);
             if (ns > 0) {
@@ -265,6 +295,8 @@ public:
     std::string stats_viterbi_rate = "";
     float stats_rs_avg = 0;
     int stats_deframer_err = 0;
+    float stats_esn0_db = NAN;   // with setQualityEstimation(true): the last call's estimates (NaN until then)
+    float stats_mer_db = NAN;
 
 private:
     dvbs2gpu_dvbs_demod* need() {
@@ -275,6 +307,7 @@ private:
         check(dvbs2gpu_dvbs_demod_create(eng->ctx, &cfg, 1, STREAM_BUFFER_SIZE, &h));
         const int rc = dvbs2gpu_dvbs_tail_create(eng->ctx, 1, STREAM_BUFFER_SIZE + 4 * 8192, &t);
         if (rc < 0) { release(); check(rc); }
+        if (quality_on) check(dvbs2gpu_dvbs_demod_set_quality(h, 1));
     }
     void release() {
         if (h) dvbs2gpu_dvbs_demod_destroy(h);
@@ -288,6 +321,7 @@ private:
     void (*d_handler)(complex_t*, int, void*) = nullptr;
     void* d_ctx = nullptr;
     std::vector<complex_t> tap;
+    bool quality_on = false;
 };
 
 }   // namespace dvbs

@@ -57,6 +57,23 @@ class FrameStats(C.Structure):
                 ('bbframe_bytes', C.c_int32)]
 
 
+class FrameQuality(C.Structure):
+    """dvbs2gpu_frame_quality"""
+    _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('gain', C.c_float), ('phase', C.c_float), ('known_symbols', C.c_int32),
+                ('payload_symbols', C.c_int32)]
+
+
+class DvbsQuality(C.Structure):
+    """dvbs2gpu_dvbs_quality"""
+    _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('amplitude', C.c_float), ('symbols', C.c_int32)]
+
+
+def _quality_dtype(st):
+    """numpy structured dtype with the fields of a ctypes record"""
+    import numpy as np
+    return np.dtype([(k, np.float32 if t is C.c_float else np.int32) for k, t in st._fields_])
+
+
 # name -> (restype, argtypes); every symbol declared in include/dvbs2gpu.h
 _vp = C.c_void_p
 _i = C.c_int
@@ -108,6 +125,8 @@ PROTOTYPES = {
     'dvbs2gpu_demod_get_stats': (_i, [_vp, C.POINTER(FrameStats), _i]),
     'dvbs2gpu_demod_get_nco_freq': (C.c_float, [_vp]),
     'dvbs2gpu_demod_get_tap': (_i, [_vp, _i, _vp, _i]),
+    'dvbs2gpu_demod_set_quality': (_i, [_vp, _i]),
+    'dvbs2gpu_demod_get_quality': (_i, [_vp, C.POINTER(FrameQuality), _i]),
     # DVB-S inner code
     'dvbs2gpu_dvbs_slice': (_i, [_vp, _vp, _i, _vp, _vp]),
     'dvbs2gpu_ccdec_create': (_i, [_vp, _i, _i, C.POINTER(_vp)]),
@@ -128,6 +147,8 @@ PROTOTYPES = {
     'dvbs2gpu_dvbs_demod_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i)]),
     'dvbs2gpu_dvbs_demod_get_stats': (_i, [_vp, _vp]),
     'dvbs2gpu_dvbs_demod_get_tap': (_i, [_vp, _i, _i, _vp, _i]),
+    'dvbs2gpu_dvbs_demod_set_quality': (_i, [_vp, _i]),
+    'dvbs2gpu_dvbs_demod_get_quality': (_i, [_vp, C.POINTER(DvbsQuality)]),
     'dvbs2gpu_dvbs_tail_create': (_i, [_vp, _i, _i, C.POINTER(_vp)]),
     'dvbs2gpu_dvbs_tail_reset': (_i, [_vp]),
     'dvbs2gpu_dvbs_tail_destroy': (None, [_vp]),
@@ -581,6 +602,19 @@ class Demod:
     def nco_freq(self):
         return float(self.lib.dvbs2gpu_demod_get_nco_freq(self.h))
 
+    def set_quality(self, on):
+        """per-frame Es/N0 and MER estimates (dvbs2gpu_demod_set_quality; off by default)"""
+        self.eng._check(self.lib.dvbs2gpu_demod_set_quality(self.h, int(bool(on))))
+
+    def quality(self):
+        """numpy structured array, one record per stats() record (esn0_db, mer_db, gain, phase, known_symbols, payload_symbols)"""
+        import numpy as np
+        n = self.eng._check(self.lib.dvbs2gpu_demod_get_quality(self.h, None, 0))
+        a = np.zeros(n, _quality_dtype(FrameQuality))
+        if n:
+            self.eng._check(self.lib.dvbs2gpu_demod_get_quality(self.h, C.cast(a.ctypes.data, C.POINTER(FrameQuality)), n))
+        return a
+
     def tap(self, which):
         import numpy as np
         n = self.eng._check(self.lib.dvbs2gpu_demod_get_tap(self.h, which, None, 0))
@@ -743,6 +777,17 @@ class DvbsDemodBank(_Handle):
         a = np.zeros(8, np.float32)
         self.eng._check(self.lib.dvbs2gpu_dvbs_demod_get_tap(self.h, stream, 1, C.c_void_p(a.ctypes.data), 8))
         return a
+
+    def set_quality(self, on):
+        """per-stream Es/N0 (M2M4) and MER of every call (dvbs2gpu_dvbs_demod_set_quality; off by default)"""
+        self.eng._check(self.lib.dvbs2gpu_dvbs_demod_set_quality(self.h, int(bool(on))))
+
+    def quality(self):
+        """numpy structured array [nstreams] of the last call (esn0_db, mer_db, amplitude, symbols); empty when it ran with quality off"""
+        import numpy as np
+        a = np.zeros(self.nstreams, _quality_dtype(DvbsQuality))
+        n = self.eng._check(self.lib.dvbs2gpu_dvbs_demod_get_quality(self.h, C.cast(a.ctypes.data, C.POINTER(DvbsQuality))))
+        return a[:n]
 
 
 class DvbsTailBank(_Handle):

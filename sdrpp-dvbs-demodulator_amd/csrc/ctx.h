@@ -93,22 +93,23 @@ struct GroupWs {        // a CCM group (process_group)
               found,    // PL-sync frame tables + counts
               frames,   // frame refs + stats + trials + corrections + slot indices
               pll, llr, bb, deliver,
-              slot_stats;   // stage pipeline: per-slot frame stats
-    void release() { for (Workspace* w : {&work, &found, &frames, &pll, &llr, &bb, &deliver, &slot_stats}) w->release(); }
+              slot_stats,   // stage pipeline: per-slot frame stats
+              quality;      // signal-quality descriptors + records (quality.hip)
+    void release() { for (Workspace* w : {&work, &found, &frames, &pll, &llr, &bb, &deliver, &slot_stats, &quality}) w->release(); }
 };
 struct VcmWs {          // a group of ACM/VCM streams (process_vcm_group)
     Workspace work,     // stream-work table + first[] + counts + FIFO cur/fill + symbol counts + NCO
               found, frames /* frames + stats + destinations + index lists */, pll, llr,
               fec_llr, fec_bb, fec_res,     // synchronous FEC parts: LLRs | BBFRAMEs | results + index lists + destinations
-              deliver;
-    void release() { for (Workspace* w : {&work, &found, &frames, &pll, &llr, &fec_llr, &fec_bb, &fec_res, &deliver}) w->release(); }
+              deliver, quality;
+    void release() { for (Workspace* w : {&work, &found, &frames, &pll, &llr, &fec_llr, &fec_bb, &fec_res, &deliver, &quality}) w->release(); }
 };
 struct MixWs {          // a mixed CCM batch (process_mixed)
     Workspace work,     // stream-work table + per-stream configurations + symbol counts + NCO + FIFO cur/fill
               found, llr_of /* per-frame LLR pointers + slot indices */, pll, slot_stats,
               fec_llr, fec_bb, fec_res,     // synchronous FEC parts, as VcmWs
-              deliver;
-    void release() { for (Workspace* w : {&work, &found, &llr_of, &pll, &slot_stats, &fec_llr, &fec_bb, &fec_res, &deliver}) w->release(); }
+              deliver, quality;
+    void release() { for (Workspace* w : {&work, &found, &llr_of, &pll, &slot_stats, &fec_llr, &fec_bb, &fec_res, &deliver, &quality}) w->release(); }
 };
 // the buffers of one pipelined FEC job (per slot and parity): LLRs | BBFRAMEs | frame refs + first[] + results (CCM), results + index lists + destinations (ACM/VCM, mixed)
 struct FecJobBufs { Workspace llr, bb, job; void release() { llr.release(); bb.release(); job.release(); } };

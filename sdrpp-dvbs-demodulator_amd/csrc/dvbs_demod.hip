@@ -29,6 +29,9 @@ struct dvbs2gpu_dvbs_demod {
     cf32* d_bandedge = nullptr;
     float* d_rrc = nullptr;
     std::vector<DvbsStreamState> init_state;
+    int quality = 0;                // dvbs2gpu_dvbs_demod_set_quality
+    DvbsQuality* d_qual = nullptr;  // [nstreams], allocated on first use
+    std::vector<DvbsQuality> qual;  // of the last call (empty: it ran with quality off)
 };
 
 namespace {
@@ -155,6 +158,7 @@ void dvbs2gpu_dvbs_demod_destroy(dvbs2gpu_dvbs_demod* d) {
     if (!d) return;
     (void)hipFree(d->d_state); (void)hipFree(d->d_buf_a); (void)hipFree(d->d_buf_b); (void)hipFree(d->d_sym); (void)hipFree(d->d_soft);
     (void)hipFree(d->d_in); (void)hipFree(d->d_out); (void)hipFree(d->d_ts); (void)hipFree(d->d_vstate); (void)hipFree(d->d_vws); (void)hipFree(d->d_bandedge);
+    (void)hipFree(d->d_qual);
     delete d;
 }
 
@@ -247,6 +251,14 @@ int dvbs2gpu_dvbs_demod_process_batch(dvbs2gpu_dvbs_demod* d, const float* const
     }
     HIP_TRY(dvbs_pack_bits_launch((const uint8_t*)wsb.p, d_nbits, d_nblk, n, mb, (uint8_t* const*)(base + off_ptr_out), cap, d_cnt, st));
     HIP_TRY(dvbs_soft_compact_launch(d_work, n, st));
+    // signal quality over the call's Costas output (quality.hip): one launch for the bank, behind the last Costas slice
+    d->qual.clear();
+    if (d->quality) {
+        if (!d->d_qual) HIP_TRY(hipMalloc((void**)&d->d_qual, sizeof(DvbsQuality) * n));
+        d->qual.resize(n);
+        HIP_TRY(dvbs_quality_launch(d_work, n, d->d_qual, st));
+        HIP_TRY(hipMemcpyAsync(d->qual.data(), d->d_qual, sizeof(DvbsQuality) * n, hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(hipMemcpyAsync(out_counts, d_cnt, sizeof(int) * n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -305,6 +317,20 @@ int dvbs2gpu_dvbs_demod_get_stats(dvbs2gpu_dvbs_demod* d, dvbs2gpu_viterbi_stats
         h_out[i].ber = v[i].ber; h_out[i].state = v[i].state; h_out[i].rate = v[i].rate; h_out[i].phase = v[i].phase; h_out[i].shift = v[i].shift;
     }
     return d->nstreams;
+}
+
+int dvbs2gpu_dvbs_demod_set_quality(dvbs2gpu_dvbs_demod* d, int on) {
+    if (!d) return DVBS2GPU_ERR_ARG;
+    CallGuard guard(d->ctx);
+    d->quality = on ? 1 : 0;
+    return 0;
+}
+
+int dvbs2gpu_dvbs_demod_get_quality(dvbs2gpu_dvbs_demod* d, dvbs2gpu_dvbs_quality* h_out) {
+    if (!d) return DVBS2GPU_ERR_ARG;
+    static_assert(sizeof(dvbs2gpu_dvbs_quality) == sizeof(DvbsQuality), "quality record layout");
+    if (h_out && !d->qual.empty()) memcpy(h_out, d->qual.data(), sizeof(DvbsQuality) * d->qual.size());
+    return (int)d->qual.size();
 }
 
 int dvbs2gpu_dvbs_demod_get_tap(dvbs2gpu_dvbs_demod* d, int stream, int which, void* h_dst, int cap) {

@@ -116,4 +116,27 @@ hipError_t dvbs_pack_bits_launch(const uint8_t* d_bits, const int* d_nbits, cons
 hipError_t dvbs_deinterleave_launch(const uint8_t* d_in, long stream_stride, int nstreams, int nbytes, uint8_t* d_out, uint8_t* d_hist,
                                     hipStream_t st);
 
+// ------------------------------------------------------------------ signal quality (quality.hip)
+struct cf32;
+struct S2VcmMod;
+struct S2ConstelDev;
+struct DvbsStreamWork;
+struct S2QualityDesc {      // one frame: its PLL output (the demapper's input; null: a dummy PLFRAME, which has none) and the PLS code its loops used
+    const cf32* pll;
+    int pls, pad;
+};
+struct S2FrameQuality {     // == dvbs2gpu_frame_quality
+    float esn0_db, mer_db, gain, phase;
+    int known_symbols, payload_symbols;
+};
+struct DvbsQuality {        // == dvbs2gpu_dvbs_quality
+    float esn0_db, mer_db, amplitude;
+    int symbols;
+};
+// one workgroup per frame; d_mods / d_cons: get_vcm_tables (s2_demod.hip); `prio`: the demapper's wave priority request
+hipError_t s2_quality_launch(const S2QualityDesc* d_desc, int nframes, const S2VcmMod* d_mods, const S2ConstelDev* d_cons, const cf32* d_sof,
+                             const cf32* d_plsc, S2FrameQuality* d_out, hipStream_t st, int prio);
+// one workgroup per stream, over the symbols its Costas loop produced in the call
+hipError_t dvbs_quality_launch(const DvbsStreamWork* d_work, int nstreams, DvbsQuality* d_out, hipStream_t st);
+
 }  // namespace s2

@@ -290,6 +290,8 @@ struct dvbs2gpu_demod {
     std::vector<int> frame_len;              // ACM/VCM: PLFRAME length of each frame of the last call (CCM: empty = mp.plframe)
     long long tap_pll_count = -1, tap_llr_count = -1;   // ACM/VCM: element counts of the taps (frames differ in size)
     float nco_freq_host = 0.f;
+    int quality = 0;                         // dvbs2gpu_demod_set_quality
+    std::vector<S2FrameQuality> qual;        // one record per `stats` record (empty while the frames' front end ran with quality off)
 };
 
 namespace {
@@ -363,7 +365,15 @@ struct PendingFec {
     hipEvent_t done = nullptr;          // recorded on the FEC stream behind the job
     hipEvent_t t0 = nullptr;            // ... and in front of it (big CCM jobs: the job's duration, for the priority balancer)
     std::vector<hipEvent_t> done_more;  // (a job whose parts ran on several streams: one event per stream)
+    std::vector<char> qual_on;          // [n] the stream had quality on when the job's front end ran (empty: none had)
+    std::vector<S2FrameQuality> hquality;   // [nf] (frames of streams with quality off: unused)
 };
+
+// the quality records of a stream's frames first..last of a call (or job) go where its stats go
+static void publish_quality(dvbs2gpu_demod* d, const std::vector<char>& on, const std::vector<S2FrameQuality>& rec, int i, int first, int last) {
+    if (on.empty() || !on[i]) return;
+    for (int f = first; f < last; ++f) d->qual.push_back(rec[f]);
+}
 
 // the streams of the whole batch a pipelined call works on: a job is collected into the buffers of whichever of ITS streams are part of this batch
 // -- in any order, in any configuration group; frames of a stream that has left are dropped (collect them with a zero-count call before it leaves)
@@ -410,13 +420,14 @@ static int deliver_job(dvbs2gpu_ctx* ctx, PendingFec* job, hipStream_t st, Works
         for (int i = 0; i < job->n; ++i) {
             if (where[i] < 0) continue;
             dvbs2gpu_demod* d = job->dm[i];
-            d->stats.clear();
+            d->stats.clear(); d->qual.clear();
             for (int f = job->first[i]; f < job->first[i + 1]; ++f) {
                 S2FrameStats s = job->hstats[f];
                 s.best_match = job->frame_bm[i][f - job->first[i]];
                 s.ldpc_trials = res[f]; s.bch_corr = res[job->nf + f]; s.bbframe_bytes = job->kb;
                 d->stats.push_back(s);
             }
+            publish_quality(d, job->qual_on, job->hquality, i, job->first[i], job->first[i + 1]);
         }
         return 0;
     }
@@ -440,13 +451,14 @@ static int deliver_job(dvbs2gpu_ctx* ctx, PendingFec* job, hipStream_t st, Works
     for (int i = 0; i < job->n; ++i) {
         if (where[i] < 0) continue;
         dvbs2gpu_demod* d = job->dm[i];
-        d->stats.clear();
+        d->stats.clear(); d->qual.clear();
         for (int f = job->first[i]; f < job->first[i + 1]; ++f) {
             S2FrameStats s = job->hstats[f];
             s.ldpc_trials = job->frame_tr[f] >= 0 ? res[job->frame_tr[f]] : 0;
             s.bch_corr = job->frame_co[f] >= 0 ? res[job->frame_co[f]] : 0;
             d->stats.push_back(s);
         }
+        publish_quality(d, job->qual_on, job->hquality, i, job->first[i], job->first[i + 1]);
     }
     return 0;
 }
@@ -548,7 +560,7 @@ int upload_work(dvbs2gpu_demod* const* dm, int n, const cf32* const* d_iq, const
         work[i].fifo = d->d_fifo[d->fifo_cur]; work[i].fifo_fill = d->fifo_fill; work[i].st = d->d_state;
         work[i].fifo_next = d->d_fifo[d->fifo_cur ^ 1]; work[i].out = d_out[i]; work[i].spec_out = d->d_spec;
         *max_count = std::max(*max_count, counts[i]);
-        if (clear & CLR_STATS) d->stats.clear();
+        if (clear & CLR_STATS) { d->stats.clear(); d->qual.clear(); }
         if (clear & CLR_FRAMES) { d->frame_ptrs.clear(); d->frame_pos.clear(); }
         if (clear & CLR_VCM) { d->frame_len.clear(); d->tap_pll = nullptr; d->tap_llr = nullptr; d->tap_pll_count = 0; d->tap_llr_count = 0; d->tap_pll_stride = 0; }
     }
@@ -576,6 +588,45 @@ int finish_call(dvbs2gpu_demod* const* dm, int n, const std::vector<int>& cur, c
     }
     return 0;
 }
+
+int get_vcm_tables(dvbs2gpu_ctx* ctx);
+
+// Signal quality of a call (quality.hip): the frames of the streams that asked for it, ONE launch on the call's stream right behind the demapper
+// (their PLL output is what it read).  The records are copied back behind it and are there once the call has synchronised `st` (finish_call).
+struct QualityCall {
+    std::vector<char> on;                    // [n] as the handles were set when this call's front end ran (empty: none was on)
+    std::vector<S2QualityDesc> desc;
+    std::vector<int> frame;                  // pooled frame index of each descriptor
+    std::vector<S2FrameQuality> rec;         // [desc]
+    QualityCall(dvbs2gpu_demod* const* dm, int n) {
+        for (int i = 0; i < n; ++i)
+            if (dm[i]->quality) { on.assign(n, 0); break; }
+        for (int i = 0; i < (int)on.size(); ++i) on[i] = dm[i]->quality != 0;
+    }
+    void add(int stream, int f, const cf32* pll, int pls) {
+        if (on.empty() || !on[stream]) return;
+        desc.push_back(S2QualityDesc{pll, pls, 0});
+        frame.push_back(f);
+    }
+    int launch(dvbs2gpu_ctx* ctx, Workspace& ws, hipStream_t st, int prio) {
+        if (desc.empty()) return 0;
+        int rc;
+        if ((rc = get_vcm_tables(ctx))) return rc;
+        const size_t nd = desc.size(), off = (sizeof(S2QualityDesc) * nd + 63) & ~(size_t)63;
+        if ((rc = ws.ensure(off + sizeof(S2FrameQuality) * nd))) return rc;
+        S2FrameQuality* d_rec = (S2FrameQuality*)((char*)ws.p + off);
+        rec.resize(nd);
+        HIP_TRY(hipMemcpyAsync(ws.p, desc.data(), sizeof(S2QualityDesc) * nd, hipMemcpyHostToDevice, st));
+        HIP_TRY(s2_quality_launch((const S2QualityDesc*)ws.p, (int)nd, ctx->d_vcm_mods, ctx->d_vcm_cons, ctx->pl.sof, ctx->pl.plsc, d_rec, st, prio));
+        HIP_TRY(hipMemcpyAsync(rec.data(), d_rec, sizeof(S2FrameQuality) * nd, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+    std::vector<S2FrameQuality> by_frame(int nf) const {     // (after the synchronisation)
+        std::vector<S2FrameQuality> r(desc.empty() ? 0 : nf);
+        for (size_t k = 0; k < frame.size(); ++k) r[frame[k]] = rec[k];
+        return r;
+    }
+};
 
 // per-stage timers of the stage pipeline
 struct Spans : S2SliceSpans {
@@ -615,7 +666,7 @@ struct SlotHandOver {
     SlotHandOver(dvbs2gpu_ctx* c, int slot_, hipStream_t st_, Workspace& wo_, const BatchMap* bm_, bool take,
                  dvbs2gpu_demod* const* dm, int n, uint8_t* const* d_out, int out_cap, int* out_bytes) : ctx(c), slot(slot_), st(st_), wo(wo_), bm(bm_) {
         if (!bm) {
-            for (int i = 0; i < n; ++i) { bm_local.pos[dm[i]] = i; out_bytes[i] = 0; dm[i]->stats.clear(); }
+            for (int i = 0; i < n; ++i) { bm_local.pos[dm[i]] = i; out_bytes[i] = 0; dm[i]->stats.clear(); dm[i]->qual.clear(); }
             bm_local.d_out = d_out; bm_local.out_bytes = out_bytes; bm_local.out_cap = out_cap;
             bm = &bm_local;
         }
@@ -783,6 +834,7 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     }
     first[n] = (int)frames.size();
     const int nf = (int)frames.size();
+    QualityCall qc(dm, n);
     std::vector<S2FrameStats> hstats(nf);
     std::vector<int32_t> trials(nf), corr(nf);
     const int force = d0->cfg.force_ldpc_iters > 0;
@@ -825,12 +877,14 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
                                           mp.pilot_blocks, raw, d_pll, d_stats, st));
         }
         { StageSpan sp(ctx->timers, ST_DEMAP, st); HIP_TRY(s2_demap_launch(CT->dev, mp.rate, mp.shortframe, mp.slots, mp.pilots, raw, d_pll, nf, d_llr, N, st, staged ? d_slot : nullptr, post_prio_wanted(ctx))); }
+        if (pipelined) HIP_TRY(hipEventRecord(ev_llr, st));      // (the decoder does not wait for the quality estimate)
+        for (int i = 0; i < n; ++i)
+            for (int f = first[i]; f < first[i + 1]; ++f) qc.add(i, f, d_pll + (size_t)(staged ? fslot[f] : f) * raw, d0->pls_code);
+        if ((rc = qc.launch(ctx, W.quality, st, post_prio_wanted(ctx)))) return rc;
         if (!pipelined) {
             if ((rc = fec_run(ctx, mp.fec, d_llr, nf, mt, force, d_bb, d_trials, d_corr, st))) return rc;
             HIP_TRY(hipMemcpyAsync(trials.data(), d_trials, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(corr.data(), d_corr, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, st));
-        } else {
-            HIP_TRY(hipEventRecord(ev_llr, st));
         }
         if (!staged) HIP_TRY(hipMemcpyAsync(hstats.data(), d_stats, sizeof(S2FrameStats) * nf, hipMemcpyDeviceToHost, st));
         for (int i = 0; i < n; ++i) {
@@ -849,6 +903,7 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     hm.mark("loops_enqueued");
     if ((rc = finish_call(dm, n, cur, d_work, d_curfill, d_nsym, d_nco, st))) return rc;
     hm.mark("frontend_all_done");
+    std::vector<S2FrameQuality> qrec = qc.by_frame(nf);
     if (!pipelined) {
         for (int i = 0; i < n; ++i) {
             for (int f = first[i]; f < first[i + 1]; ++f) {
@@ -857,6 +912,7 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
                 s.ldpc_trials = trials[f]; s.bch_corr = corr[f]; s.bbframe_bytes = kb;
                 dm[i]->stats.push_back(s);
             }
+            publish_quality(dm[i], qc.on, qrec, i, first[i], first[i + 1]);
         }
         return 0;
     }
@@ -887,6 +943,7 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         job->n = n; job->nf = nf; job->kb = kb;
         job->dm.assign(dm, dm + n);
         job->first = first; job->hstats = hstats; job->frame_bm = frame_bm;
+        job->qual_on = qc.on; job->hquality = std::move(qrec);
         job->d_frames = j_frames; job->d_first = j_first; job->d_bb = j_bb;
         job->d_trials = j_trials; job->d_corr = j_corr;
         job->d_llr = j_llr; job->N = N; job->rate = mp.rate; job->shortframe = mp.shortframe; job->max_trials = mt; job->force = force; job->slot = slot;
@@ -1056,6 +1113,7 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
     }
     first[n] = (int)frames.size();
     const int nf = (int)frames.size();
+    QualityCall qc(dm, n);
     std::vector<S2FrameStats> hstats(nf);
     std::vector<int32_t> trials(nf, 0), corr(nf, 0);
     std::unique_ptr<PendingFec> job_started;
@@ -1074,6 +1132,8 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
         HIP_TRY(hipMemcpyAsync(d_dst, dst.data(), sizeof(uint8_t*) * nf, hipMemcpyHostToDevice, st));
         { StageSpan sp(ctx->timers, ST_LOOPS, st); HIP_TRY(s2_vcm_loops_launch(d_work, n, d_frames, d_first, d0->co, ctx->pl, ctx->d_vcm_mods, ctx->d_vcm_cons, d_pll, d_stats, st)); }
         { StageSpan sp(ctx->timers, ST_DEMAP, st); HIP_TRY(s2_vcm_demap_launch(d_frames, nf, ctx->d_vcm_mods, ctx->d_vcm_cons, d_pll, d_llr, st)); }
+        for (int f = 0; f < nf; ++f)      // (a dummy PLFRAME has no PLL output; launched behind the LLR gathers below, so that no decoder waits for it)
+            qc.add(frames[f].stream, f, ctx->h_vcm_mods[frames[f].pls].valid == 1 ? d_pll + frames[f].pll_off : nullptr, frames[f].pls);
         const int force = d0->cfg.force_ldpc_iters > 0;
         const int mt = force ? d0->cfg.force_ldpc_iters : d0->cfg.max_ldpc_trials;
         // one FEC job per LDPC code present in the call; group buffers: LLRs | BBFRAMEs | trials + corrections
@@ -1129,6 +1189,7 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
             // the decoders of this call's codes go onto the FEC stream, behind the gathers; the call that follows collects them
             hipStream_t sf = ctx->fec_stream;
             HIP_TRY(hipEventRecord(ctx->ev_llr, st));
+            if ((rc = qc.launch(ctx, W.quality, st, 0))) return rc;
             {
                 std::lock_guard<std::mutex> fl(ctx->fec_mtx);
                 HIP_TRY(hipStreamWaitEvent(sf, ctx->ev_llr, 0));
@@ -1152,6 +1213,7 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
             J.d_dst = (uint8_t**)((char*)ws_gt.p + res_bytes + idx_bytes);
             J.done = ctx->ev_fec[slot][par];
         } else {
+            if ((rc = qc.launch(ctx, W.quality, st, 0))) return rc;
             std::vector<int32_t> tc(2 * all_idx.size());
             HIP_TRY(hipMemcpyAsync(tc.data(), ws_gt.p, sizeof(int32_t) * tc.size(), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(hstats.data(), d_stats, sizeof(S2FrameStats) * nf, hipMemcpyDeviceToHost, st));
@@ -1171,18 +1233,21 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
     std::vector<int> cur(n);
     for (int i = 0; i < n; ++i) cur[i] = cnts[4 * i + 1];
     if ((rc = finish_call(dm, n, cur, d_work, d_curfill, d_nsym, d_nco, st))) return rc;
+    std::vector<S2FrameQuality> qrec = qc.by_frame(nf);
     if (pipelined) {
         // the job of the previous call of this slot is collected AFTER this call's job has gone onto the FEC stream (process_group does the same)
-        if (job_started) job_started->hstats = hstats;
+        if (job_started) { job_started->hstats = hstats; job_started->qual_on = qc.on; job_started->hquality = std::move(qrec); }
         SlotHandOver h(ctx, slot, st, W.deliver, bm, true, dm, n, d_out, out_cap, out_bytes);
         return h.park_and_deliver(std::move(job_started));
     }
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i) {
         for (int f = first[i]; f < first[i + 1]; ++f) {
             S2FrameStats s = hstats[f];
             s.ldpc_trials = trials[f]; s.bch_corr = corr[f];
             dm[i]->stats.push_back(s);
         }
+        publish_quality(dm[i], qc.on, qrec, i, first[i], first[i + 1]);
+    }
     return 0;
 }
 
@@ -1288,6 +1353,7 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     }
     first[n] = (int)fslot.size();
     const int nf = (int)fslot.size();
+    QualityCall qc(dm, n);
     std::unique_ptr<PendingFec> job;
     if (nf > 0) {
         const int par = pipelined ? ctx->fec_parity[0] : 0;
@@ -1317,6 +1383,9 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         { StageSpan sp(ctx->timers, ST_DEMAP, st); HIP_TRY(s2_demap_mixed_launch(d_cfgs, max_slots, maxf, raw_max, d_pll, nf, d_llr_of, st, d_slot)); }
         if (!ctx->ev_llr) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_llr, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(ctx->ev_llr, st));
+        for (int i = 0; i < n; ++i)
+            for (int f = first[i]; f < first[i + 1]; ++f) qc.add(i, f, d_pll + (size_t)fslot[f] * raw_max, cfgs[i].pls_code);
+        if ((rc = qc.launch(ctx, W.quality, st, 0))) return rc;
         // the FEC jobs, side by side
         job.reset(new PendingFec());
         PendingFec& J = *job;
@@ -1348,6 +1417,7 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         if (pipelined) ctx->fec_parity[0] ^= 1;
     }
     if ((rc = finish_call(dm, n, cur, d_work, d_curfill, d_nsym, d_nco, st))) return rc;
+    if (job) { job->qual_on = qc.on; job->hquality = qc.by_frame(nf); }
     // (synchronous: the job is collected by this call)
     SlotHandOver h(ctx, 0, st, W.deliver, bm, pipelined, dm, n, d_out, out_cap, out_bytes);
     if (!pipelined) return job ? h.deliver(job.get()) : 0;
@@ -1584,7 +1654,7 @@ int dvbs2gpu_demod_process_batch(dvbs2gpu_demod* const* demods, int n, const flo
         for (int i = 0; i < n; ++i) {
             if (!bmap.pos.emplace(demods[i], i).second) { last_error() = "a stream appears twice in the batch"; return DVBS2GPU_ERR_ARG; }
             out_bytes[i] = 0;
-            demods[i]->stats.clear();
+            demods[i]->stats.clear(); demods[i]->qual.clear();
         }
         bmap.d_out = d_out; bmap.out_bytes = out_bytes; bmap.out_cap = out_cap;
     }
@@ -1742,6 +1812,21 @@ int dvbs2gpu_demod_get_stats(dvbs2gpu_demod* d, dvbs2gpu_frame_stats* h_out, int
     int n = (int)d->stats.size();
     static_assert(sizeof(dvbs2gpu_frame_stats) == sizeof(S2FrameStats), "stats layout");
     if (h_out) memcpy(h_out, d->stats.data(), sizeof(S2FrameStats) * std::min(n, cap));
+    return n;
+}
+
+int dvbs2gpu_demod_set_quality(dvbs2gpu_demod* d, int on) {
+    if (!d) return DVBS2GPU_ERR_ARG;
+    CallGuard guard(d->ctx);
+    d->quality = on ? 1 : 0;
+    return 0;
+}
+
+int dvbs2gpu_demod_get_quality(dvbs2gpu_demod* d, dvbs2gpu_frame_quality* h_out, int cap) {
+    if (!d || cap < 0) return DVBS2GPU_ERR_ARG;
+    static_assert(sizeof(dvbs2gpu_frame_quality) == sizeof(S2FrameQuality), "quality record layout");
+    const int n = (int)d->qual.size();
+    if (h_out) memcpy(h_out, d->qual.data(), sizeof(S2FrameQuality) * std::min(n, cap));
     return n;
 }
 
