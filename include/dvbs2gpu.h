@@ -559,6 +559,68 @@ int dvbs2gpu_bbts_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, int cnt, uint8_t* 
  * with n_out >= 17 also [15] synched, [16] bytes of the carried partial packet */
 int dvbs2gpu_bbts_get_stats(dvbs2gpu_bbts* b, int stream, int32_t* h_out, int n_out);
 
+/* ------------------------------------------------------------------ BBFRAME -> TS, mode-adaptation mode
+ * What the reference's parser leaves out, for multiple-input-stream (MIS) and ACM/VCM carriers: ISI demultiplexing, ISSY and DNP
+ * fields, null-packet reinsertion, the per-packet CRC-8, and BBFRAMEs whose size differs from frame to frame.  Off by default and
+ * separate from the calls above, which keep the reference's behaviour and their own state whether the mode is on or not.
+ *   Slot: [CRC-8 of the previous UP][187 UP bytes][ISSY: 0, 2 or 3 bytes, present iff ISSYI][DNP: 1 byte iff NPD].
+ *   Frames: header CRC-8, DFL a whole number of bytes that fits the frame, SYNCD < DFL or 65535; others are counted in
+ *     rejected_frames.  Frames with TS/GS != 11 or of an ISI that is not selected are counted in skipped_frames (SIS frames are ISI 0).
+ *   Framing is per frame: the first slot that starts in a frame starts SYNCD/8 bytes into the data field (65535: none does, the
+ *     data field continues one slot), further ones every slot length.  A slot leaves when the byte after it -- the CRC-8 of its
+ *     UP -- has arrived; what is left of a data field (1 .. slot length bytes) is carried to the next frame of the SAME ISI and
+ *     completed only if carried + SYNCD/8 == slot length, else dropped and counted in broken_joins.
+ *   Output per slot: DNP x (47 1F FF 10 + 184 x FF), then 0x47 + the 187 UP bytes; a CRC-8 mismatch sets the packet's
+ *     transport_error_indicator and counts in ts_errs.  ISSY bytes are dropped, the last ISCR is reported.
+ *   ISSY length: cfg.issy_bytes, or (0) from the first ISSY field that starts in a frame of that ISI: top bit 0 -> 2 bytes,
+ *     top bits 10 -> 3 bytes, 11 decides nothing; until then the ISI's frames are dropped and counted in `undecided`.
+ *   Capacity: every output size is computed first; if one exceeds cap the call returns DVBS2GPU_ERR_CAPACITY, no state has
+ *     advanced and needed[] holds the sizes, so the same call can be repeated with larger buffers. */
+typedef struct dvbs2gpu_bbts_ma_cfg {
+    int32_t issy_bytes;      /* 0: from the stream (see above), 2 or 3 */
+    int32_t crc_span;        /* 0: the CRC-8 covers the 187 UP bytes; 1: every byte of the slot after its first */
+    int32_t reinsert_nulls;  /* 0: DNP is ignored */
+    int32_t check_crc;       /* 0: no CRC-8 check, no transport_error_indicator */
+} dvbs2gpu_bbts_ma_cfg;
+typedef struct dvbs2gpu_bbts_ma_stats {
+    int64_t packets, nulls, ts_errs;     /* user packets emitted, null packets put back, packets that left with TEI set */
+    int32_t broken_joins, undecided, frames;   /* per selected ISI; frames = frames of this ISI parsed or dropped as undecided */
+    int32_t skipped_frames, rejected_frames;   /* per stream (the same for all its slots) */
+    int32_t issy_bytes;                  /* ISSY length in use, 0 while not known */
+    int32_t iscr_valid;  uint32_t last_iscr;   /* last ISCR seen: 15 bits (short) or 22 bits (long) */
+    int32_t carried;                     /* bytes of the partial (or held whole) slot waiting for the next frame of this ISI */
+    int32_t selected, isi;               /* is this slot in use, and for which ISI (-1: none) */
+    int32_t reserved;
+} dvbs2gpu_bbts_ma_stats;
+void dvbs2gpu_bbts_ma_default_cfg(dvbs2gpu_bbts_ma_cfg* cfg);            /* {0, 0, 1, 1} */
+/* out4 = {offset of the CRC-8, offset and length of the UP, offset of the ISSY field} inside a slot, as compiled in */
+int dvbs2gpu_bbts_ma_get_layout(int32_t* out4);
+/* a bank of one stream without a device: only the mode-adaptation calls that take host buffers work on it (ma_work, ma_flush,
+ * select_isi, the statistics); everything runs in the library's host parser, which follows the same rules as the kernels */
+int dvbs2gpu_bbts_create_host(int kbch_bits, int max_frames, dvbs2gpu_bbts** out);
+/* cfg != NULL: mode on, every stream starts afresh with ISI 0 selected.  NULL: mode off; the reference-mode parser then continues
+ * like a freshly created bank. */
+int dvbs2gpu_bbts_set_mode_adaptation(dvbs2gpu_bbts* b, const dvbs2gpu_bbts_ma_cfg* cfg);
+/* the ISIs of `stream` to deliver, n <= 8: slot k of the stream's outputs and statistics is isi[k].  The stream's slots start afresh. */
+int dvbs2gpu_bbts_select_isi(dvbs2gpu_bbts* b, int stream, const uint8_t* isi, int n);
+/* d_bb[i]: DEVICE pointer to nframes[i] (<= max_frames) BBFRAMEs back to back; frame_bytes NULL or frame_bytes[i] NULL: each is
+ * kbch/8 bytes (CCM), else frame_bytes[i][f] is the size of frame f (10 .. 7274: dvbs2gpu_frame_stats.bbframe_bytes of an ACM/VCM
+ * handle, zeros left out).  d_out[i*8 + k]: DEVICE buffer of cap bytes for slot k of stream i (unused slots may be NULL);
+ * out_bytes[i*8 + k] and needed[i*8 + k] (host; needed may be NULL).  Synchronous on `stream`. */
+int dvbs2gpu_bbts_process_ma_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb, const int* const* frame_bytes, const int* nframes,
+                                   uint8_t* const* d_out, int cap, int* out_bytes, int* needed, void* stream);
+/* the same for a bank of one stream and host buffers: h_out[8], out_bytes[8], needed[8] or NULL.  Returns 0 or a negative error. */
+int dvbs2gpu_bbts_ma_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, const int* frame_bytes, int cnt, uint8_t* const* h_out, int cap,
+                          int* out_bytes, int* needed);
+/* end of input: a whole slot held back because the CRC-8 after it has not arrived leaves unchecked, with its null packets.
+ * out[i*8 + k]: cap bytes each, DEVICE buffers (host buffers for a host bank); out_bytes[nstreams*8]. */
+int dvbs2gpu_bbts_ma_flush(dvbs2gpu_bbts* b, uint8_t* const* out, int cap, int* out_bytes);
+/* the same with HOST buffers for any bank (the companion of dvbs2gpu_bbts_ma_work) */
+int dvbs2gpu_bbts_ma_flush_host(dvbs2gpu_bbts* b, uint8_t* const* h_out, int cap, int* out_bytes);
+int dvbs2gpu_bbts_ma_get_stats(dvbs2gpu_bbts* b, int stream, int slot, dvbs2gpu_bbts_ma_stats* h_out);
+/* mask8: bit i of the 256-bit mask = a frame with a valid header and ISI i has been seen on `stream` since the mode was set */
+int dvbs2gpu_bbts_get_isi_seen(dvbs2gpu_bbts* b, int stream, uint32_t* mask8);
+
 #ifdef __cplusplus
 }
 #endif

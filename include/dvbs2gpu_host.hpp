@@ -209,6 +209,38 @@ public:
         return n;
     }
 
+    /* ---- mode-adaptation mode (include/dvbs2gpu.h): multistream and ACM/VCM carriers.  Call after setFrameSize(); cfg == nullptr
+     * switches it off again.  The reference-shaped work() above is not affected by it. */
+    void setModeAdaptation(const dvbs2gpu_bbts_ma_cfg* cfg) {
+        if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
+        check(dvbs2gpu_bbts_set_mode_adaptation(h, cfg));
+    }
+    /* the ISIs to deliver (at most 8): output k of the work() below is isi[k] */
+    void selectISI(const uint8_t* isi, int n) {
+        if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
+        check(dvbs2gpu_bbts_select_isi(h, 0, isi, n));
+    }
+    /* cnt BBFRAMEs back to back, frame_bytes[f] bytes each (nullptr: the size given to setFrameSize); tsframes[k] receives the
+     * TS of the k-th selected ISI, out_bytes[k] its size (8 entries each; unused outputs may be nullptr).  Returns false, with the sizes
+     * in needed[8] and nothing consumed, when buffer_outsize is too small for one of them: call again with larger buffers. */
+    bool work(uint8_t* bbframes, const int* frame_bytes, int cnt, uint8_t* const* tsframes, int buffer_outsize, int* out_bytes, int* needed = nullptr) {
+        if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
+        const int rc = dvbs2gpu_bbts_ma_work(h, bbframes, frame_bytes, cnt, tsframes, buffer_outsize, out_bytes, needed);
+        if (rc == DVBS2GPU_ERR_CAPACITY) return false;
+        check(rc);
+        return true;
+    }
+    /* end of the stream: the packets held back for the CRC-8 that follows them */
+    void flush(uint8_t* const* tsframes, int buffer_outsize, int* out_bytes) {
+        if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
+        check(dvbs2gpu_bbts_ma_flush_host(h, tsframes, buffer_outsize, out_bytes));
+    }
+    dvbs2gpu_bbts_ma_stats modeAdaptationStats(int output) {
+        dvbs2gpu_bbts_ma_stats s;
+        check(dvbs2gpu_bbts_ma_get_stats(h, 0, output, &s));
+        return s;
+    }
+
     BBHeader last_header;
     bool last_gse_crc_err = 0;
     int last_bb_cnt = 0;

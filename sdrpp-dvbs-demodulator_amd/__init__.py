@@ -57,6 +57,19 @@ class FrameStats(C.Structure):
                 ('bbframe_bytes', C.c_int32)]
 
 
+class BbtsMaCfg(C.Structure):
+    """dvbs2gpu_bbts_ma_cfg"""
+    _fields_ = [('issy_bytes', C.c_int32), ('crc_span', C.c_int32), ('reinsert_nulls', C.c_int32), ('check_crc', C.c_int32)]
+
+
+class BbtsMaStats(C.Structure):
+    """dvbs2gpu_bbts_ma_stats"""
+    _fields_ = [('packets', C.c_int64), ('nulls', C.c_int64), ('ts_errs', C.c_int64), ('broken_joins', C.c_int32), ('undecided', C.c_int32),
+                ('frames', C.c_int32), ('skipped_frames', C.c_int32), ('rejected_frames', C.c_int32), ('issy_bytes', C.c_int32),
+                ('iscr_valid', C.c_int32), ('last_iscr', C.c_uint32), ('carried', C.c_int32), ('selected', C.c_int32), ('isi', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
 class FrameQuality(C.Structure):
     """dvbs2gpu_frame_quality"""
     _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('gain', C.c_float), ('phase', C.c_float), ('known_symbols', C.c_int32),
@@ -178,6 +191,18 @@ PROTOTYPES = {
     'dvbs2gpu_bbts_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i), _vp]),
     'dvbs2gpu_bbts_work': (_i, [_vp, _vp, _i, _vp, _i]),
     'dvbs2gpu_bbts_get_stats': (_i, [_vp, _i, C.POINTER(C.c_int32), _i]),
+    'dvbs2gpu_bbts_ma_default_cfg': (None, [C.POINTER(BbtsMaCfg)]),
+    'dvbs2gpu_bbts_ma_get_layout': (_i, [C.POINTER(C.c_int32)]),
+    'dvbs2gpu_bbts_create_host': (_i, [_i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_bbts_set_mode_adaptation': (_i, [_vp, C.POINTER(BbtsMaCfg)]),
+    'dvbs2gpu_bbts_select_isi': (_i, [_vp, _i, C.POINTER(C.c_uint8), _i]),
+    'dvbs2gpu_bbts_process_ma_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(C.POINTER(_i)), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i),
+                                            C.POINTER(_i), _vp]),
+    'dvbs2gpu_bbts_ma_work': (_i, [_vp, _vp, C.POINTER(_i), _i, C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i)]),
+    'dvbs2gpu_bbts_ma_flush': (_i, [_vp, C.POINTER(_vp), _i, C.POINTER(_i)]),
+    'dvbs2gpu_bbts_ma_flush_host': (_i, [_vp, C.POINTER(_vp), _i, C.POINTER(_i)]),
+    'dvbs2gpu_bbts_ma_get_stats': (_i, [_vp, _i, _i, C.POINTER(BbtsMaStats)]),
+    'dvbs2gpu_bbts_get_isi_seen': (_i, [_vp, _i, C.POINTER(C.c_uint32)]),
 }
 
 _lib = None
@@ -881,6 +906,123 @@ class BbTsParserBank(_Handle):
         d = {k: a[i] for i, k in enumerate(self.HEADER_FIELDS)}
         d.update(last_gse_crc_err=a[11], last_bb_cnt=a[12], last_bb_proc=a[13], last_ts_errs=a[14], synched=a[15], count=a[16])
         return d
+
+    # ---- mode-adaptation mode (include/dvbs2gpu.h): ISI demultiplexing, ISSY / DNP, null-packet reinsertion, CRC-8, per-frame sizes
+    MA_SLOTS = 8
+
+    @classmethod
+    def host(cls, kbch_bits=58192, max_frames=64):
+        """a one-stream bank without a device: the library's host parser behind ma_work / ma_flush"""
+        self = cls.__new__(cls)
+        self.eng, self.lib, self.nstreams, self.kbch, self.max_frames = None, load_library(), 1, kbch_bits, max_frames
+        h = C.c_void_p()
+        self._check(self.lib.dvbs2gpu_bbts_create_host(kbch_bits, max_frames, C.byref(h)))
+        self.h = h
+        return self
+
+    def _check(self, rc):
+        if rc < 0:
+            raise Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+        return rc
+
+    def set_mode_adaptation(self, on=True, **kw):
+        """on: issy_bytes (0 auto, 2, 3), crc_span, reinsert_nulls, check_crc as keywords; off: back to a fresh reference-mode bank"""
+        if not on:
+            return self._check(self.lib.dvbs2gpu_bbts_set_mode_adaptation(self.h, None))
+        cfg = BbtsMaCfg()
+        self.lib.dvbs2gpu_bbts_ma_default_cfg(C.byref(cfg))
+        for k, v in kw.items():
+            if k not in dict(BbtsMaCfg._fields_):
+                raise TypeError(k)
+            setattr(cfg, k, int(v))
+        self._check(self.lib.dvbs2gpu_bbts_set_mode_adaptation(self.h, C.byref(cfg)))
+
+    def select_isi(self, stream, isis):
+        a = (C.c_uint8 * max(len(isis), 1))(*[int(x) for x in isis])
+        self._check(self.lib.dvbs2gpu_bbts_select_isi(self.h, int(stream), a, len(isis)))
+
+    def _sizes(self, frame_bytes, n):
+        if frame_bytes is None:
+            return None, None
+        keep = [(C.c_int * max(len(x), 1))(*[int(v) for v in x]) if x is not None else None for x in frame_bytes]
+        ptrs = (C.POINTER(C.c_int) * n)(*[C.cast(k, C.POINTER(C.c_int)) if k is not None else C.POINTER(C.c_int)() for k in keep])
+        return ptrs, keep
+
+    def process_ma(self, bb_tensors, out_tensors, frame_bytes=None, nframes=None):
+        """bb_tensors[i]: uint8 CUDA, the BBFRAMEs of stream i back to back; frame_bytes[i]: their sizes (None: kbch/8 each);
+        out_tensors[i][k]: uint8 CUDA buffer of slot k of stream i (a list per stream, at least as many as ISIs selected).
+        -> byte counts [nstreams][8].  Dvbs2GpuError -5 carries .needed when a buffer is too small (nothing has advanced then)."""
+        n, S = self.nstreams, self.MA_SLOTS
+        pin = (C.c_void_p * n)(*[t.data_ptr() for t in bb_tensors])
+        if nframes is None:
+            nframes = [len(frame_bytes[i]) if frame_bytes is not None and frame_bytes[i] is not None else int(bb_tensors[i].numel()) // (self.kbch // 8)
+                       for i in range(n)]
+        cnt = (C.c_int * n)(*[int(x) for x in nframes])
+        flat = [None] * (n * S)
+        for i, row in enumerate(out_tensors):
+            flat[i * S:i * S + len(row)] = list(row)
+        pout = (C.c_void_p * (n * S))(*[t.data_ptr() if t is not None else None for t in flat])
+        cap = min([int(t.numel()) for t in flat if t is not None] or [0])
+        nb, need = (C.c_int * (n * S))(), (C.c_int * (n * S))()
+        sizes, _keep = self._sizes(frame_bytes, n)
+        rc = self.lib.dvbs2gpu_bbts_process_ma_batch(self.h, pin, sizes, cnt, pout, cap, nb, need, self.eng._stream())
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            e.needed = [list(need[i * S:(i + 1) * S]) for i in range(n)]
+            raise e
+        return [list(nb[i * S:(i + 1) * S]) for i in range(n)]
+
+    def process_ma_from_demods(self, demods, bb_tensors, out_tensors):
+        """the BBFRAMEs an Engine.process_batch call left in bb_tensors (device), stream i of this bank = demods[i]: the sizes come
+        from the handles' per-frame statistics (ACM/VCM: bbframe_bytes, dummy frames left out), the bytes stay where they are"""
+        sizes = [[st.bbframe_bytes for st in d.stats() if st.bbframe_bytes] for d in demods]
+        return self.process_ma(bb_tensors, out_tensors, frame_bytes=sizes)
+
+    def ma_work(self, frames, cap=1 << 20):
+        """one stream, host buffers: frames = list of numpy uint8 BBFRAMEs (any sizes) -> list of 8 numpy arrays (TS per slot)"""
+        import numpy as np
+        S = self.MA_SLOTS
+        bb = np.ascontiguousarray(np.concatenate([np.asarray(f, np.uint8).reshape(-1) for f in frames]) if len(frames) else np.zeros(0, np.uint8))
+        sizes = (C.c_int * max(len(frames), 1))(*[int(np.asarray(f).size) for f in frames])
+        outs = [np.zeros(max(cap, 1), np.uint8) for _ in range(S)]
+        pout = (C.c_void_p * S)(*[o.ctypes.data for o in outs])
+        nb, need = (C.c_int * S)(), (C.c_int * S)()
+        rc = self.lib.dvbs2gpu_bbts_ma_work(self.h, C.c_void_p(bb.ctypes.data), sizes, len(frames), pout, cap, nb, need)
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            e.needed = list(need)
+            raise e
+        return [outs[k][:nb[k]].copy() for k in range(S)]
+
+    def ma_flush(self, cap=256 * 188):
+        """-> [nstreams][8] numpy arrays: the packets that were held back for the CRC-8 after them"""
+        import numpy as np
+        n, S = self.nstreams, self.MA_SLOTS
+        nb = (C.c_int * (n * S))()
+        if self.eng is None:
+            outs = [np.zeros(cap, np.uint8) for _ in range(n * S)]
+            pout = (C.c_void_p * (n * S))(*[o.ctypes.data for o in outs])
+            self._check(self.lib.dvbs2gpu_bbts_ma_flush(self.h, pout, cap, nb))
+            res = [outs[i][:nb[i]].copy() for i in range(n * S)]
+        else:
+            import torch
+            buf = torch.zeros((n * S, cap), dtype=torch.uint8, device='cuda')
+            pout = (C.c_void_p * (n * S))(*[buf[i].data_ptr() for i in range(n * S)])
+            self._check(self.lib.dvbs2gpu_bbts_ma_flush(self.h, pout, cap, nb))
+            host = buf.cpu().numpy()
+            res = [host[i, :nb[i]].copy() for i in range(n * S)]
+        return [res[i * S:(i + 1) * S] for i in range(n)]
+
+    def ma_stats(self, stream=0, slot=0):
+        st = BbtsMaStats()
+        self._check(self.lib.dvbs2gpu_bbts_ma_get_stats(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in BbtsMaStats._fields_ if k != 'reserved'}
+
+    def isi_seen(self, stream=0):
+        """-> sorted list of the ISIs seen on `stream` since the mode was switched on"""
+        m = (C.c_uint32 * 8)()
+        self._check(self.lib.dvbs2gpu_bbts_get_isi_seen(self.h, int(stream), m))
+        return [i for i in range(256) if m[i >> 5] >> (i & 31) & 1]
 
 
 class SegmentReceiver(_Handle):

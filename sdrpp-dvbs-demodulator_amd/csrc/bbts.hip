@@ -12,6 +12,7 @@
 // that carries one in a call is handed, for that call, to the native host parser below (BbtsHostParser), which shares
 // the synchronisation state with the device path.
 #include "ctx.h"
+#include "bbts_common.h"
 
 #include <memory>
 
@@ -34,37 +35,6 @@ struct BbtsFrameDesc {
 struct BbtsStreamPlan {
     int needs_host, out_bytes, fin_len, fin_src;       // fin_src < 0: keep the state buffer's bytes
 };
-
-// check_crc8 (bbframe_ts_parser.cpp:70-83): LSB-first register, polynomial 0xAB (reflected 0xD5), over `nbits` MSB-first bits
-__host__ __device__ inline unsigned crc8_bits(const uint8_t* in, int nbits) {
-    unsigned crc = 0;
-    for (int n = 0; n < nbits; ++n) {
-        unsigned fb = ((in[n >> 3] >> (7 - (n & 7))) ^ crc) & 1u;
-        crc >>= 1;
-        if (fb) crc ^= 0xAB;
-    }
-    return crc;
-}
-struct HeaderFields { int v[11]; };
-__host__ __device__ inline HeaderFields parse_bbheader(const uint8_t* b) {
-    HeaderFields h;
-    h.v[0] = b[0] >> 6; h.v[1] = (b[0] >> 5) & 1; h.v[2] = (b[0] >> 4) & 1; h.v[3] = (b[0] >> 3) & 1; h.v[4] = (b[0] >> 2) & 1;
-    h.v[5] = b[0] & 3;
-    h.v[6] = h.v[1] == 0 ? b[1] : 0;
-    h.v[7] = b[2] << 8 | b[3];
-    h.v[8] = b[4] << 8 | b[5];
-    h.v[9] = b[6];
-    h.v[10] = b[7] << 8 | b[8];
-    return h;
-}
-// header validation of work() (.cpp:119-152): true when the frame is parsed at all
-__host__ __device__ inline bool header_ok(const uint8_t* frame, int max_dfl, HeaderFields* h) {
-    if (crc8_bits(frame, 80) != 0) return false;
-    *h = parse_bbheader(frame);
-    const int dfl = h->v[8], syncd = h->v[10];
-    if ((unsigned)dfl > (unsigned)max_dfl || syncd >= dfl - 8) return false;
-    return dfl % 8 == 0;
-}
 
 __global__ void bbts_plan_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nframes, int nstreams, int fbytes, int max_dfl,
                                  int max_frames, BbtsDevState* __restrict__ state, BbtsFrameDesc* __restrict__ desc,
@@ -341,19 +311,37 @@ struct dvbs2gpu_bbts {
     std::vector<std::unique_ptr<BbtsHostParser>> host;
     std::vector<BbtsStreamPlan> h_plan;
     std::vector<uint8_t> h_in, h_out;
+    BbtsMa* ma = nullptr;                      // mode-adaptation mode (bbts_ma.hip); null while the mode is off
 };
+
+namespace s2 {
+BbtsBankView bbts_view(dvbs2gpu_bbts* b) { return {b->ctx, b->nstreams, b->kbch, b->max_frames, &b->ma}; }
+dvbs2gpu_bbts* bbts_new_host_bank(int kbch_bits, int max_frames) {
+    auto b = new dvbs2gpu_bbts();
+    b->nstreams = 1; b->kbch = kbch_bits; b->max_frames = max_frames;
+    return b;
+}
+int bbts_reset_reference_state(dvbs2gpu_bbts* b) {
+    if (!b->ctx) return 0;
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    HIP_TRY(hipMemset(b->d_state, 0, (size_t)b->nstreams * sizeof(BbtsDevState)));
+    for (auto& h : b->host) h.reset();
+    return 0;
+}
+}  // namespace s2
 
 extern "C" {
 
 void dvbs2gpu_bbts_destroy(dvbs2gpu_bbts* b) {
     if (!b) return;
+    bbts_ma_free(b->ma);
     void* ps[] = {b->d_state, b->d_reasm[0], b->d_reasm[1], b->d_desc, b->d_plan, b->d_args, b->d_in1, b->d_out1};
     for (void* p : ps) if (p) (void)hipFree(p);
     delete b;
 }
 
 int dvbs2gpu_bbts_set_frame_size(dvbs2gpu_bbts* b, int kbch_bits) {
-    if (!b || kbch_bits < 88 || kbch_bits % 8 || kbch_bits > 65536) return DVBS2GPU_ERR_ARG;
+    if (!b || !b->ctx || kbch_bits < 88 || kbch_bits % 8 || kbch_bits > 65536) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(b->ctx->device));
     // setFrameSize (.cpp:31-42) forgets the synchronisation; header copy and counters stay, as do the GSE slots
     std::vector<BbtsDevState> st(b->nstreams);
@@ -386,7 +374,7 @@ int dvbs2gpu_bbts_create(dvbs2gpu_ctx* ctx, int nstreams, int kbch_bits, int max
 
 int dvbs2gpu_bbts_process_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb, const int* nframes, uint8_t* const* d_out, int cap,
                                 int* out_bytes, void* stream) {
-    if (!b || !d_bb || !nframes || !d_out || !out_bytes || cap < 0) return DVBS2GPU_ERR_ARG;
+    if (!b || !b->ctx || !d_bb || !nframes || !d_out || !out_bytes || cap < 0) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(b->ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const int n = b->nstreams, fbytes = b->kbch / 8;
@@ -442,7 +430,7 @@ int dvbs2gpu_bbts_process_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb, co
 }
 
 int dvbs2gpu_bbts_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, int cnt, uint8_t* h_ts, int cap) {
-    if (!b || b->nstreams != 1 || cnt < 0 || cnt > b->max_frames || cap < 0 || (cnt > 0 && (!h_bb || !h_ts))) return DVBS2GPU_ERR_ARG;
+    if (!b || !b->ctx || b->nstreams != 1 || cnt < 0 || cnt > b->max_frames || cap < 0 || (cnt > 0 && (!h_bb || !h_ts))) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(b->ctx->device));
     const size_t fbytes = b->kbch / 8;
     if (!b->d_in1) {
@@ -469,7 +457,7 @@ int dvbs2gpu_bbts_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, int cnt, uint8_t* 
 /* h_out15 = {ts_gs, sis_mis, ccm_acm, issyi, npd, ro, isi, upl, dfl, sync, syncd (last_header), last_gse_crc_err, last_bb_cnt,
  * last_bb_proc, last_ts_errs}; h_out15[15..16] = {synched, count} when 17 ints are asked for */
 int dvbs2gpu_bbts_get_stats(dvbs2gpu_bbts* b, int stream, int32_t* h_out, int n_out) {
-    if (!b || stream < 0 || stream >= b->nstreams || !h_out || n_out < 15) return DVBS2GPU_ERR_ARG;
+    if (!b || !b->ctx || stream < 0 || stream >= b->nstreams || !h_out || n_out < 15) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(b->ctx->device));
     BbtsDevState ds;
     HIP_TRY(hipMemcpy(&ds, b->d_state + stream, sizeof(ds), hipMemcpyDeviceToHost));

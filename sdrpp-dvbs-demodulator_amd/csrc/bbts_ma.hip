@@ -1,0 +1,749 @@
+// Mode-adaptation mode of the BBFRAME -> TS bank: ISI demultiplexing, ISSY / DNP slots, null-packet reinsertion
+// and the per-packet CRC-8 for multiple-input-stream and ACM/VCM carriers, whose BBFRAMEs differ in size from frame to frame.
+// Not part of the reference (its parser cuts every data field each 188 bytes of one stream); off unless asked for.
+//
+// A slot is [CRC-8 of the previous UP][187 UP bytes][ISSY 0/2/3][DNP 0/1] (MaLayout below: the one place that says so).  The first
+// slot that starts in a frame starts SYNCD/8 bytes into the data field, so every frame is parsed on its own:
+//   bbts_ma_frame_kernel  one wave per frame: header, lane (selected ISI) lookup, ISSY length, slot geometry; one lane per whole slot
+//                         for its CRC-8 (four table look-ups per dword), DNP and ISCR; wave reductions -> one record per frame;
+//   bbts_ma_lane_kernel   one wave per (stream, selected ISI): walks the stream's records in order, joins the tail of a frame with the
+//                         head of the next one of its ISI (the spanning slot's CRC-8 by the wave, one byte per lane), sums the
+//                         output offsets and writes the lane's new state to the shadow copy;
+//   bbts_ma_emit_kernel   one workgroup per frame: DNP prefix sum, null packets, 0x47 + 187 bytes per slot in dwords, TEI.
+// The host commits the shadow state and launches the third kernel only when every lane's output fits.
+// MaHostStream below applies the same rules to host buffers, byte by byte (host-only banks; the GPU path's second implementation).
+#include "bbts_common.h"
+
+#include <memory>
+
+using namespace s2;
+#define g_err last_error()
+
+namespace s2 {
+
+// ------------------------------------------------------------------------------------------------- the slot layout
+struct MaLayout { int crc_off, up_off, up_len, issy_off; };      // the DNP byte follows the ISSY field and ends the slot
+constexpr MaLayout kMa = {0, 1, 187, 188};
+static_assert(kMa.up_len == 187 && kMa.up_off >= 1 && kMa.issy_off >= kMa.up_off + kMa.up_len, "a TS packet is 0x47 + 187 UP bytes");
+constexpr int MA_TS = 188, MA_LANES = 8, MA_CARRY = 192, MA_NO_START = 65535, MA_MAX_FRAME = 58192 / 8;
+__host__ __device__ inline int ma_slot_len(int issy, int npd) { return kMa.issy_off + issy + npd; }
+__host__ __device__ inline int ma_crc_end(int span, int L) { return span ? L : kMa.up_off + kMa.up_len; }   // CRC-8 over [up_off, end)
+
+struct MaHdr { int ts_gs, isi, issyi, npd, df, s0, nostart; };
+// a frame of `size` bytes: CRC-8 of the BBHEADER, DFL whole bytes that fit the frame, SYNCD inside the data field or 65535 (no slot
+// starts here).  The reference's `syncd >= dfl - 8` rejection is not applied: a slot may start in the last byte of a data field.
+__host__ __device__ inline bool ma_header(const uint8_t* fr, int size, MaHdr* h) {
+    if (size < 10 || crc8_bits(fr, 80) != 0) return false;
+    const HeaderFields p = parse_bbheader(fr);
+    const int dfl = p.v[8], syncd = p.v[10];
+    if (dfl % 8 || dfl > (size - 10) * 8 || !(syncd == MA_NO_START || syncd < dfl)) return false;
+    h->ts_gs = p.v[0]; h->isi = p.v[6]; h->issyi = p.v[3]; h->npd = p.v[4]; h->df = dfl / 8;
+    h->nostart = syncd == MA_NO_START;
+    h->s0 = h->nostart ? h->df : syncd / 8;
+    return true;
+}
+// what a frame says about the ISSY length: the first ISSY field that starts in it (0: nothing)
+__host__ __device__ inline int ma_issy_cand(const uint8_t* fr, const MaHdr& h) {
+    if (!h.issyi || h.nostart || h.s0 + kMa.issy_off >= h.df) return 0;
+    const unsigned top = fr[10 + h.s0 + kMa.issy_off];
+    return top < 0x80 ? 2 : top < 0xC0 ? 3 : 0;
+}
+__host__ __device__ inline bool ma_iscr(const uint8_t* f, int issy, unsigned* v) {
+    if (issy < 2) return false;
+    if (f[0] < 0x80) { *v = f[0] << 8 | f[1]; return true; }
+    if (f[0] < 0xC0 && issy == 3) { *v = (f[0] & 0x3fu) << 16 | f[1] << 8 | f[2]; return true; }
+    return false;
+}
+
+struct MaCfg { int issy_bytes, crc_span, reinsert_nulls, check_crc; };
+struct MaSel { uint8_t isi[MA_LANES]; int n; };
+struct MaLaneState {
+    int c, Lc, cfl, issy;                      // carried bytes, their slot length, issy | npd << 2 of that slot, ISSY length in use
+    int iscr_valid; unsigned iscr;
+    int frames, broken, undecided, pad;
+    long long packets, nulls, ts_errs;
+};
+struct MaStreamState { unsigned seen[8]; int rejected, skipped; };
+struct MaFrameRec {
+    int lane, isi, L, cfl;                     // lane: 0..7, -1 skipped (not TS / ISI not selected), -2 header rejected; L 0: ISSY length unknown
+    int s0, nslots, tail, df, data_off, nostart;
+    int nnull, issy_dec, first_byte, iscr_valid;
+    unsigned iscr, pad;
+    unsigned long long errmask;
+};
+struct MaFrameDesc { const uint8_t* carry; int out_off, joined, c, dnp, tei, pad; };
+struct MaFin { const uint8_t* src; int len, pad; };
+
+// CRC-8 tables: T[k][x] = CRC of byte x followed by k zero bytes (k < 4); ADV[k][b] = register bit b after k zero bytes (k <= 192)
+constexpr int MA_TAB_BYTES = 1024 + (MA_CARRY + 1) * 8;
+static void ma_build_tables(uint8_t* t) {
+    for (int x = 0; x < 256; ++x) {
+        unsigned c = x;
+        for (int i = 0; i < 8; ++i) c = (c & 0x80) ? ((c << 1) ^ 0xD5) & 0xff : (c << 1) & 0xff;   // the BBHEADER's polynomial, MSB first
+        t[x] = (uint8_t)c;
+    }
+    for (int k = 1; k < 4; ++k) for (int x = 0; x < 256; ++x) t[k * 256 + x] = t[t[(k - 1) * 256 + x]];
+    uint8_t* adv = t + 1024;
+    for (int b = 0; b < 8; ++b) adv[b] = (uint8_t)(1u << b);
+    for (int k = 1; k <= MA_CARRY; ++k) for (int b = 0; b < 8; ++b) adv[k * 8 + b] = t[adv[(k - 1) * 8 + b]];
+}
+
+typedef unsigned __attribute__((aligned(1))) unaligned_u32;
+
+__device__ inline int ma_frame_off(const int* foff, int s, int f, int max_frames, int fbytes) {
+    return foff ? foff[s * (max_frames + 1) + f] : f * fbytes;
+}
+
+__global__ void __launch_bounds__(256) bbts_ma_frame_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ foff, int fbytes,
+                                                            const int* __restrict__ nframes, int nstreams, int max_frames, MaCfg cfg,
+                                                            const MaSel* __restrict__ sel, const MaLaneState* __restrict__ lanes,
+                                                            const uint8_t* __restrict__ tabs, MaFrameRec* __restrict__ recs) {
+    __shared__ uint8_t T[4][256];
+    for (int i = threadIdx.x; i < 1024; i += 256) (&T[0][0])[i] = tabs[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int s = w / max_frames, f = w % max_frames;
+    if (s >= nstreams || f >= nframes[s]) return;
+    const uint8_t* bb = in[s];
+    const int off = ma_frame_off(foff, s, f, max_frames, fbytes), size = ma_frame_off(foff, s, f + 1, max_frames, fbytes) - off;
+    MaFrameRec r = {};
+    MaFrameRec* out = recs + (size_t)s * max_frames + f;
+    MaHdr h;
+    if (!ma_header(bb + off, size, &h)) { r.lane = -2; if (lane == 0) *out = r; return; }
+    r.isi = h.isi; r.lane = -1;
+    const MaSel se = sel[s];
+    for (int k = se.n - 1; k >= 0; --k) if (se.isi[k] == h.isi) r.lane = k;
+    if (h.ts_gs != 3 || r.lane < 0) { r.lane = -1; if (lane == 0) *out = r; return; }
+    int issy = 0;
+    if (h.issyi) {
+        issy = cfg.issy_bytes ? cfg.issy_bytes : lanes[s * MA_LANES + r.lane].issy;
+        // not known yet: the first frame of this ISI in the call, up to this one, that shows an ISCR decides (64 frames at a time)
+        for (int g0 = 0; g0 <= f && !issy; g0 += 64) {
+            const int g = g0 + lane;
+            int cand = 0;
+            if (g <= f) {
+                const int o = ma_frame_off(foff, s, g, max_frames, fbytes);
+                MaHdr hg;
+                if (ma_header(bb + o, ma_frame_off(foff, s, g + 1, max_frames, fbytes) - o, &hg) && hg.ts_gs == 3 && hg.isi == h.isi)
+                    cand = ma_issy_cand(bb + o, hg);
+            }
+            const unsigned long long m = __ballot(cand != 0);
+            if (m) issy = __shfl(cand, __ffsll((long long)m) - 1);
+        }
+        r.issy_dec = issy;
+        if (!issy) { if (lane == 0) *out = r; return; }          // L = 0
+    }
+    const int L = ma_slot_len(issy, h.npd);
+    r.L = L; r.cfl = issy | h.npd << 2; r.s0 = h.s0; r.df = h.df; r.data_off = off + 10; r.nostart = h.nostart;
+    if (h.nostart) { if (lane == 0) *out = r; return; }
+    const uint8_t* data = bb + off + 10;
+    int n = (h.df - h.s0 - 1) / L;
+    n = n < 64 ? n : 64;
+    r.nslots = n; r.tail = h.df - h.s0 - n * L; r.first_byte = data[h.s0];
+    const bool act = lane < n;
+    int dnp = 0, err = 0, has_iscr = 0;
+    unsigned iscr = 0;
+    if (act) {
+        const uint8_t* p = data + h.s0 + lane * L;
+        const int e = ma_crc_end(cfg.crc_span, L);
+        unsigned crc = 0;
+        int i = kMa.up_off;
+        while (i < e) {
+            if ((i & 3) == 0 && i + 4 <= e) {
+                const unsigned v = *reinterpret_cast<const unaligned_u32*>(p + i);
+                crc = T[3][(v & 0xff) ^ crc] ^ T[2][(v >> 8) & 0xff] ^ T[1][(v >> 16) & 0xff] ^ T[0][v >> 24];
+                i += 4;
+            } else {
+                crc = T[0][crc ^ p[i]];
+                ++i;
+            }
+        }
+        err = cfg.check_crc && crc != p[L];
+        if (h.npd && cfg.reinsert_nulls) dnp = p[L - 1];
+        if (issy) has_iscr = ma_iscr(p + kMa.issy_off, issy, &iscr);
+    }
+    r.errmask = __ballot(err);
+    int sum = dnp;
+    for (int d = 32; d; d >>= 1) sum += __shfl_xor(sum, d);
+    r.nnull = sum;
+    const unsigned long long vm = __ballot(has_iscr);
+    if (vm) { r.iscr_valid = 1; r.iscr = __shfl(iscr, 63 - __clzll((long long)vm)); }
+    if (lane == 0) *out = r;
+}
+
+// CRC-8 of the slot `carry[0..c) ++ data[0..)` over [up_off, e), by one wave: every byte's contribution advanced to the end, XORed
+__device__ inline unsigned ma_wave_crc(const uint8_t* carry, int c, const uint8_t* data, int e, const uint8_t* adv, int lane) {
+    unsigned x = 0;
+    for (int i = kMa.up_off + lane; i < e; i += 64) {
+        const unsigned v = i < c ? carry[i] : data[i - c];
+        const uint8_t* a = adv + (e - i) * 8;
+        for (int b = 0; b < 8; ++b) if (v >> b & 1) x ^= a[b];
+    }
+    for (int d = 32; d; d >>= 1) x ^= __shfl_xor(x, d);
+    return x;
+}
+
+__global__ void __launch_bounds__(256) bbts_ma_lane_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nframes, int nstreams,
+                                                           int max_frames, MaCfg cfg, const MaSel* __restrict__ sel,
+                                                           const MaFrameRec* __restrict__ recs, const uint8_t* __restrict__ tabs,
+                                                           const MaLaneState* __restrict__ lanes_old, MaLaneState* __restrict__ lanes_new,
+                                                           const MaStreamState* __restrict__ strm_old, MaStreamState* __restrict__ strm_new,
+                                                           const uint8_t* __restrict__ carry_old, uint8_t* __restrict__ joinbuf,
+                                                           MaFrameDesc* __restrict__ desc, MaFin* __restrict__ fins, int* __restrict__ needed) {
+    const int lane = threadIdx.x & 63, w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int s = w / MA_LANES, slot = w % MA_LANES;
+    if (s >= nstreams) return;
+    const int nf = nframes[s];
+    const uint8_t* bb = in[s];
+    const uint8_t* adv = tabs + 1024;
+    const MaFrameRec* rs = recs + (size_t)s * max_frames;
+    MaLaneState st = lanes_old[w];
+    const uint8_t* carry = carry_old + (size_t)w * MA_CARRY;
+    if (slot == 0) {                               // the stream's own counters travel with its first lane
+        MaStreamState ss = strm_old[s];
+        for (int f = 0; f < nf; ++f) {
+            const int l = rs[f].lane, isi = rs[f].isi;
+            if (l == -2) { ++ss.rejected; continue; }
+            for (int k = 0; k < 8; ++k) if (k == isi >> 5) ss.seen[k] |= 1u << (isi & 31);   // (a variable index would put the array into LDS)
+            if (l == -1) ++ss.skipped;
+        }
+        if (lane == 0) strm_new[s] = ss;
+    }
+    int out_off = 0;
+    if (slot < sel[s].n) {
+        for (int f = 0; f < nf; ++f) {
+            const MaFrameRec r = rs[f];
+            if (r.lane != slot) continue;
+            ++st.frames;
+            if (r.issy_dec) st.issy = r.issy_dec;
+            if (r.L == 0) { ++st.undecided; st.c = 0; continue; }
+            const uint8_t* data = bb + r.data_off;
+            const int issy = r.cfl & 3, npd = r.cfl >> 2 & 1;
+            if (r.nostart) {                       // the whole data field continues the carried slot: collect both in this frame's join buffer
+                if (st.c > 0) {
+                    if (st.Lc == r.L && st.c + r.df <= r.L) {
+                        uint8_t* jb = joinbuf + ((size_t)s * max_frames + f) * MA_CARRY;
+                        for (int i = lane; i < st.c + r.df; i += 64) jb[i] = i < st.c ? carry[i] : data[i - st.c];
+                        __threadfence();
+                        carry = jb; st.c += r.df;
+                    } else {
+                        ++st.broken; st.c = 0;
+                    }
+                }
+                continue;
+            }
+            MaFrameDesc d = {carry, out_off, 0, st.c, 0, 0, 0};
+            if (st.c > 0) {
+                if (st.Lc == r.L && st.c + r.s0 == r.L) {
+                    d.joined = 1;
+                    if (npd && cfg.reinsert_nulls) d.dnp = r.s0 > 0 ? data[r.s0 - 1] : carry[st.c - 1];
+                    if (cfg.check_crc) d.tei = ma_wave_crc(carry, st.c, data, ma_crc_end(cfg.crc_span, r.L), adv, lane) != (unsigned)r.first_byte;
+                    if (issy) {
+                        uint8_t fld[3];
+                        for (int k = 0; k < 3; ++k) { const int i = kMa.issy_off + k; fld[k] = k < issy ? (i < st.c ? carry[i] : data[i - st.c]) : 0; }
+                        unsigned v;
+                        if (ma_iscr(fld, issy, &v)) { st.iscr = v; st.iscr_valid = 1; }
+                    }
+                    ++st.packets; st.nulls += d.dnp; st.ts_errs += d.tei;
+                    out_off += (1 + d.dnp) * MA_TS;
+                } else {
+                    ++st.broken;
+                }
+            }
+            if (lane == 0) desc[(size_t)s * max_frames + f] = d;
+            out_off += (r.nslots + r.nnull) * MA_TS;
+            st.packets += r.nslots; st.nulls += r.nnull; st.ts_errs += __popcll(r.errmask);
+            if (r.iscr_valid) { st.iscr = r.iscr; st.iscr_valid = 1; }
+            st.c = r.tail; st.Lc = r.L; st.cfl = r.cfl;
+            carry = data + r.s0 + r.nslots * r.L;
+        }
+    }
+    if (lane == 0) {
+        lanes_new[w] = st;
+        MaFin fn = {carry, st.c, 0};
+        fins[w] = fn;
+        needed[w] = out_off;
+    }
+}
+
+__device__ inline void ma_store4(uint8_t* o, unsigned v, bool aligned) {
+    if (aligned) {
+        *reinterpret_cast<unsigned*>(o) = v;
+    } else {
+        o[0] = (uint8_t)v; o[1] = (uint8_t)(v >> 8); o[2] = (uint8_t)(v >> 16); o[3] = (uint8_t)(v >> 24);
+    }
+}
+// `dnp` null packets, then 0x47 + the 187 UP bytes of one slot, by one wave; 188 = 4 * 47: a dword never straddles two packets
+__device__ inline void ma_put_slot(uint8_t* o, int dnp, const uint8_t* carry, int c, const uint8_t* data, int tei, bool aligned, int lane) {
+    for (int w = lane; w < dnp * 47; w += 64) ma_store4(o + 4 * w, w % 47 == 0 ? 0x10ff1f47u : 0xffffffffu, aligned);
+    o += (size_t)dnp * MA_TS;
+    if (lane < 47) {
+        const int i = kMa.up_off - 1 + 4 * lane;                 // slot bytes [i, i + 4); data[] starts at slot byte c
+        unsigned v;
+        if (i >= c) {
+            v = *reinterpret_cast<const unaligned_u32*>(data + i - c);
+        } else {
+            v = 0;
+            for (int k = 0; k < 4; ++k) v |= (unsigned)(i + k < c ? carry[i + k] : data[i + k - c]) << (8 * k);
+        }
+        if (lane == 0) v = ((v & ~0xffu) | 0x47u) | (tei ? 0x8000u : 0u);
+        ma_store4(o + 4 * lane, v, aligned);
+    }
+}
+
+__global__ void __launch_bounds__(256) bbts_ma_emit_kernel(const uint8_t* const* __restrict__ in, uint8_t* const* __restrict__ out,
+                                                           const int* __restrict__ nframes, int max_frames, MaCfg cfg,
+                                                           const MaFrameRec* __restrict__ recs, const MaFrameDesc* __restrict__ desc,
+                                                           const MaFin* __restrict__ fins, uint8_t* __restrict__ carry_new) {
+    __shared__ int idx[64], dnps[64];
+    const int s = blockIdx.y, f = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (f == max_frames) {                         // what every lane of this stream carries into the next call
+        for (int l = 0; l < MA_LANES; ++l) {
+            const MaFin fn = fins[s * MA_LANES + l];
+            uint8_t* nw = carry_new + (size_t)(s * MA_LANES + l) * MA_CARRY;
+            for (int i = threadIdx.x; i < fn.len; i += blockDim.x) nw[i] = fn.src[i];
+        }
+        return;
+    }
+    if (f >= nframes[s]) return;
+    const MaFrameRec r = recs[(size_t)s * max_frames + f];
+    if (r.lane < 0 || r.L == 0 || r.nostart) return;
+    const MaFrameDesc d = desc[(size_t)s * max_frames + f];
+    const uint8_t* data = in[s] + r.data_off;
+    const int npd = r.cfl >> 2 & 1;
+    if (wave == 0) {                               // packet index of every whole slot inside the frame: prefix sum of 1 + DNP
+        int dn = 0;
+        if (lane < r.nslots && npd && cfg.reinsert_nulls) dn = data[r.s0 + (lane + 1) * r.L - 1];
+        int inc = 1 + dn;
+        for (int k = 1; k < 64; k <<= 1) { const int t = __shfl_up(inc, k); if (lane >= k) inc += t; }
+        idx[lane] = inc - 1 - dn; dnps[lane] = dn;
+    }
+    __syncthreads();
+    uint8_t* o = out[s * MA_LANES + r.lane] + d.out_off;
+    const bool aligned = (reinterpret_cast<uintptr_t>(o) & 3) == 0;
+    if (d.joined) {
+        if (wave == 3) ma_put_slot(o, d.dnp, d.carry, d.c, data, d.tei, aligned, lane);
+        o += (size_t)(1 + d.dnp) * MA_TS;
+    }
+    for (int k = wave; k < r.nslots; k += 4)
+        ma_put_slot(o + (size_t)idx[k] * MA_TS, dnps[k], nullptr, 0, data + r.s0 + k * r.L, (int)(r.errmask >> k & 1), aligned, lane);
+}
+
+// ------------------------------------------------------------------------------------------------- host parser
+// The same rules, one byte at a time, for one stream in host memory.
+struct MaHostStream {
+    MaLaneState st[MA_LANES] = {};
+    uint8_t carry[MA_LANES][MA_CARRY] = {};
+    MaStreamState ss = {};
+    uint8_t tab[256];
+
+    MaHostStream() {
+        uint8_t t[MA_TAB_BYTES];
+        ma_build_tables(t);
+        memcpy(tab, t, 256);
+    }
+    unsigned crc(const uint8_t* p, int a, int e) const {
+        unsigned c = 0;
+        for (int i = a; i < e; ++i) c = tab[c ^ p[i]];
+        return c;
+    }
+    // one slot (L bytes at p) -> out; chk < 0: no CRC-8 to compare with
+    void emit(MaLaneState& l, const uint8_t* p, int L, int issy, int npd, int chk, const MaCfg& cfg, std::vector<uint8_t>& out) const {
+        const int dnp = npd && cfg.reinsert_nulls ? p[L - 1] : 0;
+        for (int k = 0; k < dnp; ++k) {
+            const size_t at = out.size();
+            out.resize(at + MA_TS, 0xff);
+            out[at] = 0x47; out[at + 1] = 0x1f; out[at + 3] = 0x10;
+        }
+        l.nulls += dnp;
+        const size_t at = out.size();
+        out.push_back(0x47);
+        out.insert(out.end(), p + kMa.up_off, p + kMa.up_off + kMa.up_len);
+        if (cfg.check_crc && chk >= 0 && crc(p, kMa.up_off, ma_crc_end(cfg.crc_span, L)) != (unsigned)chk) { out[at + 1] |= 0x80; ++l.ts_errs; }
+        ++l.packets;
+        unsigned v;
+        if (issy && ma_iscr(p + kMa.issy_off, issy, &v)) { l.iscr = v; l.iscr_valid = 1; }
+    }
+    void frame(const uint8_t* fr, int size, const MaCfg& cfg, const MaSel& sel, std::vector<uint8_t>* outs) {
+        MaHdr h;
+        if (!ma_header(fr, size, &h)) { ++ss.rejected; return; }
+        ss.seen[h.isi >> 5] |= 1u << (h.isi & 31);
+        int slot = -1;
+        for (int k = sel.n - 1; k >= 0; --k) if (sel.isi[k] == h.isi) slot = k;
+        if (h.ts_gs != 3 || slot < 0) { ++ss.skipped; return; }
+        MaLaneState& l = st[slot];
+        uint8_t* cy = carry[slot];
+        ++l.frames;
+        int issy = 0;
+        if (h.issyi) {
+            if (!l.issy) l.issy = ma_issy_cand(fr, h);
+            if (!l.issy) { ++l.undecided; l.c = 0; return; }
+            issy = l.issy;
+        }
+        const int L = ma_slot_len(issy, h.npd);
+        const uint8_t* data = fr + 10;
+        if (h.nostart) {
+            if (l.c > 0) {
+                if (l.Lc == L && l.c + h.df <= L) { memcpy(cy + l.c, data, h.df); l.c += h.df; }
+                else { ++l.broken; l.c = 0; }
+            }
+            return;
+        }
+        if (l.c > 0) {
+            if (l.Lc == L && l.c + h.s0 == L) {
+                memcpy(cy + l.c, data, h.s0);
+                emit(l, cy, L, issy, h.npd, data[h.s0], cfg, outs[slot]);
+            } else {
+                ++l.broken;
+            }
+        }
+        const int n = (h.df - h.s0 - 1) / L;
+        for (int k = 0; k < n; ++k) emit(l, data + h.s0 + k * L, L, issy, h.npd, data[h.s0 + (k + 1) * L], cfg, outs[slot]);
+        l.c = h.df - h.s0 - n * L; l.Lc = L; l.cfl = issy | h.npd << 2;
+        memcpy(cy, data + h.s0 + n * L, l.c);
+    }
+};
+
+// a whole slot held back for its CRC-8 leaves unchecked
+static void ma_flush_lane(MaHostStream& tool, MaLaneState& l, const uint8_t* cy, const MaCfg& cfg, std::vector<uint8_t>& out) {
+    if (l.c > 0 && l.c == l.Lc) {
+        tool.emit(l, cy, l.Lc, l.cfl & 3, l.cfl >> 2 & 1, -1, cfg, out);
+        l.c = 0;
+    }
+}
+
+struct BbtsMa {
+    MaCfg cfg;
+    std::vector<MaSel> sel;
+    // device banks
+    MaLaneState* d_lane[2] = {nullptr, nullptr};
+    MaStreamState* d_strm[2] = {nullptr, nullptr};
+    uint8_t* d_carry[2] = {nullptr, nullptr};
+    int cur = 0;
+    MaSel* d_sel = nullptr;
+    uint8_t *d_tabs = nullptr, *d_join = nullptr;
+    MaFrameRec* d_recs = nullptr;
+    MaFrameDesc* d_desc = nullptr;
+    MaFin* d_fins = nullptr;
+    void* d_args = nullptr;                    // [in ptrs][8 out ptrs per stream][nframes][needed per lane][frame offsets]
+    std::vector<int> h_foff;
+    uint8_t *d_in1 = nullptr, *d_out1 = nullptr;   // staging of the single-stream host-buffer entry point
+    size_t out1_cap = 0;
+    // host-only banks
+    std::unique_ptr<MaHostStream> host;
+    MaHostStream tool;                         // flush of a device bank
+};
+
+void bbts_ma_free(BbtsMa* m) {
+    if (!m) return;
+    void* ps[] = {m->d_lane[0], m->d_lane[1], m->d_strm[0], m->d_strm[1], m->d_carry[0], m->d_carry[1], m->d_sel, m->d_tabs, m->d_join,
+                  m->d_recs, m->d_desc, m->d_fins, m->d_args, m->d_in1, m->d_out1};
+    for (void* p : ps) if (p) (void)hipFree(p);
+    delete m;
+}
+
+static int ma_upload_sel(const BbtsBankView& v, BbtsMa* m) {
+    if (!v.ctx) return 0;
+    HIP_TRY(hipMemcpy(m->d_sel, m->sel.data(), m->sel.size() * sizeof(MaSel), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// frame offsets of one stream from its size list (null: all kbch/8); false when a size cannot be a BBFRAME
+static bool ma_offsets(const int* sizes, int n, int fbytes, int* off) {
+    off[0] = 0;
+    for (int f = 0; f < n; ++f) {
+        const int b = sizes ? sizes[f] : fbytes;
+        if (b < 10 || b > MA_MAX_FRAME) return false;
+        off[f + 1] = off[f] + b;
+    }
+    return true;
+}
+
+}  // namespace s2
+
+extern "C" {
+
+void dvbs2gpu_bbts_ma_default_cfg(dvbs2gpu_bbts_ma_cfg* cfg) {
+    if (!cfg) return;
+    cfg->issy_bytes = 0; cfg->crc_span = 0; cfg->reinsert_nulls = 1; cfg->check_crc = 1;
+}
+
+int dvbs2gpu_bbts_ma_get_layout(int32_t* out4) {
+    if (!out4) return DVBS2GPU_ERR_ARG;
+    out4[0] = kMa.crc_off; out4[1] = kMa.up_off; out4[2] = kMa.up_len; out4[3] = kMa.issy_off;
+    return 0;
+}
+
+int dvbs2gpu_bbts_create_host(int kbch_bits, int max_frames, dvbs2gpu_bbts** out) {
+    if (!out || max_frames <= 0 || kbch_bits < 88 || kbch_bits % 8 || kbch_bits > 65536) return DVBS2GPU_ERR_ARG;
+    *out = bbts_new_host_bank(kbch_bits, max_frames);
+    return 0;
+}
+
+int dvbs2gpu_bbts_set_mode_adaptation(dvbs2gpu_bbts* b, const dvbs2gpu_bbts_ma_cfg* cfg) {
+    if (!b) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    if (!cfg) {
+        if (!*v.ma) return 0;
+        if (v.ctx) HIP_TRY(hipSetDevice(v.ctx->device));
+        bbts_ma_free(*v.ma);
+        *v.ma = nullptr;
+        return bbts_reset_reference_state(b);          // the reference-mode parser starts afresh
+    }
+    if ((cfg->issy_bytes != 0 && cfg->issy_bytes != 2 && cfg->issy_bytes != 3) || (cfg->crc_span != 0 && cfg->crc_span != 1)) {
+        g_err = "mode adaptation: issy_bytes is 0 (auto), 2 or 3 and crc_span 0 or 1";
+        return DVBS2GPU_ERR_ARG;
+    }
+    if (v.ctx) HIP_TRY(hipSetDevice(v.ctx->device));
+    bbts_ma_free(*v.ma);
+    *v.ma = nullptr;
+    std::unique_ptr<BbtsMa> m(new BbtsMa());
+    m->cfg = {cfg->issy_bytes, cfg->crc_span, cfg->reinsert_nulls != 0, cfg->check_crc != 0};
+    MaSel s0 = {};
+    s0.n = 1;                                      // ISI 0: a single-input-stream carrier works without a selection
+    m->sel.assign(v.nstreams, s0);
+    const size_t n = v.nstreams, nl = n * MA_LANES, nfr = n * v.max_frames;
+    if (v.ctx) {
+        hipError_t e = hipSuccess;
+        auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) { e = hipMalloc(p, bytes); if (e == hipSuccess) e = hipMemset(*p, 0, bytes); } };
+        for (int k = 0; k < 2; ++k) {
+            A((void**)&m->d_lane[k], nl * sizeof(MaLaneState));
+            A((void**)&m->d_strm[k], n * sizeof(MaStreamState));
+            A((void**)&m->d_carry[k], nl * MA_CARRY);
+        }
+        A((void**)&m->d_sel, n * sizeof(MaSel));
+        A((void**)&m->d_tabs, MA_TAB_BYTES);
+        A((void**)&m->d_join, nfr * MA_CARRY);
+        A((void**)&m->d_recs, nfr * sizeof(MaFrameRec));
+        A((void**)&m->d_desc, nfr * sizeof(MaFrameDesc));
+        A((void**)&m->d_fins, nl * sizeof(MaFin));
+        A(&m->d_args, n * sizeof(void*) + nl * sizeof(void*) + n * sizeof(int) + nl * sizeof(int) + n * (v.max_frames + 1) * sizeof(int));
+        if (e != hipSuccess) { bbts_ma_free(m.release()); return fail_hip(e, "hipMalloc(bbts mode adaptation)"); }
+        uint8_t t[MA_TAB_BYTES];
+        ma_build_tables(t);
+        HIP_TRY(hipMemcpy(m->d_tabs, t, sizeof(t), hipMemcpyHostToDevice));
+        if (cfg->issy_bytes) {                         // a configured ISSY length is the lanes' from the start
+            std::vector<MaLaneState> ls(nl);
+            for (auto& l : ls) l.issy = cfg->issy_bytes;
+            HIP_TRY(hipMemcpy(m->d_lane[0], ls.data(), nl * sizeof(MaLaneState), hipMemcpyHostToDevice));
+        }
+        m->h_foff.resize(n * (v.max_frames + 1));
+        const int rc = ma_upload_sel(v, m.get());
+        if (rc) return rc;
+    } else {
+        m->host.reset(new MaHostStream());
+        for (auto& l : m->host->st) l.issy = cfg->issy_bytes;
+    }
+    *v.ma = m.release();
+    return 0;
+}
+
+int dvbs2gpu_bbts_select_isi(dvbs2gpu_bbts* b, int stream, const uint8_t* isi, int n) {
+    if (!b) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    BbtsMa* m = *v.ma;
+    if (!m) { g_err = "select_isi: the mode-adaptation mode is off"; return DVBS2GPU_ERR_ARG; }
+    if (stream < 0 || stream >= v.nstreams || n < 0 || n > MA_LANES || (n > 0 && !isi)) return DVBS2GPU_ERR_ARG;
+    MaSel s = {};
+    s.n = n;
+    for (int k = 0; k < n; ++k) s.isi[k] = isi[k];
+    m->sel[stream] = s;
+    // the stream's lanes start afresh: state, counters and the carried bytes belong to the old selection
+    std::vector<MaLaneState> z(MA_LANES);
+    for (auto& l : z) l.issy = m->cfg.issy_bytes;
+    if (v.ctx) {
+        HIP_TRY(hipSetDevice(v.ctx->device));
+        HIP_TRY(hipMemcpy(m->d_lane[m->cur] + (size_t)stream * MA_LANES, z.data(), MA_LANES * sizeof(MaLaneState), hipMemcpyHostToDevice));
+        return ma_upload_sel(v, m);
+    }
+    memcpy(m->host->st, z.data(), sizeof(m->host->st));
+    return 0;
+}
+
+int dvbs2gpu_bbts_process_ma_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb, const int* const* frame_bytes, const int* nframes,
+                                   uint8_t* const* d_out, int cap, int* out_bytes, int* needed, void* stream) {
+    if (!b || !d_bb || !nframes || !d_out || !out_bytes || cap < 0) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    BbtsMa* m = *v.ma;
+    if (!v.ctx || !m) { g_err = "process_ma_batch: needs a device bank with the mode-adaptation mode on"; return DVBS2GPU_ERR_ARG; }
+    HIP_TRY(hipSetDevice(v.ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int n = v.nstreams, nl = n * MA_LANES, mf = v.max_frames;
+    for (int i = 0; i < n; ++i) {
+        if (nframes[i] < 0 || nframes[i] > mf) { g_err = "frame count exceeds max_frames"; return DVBS2GPU_ERR_ARG; }
+        if (nframes[i] > 0 && !d_bb[i]) return DVBS2GPU_ERR_ARG;
+        for (int k = 0; k < m->sel[i].n; ++k) if (nframes[i] > 0 && !d_out[i * MA_LANES + k]) return DVBS2GPU_ERR_ARG;
+        if (frame_bytes && !ma_offsets(frame_bytes[i], nframes[i], v.kbch / 8, m->h_foff.data() + (size_t)i * (mf + 1))) {
+            g_err = "a BBFRAME is 10 to 7274 bytes";
+            return DVBS2GPU_ERR_ARG;
+        }
+    }
+    if (!frame_bytes && v.kbch / 8 > MA_MAX_FRAME) { g_err = "a BBFRAME is 10 to 7274 bytes"; return DVBS2GPU_ERR_ARG; }
+    char* a = (char*)m->d_args;
+    const uint8_t** a_in = (const uint8_t**)a;
+    uint8_t** a_out = (uint8_t**)(a + sizeof(void*) * n);
+    int* a_nf = (int*)(a + sizeof(void*) * (n + nl));
+    int* a_need = a_nf + n;
+    int* a_foff = a_need + nl;
+    HIP_TRY(hipMemcpyAsync(a_in, d_bb, sizeof(void*) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(a_out, d_out, sizeof(void*) * nl, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(a_nf, nframes, sizeof(int) * n, hipMemcpyHostToDevice, st));
+    if (frame_bytes) HIP_TRY(hipMemcpyAsync(a_foff, m->h_foff.data(), sizeof(int) * n * (mf + 1), hipMemcpyHostToDevice, st));
+    const int* foff = frame_bytes ? a_foff : nullptr;
+    const int cur = m->cur;
+    hipLaunchKernelGGL(bbts_ma_frame_kernel, dim3((n * mf + 3) / 4), dim3(256), 0, st, a_in, foff, v.kbch / 8, a_nf, n, mf, m->cfg, m->d_sel,
+                       m->d_lane[cur], m->d_tabs, m->d_recs);
+    hipLaunchKernelGGL(bbts_ma_lane_kernel, dim3((nl + 3) / 4), dim3(256), 0, st, a_in, a_nf, n, mf, m->cfg, m->d_sel, m->d_recs, m->d_tabs,
+                       m->d_lane[cur], m->d_lane[cur ^ 1], m->d_strm[cur], m->d_strm[cur ^ 1], m->d_carry[cur], m->d_join, m->d_desc, m->d_fins,
+                       a_need);
+    HIP_TRY(hipGetLastError());
+    std::vector<int> need(nl);
+    HIP_TRY(hipMemcpyAsync(need.data(), a_need, sizeof(int) * nl, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    bool fits = true;
+    for (int i = 0; i < nl; ++i) {
+        if (needed) needed[i] = need[i];
+        fits = fits && need[i] <= cap;
+    }
+    if (!fits) {                                   // nothing committed: the shadow state is simply not taken
+        for (int i = 0; i < nl; ++i) out_bytes[i] = 0;
+        g_err = "mode adaptation: an output does not fit into cap (needed[] has the sizes)";
+        return DVBS2GPU_ERR_CAPACITY;
+    }
+    hipLaunchKernelGGL(bbts_ma_emit_kernel, dim3(mf + 1, n), dim3(256), 0, st, a_in, a_out, a_nf, mf, m->cfg, m->d_recs, m->d_desc, m->d_fins,
+                       m->d_carry[cur ^ 1]);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    m->cur = cur ^ 1;
+    for (int i = 0; i < nl; ++i) out_bytes[i] = need[i];
+    return 0;
+}
+
+int dvbs2gpu_bbts_ma_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, const int* frame_bytes, int cnt, uint8_t* const* h_out, int cap,
+                          int* out_bytes, int* needed) {
+    if (!b || !h_out || !out_bytes || cnt < 0 || cap < 0 || (cnt > 0 && !h_bb)) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    BbtsMa* m = *v.ma;
+    if (!m || v.nstreams != 1) { g_err = "ma_work: needs a bank of one stream with the mode-adaptation mode on"; return DVBS2GPU_ERR_ARG; }
+    if (cnt > v.max_frames) { g_err = "frame count exceeds max_frames"; return DVBS2GPU_ERR_ARG; }
+    std::vector<int> off(cnt + 1);
+    if (!ma_offsets(frame_bytes, cnt, v.kbch / 8, off.data())) { g_err = "a BBFRAME is 10 to 7274 bytes"; return DVBS2GPU_ERR_ARG; }
+    const MaSel& sel = m->sel[0];
+    for (int k = 0; k < sel.n; ++k) if (cnt > 0 && !h_out[k]) return DVBS2GPU_ERR_ARG;
+    if (!v.ctx) {
+        MaHostStream trial = *m->host;             // the state advances only when every output fits
+        std::vector<uint8_t> outs[MA_LANES];
+        for (int f = 0; f < cnt; ++f) trial.frame(h_bb + off[f], off[f + 1] - off[f], m->cfg, sel, outs);
+        bool fits = true;
+        for (int k = 0; k < MA_LANES; ++k) {
+            if (needed) needed[k] = (int)outs[k].size();
+            fits = fits && (long)outs[k].size() <= cap;
+            out_bytes[k] = 0;
+        }
+        if (!fits) { g_err = "mode adaptation: an output does not fit into cap (needed[] has the sizes)"; return DVBS2GPU_ERR_CAPACITY; }
+        *m->host = trial;
+        for (int k = 0; k < MA_LANES; ++k) {
+            out_bytes[k] = (int)outs[k].size();
+            if (!outs[k].empty()) memcpy(h_out[k], outs[k].data(), outs[k].size());
+        }
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(v.ctx->device));
+    if (!m->d_in1) HIP_TRY(hipMalloc((void**)&m->d_in1, (size_t)v.max_frames * MA_MAX_FRAME + 64));
+    if (cnt > 0) HIP_TRY(hipMemcpy(m->d_in1, h_bb, off[cnt], hipMemcpyHostToDevice));
+    const size_t per = ((size_t)cap + 67) & ~(size_t)3;
+    if (m->out1_cap < per * MA_LANES) {
+        if (m->d_out1) (void)hipFree(m->d_out1);
+        m->d_out1 = nullptr; m->out1_cap = 0;
+        HIP_TRY(hipMalloc((void**)&m->d_out1, per * MA_LANES));
+        m->out1_cap = per * MA_LANES;
+    }
+    uint8_t* d_out[MA_LANES];
+    for (int k = 0; k < MA_LANES; ++k) d_out[k] = m->d_out1 + per * k;
+    const uint8_t* in_p = m->d_in1;
+    const int rc = dvbs2gpu_bbts_process_ma_batch(b, &in_p, frame_bytes ? &frame_bytes : nullptr, &cnt, d_out, cap, out_bytes, needed, nullptr);
+    if (rc) return rc;
+    for (int k = 0; k < sel.n; ++k) if (out_bytes[k] > 0) HIP_TRY(hipMemcpy(h_out[k], d_out[k], out_bytes[k], hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static int ma_flush(dvbs2gpu_bbts* b, uint8_t* const* out, int cap, int* out_bytes, bool host_out) {
+    if (!b || !out || !out_bytes || cap < 0) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    BbtsMa* m = *v.ma;
+    if (!m) { g_err = "ma_flush: the mode-adaptation mode is off"; return DVBS2GPU_ERR_ARG; }
+    const int nl = v.nstreams * MA_LANES;
+    std::vector<MaLaneState> ls(nl);
+    std::vector<uint8_t> cy((size_t)nl * MA_CARRY);
+    if (v.ctx) {
+        HIP_TRY(hipSetDevice(v.ctx->device));
+        HIP_TRY(hipMemcpy(ls.data(), m->d_lane[m->cur], nl * sizeof(MaLaneState), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cy.data(), m->d_carry[m->cur], cy.size(), hipMemcpyDeviceToHost));
+    } else {
+        memcpy(ls.data(), m->host->st, sizeof(m->host->st));
+        memcpy(cy.data(), m->host->carry, sizeof(m->host->carry));
+    }
+    std::vector<std::vector<uint8_t>> outs(nl);
+    for (int i = 0; i < nl; ++i) {
+        out_bytes[i] = 0;
+        if (i % MA_LANES >= m->sel[i / MA_LANES].n) continue;
+        ma_flush_lane(m->tool, ls[i], cy.data() + (size_t)i * MA_CARRY, m->cfg, outs[i]);
+        if ((long)outs[i].size() > cap) { g_err = "ma_flush: cap is smaller than a held packet and its null packets"; return DVBS2GPU_ERR_CAPACITY; }
+        if (!outs[i].empty() && !out[i]) return DVBS2GPU_ERR_ARG;
+    }
+    for (int i = 0; i < nl; ++i) {
+        if (outs[i].empty()) continue;
+        if (v.ctx && !host_out) HIP_TRY(hipMemcpy(out[i], outs[i].data(), outs[i].size(), hipMemcpyHostToDevice));
+        else memcpy(out[i], outs[i].data(), outs[i].size());
+        out_bytes[i] = (int)outs[i].size();
+    }
+    if (v.ctx) HIP_TRY(hipMemcpy(m->d_lane[m->cur], ls.data(), nl * sizeof(MaLaneState), hipMemcpyHostToDevice));
+    else memcpy(m->host->st, ls.data(), sizeof(m->host->st));
+    return 0;
+}
+
+int dvbs2gpu_bbts_ma_flush(dvbs2gpu_bbts* b, uint8_t* const* out, int cap, int* out_bytes) { return ma_flush(b, out, cap, out_bytes, false); }
+int dvbs2gpu_bbts_ma_flush_host(dvbs2gpu_bbts* b, uint8_t* const* h_out, int cap, int* out_bytes) { return ma_flush(b, h_out, cap, out_bytes, true); }
+
+int dvbs2gpu_bbts_ma_get_stats(dvbs2gpu_bbts* b, int stream, int slot, dvbs2gpu_bbts_ma_stats* h_out) {
+    if (!b || !h_out || slot < 0 || slot >= MA_LANES) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    BbtsMa* m = *v.ma;
+    if (!m || stream < 0 || stream >= v.nstreams) return DVBS2GPU_ERR_ARG;
+    MaLaneState l;
+    MaStreamState ss;
+    if (v.ctx) {
+        HIP_TRY(hipSetDevice(v.ctx->device));
+        HIP_TRY(hipMemcpy(&l, m->d_lane[m->cur] + (size_t)stream * MA_LANES + slot, sizeof(l), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&ss, m->d_strm[m->cur] + stream, sizeof(ss), hipMemcpyDeviceToHost));
+    } else {
+        l = m->host->st[slot]; ss = m->host->ss;
+    }
+    const MaSel& sel = m->sel[stream];
+    dvbs2gpu_bbts_ma_stats o = {};
+    o.packets = l.packets; o.nulls = l.nulls; o.ts_errs = l.ts_errs;
+    o.broken_joins = l.broken; o.undecided = l.undecided; o.frames = l.frames;
+    o.skipped_frames = ss.skipped; o.rejected_frames = ss.rejected;
+    o.issy_bytes = l.issy; o.iscr_valid = l.iscr_valid; o.last_iscr = l.iscr; o.carried = l.c;
+    o.selected = slot < sel.n; o.isi = o.selected ? sel.isi[slot] : -1;
+    *h_out = o;
+    return 0;
+}
+
+int dvbs2gpu_bbts_get_isi_seen(dvbs2gpu_bbts* b, int stream, uint32_t* mask8) {
+    if (!b || !mask8) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    BbtsMa* m = *v.ma;
+    if (!m || stream < 0 || stream >= v.nstreams) return DVBS2GPU_ERR_ARG;
+    MaStreamState ss;
+    if (v.ctx) {
+        HIP_TRY(hipSetDevice(v.ctx->device));
+        HIP_TRY(hipMemcpy(&ss, m->d_strm[m->cur] + stream, sizeof(ss), hipMemcpyDeviceToHost));
+    } else {
+        ss = m->host->ss;
+    }
+    for (int k = 0; k < 8; ++k) mask8[k] = ss.seen[k];
+    return 0;
+}
+
+}  // extern "C"
