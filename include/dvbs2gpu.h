@@ -536,8 +536,9 @@ int dvbs2gpu_dvbs_process_ts(dvbs2gpu_dvbs_demod* d, dvbs2gpu_dvbs_tail* t, int 
  * on DVBS2Demod's output (main.cpp:532-558), for `nstreams` independent streams with persistent state (synchronisation,
  * the TS packet cut by a frame boundary, three GSE reassembly slots).  BBFRAMEs are kbch/8 bytes each, as the engine emits them.
  * MPEG-TS frames (TS/GS = 11) are packetised on the GPU: header CRC-8 / DFL / SYNCD checks, resynchronisation at SYNCD, one
- * 0x47 + 187-byte packet per 188 bytes of data field.  A stream that carries a GSE frame (TS/GS = 01) in a call is parsed, for
- * that call, by the library's native host parser (GSE -> GRE, fragment reassembly with CRC-32), sharing the same state.
+ * 0x47 + 187-byte packet per 188 bytes of data field.  GSE frames (TS/GS = 01) are decapsulated on the GPU as well (GSE -> GRE,
+ * fragment reassembly with CRC-32, .cpp:212-383); the library's native host parser follows the same rules on the same state and
+ * runs a stream's call only where dvbs2gpu_bbts_set_gse_path or one of the two fallbacks below says so.
  * Where the reference is undefined the library does this: a GSE packet that would extend beyond the end of the input of the
  * call ends the parsing of its frame; a PDU that does not fit into the rest of the output buffer or whose reassembled length
  * is negative is dropped; a fragment overflowing the 64 KiB reassembly buffer frees its slot.
@@ -558,6 +559,52 @@ int dvbs2gpu_bbts_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, int cnt, uint8_t* 
  * [12] last_bb_cnt, [13] last_bb_proc, [14] last_ts_errs (main.cpp reads these for its status lines); n_out >= 15;
  * with n_out >= 17 also [15] synched, [16] bytes of the carried partial packet */
 int dvbs2gpu_bbts_get_stats(dvbs2gpu_bbts* b, int stream, int32_t* h_out, int n_out);
+
+/* ---- GSE (the GSE branch of work(), .cpp:212-383).  Output per PDU: a GRE header 00 00, the protocol type in two more bytes
+ * for IPv4 / IPv6 (0x0800 / 0x86DD, .cpp:258-275 and :355-371), then the PDU; packets back to back, nothing between them.
+ * mode 0 (default): GSE frames are parsed by the GPU kernels.  mode 1: a stream that carries a GSE frame in a call is handed, for
+ * that call, to the host parser (six blocking copies per stream and call; kept for comparison).  Both give the same bytes, state and
+ * counters, and the mode may change between calls.  In mode 0 the host parser still runs a stream's call when
+ *   (a) one of its frames holds more than 256 GSE packets (the per-frame record capacity), or
+ *   (b) an output-capacity rule would fire in it: a GRE packet that does not fit into cap and is dropped, or no more than 188 bytes
+ *       left after a TS frame (.cpp:178,206).  cap >= nframes*kbch/8 + 376 + the bytes of the reassemblies open before the call
+ *       (at most 3 x 65536) keeps (b) away. */
+int dvbs2gpu_bbts_set_gse_path(dvbs2gpu_bbts* b, int mode);
+typedef struct dvbs2gpu_gse_stats {
+    int64_t frames;               /* GSE frames whose data field was walked (.cpp:212: UPL 0, no ISSY, no NPD) */
+    int64_t packets;              /* GSE packets taken from them (.cpp:224-252) */
+    int64_t complete_pdus;        /* unfragmented PDUs written (.cpp:254-283) */
+    int64_t reassembled_pdus;     /* PDUs written after reassembly with a good CRC-32 (.cpp:340-377) */
+    int64_t crc_failures;         /* END packets whose CRC-32 did not match (.cpp:351) */
+    int64_t dropped_no_slot;      /* START packets that found all three reassembly slots taken (.cpp:289-300) */
+    int64_t dropped_overflow;     /* reassemblies given up because a fragment would pass 64 KiB */
+    int64_t dropped_no_fit;       /* PDUs that did not fit into the rest of the output, or whose reassembled length was negative */
+    int64_t bytes_delivered;      /* GRE bytes written, headers included */
+    int64_t host_fallback_calls;  /* calls of this stream the host parser ran in mode 0 = the next two */
+    int64_t fallback_records;     /* (a) */
+    int64_t fallback_capacity;    /* (b) */
+} dvbs2gpu_gse_stats;
+int dvbs2gpu_bbts_get_gse_stats(dvbs2gpu_bbts* b, int stream, dvbs2gpu_gse_stats* h_out);
+/* One row per GRE packet the LAST call wrote for the stream, in output order (the reference sends the whole call's output as one
+ * datagram, main.cpp:551-555; with the rows a caller sends one per PDU).  The TS packets of a call that mixes TS and GSE frames are
+ * not rows: they are the bytes of [0, out_bytes) that no row covers. */
+#define DVBS2GPU_GSE_PDU_REASSEMBLED 1
+#define DVBS2GPU_GSE_PDU_LABEL 2     /* the packet (the START packet) carried a 6-byte label (.cpp:236-244) */
+typedef struct dvbs2gpu_gse_pdu {
+    uint32_t offset;     /* of the GRE header in the stream's output buffer */
+    uint32_t bytes;      /* GRE header + PDU */
+    uint16_t protocol;   /* GSE protocol type; 0x0800 / 0x86DD: 4-byte GRE header, else 2 bytes */
+    uint16_t flags;
+    uint32_t reserved;
+} dvbs2gpu_gse_pdu;
+/* h_rows[cap] (host); *n = rows of the last call, of which min(*n, cap) are written */
+int dvbs2gpu_bbts_get_pdu_table(dvbs2gpu_bbts* b, int stream, dvbs2gpu_gse_pdu* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call: *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_bbts_get_pdu_table_device(dvbs2gpu_bbts* b, int stream, const dvbs2gpu_gse_pdu** d_rows, int* n);
+/* Host only, no device needed: a CRC-32/MPEG register (polynomial 0x04c11db7, MSB first, as .cpp:85-102) advanced over nbytes
+ * zero bytes, = crc * x^(8 nbytes) mod P, with the arithmetic the GSE kernels use.  crc(a ++ b) = shift(crc(a), len b) ^ crc0(b),
+ * crc0 = the CRC from a zero register. */
+uint32_t dvbs2gpu_crc32_mpeg_shift(uint32_t crc, uint32_t nbytes);
 
 /* ------------------------------------------------------------------ BBFRAME -> TS, mode-adaptation mode
  * What the reference's parser leaves out, for multiple-input-stream (MIS) and ACM/VCM carriers: ISI demultiplexing, ISSY and DNP

@@ -209,6 +209,28 @@ public:
         return n;
     }
 
+    /* ---- GSE (bbframe_ts_parser.cpp:212-383).  work() writes GRE packets back to back; the table has one row per packet of the last
+     * work(): offset, bytes, protocol type, flags, so that a sink can send one datagram per PDU (main.cpp:551-555 sends one per call). */
+    std::vector<dvbs2gpu_gse_pdu> pdu_table() {
+        if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
+        int n = 0;
+        check(dvbs2gpu_bbts_get_pdu_table(h, 0, nullptr, 0, &n));
+        std::vector<dvbs2gpu_gse_pdu> rows(n);
+        if (n > 0) check(dvbs2gpu_bbts_get_pdu_table(h, 0, rows.data(), n, &n));
+        return rows;
+    }
+    dvbs2gpu_gse_stats gse_stats() {
+        if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
+        dvbs2gpu_gse_stats s;
+        check(dvbs2gpu_bbts_get_gse_stats(h, 0, &s));
+        return s;
+    }
+    /* 0: GSE frames are parsed on the GPU (default); 1: by the library's host parser */
+    void set_gse_path(int mode) {
+        if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
+        check(dvbs2gpu_bbts_set_gse_path(h, mode));
+    }
+
     /* ---- mode-adaptation mode (include/dvbs2gpu.h): multistream and ACM/VCM carriers.  Call after setFrameSize(); cfg == nullptr
      * switches it off again.  The reference-shaped work() above is not affected by it. */
     void setModeAdaptation(const dvbs2gpu_bbts_ma_cfg* cfg) {

@@ -70,6 +70,17 @@ class BbtsMaStats(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class GseStats(C.Structure):
+    """dvbs2gpu_gse_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('frames', 'packets', 'complete_pdus', 'reassembled_pdus', 'crc_failures', 'dropped_no_slot', 'dropped_overflow',
+                                         'dropped_no_fit', 'bytes_delivered', 'host_fallback_calls', 'fallback_records', 'fallback_capacity')]
+
+
+class GsePdu(C.Structure):
+    """dvbs2gpu_gse_pdu"""
+    _fields_ = [('offset', C.c_uint32), ('bytes', C.c_uint32), ('protocol', C.c_uint16), ('flags', C.c_uint16), ('reserved', C.c_uint32)]
+
+
 class FrameQuality(C.Structure):
     """dvbs2gpu_frame_quality"""
     _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('gain', C.c_float), ('phase', C.c_float), ('known_symbols', C.c_int32),
@@ -191,6 +202,11 @@ PROTOTYPES = {
     'dvbs2gpu_bbts_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i), _vp]),
     'dvbs2gpu_bbts_work': (_i, [_vp, _vp, _i, _vp, _i]),
     'dvbs2gpu_bbts_get_stats': (_i, [_vp, _i, C.POINTER(C.c_int32), _i]),
+    'dvbs2gpu_bbts_set_gse_path': (_i, [_vp, _i]),
+    'dvbs2gpu_bbts_get_gse_stats': (_i, [_vp, _i, C.POINTER(GseStats)]),
+    'dvbs2gpu_bbts_get_pdu_table': (_i, [_vp, _i, C.POINTER(GsePdu), _i, C.POINTER(_i)]),
+    'dvbs2gpu_bbts_get_pdu_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
+    'dvbs2gpu_crc32_mpeg_shift': (C.c_uint32, [C.c_uint32, C.c_uint32]),
     'dvbs2gpu_bbts_ma_default_cfg': (None, [C.POINTER(BbtsMaCfg)]),
     'dvbs2gpu_bbts_ma_get_layout': (_i, [C.POINTER(C.c_int32)]),
     'dvbs2gpu_bbts_create_host': (_i, [_i, _i, C.POINTER(_vp)]),
@@ -906,6 +922,33 @@ class BbTsParserBank(_Handle):
         d = {k: a[i] for i, k in enumerate(self.HEADER_FIELDS)}
         d.update(last_gse_crc_err=a[11], last_bb_cnt=a[12], last_bb_proc=a[13], last_ts_errs=a[14], synched=a[15], count=a[16])
         return d
+
+    # ---- GSE (include/dvbs2gpu.h): where GSE frames are parsed, the counters, and one row per GRE packet of the last call
+    GSE_DEVICE, GSE_HOST = 0, 1
+    PDU_REASSEMBLED, PDU_LABEL = 1, 2
+
+    def set_gse_path(self, mode):
+        """0: the GPU kernels (default); 1: the library's host parser, for comparison"""
+        self.eng._check(self.lib.dvbs2gpu_bbts_set_gse_path(self.h, int(mode)))
+
+    def gse_stats(self, stream=0):
+        st = GseStats()
+        self.eng._check(self.lib.dvbs2gpu_bbts_get_gse_stats(self.h, int(stream), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in GseStats._fields_}
+
+    def pdu_table(self, stream=0):
+        """[(offset in the stream's output, bytes, protocol type, flags)] of the last call, in output order"""
+        n = C.c_int()
+        self.eng._check(self.lib.dvbs2gpu_bbts_get_pdu_table(self.h, int(stream), None, 0, C.byref(n)))
+        rows = (GsePdu * max(n.value, 1))()
+        self.eng._check(self.lib.dvbs2gpu_bbts_get_pdu_table(self.h, int(stream), rows, n.value, C.byref(n)))
+        return [(r.offset, r.bytes, r.protocol, r.flags) for r in rows[:n.value]]
+
+    def pdu_table_device(self, stream=0):
+        """(device pointer or None, rows): the same table as dvbs2gpu_gse_pdu records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self.eng._check(self.lib.dvbs2gpu_bbts_get_pdu_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     # ---- mode-adaptation mode (include/dvbs2gpu.h): ISI demultiplexing, ISSY / DNP, null-packet reinsertion, CRC-8, per-frame sizes
     MA_SLOTS = 8

@@ -8,9 +8,10 @@
 //                      one copy descriptor per frame (the only serial part: a handful of integer operations per frame);
 //   bbts_emit_kernel   one workgroup per (frame, stream) moves the bytes: 0x47 + 187 bytes per packet, the first packet of
 //                      a frame completed from the tail of the previous one (HBM-bound byte movement, 2 x DFL/8 per frame).
-// GSE frames (TS/GS = 01) are a byte-serial protocol parse with up to 64 KiB of reassembly state per fragment id; a stream
-// that carries one in a call is handed, for that call, to the native host parser below (BbtsHostParser), which shares
-// the synchronisation state with the device path.
+// GSE frames (TS/GS = 01) stay on the device too (bbts_gse.hip): a stream that carries one in a call is parsed, for that call, by
+// the four GSE kernels, which also emit the TS frames of a mixed call.  The native host parser below (BbtsHostParser) is the second
+// implementation of the same rules: it runs a stream's call when dvbs2gpu_bbts_set_gse_path chose it, when a frame has more packets
+// than GSE_PKT_CAP records, or when one of its output-capacity rules would fire; it shares all state with the device path.
 #include "ctx.h"
 #include "bbts_common.h"
 
@@ -20,21 +21,6 @@ using namespace s2;
 #define g_err last_error()
 
 namespace s2 {
-
-constexpr int TS = 188;
-constexpr int REASM_STRIDE = 192;
-
-struct BbtsDevState {              // per stream, device resident
-    int synched, count;
-    int hdr[11];                   // ts_gs, sis_mis, ccm_acm, issyi, npd, ro, isi, upl, dfl, sync, syncd (BBHeader, bbframe_ts_parser.h:37-66)
-    int last_cnt, last_proc, pad;
-};
-struct BbtsFrameDesc {
-    int src, npk, pre_len, pre_src, out_off, pad[3];   // pre_src < 0: the carried partial lives in the state buffer
-};
-struct BbtsStreamPlan {
-    int needs_host, out_bytes, fin_len, fin_src;       // fin_src < 0: keep the state buffer's bytes
-};
 
 __global__ void bbts_plan_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nframes, int nstreams, int fbytes, int max_dfl,
                                  int max_frames, BbtsDevState* __restrict__ state, BbtsFrameDesc* __restrict__ desc,
@@ -61,7 +47,7 @@ __global__ void bbts_plan_kernel(const uint8_t* const* __restrict__ in, const in
         }
         for (int k = 0; k < 11; ++k) st.hdr[k] = h.v[k];
         ++proc;
-        if (h.v[0] == 1) { needs_host = 1; break; }
+        if (h.v[0] == 1) { needs_host = GSE_SEEN; break; }
         if (h.v[0] == 3) {
             if (df >= TS) {
                 // the reference's while loop (.cpp:178-199) in closed form: the first packet absorbs the carried partial
@@ -106,34 +92,7 @@ __global__ void __launch_bounds__(256) bbts_emit_kernel(const uint8_t* const* __
     if (f >= nframes[s]) return;
     const BbtsFrameDesc e = desc[(size_t)s * max_frames + f];
     if (e.npk == 0) return;
-    const uint8_t* pre = e.pre_src < 0 ? old : bb + e.pre_src;
-    const uint8_t* src = bb + e.src - e.pre_len;          // virtual stream = partial ++ data field
-    uint8_t* o = out[s] + e.out_off;
-    auto fetch = [&](int i) -> unsigned {                  // output byte i of this frame's packets
-        const int b = i % TS;
-        if (b == 0) return 0x47u;                          // TS_SYNC_BYTE in place of the CRC-8 of the previous packet
-        const int u = i - 1;                               // packet p is bytes [188 p, 188 p + 187) of the virtual stream; its
-        return u < e.pre_len ? pre[u] : src[u];            // 188th byte (the CRC-8 of this packet) is dropped
-    };
-    const int nbytes = e.npk * TS;
-    if ((reinterpret_cast<uintptr_t>(o) & 3) == 0) {
-        // 188 = 4 * 47: an output dword never straddles two packets, and its four source bytes are contiguous (one unaligned
-        // dword load at src + i - 1; the byte under a packet's sync position is replaced)
-        typedef unsigned __attribute__((aligned(1))) unaligned_u32;
-        for (int w = threadIdx.x; w < nbytes / 4; w += blockDim.x) {
-            const int i = 4 * w;
-            unsigned v;
-            if (i - 1 >= e.pre_len) {
-                v = *reinterpret_cast<const unaligned_u32*>(src + i - 1);
-                if (i % TS == 0) v = (v & ~0xffu) | 0x47u;
-            } else {
-                v = fetch(i) | fetch(i + 1) << 8 | fetch(i + 2) << 16 | fetch(i + 3) << 24;
-            }
-            reinterpret_cast<unsigned*>(o)[w] = v;
-        }
-    } else {
-        for (int i = threadIdx.x; i < nbytes; i += blockDim.x) o[i] = (uint8_t)fetch(i);
-    }
+    bbts_emit_frame(bb, old, e, out[s] + e.out_off);
 }
 
 // ---------------------------------------------------------------------------------------------- host parser (GSE streams)
@@ -146,6 +105,18 @@ public:
     uint8_t partial[TS] = {0};
     int hdr[11] = {0};
     int last_gse_crc_err = 0, last_cnt = 0, last_proc = 0;
+    GseCounters gc = {};                        // what dvbs2gpu_bbts_get_gse_stats reports, counted like gse_stream_kernel does
+    std::vector<dvbs2gpu_gse_pdu> rows;         // one per GRE packet written by the last run()
+    struct Reassembly {
+        bool busy = false;
+        int frag_id = 0;
+        long fill = 0;
+        unsigned proto = 0;
+        uint32_t crc = 0;
+        bool label = false;
+        std::unique_ptr<uint8_t[]> data;      // 65536 bytes, allocated on first use
+    };
+    Reassembly slots_[3];
 
     BbtsHostParser() {
         for (unsigned i = 0; i < 256; ++i) {
@@ -158,6 +129,7 @@ public:
     // returns bytes produced or DVBS2GPU_ERR_CAPACITY
     int run(const uint8_t* bb, int cnt, int fbytes, int max_dfl, uint8_t* out, int cap) {
         in_ = bb; in_end_ = (long)fbytes * cnt; out_ = out; cap_ = cap; w_ = 0;
+        rows.clear();
         int proc = 0;
         bool stop = false;
         for (int f = 0; f < cnt && !stop; ++f) {
@@ -180,7 +152,7 @@ public:
                 break;
             }
             case 1:
-                if (!h.v[3] && !h.v[4] && h.v[7] == 0) gse_frame(pos, h.v[8] / 8);
+                if (!h.v[3] && !h.v[4] && h.v[7] == 0) { ++gc.frames; gse_frame(pos, h.v[8] / 8); }
                 break;
             default: break;
             }
@@ -190,15 +162,6 @@ public:
     }
 
 private:
-    struct Reassembly {
-        bool busy = false;
-        int frag_id = 0;
-        long fill = 0;
-        unsigned proto = 0;
-        uint32_t crc = 0;
-        std::unique_ptr<uint8_t[]> data;      // 65536 bytes, allocated on first use
-    };
-    Reassembly slots_[3];
     uint32_t tab_[256];
     const uint8_t* in_ = nullptr;
     long in_end_ = 0;
@@ -229,10 +192,13 @@ private:
         if (df > 0) { memcpy(partial, in_ + pos, df); count = df; }
         return cap_ - w_ <= TS ? 1 : 0;
     }
-    void emit_gre(unsigned proto, const uint8_t* p, long n) {
+    void emit_gre(unsigned proto, const uint8_t* p, long n, bool reassembled, bool label) {
         const bool known = proto == 0x0800 || proto == 0x86DD;
         const long total = 2 + (known ? 2 : 0) + n;
-        if (n < 0 || w_ + total > cap_) return;
+        if (n < 0 || w_ + total > cap_) { ++gc.dropped_no_fit; return; }
+        ++(reassembled ? gc.reassembled_pdus : gc.complete_pdus);
+        gc.bytes_delivered += total;
+        rows.push_back({(uint32_t)w_, (uint32_t)total, (uint16_t)proto, (uint16_t)((reassembled ? 1 : 0) | (label ? 2 : 0)), 0});
         uint8_t* o = out_ + w_;
         *o++ = 0; *o++ = 0;                    // GRE: no checksum, no key, no sequence number, version 0
         if (known) { *o++ = (uint8_t)(proto >> 8); *o++ = (uint8_t)proto; }
@@ -255,17 +221,19 @@ private:
             const long plen = (field - fixed - label) & 0xffff;
             const long body = at + 2 + fixed + label;
             if (body + plen > in_end_) return;
+            ++gc.packets;
             if (first && last) {
-                emit_gre(in_[at + 2] << 8 | in_[at + 3], in_ + body, plen);
+                emit_gre(in_[at + 2] << 8 | in_[at + 3], in_ + body, plen, false, label != 0);
             } else {
                 const int id = in_[at + 2];
                 Reassembly* r = nullptr;
                 for (auto& s : slots_) {
                     if (first ? (!s.busy || s.frag_id == id) : (s.busy && s.frag_id == id)) { r = &s; break; }
                 }
+                if (!r && first) ++gc.dropped_no_slot;
                 if (r && first) {
                     if (!r->data) r->data.reset(new uint8_t[65536]);
-                    r->busy = true; r->frag_id = id;
+                    r->busy = true; r->frag_id = id; r->label = label != 0;
                     r->proto = in_[at + 5] << 8 | in_[at + 6];
                     memcpy(r->data.get(), in_ + body, plen);
                     r->fill = plen;
@@ -274,6 +242,7 @@ private:
                 } else if (r) {
                     if (r->fill + plen > 65536) {
                         r->busy = false;
+                        ++gc.dropped_overflow;
                     } else if (!last) {
                         memcpy(r->data.get() + r->fill, in_ + body, plen);
                         r->fill += plen;
@@ -286,7 +255,8 @@ private:
                         const uint32_t rx = (uint32_t)in_[body + plen - 4] << 24 | (uint32_t)in_[body + plen - 3] << 16 |
                                             (uint32_t)in_[body + plen - 2] << 8 | in_[body + plen - 1];
                         last_gse_crc_err = r->crc != rx;
-                        if (!last_gse_crc_err) emit_gre(r->proto, r->data.get(), r->fill);
+                        if (last_gse_crc_err) ++gc.crc_failures;
+                        else emit_gre(r->proto, r->data.get(), r->fill, true, r->label);
                     }
                 }
             }
@@ -312,6 +282,12 @@ struct dvbs2gpu_bbts {
     std::vector<BbtsStreamPlan> h_plan;
     std::vector<uint8_t> h_in, h_out;
     BbtsMa* ma = nullptr;                      // mode-adaptation mode (bbts_ma.hip); null while the mode is off
+    BbtsGse* gse = nullptr;                    // GSE storage on the device (bbts_gse.hip); allocated when the bank first meets a GSE frame
+    int gse_mode = 0;                          // dvbs2gpu_bbts_set_gse_path
+    std::vector<GseStreamOut> h_sout;
+    std::vector<int> nrows;                    // rows of the last call per stream; rows_host: they are in the host parser, not in HBM
+    std::vector<char> rows_host;
+    std::vector<long long> fb_records, fb_capacity;
 };
 
 namespace s2 {
@@ -326,7 +302,47 @@ int bbts_reset_reference_state(dvbs2gpu_bbts* b) {
     HIP_TRY(hipSetDevice(b->ctx->device));
     HIP_TRY(hipMemset(b->d_state, 0, (size_t)b->nstreams * sizeof(BbtsDevState)));
     for (auto& h : b->host) h.reset();
+    std::fill(b->nrows.begin(), b->nrows.end(), 0);
+    std::fill(b->fb_records.begin(), b->fb_records.end(), 0);
+    std::fill(b->fb_capacity.begin(), b->fb_capacity.end(), 0);
+    return bbts_gse_reset(b->gse);
+}
+
+// The GSE state of one stream lives in HBM once the bank has its device storage; a call that the host parser runs takes it
+// from there and returns it: slot bookkeeping, the bytes of the open reassemblies, the last CRC verdict.
+static int gse_state_to_host(dvbs2gpu_bbts* b, int i, BbtsHostParser& hp) {
+    GseDevState gs;
+    HIP_TRY(hipMemcpy(&gs, bbts_gse_state(b->gse) + i, sizeof(gs), hipMemcpyDeviceToHost));
+    hp.last_gse_crc_err = gs.crc_err;
+    for (int q = 0; q < 3; ++q) {
+        auto& r = hp.slots_[q];
+        r.busy = gs.slot[q].busy != 0; r.frag_id = gs.slot[q].frag_id; r.fill = gs.slot[q].fill; r.proto = gs.slot[q].proto;
+        r.crc = gs.slot[q].crc; r.label = gs.slot[q].label != 0;
+        if (!r.busy) continue;
+        if (!r.data) r.data.reset(new uint8_t[65536]);
+        if (r.fill > 0) HIP_TRY(hipMemcpy(r.data.get(), bbts_gse_slot_data(b->gse, i, q), r.fill, hipMemcpyDeviceToHost));
+    }
     return 0;
+}
+static int gse_state_to_device(dvbs2gpu_bbts* b, int i, const BbtsHostParser& hp) {
+    GseDevState gs;
+    HIP_TRY(hipMemcpy(&gs, bbts_gse_state(b->gse) + i, sizeof(gs), hipMemcpyDeviceToHost));
+    gs.crc_err = hp.last_gse_crc_err;
+    for (int q = 0; q < 3; ++q) {
+        const auto& r = hp.slots_[q];
+        gs.slot[q] = {r.busy ? 1 : 0, r.frag_id, (int)r.fill, r.label ? 1 : 0, r.proto, r.crc};
+        if (r.busy && r.fill > 0) HIP_TRY(hipMemcpy(bbts_gse_slot_data(b->gse, i, q), r.data.get(), r.fill, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(bbts_gse_state(b->gse) + i, &gs, sizeof(gs), hipMemcpyHostToDevice));
+    return 0;
+}
+// 3 x 64 KiB of reassembly storage per stream and the record / row tables: only for a bank that meets a GSE frame
+static int gse_storage(dvbs2gpu_bbts* b) {
+    if (b->gse) return 0;
+    int e = bbts_gse_create(b->nstreams, b->max_frames, &b->gse);
+    for (int i = 0; i < b->nstreams && !e; ++i)     // streams the host parser has served so far (dvbs2gpu_bbts_set_gse_path)
+        if (b->host[i]) e = gse_state_to_device(b, i, *b->host[i]);
+    return e;
 }
 }  // namespace s2
 
@@ -335,6 +351,7 @@ extern "C" {
 void dvbs2gpu_bbts_destroy(dvbs2gpu_bbts* b) {
     if (!b) return;
     bbts_ma_free(b->ma);
+    bbts_gse_free(b->gse);
     void* ps[] = {b->d_state, b->d_reasm[0], b->d_reasm[1], b->d_desc, b->d_plan, b->d_args, b->d_in1, b->d_out1};
     for (void* p : ps) if (p) (void)hipFree(p);
     delete b;
@@ -359,6 +376,9 @@ int dvbs2gpu_bbts_create(dvbs2gpu_ctx* ctx, int nstreams, int kbch_bits, int max
     b->ctx = ctx; b->nstreams = nstreams; b->kbch = kbch_bits; b->max_frames = max_frames;
     b->host.resize(nstreams);
     b->h_plan.resize(nstreams);
+    b->h_sout.resize(nstreams);
+    b->nrows.assign(nstreams, 0); b->rows_host.assign(nstreams, 0);
+    b->fb_records.assign(nstreams, 0); b->fb_capacity.assign(nstreams, 0);
     const size_t n = (size_t)nstreams;
     hipError_t e = hipSuccess;
     auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) { e = hipMalloc(p, bytes); if (e == hipSuccess) e = hipMemset(*p, 0, bytes); } };
@@ -399,19 +419,46 @@ int dvbs2gpu_bbts_process_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb, co
                        b->d_reasm[b->cur], b->d_reasm[b->cur ^ 1]);
     HIP_TRY(hipGetLastError());
     b->cur ^= 1;
-    HIP_TRY(hipMemcpyAsync(out_bytes, a_ob, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(b->h_plan.data(), b->d_plan, sizeof(BbtsStreamPlan) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // streams that carried a GSE frame: the whole call of that stream goes through the host parser, synchronisation
-    // state taken from and returned to the device
+    // GSE on the device: four more launches behind the two above, for the streams whose plan met a GSE frame.  A bank that
+    // has not met one yet learns it from the plan read-back, allocates its GSE storage and launches them then.
+    const bool device_gse = b->gse_mode == 0;
+    auto gse_pass = [&]() -> int {
+        return bbts_gse_launch(b->gse, st, a_in, a_out, a_nf, a_ob, fbytes, b->kbch - 80, cap, b->d_state, b->d_desc, b->d_plan, b->d_reasm[b->cur]);
+    };
+    auto read_back = [&](bool with_gse) -> int {
+        HIP_TRY(hipMemcpyAsync(out_bytes, a_ob, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(b->h_plan.data(), b->d_plan, sizeof(BbtsStreamPlan) * n, hipMemcpyDeviceToHost, st));
+        if (with_gse) HIP_TRY(hipMemcpyAsync(b->h_sout.data(), bbts_gse_stream_out(b->gse), sizeof(GseStreamOut) * n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return 0;
+    };
+    bool ran_gse = device_gse && b->gse;
+    if (ran_gse) { const int e = gse_pass(); if (e) return e; }
+    { const int e = read_back(ran_gse); if (e) return e; }
+    if (device_gse && !b->gse) {
+        bool seen = false;
+        for (int i = 0; i < n; ++i) seen |= b->h_plan[i].needs_host == GSE_SEEN;
+        if (seen) {
+            int e = gse_storage(b);
+            if (e || (e = gse_pass()) || (e = read_back(true))) return e;
+            ran_gse = true;
+        }
+    }
+    // streams left to the host parser: the whole call of that stream, all state taken from and returned to the device
     int rc = 0;
     for (int i = 0; i < n; ++i) {
-        if (!b->h_plan[i].needs_host) continue;
+        const int why = b->h_plan[i].needs_host;
+        b->rows_host[i] = 0;
+        b->nrows[i] = ran_gse && b->h_sout[i].ran ? b->h_sout[i].nrows : 0;
+        if (!why) continue;
+        if (why == GSE_FALLBACK_RECORDS) ++b->fb_records[i];
+        if (why == GSE_FALLBACK_CAPACITY) ++b->fb_capacity[i];
         if (!b->host[i]) b->host[i].reset(new BbtsHostParser());
         BbtsHostParser& hp = *b->host[i];
         BbtsDevState ds;
         HIP_TRY(hipMemcpy(&ds, b->d_state + i, sizeof(ds), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(hp.partial, b->d_reasm[b->cur] + (size_t)i * REASM_STRIDE, TS, hipMemcpyDeviceToHost));
+        if (b->gse) { const int e = gse_state_to_host(b, i, hp); if (e) return e; }
         hp.synched = ds.synched; hp.count = ds.count;
         memcpy(hp.hdr, ds.hdr, sizeof(ds.hdr));
         b->h_in.resize((size_t)nframes[i] * fbytes);
@@ -422,6 +469,9 @@ int dvbs2gpu_bbts_process_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb, co
         memcpy(ds.hdr, hp.hdr, sizeof(ds.hdr));
         HIP_TRY(hipMemcpy(b->d_state + i, &ds, sizeof(ds), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(b->d_reasm[b->cur] + (size_t)i * REASM_STRIDE, hp.partial, TS, hipMemcpyHostToDevice));
+        if (b->gse) { const int e = gse_state_to_device(b, i, hp); if (e) return e; }
+        b->rows_host[i] = 1;
+        b->nrows[i] = (int)hp.rows.size();
         if (got < 0) { out_bytes[i] = 0; rc = got; g_err = "output buffer too small for the TS packets of a GSE-carrying call"; continue; }
         out_bytes[i] = got;
         if (got > 0) HIP_TRY(hipMemcpy(d_out[i], b->h_out.data(), got, hipMemcpyHostToDevice));
@@ -463,9 +513,70 @@ int dvbs2gpu_bbts_get_stats(dvbs2gpu_bbts* b, int stream, int32_t* h_out, int n_
     HIP_TRY(hipMemcpy(&ds, b->d_state + stream, sizeof(ds), hipMemcpyDeviceToHost));
     for (int i = 0; i < 11; ++i) h_out[i] = ds.hdr[i];
     h_out[11] = b->host[stream] ? b->host[stream]->last_gse_crc_err : 0;
+    if (b->gse) {
+        GseDevState gs;
+        HIP_TRY(hipMemcpy(&gs, bbts_gse_state(b->gse) + stream, sizeof(gs), hipMemcpyDeviceToHost));
+        h_out[11] = gs.crc_err;
+    }
     h_out[12] = ds.last_cnt; h_out[13] = ds.last_proc; h_out[14] = 0;
     if (n_out >= 17) { h_out[15] = ds.synched; h_out[16] = ds.count; }
     return 0;
+}
+
+int dvbs2gpu_bbts_set_gse_path(dvbs2gpu_bbts* b, int mode) {
+    if (!b || !b->ctx || (mode != 0 && mode != 1)) return DVBS2GPU_ERR_ARG;
+    b->gse_mode = mode;
+    return 0;
+}
+
+int dvbs2gpu_bbts_get_gse_stats(dvbs2gpu_bbts* b, int stream, dvbs2gpu_gse_stats* out) {
+    if (!b || !b->ctx || stream < 0 || stream >= b->nstreams || !out) return DVBS2GPU_ERR_ARG;
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    static_assert(sizeof(GseCounters) == 9 * sizeof(int64_t) && sizeof(dvbs2gpu_gse_stats) == 12 * sizeof(int64_t), "layout");
+    GseDevState gs = {};
+    if (b->gse) HIP_TRY(hipMemcpy(&gs, bbts_gse_state(b->gse) + stream, sizeof(gs), hipMemcpyDeviceToHost));
+    const GseCounters zero = {};
+    const GseCounters& h = b->host[stream] ? b->host[stream]->gc : zero;
+    const long long* x = &gs.cnt.frames;
+    const long long* y = &h.frames;
+    int64_t* o = &out->frames;
+    for (int k = 0; k < 9; ++k) o[k] = x[k] + y[k];      // each call of a stream is counted by the one parser that ran it
+    out->fallback_records = b->fb_records[stream]; out->fallback_capacity = b->fb_capacity[stream];
+    out->host_fallback_calls = out->fallback_records + out->fallback_capacity;
+    return 0;
+}
+
+int dvbs2gpu_bbts_get_pdu_table(dvbs2gpu_bbts* b, int stream, dvbs2gpu_gse_pdu* h_rows, int cap, int* n) {
+    if (!b || !b->ctx || stream < 0 || stream >= b->nstreams || !n || cap < 0 || (cap > 0 && !h_rows)) return DVBS2GPU_ERR_ARG;
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    *n = b->nrows[stream];
+    const int m = *n < cap ? *n : cap;
+    if (m <= 0) return 0;
+    if (b->rows_host[stream]) memcpy(h_rows, b->host[stream]->rows.data(), m * sizeof(dvbs2gpu_gse_pdu));
+    else HIP_TRY(hipMemcpy(h_rows, bbts_gse_rows(b->gse, stream), m * sizeof(dvbs2gpu_gse_pdu), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int dvbs2gpu_bbts_get_pdu_table_device(dvbs2gpu_bbts* b, int stream, const dvbs2gpu_gse_pdu** d_rows, int* n) {
+    if (!b || !b->ctx || stream < 0 || stream >= b->nstreams || !n || !d_rows) return DVBS2GPU_ERR_ARG;
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    *n = b->nrows[stream];
+    *d_rows = nullptr;
+    if (*n == 0) return 0;
+    if (b->rows_host[stream]) {                    // a call the host parser ran: its rows go to where the kernels put theirs
+        const int e = gse_storage(b);
+        if (e) return e;
+        if (*n > b->max_frames * GSE_PKT_CAP) { g_err = "more rows than the device table holds"; return DVBS2GPU_ERR_CAPACITY; }
+        HIP_TRY(hipMemcpy(bbts_gse_rows(b->gse, stream), b->host[stream]->rows.data(), *n * sizeof(dvbs2gpu_gse_pdu), hipMemcpyHostToDevice));
+    }
+    *d_rows = (const dvbs2gpu_gse_pdu*)bbts_gse_rows(b->gse, stream);
+    return 0;
+}
+
+uint32_t dvbs2gpu_crc32_mpeg_shift(uint32_t crc, uint32_t nbytes) {
+    uint32_t r = crc;
+    for (; nbytes >= (1u << 17); nbytes -= 1u << 16) r = crc32m_mulmod(r, crc32m_xpow(1u << 16));
+    return crc32m_mulmod(r, crc32m_xpow(nbytes));
 }
 
 }  // extern "C"

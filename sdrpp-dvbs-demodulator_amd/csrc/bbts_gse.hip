@@ -1,0 +1,421 @@
+// GSE decapsulation on the device for the BBFRAME -> TS / GSE parser bank: the rules of BbtsHostParser::gse_frame /
+// emit_gre / ts_frame (bbts.hip; dsp::dvbs2::BBFrameTSParser::work, dvbs2/bbframe_ts_parser.cpp:104-390) split into
+//   gse_scan_kernel     one workgroup per (frame, stream): header check, the frame staged in LDS, one lane follows the packet chain
+//                       (next = at + 2 + field is the only serial dependency) and writes one 16-byte record per packet; the waves then
+//                       compute, per fragment, the CRC-32 of its span from a zero register and x^(8 len) mod P, 64-byte chunks per lane;
+//   gse_stream_kernel   one lane per stream, over the frame and packet records only: synchronisation, TS descriptors, slot choice and
+//                       fill, the running CRC as crc' = crc * xpow ^ crc0, the END verdict, every output offset, the PDU table rows,
+//                       the capacity rules.  State is kept in registers and stored only when the call needs no fallback;
+//   gse_move_kernel     one workgroup per (frame, stream): TS packets, complete PDUs, and PDUs that END in this frame, gathered
+//                       from their fragments in the input and, for what earlier calls brought, from the slot buffer;
+//   gse_append_kernel   one workgroup per (slot, stream): fragments of PDUs still open go to the slot buffers; one more
+//                       workgroup per stream stores the carried TS partial.
+// The slot buffers are only READ by gse_move_kernel and only WRITTEN by gse_append_kernel, a later launch on the same stream:
+// a slot restarted within the call is written at offset 0 after the PDU that ended in it has been gathered.
+#include "ctx.h"
+#include "bbts_common.h"
+
+using namespace s2;
+
+namespace s2 {
+
+struct BbtsGse {
+    int nstreams = 0, max_frames = 0;
+    GseDevState* d_state = nullptr;
+    GseFrameRec* d_frec = nullptr;          // [stream][max_frames]
+    GsePkt* d_pkt = nullptr;                // [stream][max_frames][GSE_PKT_CAP]
+    dvbs2gpu_gse_pdu* d_rows = nullptr;     // [stream][max_frames * GSE_PKT_CAP]
+    GseStreamOut* d_sout = nullptr;
+    uint8_t* d_slots = nullptr;             // [stream][3][GSE_SLOT_BYTES]
+};
+
+// ---------------------------------------------------------------------------------------------------------------- frame pass
+__global__ void __launch_bounds__(256) gse_scan_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nframes, int fbytes, int max_dfl,
+                                                       int max_frames, const BbtsDevState* __restrict__ state,
+                                                       const BbtsStreamPlan* __restrict__ plan, GseFrameRec* __restrict__ frec,
+                                                       GsePkt* __restrict__ pkts) {
+    const int s = blockIdx.y, f = blockIdx.x, tid = threadIdx.x;
+    if (plan[s].needs_host != GSE_SEEN || f >= nframes[s]) return;
+    __shared__ __attribute__((aligned(16))) uint8_t stage[8192];
+    __shared__ GsePkt rec[GSE_PKT_CAP];
+    __shared__ int span_at[GSE_PKT_CAP], span_len[GSE_PKT_CAP];
+    __shared__ GseFrameRec fr;
+    const uint8_t* bb = in[s];
+    const int base = f * fbytes, in_end = nframes[s] * fbytes;
+    if ((reinterpret_cast<uintptr_t>(bb + base) & 3) == 0) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(bb + base);
+        for (int i = tid; i < fbytes / 4; i += 256) reinterpret_cast<uint32_t*>(stage)[i] = src[i];
+        for (int i = (fbytes & ~3) + tid; i < fbytes; i += 256) stage[i] = bb[base + i];
+    } else {
+        for (int i = tid; i < fbytes; i += 256) stage[i] = bb[base + i];
+    }
+    __syncthreads();
+    auto rd = [&](int i) -> unsigned { return (i >= base && i < base + fbytes) ? stage[i - base] : bb[i]; };   // i < in_end
+    if (tid == 0) {
+        GseFrameRec r = {0, 0, 0, 0};
+        HeaderFields h;
+        if (header_ok(stage, max_dfl, &h)) {
+            HeaderFields hp;
+            const bool synched = f == 0 ? state[s].synched != 0 : header_ok(bb + base - fbytes, max_dfl, &hp);
+            int pos = base + 10;
+            if (!synched) { pos += h.v[10] / 8 + 1; r.resync = 1; }
+            r.pos = pos;
+            r.kind = h.v[0] == 3 ? 3 : 1;
+            if (h.v[0] == 1 && !h.v[3] && !h.v[4] && h.v[7] == 0) {
+                r.kind = 2;
+                int at = pos, n = 0;
+                const int end = pos + h.v[8] / 8;
+                while (at < end) {
+                    if (at + 2 > in_end) break;
+                    const unsigned h1 = rd(at);
+                    const bool first = h1 & 0x80, last = h1 & 0x40, label6 = (h1 & 0x30) == 0;
+                    if (!first && !last && label6) break;
+                    const unsigned field = (h1 & 0x0f) << 8 | rd(at + 1);
+                    const int fixed = first && last ? 2 : first ? 5 : 1;
+                    const int label = first && label6 ? 6 : 0;
+                    const int plen = (int)((field - fixed - label) & 0xffff);
+                    const int body = at + 2 + fixed + label;
+                    if (body + plen > in_end) break;
+                    if (n == GSE_PKT_CAP) { r.kind = 4; break; }
+                    GsePkt p = {(uint32_t)body, (uint32_t)plen, 0, 0};
+                    int kind, sa = body, sl = 0;
+                    if (first && last) {
+                        kind = GSE_COMPLETE;
+                        p.b = rd(at + 2) << 8 | rd(at + 3);
+                    } else {
+                        p.w1 |= rd(at + 2) << 16;
+                        if (first) { kind = GSE_START; p.b = rd(at + 5) << 8 | rd(at + 6); sa = at + 3; sl = body + plen - sa; }
+                        else if (!last) { kind = GSE_MIDDLE; sl = plen; }
+                        else { kind = GSE_END; sl = plen >= 4 ? plen - 4 : 0; }
+                    }
+                    p.w1 |= (uint32_t)kind << 24 | (uint32_t)(label ? 1 : 0) << 26;
+                    rec[n] = p; span_at[n] = sa; span_len[n] = sl;
+                    at = body + plen;
+                    ++n;
+                }
+                r.npkt = n;
+            }
+        }
+        fr = r;
+    }
+    __syncthreads();
+    const int n = fr.npkt;
+    // CRC-32 of every fragment's span from a zero register: a wave per packet, 64-byte chunks counted from the END of the
+    // span per lane, each moved to the end of the span by x^(8 * 64 m), XOR-reduced over the wave
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int k = wave; k < n; k += 4) {
+        const int kind = (rec[k].w1 >> 24) & 3;
+        if (kind == GSE_COMPLETE) continue;
+        const int sa = span_at[k], sl = span_len[k];
+        uint32_t acc = 0;
+        for (int m = lane; m * 64 < sl; m += 64) {
+            const int hi = sl - 64 * m, lo = hi > 64 ? hi - 64 : 0;
+            uint32_t c = 0;
+            for (int i = lo; i < hi; ++i) c = crc32m_byte(c, rd(sa + i));
+            acc ^= crc32m_mulmod(c, crc32m_xpow(64u * m));
+        }
+        for (int d = 32; d > 0; d >>= 1) acc ^= __shfl_xor(acc, d, 64);
+        if (lane == 0) {
+            const uint32_t xp = crc32m_xpow((uint32_t)sl);
+            if (kind == GSE_START) {
+                rec[k].a = crc32m_mulmod(0xffffffffu, xp) ^ acc;
+            } else if (kind == GSE_MIDDLE) {
+                rec[k].a = acc; rec[k].b = xp;
+            } else {
+                const int e = (int)rec[k].src + (int)(rec[k].w1 & 0xffff);
+                const uint32_t rx = rd(e - 4) << 24 | rd(e - 3) << 16 | rd(e - 2) << 8 | rd(e - 1);
+                rec[k].a = acc ^ rx; rec[k].b = xp;
+            }
+        }
+    }
+    __syncthreads();
+    GsePkt* o = pkts + ((size_t)s * max_frames + f) * GSE_PKT_CAP;
+    for (int k = tid; k < n; k += 256) o[k] = rec[k];
+    if (tid == 0) frec[(size_t)s * max_frames + f] = fr;
+}
+
+// --------------------------------------------------------------------------------------------------------------- stream pass
+__global__ void __launch_bounds__(64) gse_stream_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nframes, int nstreams, int fbytes,
+                                                        int max_frames, int cap, BbtsDevState* __restrict__ state, GseDevState* __restrict__ gstate,
+                                                        const GseFrameRec* __restrict__ frec, GsePkt* __restrict__ pkts,
+                                                        BbtsFrameDesc* __restrict__ desc, BbtsStreamPlan* __restrict__ plan,
+                                                        dvbs2gpu_gse_pdu* __restrict__ rows, GseStreamOut* __restrict__ sout,
+                                                        int* __restrict__ out_bytes) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nstreams) return;
+    GseStreamOut so = {{-1, -1, -1}, 0, 0, {0, 0, 0}};
+    if (plan[s].needs_host != GSE_SEEN) { sout[s] = so; return; }
+    BbtsDevState st = state[s];
+    GseDevState gs = gstate[s];
+    const uint8_t* bb = in[s];
+    const int nf = nframes[s];
+    BbtsFrameDesc* d = desc + (size_t)s * max_frames;
+    GsePkt* pk = pkts + (size_t)s * max_frames * GSE_PKT_CAP;
+    dvbs2gpu_gse_pdu* row = rows + (size_t)s * max_frames * GSE_PKT_CAP;
+    int synched = st.synched, pre_len = st.count, pre_src = -1, w = 0, proc = 0, last_good = -1, fallback = 0;
+    for (int f = 0; f < nf && !fallback; ++f) {
+        BbtsFrameDesc e = {0, 0, 0, -1, 0, {0, 0, 0}};
+        const GseFrameRec fr = frec[(size_t)s * max_frames + f];
+        if (fr.kind == 0) { synched = 0; d[f] = e; continue; }
+        if (fr.resync) pre_len = 0;
+        synched = 1;
+        last_good = f;
+        ++proc;
+        if (fr.kind == 4) { fallback = GSE_FALLBACK_RECORDS; break; }
+        if (fr.kind == 3) {
+            const int pos = fr.pos;
+            const int df = (bb[f * fbytes + 4] << 8 | bb[f * fbytes + 5]) / 8 - (pos - (f * fbytes + 10));
+            if (df >= TS) {
+                const int d1 = pre_len > 0 ? df - (TS - pre_len) : df;
+                const int n = (pre_len > 0 ? 1 : 0) + d1 / TS, rem = d1 % TS;
+                e.src = pos; e.npk = n; e.pre_len = pre_len; e.pre_src = pre_src; e.out_off = w;
+                w += n * TS;
+                pre_len = rem; pre_src = pos + df - rem;
+            } else if (df > 0) {
+                pre_len = df; pre_src = pos;
+            }
+            // the host parser's loop wants more than 188 bytes free before every packet and stops the call when no more than
+            // 188 are left after a TS frame (.cpp:178,206): both are seen from the sizes
+            if (cap - w <= TS) { fallback = GSE_FALLBACK_CAPACITY; break; }
+        } else if (fr.kind == 2) {
+            ++gs.cnt.frames;
+            for (int k = 0; k < fr.npkt && !fallback; ++k) {
+                const int idx = f * GSE_PKT_CAP + k;
+                GsePkt p = pk[idx];
+                const int plen = p.w1 & 0xffff, id = (p.w1 >> 16) & 0xff, kind = (p.w1 >> 24) & 3, label = (p.w1 >> 26) & 1;
+                ++gs.cnt.packets;
+                if (kind == GSE_COMPLETE) {
+                    const unsigned proto = p.b;
+                    const int total = 2 + ((proto == 0x0800 || proto == 0x86DD) ? 2 : 0) + plen;
+                    if (w + total > cap) { fallback = GSE_FALLBACK_CAPACITY; break; }
+                    row[so.nrows++] = {(uint32_t)w, (uint32_t)total, (uint16_t)proto, (uint16_t)(label ? 2 : 0), 0};
+                    pk[idx].a = (uint32_t)w;
+                    w += total;
+                    ++gs.cnt.complete_pdus; gs.cnt.bytes_delivered += total;
+                    continue;
+                }
+                int r = -1;
+#pragma unroll
+                for (int q = 2; q >= 0; --q) {
+                    const GseSlot& sq = gs.slot[q];
+                    if (kind == GSE_START ? (!sq.busy || sq.frag_id == id) : (sq.busy && sq.frag_id == id)) r = q;
+                }
+                if (r < 0) {
+                    if (kind == GSE_START) ++gs.cnt.dropped_no_slot;
+                    pk[idx].a = 0xffffffffu;
+                    continue;
+                }
+                // the slot and its chain end in registers (selected, not indexed: indexing would put the state into scratch)
+                GseSlot sl = r == 0 ? gs.slot[0] : r == 1 ? gs.slot[1] : gs.slot[2];
+                int ol = r == 0 ? so.open_last[0] : r == 1 ? so.open_last[1] : so.open_last[2];
+                auto put = [&]() {
+                    if (r == 0) { gs.slot[0] = sl; so.open_last[0] = ol; }
+                    else if (r == 1) { gs.slot[1] = sl; so.open_last[1] = ol; }
+                    else { gs.slot[2] = sl; so.open_last[2] = ol; }
+                };
+                const int link = ol >= 0 ? ol : -(1 + r);
+                if (kind == GSE_START) {
+                    sl.busy = 1; sl.frag_id = id; sl.proto = p.b; sl.fill = plen; sl.crc = p.a; sl.label = label;
+                    pk[idx].a = 0; pk[idx].b = (uint32_t)(-(1 + r));
+                    ol = idx;
+                } else if (sl.fill + plen > GSE_SLOT_BYTES) {
+                    sl.busy = 0; ol = -1;
+                    ++gs.cnt.dropped_overflow;
+                    pk[idx].a = 0xffffffffu;
+                } else if (kind == GSE_MIDDLE) {
+                    sl.crc = crc32m_mulmod(sl.crc, p.b) ^ p.a;
+                    pk[idx].a = (uint32_t)sl.fill; pk[idx].b = (uint32_t)link;
+                    sl.fill += plen;
+                    ol = idx;
+                } else {
+                    sl.busy = 0; ol = -1;
+                    put();
+                    const int len = sl.fill + plen - 4;
+                    gs.crc_err = crc32m_mulmod(sl.crc, p.b) != p.a;
+                    pk[idx].a = 0xffffffffu;
+                    if (gs.crc_err) { ++gs.cnt.crc_failures; continue; }
+                    const int total = 2 + ((sl.proto == 0x0800 || sl.proto == 0x86DD) ? 2 : 0) + len;
+                    if (len < 0) { ++gs.cnt.dropped_no_fit; continue; }
+                    if (w + total > cap) { fallback = GSE_FALLBACK_CAPACITY; break; }
+                    pk[idx].a = (uint32_t)so.nrows; pk[idx].b = (uint32_t)link;
+                    row[so.nrows++] = {(uint32_t)w, (uint32_t)total, (uint16_t)sl.proto, (uint16_t)(1 | (sl.label ? 2 : 0)), 0};
+                    w += total;
+                    ++gs.cnt.reassembled_pdus; gs.cnt.bytes_delivered += total;
+                }
+                put();
+            }
+        }
+        d[f] = e;
+    }
+    BbtsStreamPlan p;
+    if (fallback) {
+        // nothing of this call is kept: the host parser runs it again from the state as it was
+        for (int f = 0; f < nf; ++f) d[f].npk = 0;
+        so = {{-1, -1, -1}, 0, 0, {0, 0, 0}};
+        p.needs_host = fallback; p.out_bytes = 0; p.fin_len = 0; p.fin_src = -1;
+    } else {
+        if (last_good >= 0) {
+            const HeaderFields h = parse_bbheader(bb + last_good * fbytes);
+            for (int k = 0; k < 11; ++k) st.hdr[k] = h.v[k];
+        }
+        st.synched = synched; st.count = pre_len; st.last_cnt = nf; st.last_proc = proc;
+        state[s] = st;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) if (!gs.slot[q].busy) so.open_last[q] = -1;
+        gstate[s] = gs;
+        so.ran = 1;
+        p.needs_host = 0; p.out_bytes = w; p.fin_len = pre_src < 0 ? 0 : pre_len; p.fin_src = pre_src;
+    }
+    plan[s] = p;
+    sout[s] = so;
+    out_bytes[s] = p.out_bytes;
+}
+
+// ------------------------------------------------------------------------------------------------------------- byte movement
+// dword stores where the destination allows, the source read unaligned
+// (t of nt threads take part)
+__device__ inline void gse_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int n, int t, int nt) {
+    typedef unsigned __attribute__((aligned(1))) unaligned_u32;
+    if (n <= 0) return;
+    int head = (int)((4 - (reinterpret_cast<uintptr_t>(dst) & 3)) & 3);
+    if (head > n) head = n;
+    const int words = (n - head) / 4;
+    for (int i = t; i < head; i += nt) dst[i] = src[i];
+    for (int i = t; i < words; i += nt)
+        reinterpret_cast<unsigned*>(dst + head)[i] = *reinterpret_cast<const unaligned_u32*>(src + head + 4 * i);
+    for (int i = head + 4 * words + t; i < n; i += nt) dst[i] = src[i];
+}
+
+__device__ inline int gse_gre_header(uint8_t* o, unsigned proto, int t) {
+    const bool known = proto == 0x0800 || proto == 0x86DD;
+    if (t == 0) {
+        o[0] = 0; o[1] = 0;                    // GRE: no checksum, no key, no sequence number, version 0
+        if (known) { o[2] = (uint8_t)(proto >> 8); o[3] = (uint8_t)proto; }
+    }
+    return known ? 4 : 2;
+}
+
+__global__ void __launch_bounds__(256) gse_move_kernel(const uint8_t* const* __restrict__ in, uint8_t* const* __restrict__ out,
+                                                       const int* __restrict__ nframes, int max_frames, const BbtsFrameDesc* __restrict__ desc,
+                                                       const BbtsStreamPlan* __restrict__ plan, const GseFrameRec* __restrict__ frec,
+                                                       const GsePkt* __restrict__ pkts, const dvbs2gpu_gse_pdu* __restrict__ rows,
+                                                       const GseStreamOut* __restrict__ sout, const uint8_t* __restrict__ partial,
+                                                       const uint8_t* __restrict__ slots) {
+    const int s = blockIdx.y, f = blockIdx.x;
+    // streams the stream pass did not finish have no rows and no TS descriptors; streams without GSE were emitted before
+    if (f >= nframes[s] || !sout[s].ran) return;
+    const GseFrameRec fr = frec[(size_t)s * max_frames + f];
+    const uint8_t* bb = in[s];
+    if (fr.kind == 3) {
+        const BbtsFrameDesc e = desc[(size_t)s * max_frames + f];
+        if (e.npk > 0) bbts_emit_frame(bb, partial + (size_t)s * REASM_STRIDE, e, out[s] + e.out_off);
+        return;
+    }
+    if (fr.kind != 2) return;
+    const GsePkt* pk = pkts + (size_t)s * max_frames * GSE_PKT_CAP;
+    const dvbs2gpu_gse_pdu* row = rows + (size_t)s * max_frames * GSE_PKT_CAP;
+    const int lane = threadIdx.x & 63;
+    for (int k = threadIdx.x >> 6; k < fr.npkt; k += 4) {       // a wave per packet
+        const GsePkt p = pk[f * GSE_PKT_CAP + k];
+        if (p.a == 0xffffffffu) continue;
+        const int plen = p.w1 & 0xffff, kind = (p.w1 >> 24) & 3;
+        if (kind == GSE_COMPLETE) {
+            uint8_t* o = out[s] + p.a;
+            const int hl = gse_gre_header(o, p.b, lane);
+            gse_copy(o + hl, bb + p.src, plen, lane, 64);
+        } else if (kind == GSE_END) {
+            const dvbs2gpu_gse_pdu r = row[p.a];
+            uint8_t* o = out[s] + r.offset;
+            const int hl = gse_gre_header(o, r.protocol, lane);
+            const int len = (int)r.bytes - hl;
+            o += hl;
+            GsePkt q = p;
+            int off = len - (plen - 4);           // where this fragment starts in the PDU; the PDU is the first `len` bytes
+            for (;;) {
+                const int n = (int)(q.w1 & 0xffff);
+                gse_copy(o + off, bb + q.src, (off + n > len ? len - off : n), lane, 64);
+                const int link = (int)q.b;
+                if (link < 0) {
+                    gse_copy(o, slots + ((size_t)s * 3 + (-1 - link)) * GSE_SLOT_BYTES, off < len ? off : len, lane, 64);
+                    break;
+                }
+                q = pk[link];
+                off = (int)q.a;
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) gse_append_kernel(const uint8_t* const* __restrict__ in, const BbtsStreamPlan* __restrict__ plan,
+                                                         const GsePkt* __restrict__ pkts, int max_frames, const GseStreamOut* __restrict__ sout,
+                                                         uint8_t* __restrict__ partial, uint8_t* __restrict__ slots) {
+    const int s = blockIdx.y, r = blockIdx.x;
+    const BbtsStreamPlan p = plan[s];
+    if (!sout[s].ran) return;
+    const uint8_t* bb = in[s];
+    if (r == 3) {                                 // the TS partial carried into the next call (streams without GSE: fin_len 0 here)
+        if (p.fin_src >= 0) gse_copy(partial + (size_t)s * REASM_STRIDE, bb + p.fin_src, p.fin_len, threadIdx.x, 256);
+        return;
+    }
+    int at = sout[s].open_last[r];
+    if (at < 0) return;
+    const GsePkt* pk = pkts + (size_t)s * max_frames * GSE_PKT_CAP;
+    uint8_t* buf = slots + ((size_t)s * 3 + r) * GSE_SLOT_BYTES;
+    while (at >= 0) {
+        const GsePkt q = pk[at];
+        gse_copy(buf + q.a, bb + q.src, (int)(q.w1 & 0xffff), threadIdx.x, 256);      // fill + length <= 64 KiB by the overflow rule
+        at = (int)q.b;
+    }
+}
+
+// -------------------------------------------------------------------------------------------------------------------- host
+void bbts_gse_free(BbtsGse* g) {
+    if (!g) return;
+    void* ps[] = {g->d_state, g->d_frec, g->d_pkt, g->d_rows, g->d_sout, g->d_slots};
+    for (void* p : ps) if (p) (void)hipFree(p);
+    delete g;
+}
+
+int bbts_gse_create(int nstreams, int max_frames, BbtsGse** out) {
+    auto g = new BbtsGse();
+    g->nstreams = nstreams; g->max_frames = max_frames;
+    const size_t n = (size_t)nstreams, np = n * max_frames * GSE_PKT_CAP;
+    hipError_t e = hipSuccess;
+    auto A = [&](void** p, size_t bytes, bool zero) { if (e == hipSuccess) { e = hipMalloc(p, bytes); if (e == hipSuccess && zero) e = hipMemset(*p, 0, bytes); } };
+    A((void**)&g->d_state, n * sizeof(GseDevState), true);
+    A((void**)&g->d_frec, n * max_frames * sizeof(GseFrameRec), true);
+    A((void**)&g->d_pkt, np * sizeof(GsePkt), false);
+    A((void**)&g->d_rows, np * sizeof(dvbs2gpu_gse_pdu), false);
+    A((void**)&g->d_sout, n * sizeof(GseStreamOut), true);
+    A((void**)&g->d_slots, n * 3 * GSE_SLOT_BYTES, false);
+    if (e != hipSuccess) { bbts_gse_free(g); return fail_hip(e, "hipMalloc(bbts gse)"); }
+    *out = g;
+    return 0;
+}
+
+int bbts_gse_reset(BbtsGse* g) {
+    if (!g) return 0;
+    HIP_TRY(hipMemset(g->d_state, 0, (size_t)g->nstreams * sizeof(GseDevState)));
+    HIP_TRY(hipMemset(g->d_sout, 0, (size_t)g->nstreams * sizeof(GseStreamOut)));
+    return 0;
+}
+
+GseDevState* bbts_gse_state(BbtsGse* g) { return g->d_state; }
+uint8_t* bbts_gse_slot_data(BbtsGse* g, int stream, int slot) { return g->d_slots + ((size_t)stream * 3 + slot) * GSE_SLOT_BYTES; }
+GseStreamOut* bbts_gse_stream_out(BbtsGse* g) { return g->d_sout; }
+void* bbts_gse_rows(BbtsGse* g, int stream) { return g->d_rows + (size_t)stream * g->max_frames * GSE_PKT_CAP; }
+
+int bbts_gse_launch(BbtsGse* g, hipStream_t st, const uint8_t* const* d_in, uint8_t* const* d_out, const int* d_nframes, int* d_out_bytes,
+                    int fbytes, int max_dfl, int cap, BbtsDevState* d_state, BbtsFrameDesc* d_desc, BbtsStreamPlan* d_plan, uint8_t* d_partial) {
+    const int n = g->nstreams, mf = g->max_frames;
+    hipLaunchKernelGGL(gse_scan_kernel, dim3(mf, n), dim3(256), 0, st, d_in, d_nframes, fbytes, max_dfl, mf, d_state, d_plan, g->d_frec, g->d_pkt);
+    hipLaunchKernelGGL(gse_stream_kernel, dim3((n + 63) / 64), dim3(64), 0, st, d_in, d_nframes, n, fbytes, mf, cap, d_state, g->d_state, g->d_frec,
+                       g->d_pkt, d_desc, d_plan, g->d_rows, g->d_sout, d_out_bytes);
+    hipLaunchKernelGGL(gse_move_kernel, dim3(mf, n), dim3(256), 0, st, d_in, d_out, d_nframes, mf, d_desc, d_plan, g->d_frec, g->d_pkt, g->d_rows,
+                       g->d_sout, d_partial, g->d_slots);
+    hipLaunchKernelGGL(gse_append_kernel, dim3(4, n), dim3(256), 0, st, d_in, d_plan, g->d_pkt, mf, g->d_sout, d_partial, g->d_slots);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace s2

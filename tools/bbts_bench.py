@@ -2,7 +2,11 @@
 """BBFRAME -> TS parser bank timing: S streams x F BBFRAMEs of 8PSK 3/4 normal frames (kbch 48408) per call,
 frames resident in HBM.  Prints one JSON line: packets/s, frames/s, GB/s moved (read DFL/8 + write 188 per 188) against HBM.
 --ma: the same frames through the mode-adaptation mode (CCM sizes, SIS, no ISSY / NPD: the same bytes in and out, so the two figures
-compare like with like; MA_ISSY=2|3 and MA_NPD=1 in the environment add the fields, payload then from tests/ma_ref.py)."""
+compare like with like; MA_ISSY=2|3 and MA_NPD=1 in the environment add the fields, payload then from tests/ma_ref.py).
+--gse: well-formed GSE data fields instead (the transmitter of tests/test_gpu_gse.py: 45 % of the packets complete PDUs of 40-1500 bytes,
+20 % START packets of PDUs cut into 2-5 fragments of 40-1400 bytes, the rest their continuations; 64 different streams repeated over the
+bank), for 4096, 64 and 1 streams x 8 frames per call, the device path and the forced host path (dvbs2gpu_bbts_set_gse_path) timed in
+alternation in one process; one JSON line per bank size."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -14,6 +18,60 @@ import orc_bbts as B
 
 pkg = g.load_package()
 eng = pkg.Engine(0)
+
+
+def gse_bench():
+    import ctypes as C
+    import test_gpu_gse as T
+    kbch, F, P = int(os.environ.get('KBCH', '48408')), 8, 64
+    fb = kbch // 8
+    pats = []
+    for p in range(P):
+        pk, _ = T.transmitter(np.random.default_rng(p), 4 * F * (fb - 10))
+        fr = T.pack_frames(pk, kbch)[:4 * F]
+        assert len(fr) == 4 * F
+        pats.append(torch.from_numpy(fr).cuda())
+    cap = F * fb + 376 + 3 * 7000          # three open reassemblies of this traffic hold at most 5 x 1400 bytes each
+    for S in [int(x) for x in os.environ.get('STREAMS', '4096,64,1').split(',')]:
+        outs = torch.zeros((S, cap), dtype=torch.uint8, device='cuda')
+        pout = (C.c_void_p * S)(*[outs[i].data_ptr() for i in range(S)])
+        pin = [(C.c_void_p * S)(*[pats[i % P][k * F:(k + 1) * F].data_ptr() for i in range(S)]) for k in range(4)]
+        cnt, nb = (C.c_int * S)(*[F] * S), (C.c_int * S)()
+        banks = {}
+        for name, mode in (('device', 0), ('host', 1)):
+            banks[name] = pkg.BbTsParserBank(eng, S, kbch, F)
+            banks[name].set_gse_path(mode)
+
+        def run(name, k):
+            eng._check(banks[name].lib.dvbs2gpu_bbts_process_batch(banks[name].h, pin[k], cnt, pout, cap, nb, eng._stream()))
+            return sum(nb)
+        res = {'device': [], 'host': []}
+        pdus = {}
+        reps = int(os.environ.get('REPS', '5'))
+        for r in range(reps + 1):                       # round 0 warms up (and allocates the device path's GSE storage)
+            for name in ('device', 'host'):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                tot = sum(run(name, k) for k in range(4))
+                torch.cuda.synchronize()
+                if r:
+                    res[name].append(((time.perf_counter() - t0) / 4, tot / 4))
+        line = {'mode': 'gse', 'streams': S, 'frames_per_call': F, 'kbch': kbch}
+        for name in ('device', 'host'):
+            st = [banks[name].gse_stats(i) for i in range(min(S, P))]
+            per_call = sum(x['complete_pdus'] + x['reassembled_pdus'] for x in st) / len(st) * S / (4 * (reps + 1))
+            dt = float(np.median([a for a, _ in res[name]]))
+            line[name] = {'ms_per_call': round(dt * 1e3, 3), 'min_ms': round(min(a for a, _ in res[name]) * 1e3, 3), 'pdus_per_s': round(per_call / dt),
+                          'GB_per_s_read_plus_write': round((S * F * fb + res[name][0][1]) / dt / 1e9, 2),
+                          'host_fallback_calls': sum(x['host_fallback_calls'] for x in st)}
+        line['host_over_device'] = round(line['host']['ms_per_call'] / line['device']['ms_per_call'], 1)
+        line['includes'] = 'host arg upload + sync per call'
+        print(json.dumps(line), flush=True)
+
+
+if '--gse' in sys.argv:
+    gse_bench()
+    sys.exit(0)
 S = int(os.environ.get('STREAMS', '4096'))
 F = int(os.environ.get('FRAMES', '4'))
 KBCH = int(os.environ.get('KBCH', '48408'))
