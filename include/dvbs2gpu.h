@@ -55,7 +55,7 @@ int dvbs2gpu_set_option(dvbs2gpu_ctx* ctx, const char* name, int value);
 /* Read-only introspection (no reference counterpart; bench.py records the run-time balancer's final state and the launches a drop-in call costs with it).
  * Names: "kernel_launches" (kernel launches of the whole library in this process so far), "g_prio_duty" / "g_prio_auto" / "g_prio_hold" (the pipelined mode's priority
  * share of the timing loop, whether it is balanced at run time, calls the balancer still rests), "stage_pipeline_on" (the last CCM batch ran its post stages behind
- * every front-end slice), "pipelined", "num_cus", "fec_part_on" (always 0: the FEC partition stream it reported is gone; kept because bench.py --full reads it). */
+ * every front-end slice), "pipelined", "num_cus", "engine_streams" (HIP streams the context owns right now), "fec_part_on" (always 0: the FEC partition stream it reported is gone; kept because bench.py --full reads it). */
 int dvbs2gpu_get_state(dvbs2gpu_ctx* ctx, const char* name, long long* value);
 /* Test / bench aid: the pipelined CCM decoder job that configuration group `slot` (0 for a single-configuration batch) DELIVERED last -- what the decoder read and what it
  * wrote, still in place until the group starts another job of the same parity (two calls later).  out10 = {device pointer of the LLRs [nf][N] int8, device pointer of the

@@ -402,6 +402,16 @@ int dvbs2gpu_get_state(dvbs2gpu_ctx* ctx, const char* name, long long* value) {
     else if (n == "stage_pipeline_on") *value = ctx->last_call_staged ? 1 : 0;
     else if (n == "fec_part_on") *value = 0;     // (the FEC partition stream is gone; the name stays for readers of the state)
     else if (n == "pipelined") *value = ctx->pipeline_fec;
+    else if (n == "engine_streams") {       // HIP streams the context owns right now (the host's own stream is not among them)
+        long long k = (ctx->fe_stream ? 1 : 0) + (ctx->fec_stream ? 1 : 0);
+        for (hipStream_t sg : ctx->grp_stream) k += sg ? 1 : 0;
+        std::lock_guard<std::mutex> l(ctx->mtx);
+        for (const auto& kv : ctx->fe_aux) {
+            for (hipStream_t x : {kv.second.aux, kv.second.aux2, kv.second.aux3}) k += x ? 1 : 0;
+            for (hipStream_t x : kv.second.dvbs_aux) k += x ? 1 : 0;
+        }
+        *value = k;
+    }
     else if (n == "num_cus") *value = ctx->num_cus;
     else { g_err = std::string("unknown state name: ") + name; return DVBS2GPU_ERR_ARG; }
     return DVBS2GPU_OK;

@@ -464,7 +464,13 @@ static int deliver_job(dvbs2gpu_ctx* ctx, PendingFec* job, hipStream_t st, Works
 }
 
 // development aid: DVBS2GPU_HOST_TIMING=1 prints where the HOST spends a call (ms since entry at each mark)
-// AGC/NCO + timing recovery of a batch, time-sliced over the caller's stream and its auxiliary stream (ctx.h FeAux, created on first use)
+// AGC/NCO + timing recovery of a batch, time-sliced over the caller's stream and its auxiliary stream (ctx.h FeAux; the throughput mode's is created by
+// dvbs2gpu_set_pipelined, the others on first use).  Which stages go where:
+//   synchronous mode, small banks:        st: timing recovery | aux: AGC | aux2: post stages (RRC, PL-sync walk) | aux3 (big banks): frame loops
+//   throughput mode, big bank, staged:    st: AGC + timing recovery | aux: post stages + frame loops | FEC stream: decoder launches     (the three-stream plan)
+//   throughput mode, big bank, unstaged:  st: timing recovery, then RRC + walk + loops | aux: AGC | FEC stream: decoder launches
+// The plan keeps a big bank's engine streams at three: with the host's stream each then has a hardware queue of its own on the runtime's default of four
+// (streams share queues in the order they were created, and streams of one queue take turns -- DESIGN section 10).
 // (round 6 tried HIP stream priorities -- front-end streams at the device's highest queue priority, the FEC stream at its lowest, or only the post-stage streams high:
 //  302.8 / 303.2 / 304.0 ms per headline step, nothing: queue priority does not decide which resident kernel's workgroups get a compute unit's free wave slots)
 // The data-parallel post stages (RRC, PL-sync walk, demapper) above the decoder's wave priority: where the pipelined mode's balancer has found the FRONT END to be the critical
@@ -479,6 +485,21 @@ constexpr int S2_PRIO_MAX_DUTY = 7;       // the highest share the balancer may 
 #endif
 static int post_prio_wanted(const dvbs2gpu_ctx* ctx) { return ctx->pipeline_fec && ctx->g_prio_duty >= S2_POST_PRIO_MIN_DUTY ? 1 : 0; }
 static hipError_t create_stream(dvbs2gpu_ctx*, hipStream_t* out, int) { return hipStreamCreateWithFlags(out, hipStreamNonBlocking); }
+// the auxiliary stream of a main stream + the slice events (ctx.h FeAux), created on first use
+static hipError_t fe_aux_get(dvbs2gpu_ctx* ctx, hipStream_t st, dvbs2gpu_ctx::FeAux** out) {
+    std::lock_guard<std::mutex> l(ctx->mtx);
+    dvbs2gpu_ctx::FeAux* fa = &ctx->fe_aux[st];
+    if (!fa->aux) {
+        hipError_t e = create_stream(ctx, &fa->aux, +1);
+        if (e != hipSuccess) return e;
+        for (int i = 0; i <= S2_FE_MAX_SLICES; ++i) {
+            if ((e = hipEventCreateWithFlags(&fa->ev[i], hipEventDisableTiming)) != hipSuccess) return e;
+            if ((e = hipEventCreateWithFlags(&fa->ev2[i], hipEventDisableTiming)) != hipSuccess) return e;
+        }
+    }
+    *out = fa;
+    return hipSuccess;
+}
 #ifndef S2_MIN_SLICE_SAMPLES
 #define S2_MIN_SLICE_SAMPLES 1024     // a time slice holds at least this many samples per stream (a call of a few thousand samples is not cut into 32 slices of 133 launches)
 #endif
@@ -501,23 +522,19 @@ static hipError_t frontend_sliced(dvbs2gpu_ctx* ctx, const S2StreamWork* d_work,
     cc.g_form = ctx->gardner_form; cc.g_cand_skew = ctx->gardner_cand_skew;
     dvbs2gpu_ctx::FeAux* fa = nullptr;
     if (nsub > 1) {
-        std::lock_guard<std::mutex> l(ctx->mtx);
-        fa = &ctx->fe_aux[st];
-        if (!fa->aux) {
-            hipError_t e = create_stream(ctx, &fa->aux, +1);
-            if (e != hipSuccess) return e;
-            for (int i = 0; i <= S2_FE_MAX_SLICES; ++i) {
-                if ((e = hipEventCreateWithFlags(&fa->ev[i], hipEventDisableTiming)) != hipSuccess) return e;
-                if ((e = hipEventCreateWithFlags(&fa->ev2[i], hipEventDisableTiming)) != hipSuccess) return e;
-            }
-        }
+        hipError_t e = fe_aux_get(ctx, st, &fa);
+        if (e != hipSuccess) return e;
     }
+    // The stream plan of a big bank in the throughput mode: AGC + timing recovery on `st`, the post stages on `aux`, the decoder on the FEC stream -- three
+    // engine streams, so that with the host's stream each has a hardware queue to itself on the runtime's default of four.  (With aux2 / aux3 on top the frame loops shared the
+    // FEC stream's queue there and waited behind the decoder launch: headline 307 ms per step on 4 queues against 255 on 12.)
+    const bool plan3 = fa && post && !own_post_stream && ctx->pipeline_fec && n > S2_SMALL_BANK;
     if (fa && post && own_post_stream && !fa->aux2) {
         std::lock_guard<std::mutex> l(ctx->mtx);
         hipError_t e = create_stream(ctx, &fa->aux2, +1);
         if (e != hipSuccess) return e;
     }
-    // (big banks: the frame loops on a third auxiliary stream, s2_frontend_launch)
+    // (big banks, synchronous mode: the frame loops on a third auxiliary stream, s2_frontend_launch)
     const bool loops_own = fa && post && own_post_stream && n > S2_SMALL_BANK && nsub > 1;
     if (loops_own && !fa->aux3) {
         std::lock_guard<std::mutex> l(ctx->mtx);
@@ -526,7 +543,7 @@ static hipError_t frontend_sliced(dvbs2gpu_ctx* ctx, const S2StreamWork* d_work,
         for (hipEvent_t& ev : fa->ev3) if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
     }
     return s2_frontend_launch(d_work, n, cc, ctx->d_gardner_bank, st, fa ? fa->aux : nullptr, fa ? fa->ev : nullptr, nsub, post, fa ? fa->ev2 : nullptr,
-                              fa && own_post_stream ? fa->aux2 : nullptr, loops_own ? fa->aux3 : nullptr, loops_own ? fa->ev3 : nullptr);
+                              fa && own_post_stream ? fa->aux2 : nullptr, loops_own ? fa->aux3 : nullptr, loops_own ? fa->ev3 : nullptr, plan3);
 }
 
 struct HostMarks {
@@ -784,11 +801,12 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         Spans spans(&ctx->timers);
         S2PostStages post = post_stages(ctx, spans, d0, d_taps, max_count, raw, raw, maxf, d_found, d_counts, (cf32*)W.pll.p, (S2FrameStats*)W.slot_stats.p, spec_loops);
         post.con = CT->dev; post.pls_code = d0->pls_code; post.slots = mp.slots; post.pilots = mp.pilots; post.pilot_blocks = mp.pilot_blocks;
-        // the post stages on a stream of their own, but for a big bank in the throughput mode beside a decoder that is the critical path
-        // (a small bank is a set of latency chains in the throughput mode too: its post stages on the AGC's stream made one stream's 4-frame call 39.9 ms instead of 25;
-        //  a big bank whose FRONT END the balancer has found critical -- priority share 4 or more: the plugin's mode, QPSK -- likewise: AGC + RRC + walk + frame loops on one
-        //  stream were 127 ms of launches per 140 ms step; beside a decoder that is the critical path the shared stream stays: headline 347 vs 361 ms per step)
-        const bool own_post_stream = !pipelined || n <= S2_SMALL_BANK || (ctx->g_prio_auto && ctx->g_prio_duty >= 4);
+        // the post stages on a stream of their own (aux2) -- but for a big bank in the throughput mode, which follows the three-stream plan of frontend_sliced: AGC + timing
+        // recovery on `st`, the post stages on the auxiliary stream
+        // (a small bank is a set of latency chains in the throughput mode too: its post stages on the AGC's stream made one stream's 4-frame call 39.9 ms instead of 25.
+        //  Until the stream plan a big bank whose front end the balancer had found critical -- share 4 or more -- took a post stream AND a loops stream of its own: five engine
+        //  streams, and on the runtime's default of four hardware queues the frame loops shared the FEC stream's queue and waited behind the decoder launch)
+        const bool own_post_stream = !pipelined || n <= S2_SMALL_BANK;
         { StageSpan sp(ctx->timers, ST_FRONTEND, st); HIP_TRY(frontend_sliced(ctx, d_work, n, d0->co, st, &post, own_post_stream, nullptr, max_count)); }
         slot_stats.resize(nslot);
         HIP_TRY(hipMemcpyAsync(slot_stats.data(), W.slot_stats.p, sizeof(S2FrameStats) * nslot, hipMemcpyDeviceToHost, st));
@@ -1598,6 +1616,8 @@ int dvbs2gpu_set_pipelined(dvbs2gpu_ctx* ctx, int on) {
         if (!ctx->pipeline_fec) { int rr = release_streams(ctx); if (rr) return rr; }
         if (!ctx->fe_stream) HIP_TRY(create_stream(ctx, &ctx->fe_stream, +1));
         if (!ctx->fec_stream) HIP_TRY(create_stream(ctx, &ctx->fec_stream, -1));
+        // (the third stream of a big bank's plan here too, not on first use inside a call: the runtime maps streams onto hardware queues in the order they are created)
+        { dvbs2gpu_ctx::FeAux* fa; HIP_TRY(fe_aux_get(ctx, ctx->fe_stream, &fa)); }
         if (!ctx->ev_llr) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_llr, hipEventDisableTiming));
     }
     if (!on && ctx->fec_stream) {

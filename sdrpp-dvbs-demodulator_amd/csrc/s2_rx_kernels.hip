@@ -3281,7 +3281,10 @@ static void gardner_launch(const S2StreamWork* d_work, int nstreams, const S2Loo
 }
 #define GARDNER_LAUNCH(c_, n_) gardner_launch(d_work, nstreams, coefs, d_bank, st, (c_), (n_))
 hipError_t s2_frontend_launch(const S2StreamWork* d_work, int nstreams, S2LoopCoefs coefs, const float* d_bank, hipStream_t st, hipStream_t aux,
-                              hipEvent_t* ev, int nsub, const S2PostStages* post, hipEvent_t* ev2, hipStream_t post_stream, hipStream_t loops_stream, hipEvent_t* ev3) {
+                              hipEvent_t* ev, int nsub, const S2PostStages* post, hipEvent_t* ev2, hipStream_t post_stream, hipStream_t loops_stream, hipEvent_t* ev3,
+                              bool agc_serial) {
+    // agc_serial (the throughput mode's stream plan for a big bank, s2_demod.hip frontend_sliced): the AGC slice c runs on `st` in front of the timing recovery of slice c,
+    // and `aux` is left to the post stages -- two front-end streams beside the FEC stream, so that each has a hardware queue of its own on the runtime's default of four.
     // loops_stream (+ ev3: 2 (nsub + 1) events): the frame loops of slice c on a stream of their own, beside the RRC of slice c + 1 -- a big bank's post stages are a pipeline
     // of their own (plugin's mode, r06 timeline: RRC 3 + PL-sync walk 2 + frame loops 10 ms per slice behind 10 ms of timing recovery: the post stages, not the timing
     // recovery, set the step).  The PL-sync walk of slice c + 1 still waits for the frame loops of slice c (they read its frame table); the RRC of slice c + 1 only appends
@@ -3303,19 +3306,20 @@ hipError_t s2_frontend_launch(const S2StreamWork* d_work, int nstreams, S2LoopCo
     int agc_next = 0;
     auto agc_upto = [&](int k) -> hipError_t {
         for (; agc_next <= k && agc_next < nsub; ++agc_next) {
-            hipLaunchKernelGGL(agc_pc_kernel<AgcS2Traits>, ga, dim3(128), 0, aux, d_work, nstreams, coefs, agc_next, nsub);
+            hipLaunchKernelGGL(agc_pc_kernel<AgcS2Traits>, ga, dim3(128), 0, agc_serial ? st : aux, d_work, nstreams, coefs, agc_next, nsub);
+            if (agc_serial) continue;
             hipError_t e2 = hipEventRecord(ev[agc_next], aux);
             if (e2 != hipSuccess) return e2;
         }
         return hipSuccess;
     };
     for (int c = 0; c < nsub; ++c) {
-        if ((e = agc_upto(post ? c + 1 : c)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(st, ev[c], 0)) != hipSuccess) return e;
+        if ((e = agc_upto(post && !agc_serial ? c + 1 : c)) != hipSuccess) return e;
+        if (!agc_serial && (e = hipStreamWaitEvent(st, ev[c], 0)) != hipSuccess) return e;
         GARDNER_LAUNCH(c, nsub);
         if (post) {
             if ((e = hipEventRecord(ev2[c], st)) != hipSuccess) return e;
-            if ((e = agc_upto(c + 2)) != hipSuccess) return e;              // (the AGC stays ahead of the timing loop: its next slices go in before this slice's post stages)
+            if (!agc_serial && (e = agc_upto(c + 2)) != hipSuccess) return e;              // (the AGC stays ahead of the timing loop: its next slices go in before this slice's post stages)
             if ((e = hipStreamWaitEvent(ps, ev2[c], 0)) != hipSuccess) return e;
             if (loops_stream && ev3) {
                 hipEvent_t* walked = ev3;                  // [c]: PL-sync walk of slice c done
