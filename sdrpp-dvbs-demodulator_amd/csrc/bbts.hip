@@ -275,7 +275,7 @@ struct dvbs2gpu_bbts {
     int cur = 0;
     BbtsFrameDesc* d_desc = nullptr;
     BbtsStreamPlan* d_plan = nullptr;
-    void* d_args = nullptr;                    // [in ptrs][out ptrs][nframes][out bytes]
+    void* d_args = nullptr;                    // BankArgs(nstreams): [in ptrs][out ptrs][nframes][out bytes]
     uint8_t *d_in1 = nullptr, *d_out1 = nullptr;   // staging of the single-stream host-buffer entry point
     size_t out1_cap = 0;
     std::vector<std::unique_ptr<BbtsHostParser>> host;
@@ -386,7 +386,7 @@ int dvbs2gpu_bbts_create(dvbs2gpu_ctx* ctx, int nstreams, int kbch_bits, int max
     A((void**)&b->d_reasm[0], n * REASM_STRIDE); A((void**)&b->d_reasm[1], n * REASM_STRIDE);
     A((void**)&b->d_desc, n * max_frames * sizeof(BbtsFrameDesc));
     A((void**)&b->d_plan, n * sizeof(BbtsStreamPlan));
-    A(&b->d_args, n * (2 * sizeof(void*) + 2 * sizeof(int)));
+    A(&b->d_args, BankArgs(n).L.bytes());
     if (e != hipSuccess) { dvbs2gpu_bbts_destroy(b); return fail_hip(e, "hipMalloc(bbts)"); }
     *out = b;
     return 0;
@@ -405,11 +405,9 @@ int dvbs2gpu_bbts_process_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb, co
         // when fewer than 189 bytes are left (.cpp:178,206): with this bound it never does
         if ((long)cap < (long)nframes[i] * fbytes + 2 * TS) { g_err = "cap must be >= nframes*kbch/8 + 376"; return DVBS2GPU_ERR_CAPACITY; }
     }
-    char* a = (char*)b->d_args;
-    const uint8_t** a_in = (const uint8_t**)a;
-    uint8_t** a_out = (uint8_t**)(a + sizeof(void*) * n);
-    int* a_nf = (int*)(a + 2 * sizeof(void*) * n);
-    int* a_ob = a_nf + n;
+    const BankArgs a(n);
+    const uint8_t** a_in = a.in(b->d_args); uint8_t** a_out = a.out(b->d_args);
+    int *a_nf = a.cnt(b->d_args), *a_ob = a.ob(b->d_args);
     HIP_TRY(hipMemcpyAsync(a_in, d_bb, sizeof(void*) * n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(a_out, d_out, sizeof(void*) * n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(a_nf, nframes, sizeof(int) * n, hipMemcpyHostToDevice, st));

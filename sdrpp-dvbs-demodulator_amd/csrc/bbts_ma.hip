@@ -412,6 +412,11 @@ static void ma_flush_lane(MaHostStream& tool, MaLaneState& l, const uint8_t* cy,
     }
 }
 
+struct MaArgs {                                // the layout of d_args for n streams of up to mf frames
+    ScratchLayout L;
+    ScratchPart<const uint8_t*> in; ScratchPart<uint8_t*> out; ScratchPart<int> nf, need, foff;
+    MaArgs(size_t n, size_t mf) : in(L.add<const uint8_t*>(n)), out(L.add<uint8_t*>(n * MA_LANES)), nf(L.add<int>(n)), need(L.add<int>(n * MA_LANES)), foff(L.add<int>(n * (mf + 1))) {}
+};
 struct BbtsMa {
     MaCfg cfg;
     std::vector<MaSel> sel;
@@ -425,7 +430,7 @@ struct BbtsMa {
     MaFrameRec* d_recs = nullptr;
     MaFrameDesc* d_desc = nullptr;
     MaFin* d_fins = nullptr;
-    void* d_args = nullptr;                    // [in ptrs][8 out ptrs per stream][nframes][needed per lane][frame offsets]
+    void* d_args = nullptr;                    // MaArgs: [in ptrs][8 out ptrs per stream][nframes][needed per lane][frame offsets]
     std::vector<int> h_foff;
     uint8_t *d_in1 = nullptr, *d_out1 = nullptr;   // staging of the single-stream host-buffer entry point
     size_t out1_cap = 0;
@@ -517,7 +522,7 @@ int dvbs2gpu_bbts_set_mode_adaptation(dvbs2gpu_bbts* b, const dvbs2gpu_bbts_ma_c
         A((void**)&m->d_recs, nfr * sizeof(MaFrameRec));
         A((void**)&m->d_desc, nfr * sizeof(MaFrameDesc));
         A((void**)&m->d_fins, nl * sizeof(MaFin));
-        A(&m->d_args, n * sizeof(void*) + nl * sizeof(void*) + n * sizeof(int) + nl * sizeof(int) + n * (v.max_frames + 1) * sizeof(int));
+        A(&m->d_args, MaArgs(n, v.max_frames).L.bytes());
         if (e != hipSuccess) { bbts_ma_free(m.release()); return fail_hip(e, "hipMalloc(bbts mode adaptation)"); }
         uint8_t t[MA_TAB_BYTES];
         ma_build_tables(t);
@@ -579,12 +584,9 @@ int dvbs2gpu_bbts_process_ma_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb,
         }
     }
     if (!frame_bytes && v.kbch / 8 > MA_MAX_FRAME) { g_err = "a BBFRAME is 10 to 7274 bytes"; return DVBS2GPU_ERR_ARG; }
-    char* a = (char*)m->d_args;
-    const uint8_t** a_in = (const uint8_t**)a;
-    uint8_t** a_out = (uint8_t**)(a + sizeof(void*) * n);
-    int* a_nf = (int*)(a + sizeof(void*) * (n + nl));
-    int* a_need = a_nf + n;
-    int* a_foff = a_need + nl;
+    const MaArgs a(n, mf);
+    const uint8_t** a_in = a.in(m->d_args); uint8_t** a_out = a.out(m->d_args);
+    int *a_nf = a.nf(m->d_args), *a_need = a.need(m->d_args), *a_foff = a.foff(m->d_args);
     HIP_TRY(hipMemcpyAsync(a_in, d_bb, sizeof(void*) * n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(a_out, d_out, sizeof(void*) * nl, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(a_nf, nframes, sizeof(int) * n, hipMemcpyHostToDevice, st));

@@ -2,6 +2,7 @@
 // Host-side only logic here; kernels live in *_kernel.hip.  No CPU fallback: without a HIP device
 // dvbs2gpu_create fails with DVBS2GPU_ERR_NODEVICE.
 #include "ctx.h"
+#include <algorithm>
 #include <climits>
 #include <cstdlib>
 
@@ -235,63 +236,43 @@ int fec_run(dvbs2gpu_ctx* ctx, const FecParams& f, const int8_t* d_llr, int nfra
 }  // namespace s2
 
 namespace s2 {
+// the dynamic work counter of a decoder launch, in a block of its own between the message records and the sign scratch
+struct alignas(256) LdpcWorkCounter { unsigned int v[64]; };
+
 static int ldpc_run(dvbs2gpu_ctx* ctx, const FecParams& f, const int8_t* d_llr, int nframes, int max_trials, int force,
                     uint8_t* d_hard, int hard_stride, int8_t* d_post, int32_t* d_trials, hipStream_t st, FecWs& W) {
     LdpcDeviceCode* C;
     int rc = get_ldpc(ctx, f.code_index, &C);
     if (rc) return rc;
-    if (C->use_wave) {
+    // per decoder variant: the workgroups of the launch, the frame slots of each and the message records of a slot
+    const bool wave = C->use_wave, split = !wave && C->use_split && ctx->ldpc_split;
+    int grid, fpb = 1;
+    size_t rec_bytes;
+    if (wave) {
         // wave-per-frame decoder: one 64-thread workgroup per frame slot, as many as the LDS of the device holds at once
         const size_t lds = ldpc_wave_lds_bytes(*C);
         int per_cu = (int)((size_t)(160 * 1024 - LDPC_WAVE_LDS_RESERVE) / lds);
         per_cu = per_cu < 1 ? 1 : (per_cu > 16 ? 16 : per_cu);
-        int grid = ctx->num_cus * per_cu;
-        if (grid > nframes) grid = nframes;
-        size_t need = (size_t)grid * ldpc_wave_msg_bytes_per_frame(*C);
-        need = (need + 255) & ~(size_t)255;
-        const size_t sgn_bytes = (size_t)grid * ldpc_sign_ws_bytes_per_slot();
-        if ((rc = W.msg.ensure(need + 256 + sgn_bytes))) return rc;
-        if (!d_trials) {
-            if ((rc = W.misc.ensure((size_t)nframes * 2 * sizeof(int32_t)))) return rc;
-            d_trials = (int32_t*)W.misc.p;
-        }
-        if (!d_hard) {
-            if ((rc = W.hard.ensure((size_t)nframes * (f.K / 8)))) return rc;
-            d_hard = (uint8_t*)W.hard.p; hard_stride = f.K / 8;
-        }
-        HIP_TRY(ldpc_wave_decode_launch(*C, d_llr, nframes, max_trials, force, d_hard, hard_stride, d_post, d_trials, (uint8_t*)W.msg.p, grid, st,
-                                        (unsigned int*)((char*)W.msg.p + need), (uint32_t*)((char*)W.msg.p + need + 256)));
-        return 0;
-    }
-    if (C->use_split && ctx->ldpc_split) {
+        grid = std::min(ctx->num_cus * per_cu, nframes);
+        rec_bytes = ldpc_wave_msg_bytes_per_frame(*C);
+    } else if (split) {
         // half-row decoder: one frame per workgroup, frames beyond the first wave of workgroups claimed through the work counter
-        int grid = ctx->num_cus * C->split_blocks_per_cu;
-        if (grid > nframes) grid = nframes;
-        size_t need = (size_t)grid * ldpc_split_msg_bytes_per_block(*C);
-        need = (need + 255) & ~(size_t)255;
-        const size_t sgn_bytes = (size_t)grid * ldpc_sign_ws_bytes_per_slot();
-        if ((rc = W.msg.ensure(need + 256 + sgn_bytes))) return rc;
-        if (!d_trials) {
-            if ((rc = W.misc.ensure((size_t)nframes * 2 * sizeof(int32_t)))) return rc;
-            d_trials = (int32_t*)W.misc.p;
-        }
-        if (!d_hard) {
-            if ((rc = W.hard.ensure((size_t)nframes * (f.K / 8)))) return rc;
-            d_hard = (uint8_t*)W.hard.p; hard_stride = f.K / 8;
-        }
-        if (nframes > 0)
-            HIP_TRY(ldpc_split_decode_launch(*C, d_llr, nframes, max_trials, force, d_hard, hard_stride, d_post, d_trials, (uint32_t*)W.msg.p, grid, st,
-                                             (unsigned int*)((char*)W.msg.p + need), (uint32_t*)((char*)W.msg.p + need + 256), ctx->ldpc_split_fail_attempts));
-        return 0;
+        grid = std::min(ctx->num_cus * C->split_blocks_per_cu, nframes);
+        rec_bytes = ldpc_split_msg_bytes_per_block(*C);
+    } else {
+        // workgroups hold 2 frame slots, or 1 for batches smaller than the device (ldpc_kernel.hip)
+        fpb = ldpc_frames_per_block(nframes, ctx->num_cus);
+        grid = std::min(ctx->num_cus * C->blocks_per_cu, (nframes + fpb - 1) / fpb);
+        rec_bytes = (size_t)C->R * C->rec_dwords * sizeof(uint32_t);
     }
-    // workgroups hold 2 frame slots, or 1 for batches smaller than the device (ldpc_kernel.hip)
-    const int fpb = ldpc_frames_per_block(nframes, ctx->num_cus);
-    int grid = ctx->num_cus * C->blocks_per_cu;
-    if (grid > (nframes + fpb - 1) / fpb) grid = (nframes + fpb - 1) / fpb;
-    size_t need = (size_t)grid * fpb * C->R * C->rec_dwords * sizeof(uint32_t);
-    need = (need + 255) & ~(size_t)255;
-    const size_t sgn_bytes = (size_t)grid * fpb * ldpc_sign_ws_bytes_per_slot();   // bit-packed signs for the syndrome check
-    if ((rc = W.msg.ensure(need + 256 + sgn_bytes))) return rc;   // + the dynamic work counter + the sign scratch
+    const size_t slots = (size_t)grid * fpb;
+    ScratchLayout L;        // W.msg: message records | work counter | bit-packed signs for the syndrome check
+    const auto l_msg = L.add<uint8_t>(slots * rec_bytes); const auto l_counter = L.add<LdpcWorkCounter>(1);
+    const auto l_sgn = L.add<uint32_t>(slots * ldpc_sign_ws_bytes_per_slot() / sizeof(uint32_t));
+    if ((rc = W.msg.ensure(L.bytes()))) return rc;
+    uint8_t* msg = l_msg(W.msg.p);
+    unsigned int* counter = l_counter(W.msg.p)->v;
+    uint32_t* sgn = l_sgn(W.msg.p);
     if (!d_trials) {
         if ((rc = W.misc.ensure((size_t)nframes * 2 * sizeof(int32_t)))) return rc;
         d_trials = (int32_t*)W.misc.p;
@@ -300,9 +281,13 @@ static int ldpc_run(dvbs2gpu_ctx* ctx, const FecParams& f, const int8_t* d_llr, 
         if ((rc = W.hard.ensure((size_t)nframes * (f.K / 8)))) return rc;
         d_hard = (uint8_t*)W.hard.p; hard_stride = f.K / 8;
     }
-    HIP_TRY(ldpc_decode_launch(*C, d_llr, nframes, max_trials, force, d_hard, hard_stride, d_post, d_trials,
-                               (uint32_t*)W.msg.p, grid, fpb, st, (unsigned int*)((char*)W.msg.p + need),
-                               (uint32_t*)((char*)W.msg.p + need + 256)));
+    if (wave)
+        HIP_TRY(ldpc_wave_decode_launch(*C, d_llr, nframes, max_trials, force, d_hard, hard_stride, d_post, d_trials, msg, grid, st, counter, sgn));
+    else if (!split)
+        HIP_TRY(ldpc_decode_launch(*C, d_llr, nframes, max_trials, force, d_hard, hard_stride, d_post, d_trials, (uint32_t*)msg, grid, fpb, st, counter, sgn));
+    else if (nframes > 0)
+        HIP_TRY(ldpc_split_decode_launch(*C, d_llr, nframes, max_trials, force, d_hard, hard_stride, d_post, d_trials, (uint32_t*)msg, grid, st, counter, sgn,
+                                         ctx->ldpc_split_fail_attempts));
     return 0;
 }
 }  // namespace s2
@@ -313,9 +298,10 @@ static int bch_run(dvbs2gpu_ctx* ctx, const FecParams& f, uint8_t* d_frames, int
     // GF(2^16): t = 8 and 10 use the first 2t syndromes of the same field; tables depend on (m, t) only via t rows
     int rc = get_bch(ctx, f.bch_m, f.bch_t, &B);
     if (rc) return rc;
-    if ((rc = W.syn.ensure((size_t)nframes * 32 * sizeof(uint16_t) + (size_t)(nframes + 2) * sizeof(int32_t)))) return rc;
-    uint16_t* syn = (uint16_t*)W.syn.p;
-    int32_t* todo = (int32_t*)(syn + (size_t)nframes * 32);      // counters + list of the frames that need the correction kernel
+    ScratchLayout L;        // W.syn: syndromes | counters + list of the frames that need the correction kernel
+    const auto l_syn = L.add<uint16_t>((size_t)nframes * 32); const auto l_todo = L.add<int32_t>((size_t)nframes + 2);
+    if ((rc = W.syn.ensure(L.bytes()))) return rc;
+    uint16_t* syn = l_syn(W.syn.p); int32_t* todo = l_todo(W.syn.p);
     HIP_TRY(bch_syndromes_launch(*B, d_frames, f.K / 8, f.K, nframes, syn, todo, d_corr, st));
     HIP_TRY(bch_correct_launch(*B, d_frames, f.K / 8, f.K, f.kbch, nframes, syn, todo, d_corr, st));
     return 0;

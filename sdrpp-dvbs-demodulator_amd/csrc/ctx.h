@@ -15,6 +15,7 @@
 #include <chrono>
 #include "kernels.h"
 #include "s2_rx.h"
+#include "scratch_layout.h"
 
 namespace s2 {
 
@@ -113,6 +114,13 @@ struct MixWs {          // a mixed CCM batch (process_mixed)
 };
 // the buffers of one pipelined FEC job (per slot and parity): LLRs | BBFRAMEs | frame refs + first[] + results (CCM), results + index lists + destinations (ACM/VCM, mixed)
 struct FecJobBufs { Workspace llr, bb, job; void release() { llr.release(); bb.release(); job.release(); } };
+
+// the argument table of a bank call for n streams (dvbs_capi.hip, bbts.hip): input pointers | output pointers | counts in | bytes out
+struct BankArgs {
+    ScratchLayout L;
+    ScratchPart<const uint8_t*> in; ScratchPart<uint8_t*> out; ScratchPart<int> cnt, ob;
+    explicit BankArgs(size_t n) : in(L.add<const uint8_t*>(n)), out(L.add<uint8_t*>(n)), cnt(L.add<int>(n)), ob(L.add<int>(n)) {}
+};
 
 struct ConstelTables {          // device tables of one constellation (type, gamma1, gamma2)
     S2ConstelDev dev;

@@ -151,7 +151,7 @@ struct dvbs2gpu_dvbs_tail {
     uint8_t* d_gf = nullptr;
     uint8_t* d_prbs = nullptr;
     DvbsTailState* d_state = nullptr;
-    void* d_args = nullptr;                    // [in ptrs][out ptrs][counts][out bytes]
+    void* d_args = nullptr;                    // BankArgs(nstreams): [in ptrs][out ptrs][counts][out bytes]
 };
 
 extern "C" {
@@ -197,7 +197,7 @@ int dvbs2gpu_dvbs_tail_create(dvbs2gpu_ctx* ctx, int nstreams, int max_bits, dvb
     A((void**)&t->d_status, n * t->max_frames * 8); A((void**)&t->d_rs_err, n * t->max_frames * 8 * sizeof(int));
     A((void**)&t->d_gf, 768); A((void**)&t->d_prbs, 32767);
     A((void**)&t->d_state, n * sizeof(DvbsTailState));
-    A(&t->d_args, n * (2 * sizeof(void*) + 2 * sizeof(int)));
+    A(&t->d_args, BankArgs(n).L.bytes());
     if (e != hipSuccess) { dvbs2gpu_dvbs_tail_destroy(t); return fail_hip(e, "hipMalloc(dvbs tail)"); }
     HIP_TRY(hipMemcpy(t->d_gf, gf.data(), 768, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(t->d_prbs, prbs.data(), 32767, hipMemcpyHostToDevice));
@@ -237,11 +237,9 @@ int dvbs2gpu_dvbs_tail_process_batch(dvbs2gpu_dvbs_tail* t, const uint8_t* const
         if (counts[i] < 0 || counts[i] > t->max_bits) { last_error() = "bit count exceeds max_bits"; return DVBS2GPU_ERR_ARG; }
         if (counts[i] > 0 && !d_bits[i]) return DVBS2GPU_ERR_ARG;
     }
-    char* a = (char*)t->d_args;
-    const uint8_t** d_in = (const uint8_t**)a;
-    uint8_t** d_out = (uint8_t**)(a + sizeof(void*) * n);
-    int* d_cnt = (int*)(a + 2 * sizeof(void*) * n);
-    int* d_ob = d_cnt + n;
+    const BankArgs a(n);
+    const uint8_t** d_in = a.in(t->d_args); uint8_t** d_out = a.out(t->d_args);
+    int *d_cnt = a.cnt(t->d_args), *d_ob = a.ob(t->d_args);
     HIP_TRY(hipMemcpyAsync(d_in, d_bits, sizeof(void*) * n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_out, d_ts, sizeof(void*) * n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_cnt, counts, sizeof(int) * n, hipMemcpyHostToDevice, st));
@@ -301,9 +299,8 @@ int dvbs2gpu_dvbs_tail_rs_stage(dvbs2gpu_dvbs_tail* t, const uint8_t* h_packets,
     HIP_TRY(hipMemset(t->d_rs_err, 0, (size_t)n * t->max_frames * 8 * sizeof(int)));
     uint8_t* d_ts = nullptr;
     HIP_TRY(hipMalloc((void**)&d_ts, (size_t)std::max(cap, 1) * n));
-    char* a = (char*)t->d_args;
-    uint8_t** d_out = (uint8_t**)(a + sizeof(void*) * n);
-    int* d_ob = (int*)(a + 2 * sizeof(void*) * n) + n;
+    const BankArgs a(n);
+    uint8_t** d_out = a.out(t->d_args); int* d_ob = a.ob(t->d_args);
     std::vector<uint8_t*> outs(n);
     for (int i = 0; i < n; ++i) outs[i] = d_ts + (size_t)i * std::max(cap, 1);
     hipError_t e = hipMemcpy(d_out, outs.data(), sizeof(void*) * n, hipMemcpyHostToDevice);
@@ -321,10 +318,12 @@ int dvbs2gpu_dvbs_depuncture(dvbs2gpu_ctx* ctx, int period, int mode, const uint
     if (out_cap < 2 * size + 2) return DVBS2GPU_ERR_CAPACITY;
     CallGuard guard(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
+    ScratchLayout L;
+    const auto l_in = L.add<uint8_t>(size); const auto l_out = L.add<uint8_t>(out_cap); const auto l_st = L.add<int>(5);     // (state[4], output count)
     uint8_t* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, (size_t)size + out_cap + 64));
-    uint8_t* d_in = d, *d_out = d + size;
-    int* d_st = (int*)(d + (((size_t)size + out_cap + 3) & ~(size_t)3));
+    HIP_TRY(hipMalloc((void**)&d, L.bytes()));
+    uint8_t *d_in = l_in(d), *d_out = l_out(d);
+    int* d_st = l_st(d);
     int n = 0;
     hipError_t e = hipMemcpy(d_in, h_in, size, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_out, h_out, out_cap, hipMemcpyHostToDevice);       // (bytes the stage does not write keep the caller's fill)

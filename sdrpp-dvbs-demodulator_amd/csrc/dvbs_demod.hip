@@ -183,23 +183,21 @@ int dvbs2gpu_dvbs_demod_process_batch(dvbs2gpu_dvbs_demod* d, const float* const
     }
     const int mb = d->max_blocks;
     Workspace& ws = ctx->ws_dvbs[0];
-    const size_t off_ptr_in = sizeof(DvbsStreamWork) * n, off_ptr_out = off_ptr_in + sizeof(void*) * n, off_nblk = off_ptr_out + sizeof(void*) * n;
-    const size_t off_cnt = off_nblk + sizeof(int) * n, off_blk0 = off_cnt + sizeof(int) * n, off_nbits = off_blk0 + sizeof(int) * n, total = off_nbits + sizeof(int) * (size_t)n * mb;
+    ScratchLayout L;
+    const auto l_work = L.add<DvbsStreamWork>(n); const auto l_ptr_in = L.add<const int8_t*>(n); const auto l_ptr_out = L.add<uint8_t*>(n);
+    const auto l_nblk = L.add<int>(n); const auto l_cnt = L.add<int>(n); const auto l_blk0 = L.add<int>(n); const auto l_nbits = L.add<int>((size_t)n * mb);
     int rc;
-    if ((rc = ws.ensure(total + 64))) return rc;
+    if ((rc = ws.ensure(L.bytes()))) return rc;
     Workspace& wsb = ctx->ws_dvbs[1];
     if ((rc = wsb.ensure((size_t)n * mb * DVBS_SOFT_BLOCK))) return rc;
-    char* base = (char*)ws.p;
-    DvbsStreamWork* d_work = (DvbsStreamWork*)base;
+    DvbsStreamWork* d_work = l_work(ws.p);
+    const int8_t** d_ptr_in = l_ptr_in(ws.p); uint8_t** d_ptr_out = l_ptr_out(ws.p);
     std::vector<const int8_t*> pin(n);
     for (int i = 0; i < n; ++i) pin[i] = work[i].soft;
     HIP_TRY(hipMemcpyAsync(d_work, work.data(), sizeof(DvbsStreamWork) * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(base + off_ptr_in, pin.data(), sizeof(void*) * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(base + off_ptr_out, d_bits, sizeof(void*) * n, hipMemcpyHostToDevice, st));
-    int* d_nblk = (int*)(base + off_nblk);
-    int* d_cnt = (int*)(base + off_cnt);
-    int* d_nbits = (int*)(base + off_nbits);
-    int* d_blk0 = (int*)(base + off_blk0);
+    HIP_TRY(hipMemcpyAsync(d_ptr_in, pin.data(), sizeof(void*) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_ptr_out, d_bits, sizeof(void*) * n, hipMemcpyHostToDevice, st));
+    int *d_nblk = l_nblk(ws.p), *d_cnt = l_cnt(ws.p), *d_nbits = l_nbits(ws.p), *d_blk0 = l_blk0(ws.p);
     // The serial stages time-sliced over their own streams (s2_rx_kernels.hip, dvbs_frontend_launch): AGC, FLL + RRC, timing recovery, and --
     // behind every timing-recovery slice -- the slice's Costas loop, soft FIFO append and the Viterbi decoding of the blocks it completed.
     // One carrier then costs its slowest stage instead of the sum; a bank of thousands gains too (4096 carriers: 206 -> 146 ms per call),
@@ -232,7 +230,7 @@ int dvbs2gpu_dvbs_demod_process_batch(dvbs2gpu_dvbs_demod* d, const float* const
                                        d->cfg.viterbi_max_outsync, sv, d_blk0);
         }
     } hook;
-    hook.d = d; hook.fa = fa; hook.d_work = d_work; hook.d_in_ptrs = (const int8_t* const*)(base + off_ptr_in); hook.n = n; hook.max_count = max_count;
+    hook.d = d; hook.fa = fa; hook.d_work = d_work; hook.d_in_ptrs = d_ptr_in; hook.n = n; hook.max_count = max_count;
     hook.nsub = nsub; hook.mb = mb; hook.d_blk0 = d_blk0; hook.d_nblk = d_nblk; hook.d_nbits = d_nbits; hook.d_bits = (uint8_t*)wsb.p; hook.st = st;
     // (tried: the Costas slices on the AGC's stream and the decoder alone on `sv` -- AGC + Costas then carry 0.94 ms per slice beside the FLL's 0.81: nothing gained)
     // (a few carriers: the AGC slices on a stream of their own -- one carrier 39.4 -> 36.7 ms per call; a bank keeps them ahead on the Viterbi stream)
@@ -246,10 +244,10 @@ int dvbs2gpu_dvbs_demod_process_batch(dvbs2gpu_dvbs_demod* d, const float* const
         HIP_TRY(dvbs_soft_count_launch(d_work, n, d_nblk, st));          // (FIFO fill and block count of the whole call, for the packing and the compaction)
     } else {
         HIP_TRY(dvbs_soft_count_launch(d_work, n, d_nblk, st));
-        HIP_TRY(dvbs_viterbi_launch(nullptr, (const int8_t* const*)(base + off_ptr_in), d_nblk, n, mb, (uint8_t*)wsb.p, d_nbits, nullptr, d->d_vstate,
+        HIP_TRY(dvbs_viterbi_launch(nullptr, d_ptr_in, d_nblk, n, mb, (uint8_t*)wsb.p, d_nbits, nullptr, d->d_vstate,
                                     d->d_vws, d->cfg.viterbi_ber_threshold, d->cfg.viterbi_max_outsync, st));
     }
-    HIP_TRY(dvbs_pack_bits_launch((const uint8_t*)wsb.p, d_nbits, d_nblk, n, mb, (uint8_t* const*)(base + off_ptr_out), cap, d_cnt, st));
+    HIP_TRY(dvbs_pack_bits_launch((const uint8_t*)wsb.p, d_nbits, d_nblk, n, mb, d_ptr_out, cap, d_cnt, st));
     HIP_TRY(dvbs_soft_compact_launch(d_work, n, st));
     // signal quality over the call's Costas output (quality.hip): one launch for the bank, behind the last Costas slice
     d->qual.clear();

@@ -564,9 +564,10 @@ struct HostMarks {
 enum : unsigned { CLR_FRAMES = 1, CLR_STATS = 2, CLR_VCM = 4 /* ACM/VCM: also the frame lengths and the taps */ };
 
 // The stream-work table of a call: checks every count against its handle's max_samples, fills S2StreamWork, clears the handle's per-call fields and uploads the
-// table to the front of `ws` (sized for the table + `extra` bytes).  `spec`: the frame loops run ahead of the PL sync (their buffer is allocated on first use).
+// table to the front of `ws`, sized to `total` bytes: those of the caller's layout, whose first array is the table.  `spec`: the frame loops run ahead of the PL sync
+// (their buffer is allocated on first use).
 int upload_work(dvbs2gpu_demod* const* dm, int n, const cf32* const* d_iq, const int* counts, uint8_t* const* d_out, unsigned clear, bool spec,
-                Workspace& ws, size_t extra, hipStream_t st, int* max_count) {
+                Workspace& ws, size_t total, hipStream_t st, int* max_count) {
     std::vector<S2StreamWork> work(n);
     *max_count = 0;
     for (int i = 0; i < n; ++i) {
@@ -582,7 +583,7 @@ int upload_work(dvbs2gpu_demod* const* dm, int n, const cf32* const* d_iq, const
         if (clear & CLR_VCM) { d->frame_len.clear(); d->tap_pll = nullptr; d->tap_llr = nullptr; d->tap_pll_count = 0; d->tap_llr_count = 0; d->tap_pll_stride = 0; }
     }
     int rc;
-    if ((rc = ws.ensure(sizeof(S2StreamWork) * n + extra))) return rc;
+    if ((rc = ws.ensure(total))) return rc;
     HIP_TRY(hipMemcpyAsync(ws.p, work.data(), sizeof(S2StreamWork) * n, hipMemcpyHostToDevice, st));
     return 0;
 }
@@ -629,12 +630,14 @@ struct QualityCall {
         if (desc.empty()) return 0;
         int rc;
         if ((rc = get_vcm_tables(ctx))) return rc;
-        const size_t nd = desc.size(), off = (sizeof(S2QualityDesc) * nd + 63) & ~(size_t)63;
-        if ((rc = ws.ensure(off + sizeof(S2FrameQuality) * nd))) return rc;
-        S2FrameQuality* d_rec = (S2FrameQuality*)((char*)ws.p + off);
+        const size_t nd = desc.size();
+        ScratchLayout L;
+        const auto l_desc = L.add<S2QualityDesc>(nd); const auto l_rec = L.add<S2FrameQuality>(nd);
+        if ((rc = ws.ensure(L.bytes()))) return rc;
+        S2QualityDesc* d_desc = l_desc(ws.p); S2FrameQuality* d_rec = l_rec(ws.p);
         rec.resize(nd);
-        HIP_TRY(hipMemcpyAsync(ws.p, desc.data(), sizeof(S2QualityDesc) * nd, hipMemcpyHostToDevice, st));
-        HIP_TRY(s2_quality_launch((const S2QualityDesc*)ws.p, (int)nd, ctx->d_vcm_mods, ctx->d_vcm_cons, ctx->pl.sof, ctx->pl.plsc, d_rec, st, prio));
+        HIP_TRY(hipMemcpyAsync(d_desc, desc.data(), sizeof(S2QualityDesc) * nd, hipMemcpyHostToDevice, st));
+        HIP_TRY(s2_quality_launch(d_desc, (int)nd, ctx->d_vcm_mods, ctx->d_vcm_cons, ctx->pl.sof, ctx->pl.plsc, d_rec, st, prio));
         HIP_TRY(hipMemcpyAsync(rec.data(), d_rec, sizeof(S2FrameQuality) * nd, hipMemcpyDeviceToHost, st));
         return 0;
     }
@@ -770,20 +773,21 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     // the window they are ahead in keeps its PLL output in a buffer of the stream's own (one PLFRAME of the longest kind)
     const bool spec_loops = n <= S2_SMALL_BANK && !d0->cfg.pilot_aided && ctx->stage_pipeline_launches <= 0;     // (S2_SMALL_BANK = FL_SMALL_BANK of the kernels)
     int max_count;
-    if ((rc = upload_work(dm, n, d_iq, counts, d_out, CLR_FRAMES | (pipelined ? 0 : CLR_STATS), spec_loops, W.work,
-                          sizeof(int) * (n + 1) + sizeof(int) * 4 * n + 64, st, &max_count))) return rc;
-    S2StreamWork* d_work = (S2StreamWork*)W.work.p;
-    int* d_first = (int*)(d_work + n);        // [n + 1]
-    int* d_nsym = d_first + (n + 1);          // [n]
-    float* d_nco = (float*)(d_nsym + n);      // [n]
-    int* d_curfill = (int*)(d_nco + n);       // [2n]
+    ScratchLayout lw;       // W.work
+    const auto l_work = lw.add<S2StreamWork>(n); const auto l_first = lw.add<int>(n + 1); const auto l_nsym = lw.add<int>(n);
+    const auto l_nco = lw.add<float>(n); const auto l_curfill = lw.add<int>(2 * n);
+    if ((rc = upload_work(dm, n, d_iq, counts, d_out, CLR_FRAMES | (pipelined ? 0 : CLR_STATS), spec_loops, W.work, lw.bytes(), st, &max_count))) return rc;
+    S2StreamWork* d_work = l_work(W.work.p);
+    int *d_first = l_first(W.work.p), *d_nsym = l_nsym(W.work.p), *d_curfill = l_curfill(W.work.p);
+    float* d_nco = l_nco(W.work.p);
     // ---- 3: PL sync.  The 2-state realign machine of S2PLSyncBlock runs on the device, one workgroup per stream walking its windows
     // in order (s2_ccm_walk_kernel); the host only pools the frame tables it gets back (ONE synchronisation for stages 1-3, or 1-4).
     int maxf = 0;
     for (int i = 0; i < n; ++i) maxf = std::max(maxf, dm[i]->fifo_cap / raw + 2);
-    if ((rc = W.found.ensure(sizeof(S2VcmFound) * (size_t)n * maxf + sizeof(int) * 4 * n + 64))) return rc;
-    S2VcmFound* d_found = (S2VcmFound*)W.found.p;
-    int* d_counts = (int*)(d_found + (size_t)n * maxf);
+    ScratchLayout lf;       // W.found
+    const auto l_found = lf.add<S2VcmFound>((size_t)n * maxf); const auto l_counts = lf.add<int>(4 * n);
+    if ((rc = W.found.ensure(lf.bytes()))) return rc;
+    S2VcmFound* d_found = l_found(W.found.p); int* d_counts = l_counts(W.found.p);
     // Stage pipeline (calls of one configuration): RRC, walk and the frame loops run behind every timing-recovery slice on the auxiliary stream
     // (s2_frontend_launch); a stream's frames stay in its maxf slots of the PLL-output / statistics arrays until the host has pooled the tables.
     // Not while the decoder of the previous call is the critical path anyway (pipelined mode, the balancer has taken the timing loop's priority
@@ -859,22 +863,24 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     const int mt = force ? d0->cfg.force_ldpc_iters : d0->cfg.max_ldpc_trials;
     const int par = ctx->fec_parity[slot];
     FecJobBufs& jb = ctx->ws_fecbuf[slot][par];     // (pipelined: the FEC job's own buffers)
+    // the FEC job keeps its own copy of the frame table and its result arrays (phase A of the next call reuses W.frames)
+    ScratchLayout lj;       // jb.job
+    const auto j_frames = lj.add<S2FrameRef>(nf); const auto j_first = lj.add<int>(n + 1); const auto j_trials = lj.add<int32_t>(nf); const auto j_corr = lj.add<int32_t>(nf);
     if (nf > 0) {
-        if ((rc = W.frames.ensure(sizeof(S2FrameRef) * nf + sizeof(S2FrameStats) * nf + sizeof(int32_t) * 3 * nf + 64))) return rc;
-        S2FrameRef* d_frames = (S2FrameRef*)W.frames.p;
-        S2FrameStats* d_stats = (S2FrameStats*)(d_frames + nf);
-        int32_t* d_trials = (int32_t*)(d_stats + nf);
-        int32_t* d_corr = d_trials + nf;
-        int* d_slot = (int*)(d_corr + nf);
+        ScratchLayout lr;   // W.frames
+        const auto l_frames = lr.add<S2FrameRef>(nf); const auto l_stats = lr.add<S2FrameStats>(nf); const auto l_trials = lr.add<int32_t>(nf);
+        const auto l_corr = lr.add<int32_t>(nf); const auto l_slot = lr.add<int>(nf);
+        if ((rc = W.frames.ensure(lr.bytes()))) return rc;
+        if (pipelined && (rc = jb.job.ensure(lj.bytes()))) return rc;
+        S2FrameRef* d_frames = l_frames(W.frames.p); S2FrameStats* d_stats = l_stats(W.frames.p);
+        int32_t* d_trials = pipelined ? j_trials(jb.job.p) : l_trials(W.frames.p);
+        int32_t* d_corr = pipelined ? j_corr(jb.job.p) : l_corr(W.frames.p);
+        int* d_slot = l_slot(W.frames.p);
         Workspace& ws_llr = pipelined ? jb.llr : W.llr;
         Workspace& ws_bb = pipelined ? jb.bb : W.bb;
         if (pipelined) {
-            // the FEC job keeps its own copy of the frame table and its result arrays (phase A of the next call reuses W.frames)
-            if ((rc = jb.job.ensure(sizeof(S2FrameRef) * nf + sizeof(int) * (n + 1) + sizeof(int32_t) * 2 * nf + 64))) return rc;
-            d_trials = (int32_t*)((char*)jb.job.p + sizeof(S2FrameRef) * nf + sizeof(int) * (n + 1));
-            d_corr = d_trials + nf;
-            HIP_TRY(hipMemcpyAsync(jb.job.p, frames.data(), sizeof(S2FrameRef) * nf, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync((char*)jb.job.p + sizeof(S2FrameRef) * nf, first.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(j_frames(jb.job.p), frames.data(), sizeof(S2FrameRef) * nf, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(j_first(jb.job.p), first.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, st));
         }
         if (!staged && (rc = W.pll.ensure((size_t)nf * raw * sizeof(cf32)))) return rc;
         if ((rc = ws_llr.ensure((size_t)nf * N))) return rc;
@@ -951,10 +957,6 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         prev_delivered = true;
     }
     if (nf > 0) {
-        S2FrameRef* j_frames = (S2FrameRef*)jb.job.p;
-        int* j_first = (int*)((char*)jb.job.p + sizeof(S2FrameRef) * nf);
-        int32_t* j_trials = (int32_t*)((char*)jb.job.p + sizeof(S2FrameRef) * nf + sizeof(int) * (n + 1));
-        int32_t* j_corr = j_trials + nf;
         const int8_t* j_llr = (const int8_t*)jb.llr.p;
         uint8_t* j_bb = (uint8_t*)jb.bb.p;
         auto job = std::make_unique<PendingFec>();
@@ -962,8 +964,8 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         job->dm.assign(dm, dm + n);
         job->first = first; job->hstats = hstats; job->frame_bm = frame_bm;
         job->qual_on = qc.on; job->hquality = std::move(qrec);
-        job->d_frames = j_frames; job->d_first = j_first; job->d_bb = j_bb;
-        job->d_trials = j_trials; job->d_corr = j_corr;
+        job->d_frames = j_frames(jb.job.p); job->d_first = j_first(jb.job.p); job->d_bb = j_bb;
+        job->d_trials = j_trials(jb.job.p); job->d_corr = j_corr(jb.job.p);
         job->d_llr = j_llr; job->N = N; job->rate = mp.rate; job->shortframe = mp.shortframe; job->max_trials = mt; job->force = force; job->slot = slot;
         // A group's job that cannot fill the device (fewer decoder workgroups than half the CUs: the groups of a 64-transponder batch -- a
         // handful of workgroups and 4-6 ms of decoder LATENCY each) runs beside the other groups' jobs: on the GROUP's stream, behind its
@@ -971,7 +973,7 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         // waits behind the job; more streams would only share the few hardware queues).  Big jobs queue up on the shared FEC stream as
         // before (two persistent decoders would only take turns).
         if (beside) {
-            if ((rc = fec_run(ctx, mp.fec, j_llr, nf, mt, force, j_bb, j_trials, j_corr, st, &ctx->fws_grp[slot]))) return rc;
+            if ((rc = fec_run(ctx, mp.fec, j_llr, nf, mt, force, j_bb, j_trials(jb.job.p), j_corr(jb.job.p), st, &ctx->fws_grp[slot]))) return rc;
             if (!ctx->ev_fec[slot][par]) HIP_TRY(hipEventCreate(&ctx->ev_fec[slot][par]));
             HIP_TRY(hipEventRecord(ctx->ev_fec[slot][par], st));
             job->done = ctx->ev_fec[slot][par];
@@ -981,7 +983,7 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
             HIP_TRY(hipStreamWaitEvent(sf, ev_llr, 0));
             if (!ctx->ev_fec_t0[slot][par]) HIP_TRY(hipEventCreate(&ctx->ev_fec_t0[slot][par]));
             HIP_TRY(hipEventRecord(ctx->ev_fec_t0[slot][par], sf));
-            if ((rc = fec_run(ctx, mp.fec, j_llr, nf, mt, force, j_bb, j_trials, j_corr, sf))) return rc;
+            if ((rc = fec_run(ctx, mp.fec, j_llr, nf, mt, force, j_bb, j_trials(jb.job.p), j_corr(jb.job.p), sf))) return rc;
             if (!ctx->ev_fec[slot][par]) HIP_TRY(hipEventCreate(&ctx->ev_fec[slot][par]));
             HIP_TRY(hipEventRecord(ctx->ev_fec[slot][par], sf));
             job->done = ctx->ev_fec[slot][par];
@@ -1070,14 +1072,13 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
     if ((rc = W.found.ensure(sizeof(S2VcmFound) * (size_t)n * maxf))) return rc;
     S2VcmFound* d_found = (S2VcmFound*)W.found.p;
     // (the frames of a call differ in size: this flow also clears their lengths and the taps' element counts)
-    if ((rc = upload_work(dm, n, d_iq, counts, d_out, CLR_FRAMES | CLR_VCM | (pipelined ? 0 : CLR_STATS), false, W.work,
-                          sizeof(int) * (n + 1) + sizeof(int) * 8 * n + sizeof(float) * n + 64, st, &max_count))) return rc;
-    S2StreamWork* d_work = (S2StreamWork*)W.work.p;
-    int* d_first = (int*)(d_work + n);            // [n + 1]
-    int* d_counts = d_first + (n + 1);            // [4n]
-    int* d_curfill = d_counts + 4 * n;            // [2n]
-    int* d_nsym = d_curfill + 2 * n;              // [n]
-    float* d_nco = (float*)(d_nsym + n);          // [n]
+    ScratchLayout lw;       // W.work
+    const auto l_work = lw.add<S2StreamWork>(n); const auto l_first = lw.add<int>(n + 1); const auto l_counts = lw.add<int>(4 * n);
+    const auto l_curfill = lw.add<int>(2 * n); const auto l_nsym = lw.add<int>(n); const auto l_nco = lw.add<float>(n);
+    if ((rc = upload_work(dm, n, d_iq, counts, d_out, CLR_FRAMES | CLR_VCM | (pipelined ? 0 : CLR_STATS), false, W.work, lw.bytes(), st, &max_count))) return rc;
+    S2StreamWork* d_work = l_work(W.work.p);
+    int *d_first = l_first(W.work.p), *d_counts = l_counts(W.work.p), *d_curfill = l_curfill(W.work.p), *d_nsym = l_nsym(W.work.p);
+    float* d_nco = l_nco(W.work.p);
     { StageSpan sp(ctx->timers, ST_FRONTEND, st); HIP_TRY(frontend_sliced(ctx, d_work, n, d0->co, st)); }
     { StageSpan sp(ctx->timers, ST_RRC, st); HIP_TRY(s2_rrc_decim_launch(d_work, n, max_count + max_count / 32 + 8, d_taps, d0->cfg.rrc_taps, st)); }
     { StageSpan sp(ctx->timers, ST_PLSYNC, st); HIP_TRY(s2_vcm_walk_launch(d_work, n, ctx->pl, ctx->d_vcm_mods, d0->cfg.sof_threshold, maxf, d_found, d_counts, st)); }
@@ -1136,11 +1137,12 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
     std::vector<int32_t> trials(nf, 0), corr(nf, 0);
     std::unique_ptr<PendingFec> job_started;
     if (nf > 0) {
-        if ((rc = W.frames.ensure(sizeof(S2VcmFrame) * nf + sizeof(S2FrameStats) * nf + sizeof(uint8_t*) * nf + sizeof(int) * nf + 64))) return rc;
-        S2VcmFrame* d_frames = (S2VcmFrame*)W.frames.p;
-        S2FrameStats* d_stats = (S2FrameStats*)(d_frames + nf);
-        uint8_t** d_dst = (uint8_t**)(d_stats + nf);
-        int* d_idx = (int*)(d_dst + nf);
+        static_assert(sizeof(S2VcmFrame) == 40 && sizeof(S2FrameStats) == 32, "tests/cpp/scratch_layout_host.cpp mirrors these sizes");
+        ScratchLayout lr;   // W.frames
+        const auto l_frames = lr.add<S2VcmFrame>(nf); const auto l_stats = lr.add<S2FrameStats>(nf); const auto l_dst = lr.add<uint8_t*>(nf); const auto l_idx = lr.add<int>(nf);
+        if ((rc = W.frames.ensure(lr.bytes()))) return rc;
+        S2VcmFrame* d_frames = l_frames(W.frames.p); S2FrameStats* d_stats = l_stats(W.frames.p);
+        uint8_t** d_dst = l_dst(W.frames.p); int* d_idx = l_idx(W.frames.p);
         if ((rc = W.pll.ensure((size_t)std::max<long long>(pll_off, 1) * sizeof(cf32)))) return rc;
         if ((rc = W.llr.ensure((size_t)std::max<long long>(llr_off, 4)))) return rc;
         cf32* d_pll = (cf32*)W.pll.p;
@@ -1172,9 +1174,10 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
         Workspace& ws_gb = pipelined ? ctx->ws_fecbuf[slot][par].bb : W.fec_bb;
         Workspace& ws_gt = pipelined ? ctx->ws_fecbuf[slot][par].job : W.fec_res;
         const size_t nall = all_idx.size();
-        const size_t res_bytes = (sizeof(int32_t) * 2 * nall + 63) & ~(size_t)63, idx_bytes = (sizeof(int) * nall + 63) & ~(size_t)63;
-        if ((rc = ws_gl.ensure(llr_need + 64)) || (rc = ws_gb.ensure(bb_need + 64)) || (rc = ws_gt.ensure(res_bytes + idx_bytes + sizeof(uint8_t*) * nf + 64))) return rc;
-        int* j_idx = (int*)((char*)ws_gt.p + res_bytes);
+        ScratchLayout lt;   // ws_gt
+        const auto l_res = lt.add<int32_t>(2 * nall); const auto l_jidx = lt.add<int>(nall); const auto l_jdst = lt.add<uint8_t*>(nf);
+        if ((rc = ws_gl.ensure(llr_need + 64)) || (rc = ws_gb.ensure(bb_need + 64)) || (rc = ws_gt.ensure(lt.bytes()))) return rc;
+        int32_t* d_res = l_res(ws_gt.p); int* j_idx = l_jidx(ws_gt.p);
         if (pipelined) {
             HIP_TRY(hipMemcpyAsync(j_idx, all_idx.data(), sizeof(int) * nall, hipMemcpyHostToDevice, st));
             if (!ctx->ev_llr) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_llr, hipEventDisableTiming));
@@ -1190,7 +1193,7 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
             const int cnt = (int)kv.second.size(), kb = f.kbch / 8;
             int8_t* g_llr = (int8_t*)ws_gl.p + lo;
             uint8_t* g_bb = (uint8_t*)ws_gb.p + bo;
-            int32_t* g_tr = (int32_t*)ws_gt.p + to;
+            int32_t* g_tr = d_res + to;
             HIP_TRY(s2_vcm_gather_launch(d_frames, d_idx + off_idx, cnt, f.N, d_llr, g_llr, st));
             if (!pipelined) {
                 if ((rc = fec_run(ctx, f, g_llr, cnt, mt, force, g_bb, g_tr, g_tr + cnt, st))) return rc;
@@ -1227,13 +1230,13 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
                 const std::vector<int>& idx = groups[o.code];
                 for (int k = 0; k < o.cnt; ++k) { J.frame_tr[idx[k]] = (int)(o.to + k); J.frame_co[idx[k]] = (int)(o.to + o.cnt + k); }
             }
-            J.d_trials = (const int32_t*)ws_gt.p; J.n_results = 2 * nall;
-            J.d_dst = (uint8_t**)((char*)ws_gt.p + res_bytes + idx_bytes);
+            J.d_trials = d_res; J.n_results = 2 * nall;
+            J.d_dst = l_jdst(ws_gt.p);
             J.done = ctx->ev_fec[slot][par];
         } else {
             if ((rc = qc.launch(ctx, W.quality, st, 0))) return rc;
             std::vector<int32_t> tc(2 * all_idx.size());
-            HIP_TRY(hipMemcpyAsync(tc.data(), ws_gt.p, sizeof(int32_t) * tc.size(), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(tc.data(), d_res, sizeof(int32_t) * tc.size(), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(hstats.data(), d_stats, sizeof(S2FrameStats) * nf, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             for (const Out& o : outs) {
@@ -1299,18 +1302,19 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         maxf = std::max(maxf, d->fifo_cap / mp.plframe + 2);
         raw_max = std::max(raw_max, mp.plframe); raw_min = std::min(raw_min, mp.plframe); max_slots = std::max(max_slots, mp.slots);
     }
-    if ((rc = upload_work(dm, n, d_iq, counts, d_out, CLR_FRAMES | (pipelined ? 0 : CLR_STATS), spec_loops, W.work,
-                          sizeof(S2StreamCfgDev) * n + sizeof(int) * 4 * n + sizeof(float) * n + 256, st, &max_count))) return rc;
-    S2StreamWork* d_work = (S2StreamWork*)W.work.p;
-    S2StreamCfgDev* d_cfgs = (S2StreamCfgDev*)(d_work + n);
-    int* d_nsym = (int*)(d_cfgs + n);              // [n]
-    float* d_nco = (float*)(d_nsym + n);           // [n]
-    int* d_curfill = (int*)(d_nco + n);            // [2n]
+    ScratchLayout lw;       // W.work
+    const auto l_work = lw.add<S2StreamWork>(n); const auto l_cfgs = lw.add<S2StreamCfgDev>(n); const auto l_nsym = lw.add<int>(n);
+    const auto l_nco = lw.add<float>(n); const auto l_curfill = lw.add<int>(2 * n);
+    if ((rc = upload_work(dm, n, d_iq, counts, d_out, CLR_FRAMES | (pipelined ? 0 : CLR_STATS), spec_loops, W.work, lw.bytes(), st, &max_count))) return rc;
+    S2StreamWork* d_work = l_work(W.work.p); S2StreamCfgDev* d_cfgs = l_cfgs(W.work.p);
+    int *d_nsym = l_nsym(W.work.p), *d_curfill = l_curfill(W.work.p);
+    float* d_nco = l_nco(W.work.p);
     HIP_TRY(hipMemcpyAsync(d_cfgs, cfgs.data(), sizeof(S2StreamCfgDev) * n, hipMemcpyHostToDevice, st));
     const size_t nslot = (size_t)n * maxf;
-    if ((rc = W.found.ensure(sizeof(S2VcmFound) * nslot + sizeof(int) * 4 * n + 64))) return rc;
-    S2VcmFound* d_found = (S2VcmFound*)W.found.p;
-    int* d_counts = (int*)(d_found + nslot);
+    ScratchLayout lf;       // W.found
+    const auto l_found = lf.add<S2VcmFound>(nslot); const auto l_counts = lf.add<int>(4 * n);
+    if ((rc = W.found.ensure(lf.bytes()))) return rc;
+    S2VcmFound* d_found = l_found(W.found.p); int* d_counts = l_counts(W.found.p);
     if ((rc = W.pll.ensure(nslot * raw_max * sizeof(cf32)))) return rc;
     if ((rc = W.slot_stats.ensure(sizeof(S2FrameStats) * nslot + 64))) return rc;
     cf32* d_pll = (cf32*)W.pll.p;
@@ -1383,12 +1387,12 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
             P.lo = lo; P.bo = bo; P.to = to;
             lo += (size_t)P.frames.size() * P.f.N; bo += ((size_t)P.frames.size() * (P.f.kbch / 8) + 63) & ~(size_t)63; to += 2 * P.frames.size();
         }
-        const size_t res_bytes = (sizeof(int32_t) * to + 63) & ~(size_t)63, idx_bytes = (sizeof(int) * nf + 63) & ~(size_t)63;
-        if ((rc = ws_gl.ensure(lo + 64)) || (rc = ws_gb.ensure(bo + 64)) || (rc = ws_gt.ensure(res_bytes + idx_bytes + sizeof(uint8_t*) * nf + 64))) return rc;
-        if ((rc = W.llr_of.ensure(sizeof(int) * nf + sizeof(int8_t*) * nf + 64))) return rc;
-        int8_t** d_llr_of = (int8_t**)W.llr_of.p;
-        int* d_slot = (int*)(d_llr_of + nf);
-        int* j_idx = (int*)((char*)ws_gt.p + res_bytes);
+        ScratchLayout lt, ll;   // ws_gt, W.llr_of
+        const auto l_res = lt.add<int32_t>(to); const auto l_jidx = lt.add<int>(nf); const auto l_jdst = lt.add<uint8_t*>(nf);
+        const auto l_llr_of = ll.add<int8_t*>(nf); const auto l_slot = ll.add<int>(nf);
+        if ((rc = ws_gl.ensure(lo + 64)) || (rc = ws_gb.ensure(bo + 64)) || (rc = ws_gt.ensure(lt.bytes())) || (rc = W.llr_of.ensure(ll.bytes()))) return rc;
+        int8_t** d_llr_of = l_llr_of(W.llr_of.p); int* d_slot = l_slot(W.llr_of.p);
+        int32_t* d_res = l_res(ws_gt.p); int* j_idx = l_jidx(ws_gt.p);
         std::vector<int8_t*> llr_of(nf);
         std::vector<int> all_idx;
         for (const PartH& P : parts)
@@ -1410,8 +1414,8 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         J.vcm = true; J.n = n; J.nf = nf; J.dm.assign(dm, dm + n); J.first = first; J.hstats = hstats;
         J.frame_off = frame_off; J.stream_bytes = stream_bytes;
         J.frame_tr.assign(nf, -1); J.frame_co.assign(nf, -1);
-        J.d_trials = (const int32_t*)ws_gt.p; J.n_results = to;
-        J.d_dst = (uint8_t**)((char*)ws_gt.p + res_bytes + idx_bytes);
+        J.d_trials = d_res; J.n_results = to;
+        J.d_dst = l_jdst(ws_gt.p);
         const int nside = std::min<int>((int)parts.size(), dvbs2gpu_ctx::MIX_FEC_STREAMS);
         size_t off_idx = 0;
         for (size_t pi = 0; pi < parts.size(); ++pi) {
@@ -1420,7 +1424,7 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
             if (!ctx->grp_stream[k]) HIP_TRY(hipStreamCreateWithFlags(&ctx->grp_stream[k], hipStreamNonBlocking));
             hipStream_t sk = ctx->grp_stream[k];
             if ((int)pi < nside) HIP_TRY(hipStreamWaitEvent(sk, ctx->ev_llr, 0));
-            int32_t* g_tr = (int32_t*)ws_gt.p + P.to;
+            int32_t* g_tr = d_res + P.to;
             uint8_t* g_bb = (uint8_t*)ws_gb.p + P.bo;
             if ((rc = fec_run(ctx, P.f, (const int8_t*)ws_gl.p + P.lo, cnt, P.mt, P.force, g_bb, g_tr, g_tr + cnt, sk, &ctx->fws_grp[k]))) return rc;
             J.parts.push_back(PendingFec::Part{P.f.kbch / 8, cnt, g_bb, j_idx + off_idx, P.to});
@@ -1454,10 +1458,10 @@ int frontend_prepass(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const 
     if ((rc = get_rrc(ctx, d0->cfg.rrc_taps, d0->cfg.rrc_alpha, d0->cfg.samplerate / d0->cfg.symbolrate, &d_taps))) return rc;
     Workspace& ws = ctx->ws_rx.slot_stats;      // (free: a pre-passed group is never staged)
     int max_count;
-    if ((rc = upload_work(dm, n, d_iq, counts, d_out, 0, false, ws, sizeof(int) * n + sizeof(float) * n + 64, st, &max_count))) return rc;
-    S2StreamWork* d_work = (S2StreamWork*)ws.p;
-    int* d_nsym = (int*)(d_work + n);
-    float* d_nco = (float*)(d_nsym + n);
+    ScratchLayout L;
+    const auto l_work = L.add<S2StreamWork>(n); const auto l_nsym = L.add<int>(n); const auto l_nco = L.add<float>(n);
+    if ((rc = upload_work(dm, n, d_iq, counts, d_out, 0, false, ws, L.bytes(), st, &max_count))) return rc;
+    S2StreamWork* d_work = l_work(ws.p); int* d_nsym = l_nsym(ws.p); float* d_nco = l_nco(ws.p);
     { StageSpan sp(ctx->timers, ST_FRONTEND, st); HIP_TRY(frontend_sliced(ctx, d_work, n, d0->co, st)); }
     { StageSpan sp(ctx->timers, ST_RRC, st); HIP_TRY(s2_rrc_decim_launch(d_work, n, max_count + max_count / 32 + 8, d_taps, d0->cfg.rrc_taps, st)); }
     nsym_out->assign(n, 0);
