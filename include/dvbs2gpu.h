@@ -612,7 +612,8 @@ uint32_t dvbs2gpu_crc32_mpeg_shift(uint32_t crc, uint32_t nbytes);
  * separate from the calls above, which keep the reference's behaviour and their own state whether the mode is on or not.
  *   Slot: [CRC-8 of the previous UP][187 UP bytes][ISSY: 0, 2 or 3 bytes, present iff ISSYI][DNP: 1 byte iff NPD].
  *   Frames: header CRC-8, DFL a whole number of bytes that fits the frame, SYNCD < DFL or 65535; others are counted in
- *     rejected_frames.  Frames with TS/GS != 11 or of an ISI that is not selected are counted in skipped_frames (SIS frames are ISI 0).
+ *     rejected_frames.  Frames with TS/GS != 11 or of an ISI that is not selected are counted in skipped_frames (SIS frames are ISI 0);
+ *     with dvbs2gpu_bbts_ma_set_gse on, the GSE frames of a selected ISI are decapsulated instead (below).
  *   Framing is per frame: the first slot that starts in a frame starts SYNCD/8 bytes into the data field (65535: none does, the
  *     data field continues one slot), further ones every slot length.  A slot leaves when the byte after it -- the CRC-8 of its
  *     UP -- has arrived; what is left of a data field (1 .. slot length bytes) is carried to the next frame of the SAME ISI and
@@ -665,6 +666,53 @@ int dvbs2gpu_bbts_ma_flush(dvbs2gpu_bbts* b, uint8_t* const* out, int cap, int* 
 /* the same with HOST buffers for any bank (the companion of dvbs2gpu_bbts_ma_work) */
 int dvbs2gpu_bbts_ma_flush_host(dvbs2gpu_bbts* b, uint8_t* const* h_out, int cap, int* out_bytes);
 int dvbs2gpu_bbts_ma_get_stats(dvbs2gpu_bbts* b, int stream, int slot, dvbs2gpu_bbts_ma_stats* h_out);
+
+/* ---- GSE in the mode-adaptation mode (TS 102 606-1): one reassembly context per (stream, selected ISI) lane.  Off by default; while
+ * it is off every call above behaves as before and GSE frames count in skipped_frames.  Rules, where they differ from the reference
+ * mode's above or where the standard (or memory of it) leaves room:
+ *   Frames walked: header accepted as above, ISI selected, TS/GS = 01, UPL = 0, neither ISSYI nor NPD.  Other TS/GS = 01 frames of a
+ *     selected ISI count in skipped_frames.  A walked frame counts in dvbs2gpu_bbts_ma_stats.frames of its lane.
+ *   The walk starts at byte 0 of the data field and covers DFL/8 bytes.  SYNCD is not used: there is no "synchronised" state and no
+ *     SYNCD/8 + 1 skip, so the result does not depend on how calls cut the frame sequence.  Frame sizes come from frame_bytes.
+ *   Packet: S, E, LT and a 12-bit GSE length.  Fixed fields after the two header bytes: S=1 E=1 protocol type (2); S=1 E=0 frag id,
+ *     total length, protocol type (5); S=0 frag id (1), and an END (S=0 E=1) ends with its CRC-32 (4 more).  Labels exist in S=1
+ *     packets only: LT 00 six bytes, 01 three bytes, 10 none, 11 (re-use of the label before) none.  They are skipped, not filtered
+ *     (DVBS2GPU_GSE_PDU_LABEL in a row says that label BYTES were present: a re-use packet reports "no label"),
+ *     and LT is not looked at in S=0 packets.  S=0 E=0 LT=00 is padding and ends the frame's walk, also in the last byte of a data field.
+ *   Malformed: a length field smaller than the fixed fields + label (for an END: + 4, so a reassembled length is never negative and
+ *     dropped_no_fit stays 0 in this mode), a packet that would pass the end of the data field, or one byte left that is not padding.
+ *     It ends the walk of ITS frame only and counts once in malformed_frames; the packets before it stand.  The reference mode's
+ *     `& 0xffff` length arithmetic and its "past the end of the call's input" rule do not apply.  The total-length field of a START is
+ *     covered by the CRC-32 and otherwise not used, as in the reference.
+ *   Reassembly: three slots per lane, first fit; a START takes a free slot or the one that holds its frag id; other fragments go to
+ *     the busy slot with their frag id or are ignored; a fragment that would pass 64 KiB frees the slot (dropped_overflow); CRC-32/MPEG
+ *     over total length, protocol type, label and PDU; last_crc_err is the verdict of the lane's last END.  Slots belong to the lane:
+ *     frames of another ISI never touch them.  dvbs2gpu_bbts_select_isi (for that stream), dvbs2gpu_bbts_set_mode_adaptation and
+ *     switching GSE off start them afresh.
+ *   Output: the GRE packets of the reference mode (00 00, + the protocol type for 0x0800 / 0x86DD, then the PDU) in the lane's own
+ *     buffer d_out[i*8 + k].  A lane that receives TS and GSE frames writes both in FRAME ORDER: the concatenated output of any
+ *     cutting of the sequence into calls is the same.
+ *   Capacity: as for TS.  Sizes first, GRE bytes included; if one exceeds cap: DVBS2GPU_ERR_CAPACITY, needed[] filled, no state (TS or
+ *     GSE) has advanced, the table of the call is empty.  No PDU is ever dropped for lack of room.
+ *   The one host fallback: a frame with more than 256 packets.  That stream's call is then run by the library's host parser from
+ *     the same state (counted in host_fallback_calls); bytes, rows and state are what an unbounded record table would have given.
+ *   Memory (device banks): 3 x 64 KiB of slot storage per SELECTED lane plus 8 KiB of records and rows per frame of a call, allocated
+ *     when the bank first meets a GSE frame with the switch on; a later selection with more lanes makes the pool grow. */
+int dvbs2gpu_bbts_ma_set_gse(dvbs2gpu_bbts* b, int on);   /* needs the mode on */
+typedef struct dvbs2gpu_bbts_ma_gse_stats {
+    int64_t frames, packets, complete_pdus, reassembled_pdus, crc_failures, dropped_no_slot, dropped_overflow, dropped_no_fit,
+            bytes_delivered;             /* as in dvbs2gpu_gse_stats, per lane */
+    int64_t malformed_frames;            /* frames whose walk ended at a malformed packet */
+    int64_t host_fallback_calls;         /* per stream (the same for all its slots) */
+    int32_t open_slots;                  /* reassemblies open now, 0..3 */
+    int32_t last_crc_err;
+} dvbs2gpu_bbts_ma_gse_stats;
+int dvbs2gpu_bbts_ma_get_gse_stats(dvbs2gpu_bbts* b, int stream, int slot, dvbs2gpu_bbts_ma_gse_stats* h_out);
+/* the rows of the last call for slot `slot` of `stream`, in output order; offset is relative to that slot's buffer and
+ * DVBS2GPU_GSE_PDU_LABEL means label bytes of any length (6 or 3; not set for label re-use, which carries none).  The TS packets of a lane that mixes both are the bytes no row covers. */
+int dvbs2gpu_bbts_ma_get_pdu_table(dvbs2gpu_bbts* b, int stream, int slot, dvbs2gpu_gse_pdu* h_rows, int cap, int* n);
+/* the same in HBM, valid until the bank's next call (device banks only; NULL when *n == 0) */
+int dvbs2gpu_bbts_ma_get_pdu_table_device(dvbs2gpu_bbts* b, int stream, int slot, const dvbs2gpu_gse_pdu** d_rows, int* n);
 /* mask8: bit i of the 256-bit mask = a frame with a valid header and ISI i has been seen on `stream` since the mode was set */
 int dvbs2gpu_bbts_get_isi_seen(dvbs2gpu_bbts* b, int stream, uint32_t* mask8);
 

@@ -257,6 +257,26 @@ public:
         if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
         check(dvbs2gpu_bbts_ma_flush_host(h, tsframes, buffer_outsize, out_bytes));
     }
+    /* GSE frames of the selected ISIs: decapsulated into output k like in work() of the reference mode, one reassembly context per
+     * ISI (include/dvbs2gpu.h has the rules).  Off by default; needs setModeAdaptation() first. */
+    void setModeAdaptationGSE(bool on) {
+        if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
+        check(dvbs2gpu_bbts_ma_set_gse(h, on ? 1 : 0));
+    }
+    dvbs2gpu_bbts_ma_gse_stats modeAdaptationGSEStats(int output) {
+        dvbs2gpu_bbts_ma_gse_stats s;
+        check(dvbs2gpu_bbts_ma_get_gse_stats(h, 0, output, &s));
+        return s;
+    }
+    /* one row per GRE packet the last mode-adaptation work() wrote into output k; offsets are relative to tsframes[k] */
+    std::vector<dvbs2gpu_gse_pdu> modeAdaptationPduTable(int output) {
+        if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
+        int n = 0;
+        check(dvbs2gpu_bbts_ma_get_pdu_table(h, 0, output, nullptr, 0, &n));
+        std::vector<dvbs2gpu_gse_pdu> rows(n);
+        if (n > 0) check(dvbs2gpu_bbts_ma_get_pdu_table(h, 0, output, rows.data(), n, &n));
+        return rows;
+    }
     dvbs2gpu_bbts_ma_stats modeAdaptationStats(int output) {
         dvbs2gpu_bbts_ma_stats s;
         check(dvbs2gpu_bbts_ma_get_stats(h, 0, output, &s));

@@ -76,6 +76,13 @@ class GseStats(C.Structure):
                                          'dropped_no_fit', 'bytes_delivered', 'host_fallback_calls', 'fallback_records', 'fallback_capacity')]
 
 
+class BbtsMaGseStats(C.Structure):
+    """dvbs2gpu_bbts_ma_gse_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('frames', 'packets', 'complete_pdus', 'reassembled_pdus', 'crc_failures', 'dropped_no_slot', 'dropped_overflow',
+                                         'dropped_no_fit', 'bytes_delivered', 'malformed_frames', 'host_fallback_calls')] + \
+               [('open_slots', C.c_int32), ('last_crc_err', C.c_int32)]
+
+
 class GsePdu(C.Structure):
     """dvbs2gpu_gse_pdu"""
     _fields_ = [('offset', C.c_uint32), ('bytes', C.c_uint32), ('protocol', C.c_uint16), ('flags', C.c_uint16), ('reserved', C.c_uint32)]
@@ -219,6 +226,10 @@ PROTOTYPES = {
     'dvbs2gpu_bbts_ma_flush_host': (_i, [_vp, C.POINTER(_vp), _i, C.POINTER(_i)]),
     'dvbs2gpu_bbts_ma_get_stats': (_i, [_vp, _i, _i, C.POINTER(BbtsMaStats)]),
     'dvbs2gpu_bbts_get_isi_seen': (_i, [_vp, _i, C.POINTER(C.c_uint32)]),
+    'dvbs2gpu_bbts_ma_set_gse': (_i, [_vp, _i]),
+    'dvbs2gpu_bbts_ma_get_gse_stats': (_i, [_vp, _i, _i, C.POINTER(BbtsMaGseStats)]),
+    'dvbs2gpu_bbts_ma_get_pdu_table': (_i, [_vp, _i, _i, C.POINTER(GsePdu), _i, C.POINTER(_i)]),
+    'dvbs2gpu_bbts_ma_get_pdu_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
 }
 
 _lib = None
@@ -1060,6 +1071,30 @@ class BbTsParserBank(_Handle):
         st = BbtsMaStats()
         self._check(self.lib.dvbs2gpu_bbts_ma_get_stats(self.h, int(stream), int(slot), C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in BbtsMaStats._fields_ if k != 'reserved'}
+
+    # ---- GSE in the mode-adaptation mode: one reassembly context per (stream, selected ISI); GRE packets in the slot's own buffer
+    def ma_set_gse(self, on=True):
+        """GSE frames of the selected ISIs are decapsulated (off: skipped, the slots' GSE state dropped); needs the mode on"""
+        self._check(self.lib.dvbs2gpu_bbts_ma_set_gse(self.h, int(bool(on))))
+
+    def ma_gse_stats(self, stream=0, slot=0):
+        st = BbtsMaGseStats()
+        self._check(self.lib.dvbs2gpu_bbts_ma_get_gse_stats(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in BbtsMaGseStats._fields_}
+
+    def ma_pdu_table(self, stream=0, slot=0):
+        """[(offset in the slot's output, bytes, protocol type, flags)] of the last call, in output order"""
+        n = C.c_int()
+        self._check(self.lib.dvbs2gpu_bbts_ma_get_pdu_table(self.h, int(stream), int(slot), None, 0, C.byref(n)))
+        rows = (GsePdu * max(n.value, 1))()
+        self._check(self.lib.dvbs2gpu_bbts_ma_get_pdu_table(self.h, int(stream), int(slot), rows, n.value, C.byref(n)))
+        return [(r.offset, r.bytes, r.protocol, r.flags) for r in rows[:n.value]]
+
+    def ma_pdu_table_device(self, stream=0, slot=0):
+        """(device pointer or None, rows): the same table as dvbs2gpu_gse_pdu records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self.lib.dvbs2gpu_bbts_ma_get_pdu_table_device(self.h, int(stream), int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     def isi_seen(self, stream=0):
         """-> sorted list of the ISIs seen on `stream` since the mode was switched on"""

@@ -14,6 +14,7 @@
 // a slot restarted within the call is written at offset 0 after the PDU that ended in it has been gathered.
 #include "ctx.h"
 #include "bbts_common.h"
+#include "bbts_gse_dev.h"
 
 using namespace s2;
 
@@ -100,34 +101,7 @@ __global__ void __launch_bounds__(256) gse_scan_kernel(const uint8_t* const* __r
     }
     __syncthreads();
     const int n = fr.npkt;
-    // CRC-32 of every fragment's span from a zero register: a wave per packet, 64-byte chunks counted from the END of the
-    // span per lane, each moved to the end of the span by x^(8 * 64 m), XOR-reduced over the wave
-    const int wave = tid >> 6, lane = tid & 63;
-    for (int k = wave; k < n; k += 4) {
-        const int kind = (rec[k].w1 >> 24) & 3;
-        if (kind == GSE_COMPLETE) continue;
-        const int sa = span_at[k], sl = span_len[k];
-        uint32_t acc = 0;
-        for (int m = lane; m * 64 < sl; m += 64) {
-            const int hi = sl - 64 * m, lo = hi > 64 ? hi - 64 : 0;
-            uint32_t c = 0;
-            for (int i = lo; i < hi; ++i) c = crc32m_byte(c, rd(sa + i));
-            acc ^= crc32m_mulmod(c, crc32m_xpow(64u * m));
-        }
-        for (int d = 32; d > 0; d >>= 1) acc ^= __shfl_xor(acc, d, 64);
-        if (lane == 0) {
-            const uint32_t xp = crc32m_xpow((uint32_t)sl);
-            if (kind == GSE_START) {
-                rec[k].a = crc32m_mulmod(0xffffffffu, xp) ^ acc;
-            } else if (kind == GSE_MIDDLE) {
-                rec[k].a = acc; rec[k].b = xp;
-            } else {
-                const int e = (int)rec[k].src + (int)(rec[k].w1 & 0xffff);
-                const uint32_t rx = rd(e - 4) << 24 | rd(e - 3) << 16 | rd(e - 2) << 8 | rd(e - 1);
-                rec[k].a = acc ^ rx; rec[k].b = xp;
-            }
-        }
-    }
+    gse_span_crcs(rec, span_at, span_len, n, rd, tid);
     __syncthreads();
     GsePkt* o = pkts + ((size_t)s * max_frames + f) * GSE_PKT_CAP;
     for (int k = tid; k < n; k += 256) o[k] = rec[k];
@@ -181,68 +155,7 @@ __global__ void __launch_bounds__(64) gse_stream_kernel(const uint8_t* const* __
             ++gs.cnt.frames;
             for (int k = 0; k < fr.npkt && !fallback; ++k) {
                 const int idx = f * GSE_PKT_CAP + k;
-                GsePkt p = pk[idx];
-                const int plen = p.w1 & 0xffff, id = (p.w1 >> 16) & 0xff, kind = (p.w1 >> 24) & 3, label = (p.w1 >> 26) & 1;
-                ++gs.cnt.packets;
-                if (kind == GSE_COMPLETE) {
-                    const unsigned proto = p.b;
-                    const int total = 2 + ((proto == 0x0800 || proto == 0x86DD) ? 2 : 0) + plen;
-                    if (w + total > cap) { fallback = GSE_FALLBACK_CAPACITY; break; }
-                    row[so.nrows++] = {(uint32_t)w, (uint32_t)total, (uint16_t)proto, (uint16_t)(label ? 2 : 0), 0};
-                    pk[idx].a = (uint32_t)w;
-                    w += total;
-                    ++gs.cnt.complete_pdus; gs.cnt.bytes_delivered += total;
-                    continue;
-                }
-                int r = -1;
-#pragma unroll
-                for (int q = 2; q >= 0; --q) {
-                    const GseSlot& sq = gs.slot[q];
-                    if (kind == GSE_START ? (!sq.busy || sq.frag_id == id) : (sq.busy && sq.frag_id == id)) r = q;
-                }
-                if (r < 0) {
-                    if (kind == GSE_START) ++gs.cnt.dropped_no_slot;
-                    pk[idx].a = 0xffffffffu;
-                    continue;
-                }
-                // the slot and its chain end in registers (selected, not indexed: indexing would put the state into scratch)
-                GseSlot sl = r == 0 ? gs.slot[0] : r == 1 ? gs.slot[1] : gs.slot[2];
-                int ol = r == 0 ? so.open_last[0] : r == 1 ? so.open_last[1] : so.open_last[2];
-                auto put = [&]() {
-                    if (r == 0) { gs.slot[0] = sl; so.open_last[0] = ol; }
-                    else if (r == 1) { gs.slot[1] = sl; so.open_last[1] = ol; }
-                    else { gs.slot[2] = sl; so.open_last[2] = ol; }
-                };
-                const int link = ol >= 0 ? ol : -(1 + r);
-                if (kind == GSE_START) {
-                    sl.busy = 1; sl.frag_id = id; sl.proto = p.b; sl.fill = plen; sl.crc = p.a; sl.label = label;
-                    pk[idx].a = 0; pk[idx].b = (uint32_t)(-(1 + r));
-                    ol = idx;
-                } else if (sl.fill + plen > GSE_SLOT_BYTES) {
-                    sl.busy = 0; ol = -1;
-                    ++gs.cnt.dropped_overflow;
-                    pk[idx].a = 0xffffffffu;
-                } else if (kind == GSE_MIDDLE) {
-                    sl.crc = crc32m_mulmod(sl.crc, p.b) ^ p.a;
-                    pk[idx].a = (uint32_t)sl.fill; pk[idx].b = (uint32_t)link;
-                    sl.fill += plen;
-                    ol = idx;
-                } else {
-                    sl.busy = 0; ol = -1;
-                    put();
-                    const int len = sl.fill + plen - 4;
-                    gs.crc_err = crc32m_mulmod(sl.crc, p.b) != p.a;
-                    pk[idx].a = 0xffffffffu;
-                    if (gs.crc_err) { ++gs.cnt.crc_failures; continue; }
-                    const int total = 2 + ((sl.proto == 0x0800 || sl.proto == 0x86DD) ? 2 : 0) + len;
-                    if (len < 0) { ++gs.cnt.dropped_no_fit; continue; }
-                    if (w + total > cap) { fallback = GSE_FALLBACK_CAPACITY; break; }
-                    pk[idx].a = (uint32_t)so.nrows; pk[idx].b = (uint32_t)link;
-                    row[so.nrows++] = {(uint32_t)w, (uint32_t)total, (uint16_t)sl.proto, (uint16_t)(1 | (sl.label ? 2 : 0)), 0};
-                    w += total;
-                    ++gs.cnt.reassembled_pdus; gs.cnt.bytes_delivered += total;
-                }
-                put();
+                if (!gse_apply_packet(gs, so, w, cap, pk, idx, row, true)) fallback = GSE_FALLBACK_CAPACITY;
             }
         }
         d[f] = e;
@@ -272,29 +185,6 @@ __global__ void __launch_bounds__(64) gse_stream_kernel(const uint8_t* const* __
 }
 
 // ------------------------------------------------------------------------------------------------------------- byte movement
-// dword stores where the destination allows, the source read unaligned
-// (t of nt threads take part)
-__device__ inline void gse_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int n, int t, int nt) {
-    typedef unsigned __attribute__((aligned(1))) unaligned_u32;
-    if (n <= 0) return;
-    int head = (int)((4 - (reinterpret_cast<uintptr_t>(dst) & 3)) & 3);
-    if (head > n) head = n;
-    const int words = (n - head) / 4;
-    for (int i = t; i < head; i += nt) dst[i] = src[i];
-    for (int i = t; i < words; i += nt)
-        reinterpret_cast<unsigned*>(dst + head)[i] = *reinterpret_cast<const unaligned_u32*>(src + head + 4 * i);
-    for (int i = head + 4 * words + t; i < n; i += nt) dst[i] = src[i];
-}
-
-__device__ inline int gse_gre_header(uint8_t* o, unsigned proto, int t) {
-    const bool known = proto == 0x0800 || proto == 0x86DD;
-    if (t == 0) {
-        o[0] = 0; o[1] = 0;                    // GRE: no checksum, no key, no sequence number, version 0
-        if (known) { o[2] = (uint8_t)(proto >> 8); o[3] = (uint8_t)proto; }
-    }
-    return known ? 4 : 2;
-}
-
 __global__ void __launch_bounds__(256) gse_move_kernel(const uint8_t* const* __restrict__ in, uint8_t* const* __restrict__ out,
                                                        const int* __restrict__ nframes, int max_frames, const BbtsFrameDesc* __restrict__ desc,
                                                        const BbtsStreamPlan* __restrict__ plan, const GseFrameRec* __restrict__ frec,
@@ -314,36 +204,7 @@ __global__ void __launch_bounds__(256) gse_move_kernel(const uint8_t* const* __r
     if (fr.kind != 2) return;
     const GsePkt* pk = pkts + (size_t)s * max_frames * GSE_PKT_CAP;
     const dvbs2gpu_gse_pdu* row = rows + (size_t)s * max_frames * GSE_PKT_CAP;
-    const int lane = threadIdx.x & 63;
-    for (int k = threadIdx.x >> 6; k < fr.npkt; k += 4) {       // a wave per packet
-        const GsePkt p = pk[f * GSE_PKT_CAP + k];
-        if (p.a == 0xffffffffu) continue;
-        const int plen = p.w1 & 0xffff, kind = (p.w1 >> 24) & 3;
-        if (kind == GSE_COMPLETE) {
-            uint8_t* o = out[s] + p.a;
-            const int hl = gse_gre_header(o, p.b, lane);
-            gse_copy(o + hl, bb + p.src, plen, lane, 64);
-        } else if (kind == GSE_END) {
-            const dvbs2gpu_gse_pdu r = row[p.a];
-            uint8_t* o = out[s] + r.offset;
-            const int hl = gse_gre_header(o, r.protocol, lane);
-            const int len = (int)r.bytes - hl;
-            o += hl;
-            GsePkt q = p;
-            int off = len - (plen - 4);           // where this fragment starts in the PDU; the PDU is the first `len` bytes
-            for (;;) {
-                const int n = (int)(q.w1 & 0xffff);
-                gse_copy(o + off, bb + q.src, (off + n > len ? len - off : n), lane, 64);
-                const int link = (int)q.b;
-                if (link < 0) {
-                    gse_copy(o, slots + ((size_t)s * 3 + (-1 - link)) * GSE_SLOT_BYTES, off < len ? off : len, lane, 64);
-                    break;
-                }
-                q = pk[link];
-                off = (int)q.a;
-            }
-        }
-    }
+    gse_move_packets(bb, out[s], pk, row, f, fr.npkt, slots + (size_t)s * 3 * GSE_SLOT_BYTES);
 }
 
 __global__ void __launch_bounds__(256) gse_append_kernel(const uint8_t* const* __restrict__ in, const BbtsStreamPlan* __restrict__ plan,
@@ -360,12 +221,7 @@ __global__ void __launch_bounds__(256) gse_append_kernel(const uint8_t* const* _
     int at = sout[s].open_last[r];
     if (at < 0) return;
     const GsePkt* pk = pkts + (size_t)s * max_frames * GSE_PKT_CAP;
-    uint8_t* buf = slots + ((size_t)s * 3 + r) * GSE_SLOT_BYTES;
-    while (at >= 0) {
-        const GsePkt q = pk[at];
-        gse_copy(buf + q.a, bb + q.src, (int)(q.w1 & 0xffff), threadIdx.x, 256);      // fill + length <= 64 KiB by the overflow rule
-        at = (int)q.b;
-    }
+    gse_append_chain(bb, pk, at, slots + ((size_t)s * 3 + r) * GSE_SLOT_BYTES);
 }
 
 // -------------------------------------------------------------------------------------------------------------------- host

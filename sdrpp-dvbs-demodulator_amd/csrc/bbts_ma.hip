@@ -12,7 +12,20 @@
 //   bbts_ma_emit_kernel   one workgroup per frame: DNP prefix sum, null packets, 0x47 + 187 bytes per slot in dwords, TEI.
 // The host commits the shadow state and launches the third kernel only when every lane's output fits.
 // MaHostStream below applies the same rules to host buffers, byte by byte (host-only banks; the GPU path's second implementation).
+//
+// GSE in this mode (dvbs2gpu_bbts_ma_set_gse; rules in include/dvbs2gpu.h): one reassembly context per (stream, selected ISI) lane.
+//   bbts_ma_frame_kernel      marks the GSE frames of selected ISIs in their records;
+//   bbts_ma_gse_scan_kernel   one workgroup per (frame, stream): the data field staged in LDS, one lane follows the packet chain, a wave
+//                             per fragment computes the CRC-32 of its span (bbts_gse_dev.h); 16 bytes per packet;
+//   bbts_ma_lane_kernel<true> the lane pass above, which now also applies the packet records of its lane's GSE frames to the lane's
+//                             three slots where the frame stands in the sequence: the GRE bytes enter the SAME running output offset
+//                             as the TS packets, so both interleave in frame order and the call still synchronises twice;
+//   bbts_ma_gse_move_kernel   behind the emit kernel: complete PDUs and PDUs that END in a frame, gathered into the lane's buffer;
+//   bbts_ma_gse_append_kernel fragments of PDUs still open go to the lane's slot buffers (only read by move, only written here).
 #include "bbts_common.h"
+#include "bbts_gse_dev.h"
+
+#include <climits>
 
 #include <memory>
 
@@ -29,7 +42,7 @@ constexpr int MA_TS = 188, MA_LANES = 8, MA_CARRY = 192, MA_NO_START = 65535, MA
 __host__ __device__ inline int ma_slot_len(int issy, int npd) { return kMa.issy_off + issy + npd; }
 __host__ __device__ inline int ma_crc_end(int span, int L) { return span ? L : kMa.up_off + kMa.up_len; }   // CRC-8 over [up_off, end)
 
-struct MaHdr { int ts_gs, isi, issyi, npd, df, s0, nostart; };
+struct MaHdr { int ts_gs, isi, issyi, npd, df, s0, nostart, upl; };
 // a frame of `size` bytes: CRC-8 of the BBHEADER, DFL whole bytes that fit the frame, SYNCD inside the data field or 65535 (no slot
 // starts here).  The reference's `syncd >= dfl - 8` rejection is not applied: a slot may start in the last byte of a data field.
 __host__ __device__ inline bool ma_header(const uint8_t* fr, int size, MaHdr* h) {
@@ -38,7 +51,7 @@ __host__ __device__ inline bool ma_header(const uint8_t* fr, int size, MaHdr* h)
     const int dfl = p.v[8], syncd = p.v[10];
     if (dfl % 8 || dfl > (size - 10) * 8 || !(syncd == MA_NO_START || syncd < dfl)) return false;
     h->ts_gs = p.v[0]; h->isi = p.v[6]; h->issyi = p.v[3]; h->npd = p.v[4]; h->df = dfl / 8;
-    h->nostart = syncd == MA_NO_START;
+    h->nostart = syncd == MA_NO_START; h->upl = p.v[7];
     h->s0 = h->nostart ? h->df : syncd / 8;
     return true;
 }
@@ -55,7 +68,7 @@ __host__ __device__ inline bool ma_iscr(const uint8_t* f, int issy, unsigned* v)
     return false;
 }
 
-struct MaCfg { int issy_bytes, crc_span, reinsert_nulls, check_crc; };
+struct MaCfg { int issy_bytes, crc_span, reinsert_nulls, check_crc, gse; };
 struct MaSel { uint8_t isi[MA_LANES]; int n; };
 struct MaLaneState {
     int c, Lc, cfl, issy;                      // carried bytes, their slot length, issy | npd << 2 of that slot, ISSY length in use
@@ -68,11 +81,43 @@ struct MaFrameRec {
     int lane, isi, L, cfl;                     // lane: 0..7, -1 skipped (not TS / ISI not selected), -2 header rejected; L 0: ISSY length unknown
     int s0, nslots, tail, df, data_off, nostart;
     int nnull, issy_dec, first_byte, iscr_valid;
-    unsigned iscr, pad;
+    unsigned iscr;
+    int gse;                                   // a GSE frame of lane `lane` that is walked (df, data_off set; the TS fields are not)
     unsigned long long errmask;
 };
 struct MaFrameDesc { const uint8_t* carry; int out_off, joined, c, dnp, tei, pad; };
 struct MaFin { const uint8_t* src; int len, pad; };
+
+// ------------------------------------------------------------------------------------------------- GSE per lane
+__host__ __device__ inline bool ma_gse_frame(const MaHdr& h) { return h.ts_gs == 1 && h.upl == 0 && !h.issyi && !h.npd; }
+struct MaGsePkt { int kind, id, label, body, plen; unsigned proto; };
+// the GSE packet at byte `at` of a data field of df bytes (rd(i): its byte i): 0 padding, the walk ends; -1 malformed (the length field
+// is smaller than the fixed fields + label, an END shorter than its CRC-32 included, or the packet passes the end of the data field);
+// else the bytes the packet takes
+template <typename Rd>
+__host__ __device__ inline int ma_gse_packet(Rd rd, int at, int df, MaGsePkt* p) {
+    const unsigned h1 = rd(at);
+    if ((h1 & 0xf0) == 0) return 0;                                // S = 0, E = 0, LT = 00
+    if (at + 2 > df) return -1;
+    const bool S = h1 & 0x80, E = h1 & 0x40;
+    const int lt = h1 >> 4 & 3, field = (int)((h1 & 0x0f) << 8 | rd(at + 1));
+    const int fixed = S && E ? 2 : S ? 5 : 1;                      // protocol type | frag id, total length, protocol type | frag id
+    const int label = S ? (lt == 0 ? 6 : lt == 1 ? 3 : 0) : 0;     // 10: none, 11: the label of the packet before (re-use), no bytes
+    if (field < fixed + label + (!S && E ? 4 : 0) || at + 2 + field > df) return -1;
+    p->kind = S && E ? GSE_COMPLETE : S ? GSE_START : E ? GSE_END : GSE_MIDDLE;
+    p->id = S && E ? 0 : (int)rd(at + 2);
+    p->label = label; p->body = at + 2 + fixed + label; p->plen = field - fixed - label;
+    p->proto = S && E ? rd(at + 2) << 8 | rd(at + 3) : S ? rd(at + 5) << 8 | rd(at + 6) : 0;
+    return 2 + field;
+}
+struct MaGseLane { GseDevState g; long long malformed; };          // three slots, the counters, the last END's verdict
+struct MaGseFrame { int npkt, malformed, over, pad; };              // over: more than GSE_PKT_CAP packets (the one host fallback)
+enum { MA_GSE_DONE = 0, MA_GSE_RECORDS = 1, MA_GSE_STORAGE = 2 };
+struct MaGseOut { int open_last[3]; int nrows, flag, rowbase, pad[2]; };   // per lane and call; rowbase: its rows in the stream's table
+struct MaGseDev {                                                   // what the lane pass needs for GSE (all null while the switch is off)
+    const MaGseFrame* gfr; GsePkt* pkts; dvbs2gpu_gse_pdu* rows;
+    const MaGseLane* lanes_old; MaGseLane* lanes_new; MaGseOut* out; int* info;
+};
 
 // CRC-8 tables: T[k][x] = CRC of byte x followed by k zero bytes (k < 4); ADV[k][b] = register bit b after k zero bytes (k <= 192)
 constexpr int MA_TAB_BYTES = 1024 + (MA_CARRY + 1) * 8;
@@ -113,6 +158,11 @@ __global__ void __launch_bounds__(256) bbts_ma_frame_kernel(const uint8_t* const
     r.isi = h.isi; r.lane = -1;
     const MaSel se = sel[s];
     for (int k = se.n - 1; k >= 0; --k) if (se.isi[k] == h.isi) r.lane = k;
+    if (cfg.gse && r.lane >= 0 && ma_gse_frame(h)) {
+        r.gse = 1; r.df = h.df; r.data_off = off + 10;
+        if (lane == 0) *out = r;
+        return;
+    }
     if (h.ts_gs != 3 || r.lane < 0) { r.lane = -1; if (lane == 0) *out = r; return; }
     int issy = 0;
     if (h.issyi) {
@@ -183,13 +233,15 @@ __device__ inline unsigned ma_wave_crc(const uint8_t* carry, int c, const uint8_
     return x;
 }
 
+template <bool GSE>
 __global__ void __launch_bounds__(256) bbts_ma_lane_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nframes, int nstreams,
                                                            int max_frames, MaCfg cfg, const MaSel* __restrict__ sel,
                                                            const MaFrameRec* __restrict__ recs, const uint8_t* __restrict__ tabs,
                                                            const MaLaneState* __restrict__ lanes_old, MaLaneState* __restrict__ lanes_new,
                                                            const MaStreamState* __restrict__ strm_old, MaStreamState* __restrict__ strm_new,
                                                            const uint8_t* __restrict__ carry_old, uint8_t* __restrict__ joinbuf,
-                                                           MaFrameDesc* __restrict__ desc, MaFin* __restrict__ fins, int* __restrict__ needed) {
+                                                           MaFrameDesc* __restrict__ desc, MaFin* __restrict__ fins, int* __restrict__ needed,
+                                                           MaGseDev gd) {
     const int lane = threadIdx.x & 63, w = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int s = w / MA_LANES, slot = w % MA_LANES;
     if (s >= nstreams) return;
@@ -210,11 +262,29 @@ __global__ void __launch_bounds__(256) bbts_ma_lane_kernel(const uint8_t* const*
         if (lane == 0) strm_new[s] = ss;
     }
     int out_off = 0;
+    // GSE: the lane's context and what this call does to it; every lane of the wave computes the same, lane 0 stores
+    MaGseLane gs = {};
+    GseStreamOut so = {{-1, -1, -1}, 0, 0, {0, 0, 0}};
+    int gflag = MA_GSE_DONE, rowbase = 0;
+    if (GSE) gs = gd.lanes_old[w];
     if (slot < sel[s].n) {
+        if (GSE)                                   // the lane's rows follow those of the lower lanes' GSE frames in the stream's table
+            for (int f = 0; f < nf; ++f) if (rs[f].gse && rs[f].lane < slot) rowbase += GSE_PKT_CAP;
         for (int f = 0; f < nf; ++f) {
             const MaFrameRec r = rs[f];
             if (r.lane != slot) continue;
             ++st.frames;
+            if (GSE && r.gse) {
+                if (gflag) continue;
+                if (!gd.pkts) { gflag = MA_GSE_STORAGE; continue; }
+                const MaGseFrame gf = gd.gfr[(size_t)s * max_frames + f];
+                if (gf.over) { gflag = MA_GSE_RECORDS; continue; }
+                ++gs.g.cnt.frames; gs.malformed += gf.malformed;
+                GsePkt* pk = gd.pkts + (size_t)s * max_frames * GSE_PKT_CAP;
+                dvbs2gpu_gse_pdu* row = gd.rows + (size_t)s * max_frames * GSE_PKT_CAP + rowbase;
+                for (int k = 0; k < gf.npkt; ++k) gse_apply_packet(gs.g, so, out_off, INT_MAX, pk, f * GSE_PKT_CAP + k, row, lane == 0);
+                continue;
+            }
             if (r.issy_dec) st.issy = r.issy_dec;
             if (r.L == 0) { ++st.undecided; st.c = 0; continue; }
             const uint8_t* data = bb + r.data_off;
@@ -263,7 +333,99 @@ __global__ void __launch_bounds__(256) bbts_ma_lane_kernel(const uint8_t* const*
         MaFin fn = {carry, st.c, 0};
         fins[w] = fn;
         needed[w] = out_off;
+        if (GSE) {
+            MaGseOut o = {{-1, -1, -1}, so.nrows, gflag, rowbase, {0, 0}};
+            if (gs.g.slot[0].busy) o.open_last[0] = so.open_last[0];
+            if (gs.g.slot[1].busy) o.open_last[1] = so.open_last[1];
+            if (gs.g.slot[2].busy) o.open_last[2] = so.open_last[2];
+            gd.lanes_new[w] = gs;
+            gd.out[w] = o;
+            gd.info[w] = gflag | so.nrows << 2;
+        }
     }
+}
+
+// ------------------------------------------------------------------------------------------------- GSE: frame pass, byte movement
+__global__ void __launch_bounds__(256) bbts_ma_gse_scan_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nframes, int max_frames,
+                                                               const MaFrameRec* __restrict__ recs, MaGseFrame* __restrict__ gfr,
+                                                               GsePkt* __restrict__ pkts) {
+    const int s = blockIdx.y, f = blockIdx.x, tid = threadIdx.x;
+    if (f >= nframes[s]) return;
+    const MaFrameRec r = recs[(size_t)s * max_frames + f];
+    if (!r.gse) return;
+    __shared__ __attribute__((aligned(16))) uint8_t stage[MA_MAX_FRAME - 10];
+    __shared__ GsePkt rec[GSE_PKT_CAP];
+    __shared__ int span_at[GSE_PKT_CAP], span_len[GSE_PKT_CAP];
+    __shared__ MaGseFrame fr;
+    const uint8_t* data = in[s] + r.data_off;
+    const int df = r.df;                           // <= frame size - 10 <= sizeof(stage) by ma_header and the size check of the call
+    if ((reinterpret_cast<uintptr_t>(data) & 3) == 0) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(data);
+        for (int i = tid; i < df / 4; i += 256) reinterpret_cast<uint32_t*>(stage)[i] = src[i];
+        for (int i = (df & ~3) + tid; i < df; i += 256) stage[i] = data[i];
+    } else {
+        for (int i = tid; i < df; i += 256) stage[i] = data[i];
+    }
+    __syncthreads();
+    auto rd = [&](int i) -> unsigned { return stage[i]; };
+    if (tid == 0) {
+        MaGseFrame g = {0, 0, 0, 0};
+        int at = 0;
+        while (at < df) {
+            MaGsePkt p;
+            const int len = ma_gse_packet(rd, at, df, &p);
+            if (len == 0) break;
+            if (len < 0) { g.malformed = 1; break; }
+            if (g.npkt == GSE_PKT_CAP) { g.over = 1; g.npkt = 0; break; }
+            // records and spans count from the start of the stream's input, as in the reference mode
+            GsePkt q = {(uint32_t)(r.data_off + p.body), (uint32_t)p.plen | (uint32_t)p.id << 16 | (uint32_t)p.kind << 24 | (uint32_t)(p.label ? 1 : 0) << 26, 0, p.proto};
+            int sa = p.body, sl = 0;
+            if (p.kind == GSE_START) { sa = at + 3; sl = p.body + p.plen - sa; }        // total length, protocol type, label, payload
+            else if (p.kind == GSE_MIDDLE) sl = p.plen;
+            else if (p.kind == GSE_END) sl = p.plen - 4;
+            rec[g.npkt] = q; span_at[g.npkt] = r.data_off + sa; span_len[g.npkt] = sl;
+            ++g.npkt;
+            at += len;
+        }
+        fr = g;
+    }
+    __syncthreads();
+    const int n = fr.npkt, base = r.data_off;
+    gse_span_crcs(rec, span_at, span_len, n, [&](int i) -> unsigned { return stage[i - base]; }, tid);
+    __syncthreads();
+    GsePkt* o = pkts + ((size_t)s * max_frames + f) * GSE_PKT_CAP;
+    for (int k = tid; k < n; k += 256) o[k] = rec[k];
+    if (tid == 0) gfr[(size_t)s * max_frames + f] = fr;
+}
+
+// nframes: 0 for a stream whose call the host parser runs
+__global__ void __launch_bounds__(256) bbts_ma_gse_move_kernel(const uint8_t* const* __restrict__ in, uint8_t* const* __restrict__ out,
+                                                               const int* __restrict__ nframes, int max_frames, const MaFrameRec* __restrict__ recs,
+                                                               const MaGseFrame* __restrict__ gfr, const GsePkt* __restrict__ pkts,
+                                                               const dvbs2gpu_gse_pdu* __restrict__ rows, const MaGseOut* __restrict__ gout,
+                                                               const int* __restrict__ slotmap, const uint8_t* __restrict__ slots) {
+    const int s = blockIdx.y, f = blockIdx.x;
+    if (f >= nframes[s]) return;
+    const MaFrameRec r = recs[(size_t)s * max_frames + f];
+    if (!r.gse) return;
+    const int w = s * MA_LANES + r.lane, sm = slotmap[w];
+    if (sm < 0) return;
+    const size_t sb = (size_t)s * max_frames * GSE_PKT_CAP;
+    gse_move_packets(in[s], out[w], pkts + sb, rows + sb + gout[w].rowbase, f, gfr[(size_t)s * max_frames + f].npkt,
+                     slots + (size_t)sm * 3 * GSE_SLOT_BYTES);
+}
+
+__global__ void __launch_bounds__(256) bbts_ma_gse_append_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nframes,
+                                                                 int max_frames, const GsePkt* __restrict__ pkts, const MaGseOut* __restrict__ gout,
+                                                                 const int* __restrict__ slotmap, const int* __restrict__ placed,
+                                                                 uint8_t* __restrict__ slots) {
+    const int w = placed[blockIdx.y], r = blockIdx.x;      // the lanes that have a place in the pool: the selected ones
+    if (w < 0) return;
+    const int s = w / MA_LANES;
+    if (nframes[s] == 0) return;
+    const int at = gout[w].open_last[r], sm = slotmap[w];
+    if (at < 0 || sm < 0) return;
+    gse_append_chain(in[s], pkts + (size_t)s * max_frames * GSE_PKT_CAP, at, slots + ((size_t)sm * 3 + r) * GSE_SLOT_BYTES);
 }
 
 __device__ inline void ma_store4(uint8_t* o, unsigned v, bool aligned) {
@@ -336,11 +498,79 @@ struct MaHostStream {
     uint8_t carry[MA_LANES][MA_CARRY] = {};
     MaStreamState ss = {};
     uint8_t tab[256];
+    // GSE: per lane the context, the bytes of its open reassemblies (as many as are filled) and the rows of the last call
+    MaGseLane gse[MA_LANES] = {};
+    std::vector<uint8_t> gdata[MA_LANES][3];
+    std::vector<dvbs2gpu_gse_pdu> rows[MA_LANES];
 
     MaHostStream() {
         uint8_t t[MA_TAB_BYTES];
         ma_build_tables(t);
         memcpy(tab, t, 256);
+    }
+    void gse_reset() {
+        for (int k = 0; k < MA_LANES; ++k) {
+            gse[k] = MaGseLane{};
+            rows[k].clear();
+            for (auto& d : gdata[k]) d.clear();
+        }
+    }
+    static uint32_t crc32(uint32_t c, const uint8_t* p, int n) {
+        for (int i = 0; i < n; ++i) c = crc32m_byte(c, p[i]);
+        return c;
+    }
+    void gre(int slot, unsigned proto, const uint8_t* p, int n, int flags, std::vector<uint8_t>& out) {
+        const bool known = proto == 0x0800 || proto == 0x86DD;
+        const int total = 2 + (known ? 2 : 0) + n;
+        GseCounters& c = gse[slot].g.cnt;
+        ++((flags & 1) ? c.reassembled_pdus : c.complete_pdus);
+        c.bytes_delivered += total;
+        rows[slot].push_back({(uint32_t)out.size(), (uint32_t)total, (uint16_t)proto, (uint16_t)flags, 0});
+        out.push_back(0); out.push_back(0);    // GRE: no checksum, no key, no sequence number, version 0
+        if (known) { out.push_back((uint8_t)(proto >> 8)); out.push_back((uint8_t)proto); }
+        out.insert(out.end(), p, p + n);
+    }
+    // the data field of one GSE frame, packet by packet, with no limit on their number
+    void gse_frame(int slot, const uint8_t* data, int df, std::vector<uint8_t>& out) {
+        MaGseLane& gl = gse[slot];
+        ++gl.g.cnt.frames;
+        auto rd = [&](int i) -> unsigned { return data[i]; };
+        for (int at = 0, len; at < df; at += len) {
+            MaGsePkt p;
+            len = ma_gse_packet(rd, at, df, &p);
+            if (len == 0) break;
+            if (len < 0) { ++gl.malformed; break; }
+            ++gl.g.cnt.packets;
+            const uint8_t* body = data + p.body;
+            if (p.kind == GSE_COMPLETE) { gre(slot, p.proto, body, p.plen, p.label ? 2 : 0, out); continue; }
+            int r = -1;
+            for (int q = 2; q >= 0; --q) {
+                const GseSlot& sq = gl.g.slot[q];
+                if (p.kind == GSE_START ? (!sq.busy || sq.frag_id == p.id) : (sq.busy && sq.frag_id == p.id)) r = q;
+            }
+            if (r < 0) { if (p.kind == GSE_START) ++gl.g.cnt.dropped_no_slot; continue; }
+            GseSlot& sl = gl.g.slot[r];
+            std::vector<uint8_t>& buf = gdata[slot][r];
+            if (p.kind == GSE_START) {
+                sl = {1, p.id, p.plen, p.label ? 1 : 0, p.proto, crc32(0xffffffffu, data + at + 3, p.body + p.plen - (at + 3))};
+                buf.assign(body, body + p.plen);
+            } else if (sl.fill + p.plen > GSE_SLOT_BYTES) {
+                sl.busy = 0; buf.clear();
+                ++gl.g.cnt.dropped_overflow;
+            } else if (p.kind == GSE_MIDDLE) {
+                buf.insert(buf.end(), body, body + p.plen);
+                sl.fill += p.plen; sl.crc = crc32(sl.crc, body, p.plen);
+            } else {
+                buf.insert(buf.end(), body, body + p.plen - 4);
+                const uint8_t* e = body + p.plen;
+                const uint32_t rx = (uint32_t)e[-4] << 24 | (uint32_t)e[-3] << 16 | (uint32_t)e[-2] << 8 | e[-1];
+                sl.busy = 0;
+                gl.g.crc_err = crc32(sl.crc, body, p.plen - 4) != rx;
+                if (gl.g.crc_err) ++gl.g.cnt.crc_failures;
+                else gre(slot, sl.proto, buf.data(), (int)buf.size(), 1 | (sl.label ? 2 : 0), out);
+                buf.clear();
+            }
+        }
     }
     unsigned crc(const uint8_t* p, int a, int e) const {
         unsigned c = 0;
@@ -370,6 +600,7 @@ struct MaHostStream {
         ss.seen[h.isi >> 5] |= 1u << (h.isi & 31);
         int slot = -1;
         for (int k = sel.n - 1; k >= 0; --k) if (sel.isi[k] == h.isi) slot = k;
+        if (cfg.gse && slot >= 0 && ma_gse_frame(h)) { ++st[slot].frames; gse_frame(slot, fr + 10, h.df, outs[slot]); return; }
         if (h.ts_gs != 3 || slot < 0) { ++ss.skipped; return; }
         MaLaneState& l = st[slot];
         uint8_t* cy = carry[slot];
@@ -414,8 +645,9 @@ static void ma_flush_lane(MaHostStream& tool, MaLaneState& l, const uint8_t* cy,
 
 struct MaArgs {                                // the layout of d_args for n streams of up to mf frames
     ScratchLayout L;
-    ScratchPart<const uint8_t*> in; ScratchPart<uint8_t*> out; ScratchPart<int> nf, need, foff;
-    MaArgs(size_t n, size_t mf) : in(L.add<const uint8_t*>(n)), out(L.add<uint8_t*>(n * MA_LANES)), nf(L.add<int>(n)), need(L.add<int>(n * MA_LANES)), foff(L.add<int>(n * (mf + 1))) {}
+    ScratchPart<const uint8_t*> in; ScratchPart<uint8_t*> out; ScratchPart<int> nf, need, foff, ginfo, nf2;
+    MaArgs(size_t n, size_t mf) : in(L.add<const uint8_t*>(n)), out(L.add<uint8_t*>(n * MA_LANES)), nf(L.add<int>(n)), need(L.add<int>(n * MA_LANES)), foff(L.add<int>(n * (mf + 1))),
+                                  ginfo(L.add<int>(n * MA_LANES)), nf2(L.add<int>(n)) {}   // GSE: flag | rows << 2 per lane; frame counts without the host parser's streams
 };
 struct BbtsMa {
     MaCfg cfg;
@@ -434,6 +666,20 @@ struct BbtsMa {
     std::vector<int> h_foff;
     uint8_t *d_in1 = nullptr, *d_out1 = nullptr;   // staging of the single-stream host-buffer entry point
     size_t out1_cap = 0;
+    // GSE (dvbs2gpu_bbts_ma_set_gse): contexts and per-call results from the first switch-on; records, rows and slot buffers from the
+    // first GSE frame.  The slot pool has 3 x 64 KiB per SELECTED lane: slotmap[stream * 8 + k] is the lane's place in it or -1.
+    MaGseLane* d_glane[2] = {nullptr, nullptr};
+    MaGseOut* d_gout = nullptr;
+    int* d_slotmap = nullptr;
+    MaGseFrame* d_gfr = nullptr;
+    GsePkt* d_pkt = nullptr;
+    dvbs2gpu_gse_pdu* d_rows = nullptr;
+    uint8_t* d_slots = nullptr;
+    size_t slot_cap = 0;                       // lanes the pool holds
+    std::vector<int> slotmap, slot_free, ginfo;
+    std::vector<long long> fb_calls;           // per stream: calls the host parser ran
+    std::vector<std::vector<dvbs2gpu_gse_pdu>> fb_rows;   // per lane: the rows of such a call
+    std::vector<char> rows_host;
     // host-only banks
     std::unique_ptr<MaHostStream> host;
     MaHostStream tool;                         // flush of a device bank
@@ -442,7 +688,8 @@ struct BbtsMa {
 void bbts_ma_free(BbtsMa* m) {
     if (!m) return;
     void* ps[] = {m->d_lane[0], m->d_lane[1], m->d_strm[0], m->d_strm[1], m->d_carry[0], m->d_carry[1], m->d_sel, m->d_tabs, m->d_join,
-                  m->d_recs, m->d_desc, m->d_fins, m->d_args, m->d_in1, m->d_out1};
+                  m->d_recs, m->d_desc, m->d_fins, m->d_args, m->d_in1, m->d_out1, m->d_glane[0], m->d_glane[1], m->d_gout, m->d_slotmap,
+                  m->d_gfr, m->d_pkt, m->d_rows, m->d_slots};
     for (void* p : ps) if (p) (void)hipFree(p);
     delete m;
 }
@@ -462,6 +709,98 @@ static bool ma_offsets(const int* sizes, int n, int fbytes, int* off) {
         off[f + 1] = off[f] + b;
     }
     return true;
+}
+
+// ---- GSE storage of a device bank
+// d_slotmap: lane -> place [nstreams * 8], then place -> lane [nstreams * 8, of which slot_cap are used] for the append launch
+static int ma_gse_upload_map(BbtsMa* m) {
+    const size_t nl = m->slotmap.size();
+    std::vector<int> both(2 * nl, -1);
+    for (size_t w = 0; w < nl; ++w) {
+        both[w] = m->slotmap[w];
+        if (m->slotmap[w] >= 0) both[nl + m->slotmap[w]] = (int)w;
+    }
+    HIP_TRY(hipMemcpy(m->d_slotmap, both.data(), both.size() * sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+}
+// the pool grows to `lanes` places; what the lanes in it hold is kept
+static int ma_gse_grow_pool(BbtsMa* m, size_t lanes) {
+    if (lanes <= m->slot_cap) return 0;
+    uint8_t* nw = nullptr;
+    HIP_TRY(hipMalloc((void**)&nw, lanes * 3 * GSE_SLOT_BYTES));
+    if (m->d_slots) {
+        hipError_t e = hipMemcpy(nw, m->d_slots, m->slot_cap * 3 * GSE_SLOT_BYTES, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) { (void)hipFree(nw); return fail_hip(e, "hipMemcpy(bbts gse slots)"); }
+        (void)hipFree(m->d_slots);
+    }
+    for (size_t k = lanes; k-- > m->slot_cap;) m->slot_free.push_back((int)k);
+    m->d_slots = nw; m->slot_cap = lanes;
+    return 0;
+}
+// every selected lane of `stream` gets a place in the pool (its old ones go back first: a new selection starts afresh)
+static int ma_gse_place_stream(BbtsMa* m, int stream) {
+    int* map = m->slotmap.data() + (size_t)stream * MA_LANES;
+    for (int k = 0; k < MA_LANES; ++k) if (map[k] >= 0) { m->slot_free.push_back(map[k]); map[k] = -1; }
+    const int want = m->sel[stream].n;
+    if ((int)m->slot_free.size() < want) {
+        // at least the missing places, and at least half as many again as there are: re-selecting stream after stream
+        // reallocates and copies the pool a logarithmic number of times, not once per call
+        const size_t miss = want - m->slot_free.size(), half = m->slot_cap / 2;
+        size_t to = m->slot_cap + (miss > half ? miss : half);
+        if (to > m->slotmap.size()) to = m->slotmap.size();      // every lane of the bank placed: never more (and then enough)
+        const int rc = ma_gse_grow_pool(m, to);
+        if (rc) return rc;
+    }
+    for (int k = 0; k < want; ++k) { map[k] = m->slot_free.back(); m->slot_free.pop_back(); }
+    return 0;
+}
+// records, rows and the slot pool: when a bank with the switch on first meets a GSE frame
+static int ma_gse_storage(const BbtsBankView& v, BbtsMa* m) {
+    if (m->d_pkt) return 0;                        // the last of the allocations below: set when all of them stand
+    const size_t nfr = (size_t)v.nstreams * v.max_frames;
+    size_t lanes = 0;
+    for (const MaSel& s : m->sel) lanes += s.n;
+    // a call that failed half way (the pool is the large one) left what it had got: taken up here, not allocated again
+    if (!m->d_gfr) HIP_TRY(hipMalloc((void**)&m->d_gfr, nfr * sizeof(MaGseFrame)));
+    if (!m->d_rows) HIP_TRY(hipMalloc((void**)&m->d_rows, nfr * GSE_PKT_CAP * sizeof(dvbs2gpu_gse_pdu)));
+    int rc = ma_gse_grow_pool(m, lanes > 0 ? lanes : 1);
+    for (int i = 0; i < v.nstreams && !rc; ++i) rc = ma_gse_place_stream(m, i);
+    if (rc || (rc = ma_gse_upload_map(m))) return rc;
+    HIP_TRY(hipMalloc((void**)&m->d_pkt, nfr * GSE_PKT_CAP * sizeof(GsePkt)));
+    return 0;
+}
+
+// One stream of a device bank as a host parser, from state bank `bank`, and back: TS lanes, carried bytes, counters, GSE contexts and
+// the bytes of their open reassemblies.  This is how the host parser runs a stream's call in place of the kernels.
+static int ma_stream_to_host(BbtsMa* m, int i, int bank, MaHostStream& hs) {
+    const size_t w0 = (size_t)i * MA_LANES;
+    HIP_TRY(hipMemcpy(hs.st, m->d_lane[bank] + w0, sizeof(hs.st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hs.carry, m->d_carry[bank] + w0 * MA_CARRY, sizeof(hs.carry), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&hs.ss, m->d_strm[bank] + i, sizeof(hs.ss), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hs.gse, m->d_glane[bank] + w0, sizeof(hs.gse), hipMemcpyDeviceToHost));
+    for (int k = 0; k < MA_LANES; ++k)
+        for (int q = 0; q < 3; ++q) {
+            const GseSlot& sl = hs.gse[k].g.slot[q];
+            hs.gdata[k][q].clear();
+            if (!sl.busy || sl.fill <= 0 || m->slotmap[w0 + k] < 0) continue;
+            hs.gdata[k][q].resize(sl.fill);
+            HIP_TRY(hipMemcpy(hs.gdata[k][q].data(), m->d_slots + ((size_t)m->slotmap[w0 + k] * 3 + q) * GSE_SLOT_BYTES, sl.fill, hipMemcpyDeviceToHost));
+        }
+    return 0;
+}
+static int ma_stream_to_device(BbtsMa* m, int i, int bank, const MaHostStream& hs) {
+    const size_t w0 = (size_t)i * MA_LANES;
+    HIP_TRY(hipMemcpy(m->d_lane[bank] + w0, hs.st, sizeof(hs.st), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_carry[bank] + w0 * MA_CARRY, hs.carry, sizeof(hs.carry), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_strm[bank] + i, &hs.ss, sizeof(hs.ss), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_glane[bank] + w0, hs.gse, sizeof(hs.gse), hipMemcpyHostToDevice));
+    for (int k = 0; k < MA_LANES; ++k)
+        for (int q = 0; q < 3; ++q) {
+            const std::vector<uint8_t>& d = hs.gdata[k][q];
+            if (!hs.gse[k].g.slot[q].busy || d.empty() || m->slotmap[w0 + k] < 0) continue;
+            HIP_TRY(hipMemcpy(m->d_slots + ((size_t)m->slotmap[w0 + k] * 3 + q) * GSE_SLOT_BYTES, d.data(), d.size(), hipMemcpyHostToDevice));
+        }
+    return 0;
 }
 
 }  // namespace s2
@@ -559,9 +898,18 @@ int dvbs2gpu_bbts_select_isi(dvbs2gpu_bbts* b, int stream, const uint8_t* isi, i
     if (v.ctx) {
         HIP_TRY(hipSetDevice(v.ctx->device));
         HIP_TRY(hipMemcpy(m->d_lane[m->cur] + (size_t)stream * MA_LANES, z.data(), MA_LANES * sizeof(MaLaneState), hipMemcpyHostToDevice));
+        if (m->d_glane[0]) {                           // and so do their GSE contexts and, once there is a pool, their places in it
+            HIP_TRY(hipMemset(m->d_glane[m->cur] + (size_t)stream * MA_LANES, 0, MA_LANES * sizeof(MaGseLane)));
+            for (int k = 0; k < MA_LANES; ++k) { m->ginfo[stream * MA_LANES + k] = 0; m->rows_host[stream * MA_LANES + k] = 0; }
+            if (m->d_pkt) {
+                int rc = ma_gse_place_stream(m, stream);
+                if (rc || (rc = ma_gse_upload_map(m))) return rc;
+            }
+        }
         return ma_upload_sel(v, m);
     }
     memcpy(m->host->st, z.data(), sizeof(m->host->st));
+    m->host->gse_reset();
     return 0;
 }
 
@@ -593,15 +941,65 @@ int dvbs2gpu_bbts_process_ma_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb,
     if (frame_bytes) HIP_TRY(hipMemcpyAsync(a_foff, m->h_foff.data(), sizeof(int) * n * (mf + 1), hipMemcpyHostToDevice, st));
     const int* foff = frame_bytes ? a_foff : nullptr;
     const int cur = m->cur;
+    const bool gse = m->cfg.gse != 0;
+    int *a_ginfo = a.ginfo(m->d_args), *a_nf2 = a.nf2(m->d_args);
     hipLaunchKernelGGL(bbts_ma_frame_kernel, dim3((n * mf + 3) / 4), dim3(256), 0, st, a_in, foff, v.kbch / 8, a_nf, n, mf, m->cfg, m->d_sel,
                        m->d_lane[cur], m->d_tabs, m->d_recs);
-    hipLaunchKernelGGL(bbts_ma_lane_kernel, dim3((nl + 3) / 4), dim3(256), 0, st, a_in, a_nf, n, mf, m->cfg, m->d_sel, m->d_recs, m->d_tabs,
-                       m->d_lane[cur], m->d_lane[cur ^ 1], m->d_strm[cur], m->d_strm[cur ^ 1], m->d_carry[cur], m->d_join, m->d_desc, m->d_fins,
-                       a_need);
-    HIP_TRY(hipGetLastError());
     std::vector<int> need(nl);
-    HIP_TRY(hipMemcpyAsync(need.data(), a_need, sizeof(int) * nl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    // GSE on: the scan pass once the bank has its records, then the lane pass with the lanes' contexts.  A bank that meets its first GSE
+    // frame learns so from the lanes' flags, gets its storage and runs the two again (that one call synchronises three times).
+    auto lane_pass = [&]() -> int {
+        if (gse) {
+            if (m->d_pkt) hipLaunchKernelGGL(bbts_ma_gse_scan_kernel, dim3(mf, n), dim3(256), 0, st, a_in, a_nf, mf, m->d_recs, m->d_gfr, m->d_pkt);
+            const MaGseDev gd = {m->d_gfr, m->d_pkt, m->d_rows, m->d_glane[cur], m->d_glane[cur ^ 1], m->d_gout, a_ginfo};
+            hipLaunchKernelGGL(bbts_ma_lane_kernel<true>, dim3((nl + 3) / 4), dim3(256), 0, st, a_in, a_nf, n, mf, m->cfg, m->d_sel, m->d_recs, m->d_tabs,
+                               m->d_lane[cur], m->d_lane[cur ^ 1], m->d_strm[cur], m->d_strm[cur ^ 1], m->d_carry[cur], m->d_join, m->d_desc,
+                               m->d_fins, a_need, gd);
+        } else {
+            hipLaunchKernelGGL(bbts_ma_lane_kernel<false>, dim3((nl + 3) / 4), dim3(256), 0, st, a_in, a_nf, n, mf, m->cfg, m->d_sel, m->d_recs, m->d_tabs,
+                               m->d_lane[cur], m->d_lane[cur ^ 1], m->d_strm[cur], m->d_strm[cur ^ 1], m->d_carry[cur], m->d_join, m->d_desc,
+                               m->d_fins, a_need, MaGseDev{});
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(need.data(), a_need, sizeof(int) * nl, hipMemcpyDeviceToHost, st));
+        if (gse) HIP_TRY(hipMemcpyAsync(m->ginfo.data(), a_ginfo, sizeof(int) * nl, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return 0;
+    };
+    { const int rc = lane_pass(); if (rc) return rc; }
+    // the one host fallback: a frame with more than GSE_PKT_CAP packets.  The host parser runs that stream's call from the same state;
+    // first only for the sizes, so that the capacity rule holds for it as for every other stream
+    struct Fallback { int stream; MaHostStream hs; std::vector<uint8_t> outs[MA_LANES]; };
+    std::vector<std::unique_ptr<Fallback>> fbs;
+    bool moved = false;
+    if (gse) {
+        bool storage = false;
+        for (int i = 0; i < nl; ++i) storage |= (m->ginfo[i] & 3) == MA_GSE_STORAGE;
+        if (storage) {
+            int rc = ma_gse_storage(v, m);
+            if (rc || (rc = lane_pass())) return rc;
+        }
+        std::vector<uint8_t> h_in;
+        for (int i = 0; i < n; ++i) {
+            bool over = false;
+            for (int k = 0; k < MA_LANES; ++k) over |= (m->ginfo[i * MA_LANES + k] & 3) == MA_GSE_RECORDS;
+            if (!over) continue;
+            std::unique_ptr<Fallback> fb(new Fallback());
+            fb->stream = i;
+            const int rc = ma_stream_to_host(m, i, cur, fb->hs);
+            if (rc) return rc;
+            std::vector<int> own(nframes[i] + 1);
+            const int* off = frame_bytes ? m->h_foff.data() + (size_t)i * (mf + 1) : own.data();
+            if (!frame_bytes) for (int f = 0; f <= nframes[i]; ++f) own[f] = f * (v.kbch / 8);
+            h_in.resize(off[nframes[i]]);
+            HIP_TRY(hipMemcpy(h_in.data(), d_bb[i], h_in.size(), hipMemcpyDeviceToHost));
+            for (auto& r : fb->hs.rows) r.clear();
+            for (int f = 0; f < nframes[i]; ++f) fb->hs.frame(h_in.data() + off[f], off[f + 1] - off[f], m->cfg, m->sel[i], fb->outs);
+            for (int k = 0; k < MA_LANES; ++k) need[i * MA_LANES + k] = (int)fb->outs[k].size();
+            fbs.push_back(std::move(fb));
+        }
+        moved = m->d_pkt != nullptr;
+    }
     bool fits = true;
     for (int i = 0; i < nl; ++i) {
         if (needed) needed[i] = need[i];
@@ -609,13 +1007,40 @@ int dvbs2gpu_bbts_process_ma_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb,
     }
     if (!fits) {                                   // nothing committed: the shadow state is simply not taken
         for (int i = 0; i < nl; ++i) out_bytes[i] = 0;
+        if (gse) { std::fill(m->ginfo.begin(), m->ginfo.end(), 0); std::fill(m->rows_host.begin(), m->rows_host.end(), 0); }
         g_err = "mode adaptation: an output does not fit into cap (needed[] has the sizes)";
         return DVBS2GPU_ERR_CAPACITY;
     }
-    hipLaunchKernelGGL(bbts_ma_emit_kernel, dim3(mf + 1, n), dim3(256), 0, st, a_in, a_out, a_nf, mf, m->cfg, m->d_recs, m->d_desc, m->d_fins,
+    const int* e_nf = a_nf;
+    if (!fbs.empty()) {                            // the kernels leave the host parser's streams alone
+        std::vector<int> nf2(nframes, nframes + n);
+        for (auto& fb : fbs) nf2[fb->stream] = 0;
+        HIP_TRY(hipMemcpyAsync(a_nf2, nf2.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));         // nf2 leaves this scope
+        e_nf = a_nf2;
+    }
+    hipLaunchKernelGGL(bbts_ma_emit_kernel, dim3(mf + 1, n), dim3(256), 0, st, a_in, a_out, e_nf, mf, m->cfg, m->d_recs, m->d_desc, m->d_fins,
                        m->d_carry[cur ^ 1]);
+    if (moved) {
+        hipLaunchKernelGGL(bbts_ma_gse_move_kernel, dim3(mf, n), dim3(256), 0, st, a_in, a_out, e_nf, mf, m->d_recs, m->d_gfr, m->d_pkt, m->d_rows,
+                           m->d_gout, m->d_slotmap, m->d_slots);
+        hipLaunchKernelGGL(bbts_ma_gse_append_kernel, dim3(3, (unsigned)m->slot_cap), dim3(256), 0, st, a_in, e_nf, mf, m->d_pkt, m->d_gout, m->d_slotmap,
+                           m->d_slotmap + nl, m->d_slots);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
+    if (gse) std::fill(m->rows_host.begin(), m->rows_host.end(), 0);
+    for (auto& fb : fbs) {                         // their output and their state, into the half the call makes current
+        const int i = fb->stream;
+        ++m->fb_calls[i];
+        for (int k = 0; k < MA_LANES; ++k) {
+            if (!fb->outs[k].empty()) HIP_TRY(hipMemcpy(d_out[i * MA_LANES + k], fb->outs[k].data(), fb->outs[k].size(), hipMemcpyHostToDevice));
+            m->fb_rows[i * MA_LANES + k] = fb->hs.rows[k];
+            m->rows_host[i * MA_LANES + k] = 1;
+        }
+        const int rc = ma_stream_to_device(m, i, cur ^ 1, fb->hs);
+        if (rc) return rc;
+    }
     m->cur = cur ^ 1;
     for (int i = 0; i < nl; ++i) out_bytes[i] = need[i];
     return 0;
@@ -634,6 +1059,7 @@ int dvbs2gpu_bbts_ma_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, const int* fram
     for (int k = 0; k < sel.n; ++k) if (cnt > 0 && !h_out[k]) return DVBS2GPU_ERR_ARG;
     if (!v.ctx) {
         MaHostStream trial = *m->host;             // the state advances only when every output fits
+        for (auto& r : trial.rows) r.clear();
         std::vector<uint8_t> outs[MA_LANES];
         for (int f = 0; f < cnt; ++f) trial.frame(h_bb + off[f], off[f + 1] - off[f], m->cfg, sel, outs);
         bool fits = true;
@@ -642,7 +1068,11 @@ int dvbs2gpu_bbts_ma_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, const int* fram
             fits = fits && (long)outs[k].size() <= cap;
             out_bytes[k] = 0;
         }
-        if (!fits) { g_err = "mode adaptation: an output does not fit into cap (needed[] has the sizes)"; return DVBS2GPU_ERR_CAPACITY; }
+        if (!fits) {                               // nothing advanced; the failed call has no rows
+            for (auto& r : m->host->rows) r.clear();
+            g_err = "mode adaptation: an output does not fit into cap (needed[] has the sizes)";
+            return DVBS2GPU_ERR_CAPACITY;
+        }
         *m->host = trial;
         for (int k = 0; k < MA_LANES; ++k) {
             out_bytes[k] = (int)outs[k].size();
@@ -729,6 +1159,114 @@ int dvbs2gpu_bbts_ma_get_stats(dvbs2gpu_bbts* b, int stream, int slot, dvbs2gpu_
     o.issy_bytes = l.issy; o.iscr_valid = l.iscr_valid; o.last_iscr = l.iscr; o.carried = l.c;
     o.selected = slot < sel.n; o.isi = o.selected ? sel.isi[slot] : -1;
     *h_out = o;
+    return 0;
+}
+
+int dvbs2gpu_bbts_ma_set_gse(dvbs2gpu_bbts* b, int on) {
+    if (!b) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    BbtsMa* m = *v.ma;
+    if (!m) { g_err = "ma_set_gse: the mode-adaptation mode is off"; return DVBS2GPU_ERR_ARG; }
+    if (!v.ctx) {
+        if (!on) m->host->gse_reset();
+        m->cfg.gse = on != 0;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(v.ctx->device));
+    const size_t nl = (size_t)v.nstreams * MA_LANES;
+    if (on && !m->d_glane[0]) {
+        for (int k = 0; k < 2; ++k) {
+            HIP_TRY(hipMalloc((void**)&m->d_glane[k], nl * sizeof(MaGseLane)));
+            HIP_TRY(hipMemset(m->d_glane[k], 0, nl * sizeof(MaGseLane)));
+        }
+        HIP_TRY(hipMalloc((void**)&m->d_gout, nl * sizeof(MaGseOut)));
+        HIP_TRY(hipMalloc((void**)&m->d_slotmap, 2 * nl * sizeof(int)));
+        m->slotmap.assign(nl, -1); m->ginfo.assign(nl, 0); m->rows_host.assign(nl, 0);
+        m->fb_rows.resize(nl); m->fb_calls.assign(v.nstreams, 0);
+    }
+    if (!on && m->d_glane[0]) {                        // the lanes' GSE state is dropped; the storage stays with the bank
+        HIP_TRY(hipMemset(m->d_glane[m->cur], 0, nl * sizeof(MaGseLane)));
+        std::fill(m->ginfo.begin(), m->ginfo.end(), 0);
+        std::fill(m->rows_host.begin(), m->rows_host.end(), 0);
+        std::fill(m->fb_calls.begin(), m->fb_calls.end(), 0);
+    }
+    m->cfg.gse = on != 0;
+    return 0;
+}
+
+int dvbs2gpu_bbts_ma_get_gse_stats(dvbs2gpu_bbts* b, int stream, int slot, dvbs2gpu_bbts_ma_gse_stats* h_out) {
+    if (!b || !h_out || slot < 0 || slot >= MA_LANES) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    BbtsMa* m = *v.ma;
+    if (!m || stream < 0 || stream >= v.nstreams) return DVBS2GPU_ERR_ARG;
+    MaGseLane gl = {};
+    if (!v.ctx) {
+        gl = m->host->gse[slot];
+    } else if (m->d_glane[0]) {
+        HIP_TRY(hipSetDevice(v.ctx->device));
+        HIP_TRY(hipMemcpy(&gl, m->d_glane[m->cur] + (size_t)stream * MA_LANES + slot, sizeof(gl), hipMemcpyDeviceToHost));
+    }
+    static_assert(sizeof(GseCounters) == 9 * sizeof(int64_t) && sizeof(dvbs2gpu_bbts_ma_gse_stats) == 12 * sizeof(int64_t), "layout");
+    dvbs2gpu_bbts_ma_gse_stats o = {};
+    memcpy(&o.frames, &gl.g.cnt, sizeof(GseCounters));
+    o.malformed_frames = gl.malformed;
+    o.host_fallback_calls = v.ctx && !m->fb_calls.empty() ? m->fb_calls[stream] : 0;
+    o.open_slots = gl.g.slot[0].busy + gl.g.slot[1].busy + gl.g.slot[2].busy;
+    o.last_crc_err = gl.g.crc_err;
+    *h_out = o;
+    return 0;
+}
+
+// the rows of lane (stream, slot) of the last call: where they are and how many
+static int ma_rows(const BbtsBankView& v, BbtsMa* m, int stream, int slot, const dvbs2gpu_gse_pdu** host, const dvbs2gpu_gse_pdu** dev, int* n) {
+    *host = nullptr; *dev = nullptr; *n = 0;
+    const int w = stream * MA_LANES + slot;
+    if (!v.ctx) { *host = m->host->rows[slot].data(); *n = (int)m->host->rows[slot].size(); return 0; }
+    if (!m->d_glane[0]) return 0;
+    if (m->rows_host[w]) { *host = m->fb_rows[w].data(); *n = (int)m->fb_rows[w].size(); return 0; }
+    *n = m->ginfo[w] >> 2;
+    if (*n == 0) return 0;
+    MaGseOut o;
+    HIP_TRY(hipMemcpy(&o, m->d_gout + w, sizeof(o), hipMemcpyDeviceToHost));
+    *dev = m->d_rows + (size_t)stream * v.max_frames * GSE_PKT_CAP + o.rowbase;
+    return 0;
+}
+
+int dvbs2gpu_bbts_ma_get_pdu_table(dvbs2gpu_bbts* b, int stream, int slot, dvbs2gpu_gse_pdu* h_rows, int cap, int* n) {
+    if (!b || !n || cap < 0 || (cap > 0 && !h_rows) || slot < 0 || slot >= MA_LANES) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    BbtsMa* m = *v.ma;
+    if (!m || stream < 0 || stream >= v.nstreams) return DVBS2GPU_ERR_ARG;
+    if (v.ctx) HIP_TRY(hipSetDevice(v.ctx->device));
+    const dvbs2gpu_gse_pdu *host, *dev;
+    const int rc = ma_rows(v, m, stream, slot, &host, &dev, n);
+    if (rc) return rc;
+    const int k = *n < cap ? *n : cap;
+    if (k <= 0) return 0;
+    if (host) memcpy(h_rows, host, k * sizeof(dvbs2gpu_gse_pdu));
+    else HIP_TRY(hipMemcpy(h_rows, dev, k * sizeof(dvbs2gpu_gse_pdu), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int dvbs2gpu_bbts_ma_get_pdu_table_device(dvbs2gpu_bbts* b, int stream, int slot, const dvbs2gpu_gse_pdu** d_rows, int* n) {
+    if (!b || !n || !d_rows || slot < 0 || slot >= MA_LANES) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    BbtsMa* m = *v.ma;
+    if (!m || stream < 0 || stream >= v.nstreams) return DVBS2GPU_ERR_ARG;
+    if (!v.ctx) { g_err = "ma_get_pdu_table_device: a host bank has no device table"; return DVBS2GPU_ERR_ARG; }
+    HIP_TRY(hipSetDevice(v.ctx->device));
+    const dvbs2gpu_gse_pdu *host, *dev;
+    const int rc = ma_rows(v, m, stream, slot, &host, &dev, n);
+    if (rc) return rc;
+    *d_rows = dev;
+    if (!host || *n == 0) return 0;
+    // a call the host parser ran: its rows go to where the kernels put theirs, lane after lane, if the stream's table holds them
+    size_t at = 0;
+    for (int k = 0; k < slot; ++k) at += m->fb_rows[stream * MA_LANES + k].size();
+    if (at + *n > (size_t)v.max_frames * GSE_PKT_CAP) { g_err = "more rows than the device table holds"; return DVBS2GPU_ERR_CAPACITY; }
+    dvbs2gpu_gse_pdu* d = m->d_rows + (size_t)stream * v.max_frames * GSE_PKT_CAP + at;
+    HIP_TRY(hipMemcpy(d, host, *n * sizeof(dvbs2gpu_gse_pdu), hipMemcpyHostToDevice));
+    *d_rows = d;
     return 0;
 }
 
