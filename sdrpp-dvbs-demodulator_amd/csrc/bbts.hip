@@ -9,9 +9,11 @@
 //   bbts_emit_kernel   one workgroup per (frame, stream) moves the bytes: 0x47 + 187 bytes per packet, the first packet of
 //                      a frame completed from the tail of the previous one (HBM-bound byte movement, 2 x DFL/8 per frame).
 // GSE frames (TS/GS = 01) stay on the device too (bbts_gse.hip): a stream that carries one in a call is parsed, for that call, by
-// the four GSE kernels, which also emit the TS frames of a mixed call.  The native host parser below (BbtsHostParser) is the second
-// implementation of the same rules: it runs a stream's call when dvbs2gpu_bbts_set_gse_path chose it, when a frame has more packets
-// than GSE_PKT_CAP records, or when one of its output-capacity rules would fire; it shares all state with the device path.
+// the four GSE kernels, which also emit the TS frames of a mixed call.  The native host parser (BbtsHostParser, bbts_host.h) is the
+// second implementation of the same rules: it runs a stream's call when dvbs2gpu_bbts_set_gse_path chose it, when a frame has more
+// packets than GSE_PKT_CAP records, or when one of its output-capacity rules would fire; it shares all state with the device path
+// (gse_ctx_to_host / gse_ctx_to_device, bbts_common.h).  The two read a GSE packet header through the same gse_parse_packet
+// (bbts_rules.h); the reassembly rule is stated once for the device (gse_apply_packet) and once for the host (GseHostCtx::apply).
 #include "ctx.h"
 #include "bbts_common.h"
 
@@ -95,176 +97,6 @@ __global__ void __launch_bounds__(256) bbts_emit_kernel(const uint8_t* const* __
     bbts_emit_frame(bb, old, e, out[s] + e.out_off);
 }
 
-// ---------------------------------------------------------------------------------------------- host parser (GSE streams)
-// Full BBFrameTSParser::work semantics for one stream.  Where the reference's behaviour is undefined (reads past the
-// input buffer, writes past the output or the 64 KiB reassembly buffers, negative copy lengths) the rules stated in
-// include/dvbs2gpu.h apply.
-class BbtsHostParser {
-public:
-    int synched = 0, count = 0;
-    uint8_t partial[TS] = {0};
-    int hdr[11] = {0};
-    int last_gse_crc_err = 0, last_cnt = 0, last_proc = 0;
-    GseCounters gc = {};                        // what dvbs2gpu_bbts_get_gse_stats reports, counted like gse_stream_kernel does
-    std::vector<dvbs2gpu_gse_pdu> rows;         // one per GRE packet written by the last run()
-    struct Reassembly {
-        bool busy = false;
-        int frag_id = 0;
-        long fill = 0;
-        unsigned proto = 0;
-        uint32_t crc = 0;
-        bool label = false;
-        std::unique_ptr<uint8_t[]> data;      // 65536 bytes, allocated on first use
-    };
-    Reassembly slots_[3];
-
-    BbtsHostParser() {
-        for (unsigned i = 0; i < 256; ++i) {
-            uint32_t r = i << 24;
-            for (int b = 0; b < 8; ++b) r = (r << 1) ^ ((r >> 31) ? 0x04c11db7u : 0u);
-            tab_[i] = r;
-        }
-    }
-
-    // returns bytes produced or DVBS2GPU_ERR_CAPACITY
-    int run(const uint8_t* bb, int cnt, int fbytes, int max_dfl, uint8_t* out, int cap) {
-        in_ = bb; in_end_ = (long)fbytes * cnt; out_ = out; cap_ = cap; w_ = 0;
-        rows.clear();
-        int proc = 0;
-        bool stop = false;
-        for (int f = 0; f < cnt && !stop; ++f) {
-            const long base = (long)fbytes * f;
-            HeaderFields h;
-            if (!header_ok(bb + base, max_dfl, &h)) { synched = 0; continue; }
-            long pos = base + 10;
-            int df = h.v[8] / 8;
-            if (!synched) {
-                const int skip = h.v[10] / 8 + 1;
-                pos += skip; df -= skip; count = 0; synched = 1;
-            }
-            memcpy(hdr, h.v, sizeof(hdr));
-            ++proc;
-            switch (h.v[0]) {
-            case 3: {
-                const int rc = ts_frame(pos, df);
-                if (rc < 0) { synched = 0; return DVBS2GPU_ERR_CAPACITY; }
-                stop = rc > 0;
-                break;
-            }
-            case 1:
-                if (!h.v[3] && !h.v[4] && h.v[7] == 0) { ++gc.frames; gse_frame(pos, h.v[8] / 8); }
-                break;
-            default: break;
-            }
-        }
-        last_cnt = cnt; last_proc = proc;
-        return w_;
-    }
-
-private:
-    uint32_t tab_[256];
-    const uint8_t* in_ = nullptr;
-    long in_end_ = 0;
-    uint8_t* out_ = nullptr;
-    int cap_ = 0, w_ = 0;
-
-    uint32_t crc32(uint32_t c, long off, long n) const {
-        for (long i = 0; i < n; ++i) c = (c << 8) ^ tab_[(c >> 24) ^ in_[off + i]];
-        return c;
-    }
-    // 1: the output is nearly full, stop after this frame (.cpp:206-209); -1: undefined in the reference; 0 otherwise
-    int ts_frame(long pos, int df) {
-        while (df >= TS && cap_ - w_ > TS) {
-            uint8_t* o = out_ + w_;
-            o[0] = 0x47;
-            if (count > 0) {
-                const int need = TS - count;
-                memcpy(partial + count, in_ + pos, need);
-                memcpy(o + 1, partial, TS - 1);
-                pos += need; df -= need; count = 0;
-            } else {
-                memcpy(o + 1, in_ + pos, TS - 1);
-                pos += TS; df -= TS;
-            }
-            w_ += TS;
-        }
-        if (df >= TS) return -1;
-        if (df > 0) { memcpy(partial, in_ + pos, df); count = df; }
-        return cap_ - w_ <= TS ? 1 : 0;
-    }
-    void emit_gre(unsigned proto, const uint8_t* p, long n, bool reassembled, bool label) {
-        const bool known = proto == 0x0800 || proto == 0x86DD;
-        const long total = 2 + (known ? 2 : 0) + n;
-        if (n < 0 || w_ + total > cap_) { ++gc.dropped_no_fit; return; }
-        ++(reassembled ? gc.reassembled_pdus : gc.complete_pdus);
-        gc.bytes_delivered += total;
-        rows.push_back({(uint32_t)w_, (uint32_t)total, (uint16_t)proto, (uint16_t)((reassembled ? 1 : 0) | (label ? 2 : 0)), 0});
-        uint8_t* o = out_ + w_;
-        *o++ = 0; *o++ = 0;                    // GRE: no checksum, no key, no sequence number, version 0
-        if (known) { *o++ = (uint8_t)(proto >> 8); *o++ = (uint8_t)proto; }
-        memcpy(o, p, n);
-        w_ += (int)total;
-    }
-    void gse_frame(long start, int dfl_bytes) {
-        long at = start;
-        const long end = start + dfl_bytes;
-        while (at < end) {
-            if (at + 2 > in_end_) return;
-            const unsigned h1 = in_[at];
-            const bool first = h1 & 0x80, last = h1 & 0x40;
-            const bool label6 = (h1 & 0x30) == 0;          // the reference tests ((h1 & 0x30) >> 2) against 0 and 2: only 0 can match
-            if (!first && !last && label6) return;          // padding
-            const unsigned field = (h1 & 0x0f) << 8 | in_[at + 1];
-            // bytes between the 2-byte GSE header and the payload; the length arithmetic is uint16 in the reference
-            const int fixed = first && last ? 2 : first ? 5 : 1;
-            const int label = first && label6 ? 6 : 0;
-            const long plen = (field - fixed - label) & 0xffff;
-            const long body = at + 2 + fixed + label;
-            if (body + plen > in_end_) return;
-            ++gc.packets;
-            if (first && last) {
-                emit_gre(in_[at + 2] << 8 | in_[at + 3], in_ + body, plen, false, label != 0);
-            } else {
-                const int id = in_[at + 2];
-                Reassembly* r = nullptr;
-                for (auto& s : slots_) {
-                    if (first ? (!s.busy || s.frag_id == id) : (s.busy && s.frag_id == id)) { r = &s; break; }
-                }
-                if (!r && first) ++gc.dropped_no_slot;
-                if (r && first) {
-                    if (!r->data) r->data.reset(new uint8_t[65536]);
-                    r->busy = true; r->frag_id = id; r->label = label != 0;
-                    r->proto = in_[at + 5] << 8 | in_[at + 6];
-                    memcpy(r->data.get(), in_ + body, plen);
-                    r->fill = plen;
-                    // CRC-32 over total length, protocol type, label, payload
-                    r->crc = crc32(crc32(crc32(0xffffffffu, at + 3, 4), at + 7, label), body, plen);
-                } else if (r) {
-                    if (r->fill + plen > 65536) {
-                        r->busy = false;
-                        ++gc.dropped_overflow;
-                    } else if (!last) {
-                        memcpy(r->data.get() + r->fill, in_ + body, plen);
-                        r->fill += plen;
-                        r->crc = crc32(r->crc, body, plen);
-                    } else {
-                        memcpy(r->data.get() + r->fill, in_ + body, plen);
-                        r->busy = false;
-                        r->fill += plen - 4;
-                        r->crc = crc32(r->crc, body, plen - 4);
-                        const uint32_t rx = (uint32_t)in_[body + plen - 4] << 24 | (uint32_t)in_[body + plen - 3] << 16 |
-                                            (uint32_t)in_[body + plen - 2] << 8 | in_[body + plen - 1];
-                        last_gse_crc_err = r->crc != rx;
-                        if (last_gse_crc_err) ++gc.crc_failures;
-                        else emit_gre(r->proto, r->data.get(), r->fill, true, r->label);
-                    }
-                }
-            }
-            at = body + plen;
-        }
-    }
-};
-
 }  // namespace s2
 
 struct dvbs2gpu_bbts {
@@ -308,32 +140,22 @@ int bbts_reset_reference_state(dvbs2gpu_bbts* b) {
     return bbts_gse_reset(b->gse);
 }
 
-// The GSE state of one stream lives in HBM once the bank has its device storage; a call that the host parser runs takes it
-// from there and returns it: slot bookkeeping, the bytes of the open reassemblies, the last CRC verdict.
+// The GSE context of one stream lives in HBM once the bank has its device storage; a call that the host parser runs takes it
+// from there and returns it: slots, counters, the last CRC verdict, the bytes of the open reassemblies.
 static int gse_state_to_host(dvbs2gpu_bbts* b, int i, BbtsHostParser& hp) {
-    GseDevState gs;
-    HIP_TRY(hipMemcpy(&gs, bbts_gse_state(b->gse) + i, sizeof(gs), hipMemcpyDeviceToHost));
-    hp.last_gse_crc_err = gs.crc_err;
-    for (int q = 0; q < 3; ++q) {
-        auto& r = hp.slots_[q];
-        r.busy = gs.slot[q].busy != 0; r.frag_id = gs.slot[q].frag_id; r.fill = gs.slot[q].fill; r.proto = gs.slot[q].proto;
-        r.crc = gs.slot[q].crc; r.label = gs.slot[q].label != 0;
-        if (!r.busy) continue;
-        if (!r.data) r.data.reset(new uint8_t[65536]);
-        if (r.fill > 0) HIP_TRY(hipMemcpy(r.data.get(), bbts_gse_slot_data(b->gse, i, q), r.fill, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return gse_ctx_to_host(hp.gse, bbts_gse_state(b->gse) + i, bbts_gse_slot_data(b->gse, i, 0));
 }
 static int gse_state_to_device(dvbs2gpu_bbts* b, int i, const BbtsHostParser& hp) {
-    GseDevState gs;
-    HIP_TRY(hipMemcpy(&gs, bbts_gse_state(b->gse) + i, sizeof(gs), hipMemcpyDeviceToHost));
-    gs.crc_err = hp.last_gse_crc_err;
-    for (int q = 0; q < 3; ++q) {
-        const auto& r = hp.slots_[q];
-        gs.slot[q] = {r.busy ? 1 : 0, r.frag_id, (int)r.fill, r.label ? 1 : 0, r.proto, r.crc};
-        if (r.busy && r.fill > 0) HIP_TRY(hipMemcpy(bbts_gse_slot_data(b->gse, i, q), r.data.get(), r.fill, hipMemcpyHostToDevice));
+    return gse_ctx_to_device(hp.gse, bbts_gse_state(b->gse) + i, bbts_gse_slot_data(b->gse, i, 0));
+}
+// The context as it stands: in HBM once the bank has its device storage, until then with the stream's host parser if it has one.  The
+// counters travel with it, so each call of a stream is counted once, by the parser that ran it.
+static int bbts_gse_context(dvbs2gpu_bbts* b, int stream, GseDevState* gs) {
+    if (!b->gse) {
+        if (b->host[stream]) *gs = b->host[stream]->gse.g;
+        return 0;
     }
-    HIP_TRY(hipMemcpy(bbts_gse_state(b->gse) + i, &gs, sizeof(gs), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(gs, bbts_gse_state(b->gse) + stream, sizeof(*gs), hipMemcpyDeviceToHost));
     return 0;
 }
 // 3 x 64 KiB of reassembly storage per stream and the record / row tables: only for a bank that meets a GSE frame
@@ -381,12 +203,11 @@ int dvbs2gpu_bbts_create(dvbs2gpu_ctx* ctx, int nstreams, int kbch_bits, int max
     b->fb_records.assign(nstreams, 0); b->fb_capacity.assign(nstreams, 0);
     const size_t n = (size_t)nstreams;
     hipError_t e = hipSuccess;
-    auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) { e = hipMalloc(p, bytes); if (e == hipSuccess) e = hipMemset(*p, 0, bytes); } };
-    A((void**)&b->d_state, n * sizeof(BbtsDevState));
-    A((void**)&b->d_reasm[0], n * REASM_STRIDE); A((void**)&b->d_reasm[1], n * REASM_STRIDE);
-    A((void**)&b->d_desc, n * max_frames * sizeof(BbtsFrameDesc));
-    A((void**)&b->d_plan, n * sizeof(BbtsStreamPlan));
-    A(&b->d_args, BankArgs(n).L.bytes());
+    bbts_alloc(e, &b->d_state, n * sizeof(BbtsDevState));
+    bbts_alloc(e, &b->d_reasm[0], n * REASM_STRIDE); bbts_alloc(e, &b->d_reasm[1], n * REASM_STRIDE);
+    bbts_alloc(e, &b->d_desc, n * max_frames * sizeof(BbtsFrameDesc));
+    bbts_alloc(e, &b->d_plan, n * sizeof(BbtsStreamPlan));
+    bbts_alloc(e, &b->d_args, BankArgs(n).L.bytes());
     if (e != hipSuccess) { dvbs2gpu_bbts_destroy(b); return fail_hip(e, "hipMalloc(bbts)"); }
     *out = b;
     return 0;
@@ -469,7 +290,7 @@ int dvbs2gpu_bbts_process_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb, co
         HIP_TRY(hipMemcpy(b->d_reasm[b->cur] + (size_t)i * REASM_STRIDE, hp.partial, TS, hipMemcpyHostToDevice));
         if (b->gse) { const int e = gse_state_to_device(b, i, hp); if (e) return e; }
         b->rows_host[i] = 1;
-        b->nrows[i] = (int)hp.rows.size();
+        b->nrows[i] = (int)hp.gse.rows.size();
         if (got < 0) { out_bytes[i] = 0; rc = got; g_err = "output buffer too small for the TS packets of a GSE-carrying call"; continue; }
         out_bytes[i] = got;
         if (got > 0) HIP_TRY(hipMemcpy(d_out[i], b->h_out.data(), got, hipMemcpyHostToDevice));
@@ -510,12 +331,10 @@ int dvbs2gpu_bbts_get_stats(dvbs2gpu_bbts* b, int stream, int32_t* h_out, int n_
     BbtsDevState ds;
     HIP_TRY(hipMemcpy(&ds, b->d_state + stream, sizeof(ds), hipMemcpyDeviceToHost));
     for (int i = 0; i < 11; ++i) h_out[i] = ds.hdr[i];
-    h_out[11] = b->host[stream] ? b->host[stream]->last_gse_crc_err : 0;
-    if (b->gse) {
-        GseDevState gs;
-        HIP_TRY(hipMemcpy(&gs, bbts_gse_state(b->gse) + stream, sizeof(gs), hipMemcpyDeviceToHost));
-        h_out[11] = gs.crc_err;
-    }
+    GseDevState gs = {};
+    const int e = bbts_gse_context(b, stream, &gs);
+    if (e) return e;
+    h_out[11] = gs.crc_err;
     h_out[12] = ds.last_cnt; h_out[13] = ds.last_proc; h_out[14] = 0;
     if (n_out >= 17) { h_out[15] = ds.synched; h_out[16] = ds.count; }
     return 0;
@@ -532,13 +351,9 @@ int dvbs2gpu_bbts_get_gse_stats(dvbs2gpu_bbts* b, int stream, dvbs2gpu_gse_stats
     HIP_TRY(hipSetDevice(b->ctx->device));
     static_assert(sizeof(GseCounters) == 9 * sizeof(int64_t) && sizeof(dvbs2gpu_gse_stats) == 12 * sizeof(int64_t), "layout");
     GseDevState gs = {};
-    if (b->gse) HIP_TRY(hipMemcpy(&gs, bbts_gse_state(b->gse) + stream, sizeof(gs), hipMemcpyDeviceToHost));
-    const GseCounters zero = {};
-    const GseCounters& h = b->host[stream] ? b->host[stream]->gc : zero;
-    const long long* x = &gs.cnt.frames;
-    const long long* y = &h.frames;
-    int64_t* o = &out->frames;
-    for (int k = 0; k < 9; ++k) o[k] = x[k] + y[k];      // each call of a stream is counted by the one parser that ran it
+    const int e = bbts_gse_context(b, stream, &gs);
+    if (e) return e;
+    memcpy(&out->frames, &gs.cnt, sizeof(GseCounters));
     out->fallback_records = b->fb_records[stream]; out->fallback_capacity = b->fb_capacity[stream];
     out->host_fallback_calls = out->fallback_records + out->fallback_capacity;
     return 0;
@@ -550,7 +365,7 @@ int dvbs2gpu_bbts_get_pdu_table(dvbs2gpu_bbts* b, int stream, dvbs2gpu_gse_pdu* 
     *n = b->nrows[stream];
     const int m = *n < cap ? *n : cap;
     if (m <= 0) return 0;
-    if (b->rows_host[stream]) memcpy(h_rows, b->host[stream]->rows.data(), m * sizeof(dvbs2gpu_gse_pdu));
+    if (b->rows_host[stream]) memcpy(h_rows, b->host[stream]->gse.rows.data(), m * sizeof(dvbs2gpu_gse_pdu));
     else HIP_TRY(hipMemcpy(h_rows, bbts_gse_rows(b->gse, stream), m * sizeof(dvbs2gpu_gse_pdu), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -565,7 +380,7 @@ int dvbs2gpu_bbts_get_pdu_table_device(dvbs2gpu_bbts* b, int stream, const dvbs2
         const int e = gse_storage(b);
         if (e) return e;
         if (*n > b->max_frames * GSE_PKT_CAP) { g_err = "more rows than the device table holds"; return DVBS2GPU_ERR_CAPACITY; }
-        HIP_TRY(hipMemcpy(bbts_gse_rows(b->gse, stream), b->host[stream]->rows.data(), *n * sizeof(dvbs2gpu_gse_pdu), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(bbts_gse_rows(b->gse, stream), b->host[stream]->gse.rows.data(), *n * sizeof(dvbs2gpu_gse_pdu), hipMemcpyHostToDevice));
     }
     *d_rows = (const dvbs2gpu_gse_pdu*)bbts_gse_rows(b->gse, stream);
     return 0;

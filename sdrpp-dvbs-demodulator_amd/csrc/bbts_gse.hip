@@ -1,8 +1,10 @@
-// GSE decapsulation on the device for the BBFRAME -> TS / GSE parser bank: the rules of BbtsHostParser::gse_frame /
-// emit_gre / ts_frame (bbts.hip; dsp::dvbs2::BBFrameTSParser::work, dvbs2/bbframe_ts_parser.cpp:104-390) split into
+// GSE decapsulation on the device for the BBFRAME -> TS / GSE parser bank: the rules of BbtsHostParser (bbts_host.h;
+// dsp::dvbs2::BBFrameTSParser::work, dvbs2/bbframe_ts_parser.cpp:104-390) split into four kernels.  The packet header is read by
+// gse_parse_packet<GseReference> (bbts_rules.h), the chain walked by gse_walk_frame and the reassembly rule stated by gse_apply_packet
+// (bbts_gse_dev.h); this file has the frame selection, synchronisation, TS descriptors and capacity rules of the reference mode.
 //   gse_scan_kernel     one workgroup per (frame, stream): header check, the frame staged in LDS, one lane follows the packet chain
-//                       (next = at + 2 + field is the only serial dependency) and writes one 16-byte record per packet; the waves then
-//                       compute, per fragment, the CRC-32 of its span from a zero register and x^(8 len) mod P, 64-byte chunks per lane;
+//                       and writes one 16-byte record per packet; the waves then compute, per fragment, the CRC-32 of its span
+//                       from a zero register and x^(8 len) mod P, 64-byte chunks per lane;
 //   gse_stream_kernel   one lane per stream, over the frame and packet records only: synchronisation, TS descriptors, slot choice and
 //                       fill, the running CRC as crc' = crc * xpow ^ crc0, the END verdict, every output offset, the PDU table rows,
 //                       the capacity rules.  State is kept in registers and stored only when the call needs no fallback;
@@ -43,68 +45,21 @@ __global__ void __launch_bounds__(256) gse_scan_kernel(const uint8_t* const* __r
     __shared__ GseFrameRec fr;
     const uint8_t* bb = in[s];
     const int base = f * fbytes, in_end = nframes[s] * fbytes;
-    if ((reinterpret_cast<uintptr_t>(bb + base) & 3) == 0) {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(bb + base);
-        for (int i = tid; i < fbytes / 4; i += 256) reinterpret_cast<uint32_t*>(stage)[i] = src[i];
-        for (int i = (fbytes & ~3) + tid; i < fbytes; i += 256) stage[i] = bb[base + i];
-    } else {
-        for (int i = tid; i < fbytes; i += 256) stage[i] = bb[base + i];
-    }
-    __syncthreads();
-    auto rd = [&](int i) -> unsigned { return (i >= base && i < base + fbytes) ? stage[i - base] : bb[i]; };   // i < in_end
-    if (tid == 0) {
-        GseFrameRec r = {0, 0, 0, 0};
-        HeaderFields h;
-        if (header_ok(stage, max_dfl, &h)) {
-            HeaderFields hp;
-            const bool synched = f == 0 ? state[s].synched != 0 : header_ok(bb + base - fbytes, max_dfl, &hp);
-            int pos = base + 10;
-            if (!synched) { pos += h.v[10] / 8 + 1; r.resync = 1; }
-            r.pos = pos;
-            r.kind = h.v[0] == 3 ? 3 : 1;
-            if (h.v[0] == 1 && !h.v[3] && !h.v[4] && h.v[7] == 0) {
-                r.kind = 2;
-                int at = pos, n = 0;
-                const int end = pos + h.v[8] / 8;
-                while (at < end) {
-                    if (at + 2 > in_end) break;
-                    const unsigned h1 = rd(at);
-                    const bool first = h1 & 0x80, last = h1 & 0x40, label6 = (h1 & 0x30) == 0;
-                    if (!first && !last && label6) break;
-                    const unsigned field = (h1 & 0x0f) << 8 | rd(at + 1);
-                    const int fixed = first && last ? 2 : first ? 5 : 1;
-                    const int label = first && label6 ? 6 : 0;
-                    const int plen = (int)((field - fixed - label) & 0xffff);
-                    const int body = at + 2 + fixed + label;
-                    if (body + plen > in_end) break;
-                    if (n == GSE_PKT_CAP) { r.kind = 4; break; }
-                    GsePkt p = {(uint32_t)body, (uint32_t)plen, 0, 0};
-                    int kind, sa = body, sl = 0;
-                    if (first && last) {
-                        kind = GSE_COMPLETE;
-                        p.b = rd(at + 2) << 8 | rd(at + 3);
-                    } else {
-                        p.w1 |= rd(at + 2) << 16;
-                        if (first) { kind = GSE_START; p.b = rd(at + 5) << 8 | rd(at + 6); sa = at + 3; sl = body + plen - sa; }
-                        else if (!last) { kind = GSE_MIDDLE; sl = plen; }
-                        else { kind = GSE_END; sl = plen >= 4 ? plen - 4 : 0; }
-                    }
-                    p.w1 |= (uint32_t)kind << 24 | (uint32_t)(label ? 1 : 0) << 26;
-                    rec[n] = p; span_at[n] = sa; span_len[n] = sl;
-                    at = body + plen;
-                    ++n;
-                }
-                r.npkt = n;
-            }
-        }
-        fr = r;
-    }
-    __syncthreads();
-    const int n = fr.npkt;
-    gse_span_crcs(rec, span_at, span_len, n, rd, tid);
-    __syncthreads();
-    GsePkt* o = pkts + ((size_t)s * max_frames + f) * GSE_PKT_CAP;
-    for (int k = tid; k < n; k += 256) o[k] = rec[k];
+    auto prologue = [&]() -> GseWalkRange {       // header check and resynchronisation; a GSE frame is walked from fr.pos for DFL/8 bytes
+        fr = {0, 0, 0, 0};
+        HeaderFields h, hp;
+        if (!header_ok(stage, max_dfl, &h)) return {0, 0, 0};
+        const bool synched = f == 0 ? state[s].synched != 0 : header_ok(bb + base - fbytes, max_dfl, &hp);
+        const int pos = base + 10 + (synched ? 0 : h.v[10] / 8 + 1);
+        fr.resync = !synched; fr.pos = pos;
+        fr.kind = h.v[0] == 3 ? 3 : 1;
+        if (h.v[0] != 1 || h.v[3] || h.v[4] || h.v[7] != 0) return {0, 0, 0};
+        fr.kind = 2;
+        return {pos, pos + h.v[8] / 8, in_end};
+    };
+    gse_walk_frame<GseReference>(bb, base, fbytes, stage, rec, span_at, span_len, prologue,
+                                 [&](int n, int why) { fr.npkt = n; if (why == GSE_OVER) fr.kind = 4; }, &fr.npkt,
+                                 pkts + ((size_t)s * max_frames + f) * GSE_PKT_CAP, tid);
     if (tid == 0) frec[(size_t)s * max_frames + f] = fr;
 }
 
@@ -237,13 +192,12 @@ int bbts_gse_create(int nstreams, int max_frames, BbtsGse** out) {
     g->nstreams = nstreams; g->max_frames = max_frames;
     const size_t n = (size_t)nstreams, np = n * max_frames * GSE_PKT_CAP;
     hipError_t e = hipSuccess;
-    auto A = [&](void** p, size_t bytes, bool zero) { if (e == hipSuccess) { e = hipMalloc(p, bytes); if (e == hipSuccess && zero) e = hipMemset(*p, 0, bytes); } };
-    A((void**)&g->d_state, n * sizeof(GseDevState), true);
-    A((void**)&g->d_frec, n * max_frames * sizeof(GseFrameRec), true);
-    A((void**)&g->d_pkt, np * sizeof(GsePkt), false);
-    A((void**)&g->d_rows, np * sizeof(dvbs2gpu_gse_pdu), false);
-    A((void**)&g->d_sout, n * sizeof(GseStreamOut), true);
-    A((void**)&g->d_slots, n * 3 * GSE_SLOT_BYTES, false);
+    bbts_alloc(e, &g->d_state, n * sizeof(GseDevState));
+    bbts_alloc(e, &g->d_frec, n * max_frames * sizeof(GseFrameRec));
+    bbts_alloc(e, &g->d_pkt, np * sizeof(GsePkt), false);
+    bbts_alloc(e, &g->d_rows, np * sizeof(dvbs2gpu_gse_pdu), false);
+    bbts_alloc(e, &g->d_sout, n * sizeof(GseStreamOut));
+    bbts_alloc(e, &g->d_slots, n * 3 * GSE_SLOT_BYTES, false);
     if (e != hipSuccess) { bbts_gse_free(g); return fail_hip(e, "hipMalloc(bbts gse)"); }
     *out = g;
     return 0;

@@ -1,7 +1,8 @@
 // Device routines of GSE decapsulation that the reference-mode kernels (bbts_gse.hip) and the mode-adaptation ones (bbts_ma.hip)
-// share, because the rule is the same in both: the CRC-32 of a fragment's span, what one packet record does to a reassembly
-// context, and the byte movement of the move / append launches.  What differs -- which frames are walked, how the packet chain is
-// followed, capacity -- stays with each mode.
+// share: the walk of one frame's packet chain (gse_walk_frame, over gse_parse_packet of bbts_rules.h), the CRC-32 of a fragment's
+// span, what one packet record does to a reassembly context (gse_apply_packet: the device's statement of the reassembly rule;
+// GseHostCtx::apply of bbts_host.h is the host's), and the byte movement of the move / append launches.  What differs -- which
+// frames are walked and under which rule set, capacity -- stays with each mode.
 #pragma once
 #include "bbts_common.h"
 
@@ -39,6 +40,52 @@ __device__ inline void gse_span_crcs(GsePkt* rec, const int* span_at, const int*
             }
         }
     }
+}
+
+// One frame's packets, by a workgroup of 256 threads.  Bytes [lo, lo + len) of the stream's input `bb` are staged in `stage`; lane 0
+// asks the kernel's prologue `where()` what to walk, follows the chain (next = at + what gse_parse_packet returns: the only serial
+// dependency) and fills one record and one CRC span per packet; `done(n, why)` puts the kernel's own frame record into LDS, *npkt
+// included (why: what ended the walk; GSE_OVER: more than GSE_PKT_CAP packets); the waves compute the spans' CRCs and the n records
+// go to `out`.  Offsets count from the start of the stream's input.  Only a reference packet can leave the staged bytes.
+enum { GSE_OVER = -3 };
+struct GseWalkRange { int at, end, limit; };      // at >= end: nothing to walk
+template <typename Rules, typename Where, typename Done>
+__device__ __forceinline__ void gse_walk_frame(const uint8_t* __restrict__ bb, int lo, int len, uint8_t* stage, GsePkt* rec, int* span_at,
+                                               int* span_len, Where where, Done done, const int* npkt, GsePkt* __restrict__ out, int tid) {
+    const uint8_t* src = bb + lo;
+    if ((reinterpret_cast<uintptr_t>(src) & 3) == 0) {
+        for (int i = tid; i < len / 4; i += 256) reinterpret_cast<uint32_t*>(stage)[i] = reinterpret_cast<const uint32_t*>(src)[i];
+        for (int i = (len & ~3) + tid; i < len; i += 256) stage[i] = src[i];
+    } else {
+        for (int i = tid; i < len; i += 256) stage[i] = src[i];
+    }
+    __syncthreads();
+    auto rd = [&](int i) -> unsigned {
+        const bool staged = !Rules::reference || (i >= lo && i < lo + len);
+        unsigned v = stage[staged ? i - lo : 0];
+        if (!staged) v = bb[i];
+        return v;
+    };
+    if (tid == 0) {
+        const GseWalkRange w = where();
+        int at = w.at, n = 0, why = GSE_PADDING;
+        while (at < w.end) {
+            GsePktHdr p;
+            const int took = gse_parse_packet<Rules>(rd, at, w.limit, &p);
+            if (took <= 0) { why = took; break; }
+            if (n == GSE_PKT_CAP) { why = GSE_OVER; break; }
+            rec[n] = {(uint32_t)p.body, (uint32_t)p.plen | (uint32_t)p.id << 16 | (uint32_t)p.kind << 24 | (uint32_t)(p.label ? 1 : 0) << 26, 0, p.proto};
+            span_at[n] = p.span_at; span_len[n] = p.span_len;
+            ++n;
+            at += took;
+        }
+        done(n, why);
+    }
+    __syncthreads();
+    const int n = *npkt;
+    gse_span_crcs(rec, span_at, span_len, n, rd, tid);
+    __syncthreads();
+    for (int k = tid; k < n; k += 256) out[k] = rec[k];
 }
 
 // One packet record (pk[idx], as the frame pass left it) applied to a reassembly context: slot choice (three slots, first fit; a

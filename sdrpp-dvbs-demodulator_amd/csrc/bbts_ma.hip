@@ -14,6 +14,9 @@
 // MaHostStream below applies the same rules to host buffers, byte by byte (host-only banks; the GPU path's second implementation).
 //
 // GSE in this mode (dvbs2gpu_bbts_ma_set_gse; rules in include/dvbs2gpu.h): one reassembly context per (stream, selected ISI) lane.
+// Nothing of GSE is stated here: the packet header is gse_parse_packet<GseStrict> (bbts_rules.h), the device's chain walk and
+// reassembly are gse_walk_frame and gse_apply_packet (bbts_gse_dev.h), the host's are GseHostCtx (bbts_host.h), and a context moves
+// between the two with gse_ctx_to_host / gse_ctx_to_device (bbts_common.h).  This file says which frames, which lane, which order.
 //   bbts_ma_frame_kernel      marks the GSE frames of selected ISIs in their records;
 //   bbts_ma_gse_scan_kernel   one workgroup per (frame, stream): the data field staged in LDS, one lane follows the packet chain, a wave
 //                             per fragment computes the CRC-32 of its span (bbts_gse_dev.h); 16 bytes per packet;
@@ -90,26 +93,6 @@ struct MaFin { const uint8_t* src; int len, pad; };
 
 // ------------------------------------------------------------------------------------------------- GSE per lane
 __host__ __device__ inline bool ma_gse_frame(const MaHdr& h) { return h.ts_gs == 1 && h.upl == 0 && !h.issyi && !h.npd; }
-struct MaGsePkt { int kind, id, label, body, plen; unsigned proto; };
-// the GSE packet at byte `at` of a data field of df bytes (rd(i): its byte i): 0 padding, the walk ends; -1 malformed (the length field
-// is smaller than the fixed fields + label, an END shorter than its CRC-32 included, or the packet passes the end of the data field);
-// else the bytes the packet takes
-template <typename Rd>
-__host__ __device__ inline int ma_gse_packet(Rd rd, int at, int df, MaGsePkt* p) {
-    const unsigned h1 = rd(at);
-    if ((h1 & 0xf0) == 0) return 0;                                // S = 0, E = 0, LT = 00
-    if (at + 2 > df) return -1;
-    const bool S = h1 & 0x80, E = h1 & 0x40;
-    const int lt = h1 >> 4 & 3, field = (int)((h1 & 0x0f) << 8 | rd(at + 1));
-    const int fixed = S && E ? 2 : S ? 5 : 1;                      // protocol type | frag id, total length, protocol type | frag id
-    const int label = S ? (lt == 0 ? 6 : lt == 1 ? 3 : 0) : 0;     // 10: none, 11: the label of the packet before (re-use), no bytes
-    if (field < fixed + label + (!S && E ? 4 : 0) || at + 2 + field > df) return -1;
-    p->kind = S && E ? GSE_COMPLETE : S ? GSE_START : E ? GSE_END : GSE_MIDDLE;
-    p->id = S && E ? 0 : (int)rd(at + 2);
-    p->label = label; p->body = at + 2 + fixed + label; p->plen = field - fixed - label;
-    p->proto = S && E ? rd(at + 2) << 8 | rd(at + 3) : S ? rd(at + 5) << 8 | rd(at + 6) : 0;
-    return 2 + field;
-}
 struct MaGseLane { GseDevState g; long long malformed; };          // three slots, the counters, the last END's verdict
 struct MaGseFrame { int npkt, malformed, over, pad; };              // over: more than GSE_PKT_CAP packets (the one host fallback)
 enum { MA_GSE_DONE = 0, MA_GSE_RECORDS = 1, MA_GSE_STORAGE = 2 };
@@ -357,44 +340,11 @@ __global__ void __launch_bounds__(256) bbts_ma_gse_scan_kernel(const uint8_t* co
     __shared__ GsePkt rec[GSE_PKT_CAP];
     __shared__ int span_at[GSE_PKT_CAP], span_len[GSE_PKT_CAP];
     __shared__ MaGseFrame fr;
-    const uint8_t* data = in[s] + r.data_off;
-    const int df = r.df;                           // <= frame size - 10 <= sizeof(stage) by ma_header and the size check of the call
-    if ((reinterpret_cast<uintptr_t>(data) & 3) == 0) {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(data);
-        for (int i = tid; i < df / 4; i += 256) reinterpret_cast<uint32_t*>(stage)[i] = src[i];
-        for (int i = (df & ~3) + tid; i < df; i += 256) stage[i] = data[i];
-    } else {
-        for (int i = tid; i < df; i += 256) stage[i] = data[i];
-    }
-    __syncthreads();
-    auto rd = [&](int i) -> unsigned { return stage[i]; };
-    if (tid == 0) {
-        MaGseFrame g = {0, 0, 0, 0};
-        int at = 0;
-        while (at < df) {
-            MaGsePkt p;
-            const int len = ma_gse_packet(rd, at, df, &p);
-            if (len == 0) break;
-            if (len < 0) { g.malformed = 1; break; }
-            if (g.npkt == GSE_PKT_CAP) { g.over = 1; g.npkt = 0; break; }
-            // records and spans count from the start of the stream's input, as in the reference mode
-            GsePkt q = {(uint32_t)(r.data_off + p.body), (uint32_t)p.plen | (uint32_t)p.id << 16 | (uint32_t)p.kind << 24 | (uint32_t)(p.label ? 1 : 0) << 26, 0, p.proto};
-            int sa = p.body, sl = 0;
-            if (p.kind == GSE_START) { sa = at + 3; sl = p.body + p.plen - sa; }        // total length, protocol type, label, payload
-            else if (p.kind == GSE_MIDDLE) sl = p.plen;
-            else if (p.kind == GSE_END) sl = p.plen - 4;
-            rec[g.npkt] = q; span_at[g.npkt] = r.data_off + sa; span_len[g.npkt] = sl;
-            ++g.npkt;
-            at += len;
-        }
-        fr = g;
-    }
-    __syncthreads();
-    const int n = fr.npkt, base = r.data_off;
-    gse_span_crcs(rec, span_at, span_len, n, [&](int i) -> unsigned { return stage[i - base]; }, tid);
-    __syncthreads();
-    GsePkt* o = pkts + ((size_t)s * max_frames + f) * GSE_PKT_CAP;
-    for (int k = tid; k < n; k += 256) o[k] = rec[k];
+    // r.df <= frame size - 10 <= sizeof(stage) by ma_header and the size check of the call
+    gse_walk_frame<GseStrict>(in[s], r.data_off, r.df, stage, rec, span_at, span_len,
+                              [&]() -> GseWalkRange { return {r.data_off, r.data_off + r.df, r.data_off + r.df}; },
+                              [&](int n, int why) { fr = {why == GSE_OVER ? 0 : n, why == GSE_MALFORMED, why == GSE_OVER, 0}; }, &fr.npkt,
+                              pkts + ((size_t)s * max_frames + f) * GSE_PKT_CAP, tid);
     if (tid == 0) gfr[(size_t)s * max_frames + f] = fr;
 }
 
@@ -498,10 +448,9 @@ struct MaHostStream {
     uint8_t carry[MA_LANES][MA_CARRY] = {};
     MaStreamState ss = {};
     uint8_t tab[256];
-    // GSE: per lane the context, the bytes of its open reassemblies (as many as are filled) and the rows of the last call
-    MaGseLane gse[MA_LANES] = {};
-    std::vector<uint8_t> gdata[MA_LANES][3];
-    std::vector<dvbs2gpu_gse_pdu> rows[MA_LANES];
+    // GSE: per lane the context (bbts_host.h: state, the bytes of its open reassemblies, the rows of the last call)
+    GseHostCtx gse[MA_LANES];
+    long long malformed[MA_LANES] = {};
 
     MaHostStream() {
         uint8_t t[MA_TAB_BYTES];
@@ -509,69 +458,9 @@ struct MaHostStream {
         memcpy(tab, t, 256);
     }
     void gse_reset() {
-        for (int k = 0; k < MA_LANES; ++k) {
-            gse[k] = MaGseLane{};
-            rows[k].clear();
-            for (auto& d : gdata[k]) d.clear();
-        }
+        for (int k = 0; k < MA_LANES; ++k) { gse[k] = GseHostCtx(); malformed[k] = 0; }
     }
-    static uint32_t crc32(uint32_t c, const uint8_t* p, int n) {
-        for (int i = 0; i < n; ++i) c = crc32m_byte(c, p[i]);
-        return c;
-    }
-    void gre(int slot, unsigned proto, const uint8_t* p, int n, int flags, std::vector<uint8_t>& out) {
-        const bool known = proto == 0x0800 || proto == 0x86DD;
-        const int total = 2 + (known ? 2 : 0) + n;
-        GseCounters& c = gse[slot].g.cnt;
-        ++((flags & 1) ? c.reassembled_pdus : c.complete_pdus);
-        c.bytes_delivered += total;
-        rows[slot].push_back({(uint32_t)out.size(), (uint32_t)total, (uint16_t)proto, (uint16_t)flags, 0});
-        out.push_back(0); out.push_back(0);    // GRE: no checksum, no key, no sequence number, version 0
-        if (known) { out.push_back((uint8_t)(proto >> 8)); out.push_back((uint8_t)proto); }
-        out.insert(out.end(), p, p + n);
-    }
-    // the data field of one GSE frame, packet by packet, with no limit on their number
-    void gse_frame(int slot, const uint8_t* data, int df, std::vector<uint8_t>& out) {
-        MaGseLane& gl = gse[slot];
-        ++gl.g.cnt.frames;
-        auto rd = [&](int i) -> unsigned { return data[i]; };
-        for (int at = 0, len; at < df; at += len) {
-            MaGsePkt p;
-            len = ma_gse_packet(rd, at, df, &p);
-            if (len == 0) break;
-            if (len < 0) { ++gl.malformed; break; }
-            ++gl.g.cnt.packets;
-            const uint8_t* body = data + p.body;
-            if (p.kind == GSE_COMPLETE) { gre(slot, p.proto, body, p.plen, p.label ? 2 : 0, out); continue; }
-            int r = -1;
-            for (int q = 2; q >= 0; --q) {
-                const GseSlot& sq = gl.g.slot[q];
-                if (p.kind == GSE_START ? (!sq.busy || sq.frag_id == p.id) : (sq.busy && sq.frag_id == p.id)) r = q;
-            }
-            if (r < 0) { if (p.kind == GSE_START) ++gl.g.cnt.dropped_no_slot; continue; }
-            GseSlot& sl = gl.g.slot[r];
-            std::vector<uint8_t>& buf = gdata[slot][r];
-            if (p.kind == GSE_START) {
-                sl = {1, p.id, p.plen, p.label ? 1 : 0, p.proto, crc32(0xffffffffu, data + at + 3, p.body + p.plen - (at + 3))};
-                buf.assign(body, body + p.plen);
-            } else if (sl.fill + p.plen > GSE_SLOT_BYTES) {
-                sl.busy = 0; buf.clear();
-                ++gl.g.cnt.dropped_overflow;
-            } else if (p.kind == GSE_MIDDLE) {
-                buf.insert(buf.end(), body, body + p.plen);
-                sl.fill += p.plen; sl.crc = crc32(sl.crc, body, p.plen);
-            } else {
-                buf.insert(buf.end(), body, body + p.plen - 4);
-                const uint8_t* e = body + p.plen;
-                const uint32_t rx = (uint32_t)e[-4] << 24 | (uint32_t)e[-3] << 16 | (uint32_t)e[-2] << 8 | e[-1];
-                sl.busy = 0;
-                gl.g.crc_err = crc32(sl.crc, body, p.plen - 4) != rx;
-                if (gl.g.crc_err) ++gl.g.cnt.crc_failures;
-                else gre(slot, sl.proto, buf.data(), (int)buf.size(), 1 | (sl.label ? 2 : 0), out);
-                buf.clear();
-            }
-        }
-    }
+    void clear_rows() { for (auto& c : gse) c.rows.clear(); }
     unsigned crc(const uint8_t* p, int a, int e) const {
         unsigned c = 0;
         for (int i = a; i < e; ++i) c = tab[c ^ p[i]];
@@ -600,7 +489,12 @@ struct MaHostStream {
         ss.seen[h.isi >> 5] |= 1u << (h.isi & 31);
         int slot = -1;
         for (int k = sel.n - 1; k >= 0; --k) if (sel.isi[k] == h.isi) slot = k;
-        if (cfg.gse && slot >= 0 && ma_gse_frame(h)) { ++st[slot].frames; gse_frame(slot, fr + 10, h.df, outs[slot]); return; }
+        if (cfg.gse && slot >= 0 && ma_gse_frame(h)) {     // strict rules, offsets from the start of the data field
+            ++st[slot].frames;
+            GseGrowingOut sink = {outs[slot]};
+            if (gse[slot].frame<GseStrict>(fr + 10, 0, h.df, h.df, sink) == GSE_MALFORMED) ++malformed[slot];
+            return;
+        }
         if (h.ts_gs != 3 || slot < 0) { ++ss.skipped; return; }
         MaLaneState& l = st[slot];
         uint8_t* cy = carry[slot];
@@ -770,6 +664,8 @@ static int ma_gse_storage(const BbtsBankView& v, BbtsMa* m) {
     return 0;
 }
 
+// the three slot buffers of lane w, or null while it has no place in the pool
+static uint8_t* ma_lane_slots(BbtsMa* m, size_t w) { return m->slotmap[w] < 0 ? nullptr : m->d_slots + (size_t)m->slotmap[w] * 3 * GSE_SLOT_BYTES; }
 // One stream of a device bank as a host parser, from state bank `bank`, and back: TS lanes, carried bytes, counters, GSE contexts and
 // the bytes of their open reassemblies.  This is how the host parser runs a stream's call in place of the kernels.
 static int ma_stream_to_host(BbtsMa* m, int i, int bank, MaHostStream& hs) {
@@ -777,15 +673,12 @@ static int ma_stream_to_host(BbtsMa* m, int i, int bank, MaHostStream& hs) {
     HIP_TRY(hipMemcpy(hs.st, m->d_lane[bank] + w0, sizeof(hs.st), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(hs.carry, m->d_carry[bank] + w0 * MA_CARRY, sizeof(hs.carry), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&hs.ss, m->d_strm[bank] + i, sizeof(hs.ss), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hs.gse, m->d_glane[bank] + w0, sizeof(hs.gse), hipMemcpyDeviceToHost));
-    for (int k = 0; k < MA_LANES; ++k)
-        for (int q = 0; q < 3; ++q) {
-            const GseSlot& sl = hs.gse[k].g.slot[q];
-            hs.gdata[k][q].clear();
-            if (!sl.busy || sl.fill <= 0 || m->slotmap[w0 + k] < 0) continue;
-            hs.gdata[k][q].resize(sl.fill);
-            HIP_TRY(hipMemcpy(hs.gdata[k][q].data(), m->d_slots + ((size_t)m->slotmap[w0 + k] * 3 + q) * GSE_SLOT_BYTES, sl.fill, hipMemcpyDeviceToHost));
-        }
+    for (int k = 0; k < MA_LANES; ++k) {
+        const MaGseLane* gl = m->d_glane[bank] + w0 + k;
+        const int rc = gse_ctx_to_host(hs.gse[k], &gl->g, ma_lane_slots(m, w0 + k));
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(&hs.malformed[k], &gl->malformed, sizeof(gl->malformed), hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 static int ma_stream_to_device(BbtsMa* m, int i, int bank, const MaHostStream& hs) {
@@ -793,13 +686,12 @@ static int ma_stream_to_device(BbtsMa* m, int i, int bank, const MaHostStream& h
     HIP_TRY(hipMemcpy(m->d_lane[bank] + w0, hs.st, sizeof(hs.st), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m->d_carry[bank] + w0 * MA_CARRY, hs.carry, sizeof(hs.carry), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m->d_strm[bank] + i, &hs.ss, sizeof(hs.ss), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->d_glane[bank] + w0, hs.gse, sizeof(hs.gse), hipMemcpyHostToDevice));
-    for (int k = 0; k < MA_LANES; ++k)
-        for (int q = 0; q < 3; ++q) {
-            const std::vector<uint8_t>& d = hs.gdata[k][q];
-            if (!hs.gse[k].g.slot[q].busy || d.empty() || m->slotmap[w0 + k] < 0) continue;
-            HIP_TRY(hipMemcpy(m->d_slots + ((size_t)m->slotmap[w0 + k] * 3 + q) * GSE_SLOT_BYTES, d.data(), d.size(), hipMemcpyHostToDevice));
-        }
+    for (int k = 0; k < MA_LANES; ++k) {
+        MaGseLane* gl = m->d_glane[bank] + w0 + k;
+        const int rc = gse_ctx_to_device(hs.gse[k], &gl->g, ma_lane_slots(m, w0 + k));
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(&gl->malformed, &hs.malformed[k], sizeof(gl->malformed), hipMemcpyHostToDevice));
+    }
     return 0;
 }
 
@@ -849,19 +741,18 @@ int dvbs2gpu_bbts_set_mode_adaptation(dvbs2gpu_bbts* b, const dvbs2gpu_bbts_ma_c
     const size_t n = v.nstreams, nl = n * MA_LANES, nfr = n * v.max_frames;
     if (v.ctx) {
         hipError_t e = hipSuccess;
-        auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) { e = hipMalloc(p, bytes); if (e == hipSuccess) e = hipMemset(*p, 0, bytes); } };
         for (int k = 0; k < 2; ++k) {
-            A((void**)&m->d_lane[k], nl * sizeof(MaLaneState));
-            A((void**)&m->d_strm[k], n * sizeof(MaStreamState));
-            A((void**)&m->d_carry[k], nl * MA_CARRY);
+            bbts_alloc(e, &m->d_lane[k], nl * sizeof(MaLaneState));
+            bbts_alloc(e, &m->d_strm[k], n * sizeof(MaStreamState));
+            bbts_alloc(e, &m->d_carry[k], nl * MA_CARRY);
         }
-        A((void**)&m->d_sel, n * sizeof(MaSel));
-        A((void**)&m->d_tabs, MA_TAB_BYTES);
-        A((void**)&m->d_join, nfr * MA_CARRY);
-        A((void**)&m->d_recs, nfr * sizeof(MaFrameRec));
-        A((void**)&m->d_desc, nfr * sizeof(MaFrameDesc));
-        A((void**)&m->d_fins, nl * sizeof(MaFin));
-        A(&m->d_args, MaArgs(n, v.max_frames).L.bytes());
+        bbts_alloc(e, &m->d_sel, n * sizeof(MaSel));
+        bbts_alloc(e, &m->d_tabs, MA_TAB_BYTES);
+        bbts_alloc(e, &m->d_join, nfr * MA_CARRY);
+        bbts_alloc(e, &m->d_recs, nfr * sizeof(MaFrameRec));
+        bbts_alloc(e, &m->d_desc, nfr * sizeof(MaFrameDesc));
+        bbts_alloc(e, &m->d_fins, nl * sizeof(MaFin));
+        bbts_alloc(e, &m->d_args, MaArgs(n, v.max_frames).L.bytes());
         if (e != hipSuccess) { bbts_ma_free(m.release()); return fail_hip(e, "hipMalloc(bbts mode adaptation)"); }
         uint8_t t[MA_TAB_BYTES];
         ma_build_tables(t);
@@ -993,7 +884,7 @@ int dvbs2gpu_bbts_process_ma_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb,
             if (!frame_bytes) for (int f = 0; f <= nframes[i]; ++f) own[f] = f * (v.kbch / 8);
             h_in.resize(off[nframes[i]]);
             HIP_TRY(hipMemcpy(h_in.data(), d_bb[i], h_in.size(), hipMemcpyDeviceToHost));
-            for (auto& r : fb->hs.rows) r.clear();
+            fb->hs.clear_rows();
             for (int f = 0; f < nframes[i]; ++f) fb->hs.frame(h_in.data() + off[f], off[f + 1] - off[f], m->cfg, m->sel[i], fb->outs);
             for (int k = 0; k < MA_LANES; ++k) need[i * MA_LANES + k] = (int)fb->outs[k].size();
             fbs.push_back(std::move(fb));
@@ -1035,7 +926,7 @@ int dvbs2gpu_bbts_process_ma_batch(dvbs2gpu_bbts* b, const uint8_t* const* d_bb,
         ++m->fb_calls[i];
         for (int k = 0; k < MA_LANES; ++k) {
             if (!fb->outs[k].empty()) HIP_TRY(hipMemcpy(d_out[i * MA_LANES + k], fb->outs[k].data(), fb->outs[k].size(), hipMemcpyHostToDevice));
-            m->fb_rows[i * MA_LANES + k] = fb->hs.rows[k];
+            m->fb_rows[i * MA_LANES + k] = fb->hs.gse[k].rows;
             m->rows_host[i * MA_LANES + k] = 1;
         }
         const int rc = ma_stream_to_device(m, i, cur ^ 1, fb->hs);
@@ -1059,7 +950,7 @@ int dvbs2gpu_bbts_ma_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, const int* fram
     for (int k = 0; k < sel.n; ++k) if (cnt > 0 && !h_out[k]) return DVBS2GPU_ERR_ARG;
     if (!v.ctx) {
         MaHostStream trial = *m->host;             // the state advances only when every output fits
-        for (auto& r : trial.rows) r.clear();
+        trial.clear_rows();
         std::vector<uint8_t> outs[MA_LANES];
         for (int f = 0; f < cnt; ++f) trial.frame(h_bb + off[f], off[f + 1] - off[f], m->cfg, sel, outs);
         bool fits = true;
@@ -1069,7 +960,7 @@ int dvbs2gpu_bbts_ma_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, const int* fram
             out_bytes[k] = 0;
         }
         if (!fits) {                               // nothing advanced; the failed call has no rows
-            for (auto& r : m->host->rows) r.clear();
+            m->host->clear_rows();
             g_err = "mode adaptation: an output does not fit into cap (needed[] has the sizes)";
             return DVBS2GPU_ERR_CAPACITY;
         }
@@ -1201,7 +1092,7 @@ int dvbs2gpu_bbts_ma_get_gse_stats(dvbs2gpu_bbts* b, int stream, int slot, dvbs2
     if (!m || stream < 0 || stream >= v.nstreams) return DVBS2GPU_ERR_ARG;
     MaGseLane gl = {};
     if (!v.ctx) {
-        gl = m->host->gse[slot];
+        gl = {m->host->gse[slot].g, m->host->malformed[slot]};
     } else if (m->d_glane[0]) {
         HIP_TRY(hipSetDevice(v.ctx->device));
         HIP_TRY(hipMemcpy(&gl, m->d_glane[m->cur] + (size_t)stream * MA_LANES + slot, sizeof(gl), hipMemcpyDeviceToHost));
@@ -1221,7 +1112,7 @@ int dvbs2gpu_bbts_ma_get_gse_stats(dvbs2gpu_bbts* b, int stream, int slot, dvbs2
 static int ma_rows(const BbtsBankView& v, BbtsMa* m, int stream, int slot, const dvbs2gpu_gse_pdu** host, const dvbs2gpu_gse_pdu** dev, int* n) {
     *host = nullptr; *dev = nullptr; *n = 0;
     const int w = stream * MA_LANES + slot;
-    if (!v.ctx) { *host = m->host->rows[slot].data(); *n = (int)m->host->rows[slot].size(); return 0; }
+    if (!v.ctx) { *host = m->host->gse[slot].rows.data(); *n = (int)m->host->gse[slot].rows.size(); return 0; }
     if (!m->d_glane[0]) return 0;
     if (m->rows_host[w]) { *host = m->fb_rows[w].data(); *n = (int)m->fb_rows[w].size(); return 0; }
     *n = m->ginfo[w] >> 2;
