@@ -5,10 +5,8 @@
 //   BbTsParser::set_frame_size   .cpp:31-42
 //   BbTsParser::work         .cpp:104-390   header checks :119-152, resynchronisation :159-170, MPEG-TS packetisation :176-207,
 //                                            GSE -> GRE decapsulation with three reassembly slots :211-383, CRC-32 :85-102
-// PARITY UNPINNED: bbframe_ts_parser.h includes <dsp/stream.h> of SDR++ core, which is not vendored with the reference
-// and absent from this image, so the reference's own translation unit cannot be compiled here (no stand-in headers are
-// written); the reference holds no test vectors for it either.  The restatement is anchored on the reference's code as
-// read, and on round trips through this repo's transmitter (TS packets -> BBFRAMEs per EN 302 307-1 5.1.4-5.1.6 -> parser).
+// Pinned: the reference's own translation unit compiles over the stand-in headers of oracle/shim (its <dsp/stream.h> include
+// is unused) and tests/test_oracle_bbts.py compares call by call; the golden vectors of tests/golden/bbts_golden.json are its outputs.
 //
 // Where the reference's behaviour is undefined (reads beyond the caller's input buffer, writes beyond the output buffer
 // or the 64 KiB reassembly buffers, a negative length passed to memcpy) this restatement -- and the engine -- do:
@@ -17,6 +15,8 @@
 //   * a PDU that does not fit into the remaining output space, or whose reassembled length is negative, is dropped;
 //   * a fragment that would overflow a reassembly buffer frees the slot and is dropped;
 //   * the TS loop running out of output space with more than 187 bytes of data field left returns -1.
+// Each work() call records in `last_undefined` which of these it met (BBTS_UB_*), so that a comparison with the reference's
+// own code can tell the calls that stayed inside defined behaviour from those where the two need not agree.
 #include "bbframe_ts.h"
 
 #include <cstring>
@@ -76,10 +76,11 @@ int BbTsParser::work(const uint8_t* bb, int cnt, uint8_t* out, int cap) {
     const long fbytes = kbch / 8;
     const long total = fbytes * cnt;
     int out_p = 0, bbproc = 0;
+    last_undefined = 0;
 
     auto put_gre = [&](uint16_t proto, const uint8_t* data, int len) {   // .cpp:254-263 / :338-349
         int hdr = 2 + ((proto == 0x0800 || proto == 0x86DD) ? 2 : 0);
-        if (len < 0 || (long)out_p + hdr + len > cap) return;            // dropped (see header)
+        if (len < 0 || (long)out_p + hdr + len > cap) { last_undefined |= len < 0 ? BBTS_UB_LENGTH : BBTS_UB_OUTPUT; return; }   // dropped (see header)
         out[out_p++] = 0;
         out[out_p++] = 0;
         if (hdr == 4) { out[out_p++] = proto >> 8; out[out_p++] = proto & 0xff; }
@@ -122,7 +123,7 @@ int BbTsParser::work(const uint8_t* bb, int cnt, uint8_t* out, int cap) {
                 memcpy(out + out_p + 1, cur, 187);
                 out_p += 188;
             }
-            if (df >= 188) { synched = 0; return -1; }
+            if (df >= 188) { synched = 0; last_undefined |= BBTS_UB_OUTPUT; return -1; }
             if (df > 0) {
                 count = (int)df;
                 memcpy(partial, bb + pos, df);
@@ -134,7 +135,7 @@ int BbTsParser::work(const uint8_t* bb, int cnt, uint8_t* out, int cap) {
             while (cur < dfl8) {
                 if (hd.issyi || hd.npd || hd.upl != 0) { cur = dfl8; break; }
                 const long p = pos + cur;
-                if (p + 2 > total) break;
+                if (p + 2 > total) { last_undefined |= BBTS_UB_INPUT; break; }
                 const uint8_t h1 = bb[p], h2 = bb[p + 1];
                 const int S = h1 >> 7, E = (h1 >> 6) & 1;
                 const int lt = (h1 & 0x30) >> 2;            // 0, 4, 8 or 12: only label type 00 is ever told apart (.cpp:216)
@@ -144,7 +145,7 @@ int BbTsParser::work(const uint8_t* bb, int cnt, uint8_t* out, int cap) {
                     int start = 4;
                     len -= 2;
                     if (lt == 0) { start += 6; len -= 6; }
-                    if (p + start + len > total) break;
+                    if (p + start + len > total) { last_undefined |= BBTS_UB_INPUT; break; }
                     uint16_t proto = (uint16_t)(bb[p + 2] << 8 | bb[p + 3]);
                     put_gre(proto, bb + p + start, len);
                     cur += start + len;
@@ -152,7 +153,7 @@ int BbTsParser::work(const uint8_t* bb, int cnt, uint8_t* out, int cap) {
                     int start = 7;
                     len -= 5;
                     if (lt == 0) { start += 6; len -= 6; }
-                    if (p + start + len > total) break;
+                    if (p + start + len > total) { last_undefined |= BBTS_UB_INPUT; break; }
                     const int fragid = bb[p + 2];
                     for (auto& s : slot) {
                         if (!s.active || s.id == fragid) {
@@ -173,11 +174,11 @@ int BbTsParser::work(const uint8_t* bb, int cnt, uint8_t* out, int cap) {
                 } else {
                     const int start = 3;
                     len -= 1;
-                    if (p + start + len > total) break;
+                    if (p + start + len > total) { last_undefined |= BBTS_UB_INPUT; break; }
                     const int fragid = bb[p + 2];
                     for (auto& s : slot) {
                         if (s.active && s.id == fragid) {
-                            if ((long)s.ctr + len > 65536) { s.active = false; break; }
+                            if ((long)s.ctr + len > 65536) { s.active = false; last_undefined |= BBTS_UB_SLOT; break; }
                             s.buf.resize(s.ctr);
                             s.buf.insert(s.buf.end(), bb + p + start, bb + p + start + len);
                             if (E) {

@@ -10,6 +10,12 @@ struct BbHeader {
     int ts_gs = 0, sis_mis = 0, ccm_acm = 0, issyi = 0, npd = 0, ro = 0, isi = 0, upl = 0, dfl = 0, sync = 0, syncd = 0;
 };
 
+// where the reference's behaviour is undefined and this restatement follows its own rule instead (bbframe_ts.cpp, header comment)
+enum { BBTS_UB_INPUT = 1,      // a GSE packet extends beyond the last BBFRAME of the call
+       BBTS_UB_OUTPUT = 2,     // a PDU or a TS packet does not fit into the output space
+       BBTS_UB_LENGTH = 4,     // a reassembled PDU of negative length
+       BBTS_UB_SLOT = 8 };     // a fragment would carry a reassembly buffer past 64 KiB
+
 // dsp::dvbs2::BBFrameTSParser (dvbs2/bbframe_ts_parser.h:68-112, .cpp:31-390)
 struct BbTsParser {
     BbHeader last_header;
@@ -23,6 +29,7 @@ struct BbTsParser {
 
     // exposed for tests
     int synched = 0, count = 0;
+    int last_undefined = 0;      // BBTS_UB_* met by the last work() call (see bbframe_ts.cpp)
 
 private:
     int kbch = 0, max_dfl = 0;

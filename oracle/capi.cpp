@@ -338,5 +338,6 @@ void orc_bbts_get_stats(void* h, int32_t* o17) {
                        p->last_gse_crc_err, p->last_bb_cnt, p->last_bb_proc, p->last_ts_errs, p->synched, p->count};
     for (int i = 0; i < 17; ++i) o17[i] = v[i];
 }
+int orc_bbts_last_undefined(void* h) { return ((const BbTsParser*)h)->last_undefined; }
 unsigned orc_bbts_crc8_bits(const uint8_t* in, int nbits) { return bbts_crc8_bits(in, nbits); }
 }  // extern "C"

@@ -13,9 +13,9 @@
 //   CCEncoder::work                           dvbs/viterbi/cc_encoder.cpp:92-104
 //   Viterbi_DVBS::get_ber / work              dvbs/viterbi_all.cpp:59-276
 //   DVBSInterleaving::deinterleave            dvbs/dvbs_interleaving.h:58-70            (pinned via oracle/_ref)
-// PARITY UNPINNED for the Viterbi decoder itself: cc_decoder.cpp / volk_k7_r2_generic_fixed.h include VOLK headers,
-// which are not in /root/reference, so they cannot be compiled here; on x86 with VOLK present the
-// reference would even pick VOLK's "spiral" kernel instead of the bundled generic one (Q8).
+// The Viterbi decoder is pinned too: viterbi_all.cpp, cc_decoder.cpp and cc_encoder.cpp compile over the stand-in headers of
+// oracle/shim (no arithmetic there) and tests/test_oracle_dvbs.py compares block by block.  With no VOLK implementation
+// listed the reference runs its bundled generic kernel; on x86 with VOLK present it would pick VOLK's "spiral" one (Q8).
 #include "dvbs.h"
 #include <cstring>
 #include <cstdlib>

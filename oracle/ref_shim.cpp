@@ -176,3 +176,115 @@ int ref_dvbsrs_decode(void* h, uint8_t* data204) { return ((dsp::dvbs::DVBSReedS
 void* ref_dvbsdescr_create() { return new dsp::dvbs::DVBSScrambling(); }
 void ref_dvbsdescr_work(void* h, uint8_t* frm) { ((dsp::dvbs::DVBSScrambling*)h)->descramble(frm); }
 }
+
+// ---------------------------------------------------------------------------------- DVB-S inner code: Viterbi_DVBS, CCDecoder, CCEncoder
+// These translation units include VOLK and nng headers for a container, a kernel query and nothing else; oracle/shim/ stands
+// in for those headers (no arithmetic there: the ACS kernel that runs is the reference's own volk_k7_r2_generic_fixed.h).
+#include "dvbs/viterbi_all.h"
+#include "dvbs/dvbs_defines.h"
+#include <new>
+
+// Viterbi_DVBS keeps the phase it locked on private, hands its shift out as a bool (viterbi_all.h:158) and its d_ber only
+// while locked (ber() of an idle decoder is the smallest BER of the last search, viterbi_all.cpp:282-311).  Explicit
+// instantiation may name private members, which gives read access without touching the reference's text.
+template <class Tag, typename Tag::type M>
+struct PrivateMember {
+    friend typename Tag::type member_of(Tag) { return M; }
+};
+struct VitPhase { typedef phase_t viterbi::Viterbi_DVBS::*type; friend type member_of(VitPhase); };
+struct VitShift { typedef int viterbi::Viterbi_DVBS::*type; friend type member_of(VitShift); };
+template struct PrivateMember<VitPhase, &viterbi::Viterbi_DVBS::d_phase>;
+template struct PrivateMember<VitShift, &viterbi::Viterbi_DVBS::d_shift>;
+struct VitBer { typedef float viterbi::Viterbi_DVBS::*type; friend type member_of(VitBer); };
+template struct PrivateMember<VitBer, &viterbi::Viterbi_DVBS::d_ber>;
+
+extern "C" {
+// Constructed exactly as module_dvbs_demod.cpp:23 does: VIT_BUF_SIZE and {PHASE_0, PHASE_90}.  NOT the class's default of four
+// phases: work() indexes d_bers_*[2][12] with the phase (viterbi_all.cpp:91,115,140,164,189), so PHASE_180 / PHASE_270 write
+// rows 2 and 3 of two-row arrays and overwrite the members that follow (seen under UBSan, and as a crash).
+//
+// The object is built in storage that was zeroed first, so that the members the constructor leaves alone read 0 instead of
+// heap garbage: d_rate / d_phase / d_shift until the first lock (viterbi_all.h:44-46), and ber_depunc_buffer (:77), of which
+// the rate-7/8 test decoder reads 2 * (1792 + 6) = 3596 bytes (cc_decoder.cpp:297 from viterbi_all.cpp:186) although no
+// de-puncturer ever writes beyond byte 3584 of it.  Zero is what the oracle and the engine define for those bytes.
+void* ref_viterbi_create(float thr, int max_outsync) {
+    void* mem = operator new(sizeof(viterbi::Viterbi_DVBS));
+    memset(mem, 0, sizeof(viterbi::Viterbi_DVBS));
+    return new (mem) viterbi::Viterbi_DVBS(thr, max_outsync, VIT_BUF_SIZE, {PHASE_0, PHASE_90});
+}
+void ref_viterbi_destroy(void* h) { delete (viterbi::Viterbi_DVBS*)h; }
+int ref_viterbi_buf_size(void) { return VIT_BUF_SIZE; }
+// `input` is rotated in place when the decoder is locked (viterbi_all.cpp:211)
+int ref_viterbi_work(void* h, int8_t* input, int size, uint8_t* output) { return ((viterbi::Viterbi_DVBS*)h)->work(input, size, output); }
+float ref_viterbi_ber(void* h) { return ((viterbi::Viterbi_DVBS*)h)->ber(); }
+int ref_viterbi_state(void* h) { return ((viterbi::Viterbi_DVBS*)h)->getState(); }
+int ref_viterbi_rate(void* h) { return (int)((viterbi::Viterbi_DVBS*)h)->rate(); }
+int ref_viterbi_getshift(void* h) { return ((viterbi::Viterbi_DVBS*)h)->getshift(); }
+int ref_viterbi_phase(void* h) { return (int)(((viterbi::Viterbi_DVBS*)h)->*member_of(VitPhase())); }
+int ref_viterbi_shift(void* h) { return ((viterbi::Viterbi_DVBS*)h)->*member_of(VitShift()); }
+float ref_viterbi_d_ber(void* h) { return ((viterbi::Viterbi_DVBS*)h)->*member_of(VitBer()); }
+
+// K = 7, r = 1/2, polynomials {79, 109}: the arguments of every decoder / encoder in viterbi_all.cpp:17-32
+void* ref_ccdec_create(int frame) { return new viterbi::CCDecoder(frame, 7, 2, {79, 109}); }
+void ref_ccdec_destroy(void* h) { delete (viterbi::CCDecoder*)h; }
+void ref_ccdec_work(void* h, uint8_t* in, uint8_t* out) { ((viterbi::CCDecoder*)h)->work(in, out); }
+void* ref_ccenc_create(int frame) { return new viterbi::CCEncoder(frame, 7, 2, {79, 109}); }
+void ref_ccenc_destroy(void* h) { delete (viterbi::CCEncoder*)h; }
+void ref_ccenc_work(void* h, uint8_t* in, uint8_t* out) { ((viterbi::CCEncoder*)h)->work(in, out); }
+}
+
+// ---------------------------------------------------------------------------------- BBFRAME -> TS / GSE parser
+#include "dvbs2/bbframe_ts_parser.h"
+namespace {
+// The reference's parser trusts its input: a GSE length field can send its reads past the last BBFRAME of the call and its
+// writes past `buffer_outsize` (bbframe_ts_parser.cpp:269,311,334,357,371 have no bound).  So that such a call neither faults
+// nor goes unnoticed, work() runs on private copies with guard zones behind both buffers: the input guard is filled with a
+// byte the caller chooses (two handles with different fills give different results exactly where out-of-bounds input
+// mattered), the output guard with a canary that is checked afterwards.
+struct RefBbTs {
+    dsp::dvbs2::BBFrameTSParser* p;
+    int kbch = 0, left_output = 0;
+    uint8_t guard_fill;
+    std::vector<uint8_t> in, out;
+};
+const size_t BBTS_GUARD = 1 << 20;
+const uint8_t BBTS_CANARY = 0xC5;
+}
+extern "C" {
+void* ref_bbts_create(int kbch_bits, int guard_fill) {
+    auto* r = new RefBbTs();
+    // BBFrameTSParser has no constructor and leaves count, synched, df_remaining, ... uninitialised (bbframe_ts_parser.h:79-89);
+    // value-initialisation zeroes them so that runs are reproducible
+    r->p = new dsp::dvbs2::BBFrameTSParser();
+    r->guard_fill = (uint8_t)guard_fill;
+    r->kbch = kbch_bits;
+    r->p->setFrameSize(kbch_bits);
+    return r;
+}
+void ref_bbts_destroy(void* h) { delete ((RefBbTs*)h)->p; delete (RefBbTs*)h; }
+void ref_bbts_set_frame_size(void* h, int kbch_bits) { ((RefBbTs*)h)->kbch = kbch_bits; ((RefBbTs*)h)->p->setFrameSize(kbch_bits); }
+// `out` holds `cap` bytes, pre-filled by the caller; at most `cap` bytes come back whatever the return value says
+int ref_bbts_work(void* h, const uint8_t* bbframes, int cnt, uint8_t* out, int cap) {
+    RefBbTs* r = (RefBbTs*)h;
+    const size_t nin = (size_t)(r->kbch / 8) * cnt;
+    r->in.assign(nin + BBTS_GUARD, r->guard_fill);
+    memcpy(r->in.data(), bbframes, nin);
+    r->out.assign((size_t)cap + BBTS_GUARD, BBTS_CANARY);
+    memcpy(r->out.data(), out, cap);
+    const int n = r->p->work(r->in.data(), cnt, r->out.data(), cap);
+    memcpy(out, r->out.data(), cap);
+    r->left_output = n > cap;
+    for (size_t i = cap; i < r->out.size() && !r->left_output; ++i) r->left_output = r->out[i] != BBTS_CANARY;
+    return n;
+}
+// 1 when the last work() wrote beyond `cap`
+int ref_bbts_left_output(void* h) { return ((RefBbTs*)h)->left_output; }
+// the public fields: {ts_gs, sis_mis, ccm_acm, issyi, npd, ro, isi, upl, dfl, sync, syncd, last_gse_crc_err, last_bb_cnt, last_bb_proc, last_ts_errs}
+void ref_bbts_get_fields(void* h, int32_t* o15) {
+    const dsp::dvbs2::BBFrameTSParser* p = ((RefBbTs*)h)->p;
+    const dsp::dvbs2::BBHeader& q = p->last_header;
+    const int v[15] = {q.ts_gs, q.sis_mis, q.ccm_acm, q.issyi, q.npd, q.ro, q.isi, q.upl, q.dfl, q.sync, q.syncd,
+                       p->last_gse_crc_err, p->last_bb_cnt, p->last_bb_proc, p->last_ts_errs};
+    for (int i = 0; i < 15; ++i) o15[i] = v[i];
+}
+}

@@ -101,8 +101,9 @@ class OracleViterbi:
         except Exception:
             pass
 
-    def work(self, soft_blocks):
-        """soft_blocks int8 [nblocks, 8192] -> bits uint8 [nblocks, 8192] (zero beyond nbits), nbits [nblocks], stats [nblocks, 5]"""
+    def work(self, soft_blocks, fill=0):
+        """soft_blocks int8 [nblocks, 8192] -> bits uint8 [nblocks, 8192] (`fill` where the decoder wrote nothing), nbits [nblocks],
+        stats [nblocks, 5] = BER as float bits, state, rate, phase, shift"""
         nb = soft_blocks.shape[0]
         bits = np.zeros((nb, 8192), np.uint8)
         nbits = np.zeros(nb, np.int32)
@@ -110,12 +111,127 @@ class OracleViterbi:
         st = np.zeros(4, np.float32)
         for b in range(nb):
             x = np.ascontiguousarray(soft_blocks[b]).copy()
-            o = np.zeros(8192 + 64, np.uint8)
+            o = np.full(8192 + 64, fill, np.uint8)
             nbits[b] = self.l.orc_vitdvbs_work(self.h, P(x), 8192, P(o), P(st))
             bits[b] = o[:8192]
             ps = int(st[3])
             stats[b] = [np.float32(st[0]).view(np.int32), int(st[1]), int(st[2]), ps // 16, ps % 16]
         return bits, nbits, stats
+
+
+def R():
+    """the compiled reference (oracle/_ref) with its DVB-S inner-code entry points bound, or None when it is not built"""
+    r = ref()
+    if r is None or not hasattr(r, 'ref_viterbi_create'):
+        return None
+    if not getattr(r, '_dvbs_inner_bound', False):
+        for n in ('ref_viterbi_create', 'ref_ccdec_create', 'ref_ccenc_create'):
+            getattr(r, n).restype = VP
+        r.ref_viterbi_create.argtypes = [C.c_float, C.c_int]
+        r.ref_ccdec_create.argtypes = r.ref_ccenc_create.argtypes = [C.c_int]
+        for n in ('ref_viterbi_destroy', 'ref_ccdec_destroy', 'ref_ccenc_destroy'):
+            getattr(r, n).restype = None
+            getattr(r, n).argtypes = [VP]
+        r.ref_viterbi_work.argtypes = [VP, VP, C.c_int, VP]
+        r.ref_viterbi_ber.restype = r.ref_viterbi_d_ber.restype = C.c_float
+        for n in ('ref_viterbi_ber', 'ref_viterbi_d_ber', 'ref_viterbi_state', 'ref_viterbi_rate', 'ref_viterbi_getshift', 'ref_viterbi_phase', 'ref_viterbi_shift'):
+            getattr(r, n).argtypes = [VP]
+        r.ref_ccdec_work.argtypes = r.ref_ccenc_work.argtypes = [VP, VP, VP]
+        r.ref_ccdec_work.restype = r.ref_ccenc_work.restype = None
+        r._dvbs_inner_bound = True
+    return r
+
+
+class RefViterbi:
+    """the reference's Viterbi_DVBS, constructed as the plugin does (8192-soft blocks, phases 0 and 90 degrees)"""
+
+    def __init__(self, thr=0.15, max_outsync=20):
+        self.r = R()
+        assert self.r.ref_viterbi_buf_size() == 8192
+        self.h = VP(self.r.ref_viterbi_create(thr, max_outsync))
+
+    def __del__(self):
+        try:
+            self.r.ref_viterbi_destroy(self.h)
+        except Exception:
+            pass
+
+    def work(self, soft_blocks, fill=0):
+        """as OracleViterbi.work (rate, phase and shift read 0 until the first lock: see ref_viterbi_create in oracle/ref_shim.cpp)"""
+        r, nb = self.r, soft_blocks.shape[0]
+        bits = np.zeros((nb, 8192), np.uint8)
+        nbits = np.zeros(nb, np.int32)
+        stats = np.zeros((nb, 5), np.int32)
+        for b in range(nb):
+            x = np.ascontiguousarray(soft_blocks[b]).copy()
+            o = np.full(8192 + 64, fill, np.uint8)
+            nbits[b] = r.ref_viterbi_work(self.h, P(x), 8192, P(o))
+            bits[b] = o[:8192]
+            # the BER of the stats row is the member d_ber; the public ber() is that member while locked, and in IDLE the smallest
+            # BER of the last search (viterbi_all.cpp:278-313), a display value that the oracle and the engine do not offer
+            ber = np.float32(r.ref_viterbi_d_ber(self.h)).view(np.int32)
+            if r.ref_viterbi_state(self.h) == 1:
+                assert np.float32(r.ref_viterbi_ber(self.h)).view(np.int32) == ber
+            assert r.ref_viterbi_getshift(self.h) == int(r.ref_viterbi_shift(self.h) != 0)
+            stats[b] = [ber, r.ref_viterbi_state(self.h), r.ref_viterbi_rate(self.h), r.ref_viterbi_phase(self.h), r.ref_viterbi_shift(self.h)]
+        return bits, nbits, stats
+
+
+def viterbi_written_bits(bits, nbits, stats):
+    """the bits the decoder wrote, block after block: [0, count) of each block, at rate 5/6 [0, 6799) (the reference's main decoder
+    of that rate handles 6799 bits and leaves the rest of the count unwritten)"""
+    return np.concatenate([bits[b, :min(int(nbits[b]), 6799) if stats[b, 2] == 3 else int(nbits[b])] for b in range(len(nbits))] + [np.zeros(0, np.uint8)])
+
+
+def viterbi_case_streams(nb):
+    """the Viterbi_DVBS test streams, list of (name, soft int8 [nb, 8192]), nb >= 6: five rates x puncturing shifts x 90 degree rotation,
+    noise, marginal SNR at 1/2 and 7/8, and lock -> noise -> re-lock at another rate"""
+    rng = np.random.default_rng(77)
+    cases = []
+    for rate in range(5):
+        for drop, rot in ((0, False), (1, True), (3, False)):
+            if rate in (2, 4):
+                drop = 2 * (drop > 0)
+            soft, _ = dvbs_tx(rate, nb * 8192, seed=300 + 10 * rate + drop + rot, drop=drop, rot90=rot, sigma=12.0)
+            cases.append((f'rate{rate}_d{drop}_r{int(rot)}', soft.reshape(nb, 8192)))
+    cases.append(('noise', rng.integers(-70, 71, (nb, 8192)).astype(np.int8)))
+    cases.append(('full_range_noise', rng.integers(-128, 128, (nb, 8192)).astype(np.int8)))
+    # marginal SNR: BER hovers around the threshold, watchdog counting matters
+    soft, _ = dvbs_tx(0, nb * 8192, seed=501, sigma=30.0)
+    cases.append(('marginal_12', soft.reshape(nb, 8192)))
+    soft, _ = dvbs_tx(4, nb * 8192, seed=502, sigma=17.0)
+    cases.append(('marginal_78', soft.reshape(nb, 8192)))
+    # signal, then noise, then a different rate: lock -> watchdog -> IDLE -> re-lock
+    a, _ = dvbs_tx(1, nb * 8192, seed=503)
+    b, _ = dvbs_tx(3, nb * 8192, seed=504, rot90=True)
+    x = a.reshape(nb, 8192).copy()
+    x[2:5] = rng.integers(-70, 71, (3, 8192))
+    x[5:] = b.reshape(nb, 8192)[5:]
+    cases.append(('relock', x))
+    return cases
+
+
+CCDEC_FRAMES = [54, 56, 57, 59, 114, 1024, 1366, 1699, 4096, 6799]     # (frame + 6 steps in chunks of 60 = 10 rotations of the state layout: every remainder 0..5, a chunk that is exactly full)
+
+
+def ccdec_case_softs(frame, S=6, nblk=4):
+    """unsigned softs uint8 [S, 2 * frame * nblk + 64] for chained CCDecoder blocks of `frame` bits: five noise levels (one with
+    erasures) and pure garbage; consecutive blocks start 2 * frame apart and overlap by the 12-byte tail, like the reference's buffers"""
+    rng = np.random.default_rng(frame)
+    stride = 2 * frame
+    Lb = stride * nblk + 64
+    soft = np.zeros((S, Lb), np.uint8)
+    for s in range(S):
+        bits = rng.integers(0, 2, frame * nblk + 64, dtype=np.uint8)
+        enc = cc_encode(bits)[:Lb]
+        sigma = [10, 25, 40, 60, 90, 1e-3][s]
+        x = np.where(enc > 0, 127 + 35, 127 - 35) + rng.normal(0, sigma, Lb)
+        x = np.clip(np.rint(x), 0, 255).astype(np.uint8)
+        if s == 4:
+            x[rng.random(Lb) < 0.3] = 128   # erasures
+        soft[s] = x
+    soft[5] = rng.integers(0, 256, Lb, dtype=np.uint8)   # pure garbage: exercises the uint8 wrap-around of the metrics
+    return soft
 
 
 # ------------------------------------------------------------------ DVB-S front end (oracle/dvbs_fe.cpp)

@@ -23,24 +23,12 @@ def test_slice_matches_oracle(engine, pkg):
     assert pkg.dvbs_slice(engine, torch.zeros(0, dtype=torch.complex64, device='cuda')).numel() == 0
 
 
-@pytest.mark.parametrize('frame', [54, 56, 57, 59, 114, 1024, 1366, 1699, 4096, 6799])     # (frame + 6 steps in chunks of 60 = 10 rotations of the state layout: every remainder 0..5, a chunk that is exactly full)
+@pytest.mark.parametrize('frame', od.CCDEC_FRAMES)
 def test_ccdec_chained_blocks_bit_exact(engine, pkg, frame):
     import torch
-    rng = np.random.default_rng(frame)
     S, nblk = 6, 4
-    stride = 2 * frame                      # consecutive blocks overlap by the 12-byte tail, like the reference's buffers
-    Lb = stride * nblk + 64
-    soft = np.zeros((S, Lb), np.uint8)
-    for s in range(S):
-        bits = rng.integers(0, 2, frame * nblk + 64, dtype=np.uint8)
-        enc = od.cc_encode(bits)[:Lb]
-        sigma = [10, 25, 40, 60, 90, 1e-3][s]
-        x = np.where(enc > 0, 127 + 35, 127 - 35) + rng.normal(0, sigma, Lb)
-        x = np.clip(np.rint(x), 0, 255).astype(np.uint8)
-        if s == 4:
-            x[rng.random(Lb) < 0.3] = 128   # erasures
-        soft[s] = x
-    soft[5] = rng.integers(0, 256, Lb, dtype=np.uint8)   # pure garbage: exercises the uint8 wrap-around of the metrics
+    stride = 2 * frame
+    soft = od.ccdec_case_softs(frame, S, nblk)
     dec = pkg.CcDecoderBatch(engine, S, frame)
     got = dec.work(torch.from_numpy(soft).cuda(), nblk, stride).cpu().numpy()
     got2 = dec.work(torch.from_numpy(soft).cuda(), nblk, stride).cpu().numpy()   # second call continues the chain
@@ -54,33 +42,6 @@ def test_ccdec_chained_blocks_bit_exact(engine, pkg, frame):
                 assert (g[s, b] == out).all(), (s, rep, b, int((g[s, b] != out).sum()))
         o.orc_ccdec_destroy(h)
     dec.close()
-
-
-def _viterbi_case_streams(nb):
-    """list of (name, soft int8 [nb, 8192])"""
-    rng = np.random.default_rng(77)
-    cases = []
-    for rate in range(5):
-        for drop, rot in ((0, False), (1, True), (3, False)):
-            if rate in (2, 4):
-                drop = 2 * (drop > 0)
-            soft, _ = od.dvbs_tx(rate, nb * 8192, seed=300 + 10 * rate + drop + rot, drop=drop, rot90=rot, sigma=12.0)
-            cases.append((f'rate{rate}_d{drop}_r{int(rot)}', soft.reshape(nb, 8192)))
-    cases.append(('noise', rng.integers(-70, 71, (nb, 8192)).astype(np.int8)))
-    cases.append(('full_range_noise', rng.integers(-128, 128, (nb, 8192)).astype(np.int8)))
-    # marginal SNR: BER hovers around the threshold, watchdog counting matters
-    soft, _ = od.dvbs_tx(0, nb * 8192, seed=501, sigma=30.0)
-    cases.append(('marginal_12', soft.reshape(nb, 8192)))
-    soft, _ = od.dvbs_tx(4, nb * 8192, seed=502, sigma=17.0)
-    cases.append(('marginal_78', soft.reshape(nb, 8192)))
-    # signal, then noise, then a different rate: lock -> watchdog -> IDLE -> re-lock
-    a, _ = od.dvbs_tx(1, nb * 8192, seed=503)
-    b, _ = od.dvbs_tx(3, nb * 8192, seed=504, rot90=True)
-    x = a.reshape(nb, 8192).copy()
-    x[2:5] = rng.integers(-70, 71, (3, 8192))
-    x[5:] = b.reshape(nb, 8192)[5:]
-    cases.append(('relock', x))
-    return cases
 
 
 def _check_viterbi(names, soft, gb, gn, gs, thr, max_outsync):
@@ -99,7 +60,7 @@ def _check_viterbi(names, soft, gb, gn, gs, thr, max_outsync):
 def test_viterbi_dvbs_bit_exact(engine, pkg):
     import torch
     nb = 8
-    cases = _viterbi_case_streams(nb)
+    cases = od.viterbi_case_streams(nb)
     soft = np.stack([c[1] for c in cases])
     vit = pkg.ViterbiBatch(engine, len(cases), 0.15, 3)     # short watchdog so the relock case goes through IDLE again
     d = torch.from_numpy(soft).cuda()

@@ -7,7 +7,9 @@ checked against the fixture before it is fed to the GPU.
 Covers: all 84 LDPC cases over the 21 codes + the stored full vector (bbframe_ldpc.cpp:123-139), the 28 BCH cases + stored vectors
 (bbframe_bch.cpp:380-405), the BB PRBS (bbframe_descramble.cpp:122-143), the bit de-interleaver maps (s2_deinterleaver.cpp:72-136),
 the DVB-S de-puncturers (depunc.h), soft rotation (rotation.cpp), Forney de-interleaver (dvbs_interleaving.h), TS deframer
-(dvbs_ts_deframer.cpp), RS(204,188) wrapper (dvbs_reedsolomon.h over libcorrect) and energy-dispersal removal (dvbs_scrambling.h)."""
+(dvbs_ts_deframer.cpp), RS(204,188) wrapper (dvbs_reedsolomon.h over libcorrect), energy-dispersal removal (dvbs_scrambling.h), the
+self-locking Viterbi decoder (viterbi_all.cpp) with its K=7 block decoder (viterbi/cc_decoder.cpp), and the BBFRAME -> TS / GSE parser
+(dvbs2/bbframe_ts_parser.cpp)."""
 import hashlib
 import json
 import os
@@ -22,6 +24,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 G = json.load(open(os.path.join(HERE, 'golden', 'fec_golden.json')))
 GD = json.load(open(os.path.join(HERE, 'golden', 'dvbs_golden.json')))
+GB = json.load(open(os.path.join(HERE, 'golden', 'bbts_golden.json')))
 
 
 def sha(a):
@@ -244,3 +247,97 @@ def test_energy_dispersal_removal(engine, pkg):
         outs.append(o.reshape(-1))
     tail.close()
     assert sha(np.concatenate(outs)) == c['sha']
+
+
+def test_viterbi_reproduces_reference_outputs(engine, pkg):
+    """Viterbi_DVBS::work as the reference ran it over every golden stream: one ViterbiBatch, two calls of 3 + 5 blocks; per block the
+    output count and the state row (BER bits, state, rate, phase, shift), per stream the digest of the bits written"""
+    import torch
+    import orc_dvbs as od
+    g = GD['viterbi']
+    cases = od.viterbi_case_streams(g['blocks'])
+    assert [c[0] for c in cases] == [c['name'] for c in g['streams']]
+    for (name, soft), c in zip(cases, g['streams']):
+        assert sha(soft) == c['in_sha'], 'input generator drifted; regenerate the goldens'
+    d = torch.from_numpy(np.stack([c[1] for c in cases])).cuda()
+    vit = pkg.ViterbiBatch(engine, len(cases), g['ber_threshold'], g['max_outsync'])
+    parts = [vit.work(d[:, :3].contiguous()), vit.work(d[:, 3:].contiguous())]
+    gb, gn, gs = [torch.cat([parts[0][k], parts[1][k]], 1).cpu().numpy() for k in range(3)]
+    vit.close()
+    for s, c in enumerate(g['streams']):
+        assert gn[s].tolist() == c['counts'], c['name']
+        assert gs[s].tolist() == c['state_rows'], c['name']
+        assert sha(od.viterbi_written_bits(gb[s], gn[s], gs[s])) == c['bits_sha'], c['name']
+
+
+def test_ccdec_reproduces_reference_outputs(engine, pkg):
+    """CCDecoder::work, chained blocks twice over, for every golden frame size: the digest of each decoded block"""
+    import torch
+    import orc_dvbs as od
+    assert [c['frame'] for c in GD['ccdec']] == od.CCDEC_FRAMES
+    for c in GD['ccdec']:
+        frame, S, nblk = c['frame'], c['streams'], c['blocks']
+        soft = od.ccdec_case_softs(frame, S, nblk)
+        assert sha(soft) == c['in_sha'], 'input generator drifted; regenerate the goldens'
+        dec = pkg.CcDecoderBatch(engine, S, frame)
+        got = [dec.work(torch.from_numpy(soft).cuda(), nblk, 2 * frame).cpu().numpy() for _ in range(c['reps'])]
+        dec.close()
+        assert [sha(got[rep][s, b]) for s in range(S) for rep in range(c['reps']) for b in range(nblk)] == c['block_sha'], frame
+
+
+def _bbts_golden_cases():
+    """(golden case, its calls' frames) for kbch 3072 and 14232, cut after 9 frames"""
+    import orc_bbts as B
+    frames = {c[0]: c for c in B.all_parser_cases()}
+    out = []
+    for c in GB['ts_fuzz'] + GB['gse']:
+        if c['kbch'] not in (3072, 14232):
+            continue
+        calls, used = [], 0
+        for fr, want in zip(frames[c['name']][2], c['calls']):
+            used += len(fr)
+            if used > 9:
+                break
+            assert sha(fr) == want['sha256_in'], 'input generator drifted; regenerate the goldens'
+            calls.append((fr, want))
+        out.append((c, calls))
+    return out
+
+
+@pytest.mark.parametrize('variant', ['gse_on_device', 'gse_on_host', 'mode_adaptation_switched_off'])
+def test_bbts_parser_reproduces_reference_outputs(engine, pkg, variant):
+    """BBFrameTSParser::work as the reference ran it, call by call: return value, bytes and the public fields.  A call recorded as
+    undefined in the reference is not fed; a fresh bank follows it, as in the generator."""
+    import orc_bbts as B
+    compared = gse_bytes = 0
+
+    def bank(kbch):
+        p = pkg.BbTsParserBank(engine, 1, kbch, 8)
+        if variant == 'gse_on_host':
+            p.set_gse_path(p.GSE_HOST)
+        if variant == 'mode_adaptation_switched_off':
+            p.set_mode_adaptation(True)
+            p.set_mode_adaptation(False)
+        return p
+
+    for c in GB['ts_round_trip']:
+        if c['kbch'] not in (3072, 14232):
+            continue
+        fr, _ = B.ts_round_trip_frames(c['kbch'], c['dfl_bytes'], c['nframes'])
+        assert sha(fr) == c['sha256_in']
+        p = bank(c['kbch'])
+        out = np.concatenate([p.work(fr[:4]), p.work(fr[4:])])
+        assert sha(out) == c['sha256_out'] and out.size == 188 * c['packets_out']
+    for c, calls in _bbts_golden_cases():
+        p = bank(c['kbch'])
+        for ci, (fr, want) in enumerate(calls):
+            if want['undefined']:
+                p = bank(c['kbch'])
+                continue
+            out = p.work(fr, cap=B.call_cap(fr))
+            st = p.stats()
+            assert out.size == want['n'] and sha(out) == want['sha256_out'], (c['name'], ci)
+            assert [st[k] for k in B.FIELD_KEYS] == want['fields'], (c['name'], ci)
+            compared += 1
+            gse_bytes += out.size if c['name'] in [g['name'] for g in GB['gse']] else 0
+    assert compared > 100 and gse_bytes > 10000       # the cut to 9 frames and the undefined calls left the comparison its substance

@@ -1,6 +1,6 @@
-"""CPU tests of the oracle's BBFRAME -> TS / GSE parser restatement (oracle/bbframe_ts.cpp).  The reference's translation unit
-cannot be compiled here (it needs SDR++ core's <dsp/stream.h>), so these are semantic round trips through this repo's own
-transmitter side: PARITY UNPINNED for this row."""
+"""CPU tests of the oracle's BBFRAME -> TS / GSE parser restatement (oracle/bbframe_ts.cpp): semantic round trips through this repo's
+own transmitter side, and equality with the reference's own BBFrameTSParser (oracle/_ref, built over the stand-in headers of
+oracle/shim) call by call over the TS, fuzz and GSE cases of orc_bbts.py."""
 import numpy as np
 import pytest
 
@@ -149,12 +149,13 @@ def test_output_space_rules():
 
 def test_golden_vectors():
     """tests/golden/bbts_golden.json (generator: tests/golden/make_golden_bbts.py): clean round trips whose expected output is the
-    transmitted packet sequence, and fuzzed sequences anchored on the restatement's own output (regression only: parity unpinned)"""
+    transmitted packet sequence, and fuzzed sequences whose expected output the reference's own parser produced"""
     import hashlib
     import json
     import os
     G = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'bbts_golden.json')))
     sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    cases = {c[0]: c for c in B.all_parser_cases()}
     for c in G['ts_round_trip']:
         rng = np.random.default_rng(c['seed'])
         D = c['dfl_bytes'] if c['dfl_bytes'] is not None else c['kbch'] // 8 - 10
@@ -173,3 +174,50 @@ def test_golden_vectors():
             st = p.stats()
             assert sha(o) == c['sha256_out_per_call'][call]
             assert [st['synched'], st['last_bb_proc'], st['last_gse_crc_err'], st['ts_gs'], int(o.size)] == c['state_per_call'][call]
+    for c in G['ts_fuzz'] + G['gse']:
+        calls = cases[c['name']][2]
+        p = B.OracleBbTs(c['kbch'])
+        assert len(calls) == len(c['calls'])
+        for fr, want in zip(calls, c['calls']):
+            assert sha(fr) == want['sha256_in']
+            n, out = p.work_raw(fr, B.call_cap(fr))
+            st = p.stats()
+            if want['undefined']:
+                p = B.OracleBbTs(c['kbch'])
+                continue
+            assert n == want['n'] and sha(out[:n]) == want['sha256_out']
+            assert [st[k] for k in B.FIELD_KEYS] == want['fields']
+
+
+# ---------------------------------------------------------------- pinned to the compiled reference
+_cases = {c[0]: c for c in B.all_parser_cases()}
+
+
+@pytest.mark.parametrize('name', list(_cases))
+def test_parser_matches_reference(name):
+    """every call of the case: return value, the whole output buffer (pre-filled alike) and every public field"""
+    if B.R() is None:
+        pytest.skip('oracle/_ref not built')
+    _, kbch, calls = _cases[name]
+    recs = B.walk_case(name, kbch, calls)
+    for ci, rec in enumerate(recs):
+        if rec['ub']:
+            continue
+        (n, out, f), (rn, rout, rf) = rec['orc'], rec['ref']
+        assert not rec['left_output'], (name, ci)
+        assert n == rn and f == rf, (name, ci, n, rn, {k: (f[k], rf[k]) for k in f if f[k] != rf[k]})
+        assert np.array_equal(out, rout), (name, ci, int((out != rout).sum()))
+    if not name.startswith(('ts_fuzz', 'gse_fuzz')):
+        assert not any(rec['ub'] for rec in recs), name            # the structured cases stay inside defined behaviour
+    if name.startswith('past_64k'):
+        assert sum(rec['orc'][0] for rec in recs) == 4 + 77 + 4 + 77   # the two PDUs behind the overflow came out
+
+
+def test_parser_pin_covers_what_it_is_for():
+    if B.R() is None:
+        pytest.skip('oracle/_ref not built')
+    recs = {n: B.walk_case(*c) for n, c in _cases.items()}
+    ok = lambda pre: [r for n, rs in recs.items() if n.startswith(pre) for r in rs if not r['ub']]
+    assert len(ok('gse_fuzz')) >= 40 and len(ok('ts_fuzz')) >= 90
+    assert sum(r['ref'][0] for r in ok('gse_fuzz')) > 20000 and any(r['ref'][2]['last_gse_crc_err'] for r in ok('gse_fuzz'))
+    assert any(r['ref'][2]['last_gse_crc_err'] for r in recs['bad_crc_14232']) and not recs['bad_crc_14232'][-1]['ref'][2]['last_gse_crc_err']

@@ -1,7 +1,6 @@
-"""CPU tests of the DVB-S oracle (oracle/dvbs.cpp): pinned against the compiled reference where the reference's sources build
-here (de-puncturers, Forney de-interleaver, soft rotation: header-only / self-contained); the convolutional decoder itself needs
-VOLK headers (absent) so it is checked by encode -> noise -> decode round trips and lock behaviour ("parity unpinned" for
-CCDecoder)."""
+"""CPU tests of the DVB-S oracle (oracle/dvbs.cpp): pinned against the compiled reference (de-puncturers, Forney de-interleaver, soft
+rotation as they are; Viterbi_DVBS, CCDecoder and CCEncoder over the stand-in headers of oracle/shim), plus
+encode -> noise -> decode round trips and lock behaviour."""
 import ctypes as C
 import numpy as np
 import pytest
@@ -193,3 +192,69 @@ def test_forney_and_rotation_golden_vectors():
         x = rng.integers(-128, 128, 512, dtype=np.int8)
         o.orc_rotate_soft(P(x), 512, c['phase'], c['iqswap'])
         assert _sha(x) == c['sha']
+
+
+# ---------------------------------------------------------------- Viterbi_DVBS / CCDecoder / CCEncoder pinned to the compiled reference
+def _ref_inner():
+    r = od.R()
+    if r is None:
+        pytest.skip('oracle/_ref not built')
+    return r
+
+
+_streams = {}
+
+
+def _viterbi_streams():
+    if not _streams:
+        _streams.update(od.viterbi_case_streams(8))
+    return _streams
+
+
+@pytest.mark.parametrize('thr,max_outsync', [(0.15, 3), (0.15, 20)])
+def test_viterbi_dvbs_matches_reference(thr, max_outsync):
+    """Viterbi_DVBS::work over 8 blocks of 8192 softs per stream: per block the output count, state / rate / phase / shift, the BER as
+    float bits and the whole output buffer (pre-filled alike on both sides: rate 5/6 leaves bits [6799, count) unwritten)"""
+    _ref_inner()
+    for name, soft in _viterbi_streams().items():
+        eb, en, es = od.RefViterbi(thr, max_outsync).work(soft, fill=0xA5)
+        ob, on, os_ = od.OracleViterbi(thr, max_outsync).work(soft, fill=0xA5)
+        assert (on == en).all(), (name, on, en)
+        assert (os_ == es).all(), (name, os_, es)
+        assert (ob == eb).all(), (name, np.argwhere(ob != eb)[:4])
+    # the scenario did what it is for: every rate locked, both phases, non-zero shifts, the relock stream fell back to IDLE
+    seen = np.concatenate([od.OracleViterbi(thr, max_outsync).work(s)[2] for s in _viterbi_streams().values()])
+    locked = seen[seen[:, 1] == 1]
+    assert set(locked[:, 2]) == set(range(5)) and set(locked[:, 3]) == {0, 1} and (locked[:, 4] > 1).any() and (seen[:, 1] == 0).any()
+
+
+@pytest.mark.parametrize('frame', od.CCDEC_FRAMES)
+def test_ccdec_chained_blocks_match_reference(frame):
+    """CCDecoder::work, 4 chained blocks twice over, six input kinds (noise levels, erasures, garbage)"""
+    o, r = od.L(), _ref_inner()
+    soft = od.ccdec_case_softs(frame)
+    for s in range(soft.shape[0]):
+        ho, hr = VP(o.orc_ccdec_create(frame)), VP(r.ref_ccdec_create(frame))
+        for rep in range(2):
+            for b in range(4):
+                x = np.ascontiguousarray(soft[s, 2 * frame * b:])
+                a = np.full(frame + 8, 0xA5, np.uint8); e = a.copy()
+                o.orc_ccdec_work(ho, P(x), P(a)); r.ref_ccdec_work(hr, P(x.copy()), P(e))
+                assert (a == e).all(), (s, rep, b, int((a != e).sum()))
+        o.orc_ccdec_destroy(ho); r.ref_ccdec_destroy(hr)
+
+
+def test_ccenc_matches_reference():
+    """CCEncoder::work on random bits (values 0..255: only bit 0 counts), the register carried across calls"""
+    o, r = od.L(), _ref_inner()
+    rng = np.random.default_rng(9)
+    for frame in (1, 7, 1024, 1792):
+        ho, hr = VP(o.orc_ccenc_create(frame)), VP(r.ref_ccenc_create(frame))
+        for rep in range(3):
+            x = rng.integers(0, 256 if rep == 2 else 2, frame, dtype=np.uint8)
+            a = np.full(2 * frame + 8, 0xA5, np.uint8); e = a.copy()
+            o.orc_ccenc_work(ho, P(x), P(a)); r.ref_ccenc_work(hr, P(x.copy()), P(e))
+            assert (a == e).all(), (frame, rep)
+            if rep == 0:
+                assert (od.cc_encode(x) == e[:2 * frame]).all()
+        o.orc_ccenc_destroy(ho); r.ref_ccenc_destroy(hr)
