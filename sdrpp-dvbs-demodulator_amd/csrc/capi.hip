@@ -7,7 +7,6 @@
 #include <cstdlib>
 
 using namespace s2;
-namespace s2 { extern unsigned long long* g_ldpc_prof; }
 
 namespace s2 {
 std::atomic<long long> g_kernel_launches{0};
@@ -239,40 +238,35 @@ namespace s2 {
 // the dynamic work counter of a decoder launch, in a block of its own between the message records and the sign scratch
 struct alignas(256) LdpcWorkCounter { unsigned int v[64]; };
 
+// which decoder serves a batch of the code (== dvbs2gpu_ldpc_decoder_form), and per form: the workgroups of the launch, the frame slots of each, the message records of a slot
+enum class LdpcForm : int { lane = 0, wave = 1, split = 2 };
+static LdpcForm ldpc_form(const dvbs2gpu_ctx* ctx, const LdpcDeviceCode& C) { return C.use_wave ? LdpcForm::wave : (C.use_split && ctx->ldpc_split) ? LdpcForm::split : LdpcForm::lane; }
+struct LdpcGeometry { int grid, fpb; size_t rec_bytes; };
+static LdpcGeometry ldpc_geometry(const dvbs2gpu_ctx* ctx, const LdpcDeviceCode& C, LdpcForm form, int nframes) {
+    if (form == LdpcForm::wave) {
+        // wave-per-frame decoder: one 64-thread workgroup per frame slot, as many as the LDS of the device holds at once
+        const int per_cu = (int)((size_t)(160 * 1024 - LDPC_WAVE_LDS_RESERVE) / ldpc_wave_lds_bytes(C));
+        return {std::min(ctx->num_cus * std::min(std::max(per_cu, 1), 16), nframes), 1, ldpc_wave_msg_bytes_per_frame(C)};
+    }
+    // half-row decoder: one frame per workgroup, frames beyond the first wave of workgroups claimed through the work counter
+    if (form == LdpcForm::split) return {std::min(ctx->num_cus * C.split_blocks_per_cu, nframes), 1, ldpc_split_msg_bytes_per_block(C)};
+    // workgroups hold 2 frame slots, or 1 for batches smaller than the device (ldpc_kernel.hip)
+    const int fpb = ldpc_frames_per_block(nframes, ctx->num_cus);
+    return {std::min(ctx->num_cus * C.blocks_per_cu, (nframes + fpb - 1) / fpb), fpb, (size_t)C.R * C.rec_dwords * sizeof(uint32_t)};
+}
+
 static int ldpc_run(dvbs2gpu_ctx* ctx, const FecParams& f, const int8_t* d_llr, int nframes, int max_trials, int force,
                     uint8_t* d_hard, int hard_stride, int8_t* d_post, int32_t* d_trials, hipStream_t st, FecWs& W) {
     LdpcDeviceCode* C;
     int rc = get_ldpc(ctx, f.code_index, &C);
     if (rc) return rc;
-    // per decoder variant: the workgroups of the launch, the frame slots of each and the message records of a slot
-    const bool wave = C->use_wave, split = !wave && C->use_split && ctx->ldpc_split;
-    int grid, fpb = 1;
-    size_t rec_bytes;
-    if (wave) {
-        // wave-per-frame decoder: one 64-thread workgroup per frame slot, as many as the LDS of the device holds at once
-        const size_t lds = ldpc_wave_lds_bytes(*C);
-        int per_cu = (int)((size_t)(160 * 1024 - LDPC_WAVE_LDS_RESERVE) / lds);
-        per_cu = per_cu < 1 ? 1 : (per_cu > 16 ? 16 : per_cu);
-        grid = std::min(ctx->num_cus * per_cu, nframes);
-        rec_bytes = ldpc_wave_msg_bytes_per_frame(*C);
-    } else if (split) {
-        // half-row decoder: one frame per workgroup, frames beyond the first wave of workgroups claimed through the work counter
-        grid = std::min(ctx->num_cus * C->split_blocks_per_cu, nframes);
-        rec_bytes = ldpc_split_msg_bytes_per_block(*C);
-    } else {
-        // workgroups hold 2 frame slots, or 1 for batches smaller than the device (ldpc_kernel.hip)
-        fpb = ldpc_frames_per_block(nframes, ctx->num_cus);
-        grid = std::min(ctx->num_cus * C->blocks_per_cu, (nframes + fpb - 1) / fpb);
-        rec_bytes = (size_t)C->R * C->rec_dwords * sizeof(uint32_t);
-    }
-    const size_t slots = (size_t)grid * fpb;
+    const LdpcForm form = ldpc_form(ctx, *C);
+    const LdpcGeometry G = ldpc_geometry(ctx, *C, form, nframes);
+    const size_t slots = (size_t)G.grid * G.fpb;
     ScratchLayout L;        // W.msg: message records | work counter | bit-packed signs for the syndrome check
-    const auto l_msg = L.add<uint8_t>(slots * rec_bytes); const auto l_counter = L.add<LdpcWorkCounter>(1);
+    const auto l_msg = L.add<uint8_t>(slots * G.rec_bytes); const auto l_counter = L.add<LdpcWorkCounter>(1);
     const auto l_sgn = L.add<uint32_t>(slots * ldpc_sign_ws_bytes_per_slot() / sizeof(uint32_t));
     if ((rc = W.msg.ensure(L.bytes()))) return rc;
-    uint8_t* msg = l_msg(W.msg.p);
-    unsigned int* counter = l_counter(W.msg.p)->v;
-    uint32_t* sgn = l_sgn(W.msg.p);
     if (!d_trials) {
         if ((rc = W.misc.ensure((size_t)nframes * 2 * sizeof(int32_t)))) return rc;
         d_trials = (int32_t*)W.misc.p;
@@ -281,13 +275,11 @@ static int ldpc_run(dvbs2gpu_ctx* ctx, const FecParams& f, const int8_t* d_llr, 
         if ((rc = W.hard.ensure((size_t)nframes * (f.K / 8)))) return rc;
         d_hard = (uint8_t*)W.hard.p; hard_stride = f.K / 8;
     }
-    if (wave)
-        HIP_TRY(ldpc_wave_decode_launch(*C, d_llr, nframes, max_trials, force, d_hard, hard_stride, d_post, d_trials, msg, grid, st, counter, sgn));
-    else if (!split)
-        HIP_TRY(ldpc_decode_launch(*C, d_llr, nframes, max_trials, force, d_hard, hard_stride, d_post, d_trials, (uint32_t*)msg, grid, fpb, st, counter, sgn));
-    else if (nframes > 0)
-        HIP_TRY(ldpc_split_decode_launch(*C, d_llr, nframes, max_trials, force, d_hard, hard_stride, d_post, d_trials, (uint32_t*)msg, grid, st, counter, sgn,
-                                         ctx->ldpc_split_fail_attempts));
+    const LdpcJob J = {d_llr, nframes, max_trials, force, d_hard, hard_stride, d_post, d_trials, (uint32_t*)l_msg(W.msg.p), l_sgn(W.msg.p), l_counter(W.msg.p)->v,
+                       G.grid, G.fpb, ctx->ldpc_split_fail_attempts, st};
+    if (form == LdpcForm::wave) HIP_TRY(ldpc_wave_decode_launch(*C, J));
+    else if (form == LdpcForm::lane) HIP_TRY(ldpc_decode_launch(*C, J));
+    else if (nframes > 0) HIP_TRY(ldpc_split_decode_launch(*C, J));
     return 0;
 }
 }  // namespace s2
@@ -585,7 +577,7 @@ int dvbs2gpu_ldpc_plan_info(dvbs2gpu_ctx* ctx, int rate, int shortframes, int32_
     LdpcPlan P = build_ldpc_plan(f.code_index);
     out8[0] = C->q; out8[1] = C->max_deg; out8[2] = C->rec_dwords; out8[3] = P.sum_depth;
     out8[4] = C->blocks_per_cu; out8[5] = ctx->num_cus; out8[6] = C->edges; out8[7] = P.conflict_layers;
-    if (C->use_split && ctx->ldpc_split) { out8[2] = ldpc_split_plan_rec_dwords(P.max_deg); out8[4] = C->split_blocks_per_cu; }
+    if (ldpc_form(ctx, *C) == LdpcForm::split) { out8[2] = ldpc_split_plan_rec_dwords(P.max_deg); out8[4] = C->split_blocks_per_cu; }
     return 0;
 }
 
@@ -597,7 +589,7 @@ int dvbs2gpu_ldpc_decoder_form(dvbs2gpu_ctx* ctx, int rate, int shortframes) {
     LdpcDeviceCode* C;
     int rc = get_ldpc(ctx, f.code_index, &C);
     if (rc) return rc;
-    return C->use_wave ? 1 : (C->use_split && ctx->ldpc_split) ? 2 : 0;
+    return (int)ldpc_form(ctx, *C);
 }
 
 int dvbs2gpu_ldpc_decode_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, const int8_t* d_llr, int nframes, int max_trials,

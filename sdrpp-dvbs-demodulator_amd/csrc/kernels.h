@@ -22,7 +22,7 @@ struct LdpcDeviceCode {
     uint32_t* d_wave_lanec = nullptr;
     uint16_t* d_wave_steps = nullptr;
     uint32_t* d_wave_layer_end = nullptr;
-    bool use_wave = false;          // which of the two decoders a batch of this code goes to
+    bool use_wave = false;          // short frames: the wave-per-frame decoder serves this code (capi.hip: ldpc_form)
     // half-row form (ldpc_split_plan.h / ldpc_split_kernel.hip): two lanes per row, one frame per workgroup
     struct LdpcSplitLayer* d_split_layers = nullptr;
     uint32_t* d_split_atab = nullptr;
@@ -30,22 +30,35 @@ struct LdpcDeviceCode {
     bool use_split = false;
 };
 
+// One decoder launch: what the caller decides.  The code's own figures come from the LdpcDeviceCode (ldpc_dev_common.h: ldpc_kernel_args).
+struct LdpcJob {
+    const int8_t* llr;
+    int nframes, max_trials, force;
+    uint8_t* hard;
+    int hard_stride;
+    int8_t* post;
+    int32_t* trials;
+    uint32_t* msg_ws;
+    uint32_t* sgn_ws;
+    unsigned int* work_ctr;
+    int grid, fpb;              // workgroups; frame slots of each (lane-per-row decoder: 1 or 2)
+    int dbg;                    // context option ldpc_split_fail_attempts (half-row decoder)
+    hipStream_t stream;
+};
+extern unsigned long long* g_ldpc_prof;   // (ldpc_kernel.hip; set by tools/ldpc_prof.py through dvbs2gpu_debug_set_prof, PROF builds)
+
 int ldpc_blocks_per_cu(int max_deg, int irregular, int N);
 int ldpc_frames_per_block(int nframes, int num_cus);
-hipError_t ldpc_decode_launch(const LdpcDeviceCode& C, const int8_t* llr, int nframes, int max_trials, int force,
-                              uint8_t* hard, int hard_stride, int8_t* post, int32_t* trials, uint32_t* msg_ws, int grid,
-                              int fpb, hipStream_t stream, unsigned int* work_ctr, uint32_t* sgn_ws);
+hipError_t ldpc_decode_launch(const LdpcDeviceCode& C, const LdpcJob& J);
 size_t ldpc_sign_ws_bytes_per_slot();
 bool ldpc_split_supported(int max_deg);
 bool ldpc_split_noprev_shared(int max_deg);      // kernels whose layers with shared bits handle the row without a previous parity bit
 int ldpc_split_blocks_per_cu(int max_deg, int N);
 size_t ldpc_split_msg_bytes_per_block(const LdpcDeviceCode& C);
-hipError_t ldpc_split_decode_launch(const LdpcDeviceCode& C, const int8_t* llr, int nframes, int max_trials, int force, uint8_t* hard, int hard_stride,
-                                    int8_t* post, int32_t* trials, uint32_t* msg_ws, int grid, hipStream_t stream, unsigned int* work_ctr, uint32_t* sgn_ws, int dbg = 0);
+hipError_t ldpc_split_decode_launch(const LdpcDeviceCode& C, const LdpcJob& J);
 size_t ldpc_wave_msg_bytes_per_frame(const LdpcDeviceCode& C);
 size_t ldpc_wave_lds_bytes(const LdpcDeviceCode& C);
-hipError_t ldpc_wave_decode_launch(const LdpcDeviceCode& C, const int8_t* llr, int nframes, int max_trials, int force, uint8_t* hard, int hard_stride,
-                                   int8_t* post, int32_t* trials, uint8_t* msg_ws, int grid, hipStream_t stream, unsigned int* work_ctr, uint32_t* sgn_ws);
+hipError_t ldpc_wave_decode_launch(const LdpcDeviceCode& C, const LdpcJob& J);
 
 // Device-resident tables of one BCH family (GF(2^m), t).
 struct BchDeviceCode {

@@ -1,10 +1,59 @@
-// Device helpers shared by the LDPC decoder kernels (ldpc_kernel.hip: lane = row, workgroup = two frames; ldpc_wave_kernel.hip: wave =
-// frame): the int8 rules of the reference's SIMD lanes and the bit-vector form of its syndrome check.
+// What the three LDPC decoder kernels share (ldpc_kernel.hip: lane = row; ldpc_split_kernel.hip: two lanes = row; ldpc_wave_kernel.hip: wave = frame), i.e. everything but
+// the layout of a sweep over lanes: the launch arguments and how a launch is made, the int8 rules of the reference's SIMD lanes, the bit-vector form of its syndrome check,
+// and a frame's way in and out (load, verdict after a check, outputs).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "kernels.h"
 
 namespace s2 {
+
+// Code tables are separate `const T* __restrict__` kernel parameters (not struct members) so that hipcc can
+// prove them invariant and fetch the wave-uniform layer/link descriptors with scalar loads (s_load_*).
+struct LdpcKernelArgs {
+    const int8_t* llr;     // [nframes][N]
+    uint8_t* hard;         // [nframes][hard_stride] packed hard decisions of bits [0,K), MSB first
+    int8_t* post;          // optional [nframes][N] posteriors (reference layout), may be null
+    int32_t* trials;       // [nframes]
+    uint32_t* msg_ws;      // [gridDim.x * slots][message records of a slot: LdpcGeometry::rec_bytes]
+    int nframes, N, K, R, q;
+    int pent_base;         // offset of the pair-format link table inside ents[] (ldpc_plan.h); half-row decoder: message words per workgroup
+    int synd_base;         // offset of the syndrome-check table inside ents[] (ldpc_plan.h)
+    int max_trials, force;
+    int hard_stride;
+    int dbg;                    // tests only (context option ldpc_split_fail_attempts): 1 = every attempt of the half-row decoder's layers with shared bits is made to fail (the fall-back path)
+    uint32_t* sgn_ws;           // [gridDim.x * slots][SGN_WS_DWORDS]: bit-packed posterior signs for the syndrome check
+    unsigned int* work_ctr;     // optional: frames beyond the first gridDim.x * slots are claimed dynamically (workgroups slowed by
+                                // co-resident kernels of the pipelined mode then simply take fewer frames)
+    unsigned long long* prof;   // development aid (-DLDPC_PROF builds only): per-wave phase cycle sums of workgroup 0
+};
+
+// ---- host side of a launch (kernels.h: LdpcJob): the arguments, the dynamic-LDS attribute + launch, the occupancy query
+inline hipError_t ldpc_kernel_args(const LdpcDeviceCode& C, const LdpcJob& J, LdpcKernelArgs* A) {
+    if (J.work_ctr) {
+        hipError_t e = hipMemsetAsync(J.work_ctr, 0, sizeof(unsigned int), J.stream);
+        if (e != hipSuccess) return e;
+    }
+    A->llr = J.llr; A->hard = J.hard; A->post = J.post; A->trials = J.trials; A->msg_ws = J.msg_ws;
+    A->nframes = J.nframes; A->N = C.N; A->K = C.K; A->R = C.R; A->q = C.q; A->pent_base = C.pent_base; A->synd_base = C.synd_base;
+    A->max_trials = J.max_trials; A->force = J.force; A->hard_stride = J.hard_stride; A->dbg = J.dbg;
+    A->sgn_ws = J.sgn_ws; A->work_ctr = J.work_ctr; A->prof = g_ldpc_prof;
+    return hipSuccess;
+}
+template <typename Kern, typename... KArgs>
+hipError_t ldpc_launch(Kern kern, int grid, int threads, size_t lds, hipStream_t stream, const KArgs&... args) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, stream, args...);
+    return hipGetLastError();
+}
+template <typename Kern>
+int ldpc_occupancy(Kern kern, int threads, size_t lds) {
+    int nb = 0;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, lds) != hipSuccess) nb = 1;
+    return nb < 1 ? 1 : nb;
+}
 
 __device__ __forceinline__ int med3i(int a, int lo, int hi) { return min(max(a, lo), hi); }  // folds to v_med3_i32 for lo <= hi
 __device__ __forceinline__ int clamp8(int v) { return med3i(v, -128, 127); }
@@ -107,5 +156,50 @@ __device__ __forceinline__ bool syndromes_bad(int q, int synd_base, const uint32
     return bad;
 }
 
+// ---- a frame's way in and out.  T = threads of a frame slot (LDPC_TPS, LDPC_SPLIT_T, 64), t = the thread's index within the slot.
+// information-bit LLRs: straight copy (K is a multiple of 8); parity LLRs: pty[360*i + jj] = llr[K + q*jj + i]   (layered_decoder.hh:124-126)
+template <int T>
+__device__ __forceinline__ void ldpc_frame_load(int8_t* __restrict__ post, const int8_t* __restrict__ src, int K, int R, int q, int t) {
+    for (int i = t; i < K / 8; i += T) reinterpret_cast<uint2*>(post)[i] = reinterpret_cast<const uint2*>(src)[i];
+    for (int c = t; c < R; c += T) {
+        const int jj = c / q, i = c - jj * q;
+        post[K + 360 * i + jj] = src[K + c];
+    }
+}
+// what a syndrome check decides (`any`: some row is bad): in forced mode the one check after the last sweep, else converged | exhausted | go on
+__device__ __forceinline__ bool ldpc_verdict(int force, bool any, int it, int max_trials, int& ret) {
+    if (force) { ret = any ? -1 : max_trials; return true; }
+    if (!any) { ret = it; return true; }
+    if (it == max_trials) { ret = -1; return true; }
+    return false;
+}
+// trials[f]; hard decisions of [0,K): 64 bits per wave step via ballot, MSB-first bytes (module_dvbs2_demod.cpp:357-360); optionally the posteriors, reference layout
+template <int T>
+__device__ __forceinline__ void ldpc_frame_store(const int8_t* __restrict__ post, int f, int ret, int32_t* trials, uint8_t* hard, int hard_stride, int8_t* post_out,
+                                                 int N, int K, int R, int q, int t, int wave) {
+    if (t == 0) trials[f] = ret;
+    uint8_t* __restrict__ hd = hard + (size_t)f * hard_stride;
+    const int lane = t & 63;
+    for (int base = wave * 64; base < K; base += T) {
+        const int idx = base + lane;
+        const int neg = (idx < K) ? (post[idx] < 0) : 0;
+        unsigned long long b = __ballot(neg);
+        b = __builtin_bswap64(__brevll(b));
+        if (lane == 0) {
+            const int nbytes = min(8, (K - base) / 8);
+            // (K / 8 is odd for some codes, and a caller's stride need not be a multiple of 8: the 8-byte store only where it is aligned)
+            if (nbytes == 8 && ((uintptr_t)(hd + base / 8) & 7u) == 0) *reinterpret_cast<uint2*>(hd + base / 8) = make_uint2((uint32_t)b, (uint32_t)(b >> 32));
+            else for (int n = 0; n < nbytes; ++n) hd[base / 8 + n] = (uint8_t)(b >> (8 * n));
+        }
+    }
+    if (post_out) {
+        int8_t* __restrict__ dst = post_out + (size_t)f * N;
+        for (int i = t; i < K / 8; i += T) reinterpret_cast<uint2*>(dst)[i] = reinterpret_cast<const uint2*>(post)[i];
+        for (int c = t; c < R; c += T) {
+            const int jj = c / q, i = c - jj * q;
+            dst[K + c] = post[K + 360 * i + jj];
+        }
+    }
+}
 
 }  // namespace s2

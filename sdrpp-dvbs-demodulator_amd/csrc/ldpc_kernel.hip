@@ -594,14 +594,7 @@ __global__ __launch_bounds__(LDPC_FPB * LDPC_TPS) __attribute__((amdgpu_waves_pe
         const bool valid = f < A.nframes;
         const bool lane_ok = (j < 360) && valid;
         if (valid) {
-            const int8_t* __restrict__ src = A.llr + (size_t)f * N;
-            // information-bit LLRs: straight copy (K is a multiple of 8)
-            for (int i = j; i < K / 8; i += LDPC_TPS) reinterpret_cast<uint2*>(post)[i] = reinterpret_cast<const uint2*>(src)[i];
-            // parity LLRs: pty[360*i + jj] = llr[K + q*jj + i]   (layered_decoder.hh:124-126)
-            for (int c = j; c < R; c += LDPC_TPS) {
-                int jj = c / q, i = c - jj * q;
-                post[K + 360 * i + jj] = src[K + c];
-            }
+            ldpc_frame_load<LDPC_TPS>(post, A.llr + (size_t)f * N, K, R, q, j);
             if constexpr (ldpc_diet<MAXDEG, IRREG>()) {
                 // the first sweep reads all-zero messages: this lane's records are cleared here, so that a sweep fetches them without asking which sweep it is
                 if (j < 360 && !(LDPC_EXP & 1)) {
@@ -632,10 +625,8 @@ __global__ __launch_bounds__(LDPC_FPB * LDPC_TPS) __attribute__((amdgpu_waves_pe
             }
             lds_barrier();
             if (check) {
-                int any = s_flag[fs][0] | s_flag[fs][1] | s_flag[fs][2] | s_flag[fs][3] | s_flag[fs][4] | s_flag[fs][5];
-                if (A.force) { ret = any ? -1 : A.max_trials; done = true; }
-                else if (!any) { ret = it; done = true; }
-                else if (it == A.max_trials) { ret = -1; done = true; }
+                const int any = s_flag[fs][0] | s_flag[fs][1] | s_flag[fs][2] | s_flag[fs][3] | s_flag[fs][4] | s_flag[fs][5];
+                done = ldpc_verdict(A.force, any != 0, it, A.max_trials, ret);
             }
             if (j == 0) s_done[fs] = done;
             lds_barrier();
@@ -750,32 +741,7 @@ __global__ __launch_bounds__(LDPC_FPB * LDPC_TPS) __attribute__((amdgpu_waves_pe
             ++trip;
         }
 
-        // ---- outputs
-        if (valid) {
-            if (j == 0) A.trials[f] = ret;
-            // hard decisions of [0,K): 64 bits per wave step via ballot, MSB-first bytes (module_dvbs2_demod.cpp:357-360)
-            uint8_t* __restrict__ hd = A.hard + (size_t)f * A.hard_stride;
-            const int lane = j & 63, wave = j >> 6;
-            for (int base = wave * 64; base < K; base += 6 * 64) {
-                int idx = base + lane;
-                int neg = (idx < K) ? (post[idx] < 0) : 0;
-                unsigned long long b = __ballot(neg);
-                b = __builtin_bswap64(__brevll(b));
-                if (lane == 0) {
-                    int nbytes = min(8, (K - base) / 8);
-                    if (nbytes == 8 && ((uintptr_t)(hd + base / 8) & 7u) == 0) *reinterpret_cast<uint2*>(hd + base / 8) = make_uint2((uint32_t)b, (uint32_t)(b >> 32));   // (a caller's stride need not be a multiple of 8)
-                    else for (int n = 0; n < nbytes; ++n) hd[base / 8 + n] = (uint8_t)(b >> (8 * n));
-                }
-            }
-            if (A.post) {
-                int8_t* __restrict__ dst = A.post + (size_t)f * N;
-                for (int i = j; i < K / 8; i += LDPC_TPS) reinterpret_cast<uint2*>(dst)[i] = reinterpret_cast<const uint2*>(post)[i];
-                for (int c = j; c < R; c += LDPC_TPS) {
-                    int jj = c / q, i = c - jj * q;
-                    dst[K + c] = post[K + 360 * i + jj];
-                }
-            }
-        }
+        if (valid) ldpc_frame_store<LDPC_TPS>(post, f, ret, A.trials, A.hard, A.hard_stride, A.post, N, K, R, q, j, j >> 6);
         if (A.work_ctr) {
             if (threadIdx.x == 0) s_next = (int)(gridDim.x * LDPC_FPB + atomicAdd(A.work_ctr, (unsigned int)LDPC_FPB));
             lds_barrier();
@@ -789,30 +755,13 @@ __global__ __launch_bounds__(LDPC_FPB * LDPC_TPS) __attribute__((amdgpu_waves_pe
 
 template <int MAXDEG, int REC, bool IRREG>
 static hipError_t launch_ldpc(const LdpcDeviceCode& C, const LdpcKernelArgs& A, int grid, int fpb, hipStream_t stream) {
-    size_t lds = (size_t)((A.N + 15) / 16) * 16 * fpb;
-    if (fpb == 1) {
-        auto kern = ldpc_decode_kernel<MAXDEG, REC, IRREG, 1>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(LDPC_TPS), lds, stream, C.d_layers, C.d_ents, C.d_rows, C.d_atab, A);
-    } else {
-        auto kern = ldpc_decode_kernel<MAXDEG, REC, IRREG, 2>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(2 * LDPC_TPS), lds, stream, C.d_layers, C.d_ents, C.d_rows, C.d_atab, A);
-    }
-    return hipGetLastError();
+    const size_t lds = (size_t)((A.N + 15) / 16) * 16 * fpb;
+    if (fpb == 1) return ldpc_launch(ldpc_decode_kernel<MAXDEG, REC, IRREG, 1>, grid, LDPC_TPS, lds, stream, C.d_layers, C.d_ents, C.d_rows, C.d_atab, A);
+    return ldpc_launch(ldpc_decode_kernel<MAXDEG, REC, IRREG, 2>, grid, 2 * LDPC_TPS, lds, stream, C.d_layers, C.d_ents, C.d_rows, C.d_atab, A);
 }
 
 template <int MAXDEG, int REC, bool IRREG>
-static int occupancy_ldpc(int N) {
-    int nb = 0;
-    size_t lds = (size_t)((N + 15) / 16) * 16 * 2;
-    auto kern = ldpc_decode_kernel<MAXDEG, REC, IRREG, 2>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 2 * LDPC_TPS, lds) != hipSuccess) nb = 1;
-    return nb < 1 ? 1 : nb;
-}
+static int occupancy_ldpc(int N) { return ldpc_occupancy(ldpc_decode_kernel<MAXDEG, REC, IRREG, 2>, 2 * LDPC_TPS, (size_t)((N + 15) / 16) * 16 * 2); }
 
 // (max_deg, irregular) pairs that occur in DVB-S2: regular B1..B11, C2, C3, C5, C6, C10; irregular C1 C4 C7 C8 C9
 #define LDPC_DISPATCH(FN, ...)                                                             \
@@ -852,22 +801,12 @@ int ldpc_blocks_per_cu(int max_deg, int irregular, int N) {
 
 unsigned long long* g_ldpc_prof = nullptr;   // set by tools/ldpc_prof.py through dvbs2gpu_debug_set_prof (PROF builds)
 
-hipError_t ldpc_decode_launch(const LdpcDeviceCode& C, const int8_t* llr, int nframes, int max_trials, int force,
-                              uint8_t* hard, int hard_stride, int8_t* post, int32_t* trials, uint32_t* msg_ws, int grid, int fpb,
-                              hipStream_t stream, unsigned int* work_ctr, uint32_t* sgn_ws) {
+hipError_t ldpc_decode_launch(const LdpcDeviceCode& C, const LdpcJob& J) {
     LdpcKernelArgs A;
-    A.work_ctr = work_ctr;
-    A.sgn_ws = sgn_ws;
-    if (work_ctr) {
-        hipError_t e = hipMemsetAsync(work_ctr, 0, sizeof(unsigned int), stream);
-        if (e != hipSuccess) return e;
-    }
-    A.llr = llr; A.hard = hard; A.post = post; A.trials = trials; A.msg_ws = msg_ws;
-    A.nframes = nframes; A.N = C.N; A.K = C.K; A.R = C.R; A.q = C.q; A.pent_base = C.pent_base; A.synd_base = C.synd_base;
-    A.max_trials = max_trials; A.force = force; A.hard_stride = hard_stride; A.dbg = 0;
-    A.prof = g_ldpc_prof;
+    hipError_t e = ldpc_kernel_args(C, J, &A);
+    if (e != hipSuccess) return e;
     const int max_deg = C.max_deg, irregular = C.irregular;
-    LDPC_DISPATCH(launch_ldpc, C, A, grid, fpb, stream)
+    LDPC_DISPATCH(launch_ldpc, C, A, J.grid, J.fpb, J.stream)
     return hipErrorInvalidValue;
 }
 

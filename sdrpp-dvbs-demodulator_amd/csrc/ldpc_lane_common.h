@@ -1,6 +1,6 @@
 // Device helpers shared by the lane-per-row LDPC decoders (ldpc_kernel.hip: one lane = one row, a workgroup = two frames;
-// ldpc_split_kernel.hip: two lanes = one row, a workgroup = one frame): kernel arguments, LDS byte traffic issued by hand, the
-// message records and the chain walk's hand-off records.
+// ldpc_split_kernel.hip: two lanes = one row, a workgroup = one frame): the kernel-argument structure read section by section, LDS byte
+// traffic issued by hand, the message records and the chain walk's hand-off records.  (Launch arguments, frame load / output: ldpc_dev_common.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,26 +11,6 @@
 #include "ldpc_dev_common.h"
 
 namespace s2 {
-
-// Code tables are separate `const T* __restrict__` kernel parameters (not struct members) so that hipcc can
-// prove them invariant and fetch the wave-uniform layer/link descriptors with scalar loads (s_load_*).
-struct LdpcKernelArgs {
-    const int8_t* llr;     // [nframes][N]
-    uint8_t* hard;         // [nframes][hard_stride] packed hard decisions of bits [0,K), MSB first
-    int8_t* post;          // optional [nframes][N] posteriors (reference layout), may be null
-    int32_t* trials;       // [nframes]
-    uint32_t* msg_ws;      // [gridDim.x][R][REC]
-    int nframes, N, K, R, q;
-    int pent_base;         // offset of the pair-format link table inside ents[] (ldpc_plan.h)
-    int synd_base;         // offset of the syndrome-check table inside ents[] (ldpc_plan.h)
-    int max_trials, force;
-    int hard_stride;
-    int dbg;                    // tests only (context option ldpc_split_fail_attempts): 1 = every attempt of the half-row decoder's layers with shared bits is made to fail (the fall-back path)
-    uint32_t* sgn_ws;           // [gridDim.x * slots][SGN_WS_DWORDS]: bit-packed posterior signs for the syndrome check
-    unsigned int* work_ctr;     // optional: frames beyond the first gridDim.x*2 are claimed dynamically (workgroups slowed by
-                                // co-resident kernels of the pipelined mode then simply take fewer frames)
-    unsigned long long* prof;   // development aid (-DLDPC_PROF builds only): per-wave phase cycle sums of workgroup 0
-};
 
 // What a decoder kernel is told arrives in ONE structure, read from the kernel-argument segment through a pointer the compiler cannot see through, afresh in every section
 // of the kernel (frame load | syndrome check + sweep | output): kept in scalar registers for the whole kernel, the two dozen values only the frame load and the output need

@@ -668,12 +668,7 @@ __global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(8)
             const int8_t* __restrict__ src = P->A.llr + (size_t)f * N;
             int t = threadIdx.x;                  // (an opaque copy, as in the sweep: the strided indices of these loops, hoisted out of the frame loop, would stay live through every layer)
             asm volatile("" : "+v"(t));
-            for (int i = t; i < K / 8; i += T) reinterpret_cast<uint2*>(post)[i] = reinterpret_cast<const uint2*>(src)[i];
-            // parity LLRs: pty[360*i + jj] = llr[K + q*jj + i]   (layered_decoder.hh:124-126)
-            for (int c = t; c < R; c += T) {
-                int jj = c / q, i = c - jj * q;
-                post[K + 360 * i + jj] = src[K + c];
-            }
+            ldpc_frame_load<T>(post, src, K, R, q, t);
             // the first sweep reads all-zero messages: the records are cleared here, so that a sweep fetches them without asking which sweep it is
             for (uint32_t o = (uint32_t)t; o < (uint32_t)P->A.pent_base; o += T) msg[o] = 0;
             if (t < 2) reinterpret_cast<uint32_t*>(lds_all + ((N + LDPC_SPLIT_SCRATCH + 15) & ~15) + 8 * 360)[t] = 0;      // the chain layers' verdict words
@@ -726,6 +721,8 @@ __global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(8)
 #if defined(LDPC_PROF) && LDPC_PROF == 5
                 if (A.prof && blockIdx.x == 0 && t == 0) { const unsigned long long tc4 = clock64(); A.prof[400] += tc1 - tc0; A.prof[401] += tc2 - tc1; A.prof[402] += tc3 - tc2; A.prof[403] += tc4 - tc3; A.prof[404] += 1; }
 #endif
+                // (ldpc_verdict's rule, written out: three exits of their own from the trial loop.  Through the helper -- one merged exit -- the register allocation of the
+                // whole <12> kernel comes out differently: 5 spilled VGPRs for 11 and ~700 instructions of the sweep in other places, i.e. another kernel to measure)
                 if (A.force) { ret = any ? -1 : A.max_trials; break; }
                 if (!any) { ret = it; break; }
                 if (it == A.max_trials) { ret = -1; break; }
@@ -815,29 +812,7 @@ __global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(8)
             int* __restrict__ s_flag = reinterpret_cast<int*>(lds_all + N);
             int t = threadIdx.x;
             asm volatile("" : "+v"(t));
-            if (t == 0) A.trials[f] = ret;
-            // hard decisions of [0,K): 64 bits per wave step via ballot, MSB-first bytes (module_dvbs2_demod.cpp:357-360)
-            uint8_t* __restrict__ hd = A.hard + (size_t)f * A.hard_stride;
-            const int lane = t & 63;
-            for (int base = wave * 64; base < K; base += (T / 64) * 64) {
-                int idx = base + lane;
-                int neg = (idx < K) ? (post[idx] < 0) : 0;
-                unsigned long long b = __ballot(neg);
-                b = __builtin_bswap64(__brevll(b));
-                if (lane == 0) {
-                    int nbytes = min(8, (K - base) / 8);
-                    if (nbytes == 8 && ((uintptr_t)(hd + base / 8) & 7u) == 0) *reinterpret_cast<uint2*>(hd + base / 8) = make_uint2((uint32_t)b, (uint32_t)(b >> 32));
-                    else for (int n = 0; n < nbytes; ++n) hd[base / 8 + n] = (uint8_t)(b >> (8 * n));
-                }
-            }
-            if (A.post) {
-                int8_t* __restrict__ dst = A.post + (size_t)f * N;
-                for (int i = t; i < K / 8; i += T) reinterpret_cast<uint2*>(dst)[i] = reinterpret_cast<const uint2*>(post)[i];
-                for (int c = t; c < R; c += T) {
-                    int jj = c / q, i = c - jj * q;
-                    dst[K + c] = post[K + 360 * i + jj];
-                }
-            }
+            ldpc_frame_store<T>(post, f, ret, A.trials, A.hard, A.hard_stride, A.post, N, K, R, q, t, wave);
             if (A.work_ctr) {
                 if (t == 0) s_flag[12] = (int)(gridDim.x + atomicAdd(A.work_ctr, 1u));
                 lds_barrier();
@@ -859,24 +834,12 @@ size_t ldpc_split_msg_bytes_per_block(const LdpcDeviceCode& C) { return (size_t)
 
 template <int MAXDEG>
 static hipError_t launch_split(const LdpcDeviceCode& C, const LdpcKernelArgs& A, int grid, hipStream_t stream) {
-    const size_t lds = ldpc_split_lds_bytes(A.N);
-    auto kern = ldpc_split_kernel<MAXDEG>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
     LdpcKernelParams P;
     P.A = A; P.layers = C.d_split_layers; P.ents = C.d_ents; P.atab = C.d_split_atab; P.rows = C.d_rows; P.npl = C.split_npl; P.tab_words = C.split_tab_words;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(LDPC_SPLIT_T), lds, stream, P);
-    return hipGetLastError();
+    return ldpc_launch(ldpc_split_kernel<MAXDEG>, grid, LDPC_SPLIT_T, ldpc_split_lds_bytes(A.N), stream, P);
 }
 template <int MAXDEG>
-static int occupancy_split(int N) {
-    int nb = 0;
-    const size_t lds = ldpc_split_lds_bytes(N);
-    auto kern = ldpc_split_kernel<MAXDEG>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, LDPC_SPLIT_T, lds) != hipSuccess) nb = 1;
-    return nb < 1 ? 1 : nb;
-}
+static int occupancy_split(int N) { return ldpc_occupancy(ldpc_split_kernel<MAXDEG>, LDPC_SPLIT_T, ldpc_split_lds_bytes(N)); }
 
 #define LDPC_SPLIT_DISPATCH(FN, ...)                    \
     switch (max_deg) {                                  \
@@ -889,7 +852,6 @@ static int occupancy_split(int N) {
         default: break;                                 \
     }
 
-extern unsigned long long* g_ldpc_prof;   // (ldpc_kernel.hip)
 bool ldpc_split_supported(int max_deg) { return max_deg == 2 || max_deg == 4 || max_deg == 5 || max_deg == 8 || max_deg == 9 || max_deg == 12; }
 bool ldpc_split_noprev_shared(int max_deg) { return max_deg == 4 || max_deg == 8; }      // SplitShape::NOPREV_SHARED
 int ldpc_split_blocks_per_cu(int max_deg, int N) {
@@ -897,21 +859,13 @@ int ldpc_split_blocks_per_cu(int max_deg, int N) {
     return 1;
 }
 
-hipError_t ldpc_split_decode_launch(const LdpcDeviceCode& C, const int8_t* llr, int nframes, int max_trials, int force, uint8_t* hard, int hard_stride,
-                                    int8_t* post, int32_t* trials, uint32_t* msg_ws, int grid, hipStream_t stream, unsigned int* work_ctr, uint32_t* sgn_ws, int dbg) {
+hipError_t ldpc_split_decode_launch(const LdpcDeviceCode& C, const LdpcJob& J) {
     LdpcKernelArgs A;
-    A.work_ctr = work_ctr;
-    A.sgn_ws = sgn_ws;
-    if (work_ctr) {
-        hipError_t e = hipMemsetAsync(work_ctr, 0, sizeof(unsigned int), stream);
-        if (e != hipSuccess) return e;
-    }
-    A.llr = llr; A.hard = hard; A.post = post; A.trials = trials; A.msg_ws = msg_ws;
-    A.nframes = nframes; A.N = C.N; A.K = C.K; A.R = C.R; A.q = C.q; A.pent_base = C.split_rec_total; A.synd_base = C.synd_base;
-    A.max_trials = max_trials; A.force = force; A.hard_stride = hard_stride; A.dbg = dbg;
-    A.prof = g_ldpc_prof;
+    hipError_t e = ldpc_kernel_args(C, J, &A);
+    if (e != hipSuccess) return e;
+    A.pent_base = C.split_rec_total;            // (this decoder has no pair table: the field carries the message words of a workgroup)
     const int max_deg = C.max_deg;
-    LDPC_SPLIT_DISPATCH(launch_split, C, A, grid, stream)
+    LDPC_SPLIT_DISPATCH(launch_split, C, A, J.grid, J.stream)
     return hipErrorInvalidValue;
 }
 

@@ -18,17 +18,18 @@
 
 namespace s2 {
 
-// The code tables are separate `const T* __restrict__` kernel parameters (not struct members): hipcc then proves them invariant and
-// fetches the wave-uniform entries with scalar loads.
+// The wave kernel's arguments in an arrangement of their own: the pointers first, then the integers.  Handed LdpcKernelArgs + three integers -- in any parameter order, or
+// inside a wrapper -- the kernel keeps two more scalar registers in vector-register lanes and its sweep is scheduled differently: 0.5-1.1 % slower on rate 8/9 short
+// (profiles/ldpc_frame_io_ab.json).  Filled from LdpcKernelArgs by ldpc_wave_decode_launch, nowhere else.
 struct LdpcWaveArgs {
-    const int8_t* llr;          // [nframes][N]
-    uint8_t* hard;              // [nframes][hard_stride]
-    int8_t* post;               // optional [nframes][N]
-    int32_t* trials;            // [nframes]
-    uint8_t* msg_ws;            // [gridDim.x][R * 8 * element bytes]
-    uint32_t* sgn_ws;           // [gridDim.x][SGN_WS_DWORDS]
+    const int8_t* llr;
+    uint8_t* hard;
+    int8_t* post;
+    int32_t* trials;
+    uint32_t* msg_ws;           // [gridDim.x][R * 8 * element bytes]
+    uint32_t* sgn_ws;
     unsigned int* work_ctr;
-    int nframes, N, K, R, q, nsteps, absent_base, synd_base, max_deg, max_trials, force, hard_stride;
+    int nframes, N, K, R, q, nsteps, absent_base, synd_base, max_deg, max_trials, force, hard_stride;      // (nsteps: not read by the kernel; its slot is part of the arrangement)
 };
 
 #define WQUAD(x_, ctrl) __builtin_amdgcn_update_dpp(0, (x_), (ctrl), 0xf, 0xf, true)
@@ -86,14 +87,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ld
 
     int f = blockIdx.x;
     while (f < A.nframes) {
-        {
-            const int8_t* __restrict__ src = A.llr + (size_t)f * N;
-            for (int i = lane; i < K / 8; i += 64) reinterpret_cast<uint2*>(post)[i] = reinterpret_cast<const uint2*>(src)[i];
-            for (int c = lane; c < R; c += 64) {          // parity LLRs: pty[360*i + jj] = llr[K + q*jj + i]   (layered_decoder.hh:124-126)
-                const int jj = c / q, i = c - jj * q;
-                post[K + 360 * i + jj] = src[K + c];
-            }
-        }
+        ldpc_frame_load<64>(post, A.llr + (size_t)f * N, K, R, q, lane);
         int it = 0, ret = 0;
         bool done = false;
         while (true) {
@@ -105,9 +99,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ld
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                 const bool bad = z != 0 || wave_syndromes_bad(q, A.max_deg, ents + A.synd_base, sgn, lane);
                 const bool any = __ballot(bad) != 0;
-                if (A.force) { ret = any ? -1 : A.max_trials; done = true; }
-                else if (!any) { ret = it; done = true; }
-                else if (it == A.max_trials) { ret = -1; done = true; }
+                done = ldpc_verdict(A.force, any, it, A.max_trials, ret);
             }
             if (done) break;
             // ---- one layered sweep (LDPCDecoder::update): layer by layer, a layer's steps in chunks of U; step list and message elements
@@ -254,29 +246,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ld
             ++it;
         }
 
-        // ---- outputs
-        if (lane == 0) A.trials[f] = ret;
-        uint8_t* __restrict__ hd = A.hard + (size_t)f * A.hard_stride;
-        for (int base = 0; base < K; base += 64) {
-            const int idx = base + lane;
-            const int neg = (idx < K) ? (post[idx] < 0) : 0;
-            unsigned long long b = __ballot(neg);
-            b = __builtin_bswap64(__brevll(b));
-            if (lane == 0) {
-                const int nbytes = min(8, (K - base) / 8);
-                // (K / 8 is odd for three of the codes this decoder serves, and a caller's stride need not be a multiple of 8: the 8-byte store only where it is aligned)
-                if (nbytes == 8 && ((uintptr_t)(hd + base / 8) & 7u) == 0) *reinterpret_cast<uint2*>(hd + base / 8) = make_uint2((uint32_t)b, (uint32_t)(b >> 32));
-                else for (int n = 0; n < nbytes; ++n) hd[base / 8 + n] = (uint8_t)(b >> (8 * n));
-            }
-        }
-        if (A.post) {
-            int8_t* __restrict__ dst = A.post + (size_t)f * N;
-            for (int i = lane; i < K / 8; i += 64) reinterpret_cast<uint2*>(dst)[i] = reinterpret_cast<const uint2*>(post)[i];
-            for (int c = lane; c < R; c += 64) {
-                const int jj = c / q, i = c - jj * q;
-                dst[K + c] = post[K + 360 * i + jj];
-            }
-        }
+        ldpc_frame_store<64>(post, f, ret, A.trials, A.hard, A.hard_stride, A.post, N, K, R, q, lane, 0);
         if (A.work_ctr) {
             if (lane == 0) s_next = (int)(gridDim.x + atomicAdd(A.work_ctr, 1u));
             f = __builtin_amdgcn_readfirstlane(*(volatile int*)&s_next);
@@ -287,12 +257,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ld
 }
 
 template <int LW, int ABS_FROM>
-static hipError_t launch_wave(const LdpcDeviceCode& C, const LdpcWaveArgs& A, int grid, size_t lds, hipStream_t stream) {
-    auto kern = ldpc_wave_kernel<LW, ABS_FROM>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds, stream, C.d_wave_lanec, C.d_wave_steps, C.d_wave_layer_end, C.d_ents, A);
-    return hipGetLastError();
+static hipError_t launch_wave(const LdpcDeviceCode& C, const LdpcWaveArgs& A, int grid, hipStream_t stream) {
+    return ldpc_launch(ldpc_wave_kernel<LW, ABS_FROM>, grid, 64, ldpc_wave_lds_bytes(C), stream, C.d_wave_lanec, C.d_wave_steps, C.d_wave_layer_end, C.d_ents, A);
 }
 
 size_t ldpc_wave_msg_bytes_per_frame(const LdpcDeviceCode& C) {
@@ -301,19 +267,14 @@ size_t ldpc_wave_msg_bytes_per_frame(const LdpcDeviceCode& C) {
 }
 size_t ldpc_wave_lds_bytes(const LdpcDeviceCode& C) { return (size_t)((C.N + 8 + 15) / 16) * 16; }
 
-hipError_t ldpc_wave_decode_launch(const LdpcDeviceCode& C, const int8_t* llr, int nframes, int max_trials, int force, uint8_t* hard, int hard_stride,
-                                   int8_t* post, int32_t* trials, uint8_t* msg_ws, int grid, hipStream_t stream, unsigned int* work_ctr, uint32_t* sgn_ws) {
-    LdpcWaveArgs A;
-    A.llr = llr; A.hard = hard; A.post = post; A.trials = trials; A.msg_ws = msg_ws; A.sgn_ws = sgn_ws; A.work_ctr = work_ctr;
-    A.nframes = nframes; A.N = C.N; A.K = C.K; A.R = C.R; A.q = C.q; A.nsteps = C.wave_nsteps;
-    A.absent_base = C.wave_absent_base; A.synd_base = C.synd_base; A.max_deg = C.max_deg; A.max_trials = max_trials; A.force = force; A.hard_stride = hard_stride;
-    if (work_ctr) {
-        hipError_t e = hipMemsetAsync(work_ctr, 0, sizeof(unsigned int), stream);
-        if (e != hipSuccess) return e;
-    }
-    const size_t lds = ldpc_wave_lds_bytes(C);
+hipError_t ldpc_wave_decode_launch(const LdpcDeviceCode& C, const LdpcJob& J) {
+    LdpcKernelArgs K;
+    hipError_t e = ldpc_kernel_args(C, J, &K);
+    if (e != hipSuccess) return e;
+    const LdpcWaveArgs A = {K.llr, K.hard, K.post, K.trials, K.msg_ws, K.sgn_ws, K.work_ctr, K.nframes, K.N, K.K, K.R, K.q, C.wave_nsteps, C.wave_absent_base, K.synd_base, C.max_deg,
+                            K.max_trials, K.force, K.hard_stride};
     const int abs_from = C.wave_nl_min / 8;         // first slot index kk that holds a link slot >= the smallest row degree
-#define WAVE_CASE(LW_, AF_) if (C.wave_lw == LW_ && abs_from == AF_) return launch_wave<LW_, AF_>(C, A, grid, lds, stream)
+#define WAVE_CASE(LW_, AF_) if (C.wave_lw == LW_ && abs_from == AF_) return launch_wave<LW_, AF_>(C, A, J.grid, J.stream)
     WAVE_CASE(1, 0); WAVE_CASE(1, 1);
     WAVE_CASE(2, 0); WAVE_CASE(2, 1); WAVE_CASE(2, 2);
     WAVE_CASE(3, 0); WAVE_CASE(3, 1); WAVE_CASE(3, 2); WAVE_CASE(3, 3);

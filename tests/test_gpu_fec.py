@@ -133,6 +133,37 @@ def test_ldpc_batch_larger_than_grid_and_empty(engine):
     assert h.shape[0] == 0
 
 
+# decoder form (dvbs2gpu_ldpc_decoder_form) -> the context options that select it, and the nearest code with an odd K / 8 it serves: rate 1/4 short
+# (K / 8 = 405); the half-row decoder takes normal frames only: rate 1/4 normal (K / 8 = 2025)
+ODD_K8_FORMS = {'lane_per_row': (0, {'ldpc_wave': 0}, 0, 1), 'wave_per_frame': (1, {'ldpc_wave': 1}, 0, 1), 'half_row': (2, {'ldpc_split': 1}, 0, 0)}
+
+
+@pytest.mark.parametrize('name', list(ODD_K8_FORMS))
+def test_ldpc_frame_output_odd_byte_count_every_form(pkg, name):
+    """three frames of a code with an odd K / 8: frames 1 and 2 start at a hard-decision address that is no multiple of 8 (both store paths of the shared
+    frame output), and the odd count leaves the lane-per-row decoder's second frame slot empty in its last workgroup; early exit and forced mode"""
+    import torch
+    form, options, rate, short = ODD_K8_FORMS[name]
+    p = orc.fec_params(rate, short)
+    assert (p['K'] // 8) % 2 == 1
+    m = MARGINAL_SNR[rate]
+    _, llr, _ = make_llrs(rate, short, 3, np.random.default_rng(31), [m + 3.0, m, -8.0])
+    eng = pkg.Engine(0, options=options)
+    try:
+        assert eng.ldpc_decoder_form(rate, bool(short)) == form
+        for force, mt in ((0, 4), (1, 4)):
+            want_post, want_trials = oracle_ldpc(rate, short, llr, mt, force)
+            if not force:
+                assert (want_trials >= 0).any() and (want_trials < 0).any(), want_trials       # one frame converges, one does not
+            hard, trials, post = eng.ldpc_decode(torch.from_numpy(llr).cuda(), rate, bool(short), max_trials=mt, force=bool(force), want_post=True)
+            torch.cuda.synchronize()
+            assert np.array_equal(trials.cpu().numpy(), want_trials), (force, mt)
+            assert np.array_equal(post.cpu().numpy(), want_post), (force, mt)
+            assert np.array_equal(hard.cpu().numpy(), np.packbits((want_post[:, :p['K']] < 0).astype(np.uint8), axis=1)), (force, mt)
+    finally:
+        eng.close()
+
+
 def test_fec_round_trip_at_the_headline_batch_size(engine):
     """BASELINE's headline shape -- 4096 normal frames of rate 3/4, 50 forced iterations, one launch -- through size-independent properties:
     encode -> independent noise per frame -> decode returns every transmitted BBFRAME; frames with identical input (the noise repeats every
