@@ -716,6 +716,74 @@ int dvbs2gpu_bbts_ma_get_pdu_table_device(dvbs2gpu_bbts* b, int stream, int slot
 /* mask8: bit i of the 256-bit mask = a frame with a valid header and ISI i has been seen on `stream` since the mode was set */
 int dvbs2gpu_bbts_get_isi_seen(dvbs2gpu_bbts* b, int stream, uint32_t* mask8);
 
+/* ------------------------------------------------------------------ TS monitor bank (own extension)
+ * Nothing in the reference does this: it hands the packets of dsp::dvbs2::BBFrameTSParser / dsp::dvbs::DVBSDemod on unlooked at.
+ * For `nstreams` transport streams in HBM -- the output buffers of dvbs2gpu_bbts_process_batch, dvbs2gpu_bbts_process_ma_batch or
+ * dvbs2gpu_dvbs_tail_process_batch -- a bank keeps the packet-header checks of ETSI TR 101 290 first priority (sync byte,
+ * continuity count) per stream, reports which PIDs the last call brought, and compacts the packets a PID filter lets pass.
+ *   Packet: 188 bytes at offset 188 k of a stream's input; no sync search (the packetisers emit whole packets from offset 0).
+ *   Header (ISO/IEC 13818-1 2.4.3.2): sync b0, TEI b1>>7, PUSI (b1>>6)&1, PID (b1&0x1f)<<8|b2, TSC b3>>6, AFC (b3>>4)&3, CC b3&15;
+ *     DI (discontinuity indicator) b5>>7, taken only when AFC&2 and b4 > 0, else 0.
+ *   Classification, in this order: b0 != 0x47 a sync-byte error (nothing else of the packet counts); TEI set a TEI packet (header
+ *     not trusted: no PID row, no continuity step); PID 0x1FFF a null packet (a PID row, no continuity step); else the continuity
+ *     step of its PID.
+ *   Continuity per (stream, PID), state seen / last (4 bits) / dup_used, in this order: never seen: seen=1, last=CC, row flag
+ *     FIRST_SEEN, no verdict.  DI: last=CC, row flag DISCONTINUITY, counted in `discontinuities`, no verdict.  No payload (AFC 0 or
+ *     2): an error if CC != last.  Payload: CC == last+1 (mod 16) is good; CC == last with dup_used clear is a duplicate and sets
+ *     dup_used; anything else is a continuity error.  Every step ends with last=CC, and dup_used clear unless it was the duplicate.
+ *     A duplicate is recognised by CC alone: the two packets' bytes are not compared.
+ *   State survives from call to call: the result does not depend on how a stream is cut into calls.  reset forgets it (the
+ *     counters too; the filters stay).
+ *   Filter per stream: mode 0 every PID passes, 1 the listed PIDs, 2 all but the listed; drop_null / drop_tei / drop_bad_sync take
+ *     those packets out whatever the list says.  A TEI packet or one with a bad sync byte has no trusted PID: it passes unless its
+ *     flag drops it.  The statistics and the table do not depend on the filter, except passed_packets.
+ *   Capacity: sizes first.  If the passing packets of one stream exceed cap the call returns DVBS2GPU_ERR_CAPACITY, out_bytes[]
+ *     holds the sizes, no state or counter of any stream has advanced and the table of the call is empty: the same call can be
+ *     repeated with larger buffers.
+ *   Limits: max_packets <= 8192 per stream and call.  Memory (device banks): 8 KiB of continuity state and 1 KiB of filter per
+ *     stream, 25 bytes per packet of max_packets for the table. */
+typedef struct dvbs2gpu_tsmon dvbs2gpu_tsmon;
+int dvbs2gpu_tsmon_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, dvbs2gpu_tsmon** out);
+/* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_tsmon_work only */
+int dvbs2gpu_tsmon_create_host(int nstreams, int max_packets, dvbs2gpu_tsmon** out);
+int dvbs2gpu_tsmon_reset(dvbs2gpu_tsmon* m);
+void dvbs2gpu_tsmon_destroy(dvbs2gpu_tsmon* m);
+typedef struct dvbs2gpu_tsmon_filter {
+    int32_t mode;            /* 0 pass all, 1 pass listed, 2 drop listed */
+    int32_t drop_null, drop_tei, drop_bad_sync;
+} dvbs2gpu_tsmon_filter;
+/* pids[n]: the list (each <= 0x1FFF; n may be 0).  A new bank passes everything. */
+int dvbs2gpu_tsmon_set_filter(dvbs2gpu_tsmon* m, int stream, const dvbs2gpu_tsmon_filter* f, const uint16_t* pids, int n);
+/* d_ts[i]: DEVICE pointer to nbytes[i] bytes (a multiple of 188, at most 188*max_packets) of stream i.  d_out NULL: statistics and
+ * table only (out_bytes may be NULL too).  Else d_out[i]: DEVICE buffer of cap bytes that receives the passing packets in input
+ * order, out_bytes[i] (host) their bytes; d_out[i] must not overlap d_ts[i].  Synchronous on `stream`: chained behind a packetiser
+ * call on the same stream, the packets never visit the host. */
+int dvbs2gpu_tsmon_process_batch(dvbs2gpu_tsmon* m, const uint8_t* const* d_ts, const int* nbytes, uint8_t* const* d_out, int cap,
+                                 int* out_bytes, void* stream);
+/* one stream of any bank with HOST buffers (h_out NULL: statistics only): returns the bytes written to h_out or a negative error.
+ * The other streams of the bank receive an empty call. */
+int dvbs2gpu_tsmon_work(dvbs2gpu_tsmon* m, int stream, const uint8_t* h_ts, int nbytes, uint8_t* h_out, int cap);
+typedef struct dvbs2gpu_tsmon_stats {          /* since creation or reset */
+    int64_t packets;             /* every 188 bytes handed in */
+    int64_t null_packets, tei_packets, sync_byte_errors;
+    int64_t cc_errors, duplicates, discontinuities;
+    int64_t scrambled_packets;   /* trusted packets (null packets included) with TSC != 0 */
+    int64_t passed_packets;      /* packets the filter let pass (also counted in calls without output buffers) */
+    int64_t pids_seen;           /* PIDs whose `seen` bit is set */
+} dvbs2gpu_tsmon_stats;
+int dvbs2gpu_tsmon_get_stats(dvbs2gpu_tsmon* m, int stream, dvbs2gpu_tsmon_stats* h_out);
+/* One row per PID among the trusted packets of the LAST call (the null PID included), ascending by PID. */
+#define DVBS2GPU_TSMON_PID_FIRST_SEEN 1      /* the PID's first packet since reset came in this call */
+#define DVBS2GPU_TSMON_PID_DISCONTINUITY 2   /* a packet of the PID announced a discontinuity in this call */
+typedef struct dvbs2gpu_tsmon_pid {
+    uint16_t pid, flags;
+    uint32_t packets, cc_errors, duplicates, scrambled, pusi;
+} dvbs2gpu_tsmon_pid;
+/* h_rows[cap] (host); *n = rows of the last call, of which min(*n, cap) are written */
+int dvbs2gpu_tsmon_get_pid_table(dvbs2gpu_tsmon* m, int stream, dvbs2gpu_tsmon_pid* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_tsmon_get_pid_table_device(dvbs2gpu_tsmon* m, int stream, const dvbs2gpu_tsmon_pid** d_rows, int* n);
+
 #ifdef __cplusplus
 }
 #endif

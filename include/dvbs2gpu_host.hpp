@@ -440,5 +440,70 @@ private:
     dvbs2gpu_fleet* f = nullptr;
     int nt = 0, cap = 0;
 };
+
+/* TS monitor for one transport stream (dvbs2gpu_tsmon_*, include/dvbs2gpu.h; an extension, the reference has no counterpart): a block
+ * behind BBFrameTSParser or DVBSDemod in a sink handler.  init() and the setters throw like everything above.  work() sits in the
+ * data path and does NOT throw: a failing call returns 0 bytes and leaves its code in status() and its text in error(), where they
+ * stay (sticky: the first failure is kept, later calls still run) until clearStatus(). */
+class TSMonitor {
+public:
+    TSMonitor() {}
+    ~TSMonitor() {
+        if (h) dvbs2gpu_tsmon_destroy(h);
+    }
+    TSMonitor(const TSMonitor&) = delete;
+    TSMonitor& operator=(const TSMonitor&) = delete;
+
+    void init(int max_packets, int device = 0) {
+        if (h) dvbs2gpu_tsmon_destroy(h);
+        h = nullptr;
+        eng = Engine::get(device);
+        check(dvbs2gpu_tsmon_create(eng->ctx, 1, max_packets, &h));
+    }
+    void reset() { check(dvbs2gpu_tsmon_reset(need())); }
+    /* mode 0 pass all, 1 pass the listed PIDs, 2 drop them */
+    void setFilter(int mode, const std::vector<uint16_t>& pids, bool drop_null = false, bool drop_tei = false, bool drop_bad_sync = false) {
+        const dvbs2gpu_tsmon_filter f = {mode, drop_null, drop_tei, drop_bad_sync};
+        check(dvbs2gpu_tsmon_set_filter(need(), 0, &f, pids.data(), (int)pids.size()));
+    }
+    /* nbytes of whole TS packets in; the passing packets to `out` (nullptr: statistics and table only); returns the bytes written,
+     * 0 on failure (see status()) */
+    int work(const uint8_t* ts, int nbytes, uint8_t* out, int buffer_outsize) noexcept {
+        const int n = h ? dvbs2gpu_tsmon_work(h, 0, ts, nbytes, out, buffer_outsize) : DVBS2GPU_ERR_ARG;
+        if (n >= 0) return n;
+        if (status_ == 0) {
+            status_ = n;
+            try { error_ = h ? dvbs2gpu_last_error() : "TSMonitor used before init()"; } catch (...) {}
+        }
+        return 0;
+    }
+    int status() const { return status_; }
+    const std::string& error() const { return error_; }
+    void clearStatus() { status_ = 0; error_.clear(); }
+
+    dvbs2gpu_tsmon_stats stats() {
+        dvbs2gpu_tsmon_stats s;
+        check(dvbs2gpu_tsmon_get_stats(need(), 0, &s));
+        return s;
+    }
+    /* one row per PID of the last work(), ascending */
+    std::vector<dvbs2gpu_tsmon_pid> pidTable() {
+        int n = 0;
+        check(dvbs2gpu_tsmon_get_pid_table(need(), 0, nullptr, 0, &n));
+        std::vector<dvbs2gpu_tsmon_pid> rows((size_t)n);
+        if (n > 0) check(dvbs2gpu_tsmon_get_pid_table(h, 0, rows.data(), n, &n));
+        return rows;
+    }
+
+private:
+    dvbs2gpu_tsmon* need() {
+        if (!h) throw std::runtime_error("dvbs2gpu: TSMonitor used before init()");
+        return h;
+    }
+    std::shared_ptr<Engine> eng;
+    dvbs2gpu_tsmon* h = nullptr;
+    int status_ = 0;
+    std::string error_;
+};
 }   // namespace dvbs2gpu_host
 #endif

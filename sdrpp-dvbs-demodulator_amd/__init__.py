@@ -88,6 +88,23 @@ class GsePdu(C.Structure):
     _fields_ = [('offset', C.c_uint32), ('bytes', C.c_uint32), ('protocol', C.c_uint16), ('flags', C.c_uint16), ('reserved', C.c_uint32)]
 
 
+class TsMonFilter(C.Structure):
+    """dvbs2gpu_tsmon_filter"""
+    _fields_ = [('mode', C.c_int32), ('drop_null', C.c_int32), ('drop_tei', C.c_int32), ('drop_bad_sync', C.c_int32)]
+
+
+class TsMonStats(C.Structure):
+    """dvbs2gpu_tsmon_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('packets', 'null_packets', 'tei_packets', 'sync_byte_errors', 'cc_errors', 'duplicates', 'discontinuities',
+                                         'scrambled_packets', 'passed_packets', 'pids_seen')]
+
+
+class TsMonPid(C.Structure):
+    """dvbs2gpu_tsmon_pid"""
+    _fields_ = [('pid', C.c_uint16), ('flags', C.c_uint16), ('packets', C.c_uint32), ('cc_errors', C.c_uint32), ('duplicates', C.c_uint32),
+                ('scrambled', C.c_uint32), ('pusi', C.c_uint32)]
+
+
 class FrameQuality(C.Structure):
     """dvbs2gpu_frame_quality"""
     _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('gain', C.c_float), ('phase', C.c_float), ('known_symbols', C.c_int32),
@@ -230,6 +247,16 @@ PROTOTYPES = {
     'dvbs2gpu_bbts_ma_get_gse_stats': (_i, [_vp, _i, _i, C.POINTER(BbtsMaGseStats)]),
     'dvbs2gpu_bbts_ma_get_pdu_table': (_i, [_vp, _i, _i, C.POINTER(GsePdu), _i, C.POINTER(_i)]),
     'dvbs2gpu_bbts_ma_get_pdu_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
+    'dvbs2gpu_tsmon_create': (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_tsmon_create_host': (_i, [_i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_tsmon_reset': (_i, [_vp]),
+    'dvbs2gpu_tsmon_destroy': (None, [_vp]),
+    'dvbs2gpu_tsmon_set_filter': (_i, [_vp, _i, C.POINTER(TsMonFilter), C.POINTER(C.c_uint16), _i]),
+    'dvbs2gpu_tsmon_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i), _vp]),
+    'dvbs2gpu_tsmon_work': (_i, [_vp, _i, _vp, _i, _vp, _i]),
+    'dvbs2gpu_tsmon_get_stats': (_i, [_vp, _i, C.POINTER(TsMonStats)]),
+    'dvbs2gpu_tsmon_get_pid_table': (_i, [_vp, _i, C.POINTER(TsMonPid), _i, C.POINTER(_i)]),
+    'dvbs2gpu_tsmon_get_pid_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
 }
 
 _lib = None
@@ -1101,6 +1128,94 @@ class BbTsParserBank(_Handle):
         m = (C.c_uint32 * 8)()
         self._check(self.lib.dvbs2gpu_bbts_get_isi_seen(self.h, int(stream), m))
         return [i for i in range(256) if m[i >> 5] >> (i & 31) & 1]
+
+
+class TsMonitorBank(_Handle):
+    """TS monitor for `nstreams` transport streams (own extension; include/dvbs2gpu.h, TS monitor bank): per-PID continuity checks, the
+    PID table of the last call and a PID filter that compacts the passing packets on the GPU.  Its input is what BbTsParserBank or
+    DvbsTailBank left in HBM."""
+    _destroy = 'dvbs2gpu_tsmon_destroy'
+    PASS_ALL, PASS_LISTED, DROP_LISTED = 0, 1, 2
+    PID_FIRST_SEEN, PID_DISCONTINUITY = 1, 2
+
+    def __init__(self, engine, nstreams=1, max_packets=4096):
+        self.eng, self.lib, self.nstreams, self.max_packets = engine, engine.lib, nstreams, max_packets
+        h = C.c_void_p()
+        engine._check(self.lib.dvbs2gpu_tsmon_create(engine.h, nstreams, max_packets, C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        self = cls.__new__(cls)
+        self.eng, self.lib, self.nstreams, self.max_packets = None, load_library(), nstreams, max_packets
+        h = C.c_void_p()
+        self._check(self.lib.dvbs2gpu_tsmon_create_host(nstreams, max_packets, C.byref(h)))
+        self.h = h
+        return self
+
+    def _check(self, rc):
+        if rc < 0:
+            raise Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+        return rc
+
+    def reset(self):
+        self._check(self.lib.dvbs2gpu_tsmon_reset(self.h))
+
+    def set_filter(self, stream, mode=0, pids=(), drop_null=False, drop_tei=False, drop_bad_sync=False):
+        f = TsMonFilter(int(mode), int(bool(drop_null)), int(bool(drop_tei)), int(bool(drop_bad_sync)))
+        a = (C.c_uint16 * max(len(pids), 1))(*[int(p) for p in pids])
+        self._check(self.lib.dvbs2gpu_tsmon_set_filter(self.h, int(stream), C.byref(f), a, len(pids)))
+
+    def process(self, ts_tensors, out_tensors=None, nbytes=None):
+        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors: None for statistics and
+        table only, else uint8 CUDA buffers that receive the passing packets -> byte counts.  Dvbs2GpuError -5 carries .needed when a
+        buffer is too small (nothing has advanced then)."""
+        n = self.nstreams
+        pin = (C.c_void_p * n)(*[t.data_ptr() for t in ts_tensors])
+        cnt = (C.c_int * n)(*[int(t.numel()) if nbytes is None else int(nbytes[i]) for i, t in enumerate(ts_tensors)])
+        nb = (C.c_int * n)()
+        pout, cap = None, 0
+        if out_tensors is not None:
+            pout = (C.c_void_p * n)(*[t.data_ptr() for t in out_tensors])
+            cap = min(int(t.numel()) for t in out_tensors)
+        rc = self.lib.dvbs2gpu_tsmon_process_batch(self.h, pin, cnt, pout, cap, nb, self.eng._stream())
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            e.needed = list(nb)
+            raise e
+        return list(nb)
+
+    def work(self, ts, stream=0, cap=None, filtered=True):
+        """one stream, host buffers: numpy uint8 packets in -> the passing packets (numpy uint8), or None with filtered=False"""
+        import numpy as np
+        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
+        if not filtered:
+            self._check(self.lib.dvbs2gpu_tsmon_work(self.h, int(stream), C.c_void_p(ts.ctypes.data), ts.size, None, 0))
+            return None
+        cap = ts.size if cap is None else cap
+        out = np.zeros(max(cap, 1), np.uint8)
+        n = self._check(self.lib.dvbs2gpu_tsmon_work(self.h, int(stream), C.c_void_p(ts.ctypes.data), ts.size, C.c_void_p(out.ctypes.data), cap))
+        return out[:n].copy()
+
+    def stats(self, stream=0):
+        st = TsMonStats()
+        self._check(self.lib.dvbs2gpu_tsmon_get_stats(self.h, int(stream), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in TsMonStats._fields_}
+
+    def pid_table(self, stream=0):
+        """[(pid, flags, packets, cc_errors, duplicates, scrambled, pusi)] of the last call, ascending by PID"""
+        n = C.c_int()
+        self._check(self.lib.dvbs2gpu_tsmon_get_pid_table(self.h, int(stream), None, 0, C.byref(n)))
+        rows = (TsMonPid * max(n.value, 1))()
+        self._check(self.lib.dvbs2gpu_tsmon_get_pid_table(self.h, int(stream), rows, n.value, C.byref(n)))
+        return [(r.pid, r.flags, r.packets, r.cc_errors, r.duplicates, r.scrambled, r.pusi) for r in rows[:n.value]]
+
+    def pid_table_device(self, stream=0):
+        """(device pointer or None, rows): the same table as dvbs2gpu_tsmon_pid records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self.lib.dvbs2gpu_tsmon_get_pid_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
+        return p.value, n.value
 
 
 class SegmentReceiver(_Handle):
