@@ -90,8 +90,9 @@ def test_bch_decode_bit_exact(engine, rate, short):
     assert np.array_equal(d.cpu().numpy(), want)
 
 
-@pytest.mark.parametrize('rate,short', [(6, 0), (3, 0), (9, 1), (0, 1)])
+@pytest.mark.parametrize('rate,short', orc.ALL_CODES)
 def test_fec_chain_recovers_bbframes(engine, rate, short):
+    """(at these noise levels the CPU oracle decodes all six frames of every one of the 21 codes)"""
     import torch
     rng = np.random.default_rng(3)
     m = MARGINAL_SNR[rate]
