@@ -784,6 +784,110 @@ int dvbs2gpu_tsmon_get_pid_table(dvbs2gpu_tsmon* m, int stream, dvbs2gpu_tsmon_p
 /* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
 int dvbs2gpu_tsmon_get_pid_table_device(dvbs2gpu_tsmon* m, int stream, const dvbs2gpu_tsmon_pid** d_rows, int* n);
 
+/* ------------------------------------------------------------------ PSI section bank (own extension)
+ * Nothing in the reference does this.  For `nstreams` transport streams in HBM a bank reassembles the PSI/SI sections on up to 16
+ * watched PIDs per stream, checks each section's CRC-32, writes the sections and one table row per section to device buffers and keeps
+ * the decoded PAT and PMTs on the host.  The sequential form below is the definition (csrc/psi_rules.h, PsiHostStream::run); the
+ * kernels give its results for every cutting of a stream into calls.  The section syntax (ISO/IEC 13818-1 2.4.4) is one struct of
+ * offsets, dvbs2gpu_psi_layout.
+ *   State per (stream, watched slot): the continuity byte of the TS monitor's automaton; a 4096-byte section buffer; fill, the bytes
+ *     buffered (0: no section is open); the last four bytes of the last valid section and a flag that there has been one.
+ *   Packet: 188 bytes at offset 188 k, classified as the TS monitor does.  Packets of unwatched PIDs, sync-byte errors and TEI packets
+ *     are not looked at (the gap a TEI packet leaves shows in the next packet's continuity step); PID 0x1FFF cannot be watched.
+ *   A packet of a watched PID, in this order.  "Drop" = the open section is forgotten; with fill > 0 it counts in dropped_sections.
+ *     1. TSC != 0: scrambled_packets, drop, the continuity step; nothing more of the packet is used.
+ *     2. The continuity step.  Duplicate: ignored.  Continuity error or announced discontinuity: drop, then go on with this packet
+ *        (with nothing open only a PUSI packet starts anything).  No payload (AFC&1 = 0): done.
+ *     3. The payload starts at 4, or at 5 + b4 when AFC&2.  >= 188: malformed_packets, drop, done.
+ *     4. PUSI set: ptr = the first payload byte.  ptr > the bytes after it: malformed_packets, drop, done.  The ptr bytes after the
+ *        pointer go to an open section: if they complete it, it is emitted and what is left of them is ignored; if it is still
+ *        incomplete after them, it is dropped; with nothing open they are ignored.  Then section starts are parsed behind them (6).
+ *     5. PUSI clear: the whole payload goes to an open section; if it completes it, it is emitted and the rest of the payload is
+ *        ignored.  With nothing open the payload is ignored.
+ *     6. At a section start, until the packet ends: a byte 0xFF ends the packet (stuffing).  Otherwise bytes are buffered; with three,
+ *        total = 3 + (((b1 & 0x0F) << 8) | b2); section_length > 4093: malformed_sections, nothing is open, the rest of the packet is
+ *        ignored (the same where an open section's header is completed by a later packet).  When the buffered bytes reach total the
+ *        section is emitted and the next byte is a section start.  A section, or a header of one or two bytes, that the packet's end
+ *        cuts stays open.
+ *   Emitting.  ssi = b1 >> 7.  ssi set and total < 12: malformed_sections, no row, no bytes, nothing else.  Otherwise the section
+ *     counts in `sections`, and in unexpected_table_id if the watch names another table_id.  ssi set: valid if CRC-32/MPEG (initial
+ *     value 0xFFFFFFFF, polynomial 0x04C11DB7) over all its bytes is 0; else crc_errors and row flag CRC_ERROR, row and bytes still
+ *     delivered.  ssi clear: valid.  A valid section is CHANGED when the slot has had no valid section, or its last four bytes (the
+ *     CRC field with ssi set; of a 3-byte section all three) differ from the stored ones; the stored ones are then replaced.
+ *     Consequence: a table of one section (a PAT, a PMT) is flagged once per version; the sections of a multi-section table flag
+ *     each other.
+ *   Row: one per emitted section, ordered by (packet that held its last byte, position in it): one order per stream across its PIDs.
+ *   Deliver mode per stream: 0 the bytes of every emitted section, 1 only those of valid changed ones.  Rows and counters do not
+ *     depend on it, except row.offset and bytes_delivered; a call without output buffers delivers nothing.
+ *   State survives from call to call.  reset forgets it (counters and decoded views too; watches and deliver modes stay); changing a
+ *     slot's watch starts that slot afresh.
+ *   Capacity: sizes first.  If one stream's bytes exceed cap or its rows exceed max_sections the call returns DVBS2GPU_ERR_CAPACITY,
+ *     out_bytes[] holds the byte sizes (-1 for a stream whose rows did not fit: its sections were not checked) and out_rows[] the row
+ *     counts; no state or counter of any stream has advanced, the table of the call is empty, the call can be repeated.
+ *   Decoded views: the host keeps, per slot, the bytes of its last valid CHANGED section with ssi, table_id 0 or 2 and current_next 1;
+ *     a device bank copies them across in the call that flags them, and only then.  Nothing follows the PAT by itself: which PMT PIDs
+ *     are watched is the caller's set_watch, so no result depends on where a call boundary fell.
+ *   Limits: max_packets <= 4096 per stream and call.  Memory (device banks) per stream: 64 KiB of section buffers, 64 KiB of view
+ *     staging, 6 bytes per packet of max_packets and 40 bytes per row of max_sections. */
+typedef struct dvbs2gpu_psi dvbs2gpu_psi;
+typedef struct dvbs2gpu_psi_layout {
+    int32_t header_bytes, length_mask, max_section_length, max_section_bytes, min_long_section;
+    int32_t ext_at, version_at, section_number_at, last_section_number_at, long_header_bytes, crc_bytes;
+    int32_t pat_loop_at, pat_stride, pmt_pcr_at, pmt_info_length_at, pmt_loop_at, pmt_stride;
+} dvbs2gpu_psi_layout;
+int dvbs2gpu_psi_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_sections, dvbs2gpu_psi** out);
+/* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_psi_work only */
+int dvbs2gpu_psi_create_host(int nstreams, int max_packets, int max_sections, dvbs2gpu_psi** out);
+int dvbs2gpu_psi_reset(dvbs2gpu_psi* b);
+void dvbs2gpu_psi_destroy(dvbs2gpu_psi* b);
+int dvbs2gpu_psi_get_layout(dvbs2gpu_psi_layout* h_out);
+/* slot 0..15; pid 0..0x1FFE, or -1: the slot watches nothing; expect_table_id 0..255, or -1: any.  A new bank watches PID 0 in slot 0
+ * of every stream, expecting table_id 0.  The same PID in two slots of a stream is DVBS2GPU_ERR_ARG. */
+int dvbs2gpu_psi_set_watch(dvbs2gpu_psi* b, int stream, int slot, int pid, int expect_table_id);
+int dvbs2gpu_psi_set_deliver(dvbs2gpu_psi* b, int stream, int mode);
+/* d_ts[i]: DEVICE pointer to nbytes[i] bytes (a multiple of 188, at most 188*max_packets) of stream i.  d_out NULL: rows and counters
+ * only (never a capacity failure for bytes; out_bytes may be NULL).  Else d_out[i]: DEVICE buffer of cap bytes for the delivered
+ * sections, back to back in row order; out_bytes[i] (host) their bytes.  out_rows (host, may be NULL): the row counts.  Synchronous
+ * on `stream`; chained behind a packetiser or monitor call on the same stream, no packet visits the host. */
+int dvbs2gpu_psi_process_batch(dvbs2gpu_psi* b, const uint8_t* const* d_ts, const int* nbytes, uint8_t* const* d_out, int cap, int* out_bytes,
+                               int* out_rows, void* stream);
+/* one stream of any bank with HOST buffers (h_out NULL: rows and counters only): returns the bytes written to h_out or a negative
+ * error.  The other streams of the bank receive an empty call. */
+int dvbs2gpu_psi_work(dvbs2gpu_psi* b, int stream, const uint8_t* h_ts, int nbytes, uint8_t* h_out, int cap);
+/* the byte and row sizes that the stream's last call needed, whether it succeeded or failed for capacity (what out_bytes / out_rows
+ * held; the way to them behind dvbs2gpu_psi_work) */
+int dvbs2gpu_psi_get_needed(dvbs2gpu_psi* b, int stream, int* bytes, int* rows);
+typedef struct dvbs2gpu_psi_stats {            /* since creation or reset; kept on the host */
+    int64_t packets;                 /* trusted packets of the watched PID */
+    int64_t sections, valid, changed, crc_errors, dropped_sections, malformed_sections, malformed_packets, scrambled_packets,
+            unexpected_table_id, bytes_delivered;
+} dvbs2gpu_psi_stats;
+/* slot -1: the sum over the stream's slots.  A slot's counters start again when its watch changes. */
+int dvbs2gpu_psi_get_stats(dvbs2gpu_psi* b, int stream, int slot, dvbs2gpu_psi_stats* h_out);
+#define DVBS2GPU_PSI_CRC_ERROR 1
+#define DVBS2GPU_PSI_CHANGED 2
+typedef struct dvbs2gpu_psi_section {
+    uint16_t pid, flags;
+    uint8_t table_id, ssi, version, current_next, section_number, last_section_number;   /* from version on: 0 when ssi is clear */
+    uint16_t table_id_ext;
+    int32_t length;                  /* total bytes */
+    int32_t offset;                  /* into the stream's output buffer; -1: not delivered */
+    int32_t first_packet;            /* index in this call of the packet that held its first byte; -1: an earlier call */
+} dvbs2gpu_psi_section;
+/* h_rows[cap] (host); *n = rows of the last call, of which min(*n, cap) are written */
+int dvbs2gpu_psi_get_section_table(dvbs2gpu_psi* b, int stream, dvbs2gpu_psi_section* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_psi_get_section_table_device(dvbs2gpu_psi* b, int stream, const dvbs2gpu_psi_section** d_rows, int* n);
+/* Decoded views (host parsers, csrc/psi_rules.h; no device is touched).  A loop or descriptor length that runs past the section's
+ * end makes the view empty and sets hdr.malformed; no byte outside the section is read. */
+typedef struct dvbs2gpu_psi_program { uint16_t program_number, pid; } dvbs2gpu_psi_program;   /* program 0: the network PID */
+typedef struct dvbs2gpu_psi_pat { int32_t transport_stream_id, version, malformed; } dvbs2gpu_psi_pat;   /* -1, -1, 0: no PAT held */
+/* from the PAT held by the stream's lowest slot that holds one */
+int dvbs2gpu_psi_get_programs(dvbs2gpu_psi* b, int stream, dvbs2gpu_psi_pat* hdr, dvbs2gpu_psi_program* h_rows, int cap, int* n);
+typedef struct dvbs2gpu_psi_es { uint16_t stream_type, elementary_pid; } dvbs2gpu_psi_es;
+typedef struct dvbs2gpu_psi_pmt { int32_t program_number, version, pcr_pid, malformed; } dvbs2gpu_psi_pmt;   /* program_number -1: no PMT held */
+int dvbs2gpu_psi_get_program_map(dvbs2gpu_psi* b, int stream, int slot, dvbs2gpu_psi_pmt* hdr, dvbs2gpu_psi_es* h_rows, int cap, int* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -505,5 +505,112 @@ private:
     int status_ = 0;
     std::string error_;
 };
+
+/* PSI section bank for one transport stream (dvbs2gpu_psi_*, include/dvbs2gpu.h; an extension): PAT / PMT / SI sections of up to 16
+ * watched PIDs behind BBFrameTSParser, DVBSDemod or TSMonitor.  init() (a device bank) or initHost() (the library's host
+ * implementation, no device) and the setters throw; work() sits in the data path and does NOT throw: a failing call returns 0 bytes
+ * and leaves its code in status() and its text in error(), sticky until clearStatus(). */
+class PsiBank {
+public:
+    PsiBank() {}
+    ~PsiBank() {
+        if (h) dvbs2gpu_psi_destroy(h);
+    }
+    PsiBank(const PsiBank&) = delete;
+    PsiBank& operator=(const PsiBank&) = delete;
+
+    void init(int max_packets, int max_sections, int device = 0) {
+        release();
+        eng = Engine::get(device);
+        check(dvbs2gpu_psi_create(eng->ctx, 1, max_packets, max_sections, &h));
+    }
+    void initHost(int max_packets, int max_sections) {
+        release();
+        check(dvbs2gpu_psi_create_host(1, max_packets, max_sections, &h));
+    }
+    void reset() { check(dvbs2gpu_psi_reset(need())); }
+    /* slot 0..15; pid -1 clears the slot; expect_table_id -1: any */
+    void setWatch(int slot, int pid, int expect_table_id = -1) {
+        check(dvbs2gpu_psi_set_watch(need(), 0, slot, pid, expect_table_id));
+        watched[slot] = pid;
+    }
+    void setDeliver(int mode) { check(dvbs2gpu_psi_set_deliver(need(), 0, mode)); }
+    /* slots 1..15 start afresh and watch the PMT PIDs of the PAT's programs (not program 0), expecting table_id 2, as far as the
+     * slots go; returns the programs that did not fit */
+    std::vector<dvbs2gpu_psi_program> followPat() {
+        dvbs2gpu_psi_pat hdr;
+        std::vector<dvbs2gpu_psi_program> left, seen;
+        int slot = 1;
+        for (int s = 1; s < 16; ++s) setWatch(s, -1);
+        for (const dvbs2gpu_psi_program& p : programs(&hdr)) {
+            if (p.program_number == 0 || p.pid == watched[0]) continue;   // (a PMT PID that slot 0 watches already stays there)
+            if (std::any_of(seen.begin(), seen.end(), [&](const dvbs2gpu_psi_program& q) { return q.pid == p.pid; })) continue;
+            if (slot >= 16) { left.push_back(p); continue; }
+            seen.push_back(p);
+            setWatch(slot++, p.pid, 2);
+        }
+        return left;
+    }
+    /* nbytes of whole TS packets in; the delivered sections to `out` (nullptr: rows and counters only); returns the bytes written,
+     * 0 on failure (see status(); after DVBS2GPU_ERR_CAPACITY needed() holds the sizes) */
+    int work(const uint8_t* ts, int nbytes, uint8_t* out, int buffer_outsize) noexcept {
+        const int n = h ? dvbs2gpu_psi_work(h, 0, ts, nbytes, out, buffer_outsize) : DVBS2GPU_ERR_ARG;
+        if (n >= 0) return n;
+        if (status_ == 0) {
+            status_ = n;
+            try { error_ = h ? dvbs2gpu_last_error() : "PsiBank used before init()"; } catch (...) {}
+        }
+        return 0;
+    }
+    int status() const { return status_; }
+    const std::string& error() const { return error_; }
+    void clearStatus() { status_ = 0; error_.clear(); }
+    void needed(int* bytes, int* rows) { check(dvbs2gpu_psi_get_needed(need(), 0, bytes, rows)); }
+
+    dvbs2gpu_psi_stats stats(int slot = -1) {
+        dvbs2gpu_psi_stats s;
+        check(dvbs2gpu_psi_get_stats(need(), 0, slot, &s));
+        return s;
+    }
+    /* one row per section of the last work(), in row order */
+    std::vector<dvbs2gpu_psi_section> sectionTable() {
+        int n = 0;
+        check(dvbs2gpu_psi_get_section_table(need(), 0, nullptr, 0, &n));
+        std::vector<dvbs2gpu_psi_section> rows((size_t)n);
+        if (n > 0) check(dvbs2gpu_psi_get_section_table(h, 0, rows.data(), n, &n));
+        return rows;
+    }
+    std::vector<dvbs2gpu_psi_program> programs(dvbs2gpu_psi_pat* hdr) {
+        int n = 0;
+        check(dvbs2gpu_psi_get_programs(need(), 0, hdr, nullptr, 0, &n));
+        std::vector<dvbs2gpu_psi_program> rows((size_t)n);
+        if (n > 0) check(dvbs2gpu_psi_get_programs(h, 0, hdr, rows.data(), n, &n));
+        return rows;
+    }
+    std::vector<dvbs2gpu_psi_es> programMap(int slot, dvbs2gpu_psi_pmt* hdr) {
+        int n = 0;
+        check(dvbs2gpu_psi_get_program_map(need(), 0, slot, hdr, nullptr, 0, &n));
+        std::vector<dvbs2gpu_psi_es> rows((size_t)n);
+        if (n > 0) check(dvbs2gpu_psi_get_program_map(h, 0, slot, hdr, rows.data(), n, &n));
+        return rows;
+    }
+
+private:
+    void release() {
+        if (h) dvbs2gpu_psi_destroy(h);
+        h = nullptr;
+        std::fill(watched, watched + 16, -1);
+        watched[0] = 0;                                    // a new bank watches the PAT in slot 0
+    }
+    dvbs2gpu_psi* need() {
+        if (!h) throw std::runtime_error("dvbs2gpu: PsiBank used before init()");
+        return h;
+    }
+    std::shared_ptr<Engine> eng;
+    dvbs2gpu_psi* h = nullptr;
+    int watched[16] = {0, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // slot -> PID, as setWatch left them
+    int status_ = 0;
+    std::string error_;
+};
 }   // namespace dvbs2gpu_host
 #endif

@@ -105,6 +105,46 @@ class TsMonPid(C.Structure):
                 ('scrambled', C.c_uint32), ('pusi', C.c_uint32)]
 
 
+class PsiLayout(C.Structure):
+    """dvbs2gpu_psi_layout"""
+    _fields_ = [(k, C.c_int32) for k in ('header_bytes', 'length_mask', 'max_section_length', 'max_section_bytes', 'min_long_section', 'ext_at',
+                                         'version_at', 'section_number_at', 'last_section_number_at', 'long_header_bytes', 'crc_bytes', 'pat_loop_at',
+                                         'pat_stride', 'pmt_pcr_at', 'pmt_info_length_at', 'pmt_loop_at', 'pmt_stride')]
+
+
+class PsiStats(C.Structure):
+    """dvbs2gpu_psi_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('packets', 'sections', 'valid', 'changed', 'crc_errors', 'dropped_sections', 'malformed_sections',
+                                         'malformed_packets', 'scrambled_packets', 'unexpected_table_id', 'bytes_delivered')]
+
+
+class PsiSection(C.Structure):
+    """dvbs2gpu_psi_section"""
+    _fields_ = [('pid', C.c_uint16), ('flags', C.c_uint16), ('table_id', C.c_uint8), ('ssi', C.c_uint8), ('version', C.c_uint8), ('current_next', C.c_uint8),
+                ('section_number', C.c_uint8), ('last_section_number', C.c_uint8), ('table_id_ext', C.c_uint16), ('length', C.c_int32),
+                ('offset', C.c_int32), ('first_packet', C.c_int32)]
+
+
+class PsiProgram(C.Structure):
+    """dvbs2gpu_psi_program"""
+    _fields_ = [('program_number', C.c_uint16), ('pid', C.c_uint16)]
+
+
+class PsiPat(C.Structure):
+    """dvbs2gpu_psi_pat"""
+    _fields_ = [('transport_stream_id', C.c_int32), ('version', C.c_int32), ('malformed', C.c_int32)]
+
+
+class PsiEs(C.Structure):
+    """dvbs2gpu_psi_es"""
+    _fields_ = [('stream_type', C.c_uint16), ('elementary_pid', C.c_uint16)]
+
+
+class PsiPmt(C.Structure):
+    """dvbs2gpu_psi_pmt"""
+    _fields_ = [('program_number', C.c_int32), ('version', C.c_int32), ('pcr_pid', C.c_int32), ('malformed', C.c_int32)]
+
+
 class FrameQuality(C.Structure):
     """dvbs2gpu_frame_quality"""
     _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('gain', C.c_float), ('phase', C.c_float), ('known_symbols', C.c_int32),
@@ -257,6 +297,21 @@ PROTOTYPES = {
     'dvbs2gpu_tsmon_get_stats': (_i, [_vp, _i, C.POINTER(TsMonStats)]),
     'dvbs2gpu_tsmon_get_pid_table': (_i, [_vp, _i, C.POINTER(TsMonPid), _i, C.POINTER(_i)]),
     'dvbs2gpu_tsmon_get_pid_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
+    'dvbs2gpu_psi_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_psi_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_psi_reset': (_i, [_vp]),
+    'dvbs2gpu_psi_destroy': (None, [_vp]),
+    'dvbs2gpu_psi_get_layout': (_i, [C.POINTER(PsiLayout)]),
+    'dvbs2gpu_psi_set_watch': (_i, [_vp, _i, _i, _i, _i]),
+    'dvbs2gpu_psi_set_deliver': (_i, [_vp, _i, _i]),
+    'dvbs2gpu_psi_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    'dvbs2gpu_psi_work': (_i, [_vp, _i, _vp, _i, _vp, _i]),
+    'dvbs2gpu_psi_get_needed': (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),
+    'dvbs2gpu_psi_get_stats': (_i, [_vp, _i, _i, C.POINTER(PsiStats)]),
+    'dvbs2gpu_psi_get_section_table': (_i, [_vp, _i, C.POINTER(PsiSection), _i, C.POINTER(_i)]),
+    'dvbs2gpu_psi_get_section_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
+    'dvbs2gpu_psi_get_programs': (_i, [_vp, _i, C.POINTER(PsiPat), C.POINTER(PsiProgram), _i, C.POINTER(_i)]),
+    'dvbs2gpu_psi_get_program_map': (_i, [_vp, _i, _i, C.POINTER(PsiPmt), C.POINTER(PsiEs), _i, C.POINTER(_i)]),
 }
 
 _lib = None
@@ -1216,6 +1271,146 @@ class TsMonitorBank(_Handle):
         p, n = C.c_void_p(), C.c_int()
         self._check(self.lib.dvbs2gpu_tsmon_get_pid_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
         return p.value, n.value
+
+
+class PsiBank(_Handle):
+    """PSI section bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, PSI section bank): PAT / PMT / SI section
+    reassembly with CRC-32 on up to 16 watched PIDs per stream, one table row per section, the decoded PAT and PMTs on the host."""
+    _destroy = 'dvbs2gpu_psi_destroy'
+    SLOTS = 16
+    CRC_ERROR, CHANGED = 1, 2
+    ROW_KEYS = tuple(k for k, _ in PsiSection._fields_)
+
+    def __init__(self, engine, nstreams=1, max_packets=4096, max_sections=1024):
+        self.eng, self.lib, self.nstreams, self.max_packets, self.max_sections = engine, engine.lib, nstreams, max_packets, max_sections
+        h = C.c_void_p()
+        engine._check(self.lib.dvbs2gpu_psi_create(engine.h, nstreams, max_packets, max_sections, C.byref(h)))
+        self.h = h
+        self._watched = [{0: 0} for _ in range(nstreams)]           # per stream: slot -> PID, as set_watch left them
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096, max_sections=1024):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        self = cls.__new__(cls)
+        self.eng, self.lib, self.nstreams, self.max_packets, self.max_sections = None, load_library(), nstreams, max_packets, max_sections
+        h = C.c_void_p()
+        self._check(self.lib.dvbs2gpu_psi_create_host(nstreams, max_packets, max_sections, C.byref(h)))
+        self.h = h
+        self._watched = [{0: 0} for _ in range(nstreams)]
+        return self
+
+    def _check(self, rc):
+        if rc < 0:
+            raise Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+        return rc
+
+    @staticmethod
+    def layout():
+        """the section syntax the library relies on (dvbs2gpu_psi_layout) as a dict"""
+        lay = PsiLayout()
+        load_library().dvbs2gpu_psi_get_layout(C.byref(lay))
+        return {k: int(getattr(lay, k)) for k, _ in PsiLayout._fields_}
+
+    def reset(self):
+        self._check(self.lib.dvbs2gpu_psi_reset(self.h))
+
+    def set_watch(self, stream, slot, pid, expect_table_id=-1):
+        """pid -1 clears the slot; the slot starts afresh"""
+        self._check(self.lib.dvbs2gpu_psi_set_watch(self.h, int(stream), int(slot), int(pid), int(expect_table_id)))
+        self._watched[int(stream)].pop(int(slot), None)
+        if pid >= 0:
+            self._watched[int(stream)][int(slot)] = int(pid)
+
+    def set_deliver(self, stream, mode):
+        self._check(self.lib.dvbs2gpu_psi_set_deliver(self.h, int(stream), int(mode)))
+
+    def follow_pat(self, stream=0):
+        """slots 1..15 of the stream start afresh and watch the PMT PIDs of the programs of the stream's PAT (program 0, the network PID,
+        is no program), in the PAT's order and expecting table_id 2, as far as the slots go -> [(program_number, pid)] of the programs
+        that did not fit.  Programs that share a PMT PID share its slot; a PMT PID that slot 0 watches already stays there."""
+        free, left, seen = list(range(1, self.SLOTS)), [], {self._watched[int(stream)].get(0, -1)}
+        for slot in free:
+            self.set_watch(stream, slot, -1)
+        for n, p in self.programs(stream)[1]:
+            if n == 0 or p in seen:
+                continue
+            if not free:
+                left.append((n, p))
+                continue
+            seen.add(p)
+            self.set_watch(stream, free.pop(0), p, 2)
+        return left
+
+    def process(self, ts_tensors, out_tensors=None, nbytes=None):
+        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors: None for rows and counters
+        only, else uint8 CUDA buffers that receive the delivered sections -> byte counts.  Dvbs2GpuError -5 carries .needed and .rows
+        when a buffer or max_sections is too small (nothing has advanced then)."""
+        n = self.nstreams
+        pin = (C.c_void_p * n)(*[t.data_ptr() for t in ts_tensors])
+        cnt = (C.c_int * n)(*[int(t.numel()) if nbytes is None else int(nbytes[i]) for i, t in enumerate(ts_tensors)])
+        nb, nr = (C.c_int * n)(), (C.c_int * n)()
+        pout, cap = None, 0
+        if out_tensors is not None:
+            pout = (C.c_void_p * n)(*[t.data_ptr() for t in out_tensors])
+            cap = min(int(t.numel()) for t in out_tensors)
+        rc = self.lib.dvbs2gpu_psi_process_batch(self.h, pin, cnt, pout, cap, nb, nr, self.eng._stream())
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            e.needed, e.rows = list(nb), list(nr)
+            raise e
+        return list(nb)
+
+    def work(self, ts, stream=0, cap=None, deliver=True):
+        """one stream, host buffers: numpy uint8 packets in -> the delivered sections back to back (numpy uint8), or None with
+        deliver=False (rows and counters only)"""
+        import numpy as np
+        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
+        cap = ts.size + self.SLOTS * 4096 if cap is None else cap
+        out = np.zeros(max(cap, 1), np.uint8) if deliver else None
+        rc = self.lib.dvbs2gpu_psi_work(self.h, int(stream), C.c_void_p(ts.ctypes.data), ts.size, C.c_void_p(out.ctypes.data) if deliver else None,
+                                        cap if deliver else 0)
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            nb, nr = C.c_int(), C.c_int()
+            self.lib.dvbs2gpu_psi_get_needed(self.h, int(stream), C.byref(nb), C.byref(nr))
+            e.needed, e.rows = nb.value, nr.value
+            raise e
+        return out[:rc].copy() if deliver else None
+
+    def stats(self, stream=0, slot=-1):
+        st = PsiStats()
+        self._check(self.lib.dvbs2gpu_psi_get_stats(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in PsiStats._fields_}
+
+    def section_table(self, stream=0):
+        """one dict per section of the last call (the fields of dvbs2gpu_psi_section), in row order"""
+        n = C.c_int()
+        self._check(self.lib.dvbs2gpu_psi_get_section_table(self.h, int(stream), None, 0, C.byref(n)))
+        rows = (PsiSection * max(n.value, 1))()
+        self._check(self.lib.dvbs2gpu_psi_get_section_table(self.h, int(stream), rows, n.value, C.byref(n)))
+        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows[:n.value]]
+
+    def section_table_device(self, stream=0):
+        """(device pointer or None, rows): the same table as dvbs2gpu_psi_section records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self.lib.dvbs2gpu_psi_get_section_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def programs(self, stream=0):
+        """-> ({transport_stream_id, version, malformed}, [(program_number, pid)]) from the PAT the stream holds (-1, -1: none)"""
+        hdr, n = PsiPat(), C.c_int()
+        self._check(self.lib.dvbs2gpu_psi_get_programs(self.h, int(stream), C.byref(hdr), None, 0, C.byref(n)))
+        rows = (PsiProgram * max(n.value, 1))()
+        self._check(self.lib.dvbs2gpu_psi_get_programs(self.h, int(stream), C.byref(hdr), rows, n.value, C.byref(n)))
+        return {k: int(getattr(hdr, k)) for k, _ in PsiPat._fields_}, [(r.program_number, r.pid) for r in rows[:n.value]]
+
+    def program_map(self, stream=0, slot=1):
+        """-> ({program_number, version, pcr_pid, malformed}, [(stream_type, elementary_pid)]) from the slot's PMT (program_number -1: none)"""
+        hdr, n = PsiPmt(), C.c_int()
+        self._check(self.lib.dvbs2gpu_psi_get_program_map(self.h, int(stream), int(slot), C.byref(hdr), None, 0, C.byref(n)))
+        rows = (PsiEs * max(n.value, 1))()
+        self._check(self.lib.dvbs2gpu_psi_get_program_map(self.h, int(stream), int(slot), C.byref(hdr), rows, n.value, C.byref(n)))
+        return {k: int(getattr(hdr, k)) for k, _ in PsiPmt._fields_}, [(r.stream_type, r.elementary_pid) for r in rows[:n.value]]
 
 
 class SegmentReceiver(_Handle):

@@ -1,0 +1,794 @@
+// PSI section bank (own extension; include/dvbs2gpu.h): PAT / PMT / SI section reassembly with CRC-32 on up to 16
+// watched PIDs of each of `nstreams` transport streams in HBM.  Every rule is in psi_rules.h, whose PsiHostStream is the sequential
+// definition, the host bank and the kernels' yardstick; this file says how a call's packets are cut into independent pieces.
+//
+// What makes the parallel form possible: a section STARTS only behind the pointer field of a PUSI packet (a packet without PUSI only
+// continues an open section and ignores what is left), so all section boundaries of a packet chain from its own pointer and the
+// chain never leaves the packet; only the LAST section of a PUSI packet can reach into later packets, and it ends at the latest in
+// the pointer bytes of the slot's next PUSI packet.
+//
+//   psi_scan_kernel    one workgroup per stream.
+//     A  every packet's header is read once (the two dwords of tsmon.hip) and its PID matched against the 16 watch entries; the
+//        watched packets are compacted in input order into LDS (an exact prefix sum over a contiguous run of packets per thread),
+//        with payload start and pointer byte.
+//     B  one lane per slot takes the continuity steps of its packets in order (tsmon_step, from the slot's state byte) and classes
+//        each: SKIP (duplicate, no payload), CUT (drops an open section and brings nothing), CONT, PUSI, PUSI after a break.
+//     C  one lane per PUSI packet hops from section header to section header inside its packet and follows the section that the
+//        packet's end cuts through the slot's next packets until it is complete, dropped or the call ends; one lane per slot does
+//        the same for the section carried in from the last call.  A first pass counts the rows every packet ends (at most one
+//        carried section, then its own), a prefix sum in input order numbers them -- the row order of the rules -- and the second
+//        pass writes one record (first packet, offset, last packet, bytes) per row.
+//     D  one wave per row gathers the section's pieces into LDS, each lane takes the CRC of 64 bytes from a zero register
+//        (crc32m_byte), the lanes' registers are shifted to the section's end (crc32m_mulmod, crc32m_xpow) and summed; the row's
+//        fields come from the gathered bytes.
+//     E  one lane per slot walks the slot's rows in order for CHANGED (the one sequential dependency between sections); a prefix sum
+//        over the rows gives the output offsets; the changed PAT / PMT sections are gathered once more into the view staging.
+//   psi_commit_kernel  (once the host has seen that every stream's bytes and rows fit) one workgroup per stream: a wave per delivered
+//     row gathers the section and stores it at its offset, a dword per lane where the destination allows; then the open section
+//     goes to the slot's 4 KiB buffer and the slots' new states are stored.
+// Two launches per call, one device-to-host copy of the per-stream call record (PsiCall), and one small copy per changed PAT / PMT.
+#include "ctx.h"
+#include "psi_rules.h"
+
+#include <memory>
+
+using namespace s2;
+#define g_err last_error()
+
+namespace s2 {
+
+constexpr int PSI_MAX_PACKETS = 4096;            // per stream and call: 10 bytes of LDS per packet (scan; 6 in commit) beside 17 KiB of gathered sections
+constexpr int PSI_WG = 256, PSI_WAVES = PSI_WG / 64;
+constexpr int PSI_SEC_LDS = PSI_BUF + PSI_BUF / 64 * 4;    // a gathered section, 4 bytes of padding behind every 64: lane L's chunk starts in bank 17 L
+static_assert(sizeof(PsiRow) == sizeof(dvbs2gpu_psi_section) && sizeof(PsiRow) == 24, "row layout");
+static_assert(sizeof(PsiLayout) == sizeof(dvbs2gpu_psi_layout), "layout layout");
+static_assert(sizeof(PsiProgram) == sizeof(dvbs2gpu_psi_program) && sizeof(PsiEs) == sizeof(dvbs2gpu_psi_es), "view rows");
+static_assert(sizeof(PsiPatHeader) == sizeof(dvbs2gpu_psi_pat) && sizeof(PsiPmtHeader) == sizeof(dvbs2gpu_psi_pmt), "view headers");
+
+enum { PK_SKIP = 0, PK_CUT, PK_CONT, PK_PUSI, PK_PUSI_BRK };
+enum { C_PACKETS = 0, C_SECTIONS, C_VALID, C_CHANGED, C_CRC, C_DROPPED, C_MALSEC, C_MALPKT, C_SCR, C_UNEXP, C_BYTES };
+static_assert(sizeof(PsiCnt) == PSI_NCNT * sizeof(int32_t) && C_BYTES == PSI_NCNT - 1, "counter order");
+
+struct PsiDevSlot { uint32_t last4; uint16_t fill; uint8_t cont, has_last; };
+// a section of the call: its first byte at offset `at` of watched packet j0 (j0 -1: carried in, the slot's buffer comes first), its
+// last byte in watched packet j1.  As the open section of a slot: j0 -2 none
+struct PsiRec { int32_t j0, j1; uint16_t at, slot; int32_t total; };
+struct PsiCall { int32_t needed, nrows, watched, pad; uint16_t view_len[PSI_SLOTS]; PsiCnt cnt[PSI_SLOTS]; };
+
+// a watched packet in LDS.  wa: index k bits 0-12, slot 13-16, class 17-19 (after the walk); before it CC 20-23, AFC 24-25, DI 26,
+// PUSI 27, scrambled 28.  wb: payload start (188: none) | pointer byte << 8
+__device__ inline int wa_k(unsigned e) { return (int)(e & 0x1fff); }
+__device__ inline int wa_slot(unsigned e) { return (int)(e >> 13 & 15); }
+__device__ inline int wa_kind(unsigned e) { return (int)(e >> 17 & 7); }
+__device__ inline int psi_sx(int i) { return i + (i >> 6) * 4; }
+
+typedef unsigned __attribute__((aligned(1))) psi_unaligned_u32;
+__device__ inline TsmonHdr psi_load(const uint8_t* __restrict__ ts, int k, unsigned* b4) {
+    const uint8_t* p = ts + (size_t)k * TSMON_TS;
+    const unsigned a = *reinterpret_cast<const psi_unaligned_u32*>(p), b = *reinterpret_cast<const psi_unaligned_u32*>(p + 4);
+    const uint8_t h[8] = {(uint8_t)a, (uint8_t)(a >> 8), (uint8_t)(a >> 16), (uint8_t)(a >> 24), (uint8_t)b, (uint8_t)(b >> 8), 0, 0};
+    *b4 = b & 255;
+    return tsmon_parse(h);
+}
+__device__ inline int psi_match(const TsmonHdr& h, const PsiWatch* w) {
+    if (h.cls != TSMON_DATA) return -1;
+    for (int s = 0; s < PSI_SLOTS; ++s) if (w[s].pid == h.pid) return s;
+    return -1;
+}
+
+// exclusive prefix sum of one int per thread over the workgroup; *total: the sum.  wsum: PSI_WAVES ints of LDS
+__device__ inline int psi_block_scan(int v, int* wsum, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+    for (int k = 1; k < 64; k <<= 1) { const int t = __shfl_up(inc, k); if (lane >= k) inc += t; }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int base = 0, sum = 0;
+    for (int w = 0; w < PSI_WAVES; ++w) { if (w < wave) base += wsum[w]; sum += wsum[w]; }
+    __syncthreads();
+    *total = sum;
+    return base + inc - v;
+}
+
+struct PsiView {                                 // what the section walkers read of one stream
+    const uint8_t* ts; const unsigned* wa; const uint16_t* wb; int W;
+    const uint8_t* sbuf;                         // the stream's 16 section buffers
+    const PsiDevSlot* ss;                        // the slots' states before the call
+};
+struct PsiOut {
+    int* rc; PsiRec* rec; PsiRec* open; PsiDevSlot* nss; int (*cnt)[PSI_NCNT]; int max_sections;
+};
+
+// the pieces of section r, in order, into dst (indexed through psi_sx): all 64 lanes of a wave
+__device__ inline void psi_copy_in(uint8_t* dst, int pos, const uint8_t* src, int len, int lane) {
+    for (int i = lane; i < len; i += 64) dst[psi_sx(pos + i)] = src[i];
+}
+__device__ void psi_gather(uint8_t* dst, const PsiRec& r, const PsiView& v, int lane) {
+    const int total = r.total < PSI_BUF ? r.total : PSI_BUF;
+    int pos, jn = 0;
+    if (r.j0 < 0) {
+        pos = v.ss[r.slot].fill < total ? v.ss[r.slot].fill : total;
+        psi_copy_in(dst, 0, v.sbuf + (size_t)r.slot * PSI_BUF, pos, lane);
+    } else {
+        pos = TSMON_TS - r.at < total ? TSMON_TS - r.at : total;
+        psi_copy_in(dst, 0, v.ts + (size_t)wa_k(v.wa[r.j0]) * TSMON_TS + r.at, pos, lane);
+        jn = r.j0 + 1;
+    }
+    for (int j = jn; pos < total && j < v.W; ++j) {
+        const unsigned e = v.wa[j];
+        if (wa_slot(e) != r.slot || wa_kind(e) == PK_SKIP) continue;
+        if (wa_kind(e) != PK_CONT && wa_kind(e) != PK_PUSI) break;
+        const int ps = v.wb[j] & 255, lo = wa_kind(e) == PK_PUSI ? ps + 1 : ps, avail = wa_kind(e) == PK_PUSI ? v.wb[j] >> 8 : TSMON_TS - ps;
+        const int len = avail < total - pos ? avail : total - pos;
+        psi_copy_in(dst, pos, v.ts + (size_t)wa_k(e) * TSMON_TS + lo, len, lane);
+        pos += len;
+    }
+}
+
+// The open section of `slot` -- `fill` bytes so far, header bytes b1, b2 where fill reaches them, first byte at (j0, at) -- through
+// the slot's packets from watched packet jn on: rules 4 and 5.  One lane.
+template <bool WRITE>
+__device__ void psi_resolve(const PsiView& v, const PsiOut& o, int slot, int j0, int at, int fill, unsigned b1, unsigned b2, int jn) {
+    enum { R_OPEN, R_DONE, R_DROPPED, R_BAD_LENGTH };
+    int outcome = R_OPEN, endj = -1, total = 0;
+    for (int j = jn; j < v.W; ++j) {
+        const unsigned e = v.wa[j];
+        const int kind = wa_kind(e);
+        if (wa_slot(e) != slot || kind == PK_SKIP) continue;
+        if (kind == PK_CUT || kind == PK_PUSI_BRK) { outcome = R_DROPPED; break; }
+        const int ps = v.wb[j] & 255, lo = kind == PK_PUSI ? ps + 1 : ps, avail = kind == PK_PUSI ? v.wb[j] >> 8 : TSMON_TS - ps;
+        const uint8_t* p = v.ts + (size_t)wa_k(e) * TSMON_TS + lo;
+        int used = 0;
+        while (fill < PSI.header_bytes && used < avail) {
+            const unsigned byte = p[used++];
+            if (fill == 1) b1 = byte; else if (fill == 2) b2 = byte;
+            ++fill;
+        }
+        if (fill >= PSI.header_bytes) {
+            if (psi_section_length(b1, b2) > PSI.max_section_length) { outcome = R_BAD_LENGTH; break; }
+            total = PSI.header_bytes + psi_section_length(b1, b2);
+            fill += avail - used < total - fill ? avail - used : total - fill;
+            if (fill == total) { outcome = R_DONE; endj = j; break; }
+        }
+        if (kind == PK_PUSI) { outcome = R_DROPPED; break; }
+    }
+    if (outcome == R_DONE) {
+        const bool row = !((b1 >> 7) && total < PSI.min_long_section);
+        if (!WRITE) { if (row) atomicAdd(&o.rc[endj], 1); }
+        else if (!row) atomicAdd(&o.cnt[slot][C_MALSEC], 1);
+        else {
+            const int r = o.rc[endj] >> 1;
+            if (r < o.max_sections) { const PsiRec rec = {j0, endj, (uint16_t)at, (uint16_t)slot, total}; o.rec[r] = rec; }
+        }
+    } else if (WRITE) {
+        if (outcome == R_DROPPED) atomicAdd(&o.cnt[slot][C_DROPPED], 1);
+        else if (outcome == R_BAD_LENGTH) atomicAdd(&o.cnt[slot][C_MALSEC], 1);
+        else { const PsiRec rec = {j0, v.W, (uint16_t)at, (uint16_t)slot, fill}; o.open[slot] = rec; o.nss[slot].fill = (uint16_t)fill; }
+    }
+}
+
+// watched packet j, a PUSI packet: the section starts behind its pointer (rule 6).  One lane.
+template <bool WRITE>
+__device__ void psi_pusi_job(const PsiView& v, const PsiOut& o, int j) {
+    const unsigned e = v.wa[j];
+    const int slot = wa_slot(e), ps = v.wb[j] & 255, ptr = v.wb[j] >> 8;
+    const uint8_t* p = v.ts + (size_t)wa_k(e) * TSMON_TS;
+    const int base = WRITE ? (o.rc[j] >> 1) + (o.rc[j] & 1) : 0;
+    int at = ps + 1 + ptr, i = 0;
+    while (at < TSMON_TS) {
+        if (p[at] == 0xFF) break;
+        const int have = TSMON_TS - at;
+        const unsigned b1 = have >= 2 ? p[at + 1] : 0, b2 = have >= 3 ? p[at + 2] : 0;
+        if (have >= PSI.header_bytes) {
+            if (psi_section_length(b1, b2) > PSI.max_section_length) { if (WRITE) atomicAdd(&o.cnt[slot][C_MALSEC], 1); break; }
+            const int total = PSI.header_bytes + psi_section_length(b1, b2);
+            if (total <= have) {
+                if ((b1 >> 7) && total < PSI.min_long_section) { if (WRITE) atomicAdd(&o.cnt[slot][C_MALSEC], 1); }
+                else {
+                    if (WRITE && base + i < o.max_sections) { const PsiRec rec = {j, j, (uint16_t)at, (uint16_t)slot, total}; o.rec[base + i] = rec; }
+                    ++i;
+                }
+                at += total;
+                continue;
+            }
+        }
+        psi_resolve<WRITE>(v, o, slot, j, at, have, b1, b2, j + 1);
+        break;
+    }
+    if (!WRITE && i) atomicAdd(&o.rc[j], 2 * i);
+}
+
+template <bool WRITE>
+__device__ void psi_jobs(const PsiView& v, const PsiOut& o, const PsiWatch* w) {
+    for (int t = threadIdx.x; t < v.W + PSI_SLOTS; t += PSI_WG) {
+        if (t < PSI_SLOTS) {
+            const int fill = v.ss[t].fill;
+            if (w[t].pid < 0 || fill <= 0) continue;
+            const uint8_t* sb = v.sbuf + (size_t)t * PSI_BUF;
+            psi_resolve<WRITE>(v, o, t, -1, 0, fill, fill >= 2 ? sb[1] : 0, fill >= 3 ? sb[2] : 0, 0);
+        } else if (wa_kind(v.wa[t - PSI_SLOTS]) >= PK_PUSI) psi_pusi_job<WRITE>(v, o, t - PSI_SLOTS);
+    }
+}
+
+// phase A of both kernels: the watched packets of the stream into wa / wb, in input order; returns their number
+__device__ int psi_collect(const uint8_t* __restrict__ ts, int n, const PsiWatch* w, unsigned* wa, uint16_t* wb, int* wsum) {
+    const int tid = threadIdx.x;
+    const int chunk = (n + PSI_WG - 1) / PSI_WG, k0 = tid * chunk, k1 = k0 + chunk < n ? k0 + chunk : n;   // <= 16 packets per thread
+    unsigned mask = 0, b4;
+    for (int k = k0; k < k1; ++k) mask |= (unsigned)(psi_match(psi_load(ts, k, &b4), w) >= 0) << (k - k0);
+    int W;
+    int at = psi_block_scan(__popc(mask), wsum, &W);
+    for (int k = k0; k < k1; ++k) {
+        if (!(mask >> (k - k0) & 1)) continue;
+        const TsmonHdr h = psi_load(ts, k, &b4);
+        int ps = psi_payload_start(h.afc, b4);
+        if (ps > TSMON_TS) ps = TSMON_TS;
+        const unsigned ptr = (h.pusi && (h.afc & 1) && ps < TSMON_TS) ? ts[(size_t)k * TSMON_TS + ps] : 0;
+        wa[at] = (unsigned)k | (unsigned)psi_match(h, w) << 13 | (unsigned)h.cc << 20 | (unsigned)h.afc << 24 | (unsigned)h.di << 26 |
+                 (unsigned)h.pusi << 27 | (unsigned)(h.tsc != 0) << 28;
+        wb[at] = (uint16_t)(ps | ptr << 8);
+        ++at;
+    }
+    __syncthreads();
+    return W;
+}
+
+// dynamic LDS: wa[max_packets] (dwords), rc[max_packets] (dwords), wb[max_packets] (16 bits each)
+__global__ void __launch_bounds__(PSI_WG) psi_scan_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nbytes, int max_packets,
+                                                          int max_sections, const PsiWatch* __restrict__ watch, const int* __restrict__ deliver,
+                                                          const PsiDevSlot* __restrict__ state, PsiDevSlot* __restrict__ newst,
+                                                          const uint8_t* __restrict__ bufs, uint8_t* __restrict__ views, unsigned* __restrict__ wa_g,
+                                                          uint16_t* __restrict__ wb_g, PsiRec* __restrict__ recs, PsiRec* __restrict__ opens,
+                                                          PsiRow* __restrict__ rows_g, PsiCall* __restrict__ call, int have_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned psi_lds[];
+    __shared__ __attribute__((aligned(16))) uint8_t sec[PSI_WAVES][PSI_SEC_LDS];
+    __shared__ int cnt[PSI_SLOTS][PSI_NCNT], wsum[PSI_WAVES], view_row[PSI_SLOTS];
+    __shared__ PsiWatch w[PSI_SLOTS];
+    __shared__ PsiDevSlot ss[PSI_SLOTS], nss[PSI_SLOTS];
+    unsigned* wa = psi_lds;
+    int* rc = reinterpret_cast<int*>(psi_lds + max_packets);
+    uint16_t* wb = reinterpret_cast<uint16_t*>(psi_lds + 2 * (size_t)max_packets);
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int n = nbytes[s] / TSMON_TS;
+    if (n > max_packets) n = max_packets;            // (the host has refused such a call)
+    if (tid < PSI_SLOTS) {
+        w[tid] = watch[(size_t)s * PSI_SLOTS + tid];
+        ss[tid] = state[(size_t)s * PSI_SLOTS + tid];
+        nss[tid] = ss[tid];
+        view_row[tid] = -1;
+        for (int c = 0; c < PSI_NCNT; ++c) cnt[tid][c] = 0;
+        const PsiRec none = {-2, 0, 0, (uint16_t)tid, 0};
+        opens[(size_t)s * PSI_SLOTS + tid] = none;
+    }
+    __syncthreads();
+    const uint8_t* ts = in[s];
+    const int W = n > 0 ? psi_collect(ts, n, w, wa, wb, wsum) : 0;
+    // B: the continuity walk, one lane per slot
+    if (tid < PSI_SLOTS && w[tid].pid >= 0) {
+        uint8_t st = ss[tid].cont;
+        int c_pk = 0, c_scr = 0, c_mal = 0;
+        for (int j = 0; j < W; ++j) {
+            const unsigned e = wa[j];
+            if (wa_slot(e) != tid) continue;
+            const int cc = e >> 20 & 15, afc = e >> 24 & 3, di = e >> 26 & 1, pusi = e >> 27 & 1, ps = wb[j] & 255, ptr = wb[j] >> 8;
+            int kind;
+            ++c_pk;
+            const int v = tsmon_step(&st, afc, cc, di);
+            const bool brk = v == TSMON_CC_ERROR || v == TSMON_DISC;
+            if (e >> 28 & 1) { ++c_scr; kind = PK_CUT; }
+            else if (v == TSMON_DUPLICATE) kind = PK_SKIP;
+            else if (!(afc & 1)) kind = brk ? PK_CUT : PK_SKIP;
+            else if (ps >= TSMON_TS || (pusi && ptr > TSMON_TS - ps - 1)) { ++c_mal; kind = PK_CUT; }
+            else if (pusi) kind = brk ? PK_PUSI_BRK : PK_PUSI;
+            else kind = brk ? PK_CUT : PK_CONT;
+            wa[j] = (e & 0x1ffffu) | (unsigned)kind << 17;  // (the other slots' lanes read this word for its slot bits only, which stay)
+        }
+        nss[tid].cont = st;
+        nss[tid].fill = 0;
+        cnt[tid][C_PACKETS] = c_pk; cnt[tid][C_SCR] = c_scr; cnt[tid][C_MALPKT] = c_mal;
+    }
+    for (int j = tid; j < W; j += PSI_WG) rc[j] = 0;
+    __syncthreads();
+    // C: sections
+    const PsiView v = {ts, wa, wb, W, bufs + (size_t)s * PSI_SLOTS * PSI_BUF, ss};
+    PsiRec* rec = recs + (size_t)s * max_sections;
+    const PsiOut o = {rc, rec, opens + (size_t)s * PSI_SLOTS, nss, cnt, max_sections};
+    psi_jobs<false>(v, o, w);
+    __syncthreads();
+    int nrows;
+    {
+        const int chunk = (W + PSI_WG - 1) / PSI_WG, j0 = tid * chunk, j1 = j0 + chunk < W ? j0 + chunk : W;
+        int mine = 0;
+        for (int j = j0; j < j1; ++j) mine += (rc[j] >> 1) + (rc[j] & 1);
+        int run = psi_block_scan(mine, wsum, &nrows);
+        for (int j = j0; j < j1; ++j) { const int c = rc[j]; rc[j] = run << 1 | (c & 1); run += (c >> 1) + (c & 1); }
+    }
+    __syncthreads();
+    const bool fits = nrows <= max_sections;
+    PsiRow* rows = rows_g + (size_t)s * max_sections;
+    int needed = fits ? 0 : -1;
+    if (fits) {
+        psi_jobs<true>(v, o, w);
+        __syncthreads();
+        // D: a wave per row
+        for (int r0 = 0; r0 < nrows; r0 += PSI_WAVES) {
+            const int r = r0 + wave;
+            PsiRec q = {0, 0, 0, 0, 0};
+            if (r < nrows) { q = rec[r]; psi_gather(sec[wave], q, v, lane); }
+            __syncthreads();
+            if (r < nrows) {
+                const uint8_t* sb = sec[wave];
+                const int total = q.total < PSI_BUF ? q.total : PSI_BUF, start = 64 * lane;
+                const int len = total - start < 0 ? 0 : (total - start < 64 ? total - start : 64);
+                uint32_t c = 0;
+                for (int i = 0; i < len; i += 4) {
+                    const unsigned d = *reinterpret_cast<const unsigned*>(sb + 68 * lane + i);
+                    for (int b = 0; b < 4; ++b) if (i + b < len) c = crc32m_byte(c, d >> (8 * b) & 255);
+                }
+                uint32_t x = len > 0 ? crc32m_mulmod(c, crc32m_xpow((uint32_t)(total - start - len))) : 0;
+                if (lane == 0) x ^= crc32m_mulmod(0xFFFFFFFFu, crc32m_xpow((uint32_t)total));
+                for (int k = 32; k > 0; k >>= 1) x ^= __shfl_xor(x, k);
+                if (lane == 0) {
+                    auto rd = [&](int i) { return (unsigned)sb[psi_sx(i)]; };
+                    const bool valid = !(rd(1) >> 7) || x == 0;
+                    PsiRow row = psi_row_fields(rd, total, w[q.slot].pid, valid, q.j0 < 0 ? -1 : wa_k(wa[q.j0]));
+                    uint32_t l4 = 0;
+                    for (int i = total < 4 ? 0 : total - 4; i < total; ++i) l4 = l4 << 8 | rd(i);
+                    row.offset = (int32_t)l4;                   // until phase E has used it
+                    rows[r] = row;
+                }
+            }
+            __syncthreads();
+        }
+        // E: CHANGED, one lane per slot over its rows in order
+        if (tid < PSI_SLOTS && w[tid].pid >= 0) {
+            uint32_t last = ss[tid].last4;
+            int has = ss[tid].has_last, c_sec = 0, c_valid = 0, c_chg = 0, c_crc = 0, c_unexp = 0;
+            for (int r = 0; r < nrows; ++r) {
+                if (rec[r].slot != tid) continue;
+                PsiRow row = rows[r];
+                ++c_sec;
+                c_unexp += w[tid].expect >= 0 && row.table_id != w[tid].expect;
+                if (row.flags & PSI_CRC_ERROR) ++c_crc;
+                else {
+                    ++c_valid;
+                    if (!has || (uint32_t)row.offset != last) { row.flags |= PSI_CHANGED; ++c_chg; rows[r].flags = row.flags; }
+                    has = 1; last = (uint32_t)row.offset;
+                    if (psi_is_view(row)) view_row[tid] = r;
+                }
+            }
+            nss[tid].last4 = last; nss[tid].has_last = (uint8_t)has;
+            cnt[tid][C_SECTIONS] = c_sec; cnt[tid][C_VALID] = c_valid; cnt[tid][C_CHANGED] = c_chg; cnt[tid][C_CRC] = c_crc; cnt[tid][C_UNEXP] = c_unexp;
+        }
+        __syncthreads();
+        {   // the output offsets: an exact prefix sum in row order
+            const int mode = deliver[s];
+            const int chunk = (nrows + PSI_WG - 1) / PSI_WG, r0 = tid * chunk, r1 = r0 + chunk < nrows ? r0 + chunk : nrows;
+            auto bytes_of = [&](int r) { return have_out && (mode == 0 || (rows[r].flags & PSI_CHANGED)) ? rows[r].length : 0; };
+            int mine = 0;
+            for (int r = r0; r < r1; ++r) mine += bytes_of(r);
+            int at = psi_block_scan(mine, wsum, &needed);
+            for (int r = r0; r < r1; ++r) {
+                const int b = bytes_of(r);
+                rows[r].offset = b ? at : -1;
+                if (b) atomicAdd(&cnt[rec[r].slot][C_BYTES], b);
+                at += b;
+            }
+        }
+        // the changed PAT / PMT sections, once more, for the host's decoded views
+        for (int s0 = 0; s0 < PSI_SLOTS; s0 += PSI_WAVES) {
+            const int sl = s0 + wave, r = view_row[sl];
+            PsiRec q = {0, 0, 0, 0, 0};
+            if (r >= 0) { q = rec[r]; psi_gather(sec[wave], q, v, lane); }
+            __syncthreads();
+            if (r >= 0) {
+                uint8_t* dst = views + ((size_t)s * PSI_SLOTS + sl) * PSI_BUF;
+                for (int i = lane; i < q.total && i < PSI_BUF; i += 64) dst[i] = sec[wave][psi_sx(i)];
+            }
+            __syncthreads();
+        }
+    }
+    for (int j = tid; j < W; j += PSI_WG) { wa_g[(size_t)s * max_packets + j] = wa[j]; wb_g[(size_t)s * max_packets + j] = wb[j]; }
+    if (tid < PSI_SLOTS) {
+        newst[(size_t)s * PSI_SLOTS + tid] = nss[tid];
+        PsiCall* c = call + s;
+        if (tid == 0) { c->needed = needed; c->nrows = nrows; c->watched = W; c->pad = 0; }
+        c->view_len[tid] = (uint16_t)(fits && view_row[tid] >= 0 ? rec[view_row[tid]].total : 0);
+        int32_t* dst = reinterpret_cast<int32_t*>(&c->cnt[tid]);
+        for (int k = 0; k < PSI_NCNT; ++k) dst[k] = cnt[tid][k];
+    }
+}
+
+// dynamic LDS: wa[max_packets] (dwords), wb[max_packets] (16 bits each)
+__global__ void __launch_bounds__(PSI_WG) psi_commit_kernel(const uint8_t* const* __restrict__ in, uint8_t* const* __restrict__ out, int max_packets,
+                                                            int max_sections, int cap, PsiDevSlot* __restrict__ state,
+                                                            const PsiDevSlot* __restrict__ newst, uint8_t* __restrict__ bufs,
+                                                            const unsigned* __restrict__ wa_g, const uint16_t* __restrict__ wb_g,
+                                                            const PsiRec* __restrict__ recs, const PsiRec* __restrict__ opens,
+                                                            const PsiRow* __restrict__ rows_g, const PsiCall* __restrict__ call) {
+    extern __shared__ __attribute__((aligned(16))) unsigned psi_lds[];
+    __shared__ __attribute__((aligned(16))) uint8_t sec[PSI_WAVES][PSI_SEC_LDS];
+    __shared__ PsiDevSlot ss[PSI_SLOTS];
+    unsigned* wa = psi_lds;
+    uint16_t* wb = reinterpret_cast<uint16_t*>(psi_lds + max_packets);
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int W = call[s].watched, nrows = call[s].nrows;
+    if (W > max_packets) W = max_packets;
+    if (nrows > max_sections) nrows = max_sections;
+    for (int j = tid; j < W; j += PSI_WG) { wa[j] = wa_g[(size_t)s * max_packets + j]; wb[j] = wb_g[(size_t)s * max_packets + j]; }
+    if (tid < PSI_SLOTS) ss[tid] = state[(size_t)s * PSI_SLOTS + tid];
+    __syncthreads();
+    uint8_t* sbuf = bufs + (size_t)s * PSI_SLOTS * PSI_BUF;
+    const PsiView v = {in[s], wa, wb, W, sbuf, ss};
+    const PsiRec* rec = recs + (size_t)s * max_sections;
+    const PsiRow* rows = rows_g + (size_t)s * max_sections;
+    uint8_t* o = out ? out[s] : nullptr;
+    for (int r0 = 0; o && r0 < nrows; r0 += PSI_WAVES) {
+        const int r = r0 + wave;
+        int off = -1, total = 0;
+        if (r < nrows) { off = rows[r].offset; total = rows[r].length < PSI_BUF ? rows[r].length : PSI_BUF; }
+        if (off < 0 || off + total > cap) off = -1;
+        if (off >= 0) psi_gather(sec[wave], rec[r], v, lane);
+        __syncthreads();
+        if (off >= 0) {
+            uint8_t* d = o + off;
+            const uint8_t* sb = sec[wave];
+            int head = (int)((4 - (reinterpret_cast<uintptr_t>(d) & 3)) & 3);
+            if (head > total) head = total;
+            const int nd = (total - head) / 4;
+            if (lane < head) d[lane] = sb[psi_sx(lane)];
+            for (int i = lane; i < nd; i += 64) {
+                const int b = head + 4 * i;
+                *reinterpret_cast<unsigned*>(d + b) = (unsigned)sb[psi_sx(b)] | (unsigned)sb[psi_sx(b + 1)] << 8 | (unsigned)sb[psi_sx(b + 2)] << 16 |
+                                                      (unsigned)sb[psi_sx(b + 3)] << 24;
+            }
+            const int tail = head + 4 * nd;
+            if (lane < total - tail) d[tail + lane] = sb[psi_sx(tail + lane)];
+        }
+        __syncthreads();
+    }
+    // the open sections into the slots' buffers (what they read of the buffers is in LDS before the barrier), then the states
+    for (int s0 = 0; s0 < PSI_SLOTS; s0 += PSI_WAVES) {
+        const int sl = s0 + wave;
+        const PsiRec q = opens[(size_t)s * PSI_SLOTS + sl];
+        if (q.j0 > -2) psi_gather(sec[wave], q, v, lane);
+        __syncthreads();
+        if (q.j0 > -2) for (int i = lane; i < q.total && i < PSI_BUF; i += 64) sbuf[(size_t)sl * PSI_BUF + i] = sec[wave][psi_sx(i)];
+        __syncthreads();
+    }
+    if (tid < PSI_SLOTS) state[(size_t)s * PSI_SLOTS + tid] = newst[(size_t)s * PSI_SLOTS + tid];
+}
+
+}  // namespace s2
+
+struct dvbs2gpu_psi {
+    dvbs2gpu_ctx* ctx = nullptr;                   // null: a host-only bank (dvbs2gpu_psi_create_host)
+    int nstreams = 0, max_packets = 0, max_sections = 0;
+    std::vector<PsiWatch> watch;                   // nstreams x 16
+    std::vector<int> deliver;
+    std::vector<dvbs2gpu_psi_stats> stats;         // nstreams x 16, since reset; the kernels report each call's share (PsiCall)
+    std::vector<int> nrows, need_bytes, need_rows; // of the last call per stream
+    std::vector<std::vector<uint8_t>> view;        // nstreams x 16: the decoded views' sections (device banks)
+    std::vector<PsiCall> h_call;
+    std::vector<char> h_args;
+    // device banks
+    PsiWatch* d_watch = nullptr;
+    int* d_deliver = nullptr;
+    PsiDevSlot *d_state = nullptr, *d_newst = nullptr;
+    uint8_t *d_bufs = nullptr, *d_views = nullptr; // nstreams x 16 x 4096 each
+    unsigned* d_wa = nullptr;                      // nstreams x max_packets: the watched packets of the last call
+    uint16_t* d_wb = nullptr;
+    PsiRec *d_recs = nullptr, *d_opens = nullptr;
+    PsiRow* d_rows = nullptr;                      // nstreams x max_sections
+    PsiCall* d_call = nullptr;
+    char* d_args = nullptr;                        // in[n], out[n], nbytes[n]
+    uint8_t *d_in1 = nullptr, *d_out1 = nullptr;   // staging of the host-buffer entry point
+    size_t out1_cap = 0;
+    // host-only banks
+    std::vector<PsiHostStream> host;
+};
+
+namespace s2 {
+static void psi_account(dvbs2gpu_psi* b, int i, const PsiCnt* c) {
+    for (int s = 0; s < PSI_SLOTS; ++s) {
+        int64_t* d = reinterpret_cast<int64_t*>(&b->stats[(size_t)i * PSI_SLOTS + s]);
+        const int32_t* a = reinterpret_cast<const int32_t*>(&c[s]);
+        for (int k = 0; k < PSI_NCNT; ++k) d[k] += a[k];
+    }
+}
+static_assert(sizeof(dvbs2gpu_psi_stats) == PSI_NCNT * sizeof(int64_t), "stats order");
+static bool psi_create_args_ok(int nstreams, int max_packets, int max_sections, dvbs2gpu_psi** out) {
+    if (!out || nstreams <= 0 || max_packets <= 0 || max_sections <= 0) return false;
+    if (max_packets > PSI_MAX_PACKETS) { g_err = "PSI bank: max_packets is at most 4096 per stream and call"; return false; }
+    return true;
+}
+static dvbs2gpu_psi* psi_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_sections) {
+    auto b = new dvbs2gpu_psi();
+    b->ctx = ctx; b->nstreams = nstreams; b->max_packets = max_packets; b->max_sections = max_sections;
+    b->watch.assign((size_t)nstreams * PSI_SLOTS, PsiWatch{-1, -1});
+    for (int i = 0; i < nstreams; ++i) b->watch[(size_t)i * PSI_SLOTS] = {0, 0};
+    b->deliver.assign(nstreams, 0);
+    b->stats.assign((size_t)nstreams * PSI_SLOTS, dvbs2gpu_psi_stats{});
+    b->nrows.assign(nstreams, 0); b->need_bytes.assign(nstreams, 0); b->need_rows.assign(nstreams, 0);
+    b->h_call.resize(nstreams);
+    return b;
+}
+static const std::vector<uint8_t>& psi_view_of(dvbs2gpu_psi* b, int stream, int slot) {
+    return b->ctx ? b->view[(size_t)stream * PSI_SLOTS + slot] : b->host[stream].view[slot];
+}
+}  // namespace s2
+
+extern "C" {
+
+void dvbs2gpu_psi_destroy(dvbs2gpu_psi* b) {
+    if (!b) return;
+    void* ps[] = {b->d_watch, b->d_deliver, b->d_state, b->d_newst, b->d_bufs, b->d_views, b->d_wa, b->d_wb, b->d_recs, b->d_opens, b->d_rows, b->d_call,
+                  b->d_args, b->d_in1, b->d_out1};
+    for (void* p : ps) if (p) (void)hipFree(p);
+    delete b;
+}
+
+int dvbs2gpu_psi_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_sections, dvbs2gpu_psi** out) {
+    if (!ctx || !psi_create_args_ok(nstreams, max_packets, max_sections, out)) return DVBS2GPU_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    dvbs2gpu_psi* b = psi_new(ctx, nstreams, max_packets, max_sections);
+    b->view.resize((size_t)nstreams * PSI_SLOTS);
+    const size_t n = (size_t)nstreams, ns = n * PSI_SLOTS;
+    hipError_t e = hipMalloc((void**)&b->d_watch, ns * sizeof(PsiWatch));
+    if (e == hipSuccess) e = hipMemcpy(b->d_watch, b->watch.data(), ns * sizeof(PsiWatch), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_deliver, n * sizeof(int));
+    if (e == hipSuccess) e = hipMemset(b->d_deliver, 0, n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_state, ns * sizeof(PsiDevSlot));
+    if (e == hipSuccess) e = hipMemset(b->d_state, 0, ns * sizeof(PsiDevSlot));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_newst, ns * sizeof(PsiDevSlot));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_bufs, ns * PSI_BUF);
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_views, ns * PSI_BUF);
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_wa, n * max_packets * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_wb, n * max_packets * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_recs, n * max_sections * sizeof(PsiRec));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_opens, ns * sizeof(PsiRec));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_rows, n * max_sections * sizeof(PsiRow));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_call, n * sizeof(PsiCall));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->d_args, n * 20);
+    if (e != hipSuccess) { dvbs2gpu_psi_destroy(b); return fail_hip(e, "hipMalloc(psi)"); }
+    b->h_args.resize(n * 20);
+    *out = b;
+    return 0;
+}
+
+int dvbs2gpu_psi_create_host(int nstreams, int max_packets, int max_sections, dvbs2gpu_psi** out) {
+    if (!psi_create_args_ok(nstreams, max_packets, max_sections, out)) return DVBS2GPU_ERR_ARG;
+    dvbs2gpu_psi* b = psi_new(nullptr, nstreams, max_packets, max_sections);
+    b->host.resize(nstreams);
+    *out = b;
+    return 0;
+}
+
+int dvbs2gpu_psi_reset(dvbs2gpu_psi* b) {
+    if (!b) return DVBS2GPU_ERR_ARG;
+    if (b->ctx) {
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        HIP_TRY(hipMemset(b->d_state, 0, (size_t)b->nstreams * PSI_SLOTS * sizeof(PsiDevSlot)));
+    }
+    for (auto& h : b->host) { for (int s = 0; s < PSI_SLOTS; ++s) h.clear_slot(s); h.rows.clear(); h.bytes.clear(); }
+    for (auto& v : b->view) v.clear();
+    std::fill(b->stats.begin(), b->stats.end(), dvbs2gpu_psi_stats{});
+    std::fill(b->nrows.begin(), b->nrows.end(), 0);
+    return 0;
+}
+
+int dvbs2gpu_psi_get_layout(dvbs2gpu_psi_layout* h_out) {
+    if (!h_out) return DVBS2GPU_ERR_ARG;
+    memcpy(h_out, &PSI, sizeof(PSI));
+    return 0;
+}
+
+int dvbs2gpu_psi_set_watch(dvbs2gpu_psi* b, int stream, int slot, int pid, int expect_table_id) {
+    if (!b || stream < 0 || stream >= b->nstreams || slot < 0 || slot >= PSI_SLOTS) return DVBS2GPU_ERR_ARG;
+    if (pid < -1 || pid >= TSMON_NULL_PID || expect_table_id < -1 || expect_table_id > 255) {
+        g_err = "PSI bank: a watched PID is 0..0x1FFE (-1 clears the slot), an expected table_id 0..255 or -1";
+        return DVBS2GPU_ERR_ARG;
+    }
+    PsiWatch* w = b->watch.data() + (size_t)stream * PSI_SLOTS;
+    for (int s = 0; s < PSI_SLOTS; ++s)
+        if (pid >= 0 && s != slot && w[s].pid == pid) { g_err = "PSI bank: the PID is watched in another slot of the stream"; return DVBS2GPU_ERR_ARG; }
+    const size_t at = (size_t)stream * PSI_SLOTS + slot;
+    w[slot] = {pid, pid < 0 ? -1 : expect_table_id};
+    b->stats[at] = dvbs2gpu_psi_stats{};
+    if (b->ctx) {
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        HIP_TRY(hipMemcpy(b->d_watch + at, &w[slot], sizeof(PsiWatch), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(b->d_state + at, 0, sizeof(PsiDevSlot)));
+        b->view[at].clear();
+    } else {
+        b->host[stream].watch[slot] = w[slot];
+        b->host[stream].clear_slot(slot);
+    }
+    return 0;
+}
+
+int dvbs2gpu_psi_set_deliver(dvbs2gpu_psi* b, int stream, int mode) {
+    if (!b || stream < 0 || stream >= b->nstreams) return DVBS2GPU_ERR_ARG;
+    if (mode < 0 || mode > 1) { g_err = "PSI bank: deliver mode is 0 (every section) or 1 (valid changed sections)"; return DVBS2GPU_ERR_ARG; }
+    b->deliver[stream] = mode;
+    if (b->ctx) {
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        HIP_TRY(hipMemcpy(b->d_deliver + stream, &mode, sizeof(int), hipMemcpyHostToDevice));
+    } else b->host[stream].deliver = mode;
+    return 0;
+}
+
+int dvbs2gpu_psi_process_batch(dvbs2gpu_psi* b, const uint8_t* const* d_ts, const int* nbytes, uint8_t* const* d_out, int cap, int* out_bytes,
+                               int* out_rows, void* stream) {
+    if (!b || !d_ts || !nbytes || cap < 0 || (d_out && !out_bytes)) return DVBS2GPU_ERR_ARG;
+    if (!b->ctx) { g_err = "PSI bank: a host bank takes host buffers (dvbs2gpu_psi_work)"; return DVBS2GPU_ERR_ARG; }
+    const int n = b->nstreams;
+    for (int i = 0; i < n; ++i) {
+        if (nbytes[i] < 0 || nbytes[i] % TSMON_TS) { g_err = "PSI bank: a byte count is a whole number of 188-byte packets"; return DVBS2GPU_ERR_ARG; }
+        if (nbytes[i] / TSMON_TS > b->max_packets) { g_err = "PSI bank: packet count exceeds max_packets"; return DVBS2GPU_ERR_ARG; }
+        if ((nbytes[i] > 0 && !d_ts[i]) || (d_out && (!d_out[i] || d_out[i] == d_ts[i]))) {
+            g_err = "PSI bank: null buffer, or an output buffer that is its stream's input";
+            return DVBS2GPU_ERR_ARG;
+        }
+    }
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        const uint8_t** in = reinterpret_cast<const uint8_t**>(b->h_args.data());
+        uint8_t** out = reinterpret_cast<uint8_t**>(b->h_args.data() + (size_t)n * 8);
+        int* nb = reinterpret_cast<int*>(b->h_args.data() + (size_t)n * 16);
+        for (int i = 0; i < n; ++i) { in[i] = d_ts[i]; out[i] = d_out ? d_out[i] : nullptr; nb[i] = nbytes[i]; }
+    }
+    HIP_TRY(hipMemcpyAsync(b->d_args, b->h_args.data(), b->h_args.size(), hipMemcpyHostToDevice, st));
+    const uint8_t* const* a_in = reinterpret_cast<const uint8_t* const*>(b->d_args);
+    uint8_t* const* a_out = reinterpret_cast<uint8_t* const*>(b->d_args + (size_t)n * 8);
+    const int* a_nb = reinterpret_cast<const int*>(b->d_args + (size_t)n * 16);
+    const size_t lds_scan = (size_t)b->max_packets * 10 + 16, lds_commit = (size_t)b->max_packets * 6 + 16;   // <= 40 KiB beside 18 KiB static
+    hipLaunchKernelGGL(psi_scan_kernel, dim3(n), dim3(PSI_WG), lds_scan, st, a_in, a_nb, b->max_packets, b->max_sections, b->d_watch, b->d_deliver,
+                       b->d_state, b->d_newst, b->d_bufs, b->d_views, b->d_wa, b->d_wb, b->d_recs, b->d_opens, b->d_rows, b->d_call, d_out ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_call.data(), b->d_call, sizeof(PsiCall) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    bool fits = true;
+    for (int i = 0; i < n; ++i) {
+        const PsiCall& c = b->h_call[i];
+        fits &= c.nrows <= b->max_sections && (!d_out || c.needed <= cap);
+        b->need_bytes[i] = c.needed; b->need_rows[i] = c.nrows;
+        if (out_bytes) out_bytes[i] = c.needed;
+        if (out_rows) out_rows[i] = c.nrows;
+    }
+    if (!fits) {                                       // nothing has been stored: the same call may come again with more room
+        std::fill(b->nrows.begin(), b->nrows.end(), 0);
+        g_err = "PSI bank: the sections of a stream do not fit cap, or its rows max_sections (out_bytes / out_rows hold the sizes)";
+        return DVBS2GPU_ERR_CAPACITY;
+    }
+    hipLaunchKernelGGL(psi_commit_kernel, dim3(n), dim3(PSI_WG), lds_commit, st, a_in, d_out ? a_out : nullptr, b->max_packets, b->max_sections, cap,
+                       b->d_state, b->d_newst, b->d_bufs, b->d_wa, b->d_wb, b->d_recs, b->d_opens, b->d_rows, b->d_call);
+    HIP_TRY(hipGetLastError());
+    for (int i = 0; i < n; ++i)                        // the changed PAT / PMT sections, and only those
+        for (int s = 0; s < PSI_SLOTS; ++s) {
+            const int len = b->h_call[i].view_len[s];
+            if (!len) continue;
+            std::vector<uint8_t>& v = b->view[(size_t)i * PSI_SLOTS + s];
+            v.resize(len);
+            HIP_TRY(hipMemcpyAsync(v.data(), b->d_views + ((size_t)i * PSI_SLOTS + s) * PSI_BUF, len, hipMemcpyDeviceToHost, st));
+        }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) { psi_account(b, i, b->h_call[i].cnt); b->nrows[i] = b->h_call[i].nrows; }
+    return 0;
+}
+
+int dvbs2gpu_psi_work(dvbs2gpu_psi* b, int stream, const uint8_t* h_ts, int nbytes, uint8_t* h_out, int cap) {
+    if (!b || stream < 0 || stream >= b->nstreams || nbytes < 0 || cap < 0 || (nbytes > 0 && !h_ts)) return DVBS2GPU_ERR_ARG;
+    if (nbytes % TSMON_TS) { g_err = "PSI bank: a byte count is a whole number of 188-byte packets"; return DVBS2GPU_ERR_ARG; }
+    if (nbytes / TSMON_TS > b->max_packets) { g_err = "PSI bank: packet count exceeds max_packets"; return DVBS2GPU_ERR_ARG; }
+    if (h_out && h_out == h_ts) { g_err = "PSI bank: the output buffer is the input"; return DVBS2GPU_ERR_ARG; }
+    if (!b->ctx) {
+        PsiHostStream& h = b->host[stream];
+        std::fill(b->nrows.begin(), b->nrows.end(), 0);    // the table is of the LAST call, which brought the others nothing
+        std::vector<std::pair<int, PsiSlot>> before;       // what a capacity failure has to put back: the watched slots and their views
+        std::vector<uint8_t> views[PSI_SLOTS];
+        for (int s = 0; s < PSI_SLOTS; ++s)
+            if (h.watch[s].pid >= 0) { before.emplace_back(s, h.slot[s]); views[s] = h.view[s]; }
+        h.run(h_ts, nbytes / TSMON_TS, h_out != nullptr);
+        const bool rows_fit = (int)h.rows.size() <= b->max_sections;
+        b->need_rows[stream] = (int)h.rows.size();
+        b->need_bytes[stream] = rows_fit ? (int)h.bytes.size() : -1;
+        if (!rows_fit || (h_out && (int)h.bytes.size() > cap)) {
+            for (const auto& kv : before) { h.slot[kv.first] = kv.second; h.view[kv.first] = views[kv.first]; }
+            h.rows.clear(); h.bytes.clear();
+            g_err = "PSI bank: the sections do not fit cap, or the rows max_sections (dvbs2gpu_psi_get_needed holds the sizes)";
+            return DVBS2GPU_ERR_CAPACITY;
+        }
+        psi_account(b, stream, h.cnt);
+        b->nrows[stream] = (int)h.rows.size();
+        if (h_out && !h.bytes.empty()) memcpy(h_out, h.bytes.data(), h.bytes.size());
+        return (int)h.bytes.size();
+    }
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    if (!b->d_in1) HIP_TRY(hipMalloc((void**)&b->d_in1, (size_t)b->max_packets * TSMON_TS));
+    if (nbytes > 0) HIP_TRY(hipMemcpy(b->d_in1, h_ts, nbytes, hipMemcpyHostToDevice));
+    if (h_out && (!b->d_out1 || b->out1_cap < (size_t)cap + 4)) {
+        if (b->d_out1) (void)hipFree(b->d_out1);
+        b->d_out1 = nullptr; b->out1_cap = 0;
+        HIP_TRY(hipMalloc((void**)&b->d_out1, (size_t)cap + 4));
+        b->out1_cap = (size_t)cap + 4;
+    }
+    std::vector<const uint8_t*> in(b->nstreams, nullptr);
+    std::vector<uint8_t*> out(b->nstreams, b->d_out1);
+    std::vector<int> nb(b->nstreams, 0), ob(b->nstreams, 0);
+    in[stream] = b->d_in1; nb[stream] = nbytes;
+    const int rc = dvbs2gpu_psi_process_batch(b, in.data(), nb.data(), h_out ? out.data() : nullptr, cap, ob.data(), nullptr, nullptr);
+    if (rc < 0) return rc;
+    if (h_out && ob[stream] > 0) HIP_TRY(hipMemcpy(h_out, b->d_out1, ob[stream], hipMemcpyDeviceToHost));
+    return ob[stream];
+}
+
+/* the byte and row sizes the stream's last call needed, whether it succeeded or failed for capacity (bytes -1: the rows did not fit) */
+int dvbs2gpu_psi_get_needed(dvbs2gpu_psi* b, int stream, int* bytes, int* rows) {
+    if (!b || stream < 0 || stream >= b->nstreams || !bytes || !rows) return DVBS2GPU_ERR_ARG;
+    *bytes = b->need_bytes[stream]; *rows = b->need_rows[stream];
+    return 0;
+}
+
+int dvbs2gpu_psi_get_stats(dvbs2gpu_psi* b, int stream, int slot, dvbs2gpu_psi_stats* h_out) {
+    if (!b || stream < 0 || stream >= b->nstreams || slot < -1 || slot >= PSI_SLOTS || !h_out) return DVBS2GPU_ERR_ARG;
+    *h_out = dvbs2gpu_psi_stats{};
+    int64_t* d = reinterpret_cast<int64_t*>(h_out);
+    for (int s = slot < 0 ? 0 : slot; s < (slot < 0 ? PSI_SLOTS : slot + 1); ++s) {
+        const int64_t* a = reinterpret_cast<const int64_t*>(&b->stats[(size_t)stream * PSI_SLOTS + s]);
+        for (int k = 0; k < PSI_NCNT; ++k) d[k] += a[k];
+    }
+    return 0;
+}
+
+int dvbs2gpu_psi_get_section_table(dvbs2gpu_psi* b, int stream, dvbs2gpu_psi_section* h_rows, int cap, int* n) {
+    if (!b || stream < 0 || stream >= b->nstreams || !n || cap < 0 || (cap > 0 && !h_rows)) return DVBS2GPU_ERR_ARG;
+    *n = b->nrows[stream];
+    const int k = *n < cap ? *n : cap;
+    if (k <= 0) return 0;
+    if (!b->ctx) { memcpy(h_rows, b->host[stream].rows.data(), k * sizeof(PsiRow)); return 0; }
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    HIP_TRY(hipMemcpy(h_rows, b->d_rows + (size_t)stream * b->max_sections, k * sizeof(PsiRow), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int dvbs2gpu_psi_get_section_table_device(dvbs2gpu_psi* b, int stream, const dvbs2gpu_psi_section** d_rows, int* n) {
+    if (!b || !b->ctx || stream < 0 || stream >= b->nstreams || !n || !d_rows) return DVBS2GPU_ERR_ARG;
+    *n = b->nrows[stream];
+    *d_rows = *n ? reinterpret_cast<const dvbs2gpu_psi_section*>(b->d_rows + (size_t)stream * b->max_sections) : nullptr;
+    return 0;
+}
+
+int dvbs2gpu_psi_get_programs(dvbs2gpu_psi* b, int stream, dvbs2gpu_psi_pat* hdr, dvbs2gpu_psi_program* h_rows, int cap, int* n) {
+    if (!b || stream < 0 || stream >= b->nstreams || !hdr || !n || cap < 0 || (cap > 0 && !h_rows)) return DVBS2GPU_ERR_ARG;
+    *n = 0;
+    *hdr = {-1, -1, 0};
+    for (int s = 0; s < PSI_SLOTS; ++s) {
+        const std::vector<uint8_t>& v = psi_view_of(b, stream, s);
+        if (v.empty() || v[0] != 0) continue;
+        std::vector<PsiProgram> out;
+        const PsiPatHeader h = psi_parse_pat(v.data(), (int)v.size(), &out);
+        memcpy(hdr, &h, sizeof(h));
+        *n = (int)out.size();
+        if (cap > 0 && !out.empty()) memcpy(h_rows, out.data(), (size_t)(*n < cap ? *n : cap) * sizeof(PsiProgram));
+        break;
+    }
+    return 0;
+}
+
+int dvbs2gpu_psi_get_program_map(dvbs2gpu_psi* b, int stream, int slot, dvbs2gpu_psi_pmt* hdr, dvbs2gpu_psi_es* h_rows, int cap, int* n) {
+    if (!b || stream < 0 || stream >= b->nstreams || slot < 0 || slot >= PSI_SLOTS || !hdr || !n || cap < 0 || (cap > 0 && !h_rows)) return DVBS2GPU_ERR_ARG;
+    *n = 0;
+    *hdr = {-1, -1, -1, 0};
+    const std::vector<uint8_t>& v = psi_view_of(b, stream, slot);
+    if (v.empty() || v[0] != 2) return 0;
+    std::vector<PsiEs> out;
+    const PsiPmtHeader h = psi_parse_pmt(v.data(), (int)v.size(), &out);
+    memcpy(hdr, &h, sizeof(h));
+    *n = (int)out.size();
+    if (cap > 0 && !out.empty()) memcpy(h_rows, out.data(), (size_t)(*n < cap ? *n : cap) * sizeof(PsiEs));
+    return 0;
+}
+
+}  // extern "C"
