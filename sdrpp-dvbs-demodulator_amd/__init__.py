@@ -1185,7 +1185,44 @@ class BbTsParserBank(_Handle):
         return [i for i in range(256) if m[i >> 5] >> (i & 31) & 1]
 
 
-class TsMonitorBank(_Handle):
+class _TsBank(_Handle):
+    """what the banks on transport streams in HBM share (csrc/ts_bank.h): error check, host-bank construction, the pointer tables of a
+    batch call and the two-call table read"""
+
+    def _check(self, rc):
+        if rc < 0:
+            raise Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+        return rc
+
+    @classmethod
+    def _host(cls, create, **dims):
+        self = cls.__new__(cls)
+        self.eng, self.lib = None, load_library()
+        self.__dict__.update(dims)
+        h = C.c_void_p()
+        self._check(getattr(self.lib, create)(*dims.values(), C.byref(h)))
+        self.h = h
+        return self
+
+    def _marshal(self, ts_tensors, out_tensors, nbytes):
+        """-> (input pointers, byte counts, output pointers or None, cap: the smallest output buffer)"""
+        n = self.nstreams
+        pin = (C.c_void_p * n)(*[t.data_ptr() for t in ts_tensors])
+        cnt = (C.c_int * n)(*[int(t.numel()) if nbytes is None else int(nbytes[i]) for i, t in enumerate(ts_tensors)])
+        if out_tensors is None:
+            return pin, cnt, None, 0
+        return pin, cnt, (C.c_void_p * n)(*[t.data_ptr() for t in out_tensors]), min(int(t.numel()) for t in out_tensors)
+
+    def _rows(self, getter, Row, *args):
+        """ask how many rows there are, then fetch them: getter(h, *args, rows, cap, &n) -> the rows"""
+        n = C.c_int()
+        self._check(getter(self.h, *args, None, 0, C.byref(n)))
+        rows = (Row * max(n.value, 1))()
+        self._check(getter(self.h, *args, rows, n.value, C.byref(n)))
+        return rows[:n.value]
+
+
+class TsMonitorBank(_TsBank):
     """TS monitor for `nstreams` transport streams (own extension; include/dvbs2gpu.h, TS monitor bank): per-PID continuity checks, the
     PID table of the last call and a PID filter that compacts the passing packets on the GPU.  Its input is what BbTsParserBank or
     DvbsTailBank left in HBM."""
@@ -1202,17 +1239,7 @@ class TsMonitorBank(_Handle):
     @classmethod
     def host(cls, nstreams=1, max_packets=4096):
         """a bank without a device: the library's host implementation of the same rules, behind work()"""
-        self = cls.__new__(cls)
-        self.eng, self.lib, self.nstreams, self.max_packets = None, load_library(), nstreams, max_packets
-        h = C.c_void_p()
-        self._check(self.lib.dvbs2gpu_tsmon_create_host(nstreams, max_packets, C.byref(h)))
-        self.h = h
-        return self
-
-    def _check(self, rc):
-        if rc < 0:
-            raise Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
-        return rc
+        return cls._host('dvbs2gpu_tsmon_create_host', nstreams=nstreams, max_packets=max_packets)
 
     def reset(self):
         self._check(self.lib.dvbs2gpu_tsmon_reset(self.h))
@@ -1226,14 +1253,8 @@ class TsMonitorBank(_Handle):
         """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors: None for statistics and
         table only, else uint8 CUDA buffers that receive the passing packets -> byte counts.  Dvbs2GpuError -5 carries .needed when a
         buffer is too small (nothing has advanced then)."""
-        n = self.nstreams
-        pin = (C.c_void_p * n)(*[t.data_ptr() for t in ts_tensors])
-        cnt = (C.c_int * n)(*[int(t.numel()) if nbytes is None else int(nbytes[i]) for i, t in enumerate(ts_tensors)])
-        nb = (C.c_int * n)()
-        pout, cap = None, 0
-        if out_tensors is not None:
-            pout = (C.c_void_p * n)(*[t.data_ptr() for t in out_tensors])
-            cap = min(int(t.numel()) for t in out_tensors)
+        pin, cnt, pout, cap = self._marshal(ts_tensors, out_tensors, nbytes)
+        nb = (C.c_int * self.nstreams)()
         rc = self.lib.dvbs2gpu_tsmon_process_batch(self.h, pin, cnt, pout, cap, nb, self.eng._stream())
         if rc < 0:
             e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
@@ -1260,11 +1281,8 @@ class TsMonitorBank(_Handle):
 
     def pid_table(self, stream=0):
         """[(pid, flags, packets, cc_errors, duplicates, scrambled, pusi)] of the last call, ascending by PID"""
-        n = C.c_int()
-        self._check(self.lib.dvbs2gpu_tsmon_get_pid_table(self.h, int(stream), None, 0, C.byref(n)))
-        rows = (TsMonPid * max(n.value, 1))()
-        self._check(self.lib.dvbs2gpu_tsmon_get_pid_table(self.h, int(stream), rows, n.value, C.byref(n)))
-        return [(r.pid, r.flags, r.packets, r.cc_errors, r.duplicates, r.scrambled, r.pusi) for r in rows[:n.value]]
+        rows = self._rows(self.lib.dvbs2gpu_tsmon_get_pid_table, TsMonPid, int(stream))
+        return [(r.pid, r.flags, r.packets, r.cc_errors, r.duplicates, r.scrambled, r.pusi) for r in rows]
 
     def pid_table_device(self, stream=0):
         """(device pointer or None, rows): the same table as dvbs2gpu_tsmon_pid records in HBM, valid until the next call"""
@@ -1273,7 +1291,7 @@ class TsMonitorBank(_Handle):
         return p.value, n.value
 
 
-class PsiBank(_Handle):
+class PsiBank(_TsBank):
     """PSI section bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, PSI section bank): PAT / PMT / SI section
     reassembly with CRC-32 on up to 16 watched PIDs per stream, one table row per section, the decoded PAT and PMTs on the host."""
     _destroy = 'dvbs2gpu_psi_destroy'
@@ -1291,18 +1309,9 @@ class PsiBank(_Handle):
     @classmethod
     def host(cls, nstreams=1, max_packets=4096, max_sections=1024):
         """a bank without a device: the library's host implementation of the same rules, behind work()"""
-        self = cls.__new__(cls)
-        self.eng, self.lib, self.nstreams, self.max_packets, self.max_sections = None, load_library(), nstreams, max_packets, max_sections
-        h = C.c_void_p()
-        self._check(self.lib.dvbs2gpu_psi_create_host(nstreams, max_packets, max_sections, C.byref(h)))
-        self.h = h
+        self = cls._host('dvbs2gpu_psi_create_host', nstreams=nstreams, max_packets=max_packets, max_sections=max_sections)
         self._watched = [{0: 0} for _ in range(nstreams)]
         return self
-
-    def _check(self, rc):
-        if rc < 0:
-            raise Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
-        return rc
 
     @staticmethod
     def layout():
@@ -1345,14 +1354,8 @@ class PsiBank(_Handle):
         """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors: None for rows and counters
         only, else uint8 CUDA buffers that receive the delivered sections -> byte counts.  Dvbs2GpuError -5 carries .needed and .rows
         when a buffer or max_sections is too small (nothing has advanced then)."""
-        n = self.nstreams
-        pin = (C.c_void_p * n)(*[t.data_ptr() for t in ts_tensors])
-        cnt = (C.c_int * n)(*[int(t.numel()) if nbytes is None else int(nbytes[i]) for i, t in enumerate(ts_tensors)])
-        nb, nr = (C.c_int * n)(), (C.c_int * n)()
-        pout, cap = None, 0
-        if out_tensors is not None:
-            pout = (C.c_void_p * n)(*[t.data_ptr() for t in out_tensors])
-            cap = min(int(t.numel()) for t in out_tensors)
+        pin, cnt, pout, cap = self._marshal(ts_tensors, out_tensors, nbytes)
+        nb, nr = (C.c_int * self.nstreams)(), (C.c_int * self.nstreams)()
         rc = self.lib.dvbs2gpu_psi_process_batch(self.h, pin, cnt, pout, cap, nb, nr, self.eng._stream())
         if rc < 0:
             e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
@@ -1384,11 +1387,8 @@ class PsiBank(_Handle):
 
     def section_table(self, stream=0):
         """one dict per section of the last call (the fields of dvbs2gpu_psi_section), in row order"""
-        n = C.c_int()
-        self._check(self.lib.dvbs2gpu_psi_get_section_table(self.h, int(stream), None, 0, C.byref(n)))
-        rows = (PsiSection * max(n.value, 1))()
-        self._check(self.lib.dvbs2gpu_psi_get_section_table(self.h, int(stream), rows, n.value, C.byref(n)))
-        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows[:n.value]]
+        rows = self._rows(self.lib.dvbs2gpu_psi_get_section_table, PsiSection, int(stream))
+        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows]
 
     def section_table_device(self, stream=0):
         """(device pointer or None, rows): the same table as dvbs2gpu_psi_section records in HBM, valid until the next call"""
@@ -1398,19 +1398,15 @@ class PsiBank(_Handle):
 
     def programs(self, stream=0):
         """-> ({transport_stream_id, version, malformed}, [(program_number, pid)]) from the PAT the stream holds (-1, -1: none)"""
-        hdr, n = PsiPat(), C.c_int()
-        self._check(self.lib.dvbs2gpu_psi_get_programs(self.h, int(stream), C.byref(hdr), None, 0, C.byref(n)))
-        rows = (PsiProgram * max(n.value, 1))()
-        self._check(self.lib.dvbs2gpu_psi_get_programs(self.h, int(stream), C.byref(hdr), rows, n.value, C.byref(n)))
-        return {k: int(getattr(hdr, k)) for k, _ in PsiPat._fields_}, [(r.program_number, r.pid) for r in rows[:n.value]]
+        hdr = PsiPat()
+        rows = self._rows(self.lib.dvbs2gpu_psi_get_programs, PsiProgram, int(stream), C.byref(hdr))
+        return {k: int(getattr(hdr, k)) for k, _ in PsiPat._fields_}, [(r.program_number, r.pid) for r in rows]
 
     def program_map(self, stream=0, slot=1):
         """-> ({program_number, version, pcr_pid, malformed}, [(stream_type, elementary_pid)]) from the slot's PMT (program_number -1: none)"""
-        hdr, n = PsiPmt(), C.c_int()
-        self._check(self.lib.dvbs2gpu_psi_get_program_map(self.h, int(stream), int(slot), C.byref(hdr), None, 0, C.byref(n)))
-        rows = (PsiEs * max(n.value, 1))()
-        self._check(self.lib.dvbs2gpu_psi_get_program_map(self.h, int(stream), int(slot), C.byref(hdr), rows, n.value, C.byref(n)))
-        return {k: int(getattr(hdr, k)) for k, _ in PsiPmt._fields_}, [(r.stream_type, r.elementary_pid) for r in rows[:n.value]]
+        hdr = PsiPmt()
+        rows = self._rows(self.lib.dvbs2gpu_psi_get_program_map, PsiEs, int(stream), int(slot), C.byref(hdr))
+        return {k: int(getattr(hdr, k)) for k, _ in PsiPmt._fields_}, [(r.stream_type, r.elementary_pid) for r in rows]
 
 
 class SegmentReceiver(_Handle):

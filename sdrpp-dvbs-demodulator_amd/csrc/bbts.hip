@@ -108,8 +108,7 @@ struct dvbs2gpu_bbts {
     BbtsFrameDesc* d_desc = nullptr;
     BbtsStreamPlan* d_plan = nullptr;
     void* d_args = nullptr;                    // BankArgs(nstreams): [in ptrs][out ptrs][nframes][out bytes]
-    uint8_t *d_in1 = nullptr, *d_out1 = nullptr;   // staging of the single-stream host-buffer entry point
-    size_t out1_cap = 0;
+    Workspace in1, out1;                       // staging of the single-stream host-buffer entry point
     std::vector<std::unique_ptr<BbtsHostParser>> host;
     std::vector<BbtsStreamPlan> h_plan;
     std::vector<uint8_t> h_in, h_out;
@@ -174,8 +173,9 @@ void dvbs2gpu_bbts_destroy(dvbs2gpu_bbts* b) {
     if (!b) return;
     bbts_ma_free(b->ma);
     bbts_gse_free(b->gse);
-    void* ps[] = {b->d_state, b->d_reasm[0], b->d_reasm[1], b->d_desc, b->d_plan, b->d_args, b->d_in1, b->d_out1};
+    void* ps[] = {b->d_state, b->d_reasm[0], b->d_reasm[1], b->d_desc, b->d_plan, b->d_args};
     for (void* p : ps) if (p) (void)hipFree(p);
+    b->in1.release(); b->out1.release();
     delete b;
 }
 
@@ -302,18 +302,11 @@ int dvbs2gpu_bbts_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, int cnt, uint8_t* 
     if (!b || !b->ctx || b->nstreams != 1 || cnt < 0 || cnt > b->max_frames || cap < 0 || (cnt > 0 && (!h_bb || !h_ts))) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(b->ctx->device));
     const size_t fbytes = b->kbch / 8;
-    if (!b->d_in1) {
-        HIP_TRY(hipMalloc((void**)&b->d_in1, (size_t)b->max_frames * 8192 + 64));
-    }
-    HIP_TRY(hipMemcpy(b->d_in1, h_bb, cnt * fbytes, hipMemcpyHostToDevice));
-    if (b->out1_cap < (size_t)cap + 64) {
-        if (b->d_out1) (void)hipFree(b->d_out1);
-        b->d_out1 = nullptr; b->out1_cap = 0;
-        HIP_TRY(hipMalloc((void**)&b->d_out1, (size_t)cap + 64));
-        b->out1_cap = (size_t)cap + 64;
-    }
-    uint8_t* d_out = b->d_out1;
-    const uint8_t* in_p = b->d_in1;
+    if (const int e = b->in1.ensure((size_t)b->max_frames * 8192 + 64)) return e;
+    HIP_TRY(hipMemcpy(b->in1.p, h_bb, cnt * fbytes, hipMemcpyHostToDevice));
+    if (const int e = b->out1.ensure((size_t)cap + 64)) return e;
+    uint8_t* d_out = static_cast<uint8_t*>(b->out1.p);
+    const uint8_t* in_p = static_cast<const uint8_t*>(b->in1.p);
     int got = 0;
     int rc = dvbs2gpu_bbts_process_batch(b, &in_p, &cnt, &d_out, cap, &got, nullptr);
     if (rc == 0 && got > 0) {

@@ -558,8 +558,7 @@ struct BbtsMa {
     MaFin* d_fins = nullptr;
     void* d_args = nullptr;                    // MaArgs: [in ptrs][8 out ptrs per stream][nframes][needed per lane][frame offsets]
     std::vector<int> h_foff;
-    uint8_t *d_in1 = nullptr, *d_out1 = nullptr;   // staging of the single-stream host-buffer entry point
-    size_t out1_cap = 0;
+    Workspace in1, out1;                       // staging of the single-stream host-buffer entry point
     // GSE (dvbs2gpu_bbts_ma_set_gse): contexts and per-call results from the first switch-on; records, rows and slot buffers from the
     // first GSE frame.  The slot pool has 3 x 64 KiB per SELECTED lane: slotmap[stream * 8 + k] is the lane's place in it or -1.
     MaGseLane* d_glane[2] = {nullptr, nullptr};
@@ -582,9 +581,10 @@ struct BbtsMa {
 void bbts_ma_free(BbtsMa* m) {
     if (!m) return;
     void* ps[] = {m->d_lane[0], m->d_lane[1], m->d_strm[0], m->d_strm[1], m->d_carry[0], m->d_carry[1], m->d_sel, m->d_tabs, m->d_join,
-                  m->d_recs, m->d_desc, m->d_fins, m->d_args, m->d_in1, m->d_out1, m->d_glane[0], m->d_glane[1], m->d_gout, m->d_slotmap,
+                  m->d_recs, m->d_desc, m->d_fins, m->d_args, m->d_glane[0], m->d_glane[1], m->d_gout, m->d_slotmap,
                   m->d_gfr, m->d_pkt, m->d_rows, m->d_slots};
     for (void* p : ps) if (p) (void)hipFree(p);
+    m->in1.release(); m->out1.release();
     delete m;
 }
 
@@ -972,18 +972,13 @@ int dvbs2gpu_bbts_ma_work(dvbs2gpu_bbts* b, const uint8_t* h_bb, const int* fram
         return 0;
     }
     HIP_TRY(hipSetDevice(v.ctx->device));
-    if (!m->d_in1) HIP_TRY(hipMalloc((void**)&m->d_in1, (size_t)v.max_frames * MA_MAX_FRAME + 64));
-    if (cnt > 0) HIP_TRY(hipMemcpy(m->d_in1, h_bb, off[cnt], hipMemcpyHostToDevice));
+    if (const int e = m->in1.ensure((size_t)v.max_frames * MA_MAX_FRAME + 64)) return e;
+    if (cnt > 0) HIP_TRY(hipMemcpy(m->in1.p, h_bb, off[cnt], hipMemcpyHostToDevice));
     const size_t per = ((size_t)cap + 67) & ~(size_t)3;
-    if (m->out1_cap < per * MA_LANES) {
-        if (m->d_out1) (void)hipFree(m->d_out1);
-        m->d_out1 = nullptr; m->out1_cap = 0;
-        HIP_TRY(hipMalloc((void**)&m->d_out1, per * MA_LANES));
-        m->out1_cap = per * MA_LANES;
-    }
+    if (const int e = m->out1.ensure(per * MA_LANES)) return e;
     uint8_t* d_out[MA_LANES];
-    for (int k = 0; k < MA_LANES; ++k) d_out[k] = m->d_out1 + per * k;
-    const uint8_t* in_p = m->d_in1;
+    for (int k = 0; k < MA_LANES; ++k) d_out[k] = static_cast<uint8_t*>(m->out1.p) + per * k;
+    const uint8_t* in_p = static_cast<const uint8_t*>(m->in1.p);
     const int rc = dvbs2gpu_bbts_process_ma_batch(b, &in_p, frame_bytes ? &frame_bytes : nullptr, &cnt, d_out, cap, out_bytes, needed, nullptr);
     if (rc) return rc;
     for (int k = 0; k < sel.n; ++k) if (out_bytes[k] > 0) HIP_TRY(hipMemcpy(h_out[k], d_out[k], out_bytes[k], hipMemcpyDeviceToHost));

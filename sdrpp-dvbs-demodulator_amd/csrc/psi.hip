@@ -8,7 +8,7 @@
 // the pointer bytes of the slot's next PUSI packet.
 //
 //   psi_scan_kernel    one workgroup per stream.
-//     A  every packet's header is read once (the two dwords of tsmon.hip) and its PID matched against the 16 watch entries; the
+//     A  every packet's header is read once (ts_load_header, ts_bank.h) and its PID matched against the 16 watch entries; the
 //        watched packets are compacted in input order into LDS (an exact prefix sum over a contiguous run of packets per thread),
 //        with payload start and pointer byte.
 //     B  one lane per slot takes the continuity steps of its packets in order (tsmon_step, from the slot's state byte) and classes
@@ -27,7 +27,7 @@
 //     row gathers the section and stores it at its offset, a dword per lane where the destination allows; then the open section
 //     goes to the slot's 4 KiB buffer and the slots' new states are stored.
 // Two launches per call, one device-to-host copy of the per-stream call record (PsiCall), and one small copy per changed PAT / PMT.
-#include "ctx.h"
+#include "ts_bank.h"
 #include "psi_rules.h"
 
 #include <memory>
@@ -42,6 +42,7 @@ constexpr int PSI_WG = 256, PSI_WAVES = PSI_WG / 64;
 constexpr int PSI_SEC_LDS = PSI_BUF + PSI_BUF / 64 * 4;    // a gathered section, 4 bytes of padding behind every 64: lane L's chunk starts in bank 17 L
 static_assert(sizeof(PsiRow) == sizeof(dvbs2gpu_psi_section) && sizeof(PsiRow) == 24, "row layout");
 static_assert(sizeof(PsiLayout) == sizeof(dvbs2gpu_psi_layout), "layout layout");
+static_assert(PSI_MAX_PACKETS <= 32 * PSI_WG, "psi_collect keeps a thread's match flags in one 32-bit mask (ts_thread_run)");
 static_assert(sizeof(PsiProgram) == sizeof(dvbs2gpu_psi_program) && sizeof(PsiEs) == sizeof(dvbs2gpu_psi_es), "view rows");
 static_assert(sizeof(PsiPatHeader) == sizeof(dvbs2gpu_psi_pat) && sizeof(PsiPmtHeader) == sizeof(dvbs2gpu_psi_pmt), "view headers");
 
@@ -62,32 +63,10 @@ __device__ inline int wa_slot(unsigned e) { return (int)(e >> 13 & 15); }
 __device__ inline int wa_kind(unsigned e) { return (int)(e >> 17 & 7); }
 __device__ inline int psi_sx(int i) { return i + (i >> 6) * 4; }
 
-typedef unsigned __attribute__((aligned(1))) psi_unaligned_u32;
-__device__ inline TsmonHdr psi_load(const uint8_t* __restrict__ ts, int k, unsigned* b4) {
-    const uint8_t* p = ts + (size_t)k * TSMON_TS;
-    const unsigned a = *reinterpret_cast<const psi_unaligned_u32*>(p), b = *reinterpret_cast<const psi_unaligned_u32*>(p + 4);
-    const uint8_t h[8] = {(uint8_t)a, (uint8_t)(a >> 8), (uint8_t)(a >> 16), (uint8_t)(a >> 24), (uint8_t)b, (uint8_t)(b >> 8), 0, 0};
-    *b4 = b & 255;
-    return tsmon_parse(h);
-}
 __device__ inline int psi_match(const TsmonHdr& h, const PsiWatch* w) {
     if (h.cls != TSMON_DATA) return -1;
     for (int s = 0; s < PSI_SLOTS; ++s) if (w[s].pid == h.pid) return s;
     return -1;
-}
-
-// exclusive prefix sum of one int per thread over the workgroup; *total: the sum.  wsum: PSI_WAVES ints of LDS
-__device__ inline int psi_block_scan(int v, int* wsum, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-    for (int k = 1; k < 64; k <<= 1) { const int t = __shfl_up(inc, k); if (lane >= k) inc += t; }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0, sum = 0;
-    for (int w = 0; w < PSI_WAVES; ++w) { if (w < wave) base += wsum[w]; sum += wsum[w]; }
-    __syncthreads();
-    *total = sum;
-    return base + inc - v;
 }
 
 struct PsiView {                                 // what the section walkers read of one stream
@@ -212,15 +191,15 @@ __device__ void psi_jobs(const PsiView& v, const PsiOut& o, const PsiWatch* w) {
 
 // phase A of both kernels: the watched packets of the stream into wa / wb, in input order; returns their number
 __device__ int psi_collect(const uint8_t* __restrict__ ts, int n, const PsiWatch* w, unsigned* wa, uint16_t* wb, int* wsum) {
-    const int tid = threadIdx.x;
-    const int chunk = (n + PSI_WG - 1) / PSI_WG, k0 = tid * chunk, k1 = k0 + chunk < n ? k0 + chunk : n;   // <= 16 packets per thread
-    unsigned mask = 0, b4;
-    for (int k = k0; k < k1; ++k) mask |= (unsigned)(psi_match(psi_load(ts, k, &b4), w) >= 0) << (k - k0);
+    int k0, k1; ts_thread_run(n, PSI_WG, &k0, &k1);              // <= 16 packets per thread
+    unsigned mask = 0;
+    for (int k = k0; k < k1; ++k) mask |= (unsigned)(psi_match(ts_load_header(ts, k), w) >= 0) << (k - k0);
     int W;
-    int at = psi_block_scan(__popc(mask), wsum, &W);
+    int at = ts_block_scan<PSI_WG>(__popc(mask), wsum, &W);
     for (int k = k0; k < k1; ++k) {
         if (!(mask >> (k - k0) & 1)) continue;
-        const TsmonHdr h = psi_load(ts, k, &b4);
+        unsigned b4;
+        const TsmonHdr h = ts_load_header(ts, k, &b4);
         int ps = psi_payload_start(h.afc, b4);
         if (ps > TSMON_TS) ps = TSMON_TS;
         const unsigned ptr = (h.pusi && (h.afc & 1) && ps < TSMON_TS) ? ts[(size_t)k * TSMON_TS + ps] : 0;
@@ -297,10 +276,10 @@ __global__ void __launch_bounds__(PSI_WG) psi_scan_kernel(const uint8_t* const* 
     __syncthreads();
     int nrows;
     {
-        const int chunk = (W + PSI_WG - 1) / PSI_WG, j0 = tid * chunk, j1 = j0 + chunk < W ? j0 + chunk : W;
+        int j0, j1; ts_thread_run(W, PSI_WG, &j0, &j1);
         int mine = 0;
         for (int j = j0; j < j1; ++j) mine += (rc[j] >> 1) + (rc[j] & 1);
-        int run = psi_block_scan(mine, wsum, &nrows);
+        int run = ts_block_scan<PSI_WG>(mine, wsum, &nrows);
         for (int j = j0; j < j1; ++j) { const int c = rc[j]; rc[j] = run << 1 | (c & 1); run += (c >> 1) + (c & 1); }
     }
     __syncthreads();
@@ -363,11 +342,11 @@ __global__ void __launch_bounds__(PSI_WG) psi_scan_kernel(const uint8_t* const* 
         __syncthreads();
         {   // the output offsets: an exact prefix sum in row order
             const int mode = deliver[s];
-            const int chunk = (nrows + PSI_WG - 1) / PSI_WG, r0 = tid * chunk, r1 = r0 + chunk < nrows ? r0 + chunk : nrows;
+            int r0, r1; ts_thread_run(nrows, PSI_WG, &r0, &r1);
             auto bytes_of = [&](int r) { return have_out && (mode == 0 || (rows[r].flags & PSI_CHANGED)) ? rows[r].length : 0; };
             int mine = 0;
             for (int r = r0; r < r1; ++r) mine += bytes_of(r);
-            int at = psi_block_scan(mine, wsum, &needed);
+            int at = ts_block_scan<PSI_WG>(mine, wsum, &needed);
             for (int r = r0; r < r1; ++r) {
                 const int b = bytes_of(r);
                 rows[r].offset = b ? at : -1;
@@ -481,9 +460,8 @@ struct dvbs2gpu_psi {
     PsiRec *d_recs = nullptr, *d_opens = nullptr;
     PsiRow* d_rows = nullptr;                      // nstreams x max_sections
     PsiCall* d_call = nullptr;
-    char* d_args = nullptr;                        // in[n], out[n], nbytes[n]
-    uint8_t *d_in1 = nullptr, *d_out1 = nullptr;   // staging of the host-buffer entry point
-    size_t out1_cap = 0;
+    void* d_args = nullptr;                        // TsBankArgs(nstreams)
+    TsHostStage stage;                             // of the host-buffer entry point
     // host-only banks
     std::vector<PsiHostStream> host;
 };
@@ -523,7 +501,7 @@ extern "C" {
 void dvbs2gpu_psi_destroy(dvbs2gpu_psi* b) {
     if (!b) return;
     void* ps[] = {b->d_watch, b->d_deliver, b->d_state, b->d_newst, b->d_bufs, b->d_views, b->d_wa, b->d_wb, b->d_recs, b->d_opens, b->d_rows, b->d_call,
-                  b->d_args, b->d_in1, b->d_out1};
+                  b->d_args};
     for (void* p : ps) if (p) (void)hipFree(p);
     delete b;
 }
@@ -534,24 +512,23 @@ int dvbs2gpu_psi_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int ma
     dvbs2gpu_psi* b = psi_new(ctx, nstreams, max_packets, max_sections);
     b->view.resize((size_t)nstreams * PSI_SLOTS);
     const size_t n = (size_t)nstreams, ns = n * PSI_SLOTS;
-    hipError_t e = hipMalloc((void**)&b->d_watch, ns * sizeof(PsiWatch));
+    hipError_t e = hipSuccess;                         // (zero-filled: the delivery modes and the slots' states; the kernels write the rest before it is read)
+    bbts_alloc(e, &b->d_watch, ns * sizeof(PsiWatch), false);
     if (e == hipSuccess) e = hipMemcpy(b->d_watch, b->watch.data(), ns * sizeof(PsiWatch), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_deliver, n * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(b->d_deliver, 0, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_state, ns * sizeof(PsiDevSlot));
-    if (e == hipSuccess) e = hipMemset(b->d_state, 0, ns * sizeof(PsiDevSlot));
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_newst, ns * sizeof(PsiDevSlot));
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_bufs, ns * PSI_BUF);
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_views, ns * PSI_BUF);
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_wa, n * max_packets * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_wb, n * max_packets * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_recs, n * max_sections * sizeof(PsiRec));
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_opens, ns * sizeof(PsiRec));
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_rows, n * max_sections * sizeof(PsiRow));
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_call, n * sizeof(PsiCall));
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_args, n * 20);
+    bbts_alloc(e, &b->d_deliver, n * sizeof(int));
+    bbts_alloc(e, &b->d_state, ns * sizeof(PsiDevSlot));
+    bbts_alloc(e, &b->d_newst, ns * sizeof(PsiDevSlot), false);
+    bbts_alloc(e, &b->d_bufs, ns * PSI_BUF, false);
+    bbts_alloc(e, &b->d_views, ns * PSI_BUF, false);
+    bbts_alloc(e, &b->d_wa, n * max_packets * sizeof(unsigned), false);
+    bbts_alloc(e, &b->d_wb, n * max_packets * sizeof(uint16_t), false);
+    bbts_alloc(e, &b->d_recs, n * max_sections * sizeof(PsiRec), false);
+    bbts_alloc(e, &b->d_opens, ns * sizeof(PsiRec), false);
+    bbts_alloc(e, &b->d_rows, n * max_sections * sizeof(PsiRow), false);
+    bbts_alloc(e, &b->d_call, n * sizeof(PsiCall), false);
+    bbts_alloc(e, &b->d_args, TsBankArgs(n).L.bytes(), false);
     if (e != hipSuccess) { dvbs2gpu_psi_destroy(b); return fail_hip(e, "hipMalloc(psi)"); }
-    b->h_args.resize(n * 20);
+    b->h_args.resize(TsBankArgs(n).L.bytes());
     *out = b;
     return 0;
 }
@@ -624,8 +601,8 @@ int dvbs2gpu_psi_process_batch(dvbs2gpu_psi* b, const uint8_t* const* d_ts, cons
     if (!b->ctx) { g_err = "PSI bank: a host bank takes host buffers (dvbs2gpu_psi_work)"; return DVBS2GPU_ERR_ARG; }
     const int n = b->nstreams;
     for (int i = 0; i < n; ++i) {
-        if (nbytes[i] < 0 || nbytes[i] % TSMON_TS) { g_err = "PSI bank: a byte count is a whole number of 188-byte packets"; return DVBS2GPU_ERR_ARG; }
-        if (nbytes[i] / TSMON_TS > b->max_packets) { g_err = "PSI bank: packet count exceeds max_packets"; return DVBS2GPU_ERR_ARG; }
+        if (!ts_bank_check_counts("PSI bank: ", nbytes + i, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
+        // once d_out is given every stream needs its output pointer, an empty one too (the TS monitor asks only streams that bring packets)
         if ((nbytes[i] > 0 && !d_ts[i]) || (d_out && (!d_out[i] || d_out[i] == d_ts[i]))) {
             g_err = "PSI bank: null buffer, or an output buffer that is its stream's input";
             return DVBS2GPU_ERR_ARG;
@@ -633,18 +610,11 @@ int dvbs2gpu_psi_process_batch(dvbs2gpu_psi* b, const uint8_t* const* d_ts, cons
     }
     HIP_TRY(hipSetDevice(b->ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    {
-        const uint8_t** in = reinterpret_cast<const uint8_t**>(b->h_args.data());
-        uint8_t** out = reinterpret_cast<uint8_t**>(b->h_args.data() + (size_t)n * 8);
-        int* nb = reinterpret_cast<int*>(b->h_args.data() + (size_t)n * 16);
-        for (int i = 0; i < n; ++i) { in[i] = d_ts[i]; out[i] = d_out ? d_out[i] : nullptr; nb[i] = nbytes[i]; }
-    }
+    const TsBankArgs a(n);
+    a.fill(b->h_args.data(), n, d_ts, d_out, nbytes);
     HIP_TRY(hipMemcpyAsync(b->d_args, b->h_args.data(), b->h_args.size(), hipMemcpyHostToDevice, st));
-    const uint8_t* const* a_in = reinterpret_cast<const uint8_t* const*>(b->d_args);
-    uint8_t* const* a_out = reinterpret_cast<uint8_t* const*>(b->d_args + (size_t)n * 8);
-    const int* a_nb = reinterpret_cast<const int*>(b->d_args + (size_t)n * 16);
     const size_t lds_scan = (size_t)b->max_packets * 10 + 16, lds_commit = (size_t)b->max_packets * 6 + 16;   // <= 40 KiB beside 18 KiB static
-    hipLaunchKernelGGL(psi_scan_kernel, dim3(n), dim3(PSI_WG), lds_scan, st, a_in, a_nb, b->max_packets, b->max_sections, b->d_watch, b->d_deliver,
+    hipLaunchKernelGGL(psi_scan_kernel, dim3(n), dim3(PSI_WG), lds_scan, st, a.in(b->d_args), a.nbytes(b->d_args), b->max_packets, b->max_sections, b->d_watch, b->d_deliver,
                        b->d_state, b->d_newst, b->d_bufs, b->d_views, b->d_wa, b->d_wb, b->d_recs, b->d_opens, b->d_rows, b->d_call, d_out ? 1 : 0);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(b->h_call.data(), b->d_call, sizeof(PsiCall) * n, hipMemcpyDeviceToHost, st));
@@ -662,7 +632,7 @@ int dvbs2gpu_psi_process_batch(dvbs2gpu_psi* b, const uint8_t* const* d_ts, cons
         g_err = "PSI bank: the sections of a stream do not fit cap, or its rows max_sections (out_bytes / out_rows hold the sizes)";
         return DVBS2GPU_ERR_CAPACITY;
     }
-    hipLaunchKernelGGL(psi_commit_kernel, dim3(n), dim3(PSI_WG), lds_commit, st, a_in, d_out ? a_out : nullptr, b->max_packets, b->max_sections, cap,
+    hipLaunchKernelGGL(psi_commit_kernel, dim3(n), dim3(PSI_WG), lds_commit, st, a.in(b->d_args), d_out ? a.out(b->d_args) : nullptr, b->max_packets, b->max_sections, cap,
                        b->d_state, b->d_newst, b->d_bufs, b->d_wa, b->d_wb, b->d_recs, b->d_opens, b->d_rows, b->d_call);
     HIP_TRY(hipGetLastError());
     for (int i = 0; i < n; ++i)                        // the changed PAT / PMT sections, and only those
@@ -680,8 +650,7 @@ int dvbs2gpu_psi_process_batch(dvbs2gpu_psi* b, const uint8_t* const* d_ts, cons
 
 int dvbs2gpu_psi_work(dvbs2gpu_psi* b, int stream, const uint8_t* h_ts, int nbytes, uint8_t* h_out, int cap) {
     if (!b || stream < 0 || stream >= b->nstreams || nbytes < 0 || cap < 0 || (nbytes > 0 && !h_ts)) return DVBS2GPU_ERR_ARG;
-    if (nbytes % TSMON_TS) { g_err = "PSI bank: a byte count is a whole number of 188-byte packets"; return DVBS2GPU_ERR_ARG; }
-    if (nbytes / TSMON_TS > b->max_packets) { g_err = "PSI bank: packet count exceeds max_packets"; return DVBS2GPU_ERR_ARG; }
+    if (!ts_bank_check_counts("PSI bank: ", &nbytes, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
     if (h_out && h_out == h_ts) { g_err = "PSI bank: the output buffer is the input"; return DVBS2GPU_ERR_ARG; }
     if (!b->ctx) {
         PsiHostStream& h = b->host[stream];
@@ -706,22 +675,9 @@ int dvbs2gpu_psi_work(dvbs2gpu_psi* b, int stream, const uint8_t* h_ts, int nbyt
         return (int)h.bytes.size();
     }
     HIP_TRY(hipSetDevice(b->ctx->device));
-    if (!b->d_in1) HIP_TRY(hipMalloc((void**)&b->d_in1, (size_t)b->max_packets * TSMON_TS));
-    if (nbytes > 0) HIP_TRY(hipMemcpy(b->d_in1, h_ts, nbytes, hipMemcpyHostToDevice));
-    if (h_out && (!b->d_out1 || b->out1_cap < (size_t)cap + 4)) {
-        if (b->d_out1) (void)hipFree(b->d_out1);
-        b->d_out1 = nullptr; b->out1_cap = 0;
-        HIP_TRY(hipMalloc((void**)&b->d_out1, (size_t)cap + 4));
-        b->out1_cap = (size_t)cap + 4;
-    }
-    std::vector<const uint8_t*> in(b->nstreams, nullptr);
-    std::vector<uint8_t*> out(b->nstreams, b->d_out1);
-    std::vector<int> nb(b->nstreams, 0), ob(b->nstreams, 0);
-    in[stream] = b->d_in1; nb[stream] = nbytes;
-    const int rc = dvbs2gpu_psi_process_batch(b, in.data(), nb.data(), h_out ? out.data() : nullptr, cap, ob.data(), nullptr, nullptr);
-    if (rc < 0) return rc;
-    if (h_out && ob[stream] > 0) HIP_TRY(hipMemcpy(h_out, b->d_out1, ob[stream], hipMemcpyDeviceToHost));
-    return ob[stream];
+    return ts_bank_work(b->stage, b->nstreams, stream, h_ts, nbytes, b->max_packets, h_out, cap, true, [&](const uint8_t* const* in, const int* nb, uint8_t* const* out, int* ob) {
+        return dvbs2gpu_psi_process_batch(b, in, nb, out, cap, ob, nullptr, nullptr);
+    });
 }
 
 /* the byte and row sizes the stream's last call needed, whether it succeeded or failed for capacity (bytes -1: the rows did not fit) */
@@ -743,21 +699,11 @@ int dvbs2gpu_psi_get_stats(dvbs2gpu_psi* b, int stream, int slot, dvbs2gpu_psi_s
 }
 
 int dvbs2gpu_psi_get_section_table(dvbs2gpu_psi* b, int stream, dvbs2gpu_psi_section* h_rows, int cap, int* n) {
-    if (!b || stream < 0 || stream >= b->nstreams || !n || cap < 0 || (cap > 0 && !h_rows)) return DVBS2GPU_ERR_ARG;
-    *n = b->nrows[stream];
-    const int k = *n < cap ? *n : cap;
-    if (k <= 0) return 0;
-    if (!b->ctx) { memcpy(h_rows, b->host[stream].rows.data(), k * sizeof(PsiRow)); return 0; }
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    HIP_TRY(hipMemcpy(h_rows, b->d_rows + (size_t)stream * b->max_sections, k * sizeof(PsiRow), hipMemcpyDeviceToHost));
-    return 0;
+    return ts_bank_rows(b, &dvbs2gpu_psi::max_sections, stream, h_rows, cap, n);
 }
 
 int dvbs2gpu_psi_get_section_table_device(dvbs2gpu_psi* b, int stream, const dvbs2gpu_psi_section** d_rows, int* n) {
-    if (!b || !b->ctx || stream < 0 || stream >= b->nstreams || !n || !d_rows) return DVBS2GPU_ERR_ARG;
-    *n = b->nrows[stream];
-    *d_rows = *n ? reinterpret_cast<const dvbs2gpu_psi_section*>(b->d_rows + (size_t)stream * b->max_sections) : nullptr;
-    return 0;
+    return ts_bank_rows_device(b, &dvbs2gpu_psi::max_sections, stream, d_rows, n);
 }
 
 int dvbs2gpu_psi_get_programs(dvbs2gpu_psi* b, int stream, dvbs2gpu_psi_pat* hdr, dvbs2gpu_psi_program* h_rows, int cap, int* n) {

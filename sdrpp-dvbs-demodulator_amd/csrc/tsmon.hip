@@ -16,8 +16,8 @@
 // Two launches at most, whatever nstreams and the packet counts are; one device-to-host copy (TsmonCall per stream: bytes needed,
 // rows, the call's counters).  The cumulative counters live on the host; the device keeps 8 KiB of continuity state per stream.
 // TsmonHostStream below applies the same rules to host buffers, packet by packet (host-only banks; the kernels' yardstick).
-#include "ctx.h"
-#include "tsmon_rules.h"
+// The header read, the prefix sum, the argument table, the count checks, the host staging and the table getters: ts_bank.h.
+#include "ts_bank.h"
 
 #include <map>
 #include <memory>
@@ -32,16 +32,8 @@ constexpr int TSMON_WG = 256;
 constexpr unsigned TSMON_KEY_NONE = 0xffffffffu; // sorts behind every PID: untrusted packets and the padding to a power of two
 static_assert(sizeof(TsmonRow) == sizeof(dvbs2gpu_tsmon_pid) && sizeof(TsmonRow) == 24, "row layout");
 static_assert(sizeof(TsmonFilter) == sizeof(dvbs2gpu_tsmon_filter), "filter layout");
+static_assert(TSMON_MAX_PACKETS <= 32 * TSMON_WG, "the emit kernel keeps a thread's pass flags in one 32-bit mask (ts_thread_run)");
 
-typedef unsigned __attribute__((aligned(1))) tsmon_unaligned_u32;
-
-// the header of packet k of a stream, read as two dwords (they lie inside the packet: 188 >= 8)
-__device__ inline TsmonHdr tsmon_load(const uint8_t* __restrict__ ts, int k) {
-    const uint8_t* p = ts + (size_t)k * TSMON_TS;
-    const unsigned a = *reinterpret_cast<const tsmon_unaligned_u32*>(p), b = *reinterpret_cast<const tsmon_unaligned_u32*>(p + 4);
-    const uint8_t h[8] = {(uint8_t)a, (uint8_t)(a >> 8), (uint8_t)(a >> 16), (uint8_t)(a >> 24), (uint8_t)b, (uint8_t)(b >> 8), 0, 0};
-    return tsmon_parse(h);
-}
 // nine bits of a trusted packet's header for the walk
 __device__ inline unsigned tsmon_pack(const TsmonHdr& h) { return h.cc | h.afc << 4 | h.di << 6 | h.pusi << 7 | (h.tsc != 0) << 8; }
 __device__ inline TsmonHdr tsmon_unpack(unsigned v, int pid) {
@@ -49,26 +41,6 @@ __device__ inline TsmonHdr tsmon_unpack(unsigned v, int pid) {
                   (int)(v >> 6 & 1)};
     return h;
 }
-
-// exclusive prefix sum of one int per thread over the 256 threads of the workgroup; *total: the sum.  wsum: 4 ints of LDS
-__device__ inline int tsmon_block_scan(int v, int* wsum, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-    for (int k = 1; k < 64; k <<= 1) { const int t = __shfl_up(inc, k); if (lane >= k) inc += t; }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0, sum = 0;
-    for (int w = 0; w < TSMON_WG / 64; ++w) { if (w < wave) base += wsum[w]; sum += wsum[w]; }
-    __syncthreads();                               // wsum may be written again
-    *total = sum;
-    return base + inc - v;
-}
-
-struct TsmonArgs {                                 // the layout of d_args for n streams
-    ScratchLayout L;
-    ScratchPart<const uint8_t*> in; ScratchPart<uint8_t*> out; ScratchPart<int> nbytes;
-    explicit TsmonArgs(size_t n) : in(L.add<const uint8_t*>(n)), out(L.add<uint8_t*>(n)), nbytes(L.add<int>(n)) {}
-};
 
 enum { TC_NULL = 0, TC_TEI, TC_SYNC, TC_CC, TC_DUP, TC_DISC, TC_SCR, TC_PASS, TC_FIRST, TC_COUNT };
 
@@ -100,7 +72,7 @@ __global__ void __launch_bounds__(TSMON_WG) tsmon_scan_kernel(const uint8_t* con
     for (int k = tid; k < npad; k += TSMON_WG) {
         unsigned key = TSMON_KEY_NONE;
         if (k < n) {
-            const TsmonHdr h = tsmon_load(ts, k);
+            const TsmonHdr h = ts_load_header(ts, k);
             c_sync += h.cls == TSMON_SYNC_ERROR; c_tei += h.cls == TSMON_TEI; c_null += h.cls == TSMON_NULL;
             c_pass += tsmon_passes(h, f, map);
             if (h.cls >= TSMON_NULL) { key = (unsigned)h.pid << 13 | (unsigned)k; hdr[k] = (uint16_t)tsmon_pack(h); }
@@ -125,12 +97,12 @@ __global__ void __launch_bounds__(TSMON_WG) tsmon_scan_kernel(const uint8_t* con
             __syncthreads();
         }
     // a contiguous run of sorted positions per thread; the heads of the PID runs in it are this thread's rows
-    const int chunk = (n + TSMON_WG - 1) / TSMON_WG, p0 = tid * chunk, p1 = p0 + chunk < n ? p0 + chunk : n;
+    const int chunk = (n + TSMON_WG - 1) / TSMON_WG, p0 = tid * chunk, p1 = p0 + chunk < n ? p0 + chunk : n;   // (ts_thread_run written out: through it four compares below come out unsigned)
     auto is_head = [&](int p) { return keys[p] != TSMON_KEY_NONE && (p == 0 || (keys[p - 1] >> 13) != (keys[p] >> 13)); };
     int heads = 0;
     for (int p = p0; p < p1; ++p) heads += is_head(p);
     int nrows;
-    int rank = tsmon_block_scan(heads, wsum, &nrows);
+    int rank = ts_block_scan<TSMON_WG>(heads, wsum, &nrows);
     int c_cc = 0, c_dup = 0, c_disc = 0, c_scr = 0, c_first = 0;
     for (int p = p0; p < p1; ++p) {
         if (!is_head(p)) continue;
@@ -189,11 +161,11 @@ __global__ void __launch_bounds__(TSMON_WG) tsmon_emit_kernel(const uint8_t* con
     const TsmonFilter f = filt[s];
     const uint32_t* map = maps + (size_t)s * TSMON_MAP_WORDS;
     // a contiguous run of at most 32 packets per thread (8192 / 256): its pass flags in one word
-    const int chunk = (n + TSMON_WG - 1) / TSMON_WG, k0 = tid * chunk, k1 = k0 + chunk < n ? k0 + chunk : n;
+    int k0, k1; ts_thread_run(n, TSMON_WG, &k0, &k1);
     unsigned mask = 0;
-    for (int k = k0; k < k1; ++k) mask |= (unsigned)tsmon_passes(tsmon_load(ts, k), f, map) << (k - k0);
+    for (int k = k0; k < k1; ++k) mask |= (unsigned)tsmon_passes(ts_load_header(ts, k), f, map) << (k - k0);
     int total;
-    int at = tsmon_block_scan(__popc(mask), wsum, &total);
+    int at = ts_block_scan<TSMON_WG>(__popc(mask), wsum, &total);
     for (int k = k0; k < k1; ++k) if (mask >> (k - k0) & 1) src[at++] = (uint16_t)k;
     __syncthreads();
     if (total > cap / TSMON_TS) total = cap / TSMON_TS;  // (the host launches this kernel only when every stream fits)
@@ -268,9 +240,8 @@ struct dvbs2gpu_tsmon {
     TsmonRow* d_rows = nullptr;                    // nstreams x maxrows
     uint8_t* d_newst = nullptr;                    // the state byte behind every row's last packet
     TsmonCall* d_call = nullptr;
-    void* d_args = nullptr;                        // TsmonArgs(nstreams)
-    uint8_t *d_in1 = nullptr, *d_out1 = nullptr;   // staging of the host-buffer entry point
-    size_t out1_cap = 0;
+    void* d_args = nullptr;                        // TsBankArgs(nstreams)
+    TsHostStage stage;                             // of the host-buffer entry point
     // host-only banks
     std::vector<TsmonHostStream> host;
 };
@@ -306,7 +277,7 @@ extern "C" {
 
 void dvbs2gpu_tsmon_destroy(dvbs2gpu_tsmon* m) {
     if (!m) return;
-    void* ps[] = {m->d_state, m->d_filt, m->d_map, m->d_rows, m->d_newst, m->d_call, m->d_args, m->d_in1, m->d_out1};
+    void* ps[] = {m->d_state, m->d_filt, m->d_map, m->d_rows, m->d_newst, m->d_call, m->d_args};
     for (void* p : ps) if (p) (void)hipFree(p);
     delete m;
 }
@@ -316,18 +287,16 @@ int dvbs2gpu_tsmon_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, dvbs
     HIP_TRY(hipSetDevice(ctx->device));
     dvbs2gpu_tsmon* m = tsmon_new(ctx, nstreams, max_packets);
     const size_t n = (size_t)nstreams;
-    hipError_t e = hipMalloc((void**)&m->d_state, n * TSMON_PIDS);
-    if (e == hipSuccess) e = hipMemset(m->d_state, 0, n * TSMON_PIDS);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->d_filt, n * sizeof(TsmonFilter));
-    if (e == hipSuccess) e = hipMemset(m->d_filt, 0, n * sizeof(TsmonFilter));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->d_map, n * TSMON_MAP_WORDS * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(m->d_map, 0, n * TSMON_MAP_WORDS * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->d_rows, n * m->maxrows * sizeof(TsmonRow));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->d_newst, n * m->maxrows);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->d_call, n * sizeof(TsmonCall));
-    if (e == hipSuccess) e = hipMalloc(&m->d_args, TsmonArgs(n).L.bytes());
+    hipError_t e = hipSuccess;                         // (the rows, their states and the call records are written before they are read)
+    bbts_alloc(e, &m->d_state, n * TSMON_PIDS);
+    bbts_alloc(e, &m->d_filt, n * sizeof(TsmonFilter));
+    bbts_alloc(e, &m->d_map, n * TSMON_MAP_WORDS * sizeof(uint32_t));
+    bbts_alloc(e, &m->d_rows, n * m->maxrows * sizeof(TsmonRow), false);
+    bbts_alloc(e, &m->d_newst, n * m->maxrows, false);
+    bbts_alloc(e, &m->d_call, n * sizeof(TsmonCall), false);
+    bbts_alloc(e, &m->d_args, TsBankArgs(n).L.bytes(), false);
     if (e != hipSuccess) { dvbs2gpu_tsmon_destroy(m); return fail_hip(e, "hipMalloc(tsmon)"); }
-    m->h_args.resize(TsmonArgs(n).L.bytes());
+    m->h_args.resize(TsBankArgs(n).L.bytes());
     *out = m;
     return 0;
 }
@@ -374,8 +343,8 @@ int dvbs2gpu_tsmon_process_batch(dvbs2gpu_tsmon* m, const uint8_t* const* d_ts, 
     if (!m->ctx) { g_err = "TS monitor: a host bank takes host buffers (dvbs2gpu_tsmon_work)"; return DVBS2GPU_ERR_ARG; }
     const int n = m->nstreams;
     for (int i = 0; i < n; ++i) {
-        if (nbytes[i] < 0 || nbytes[i] % TSMON_TS) { g_err = "TS monitor: a byte count is a whole number of 188-byte packets"; return DVBS2GPU_ERR_ARG; }
-        if (nbytes[i] / TSMON_TS > m->max_packets) { g_err = "TS monitor: packet count exceeds max_packets"; return DVBS2GPU_ERR_ARG; }
+        if (!ts_bank_check_counts("TS monitor: ", nbytes + i, 1, m->max_packets)) return DVBS2GPU_ERR_ARG;
+        // only a stream that brings packets needs its buffers (the PSI bank wants an output pointer for every stream)
         if (nbytes[i] > 0 && (!d_ts[i] || (d_out && (!d_out[i] || d_out[i] == d_ts[i])))) {
             g_err = "TS monitor: null buffer, or an output buffer that is its stream's input";
             return DVBS2GPU_ERR_ARG;
@@ -383,12 +352,8 @@ int dvbs2gpu_tsmon_process_batch(dvbs2gpu_tsmon* m, const uint8_t* const* d_ts, 
     }
     HIP_TRY(hipSetDevice(m->ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    const TsmonArgs a(n);
-    for (int i = 0; i < n; ++i) {
-        a.in(m->h_args.data())[i] = d_ts[i];
-        a.out(m->h_args.data())[i] = d_out ? d_out[i] : nullptr;
-        a.nbytes(m->h_args.data())[i] = nbytes[i];
-    }
+    const TsBankArgs a(n);
+    a.fill(m->h_args.data(), n, d_ts, d_out, nbytes);
     HIP_TRY(hipMemcpyAsync(m->d_args, m->h_args.data(), m->h_args.size(), hipMemcpyHostToDevice, st));
     const size_t lds_scan = (size_t)m->npad_max * 6, lds_emit = ((size_t)m->max_packets * 2 + 15) / 16 * 16;   // <= 48 KiB
     hipLaunchKernelGGL(tsmon_scan_kernel, dim3(n), dim3(TSMON_WG), lds_scan, st, a.in(m->d_args), a.nbytes(m->d_args), m->max_packets, m->npad_max,
@@ -418,12 +383,11 @@ int dvbs2gpu_tsmon_process_batch(dvbs2gpu_tsmon* m, const uint8_t* const* d_ts, 
 
 int dvbs2gpu_tsmon_work(dvbs2gpu_tsmon* m, int stream, const uint8_t* h_ts, int nbytes, uint8_t* h_out, int cap) {
     if (!m || stream < 0 || stream >= m->nstreams || nbytes < 0 || cap < 0 || (nbytes > 0 && !h_ts)) return DVBS2GPU_ERR_ARG;
-    if (nbytes % TSMON_TS) { g_err = "TS monitor: a byte count is a whole number of 188-byte packets"; return DVBS2GPU_ERR_ARG; }
-    if (nbytes / TSMON_TS > m->max_packets) { g_err = "TS monitor: packet count exceeds max_packets"; return DVBS2GPU_ERR_ARG; }
+    if (!ts_bank_check_counts("TS monitor: ", &nbytes, 1, m->max_packets)) return DVBS2GPU_ERR_ARG;
     if (h_out && h_out == h_ts) { g_err = "TS monitor: the output buffer is the input"; return DVBS2GPU_ERR_ARG; }
     if (!m->ctx) {
         TsmonCall c;
-        std::fill(m->nrows.begin(), m->nrows.end(), 0);    // as below: the table is of the LAST call, which brought the others nothing
+        std::fill(m->nrows.begin(), m->nrows.end(), 0);    // as on the device: the table is of the LAST call, which brought the others nothing
         if (m->host[stream].run(m->filt[stream], m->map.data() + (size_t)stream * TSMON_MAP_WORDS, h_ts, nbytes / TSMON_TS, h_out, cap, &c) < 0) {
             m->nrows[stream] = 0;
             g_err = "TS monitor: the passing packets do not fit cap";
@@ -433,23 +397,9 @@ int dvbs2gpu_tsmon_work(dvbs2gpu_tsmon* m, int stream, const uint8_t* h_ts, int 
         return h_out ? c.needed : 0;
     }
     HIP_TRY(hipSetDevice(m->ctx->device));
-    if (!m->d_in1) HIP_TRY(hipMalloc((void**)&m->d_in1, (size_t)m->max_packets * TSMON_TS));
-    if (nbytes > 0) HIP_TRY(hipMemcpy(m->d_in1, h_ts, nbytes, hipMemcpyHostToDevice));
-    if (h_out && m->out1_cap < (size_t)cap + 4) {
-        if (m->d_out1) (void)hipFree(m->d_out1);
-        m->d_out1 = nullptr; m->out1_cap = 0;
-        HIP_TRY(hipMalloc((void**)&m->d_out1, (size_t)cap + 4));
-        m->out1_cap = (size_t)cap + 4;
-    }
-    // the other streams of the bank bring nothing: their state and counters stay, their tables of the last call are empty
-    std::vector<const uint8_t*> in(m->nstreams, nullptr);
-    std::vector<uint8_t*> out(m->nstreams, nullptr);
-    std::vector<int> nb(m->nstreams, 0), ob(m->nstreams, 0);
-    in[stream] = m->d_in1; out[stream] = m->d_out1; nb[stream] = nbytes;
-    const int rc = dvbs2gpu_tsmon_process_batch(m, in.data(), nb.data(), h_out ? out.data() : nullptr, cap, ob.data(), nullptr);
-    if (rc < 0) return rc;
-    if (h_out && ob[stream] > 0) HIP_TRY(hipMemcpy(h_out, m->d_out1, ob[stream], hipMemcpyDeviceToHost));
-    return ob[stream];
+    return ts_bank_work(m->stage, m->nstreams, stream, h_ts, nbytes, m->max_packets, h_out, cap, false, [&](const uint8_t* const* in, const int* nb, uint8_t* const* out, int* ob) {
+        return dvbs2gpu_tsmon_process_batch(m, in, nb, out, cap, ob, nullptr);
+    });
 }
 
 int dvbs2gpu_tsmon_get_stats(dvbs2gpu_tsmon* m, int stream, dvbs2gpu_tsmon_stats* h_out) {
@@ -459,21 +409,11 @@ int dvbs2gpu_tsmon_get_stats(dvbs2gpu_tsmon* m, int stream, dvbs2gpu_tsmon_stats
 }
 
 int dvbs2gpu_tsmon_get_pid_table(dvbs2gpu_tsmon* m, int stream, dvbs2gpu_tsmon_pid* h_rows, int cap, int* n) {
-    if (!m || stream < 0 || stream >= m->nstreams || !n || cap < 0 || (cap > 0 && !h_rows)) return DVBS2GPU_ERR_ARG;
-    *n = m->nrows[stream];
-    const int k = *n < cap ? *n : cap;
-    if (k <= 0) return 0;
-    if (!m->ctx) { memcpy(h_rows, m->host[stream].rows.data(), k * sizeof(TsmonRow)); return 0; }
-    HIP_TRY(hipSetDevice(m->ctx->device));
-    HIP_TRY(hipMemcpy(h_rows, m->d_rows + (size_t)stream * m->maxrows, k * sizeof(TsmonRow), hipMemcpyDeviceToHost));
-    return 0;
+    return ts_bank_rows(m, &dvbs2gpu_tsmon::maxrows, stream, h_rows, cap, n);
 }
 
 int dvbs2gpu_tsmon_get_pid_table_device(dvbs2gpu_tsmon* m, int stream, const dvbs2gpu_tsmon_pid** d_rows, int* n) {
-    if (!m || !m->ctx || stream < 0 || stream >= m->nstreams || !n || !d_rows) return DVBS2GPU_ERR_ARG;
-    *n = m->nrows[stream];
-    *d_rows = *n ? reinterpret_cast<const dvbs2gpu_tsmon_pid*>(m->d_rows + (size_t)stream * m->maxrows) : nullptr;
-    return 0;
+    return ts_bank_rows_device(m, &dvbs2gpu_tsmon::maxrows, stream, d_rows, n);
 }
 
 }  // extern "C"

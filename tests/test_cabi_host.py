@@ -61,6 +61,21 @@ def test_no_cpu_fallback(pkg):
         pkg.Engine(0)
 
 
+def test_count_error_texts_of_both_host_banks(pkg):
+    """187 bytes and max_packets + 1 packets into the host banks of the TS monitor and of the PSI bank: the texts as the sources of the
+    commit before the banks shared their count checks spell them, behind each bank's prefix (tests/test_gpu_tsmon.py: the device banks)"""
+    mp = 8
+    ts = np.zeros((mp + 1) * 188, np.uint8)
+    texts = ('a byte count is a whole number of 188-byte packets', 'packet count exceeds max_packets')
+    for bank, prefix in ((pkg.TsMonitorBank.host(2, mp), 'TS monitor: '), (pkg.PsiBank.host(2, mp, 16), 'PSI bank: ')):
+        for nbytes, text in zip((187, (mp + 1) * 188), texts):
+            with pytest.raises(pkg.Dvbs2GpuError) as e:
+                bank.work(ts[:nbytes], stream=1)
+            assert e.value.code == -1 and str(e.value) == 'dvbs2gpu %s (-1): %s%s' % (pkg.ERR_NAMES[-1], prefix, text)
+        assert bank.stats(0)['packets'] == bank.stats(1)['packets'] == 0       # nothing was taken
+        bank.close()
+
+
 @pytest.mark.parametrize('rate,short', orc.ALL_CODES)
 def test_ldpc_plan_matches_reference_row_order(pkg, rate, short):
     lib = pkg.load_library()

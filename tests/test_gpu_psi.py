@@ -120,6 +120,17 @@ def test_slot_shapes(pkg, eng):
     assert rig.models[2].stats(3)['packets'] == 0 and rig.models[2].stats(9)['sections'] > 20
 
 
+def test_three_streams_with_an_empty_one_in_the_middle(pkg, eng):
+    """an odd stream count: the three arrays of the argument table (input pointers, output pointers, byte counts) lie where the
+    declared layout puts them, which for 3 streams is not where 3 x 8 and 3 x 16 bytes would; the empty stream has its output buffer"""
+    zp = P.Packetiser(0)
+    pats = [zp.lay([P.pat(7 + i, [(0, 0x10), (1, 0x100 + i)])]) for i in range(2)]
+    rig = Rig(pkg, eng, 3, 8, 16, watches=[[(0, 0, 0)]] * 3)
+    rig.call([pats[0], np.zeros((0, 188), np.uint8), pats[1]])
+    assert [rig.models[i].stats()['changed'] for i in range(3)] == [1, 0, 1] and rig.models[1].stats()['packets'] == 0
+    assert rig.dv.programs(0)[1] == [(0, 0x10), (1, 0x100)] and rig.dv.programs(1)[1] == [] and rig.dv.programs(2)[1] == [(0, 0x10), (1, 0x101)]
+
+
 def test_a_call_with_only_the_tail_of_a_carried_section(pkg, eng):
     z = P.Packetiser(PID)
     ts = z.lay([K._sec(900, 77)])

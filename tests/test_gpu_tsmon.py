@@ -157,6 +157,27 @@ def test_filters_and_capacity(pkg, eng):
     assert e.value.code == -1
 
 
+# as the sources of the commit before the banks shared their count checks spell them, behind each bank's prefix
+COUNT_ERRORS = ('a byte count is a whole number of 188-byte packets', 'packet count exceeds max_packets')
+
+
+def test_count_error_texts_of_both_banks(pkg, eng):
+    """187 bytes and max_packets + 1 packets, through the batch call and through the host-buffer call of a device bank"""
+    import torch
+    mp = 8
+    buf = torch.zeros((mp + 1) * 188, dtype=torch.uint8, device='cuda')
+    host = np.zeros((mp + 1) * 188, np.uint8)
+    for bank, prefix in ((pkg.TsMonitorBank(eng, 2, mp), 'TS monitor: '), (pkg.PsiBank(eng, 2, mp, 16), 'PSI bank: ')):
+        for nbytes, text in zip((187, (mp + 1) * 188), COUNT_ERRORS):
+            with pytest.raises(pkg.Dvbs2GpuError) as e:
+                bank.process([buf, buf], nbytes=[188, nbytes])
+            assert e.value.code == -1 and str(e.value) == 'dvbs2gpu %s (-1): %s%s' % (pkg.ERR_NAMES[-1], prefix, text)
+            with pytest.raises(pkg.Dvbs2GpuError) as e:
+                bank.work(host[:nbytes], stream=1)
+            assert e.value.code == -1 and str(e.value) == 'dvbs2gpu %s (-1): %s%s' % (pkg.ERR_NAMES[-1], prefix, text)
+        assert bank.stats(0)['packets'] == bank.stats(1)['packets'] == 0       # nothing was taken
+
+
 def test_70_streams_and_launch_count(pkg, eng):
     rng = np.random.default_rng(70)
     n, mp = 70, 128
