@@ -888,6 +888,110 @@ typedef struct dvbs2gpu_psi_es { uint16_t stream_type, elementary_pid; } dvbs2gp
 typedef struct dvbs2gpu_psi_pmt { int32_t program_number, version, pcr_pid, malformed; } dvbs2gpu_psi_pmt;   /* program_number -1: no PMT held */
 int dvbs2gpu_psi_get_program_map(dvbs2gpu_psi* b, int stream, int slot, dvbs2gpu_psi_pmt* hdr, dvbs2gpu_psi_es* h_rows, int cap, int* n);
 
+/* ------------------------------------------------------------------ PCR bank (own extension)
+ * Nothing in the reference does this.  For `nstreams` transport streams in HBM a bank checks the programme clock references of up to
+ * 16 watched PIDs per stream: PCR repetition, PCR discontinuity and PCR accuracy of ETSI TR 101 290 second priority (2.3a, 2.3b, 2.4),
+ * one table row per PCR.  The engine has no clock: a PCR is a 27 MHz clock, and on a constant-rate stream (DVB-S, DVB-S2 CCM) the
+ * packet position is a second one, so every check is integer arithmetic on (PCR value, packet position) pairs and no result depends
+ * on how a stream is cut into calls.  The sequential form below is the definition (csrc/pcr_rules.h, PcrHostStream::run).
+ *   Watches: 16 slots per stream, each a PID 0..0x1FFE or nothing.  A new bank watches nothing.  Changing a slot's watch starts the
+ *     slot afresh, state and counters.
+ *   Packet: 188 bytes at offset 188 k, classified as the TS monitor does.  Sync-byte errors, TEI packets and null packets are not
+ *     looked at.  Scrambling does not matter (the adaptation field is never scrambled); continuity is deliberately not consulted: a
+ *     lost packet does not make a PCR wrong.
+ *   A packet carries a PCR when AFC&2 is set, b4 (adaptation_field_length) >= 1 and b5 & 0x10 is set.  It is then malformed if
+ *     b4 < 7, or b4 > 183 (> 182 with AFC = 3), or the extension is > 299; base is the 33 bits b6 b7 b8 b9 and the top bit of b10, the
+ *     extension the low bit of b10 and b11.  A malformed packet of a watched PID is counted in its slot, gets no row and does not
+ *     step the state; one of an unwatched PID is ignored.  Otherwise P = base * 300 + ext, the value modulo M = 2^33 * 300.
+ *   A well-formed PCR packet of an unwatched PID adds to the stream's unwatched_pcr_packets; the PID of the call's first one in input
+ *     order is first_unwatched_pid (-1: none): how a caller finds PCR PIDs it did not know of.
+ *   Position: n = the stream's packet count since creation or reset + the packet's index in the call, 64 bits.  Every packet of
+ *     every call counts, untrusted ones too.
+ *   State per slot: seen; last_pcr; ref_n, the position that the next interval is measured from.
+ *   Step for a record (P, n, DI), in this order:
+ *     1. not seen: FIRST; state := (P, n).
+ *     2. DI set: ANNOUNCED; state := (P, n).
+ *     3. P == last_pcr: REPEATED; the state is unchanged (a legal duplicate packet does not shift the reference: the pair behind
+ *        a run of equal values is measured from the run's first packet).
+ *     4. dP = (P - last_pcr) mod M, dN = n - ref_n.  dP > 2 700 000 (100 ms): JUMP (2.3b; a backward step lands here).
+ *        dP > 1 080 000 (40 ms): LATE (2.3a).  Else OK.  State := (P, n).
+ *   Accuracy: LATE and OK pairs against the stream's rate, if one is set (ticks per 188-byte packet in Q24.24, tpp):
+ *     e = (dP << 24) - min(dN, 32767) * tpp (int64), accuracy = e >> 18 (arithmetic) clamped to +-(2^31 - 1), in 1/64 tick.
+ *     |accuracy| > limit: flag ACCURACY_ERROR.  dN > 32767: flag SATURATED.  No rate set: accuracy 0, no flag.
+ *   Row: one per well-formed PCR packet of a watched PID, in input order across the slots.  delta_ticks = dP and delta_packets = dN
+ *     saturate at 2^32 - 1; both are 0 for FIRST, ANNOUNCED and REPEATED.  The table holds the first max_rows rows of a call: a
+ *     monitor does not fail for room.  out_rows[] carries the true count, rows_dropped accumulates the excess, and the counters
+ *     cover every record, row or not.
+ *   State survives from call to call.  reset forgets it (positions and counters too; watches and rates stay).
+ *   Limits: max_packets <= 4096 per stream and call.  Memory (device banks) per stream: 400 bytes of state, 32 bytes per row of
+ *     max_rows and a call record of 1 KiB. */
+typedef struct dvbs2gpu_pcr dvbs2gpu_pcr;
+int dvbs2gpu_pcr_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_pcr** out);
+/* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_pcr_work only */
+int dvbs2gpu_pcr_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_pcr** out);
+int dvbs2gpu_pcr_reset(dvbs2gpu_pcr* b);
+void dvbs2gpu_pcr_destroy(dvbs2gpu_pcr* b);
+/* slot 0..15; pid 0..0x1FFE, or -1: the slot watches nothing.  The same PID in two slots of a stream is DVBS2GPU_ERR_ARG. */
+int dvbs2gpu_pcr_set_watch(dvbs2gpu_pcr* b, int stream, int slot, int pid);
+/* ticks_per_packet_q24: 27 MHz ticks per 188-byte packet in Q24.24, round(1504 * 27e6 / bit rate * 2^24) (1000 << 24 at
+ * 40.608 Mbit/s), < 2^48, 0: not set (a new bank).  limit_q6 >= 0 in 1/64 tick; a new bank has 864 = 13.5 ticks = 500 ns (TR 101 290
+ * 2.4).  The slots' states and counters stay. */
+int dvbs2gpu_pcr_set_rate(dvbs2gpu_pcr* b, int stream, uint64_t ticks_per_packet_q24, int limit_q6);
+/* d_ts[i]: DEVICE pointer to nbytes[i] bytes (a multiple of 188, at most 188*max_packets) of stream i, of any alignment.  out_rows
+ * (host, may be NULL): the records of the call per stream, of which the table holds the first max_rows.  One kernel launch.
+ * Synchronous on `stream`; chained behind a packetiser or monitor call on the same stream, no packet visits the host. */
+int dvbs2gpu_pcr_process_batch(dvbs2gpu_pcr* b, const uint8_t* const* d_ts, const int* nbytes, int* out_rows, void* stream);
+/* one stream of any bank with a HOST buffer: returns the records of the call or a negative error.  The other streams of the bank
+ * receive an empty call. */
+int dvbs2gpu_pcr_work(dvbs2gpu_pcr* b, int stream, const uint8_t* h_ts, int nbytes);
+typedef struct dvbs2gpu_pcr_stats {            /* of a slot, since creation, reset or the slot's last set_watch; kept on the host */
+    int64_t pcr_packets;             /* records: first + announced + repeated + jumps + late + ok */
+    int64_t first, announced, repeated, jumps, late, ok;
+    int64_t malformed;
+    int64_t accuracy_measured, accuracy_errors;
+    int64_t sum_ticks, sum_packets;  /* over LATE and OK pairs that are not SATURATED */
+    int64_t max_delta_ticks;         /* over LATE and OK pairs */
+    int64_t max_abs_accuracy;
+} dvbs2gpu_pcr_stats;
+/* slot -1: the sum over the stream's slots (of the two maxima the larger) */
+int dvbs2gpu_pcr_get_stats(dvbs2gpu_pcr* b, int stream, int slot, dvbs2gpu_pcr_stats* h_out);
+typedef struct dvbs2gpu_pcr_stream_stats {
+    int64_t packets;                 /* every 188 bytes handed in: the position of the next packet */
+    int64_t unwatched_pcr_packets;
+    int64_t rows_dropped;
+    int32_t first_unwatched_pid;     /* of the last call; -1: none */
+    int32_t reserved;
+    int64_t packets_since_pcr[16];   /* per slot: `packets` minus the position of the slot's last record (1: the stream's last
+                                        packet was it); -1: the slot has had none */
+} dvbs2gpu_pcr_stream_stats;
+int dvbs2gpu_pcr_get_stream_stats(dvbs2gpu_pcr* b, int stream, dvbs2gpu_pcr_stream_stats* h_out);
+/* the transport-stream rate as the slot's PCRs give it: 1504 * 27e6 * sum_packets / sum_ticks in bit/s, 0 with no pairs (slot -1:
+ * over all slots).  Host arithmetic. */
+int dvbs2gpu_pcr_get_rate(dvbs2gpu_pcr* b, int stream, int slot, double* bits_per_s);
+#define DVBS2GPU_PCR_FIRST 0
+#define DVBS2GPU_PCR_ANNOUNCED 1
+#define DVBS2GPU_PCR_REPEATED 2
+#define DVBS2GPU_PCR_OK 3
+#define DVBS2GPU_PCR_LATE 4
+#define DVBS2GPU_PCR_JUMP 5
+#define DVBS2GPU_PCR_ACCURACY_ERROR 1
+#define DVBS2GPU_PCR_SATURATED 2
+#pragma pack(push, 4)
+typedef struct dvbs2gpu_pcr_row {              /* 32 bytes; pcr lies at offset 12 */
+    uint16_t pid;
+    uint8_t slot, kind;              /* DVBS2GPU_PCR_FIRST .. DVBS2GPU_PCR_JUMP */
+    uint16_t flags, reserved;
+    int32_t packet;                  /* index in this call */
+    uint64_t pcr;                    /* P */
+    uint32_t delta_ticks, delta_packets;
+    int32_t accuracy;                /* 1/64 tick */
+} dvbs2gpu_pcr_row;
+#pragma pack(pop)
+/* h_rows[cap] (host); *n = rows of the last call in the table, of which min(*n, cap) are written */
+int dvbs2gpu_pcr_get_row_table(dvbs2gpu_pcr* b, int stream, dvbs2gpu_pcr_row* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_pcr_get_row_table_device(dvbs2gpu_pcr* b, int stream, const dvbs2gpu_pcr_row** d_rows, int* n);
+
 #ifdef __cplusplus
 }
 #endif

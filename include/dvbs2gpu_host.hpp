@@ -612,5 +612,108 @@ private:
     int status_ = 0;
     std::string error_;
 };
+
+/* PCR bank for one transport stream (dvbs2gpu_pcr_*, include/dvbs2gpu.h; an extension): PCR repetition, discontinuity and accuracy
+ * checks on up to 16 watched PIDs behind BBFrameTSParser, DVBSDemod or TSMonitor.  init() (a device bank) or initHost() (the
+ * library's host implementation, no device) and the setters throw; work() sits in the data path and does NOT throw: a failing call
+ * returns 0 and leaves its code in status() and its text in error(), sticky until clearStatus(). */
+class PcrBank {
+public:
+    PcrBank() {}
+    ~PcrBank() {
+        if (h) dvbs2gpu_pcr_destroy(h);
+    }
+    PcrBank(const PcrBank&) = delete;
+    PcrBank& operator=(const PcrBank&) = delete;
+
+    void init(int max_packets, int max_rows, int device = 0) {
+        release();
+        eng = Engine::get(device);
+        check(dvbs2gpu_pcr_create(eng->ctx, 1, max_packets, max_rows, &h));
+    }
+    void initHost(int max_packets, int max_rows) {
+        release();
+        check(dvbs2gpu_pcr_create_host(1, max_packets, max_rows, &h));
+    }
+    void reset() { check(dvbs2gpu_pcr_reset(need())); }
+    /* slot 0..15; pid -1 clears the slot */
+    void setWatch(int slot, int pid) {
+        check(dvbs2gpu_pcr_set_watch(need(), 0, slot, pid));
+        watched[slot] = pid;
+    }
+    /* 27 MHz ticks per 188-byte packet in Q24.24 (0: no accuracy check), the accuracy limit in 1/64 tick */
+    void setRate(uint64_t ticks_per_packet_q24, int limit_q6 = 864) { check(dvbs2gpu_pcr_set_rate(need(), 0, ticks_per_packet_q24, limit_q6)); }
+    /* watches the PCR PIDs of the PMTs that `psi` holds decoded, in free slots, in the order of its slots; 0x1FFF and PIDs watched
+     * already are skipped; returns the PIDs that found no free slot */
+    std::vector<int> followPmts(PsiBank& psi) {
+        std::vector<int> left;
+        for (int slot = 0; slot < 16; ++slot) {
+            dvbs2gpu_psi_pmt pmt;
+            psi.programMap(slot, &pmt);
+            const int pid = pmt.pcr_pid;
+            if (pmt.program_number < 0 || pid < 0 || pid == 0x1FFF || std::find(watched, watched + 16, pid) != watched + 16 ||
+                std::find(left.begin(), left.end(), pid) != left.end())
+                continue;
+            int* free_slot = std::find(watched, watched + 16, -1);
+            if (free_slot == watched + 16) left.push_back(pid);
+            else setWatch((int)(free_slot - watched), pid);
+        }
+        return left;
+    }
+    /* nbytes of whole TS packets in; returns the records (PCR packets of watched PIDs) of the call, 0 on failure (see status()) */
+    int work(const uint8_t* ts, int nbytes) noexcept {
+        const int n = h ? dvbs2gpu_pcr_work(h, 0, ts, nbytes) : DVBS2GPU_ERR_ARG;
+        if (n >= 0) return n;
+        if (status_ == 0) {
+            status_ = n;
+            try { error_ = h ? dvbs2gpu_last_error() : "PcrBank used before init()"; } catch (...) {}
+        }
+        return 0;
+    }
+    int status() const { return status_; }
+    const std::string& error() const { return error_; }
+    void clearStatus() { status_ = 0; error_.clear(); }
+
+    dvbs2gpu_pcr_stats stats(int slot = -1) {
+        dvbs2gpu_pcr_stats s;
+        check(dvbs2gpu_pcr_get_stats(need(), 0, slot, &s));
+        return s;
+    }
+    dvbs2gpu_pcr_stream_stats streamStats() {
+        dvbs2gpu_pcr_stream_stats s;
+        check(dvbs2gpu_pcr_get_stream_stats(need(), 0, &s));
+        return s;
+    }
+    /* bit/s as the slot's PCRs give it; 0 with no pairs */
+    double rate(int slot = -1) {
+        double v = 0;
+        check(dvbs2gpu_pcr_get_rate(need(), 0, slot, &v));
+        return v;
+    }
+    /* one row per PCR of the last work(), in input order (the first max_rows) */
+    std::vector<dvbs2gpu_pcr_row> rowTable() {
+        int n = 0;
+        check(dvbs2gpu_pcr_get_row_table(need(), 0, nullptr, 0, &n));
+        std::vector<dvbs2gpu_pcr_row> rows((size_t)n);
+        if (n > 0) check(dvbs2gpu_pcr_get_row_table(h, 0, rows.data(), n, &n));
+        return rows;
+    }
+
+private:
+    void release() {
+        if (h) dvbs2gpu_pcr_destroy(h);
+        h = nullptr;
+        std::fill(watched, watched + 16, -1);
+    }
+    dvbs2gpu_pcr* need() {
+        if (!h) throw std::runtime_error("dvbs2gpu: PcrBank used before init()");
+        return h;
+    }
+    std::shared_ptr<Engine> eng;
+    dvbs2gpu_pcr* h = nullptr;
+    int watched[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // slot -> PID, as setWatch left them
+    int status_ = 0;
+    std::string error_;
+};
 }   // namespace dvbs2gpu_host
 #endif

@@ -145,6 +145,25 @@ class PsiPmt(C.Structure):
     _fields_ = [('program_number', C.c_int32), ('version', C.c_int32), ('pcr_pid', C.c_int32), ('malformed', C.c_int32)]
 
 
+class PcrStats(C.Structure):
+    """dvbs2gpu_pcr_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('pcr_packets', 'first', 'announced', 'repeated', 'jumps', 'late', 'ok', 'malformed', 'accuracy_measured',
+                                         'accuracy_errors', 'sum_ticks', 'sum_packets', 'max_delta_ticks', 'max_abs_accuracy')]
+
+
+class PcrStreamStats(C.Structure):
+    """dvbs2gpu_pcr_stream_stats"""
+    _fields_ = [('packets', C.c_int64), ('unwatched_pcr_packets', C.c_int64), ('rows_dropped', C.c_int64), ('first_unwatched_pid', C.c_int32),
+                ('reserved', C.c_int32), ('packets_since_pcr', C.c_int64 * 16)]
+
+
+class PcrRow(C.Structure):
+    """dvbs2gpu_pcr_row"""
+    _pack_ = 4
+    _fields_ = [('pid', C.c_uint16), ('slot', C.c_uint8), ('kind', C.c_uint8), ('flags', C.c_uint16), ('reserved', C.c_uint16), ('packet', C.c_int32),
+                ('pcr', C.c_uint64), ('delta_ticks', C.c_uint32), ('delta_packets', C.c_uint32), ('accuracy', C.c_int32)]
+
+
 class FrameQuality(C.Structure):
     """dvbs2gpu_frame_quality"""
     _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('gain', C.c_float), ('phase', C.c_float), ('known_symbols', C.c_int32),
@@ -312,6 +331,19 @@ PROTOTYPES = {
     'dvbs2gpu_psi_get_section_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
     'dvbs2gpu_psi_get_programs': (_i, [_vp, _i, C.POINTER(PsiPat), C.POINTER(PsiProgram), _i, C.POINTER(_i)]),
     'dvbs2gpu_psi_get_program_map': (_i, [_vp, _i, _i, C.POINTER(PsiPmt), C.POINTER(PsiEs), _i, C.POINTER(_i)]),
+    'dvbs2gpu_pcr_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_pcr_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_pcr_reset': (_i, [_vp]),
+    'dvbs2gpu_pcr_destroy': (None, [_vp]),
+    'dvbs2gpu_pcr_set_watch': (_i, [_vp, _i, _i, _i]),
+    'dvbs2gpu_pcr_set_rate': (_i, [_vp, _i, C.c_uint64, _i]),
+    'dvbs2gpu_pcr_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _vp]),
+    'dvbs2gpu_pcr_work': (_i, [_vp, _i, _vp, _i]),
+    'dvbs2gpu_pcr_get_stats': (_i, [_vp, _i, _i, C.POINTER(PcrStats)]),
+    'dvbs2gpu_pcr_get_stream_stats': (_i, [_vp, _i, C.POINTER(PcrStreamStats)]),
+    'dvbs2gpu_pcr_get_rate': (_i, [_vp, _i, _i, C.POINTER(C.c_double)]),
+    'dvbs2gpu_pcr_get_row_table': (_i, [_vp, _i, C.POINTER(PcrRow), _i, C.POINTER(_i)]),
+    'dvbs2gpu_pcr_get_row_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
 }
 
 _lib = None
@@ -1407,6 +1439,105 @@ class PsiBank(_TsBank):
         hdr = PsiPmt()
         rows = self._rows(self.lib.dvbs2gpu_psi_get_program_map, PsiEs, int(stream), int(slot), C.byref(hdr))
         return {k: int(getattr(hdr, k)) for k, _ in PsiPmt._fields_}, [(r.stream_type, r.elementary_pid) for r in rows]
+
+
+class PcrBank(_TsBank):
+    """PCR bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, PCR bank): PCR repetition, discontinuity and
+    accuracy checks on up to 16 watched PIDs per stream, one table row per PCR, in integers on (PCR value, packet position)."""
+    _destroy = 'dvbs2gpu_pcr_destroy'
+    SLOTS = 16
+    FIRST, ANNOUNCED, REPEATED, OK, LATE, JUMP = range(6)
+    ACCURACY_ERROR, SATURATED = 1, 2
+    DEFAULT_LIMIT_Q6 = 864
+    ROW_KEYS = tuple(k for k, _ in PcrRow._fields_)
+
+    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=1024):
+        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
+        h = C.c_void_p()
+        engine._check(self.lib.dvbs2gpu_pcr_create(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
+        self.h = h
+        self._watched = [{} for _ in range(nstreams)]               # per stream: slot -> PID, as set_watch left them
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096, max_rows=1024):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        self = cls._host('dvbs2gpu_pcr_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
+        self._watched = [{} for _ in range(nstreams)]
+        return self
+
+    def reset(self):
+        """forgets states, positions and counters; watches and rates stay"""
+        self._check(self.lib.dvbs2gpu_pcr_reset(self.h))
+
+    def set_watch(self, stream, slot, pid):
+        """pid -1 clears the slot; the slot starts afresh"""
+        self._check(self.lib.dvbs2gpu_pcr_set_watch(self.h, int(stream), int(slot), int(pid)))
+        self._watched[int(stream)].pop(int(slot), None)
+        if pid >= 0:
+            self._watched[int(stream)][int(slot)] = int(pid)
+
+    def set_rate(self, stream, ticks_per_packet_q24, limit_q6=DEFAULT_LIMIT_Q6):
+        """27 MHz ticks per 188-byte packet in Q24.24 (0: no accuracy check) and the accuracy limit in 1/64 tick"""
+        self._check(self.lib.dvbs2gpu_pcr_set_rate(self.h, int(stream), int(ticks_per_packet_q24), int(limit_q6)))
+
+    def follow_pmts(self, psi_bank, stream=0):
+        """watches the PCR PIDs of the PMTs that `psi_bank` (a PsiBank that read the same stream) holds decoded, in free slots, in the
+        order of its slots; 0x1FFF (a programme without a PCR) and PIDs watched already are skipped -> the PIDs that found no free slot"""
+        watched = self._watched[int(stream)]
+        left = []
+        for slot in range(psi_bank.SLOTS):
+            hdr = psi_bank.program_map(stream, slot)[0]
+            pid = hdr['pcr_pid']
+            if hdr['program_number'] < 0 or pid < 0 or pid == 0x1FFF or pid in watched.values() or pid in left:
+                continue
+            free = [s for s in range(self.SLOTS) if s not in watched]
+            if free:
+                self.set_watch(stream, free[0], pid)
+            else:
+                left.append(pid)
+        return left
+
+    def process(self, ts_tensors, nbytes=None):
+        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all), of any alignment -> the records of the
+        call per stream (the table holds the first max_rows of them)"""
+        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
+        nr = (C.c_int * self.nstreams)()
+        self._check(self.lib.dvbs2gpu_pcr_process_batch(self.h, pin, cnt, nr, self.eng._stream()))
+        return list(nr)
+
+    def work(self, ts, stream=0):
+        """one stream, a host buffer: numpy uint8 packets in -> the records of the call"""
+        import numpy as np
+        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
+        return self._check(self.lib.dvbs2gpu_pcr_work(self.h, int(stream), C.c_void_p(ts.ctypes.data), ts.size))
+
+    def stats(self, stream=0, slot=-1):
+        st = PcrStats()
+        self._check(self.lib.dvbs2gpu_pcr_get_stats(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in PcrStats._fields_}
+
+    def stream_stats(self, stream=0):
+        st = PcrStreamStats()
+        self._check(self.lib.dvbs2gpu_pcr_get_stream_stats(self.h, int(stream), C.byref(st)))
+        return dict(packets=int(st.packets), unwatched_pcr_packets=int(st.unwatched_pcr_packets), rows_dropped=int(st.rows_dropped),
+                    first_unwatched_pid=int(st.first_unwatched_pid), packets_since_pcr=[int(v) for v in st.packets_since_pcr])
+
+    def rate(self, stream=0, slot=-1):
+        """the transport-stream rate in bit/s as the slot's PCRs give it (0.0: no pairs yet)"""
+        v = C.c_double()
+        self._check(self.lib.dvbs2gpu_pcr_get_rate(self.h, int(stream), int(slot), C.byref(v)))
+        return v.value
+
+    def row_table(self, stream=0):
+        """one dict per row of the last call (the fields of dvbs2gpu_pcr_row but `reserved`), in input order"""
+        rows = self._rows(self.lib.dvbs2gpu_pcr_get_row_table, PcrRow, int(stream))
+        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS if k != 'reserved'} for r in rows]
+
+    def row_table_device(self, stream=0):
+        """(device pointer or None, rows): the same table as dvbs2gpu_pcr_row records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self.lib.dvbs2gpu_pcr_get_row_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
+        return p.value, n.value
 
 
 class SegmentReceiver(_Handle):

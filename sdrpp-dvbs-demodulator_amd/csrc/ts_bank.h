@@ -1,7 +1,7 @@
-// Shared by the banks that work on transport streams in HBM (tsmon.hip: the TS monitor; psi.hip: the PSI sections):
+// Shared by the banks that work on transport streams in HBM (tsmon.hip: the TS monitor; psi.hip: the PSI sections; pcr.hip: the PCRs):
 // what a "packet bank" does around its rules.  On the device: the one header read, the one workgroup prefix sum and the contiguous
 // run of items a thread takes ("flags in a mask, scan, scatter").  On the host: the argument table of a call, the count checks,
-// the staging of the single-stream host-buffer entry point and the table getters.  The rules stay in tsmon_rules.h / psi_rules.h.
+// the staging of the single-stream host-buffer entry point and the table getters.  The rules stay in tsmon_rules.h / psi_rules.h / pcr_rules.h.
 #pragma once
 #include "bbts_common.h"
 #include "tsmon_rules.h"
@@ -17,6 +17,12 @@ __device__ inline TsmonHdr ts_load_header(const uint8_t* __restrict__ ts, int k,
     const uint8_t h[8] = {(uint8_t)a, (uint8_t)(a >> 8), (uint8_t)(a >> 16), (uint8_t)(a >> 24), (uint8_t)b, (uint8_t)(b >> 8), 0, 0};
     if (b4) *b4 = b & 255;
     return tsmon_parse(h);
+}
+
+// header dword d of packet k, bytes 4 d .. 4 d + 3: d 1 holds the adaptation field's length and flags, d 2 (bytes 8..11, still inside
+// the packet) what a bank reads of the field's first entry, the PCR
+__device__ inline unsigned ts_load_header_dword(const uint8_t* __restrict__ ts, int k, int d) {
+    return *reinterpret_cast<const ts_unaligned_u32*>(ts + (size_t)k * TSMON_TS + 4 * d);
 }
 
 // exclusive prefix sum of one int per thread over the WG threads of the workgroup; *total: the sum.  wsum: WG / 64 ints of LDS
