@@ -102,12 +102,12 @@ __global__ void __launch_bounds__(256) bbts_emit_kernel(const uint8_t* const* __
 struct dvbs2gpu_bbts {
     dvbs2gpu_ctx* ctx = nullptr;
     int nstreams = 0, kbch = 0, max_frames = 0;
-    BbtsDevState* d_state = nullptr;
-    uint8_t* d_reasm[2] = {nullptr, nullptr};
+    DevBuf<BbtsDevState> d_state;
+    DevBuf<uint8_t> d_reasm[2];
     int cur = 0;
-    BbtsFrameDesc* d_desc = nullptr;
-    BbtsStreamPlan* d_plan = nullptr;
-    void* d_args = nullptr;                    // BankArgs(nstreams): [in ptrs][out ptrs][nframes][out bytes]
+    DevBuf<BbtsFrameDesc> d_desc;
+    DevBuf<BbtsStreamPlan> d_plan;
+    DevBuf<uint8_t> d_args;                    // BankArgs(nstreams): [in ptrs][out ptrs][nframes][out bytes]
     Workspace in1, out1;                       // staging of the single-stream host-buffer entry point
     std::vector<std::unique_ptr<BbtsHostParser>> host;
     std::vector<BbtsStreamPlan> h_plan;
@@ -173,9 +173,6 @@ void dvbs2gpu_bbts_destroy(dvbs2gpu_bbts* b) {
     if (!b) return;
     bbts_ma_free(b->ma);
     bbts_gse_free(b->gse);
-    void* ps[] = {b->d_state, b->d_reasm[0], b->d_reasm[1], b->d_desc, b->d_plan, b->d_args};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    b->in1.release(); b->out1.release();
     delete b;
 }
 
@@ -194,7 +191,7 @@ int dvbs2gpu_bbts_set_frame_size(dvbs2gpu_bbts* b, int kbch_bits) {
 int dvbs2gpu_bbts_create(dvbs2gpu_ctx* ctx, int nstreams, int kbch_bits, int max_frames, dvbs2gpu_bbts** out) {
     if (!ctx || !out || nstreams <= 0 || max_frames <= 0 || kbch_bits < 88 || kbch_bits % 8 || kbch_bits > 65536) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    auto b = new dvbs2gpu_bbts();
+    std::unique_ptr<dvbs2gpu_bbts> b(new dvbs2gpu_bbts());
     b->ctx = ctx; b->nstreams = nstreams; b->kbch = kbch_bits; b->max_frames = max_frames;
     b->host.resize(nstreams);
     b->h_plan.resize(nstreams);
@@ -202,14 +199,13 @@ int dvbs2gpu_bbts_create(dvbs2gpu_ctx* ctx, int nstreams, int kbch_bits, int max
     b->nrows.assign(nstreams, 0); b->rows_host.assign(nstreams, 0);
     b->fb_records.assign(nstreams, 0); b->fb_capacity.assign(nstreams, 0);
     const size_t n = (size_t)nstreams;
-    hipError_t e = hipSuccess;
-    bbts_alloc(e, &b->d_state, n * sizeof(BbtsDevState));
-    bbts_alloc(e, &b->d_reasm[0], n * REASM_STRIDE); bbts_alloc(e, &b->d_reasm[1], n * REASM_STRIDE);
-    bbts_alloc(e, &b->d_desc, n * max_frames * sizeof(BbtsFrameDesc));
-    bbts_alloc(e, &b->d_plan, n * sizeof(BbtsStreamPlan));
-    bbts_alloc(e, &b->d_args, BankArgs(n).L.bytes());
-    if (e != hipSuccess) { dvbs2gpu_bbts_destroy(b); return fail_hip(e, "hipMalloc(bbts)"); }
-    *out = b;
+    const char* what = "hipMalloc(bbts)";
+    RC_TRY(b->d_state.alloc(n, true, what));
+    for (auto& r : b->d_reasm) RC_TRY(r.alloc(n * REASM_STRIDE, true, what));
+    RC_TRY(b->d_desc.alloc(n * max_frames, true, what));
+    RC_TRY(b->d_plan.alloc(n, true, what));
+    RC_TRY(b->d_args.alloc(BankArgs(n).L.bytes(), true, what));
+    *out = b.release();
     return 0;
 }
 

@@ -96,13 +96,6 @@ inline int gse_ctx_to_device(const GseHostCtx& c, GseDevState* d_state, uint8_t*
     HIP_TRY(hipMemcpy(d_state, &c.g, sizeof(c.g), hipMemcpyHostToDevice));
     return 0;
 }
-// one of a run of device allocations, zero-filled unless told otherwise; `e` keeps the run's first error and later calls do nothing
-template <typename T>
-inline void bbts_alloc(hipError_t& e, T** p, size_t bytes, bool zero = true) {
-    if (e == hipSuccess) e = hipMalloc((void**)p, bytes);
-    if (e == hipSuccess && zero) e = hipMemset(*p, 0, bytes);
-}
-
 struct BbtsMa;                                  // bbts_ma.hip
 void bbts_ma_free(BbtsMa* m);
 struct BbtsBankView {

@@ -24,12 +24,12 @@ namespace s2 {
 
 struct BbtsGse {
     int nstreams = 0, max_frames = 0;
-    GseDevState* d_state = nullptr;
-    GseFrameRec* d_frec = nullptr;          // [stream][max_frames]
-    GsePkt* d_pkt = nullptr;                // [stream][max_frames][GSE_PKT_CAP]
-    dvbs2gpu_gse_pdu* d_rows = nullptr;     // [stream][max_frames * GSE_PKT_CAP]
-    GseStreamOut* d_sout = nullptr;
-    uint8_t* d_slots = nullptr;             // [stream][3][GSE_SLOT_BYTES]
+    DevBuf<GseDevState> d_state;
+    DevBuf<GseFrameRec> d_frec;             // [stream][max_frames]
+    DevBuf<GsePkt> d_pkt;                   // [stream][max_frames][GSE_PKT_CAP]
+    DevBuf<dvbs2gpu_gse_pdu> d_rows;        // [stream][max_frames * GSE_PKT_CAP]
+    DevBuf<GseStreamOut> d_sout;
+    DevBuf<uint8_t> d_slots;                // [stream][3][GSE_SLOT_BYTES]
 };
 
 // ---------------------------------------------------------------------------------------------------------------- frame pass
@@ -180,26 +180,20 @@ __global__ void __launch_bounds__(256) gse_append_kernel(const uint8_t* const* _
 }
 
 // -------------------------------------------------------------------------------------------------------------------- host
-void bbts_gse_free(BbtsGse* g) {
-    if (!g) return;
-    void* ps[] = {g->d_state, g->d_frec, g->d_pkt, g->d_rows, g->d_sout, g->d_slots};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    delete g;
-}
+void bbts_gse_free(BbtsGse* g) { delete g; }
 
 int bbts_gse_create(int nstreams, int max_frames, BbtsGse** out) {
-    auto g = new BbtsGse();
+    std::unique_ptr<BbtsGse> g(new BbtsGse());
     g->nstreams = nstreams; g->max_frames = max_frames;
     const size_t n = (size_t)nstreams, np = n * max_frames * GSE_PKT_CAP;
-    hipError_t e = hipSuccess;
-    bbts_alloc(e, &g->d_state, n * sizeof(GseDevState));
-    bbts_alloc(e, &g->d_frec, n * max_frames * sizeof(GseFrameRec));
-    bbts_alloc(e, &g->d_pkt, np * sizeof(GsePkt), false);
-    bbts_alloc(e, &g->d_rows, np * sizeof(dvbs2gpu_gse_pdu), false);
-    bbts_alloc(e, &g->d_sout, n * sizeof(GseStreamOut));
-    bbts_alloc(e, &g->d_slots, n * 3 * GSE_SLOT_BYTES, false);
-    if (e != hipSuccess) { bbts_gse_free(g); return fail_hip(e, "hipMalloc(bbts gse)"); }
-    *out = g;
+    const char* what = "hipMalloc(bbts gse)";
+    RC_TRY(g->d_state.alloc(n, true, what));
+    RC_TRY(g->d_frec.alloc(n * max_frames, true, what));
+    RC_TRY(g->d_pkt.alloc(np, false, what));
+    RC_TRY(g->d_rows.alloc(np, false, what));
+    RC_TRY(g->d_sout.alloc(n, true, what));
+    RC_TRY(g->d_slots.alloc(n * 3 * GSE_SLOT_BYTES, false, what));
+    *out = g.release();
     return 0;
 }
 

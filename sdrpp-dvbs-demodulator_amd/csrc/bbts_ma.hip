@@ -547,27 +547,27 @@ struct BbtsMa {
     MaCfg cfg;
     std::vector<MaSel> sel;
     // device banks
-    MaLaneState* d_lane[2] = {nullptr, nullptr};
-    MaStreamState* d_strm[2] = {nullptr, nullptr};
-    uint8_t* d_carry[2] = {nullptr, nullptr};
+    DevBuf<MaLaneState> d_lane[2];
+    DevBuf<MaStreamState> d_strm[2];
+    DevBuf<uint8_t> d_carry[2];
     int cur = 0;
-    MaSel* d_sel = nullptr;
-    uint8_t *d_tabs = nullptr, *d_join = nullptr;
-    MaFrameRec* d_recs = nullptr;
-    MaFrameDesc* d_desc = nullptr;
-    MaFin* d_fins = nullptr;
-    void* d_args = nullptr;                    // MaArgs: [in ptrs][8 out ptrs per stream][nframes][needed per lane][frame offsets]
+    DevBuf<MaSel> d_sel;
+    DevBuf<uint8_t> d_tabs, d_join;
+    DevBuf<MaFrameRec> d_recs;
+    DevBuf<MaFrameDesc> d_desc;
+    DevBuf<MaFin> d_fins;
+    DevBuf<uint8_t> d_args;                    // MaArgs: [in ptrs][8 out ptrs per stream][nframes][needed per lane][frame offsets]
     std::vector<int> h_foff;
     Workspace in1, out1;                       // staging of the single-stream host-buffer entry point
     // GSE (dvbs2gpu_bbts_ma_set_gse): contexts and per-call results from the first switch-on; records, rows and slot buffers from the
     // first GSE frame.  The slot pool has 3 x 64 KiB per SELECTED lane: slotmap[stream * 8 + k] is the lane's place in it or -1.
-    MaGseLane* d_glane[2] = {nullptr, nullptr};
-    MaGseOut* d_gout = nullptr;
-    int* d_slotmap = nullptr;
-    MaGseFrame* d_gfr = nullptr;
-    GsePkt* d_pkt = nullptr;
-    dvbs2gpu_gse_pdu* d_rows = nullptr;
-    uint8_t* d_slots = nullptr;
+    DevBuf<MaGseLane> d_glane[2];
+    DevBuf<MaGseOut> d_gout;
+    DevBuf<int> d_slotmap;
+    DevBuf<MaGseFrame> d_gfr;
+    DevBuf<GsePkt> d_pkt;
+    DevBuf<dvbs2gpu_gse_pdu> d_rows;
+    DevBuf<uint8_t> d_slots;
     size_t slot_cap = 0;                       // lanes the pool holds
     std::vector<int> slotmap, slot_free, ginfo;
     std::vector<long long> fb_calls;           // per stream: calls the host parser ran
@@ -578,15 +578,7 @@ struct BbtsMa {
     MaHostStream tool;                         // flush of a device bank
 };
 
-void bbts_ma_free(BbtsMa* m) {
-    if (!m) return;
-    void* ps[] = {m->d_lane[0], m->d_lane[1], m->d_strm[0], m->d_strm[1], m->d_carry[0], m->d_carry[1], m->d_sel, m->d_tabs, m->d_join,
-                  m->d_recs, m->d_desc, m->d_fins, m->d_args, m->d_glane[0], m->d_glane[1], m->d_gout, m->d_slotmap,
-                  m->d_gfr, m->d_pkt, m->d_rows, m->d_slots};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    m->in1.release(); m->out1.release();
-    delete m;
-}
+void bbts_ma_free(BbtsMa* m) { delete m; }
 
 static int ma_upload_sel(const BbtsBankView& v, BbtsMa* m) {
     if (!v.ctx) return 0;
@@ -620,15 +612,14 @@ static int ma_gse_upload_map(BbtsMa* m) {
 // the pool grows to `lanes` places; what the lanes in it hold is kept
 static int ma_gse_grow_pool(BbtsMa* m, size_t lanes) {
     if (lanes <= m->slot_cap) return 0;
-    uint8_t* nw = nullptr;
-    HIP_TRY(hipMalloc((void**)&nw, lanes * 3 * GSE_SLOT_BYTES));
+    DevBuf<uint8_t> nw;
+    RC_TRY(nw.alloc(lanes * 3 * GSE_SLOT_BYTES, false, "hipMalloc(bbts gse slots)"));
     if (m->d_slots) {
         hipError_t e = hipMemcpy(nw, m->d_slots, m->slot_cap * 3 * GSE_SLOT_BYTES, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) { (void)hipFree(nw); return fail_hip(e, "hipMemcpy(bbts gse slots)"); }
-        (void)hipFree(m->d_slots);
+        if (e != hipSuccess) return fail_hip(e, "hipMemcpy(bbts gse slots)");
     }
     for (size_t k = lanes; k-- > m->slot_cap;) m->slot_free.push_back((int)k);
-    m->d_slots = nw; m->slot_cap = lanes;
+    m->d_slots = std::move(nw); m->slot_cap = lanes;
     return 0;
 }
 // every selected lane of `stream` gets a place in the pool (its old ones go back first: a new selection starts afresh)
@@ -655,13 +646,13 @@ static int ma_gse_storage(const BbtsBankView& v, BbtsMa* m) {
     size_t lanes = 0;
     for (const MaSel& s : m->sel) lanes += s.n;
     // a call that failed half way (the pool is the large one) left what it had got: taken up here, not allocated again
-    if (!m->d_gfr) HIP_TRY(hipMalloc((void**)&m->d_gfr, nfr * sizeof(MaGseFrame)));
-    if (!m->d_rows) HIP_TRY(hipMalloc((void**)&m->d_rows, nfr * GSE_PKT_CAP * sizeof(dvbs2gpu_gse_pdu)));
+    const char* what = "hipMalloc(bbts mode adaptation gse)";
+    if (!m->d_gfr) RC_TRY(m->d_gfr.alloc(nfr, false, what));
+    if (!m->d_rows) RC_TRY(m->d_rows.alloc(nfr * GSE_PKT_CAP, false, what));
     int rc = ma_gse_grow_pool(m, lanes > 0 ? lanes : 1);
     for (int i = 0; i < v.nstreams && !rc; ++i) rc = ma_gse_place_stream(m, i);
     if (rc || (rc = ma_gse_upload_map(m))) return rc;
-    HIP_TRY(hipMalloc((void**)&m->d_pkt, nfr * GSE_PKT_CAP * sizeof(GsePkt)));
-    return 0;
+    return m->d_pkt.alloc(nfr * GSE_PKT_CAP, false, what);
 }
 
 // the three slot buffers of lane w, or null while it has no place in the pool
@@ -740,20 +731,19 @@ int dvbs2gpu_bbts_set_mode_adaptation(dvbs2gpu_bbts* b, const dvbs2gpu_bbts_ma_c
     m->sel.assign(v.nstreams, s0);
     const size_t n = v.nstreams, nl = n * MA_LANES, nfr = n * v.max_frames;
     if (v.ctx) {
-        hipError_t e = hipSuccess;
+        const char* what = "hipMalloc(bbts mode adaptation)";
         for (int k = 0; k < 2; ++k) {
-            bbts_alloc(e, &m->d_lane[k], nl * sizeof(MaLaneState));
-            bbts_alloc(e, &m->d_strm[k], n * sizeof(MaStreamState));
-            bbts_alloc(e, &m->d_carry[k], nl * MA_CARRY);
+            RC_TRY(m->d_lane[k].alloc(nl, true, what));
+            RC_TRY(m->d_strm[k].alloc(n, true, what));
+            RC_TRY(m->d_carry[k].alloc(nl * MA_CARRY, true, what));
         }
-        bbts_alloc(e, &m->d_sel, n * sizeof(MaSel));
-        bbts_alloc(e, &m->d_tabs, MA_TAB_BYTES);
-        bbts_alloc(e, &m->d_join, nfr * MA_CARRY);
-        bbts_alloc(e, &m->d_recs, nfr * sizeof(MaFrameRec));
-        bbts_alloc(e, &m->d_desc, nfr * sizeof(MaFrameDesc));
-        bbts_alloc(e, &m->d_fins, nl * sizeof(MaFin));
-        bbts_alloc(e, &m->d_args, MaArgs(n, v.max_frames).L.bytes());
-        if (e != hipSuccess) { bbts_ma_free(m.release()); return fail_hip(e, "hipMalloc(bbts mode adaptation)"); }
+        RC_TRY(m->d_sel.alloc(n, true, what));
+        RC_TRY(m->d_tabs.alloc(MA_TAB_BYTES, true, what));
+        RC_TRY(m->d_join.alloc(nfr * MA_CARRY, true, what));
+        RC_TRY(m->d_recs.alloc(nfr, true, what));
+        RC_TRY(m->d_desc.alloc(nfr, true, what));
+        RC_TRY(m->d_fins.alloc(nl, true, what));
+        RC_TRY(m->d_args.alloc(MaArgs(n, v.max_frames).L.bytes(), true, what));
         uint8_t t[MA_TAB_BYTES];
         ma_build_tables(t);
         HIP_TRY(hipMemcpy(m->d_tabs, t, sizeof(t), hipMemcpyHostToDevice));
@@ -1061,12 +1051,10 @@ int dvbs2gpu_bbts_ma_set_gse(dvbs2gpu_bbts* b, int on) {
     HIP_TRY(hipSetDevice(v.ctx->device));
     const size_t nl = (size_t)v.nstreams * MA_LANES;
     if (on && !m->d_glane[0]) {
-        for (int k = 0; k < 2; ++k) {
-            HIP_TRY(hipMalloc((void**)&m->d_glane[k], nl * sizeof(MaGseLane)));
-            HIP_TRY(hipMemset(m->d_glane[k], 0, nl * sizeof(MaGseLane)));
-        }
-        HIP_TRY(hipMalloc((void**)&m->d_gout, nl * sizeof(MaGseOut)));
-        HIP_TRY(hipMalloc((void**)&m->d_slotmap, 2 * nl * sizeof(int)));
+        const char* what = "hipMalloc(bbts mode adaptation gse)";
+        for (auto& gl : m->d_glane) RC_TRY(gl.alloc(nl, true, what));
+        RC_TRY(m->d_gout.alloc(nl, false, what));
+        RC_TRY(m->d_slotmap.alloc(2 * nl, false, what));
         m->slotmap.assign(nl, -1); m->ginfo.assign(nl, 0); m->rows_host.assign(nl, 0);
         m->fb_rows.resize(nl); m->fb_calls.assign(v.nstreams, 0);
     }

@@ -16,6 +16,17 @@ int fail_hip(hipError_t e, const char* what) {
     g_err = std::string(what) + ": " + hipGetErrorString(e);
     return DVBS2GPU_ERR_HIP;
 }
+// the one place that calls the allocator (dev_buf.h)
+int dev_alloc(void** p, size_t bytes, bool zero, const char* what) {
+    *p = nullptr;
+    hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess && zero) e = hipMemset(*p, 0, bytes);
+    if (e == hipSuccess) return 0;
+    dev_free(*p);
+    *p = nullptr;
+    return fail_hip(e, what);
+}
+void dev_free(void* p) { if (p) (void)hipFree(p); }
 }  // namespace s2
 #define g_err s2::last_error()
 
@@ -44,12 +55,10 @@ static int stage_enter(dvbs2gpu_ctx* ctx, hipStream_t st) {
     return ws_acquire(ctx, st);
 }
 
-void free_ldpc_code(LdpcDeviceCode& D);
 static int drop_ldpc_cache(dvbs2gpu_ctx* c) {
     if (fec_jobs_pending(c)) { last_error() = "option changes the decoder plan while pipelined FEC jobs are in flight"; return -1; }
     if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
     std::lock_guard<std::mutex> l(c->mtx);
-    for (auto& kv : c->ldpc) free_ldpc_code(kv.second);
     c->ldpc.clear();
     return 0;
 }
@@ -80,28 +89,19 @@ int apply_option(dvbs2gpu_ctx* c, const char* name, int v) {
     return 0;
 }
 
-// every device table of one code (hipFree(nullptr) is a no-op)
-void free_ldpc_code(LdpcDeviceCode& D) {
-    (void)hipFree(D.d_layers); (void)hipFree(D.d_ents); (void)hipFree(D.d_rows); (void)hipFree(D.d_atab);
-    (void)hipFree(D.d_wave_lanec); (void)hipFree(D.d_wave_steps); (void)hipFree(D.d_wave_layer_end);
-    (void)hipFree(D.d_split_layers); (void)hipFree(D.d_split_atab);
-    D.d_split_layers = nullptr; D.d_split_atab = nullptr;
-    D.d_layers = nullptr; D.d_ents = D.d_rows = D.d_atab = D.d_wave_lanec = D.d_wave_layer_end = nullptr; D.d_wave_steps = nullptr;
-}
 int get_ldpc(dvbs2gpu_ctx* ctx, int code_index, LdpcDeviceCode** out) {
     std::lock_guard<std::mutex> l(ctx->mtx);
     auto it = ctx->ldpc.find(code_index);
     if (it == ctx->ldpc.end()) {
         LdpcPlan P = build_ldpc_plan(code_index);
-        LdpcDeviceCode D;
+        LdpcCode D;
         D.code_index = code_index;
         D.N = P.N; D.K = P.K; D.R = P.R; D.q = P.q; D.max_deg = P.max_deg; D.irregular = (P.min_deg != P.max_deg); D.rec_dwords = P.rec_dwords; D.edges = P.edges; D.pent_base = P.pent_base; D.synd_base = P.synd_base;
         int rc;
-        auto fail = [&D](int e) { free_ldpc_code(D); return e; };      // (a failed upload gives the earlier ones back)
-        if ((rc = upload(P.layers, &D.d_layers))) return fail(rc);
-        if ((rc = upload(P.ents, &D.d_ents))) return fail(rc);
-        if ((rc = upload(P.rows, &D.d_rows))) return fail(rc);
-        if (!P.atab.empty() && (rc = upload(P.atab, &D.d_atab))) return fail(rc);
+        if ((rc = upload(P.layers, D.layers, &D.d_layers))) return rc;
+        if ((rc = upload(P.ents, D.ents, &D.d_ents))) return rc;
+        if ((rc = upload(P.rows, D.rows, &D.d_rows))) return rc;
+        if (!P.atab.empty() && (rc = upload(P.atab, D.atab, &D.d_atab))) return rc;
         D.blocks_per_cu = ldpc_blocks_per_cu(P.max_deg, D.irregular, P.N);
         if (P.N > 16200 && ldpc_split_supported(P.max_deg)) {
             // the half-row decoder (ldpc_split_plan.h / ldpc_split_kernel.hip) for the normal frames it takes, and for them the default: 32 768 frames of rate 3/4 x 50 iterations
@@ -109,10 +109,10 @@ int get_ldpc(dvbs2gpu_ctx* ctx, int code_index, LdpcDeviceCode** out) {
             // lane-per-row decoder (the parity tests run both).
             const LdpcSplitPlan SP = build_ldpc_split_plan(P);
             if (SP.ok && (!SP.noprev_shared || ldpc_split_noprev_shared(P.max_deg))) {
-                if ((rc = upload(SP.layers, &D.d_split_layers))) return fail(rc);
+                if ((rc = upload(SP.layers, D.split_layers, &D.d_split_layers))) return rc;
                 std::vector<uint32_t> tab(SP.atab);
                 tab.insert(tab.end(), SP.side.begin(), SP.side.end());
-                if ((rc = upload(tab, &D.d_split_atab))) return fail(rc);
+                if ((rc = upload(tab, D.split_atab, &D.d_split_atab))) return rc;
                 D.split_tab_words = (int)tab.size();
                 D.split_npl = (int)SP.layers.size(); D.split_rec_total = SP.rec_total;
                 D.split_blocks_per_cu = ldpc_split_blocks_per_cu(P.max_deg, P.N);
@@ -124,12 +124,12 @@ int get_ldpc(dvbs2gpu_ctx* ctx, int code_index, LdpcDeviceCode** out) {
             // the context option ldpc_wave = 0 | 1 forces one (development aid / the parity tests run both)
             const LdpcWavePlan W = build_ldpc_wave_plan(P);
             D.wave_lw = W.lw; D.wave_nsteps = W.nsteps; D.wave_nl_min = W.nl_min; D.wave_absent_base = W.absent_base;
-            if ((rc = upload(W.lanec, &D.d_wave_lanec))) return fail(rc);
-            if ((rc = upload(W.steps, &D.d_wave_steps))) return fail(rc);
-            if ((rc = upload(W.layer_end, &D.d_wave_layer_end))) return fail(rc);
+            if ((rc = upload(W.lanec, D.wave_lanec, &D.d_wave_lanec))) return rc;
+            if ((rc = upload(W.steps, D.wave_steps, &D.d_wave_steps))) return rc;
+            if ((rc = upload(W.layer_end, D.wave_layer_end, &D.d_wave_layer_end))) return rc;
             D.use_wave = ctx->ldpc_wave >= 0 ? ctx->ldpc_wave != 0 : ldpc_wave_default(code_index);
         }
-        it = ctx->ldpc.emplace(code_index, D).first;
+        it = ctx->ldpc.emplace(code_index, std::move(D)).first;
     }
     *out = &it->second;
     return 0;
@@ -182,14 +182,14 @@ int get_bch(dvbs2gpu_ctx* ctx, int m, int t, BchDeviceCode** out) {
                 T[512 + x] = (hi < (uint32_t)Q) ? vmul(hi, c) : 0;
             }
         }
-        BchDeviceCode D;
+        BchCode D;
         D.m = m; D.t = t; D.N = N; D.K_full = N - m * t;
         int rc;
-        if ((rc = upload(LOG, &D.d_log))) return rc;
-        if ((rc = upload(EXP, &D.d_exp))) return rc;
-        if ((rc = upload(IMAP, &D.d_imap))) return rc;
-        if ((rc = upload(tab, &D.d_syn_tab))) return rc;
-        it = ctx->bch.emplace(key, D).first;
+        if ((rc = upload(LOG, D.log, &D.d_log))) return rc;
+        if ((rc = upload(EXP, D.exp, &D.d_exp))) return rc;
+        if ((rc = upload(IMAP, D.imap, &D.d_imap))) return rc;
+        if ((rc = upload(tab, D.syn_tab, &D.d_syn_tab))) return rc;
+        it = ctx->bch.emplace(key, std::move(D)).first;
     }
     *out = &it->second;
     return 0;
@@ -207,7 +207,7 @@ int get_prbs(dvbs2gpu_ctx* ctx) {
         sr >>= 1;
         if (b) sr |= 0x4000;
     }
-    return upload(seq, &ctx->d_prbs);
+    return upload(seq, ctx->d_prbs);
 }
 }  // namespace s2
 
@@ -410,35 +410,10 @@ void dvbs2gpu_destroy(dvbs2gpu_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    for (auto& kv : ctx->ldpc) free_ldpc_code(kv.second);
-    for (auto& kv : ctx->bch) {
-        (void)hipFree(kv.second.d_log); (void)hipFree(kv.second.d_exp); (void)hipFree(kv.second.d_imap); (void)hipFree(kv.second.d_syn_tab);
-    }
-    if (ctx->d_prbs) (void)hipFree(ctx->d_prbs);
-    // receive-chain tables
-    if (ctx->d_gardner_bank) (void)hipFree(ctx->d_gardner_bank);
-    if (ctx->pl.sof) (void)hipFree((void*)ctx->pl.sof);
-    if (ctx->pl.plsc) (void)hipFree((void*)ctx->pl.plsc);
-    if (ctx->pl.plsc_code) (void)hipFree((void*)ctx->pl.plsc_code);
-    if (ctx->pl.rn) (void)hipFree((void*)ctx->pl.rn);
-    for (auto& kv : ctx->constel) {
-        if (kv.second.d_bits) (void)hipFree(kv.second.d_bits);
-        if (kv.second.d_bits4) (void)hipFree(kv.second.d_bits4);
-        if (kv.second.d_err) (void)hipFree(kv.second.d_err);
-        if (kv.second.d_pts) (void)hipFree(kv.second.d_pts);
-    }
-    for (auto& kv : ctx->rrc) if (kv.second) (void)hipFree(kv.second);
-    if (ctx->d_fd_bank) (void)hipFree(ctx->d_fd_bank);
-    for (auto& kv : ctx->bandedge) if (kv.second) (void)hipFree(kv.second);
-    if (ctx->d_vcm_mods) (void)hipFree(ctx->d_vcm_mods);
-    if (ctx->d_vcm_cons) (void)hipFree(ctx->d_vcm_cons);
-    ctx->ws_vcm.release();
-    ctx->ws_mix.release();
     for (auto& row : ctx->ev_mix) for (hipEvent_t& e : row) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     if (ctx->ev_ws) (void)hipEventDestroy(ctx->ev_ws);
     for (auto& sp : ctx->timers.pending) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (auto e : ctx->timers.pool) (void)hipEventDestroy(e);
-    ctx->fws.release();
     for (auto& kv : ctx->fe_aux) kv.second.release();
     if (ctx->fe_stream) (void)hipStreamDestroy(ctx->fe_stream);
     if (ctx->fec_stream) (void)hipStreamDestroy(ctx->fec_stream);
@@ -449,12 +424,7 @@ void dvbs2gpu_destroy(dvbs2gpu_ctx* ctx) {
         for (int k = 0; k < 2; ++k) if (ctx->ev_fec_t0[g][k]) (void)hipEventDestroy(ctx->ev_fec_t0[g][k]);
         if (ctx->ev_llr_grp[g]) (void)hipEventDestroy(ctx->ev_llr_grp[g]);
         if (ctx->grp_stream[g]) (void)hipStreamDestroy(ctx->grp_stream[g]);
-        ctx->fws_grp[g].release();
-        ctx->ws_grp[g].release();
-        for (auto& par : ctx->ws_fecbuf[g]) par.release();
     }
-    ctx->ws_rx.release();
-    for (auto& w : ctx->ws_dvbs) w.release();
     delete ctx;
 }
 

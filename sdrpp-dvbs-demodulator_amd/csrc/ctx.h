@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -16,6 +17,8 @@
 #include "kernels.h"
 #include "s2_rx.h"
 #include "scratch_layout.h"
+#include "dev_buf.h"
+#include <type_traits>
 
 namespace s2 {
 
@@ -26,31 +29,26 @@ int fail_hip(hipError_t e, const char* what);
         hipError_t _e = (x);                                  \
         if (_e != hipSuccess) return s2::fail_hip(_e, #x);    \
     } while (0)
+#define RC_TRY(x)                                             \
+    do {                                                      \
+        int _rc = (x);                                        \
+        if (_rc) return _rc;                                  \
+    } while (0)
 
-struct Workspace {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t n) {
-        if (n <= bytes) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        size_t want = n + n / 4;   // grow with slack so alternating sizes do not thrash
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) return fail_hip(e, "hipMalloc(workspace)");
-        bytes = want;
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-};
-
+// the table `v` on the device, held by `own` (an empty table still gets one element's worth, so the pointer is never null)
 template <typename T>
-inline int upload(const std::vector<T>& v, T** dptr) {
-    *dptr = nullptr;
-    size_t n = v.size() * sizeof(T);
-    if (!n) n = sizeof(T);
-    HIP_TRY(hipMalloc((void**)dptr, n));
-    if (!v.empty()) HIP_TRY(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+inline int upload(const std::vector<T>& v, DevBuf<T>& own) {
+    int rc = own.alloc(v.empty() ? 1 : v.size(), false, "hipMalloc(table)");
+    if (rc) return rc;
+    if (!v.empty()) HIP_TRY(hipMemcpy(own.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return 0;
+}
+// ... and `*view`, the raw pointer of a struct that a kernel reads, set to it
+template <typename T, typename U>
+inline int upload(const std::vector<T>& v, DevBuf<T>& own, U** view) {
+    const int rc = upload(v, own);
+    *view = own.get();
+    return rc;
 }
 
 // Per-stage device times (hipEvent pairs on the stream a stage is enqueued on), accumulated until dvbs2gpu_get_stage_times reads them.
@@ -87,7 +85,7 @@ struct StageSpan {
 };
 
 // the FEC stage's scratch buffers: one set per context, and one per configuration group for jobs that run side by side (s2_demod.hip)
-struct FecWs { Workspace msg, hard, syn, misc; void release() { msg.release(); hard.release(); syn.release(); misc.release(); } };
+struct FecWs { Workspace msg, hard, syn, misc; };
 // per-call scratch of the S2 batch flows (s2_demod.hip), one struct per flow.  `deliver`: the destination table of a job's delivery
 struct GroupWs {        // a CCM group (process_group)
     Workspace work,     // stream-work table + first[] + symbol counts + NCO + FIFO cur/fill
@@ -96,24 +94,21 @@ struct GroupWs {        // a CCM group (process_group)
               pll, llr, bb, deliver,
               slot_stats,   // stage pipeline: per-slot frame stats
               quality;      // signal-quality descriptors + records (quality.hip)
-    void release() { for (Workspace* w : {&work, &found, &frames, &pll, &llr, &bb, &deliver, &slot_stats, &quality}) w->release(); }
 };
 struct VcmWs {          // a group of ACM/VCM streams (process_vcm_group)
     Workspace work,     // stream-work table + first[] + counts + FIFO cur/fill + symbol counts + NCO
               found, frames /* frames + stats + destinations + index lists */, pll, llr,
               fec_llr, fec_bb, fec_res,     // synchronous FEC parts: LLRs | BBFRAMEs | results + index lists + destinations
               deliver, quality;
-    void release() { for (Workspace* w : {&work, &found, &frames, &pll, &llr, &fec_llr, &fec_bb, &fec_res, &deliver, &quality}) w->release(); }
 };
 struct MixWs {          // a mixed CCM batch (process_mixed)
     Workspace work,     // stream-work table + per-stream configurations + symbol counts + NCO + FIFO cur/fill
               found, llr_of /* per-frame LLR pointers + slot indices */, pll, slot_stats,
               fec_llr, fec_bb, fec_res,     // synchronous FEC parts, as VcmWs
               deliver, quality;
-    void release() { for (Workspace* w : {&work, &found, &llr_of, &pll, &slot_stats, &fec_llr, &fec_bb, &fec_res, &deliver, &quality}) w->release(); }
 };
 // the buffers of one pipelined FEC job (per slot and parity): LLRs | BBFRAMEs | frame refs + first[] + results (CCM), results + index lists + destinations (ACM/VCM, mixed)
-struct FecJobBufs { Workspace llr, bb, job; void release() { llr.release(); bb.release(); job.release(); } };
+struct FecJobBufs { Workspace llr, bb, job; };
 
 // the argument table of a bank call for n streams (dvbs_capi.hip, bbts.hip): input pointers | output pointers | counts in | bytes out
 struct BankArgs {
@@ -122,12 +117,28 @@ struct BankArgs {
     explicit BankArgs(size_t n) : in(L.add<const uint8_t*>(n)), out(L.add<uint8_t*>(n)), cnt(L.add<int>(n)), ob(L.add<int>(n)) {}
 };
 
+// What a kernel reads is a plain struct of raw pointers, passed by value or copied to the device; the context's caches hold it together
+// with the owners of the tables it points to (a launch takes the plain part: `*C` slices to it).
+static_assert(std::is_trivially_copyable_v<LdpcDeviceCode> && std::is_trivially_copyable_v<BchDeviceCode>, "kernel-visible structs stay plain");
+static_assert(std::is_trivially_copyable_v<S2ConstelDev> && std::is_trivially_copyable_v<S2PlTablesDev>, "kernel-visible structs stay plain");
+struct LdpcCode : LdpcDeviceCode {
+    DevBuf<LdpcLayerDesc> layers;
+    DevBuf<uint32_t> ents, rows, atab, wave_lanec, wave_layer_end, split_atab;
+    DevBuf<uint16_t> wave_steps;
+    DevBuf<LdpcSplitLayer> split_layers;
+};
+struct BchCode : BchDeviceCode { DevBuf<uint16_t> log, exp, imap, syn_tab; };
 struct ConstelTables {          // device tables of one constellation (type, gamma1, gamma2)
     S2ConstelDev dev;
-    int8_t* d_bits = nullptr;
-    uint32_t* d_bits4 = nullptr;
-    float* d_err = nullptr;
-    cf32* d_pts = nullptr;
+    DevBuf<int8_t> bits;
+    DevBuf<uint32_t> bits4;
+    DevBuf<float> err;
+    DevBuf<cf32> pts;
+};
+struct PlTables : S2PlTablesDev {       // PL header tables (s2_demod.hip: get_rx_tables)
+    DevBuf<cf32> sof_own, plsc_own;
+    DevBuf<uint64_t> plsc_code_own;
+    DevBuf<uint8_t> rn_own;
 };
 
 }  // namespace s2
@@ -146,20 +157,20 @@ struct dvbs2gpu_ctx {
     hipEvent_t ev_ws = nullptr;
     hipStream_t ws_stream = nullptr;
     bool ws_used = false;
-    std::map<int, s2::LdpcDeviceCode> ldpc;   // by code_index
-    std::map<int, s2::BchDeviceCode> bch;     // by m*100 + t
-    uint8_t* d_prbs = nullptr;                // BB scrambler sequence, 8100 bytes
+    std::map<int, s2::LdpcCode> ldpc;         // by code_index
+    std::map<int, s2::BchCode> bch;           // by m*100 + t
+    s2::DevBuf<uint8_t> d_prbs;               // BB scrambler sequence, 8100 bytes
     s2::FecWs fws;                            // LDPC message records (+ work counter, sign scratch), hard decisions, BCH syndromes, trial counts
     // receive-chain tables (s2_demod.hip)
-    float* d_gardner_bank = nullptr;
-    s2::S2PlTablesDev pl{};
+    s2::DevBuf<float> d_gardner_bank;
+    s2::PlTables pl{};
     std::map<int, s2::ConstelTables> constel; // by modcod (gammas depend on it)
-    std::map<int, float*> rrc;                // by ntaps*1000 + round(alpha*100) (Ts = 2)
+    std::map<int, s2::DevBuf<float>> rrc;           // by ntaps*1000 + round(alpha*100) (Ts = 2)
     // (ws_rx.slot_stats also holds frontend_prepass's work table -- a pre-passed group is never staged; ws_rx.deliver also collects the jobs left in slots without a group)
     s2::GroupWs ws_rx;
     // ACM/VCM mode (s2_demod.hip): what every PLS code means + the constellations it points to, on the device; per-call scratch
-    s2::S2VcmMod* d_vcm_mods = nullptr;
-    s2::S2ConstelDev* d_vcm_cons = nullptr;
+    s2::DevBuf<s2::S2VcmMod> d_vcm_mods;
+    s2::DevBuf<s2::S2ConstelDev> d_vcm_cons;
     std::vector<s2::S2VcmMod> h_vcm_mods;
     std::vector<s2::FecParams> h_vcm_fec;     // by PLS code
     s2::VcmWs ws_vcm;
@@ -234,8 +245,8 @@ struct dvbs2gpu_ctx {
     int dvbs_agc_stream = 1;                  // option dvbs_agc_stream: the AGC slices of a bank below dvbs_bank_min carriers on a third auxiliary stream (0: on the Viterbi stream)
     int dvbs_fe_slices = 24;                 // option dvbs_fe_slices: time slices of a DVB-S call (dvbs_demod.hip)
     // DVB-S front end (dvbs_demod.hip)
-    float* d_fd_bank = nullptr;               // COMPLEX_FD interpolator bank, 256 x 256
-    std::map<int, s2::cf32*> bandedge;        // FLL band-edge taps [2][ntaps] by ntaps*100000 + round(alpha*1000)*10 + sps
+    s2::DevBuf<float> d_fd_bank;              // COMPLEX_FD interpolator bank, 256 x 256
+    std::map<int, s2::DevBuf<s2::cf32>> bandedge;    // FLL band-edge taps [2][ntaps] by ntaps*100000 + round(alpha*1000)*10 + sps
     s2::Workspace ws_dvbs[4];
 };
 

@@ -9,19 +9,19 @@ struct dvbs2gpu_viterbi {
     int nstreams = 0;
     float thr = 0.15f;
     int max_outsync = 20;
-    DvbsVitState* d_states = nullptr;
-    uint8_t* d_ws = nullptr;
+    DevBuf<DvbsVitState> d_states;
+    DevBuf<uint8_t> d_ws;
 };
 struct dvbs2gpu_forney {
     dvbs2gpu_ctx* ctx = nullptr;
     int nstreams = 0;
-    uint8_t* d_hist = nullptr;
+    DevBuf<uint8_t> d_hist;
 };
 struct dvbs2gpu_ccdec {
     dvbs2gpu_ctx* ctx = nullptr;
     int nstreams = 0, frame_size = 0;
-    int* d_state = nullptr;
-    unsigned long long* d_dec = nullptr;
+    DevBuf<int> d_state;
+    DevBuf<unsigned long long> d_dec;
 };
 
 extern "C" {
@@ -38,20 +38,14 @@ int dvbs2gpu_dvbs_slice(dvbs2gpu_ctx* ctx, const float* d_iq, int nsymbols, int8
 int dvbs2gpu_ccdec_create(dvbs2gpu_ctx* ctx, int nstreams, int frame_size, dvbs2gpu_ccdec** out) {
     if (!ctx || !out || nstreams <= 0 || frame_size < 6 || frame_size > 65536) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    dvbs2gpu_ccdec* h = new dvbs2gpu_ccdec();
+    std::unique_ptr<dvbs2gpu_ccdec> h(new dvbs2gpu_ccdec());
     h->ctx = ctx; h->nstreams = nstreams; h->frame_size = frame_size;
-    hipError_t e = hipMalloc((void**)&h->d_state, sizeof(int) * 2 * nstreams);
-    if (e == hipSuccess) e = hipMemset(h->d_state, 0, sizeof(int) * 2 * nstreams);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_dec, sizeof(unsigned long long) * (size_t)(frame_size + 6) * nstreams);
-    if (e != hipSuccess) { if (h->d_state) (void)hipFree(h->d_state); delete h; return fail_hip(e, "hipMalloc(ccdec)"); }
-    *out = h;
+    RC_TRY(h->d_state.alloc((size_t)2 * nstreams, true, "hipMalloc(ccdec)"));
+    RC_TRY(h->d_dec.alloc((size_t)(frame_size + 6) * nstreams, false, "hipMalloc(ccdec)"));
+    *out = h.release();
     return 0;
 }
-void dvbs2gpu_ccdec_destroy(dvbs2gpu_ccdec* h) {
-    if (!h) return;
-    (void)hipFree(h->d_state); (void)hipFree(h->d_dec);
-    delete h;
-}
+void dvbs2gpu_ccdec_destroy(dvbs2gpu_ccdec* h) { delete h; }
 int dvbs2gpu_ccdec_work_batch(dvbs2gpu_ccdec* h, const uint8_t* d_soft, int64_t stream_stride, int block_stride, int nblocks, uint8_t* d_bits,
                               void* stream) {
     if (!h || nblocks < 0 || block_stride < 0) return DVBS2GPU_ERR_ARG;
@@ -66,15 +60,13 @@ int dvbs2gpu_ccdec_work_batch(dvbs2gpu_ccdec* h, const uint8_t* d_soft, int64_t 
 int dvbs2gpu_viterbi_create(dvbs2gpu_ctx* ctx, int nstreams, float ber_threshold, int max_outsync, dvbs2gpu_viterbi** out) {
     if (!ctx || !out || nstreams <= 0) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    dvbs2gpu_viterbi* h = new dvbs2gpu_viterbi();
+    std::unique_ptr<dvbs2gpu_viterbi> h(new dvbs2gpu_viterbi());
     h->ctx = ctx; h->nstreams = nstreams; h->thr = ber_threshold; h->max_outsync = max_outsync;
-    hipError_t e = hipMalloc((void**)&h->d_states, sizeof(DvbsVitState) * nstreams);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_ws, (size_t)DVBS_VIT_WS_BYTES * nstreams);
-    if (e != hipSuccess) { if (h->d_states) (void)hipFree(h->d_states); delete h; return fail_hip(e, "hipMalloc(viterbi)"); }
-    *out = h;
-    int rc = dvbs2gpu_viterbi_reset(h);
-    if (rc) { dvbs2gpu_viterbi_destroy(h); *out = nullptr; }
-    return rc;
+    RC_TRY(h->d_states.alloc(nstreams, false, "hipMalloc(viterbi)"));
+    RC_TRY(h->d_ws.alloc((size_t)DVBS_VIT_WS_BYTES * nstreams, false, "hipMalloc(viterbi)"));
+    RC_TRY(dvbs2gpu_viterbi_reset(h.get()));
+    *out = h.release();
+    return 0;
 }
 int dvbs2gpu_viterbi_reset(dvbs2gpu_viterbi* h) {
     if (!h) return DVBS2GPU_ERR_ARG;
@@ -86,11 +78,7 @@ int dvbs2gpu_viterbi_reset(dvbs2gpu_viterbi* h) {
     HIP_TRY(hipMemset(h->d_ws, 0, (size_t)DVBS_VIT_WS_BYTES * h->nstreams));
     return 0;
 }
-void dvbs2gpu_viterbi_destroy(dvbs2gpu_viterbi* h) {
-    if (!h) return;
-    (void)hipFree(h->d_states); (void)hipFree(h->d_ws);
-    delete h;
-}
+void dvbs2gpu_viterbi_destroy(dvbs2gpu_viterbi* h) { delete h; }
 int dvbs2gpu_viterbi_work_batch(dvbs2gpu_viterbi* h, const int8_t* d_soft, int nblocks, uint8_t* d_bits, int32_t* d_nbits,
                                 dvbs2gpu_viterbi_stats* d_stats, void* stream) {
     if (!h || nblocks < 0) return DVBS2GPU_ERR_ARG;
@@ -106,19 +94,13 @@ int dvbs2gpu_viterbi_work_batch(dvbs2gpu_viterbi* h, const int8_t* d_soft, int n
 int dvbs2gpu_forney_create(dvbs2gpu_ctx* ctx, int nstreams, dvbs2gpu_forney** out) {
     if (!ctx || !out || nstreams <= 0) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    dvbs2gpu_forney* h = new dvbs2gpu_forney();
+    std::unique_ptr<dvbs2gpu_forney> h(new dvbs2gpu_forney());
     h->ctx = ctx; h->nstreams = nstreams;
-    hipError_t e = hipMalloc((void**)&h->d_hist, (size_t)DVBS_FORNEY_HIST * nstreams);
-    if (e == hipSuccess) e = hipMemset(h->d_hist, 0, (size_t)DVBS_FORNEY_HIST * nstreams);   // FIFOs start zero-filled (dvbs_interleaving.h:27-43)
-    if (e != hipSuccess) { delete h; return fail_hip(e, "hipMalloc(forney)"); }
-    *out = h;
+    RC_TRY(h->d_hist.alloc((size_t)DVBS_FORNEY_HIST * nstreams, true, "hipMalloc(forney)"));   // FIFOs start zero-filled (dvbs_interleaving.h:27-43)
+    *out = h.release();
     return 0;
 }
-void dvbs2gpu_forney_destroy(dvbs2gpu_forney* h) {
-    if (!h) return;
-    (void)hipFree(h->d_hist);
-    delete h;
-}
+void dvbs2gpu_forney_destroy(dvbs2gpu_forney* h) { delete h; }
 int dvbs2gpu_forney_deinterleave_batch(dvbs2gpu_forney* h, const uint8_t* d_in, int nbytes, uint8_t* d_out, void* stream) {
     if (!h || nbytes < 0 || nbytes % 12 != 0) return DVBS2GPU_ERR_ARG;
     if (nbytes == 0) return 0;
@@ -137,21 +119,21 @@ struct dvbs2gpu_dvbs_tail {
     dvbs2gpu_ctx* ctx = nullptr;
     int nstreams = 0, max_bits = 0, max_frames = 0;
     long v_stride = 0, frames_stride = 0;
-    uint8_t* d_hist[2] = {nullptr, nullptr};   // last 13055 bits, double-buffered
+    DevBuf<uint8_t> d_hist[2];                 // last 13055 bits, double-buffered
     int cur = 0;
-    uint8_t* d_v = nullptr;
-    int* d_hit = nullptr;
-    int* d_nframes = nullptr;
-    int* d_errs = nullptr;
-    uint8_t* d_frames = nullptr;
-    uint8_t* d_deint = nullptr;
-    uint8_t* d_forney = nullptr;
-    uint8_t* d_status = nullptr;
-    int* d_rs_err = nullptr;
-    uint8_t* d_gf = nullptr;
-    uint8_t* d_prbs = nullptr;
-    DvbsTailState* d_state = nullptr;
-    void* d_args = nullptr;                    // BankArgs(nstreams): [in ptrs][out ptrs][counts][out bytes]
+    DevBuf<uint8_t> d_v;
+    DevBuf<int> d_hit;
+    DevBuf<int> d_nframes;
+    DevBuf<int> d_errs;
+    DevBuf<uint8_t> d_frames;
+    DevBuf<uint8_t> d_deint;
+    DevBuf<uint8_t> d_forney;
+    DevBuf<uint8_t> d_status;
+    DevBuf<int> d_rs_err;
+    DevBuf<uint8_t> d_gf;
+    DevBuf<uint8_t> d_prbs;
+    DevBuf<DvbsTailState> d_state;
+    DevBuf<uint8_t> d_args;                    // BankArgs(nstreams): [in ptrs][out ptrs][counts][out bytes]
 };
 
 extern "C" {
@@ -159,7 +141,7 @@ extern "C" {
 int dvbs2gpu_dvbs_tail_create(dvbs2gpu_ctx* ctx, int nstreams, int max_bits, dvbs2gpu_dvbs_tail** out) {
     if (!ctx || !out || nstreams <= 0 || max_bits <= 0) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    auto t = new dvbs2gpu_dvbs_tail();
+    std::unique_ptr<dvbs2gpu_dvbs_tail> t(new dvbs2gpu_dvbs_tail());
     t->ctx = ctx; t->nstreams = nstreams; t->max_bits = max_bits;
     t->max_frames = max_bits / (1632 * 8) + 3;
     t->v_stride = ((long)max_bits + 1632 * 8 + 63) & ~63L;
@@ -187,24 +169,27 @@ int dvbs2gpu_dvbs_tail_create(dvbs2gpu_ctx* ctx, int nstreams, int max_bits, dvb
         }
     }
     const size_t n = (size_t)nstreams;
-    hipError_t e = hipSuccess;
-    auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) { e = hipMalloc(p, bytes); if (e == hipSuccess) e = hipMemset(*p, 0, bytes); } };
-    A((void**)&t->d_hist[0], n * 1632 * 8); A((void**)&t->d_hist[1], n * 1632 * 8);
-    A((void**)&t->d_v, n * (size_t)t->v_stride);
-    A((void**)&t->d_hit, n * t->max_frames * sizeof(int)); A((void**)&t->d_nframes, n * sizeof(int)); A((void**)&t->d_errs, n * 2 * sizeof(int));
-    A((void**)&t->d_frames, n * (size_t)t->frames_stride); A((void**)&t->d_deint, n * (size_t)t->frames_stride);
-    A((void**)&t->d_forney, n * DVBS_FORNEY_HIST);
-    A((void**)&t->d_status, n * t->max_frames * 8); A((void**)&t->d_rs_err, n * t->max_frames * 8 * sizeof(int));
-    A((void**)&t->d_gf, 768); A((void**)&t->d_prbs, 32767);
-    A((void**)&t->d_state, n * sizeof(DvbsTailState));
-    A(&t->d_args, BankArgs(n).L.bytes());
-    if (e != hipSuccess) { dvbs2gpu_dvbs_tail_destroy(t); return fail_hip(e, "hipMalloc(dvbs tail)"); }
+    const size_t nf = n * t->max_frames;
+    const char* what = "hipMalloc(dvbs tail)";      // (all of them zero-filled)
+    for (auto& h : t->d_hist) RC_TRY(h.alloc(n * 1632 * 8, true, what));
+    RC_TRY(t->d_v.alloc(n * (size_t)t->v_stride, true, what));
+    RC_TRY(t->d_hit.alloc(nf, true, what));
+    RC_TRY(t->d_nframes.alloc(n, true, what));
+    RC_TRY(t->d_errs.alloc(n * 2, true, what));
+    RC_TRY(t->d_frames.alloc(n * (size_t)t->frames_stride, true, what));
+    RC_TRY(t->d_deint.alloc(n * (size_t)t->frames_stride, true, what));
+    RC_TRY(t->d_forney.alloc(n * DVBS_FORNEY_HIST, true, what));
+    RC_TRY(t->d_status.alloc(nf * 8, true, what));
+    RC_TRY(t->d_rs_err.alloc(nf * 8, true, what));
+    RC_TRY(t->d_gf.alloc(768, true, what));
+    RC_TRY(t->d_prbs.alloc(32767, true, what));
+    RC_TRY(t->d_state.alloc(n, true, what));
+    RC_TRY(t->d_args.alloc(BankArgs(n).L.bytes(), true, what));
     HIP_TRY(hipMemcpy(t->d_gf, gf.data(), 768, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(t->d_prbs, prbs.data(), 32767, hipMemcpyHostToDevice));
-    *out = t;
-    int rc = dvbs2gpu_dvbs_tail_reset(t);
-    if (rc) { dvbs2gpu_dvbs_tail_destroy(t); *out = nullptr; }
-    return rc;
+    RC_TRY(dvbs2gpu_dvbs_tail_reset(t.get()));
+    *out = t.release();
+    return 0;
 }
 int dvbs2gpu_dvbs_tail_reset(dvbs2gpu_dvbs_tail* t) {
     if (!t) return DVBS2GPU_ERR_ARG;
@@ -220,13 +205,7 @@ int dvbs2gpu_dvbs_tail_reset(dvbs2gpu_dvbs_tail* t) {
     t->cur = 0;
     return 0;
 }
-void dvbs2gpu_dvbs_tail_destroy(dvbs2gpu_dvbs_tail* t) {
-    if (!t) return;
-    void* ps[] = {t->d_hist[0], t->d_hist[1], t->d_v, t->d_hit, t->d_nframes, t->d_errs, t->d_frames, t->d_deint, t->d_forney, t->d_status,
-                  t->d_rs_err, t->d_gf, t->d_prbs, t->d_state, t->d_args};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    delete t;
-}
+void dvbs2gpu_dvbs_tail_destroy(dvbs2gpu_dvbs_tail* t) { delete t; }
 int dvbs2gpu_dvbs_tail_process_batch(dvbs2gpu_dvbs_tail* t, const uint8_t* const* d_bits, const int* counts, uint8_t* const* d_ts, int cap,
                                      int* out_bytes, void* stream) {
     if (!t || !d_bits || !counts || !d_ts || !out_bytes || cap < 0) return DVBS2GPU_ERR_ARG;
@@ -297,8 +276,8 @@ int dvbs2gpu_dvbs_tail_rs_stage(dvbs2gpu_dvbs_tail* t, const uint8_t* h_packets,
     HIP_TRY(hipMemcpy(t->d_deint, h_packets, (size_t)npackets * 204, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(t->d_status, 1, (size_t)n * t->max_frames * 8));
     HIP_TRY(hipMemset(t->d_rs_err, 0, (size_t)n * t->max_frames * 8 * sizeof(int)));
-    uint8_t* d_ts = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_ts, (size_t)std::max(cap, 1) * n));
+    DevBuf<uint8_t> d_ts;
+    RC_TRY(d_ts.alloc((size_t)std::max(cap, 1) * n, false, "hipMalloc(dvbs tail rs stage)"));
     const BankArgs a(n);
     uint8_t** d_out = a.out(t->d_args); int* d_ob = a.ob(t->d_args);
     std::vector<uint8_t*> outs(n);
@@ -309,7 +288,6 @@ int dvbs2gpu_dvbs_tail_rs_stage(dvbs2gpu_dvbs_tail* t, const uint8_t* h_packets,
     int nb = 0;
     if (e == hipSuccess) e = hipMemcpy(&nb, d_ob, sizeof(int), hipMemcpyDeviceToHost);
     if (e == hipSuccess && nb > 0) e = hipMemcpy(h_ts, d_ts, (size_t)nb, hipMemcpyDeviceToHost);
-    (void)hipFree(d_ts);
     if (e != hipSuccess) return fail_hip(e, "dvbs tail rs stage");
     return nb;
 }
@@ -320,8 +298,8 @@ int dvbs2gpu_dvbs_depuncture(dvbs2gpu_ctx* ctx, int period, int mode, const uint
     HIP_TRY(hipSetDevice(ctx->device));
     ScratchLayout L;
     const auto l_in = L.add<uint8_t>(size); const auto l_out = L.add<uint8_t>(out_cap); const auto l_st = L.add<int>(5);     // (state[4], output count)
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, L.bytes()));
+    DevBuf<uint8_t> d;
+    RC_TRY(d.alloc(L.bytes(), false, "hipMalloc(dvbs depuncture stage)"));
     uint8_t *d_in = l_in(d), *d_out = l_out(d);
     int* d_st = l_st(d);
     int n = 0;
@@ -332,7 +310,6 @@ int dvbs2gpu_dvbs_depuncture(dvbs2gpu_ctx* ctx, int period, int mode, const uint
     if (e == hipSuccess) e = hipMemcpy(h_out, d_out, out_cap, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(h_state4, d_st, 4 * sizeof(int), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(&n, d_st + 4, sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail_hip(e, "dvbs depuncture stage");
     return n;
 }

@@ -15,22 +15,22 @@ struct dvbs2gpu_dvbs_demod {
     DvbsLoopCoefs co{};
     int nstreams = 0, max_samples = 0, max_blocks = 0;
     size_t sym_cap = 0, soft_cap = 0;
-    DvbsStreamState* d_state = nullptr;
-    cf32* d_buf_a = nullptr;        // [nstreams][max_samples]
-    cf32* d_buf_b = nullptr;
-    cf32* d_sym = nullptr;          // [nstreams][sym_cap]
-    int8_t* d_soft = nullptr;       // [nstreams][soft_cap]
-    cf32* d_in = nullptr;           // staging for the host entry point (stream 0)
-    uint8_t* d_out = nullptr;
-    uint8_t* d_ts = nullptr;        // TS staging of dvbs2gpu_dvbs_process_ts
+    DevBuf<DvbsStreamState> d_state;
+    DevBuf<cf32> d_buf_a;           // [nstreams][max_samples]
+    DevBuf<cf32> d_buf_b;
+    DevBuf<cf32> d_sym;             // [nstreams][sym_cap]
+    DevBuf<int8_t> d_soft;          // [nstreams][soft_cap]
+    DevBuf<cf32> d_in;              // staging for the host entry point (stream 0)
+    DevBuf<uint8_t> d_out;
+    DevBuf<uint8_t> d_ts;           // TS staging of dvbs2gpu_dvbs_process_ts
     size_t ts_cap = 0;
-    DvbsVitState* d_vstate = nullptr;
-    uint8_t* d_vws = nullptr;
-    cf32* d_bandedge = nullptr;
-    float* d_rrc = nullptr;
+    DevBuf<DvbsVitState> d_vstate;
+    DevBuf<uint8_t> d_vws;
+    DevBuf<cf32> d_bandedge;
+    float* d_rrc = nullptr;         // the context's table (get_rrc)
     std::vector<DvbsStreamState> init_state;
     int quality = 0;                // dvbs2gpu_dvbs_demod_set_quality
-    DvbsQuality* d_qual = nullptr;  // [nstreams], allocated on first use
+    DevBuf<DvbsQuality> d_qual;     // [nstreams], allocated on first use
     std::vector<DvbsQuality> qual;  // of the last call (empty: it ran with quality off)
 };
 
@@ -105,7 +105,7 @@ int dvbs2gpu_dvbs_demod_create(dvbs2gpu_ctx* ctx, const dvbs2gpu_dvbs_cfg* cfg, 
         }
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    auto d = new dvbs2gpu_dvbs_demod();
+    std::unique_ptr<dvbs2gpu_dvbs_demod> d(new dvbs2gpu_dvbs_demod());
     d->ctx = ctx; d->cfg = *cfg; d->nstreams = nstreams; d->max_samples = max_samples;
     d->sym_cap = (size_t)((double)max_samples / ((cfg->samplerate / cfg->symbolrate) * (1.0 - (double)cfg->omega_rel_limit))) + 130;
     d->soft_cap = (size_t)2 * d->sym_cap + 2 * DVBS_SOFT_BLOCK + 128;
@@ -126,24 +126,23 @@ int dvbs2gpu_dvbs_demod_create(dvbs2gpu_ctx* ctx, const dvbs2gpu_dvbs_cfg* cfg, 
     memset(&s0, 0, sizeof(s0));
     s0.agc_gain = 1.0f; s0.fd_freq = omega;
     d->init_state.assign(nstreams, s0);
-    int rc = 0;
-    auto fail = [&](int code) { dvbs2gpu_dvbs_demod_destroy(d); return code; };
     {
         std::lock_guard<std::mutex> l(ctx->mtx);
-        if (!ctx->d_fd_bank && (rc = upload(make_polyphase_bank(FD_PHASES, FD_TAPS), &ctx->d_fd_bank))) return fail(rc);
+        if (!ctx->d_fd_bank) RC_TRY(upload(make_polyphase_bank(FD_PHASES, FD_TAPS), ctx->d_fd_bank));
     }
-    if ((rc = upload(make_bandedge(*cfg), &d->d_bandedge))) return fail(rc);
-    if ((rc = get_rrc(ctx, cfg->rrc_taps, cfg->rrc_alpha, cfg->samplerate / cfg->symbolrate, &d->d_rrc))) return fail(rc);
-    hipError_t e = hipMalloc((void**)&d->d_state, sizeof(DvbsStreamState) * nstreams);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->d_buf_a, sizeof(cf32) * (size_t)max_samples * nstreams);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->d_buf_b, sizeof(cf32) * (size_t)max_samples * nstreams);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->d_sym, sizeof(cf32) * d->sym_cap * nstreams);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->d_soft, d->soft_cap * nstreams);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->d_vstate, sizeof(DvbsVitState) * nstreams);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->d_vws, (size_t)DVBS_VIT_WS_BYTES * nstreams);
-    if (e != hipSuccess) { fail_hip(e, "hipMalloc(dvbs demod)"); return fail(DVBS2GPU_ERR_HIP); }
-    if ((rc = dvbs2gpu_dvbs_demod_reset(d))) return fail(rc);
-    *out = d;
+    RC_TRY(upload(make_bandedge(*cfg), d->d_bandedge));
+    RC_TRY(get_rrc(ctx, cfg->rrc_taps, cfg->rrc_alpha, cfg->samplerate / cfg->symbolrate, &d->d_rrc));
+    const char* what = "hipMalloc(dvbs demod)";
+    const size_t n = (size_t)nstreams;
+    RC_TRY(d->d_state.alloc(n, false, what));
+    RC_TRY(d->d_buf_a.alloc((size_t)max_samples * n, false, what));
+    RC_TRY(d->d_buf_b.alloc((size_t)max_samples * n, false, what));
+    RC_TRY(d->d_sym.alloc(d->sym_cap * n, false, what));
+    RC_TRY(d->d_soft.alloc(d->soft_cap * n, false, what));
+    RC_TRY(d->d_vstate.alloc(n, false, what));
+    RC_TRY(d->d_vws.alloc((size_t)DVBS_VIT_WS_BYTES * n, false, what));
+    RC_TRY(dvbs2gpu_dvbs_demod_reset(d.get()));
+    *out = d.release();
     return 0;
 }
 
@@ -154,13 +153,7 @@ int dvbs2gpu_dvbs_demod_reset(dvbs2gpu_dvbs_demod* d) {
     return vit_reset(d);
 }
 
-void dvbs2gpu_dvbs_demod_destroy(dvbs2gpu_dvbs_demod* d) {
-    if (!d) return;
-    (void)hipFree(d->d_state); (void)hipFree(d->d_buf_a); (void)hipFree(d->d_buf_b); (void)hipFree(d->d_sym); (void)hipFree(d->d_soft);
-    (void)hipFree(d->d_in); (void)hipFree(d->d_out); (void)hipFree(d->d_ts); (void)hipFree(d->d_vstate); (void)hipFree(d->d_vws); (void)hipFree(d->d_bandedge);
-    (void)hipFree(d->d_qual);
-    delete d;
-}
+void dvbs2gpu_dvbs_demod_destroy(dvbs2gpu_dvbs_demod* d) { delete d; }
 
 
 int dvbs2gpu_dvbs_demod_process_batch(dvbs2gpu_dvbs_demod* d, const float* const* d_iq, const int* counts, uint8_t* const* d_bits, int cap,
@@ -252,7 +245,7 @@ int dvbs2gpu_dvbs_demod_process_batch(dvbs2gpu_dvbs_demod* d, const float* const
     // signal quality over the call's Costas output (quality.hip): one launch for the bank, behind the last Costas slice
     d->qual.clear();
     if (d->quality) {
-        if (!d->d_qual) HIP_TRY(hipMalloc((void**)&d->d_qual, sizeof(DvbsQuality) * n));
+        if (!d->d_qual) RC_TRY(d->d_qual.alloc(n, false, "hipMalloc(dvbs demod quality)"));
         d->qual.resize(n);
         HIP_TRY(dvbs_quality_launch(d_work, n, d->d_qual, st));
         HIP_TRY(hipMemcpyAsync(d->qual.data(), d->d_qual, sizeof(DvbsQuality) * n, hipMemcpyDeviceToHost, st));
@@ -266,11 +259,11 @@ int dvbs2gpu_dvbs_demod_process(dvbs2gpu_dvbs_demod* d, int count, const float* 
     if (!d || d->nstreams != 1 || count < 0 || cap < 0 || (count > 0 && !h_iq) || (cap > 0 && !h_bits)) return DVBS2GPU_ERR_ARG;
     if (count > d->max_samples) { last_error() = "count exceeds max_samples"; return DVBS2GPU_ERR_ARG; }
     HIP_TRY(hipSetDevice(d->ctx->device));
-    if (!d->d_in) HIP_TRY(hipMalloc((void**)&d->d_in, sizeof(cf32) * (size_t)d->max_samples));
+    if (!d->d_in) RC_TRY(d->d_in.alloc((size_t)d->max_samples, false, "hipMalloc(dvbs demod staging)"));
     const size_t ocap = (size_t)d->max_blocks * DVBS_SOFT_BLOCK;
-    if (!d->d_out) HIP_TRY(hipMalloc((void**)&d->d_out, ocap));
+    if (!d->d_out) RC_TRY(d->d_out.alloc(ocap, false, "hipMalloc(dvbs demod staging)"));
     if (count) HIP_TRY(hipMemcpy(d->d_in, h_iq, sizeof(cf32) * (size_t)count, hipMemcpyHostToDevice));
-    const float* pi = (const float*)d->d_in;
+    const float* pi = (const float*)d->d_in.get();
     uint8_t* po = d->d_out;
     int nb = 0;
     const int c2 = (int)std::min<size_t>((size_t)cap, ocap);
@@ -285,15 +278,15 @@ int dvbs2gpu_dvbs_process_ts(dvbs2gpu_dvbs_demod* d, dvbs2gpu_dvbs_tail* t, int 
     if (!d || !t || d->nstreams != 1 || count < 0 || cap < 0 || (count > 0 && !h_iq) || (cap > 0 && !h_ts)) return DVBS2GPU_ERR_ARG;
     if (count > d->max_samples) { last_error() = "count exceeds max_samples"; return DVBS2GPU_ERR_ARG; }
     HIP_TRY(hipSetDevice(d->ctx->device));
-    if (!d->d_in) HIP_TRY(hipMalloc((void**)&d->d_in, sizeof(cf32) * (size_t)d->max_samples));
+    if (!d->d_in) RC_TRY(d->d_in.alloc((size_t)d->max_samples, false, "hipMalloc(dvbs demod staging)"));
     const size_t ocap = (size_t)d->max_blocks * DVBS_SOFT_BLOCK;
-    if (!d->d_out) HIP_TRY(hipMalloc((void**)&d->d_out, ocap));
+    if (!d->d_out) RC_TRY(d->d_out.alloc(ocap, false, "hipMalloc(dvbs demod staging)"));
     if (!d->d_ts) {
         d->ts_cap = (ocap / 13056 + 2) * 8 * 188;                 // a deframer frame (8 packets) per 13056 bits, plus the carried ones
-        HIP_TRY(hipMalloc((void**)&d->d_ts, d->ts_cap));
+        RC_TRY(d->d_ts.alloc(d->ts_cap, false, "hipMalloc(dvbs demod staging)"));
     }
     if (count) HIP_TRY(hipMemcpy(d->d_in, h_iq, sizeof(cf32) * (size_t)count, hipMemcpyHostToDevice));
-    const float* pi = (const float*)d->d_in;
+    const float* pi = (const float*)d->d_in.get();
     uint8_t* po = d->d_out;
     int nb = 0;
     int rc = dvbs2gpu_dvbs_demod_process_batch(d, &pi, &count, &po, (int)ocap, &nb);

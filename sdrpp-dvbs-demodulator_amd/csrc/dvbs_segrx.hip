@@ -23,15 +23,16 @@ struct dvbs2gpu_dvbs_segrx {
     dvbs2gpu_dvbs_demod* bank = nullptr;
     int nseg = 0;
     long own_s = 0, warm_s = 0, tail_s = 0, seg_cap = 0, hist_cap = 0, bits_cap = 0;   // samples / bits
-    float* d_hist = nullptr;
-    float* d_hist2 = nullptr;
-    float* d_seg0 = nullptr;
-    uint8_t* d_bits = nullptr;          // [nseg][bits_cap]
+    DevBuf<float> d_hist;
+    DevBuf<float> d_hist2;
+    DevBuf<float> d_seg0;
+    DevBuf<uint8_t> d_bits;             // [nseg][bits_cap]
     long hist_fill = 0;
     std::vector<uint8_t> tail;          // the last bits handed out (at most TAILWIN), in the polarity they were handed out
     bool first_call = true;
     int last_used = 0, last_matched = 0, last_unmatched = 0;
     long long last_bits = 0;
+    ~dvbs2gpu_dvbs_segrx() { if (bank) dvbs2gpu_dvbs_demod_destroy(bank); }
 };
 
 namespace {
@@ -72,13 +73,7 @@ __global__ void dvbs_segrx_copy_kernel(uint8_t* __restrict__ dst, const uint8_t*
 
 extern "C" {
 
-void dvbs2gpu_dvbs_segrx_destroy(dvbs2gpu_dvbs_segrx* r) {
-    if (!r) return;
-    if (r->bank) dvbs2gpu_dvbs_demod_destroy(r->bank);
-    void* ps[] = {r->d_hist, r->d_hist2, r->d_seg0, r->d_bits};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    delete r;
-}
+void dvbs2gpu_dvbs_segrx_destroy(dvbs2gpu_dvbs_segrx* r) { delete r; }
 
 int dvbs2gpu_dvbs_segrx_create(dvbs2gpu_ctx* ctx, const dvbs2gpu_dvbs_cfg* cfg, int nsegments, int own_symbols, int warm_symbols, dvbs2gpu_dvbs_segrx** out) {
     if (!ctx || !cfg || !out || nsegments < 1 || warm_symbols < 8192 || own_symbols < warm_symbols) {
@@ -86,7 +81,7 @@ int dvbs2gpu_dvbs_segrx_create(dvbs2gpu_ctx* ctx, const dvbs2gpu_dvbs_cfg* cfg, 
         return DVBS2GPU_ERR_ARG;
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    auto r = new dvbs2gpu_dvbs_segrx();
+    std::unique_ptr<dvbs2gpu_dvbs_segrx> r(new dvbs2gpu_dvbs_segrx());
     r->ctx = ctx; r->nseg = nsegments;
     r->own_s = 2L * own_symbols; r->warm_s = 2L * warm_symbols;
     r->tail_s = 2L * std::max(warm_symbols / 2, 12288);        // a segment runs on into its successor's part (the Viterbi hands out whole 4096-symbol blocks only)
@@ -94,18 +89,16 @@ int dvbs2gpu_dvbs_segrx_create(dvbs2gpu_ctx* ctx, const dvbs2gpu_dvbs_cfg* cfg, 
     r->seg_cap = r->hist_cap + r->own_s + r->tail_s + 64;
     r->bits_cap = r->seg_cap + 4 * 8192;                        // at most 1.75 bits per symbol = 0.875 per sample
     if (r->bits_cap > 0x3fffffffL) {                             // per-segment counts are ints in the bank's entry
-        delete r;
         g_err = "DVB-S segment receiver: a segment of this many symbols does not fit the bank's int counts";
         return DVBS2GPU_ERR_ARG;
     }
-    int rc = dvbs2gpu_dvbs_demod_create(ctx, cfg, nsegments, (int)r->seg_cap, &r->bank);
-    if (rc) { r->bank = nullptr; dvbs2gpu_dvbs_segrx_destroy(r); return rc; }
-    hipError_t e = hipMalloc((void**)&r->d_hist, sizeof(float) * 2 * r->hist_cap);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->d_hist2, sizeof(float) * 2 * r->hist_cap);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->d_seg0, sizeof(float) * 2 * r->seg_cap);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->d_bits, (size_t)r->bits_cap * nsegments);
-    if (e != hipSuccess) { dvbs2gpu_dvbs_segrx_destroy(r); return fail_hip(e, "hipMalloc(DVB-S segment receiver)"); }
-    *out = r;
+    RC_TRY(dvbs2gpu_dvbs_demod_create(ctx, cfg, nsegments, (int)r->seg_cap, &r->bank));    // (a failed create leaves the bank null)
+    const char* what = "hipMalloc(DVB-S segment receiver)";
+    RC_TRY(r->d_hist.alloc(2 * r->hist_cap, false, what));
+    RC_TRY(r->d_hist2.alloc(2 * r->hist_cap, false, what));
+    RC_TRY(r->d_seg0.alloc(2 * r->seg_cap, false, what));
+    RC_TRY(r->d_bits.alloc((size_t)r->bits_cap * nsegments, false, what));
+    *out = r.release();
     return 0;
 }
 

@@ -86,8 +86,8 @@ static std::vector<std::vector<int>> place(const int32_t* modcod, const double* 
 struct Unit {                 // one transponder on its member
     int table_index = -1;
     dvbs2gpu_demod* h = nullptr;
-    float* d_iq = nullptr;    // [max_samples] complex64
-    uint8_t* d_out = nullptr; // [out_cap]
+    DevBuf<float> d_iq;       // [max_samples] complex64
+    DevBuf<uint8_t> d_out;    // [out_cap]
     int max_samples = 0;
 };
 
@@ -170,9 +170,8 @@ static void release_units(Member& M) {
     (void)hipSetDevice(M.device);
     for (Unit& U : M.units) {
         if (U.h) dvbs2gpu_demod_destroy(U.h);
-        (void)hipFree(U.d_iq); (void)hipFree(U.d_out);
     }
-    M.units.clear();
+    M.units.clear();        // (the units' buffers go with them)
 }
 
 }  // namespace
@@ -261,9 +260,9 @@ int dvbs2gpu_fleet_assign(dvbs2gpu_fleet* f, const dvbs2gpu_fleet_entry* table, 
                 Unit U;
                 U.table_index = i; U.max_samples = table[i].max_samples;
                 int rc = dvbs2gpu_demod_create(M.ctx, &table[i].cfg, table[i].max_samples, &U.h);
-                if (rc == 0 && hipMalloc((void**)&U.d_iq, sizeof(float) * 2 * (size_t)std::max(table[i].max_samples, 1)) != hipSuccess) rc = fail_hip(hipGetLastError(), "hipMalloc(fleet samples)");
-                if (rc == 0 && hipMalloc((void**)&U.d_out, (size_t)std::max(out_cap, 1)) != hipSuccess) rc = fail_hip(hipGetLastError(), "hipMalloc(fleet output)");
-                M.units.push_back(U);          // (kept even on failure: release_units gives back what was made)
+                if (rc == 0) rc = U.d_iq.alloc(2 * (size_t)std::max(table[i].max_samples, 1), false, "hipMalloc(fleet samples)");
+                if (rc == 0) rc = U.d_out.alloc((size_t)std::max(out_cap, 1), false, "hipMalloc(fleet output)");
+                M.units.push_back(std::move(U));         // (kept even on failure: release_units gives back what was made)
                 if (rc != 0) {
                     const std::string msg = last_error();
                     for (auto& P : f->members) release_units(*P);

@@ -222,13 +222,13 @@ struct dvbs2gpu_pcr {
     std::vector<PcrCall> h_call;
     std::vector<char> h_args;
     // device banks
-    int32_t* d_watch = nullptr;
-    PcrRate* d_rate = nullptr;
-    PcrState* d_state = nullptr;
-    int64_t* d_pos = nullptr;
-    PcrRow* d_rows = nullptr;                      // nstreams x max_rows
-    PcrCall* d_call = nullptr;
-    void* d_args = nullptr;                        // TsBankArgs(nstreams)
+    DevBuf<int32_t> d_watch;
+    DevBuf<PcrRate> d_rate;
+    DevBuf<PcrState> d_state;
+    DevBuf<int64_t> d_pos;
+    DevBuf<PcrRow> d_rows;                         // nstreams x max_rows
+    DevBuf<PcrCall> d_call;
+    DevBuf<uint8_t> d_args;                        // TsBankArgs(nstreams)
     TsHostStage stage;                             // of the host-buffer entry point
     // host-only banks
     std::vector<PcrHostStream> host;
@@ -263,8 +263,8 @@ static bool pcr_create_args_ok(int nstreams, int max_packets, int max_rows, dvbs
     if (max_packets > PCR_MAX_PACKETS) { g_err = "PCR bank: max_packets is at most 4096 per stream and call"; return false; }
     return true;
 }
-static dvbs2gpu_pcr* pcr_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows) {
-    auto b = new dvbs2gpu_pcr();
+static std::unique_ptr<dvbs2gpu_pcr> pcr_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows) {
+    std::unique_ptr<dvbs2gpu_pcr> b(new dvbs2gpu_pcr());
     b->ctx = ctx; b->nstreams = nstreams; b->max_packets = max_packets; b->max_rows = max_rows;
     b->watch.assign((size_t)nstreams * PCR_SLOTS, -1);
     b->rate.assign(nstreams, PcrRate{0, PCR_DEFAULT_LIMIT_Q6, 0});
@@ -278,39 +278,33 @@ static dvbs2gpu_pcr* pcr_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, i
 
 extern "C" {
 
-void dvbs2gpu_pcr_destroy(dvbs2gpu_pcr* b) {
-    if (!b) return;
-    void* ps[] = {b->d_watch, b->d_rate, b->d_state, b->d_pos, b->d_rows, b->d_call, b->d_args};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    delete b;
-}
+void dvbs2gpu_pcr_destroy(dvbs2gpu_pcr* b) { delete b; }
 
 int dvbs2gpu_pcr_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_pcr** out) {
     if (!ctx || !pcr_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    dvbs2gpu_pcr* b = pcr_new(ctx, nstreams, max_packets, max_rows);
+    auto b = pcr_new(ctx, nstreams, max_packets, max_rows);
     const size_t n = (size_t)nstreams, ns = n * PCR_SLOTS;
-    hipError_t e = hipSuccess;                         // (zero-filled: the slots' states and the positions; the kernel writes rows and call records before they are read)
-    bbts_alloc(e, &b->d_watch, ns * sizeof(int32_t), false);
-    if (e == hipSuccess) e = hipMemcpy(b->d_watch, b->watch.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice);
-    bbts_alloc(e, &b->d_rate, n * sizeof(PcrRate), false);
-    if (e == hipSuccess) e = hipMemcpy(b->d_rate, b->rate.data(), n * sizeof(PcrRate), hipMemcpyHostToDevice);
-    bbts_alloc(e, &b->d_state, ns * sizeof(PcrState));
-    bbts_alloc(e, &b->d_pos, n * sizeof(int64_t));
-    bbts_alloc(e, &b->d_rows, n * max_rows * sizeof(PcrRow), false);
-    bbts_alloc(e, &b->d_call, n * sizeof(PcrCall), false);
-    bbts_alloc(e, &b->d_args, TsBankArgs(n).L.bytes(), false);
-    if (e != hipSuccess) { dvbs2gpu_pcr_destroy(b); return fail_hip(e, "hipMalloc(pcr)"); }
+    const char* what = "hipMalloc(pcr)";               // (zero-filled: the slots' states and the positions; the kernel writes rows and call records before they are read)
+    RC_TRY(b->d_watch.alloc(ns, false, what));
+    HIP_TRY(hipMemcpy(b->d_watch, b->watch.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice));
+    RC_TRY(b->d_rate.alloc(n, false, what));
+    HIP_TRY(hipMemcpy(b->d_rate, b->rate.data(), n * sizeof(PcrRate), hipMemcpyHostToDevice));
+    RC_TRY(b->d_state.alloc(ns, true, what));
+    RC_TRY(b->d_pos.alloc(n, true, what));
+    RC_TRY(b->d_rows.alloc(n * max_rows, false, what));
+    RC_TRY(b->d_call.alloc(n, false, what));
+    RC_TRY(b->d_args.alloc(TsBankArgs(n).L.bytes(), false, what));
     b->h_args.resize(TsBankArgs(n).L.bytes());
-    *out = b;
+    *out = b.release();
     return 0;
 }
 
 int dvbs2gpu_pcr_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_pcr** out) {
     if (!pcr_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
-    dvbs2gpu_pcr* b = pcr_new(nullptr, nstreams, max_packets, max_rows);
+    auto b = pcr_new(nullptr, nstreams, max_packets, max_rows);
     b->host.resize(nstreams);
-    *out = b;
+    *out = b.release();
     return 0;
 }
 

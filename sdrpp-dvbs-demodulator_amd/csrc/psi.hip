@@ -451,16 +451,16 @@ struct dvbs2gpu_psi {
     std::vector<PsiCall> h_call;
     std::vector<char> h_args;
     // device banks
-    PsiWatch* d_watch = nullptr;
-    int* d_deliver = nullptr;
-    PsiDevSlot *d_state = nullptr, *d_newst = nullptr;
-    uint8_t *d_bufs = nullptr, *d_views = nullptr; // nstreams x 16 x 4096 each
-    unsigned* d_wa = nullptr;                      // nstreams x max_packets: the watched packets of the last call
-    uint16_t* d_wb = nullptr;
-    PsiRec *d_recs = nullptr, *d_opens = nullptr;
-    PsiRow* d_rows = nullptr;                      // nstreams x max_sections
-    PsiCall* d_call = nullptr;
-    void* d_args = nullptr;                        // TsBankArgs(nstreams)
+    DevBuf<PsiWatch> d_watch;
+    DevBuf<int> d_deliver;
+    DevBuf<PsiDevSlot> d_state, d_newst;
+    DevBuf<uint8_t> d_bufs, d_views;               // nstreams x 16 x 4096 each
+    DevBuf<unsigned> d_wa;                         // nstreams x max_packets: the watched packets of the last call
+    DevBuf<uint16_t> d_wb;
+    DevBuf<PsiRec> d_recs, d_opens;
+    DevBuf<PsiRow> d_rows;                         // nstreams x max_sections
+    DevBuf<PsiCall> d_call;
+    DevBuf<uint8_t> d_args;                        // TsBankArgs(nstreams)
     TsHostStage stage;                             // of the host-buffer entry point
     // host-only banks
     std::vector<PsiHostStream> host;
@@ -480,8 +480,8 @@ static bool psi_create_args_ok(int nstreams, int max_packets, int max_sections, 
     if (max_packets > PSI_MAX_PACKETS) { g_err = "PSI bank: max_packets is at most 4096 per stream and call"; return false; }
     return true;
 }
-static dvbs2gpu_psi* psi_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_sections) {
-    auto b = new dvbs2gpu_psi();
+static std::unique_ptr<dvbs2gpu_psi> psi_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_sections) {
+    std::unique_ptr<dvbs2gpu_psi> b(new dvbs2gpu_psi());
     b->ctx = ctx; b->nstreams = nstreams; b->max_packets = max_packets; b->max_sections = max_sections;
     b->watch.assign((size_t)nstreams * PSI_SLOTS, PsiWatch{-1, -1});
     for (int i = 0; i < nstreams; ++i) b->watch[(size_t)i * PSI_SLOTS] = {0, 0};
@@ -498,46 +498,39 @@ static const std::vector<uint8_t>& psi_view_of(dvbs2gpu_psi* b, int stream, int 
 
 extern "C" {
 
-void dvbs2gpu_psi_destroy(dvbs2gpu_psi* b) {
-    if (!b) return;
-    void* ps[] = {b->d_watch, b->d_deliver, b->d_state, b->d_newst, b->d_bufs, b->d_views, b->d_wa, b->d_wb, b->d_recs, b->d_opens, b->d_rows, b->d_call,
-                  b->d_args};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    delete b;
-}
+void dvbs2gpu_psi_destroy(dvbs2gpu_psi* b) { delete b; }
 
 int dvbs2gpu_psi_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_sections, dvbs2gpu_psi** out) {
     if (!ctx || !psi_create_args_ok(nstreams, max_packets, max_sections, out)) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    dvbs2gpu_psi* b = psi_new(ctx, nstreams, max_packets, max_sections);
+    auto b = psi_new(ctx, nstreams, max_packets, max_sections);
     b->view.resize((size_t)nstreams * PSI_SLOTS);
     const size_t n = (size_t)nstreams, ns = n * PSI_SLOTS;
-    hipError_t e = hipSuccess;                         // (zero-filled: the delivery modes and the slots' states; the kernels write the rest before it is read)
-    bbts_alloc(e, &b->d_watch, ns * sizeof(PsiWatch), false);
-    if (e == hipSuccess) e = hipMemcpy(b->d_watch, b->watch.data(), ns * sizeof(PsiWatch), hipMemcpyHostToDevice);
-    bbts_alloc(e, &b->d_deliver, n * sizeof(int));
-    bbts_alloc(e, &b->d_state, ns * sizeof(PsiDevSlot));
-    bbts_alloc(e, &b->d_newst, ns * sizeof(PsiDevSlot), false);
-    bbts_alloc(e, &b->d_bufs, ns * PSI_BUF, false);
-    bbts_alloc(e, &b->d_views, ns * PSI_BUF, false);
-    bbts_alloc(e, &b->d_wa, n * max_packets * sizeof(unsigned), false);
-    bbts_alloc(e, &b->d_wb, n * max_packets * sizeof(uint16_t), false);
-    bbts_alloc(e, &b->d_recs, n * max_sections * sizeof(PsiRec), false);
-    bbts_alloc(e, &b->d_opens, ns * sizeof(PsiRec), false);
-    bbts_alloc(e, &b->d_rows, n * max_sections * sizeof(PsiRow), false);
-    bbts_alloc(e, &b->d_call, n * sizeof(PsiCall), false);
-    bbts_alloc(e, &b->d_args, TsBankArgs(n).L.bytes(), false);
-    if (e != hipSuccess) { dvbs2gpu_psi_destroy(b); return fail_hip(e, "hipMalloc(psi)"); }
+    const char* what = "hipMalloc(psi)";               // (zero-filled: the delivery modes and the slots' states; the kernels write the rest before it is read)
+    RC_TRY(b->d_watch.alloc(ns, false, what));
+    HIP_TRY(hipMemcpy(b->d_watch, b->watch.data(), ns * sizeof(PsiWatch), hipMemcpyHostToDevice));
+    RC_TRY(b->d_deliver.alloc(n, true, what));
+    RC_TRY(b->d_state.alloc(ns, true, what));
+    RC_TRY(b->d_newst.alloc(ns, false, what));
+    RC_TRY(b->d_bufs.alloc(ns * PSI_BUF, false, what));
+    RC_TRY(b->d_views.alloc(ns * PSI_BUF, false, what));
+    RC_TRY(b->d_wa.alloc(n * max_packets, false, what));
+    RC_TRY(b->d_wb.alloc(n * max_packets, false, what));
+    RC_TRY(b->d_recs.alloc(n * max_sections, false, what));
+    RC_TRY(b->d_opens.alloc(ns, false, what));
+    RC_TRY(b->d_rows.alloc(n * max_sections, false, what));
+    RC_TRY(b->d_call.alloc(n, false, what));
+    RC_TRY(b->d_args.alloc(TsBankArgs(n).L.bytes(), false, what));
     b->h_args.resize(TsBankArgs(n).L.bytes());
-    *out = b;
+    *out = b.release();
     return 0;
 }
 
 int dvbs2gpu_psi_create_host(int nstreams, int max_packets, int max_sections, dvbs2gpu_psi** out) {
     if (!psi_create_args_ok(nstreams, max_packets, max_sections, out)) return DVBS2GPU_ERR_ARG;
-    dvbs2gpu_psi* b = psi_new(nullptr, nstreams, max_packets, max_sections);
+    auto b = psi_new(nullptr, nstreams, max_packets, max_sections);
     b->host.resize(nstreams);
-    *out = b;
+    *out = b.release();
     return 0;
 }
 

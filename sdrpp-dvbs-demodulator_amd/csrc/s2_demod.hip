@@ -180,14 +180,12 @@ int get_rx_tables(dvbs2gpu_ctx* ctx) {
     uint32_t stx = 0x00001, sty = 0x3ffff;
     for (int i = 0; i < 131072; ++i) { rn[i] = (uint8_t)((stx ^ sty) & 1); stx = lfsr_x(stx); sty = lfsr_y(sty); }
     for (int i = 0; i < 131072; ++i) { rn[i] |= (uint8_t)(((stx ^ sty) & 1) << 1); stx = lfsr_x(stx); sty = lfsr_y(sty); }
-    cf32 *d_sof = nullptr, *d_plsc = nullptr; uint64_t* d_codes = nullptr; uint8_t* d_rn = nullptr; float* d_bank = nullptr;
-    if ((rc = upload(sof, &d_sof)) || (rc = upload(plsc, &d_plsc)) || (rc = upload(codes, &d_codes)) || (rc = upload(rn, &d_rn)) ||
-        (rc = upload(make_gardner_bank(), &d_bank))) {
-        (void)hipFree(d_sof); (void)hipFree(d_plsc); (void)hipFree(d_codes); (void)hipFree(d_rn); (void)hipFree(d_bank);
-        return rc;
-    }
-    ctx->pl.sof = d_sof; ctx->pl.plsc = d_plsc; ctx->pl.plsc_code = d_codes; ctx->pl.rn = d_rn;
-    ctx->d_gardner_bank = d_bank;
+    PlTables T{};       // (built aside and moved in whole: a failed upload leaves the context without tables and without their memory)
+    DevBuf<float> bank;
+    if ((rc = upload(sof, T.sof_own, &T.sof)) || (rc = upload(plsc, T.plsc_own, &T.plsc)) || (rc = upload(codes, T.plsc_code_own, &T.plsc_code)) ||
+        (rc = upload(rn, T.rn_own, &T.rn)) || (rc = upload(make_gardner_bank(), bank))) return rc;
+    ctx->pl = std::move(T);
+    ctx->d_gardner_bank = std::move(bank);
     return 0;
 }
 
@@ -203,9 +201,8 @@ int get_constel(dvbs2gpu_ctx* ctx, const ModcodParams& mp, ConstelTables** out) 
         for (int i = 0; i < 32; ++i) T.dev.pts[i] = i < H.states ? H.pts[i] : cf32{0, 0};
         {
             std::vector<cf32> pv(T.dev.pts, T.dev.pts + 32);
-            int rcp = upload(pv, &T.d_pts);
+            int rcp = upload(pv, T.pts, &T.dev.pts_g);
             if (rcp) return rcp;
-            T.dev.pts_g = T.d_pts;
         }
         T.dev.lut_bits = nullptr; T.dev.lut_err = nullptr; T.dev.lut_bits4 = nullptr;
         if (H.bits != 5) {   // make_lut(256), constellation.cpp:272-291 -- built on the host with the shared math definitions, uploaded
@@ -217,17 +214,15 @@ int get_constel(dvbs2gpu_ctx* ctx, const ModcodParams& mp, ConstelTables** out) 
                     H.soft_calc(cf32{xv, yv}, &lb[((size_t)x * 256 + y) * H.bits], &le[(size_t)x * 256 + y]);
                 }
             int rc;
-            if ((rc = upload(lb, &T.d_bits))) return rc;
-            if ((rc = upload(le, &T.d_err))) return rc;
-            T.dev.lut_bits = T.d_bits; T.dev.lut_err = T.d_err;
+            if ((rc = upload(lb, T.bits, &T.dev.lut_bits))) return rc;
+            if ((rc = upload(le, T.err, &T.dev.lut_err))) return rc;
             // the same soft values, one word per cell (the demapper fetches a cell with one load)
             std::vector<uint32_t> lb4(65536, 0u);
             for (size_t cell = 0; cell < 65536; ++cell)
                 for (int c = 0; c < H.bits; ++c) lb4[cell] |= (uint32_t)(uint8_t)lb[cell * H.bits + c] << (8 * c);
-            if ((rc = upload(lb4, &T.d_bits4))) return rc;
-            T.dev.lut_bits4 = T.d_bits4;
+            if ((rc = upload(lb4, T.bits4, &T.dev.lut_bits4))) return rc;
         }
-        it = ctx->constel.emplace(key, T).first;
+        it = ctx->constel.emplace(key, std::move(T)).first;
     }
     *out = &it->second;
     return 0;
@@ -240,10 +235,10 @@ int get_rrc(dvbs2gpu_ctx* ctx, int ntaps, float alpha, double Ts, float** out) {
     int key = ntaps * 100000 + (int)lround(alpha * 1000) * 10 + (int)lround(Ts);
     auto it = ctx->rrc.find(key);
     if (it == ctx->rrc.end()) {
-        float* d;
-        int rc = upload(make_rrc_taps(ntaps, alpha, Ts), &d);
+        DevBuf<float> d;
+        int rc = upload(make_rrc_taps(ntaps, alpha, Ts), d);
         if (rc) return rc;
-        it = ctx->rrc.emplace(key, d).first;
+        it = ctx->rrc.emplace(key, std::move(d)).first;
     }
     *out = it->second;
     return 0;
@@ -270,12 +265,12 @@ struct dvbs2gpu_demod {
     int pls_code = 0;
     int max_samples = 0;
     // device
-    S2StreamState* d_state = nullptr;
-    cf32* d_in = nullptr;        // staging for the host-pointer entry point
-    cf32* d_fe = nullptr;        // timing-recovery output + scratch
-    cf32* d_fifo[2] = {nullptr, nullptr};
-    cf32* d_spec = nullptr;                  // PLL output of the window the frame loops are ahead of the PL sync in (small banks; allocated on first use)
-    uint8_t* d_out = nullptr;    // staging for the host-pointer entry point
+    DevBuf<S2StreamState> d_state;
+    DevBuf<cf32> d_in;           // staging for the host-pointer entry point
+    DevBuf<cf32> d_fe;           // timing-recovery output + scratch
+    DevBuf<cf32> d_fifo[2];
+    DevBuf<cf32> d_spec;                     // PLL output of the window the frame loops are ahead of the PL sync in (small banks; allocated on first use)
+    DevBuf<uint8_t> d_out;       // staging for the host-pointer entry point
     int fifo_cap = 0, fifo_cur = 0, fifo_fill = 0;
     // (the PL-sync state machine's state -- pending realign offset, last best_match -- lives in the device-side S2StreamState)
     // results of the last call
@@ -573,7 +568,7 @@ int upload_work(dvbs2gpu_demod* const* dm, int n, const cf32* const* d_iq, const
     for (int i = 0; i < n; ++i) {
         dvbs2gpu_demod* d = dm[i];
         if (counts[i] < 0 || counts[i] > d->max_samples) { last_error() = "count exceeds max_samples"; return DVBS2GPU_ERR_ARG; }
-        if (spec && !d->d_spec) HIP_TRY(hipMalloc((void**)&d->d_spec, sizeof(cf32) * 33282));
+        if (spec && !d->d_spec) RC_TRY(d->d_spec.alloc(33282, false, "hipMalloc(demod window)"));
         work[i].in = d_iq[i]; work[i].count = counts[i]; work[i].fe_out = d->d_fe;
         work[i].fifo = d->d_fifo[d->fifo_cur]; work[i].fifo_fill = d->fifo_fill; work[i].st = d->d_state;
         work[i].fifo_next = d->d_fifo[d->fifo_cur ^ 1]; work[i].out = d_out[i]; work[i].spec_out = d->d_spec;
@@ -1046,13 +1041,13 @@ int get_vcm_tables(dvbs2gpu_ctx* ctx) {
     }
     std::lock_guard<std::mutex> l(ctx->mtx);
     if (ctx->d_vcm_mods) return 0;
-    S2VcmMod* dm = nullptr;
-    S2ConstelDev* dc = nullptr;
+    DevBuf<S2VcmMod> dm;
+    DevBuf<S2ConstelDev> dc;
     int rc;
-    if ((rc = upload(mods, &dm)) || (rc = upload(cons, &dc))) { (void)hipFree(dm); (void)hipFree(dc); return rc; }
+    if ((rc = upload(mods, dm)) || (rc = upload(cons, dc))) return rc;
     ctx->h_vcm_mods = mods; ctx->h_vcm_fec = fec;
-    ctx->d_vcm_cons = dc;
-    ctx->d_vcm_mods = dm;
+    ctx->d_vcm_cons = std::move(dc);
+    ctx->d_vcm_mods = std::move(dm);
     return 0;
 }
 
@@ -1524,11 +1519,12 @@ int dvbs2gpu_demod_create(dvbs2gpu_ctx* ctx, const dvbs2gpu_demod_cfg* cfg, int 
     if (rc) return rc;
     CallGuard guard(ctx);               // (one context may serve several blocks on several host threads: whole calls are serialised, ctx.h)
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMalloc((void**)&d->d_state, sizeof(S2StreamState)));
-    HIP_TRY(hipMalloc((void**)&d->d_fe, fe_capacity(max_samples) * sizeof(cf32)));
+    const char* what = "hipMalloc(demod)";
+    RC_TRY(d->d_state.alloc(1, false, what));
+    RC_TRY(d->d_fe.alloc(fe_capacity(max_samples), false, what));
     // FIFO: leftover (< 2 PLFRAMEs, the largest one) + the symbols of one call
     d->fifo_cap = max_samples / 2 + max_samples / 32 + 2 * 33282 + 1024;
-    for (int k = 0; k < 2; ++k) HIP_TRY(hipMalloc((void**)&d->d_fifo[k], (size_t)d->fifo_cap * sizeof(cf32)));
+    for (auto& f : d->d_fifo) RC_TRY(f.alloc((size_t)d->fifo_cap, false, what));
     if ((rc = demod_reset_state(d.get()))) return rc;
     *out = d.release();
     return DVBS2GPU_OK;
@@ -1543,9 +1539,6 @@ void dvbs2gpu_demod_destroy(dvbs2gpu_demod* d) {
     // for it (its frames are dropped at the collecting call, like those of any stream that has left the batch)
     for (void* pj : d->ctx->pending_fec)
         if (pj) for (auto& h : ((PendingFec*)pj)->dm) if (h == d) h = nullptr;
-    (void)hipFree(d->d_state); if (d->d_in) (void)hipFree(d->d_in); (void)hipFree(d->d_fe);
-    (void)hipFree(d->d_fifo[0]); (void)hipFree(d->d_fifo[1]); if (d->d_out) (void)hipFree(d->d_out);
-    if (d->d_spec) (void)hipFree(d->d_spec);
     delete d;
 }
 
@@ -1582,13 +1575,13 @@ int dvbs2gpu_demod_set_params(dvbs2gpu_demod* d, int modcod, int shortframes, in
             if (hs.spec_on) {
                 const float back[2] = {hs.spec_phase0, hs.spec_freq0};
                 static_assert(offsetof(S2StreamState, pll_freq) == offsetof(S2StreamState, pll_phase) + sizeof(float), "pll_phase, pll_freq are restored together");
-                HIP_TRY(hipMemcpy((char*)d->d_state + offsetof(S2StreamState, pll_phase), back, sizeof(back), hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy((char*)d->d_state.get() + offsetof(S2StreamState, pll_phase), back, sizeof(back), hipMemcpyHostToDevice));
                 const int off = 0;
-                HIP_TRY(hipMemcpy((char*)d->d_state + offsetof(S2StreamState, spec_on), &off, sizeof(off), hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy((char*)d->d_state.get() + offsetof(S2StreamState, spec_on), &off, sizeof(off), hipMemcpyHostToDevice));
             }
         }
-        HIP_TRY(hipMemcpy((char*)d->d_state + offsetof(S2StreamState, pl_pending), zero_pl, sizeof(zero_pl), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy((char*)d->d_state + offsetof(S2StreamState, walk_cur), zero_walk, sizeof(zero_walk), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((char*)d->d_state.get() + offsetof(S2StreamState, pl_pending), zero_pl, sizeof(zero_pl), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((char*)d->d_state.get() + offsetof(S2StreamState, walk_cur), zero_walk, sizeof(zero_walk), hipMemcpyHostToDevice));
     }
     return 0;
 }
@@ -1807,11 +1800,9 @@ int dvbs2gpu_demod_process(dvbs2gpu_demod* d, int count, const float* h_iq, uint
     CallGuard guard(d->ctx);                    // the per-call workspaces are context-wide: one call at a time per context
     HIP_TRY(hipSetDevice(d->ctx->device));
     { int rq = ws_quiesce(d->ctx); if (rq) return rq; }
-    if (!d->d_in) {   // staging buffers of the host-pointer entry point, allocated on first use
-        HIP_TRY(hipMalloc((void**)&d->d_in, (size_t)d->max_samples * sizeof(cf32)));
-        int max_frames = d->fifo_cap / 3330 + 2;
-        HIP_TRY(hipMalloc((void**)&d->d_out, (size_t)max_frames * 8100));
-    }
+    // staging buffers of the host-pointer entry point, allocated on first use
+    if (!d->d_in) RC_TRY(d->d_in.alloc((size_t)d->max_samples, false, "hipMalloc(demod staging)"));
+    if (!d->d_out) RC_TRY(d->d_out.alloc((size_t)(d->fifo_cap / 3330 + 2) * 8100, false, "hipMalloc(demod staging)"));
     if (count) HIP_TRY(hipMemcpy(d->d_in, h_iq, (size_t)count * sizeof(cf32), hipMemcpyHostToDevice));
     const cf32* in = d->d_in;
     uint8_t* dout = d->d_out;

@@ -22,26 +22,21 @@ struct dvbs2gpu_segrx {
     long spf = 0;                      // samples per PLFRAME at 2 samples per symbol
     long seg_cap = 0, hist_cap = 0, out_stride = 0;
     std::vector<dvbs2gpu_demod*> dm;
-    float* d_hist = nullptr;           // the last hist_fill samples of the stream so far
-    float* d_hist2 = nullptr;
-    float* d_seg0 = nullptr;           // history ++ head of the chunk: the first segment's input
-    uint8_t* d_segout = nullptr;
+    DevBuf<float> d_hist;              // the last hist_fill samples of the stream so far
+    DevBuf<float> d_hist2;
+    DevBuf<float> d_seg0;              // history ++ head of the chunk: the first segment's input
+    DevBuf<uint8_t> d_segout;
     long hist_fill = 0;
     long long abs_next = 0;            // stream index of the next call's first sample
     long long last_emit = 0;
     bool emitted_any = false, first_call = true;
     int last_found = 0, last_emitted = 0, last_dropped = 0;
+    ~dvbs2gpu_segrx() { for (auto* d : dm) if (d) dvbs2gpu_demod_destroy(d); }
 };
 
 extern "C" {
 
-void dvbs2gpu_segrx_destroy(dvbs2gpu_segrx* r) {
-    if (!r) return;
-    for (auto* d : r->dm) if (d) dvbs2gpu_demod_destroy(d);
-    void* ps[] = {r->d_hist, r->d_hist2, r->d_seg0, r->d_segout};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    delete r;
-}
+void dvbs2gpu_segrx_destroy(dvbs2gpu_segrx* r) { delete r; }
 
 int dvbs2gpu_segrx_create(dvbs2gpu_ctx* ctx, const dvbs2gpu_demod_cfg* cfg, int nsegments, int own_frames, int warm_frames, dvbs2gpu_segrx** out) {
     if (!ctx || !cfg || !out || nsegments < 1 || own_frames < 1 || warm_frames < 1 || own_frames < warm_frames) {
@@ -52,7 +47,7 @@ int dvbs2gpu_segrx_create(dvbs2gpu_ctx* ctx, const dvbs2gpu_demod_cfg* cfg, int 
     int rc = dvbs2gpu_modcod_info_get(cfg->modcod, cfg->shortframes, cfg->pilots, &mi);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    auto r = new dvbs2gpu_segrx();
+    std::unique_ptr<dvbs2gpu_segrx> r(new dvbs2gpu_segrx());
     r->ctx = ctx; r->cfg = *cfg; r->nseg = nsegments; r->own = own_frames; r->warm = warm_frames;
     r->kb = mi.kbch / 8;
     r->spf = 2L * mi.plframe_symbols;
@@ -60,20 +55,17 @@ int dvbs2gpu_segrx_create(dvbs2gpu_ctx* ctx, const dvbs2gpu_demod_cfg* cfg, int 
     r->seg_cap = (long)(warm_frames + own_frames + warm_frames / 2 + 4) * r->spf + 64;
     r->out_stride = (long)(warm_frames + own_frames + warm_frames / 2 + 6) * r->kb;
     if (r->seg_cap > 0x3fffffffL || r->out_stride > 0x7fffffffL) {      // per-segment counts are ints in the batch entry
-        delete r;
         g_err = "segment receiver: a segment of this many frames does not fit the batch entry's int counts";
         return DVBS2GPU_ERR_ARG;
     }
     r->dm.assign(nsegments, nullptr);
-    for (int g = 0; g < nsegments; ++g) {
-        if ((rc = dvbs2gpu_demod_create(ctx, cfg, (int)r->seg_cap, &r->dm[g]))) { dvbs2gpu_segrx_destroy(r); return rc; }
-    }
-    hipError_t e = hipMalloc((void**)&r->d_hist, sizeof(float) * 2 * r->hist_cap);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->d_hist2, sizeof(float) * 2 * r->hist_cap);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->d_seg0, sizeof(float) * 2 * r->seg_cap);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->d_segout, (size_t)r->out_stride * nsegments);
-    if (e != hipSuccess) { dvbs2gpu_segrx_destroy(r); return fail_hip(e, "hipMalloc(segment receiver)"); }
-    *out = r;
+    for (int g = 0; g < nsegments; ++g) RC_TRY(dvbs2gpu_demod_create(ctx, cfg, (int)r->seg_cap, &r->dm[g]));
+    const char* what = "hipMalloc(segment receiver)";
+    RC_TRY(r->d_hist.alloc(2 * r->hist_cap, false, what));
+    RC_TRY(r->d_hist2.alloc(2 * r->hist_cap, false, what));
+    RC_TRY(r->d_seg0.alloc(2 * r->seg_cap, false, what));
+    RC_TRY(r->d_segout.alloc((size_t)r->out_stride * nsegments, false, what));
+    *out = r.release();
     return 0;
 }
 

@@ -73,11 +73,7 @@ __attribute__((always_inline)) inline bool ts_bank_check_counts(const char* pref
 
 // The device copies of one stream's host buffers (the single-stream entry points).  Workspace::ensure grows with a quarter of
 // slack: harmless here, the input never grows after the first call and the output follows the largest cap seen.
-struct TsHostStage {
-    Workspace in, out;
-    TsHostStage() = default; TsHostStage(const TsHostStage&) = delete;
-    ~TsHostStage() { in.release(); out.release(); }
-};
+struct TsHostStage { Workspace in, out; };
 // The device path of a single-stream call with host buffers: h_ts staged, room for cap + 4 output bytes, per-stream vectors in which the other
 // streams bring nothing (out_all: they have the output pointer all the same), the bank's batch(in, nbytes, out or null, out_bytes), copy back
 template <typename Batch>

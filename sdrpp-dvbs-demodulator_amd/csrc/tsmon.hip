@@ -234,13 +234,13 @@ struct dvbs2gpu_tsmon {
     std::vector<TsmonCall> h_call;
     std::vector<char> h_args;
     // device banks
-    uint8_t* d_state = nullptr;                    // nstreams x 8192 continuity bytes (tsmon_rules.h)
-    TsmonFilter* d_filt = nullptr;
-    uint32_t* d_map = nullptr;
-    TsmonRow* d_rows = nullptr;                    // nstreams x maxrows
-    uint8_t* d_newst = nullptr;                    // the state byte behind every row's last packet
-    TsmonCall* d_call = nullptr;
-    void* d_args = nullptr;                        // TsBankArgs(nstreams)
+    DevBuf<uint8_t> d_state;                       // nstreams x 8192 continuity bytes (tsmon_rules.h)
+    DevBuf<TsmonFilter> d_filt;
+    DevBuf<uint32_t> d_map;
+    DevBuf<TsmonRow> d_rows;                       // nstreams x maxrows
+    DevBuf<uint8_t> d_newst;                       // the state byte behind every row's last packet
+    DevBuf<TsmonCall> d_call;
+    DevBuf<uint8_t> d_args;                        // TsBankArgs(nstreams)
     TsHostStage stage;                             // of the host-buffer entry point
     // host-only banks
     std::vector<TsmonHostStream> host;
@@ -254,8 +254,8 @@ static void tsmon_account(dvbs2gpu_tsmon* m, int i, const TsmonCall& c) {
     s.scrambled_packets += c.scrambled_packets; s.passed_packets += c.passed_packets; s.pids_seen += c.first_seen;
     m->nrows[i] = c.nrows;
 }
-static dvbs2gpu_tsmon* tsmon_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets) {
-    auto m = new dvbs2gpu_tsmon();
+static std::unique_ptr<dvbs2gpu_tsmon> tsmon_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets) {
+    std::unique_ptr<dvbs2gpu_tsmon> m(new dvbs2gpu_tsmon());
     m->ctx = ctx; m->nstreams = nstreams; m->max_packets = max_packets;
     m->maxrows = max_packets < TSMON_PIDS ? max_packets : TSMON_PIDS;
     while (m->npad_max < max_packets) m->npad_max <<= 1;
@@ -275,37 +275,31 @@ static bool tsmon_create_args_ok(int nstreams, int max_packets, dvbs2gpu_tsmon**
 
 extern "C" {
 
-void dvbs2gpu_tsmon_destroy(dvbs2gpu_tsmon* m) {
-    if (!m) return;
-    void* ps[] = {m->d_state, m->d_filt, m->d_map, m->d_rows, m->d_newst, m->d_call, m->d_args};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    delete m;
-}
+void dvbs2gpu_tsmon_destroy(dvbs2gpu_tsmon* m) { delete m; }
 
 int dvbs2gpu_tsmon_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, dvbs2gpu_tsmon** out) {
     if (!ctx || !tsmon_create_args_ok(nstreams, max_packets, out)) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    dvbs2gpu_tsmon* m = tsmon_new(ctx, nstreams, max_packets);
+    auto m = tsmon_new(ctx, nstreams, max_packets);
     const size_t n = (size_t)nstreams;
-    hipError_t e = hipSuccess;                         // (the rows, their states and the call records are written before they are read)
-    bbts_alloc(e, &m->d_state, n * TSMON_PIDS);
-    bbts_alloc(e, &m->d_filt, n * sizeof(TsmonFilter));
-    bbts_alloc(e, &m->d_map, n * TSMON_MAP_WORDS * sizeof(uint32_t));
-    bbts_alloc(e, &m->d_rows, n * m->maxrows * sizeof(TsmonRow), false);
-    bbts_alloc(e, &m->d_newst, n * m->maxrows, false);
-    bbts_alloc(e, &m->d_call, n * sizeof(TsmonCall), false);
-    bbts_alloc(e, &m->d_args, TsBankArgs(n).L.bytes(), false);
-    if (e != hipSuccess) { dvbs2gpu_tsmon_destroy(m); return fail_hip(e, "hipMalloc(tsmon)"); }
+    const char* what = "hipMalloc(tsmon)";             // (the rows, their states and the call records are written before they are read)
+    RC_TRY(m->d_state.alloc(n * TSMON_PIDS, true, what));
+    RC_TRY(m->d_filt.alloc(n, true, what));
+    RC_TRY(m->d_map.alloc(n * TSMON_MAP_WORDS, true, what));
+    RC_TRY(m->d_rows.alloc(n * m->maxrows, false, what));
+    RC_TRY(m->d_newst.alloc(n * m->maxrows, false, what));
+    RC_TRY(m->d_call.alloc(n, false, what));
+    RC_TRY(m->d_args.alloc(TsBankArgs(n).L.bytes(), false, what));
     m->h_args.resize(TsBankArgs(n).L.bytes());
-    *out = m;
+    *out = m.release();
     return 0;
 }
 
 int dvbs2gpu_tsmon_create_host(int nstreams, int max_packets, dvbs2gpu_tsmon** out) {
     if (!tsmon_create_args_ok(nstreams, max_packets, out)) return DVBS2GPU_ERR_ARG;
-    dvbs2gpu_tsmon* m = tsmon_new(nullptr, nstreams, max_packets);
+    auto m = tsmon_new(nullptr, nstreams, max_packets);
     m->host.resize(nstreams);
-    *out = m;
+    *out = m.release();
     return 0;
 }
 
