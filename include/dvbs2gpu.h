@@ -992,6 +992,129 @@ int dvbs2gpu_pcr_get_row_table(dvbs2gpu_pcr* b, int stream, dvbs2gpu_pcr_row* h_
 /* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
 int dvbs2gpu_pcr_get_row_table_device(dvbs2gpu_pcr* b, int stream, const dvbs2gpu_pcr_row** d_rows, int* n);
 
+/* ------------------------------------------------------------------ PES bank (own extension)
+ * Nothing in the reference does this.  For `nstreams` transport streams in HBM a bank looks at the elementary streams of up to 16
+ * watched PIDs per stream: where PES packets start and what their headers say, whether the PES packets are whole (PES_packet_length
+ * against the payload bytes that came, continuity in between), and the presentation and decoding timestamps -- PTS_error of ETSI
+ * TR 101 290 second priority (2.5) among them.  One table row per PES packet start.  The engine has no clock: a timestamp is a 90 kHz
+ * clock and on a constant-rate stream the packet position is a second one, so every check is integer arithmetic and no result depends
+ * on how a stream is cut into calls.  The sequential form below is the definition (csrc/pes_rules.h, PesHostStream::run).
+ *   Watches: 16 slots per stream, each a PID 0..0x1FFE or nothing.  A new bank watches nothing.  Changing a slot's watch starts the
+ *     slot afresh, state and counters.
+ *   Packet: 188 bytes at offset 188 k, classified as the TS monitor does.  Sync-byte errors, TEI packets, null packets and packets of
+ *     unwatched PIDs are not looked at.  A remaining packet of a watched PID counts in `packets` and, in this order:
+ *     1. takes the TS monitor's continuity step (dvbs2gpu_tsmon_*: one state byte per slot).  DUPLICATE: counted in duplicates, nothing
+ *        more of the packet is used.  CC_ERROR (counted in cc_errors) or an announced discontinuity: the slot's open PES packet is
+ *        marked GAP, and the packet goes on.
+ *     2. No payload (AFC&1 clear): done.
+ *     3. AFC = 3 and b4 (adaptation_field_length) > 182: malformed_packets, the open PES packet is marked GAP, done.
+ *     4. The payload starts at byte 4 (AFC = 1) or 5 + b4 (AFC = 3) and holds L = 188 - start bytes.  L adds to payload_bytes; a packet
+ *        with TSC != 0 adds to scrambled_packets, and its payload is not read.
+ *     5. PUSI clear: L adds to the bytes of the open PES packet, 1 to its packets (both saturate at 2^32 - 1).  PUSI set: a start.
+ *   Start: one row; the kind is the first of
+ *       SCRAMBLED   TSC != 0
+ *       SHORT       L < 6
+ *       BAD_START   payload[0..2] != 00 00 01
+ *       PLAIN       stream_id 0xBC, 0xBE, 0xBF, 0xF0, 0xF1, 0xF2, 0xF8 or 0xFF: a stream without the optional header
+ *       SHORT       L < 9
+ *       MALFORMED   (payload[6] & 0xC0) != 0x80, or PTS_DTS_flags = 01, or PES_header_data_length < 5 (flags 10) or < 10 (flags 11)
+ *       SHORT       L < 14 (flags 10) or L < 19 (flags 11): the header is split over packets, which is legal and rare; it is not parsed
+ *       MALFORMED   a marker bit of a timestamp is 0, or its 4-bit prefix is not 0010 (PTS alone), 0011 (PTS with DTS), 0001 (DTS)
+ *       HEADER      anything else
+ *     stream_id = payload[3] from BAD_START on (0 before).  declared = PES_packet_length, payload[4..5], from PLAIN on and for the
+ *     second SHORT; 0 (unknown) for SCRAMBLED, the first SHORT and BAD_START.  pts / dts: the 33-bit values of a HEADER row, all ones
+ *     where absent and in every other kind.  A HEADER start with declared = 0 and a stream_id outside 0xE0..0xEF has the flag
+ *     UNBOUNDED_NONVIDEO (only video may leave the length open).
+ *   Closing: a start closes the slot's open PES packet, if there is one: closed_bytes and closed_packets are that packet's (the
+ *     start's own L is not among them), with the flag CLOSED and one of: CLOSED_GAP if it was marked GAP; else CLOSED_UNCHECKED if its
+ *     declared length was 0; else CLOSED_MISMATCH if its bytes != declared + 6.  None of the three: the PES packet was whole.  The
+ *     start then is the open PES packet: its declared, L bytes, 1 packet, no GAP.
+ *   Timestamps: HEADER rows with a PTS.  T = the DTS if present, else the PTS.  DTS_AFTER_PTS: both present and (pts - dts) mod 2^33
+ *     >= 2^32.  State per slot: seen, last_T, ref_n.  Not seen: flag TS_FIRST, no deltas.  Else dT = (T - last_T) mod 2^33 and dN =
+ *     n - ref_n: dT >= 2^32: TS_BACKWARD; else dT > 63 000 (0.7 s at 90 kHz): TS_GAP; with a rate set and dN > late_packets: PTS_LATE
+ *     (TR 101 290 2.5: a PTS repetition period of more than 700 ms), late_packets = floor((18 900 000 << 24) / ticks_per_packet_q24).
+ *     delta_ts = dT as int32 (values >= 2^32 shown negative, dT - 2^33; clamped), delta_packets = dN saturating at 2^32 - 1.  Then
+ *     state := (T, n).
+ *   Position: n = the stream's packet count since creation or reset + the packet's index in the call, 64 bits.  Every packet of
+ *     every call counts, untrusted ones too.
+ *   Row: one per start, in input order across the slots.  The table holds the first max_rows rows of a call: a monitor does not fail
+ *     for room.  out_rows[] carries the true count, rows_dropped accumulates the excess, and the counters cover every start.
+ *   State survives from call to call.  reset forgets it (positions and counters too; watches and rates stay).
+ *   Limits: max_packets <= 4096 per stream and call.  Memory (device banks) per stream: 512 bytes of state, 48 bytes per row of
+ *     max_rows and a call record of 1552 bytes. */
+typedef struct dvbs2gpu_pes dvbs2gpu_pes;
+int dvbs2gpu_pes_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_pes** out);
+/* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_pes_work only */
+int dvbs2gpu_pes_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_pes** out);
+int dvbs2gpu_pes_reset(dvbs2gpu_pes* b);
+void dvbs2gpu_pes_destroy(dvbs2gpu_pes* b);
+/* slot 0..15; pid 0..0x1FFE, or -1: the slot watches nothing.  The same PID in two slots of a stream is DVBS2GPU_ERR_ARG. */
+int dvbs2gpu_pes_set_watch(dvbs2gpu_pes* b, int stream, int slot, int pid);
+/* ticks_per_packet_q24: the quantity of dvbs2gpu_pcr_set_rate (27 MHz ticks per 188-byte packet in Q24.24, < 2^48), 0: not set (a new
+ * bank; no PTS_LATE).  The slots' states and counters stay. */
+int dvbs2gpu_pes_set_rate(dvbs2gpu_pes* b, int stream, uint64_t ticks_per_packet_q24);
+/* d_ts[i]: DEVICE pointer to nbytes[i] bytes (a multiple of 188, at most 188*max_packets) of stream i, of any alignment.  out_rows
+ * (host, may be NULL): the starts of the call per stream, of which the table holds the first max_rows.  One kernel launch.
+ * Synchronous on `stream`; chained behind a packetiser or monitor call on the same stream, no packet visits the host. */
+int dvbs2gpu_pes_process_batch(dvbs2gpu_pes* b, const uint8_t* const* d_ts, const int* nbytes, int* out_rows, void* stream);
+/* one stream of any bank with a HOST buffer: returns the starts of the call or a negative error.  The other streams of the bank
+ * receive an empty call. */
+int dvbs2gpu_pes_work(dvbs2gpu_pes* b, int stream, const uint8_t* h_ts, int nbytes);
+typedef struct dvbs2gpu_pes_stats {            /* of a slot, since creation, reset or the slot's last set_watch; kept on the host */
+    int64_t packets;                 /* trusted packets of the watched PID, duplicates among them */
+    int64_t payload_bytes, duplicates, cc_errors, scrambled_packets, malformed_packets;
+    int64_t starts;                  /* rows: the sum of the six kinds */
+    int64_t starts_scrambled, starts_short, starts_bad_start, starts_plain, starts_malformed, starts_header;
+    int64_t with_pts, with_dts;      /* HEADER starts */
+    int64_t closed_ok;               /* CLOSED and none of the three flags below */
+    int64_t closed_mismatch, closed_gap, closed_unchecked;
+    int64_t ts_backward, ts_gap, pts_late, dts_after_pts;
+    int64_t max_delta_packets;
+} dvbs2gpu_pes_stats;
+/* slot -1: the sum over the stream's slots (of the maximum the larger) */
+int dvbs2gpu_pes_get_stats(dvbs2gpu_pes* b, int stream, int slot, dvbs2gpu_pes_stats* h_out);
+typedef struct dvbs2gpu_pes_stream_stats {
+    int64_t packets;                 /* every 188 bytes handed in: the position of the next packet */
+    int64_t rows_dropped;
+    int64_t packets_since_start[16]; /* per slot: `packets` minus the position of the slot's last start (1: the stream's last packet
+                                        was it); -1: the slot has had none */
+} dvbs2gpu_pes_stream_stats;
+int dvbs2gpu_pes_get_stream_stats(dvbs2gpu_pes* b, int stream, dvbs2gpu_pes_stream_stats* h_out);
+#define DVBS2GPU_PES_SCRAMBLED 0
+#define DVBS2GPU_PES_SHORT 1
+#define DVBS2GPU_PES_BAD_START 2
+#define DVBS2GPU_PES_PLAIN 3
+#define DVBS2GPU_PES_MALFORMED 4
+#define DVBS2GPU_PES_HEADER 5
+#define DVBS2GPU_PES_CLOSED 1
+#define DVBS2GPU_PES_CLOSED_GAP 2
+#define DVBS2GPU_PES_CLOSED_MISMATCH 4
+#define DVBS2GPU_PES_CLOSED_UNCHECKED 8
+#define DVBS2GPU_PES_UNBOUNDED_NONVIDEO 16
+#define DVBS2GPU_PES_TS_FIRST 32
+#define DVBS2GPU_PES_TS_BACKWARD 64
+#define DVBS2GPU_PES_TS_GAP 128
+#define DVBS2GPU_PES_PTS_LATE 256
+#define DVBS2GPU_PES_DTS_AFTER_PTS 512
+#pragma pack(push, 4)
+typedef struct dvbs2gpu_pes_row {              /* 48 bytes */
+    uint16_t pid;                    /* offset 0 */
+    uint8_t slot, kind;              /* 2, 3: DVBS2GPU_PES_SCRAMBLED .. DVBS2GPU_PES_HEADER */
+    uint16_t flags;                  /* 4 */
+    uint8_t stream_id, reserved;     /* 6, 7 */
+    int32_t packet;                  /* 8: index in this call */
+    uint32_t declared;               /* 12: PES_packet_length, 0: unknown or unbounded */
+    uint64_t pts, dts;               /* 16, 24: all ones: absent */
+    uint32_t closed_bytes, closed_packets;   /* 32, 36: of the PES packet that this start closed */
+    uint32_t delta_packets;          /* 40 */
+    int32_t delta_ts;                /* 44: 90 kHz ticks */
+} dvbs2gpu_pes_row;
+#pragma pack(pop)
+/* h_rows[cap] (host); *n = rows of the last call in the table, of which min(*n, cap) are written */
+int dvbs2gpu_pes_get_row_table(dvbs2gpu_pes* b, int stream, dvbs2gpu_pes_row* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_pes_get_row_table_device(dvbs2gpu_pes* b, int stream, const dvbs2gpu_pes_row** d_rows, int* n);
+
 #ifdef __cplusplus
 }
 #endif

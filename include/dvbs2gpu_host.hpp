@@ -715,5 +715,106 @@ private:
     int status_ = 0;
     std::string error_;
 };
+
+/* PES bank for one transport stream (dvbs2gpu_pes_*, include/dvbs2gpu.h; an extension): PES packet starts, PES length checks and
+ * PTS / DTS checks on up to 16 watched PIDs behind BBFrameTSParser, DVBSDemod or TSMonitor.  init() (a device bank) or initHost() (the
+ * library's host implementation, no device) and the setters throw; work() sits in the data path and does NOT throw: a failing call
+ * returns 0 and leaves its code in status() and its text in error(), sticky until clearStatus(). */
+class PesBank {
+public:
+    PesBank() {}
+    ~PesBank() {
+        if (h) dvbs2gpu_pes_destroy(h);
+    }
+    PesBank(const PesBank&) = delete;
+    PesBank& operator=(const PesBank&) = delete;
+
+    void init(int max_packets, int max_rows, int device = 0) {
+        release();
+        eng = Engine::get(device);
+        check(dvbs2gpu_pes_create(eng->ctx, 1, max_packets, max_rows, &h));
+    }
+    void initHost(int max_packets, int max_rows) {
+        release();
+        check(dvbs2gpu_pes_create_host(1, max_packets, max_rows, &h));
+    }
+    void reset() { check(dvbs2gpu_pes_reset(need())); }
+    /* slot 0..15; pid -1 clears the slot */
+    void setWatch(int slot, int pid) {
+        check(dvbs2gpu_pes_set_watch(need(), 0, slot, pid));
+        watched[slot] = pid;
+    }
+    /* 27 MHz ticks per 188-byte packet in Q24.24, the quantity of PcrBank::setRate (0: no PTS_LATE) */
+    void setRate(uint64_t ticks_per_packet_q24) { check(dvbs2gpu_pes_set_rate(need(), 0, ticks_per_packet_q24)); }
+    /* watches the elementary PIDs of the PMTs that `psi` holds decoded, in free slots, in the order of its slots and then of each
+     * PMT's elementary streams; stream types that carry sections and PIDs watched already are skipped; returns the PIDs that found
+     * no free slot */
+    std::vector<int> followPmts(PsiBank& psi, const std::vector<int>& skip_types = {0x05, 0x0A, 0x0B, 0x0C, 0x0D, 0x86}) {
+        std::vector<int> left;
+        for (int slot = 0; slot < 16; ++slot) {
+            dvbs2gpu_psi_pmt pmt;
+            const std::vector<dvbs2gpu_psi_es> es = psi.programMap(slot, &pmt);
+            if (pmt.program_number < 0) continue;
+            for (const dvbs2gpu_psi_es& e : es) {
+                const int pid = e.elementary_pid;
+                if (std::find(skip_types.begin(), skip_types.end(), (int)e.stream_type) != skip_types.end() || pid >= 0x1FFF ||
+                    std::find(watched, watched + 16, pid) != watched + 16 || std::find(left.begin(), left.end(), pid) != left.end())
+                    continue;
+                int* free_slot = std::find(watched, watched + 16, -1);
+                if (free_slot == watched + 16) left.push_back(pid);
+                else setWatch((int)(free_slot - watched), pid);
+            }
+        }
+        return left;
+    }
+    /* nbytes of whole TS packets in; returns the starts (PES packet starts on watched PIDs) of the call, 0 on failure (see status()) */
+    int work(const uint8_t* ts, int nbytes) noexcept {
+        const int n = h ? dvbs2gpu_pes_work(h, 0, ts, nbytes) : DVBS2GPU_ERR_ARG;
+        if (n >= 0) return n;
+        if (status_ == 0) {
+            status_ = n;
+            try { error_ = h ? dvbs2gpu_last_error() : "PesBank used before init()"; } catch (...) {}
+        }
+        return 0;
+    }
+    int status() const { return status_; }
+    const std::string& error() const { return error_; }
+    void clearStatus() { status_ = 0; error_.clear(); }
+
+    dvbs2gpu_pes_stats stats(int slot = -1) {
+        dvbs2gpu_pes_stats s;
+        check(dvbs2gpu_pes_get_stats(need(), 0, slot, &s));
+        return s;
+    }
+    dvbs2gpu_pes_stream_stats streamStats() {
+        dvbs2gpu_pes_stream_stats s;
+        check(dvbs2gpu_pes_get_stream_stats(need(), 0, &s));
+        return s;
+    }
+    /* one row per start of the last work(), in input order (the first max_rows) */
+    std::vector<dvbs2gpu_pes_row> rowTable() {
+        int n = 0;
+        check(dvbs2gpu_pes_get_row_table(need(), 0, nullptr, 0, &n));
+        std::vector<dvbs2gpu_pes_row> rows((size_t)n);
+        if (n > 0) check(dvbs2gpu_pes_get_row_table(h, 0, rows.data(), n, &n));
+        return rows;
+    }
+
+private:
+    void release() {
+        if (h) dvbs2gpu_pes_destroy(h);
+        h = nullptr;
+        std::fill(watched, watched + 16, -1);
+    }
+    dvbs2gpu_pes* need() {
+        if (!h) throw std::runtime_error("dvbs2gpu: PesBank used before init()");
+        return h;
+    }
+    std::shared_ptr<Engine> eng;
+    dvbs2gpu_pes* h = nullptr;
+    int watched[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // slot -> PID, as setWatch left them
+    int status_ = 0;
+    std::string error_;
+};
 }   // namespace dvbs2gpu_host
 #endif

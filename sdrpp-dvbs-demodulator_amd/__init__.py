@@ -164,6 +164,27 @@ class PcrRow(C.Structure):
                 ('pcr', C.c_uint64), ('delta_ticks', C.c_uint32), ('delta_packets', C.c_uint32), ('accuracy', C.c_int32)]
 
 
+class PesStats(C.Structure):
+    """dvbs2gpu_pes_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('packets', 'payload_bytes', 'duplicates', 'cc_errors', 'scrambled_packets', 'malformed_packets', 'starts',
+                                         'starts_scrambled', 'starts_short', 'starts_bad_start', 'starts_plain', 'starts_malformed', 'starts_header',
+                                         'with_pts', 'with_dts', 'closed_ok', 'closed_mismatch', 'closed_gap', 'closed_unchecked', 'ts_backward', 'ts_gap',
+                                         'pts_late', 'dts_after_pts', 'max_delta_packets')]
+
+
+class PesStreamStats(C.Structure):
+    """dvbs2gpu_pes_stream_stats"""
+    _fields_ = [('packets', C.c_int64), ('rows_dropped', C.c_int64), ('packets_since_start', C.c_int64 * 16)]
+
+
+class PesRow(C.Structure):
+    """dvbs2gpu_pes_row"""
+    _pack_ = 4
+    _fields_ = [('pid', C.c_uint16), ('slot', C.c_uint8), ('kind', C.c_uint8), ('flags', C.c_uint16), ('stream_id', C.c_uint8), ('reserved', C.c_uint8),
+                ('packet', C.c_int32), ('declared', C.c_uint32), ('pts', C.c_uint64), ('dts', C.c_uint64), ('closed_bytes', C.c_uint32),
+                ('closed_packets', C.c_uint32), ('delta_packets', C.c_uint32), ('delta_ts', C.c_int32)]
+
+
 class FrameQuality(C.Structure):
     """dvbs2gpu_frame_quality"""
     _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('gain', C.c_float), ('phase', C.c_float), ('known_symbols', C.c_int32),
@@ -344,6 +365,18 @@ PROTOTYPES = {
     'dvbs2gpu_pcr_get_rate': (_i, [_vp, _i, _i, C.POINTER(C.c_double)]),
     'dvbs2gpu_pcr_get_row_table': (_i, [_vp, _i, C.POINTER(PcrRow), _i, C.POINTER(_i)]),
     'dvbs2gpu_pcr_get_row_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
+    'dvbs2gpu_pes_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_pes_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_pes_reset': (_i, [_vp]),
+    'dvbs2gpu_pes_destroy': (None, [_vp]),
+    'dvbs2gpu_pes_set_watch': (_i, [_vp, _i, _i, _i]),
+    'dvbs2gpu_pes_set_rate': (_i, [_vp, _i, C.c_uint64]),
+    'dvbs2gpu_pes_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _vp]),
+    'dvbs2gpu_pes_work': (_i, [_vp, _i, _vp, _i]),
+    'dvbs2gpu_pes_get_stats': (_i, [_vp, _i, _i, C.POINTER(PesStats)]),
+    'dvbs2gpu_pes_get_stream_stats': (_i, [_vp, _i, C.POINTER(PesStreamStats)]),
+    'dvbs2gpu_pes_get_row_table': (_i, [_vp, _i, C.POINTER(PesRow), _i, C.POINTER(_i)]),
+    'dvbs2gpu_pes_get_row_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
 }
 
 _lib = None
@@ -1537,6 +1570,103 @@ class PcrBank(_TsBank):
         """(device pointer or None, rows): the same table as dvbs2gpu_pcr_row records in HBM, valid until the next call"""
         p, n = C.c_void_p(), C.c_int()
         self._check(self.lib.dvbs2gpu_pcr_get_row_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+
+class PesBank(_TsBank):
+    """PES bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, PES bank): PES packet starts, PES length checks and
+    PTS / DTS checks on up to 16 watched PIDs per stream, one table row per PES packet start."""
+    _destroy = 'dvbs2gpu_pes_destroy'
+    SLOTS = 16
+    SCRAMBLED, SHORT, BAD_START, PLAIN, MALFORMED, HEADER = range(6)
+    CLOSED, CLOSED_GAP, CLOSED_MISMATCH, CLOSED_UNCHECKED, UNBOUNDED_NONVIDEO = 1, 2, 4, 8, 16
+    TS_FIRST, TS_BACKWARD, TS_GAP, PTS_LATE, DTS_AFTER_PTS = 32, 64, 128, 256, 512
+    NO_TS = (1 << 64) - 1
+    SECTION_STREAM_TYPES = (0x05, 0x0A, 0x0B, 0x0C, 0x0D, 0x86)     # private sections, DSM-CC (four types), SCTE 35: they carry sections
+    ROW_KEYS = tuple(k for k, _ in PesRow._fields_)
+
+    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=1024):
+        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
+        h = C.c_void_p()
+        engine._check(self.lib.dvbs2gpu_pes_create(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
+        self.h = h
+        self._watched = [{} for _ in range(nstreams)]               # per stream: slot -> PID, as set_watch left them
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096, max_rows=1024):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        self = cls._host('dvbs2gpu_pes_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
+        self._watched = [{} for _ in range(nstreams)]
+        return self
+
+    def reset(self):
+        """forgets states, positions and counters; watches and rates stay"""
+        self._check(self.lib.dvbs2gpu_pes_reset(self.h))
+
+    def set_watch(self, stream, slot, pid):
+        """pid -1 clears the slot; the slot starts afresh"""
+        self._check(self.lib.dvbs2gpu_pes_set_watch(self.h, int(stream), int(slot), int(pid)))
+        self._watched[int(stream)].pop(int(slot), None)
+        if pid >= 0:
+            self._watched[int(stream)][int(slot)] = int(pid)
+
+    def set_rate(self, stream, ticks_per_packet_q24):
+        """27 MHz ticks per 188-byte packet in Q24.24, the PCR bank's quantity (0: no PTS_LATE)"""
+        self._check(self.lib.dvbs2gpu_pes_set_rate(self.h, int(stream), int(ticks_per_packet_q24)))
+
+    def follow_pmts(self, psi_bank, stream=0, skip_types=SECTION_STREAM_TYPES):
+        """watches the elementary PIDs of the PMTs that `psi_bank` (a PsiBank that read the same stream) holds decoded, in free slots, in
+        the order of its slots and then of each PMT's elementary streams; stream types that carry sections (skip_types) and PIDs watched
+        already are skipped -> the PIDs that found no free slot"""
+        watched = self._watched[int(stream)]
+        left = []
+        for slot in range(psi_bank.SLOTS):
+            hdr, es = psi_bank.program_map(stream, slot)
+            if hdr['program_number'] < 0:
+                continue
+            for stream_type, pid in es:
+                if stream_type in skip_types or pid >= 0x1FFF or pid in watched.values() or pid in left:
+                    continue
+                free = [s for s in range(self.SLOTS) if s not in watched]
+                if free:
+                    self.set_watch(stream, free[0], pid)
+                else:
+                    left.append(pid)
+        return left
+
+    def process(self, ts_tensors, nbytes=None):
+        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all), of any alignment -> the starts of the
+        call per stream (the table holds the first max_rows of them)"""
+        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
+        nr = (C.c_int * self.nstreams)()
+        self._check(self.lib.dvbs2gpu_pes_process_batch(self.h, pin, cnt, nr, self.eng._stream()))
+        return list(nr)
+
+    def work(self, ts, stream=0):
+        """one stream, a host buffer: numpy uint8 packets in -> the starts of the call"""
+        import numpy as np
+        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
+        return self._check(self.lib.dvbs2gpu_pes_work(self.h, int(stream), C.c_void_p(ts.ctypes.data), ts.size))
+
+    def stats(self, stream=0, slot=-1):
+        st = PesStats()
+        self._check(self.lib.dvbs2gpu_pes_get_stats(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in PesStats._fields_}
+
+    def stream_stats(self, stream=0):
+        st = PesStreamStats()
+        self._check(self.lib.dvbs2gpu_pes_get_stream_stats(self.h, int(stream), C.byref(st)))
+        return dict(packets=int(st.packets), rows_dropped=int(st.rows_dropped), packets_since_start=[int(v) for v in st.packets_since_start])
+
+    def row_table(self, stream=0):
+        """one dict per row of the last call (the fields of dvbs2gpu_pes_row but `reserved`), in input order"""
+        rows = self._rows(self.lib.dvbs2gpu_pes_get_row_table, PesRow, int(stream))
+        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS if k != 'reserved'} for r in rows]
+
+    def row_table_device(self, stream=0):
+        """(device pointer or None, rows): the same table as dvbs2gpu_pes_row records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self.lib.dvbs2gpu_pes_get_row_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
         return p.value, n.value
 
 

@@ -74,20 +74,6 @@ __device__ inline int pcr_look(const uint8_t* __restrict__ ts, int k, const int3
     return pcr_parse(h.afc, b, P);
 }
 
-// exclusive maximum over the threads before this one (-1: none).  wsum: PCR_WG / 64 ints of LDS
-__device__ inline int pcr_block_scan_max(int v, int* wsum) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-    for (int k = 1; k < 64; k <<= 1) { const int t = __shfl_up(inc, k); if (lane >= k && t > inc) inc = t; }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = -1;
-    for (int w = 0; w < wave; ++w) if (wsum[w] > base) base = wsum[w];
-    __syncthreads();
-    const int prev = __shfl_up(inc, 1);
-    return lane && prev > base ? prev : base;
-}
-
 __device__ inline void pcr_flush(PcrCnt* d, const PcrCnt& a) {
     for (int i = 0; i < PCR_KINDS; ++i) if (a.kind[i]) atomicAdd(&d->kind[i], a.kind[i]);
     if (a.accuracy_measured) atomicAdd(&d->accuracy_measured, a.accuracy_measured);
@@ -178,7 +164,7 @@ __global__ void __launch_bounds__(PCR_WG) pcr_kernel(const uint8_t* const* __res
             const PcrState st = before(j, e);
             if (!(st.seen && !rec_di(e) && rec_p(e) == st.last_pcr)) mine = j;
         }
-        int last = pcr_block_scan_max(mine, sh.wsum);            // the last sorted record before j that is not REPEATED
+        int last = ts_block_scan_max(mine, sh.wsum);             // the last sorted record before j that is not REPEATED
         PcrCnt acc = pcr_cnt_zero();
         int acc_slot = -1;
         PcrRow* rows = rows_g + (size_t)s * max_rows;

@@ -1,7 +1,7 @@
-// Shared by the banks that work on transport streams in HBM (tsmon.hip: the TS monitor; psi.hip: the PSI sections; pcr.hip: the PCRs):
+// Shared by the banks that work on transport streams in HBM (tsmon.hip: the TS monitor; psi.hip: the PSI sections; pcr.hip: the PCRs; pes.hip: the PES packets):
 // what a "packet bank" does around its rules.  On the device: the one header read, the one workgroup prefix sum and the contiguous
 // run of items a thread takes ("flags in a mask, scan, scatter").  On the host: the argument table of a call, the count checks,
-// the staging of the single-stream host-buffer entry point and the table getters.  The rules stay in tsmon_rules.h / psi_rules.h / pcr_rules.h.
+// the staging of the single-stream host-buffer entry point and the table getters.  The rules stay in tsmon_rules.h / psi_rules.h / pcr_rules.h / pes_rules.h.
 #pragma once
 #include "bbts_common.h"
 #include "tsmon_rules.h"
@@ -38,6 +38,20 @@ __device__ inline int ts_block_scan(int v, int* wsum, int* total) {
     __syncthreads();                               // wsum may be written again
     *total = sum;
     return base + inc - v;
+}
+
+// exclusive maximum over the threads before this one (-1: none).  wsum: one int of LDS per wave
+__device__ inline int ts_block_scan_max(int v, int* wsum) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+    for (int k = 1; k < 64; k <<= 1) { const int t = __shfl_up(inc, k); if (lane >= k && t > inc) inc = t; }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int base = -1;
+    for (int w = 0; w < wave; ++w) if (wsum[w] > base) base = wsum[w];
+    __syncthreads();
+    const int prev = __shfl_up(inc, 1);
+    return lane && prev > base ? prev : base;
 }
 
 // the contiguous run [*k0, *k1) of n items that this thread of a workgroup of wg takes: ceil(n / wg) items, the last runs shorter or

@@ -1,0 +1,52 @@
+// dvbs2gpu_host::PesBank (include/dvbs2gpu_host.hpp) over a host bank, driven the way a sink handler would, beside a PsiBank that
+// reads the same packets:
+//   pes_host <ts.bin> <packets per call> <max_rows>
+// The PSI bank follows the PAT after the first call; the PES bank takes its watches from the decoded PMTs after the second.  Prints
+// every call's rows, then the counters and the stream counters.
+#include <dvbs2gpu_host.hpp>
+
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <iterator>
+
+int main(int argc, char** argv) {
+    if (argc < 4) { fprintf(stderr, "usage: pes_host ts per_call max_rows\n"); return 2; }
+    std::ifstream fi(argv[1], std::ios::binary);
+    const std::vector<uint8_t> ts((std::istreambuf_iterator<char>(fi)), std::istreambuf_iterator<char>());
+    const int per_call = atoi(argv[2]), max_rows = atoi(argv[3]);
+    try {
+        dvbs2gpu_host::PsiBank psi;
+        dvbs2gpu_host::PesBank pes;
+        if (pes.work(ts.data(), 0) != 0 || pes.status() != DVBS2GPU_ERR_ARG) { fprintf(stderr, "work() before init() must fail quietly\n"); return 4; }
+        pes.clearStatus();
+        psi.initHost(per_call, 64);
+        pes.initHost(per_call, max_rows);
+        pes.setRate((uint64_t)1000 << 24);
+        int calls = 0;
+        for (size_t at = 0; at < ts.size(); at += (size_t)per_call * 188, ++calls) {
+            const int nbytes = (int)std::min<size_t>((size_t)per_call * 188, ts.size() - at);
+            psi.work(ts.data() + at, nbytes, nullptr, 0);
+            const int starts = pes.work(ts.data() + at, nbytes);
+            if (psi.status() != 0 || pes.status() != 0) { fprintf(stderr, "%s%s\n", psi.error().c_str(), pes.error().c_str()); return 5; }
+            printf("call %d starts %d\n", calls, starts);
+            for (const dvbs2gpu_pes_row& r : pes.rowTable())
+                printf("row %d %u %u %u %u %u %d %u %llu %llu %u %u %u %d\n", calls, r.pid, r.slot, r.kind, r.flags, r.stream_id, r.packet, r.declared,
+                       (unsigned long long)r.pts, (unsigned long long)r.dts, r.closed_bytes, r.closed_packets, r.delta_packets, r.delta_ts);
+            if (calls == 0) psi.followPat();
+            if (calls == 1)
+                for (int pid : pes.followPmts(psi)) printf("left %d\n", pid);
+        }
+        const dvbs2gpu_pes_stats s = pes.stats();
+        const int64_t* v = &s.packets;
+        printf("stats");
+        for (size_t i = 0; i < sizeof(s) / sizeof(int64_t); ++i) printf(" %lld", (long long)v[i]);
+        const dvbs2gpu_pes_stream_stats t = pes.streamStats();
+        printf("\nstream %lld %lld since %lld %lld %lld\n", (long long)t.packets, (long long)t.rows_dropped, (long long)t.packets_since_start[0],
+               (long long)t.packets_since_start[1], (long long)t.packets_since_start[2]);
+    } catch (const std::exception& e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 3;
+    }
+    return 0;
+}
