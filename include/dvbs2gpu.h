@@ -1115,6 +1115,116 @@ int dvbs2gpu_pes_get_row_table(dvbs2gpu_pes* b, int stream, dvbs2gpu_pes_row* h_
 /* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
 int dvbs2gpu_pes_get_row_table_device(dvbs2gpu_pes* b, int stream, const dvbs2gpu_pes_row** d_rows, int* n);
 
+/* ------------------------------------------------------------------ T2-MI bank (own extension)
+ * Nothing in the reference does this.  A DVB-S2 carrier may carry a T2-MI stream (ETSI TS 102 773, the DVB-T2 modulator interface) on
+ * one PID of an otherwise empty transport stream; the services lie one level down, in the DVB-T2 BBFRAMEs that the T2-MI packets hold.
+ * For `nstreams` transport streams in HBM a bank reassembles the T2-MI packets of a PID, checks their CRC-32 and packet count, writes
+ * one table row per T2-MI packet and lays the BBFRAMEs of the chosen PLP back to back in a device buffer: with their sizes
+ * (dvbs2gpu_t2mi_get_frame_bytes) these are the d_bb[i], frame_bytes[i] and nframes[i] of dvbs2gpu_bbts_process_ma_batch.  The
+ * sequential form below is the definition (csrc/t2mi_rules.h, T2miHostStream::run); the kernels give its results for every cutting
+ * of a stream into calls.  The syntax is written from memory of TS 102 773; it is one struct, dvbs2gpu_t2mi_layout.
+ *   T2-MI packet: bytes b0..b5, the payload, the CRC.  packet_type = b0, packet_count = b1, superframe_idx = b2 >> 4, t2mi_stream_id =
+ *     b3 & 7 (the 9 bits between are rfu), payload_bits = b4 << 8 | b5.  total = 6 + ((payload_bits + 7) >> 3) + 4 bytes, 10 .. 8202.
+ *     The last four bytes are a CRC-32/MPEG (initial value 0xFFFFFFFF, polynomial 0x04C11DB7) over everything before them: a packet is
+ *     valid when the register over all `total` bytes is 0.  Every 16-bit length is legal: no header is malformed.
+ *   BBFRAME payload (packet_type 0x00): payload byte 0 frame_idx, byte 1 plp_id, byte 2 >> 7 intl_frame_start; the BBFRAME follows from
+ *     payload byte 3 and holds (payload_bits - 24) / 8 bytes.  Well-formed: payload_bits >= 24 + 80, (payload_bits - 24) % 8 == 0 and
+ *     the BBFRAME at most 7274 bytes (Kbch 58 192); otherwise the row has BAD_PAYLOAD and nothing is delivered.
+ *   Watches: 4 slots per stream, each empty or a pair (PID 0..0x1FFE, PLP -1 for every PLP or 0..255).  A new bank watches nothing.
+ *     Unlike the other banks THE SAME PID MAY SIT IN SEVERAL SLOTS of a stream (two PLPs of one feed): every slot is a complete,
+ *     independent reassembler with its own state, counters, rows and output buffer.  Changing a slot's watch starts it afresh.
+ *   Packet: 188 bytes at offset 188 k, classified as the TS monitor does: sync-byte errors, TEI packets and null packets are not looked
+ *     at.  A packet of the slot's PID counts in `packets` and, in this order ("drop" = the open T2-MI packet is forgotten; with fill > 0
+ *     it counts in dropped_packets):
+ *     1. TSC != 0: scrambled_packets, drop, the continuity step; done.
+ *     2. The continuity step (dvbs2gpu_tsmon_*: one state byte per slot).  Duplicate: ignored.  Continuity error or announced
+ *        discontinuity: drop, then go on with this packet.  No payload (AFC&1 = 0): done.
+ *     3. The payload starts at 4, or at 5 + b4 when AFC&2.  >= 188: malformed_packets, drop, done.
+ *     4. PUSI set: ptr = the first payload byte.  ptr > the bytes after it: malformed_packets, drop, done.  The ptr bytes after the
+ *        pointer go to an open packet: if they complete it, it is emitted, and what is left of them is ignored and counts once in
+ *        pointer_slack if not empty; if it is still incomplete after them (an open header of fewer than six bytes too) it is dropped;
+ *        with nothing open they are ignored.  Then packet starts are parsed behind them (6).
+ *     5. PUSI clear: the whole payload goes to an open packet; if it completes it, it is emitted and the rest of the payload is
+ *        ignored.  With nothing open the payload is ignored.
+ *     6. At a packet start, until the TS packet ends: bytes are buffered; with six, total is known; when the buffered bytes reach
+ *        total the packet is emitted and the next byte is a packet start.  There is no stuffing rule: every byte behind a start is a
+ *        header byte.  A packet, or a header of one to five bytes, that the TS packet's end cuts stays open, across calls too.
+ *   Emitting: one row per emitted packet, valid or not; it counts in t2mi_packets.  CRC not zero: flag CRC_ERROR, crc_errors, and
+ *     nothing more of the packet is used (plp_id, frame_idx and bbframe_bytes are 0).  A valid packet steps the packet-count check
+ *     (state per slot: has_count, last_count): with has_count set and packet_count != (last_count + 1) & 255 the row has COUNT_ERROR
+ *     and count_errors counts; then last_count := packet_count.  This runs over all packet types and all t2mi_stream_ids of the PID.
+ *     A valid packet of type 0x00 with a well-formed payload has BBFRAME (and INTL_FRAME_START where that bit is set) and counts in
+ *     bbframes; one with another payload has BAD_PAYLOAD and counts in bad_payload.  A BBFRAME packet is delivered when the call has
+ *     output buffers and the slot's PLP is -1 or equals plp_id: its BBFRAME bytes go to the slot's output buffer, back to back in row
+ *     order, row.offset and row.bbframe_bytes name them, bbframes_delivered and bytes_delivered count.  Every other row has offset -1.
+ *   Row: ordered by the TS packet that held the T2-MI packet's last byte, then by position in it.  One table per (stream, slot).
+ *   Capacity: sizes first.  If a slot's bytes exceed cap or its rows exceed max_rows the call returns DVBS2GPU_ERR_CAPACITY,
+ *     out_bytes[] holds the byte sizes (-1 for a slot whose rows did not fit: its packets were not checked) and out_rows[] the row
+ *     counts; no state or counter of any stream has advanced, the tables of the call are empty, the call can be repeated.
+ *   State survives from call to call.  reset forgets state, positions and counters; watches stay.
+ *   Limits: max_packets <= 4096 per stream and call.  Memory (device banks) per (stream, slot): an 8208-byte packet buffer, 6 bytes per
+ *     packet of max_packets and 52 bytes per row of max_rows. */
+typedef struct dvbs2gpu_t2mi dvbs2gpu_t2mi;
+typedef struct dvbs2gpu_t2mi_layout {
+    int32_t header_bytes, crc_bytes, min_packet_bytes, max_packet_bytes, bbframe_type, bbframe_prefix_bytes, min_bbframe_bytes,
+            max_bbframe_bytes, stream_id_mask;
+} dvbs2gpu_t2mi_layout;
+int dvbs2gpu_t2mi_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_t2mi** out);
+/* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_t2mi_work only */
+int dvbs2gpu_t2mi_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_t2mi** out);
+int dvbs2gpu_t2mi_reset(dvbs2gpu_t2mi* b);
+void dvbs2gpu_t2mi_destroy(dvbs2gpu_t2mi* b);
+int dvbs2gpu_t2mi_get_layout(dvbs2gpu_t2mi_layout* h_out);
+/* slot 0..3; pid 0..0x1FFE, or -1: the slot is empty; plp 0..255, or -1: every PLP */
+int dvbs2gpu_t2mi_set_watch(dvbs2gpu_t2mi* b, int stream, int slot, int pid, int plp);
+/* d_ts[i]: DEVICE pointer to nbytes[i] bytes (a multiple of 188, at most 188*max_packets) of stream i, of any alignment.  d_out NULL:
+ * rows and counters only (never a capacity failure for bytes; out_bytes may be NULL).  Else d_out[i*4 + k]: DEVICE buffer of cap bytes
+ * for the BBFRAMEs of slot k of stream i (NULL for an empty slot); out_bytes[i*4 + k] (host) their bytes.  out_rows[i*4 + k] (host, may
+ * be NULL): the row counts.  Two kernel launches.  Synchronous on `stream`; chained behind a packetiser or monitor call and in front of
+ * dvbs2gpu_bbts_process_ma_batch on the same stream, no packet visits the host. */
+int dvbs2gpu_t2mi_process_batch(dvbs2gpu_t2mi* b, const uint8_t* const* d_ts, const int* nbytes, uint8_t* const* d_out, int cap, int* out_bytes,
+                                int* out_rows, void* stream);
+/* one stream and slot of any bank with HOST buffers (h_out NULL: rows and counters only): returns the bytes written to h_out or a
+ * negative error.  Every other slot of the bank receives an empty call. */
+int dvbs2gpu_t2mi_work(dvbs2gpu_t2mi* b, int stream, int slot, const uint8_t* h_ts, int nbytes, uint8_t* h_out, int cap);
+/* the byte and row sizes that the slot's last call needed, whether it succeeded or failed for capacity */
+int dvbs2gpu_t2mi_get_needed(dvbs2gpu_t2mi* b, int stream, int slot, int* bytes, int* rows);
+typedef struct dvbs2gpu_t2mi_stats {           /* of a slot, since creation, reset or the slot's last set_watch; kept on the host */
+    int64_t packets;                 /* trusted TS packets of the slot's PID */
+    int64_t t2mi_packets;            /* rows */
+    int64_t crc_errors, count_errors;
+    int64_t bbframes, bad_payload;   /* valid packets of type 0x00 with a well-formed / another payload */
+    int64_t bbframes_delivered, bytes_delivered;
+    int64_t dropped_packets;         /* open T2-MI packets forgotten */
+    int64_t malformed_packets, scrambled_packets;   /* TS packets */
+    int64_t pointer_slack;           /* PUSI packets whose pointer bytes went on behind the end of the packet they completed */
+} dvbs2gpu_t2mi_stats;
+/* slot -1: the sum over the stream's slots */
+int dvbs2gpu_t2mi_get_stats(dvbs2gpu_t2mi* b, int stream, int slot, dvbs2gpu_t2mi_stats* h_out);
+#define DVBS2GPU_T2MI_CRC_ERROR 1
+#define DVBS2GPU_T2MI_COUNT_ERROR 2
+#define DVBS2GPU_T2MI_BBFRAME 4
+#define DVBS2GPU_T2MI_INTL_FRAME_START 8
+#define DVBS2GPU_T2MI_BAD_PAYLOAD 16
+typedef struct dvbs2gpu_t2mi_row {             /* 32 bytes */
+    uint8_t packet_type, packet_count, superframe_idx, stream_id;
+    uint16_t flags;
+    uint8_t plp_id, frame_idx;       /* of a valid packet of type 0x00 with payload_bits >= 24, else 0 */
+    uint32_t payload_bits;
+    int32_t length;                  /* total bytes */
+    int32_t offset;                  /* of the BBFRAME in the slot's output buffer; -1: not delivered */
+    int32_t bbframe_bytes;           /* of a BBFRAME row, delivered or not; else 0 */
+    int32_t first_packet;            /* index in this call of the TS packet that held its first byte; -1: an earlier call */
+    int32_t last_packet;             /* and of the one that held its last byte */
+} dvbs2gpu_t2mi_row;
+/* h_rows[cap] (host); *n = rows of the slot's last call, of which min(*n, cap) are written */
+int dvbs2gpu_t2mi_get_row_table(dvbs2gpu_t2mi* b, int stream, int slot, dvbs2gpu_t2mi_row* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_t2mi_get_row_table_device(dvbs2gpu_t2mi* b, int stream, int slot, const dvbs2gpu_t2mi_row** d_rows, int* n);
+/* h_sizes[cap] (host): the sizes of the BBFRAMEs that the slot's last call delivered, in order; *n = how many there are.  With the
+ * slot's output buffer: d_bb[i], frame_bytes[i] and nframes[i] of dvbs2gpu_bbts_process_ma_batch. */
+int dvbs2gpu_t2mi_get_frame_bytes(dvbs2gpu_t2mi* b, int stream, int slot, int* h_sizes, int cap, int* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace dvbs2gpu_host {
@@ -813,6 +814,96 @@ private:
     std::shared_ptr<Engine> eng;
     dvbs2gpu_pes* h = nullptr;
     int watched[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // slot -> PID, as setWatch left them
+    int status_ = 0;
+    std::string error_;
+};
+/* T2-MI bank for one transport stream (dvbs2gpu_t2mi_*, include/dvbs2gpu.h; an extension): the T2-MI packets of a PID behind
+ * BBFrameTSParser or TSMonitor are reassembled and checked, and the DVB-T2 BBFRAMEs of the chosen PLP laid back to back for a second
+ * BBFrameTSParser in mode-adaptation mode (feed()).  Four slots, each a (PID, PLP) pair and a reassembler of its own.  init() (a device
+ * bank) or initHost() (the library's host implementation, no device) and the setters throw; work() sits in the data path and does NOT
+ * throw: a failing call returns 0 and leaves its code in status() and its text in error(), sticky until clearStatus(). */
+class T2miBank {
+public:
+    T2miBank() {}
+    ~T2miBank() {
+        if (h) dvbs2gpu_t2mi_destroy(h);
+    }
+    T2miBank(const T2miBank&) = delete;
+    T2miBank& operator=(const T2miBank&) = delete;
+
+    void init(int max_packets, int max_rows, int device = 0) {
+        release();
+        eng = Engine::get(device);
+        check(dvbs2gpu_t2mi_create(eng->ctx, 1, max_packets, max_rows, &h));
+    }
+    void initHost(int max_packets, int max_rows) {
+        release();
+        check(dvbs2gpu_t2mi_create_host(1, max_packets, max_rows, &h));
+    }
+    void reset() { check(dvbs2gpu_t2mi_reset(need())); }
+    /* slot 0..3; pid -1 empties the slot; plp -1: every PLP.  The same PID may sit in several slots. */
+    void setWatch(int slot, int pid, int plp = -1) { check(dvbs2gpu_t2mi_set_watch(need(), 0, slot, pid, plp)); }
+    /* nbytes of whole TS packets in for one slot; bbframes (buffer_outsize bytes; nullptr: rows and counters only) receives the
+     * slot's BBFRAMEs back to back; returns their bytes, 0 on failure (see status(); on DVBS2GPU_ERR_CAPACITY needed() has the sizes
+     * and nothing was consumed) */
+    int work(int slot, const uint8_t* ts, int nbytes, uint8_t* bbframes, int buffer_outsize) noexcept {
+        const int n = h ? dvbs2gpu_t2mi_work(h, 0, slot, ts, nbytes, bbframes, buffer_outsize) : DVBS2GPU_ERR_ARG;
+        if (n >= 0) return n;
+        if (status_ == 0) {
+            status_ = n;
+            try { error_ = h ? dvbs2gpu_last_error() : "T2miBank used before init()"; } catch (...) {}
+        }
+        return 0;
+    }
+    int status() const { return status_; }
+    const std::string& error() const { return error_; }
+    void clearStatus() { status_ = 0; error_.clear(); }
+    /* {bytes, rows} that the slot's last work() needed */
+    std::pair<int, int> needed(int slot) {
+        int b = 0, r = 0;
+        check(dvbs2gpu_t2mi_get_needed(need(), 0, slot, &b, &r));
+        return {b, r};
+    }
+
+    dvbs2gpu_t2mi_stats stats(int slot = -1) {
+        dvbs2gpu_t2mi_stats s;
+        check(dvbs2gpu_t2mi_get_stats(need(), 0, slot, &s));
+        return s;
+    }
+    /* one row per T2-MI packet of the slot's last work(), in row order */
+    std::vector<dvbs2gpu_t2mi_row> rowTable(int slot) {
+        int n = 0;
+        check(dvbs2gpu_t2mi_get_row_table(need(), 0, slot, nullptr, 0, &n));
+        std::vector<dvbs2gpu_t2mi_row> rows((size_t)n);
+        if (n > 0) check(dvbs2gpu_t2mi_get_row_table(h, 0, slot, rows.data(), n, &n));
+        return rows;
+    }
+    /* the sizes of the BBFRAMEs that the slot's last work() delivered, in order */
+    std::vector<int> frameBytes(int slot) {
+        int n = 0;
+        check(dvbs2gpu_t2mi_get_frame_bytes(need(), 0, slot, nullptr, 0, &n));
+        std::vector<int> sizes((size_t)n);
+        if (n > 0) check(dvbs2gpu_t2mi_get_frame_bytes(h, 0, slot, sizes.data(), n, &n));
+        return sizes;
+    }
+    /* the BBFRAMEs that the slot's last work() wrote to `bbframes` into the mode-adaptation work() of `parser` (after its
+     * setFrameSize() and setModeAdaptation()): tsframes[8], out_bytes[8], needed[8] as there; false: buffer_outsize was too small */
+    bool feed(int slot, dvbs2::BBFrameTSParser& parser, uint8_t* bbframes, uint8_t* const* tsframes, int buffer_outsize, int* out_bytes, int* needed8 = nullptr) {
+        const std::vector<int> sizes = frameBytes(slot);
+        return parser.work(bbframes, sizes.data(), (int)sizes.size(), tsframes, buffer_outsize, out_bytes, needed8);
+    }
+
+private:
+    void release() {
+        if (h) dvbs2gpu_t2mi_destroy(h);
+        h = nullptr;
+    }
+    dvbs2gpu_t2mi* need() {
+        if (!h) throw std::runtime_error("dvbs2gpu: T2miBank used before init()");
+        return h;
+    }
+    std::shared_ptr<Engine> eng;
+    dvbs2gpu_t2mi* h = nullptr;
     int status_ = 0;
     std::string error_;
 };
