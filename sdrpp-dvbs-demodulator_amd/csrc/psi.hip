@@ -1,23 +1,12 @@
 // PSI section bank (own extension; include/dvbs2gpu.h): PAT / PMT / SI section reassembly with CRC-32 on up to 16
 // watched PIDs of each of `nstreams` transport streams in HBM.  Every rule is in psi_rules.h, whose PsiHostStream is the sequential
-// definition, the host bank and the kernels' yardstick; this file says how a call's packets are cut into independent pieces.
-//
-// What makes the parallel form possible: a section STARTS only behind the pointer field of a PUSI packet (a packet without PUSI only
-// continues an open section and ignores what is left), so all section boundaries of a packet chain from its own pointer and the
-// chain never leaves the packet; only the LAST section of a PUSI packet can reach into later packets, and it ends at the latest in
-// the pointer bytes of the slot's next PUSI packet.
+// definition, the host bank and the kernels' yardstick.  How a call's packets are cut into independent pieces -- why that is possible,
+// the packet list, the section walkers and the row numbering -- is ts_reasm.h with the format PsiFmt below (the T2-MI bank, t2mi.hip,
+// is its other user); this file holds what is the bank's own.
 //
 //   psi_scan_kernel    one workgroup per stream.
-//     A  every packet's header is read once (ts_load_header, ts_bank.h) and its PID matched against the 16 watch entries; the
-//        watched packets are compacted in input order into LDS (an exact prefix sum over a contiguous run of packets per thread),
-//        with payload start and pointer byte.
-//     B  one lane per slot takes the continuity steps of its packets in order (tsmon_step, from the slot's state byte) and classes
-//        each: SKIP (duplicate, no payload), CUT (drops an open section and brings nothing), CONT, PUSI, PUSI after a break.
-//     C  one lane per PUSI packet hops from section header to section header inside its packet and follows the section that the
-//        packet's end cuts through the slot's next packets until it is complete, dropped or the call ends; one lane per slot does
-//        the same for the section carried in from the last call.  A first pass counts the rows every packet ends (at most one
-//        carried section, then its own), a prefix sum in input order numbers them -- the row order of the rules -- and the second
-//        pass writes one record (first packet, offset, last packet, bytes) per row.
+//     A-C  ts_reasm.h: the packets of the 16 watched PIDs into LDS, one lane per slot for the continuity walk, one lane per PUSI packet
+//        and per carried-in section for the sections, one record (first packet, offset, last packet, bytes) per row.
 //     D  one wave per row gathers the section's pieces into LDS, each lane takes the CRC of 64 bytes from a zero register
 //        (crc32m_byte), the lanes' registers are shifted to the section's end (crc32m_mulmod, crc32m_xpow) and summed; the row's
 //        fields come from the gathered bytes.
@@ -27,7 +16,7 @@
 //     row gathers the section and stores it at its offset, a dword per lane where the destination allows; then the open section
 //     goes to the slot's 4 KiB buffer and the slots' new states are stored.
 // Two launches per call, one device-to-host copy of the per-stream call record (PsiCall), and one small copy per changed PAT / PMT.
-#include "ts_bank.h"
+#include "ts_reasm.h"
 #include "psi_rules.h"
 
 #include <memory>
@@ -42,25 +31,27 @@ constexpr int PSI_WG = 256, PSI_WAVES = PSI_WG / 64;
 constexpr int PSI_SEC_LDS = PSI_BUF + PSI_BUF / 64 * 4;    // a gathered section, 4 bytes of padding behind every 64: lane L's chunk starts in bank 17 L
 static_assert(sizeof(PsiRow) == sizeof(dvbs2gpu_psi_section) && sizeof(PsiRow) == 24, "row layout");
 static_assert(sizeof(PsiLayout) == sizeof(dvbs2gpu_psi_layout), "layout layout");
-static_assert(PSI_MAX_PACKETS <= 32 * PSI_WG, "psi_collect keeps a thread's match flags in one 32-bit mask (ts_thread_run)");
+static_assert(PSI_MAX_PACKETS <= 32 * PSI_WG, "reasm_collect keeps a thread's match flags in one 32-bit mask (ts_thread_run)");
 static_assert(sizeof(PsiProgram) == sizeof(dvbs2gpu_psi_program) && sizeof(PsiEs) == sizeof(dvbs2gpu_psi_es), "view rows");
 static_assert(sizeof(PsiPatHeader) == sizeof(dvbs2gpu_psi_pat) && sizeof(PsiPmtHeader) == sizeof(dvbs2gpu_psi_pmt), "view headers");
 
-enum { PK_SKIP = 0, PK_CUT, PK_CONT, PK_PUSI, PK_PUSI_BRK };
 enum { C_PACKETS = 0, C_SECTIONS, C_VALID, C_CHANGED, C_CRC, C_DROPPED, C_MALSEC, C_MALPKT, C_SCR, C_UNEXP, C_BYTES };
 static_assert(sizeof(PsiCnt) == PSI_NCNT * sizeof(int32_t) && C_BYTES == PSI_NCNT - 1, "counter order");
 
 struct PsiDevSlot { uint32_t last4; uint16_t fill; uint8_t cont, has_last; };
-// a section of the call: its first byte at offset `at` of watched packet j0 (j0 -1: carried in, the slot's buffer comes first), its
-// last byte in watched packet j1.  As the open section of a slot: j0 -2 none
-struct PsiRec { int32_t j0, j1; uint16_t at, slot; int32_t total; };
+// the section format of ts_reasm.h: 16 slots per workgroup, a 3-byte header with the length in bytes 1 and 2, stuffing 0xFF; a bad
+// length and a long-syntax section too short for its header and CRC are malformed sections
+struct PsiFmt {
+    typedef PsiDevSlot State;
+    static constexpr int WG = PSI_WG, SLOTS = PSI_SLOTS, BUF = PSI_BUF, HEADER = PSI.header_bytes, LEN_A = 1, LEN_B = 2, STUFFING = 0xFF;
+    static constexpr int NCNT = PSI_NCNT, C_DROPPED = s2::C_DROPPED, C_BAD_UNIT = C_MALSEC, C_SLACK = -1;
+    __device__ static int total(unsigned b1, unsigned b2) { const int n = psi_section_length(b1, b2); return n > PSI.max_section_length ? -1 : PSI.header_bytes + n; }
+    __device__ static bool is_row(unsigned b1, int total) { return !((b1 >> 7) && total < PSI.min_long_section); }
+};
+typedef ReasmRec PsiRec;
+typedef ReasmView<PsiFmt> PsiView;
 struct PsiCall { int32_t needed, nrows, watched, pad; uint16_t view_len[PSI_SLOTS]; PsiCnt cnt[PSI_SLOTS]; };
 
-// a watched packet in LDS.  wa: index k bits 0-12, slot 13-16, class 17-19 (after the walk); before it CC 20-23, AFC 24-25, DI 26,
-// PUSI 27, scrambled 28.  wb: payload start (188: none) | pointer byte << 8
-__device__ inline int wa_k(unsigned e) { return (int)(e & 0x1fff); }
-__device__ inline int wa_slot(unsigned e) { return (int)(e >> 13 & 15); }
-__device__ inline int wa_kind(unsigned e) { return (int)(e >> 17 & 7); }
 __device__ inline int psi_sx(int i) { return i + (i >> 6) * 4; }
 
 __device__ inline int psi_match(const TsmonHdr& h, const PsiWatch* w) {
@@ -69,148 +60,19 @@ __device__ inline int psi_match(const TsmonHdr& h, const PsiWatch* w) {
     return -1;
 }
 
-struct PsiView {                                 // what the section walkers read of one stream
-    const uint8_t* ts; const unsigned* wa; const uint16_t* wb; int W;
-    const uint8_t* sbuf;                         // the stream's 16 section buffers
-    const PsiDevSlot* ss;                        // the slots' states before the call
-};
-struct PsiOut {
-    int* rc; PsiRec* rec; PsiRec* open; PsiDevSlot* nss; int (*cnt)[PSI_NCNT]; int max_sections;
-};
-
 // the pieces of section r, in order, into dst (indexed through psi_sx): all 64 lanes of a wave
 __device__ inline void psi_copy_in(uint8_t* dst, int pos, const uint8_t* src, int len, int lane) {
     for (int i = lane; i < len; i += 64) dst[psi_sx(pos + i)] = src[i];
 }
 __device__ void psi_gather(uint8_t* dst, const PsiRec& r, const PsiView& v, int lane) {
-    const int total = r.total < PSI_BUF ? r.total : PSI_BUF;
-    int pos, jn = 0;
-    if (r.j0 < 0) {
-        pos = v.ss[r.slot].fill < total ? v.ss[r.slot].fill : total;
-        psi_copy_in(dst, 0, v.sbuf + (size_t)r.slot * PSI_BUF, pos, lane);
-    } else {
-        pos = TSMON_TS - r.at < total ? TSMON_TS - r.at : total;
-        psi_copy_in(dst, 0, v.ts + (size_t)wa_k(v.wa[r.j0]) * TSMON_TS + r.at, pos, lane);
-        jn = r.j0 + 1;
-    }
-    for (int j = jn; pos < total && j < v.W; ++j) {
-        const unsigned e = v.wa[j];
-        if (wa_slot(e) != r.slot || wa_kind(e) == PK_SKIP) continue;
-        if (wa_kind(e) != PK_CONT && wa_kind(e) != PK_PUSI) break;
-        const int ps = v.wb[j] & 255, lo = wa_kind(e) == PK_PUSI ? ps + 1 : ps, avail = wa_kind(e) == PK_PUSI ? v.wb[j] >> 8 : TSMON_TS - ps;
-        const int len = avail < total - pos ? avail : total - pos;
-        psi_copy_in(dst, pos, v.ts + (size_t)wa_k(e) * TSMON_TS + lo, len, lane);
-        pos += len;
-    }
+    reasm_pieces(r, v, PSI_BUF, [&](int pos, const uint8_t* src, int len) { psi_copy_in(dst, pos, src, len, lane); });
 }
-
-// The open section of `slot` -- `fill` bytes so far, header bytes b1, b2 where fill reaches them, first byte at (j0, at) -- through
-// the slot's packets from watched packet jn on: rules 4 and 5.  One lane.
-template <bool WRITE>
-__device__ void psi_resolve(const PsiView& v, const PsiOut& o, int slot, int j0, int at, int fill, unsigned b1, unsigned b2, int jn) {
-    enum { R_OPEN, R_DONE, R_DROPPED, R_BAD_LENGTH };
-    int outcome = R_OPEN, endj = -1, total = 0;
-    for (int j = jn; j < v.W; ++j) {
-        const unsigned e = v.wa[j];
-        const int kind = wa_kind(e);
-        if (wa_slot(e) != slot || kind == PK_SKIP) continue;
-        if (kind == PK_CUT || kind == PK_PUSI_BRK) { outcome = R_DROPPED; break; }
-        const int ps = v.wb[j] & 255, lo = kind == PK_PUSI ? ps + 1 : ps, avail = kind == PK_PUSI ? v.wb[j] >> 8 : TSMON_TS - ps;
-        const uint8_t* p = v.ts + (size_t)wa_k(e) * TSMON_TS + lo;
-        int used = 0;
-        while (fill < PSI.header_bytes && used < avail) {
-            const unsigned byte = p[used++];
-            if (fill == 1) b1 = byte; else if (fill == 2) b2 = byte;
-            ++fill;
-        }
-        if (fill >= PSI.header_bytes) {
-            if (psi_section_length(b1, b2) > PSI.max_section_length) { outcome = R_BAD_LENGTH; break; }
-            total = PSI.header_bytes + psi_section_length(b1, b2);
-            fill += avail - used < total - fill ? avail - used : total - fill;
-            if (fill == total) { outcome = R_DONE; endj = j; break; }
-        }
-        if (kind == PK_PUSI) { outcome = R_DROPPED; break; }
-    }
-    if (outcome == R_DONE) {
-        const bool row = !((b1 >> 7) && total < PSI.min_long_section);
-        if (!WRITE) { if (row) atomicAdd(&o.rc[endj], 1); }
-        else if (!row) atomicAdd(&o.cnt[slot][C_MALSEC], 1);
-        else {
-            const int r = o.rc[endj] >> 1;
-            if (r < o.max_sections) { const PsiRec rec = {j0, endj, (uint16_t)at, (uint16_t)slot, total}; o.rec[r] = rec; }
-        }
-    } else if (WRITE) {
-        if (outcome == R_DROPPED) atomicAdd(&o.cnt[slot][C_DROPPED], 1);
-        else if (outcome == R_BAD_LENGTH) atomicAdd(&o.cnt[slot][C_MALSEC], 1);
-        else { const PsiRec rec = {j0, v.W, (uint16_t)at, (uint16_t)slot, fill}; o.open[slot] = rec; o.nss[slot].fill = (uint16_t)fill; }
-    }
-}
-
-// watched packet j, a PUSI packet: the section starts behind its pointer (rule 6).  One lane.
-template <bool WRITE>
-__device__ void psi_pusi_job(const PsiView& v, const PsiOut& o, int j) {
-    const unsigned e = v.wa[j];
-    const int slot = wa_slot(e), ps = v.wb[j] & 255, ptr = v.wb[j] >> 8;
-    const uint8_t* p = v.ts + (size_t)wa_k(e) * TSMON_TS;
-    const int base = WRITE ? (o.rc[j] >> 1) + (o.rc[j] & 1) : 0;
-    int at = ps + 1 + ptr, i = 0;
-    while (at < TSMON_TS) {
-        if (p[at] == 0xFF) break;
-        const int have = TSMON_TS - at;
-        const unsigned b1 = have >= 2 ? p[at + 1] : 0, b2 = have >= 3 ? p[at + 2] : 0;
-        if (have >= PSI.header_bytes) {
-            if (psi_section_length(b1, b2) > PSI.max_section_length) { if (WRITE) atomicAdd(&o.cnt[slot][C_MALSEC], 1); break; }
-            const int total = PSI.header_bytes + psi_section_length(b1, b2);
-            if (total <= have) {
-                if ((b1 >> 7) && total < PSI.min_long_section) { if (WRITE) atomicAdd(&o.cnt[slot][C_MALSEC], 1); }
-                else {
-                    if (WRITE && base + i < o.max_sections) { const PsiRec rec = {j, j, (uint16_t)at, (uint16_t)slot, total}; o.rec[base + i] = rec; }
-                    ++i;
-                }
-                at += total;
-                continue;
-            }
-        }
-        psi_resolve<WRITE>(v, o, slot, j, at, have, b1, b2, j + 1);
-        break;
-    }
-    if (!WRITE && i) atomicAdd(&o.rc[j], 2 * i);
-}
-
-template <bool WRITE>
-__device__ void psi_jobs(const PsiView& v, const PsiOut& o, const PsiWatch* w) {
-    for (int t = threadIdx.x; t < v.W + PSI_SLOTS; t += PSI_WG) {
-        if (t < PSI_SLOTS) {
-            const int fill = v.ss[t].fill;
-            if (w[t].pid < 0 || fill <= 0) continue;
-            const uint8_t* sb = v.sbuf + (size_t)t * PSI_BUF;
-            psi_resolve<WRITE>(v, o, t, -1, 0, fill, fill >= 2 ? sb[1] : 0, fill >= 3 ? sb[2] : 0, 0);
-        } else if (wa_kind(v.wa[t - PSI_SLOTS]) >= PK_PUSI) psi_pusi_job<WRITE>(v, o, t - PSI_SLOTS);
-    }
-}
-
-// phase A of both kernels: the watched packets of the stream into wa / wb, in input order; returns their number
-__device__ int psi_collect(const uint8_t* __restrict__ ts, int n, const PsiWatch* w, unsigned* wa, uint16_t* wb, int* wsum) {
-    int k0, k1; ts_thread_run(n, PSI_WG, &k0, &k1);              // <= 16 packets per thread
-    unsigned mask = 0;
-    for (int k = k0; k < k1; ++k) mask |= (unsigned)(psi_match(ts_load_header(ts, k), w) >= 0) << (k - k0);
-    int W;
-    int at = ts_block_scan<PSI_WG>(__popc(mask), wsum, &W);
-    for (int k = k0; k < k1; ++k) {
-        if (!(mask >> (k - k0) & 1)) continue;
-        unsigned b4;
-        const TsmonHdr h = ts_load_header(ts, k, &b4);
-        int ps = psi_payload_start(h.afc, b4);
-        if (ps > TSMON_TS) ps = TSMON_TS;
-        const unsigned ptr = (h.pusi && (h.afc & 1) && ps < TSMON_TS) ? ts[(size_t)k * TSMON_TS + ps] : 0;
-        wa[at] = (unsigned)k | (unsigned)psi_match(h, w) << 13 | (unsigned)h.cc << 20 | (unsigned)h.afc << 24 | (unsigned)h.di << 26 |
-                 (unsigned)h.pusi << 27 | (unsigned)(h.tsc != 0) << 28;
-        wb[at] = (uint16_t)(ps | ptr << 8);
-        ++at;
-    }
-    __syncthreads();
-    return W;
-}
+// a gathered section as the source of ts_wave_copy
+struct PsiLdsBytes {
+    const uint8_t* sb;
+    __device__ unsigned u8(int i) const { return sb[psi_sx(i)]; }
+    __device__ unsigned u32(int i) const { return u8(i) | u8(i + 1) << 8 | u8(i + 2) << 16 | u8(i + 3) << 24; }
+};
 
 // dynamic LDS: wa[max_packets] (dwords), rc[max_packets] (dwords), wb[max_packets] (16 bits each)
 __global__ void __launch_bounds__(PSI_WG) psi_scan_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nbytes, int max_packets,
@@ -241,53 +103,29 @@ __global__ void __launch_bounds__(PSI_WG) psi_scan_kernel(const uint8_t* const* 
     }
     __syncthreads();
     const uint8_t* ts = in[s];
-    const int W = n > 0 ? psi_collect(ts, n, w, wa, wb, wsum) : 0;
+    const int W = n > 0 ? reasm_collect<PSI_WG>(ts, n, [&](const TsmonHdr& h) { return psi_match(h, w); }, wa, wb, wsum) : 0;
     // B: the continuity walk, one lane per slot
     if (tid < PSI_SLOTS && w[tid].pid >= 0) {
         uint8_t st = ss[tid].cont;
-        int c_pk = 0, c_scr = 0, c_mal = 0;
-        for (int j = 0; j < W; ++j) {
-            const unsigned e = wa[j];
-            if (wa_slot(e) != tid) continue;
-            const int cc = e >> 20 & 15, afc = e >> 24 & 3, di = e >> 26 & 1, pusi = e >> 27 & 1, ps = wb[j] & 255, ptr = wb[j] >> 8;
-            int kind;
-            ++c_pk;
-            const int v = tsmon_step(&st, afc, cc, di);
-            const bool brk = v == TSMON_CC_ERROR || v == TSMON_DISC;
-            if (e >> 28 & 1) { ++c_scr; kind = PK_CUT; }
-            else if (v == TSMON_DUPLICATE) kind = PK_SKIP;
-            else if (!(afc & 1)) kind = brk ? PK_CUT : PK_SKIP;
-            else if (ps >= TSMON_TS || (pusi && ptr > TSMON_TS - ps - 1)) { ++c_mal; kind = PK_CUT; }
-            else if (pusi) kind = brk ? PK_PUSI_BRK : PK_PUSI;
-            else kind = brk ? PK_CUT : PK_CONT;
-            wa[j] = (e & 0x1ffffu) | (unsigned)kind << 17;  // (the other slots' lanes read this word for its slot bits only, which stay)
-        }
+        const ReasmWalk c = reasm_classify<PsiFmt>(wa, wb, W, tid, &st);
         nss[tid].cont = st;
         nss[tid].fill = 0;
-        cnt[tid][C_PACKETS] = c_pk; cnt[tid][C_SCR] = c_scr; cnt[tid][C_MALPKT] = c_mal;
+        cnt[tid][C_PACKETS] = c.packets; cnt[tid][C_SCR] = c.scrambled; cnt[tid][C_MALPKT] = c.malformed;
     }
     for (int j = tid; j < W; j += PSI_WG) rc[j] = 0;
     __syncthreads();
     // C: sections
     const PsiView v = {ts, wa, wb, W, bufs + (size_t)s * PSI_SLOTS * PSI_BUF, ss};
     PsiRec* rec = recs + (size_t)s * max_sections;
-    const PsiOut o = {rc, rec, opens + (size_t)s * PSI_SLOTS, nss, cnt, max_sections};
-    psi_jobs<false>(v, o, w);
+    const ReasmOut<PsiFmt> o = {rc, rec, opens + (size_t)s * PSI_SLOTS, nss, cnt, max_sections};
+    reasm_jobs<false>(v, o);
     __syncthreads();
-    int nrows;
-    {
-        int j0, j1; ts_thread_run(W, PSI_WG, &j0, &j1);
-        int mine = 0;
-        for (int j = j0; j < j1; ++j) mine += (rc[j] >> 1) + (rc[j] & 1);
-        int run = ts_block_scan<PSI_WG>(mine, wsum, &nrows);
-        for (int j = j0; j < j1; ++j) { const int c = rc[j]; rc[j] = run << 1 | (c & 1); run += (c >> 1) + (c & 1); }
-    }
-    __syncthreads();
+    const int nrows = reasm_number_rows<PSI_WG>(rc, W, wsum);
     const bool fits = nrows <= max_sections;
     PsiRow* rows = rows_g + (size_t)s * max_sections;
     int needed = fits ? 0 : -1;
     if (fits) {
-        psi_jobs<true>(v, o, w);
+        reasm_jobs<true>(v, o);
         __syncthreads();
         // D: a wave per row
         for (int r0 = 0; r0 < nrows; r0 += PSI_WAVES) {
@@ -409,21 +247,7 @@ __global__ void __launch_bounds__(PSI_WG) psi_commit_kernel(const uint8_t* const
         if (off < 0 || off + total > cap) off = -1;
         if (off >= 0) psi_gather(sec[wave], rec[r], v, lane);
         __syncthreads();
-        if (off >= 0) {
-            uint8_t* d = o + off;
-            const uint8_t* sb = sec[wave];
-            int head = (int)((4 - (reinterpret_cast<uintptr_t>(d) & 3)) & 3);
-            if (head > total) head = total;
-            const int nd = (total - head) / 4;
-            if (lane < head) d[lane] = sb[psi_sx(lane)];
-            for (int i = lane; i < nd; i += 64) {
-                const int b = head + 4 * i;
-                *reinterpret_cast<unsigned*>(d + b) = (unsigned)sb[psi_sx(b)] | (unsigned)sb[psi_sx(b + 1)] << 8 | (unsigned)sb[psi_sx(b + 2)] << 16 |
-                                                      (unsigned)sb[psi_sx(b + 3)] << 24;
-            }
-            const int tail = head + 4 * nd;
-            if (lane < total - tail) d[tail + lane] = sb[psi_sx(tail + lane)];
-        }
+        if (off >= 0) ts_wave_copy(o + off, PsiLdsBytes{sec[wave]}, total, lane);
         __syncthreads();
     }
     // the open sections into the slots' buffers (what they read of the buffers is in LDS before the barrier), then the states

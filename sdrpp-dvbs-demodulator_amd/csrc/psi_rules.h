@@ -8,8 +8,7 @@
 // code relies on is a field of PsiLayout, reported through dvbs2gpu_psi_get_layout and compared with the tests' model.
 // Standard headers only: the host tests compile this file with a plain C++ compiler.
 #pragma once
-#include "bbts_rules.h"
-#include "tsmon_rules.h"
+#include "ts_reasm_rules.h"
 
 #include <cstring>
 #include <vector>
@@ -50,31 +49,19 @@ struct PsiRow {
     int32_t length, offset, first_packet;
 };
 
-#ifdef __HIPCC__
-#define PSI_HD __host__ __device__
-#else
-#define PSI_HD
-#endif
-
 // section_length from the second and third header byte; the section's bytes are PSI.header_bytes more
-PSI_HD inline int psi_section_length(unsigned b1, unsigned b2) { return (int)((b1 << 8 | b2) & (unsigned)PSI.length_mask); }
-// the payload's first byte: 4, or 5 + adaptation_field_length; >= 188 is malformed
-PSI_HD inline int psi_payload_start(int afc, unsigned b4) { return (afc & 2) ? 5 + (int)b4 : 4; }
-// CRC-32/MPEG of a whole section from the initial value 0xFFFFFFFF: 0 for an intact one
-PSI_HD inline uint32_t psi_crc(const uint8_t* b, int n) {
-    uint32_t c = 0xFFFFFFFFu;
-    for (int i = 0; i < n; ++i) c = crc32m_byte(c, b[i]);
-    return c;
-}
+TS_HD inline int psi_section_length(unsigned b1, unsigned b2) { return (int)((b1 << 8 | b2) & (unsigned)PSI.length_mask); }
+// ts_payload_start under the name that the stand-alone test program of these rules calls
+inline int psi_payload_start(int afc, unsigned b4) { return ts_payload_start(afc, b4); }
 // the last four bytes, big-endian; of a shorter section all its bytes
-PSI_HD inline uint32_t psi_last4(const uint8_t* b, int n) {
+TS_HD inline uint32_t psi_last4(const uint8_t* b, int n) {
     uint32_t v = 0;
     for (int i = n < 4 ? 0 : n - 4; i < n; ++i) v = v << 8 | b[i];
     return v;
 }
 // the row of an emitted section from its bytes (flags: PSI_CRC_ERROR only, offset -1); rd(i): byte i
 template <typename Rd>
-PSI_HD inline PsiRow psi_row_fields(Rd rd, int total, int pid, bool valid, int first_packet) {
+TS_HD inline PsiRow psi_row_fields(Rd rd, int total, int pid, bool valid, int first_packet) {
     PsiRow r = {(uint16_t)pid, (uint16_t)(valid ? 0 : PSI_CRC_ERROR), (uint8_t)rd(0), (uint8_t)(rd(1) >> 7), 0, 0, 0, 0, 0, total, -1, first_packet};
     if (r.ssi) {                                           // total >= PSI.min_long_section
         r.table_id_ext = (uint16_t)(rd(PSI.ext_at) << 8 | rd(PSI.ext_at + 1));
@@ -84,7 +71,7 @@ PSI_HD inline PsiRow psi_row_fields(Rd rd, int total, int pid, bool valid, int f
     return r;
 }
 // a valid changed section that the host keeps as the slot's decoded view: a current PAT or PMT
-PSI_HD inline bool psi_is_view(const PsiRow& r) {
+TS_HD inline bool psi_is_view(const PsiRow& r) {
     return (r.flags & PSI_CHANGED) && r.ssi && (r.table_id == 0 || r.table_id == 2) && r.current_next;
 }
 
@@ -161,7 +148,7 @@ struct PsiHostStream {
         if ((b[1] >> 7) && total < PSI.min_long_section) { ++cnt[s].malformed_sections; return; }
         ++cnt[s].sections;
         if (watch[s].expect >= 0 && b[0] != watch[s].expect) ++cnt[s].unexpected_table_id;
-        const bool valid = !(b[1] >> 7) || psi_crc(b, total) == 0;
+        const bool valid = !(b[1] >> 7) || ts_crc32(b, total) == 0;
         PsiRow r = psi_row_fields([&](int i) { return (unsigned)b[i]; }, total, watch[s].pid, valid, sl.first_packet);
         if (!valid) ++cnt[s].crc_errors;
         else {
@@ -205,39 +192,23 @@ struct PsiHostStream {
         *used = i;
         return st;
     }
+    // what the shared packet loop asks of a format (ts_reasm_rules.h)
+    struct Format {
+        PsiHostStream& h;
+        int slot_of(int pid) const { int s = 0; while (s < PSI_SLOTS && h.watch[s].pid != pid) ++s; return s < PSI_SLOTS ? s : -1; }
+        PsiSlot& state(int s) { return h.slot[s]; }
+        PsiCnt& cnt(int s) { return h.cnt[s]; }
+        void drop(int s) { h.drop(s); }
+        bool feed(int s, const uint8_t* b, int n, int* used, int, bool want_bytes) { return h.feed(s, b, n, used, want_bytes) == DONE; }
+        void begin(int s, int k) { h.slot[s].first_packet = k; }
+        void slack(int) {}
+        bool stuffing(uint8_t b) const { return b == 0xFF; }
+    };
     // one call: n packets.  The caller keeps a copy of `slot` and `view` if the call may have to be undone.
     void run(const uint8_t* ts, int n, bool want_bytes) {
         rows.clear(); bytes.clear();
         for (int s = 0; s < PSI_SLOTS; ++s) { cnt[s] = PsiCnt{}; view_new[s] = false; slot[s].first_packet = -1; }
-        for (int k = 0; k < n; ++k) {
-            const uint8_t* p = ts + (size_t)k * TSMON_TS;
-            const TsmonHdr h = tsmon_parse(p);
-            if (h.cls != TSMON_DATA) continue;
-            int s = 0;
-            while (s < PSI_SLOTS && watch[s].pid != h.pid) ++s;
-            if (s == PSI_SLOTS) continue;
-            PsiSlot& sl = slot[s];
-            ++cnt[s].packets;
-            if (h.tsc) { ++cnt[s].scrambled_packets; drop(s); tsmon_step(&sl.cont, h.afc, h.cc, h.di); continue; }
-            const int v = tsmon_step(&sl.cont, h.afc, h.cc, h.di);
-            if (v == TSMON_DUPLICATE) continue;
-            if (v == TSMON_CC_ERROR || v == TSMON_DISC) drop(s);
-            if (!(h.afc & 1)) continue;
-            const int ps = psi_payload_start(h.afc, p[4]);
-            if (ps >= TSMON_TS) { ++cnt[s].malformed_packets; drop(s); continue; }
-            int used;
-            if (!h.pusi) {
-                if (sl.fill > 0) feed(s, p + ps, TSMON_TS - ps, &used, want_bytes);
-                continue;
-            }
-            const int ptr = p[ps];
-            if (ptr > TSMON_TS - ps - 1) { ++cnt[s].malformed_packets; drop(s); continue; }
-            if (sl.fill > 0 && feed(s, p + ps + 1, ptr, &used, want_bytes) == OPEN) drop(s);
-            for (int at = ps + 1 + ptr; at < TSMON_TS && p[at] != 0xFF; at += used) {
-                sl.first_packet = k;
-                if (feed(s, p + at, TSMON_TS - at, &used, want_bytes) != DONE) break;
-            }
-        }
+        ts_reasm_run(Format{*this}, ts, n, want_bytes);
     }
 };
 

@@ -1,20 +1,14 @@
 // T2-MI bank (own extension; include/dvbs2gpu.h): the T2-MI packets of a PID of each of `nstreams` transport streams
 // in HBM, reassembled, checked (CRC-32, packet count) and the BBFRAMEs of the chosen PLP laid back to back for the mode-adaptation
 // packetiser.  Every rule is in t2mi_rules.h, whose T2miHostStream is the sequential definition, the host bank and the kernels'
-// yardstick; this file says how a call's packets are cut into independent pieces.
-//
-// What makes the parallel form possible is the section bank's observation (psi.hip): a T2-MI packet STARTS only behind the pointer
-// field of a PUSI packet, so the chain of headers of a TS packet starts at its own pointer and never leaves it; only the LAST T2-MI
-// packet begun in a PUSI packet reaches into later TS packets, at most to the pointer bytes of the slot's next PUSI packet.
+// yardstick.  How a call's packets are cut into independent pieces -- why that is possible, the packet list, the walkers and the row
+// numbering -- is ts_reasm.h with the format T2Fmt below (the section bank, psi.hip, is its other user); this file holds what is the
+// bank's own.
 //
 //   t2mi_scan_kernel    one workgroup per (stream, slot): the slots are independent reassemblers, an empty one returns at once, and
 //                       a slot sees one PID, so there is no sort by slot.
-//     A  every header is read once (ts_load_header) and the slot's packets are compacted in input order into LDS with payload start
-//        and pointer byte.
-//     B  one lane takes the continuity steps in order and classes each packet: SKIP, CUT, CONT, PUSI, PUSI behind a break.
-//     C  one lane per PUSI packet hops from header to header inside its packet and follows the T2-MI packet that the TS packet's end
-//        cuts (a header split after 1 to 5 bytes too) until it is complete, dropped or the call ends; one lane does the same for the
-//        packet carried in.  Count, prefix sum, then one record per row.
+//     A-C  ts_reasm.h: the slot's packets into LDS, one lane for the continuity walk, one lane per PUSI packet and one for the packet
+//        carried in (a header split after 1 to 5 bytes too), one record per row.
 //     D  one wave per row: each lane takes the CRC of one PIECE of the packet (its bytes in one TS payload, at most 184; 46 pieces at
 //        8202 bytes, 64 a round) from a zero register, reading the bytes from the TS payloads where they lie (a gathered copy of
 //        4 x 8202 bytes beside the packet list would not leave two workgroups per CU their LDS), the registers are shifted to the
@@ -25,7 +19,7 @@
 //     delivered row copies the BBFRAME's pieces to its offset, a dword per lane behind the unaligned head; then the open packet goes
 //     to the slot's 8208-byte buffer and the state is stored.
 // Two launches per call and one device-to-host copy, of the call record per (stream, slot).
-#include "ts_bank.h"
+#include "ts_reasm.h"
 #include "t2mi_rules.h"
 
 #include <memory>
@@ -39,156 +33,26 @@ constexpr int T2_MAX_PACKETS = 4096;             // per stream and call: 10 byte
 constexpr int T2_WG = 256, T2_WAVES = T2_WG / 64;
 static_assert(sizeof(T2miRow) == sizeof(dvbs2gpu_t2mi_row) && sizeof(T2miRow) == 32, "row layout");
 static_assert(sizeof(T2miLayout) == sizeof(dvbs2gpu_t2mi_layout), "layout layout");
-static_assert(T2_MAX_PACKETS <= 32 * T2_WG, "t2_collect keeps a thread's match flags in one 32-bit mask (ts_thread_run)");
+static_assert(T2_MAX_PACKETS <= 32 * T2_WG, "reasm_collect keeps a thread's match flags in one 32-bit mask (ts_thread_run)");
 static_assert(sizeof(T2miCnt) == T2MI_NCNT * sizeof(int32_t), "counter order");
 static_assert(sizeof(dvbs2gpu_t2mi_stats) == T2MI_NCNT * sizeof(int64_t), "stats order");
 static_assert(T2MI.max_packet_bytes <= T2MI_BUF && T2MI.max_packet_bytes < (1 << 17), "crc32m_xpow takes 17 bits of length");
 
-enum { T2K_SKIP = 0, T2K_CUT, T2K_CONT, T2K_PUSI, T2K_PUSI_BRK };
 enum { T2C_PACKETS = 0, T2C_T2MI, T2C_CRC, T2C_COUNT, T2C_BB, T2C_BADPAY, T2C_DELIVERED, T2C_BYTES, T2C_DROPPED, T2C_MALPKT, T2C_SCR, T2C_SLACK };
 
 struct T2DevSlot { int32_t fill; uint8_t cont, has_count, last_count, pad; };
-// a T2-MI packet of the call: its first byte at offset `at` of the slot's packet j0 (j0 -1: carried in, the slot's buffer comes first),
-// its last byte in the slot's packet j1.  As the open packet of a slot: j0 -2 none, total the bytes so far
-struct T2Rec { int32_t j0, j1, at, total; };
-struct T2Call { int32_t needed, nrows, watched, ndelivered; T2miCnt cnt; };
-
-// a packet of the slot in LDS.  wa: index k bits 0-12, class 13-15 (after the walk); before it CC 16-19, AFC 20-21, DI 22, PUSI 23,
-// scrambled 24.  wb: payload start (188: none) | pointer byte << 8
-__device__ inline int t2_k(unsigned e) { return (int)(e & 0x1fff); }
-__device__ inline int t2_kind(unsigned e) { return (int)(e >> 13 & 7); }
-
-struct T2View {                                  // what the packet walkers read of one (stream, slot)
-    const uint8_t* ts; const unsigned* wa; const uint16_t* wb; int W;
-    const uint8_t* sbuf;                         // the slot's packet buffer
-    int fill0;                                   // its bytes before the call
+// the T2-MI packet format of ts_reasm.h: one slot per workgroup, a 6-byte header with payload_bits in bytes 4 and 5, no stuffing, no
+// bad length, every packet a row; what a PUSI packet's pointer bytes hold beyond the open packet's end is counted
+struct T2Fmt {
+    typedef T2DevSlot State;
+    static constexpr int WG = T2_WG, SLOTS = 1, BUF = T2MI_BUF, HEADER = T2MI.header_bytes, LEN_A = 4, LEN_B = 5, STUFFING = -1;
+    static constexpr int NCNT = T2MI_NCNT, C_DROPPED = T2C_DROPPED, C_BAD_UNIT = -1, C_SLACK = T2C_SLACK;
+    __device__ static int total(unsigned b4, unsigned b5) { return t2mi_total(b4, b5); }
+    __device__ static bool is_row(unsigned, int) { return true; }
 };
-struct T2Out { int* rc; T2Rec* rec; T2Rec* open; T2DevSlot* nss; int* cnt; int max_rows; };
-
-// the pieces of packet r that hold its bytes [0, limit), in order: f(position in the packet, source, bytes)
-template <typename F>
-__device__ inline void t2_pieces(const T2Rec& r, const T2View& v, int limit, F f) {
-    const int total = r.total < limit ? r.total : limit;
-    int pos, jn = 0;
-    if (r.j0 < 0) {
-        pos = v.fill0 < total ? v.fill0 : total;
-        f(0, v.sbuf, pos);
-    } else {
-        pos = TSMON_TS - r.at < total ? TSMON_TS - r.at : total;
-        f(0, v.ts + (size_t)t2_k(v.wa[r.j0]) * TSMON_TS + r.at, pos);
-        jn = r.j0 + 1;
-    }
-    for (int j = jn; pos < total && j < v.W; ++j) {
-        const unsigned e = v.wa[j];
-        const int kind = t2_kind(e);
-        if (kind == T2K_SKIP) continue;
-        if (kind != T2K_CONT && kind != T2K_PUSI) break;
-        const int ps = v.wb[j] & 255, lo = kind == T2K_PUSI ? ps + 1 : ps, avail = kind == T2K_PUSI ? v.wb[j] >> 8 : TSMON_TS - ps;
-        const int len = avail < total - pos ? avail : total - pos;
-        f(pos, v.ts + (size_t)t2_k(e) * TSMON_TS + lo, len);
-        pos += len;
-    }
-}
-
-// The open packet -- `fill` bytes so far, header bytes b4, b5 where fill reaches them, first byte at (j0, at) -- through the slot's
-// packets from jn on: rules 4 and 5.  One lane.
-template <bool WRITE>
-__device__ void t2_resolve(const T2View& v, const T2Out& o, int j0, int at, int fill, unsigned b4, unsigned b5, int jn) {
-    enum { R_OPEN, R_DONE, R_DROPPED };
-    int outcome = R_OPEN, endj = -1, total = 0;
-    bool slack = false;
-    for (int j = jn; j < v.W; ++j) {
-        const unsigned e = v.wa[j];
-        const int kind = t2_kind(e);
-        if (kind == T2K_SKIP) continue;
-        if (kind == T2K_CUT || kind == T2K_PUSI_BRK) { outcome = R_DROPPED; break; }
-        const int ps = v.wb[j] & 255, lo = kind == T2K_PUSI ? ps + 1 : ps, avail = kind == T2K_PUSI ? v.wb[j] >> 8 : TSMON_TS - ps;
-        const uint8_t* p = v.ts + (size_t)t2_k(e) * TSMON_TS + lo;
-        int used = 0;
-        while (fill < T2MI.header_bytes && used < avail) {
-            const unsigned byte = p[used++];
-            if (fill == 4) b4 = byte; else if (fill == 5) b5 = byte;
-            ++fill;
-        }
-        if (fill >= T2MI.header_bytes) {
-            total = t2mi_total(b4, b5);
-            const int take = avail - used < total - fill ? avail - used : total - fill;
-            fill += take; used += take;
-            if (fill == total) { outcome = R_DONE; endj = j; slack = kind == T2K_PUSI && used < avail; break; }
-        }
-        if (kind == T2K_PUSI) { outcome = R_DROPPED; break; }
-    }
-    if (outcome == R_DONE) {
-        if (!WRITE) atomicAdd(&o.rc[endj], 1);
-        else {
-            const int r = o.rc[endj] >> 1;
-            if (r < o.max_rows) { const T2Rec rec = {j0, endj, at, total}; o.rec[r] = rec; }
-            if (slack) atomicAdd(&o.cnt[T2C_SLACK], 1);
-        }
-    } else if (WRITE) {
-        if (outcome == R_DROPPED) atomicAdd(&o.cnt[T2C_DROPPED], 1);
-        else { const T2Rec rec = {j0, v.W, at, fill}; *o.open = rec; o.nss->fill = fill; }
-    }
-}
-
-// the slot's packet j, a PUSI packet: the T2-MI packets that start behind its pointer (rule 6).  One lane.
-template <bool WRITE>
-__device__ void t2_pusi_job(const T2View& v, const T2Out& o, int j) {
-    const unsigned e = v.wa[j];
-    const int ps = v.wb[j] & 255, ptr = v.wb[j] >> 8;
-    const uint8_t* p = v.ts + (size_t)t2_k(e) * TSMON_TS;
-    const int base = WRITE ? (o.rc[j] >> 1) + (o.rc[j] & 1) : 0;
-    int at = ps + 1 + ptr, i = 0;
-    while (at < TSMON_TS) {
-        const int have = TSMON_TS - at;
-        if (have >= T2MI.header_bytes) {
-            const int total = t2mi_total(p[at + 4], p[at + 5]);
-            if (total <= have) {
-                if (WRITE && base + i < o.max_rows) { const T2Rec rec = {j, j, at, total}; o.rec[base + i] = rec; }
-                ++i;
-                at += total;
-                continue;
-            }
-        }
-        t2_resolve<WRITE>(v, o, j, at, have, have >= 5 ? p[at + 4] : 0, have >= 6 ? p[at + 5] : 0, j + 1);
-        break;
-    }
-    if (!WRITE && i) atomicAdd(&o.rc[j], 2 * i);
-}
-
-template <bool WRITE>
-__device__ void t2_jobs(const T2View& v, const T2Out& o) {
-    for (int t = threadIdx.x; t < v.W + 1; t += T2_WG) {
-        if (t == 0) {
-            if (v.fill0 > 0) t2_resolve<WRITE>(v, o, -1, 0, v.fill0, v.fill0 >= 5 ? v.sbuf[4] : 0, v.fill0 >= 6 ? v.sbuf[5] : 0, 0);
-        } else if (t2_kind(v.wa[t - 1]) >= T2K_PUSI) t2_pusi_job<WRITE>(v, o, t - 1);
-    }
-}
-
-// phase A: the slot's packets of the stream into wa / wb, in input order; returns their number
-__device__ int t2_collect(const uint8_t* __restrict__ ts, int n, int pid, unsigned* wa, uint16_t* wb, int* wsum) {
-    int k0, k1; ts_thread_run(n, T2_WG, &k0, &k1);               // <= 16 packets per thread
-    unsigned mask = 0;
-    for (int k = k0; k < k1; ++k) {
-        const TsmonHdr h = ts_load_header(ts, k);
-        mask |= (unsigned)(h.cls == TSMON_DATA && h.pid == pid) << (k - k0);
-    }
-    int W;
-    int at = ts_block_scan<T2_WG>(__popc(mask), wsum, &W);
-    for (int k = k0; k < k1; ++k) {
-        if (!(mask >> (k - k0) & 1)) continue;
-        unsigned b4;
-        const TsmonHdr h = ts_load_header(ts, k, &b4);
-        int ps = t2mi_payload_start(h.afc, b4);
-        if (ps > TSMON_TS) ps = TSMON_TS;
-        const unsigned ptr = (h.pusi && (h.afc & 1) && ps < TSMON_TS) ? ts[(size_t)k * TSMON_TS + ps] : 0;
-        wa[at] = (unsigned)k | (unsigned)h.cc << 16 | (unsigned)h.afc << 20 | (unsigned)h.di << 22 | (unsigned)h.pusi << 23 | (unsigned)(h.tsc != 0) << 24;
-        wb[at] = (uint16_t)(ps | ptr << 8);
-        ++at;
-    }
-    __syncthreads();
-    return W;
-}
+typedef ReasmRec T2Rec;
+typedef ReasmView<T2Fmt> T2View;
+struct T2Call { int32_t needed, nrows, watched, ndelivered; T2miCnt cnt; };
 
 // dynamic LDS: wa[max_packets] (dwords), rc[max_packets] (dwords), wb[max_packets] (16 bits each).  only >= 0: the one (stream, slot)
 // that receives its stream's packets (the single-slot entry point); the others take an empty call
@@ -206,7 +70,7 @@ __global__ void __launch_bounds__(T2_WG) t2mi_scan_kernel(const uint8_t* const* 
         if (tid == 0) {
             T2Call c = {};
             call[g] = c;
-            const T2Rec none = {-2, 0, 0, 0};
+            const T2Rec none = {-2, 0, 0, 0, 0};
             opens[g] = none;
             newst[g] = state[g];
         }
@@ -221,57 +85,35 @@ __global__ void __launch_bounds__(T2_WG) t2mi_scan_kernel(const uint8_t* const* 
     if (tid == 0) {
         nss = ss;
         last_valid = -1;
-        const T2Rec none = {-2, 0, 0, 0};
+        const T2Rec none = {-2, 0, 0, 0, 0};
         opens[g] = none;
     }
     if (tid < T2MI_NCNT) cnt[tid] = 0;
     __syncthreads();
     const uint8_t* ts = in[s];
-    const int W = n > 0 ? t2_collect(ts, n, w.pid, wa, wb, wsum) : 0;
+    const int W = n > 0 ? reasm_collect<T2_WG>(ts, n, [&](const TsmonHdr& h) { return h.cls == TSMON_DATA && h.pid == w.pid ? 0 : -1; }, wa, wb, wsum) : 0;
     // B: the continuity walk, one lane
     if (tid == 0) {
         uint8_t st = ss.cont;
-        int c_scr = 0, c_mal = 0;
-        for (int j = 0; j < W; ++j) {
-            const unsigned e = wa[j];
-            const int cc = e >> 16 & 15, afc = e >> 20 & 3, di = e >> 22 & 1, pusi = e >> 23 & 1, ps = wb[j] & 255, ptr = wb[j] >> 8;
-            int kind;
-            const int v = tsmon_step(&st, afc, cc, di);
-            const bool brk = v == TSMON_CC_ERROR || v == TSMON_DISC;
-            if (e >> 24 & 1) { ++c_scr; kind = T2K_CUT; }
-            else if (v == TSMON_DUPLICATE) kind = T2K_SKIP;
-            else if (!(afc & 1)) kind = brk ? T2K_CUT : T2K_SKIP;
-            else if (ps >= TSMON_TS || (pusi && ptr > TSMON_TS - ps - 1)) { ++c_mal; kind = T2K_CUT; }
-            else if (pusi) kind = brk ? T2K_PUSI_BRK : T2K_PUSI;
-            else kind = brk ? T2K_CUT : T2K_CONT;
-            wa[j] = (e & 0x1fffu) | (unsigned)kind << 13;
-        }
+        const ReasmWalk c = reasm_classify<T2Fmt>(wa, wb, W, 0, &st);
         nss.cont = st;
         nss.fill = 0;
-        cnt[T2C_PACKETS] = W; cnt[T2C_SCR] = c_scr; cnt[T2C_MALPKT] = c_mal;
+        cnt[T2C_PACKETS] = c.packets; cnt[T2C_SCR] = c.scrambled; cnt[T2C_MALPKT] = c.malformed;
     }
     for (int j = tid; j < W; j += T2_WG) rc[j] = 0;
     __syncthreads();
     // C: T2-MI packets
-    const T2View v = {ts, wa, wb, W, bufs + (size_t)g * T2MI_BUF, ss.fill};
+    const T2View v = {ts, wa, wb, W, bufs + (size_t)g * T2MI_BUF, state + g};
     T2Rec* rec = recs + (size_t)g * max_rows;
-    const T2Out o = {rc, rec, opens + g, &nss, cnt, max_rows};
-    t2_jobs<false>(v, o);
+    const ReasmOut<T2Fmt> o = {rc, rec, opens + g, &nss, &cnt, max_rows};
+    reasm_jobs<false>(v, o);
     __syncthreads();
-    int nrows;
-    {
-        int j0, j1; ts_thread_run(W, T2_WG, &j0, &j1);
-        int mine = 0;
-        for (int j = j0; j < j1; ++j) mine += (rc[j] >> 1) + (rc[j] & 1);
-        int run = ts_block_scan<T2_WG>(mine, wsum, &nrows);
-        for (int j = j0; j < j1; ++j) { const int c = rc[j]; rc[j] = run << 1 | (c & 1); run += (c >> 1) + (c & 1); }
-    }
-    __syncthreads();
+    const int nrows = reasm_number_rows<T2_WG>(rc, W, wsum);
     const bool fits = nrows <= max_rows;
     T2miRow* rows = rows_g + (size_t)g * max_rows;
     int needed = fits ? 0 : -1, ndelivered = 0;
     if (fits) {
-        t2_jobs<true>(v, o);
+        reasm_jobs<true>(v, o);
         __syncthreads();
         // D: a wave per row
         for (int r = wave; r < nrows; r += T2_WAVES) {
@@ -284,7 +126,7 @@ __global__ void __launch_bounds__(T2_WG) t2mi_scan_kernel(const uint8_t* const* 
             for (int base = 0;; base += 64) {
                 int idx = 0, ppos = 0, plen = 0;                                   // idx: the same in every lane
                 const uint8_t* psrc = nullptr;
-                t2_pieces(q, v, total, [&](int pos, const uint8_t* src, int len) {
+                reasm_pieces(q, v, total, [&](int pos, const uint8_t* src, int len) {
                     if (idx == base + lane) { ppos = pos; psrc = src; plen = len; }
                     ++idx;
                 });
@@ -302,14 +144,14 @@ __global__ void __launch_bounds__(T2_WG) t2mi_scan_kernel(const uint8_t* const* 
             if (lane == 0) {
                 unsigned long long h8 = 0;
                 unsigned h9 = 0;
-                t2_pieces(q, v, 9, [&](int pos, const uint8_t* src, int len) {
+                reasm_pieces(q, v, 9, [&](int pos, const uint8_t* src, int len) {
                     for (int i = 0; i < len; ++i) {
                         const int at = pos + i;
                         if (at < 8) h8 |= (unsigned long long)src[i] << (8 * at); else h9 = src[i];
                     }
                 });
                 auto rd = [&](int i) { return i < 8 ? (unsigned)(h8 >> (8 * i) & 255) : h9; };
-                rows[r] = t2mi_row_fields(rd, total, x == 0, q.j0 < 0 ? -1 : t2_k(wa[q.j0]), t2_k(wa[q.j1]));
+                rows[r] = t2mi_row_fields(rd, total, x == 0, q.j0 < 0 ? -1 : wa_k(wa[q.j0]), wa_k(wa[q.j1]));
             }
         }
         __syncthreads();
@@ -366,17 +208,6 @@ __global__ void __launch_bounds__(T2_WG) t2mi_scan_kernel(const uint8_t* const* 
     }
 }
 
-// n bytes from s to d, all 64 lanes of a wave: a dword per lane behind d's unaligned head
-__device__ inline void t2_copy(uint8_t* d, const uint8_t* s, int n, int lane) {
-    int head = (int)((4 - (reinterpret_cast<uintptr_t>(d) & 3)) & 3);
-    if (head > n) head = n;
-    const int nd = (n - head) / 4;
-    if (lane < head) d[lane] = s[lane];
-    for (int i = lane; i < nd; i += 64) *reinterpret_cast<unsigned*>(d + head + 4 * i) = *reinterpret_cast<const ts_unaligned_u32*>(s + head + 4 * i);
-    const int tail = head + 4 * nd;
-    if (lane < n - tail) d[tail + lane] = s[tail + lane];
-}
-
 __global__ void __launch_bounds__(T2_WG) t2mi_commit_kernel(const uint8_t* const* __restrict__ in, uint8_t* const* __restrict__ out, int max_packets, int max_rows,
                                                             int cap, T2DevSlot* __restrict__ state, const T2DevSlot* __restrict__ newst,
                                                             uint8_t* __restrict__ bufs, const unsigned* __restrict__ wa_g, const uint16_t* __restrict__ wb_g,
@@ -389,7 +220,7 @@ __global__ void __launch_bounds__(T2_WG) t2mi_commit_kernel(const uint8_t* const
     const T2Rec q = opens[g];
     if (nrows == 0 && q.j0 == -2 && W == 0) return;  // (an empty slot, or an empty call with nothing open: the state is what it was)
     uint8_t* sbuf = bufs + (size_t)g * T2MI_BUF;
-    const T2View v = {in[s], wa_g + (size_t)g * max_packets, wb_g + (size_t)g * max_packets, W, sbuf, state[g].fill};
+    const T2View v = {in[s], wa_g + (size_t)g * max_packets, wb_g + (size_t)g * max_packets, W, sbuf, state + g};
     const T2Rec* rec = recs + (size_t)g * max_rows;
     const T2miRow* rows = rows_g + (size_t)g * max_rows;
     uint8_t* o = out ? out[g] : nullptr;
@@ -397,14 +228,14 @@ __global__ void __launch_bounds__(T2_WG) t2mi_commit_kernel(const uint8_t* const
     for (int r = wave; o && r < nrows; r += T2_WAVES) {
         const int off = rows[r].offset, bb = rows[r].bbframe_bytes;
         if (off < 0 || bb <= 0 || off + bb > cap) continue;
-        t2_pieces(rec[r], v, skip + bb, [&](int pos, const uint8_t* src, int len) {
+        reasm_pieces(rec[r], v, skip + bb, [&](int pos, const uint8_t* src, int len) {
             const int a = pos > skip ? pos : skip, b = pos + len;
-            if (b > a) t2_copy(o + off + (a - skip), src + (a - pos), b - a, lane);
+            if (b > a) ts_wave_copy(o + off + (a - skip), TsBytes{src + (a - pos)}, b - a, lane);
         });
     }
     __syncthreads();                                 // the carried rows have read the buffer
     if (wave == 0 && q.j0 > -2)                      // the open packet: what the buffer holds already (a packet carried in and on) stays where it is
-        t2_pieces(q, v, T2MI_BUF, [&](int pos, const uint8_t* src, int len) {
+        reasm_pieces(q, v, T2MI_BUF, [&](int pos, const uint8_t* src, int len) {
             if (src != sbuf) for (int i = lane; i < len; i += 64) sbuf[pos + i] = src[i];
         });
     if (tid == 0) state[g] = newst[g];
@@ -430,19 +261,13 @@ struct dvbs2gpu_t2mi {
     DevBuf<T2miRow> d_rows;                        // nstreams x 4 x max_rows
     DevBuf<int> d_fb;                              // the sizes of the delivered BBFRAMEs, nstreams x 4 x max_rows
     DevBuf<T2Call> d_call;
-    DevBuf<uint8_t> d_args;                        // input pointers | output pointers (4 per stream) | byte counts
-    Workspace stage_in, stage_out;                 // of the host-buffer entry point
+    DevBuf<uint8_t> d_args;                        // TsBankArgsN<4>(nstreams)
+    TsHostStage stage;                             // of the host-buffer entry point
     // host-only banks
     std::vector<T2miHostStream> host;              // nstreams x 4
 };
 
 namespace s2 {
-// the argument table of a call: n input pointers | 4 n output pointers | n byte counts
-struct T2Args {
-    ScratchLayout L;
-    ScratchPart<const uint8_t*> in; ScratchPart<uint8_t*> out; ScratchPart<int> nbytes;
-    explicit T2Args(size_t n) : in(L.add<const uint8_t*>(n)), out(L.add<uint8_t*>(n * T2MI_SLOTS)), nbytes(L.add<int>(n)) {}
-};
 static void t2_account(dvbs2gpu_t2mi* b, int g, const T2miCnt& c) {
     int64_t* d = reinterpret_cast<int64_t*>(&b->stats[g]);
     const int32_t* a = reinterpret_cast<const int32_t*>(&c);
@@ -470,12 +295,8 @@ static int t2_batch(dvbs2gpu_t2mi* b, const uint8_t* const* d_ts, const int* nby
                     hipStream_t st) {
     const int n = b->nstreams, ns = n * T2MI_SLOTS;
     HIP_TRY(hipSetDevice(b->ctx->device));
-    const T2Args a(n);
-    {
-        const uint8_t** pi = a.in(b->h_args.data()); uint8_t** po = a.out(b->h_args.data()); int* pn = a.nbytes(b->h_args.data());
-        for (int i = 0; i < n; ++i) { pi[i] = d_ts[i]; pn[i] = nbytes[i]; }
-        for (int g = 0; g < ns; ++g) po[g] = d_out ? d_out[g] : nullptr;
-    }
+    const TsBankArgsN<T2MI_SLOTS> a(n);
+    a.fill(b->h_args.data(), n, d_ts, d_out, nbytes);
     HIP_TRY(hipMemcpyAsync(b->d_args, b->h_args.data(), b->h_args.size(), hipMemcpyHostToDevice, st));
     const size_t lds = (size_t)b->max_packets * 10 + 16;               // <= 40 KiB
     hipLaunchKernelGGL(t2mi_scan_kernel, dim3(ns), dim3(T2_WG), lds, st, a.in(b->d_args), a.nbytes(b->d_args), b->max_packets, b->max_rows, only, b->d_watch, b->d_state,
@@ -528,8 +349,8 @@ int dvbs2gpu_t2mi_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int m
     RC_TRY(b->d_rows.alloc(ns * max_rows, false, what));
     RC_TRY(b->d_fb.alloc(ns * max_rows, false, what));
     RC_TRY(b->d_call.alloc(ns, false, what));
-    RC_TRY(b->d_args.alloc(T2Args(n).L.bytes(), false, what));
-    b->h_args.resize(T2Args(n).L.bytes());
+    RC_TRY(b->d_args.alloc(TsBankArgsN<T2MI_SLOTS>(n).L.bytes(), false, what));
+    b->h_args.resize(TsBankArgsN<T2MI_SLOTS>(n).L.bytes());
     *out = b.release();
     return 0;
 }
@@ -629,18 +450,9 @@ int dvbs2gpu_t2mi_work(dvbs2gpu_t2mi* b, int stream, int slot, const uint8_t* h_
         return (int)h.bytes.size();
     }
     HIP_TRY(hipSetDevice(b->ctx->device));
-    if (const int e = b->stage_in.ensure((size_t)b->max_packets * TSMON_TS)) return e;
-    if (nbytes > 0) HIP_TRY(hipMemcpy(b->stage_in.p, h_ts, nbytes, hipMemcpyHostToDevice));
-    if (const int e = h_out ? b->stage_out.ensure((size_t)cap + 4) : 0) return e;
-    const size_t ns = (size_t)b->nstreams * T2MI_SLOTS;
-    std::vector<const uint8_t*> in(b->nstreams, nullptr);
-    std::vector<uint8_t*> out(ns, nullptr);
-    std::vector<int> nb(b->nstreams, 0), ob(ns, 0);
-    in[stream] = static_cast<const uint8_t*>(b->stage_in.p); out[g] = static_cast<uint8_t*>(b->stage_out.p); nb[stream] = nbytes;
-    const int rc = t2_batch(b, in.data(), nb.data(), h_out ? out.data() : nullptr, cap, ob.data(), nullptr, g, nullptr);
-    if (rc < 0) return rc;
-    if (h_out && ob[g] > 0) HIP_TRY(hipMemcpy(h_out, b->stage_out.p, ob[g], hipMemcpyDeviceToHost));
-    return ob[g];
+    return ts_bank_work<T2MI_SLOTS>(b->stage, b->nstreams, stream, h_ts, nbytes, b->max_packets, h_out, cap, false, [&](const uint8_t* const* in, const int* nb, uint8_t* const* out, int* ob) {
+        return t2_batch(b, in, nb, out, cap, ob, nullptr, g, nullptr);
+    }, slot);
 }
 
 /* the byte and row sizes the slot's last call needed, whether it succeeded or failed for capacity (bytes -1: the rows did not fit) */
@@ -662,21 +474,11 @@ int dvbs2gpu_t2mi_get_stats(dvbs2gpu_t2mi* b, int stream, int slot, dvbs2gpu_t2m
 }
 
 int dvbs2gpu_t2mi_get_row_table(dvbs2gpu_t2mi* b, int stream, int slot, dvbs2gpu_t2mi_row* h_rows, int cap, int* n) {
-    if (!t2_slot_ok(b, stream, slot) || !n || cap < 0 || (cap > 0 && !h_rows)) return DVBS2GPU_ERR_ARG;
-    const int g = stream * T2MI_SLOTS + slot;
-    const int k = (*n = b->nrows[g]) < cap ? *n : cap;
-    if (k <= 0) return 0;
-    if (!b->ctx) { memcpy(h_rows, b->host[g].rows.data(), k * sizeof(T2miRow)); return 0; }
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    HIP_TRY(hipMemcpy(h_rows, b->d_rows + (size_t)g * b->max_rows, k * sizeof(T2miRow), hipMemcpyDeviceToHost));
-    return 0;
+    return ts_bank_rows<T2MI_SLOTS>(b, &dvbs2gpu_t2mi::max_rows, stream, h_rows, cap, n, slot);
 }
 
 int dvbs2gpu_t2mi_get_row_table_device(dvbs2gpu_t2mi* b, int stream, int slot, const dvbs2gpu_t2mi_row** d_rows, int* n) {
-    if (!t2_slot_ok(b, stream, slot) || !b->ctx || !n || !d_rows) return DVBS2GPU_ERR_ARG;
-    const int g = stream * T2MI_SLOTS + slot;
-    *n = b->nrows[g]; *d_rows = *n ? reinterpret_cast<const dvbs2gpu_t2mi_row*>(b->d_rows + (size_t)g * b->max_rows) : nullptr;
-    return 0;
+    return ts_bank_rows_device<T2MI_SLOTS>(b, &dvbs2gpu_t2mi::max_rows, stream, d_rows, n, slot);
 }
 
 int dvbs2gpu_t2mi_get_frame_bytes(dvbs2gpu_t2mi* b, int stream, int slot, int* h_sizes, int cap, int* n) {

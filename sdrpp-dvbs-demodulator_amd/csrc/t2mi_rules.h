@@ -7,8 +7,7 @@
 // on is a field of T2miLayout, reported through dvbs2gpu_t2mi_get_layout and compared with the tests' model.
 // Standard headers only: the host tests compile this file with a plain C++ compiler.
 #pragma once
-#include "bbts_rules.h"
-#include "tsmon_rules.h"
+#include "ts_reasm_rules.h"
 
 #include <cstring>
 #include <vector>
@@ -46,25 +45,13 @@ struct T2miRow {
     int32_t length, offset, bbframe_bytes, first_packet, last_packet;
 };
 
-#ifdef __HIPCC__
-#define T2MI_HD __host__ __device__
-#else
-#define T2MI_HD
-#endif
-
 // a T2-MI packet's bytes from the fifth and sixth header byte: header, payload with its pad bits, CRC
-T2MI_HD inline int t2mi_total(unsigned b4, unsigned b5) { return T2MI.header_bytes + (int)(((b4 << 8 | b5) + 7) >> 3) + T2MI.crc_bytes; }
-// the payload's first byte: 4, or 5 + adaptation_field_length; >= 188 is malformed
-T2MI_HD inline int t2mi_payload_start(int afc, unsigned b4) { return (afc & 2) ? 5 + (int)b4 : 4; }
-// CRC-32/MPEG of a whole packet from the initial value 0xFFFFFFFF: 0 for an intact one
-T2MI_HD inline uint32_t t2mi_crc(const uint8_t* b, int n) {
-    uint32_t c = 0xFFFFFFFFu;
-    for (int i = 0; i < n; ++i) c = crc32m_byte(c, b[i]);
-    return c;
-}
+TS_HD inline int t2mi_total(unsigned b4, unsigned b5) { return T2MI.header_bytes + (int)(((b4 << 8 | b5) + 7) >> 3) + T2MI.crc_bytes; }
+// ts_payload_start under the name that the stand-alone test program of these rules calls
+inline int t2mi_payload_start(int afc, unsigned b4) { return ts_payload_start(afc, b4); }
 // the row of an emitted packet from its first nine bytes (total >= 10); rd(i): byte i.  COUNT_ERROR and the offset are the caller's.
 template <typename Rd>
-T2MI_HD inline T2miRow t2mi_row_fields(Rd rd, int total, bool valid, int first_packet, int last_packet) {
+TS_HD inline T2miRow t2mi_row_fields(Rd rd, int total, bool valid, int first_packet, int last_packet) {
     T2miRow r = {(uint8_t)rd(0), (uint8_t)rd(1), (uint8_t)(rd(2) >> 4), (uint8_t)(rd(3) & (unsigned)T2MI.stream_id_mask), (uint16_t)(valid ? 0 : T2MI_CRC_ERROR), 0, 0,
                  (uint32_t)(rd(4) << 8 | rd(5)), total, -1, 0, first_packet, last_packet};
     if (!valid || r.packet_type != T2MI.bbframe_type) return r;
@@ -76,7 +63,7 @@ T2MI_HD inline T2miRow t2mi_row_fields(Rd rd, int total, bool valid, int first_p
     return r;
 }
 // does the slot deliver the BBFRAME of this row
-T2MI_HD inline bool t2mi_delivers(const T2miRow& r, int plp) { return (r.flags & T2MI_BBFRAME) && (plp < 0 || plp == r.plp_id); }
+TS_HD inline bool t2mi_delivers(const T2miRow& r, int plp) { return (r.flags & T2MI_BBFRAME) && (plp < 0 || plp == r.plp_id); }
 
 // ------------------------------------------------------------------------------------------------- the sequential definition
 struct T2miState {
@@ -105,7 +92,7 @@ struct T2miHostStream {
         const uint8_t* b = st.buf;
         const int total = st.fill;
         ++cnt.t2mi_packets;
-        const bool valid = t2mi_crc(b, total) == 0;
+        const bool valid = ts_crc32(b, total) == 0;
         T2miRow r = t2mi_row_fields([&](int i) { return (unsigned)b[i]; }, total, valid, first_packet, k);
         if (!valid) ++cnt.crc_errors;
         else {
@@ -137,40 +124,24 @@ struct T2miHostStream {
         *used = i;
         return done;
     }
+    // what the shared packet loop asks of a format (ts_reasm_rules.h): one slot, no stuffing, the pointer slack counted
+    struct Format {
+        T2miHostStream& h;
+        int slot_of(int pid) const { return pid == h.watch.pid ? 0 : -1; }
+        T2miState& state(int) { return h.st; }
+        T2miCnt& cnt(int) { return h.cnt; }
+        void drop(int) { h.drop(); }
+        bool feed(int, const uint8_t* b, int n, int* used, int k, bool want_bytes) { return h.feed(b, n, used, k, want_bytes); }
+        void begin(int, int k) { h.first_packet = k; }
+        void slack(int) { ++h.cnt.pointer_slack; }
+        bool stuffing(uint8_t) const { return false; }
+    };
     // one call: n packets.  The caller keeps a copy of `st` if the call may have to be undone.
     void run(const uint8_t* ts, int n, bool want_bytes) {
         rows.clear(); bytes.clear();
         cnt = T2miCnt{};
         first_packet = -1;
-        if (watch.pid < 0) return;
-        for (int k = 0; k < n; ++k) {
-            const uint8_t* p = ts + (size_t)k * TSMON_TS;
-            const TsmonHdr h = tsmon_parse(p);
-            if (h.cls != TSMON_DATA || h.pid != watch.pid) continue;
-            ++cnt.packets;
-            if (h.tsc) { ++cnt.scrambled_packets; drop(); tsmon_step(&st.cont, h.afc, h.cc, h.di); continue; }
-            const int v = tsmon_step(&st.cont, h.afc, h.cc, h.di);
-            if (v == TSMON_DUPLICATE) continue;
-            if (v == TSMON_CC_ERROR || v == TSMON_DISC) drop();
-            if (!(h.afc & 1)) continue;
-            const int ps = t2mi_payload_start(h.afc, p[4]);
-            if (ps >= TSMON_TS) { ++cnt.malformed_packets; drop(); continue; }
-            int used = 0;
-            if (!h.pusi) {
-                if (st.fill > 0) feed(p + ps, TSMON_TS - ps, &used, k, want_bytes);
-                continue;
-            }
-            const int ptr = p[ps];
-            if (ptr > TSMON_TS - ps - 1) { ++cnt.malformed_packets; drop(); continue; }
-            if (st.fill > 0) {
-                if (!feed(p + ps + 1, ptr, &used, k, want_bytes)) drop();
-                else if (used < ptr) ++cnt.pointer_slack;
-            }
-            for (int at = ps + 1 + ptr; at < TSMON_TS; at += used) {
-                first_packet = k;
-                if (!feed(p + at, TSMON_TS - at, &used, k, want_bytes)) break;
-            }
-        }
+        if (watch.pid >= 0) ts_reasm_run(Format{*this}, ts, n, want_bytes);
     }
 };
 

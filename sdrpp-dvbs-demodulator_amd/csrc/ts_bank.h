@@ -1,7 +1,9 @@
-// Shared by the banks that work on transport streams in HBM (tsmon.hip: the TS monitor; psi.hip: the PSI sections; pcr.hip: the PCRs; pes.hip: the PES packets):
+// Shared by the banks that work on transport streams in HBM (tsmon.hip: the TS monitor; psi.hip: the PSI sections; pcr.hip: the PCRs; pes.hip: the PES packets;
+// t2mi.hip: the T2-MI packets):
 // what a "packet bank" does around its rules.  On the device: the one header read, the one workgroup prefix sum and the contiguous
 // run of items a thread takes ("flags in a mask, scan, scatter").  On the host: the argument table of a call, the count checks,
-// the staging of the single-stream host-buffer entry point and the table getters.  The rules stay in tsmon_rules.h / psi_rules.h / pcr_rules.h / pes_rules.h.
+// the staging of the single-stream host-buffer entry point and the table getters.  The rules stay in tsmon_rules.h / psi_rules.h / pcr_rules.h / pes_rules.h /
+// t2mi_rules.h; what the two reassembling banks (PSI, T2-MI) share beyond this is ts_reasm.h.
 #pragma once
 #include "bbts_common.h"
 #include "tsmon_rules.h"
@@ -63,16 +65,19 @@ __device__ inline void ts_thread_run(int n, int wg, int* k0, int* k1) {
 }
 #endif
 
-// the argument table of a call for n streams: input pointers | output pointers | byte counts
-struct TsBankArgs {
+// the argument table of a call for n streams: input pointers | output pointers, SLOTS per stream (the T2-MI bank: 4) | byte counts
+template <int SLOTS>
+struct TsBankArgsN {
     ScratchLayout L;
     ScratchPart<const uint8_t*> in; ScratchPart<uint8_t*> out; ScratchPart<int> nbytes;
-    explicit TsBankArgs(size_t n) : in(L.add<const uint8_t*>(n)), out(L.add<uint8_t*>(n)), nbytes(L.add<int>(n)) {}
+    explicit TsBankArgsN(size_t n) : in(L.add<const uint8_t*>(n)), out(L.add<uint8_t*>(n * SLOTS)), nbytes(L.add<int>(n)) {}
     void fill(void* h_args, int n, const uint8_t* const* d_ts, uint8_t* const* d_out, const int* nb) const {
         const uint8_t** pi = in(h_args); uint8_t** po = out(h_args); int* pn = nbytes(h_args);
         for (int i = 0; i < n; ++i) { pi[i] = d_ts[i]; po[i] = d_out ? d_out[i] : nullptr; pn[i] = nb[i]; }
+        if constexpr (SLOTS > 1) for (int g = n; g < n * SLOTS; ++g) po[g] = d_out ? d_out[g] : nullptr;
     }
 };
+typedef TsBankArgsN<1> TsBankArgs;
 
 // n byte counts of a call: whole packets, at most max_packets of them.  false: last_error() has the text, behind the bank's prefix.
 // The banks call it per stream inside their loops over thousands of streams: the two compares are inlined there, the text is built out of line
@@ -89,40 +94,45 @@ __attribute__((always_inline)) inline bool ts_bank_check_counts(const char* pref
 // slack: harmless here, the input never grows after the first call and the output follows the largest cap seen.
 struct TsHostStage { Workspace in, out; };
 // The device path of a single-stream call with host buffers: h_ts staged, room for cap + 4 output bytes, per-stream vectors in which the other
-// streams bring nothing (out_all: they have the output pointer all the same), the bank's batch(in, nbytes, out or null, out_bytes), copy back
-template <typename Batch>
-inline int ts_bank_work(TsHostStage& sg, int nstreams, int stream, const uint8_t* h_ts, int nbytes, int max_packets, uint8_t* h_out, int cap, bool out_all, Batch batch) {
+// streams bring nothing (out_all: they have the output pointer all the same), the bank's batch(in, nbytes, out or null, out_bytes), copy back.
+// With SLOTS outputs per stream the output vectors hold that many per stream and the call is for `slot` of `stream`
+template <int SLOTS = 1, typename Batch>
+inline int ts_bank_work(TsHostStage& sg, int nstreams, int stream, const uint8_t* h_ts, int nbytes, int max_packets, uint8_t* h_out, int cap, bool out_all, Batch batch,
+                        int slot = 0) {
     if (const int e = sg.in.ensure((size_t)max_packets * TSMON_TS)) return e;
     if (nbytes > 0) HIP_TRY(hipMemcpy(sg.in.p, h_ts, nbytes, hipMemcpyHostToDevice));
     if (const int e = h_out ? sg.out.ensure((size_t)cap + 4) : 0) return e;
     std::vector<const uint8_t*> in(nstreams, nullptr);
-    std::vector<uint8_t*> out(nstreams, out_all ? static_cast<uint8_t*>(sg.out.p) : nullptr);
-    std::vector<int> nb(nstreams, 0), ob(nstreams, 0);
-    in[stream] = static_cast<const uint8_t*>(sg.in.p); out[stream] = static_cast<uint8_t*>(sg.out.p); nb[stream] = nbytes;
+    const int g = SLOTS > 1 ? stream * SLOTS + slot : stream;
+    std::vector<uint8_t*> out(nstreams * SLOTS, out_all ? static_cast<uint8_t*>(sg.out.p) : nullptr);
+    std::vector<int> nb(nstreams, 0), ob(nstreams * SLOTS, 0);
+    in[stream] = static_cast<const uint8_t*>(sg.in.p); out[g] = static_cast<uint8_t*>(sg.out.p); nb[stream] = nbytes;
     const int rc = batch(in.data(), nb.data(), h_out ? out.data() : nullptr, ob.data());
     if (rc < 0) return rc;
-    if (h_out && ob[stream] > 0) HIP_TRY(hipMemcpy(h_out, sg.out.p, ob[stream], hipMemcpyDeviceToHost));
-    return ob[stream];
+    if (h_out && ob[g] > 0) HIP_TRY(hipMemcpy(h_out, sg.out.p, ob[g], hipMemcpyDeviceToHost));
+    return ob[g];
 }
 
 // The table getters of a bank `b` (null: an argument error) with ctx, nstreams, nrows[], the device table d_rows of b->*stride rows per
-// stream and, in a host bank (ctx null), host[stream].rows.  The rows of the stream's last call into h_rows, at most cap; *n: how many there are
-template <typename Bank, typename Pub>
-inline int ts_bank_rows(Bank* b, int Bank::*stride, int stream, Pub* h_rows, int cap, int* n) {
-    if (!b || stream < 0 || stream >= b->nstreams || !n || cap < 0 || (cap > 0 && !h_rows)) return DVBS2GPU_ERR_ARG;
+// stream and, in a host bank (ctx null), host[stream].rows.  The rows of the stream's last call into h_rows, at most cap; *n: how many there are.
+// A bank with a table per (stream, slot) has SLOTS of each per stream
+template <int SLOTS = 1, typename Bank, typename Pub>
+inline int ts_bank_rows(Bank* b, int Bank::*stride, int stream, Pub* h_rows, int cap, int* n, int slot = 0) {
+    if (!b || stream < 0 || stream >= b->nstreams || (SLOTS > 1 && (slot < 0 || slot >= SLOTS)) || !n || cap < 0 || (cap > 0 && !h_rows)) return DVBS2GPU_ERR_ARG;
     static_assert(sizeof(Pub) == sizeof(*b->d_rows), "row layout");
-    const int k = (*n = b->nrows[stream]) < cap ? *n : cap;
+    const int g = SLOTS > 1 ? stream * SLOTS + slot : stream, k = (*n = b->nrows[g]) < cap ? *n : cap;
     if (k <= 0) return 0;
-    if (!b->ctx) { memcpy(h_rows, b->host[stream].rows.data(), k * sizeof(Pub)); return 0; }
+    if (!b->ctx) { memcpy(h_rows, b->host[g].rows.data(), k * sizeof(Pub)); return 0; }
     HIP_TRY(hipSetDevice(b->ctx->device));
-    HIP_TRY(hipMemcpy(h_rows, b->d_rows + (size_t)stream * (b->*stride), k * sizeof(Pub), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_rows, b->d_rows + (size_t)g * (b->*stride), k * sizeof(Pub), hipMemcpyDeviceToHost));
     return 0;
 }
 // the same table where it lies in HBM (device banks only)
-template <typename Bank, typename Pub>
-inline int ts_bank_rows_device(Bank* b, int Bank::*stride, int stream, const Pub** d_rows, int* n) {
-    if (!b || !b->ctx || stream < 0 || stream >= b->nstreams || !n || !d_rows) return DVBS2GPU_ERR_ARG;
-    *n = b->nrows[stream]; *d_rows = *n ? reinterpret_cast<const Pub*>(b->d_rows + (size_t)stream * (b->*stride)) : nullptr;
+template <int SLOTS = 1, typename Bank, typename Pub>
+inline int ts_bank_rows_device(Bank* b, int Bank::*stride, int stream, const Pub** d_rows, int* n, int slot = 0) {
+    if (!b || !b->ctx || stream < 0 || stream >= b->nstreams || (SLOTS > 1 && (slot < 0 || slot >= SLOTS)) || !n || !d_rows) return DVBS2GPU_ERR_ARG;
+    const int g = SLOTS > 1 ? stream * SLOTS + slot : stream;
+    *n = b->nrows[g]; *d_rows = *n ? reinterpret_cast<const Pub*>(b->d_rows + (size_t)g * (b->*stride)) : nullptr;
     return 0;
 }
 

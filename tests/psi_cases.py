@@ -53,6 +53,39 @@ def edge_cases():
     return out
 
 
+# the cases of edge_cases() that the shared reassembly walk (csrc/ts_reasm.h) takes down a branch of its own
+WALK_EDGES = ('header cut after 1 byte', 'header cut after 2 bytes', 'section_length 4094 in a cut header', 'pointer completes the open section',
+              'pointer too short for the open section', 'pointer longer than the open section needs')
+
+
+def walk_cases():
+    """further branches of the walk, each for a slot that has seen nothing -> [(name, packets [k, 188], rows, (dropped_sections,
+    malformed_sections))]; rows: (table_id, length, first_packet) of the sections the packets give in one call, written out"""
+    out = []
+
+    def add(name, ts, rows, counts):
+        out.append((name, np.asarray(ts, np.uint8).reshape(-1, P.TS), rows, counts))
+    z = P.Packetiser(PID)
+    a = _sec(584, 50)                                       # 183 + 184 + 184 + 33 bytes: the third packet is lost
+    head = z.lay([a])[:2]
+    z.cc = 3
+    add('PUSI packet behind a lost packet with a section open', np.concatenate([head, z.lay([_sec(40, 51, 0x43)], pointer=33, before=a[551:])]),
+        [(0x43, 40, 2)], (1, 0))
+    z = P.Packetiser(PID)
+    add('two whole sections and a third cut in its body', z.lay([_sec(60, 52), _sec(70, 53, 0x43), _sec(100, 54, 0x44)]),
+        [(0x42, 60, 0), (0x43, 70, 0), (0x44, 100, 0)], (0, 0))
+    z = P.Packetiser(PID)
+    add('two whole sections and a third cut after 2 header bytes', z.lay([_sec(60, 55), _sec(121, 56, 0x43), _sec(100, 57, 0x44)]),
+        [(0x42, 60, 0), (0x43, 121, 0), (0x44, 100, 0)], (0, 0))
+    z = P.Packetiser(PID)
+    add('ssi section of 11 bytes that ends in the next packet', z.lay([_sec(178, 58), bytes([0x42, 0xB0, 8]) + bytes(8)]), [(0x42, 178, 0)], (0, 1))
+    z = P.Packetiser(PID)
+    add('ssi section of 11 bytes in a header cut after 1 byte', z.lay([_sec(182, 59), bytes([0x42, 0xB0, 8]) + bytes(8)]), [(0x42, 182, 0)], (0, 1))
+    z = P.Packetiser(PID)
+    add('stuffing directly behind a section, a section header behind the stuffing', z.lay([_sec(30, 60), b'\xff', _sec(20, 61, 0x43)]), [(0x42, 30, 0)], (0, 0))
+    return out
+
+
 def whole_stream(rng, cases=None):
     """the edge cases back to back with a PAT on PID 0 and packets of an unwatched PID, a TEI packet and a null packet between them"""
     cases = cases or edge_cases()

@@ -76,6 +76,23 @@ def edge_cases():
     return out
 
 
+# the cases of edge_cases() that the shared reassembly walk (csrc/ts_reasm.h) takes down a branch of its own
+WALK_EDGES = tuple('header split after %d bytes' % h for h in (1, 2, 3, 4, 5)) + (
+    'pointer = the whole rest', 'pointer bytes leave the open packet incomplete', 'pointer bytes overshoot the open packet')
+
+
+def walk_cases():
+    """further branches of the walk, each for a slot that has seen nothing -> [(name, packets [k, 188], rows as in ROWS for the packets in
+    one call, dropped_packets)]"""
+    x, y = T.t2mi_packet(0x20, 1, _bytes(390, 70)), T.t2mi_packet(0x20, 2, _bytes(50, 71))
+    lost = np.concatenate([S.packet(PID, 1, b'\x00' + x[:183], pusi=1), S.packet(PID, 2, x[183:367]),                   # (continuity counter 3 is lost)
+                           S.packet(PID, 4, bytes([33]) + x[367:] + y, pusi=1, af_len=184 - 94 - 1)]).reshape(-1, S.TS)
+    three = T.Packetiser(PID).lay([T.t2mi_packet(0x20, 1, _bytes(40, 72)), T.t2mi_packet(0x10, 2, _bytes(50, 73)), T.t2mi_packet(0x20, 3, _bytes(140, 74))])
+    return [('PUSI packet behind a lost TS packet with a packet open', lost, [(32, 2, 0, 0, 400, 60, -1, 0, 2, 2)], 1),
+            ('two whole packets and a third cut by the TS packet end', three,
+             [(32, 1, 0, 0, 320, 50, -1, 0, 0, 0), (16, 2, 0, 0, 400, 60, -1, 0, 0, 0), (32, 3, 0, 0, 1120, 150, -1, 0, 0, 1)], 0)]
+
+
 def whole_stream(rng=None, cases=None):
     """the edge cases back to back with packets of another PID, a TEI packet and a null packet between them"""
     rng = rng or np.random.default_rng(1)

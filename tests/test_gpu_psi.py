@@ -104,6 +104,26 @@ def test_constructed_edges_whole_and_cut_in_two(pkg, eng):
     assert one.models[0].stats(0)['changed'] == 3
 
 
+def test_walk_cases_whole_and_cut_at_every_packet(pkg, eng):
+    """the branches of the shared walk (csrc/ts_reasm.h) that this format takes with its own header length, or alone: each case by
+    itself on a fresh bank, in one call and cut in two at every packet boundary"""
+    edges = {name: ts for name, ts, _ in K.edge_cases()}
+    for name, ts, rows, counts in [(name, edges[name], None, None) for name in K.WALK_EDGES] + K.walk_cases():
+        whole = None
+        for at in range(len(ts)):                                  # 0: one call
+            rig, got = Rig(pkg, eng, 1, 8, 16), []
+            for k, part in enumerate([ts[:at], ts[at:]] if at else [ts]):
+                rig.call([part], shift=(at + k) % 2)
+                got += [(r['table_id'], r['length'], r['flags']) for r in rig.models[0].table]
+            st = rig.models[0].stats(1)
+            if at == 0:
+                whole = (got, st)
+                if rows is not None:
+                    assert [(r['table_id'], r['length'], r['first_packet']) for r in rig.models[0].table] == rows, name
+                    assert (st['dropped_sections'], st['malformed_sections']) == counts, name
+            assert (got, st) == whole and not rig.models[0].slot[1]['buf'], (name, at)
+
+
 def test_slot_shapes(pkg, eng):
     rng = np.random.default_rng(5)
     z = P.Packetiser(0x44)

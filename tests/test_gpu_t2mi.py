@@ -118,6 +118,27 @@ def test_constructed_cases_whole_and_cut_in_two(pkg, eng):
     assert one.models[0].stats(0) == rig.models[0].stats(0) and one.models[0].stats(1)['bbframes_delivered'] == 11
 
 
+def test_walk_cases_whole_and_cut_at_every_packet(pkg, eng):
+    """the branches of the shared walk (csrc/ts_reasm.h) that this format takes with its own header length, or alone: each case by
+    itself on a fresh bank, in one call and cut in two at every TS packet boundary"""
+    edges = dict(K.edge_cases())
+    key = lambda r: tuple(r[f] for f in K.ROW_FIELDS[:8])          # (all but first_packet and last_packet, which count from the call's start)
+    for name, ts, rows, dropped in [(name, edges[name], None, None) for name in K.WALK_EDGES] + K.walk_cases():
+        whole = None
+        for at in range(len(ts)):                                  # 0: one call
+            rig, got, off = Rig(pkg, eng, 1, 8, 32), [], 0
+            for k, part in enumerate([ts[:at], ts[at:]] if at else [ts]):
+                rig.call([part], shift=(at + k) % 4)
+                got += [key(dict(r, offset=r['offset'] + off if r['offset'] >= 0 else -1)) for r in rig.models[0].table(0)]
+                off += sum(rig.models[0].frame_bytes(0))
+            st = rig.models[0].stats(0)
+            if at == 0:
+                whole = (got, st)
+                if rows is not None:
+                    assert [tuple(r[f] for f in K.ROW_FIELDS) for r in rig.models[0].table(0)] == rows and st['dropped_packets'] == dropped, name
+            assert (got, st) == whole and not rig.models[0].slot[0].buf, (name, at)
+
+
 def test_packets_carried_over_two_and_three_calls(pkg, eng):
     cases = dict(K.edge_cases())
     big, bb = cases['payload_bits 65535: 8202 bytes over 45 TS packets'], cases['BBFRAME of 7274 bytes']

@@ -68,6 +68,19 @@ def test_constructed_edges_one_by_one(pkg):
     assert max(r['length'] for r in pair.m.table) < 4096 and pair.m.stats(1)['bytes_delivered'] > 4096
 
 
+def test_walk_cases_whole_and_cut_at_every_packet(pkg):
+    """the written-out rows of K.walk_cases(), and the same sections and counters from two calls cut at every packet boundary"""
+    for name, ts, rows, counts in K.walk_cases():
+        for at in range(len(ts)):                                   # 0: one call
+            pair, got = Pair(pkg), []
+            for part in ([ts[:at], ts[at:]] if at else [ts]):
+                pair.call(part)
+                got += [(r['table_id'], r['length']) for r in pair.m.table]
+            st = pair.m.stats(1)
+            assert got == [r[:2] for r in rows] and (st['dropped_sections'], st['malformed_sections']) == counts, (name, at)
+            assert at or [r['first_packet'] for r in pair.m.table] == [r[2] for r in rows], name
+
+
 def test_largest_section_and_row_fields(pkg):
     pair = Pair(pkg)
     sec = K._sec(4096, 12)

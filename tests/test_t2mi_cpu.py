@@ -64,6 +64,18 @@ def test_constructed_cases_one_by_one(pkg):
     assert (st['dropped_packets'], st['malformed_packets'], st['scrambled_packets'], st['pointer_slack'], st['bad_payload'], st['crc_errors']) == (4, 2, 1, 1, 4, 5)
 
 
+def test_walk_cases_whole_and_cut_at_every_packet(pkg):
+    """the written-out rows of K.walk_cases(), and the same rows but for the packet indices from two calls cut at every TS packet boundary"""
+    for name, ts, rows, dropped in K.walk_cases():
+        for at in range(len(ts)):                                    # 0: one call
+            pair, got = Pair(pkg), []
+            for part in ([ts[:at], ts[at:]] if at else [ts]):
+                pair.call(part)
+                got += [tuple(r[k] for k in K.ROW_FIELDS) for r in pair.m.table(0)]
+            assert [r[:8] for r in got] == [r[:8] for r in rows] and pair.m.stats(0)['dropped_packets'] == dropped, (name, at)
+            assert at or got == rows, name
+
+
 def test_row_fields_of_the_largest_packets(pkg):
     pair = Pair(pkg)
     cases = dict(CASES)
