@@ -638,7 +638,7 @@ typedef struct dvbs2gpu_bbts_ma_stats {
     int32_t iscr_valid;  uint32_t last_iscr;   /* last ISCR seen: 15 bits (short) or 22 bits (long) */
     int32_t carried;                     /* bytes of the partial (or held whole) slot waiting for the next frame of this ISI */
     int32_t selected, isi;               /* is this slot in use, and for which ISI (-1: none) */
-    int32_t reserved;
+    int32_t hem_frames;                  /* those of `frames` that were high-efficiency-mode frames (dvbs2gpu_bbts_ma_set_t2_hem) */
 } dvbs2gpu_bbts_ma_stats;
 void dvbs2gpu_bbts_ma_default_cfg(dvbs2gpu_bbts_ma_cfg* cfg);            /* {0, 0, 1, 1} */
 /* out4 = {offset of the CRC-8, offset and length of the UP, offset of the ISSY field} inside a slot, as compiled in */
@@ -713,6 +713,35 @@ int dvbs2gpu_bbts_ma_get_gse_stats(dvbs2gpu_bbts* b, int stream, int slot, dvbs2
 int dvbs2gpu_bbts_ma_get_pdu_table(dvbs2gpu_bbts* b, int stream, int slot, dvbs2gpu_gse_pdu* h_rows, int cap, int* n);
 /* the same in HBM, valid until the bank's next call (device banks only; NULL when *n == 0) */
 int dvbs2gpu_bbts_ma_get_pdu_table_device(dvbs2gpu_bbts* b, int stream, int slot, const dvbs2gpu_gse_pdu** d_rows, int* n);
+/* ---- DVB-T2 high-efficiency mode (HEM) in the mode-adaptation mode: the BBFRAMEs of a T2-MI feed (the T2-MI bank below) are of this
+ * kind on most networks.  Off by default; while it is off every call above behaves as before and a HEM frame counts in
+ * rejected_frames.  The rules are written from memory of EN 302 755 5.1.7 and 5.1.8; the constants are in ONE struct of the library
+ * and dvbs2gpu_bbts_ma_get_hem_layout reports them.
+ *   Mode of a frame: c = CRC-8 of the first nine header bytes.  Byte 9 == c: normal mode, the rules above.  Byte 9 == c ^ MODE (1)
+ *     and the switch on: HEM.  Anything else: rejected_frames.  DFL and SYNCD are checked as above; padding and in-band signalling
+ *     behind DFL are never looked at.  TS/GS, SIS/MIS, ISSYI, NPD and the ISI (the PLP id) are read from the same bits.  A HEM frame
+ *     with TS/GS != 11 or of an ISI that is not selected counts in skipped_frames: HEM GSE frames are not decapsulated, also with
+ *     dvbs2gpu_bbts_ma_set_gse on.  A parsed HEM frame counts in `frames` and in `hem_frames` of its lane.
+ *   Header: bytes 2-3 (UPL in normal mode) and byte 6 (SYNC) are neither; UPL is implied, 188 bytes.  With ISSYI = 1 the three are the
+ *     ISSY field of the first UP that starts in this data field (bytes 2-3 its upper bytes, byte 6 its lowest): it gives iscr_valid /
+ *     last_iscr, short or long, in frame order, from frames in which a slot starts only.  There is no ISSY field per UP, so the ISSY
+ *     length question never arises: issy_bytes and `undecided` are not touched by HEM frames.
+ *   Slot: [187 UP bytes][DNP: 1 byte iff NPD], 187 or 188 bytes; no sync byte and no CRC-8 in the data field.  Output per slot as
+ *     above: DNP null packets if cfg.reinsert_nulls, then 0x47 + the 187 bytes.  No HEM slot ever sets TEI; ts_errs does not move.
+ *   Framing is per frame: the first slot starts SYNCD/8 bytes in, further ones every slot length L.  A slot leaves as soon as its LAST
+ *     byte is there: n = (DFL/8 - SYNCD/8) / L slots, and the 0 .. L-1 bytes behind them are carried (0: nothing is).  The carry joins
+ *     the next frame of the same ISI only if carried + SYNCD/8 == L and the carried bytes are HEM bytes of the same L; else it is
+ *     dropped and counted in broken_joins.  A normal-mode frame after a HEM carry and a HEM frame after a normal-mode carry count there
+ *     once, too.  With SYNCD = 65535 the data field continues the carried slot.  With nothing carried, a frame whose SYNCD/8 > 0 starts
+ *     at its first slot and the bytes before it are not counted: the rule of normal mode for a fresh lane.  The output does not depend
+ *     on how calls cut the frame sequence.
+ *   Flush: a HEM carry is a partial slot; dvbs2gpu_bbts_ma_flush emits nothing for it and clears it.  The one exception is a slot that a
+ *     SYNCD = 65535 frame completed to its last byte: it is whole, waits for the next frame of its ISI like a held normal-mode slot and
+ *     leaves with a flush.
+ *   Capacity: as above. */
+int dvbs2gpu_bbts_ma_set_t2_hem(dvbs2gpu_bbts* b, int on);   /* needs the mode on; device and host banks; every lane starts afresh */
+/* out4 = {offset and length of the UP, offset of the DNP byte = slot length without NPD, MODE value XORed into the CRC-8} */
+int dvbs2gpu_bbts_ma_get_hem_layout(int32_t* out4);
 /* mask8: bit i of the 256-bit mask = a frame with a valid header and ISI i has been seen on `stream` since the mode was set */
 int dvbs2gpu_bbts_get_isi_seen(dvbs2gpu_bbts* b, int stream, uint32_t* mask8);
 

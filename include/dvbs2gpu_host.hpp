@@ -264,6 +264,12 @@ public:
         if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
         check(dvbs2gpu_bbts_ma_set_gse(h, on ? 1 : 0));
     }
+    /* DVB-T2 high-efficiency-mode BBFRAMEs (those of a T2-MI feed) are parsed by their own rules (include/dvbs2gpu.h) instead of
+     * being rejected.  Off by default; needs setModeAdaptation() first; the outputs start afresh. */
+    void setModeAdaptationT2HEM(bool on) {
+        if (!h) throw std::runtime_error("dvbs2gpu: BBFrameTSParser used before setFrameSize()");
+        check(dvbs2gpu_bbts_ma_set_t2_hem(h, on ? 1 : 0));
+    }
     dvbs2gpu_bbts_ma_gse_stats modeAdaptationGSEStats(int output) {
         dvbs2gpu_bbts_ma_gse_stats s;
         check(dvbs2gpu_bbts_ma_get_gse_stats(h, 0, output, &s));

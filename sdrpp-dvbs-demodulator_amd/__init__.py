@@ -67,7 +67,7 @@ class BbtsMaStats(C.Structure):
     _fields_ = [('packets', C.c_int64), ('nulls', C.c_int64), ('ts_errs', C.c_int64), ('broken_joins', C.c_int32), ('undecided', C.c_int32),
                 ('frames', C.c_int32), ('skipped_frames', C.c_int32), ('rejected_frames', C.c_int32), ('issy_bytes', C.c_int32),
                 ('iscr_valid', C.c_int32), ('last_iscr', C.c_uint32), ('carried', C.c_int32), ('selected', C.c_int32), ('isi', C.c_int32),
-                ('reserved', C.c_int32)]
+                ('hem_frames', C.c_int32)]
 
 
 class GseStats(C.Structure):
@@ -343,6 +343,8 @@ PROTOTYPES = {
     'dvbs2gpu_bbts_ma_get_stats': (_i, [_vp, _i, _i, C.POINTER(BbtsMaStats)]),
     'dvbs2gpu_bbts_get_isi_seen': (_i, [_vp, _i, C.POINTER(C.c_uint32)]),
     'dvbs2gpu_bbts_ma_set_gse': (_i, [_vp, _i]),
+    'dvbs2gpu_bbts_ma_set_t2_hem': (_i, [_vp, _i]),
+    'dvbs2gpu_bbts_ma_get_hem_layout': (_i, [C.POINTER(C.c_int32)]),
     'dvbs2gpu_bbts_ma_get_gse_stats': (_i, [_vp, _i, _i, C.POINTER(BbtsMaGseStats)]),
     'dvbs2gpu_bbts_ma_get_pdu_table': (_i, [_vp, _i, _i, C.POINTER(GsePdu), _i, C.POINTER(_i)]),
     'dvbs2gpu_bbts_ma_get_pdu_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
@@ -1249,7 +1251,21 @@ class BbTsParserBank(_Handle):
     def ma_stats(self, stream=0, slot=0):
         st = BbtsMaStats()
         self._check(self.lib.dvbs2gpu_bbts_ma_get_stats(self.h, int(stream), int(slot), C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in BbtsMaStats._fields_ if k != 'reserved'}
+        return {k: int(getattr(st, k)) for k, _ in BbtsMaStats._fields_}
+
+    # ---- DVB-T2 high-efficiency-mode BBFRAMEs (those of a T2-MI feed): [187 UP bytes][DNP], the ISSY field in the header
+    def ma_set_t2_hem(self, on=True):
+        """HEM frames are parsed by their own rules (off: rejected, as before); needs the mode on; every lane starts afresh"""
+        self._check(self.lib.dvbs2gpu_bbts_ma_set_t2_hem(self.h, int(bool(on))))
+
+    @staticmethod
+    def ma_hem_layout():
+        """the compiled-in HEM slot layout: {'up_off', 'up_len', 'dnp_off', 'mode'}"""
+        a = (C.c_int32 * 4)()
+        rc = load_library().dvbs2gpu_bbts_ma_get_hem_layout(a)
+        if rc < 0:
+            raise Dvbs2GpuError(rc, 'dvbs2gpu_bbts_ma_get_hem_layout')
+        return dict(zip(('up_off', 'up_len', 'dnp_off', 'mode'), a))
 
     # ---- GSE in the mode-adaptation mode: one reassembly context per (stream, selected ISI); GRE packets in the slot's own buffer
     def ma_set_gse(self, on=True):

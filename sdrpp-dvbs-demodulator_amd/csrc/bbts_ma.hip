@@ -13,6 +13,11 @@
 // The host commits the shadow state and launches the third kernel only when every lane's output fits.
 // MaHostStream below applies the same rules to host buffers, byte by byte (host-only banks; the GPU path's second implementation).
 //
+// DVB-T2 high-efficiency mode (dvbs2gpu_bbts_ma_set_t2_hem; rules in include/dvbs2gpu.h): a header whose CRC-8 carries the MODE value
+// announces a slot of [187 UP bytes][DNP 0/1] (MaHemLayout below) with neither sync byte nor CRC-8 and the ISSY field in the header.
+// The three kernels are the same; a HEM frame's wave (a wave is a frame, so the branch is uniform) skips the CRC and ISSY-length
+// loops, a slot leaves with its own last byte, and the mode is one more bit of MaFrameRec::cfl / MaLaneState::cfl that a join compares.
+//
 // GSE in this mode (dvbs2gpu_bbts_ma_set_gse; rules in include/dvbs2gpu.h): one reassembly context per (stream, selected ISI) lane.
 // Nothing of GSE is stated here: the packet header is gse_parse_packet<GseStrict> (bbts_rules.h), the device's chain walk and
 // reassembly are gse_walk_frame and gse_apply_packet (bbts_gse_dev.h), the host's are GseHostCtx (bbts_host.h), and a context moves
@@ -43,13 +48,28 @@ constexpr MaLayout kMa = {0, 1, 187, 188};
 static_assert(kMa.up_len == 187 && kMa.up_off >= 1 && kMa.issy_off >= kMa.up_off + kMa.up_len, "a TS packet is 0x47 + 187 UP bytes");
 constexpr int MA_TS = 188, MA_LANES = 8, MA_CARRY = 192, MA_NO_START = 65535, MA_MAX_FRAME = 58192 / 8;
 __host__ __device__ inline int ma_slot_len(int issy, int npd) { return kMa.issy_off + issy + npd; }
+// DVB-T2 high-efficiency mode: [187 UP bytes][DNP 0/1]; `mode` is XORed into the header's CRC-8 (0 would be normal mode)
+struct MaHemLayout { int up_off, up_len, dnp_off, mode; };       // dnp_off: also the slot length without NPD
+constexpr MaHemLayout kHem = {0, 187, 187, 1};
+static_assert(kHem.up_len == kMa.up_len && kHem.dnp_off == kHem.up_off + kHem.up_len && kHem.mode > 0 && kHem.mode < 256, "0x47 + the same 187 UP bytes");
+constexpr int MA_CFL_HEM = 8;                                    // the mode bit of cfl, above issy | npd << 2
+__host__ __device__ inline int ma_hem_slot_len(int npd) { return kHem.dnp_off + npd; }
+static_assert(kHem.dnp_off + 1 <= MA_CARRY, "a HEM slot fits the carry buffers");
 __host__ __device__ inline int ma_crc_end(int span, int L) { return span ? L : kMa.up_off + kMa.up_len; }   // CRC-8 over [up_off, end)
 
-struct MaHdr { int ts_gs, isi, issyi, npd, df, s0, nostart, upl; };
+struct MaHdr { int ts_gs, isi, issyi, npd, df, s0, nostart, upl, hem; };
 // a frame of `size` bytes: CRC-8 of the BBHEADER, DFL whole bytes that fit the frame, SYNCD inside the data field or 65535 (no slot
 // starts here).  The reference's `syncd >= dfl - 8` rejection is not applied: a slot may start in the last byte of a data field.
-__host__ __device__ inline bool ma_header(const uint8_t* fr, int size, MaHdr* h) {
-    if (size < 10 || crc8_bits(fr, 80) != 0) return false;
+// hem_on: byte 9 = c ^ kHem.mode, c the CRC-8 of the nine bytes before it, announces a high-efficiency-mode frame (upl is then not a
+// UPL).  The CRC is linear: over all ten bytes it leaves 0 for byte 9 = c and, for c ^ mode, what the byte `mode` alone leaves.
+__host__ __device__ inline bool ma_header(const uint8_t* fr, int size, int hem_on, MaHdr* h) {
+    if (size < 10) return false;
+    h->hem = 0;
+    if (const unsigned q = crc8_bits(fr, 80)) {
+        const uint8_t mode = (uint8_t)kHem.mode;
+        if (!hem_on || q != crc8_bits(&mode, 8)) return false;
+        h->hem = 1;
+    }
     const HeaderFields p = parse_bbheader(fr);
     const int dfl = p.v[8], syncd = p.v[10];
     if (dfl % 8 || dfl > (size - 10) * 8 || !(syncd == MA_NO_START || syncd < dfl)) return false;
@@ -71,12 +91,12 @@ __host__ __device__ inline bool ma_iscr(const uint8_t* f, int issy, unsigned* v)
     return false;
 }
 
-struct MaCfg { int issy_bytes, crc_span, reinsert_nulls, check_crc, gse; };
+struct MaCfg { int issy_bytes, crc_span, reinsert_nulls, check_crc, gse, hem; };
 struct MaSel { uint8_t isi[MA_LANES]; int n; };
 struct MaLaneState {
-    int c, Lc, cfl, issy;                      // carried bytes, their slot length, issy | npd << 2 of that slot, ISSY length in use
+    int c, Lc, cfl, issy;                      // carried bytes, their slot length, issy | npd << 2 | MA_CFL_HEM of that slot, ISSY length in use
     int iscr_valid; unsigned iscr;
-    int frames, broken, undecided, pad;
+    int frames, broken, undecided, hem;        // hem: high-efficiency-mode frames among `frames`
     long long packets, nulls, ts_errs;
 };
 struct MaStreamState { unsigned seen[8]; int rejected, skipped; };
@@ -92,7 +112,7 @@ struct MaFrameDesc { const uint8_t* carry; int out_off, joined, c, dnp, tei, pad
 struct MaFin { const uint8_t* src; int len, pad; };
 
 // ------------------------------------------------------------------------------------------------- GSE per lane
-__host__ __device__ inline bool ma_gse_frame(const MaHdr& h) { return h.ts_gs == 1 && h.upl == 0 && !h.issyi && !h.npd; }
+__host__ __device__ inline bool ma_gse_frame(const MaHdr& h) { return h.ts_gs == 1 && h.upl == 0 && !h.issyi && !h.npd && !h.hem; }
 struct MaGseLane { GseDevState g; long long malformed; };          // three slots, the counters, the last END's verdict
 struct MaGseFrame { int npkt, malformed, over, pad; };              // over: more than GSE_PKT_CAP packets (the one host fallback)
 enum { MA_GSE_DONE = 0, MA_GSE_RECORDS = 1, MA_GSE_STORAGE = 2 };
@@ -137,7 +157,7 @@ __global__ void __launch_bounds__(256) bbts_ma_frame_kernel(const uint8_t* const
     MaFrameRec r = {};
     MaFrameRec* out = recs + (size_t)s * max_frames + f;
     MaHdr h;
-    if (!ma_header(bb + off, size, &h)) { r.lane = -2; if (lane == 0) *out = r; return; }
+    if (!ma_header(bb + off, size, cfg.hem, &h)) { r.lane = -2; if (lane == 0) *out = r; return; }
     r.isi = h.isi; r.lane = -1;
     const MaSel se = sel[s];
     for (int k = se.n - 1; k >= 0; --k) if (se.isi[k] == h.isi) r.lane = k;
@@ -147,6 +167,23 @@ __global__ void __launch_bounds__(256) bbts_ma_frame_kernel(const uint8_t* const
         return;
     }
     if (h.ts_gs != 3 || r.lane < 0) { r.lane = -1; if (lane == 0) *out = r; return; }
+    if (h.hem) {                                   // no sync byte, CRC-8 or ISSY field in the slot: geometry, DNP sum, the header's ISCR
+        const int L = ma_hem_slot_len(h.npd);
+        r.L = L; r.cfl = h.npd << 2 | MA_CFL_HEM; r.s0 = h.s0; r.df = h.df; r.data_off = off + 10; r.nostart = h.nostart;
+        if (h.nostart) { if (lane == 0) *out = r; return; }
+        int n = (h.df - h.s0) / L;                 // a slot leaves with its own last byte
+        n = n < 64 ? n : 64;
+        r.nslots = n; r.tail = h.df - h.s0 - n * L;
+        int sum = lane < n && h.npd && cfg.reinsert_nulls ? bb[off + 10 + h.s0 + lane * L + L - 1] : 0;
+        for (int d = 32; d; d >>= 1) sum += __shfl_xor(sum, d);
+        r.nnull = sum;
+        if (h.issyi) {                             // of the first UP that starts here: bytes 2, 3 and 6 of the header
+            const uint8_t fld[3] = {bb[off + 2], bb[off + 3], bb[off + 6]};
+            r.iscr_valid = ma_iscr(fld, 3, &r.iscr);
+        }
+        if (lane == 0) *out = r;
+        return;
+    }
     int issy = 0;
     if (h.issyi) {
         issy = cfg.issy_bytes ? cfg.issy_bytes : lanes[s * MA_LANES + r.lane].issy;
@@ -157,7 +194,7 @@ __global__ void __launch_bounds__(256) bbts_ma_frame_kernel(const uint8_t* const
             if (g <= f) {
                 const int o = ma_frame_off(foff, s, g, max_frames, fbytes);
                 MaHdr hg;
-                if (ma_header(bb + o, ma_frame_off(foff, s, g + 1, max_frames, fbytes) - o, &hg) && hg.ts_gs == 3 && hg.isi == h.isi)
+                if (ma_header(bb + o, ma_frame_off(foff, s, g + 1, max_frames, fbytes) - o, cfg.hem, &hg) && !hg.hem && hg.ts_gs == 3 && hg.isi == h.isi)
                     cand = ma_issy_cand(bb + o, hg);
             }
             const unsigned long long m = __ballot(cand != 0);
@@ -271,10 +308,12 @@ __global__ void __launch_bounds__(256) bbts_ma_lane_kernel(const uint8_t* const*
             if (r.issy_dec) st.issy = r.issy_dec;
             if (r.L == 0) { ++st.undecided; st.c = 0; continue; }
             const uint8_t* data = bb + r.data_off;
-            const int issy = r.cfl & 3, npd = r.cfl >> 2 & 1;
+            const int issy = r.cfl & 3, npd = r.cfl >> 2 & 1, hem = r.cfl & MA_CFL_HEM;
+            if (hem) ++st.hem;
+            const bool same = st.Lc == r.L && (st.cfl & MA_CFL_HEM) == hem;       // the carried bytes are of this frame's slot shape
             if (r.nostart) {                       // the whole data field continues the carried slot: collect both in this frame's join buffer
                 if (st.c > 0) {
-                    if (st.Lc == r.L && st.c + r.df <= r.L) {
+                    if (same && st.c + r.df <= r.L) {
                         uint8_t* jb = joinbuf + ((size_t)s * max_frames + f) * MA_CARRY;
                         for (int i = lane; i < st.c + r.df; i += 64) jb[i] = i < st.c ? carry[i] : data[i - st.c];
                         __threadfence();
@@ -287,10 +326,10 @@ __global__ void __launch_bounds__(256) bbts_ma_lane_kernel(const uint8_t* const*
             }
             MaFrameDesc d = {carry, out_off, 0, st.c, 0, 0, 0};
             if (st.c > 0) {
-                if (st.Lc == r.L && st.c + r.s0 == r.L) {
+                if (same && st.c + r.s0 == r.L) {
                     d.joined = 1;
                     if (npd && cfg.reinsert_nulls) d.dnp = r.s0 > 0 ? data[r.s0 - 1] : carry[st.c - 1];
-                    if (cfg.check_crc) d.tei = ma_wave_crc(carry, st.c, data, ma_crc_end(cfg.crc_span, r.L), adv, lane) != (unsigned)r.first_byte;
+                    if (cfg.check_crc && !hem) d.tei = ma_wave_crc(carry, st.c, data, ma_crc_end(cfg.crc_span, r.L), adv, lane) != (unsigned)r.first_byte;
                     if (issy) {
                         uint8_t fld[3];
                         for (int k = 0; k < 3; ++k) { const int i = kMa.issy_off + k; fld[k] = k < issy ? (i < st.c ? carry[i] : data[i - st.c]) : 0; }
@@ -386,21 +425,36 @@ __device__ inline void ma_store4(uint8_t* o, unsigned v, bool aligned) {
     }
 }
 // `dnp` null packets, then 0x47 + the 187 UP bytes of one slot, by one wave; 188 = 4 * 47: a dword never straddles two packets
+// UP: where the UP starts in the slot (kMa.up_off or kHem.up_off); the byte before it, if there is one, gives way to 0x47
+template <int UP>
 __device__ inline void ma_put_slot(uint8_t* o, int dnp, const uint8_t* carry, int c, const uint8_t* data, int tei, bool aligned, int lane) {
     for (int w = lane; w < dnp * 47; w += 64) ma_store4(o + 4 * w, w % 47 == 0 ? 0x10ff1f47u : 0xffffffffu, aligned);
     o += (size_t)dnp * MA_TS;
     if (lane < 47) {
-        const int i = kMa.up_off - 1 + 4 * lane;                 // slot bytes [i, i + 4); data[] starts at slot byte c
+        const int i = UP - 1 + 4 * lane;                         // slot bytes [i, i + 4); data[] starts at slot byte c
         unsigned v;
-        if (i >= c) {
+        if (i >= c && i >= 0) {
             v = *reinterpret_cast<const unaligned_u32*>(data + i - c);
-        } else {
+        } else {                                                 // (slot byte -1 of a HEM slot is not read)
             v = 0;
-            for (int k = 0; k < 4; ++k) v |= (unsigned)(i + k < c ? carry[i + k] : data[i + k - c]) << (8 * k);
+            for (int k = 0; k < 4; ++k) if (i + k >= 0) v |= (unsigned)(i + k < c ? carry[i + k] : data[i + k - c]) << (8 * k);
         }
         if (lane == 0) v = ((v & ~0xffu) | 0x47u) | (tei ? 0x8000u : 0u);
         ma_store4(o + 4 * lane, v, aligned);
     }
+}
+
+// the joined slot by the last wave, the whole slots of the frame by all four
+template <int UP>
+__device__ inline void ma_put_frame(uint8_t* o, const MaFrameRec& r, const MaFrameDesc& d, const uint8_t* data, const int* idx, const int* dnps,
+                                    int wave, int lane) {
+    const bool aligned = (reinterpret_cast<uintptr_t>(o) & 3) == 0;
+    if (d.joined) {
+        if (wave == 3) ma_put_slot<UP>(o, d.dnp, d.carry, d.c, data, d.tei, aligned, lane);
+        o += (size_t)(1 + d.dnp) * MA_TS;
+    }
+    for (int k = wave; k < r.nslots; k += 4)
+        ma_put_slot<UP>(o + (size_t)idx[k] * MA_TS, dnps[k], nullptr, 0, data + r.s0 + k * r.L, (int)(r.errmask >> k & 1), aligned, lane);
 }
 
 __global__ void __launch_bounds__(256) bbts_ma_emit_kernel(const uint8_t* const* __restrict__ in, uint8_t* const* __restrict__ out,
@@ -432,13 +486,8 @@ __global__ void __launch_bounds__(256) bbts_ma_emit_kernel(const uint8_t* const*
     }
     __syncthreads();
     uint8_t* o = out[s * MA_LANES + r.lane] + d.out_off;
-    const bool aligned = (reinterpret_cast<uintptr_t>(o) & 3) == 0;
-    if (d.joined) {
-        if (wave == 3) ma_put_slot(o, d.dnp, d.carry, d.c, data, d.tei, aligned, lane);
-        o += (size_t)(1 + d.dnp) * MA_TS;
-    }
-    for (int k = wave; k < r.nslots; k += 4)
-        ma_put_slot(o + (size_t)idx[k] * MA_TS, dnps[k], nullptr, 0, data + r.s0 + k * r.L, (int)(r.errmask >> k & 1), aligned, lane);
+    if (r.cfl & MA_CFL_HEM) ma_put_frame<kHem.up_off>(o, r, d, data, idx, dnps, wave, lane);
+    else ma_put_frame<kMa.up_off>(o, r, d, data, idx, dnps, wave, lane);
 }
 
 // ------------------------------------------------------------------------------------------------- host parser
@@ -466,8 +515,8 @@ struct MaHostStream {
         for (int i = a; i < e; ++i) c = tab[c ^ p[i]];
         return c;
     }
-    // one slot (L bytes at p) -> out; chk < 0: no CRC-8 to compare with
-    void emit(MaLaneState& l, const uint8_t* p, int L, int issy, int npd, int chk, const MaCfg& cfg, std::vector<uint8_t>& out) const {
+    // one slot (L bytes at p) -> out; chk < 0: no CRC-8 to compare with; up: where its UP starts (a HEM slot: kHem.up_off, issy 0, chk < 0)
+    void emit(MaLaneState& l, const uint8_t* p, int L, int issy, int npd, int chk, const MaCfg& cfg, std::vector<uint8_t>& out, int up = kMa.up_off) const {
         const int dnp = npd && cfg.reinsert_nulls ? p[L - 1] : 0;
         for (int k = 0; k < dnp; ++k) {
             const size_t at = out.size();
@@ -477,7 +526,7 @@ struct MaHostStream {
         l.nulls += dnp;
         const size_t at = out.size();
         out.push_back(0x47);
-        out.insert(out.end(), p + kMa.up_off, p + kMa.up_off + kMa.up_len);
+        out.insert(out.end(), p + up, p + up + kMa.up_len);
         if (cfg.check_crc && chk >= 0 && crc(p, kMa.up_off, ma_crc_end(cfg.crc_span, L)) != (unsigned)chk) { out[at + 1] |= 0x80; ++l.ts_errs; }
         ++l.packets;
         unsigned v;
@@ -485,7 +534,7 @@ struct MaHostStream {
     }
     void frame(const uint8_t* fr, int size, const MaCfg& cfg, const MaSel& sel, std::vector<uint8_t>* outs) {
         MaHdr h;
-        if (!ma_header(fr, size, &h)) { ++ss.rejected; return; }
+        if (!ma_header(fr, size, cfg.hem, &h)) { ++ss.rejected; return; }
         ss.seen[h.isi >> 5] |= 1u << (h.isi & 31);
         int slot = -1;
         for (int k = sel.n - 1; k >= 0; --k) if (sel.isi[k] == h.isi) slot = k;
@@ -499,6 +548,7 @@ struct MaHostStream {
         MaLaneState& l = st[slot];
         uint8_t* cy = carry[slot];
         ++l.frames;
+        if (h.hem) { hem_frame(l, cy, fr, h, cfg, outs[slot]); return; }
         int issy = 0;
         if (h.issyi) {
             if (!l.issy) l.issy = ma_issy_cand(fr, h);
@@ -509,13 +559,13 @@ struct MaHostStream {
         const uint8_t* data = fr + 10;
         if (h.nostart) {
             if (l.c > 0) {
-                if (l.Lc == L && l.c + h.df <= L) { memcpy(cy + l.c, data, h.df); l.c += h.df; }
+                if (l.Lc == L && !(l.cfl & MA_CFL_HEM) && l.c + h.df <= L) { memcpy(cy + l.c, data, h.df); l.c += h.df; }
                 else { ++l.broken; l.c = 0; }
             }
             return;
         }
         if (l.c > 0) {
-            if (l.Lc == L && l.c + h.s0 == L) {
+            if (l.Lc == L && !(l.cfl & MA_CFL_HEM) && l.c + h.s0 == L) {
                 memcpy(cy + l.c, data, h.s0);
                 emit(l, cy, L, issy, h.npd, data[h.s0], cfg, outs[slot]);
             } else {
@@ -527,12 +577,44 @@ struct MaHostStream {
         l.c = h.df - h.s0 - n * L; l.Lc = L; l.cfl = issy | h.npd << 2;
         memcpy(cy, data + h.s0 + n * L, l.c);
     }
+    // a high-efficiency-mode frame of lane l: the framing above without the byte after a slot, the ISCR from the header
+    void hem_frame(MaLaneState& l, uint8_t* cy, const uint8_t* fr, const MaHdr& h, const MaCfg& cfg, std::vector<uint8_t>& out) const {
+        ++l.hem;
+        const int L = ma_hem_slot_len(h.npd);
+        const uint8_t* data = fr + 10;
+        const bool same = l.Lc == L && (l.cfl & MA_CFL_HEM);
+        if (h.nostart) {
+            if (l.c > 0) {
+                if (same && l.c + h.df <= L) { memcpy(cy + l.c, data, h.df); l.c += h.df; }
+                else { ++l.broken; l.c = 0; }
+            }
+            return;
+        }
+        if (l.c > 0) {
+            if (same && l.c + h.s0 == L) {
+                memcpy(cy + l.c, data, h.s0);
+                emit(l, cy, L, 0, h.npd, -1, cfg, out, kHem.up_off);
+            } else {
+                ++l.broken;
+            }
+        }
+        const int n = (h.df - h.s0) / L;
+        for (int k = 0; k < n; ++k) emit(l, data + h.s0 + k * L, L, 0, h.npd, -1, cfg, out, kHem.up_off);
+        const uint8_t fld[3] = {fr[2], fr[3], fr[6]};
+        unsigned v;
+        if (h.issyi && ma_iscr(fld, 3, &v)) { l.iscr = v; l.iscr_valid = 1; }
+        l.c = h.df - h.s0 - n * L; l.Lc = L; l.cfl = h.npd << 2 | MA_CFL_HEM;
+        memcpy(cy, data + h.s0 + n * L, l.c);
+    }
 };
 
-// a whole slot held back for its CRC-8 leaves unchecked
+// a whole slot held back for its CRC-8 leaves unchecked.  A HEM slot waits for nothing, so a HEM carry is a partial slot and is only
+// cleared; the one whole one, completed by a SYNCD = 65535 frame with no frame behind it yet, leaves like any other
 static void ma_flush_lane(MaHostStream& tool, MaLaneState& l, const uint8_t* cy, const MaCfg& cfg, std::vector<uint8_t>& out) {
     if (l.c > 0 && l.c == l.Lc) {
-        tool.emit(l, cy, l.Lc, l.cfl & 3, l.cfl >> 2 & 1, -1, cfg, out);
+        tool.emit(l, cy, l.Lc, l.cfl & 3, l.cfl >> 2 & 1, -1, cfg, out, l.cfl & MA_CFL_HEM ? kHem.up_off : kMa.up_off);
+        l.c = 0;
+    } else if (l.cfl & MA_CFL_HEM) {
         l.c = 0;
     }
 }
@@ -698,6 +780,12 @@ void dvbs2gpu_bbts_ma_default_cfg(dvbs2gpu_bbts_ma_cfg* cfg) {
 int dvbs2gpu_bbts_ma_get_layout(int32_t* out4) {
     if (!out4) return DVBS2GPU_ERR_ARG;
     out4[0] = kMa.crc_off; out4[1] = kMa.up_off; out4[2] = kMa.up_len; out4[3] = kMa.issy_off;
+    return 0;
+}
+
+int dvbs2gpu_bbts_ma_get_hem_layout(int32_t* out4) {
+    if (!out4) return DVBS2GPU_ERR_ARG;
+    out4[0] = kHem.up_off; out4[1] = kHem.up_len; out4[2] = kHem.dnp_off; out4[3] = kHem.mode;
     return 0;
 }
 
@@ -1034,6 +1122,7 @@ int dvbs2gpu_bbts_ma_get_stats(dvbs2gpu_bbts* b, int stream, int slot, dvbs2gpu_
     o.skipped_frames = ss.skipped; o.rejected_frames = ss.rejected;
     o.issy_bytes = l.issy; o.iscr_valid = l.iscr_valid; o.last_iscr = l.iscr; o.carried = l.c;
     o.selected = slot < sel.n; o.isi = o.selected ? sel.isi[slot] : -1;
+    o.hem_frames = l.hem;
     *h_out = o;
     return 0;
 }
@@ -1065,6 +1154,24 @@ int dvbs2gpu_bbts_ma_set_gse(dvbs2gpu_bbts* b, int on) {
         std::fill(m->fb_calls.begin(), m->fb_calls.end(), 0);
     }
     m->cfg.gse = on != 0;
+    return 0;
+}
+
+int dvbs2gpu_bbts_ma_set_t2_hem(dvbs2gpu_bbts* b, int on) {
+    if (!b) return DVBS2GPU_ERR_ARG;
+    const BbtsBankView v = bbts_view(b);
+    BbtsMa* m = *v.ma;
+    if (!m) { g_err = "ma_set_t2_hem: the mode-adaptation mode is off"; return DVBS2GPU_ERR_ARG; }
+    // every lane starts afresh, as after dvbs2gpu_bbts_select_isi: what is carried was cut by the other rules
+    std::vector<MaLaneState> z((size_t)v.nstreams * MA_LANES);
+    for (auto& l : z) l.issy = m->cfg.issy_bytes;
+    if (v.ctx) {
+        HIP_TRY(hipSetDevice(v.ctx->device));
+        HIP_TRY(hipMemcpy(m->d_lane[m->cur], z.data(), z.size() * sizeof(MaLaneState), hipMemcpyHostToDevice));
+    } else {
+        memcpy(m->host->st, z.data(), sizeof(m->host->st));
+    }
+    m->cfg.hem = on != 0;
     return 0;
 }
 

@@ -3,7 +3,8 @@
 frames resident in HBM.  Prints one JSON line: packets/s, frames/s, GB/s moved (read DFL/8 + write 188 per 188) against HBM.
 --ma: the same frames through the mode-adaptation mode (CCM sizes, SIS, no ISSY / NPD: the same bytes in and out, so the two figures
 compare like with like; MA_ISSY=2|3 and MA_NPD=1 in the environment add the fields, payload then from tests/ma_ref.py; MA_GSE=1 switches
-GSE decapsulation on for these TS-only frames).
+GSE decapsulation on for these TS-only frames; MA_HEM=1 feeds DVB-T2 high-efficiency-mode frames of the same data-field size instead, from
+tests/hem_ref.py, with dvbs2gpu_bbts_ma_set_t2_hem on: MA_NPD adds the DNP byte, MA_ISSY != 0 the ISSY field in the header).
 --gse: well-formed GSE data fields instead (the transmitter of tests/test_gpu_gse.py: 45 % of the packets complete PDUs of 40-1500 bytes,
 20 % START packets of PDUs cut into 2-5 fragments of 40-1400 bytes, the rest their continuations; 64 different streams repeated over the
 bank), for 4096, 64 and 1 streams x 8 frames per call, the device path and the forced host path (dvbs2gpu_bbts_set_gse_path) timed in
@@ -135,10 +136,17 @@ nfr = 4 * F
 pk = B.ts_packets(nfr * D // 188 + 2, rng)
 fr = torch.from_numpy(B.bbframes_from_ts(pk, KBCH, nfr)).cuda()
 bank = pkg.BbTsParserBank(eng, S, KBCH, F)
-MA = '--ma' in sys.argv
+MA, hem = '--ma' in sys.argv, False
 if MA:
     issy, npd = int(os.environ.get('MA_ISSY', '0')), int(os.environ.get('MA_NPD', '0'))
-    if issy or npd:
+    hem = os.environ.get('MA_HEM') == '1'
+    if hem:
+        import hem_ref as H
+        ts = H.make_ts(nfr * D // 187 + 2, rng, null_runs=False)
+        fr = torch.from_numpy(np.stack(H.frames_of_stream(H.slot_stream(ts, bool(npd)), H.slot_len(npd), [D], sis=True, issyi=issy > 0, npd=bool(npd),
+                                                            frame_bytes=fb)[:nfr])).cuda()
+        issy = 0
+    elif issy or npd:
         import ma_ref as M
         ts = M.make_ts(nfr * D // 188 + 2, rng, null_runs=False)
         st, _ = M.slot_stream(ts, issy, bool(npd))
@@ -146,6 +154,8 @@ if MA:
     bank.set_mode_adaptation(True, issy_bytes=issy)
     if os.environ.get('MA_GSE') == '1':             # the TS-only call of a bank that has GSE switched on (no GSE frame ever comes)
         bank.ma_set_gse(True)
+    if hem:
+        bank.ma_set_t2_hem(True)
 calls = [[fr[k * F:(k + 1) * F].reshape(-1).clone() for _ in range(S)] for k in range(4)]
 outs = [torch.zeros(F * fb + 376, dtype=torch.uint8, device='cuda') for _ in range(S)]
 if MA:
@@ -174,6 +184,6 @@ dt = (time.perf_counter() - t0) / (4 * reps)
 # check: the packets of the last call against the transmitted ones for stream 0 (stream state wrapped around the 4 calls: resync'd by SYNCD)
 o = outs[0][:nb[0]].cpu().numpy().reshape(-1, 188)
 assert np.all(o[:, 0] == 0x47)
-print(json.dumps({'mode': 'mode adaptation' if MA else 'reference', 'streams': S, 'frames_per_call': F, 'kbch': KBCH, 'ms_per_call': round(dt * 1e3, 3),
+print(json.dumps({'mode': ('mode adaptation, T2 HEM' if hem else 'mode adaptation') if MA else 'reference', 'streams': S, 'frames_per_call': F, 'kbch': KBCH, 'ms_per_call': round(dt * 1e3, 3),
                   'frames_per_s': round(S * F / dt), 'ts_packets_per_s': round(tot / 188 / (4 * reps) / dt),
                   'GB_per_s_read_plus_write': round((S * F * D + tot / (4 * reps)) / dt / 1e9, 1), 'includes': 'host arg upload + sync per call'}))
