@@ -512,7 +512,8 @@ int dvbs2gpu_dvbs_tail_get_tap(dvbs2gpu_dvbs_tail* t, int stream, int which, voi
 /* Stage entry (parity tests): RS(204,188) + the wrapper's stale-output rule + energy dispersal removal on `npackets` (a multiple of
  * 8) 204-byte packets supplied by the caller as stream 0's de-interleaved frames -- DVBSReedSolomon::decode and
  * DVBSScrambling::descramble without the deframer and the de-interleaver in front.  skip_rs != 0: the packets are taken as decoded
- * (descrambler alone).  HOST pointers; returns the TS bytes written to h_ts (188 per packet); taps 1-3 above then hold the
+ * (descrambler alone).  npackets is at most 8 * (max_bits / 13056 + 3), the frames one call on this handle can hold (DVBS2GPU_ERR_ARG
+ * beyond).  HOST pointers; returns the TS bytes written to h_ts (188 per packet); taps 1-3 above then hold the
  * corrected packets, the decoder status and the error counts.  Advances stream 0's dispersal / last-message state and overwrites the
  * handle's de-interleaved packets, status and frame counts: TEST HOOK, to be called on a handle of its own, never on one that is
  * receiving (calls are serialised per context like every other entry point). */

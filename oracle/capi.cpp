@@ -318,6 +318,8 @@ void* orc_dvbsrs_create() { return new DvbsRs(); }
 void orc_dvbsrs_destroy(void* h) { delete (DvbsRs*)h; }
 int orc_dvbsrs_decode(void* h, uint8_t* data204) { return ((DvbsRs*)h)->decode(data204); }
 int orc_rs255_decode(const uint8_t* enc255, uint8_t* msg239) { return rs255_decode(enc255, msg239); }
+// the same, and {locator order, root count} (tests/golden/make_rs_high_degree.py: successes with a locator of degree 9 .. 16)
+int orc_rs255_locator(const uint8_t* enc255, uint8_t* msg239, int* locator2) { return rs255_decode(enc255, msg239, locator2); }
 void* orc_dvbsdescr_create() { return new DvbsDescrambler(); }
 void orc_dvbsdescr_destroy(void* h) { delete (DvbsDescrambler*)h; }
 void orc_dvbsdescr_work(void* h, uint8_t* frm1632) { ((DvbsDescrambler*)h)->descramble(frm1632); }

@@ -90,7 +90,8 @@ static uint8_t eval_log_lut(const Gf256& F, const uint8_t* coeff_log, int order,
     return res;
 }
 
-int rs255_decode(const uint8_t* encoded, uint8_t* msg) {
+int rs255_decode(const uint8_t* encoded, uint8_t* msg, int* locator2) {
+    if (locator2) locator2[0] = locator2[1] = 0;
     const Gf256& F = gf256();
     const int MD = 16, N = 255;
     uint8_t recv[256];
@@ -145,6 +146,7 @@ int rs255_decode(const uint8_t* encoded, uint8_t* msg) {
         build_exp_lut(F, (uint8_t)e, MD - 1, lut);
         if (!eval_log_lut(F, loc_log, order, lut)) { if (nroots < 64) roots[nroots] = (uint8_t)e; nroots++; }
     }
+    if (locator2) { locator2[0] = order; locator2[1] = nroots; }
     if (nroots != order) return -1;
     // locations
     int locs[64];

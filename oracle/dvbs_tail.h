@@ -25,7 +25,8 @@ struct DvbsRs {                     // dsp::dvbs::DVBSReedSolomon (dvbs/dvbs_ree
     int decode(uint8_t* data204);   // in place on the first 188 bytes; returns the reference's error count
 };
 // correct_reed_solomon_decode for (255, 239), fcr 0, gap 1 (reed-solomon/decode.c:299-380): returns 239 or -1; msg untouched on -1
-int rs255_decode(const uint8_t* encoded255, uint8_t* msg239);
+// locator2 (optional): {order of the error locator after Berlekamp-Massey, roots the Chien search found}, {0, 0} for a codeword
+int rs255_decode(const uint8_t* encoded255, uint8_t* msg239, int* locator2 = nullptr);
 
 struct DvbsDescrambler {            // dsp::dvbs::DVBSScrambling (dvbs/dvbs_scrambling.h)
     int reg = 0;

@@ -764,6 +764,14 @@ __global__ __launch_bounds__(64) void dvbs_rs_kernel(uint8_t* __restrict__ deint
         if (lane == 0) s_nroots = base + __popcll(m);
         __syncthreads();
     }
+    // order <= 16 always, so `order > 16` never decides anything (it keeps roots[16], ev[16], der[16] safe by inspection).  From the recurrence above:
+    // numerrors only changes to i + 1 - numerrors, at a step i <= 15 with 2 * numerrors <= i, so numerrors <= 16; and loc_order <= numerrors, because
+    // `last` is the locator from before the last length change at step m (its order <= the length L' in force before that change, numerrors = m + 1 - L'
+    // since) and delay = i - m, so last_order + delay <= L' + i - m = i + 1 - numerrors, which is the new numerrors where the length changes and
+    // <= numerrors where it does not (2 * numerrors > i).  Order 9 .. 15 runs below like any other (the reference's power tables hold x^0 .. x^15).
+    // Order 16 needs numerrors = 0 at i = 15: S_0 .. S_14 = 0, S_15 != 0, the locator 1 + c x^16.  x -> x^16 is a bijection of GF(256), so that has
+    // ONE root and the packet fails here; the reference evaluates x^16 from one entry past its 16-entry tables (decode.c:289-292, polynomial.c), so
+    // its source does not define what it does with that one syndrome pattern (a word of weight >= 16 away from every codeword).
     if (s_nroots != order || order > 16) { if (lane == 0) status[(long)s * max_packets + p] = 0; return; }
     if (lane == 0) {
         // error evaluator = Lambda * S mod x^16 (polynomial.c:17-30), formal derivative (:74-87)

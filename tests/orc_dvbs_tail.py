@@ -22,6 +22,7 @@ def L():
         l.orc_tsdef_work.argtypes = [VP, VP, C.c_int, VP, VP]
         l.orc_dvbsrs_decode.argtypes = [VP, VP]
         l.orc_rs255_decode.argtypes = [VP, VP]
+        l.orc_rs255_locator.argtypes = [VP, VP, VP]
         l.orc_dvbsdescr_work.argtypes = [VP, VP]
         _b = True
     return l
@@ -96,6 +97,12 @@ def forney_interleave(data, state=None):
     return out, full[-len(hist):]
 
 
+def dvbs_coded_to_bits(coded):
+    """coded packets uint8 [n, 204] -> bits uint8 [n*204*8]: Forney interleaver, then bits MSB first (what dvbs_outer_tx does after the RS coder)"""
+    inter, _ = forney_interleave(np.ascontiguousarray(coded, np.uint8).reshape(-1))
+    return np.unpackbits(inter)
+
+
 def dvbs_outer_tx(npackets, seed):
     """npackets (multiple of 8) random TS packets -> (bits uint8 [npackets*204*8], ts [npackets, 188])"""
     rng = np.random.default_rng(seed)
@@ -112,9 +119,7 @@ def dvbs_outer_tx(npackets, seed):
         else:
             pkt[1:] ^= pr[188 * k:188 * k + 187]       # one PRBS byte is skipped over every non-inverted sync byte
         coded[p] = rs_encode_204(pkt)
-    inter, _ = forney_interleave(coded.reshape(-1))
-    bits = np.unpackbits(inter)
-    return bits, ts
+    return dvbs_coded_to_bits(coded), ts
 
 
 class OracleTail:
@@ -126,21 +131,55 @@ class OracleTail:
         self.hr, self.hs = VP(self.o.orc_dvbsrs_create()), VP(self.o.orc_dvbsdescr_create())
         self.last_rs = [0] * 8
         self.errs = np.zeros(2, np.int32)
+        self.call_status, self.call_rs = [], []          # per packet of the last call: rs255_decode produced a message, the wrapper's return value
 
     def process(self, bits):
         bits = np.ascontiguousarray(bits, np.uint8)
         frames = np.zeros(1632 * (bits.size // 13056 + 4), np.uint8)
         nf = self.o.orc_tsdef_work(self.hd, P(bits), bits.size, P(frames), P(self.errs)) if bits.size else 0
         out = []
+        self.call_status, self.call_rs = [], []
         for k in range(nf):
             f = np.ascontiguousarray(frames[1632 * k:1632 * (k + 1)])
             d = np.zeros(1632, np.uint8)
             self.ol.orc_forney_deinterleave(self.hf, P(f), P(d))
             for i in range(8):
                 pkt = np.ascontiguousarray(d[204 * i:204 * (i + 1)])
+                self.call_status.append(rs_decodes(self.o, pkt))
                 self.last_rs[i] = self.o.orc_dvbsrs_decode(self.hr, P(pkt))
+                self.call_rs.append(self.last_rs[i])
                 d[204 * i:204 * i + 188] = pkt[:188]
             self.o.orc_dvbsdescr_work(self.hs, P(d))
             for i in range(8):
                 out.append(d[204 * i:204 * i + 188].copy())
         return (np.concatenate(out) if out else np.zeros(0, np.uint8)), nf
+
+
+def rs_decodes(o, pkt204):
+    """1 where rs255_decode produces a message for the packet behind the wrapper's 51 zero bytes, 0 where it gives up"""
+    enc = np.concatenate([np.zeros(51, np.uint8), pkt204])
+    return int(o.orc_rs255_decode(P(enc), P(np.zeros(239, np.uint8))) == 239)
+
+
+class OracleRsStage:
+    """the RS wrapper and the descrambler on packets in order, with their state carried from call to call: what the stage entry
+    dvbs2gpu_dvbs_tail_rs_stage computes.  run() -> (ts uint8 [n, 188], status [n], wrapper return values [n], messages handed out [n, 188])"""
+
+    def __init__(self):
+        self.o = L()
+        self.hr, self.hs = VP(self.o.orc_dvbsrs_create()), VP(self.o.orc_dvbsdescr_create())
+
+    def run(self, packets, skip_rs=False):
+        packets = np.ascontiguousarray(packets, np.uint8)
+        n = len(packets)
+        assert n % 8 == 0
+        status, ret = np.ones(n, np.uint8), np.zeros(n, np.int32)
+        d = packets.copy()
+        if not skip_rs:
+            for k in range(n):
+                status[k] = rs_decodes(self.o, packets[k])
+                ret[k] = self.o.orc_dvbsrs_decode(self.hr, P(d[k]))          # (a row of a C-contiguous array: decoded in place)
+        msgs = d[:, :188].copy()
+        for f in range(n // 8):
+            self.o.orc_dvbsdescr_work(self.hs, P(d[8 * f:8 * f + 8]))
+        return d[:, :188].copy(), status, ret, msgs
