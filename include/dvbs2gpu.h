@@ -1255,6 +1255,154 @@ int dvbs2gpu_t2mi_get_row_table_device(dvbs2gpu_t2mi* b, int stream, int slot, c
  * slot's output buffer: d_bb[i], frame_bytes[i] and nframes[i] of dvbs2gpu_bbts_process_ma_batch. */
 int dvbs2gpu_t2mi_get_frame_bytes(dvbs2gpu_t2mi* b, int stream, int slot, int* h_sizes, int cap, int* n);
 
+/* ------------------------------------------------------------------ MPE bank (own extension)
+ * Nothing in the reference does this.  A transport-stream carrier may carry IP by Multi-Protocol Encapsulation (ETSI EN 301 192
+ * section 7): IP datagrams inside DSM-CC datagram_sections (table_id 0x3E) on one or more PIDs.  For `nstreams` transport streams in
+ * HBM a bank reassembles the sections of a PID, checks their CRC-32, applies a MAC address filter, finds the IPv4 or IPv6 datagram
+ * behind the MPE header (and LLC/SNAP), checks its header, writes one table row per section and lays the datagrams back to back in a
+ * device buffer.  The sequential form below is the definition (csrc/mpe_rules.h, MpeHostStream::run); the kernels give its results
+ * for every cutting of a stream into calls.  The syntax is written from memory of EN 301 192, RFC 791, RFC 8200 and RFC 1042; it is
+ * one struct, dvbs2gpu_mpe_layout.
+ *   Section: bytes b0 b1 b2, then section_length = (b1 << 8 | b2) & 0x0FFF more bytes: total = 3 + section_length <= 4096.
+ *     section_length > 4093 is the bad length.  datagram_section (b0 = 0x3E): b3 MAC_address_6, b4 MAC_address_5, b5 = 2 reserved |
+ *     payload_scrambling_control 2 | address_scrambling_control 2 | LLC_SNAP_flag | current_next, b6 section_number,
+ *     b7 last_section_number, b8 .. b11 MAC_address_4 .. MAC_address_1, the body from b12, the last four bytes a CRC-32/MPEG (initial
+ *     value 0xFFFFFFFF, polynomial 0x04C11DB7; the register over all `total` bytes is 0) when section_syntax_indicator (b1 >> 7) is
+ *     set, else a checksum.
+ *   Watches: 4 slots per stream, each empty (pid -1) or (PID 0..0x1FFE, mac_value[6], mac_mask[6]) in network order; an all-zero mask
+ *     means every address.  A new bank watches nothing.  THE SAME PID MAY SIT IN SEVERAL SLOTS of a stream (two MAC filters on one
+ *     PID): every slot is a complete, independent reassembler with its own state, counters, rows and output buffer.  Changing a slot's
+ *     watch starts it afresh.
+ *   Packet: 188 bytes at offset 188 k, classified as the TS monitor does: sync-byte errors, TEI packets and null packets are not looked
+ *     at.  A packet of the slot's PID counts in `packets` and, in this order ("drop" = the open section is forgotten; with fill > 0 it
+ *     counts in dropped_sections) -- the rules of the PSI section bank, one slot per reassembler:
+ *     1. TSC != 0: scrambled_packets, drop, the continuity step; done.
+ *     2. The continuity step (dvbs2gpu_tsmon_*: one state byte per slot).  Duplicate: ignored.  Continuity error or announced
+ *        discontinuity: drop, then go on with this packet.  No payload (AFC&1 = 0): done.
+ *     3. The payload starts at 4, or at 5 + b4 when AFC&2.  >= 188: malformed_packets, drop, done.
+ *     4. PUSI set: ptr = the first payload byte.  ptr > the bytes after it: malformed_packets, drop, done.  The ptr bytes after the
+ *        pointer go to an open section: if they complete it, it is emitted and what is left of them is ignored; if it is still
+ *        incomplete after them (an open header of one or two bytes too) it is dropped; if they complete a header with the bad length,
+ *        malformed_sections counts and the header is forgotten; with nothing open they are ignored.  Then section starts are parsed
+ *        behind them (6).
+ *     5. PUSI clear: the whole payload goes to an open section; if it completes it, it is emitted and the rest of the payload is
+ *        ignored; a header completed with the bad length counts in malformed_sections and is forgotten.  With nothing open the
+ *        payload is ignored.
+ *     6. At a section start, until the TS packet ends: the byte 0xFF is stuffing and ends the packet's chain.  Else bytes are buffered;
+ *        with three, total is known: the bad length counts in malformed_sections, forgets the header and ends the packet's chain; when
+ *        the buffered bytes reach total the section is emitted and the next byte is a section start.  A section, or a header of one or
+ *        two bytes, that the TS packet's end cuts stays open, across calls too.
+ *   Emitting: every emitted section is one row and counts in `sections`.  In this order; the first rule that fires ends the list (but
+ *     UNCHECKED, which goes on), and the fields of the row that later rules would set are 0:
+ *     1. b0 != 0x3E: flag OTHER_TABLE, other_table.  No CRC is taken.
+ *     2. total < 16 (12 header bytes + 4): flag MALFORMED, malformed_sections.
+ *     3. section_syntax_indicator set: the CRC-32 over all bytes must be 0, else flag CRC_ERROR, crc_errors.  Clear: the last four
+ *        bytes are a checksum of ISO/IEC 13818-6 whose definition is not at hand; it is NOT verified: flag UNCHECKED, `unchecked`,
+ *        and the list goes on.
+ *     4. mac[0..5] = b11, b10, b9, b8, b4, b3; payload_scrambling = b5 >> 4 & 3, address_scrambling = b5 >> 2 & 3, llc_snap =
+ *        b5 >> 1 & 1; section_number = b6, last_section_number = b7.
+ *     5. Either scrambling field != 0: flag SCRAMBLED, scrambled_sections.
+ *     6. ((mac[k] ^ mac_value[k]) & mac_mask[k]) != 0 for a k: flag FILTERED, `filtered`.
+ *     7. section_number != 0 or last_section_number != 0: flag FRAGMENT, `fragments`.  A datagram over several sections is NOT put
+ *        together; the rows carry both numbers.
+ *     8. body = bytes [12, total - 4).  With llc_snap the body needs at least 8 bytes that start AA AA 03 00 00 00, else flag
+ *        OTHER_PROTOCOL, other_protocol (ethertype stays 0); `ethertype` = the next two bytes, big-endian; 0x0800 / 0x86DD means IPv4 /
+ *        IPv6 from body + 8 (the version nibble is not looked at); any other ethertype: OTHER_PROTOCOL.  Without llc_snap ethertype is
+ *        0 and the high nibble of the first body byte says 4 / 6; any other value, or an empty body: OTHER_PROTOCOL.  avail = the body
+ *        bytes from the IP header on.
+ *     9. IPv4 (header bytes i0 ..): avail >= 20; IHL = i0 & 15 >= 5 and 4 IHL <= avail; total_length = i2 << 8 | i3 with 4 IHL <=
+ *        total_length <= avail; the ones'-complement sum of the 2 IHL big-endian 16-bit header words, carries folded in, is 0xFFFF.
+ *        If one does not hold: flag BAD_IP, bad_ip.  Else family 4, bytes = total_length, stuffing = avail - total_length, protocol =
+ *        i9, src4 / dst4 = i12..i15 / i16..i19 as big-endian numbers; when protocol is 6 or 17, the fragment offset ((i6 << 8 | i7) &
+ *        0x1FFF) is 0 and total_length >= 4 IHL + 4: src_port / dst_port = the two big-endian numbers at 4 IHL.
+ *    10. IPv6: avail >= 40 and 40 + payload_length (i4 << 8 | i5) <= avail, else BAD_IP.  family 6, bytes = 40 + payload_length,
+ *        stuffing the rest, protocol = next_header (i6); ports from i40 when it is 6 or 17 and payload_length >= 4 (extension headers
+ *        are not followed).  src4 / dst4 stay 0: the addresses are in the delivered bytes.
+ *    11. A row that reached 9 or 10 without BAD_IP has flag DATAGRAM and counts in `datagrams`.  It is delivered when the call has
+ *        output buffers: its `bytes` (from the IP header on, without the stuffing) go to the slot's output buffer, back to back in
+ *        row order, and row.offset names them; datagrams_delivered and bytes_delivered count.  Every other row has offset -1.
+ *   Row: ordered by the TS packet that held the section's last byte, then by position in it.  One table per (stream, slot).
+ *   Capacity: sizes first.  If a slot's bytes exceed cap or its rows exceed max_rows the call returns DVBS2GPU_ERR_CAPACITY,
+ *     out_bytes[] holds the byte sizes (-1 for a slot whose rows did not fit: its sections were not checked) and out_rows[] the row
+ *     counts; no state or counter of any stream has advanced, the tables of the call are empty, the call can be repeated.
+ *   State survives from call to call.  reset forgets state, positions and counters; watches stay.
+ *   Limits: max_packets <= 4096 per stream and call.  Memory (device banks) per (stream, slot): a 4096-byte section buffer, 6 bytes per
+ *     packet of max_packets and 64 bytes per row of max_rows.
+ *   NOT done: datagrams split over several sections; the 13818-6 checksum; MPE-FEC (table_id 0x78) and the time-slicing parameters
+ *     that then stand in the MAC bytes; ULE; IP-level filters (the rows carry what a caller filters on); finding MPE PIDs by
+ *     data_broadcast_id. */
+typedef struct dvbs2gpu_mpe dvbs2gpu_mpe;
+typedef struct dvbs2gpu_mpe_layout {
+    int32_t header_bytes, length_mask, max_section_length, max_section_bytes, table_id, mpe_header_bytes, crc_bytes, min_section_bytes;
+    int32_t mac_at[6];               /* of MAC_address_1 .. MAC_address_6 */
+    int32_t flags_at, section_number_at, last_section_number_at, llc_snap_bytes, ethertype_at, ethertype_ipv4, ethertype_ipv6;
+    int32_t ipv4_min_header, ipv4_total_length_at, ipv4_fragment_at, ipv4_protocol_at, ipv4_src_at, ipv4_dst_at;
+    int32_t ipv6_header, ipv6_payload_length_at, ipv6_next_header_at;
+    int32_t head_bytes;              /* the leading bytes of a section that decide its row, at most: 84 */
+} dvbs2gpu_mpe_layout;
+int dvbs2gpu_mpe_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_mpe** out);
+/* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_mpe_work only */
+int dvbs2gpu_mpe_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_mpe** out);
+int dvbs2gpu_mpe_reset(dvbs2gpu_mpe* b);
+void dvbs2gpu_mpe_destroy(dvbs2gpu_mpe* b);
+int dvbs2gpu_mpe_get_layout(dvbs2gpu_mpe_layout* h_out);
+/* slot 0..3; pid 0..0x1FFE, or -1: the slot is empty; mac_value / mac_mask: six bytes each in network order, NULL: all zero */
+int dvbs2gpu_mpe_set_watch(dvbs2gpu_mpe* b, int stream, int slot, int pid, const uint8_t mac_value[6], const uint8_t mac_mask[6]);
+/* d_ts[i]: DEVICE pointer to nbytes[i] bytes (a multiple of 188, at most 188*max_packets) of stream i, of any alignment.  d_out NULL:
+ * rows and counters only (never a capacity failure for bytes; out_bytes may be NULL).  Else d_out[i*4 + k]: DEVICE buffer of cap bytes
+ * for the datagrams of slot k of stream i (NULL for an empty slot); out_bytes[i*4 + k] (host) their bytes.  out_rows[i*4 + k] (host, may
+ * be NULL): the row counts.  Two kernel launches.  Synchronous on `stream`; chained behind a packetiser or monitor call on the same
+ * stream, no packet visits the host. */
+int dvbs2gpu_mpe_process_batch(dvbs2gpu_mpe* b, const uint8_t* const* d_ts, const int* nbytes, uint8_t* const* d_out, int cap, int* out_bytes,
+                               int* out_rows, void* stream);
+/* one stream and slot of any bank with HOST buffers (h_out NULL: rows and counters only): returns the bytes written to h_out or a
+ * negative error.  Every other slot of the bank receives an empty call. */
+int dvbs2gpu_mpe_work(dvbs2gpu_mpe* b, int stream, int slot, const uint8_t* h_ts, int nbytes, uint8_t* h_out, int cap);
+/* the byte and row sizes that the slot's last call needed, whether it succeeded or failed for capacity */
+int dvbs2gpu_mpe_get_needed(dvbs2gpu_mpe* b, int stream, int slot, int* bytes, int* rows);
+typedef struct dvbs2gpu_mpe_stats {            /* of a slot, since creation, reset or the slot's last set_watch; kept on the host */
+    int64_t packets;                 /* trusted TS packets of the slot's PID */
+    int64_t sections;                /* rows */
+    int64_t other_table, crc_errors, unchecked, scrambled_sections, filtered, fragments, other_protocol, bad_ip;
+    int64_t datagrams;               /* rows with DATAGRAM, delivered or not */
+    int64_t datagrams_delivered, bytes_delivered;
+    int64_t dropped_sections;        /* open sections forgotten */
+    int64_t malformed_sections;      /* the bad length, and rows with MALFORMED */
+    int64_t malformed_packets, scrambled_packets;   /* TS packets */
+} dvbs2gpu_mpe_stats;
+/* slot -1: the sum over the stream's slots */
+int dvbs2gpu_mpe_get_stats(dvbs2gpu_mpe* b, int stream, int slot, dvbs2gpu_mpe_stats* h_out);
+#define DVBS2GPU_MPE_OTHER_TABLE 1
+#define DVBS2GPU_MPE_MALFORMED 2
+#define DVBS2GPU_MPE_CRC_ERROR 4
+#define DVBS2GPU_MPE_UNCHECKED 8
+#define DVBS2GPU_MPE_SCRAMBLED 16
+#define DVBS2GPU_MPE_FILTERED 32
+#define DVBS2GPU_MPE_FRAGMENT 64
+#define DVBS2GPU_MPE_OTHER_PROTOCOL 128
+#define DVBS2GPU_MPE_BAD_IP 256
+#define DVBS2GPU_MPE_DATAGRAM 512
+typedef struct dvbs2gpu_mpe_row {              /* 48 bytes */
+    uint16_t flags;
+    uint8_t family;                  /* 4 or 6 of a DATAGRAM row, else 0 */
+    uint8_t protocol;                /* IPv4 protocol / IPv6 next_header */
+    uint8_t mac[6];                  /* network order; of a row that reached rule 4 */
+    uint8_t section_number, last_section_number;
+    uint16_t src_port, dst_port;     /* of an unfragmented TCP or UDP datagram, else 0 */
+    uint32_t src4, dst4;             /* IPv4 addresses as big-endian numbers; 0 for IPv6 */
+    int32_t length;                  /* total bytes of the section */
+    int32_t offset;                  /* of the datagram in the slot's output buffer; -1: not delivered */
+    int32_t bytes;                   /* of the datagram of a DATAGRAM row, delivered or not; else 0 */
+    int32_t first_packet;            /* index in this call of the TS packet that held its first byte; -1: an earlier call */
+    int32_t last_packet;             /* and of the one that held its last byte */
+    uint16_t ethertype;              /* of a right LLC/SNAP header, else 0 */
+    uint16_t stuffing;               /* body bytes behind the datagram */
+} dvbs2gpu_mpe_row;
+/* h_rows[cap] (host); *n = rows of the slot's last call, of which min(*n, cap) are written */
+int dvbs2gpu_mpe_get_row_table(dvbs2gpu_mpe* b, int stream, int slot, dvbs2gpu_mpe_row* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_mpe_get_row_table_device(dvbs2gpu_mpe* b, int stream, int slot, const dvbs2gpu_mpe_row** d_rows, int* n);
+
 #ifdef __cplusplus
 }
 #endif

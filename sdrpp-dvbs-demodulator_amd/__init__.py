@@ -204,6 +204,30 @@ class T2miRow(C.Structure):
                 ('bbframe_bytes', C.c_int32), ('first_packet', C.c_int32), ('last_packet', C.c_int32)]
 
 
+class MpeLayout(C.Structure):
+    """dvbs2gpu_mpe_layout"""
+    _fields_ = ([(k, C.c_int32) for k in ('header_bytes', 'length_mask', 'max_section_length', 'max_section_bytes', 'table_id', 'mpe_header_bytes', 'crc_bytes',
+                                          'min_section_bytes')] + [('mac_at', C.c_int32 * 6)] +
+                [(k, C.c_int32) for k in ('flags_at', 'section_number_at', 'last_section_number_at', 'llc_snap_bytes', 'ethertype_at', 'ethertype_ipv4',
+                                          'ethertype_ipv6', 'ipv4_min_header', 'ipv4_total_length_at', 'ipv4_fragment_at', 'ipv4_protocol_at', 'ipv4_src_at',
+                                          'ipv4_dst_at', 'ipv6_header', 'ipv6_payload_length_at', 'ipv6_next_header_at', 'head_bytes')])
+
+
+class MpeStats(C.Structure):
+    """dvbs2gpu_mpe_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('packets', 'sections', 'other_table', 'crc_errors', 'unchecked', 'scrambled_sections', 'filtered', 'fragments',
+                                         'other_protocol', 'bad_ip', 'datagrams', 'datagrams_delivered', 'bytes_delivered', 'dropped_sections',
+                                         'malformed_sections', 'malformed_packets', 'scrambled_packets')]
+
+
+class MpeRow(C.Structure):
+    """dvbs2gpu_mpe_row"""
+    _fields_ = [('flags', C.c_uint16), ('family', C.c_uint8), ('protocol', C.c_uint8), ('mac', C.c_uint8 * 6), ('section_number', C.c_uint8),
+                ('last_section_number', C.c_uint8), ('src_port', C.c_uint16), ('dst_port', C.c_uint16), ('src4', C.c_uint32), ('dst4', C.c_uint32),
+                ('length', C.c_int32), ('offset', C.c_int32), ('bytes', C.c_int32), ('first_packet', C.c_int32), ('last_packet', C.c_int32),
+                ('ethertype', C.c_uint16), ('stuffing', C.c_uint16)]
+
+
 class FrameQuality(C.Structure):
     """dvbs2gpu_frame_quality"""
     _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('gain', C.c_float), ('phase', C.c_float), ('known_symbols', C.c_int32),
@@ -411,6 +435,18 @@ PROTOTYPES = {
     'dvbs2gpu_t2mi_get_row_table': (_i, [_vp, _i, _i, C.POINTER(T2miRow), _i, C.POINTER(_i)]),
     'dvbs2gpu_t2mi_get_row_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
     'dvbs2gpu_t2mi_get_frame_bytes': (_i, [_vp, _i, _i, C.POINTER(_i), _i, C.POINTER(_i)]),
+    'dvbs2gpu_mpe_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_mpe_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_mpe_reset': (_i, [_vp]),
+    'dvbs2gpu_mpe_destroy': (None, [_vp]),
+    'dvbs2gpu_mpe_get_layout': (_i, [C.POINTER(MpeLayout)]),
+    'dvbs2gpu_mpe_set_watch': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    'dvbs2gpu_mpe_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    'dvbs2gpu_mpe_work': (_i, [_vp, _i, _i, _vp, _i, _vp, _i]),
+    'dvbs2gpu_mpe_get_needed': (_i, [_vp, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    'dvbs2gpu_mpe_get_stats': (_i, [_vp, _i, _i, C.POINTER(MpeStats)]),
+    'dvbs2gpu_mpe_get_row_table': (_i, [_vp, _i, _i, C.POINTER(MpeRow), _i, C.POINTER(_i)]),
+    'dvbs2gpu_mpe_get_row_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
 }
 
 _lib = None
@@ -1811,6 +1847,134 @@ class T2miBank(_TsBank):
         """the sizes of the BBFRAMEs that the slot's last call delivered, in order: with the slot's output buffer, the frame_bytes and
         nframes of BbTsParserBank.process_ma"""
         return [int(v) for v in self._rows(self.lib.dvbs2gpu_t2mi_get_frame_bytes, C.c_int, int(stream), int(slot))]
+
+
+class MpeBank(_TsBank):
+    """MPE bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, MPE bank): the DSM-CC datagram_sections of a PID are
+    reassembled, their CRC-32 checked, a MAC filter applied and the IPv4 / IPv6 header behind the MPE header (and LLC/SNAP) checked, one
+    table row per section, and the IP datagrams laid back to back in a device buffer.  Four slots per stream, each a (PID, MAC value,
+    MAC mask) and a reassembler of its own: the same PID may sit in several slots."""
+    _destroy = 'dvbs2gpu_mpe_destroy'
+    SLOTS = 4
+    OTHER_TABLE, MALFORMED, CRC_ERROR, UNCHECKED, SCRAMBLED, FILTERED, FRAGMENT, OTHER_PROTOCOL, BAD_IP, DATAGRAM = (1 << k for k in range(10))
+    DSMCC_STREAM_TYPES = (0x0A, 0x0D)                                # multi-protocol encapsulation, DSM-CC sections
+    ROW_KEYS = tuple(k for k, _ in MpeRow._fields_)
+
+    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=1024):
+        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
+        h = C.c_void_p()
+        engine._check(self.lib.dvbs2gpu_mpe_create(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
+        self.h = h
+        self._watched = [{} for _ in range(nstreams)]               # per stream: slot -> PID, as set_watch left them
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096, max_rows=1024):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        self = cls._host('dvbs2gpu_mpe_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
+        self._watched = [{} for _ in range(nstreams)]
+        return self
+
+    @staticmethod
+    def layout():
+        """the section and IP syntax the library relies on (dvbs2gpu_mpe_layout) as a dict; mac_at: a list of six"""
+        lay = MpeLayout()
+        load_library().dvbs2gpu_mpe_get_layout(C.byref(lay))
+        return {k: [int(v) for v in getattr(lay, k)] if k == 'mac_at' else int(getattr(lay, k)) for k, _ in MpeLayout._fields_}
+
+    def reset(self):
+        self._check(self.lib.dvbs2gpu_mpe_reset(self.h))
+
+    def set_watch(self, stream, slot, pid, mac=None, mask=None):
+        """pid -1 empties the slot; mac / mask: six bytes each in network order (None: all zero; an all-zero mask takes every address);
+        the slot starts afresh"""
+        six = lambda v: None if v is None else (C.c_uint8 * 6)(*bytes(v))
+        if any(v is not None and len(bytes(v)) != 6 for v in (mac, mask)):
+            raise ValueError('a MAC address or mask has six bytes')
+        self._check(self.lib.dvbs2gpu_mpe_set_watch(self.h, int(stream), int(slot), int(pid), six(mac), six(mask)))
+        self._watched[int(stream)].pop(int(slot), None)
+        if pid >= 0:
+            self._watched[int(stream)][int(slot)] = int(pid)
+
+    def follow_pmts(self, psi_bank, stream=0, stream_types=DSMCC_STREAM_TYPES):
+        """watches the elementary PIDs with one of `stream_types` in the PMTs that `psi_bank` (a PsiBank that read the same stream) holds
+        decoded, in free slots and with no MAC filter, in the order of its slots and then of each PMT's elementary streams; PIDs watched
+        already are skipped -> the PIDs that found no free slot.  The PMT views carry no descriptors, so a data_broadcast_id is not
+        looked at: an object-carousel PID caught this way only yields OTHER_TABLE rows."""
+        watched = self._watched[int(stream)]
+        left = []
+        for slot in range(psi_bank.SLOTS):
+            hdr, es = psi_bank.program_map(stream, slot)
+            if hdr['program_number'] < 0:
+                continue
+            for stream_type, pid in es:
+                if stream_type not in stream_types or pid >= 0x1FFF or pid in watched.values() or pid in left:
+                    continue
+                free = [s for s in range(self.SLOTS) if s not in watched]
+                if free:
+                    self.set_watch(stream, free[0], pid)
+                else:
+                    left.append(pid)
+        return left
+
+    def process(self, ts_tensors, out_tensors=None, nbytes=None):
+        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors: None for rows and counters
+        only, else out_tensors[i][k]: the uint8 CUDA buffer that receives the datagrams of slot k of stream i (None for an empty slot)
+        -> byte counts [i][k].  Dvbs2GpuError -5 carries .needed and .rows ([i][k] each) when a buffer or max_rows is too small
+        (nothing has advanced then)."""
+        n, S = self.nstreams, self.SLOTS
+        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
+        pout, cap = None, 0
+        if out_tensors is not None:
+            flat = [t for per in out_tensors for t in (list(per) + [None] * S)[:S]]
+            pout = (C.c_void_p * (n * S))(*[None if t is None else t.data_ptr() for t in flat])
+            cap = min([int(t.numel()) for t in flat if t is not None] or [0])
+        nb, nr = (C.c_int * (n * S))(), (C.c_int * (n * S))()
+        rc = self.lib.dvbs2gpu_mpe_process_batch(self.h, pin, cnt, pout, cap, nb, nr, self.eng._stream())
+        split = lambda a: [list(a[i * S:(i + 1) * S]) for i in range(n)]
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            e.needed, e.rows = split(nb), split(nr)
+            raise e
+        return split(nb)
+
+    def work(self, ts, stream=0, slot=0, cap=None, deliver=True):
+        """one stream and slot, host buffers: numpy uint8 packets in -> the delivered datagrams back to back (numpy uint8), or None with
+        deliver=False (rows and counters only)"""
+        import numpy as np
+        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
+        cap = ts.size + 4096 if cap is None else cap
+        out = np.zeros(max(cap, 1), np.uint8) if deliver else None
+        rc = self.lib.dvbs2gpu_mpe_work(self.h, int(stream), int(slot), C.c_void_p(ts.ctypes.data), ts.size,
+                                        C.c_void_p(out.ctypes.data) if deliver else None, cap if deliver else 0)
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            nb, nr = C.c_int(), C.c_int()
+            self.lib.dvbs2gpu_mpe_get_needed(self.h, int(stream), int(slot), C.byref(nb), C.byref(nr))
+            e.needed, e.rows = nb.value, nr.value
+            raise e
+        return out[:rc].copy() if deliver else None
+
+    def needed(self, stream=0, slot=0):
+        """(bytes, rows) that the slot's last call needed, whether it succeeded or failed for capacity (bytes -1: the rows did not fit)"""
+        nb, nr = C.c_int(), C.c_int()
+        self._check(self.lib.dvbs2gpu_mpe_get_needed(self.h, int(stream), int(slot), C.byref(nb), C.byref(nr)))
+        return nb.value, nr.value
+
+    def stats(self, stream=0, slot=-1):
+        st = MpeStats()
+        self._check(self.lib.dvbs2gpu_mpe_get_stats(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in MpeStats._fields_}
+
+    def row_table(self, stream=0, slot=0):
+        """one dict per section of the slot's last call (the fields of dvbs2gpu_mpe_row; mac: six bytes), in row order"""
+        rows = self._rows(self.lib.dvbs2gpu_mpe_get_row_table, MpeRow, int(stream), int(slot))
+        return [{k: bytes(r.mac) if k == 'mac' else int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows]
+
+    def row_table_device(self, stream=0, slot=0):
+        """(device pointer or None, rows): the same table as dvbs2gpu_mpe_row records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self.lib.dvbs2gpu_mpe_get_row_table_device(self.h, int(stream), int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
 
 
 class SegmentReceiver(_Handle):

@@ -1,0 +1,229 @@
+// The rules of the MPE bank (own extension; include/dvbs2gpu.h), each stated once and shared by the kernels
+// (mpe.hip), the native host bank (MpeHostStream below, behind dvbs2gpu_mpe_create_host) and a plain C++ test program: the layout of a
+// DSM-CC datagram_section and of the IP headers behind it as one struct (MpeLayout), what a TS packet of a slot's PID does to the slot,
+// and what an emitted section's row says.
+//
+// The sequential form -- MpeHostStream::run, which is ts_reasm_run with this format -- IS the definition; every other form must give
+// its results for every cutting of a stream into calls.  The syntax is written from memory of ETSI EN 301 192 (section 7), RFC 791,
+// RFC 8200 and RFC 1042: every offset and limit the code relies on is a field of MpeLayout, reported through dvbs2gpu_mpe_get_layout
+// and compared with the tests' model.
+// Standard headers only: the host tests compile this file with a plain C++ compiler.
+#pragma once
+#include "ts_reasm_rules.h"
+
+#include <cstring>
+#include <vector>
+
+namespace s2 {
+
+struct MpeLayout {                     // the layout of dvbs2gpu_mpe_layout (mpe.hip asserts it)
+    int32_t header_bytes;              // table_id, then 4 flag bits and the 12-bit section_length: 3
+    int32_t length_mask;               // of (b1 << 8 | b2): 0x0FFF
+    int32_t max_section_length;        // 4093: a section is at most 4096 bytes
+    int32_t max_section_bytes;         // 4096
+    int32_t table_id;                  // datagram_section: 0x3E
+    int32_t mpe_header_bytes;          // up to and with last_section_number: 12
+    int32_t crc_bytes;                 // CRC-32 or checksum: 4
+    int32_t min_section_bytes;         // 16
+    int32_t mac_at[6];                 // MAC_address_1 .. MAC_address_6 (network order): 11, 10, 9, 8, 4, 3
+    int32_t flags_at;                  // 2 reserved, payload_scrambling 2, address_scrambling 2, LLC_SNAP_flag, current_next: 5
+    int32_t section_number_at, last_section_number_at;     // 6, 7
+    int32_t llc_snap_bytes;            // AA AA 03 00 00 00 and the EtherType: 8
+    int32_t ethertype_at;              // in the LLC/SNAP header: 6
+    int32_t ethertype_ipv4, ethertype_ipv6;                // 0x0800, 0x86DD
+    int32_t ipv4_min_header;           // 20
+    int32_t ipv4_total_length_at, ipv4_fragment_at, ipv4_protocol_at, ipv4_src_at, ipv4_dst_at;   // 2, 6, 9, 12, 16
+    int32_t ipv6_header;               // 40
+    int32_t ipv6_payload_length_at, ipv6_next_header_at;   // 4, 6
+    int32_t head_bytes;                // a row is decided from the first 12 + 8 + 60 + 4 = 84 bytes of its section at most
+};
+constexpr MpeLayout MPE = {3, 0x0FFF, 4093, 4096, 0x3E, 12, 4, 16, {11, 10, 9, 8, 4, 3}, 5, 6, 7, 8, 6, 0x0800, 0x86DD, 20, 2, 6, 9, 12, 16, 40, 4, 6, 84};
+
+constexpr int MPE_SLOTS = 4, MPE_BUF = 4096;
+// row flags (DVBS2GPU_MPE_*)
+constexpr int MPE_OTHER_TABLE = 1, MPE_MALFORMED = 2, MPE_CRC_ERROR = 4, MPE_UNCHECKED = 8, MPE_SCRAMBLED = 16, MPE_FILTERED = 32, MPE_FRAGMENT = 64,
+              MPE_OTHER_PROTOCOL = 128, MPE_BAD_IP = 256, MPE_DATAGRAM = 512;
+
+struct MpeWatch { int32_t pid; uint8_t mac_value[6], mac_mask[6]; };       // pid -1: the slot is empty; an all-zero mask: every address
+// the counters one call adds to a slot's statistics (dvbs2gpu_mpe_stats, as 32-bit shares)
+struct MpeCnt { int32_t packets, sections, other_table, crc_errors, unchecked, scrambled_sections, filtered, fragments, other_protocol, bad_ip, datagrams,
+                        datagrams_delivered, bytes_delivered, dropped_sections, malformed_sections, malformed_packets, scrambled_packets; };
+constexpr int MPE_NCNT = 17;
+enum { MPC_PACKETS = 0, MPC_SECTIONS, MPC_OTHER_TABLE, MPC_CRC, MPC_UNCHECKED, MPC_SCR_SECTIONS, MPC_FILTERED, MPC_FRAGMENTS, MPC_OTHER_PROTOCOL, MPC_BAD_IP,
+       MPC_DATAGRAMS, MPC_DELIVERED, MPC_BYTES, MPC_DROPPED, MPC_MALSEC, MPC_MALPKT, MPC_SCR };
+// one emitted section; the layout of dvbs2gpu_mpe_row
+struct MpeRow {
+    uint16_t flags;
+    uint8_t family, protocol;
+    uint8_t mac[6];
+    uint8_t section_number, last_section_number;
+    uint16_t src_port, dst_port;
+    uint32_t src4, dst4;
+    int32_t length, offset, bytes, first_packet, last_packet;
+    uint16_t ethertype, stuffing;
+};
+
+// a section's bytes from its second and third byte; -1: section_length is beyond 4093, the bad length
+TS_HD inline int mpe_total(unsigned b1, unsigned b2) {
+    const int n = (int)((b1 << 8 | b2) & (unsigned)MPE.length_mask);
+    return n > MPE.max_section_length ? -1 : MPE.header_bytes + n;
+}
+// is the CRC-32 of an emitted section taken: not of another table, not of one too short, not with section_syntax_indicator clear
+TS_HD inline bool mpe_takes_crc(unsigned b0, unsigned b1, int total) { return (int)b0 == MPE.table_id && total >= MPE.min_section_bytes && (b1 >> 7); }
+
+// The row of an emitted section.  s: its leading bytes and the two reductions the rules take over them, so that a wave can take them
+// with a lane per term --  s.rd(i): byte i, asked for i < total only;  s.any(n, f): is f(k) true for a k in [0, n);  s.sum(n, f): the
+// sum of f(k) over [0, n); n <= 64.  crc_ok: the CRC-32 over the section is 0 (looked at where mpe_takes_crc).  The offset is the caller's.
+template <typename Src>
+TS_HD inline MpeRow mpe_row_fields(const Src& s, int total, bool crc_ok, const MpeWatch& w, int first_packet, int last_packet) {
+    MpeRow r = {};
+    r.length = total; r.offset = -1; r.first_packet = first_packet; r.last_packet = last_packet;
+    if ((int)s.rd(0) != MPE.table_id) { r.flags = MPE_OTHER_TABLE; return r; }
+    if (total < MPE.min_section_bytes) { r.flags = MPE_MALFORMED; return r; }
+    if (!(s.rd(1) >> 7)) r.flags = MPE_UNCHECKED;
+    else if (!crc_ok) { r.flags = MPE_CRC_ERROR; return r; }
+    for (int k = 0; k < 6; ++k) r.mac[k] = (uint8_t)s.rd(MPE.mac_at[k]);
+    const unsigned fl = s.rd(MPE.flags_at);
+    r.section_number = (uint8_t)s.rd(MPE.section_number_at); r.last_section_number = (uint8_t)s.rd(MPE.last_section_number_at);
+    if ((fl >> 4 & 3) || (fl >> 2 & 3)) { r.flags |= MPE_SCRAMBLED; return r; }
+    if (s.any(6, [&](int k) { return ((s.rd(MPE.mac_at[k]) ^ w.mac_value[k]) & w.mac_mask[k]) != 0; })) { r.flags |= MPE_FILTERED; return r; }
+    if (r.section_number || r.last_section_number) { r.flags |= MPE_FRAGMENT; return r; }
+    int at = MPE.mpe_header_bytes, family;
+    const int end = total - MPE.crc_bytes;                 // the body is [at, end)
+    if (fl >> 1 & 1) {
+        if (end - at < MPE.llc_snap_bytes || s.rd(at) != 0xAA || s.rd(at + 1) != 0xAA || s.rd(at + 2) != 0x03 || s.rd(at + 3) || s.rd(at + 4) || s.rd(at + 5)) {
+            r.flags |= MPE_OTHER_PROTOCOL;
+            return r;
+        }
+        r.ethertype = (uint16_t)(s.rd(at + MPE.ethertype_at) << 8 | s.rd(at + MPE.ethertype_at + 1));
+        family = r.ethertype == MPE.ethertype_ipv4 ? 4 : r.ethertype == MPE.ethertype_ipv6 ? 6 : 0;
+        at += MPE.llc_snap_bytes;
+    } else {
+        family = end > at ? (int)(s.rd(at) >> 4) : 0;
+    }
+    if (family != 4 && family != 6) { r.flags |= MPE_OTHER_PROTOCOL; return r; }
+    const int avail = end - at;
+    int ports_at = -1;
+    if (family == 4) {
+        const int hl = avail >= MPE.ipv4_min_header ? 4 * (int)(s.rd(at) & 15) : 0;
+        const int tl = hl ? (int)(s.rd(at + MPE.ipv4_total_length_at) << 8 | s.rd(at + MPE.ipv4_total_length_at + 1)) : 0;
+        if (hl < MPE.ipv4_min_header || hl > avail || tl < hl || tl > avail) { r.flags |= MPE_BAD_IP; return r; }
+        unsigned sum = s.sum(hl / 2, [&](int k) { return s.rd(at + 2 * k) << 8 | s.rd(at + 2 * k + 1); });
+        sum = (sum & 0xFFFF) + (sum >> 16); sum = (sum & 0xFFFF) + (sum >> 16);
+        if (sum != 0xFFFF) { r.flags |= MPE_BAD_IP; return r; }
+        auto be32 = [&](int i) { return (uint32_t)(s.rd(i) << 24 | s.rd(i + 1) << 16 | s.rd(i + 2) << 8 | s.rd(i + 3)); };
+        r.bytes = tl; r.protocol = (uint8_t)s.rd(at + MPE.ipv4_protocol_at);
+        r.src4 = be32(at + MPE.ipv4_src_at); r.dst4 = be32(at + MPE.ipv4_dst_at);
+        const unsigned frag = (s.rd(at + MPE.ipv4_fragment_at) << 8 | s.rd(at + MPE.ipv4_fragment_at + 1)) & 0x1FFF;
+        if (frag == 0 && tl >= hl + 4) ports_at = at + hl;
+    } else {
+        const int pl = avail >= MPE.ipv6_header ? (int)(s.rd(at + MPE.ipv6_payload_length_at) << 8 | s.rd(at + MPE.ipv6_payload_length_at + 1)) : 0;
+        if (avail < MPE.ipv6_header || MPE.ipv6_header + pl > avail) { r.flags |= MPE_BAD_IP; return r; }
+        r.bytes = MPE.ipv6_header + pl; r.protocol = (uint8_t)s.rd(at + MPE.ipv6_next_header_at);
+        if (pl >= 4) ports_at = at + MPE.ipv6_header;
+    }
+    r.family = (uint8_t)family; r.stuffing = (uint16_t)(avail - r.bytes);
+    if (ports_at >= 0 && (r.protocol == 6 || r.protocol == 17)) {
+        r.src_port = (uint16_t)(s.rd(ports_at) << 8 | s.rd(ports_at + 1)); r.dst_port = (uint16_t)(s.rd(ports_at + 2) << 8 | s.rd(ports_at + 3));
+    }
+    r.flags |= MPE_DATAGRAM;
+    return r;
+}
+// where the datagram of a DATAGRAM row starts in its section: behind the MPE header, and behind LLC/SNAP where there was one
+TS_HD inline int mpe_ip_at(const MpeRow& r) { return MPE.mpe_header_bytes + (r.ethertype ? MPE.llc_snap_bytes : 0); }
+// the counters that a row steps, but for the delivery's: add(index into MpeCnt)
+template <typename Add>
+TS_HD inline void mpe_account(unsigned flags, Add add) {
+    add(MPC_SECTIONS);
+    constexpr int of_flag[10] = {MPC_OTHER_TABLE, MPC_MALSEC, MPC_CRC, MPC_UNCHECKED, MPC_SCR_SECTIONS, MPC_FILTERED, MPC_FRAGMENTS, MPC_OTHER_PROTOCOL, MPC_BAD_IP,
+                                 MPC_DATAGRAMS};
+    for (int k = 0; k < 10; ++k) if (flags >> k & 1) add(of_flag[k]);
+}
+
+// ------------------------------------------------------------------------------------------------- the sequential definition
+struct MpeState {
+    uint8_t cont = 0;                                      // tsmon_step's byte
+    int fill = 0;                                          // bytes buffered; 0: no section is open
+    uint8_t buf[MPE_BUF];
+};
+// a section's bytes in memory, the reductions as loops
+struct MpeHostSrc {
+    const uint8_t* b;
+    unsigned rd(int i) const { return b[i]; }
+    template <typename Fn> bool any(int n, Fn f) const { for (int k = 0; k < n; ++k) if (f(k)) return true; return false; }
+    template <typename Fn> unsigned sum(int n, Fn f) const { unsigned v = 0; for (int k = 0; k < n; ++k) v += f(k); return v; }
+};
+
+// one slot of one stream: a complete reassembler
+struct MpeHostStream {
+    MpeWatch watch = {-1, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
+    MpeState st;
+    int first_packet = -1;                                 // of the open section, in this call
+    // of the last call
+    std::vector<MpeRow> rows;
+    std::vector<uint8_t> bytes;
+    MpeCnt cnt = {};
+
+    void clear() { st = MpeState(); rows.clear(); bytes.clear(); }
+
+    void drop() {
+        if (st.fill > 0) ++cnt.dropped_sections;
+        st.fill = 0;
+    }
+    void emit(int k, bool want_bytes) {
+        const uint8_t* b = st.buf;
+        const int total = st.fill;
+        const bool crc_ok = !mpe_takes_crc(b[0], b[1], total) || ts_crc32(b, total) == 0;
+        MpeRow r = mpe_row_fields(MpeHostSrc{b}, total, crc_ok, watch, first_packet, k);
+        mpe_account(r.flags, [&](int c) { ++reinterpret_cast<int32_t*>(&cnt)[c]; });
+        if (want_bytes && (r.flags & MPE_DATAGRAM)) {
+            const uint8_t* d = b + mpe_ip_at(r);
+            r.offset = (int32_t)bytes.size();
+            bytes.insert(bytes.end(), d, d + r.bytes);
+            ++cnt.datagrams_delivered; cnt.bytes_delivered += r.bytes;
+        }
+        rows.push_back(r);
+    }
+    // n bytes for the slot's section (open, or starting with them): stops behind the section's last byte.  true: it was emitted; a bad
+    // length forgets the header and is false too
+    bool feed(const uint8_t* b, int n, int* used, int k, bool want_bytes) {
+        int i = 0;
+        bool done = false;
+        while (i < n) {
+            if (st.fill < MPE.header_bytes) {
+                st.buf[st.fill++] = b[i++];
+                if (st.fill < MPE.header_bytes) continue;
+                if (mpe_total(st.buf[1], st.buf[2]) < 0) { ++cnt.malformed_sections; st.fill = 0; break; }
+            } else {
+                const int total = mpe_total(st.buf[1], st.buf[2]);
+                const int take = n - i < total - st.fill ? n - i : total - st.fill;
+                memcpy(st.buf + st.fill, b + i, (size_t)take);
+                st.fill += take; i += take;
+            }
+            if (st.fill == mpe_total(st.buf[1], st.buf[2])) { emit(k, want_bytes); st.fill = 0; done = true; break; }
+        }
+        *used = i;
+        return done;
+    }
+    // what the shared packet loop asks of a format (ts_reasm_rules.h): one slot, the section bank's stuffing byte
+    struct Format {
+        MpeHostStream& h;
+        int slot_of(int pid) const { return pid == h.watch.pid ? 0 : -1; }
+        MpeState& state(int) { return h.st; }
+        MpeCnt& cnt(int) { return h.cnt; }
+        void drop(int) { h.drop(); }
+        bool feed(int, const uint8_t* b, int n, int* used, int k, bool want_bytes) { return h.feed(b, n, used, k, want_bytes); }
+        void begin(int, int k) { h.first_packet = k; }
+        void slack(int) {}
+        bool stuffing(uint8_t b) const { return b == 0xFF; }
+    };
+    // one call: n packets.  The caller keeps a copy of `st` if the call may have to be undone.
+    void run(const uint8_t* ts, int n, bool want_bytes) {
+        rows.clear(); bytes.clear();
+        cnt = MpeCnt{};
+        first_packet = -1;
+        if (watch.pid >= 0) ts_reasm_run(Format{*this}, ts, n, want_bytes);
+    }
+};
+
+}  // namespace s2
