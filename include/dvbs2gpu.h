@@ -131,6 +131,12 @@ int dvbs2gpu_ldpc_addr_table_dump(int rate, int shortframes, uint32_t* table, in
  * layer_of: [pseudo-layer] its layer.  NULL arrays: counts only. */
 int dvbs2gpu_ldpc_split_plan_dump(int rate, int shortframes, uint32_t* layers4, uint32_t* table, int32_t* row_of, int32_t* layer_of, int32_t* counts6);
 
+/* Host-only dump of the physical-layer tables every receiver uploads (no GPU needed; the CPU test-suite compares them with what the
+ * reference's s2_defs.h and s2_scrambling.cpp give): sof52 = the 26 SOF symbols (re, im), plsc_128x64x2 = the 64 symbols of each of the
+ * 128 PLS codewords, codes128 = the codewords (bit 63 first), rn131072 = the Gold sequence of code number 0 as rotations 0..3.
+ * NULL arrays are skipped. */
+int dvbs2gpu_pl_tables_dump(float* sof52, float* plsc_128x64x2, uint64_t* codes128, uint8_t* rn131072);
+
 /* replaces BBFrameBCH::decode (bbframe_bch.cpp:380-405).  d_frames [nframes][K/8] corrected in place;
  * d_corrections [nframes] int32: #bits corrected, 0 clean, -1 uncorrectable (frame left untouched). */
 int dvbs2gpu_bch_decode_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, uint8_t* d_frames, int nframes,

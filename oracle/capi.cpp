@@ -227,6 +227,7 @@ void orc_pl_tables(float* sof52, float* plsc_128x64x2, uint64_t* codes128, uint8
     if (codes128) memcpy(codes128, T.plsc_code, sizeof(T.plsc_code));
     if (rn131072) memcpy(rn131072, T.Rn.data(), 131072);
 }
+void orc_pl_rotation_cases(float* out16) { pl_rotation_cases(out16); }
 void orc_rrc_taps(int count, double beta, double symrate, double samprate, float* out) {
     std::vector<float> t = rrc_taps(count, beta, symrate, samprate);
     memcpy(out, t.data(), t.size() * sizeof(float));

@@ -288,3 +288,88 @@ void ref_bbts_get_fields(void* h, int32_t* o15) {
     for (int i = 0; i < 15; ++i) o15[i] = v[i];
 }
 }
+
+// ---------------------------------------------------------------------------------- S2 physical layer: the integer tables
+// MODCOD -> configuration (modcod_to_cfg.cpp), SOF word and PLS codewords (s2_defs.h), Gold sequence and the four rotations
+// (s2_scrambling.cpp), over shim/dsp/types.h: complex_t as two float fields.  The float symbol tables of s2_defs.h and everything
+// in constellation.cpp need SDR++ core's arithmetic and are not reached from here.
+#include <stdexcept>
+#include "dvbs2/codings/modcod_to_cfg.h"
+#include "dvbs2/codings/s2_scrambling.h"
+#include "dvbs2/s2_defs.h"
+#include <memory>
+
+// the reference's rate enum has C7_8 between C5_6 and C8_9, ours has not: by name, never by number
+static int our_rate(dvbs2_code_rate_t r) {
+    switch (r) {
+        case C1_4: return 0; case C1_3: return 1; case C2_5: return 2; case C1_2: return 3; case C3_5: return 4; case C2_3: return 5;
+        case C3_4: return 6; case C4_5: return 7; case C5_6: return 8; case C8_9: return 9; case C9_10: return 10;
+        default: return -1;     // C7_8, or a field the reference left unset
+    }
+}
+static int our_constel(dvbs2_constellation_t c) {
+    switch (c) { case MOD_QPSK: return 0; case MOD_8PSK: return 1; case MOD_16APSK: return 2; case MOD_32APSK: return 3; default: return -1; }
+}
+
+extern "C" {
+// get_dvbs2_cfg: out4 = {slot count, constellation 0..3, rate as OUR index 0..10, short frame 0/1}, g = {g1, g2}.
+// dvb_cgf_holder is not initialised by the reference: g[0] is meaningful only for 16APSK and 32APSK, g[1] only for 32APSK
+// (modcod_to_cfg.cpp:66-132); the others are returned as NaN so that nobody records or compares them by accident.
+// Returns 0, or -1 where the reference throws (MODCOD <= 0 or >= 29, :11,135).
+int ref_modcod_cfg(int modcod, int shortframes, int pilots, int* out4, float* g) {
+    try {
+        dvb_cgf_holder c = get_dvbs2_cfg(modcod, shortframes != 0, pilots != 0);
+        out4[0] = c.frame_slot_count; out4[1] = our_constel(c.constellation); out4[2] = our_rate(c.coderate);
+        out4[3] = c.framesize == FECFRAME_SHORT ? 1 : c.framesize == FECFRAME_NORMAL ? 0 : -1;
+        const float nan = __builtin_nanf("");
+        g[0] = c.constellation == MOD_16APSK || c.constellation == MOD_32APSK ? c.g1 : nan;
+        g[1] = c.constellation == MOD_32APSK ? c.g2 : nan;
+        return c.pilots == (pilots != 0) ? 0 : -2;
+    } catch (const std::runtime_error&) {
+        return -1;
+    }
+}
+// get_dvbs2_modcod of what get_dvbs2_cfg returned: the reverse map (:142-221)
+int ref_modcod_roundtrip(int modcod, int shortframes, int pilots) {
+    try {
+        return get_dvbs2_modcod(get_dvbs2_cfg(modcod, shortframes != 0, pilots != 0));
+    } catch (const std::runtime_error&) {
+        return -1;
+    }
+}
+// s2_plscodes::codewords, and sof3 = {s2_sof::VALUE, MASK, LENGTH}
+void ref_pls_codewords(uint64_t* out128, uint32_t* sof3) {
+    std::unique_ptr<s2_plscodes> p(new s2_plscodes());
+    for (int i = 0; i < s2_plscodes::COUNT; ++i) out128[i] = p->codewords[i];
+    sof3[0] = s2_sof::VALUE; sof3[1] = s2_sof::MASK; sof3[2] = (uint32_t)s2_sof::LENGTH;
+}
+// Rn[0..131071] of S2Scrambling(codenum), read through the public interface: descramble() turns (1, 2) into one of four
+// distinct pairs, one per rotation.  Entries that are none of the four come back as 255.
+void ref_gold_sequence(int codenum, uint8_t* out131072) {
+    std::unique_ptr<S2Scrambling> s(new S2Scrambling(codenum));
+    s->reset();
+    for (int i = 0; i < 131072; ++i) {
+        dsp::complex_t p = {1.0f, 2.0f};
+        dsp::complex_t q = s->descramble(p);
+        out131072[i] = q.re == 1.0f && q.im == 2.0f ? 0 : q.re == 2.0f && q.im == -1.0f ? 1 : q.re == -1.0f && q.im == -2.0f ? 2
+                     : q.re == -2.0f && q.im == 1.0f ? 3 : 255;
+    }
+}
+// out16[4 * r + {0, 1, 2, 3}] = scramble((1, 2)).re, .im, descramble((1, 2)).re, .im at a position whose Rn is r (code number 0).
+// Returns 0, or -1 when some r does not occur in `rn`, the sequence ref_gold_sequence(0) returned.
+int ref_scramble_cases(const uint8_t* rn131072, float* out16) {
+    std::unique_ptr<S2Scrambling> s(new S2Scrambling(0));
+    for (int r = 0; r < 4; ++r) {
+        int pos = 0;
+        while (pos < 131072 && rn131072[pos] != r) ++pos;
+        if (pos == 131072) return -1;
+        dsp::complex_t p = {1.0f, 2.0f};
+        s->setPos(pos);
+        dsp::complex_t a = s->scramble(p);
+        s->setPos(pos);
+        dsp::complex_t b = s->descramble(p);
+        out16[4 * r] = a.re; out16[4 * r + 1] = a.im; out16[4 * r + 2] = b.re; out16[4 * r + 3] = b.im;
+    }
+    return 0;
+}
+}

@@ -87,6 +87,12 @@ static inline cf pl_scramble(cf p, int r) {     // s2_scrambling.cpp:60-81
         default: return p;
     }
 }
+void pl_rotation_cases(float* out16) {
+    for (int r = 0; r < 4; ++r) {
+        cf a = pl_scramble(cf{1.0f, 2.0f}, r), b = pl_descramble(cf{1.0f, 2.0f}, r);
+        out16[4 * r] = a.re; out16[4 * r + 1] = a.im; out16[4 * r + 2] = b.re; out16[4 * r + 3] = b.im;
+    }
+}
 
 // ------------------------------------------------------------------------------------------ constellation
 static cf polar(float r, int n, float i) {

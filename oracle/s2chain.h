@@ -57,6 +57,8 @@ struct PlTables {
     PlTables();
 };
 const PlTables& pl_tables();
+// out16[4 * r + {0, 1, 2, 3}] = the receiver's and transmitter's own PL (de)scrambling of (1, 2) by rotation r: scrambled re, im, descrambled re, im
+void pl_rotation_cases(float* out16);
 
 // ---- soft demapper (constellation.cpp:19-322)
 struct Constellation {

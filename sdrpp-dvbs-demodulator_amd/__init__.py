@@ -283,6 +283,7 @@ PROTOTYPES = {
     'dvbs2gpu_deinterleave_batch': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     'dvbs2gpu_set_stage_timing': (_i, [_vp, _i]),
     'dvbs2gpu_get_stage_times': (_i, [_vp, _vp]),
+    'dvbs2gpu_pl_tables_dump': (_i, [_vp, _vp, _vp, _vp]),
     'dvbs2gpu_math_eval': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'dvbs2gpu_demod_default_cfg': (None, [_i, _i, _i, C.POINTER(DemodCfg)]),
     'dvbs2gpu_demod_create': (_i, [_vp, C.POINTER(DemodCfg), _i, C.POINTER(_vp)]),
@@ -474,6 +475,17 @@ def modcod_info(modcod, shortframes=False, pilots=False):
     if rc != 0:
         raise Dvbs2GpuError(rc, load_library().dvbs2gpu_last_error().decode())
     return info.as_dict()
+
+
+def pl_tables():
+    """Host-only: the physical-layer tables a receiver uploads -> (sof complex64 [26], plsc symbols complex64 [128, 64], codewords uint64 [128], Rn uint8 [131072])"""
+    import numpy as np
+    sof, sym = np.zeros(26, np.complex64), np.zeros((128, 64), np.complex64)
+    codes, rn = np.zeros(128, np.uint64), np.zeros(131072, np.uint8)
+    rc = load_library().dvbs2gpu_pl_tables_dump(sof.ctypes.data, sym.ctypes.data, codes.ctypes.data, rn.ctypes.data)
+    if rc != 0:
+        raise Dvbs2GpuError(rc, load_library().dvbs2gpu_last_error().decode())
+    return sof, sym, codes, rn
 
 
 def fec_info(rate, shortframes=False):

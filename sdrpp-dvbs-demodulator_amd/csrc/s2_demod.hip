@@ -143,13 +143,9 @@ struct HostConstel {
     }
 };
 
-int get_rx_tables(dvbs2gpu_ctx* ctx) {
-    std::lock_guard<std::mutex> l(ctx->mtx);
-    if (ctx->d_gardner_bank) return 0;       // (set last: a failed upload below leaves the tables "not built")
-    int rc;
-    // SOF / PLSC / Gold sequence (s2_defs.h:15-80, s2_scrambling.cpp:9-28)
-    std::vector<cf32> sof(26), plsc(128 * 64);
-    std::vector<uint64_t> codes(128);
+// SOF / PLSC / Gold sequence (s2_defs.h:15-80, s2_scrambling.cpp:9-28), on the host: what get_rx_tables uploads and dvbs2gpu_pl_tables_dump hands out
+static void build_pl_tables(std::vector<cf32>& sof, std::vector<cf32>& plsc, std::vector<uint64_t>& codes, std::vector<uint8_t>& rn) {
+    sof.assign(26, cf32{0.f, 0.f}); plsc.assign(128 * 64, cf32{0.f, 0.f}); codes.assign(128, 0);
     const uint32_t VALUE = 0x18d2e82;
     for (int s = 0; s < 26; ++s) {
         int bit = (VALUE >> (25 - s)) & 1, angle = bit * 2 + (s & 1);
@@ -174,12 +170,22 @@ int get_rx_tables(dvbs2gpu_ctx* ctx) {
             plsc[index * 64 + i].im = (1 - 2 * yi) / sqrtf(2);
         }
     }
-    std::vector<uint8_t> rn(131072, 0);
+    rn.assign(131072, 0);
     auto lfsr_x = [](uint32_t X) { int bit = ((X >> 7) ^ X) & 1; return ((uint32_t)(bit << 18) | X) >> 1; };
     auto lfsr_y = [](uint32_t Y) { int bit = ((Y >> 10) ^ (Y >> 7) ^ (Y >> 5) ^ Y) & 1; return ((uint32_t)(bit << 18) | Y) >> 1; };
     uint32_t stx = 0x00001, sty = 0x3ffff;
     for (int i = 0; i < 131072; ++i) { rn[i] = (uint8_t)((stx ^ sty) & 1); stx = lfsr_x(stx); sty = lfsr_y(sty); }
     for (int i = 0; i < 131072; ++i) { rn[i] |= (uint8_t)(((stx ^ sty) & 1) << 1); stx = lfsr_x(stx); sty = lfsr_y(sty); }
+}
+
+int get_rx_tables(dvbs2gpu_ctx* ctx) {
+    std::lock_guard<std::mutex> l(ctx->mtx);
+    if (ctx->d_gardner_bank) return 0;       // (set last: a failed upload below leaves the tables "not built")
+    int rc;
+    std::vector<cf32> sof, plsc;
+    std::vector<uint64_t> codes;
+    std::vector<uint8_t> rn;
+    build_pl_tables(sof, plsc, codes, rn);
     PlTables T{};       // (built aside and moved in whole: a failed upload leaves the context without tables and without their memory)
     DevBuf<float> bank;
     if ((rc = upload(sof, T.sof_own, &T.sof)) || (rc = upload(plsc, T.plsc_own, &T.plsc)) || (rc = upload(codes, T.plsc_code_own, &T.plsc_code)) ||
@@ -1934,6 +1940,18 @@ int dvbs2gpu_deinterleave_batch(dvbs2gpu_ctx* ctx, int modcod, int shortframes, 
     if (!d_in || !d_out || d_in == d_out) return DVBS2GPU_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(s2_deinterleave_launch(mp.constel, mp.rate, mp.bits, mp.fec.N, d_in, nframes, d_out, (hipStream_t)stream));
+    return 0;
+}
+
+int dvbs2gpu_pl_tables_dump(float* sof52, float* plsc_128x64x2, uint64_t* codes128, uint8_t* rn131072) {
+    std::vector<cf32> sof, plsc;
+    std::vector<uint64_t> codes;
+    std::vector<uint8_t> rn;
+    build_pl_tables(sof, plsc, codes, rn);
+    if (sof52) memcpy(sof52, sof.data(), sof.size() * sizeof(cf32));
+    if (plsc_128x64x2) memcpy(plsc_128x64x2, plsc.data(), plsc.size() * sizeof(cf32));
+    if (codes128) memcpy(codes128, codes.data(), codes.size() * sizeof(uint64_t));
+    if (rn131072) memcpy(rn131072, rn.data(), rn.size());
     return 0;
 }
 

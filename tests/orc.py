@@ -89,6 +89,14 @@ def ref():
             L.ref_fec16_destroy.restype = None
             L.ref_fec16_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
             L.ref_build_flags.restype = C.c_char_p
+        if hasattr(L, 'ref_modcod_cfg'):         # S2 physical-layer tables (tests/test_oracle_s2_tables.py)
+            L.ref_modcod_cfg.argtypes = [C.c_int, C.c_int, C.c_int, _i32p, _f32p]
+            L.ref_modcod_roundtrip.argtypes = [C.c_int, C.c_int, C.c_int]
+            L.ref_pls_codewords.argtypes = [np.ctypeslib.ndpointer(np.uint64, flags='C_CONTIGUOUS'), np.ctypeslib.ndpointer(np.uint32, flags='C_CONTIGUOUS')]
+            L.ref_pls_codewords.restype = None
+            L.ref_gold_sequence.argtypes = [C.c_int, _u8p]
+            L.ref_gold_sequence.restype = None
+            L.ref_scramble_cases.argtypes = [_u8p, _f32p]
         _ref = L
     return _ref
 
@@ -180,6 +188,8 @@ def _bind_chain():
     L.orc_s2_deinterleave.restype = None
     L.orc_pl_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.orc_pl_tables.restype = None
+    L.orc_pl_rotation_cases.argtypes = [_f32p]
+    L.orc_pl_rotation_cases.restype = None
     L.orc_rrc_taps.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, _f32p]
     L.orc_rrc_taps.restype = None
     L.orc_gardner_bank.argtypes = [_f32p]
@@ -206,6 +216,23 @@ def modcod_params(modcod, short=0, pilots=0):
     d = dict(zip(keys, [int(x) for x in out]))
     d['g1'], d['g2'] = float(g[0]), float(g[1])
     return d
+
+
+def pl_tables():
+    """the oracle's PL tables -> (sof complex64 [26], plsc symbols complex64 [128, 64], codewords uint64 [128], Rn uint8 [131072])"""
+    L = _bind_chain()
+    sof, sym = np.zeros(26, np.complex64), np.zeros((128, 64), np.complex64)
+    codes, rn = np.zeros(128, np.uint64), np.zeros(131072, np.uint8)
+    L.orc_pl_tables(sof.ctypes.data, sym.ctypes.data, codes.ctypes.data, rn.ctypes.data)
+    return sof, sym, codes, rn
+
+
+def pl_rotation_cases():
+    """float32 [4, 4]: row r = scramble((1, 2)).re, .im, descramble((1, 2)).re, .im by rotation r, as oracle/s2chain.cpp does them"""
+    L = _bind_chain()
+    out = np.zeros(16, np.float32)
+    L.orc_pl_rotation_cases(out)
+    return out.reshape(4, 4)
 
 
 def pls_info(pls):

@@ -50,6 +50,56 @@ def test_static_queries_without_gpu(pkg):
                    (o['constel'], o['bits'], o['rate'], o['slots'], o['pilot_blocks'], o['plframe'], o['N'], o['kbch'])
 
 
+def test_modcod_info_equals_the_reference_fixture(pkg):
+    """dvbs2gpu_modcod_info_get against tests/golden/s2_tables_golden.json -- what the reference's get_dvbs2_cfg returns, recorded -- and
+    not against the oracle, which reads the same header as the engine: both frame sizes, both pilot settings, the ring ratios as bit patterns"""
+    import json
+    G = json.load(open(os.path.join(ROOT, 'tests', 'golden', 's2_tables_golden.json')))
+    bits = lambda x: '%08x' % int(np.float32(x).view(np.uint32))
+    assert len(G['modcod_cfg']) == 112
+    seen = 0
+    for c in G['modcod_cfg']:
+        if c['short'] and c['rate'] == '9/10':              # the reference returns a configuration for these four; the engine has no such FECFRAME
+            with pytest.raises(pkg.Dvbs2GpuError) as e:
+                pkg.modcod_info(c['modcod'], True, bool(c['pilots']))
+            assert e.value.code == -2
+            continue
+        g = pkg.modcod_info(c['modcod'], bool(c['short']), bool(c['pilots']))
+        slots = c['slots']
+        blocks = (slots - 1) // 16 if c['pilots'] else 0
+        assert (g['constellation'], g['bits_per_symbol'], orc.RATE_NAMES[g['rate']], g['slots']) == (c['constel'], c['constel'] + 2, c['rate'], slots), c
+        assert (g['pilot_blocks'], g['plframe_symbols']) == (blocks, 90 * (slots + 1) + 36 * blocks), c
+        assert g['ldpc_n'] == (16200 if c['short'] else 64800) == 90 * slots * g['bits_per_symbol'], c
+        assert bits(g['g1']) == (c['g1'] or bits(0.0)) and bits(g['g2']) == (c['g2'] or bits(0.0)), c     # 0 where the reference assigns none
+        seen += 1
+    assert seen == 104
+
+
+def test_pl_tables_equal_the_reference_fixture(pkg):
+    """dvbs2gpu_pl_tables_dump -- the tables every receiver uploads -- against tests/golden/s2_tables_golden.json: all 128 PLS codewords, the
+    Gold sequence (digest and both windows), the symbol tables' quadrants from the pinned integers, and the float values bit for bit as
+    the oracle has them (a codeword one bit off still decodes by minimum distance, so no stream test is certain to notice it)"""
+    import hashlib
+    import json
+    G = json.load(open(os.path.join(ROOT, 'tests', 'golden', 's2_tables_golden.json')))
+    sof, sym, codes, rn = pkg.pl_tables()
+    assert ['%016x' % int(c) for c in codes] == G['pls_codewords']
+    assert hashlib.sha256(rn.tobytes()).hexdigest() == G['gold0']['sha256']
+    assert [int(x) for x in rn[:64]] == G['gold0']['first64'] and [int(x) for x in rn[33128:33192]] == G['gold0']['at33128']
+    value, length = int(G['sof']['value'], 16), G['sof']['length']
+    assert length == sof.size == 26
+    quad = {0: (1, 1), 1: (-1, 1), 2: (-1, -1), 3: (1, -1)}
+    for s in range(length):
+        assert (np.sign(sof[s].real), np.sign(sof[s].imag)) == quad[((value >> (length - 1 - s)) & 1) * 2 + (s & 1)], s
+    for idx in range(128):
+        code = int(G['pls_codewords'][idx], 16)
+        yi = np.array([(code >> (63 - i)) & 1 for i in range(64)])
+        assert np.array_equal(np.sign(sym[idx].real), 1 - 2 * (yi ^ (np.arange(64) & 1))) and np.array_equal(np.sign(sym[idx].imag), 1 - 2 * yi), idx
+    osof, osym, ocodes, orn = orc.pl_tables()
+    assert np.array_equal(sof.view(np.uint32), osof.view(np.uint32)) and np.array_equal(sym.view(np.uint32), osym.view(np.uint32))
+    assert np.array_equal(rn, orn) and np.array_equal(codes, ocodes)
+
+
 def test_no_cpu_fallback(pkg):
     import torch
     if torch.cuda.is_available():
