@@ -1335,7 +1335,7 @@ int dvbs2gpu_t2mi_get_frame_bytes(dvbs2gpu_t2mi* b, int stream, int slot, int* h
  *   Limits: max_packets <= 4096 per stream and call.  Memory (device banks) per (stream, slot): a 4096-byte section buffer, 6 bytes per
  *     packet of max_packets and 64 bytes per row of max_rows.
  *   NOT done: datagrams split over several sections; the 13818-6 checksum; MPE-FEC (table_id 0x78) and the time-slicing parameters
- *     that then stand in the MAC bytes; ULE; IP-level filters (the rows carry what a caller filters on); finding MPE PIDs by
+ *     that then stand in the MAC bytes; IP-level filters (the rows carry what a caller filters on); finding MPE PIDs by
  *     data_broadcast_id. */
 typedef struct dvbs2gpu_mpe dvbs2gpu_mpe;
 typedef struct dvbs2gpu_mpe_layout {
@@ -1408,6 +1408,154 @@ typedef struct dvbs2gpu_mpe_row {              /* 48 bytes */
 int dvbs2gpu_mpe_get_row_table(dvbs2gpu_mpe* b, int stream, int slot, dvbs2gpu_mpe_row* h_rows, int cap, int* n);
 /* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
 int dvbs2gpu_mpe_get_row_table_device(dvbs2gpu_mpe* b, int stream, int slot, const dvbs2gpu_mpe_row** d_rows, int* n);
+
+/* ------------------------------------------------------------------ ULE bank (own extension)
+ * Nothing in the reference does this.  A transport-stream carrier may carry IP by Unidirectional Lightweight Encapsulation (RFC 4326,
+ * extension headers RFC 5163): SNDUs, length-prefixed units without DSM-CC sections around them, on a PID that the operator names
+ * (there is no dependable PMT signalling).  For `nstreams` transport streams in HBM a bank reassembles the SNDUs of a PID, checks
+ * their CRC-32, applies a filter on the destination address (NPA), follows optional extension headers and a bridged frame's MAC header,
+ * checks the IPv4 or IPv6 header behind them, writes one table row per SNDU and lays the datagrams back to back in a device buffer.
+ * The sequential form below is the definition (csrc/ule_rules.h, UleHostStream::run); the kernels give its results for every cutting of
+ * a stream into calls.  The syntax is written from memory of RFC 4326, RFC 5163, RFC 791 and RFC 8200 and pinned to no vector of
+ * theirs; it is one struct, dvbs2gpu_ule_layout.
+ *   SNDU: bytes b0 b1 b2 b3: D = b0 >> 7 ("destination address absent"), Length = (b0 << 8 | b1) & 0x7FFF, Type = b2 << 8 | b3.
+ *     Length counts the bytes behind Type, CRC included: total = 4 + Length <= 4096.  Length > 4092 is the bad length; with that cap
+ *     0xFF is never a legal first byte.  With D = 0 the six bytes behind Type are the destination NPA address.  The last four bytes
+ *     are a CRC-32/MPEG (initial value 0xFFFFFFFF, polynomial 0x04C11DB7; the register over all `total` bytes is 0).
+ *   Watches: 4 slots per stream, each empty (pid -1) or (PID 0..0x1FFE, npa_value[6], npa_mask[6], accept_unaddressed); an all-zero
+ *     mask means every address.  A new bank watches nothing.  THE SAME PID MAY SIT IN SEVERAL SLOTS of a stream: every slot is a
+ *     complete, independent reassembler with its own state, counters, rows and output buffer.  Changing a slot's watch starts it afresh.
+ *   Packet: 188 bytes at offset 188 k, classified as the TS monitor does: sync-byte errors, TEI packets and null packets are not looked
+ *     at.  A packet of the slot's PID counts in `packets` and, in this order ("drop" = the open SNDU is forgotten; with fill > 0 it
+ *     counts in dropped_sndus) -- the shared packet rules of the reassembling banks, one slot per reassembler:
+ *     1. TSC != 0: scrambled_packets, drop, the continuity step; done.
+ *     2. The continuity step (dvbs2gpu_tsmon_*: one state byte per slot).  Duplicate: ignored.  Continuity error or announced
+ *        discontinuity: drop, then go on with this packet.  No payload (AFC&1 = 0): done.
+ *     3. The payload starts at 4, or at 5 + b4 when AFC&2.  >= 188: malformed_packets, drop, done.
+ *     4. PUSI set: ptr = the first payload byte, the payload pointer.  ptr > the bytes after it: malformed_packets, drop, done.  The
+ *        ptr bytes after the pointer go to an open SNDU: if they complete it, it is emitted, and if bytes of them are left over `slack`
+ *        counts (RFC 4326 discards the SNDU on such a pointer mismatch; this bank does NOT); if it is still incomplete after them (an
+ *        open header of one byte too) it is dropped; if they complete a header with the bad length, malformed_sndus counts and the
+ *        header is forgotten; with nothing open they are ignored.  Then SNDU starts are parsed behind them (6).
+ *     5. PUSI clear: the whole payload goes to an open SNDU; if it completes it, it is emitted and the rest of the payload is ignored
+ *        (a packet without PUSI starts nothing); a header completed with the bad length counts in malformed_sndus and is forgotten.
+ *        With nothing open the payload is ignored.
+ *     6. At an SNDU start, until the TS packet ends: the byte 0xFF ends the packet's chain (the End Indicator 0xFFFF and 0xFF padding
+ *        alike).  Else bytes are buffered; with two, total is known: the bad length counts in malformed_sndus, forgets the header and
+ *        ends the packet's chain; when the buffered bytes reach total the SNDU is emitted and the next byte is an SNDU start.  An
+ *        SNDU, or a header of one byte, that the TS packet's end cuts stays open, across calls too.
+ *   Emitting: every emitted SNDU is one row and counts in `sndus`.  In this order; a rule with a flag that is not called information
+ *     ends the list, and the fields of the row that later rules would set are 0:
+ *     1. Length < 4 with D = 1, or < 10 with D = 0: flag MALFORMED, malformed_sndus.
+ *     2. The CRC-32 over all bytes must be 0, else flag CRC_ERROR, crc_errors.  It is always taken.
+ *     3. D = 0: mac[0..5] = b4..b9, the body starts at 10; ((mac[k] ^ npa_value[k]) & npa_mask[k]) != 0 for a k: flag FILTERED,
+ *        `filtered`.  D = 1: flag NO_ADDRESS (information), no_address, the body starts at 4; without accept_unaddressed: flag
+ *        FILTERED, `filtered`.  body = bytes [start, total - 4).
+ *     4. Optional extension headers: while Type < 1536 and H-LEN = Type >> 8 & 7 is not 0 (it is 1..5 then): the header is 2 H-LEN
+ *        bytes of the body, whose last two are the next Type.  If the optional headers so far exceed 40 bytes or the header runs
+ *        beyond the body: flag EXTENSION, `extension`, ethertype = the Type that asked for it.  extension_bytes = their sum.
+ *     5. Type < 1536 now (H-LEN 0, a mandatory header): 0x0000 is a Test SNDU: flag TEST, `test`; its bytes go nowhere.  0x0001 is a
+ *        bridged frame: it needs 14 body bytes (destination, source, EtherType), else EXTENSION as below; flag BRIDGED (information),
+ *        `bridged`; with D = 1 mac = the bridged destination; Type = the frame's EtherType field, the body goes on behind the 14.  Any
+ *        other (TS-Concat 0x0002, PRIV-Concat 0x0003, unknown ones): flag EXTENSION, `extension`, ethertype = that Type.  Extension
+ *        headers are not looked for behind a bridged frame's MAC header.
+ *     6. ethertype = Type.  0x0800 / 0x86DD means IPv4 / IPv6 from here (the version nibble is not looked at); any other value --
+ *        an EtherType field below 1536 of a bridged frame, an LLC length, too: flag OTHER_PROTOCOL, other_protocol.  avail = the body
+ *        bytes from the IP header on.
+ *     7. IPv4 (header bytes i0 ..): avail >= 20; IHL = i0 & 15 >= 5 and 4 IHL <= avail; total_length = i2 << 8 | i3 with 4 IHL <=
+ *        total_length <= avail; the ones'-complement sum of the 2 IHL big-endian 16-bit header words, carries folded in, is 0xFFFF.
+ *        If one does not hold: flag BAD_IP, bad_ip.  Else family 4, bytes = total_length, stuffing = avail - total_length, protocol =
+ *        i9, src4 / dst4 = i12..i15 / i16..i19 as big-endian numbers; when protocol is 6 or 17, the fragment offset ((i6 << 8 | i7) &
+ *        0x1FFF) is 0 and total_length >= 4 IHL + 4: src_port / dst_port = the two big-endian numbers at 4 IHL.
+ *     8. IPv6: avail >= 40 and 40 + payload_length (i4 << 8 | i5) <= avail, else BAD_IP.  family 6, bytes = 40 + payload_length,
+ *        stuffing the rest, protocol = next_header (i6); ports from i40 when it is 6 or 17 and payload_length >= 4 (extension headers
+ *        are not followed).  src4 / dst4 stay 0: the addresses are in the delivered bytes.
+ *     9. A row that reached 7 or 8 without BAD_IP has flag DATAGRAM, counts in `datagrams`, and ip_at = where the datagram starts in
+ *        the SNDU.  It is delivered when the call has output buffers: its `bytes` (from the IP header on, without the stuffing) go to
+ *        the slot's output buffer, back to back in row order, and row.offset names them; datagrams_delivered and bytes_delivered
+ *        count.  Every other row has offset -1.  (Rules 7 to 9 are the MPE bank's 9 to 11: csrc/ip_rules.h states them once.)
+ *   A row is decided by its SNDU's first 4 + 6 + 40 + 14 + 60 + 4 = 128 bytes at most.
+ *   Row: ordered by the TS packet that held the SNDU's last byte, then by position in it.  One table per (stream, slot).
+ *   Capacity: sizes first.  If a slot's bytes exceed cap or its rows exceed max_rows the call returns DVBS2GPU_ERR_CAPACITY,
+ *     out_bytes[] holds the byte sizes (-1 for a slot whose rows did not fit: its SNDUs were not checked) and out_rows[] the row
+ *     counts; no state or counter of any stream has advanced, the tables of the call are empty, the call can be repeated.
+ *   State survives from call to call.  reset forgets state, positions and counters; watches stay.
+ *   Limits: max_packets <= 4096 per stream and call.  Memory (device banks) per (stream, slot): a 4096-byte SNDU buffer, 6 bytes per
+ *     packet of max_packets and 64 bytes per row of max_rows.
+ *   NOT done: SNDUs above 4096 bytes; the payloads of TS-Concat and PRIV-Concat; the RFC's discard on a pointer mismatch (see
+ *     `slack`); security extensions; IP-level filters (the rows carry what a caller filters on). */
+typedef struct dvbs2gpu_ule dvbs2gpu_ule;
+typedef struct dvbs2gpu_ule_layout {
+    int32_t header_bytes, length_bytes, d_bit, length_mask, max_length, max_sndu_bytes, type_at, npa_bytes, crc_bytes, min_length_d1, min_length_d0;
+    int32_t type_test, type_bridged, type_ts_concat, type_priv_concat, ethertype_floor, hlen_shift, hlen_mask, max_hlen, max_extension_bytes;
+    int32_t mac_header_bytes, bridged_ethertype_at, ethertype_ipv4, ethertype_ipv6;
+    int32_t ipv4_min_header, ipv4_total_length_at, ipv4_fragment_at, ipv4_protocol_at, ipv4_src_at, ipv4_dst_at;
+    int32_t ipv6_header, ipv6_payload_length_at, ipv6_next_header_at;
+    int32_t head_bytes;              /* the leading bytes of an SNDU that decide its row, at most: 128 */
+} dvbs2gpu_ule_layout;
+int dvbs2gpu_ule_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_ule** out);
+/* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_ule_work only */
+int dvbs2gpu_ule_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_ule** out);
+int dvbs2gpu_ule_reset(dvbs2gpu_ule* b);
+void dvbs2gpu_ule_destroy(dvbs2gpu_ule* b);
+int dvbs2gpu_ule_get_layout(dvbs2gpu_ule_layout* h_out);
+/* slot 0..3; pid 0..0x1FFE, or -1: the slot is empty; npa_value / npa_mask: six bytes each, NULL: all zero; accept_unaddressed != 0:
+ * SNDUs with D = 1 pass the filter */
+int dvbs2gpu_ule_set_watch(dvbs2gpu_ule* b, int stream, int slot, int pid, const uint8_t npa_value[6], const uint8_t npa_mask[6], int accept_unaddressed);
+/* the arguments of dvbs2gpu_mpe_process_batch: d_ts[i], nbytes[i]; d_out NULL (rows and counters only) or d_out[i*4 + k] of cap bytes
+ * for the datagrams of slot k of stream i (NULL for an empty slot); out_bytes[i*4 + k], out_rows[i*4 + k] (host).  Two kernel launches.
+ * Synchronous on `stream`; chained behind a packetiser or monitor call on the same stream, no packet visits the host. */
+int dvbs2gpu_ule_process_batch(dvbs2gpu_ule* b, const uint8_t* const* d_ts, const int* nbytes, uint8_t* const* d_out, int cap, int* out_bytes,
+                               int* out_rows, void* stream);
+/* one stream and slot of any bank with HOST buffers (h_out NULL: rows and counters only): returns the bytes written to h_out or a
+ * negative error.  Every other slot of the bank receives an empty call. */
+int dvbs2gpu_ule_work(dvbs2gpu_ule* b, int stream, int slot, const uint8_t* h_ts, int nbytes, uint8_t* h_out, int cap);
+/* the byte and row sizes that the slot's last call needed, whether it succeeded or failed for capacity (bytes -1: the rows did not fit) */
+int dvbs2gpu_ule_get_needed(dvbs2gpu_ule* b, int stream, int slot, int* bytes, int* rows);
+typedef struct dvbs2gpu_ule_stats {            /* of a slot, since creation, reset or the slot's last set_watch; kept on the host */
+    int64_t packets;                 /* trusted TS packets of the slot's PID */
+    int64_t sndus;                   /* rows */
+    int64_t crc_errors, filtered, no_address, test, bridged, extension, other_protocol, bad_ip;
+    int64_t datagrams;               /* rows with DATAGRAM, delivered or not */
+    int64_t datagrams_delivered, bytes_delivered;
+    int64_t dropped_sndus;           /* open SNDUs forgotten */
+    int64_t malformed_sndus;         /* the bad length, and rows with MALFORMED */
+    int64_t slack;                   /* pointer bytes left over behind the end of the open SNDU */
+    int64_t malformed_packets, scrambled_packets;   /* TS packets */
+} dvbs2gpu_ule_stats;
+/* slot -1: the sum over the stream's slots */
+int dvbs2gpu_ule_get_stats(dvbs2gpu_ule* b, int stream, int slot, dvbs2gpu_ule_stats* h_out);
+#define DVBS2GPU_ULE_MALFORMED 1
+#define DVBS2GPU_ULE_CRC_ERROR 2
+#define DVBS2GPU_ULE_FILTERED 4
+#define DVBS2GPU_ULE_NO_ADDRESS 8
+#define DVBS2GPU_ULE_TEST 16
+#define DVBS2GPU_ULE_BRIDGED 32
+#define DVBS2GPU_ULE_EXTENSION 64
+#define DVBS2GPU_ULE_OTHER_PROTOCOL 128
+#define DVBS2GPU_ULE_BAD_IP 256
+#define DVBS2GPU_ULE_DATAGRAM 512
+typedef struct dvbs2gpu_ule_row {              /* 48 bytes */
+    uint16_t flags;
+    uint8_t family;                  /* 4 or 6 of a DATAGRAM row, else 0 */
+    uint8_t protocol;                /* IPv4 protocol / IPv6 next_header */
+    uint8_t mac[6];                  /* the NPA where there was one, else a bridged frame's destination, else 0 */
+    uint8_t ip_at;                   /* of a DATAGRAM row: where the datagram starts in the SNDU */
+    uint8_t extension_bytes;         /* of the optional extension headers that were followed */
+    uint16_t src_port, dst_port;     /* of an unfragmented TCP or UDP datagram, else 0 */
+    uint32_t src4, dst4;             /* IPv4 addresses as big-endian numbers; 0 for IPv6 */
+    int32_t length;                  /* total bytes of the SNDU */
+    int32_t offset;                  /* of the datagram in the slot's output buffer; -1: not delivered */
+    int32_t bytes;                   /* of the datagram of a DATAGRAM row, delivered or not; else 0 */
+    int32_t first_packet;            /* index in this call of the TS packet that held its first byte; -1: an earlier call */
+    int32_t last_packet;             /* and of the one that held its last byte */
+    uint16_t ethertype;              /* the final Type / EtherType of a row that reached rule 6; the offending Type of EXTENSION */
+    uint16_t stuffing;               /* body bytes behind the datagram */
+} dvbs2gpu_ule_row;
+/* h_rows[cap] (host); *n = rows of the slot's last call, of which min(*n, cap) are written */
+int dvbs2gpu_ule_get_row_table(dvbs2gpu_ule* b, int stream, int slot, dvbs2gpu_ule_row* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_ule_get_row_table_device(dvbs2gpu_ule* b, int stream, int slot, const dvbs2gpu_ule_row** d_rows, int* n);
 
 #ifdef __cplusplus
 }

@@ -992,5 +992,84 @@ private:
     int status_ = 0;
     std::string error_;
 };
+/* ULE bank for one transport stream (dvbs2gpu_ule_*, include/dvbs2gpu.h; an extension): the ULE SNDUs (RFC 4326) of a PID behind
+ * BBFrameTSParser or TSMonitor are reassembled and checked and their IP datagrams laid back to back.  Four slots, each a (PID, NPA
+ * value, NPA mask, accept_unaddressed) and a reassembler of its own.  init() (a device bank) or initHost() (the library's host
+ * implementation, no device) and the setters throw; work() sits in the data path and does NOT throw: a failing call returns 0 and
+ * leaves its code in status() and its text in error(), sticky until clearStatus(). */
+class UleBank {
+public:
+    UleBank() {}
+    ~UleBank() {
+        if (h) dvbs2gpu_ule_destroy(h);
+    }
+    UleBank(const UleBank&) = delete;
+    UleBank& operator=(const UleBank&) = delete;
+
+    void init(int max_packets, int max_rows, int device = 0) {
+        release();
+        eng = Engine::get(device);
+        check(dvbs2gpu_ule_create(eng->ctx, 1, max_packets, max_rows, &h));
+    }
+    void initHost(int max_packets, int max_rows) {
+        release();
+        check(dvbs2gpu_ule_create_host(1, max_packets, max_rows, &h));
+    }
+    void reset() { check(dvbs2gpu_ule_reset(need())); }
+    /* slot 0..3; pid -1 empties the slot; npa_value / npa_mask: six bytes each, nullptr: all zero (every address); accept_unaddressed:
+     * SNDUs without a destination address pass.  The same PID may sit in several slots. */
+    void setWatch(int slot, int pid, const uint8_t* npa_value = nullptr, const uint8_t* npa_mask = nullptr, bool accept_unaddressed = false) {
+        check(dvbs2gpu_ule_set_watch(need(), 0, slot, pid, npa_value, npa_mask, accept_unaddressed ? 1 : 0));
+    }
+    /* nbytes of whole TS packets in for one slot; datagrams (buffer_outsize bytes; nullptr: rows and counters only) receives the
+     * slot's IP datagrams back to back; returns their bytes, 0 on failure (see status(); on DVBS2GPU_ERR_CAPACITY needed() has the
+     * sizes and nothing was consumed) */
+    int work(int slot, const uint8_t* ts, int nbytes, uint8_t* datagrams, int buffer_outsize) noexcept {
+        const int n = h ? dvbs2gpu_ule_work(h, 0, slot, ts, nbytes, datagrams, buffer_outsize) : DVBS2GPU_ERR_ARG;
+        if (n >= 0) return n;
+        if (status_ == 0) {
+            status_ = n;
+            try { error_ = h ? dvbs2gpu_last_error() : "UleBank used before init()"; } catch (...) {}
+        }
+        return 0;
+    }
+    int status() const { return status_; }
+    const std::string& error() const { return error_; }
+    void clearStatus() { status_ = 0; error_.clear(); }
+    /* {bytes, rows} that the slot's last work() needed */
+    std::pair<int, int> needed(int slot) {
+        int b = 0, r = 0;
+        check(dvbs2gpu_ule_get_needed(need(), 0, slot, &b, &r));
+        return {b, r};
+    }
+
+    dvbs2gpu_ule_stats stats(int slot = -1) {
+        dvbs2gpu_ule_stats s;
+        check(dvbs2gpu_ule_get_stats(need(), 0, slot, &s));
+        return s;
+    }
+    /* one row per SNDU of the slot's last work(), in row order */
+    std::vector<dvbs2gpu_ule_row> rowTable(int slot) {
+        int n = 0;
+        check(dvbs2gpu_ule_get_row_table(need(), 0, slot, nullptr, 0, &n));
+        std::vector<dvbs2gpu_ule_row> rows((size_t)n);
+        if (n > 0) check(dvbs2gpu_ule_get_row_table(h, 0, slot, rows.data(), n, &n));
+        return rows;
+    }
+
+private:
+    void release() {
+        if (h) dvbs2gpu_ule_destroy(h);
+        h = nullptr;
+    }
+    dvbs2gpu_ule* need() {
+        if (!h) throw std::runtime_error("dvbs2gpu: UleBank used before init()");
+        return h;
+    }
+    std::shared_ptr<Engine> eng;
+    dvbs2gpu_ule* h = nullptr;
+    int status_ = 0;
+    std::string error_;
+};
 }   // namespace dvbs2gpu_host
 #endif

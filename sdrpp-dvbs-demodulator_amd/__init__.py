@@ -228,6 +228,29 @@ class MpeRow(C.Structure):
                 ('ethertype', C.c_uint16), ('stuffing', C.c_uint16)]
 
 
+class UleLayout(C.Structure):
+    """dvbs2gpu_ule_layout"""
+    _fields_ = [(k, C.c_int32) for k in ('header_bytes', 'length_bytes', 'd_bit', 'length_mask', 'max_length', 'max_sndu_bytes', 'type_at', 'npa_bytes', 'crc_bytes',
+                                         'min_length_d1', 'min_length_d0', 'type_test', 'type_bridged', 'type_ts_concat', 'type_priv_concat', 'ethertype_floor',
+                                         'hlen_shift', 'hlen_mask', 'max_hlen', 'max_extension_bytes', 'mac_header_bytes', 'bridged_ethertype_at', 'ethertype_ipv4',
+                                         'ethertype_ipv6', 'ipv4_min_header', 'ipv4_total_length_at', 'ipv4_fragment_at', 'ipv4_protocol_at', 'ipv4_src_at',
+                                         'ipv4_dst_at', 'ipv6_header', 'ipv6_payload_length_at', 'ipv6_next_header_at', 'head_bytes')]
+
+
+class UleStats(C.Structure):
+    """dvbs2gpu_ule_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('packets', 'sndus', 'crc_errors', 'filtered', 'no_address', 'test', 'bridged', 'extension', 'other_protocol', 'bad_ip',
+                                         'datagrams', 'datagrams_delivered', 'bytes_delivered', 'dropped_sndus', 'malformed_sndus', 'slack', 'malformed_packets',
+                                         'scrambled_packets')]
+
+
+class UleRow(C.Structure):
+    """dvbs2gpu_ule_row"""
+    _fields_ = [('flags', C.c_uint16), ('family', C.c_uint8), ('protocol', C.c_uint8), ('mac', C.c_uint8 * 6), ('ip_at', C.c_uint8), ('extension_bytes', C.c_uint8),
+                ('src_port', C.c_uint16), ('dst_port', C.c_uint16), ('src4', C.c_uint32), ('dst4', C.c_uint32), ('length', C.c_int32), ('offset', C.c_int32),
+                ('bytes', C.c_int32), ('first_packet', C.c_int32), ('last_packet', C.c_int32), ('ethertype', C.c_uint16), ('stuffing', C.c_uint16)]
+
+
 class FrameQuality(C.Structure):
     """dvbs2gpu_frame_quality"""
     _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('gain', C.c_float), ('phase', C.c_float), ('known_symbols', C.c_int32),
@@ -448,6 +471,18 @@ PROTOTYPES = {
     'dvbs2gpu_mpe_get_stats': (_i, [_vp, _i, _i, C.POINTER(MpeStats)]),
     'dvbs2gpu_mpe_get_row_table': (_i, [_vp, _i, _i, C.POINTER(MpeRow), _i, C.POINTER(_i)]),
     'dvbs2gpu_mpe_get_row_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
+    'dvbs2gpu_ule_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_ule_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_ule_reset': (_i, [_vp]),
+    'dvbs2gpu_ule_destroy': (None, [_vp]),
+    'dvbs2gpu_ule_get_layout': (_i, [C.POINTER(UleLayout)]),
+    'dvbs2gpu_ule_set_watch': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _i]),
+    'dvbs2gpu_ule_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    'dvbs2gpu_ule_work': (_i, [_vp, _i, _i, _vp, _i, _vp, _i]),
+    'dvbs2gpu_ule_get_needed': (_i, [_vp, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    'dvbs2gpu_ule_get_stats': (_i, [_vp, _i, _i, C.POINTER(UleStats)]),
+    'dvbs2gpu_ule_get_row_table': (_i, [_vp, _i, _i, C.POINTER(UleRow), _i, C.POINTER(_i)]),
+    'dvbs2gpu_ule_get_row_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
 }
 
 _lib = None
@@ -1986,6 +2021,108 @@ class MpeBank(_TsBank):
         """(device pointer or None, rows): the same table as dvbs2gpu_mpe_row records in HBM, valid until the next call"""
         p, n = C.c_void_p(), C.c_int()
         self._check(self.lib.dvbs2gpu_mpe_get_row_table_device(self.h, int(stream), int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+
+class UleBank(_TsBank):
+    """ULE bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, ULE bank): the SNDUs of a PID (Unidirectional
+    Lightweight Encapsulation, RFC 4326) are reassembled, their CRC-32 checked, a filter on the destination NPA address applied,
+    optional extension headers and a bridged frame's MAC header followed and the IPv4 / IPv6 header behind them checked, one table row
+    per SNDU, and the IP datagrams laid back to back in a device buffer.  Four slots per stream, each a (PID, NPA value, NPA mask,
+    accept_unaddressed) and a reassembler of its own: the same PID may sit in several slots.  There is no follow_pmts: ULE has no
+    dependable PMT signalling, the caller names the PID."""
+    _destroy = 'dvbs2gpu_ule_destroy'
+    SLOTS = 4
+    MALFORMED, CRC_ERROR, FILTERED, NO_ADDRESS, TEST, BRIDGED, EXTENSION, OTHER_PROTOCOL, BAD_IP, DATAGRAM = (1 << k for k in range(10))
+    ROW_KEYS = tuple(k for k, _ in UleRow._fields_)
+
+    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=1024):
+        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
+        h = C.c_void_p()
+        engine._check(self.lib.dvbs2gpu_ule_create(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096, max_rows=1024):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        return cls._host('dvbs2gpu_ule_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
+
+    @staticmethod
+    def layout():
+        """the SNDU and IP syntax the library relies on (dvbs2gpu_ule_layout) as a dict"""
+        lay = UleLayout()
+        load_library().dvbs2gpu_ule_get_layout(C.byref(lay))
+        return {k: int(getattr(lay, k)) for k, _ in UleLayout._fields_}
+
+    def reset(self):
+        self._check(self.lib.dvbs2gpu_ule_reset(self.h))
+
+    def set_watch(self, stream, slot, pid, npa=None, mask=None, accept_unaddressed=False):
+        """pid -1 empties the slot; npa / mask: six bytes each (None: all zero; an all-zero mask takes every address);
+        accept_unaddressed: SNDUs without a destination address (D = 1) pass the filter; the slot starts afresh"""
+        six = lambda v: None if v is None else (C.c_uint8 * 6)(*bytes(v))
+        if any(v is not None and len(bytes(v)) != 6 for v in (npa, mask)):
+            raise ValueError('an NPA address or mask has six bytes')
+        self._check(self.lib.dvbs2gpu_ule_set_watch(self.h, int(stream), int(slot), int(pid), six(npa), six(mask), int(bool(accept_unaddressed))))
+
+    def process(self, ts_tensors, out_tensors=None, nbytes=None):
+        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors: None for rows and counters
+        only, else out_tensors[i][k]: the uint8 CUDA buffer that receives the datagrams of slot k of stream i (None for an empty slot)
+        -> byte counts [i][k].  Dvbs2GpuError -5 carries .needed and .rows ([i][k] each) when a buffer or max_rows is too small
+        (nothing has advanced then)."""
+        n, S = self.nstreams, self.SLOTS
+        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
+        pout, cap = None, 0
+        if out_tensors is not None:
+            flat = [t for per in out_tensors for t in (list(per) + [None] * S)[:S]]
+            pout = (C.c_void_p * (n * S))(*[None if t is None else t.data_ptr() for t in flat])
+            cap = min([int(t.numel()) for t in flat if t is not None] or [0])
+        nb, nr = (C.c_int * (n * S))(), (C.c_int * (n * S))()
+        rc = self.lib.dvbs2gpu_ule_process_batch(self.h, pin, cnt, pout, cap, nb, nr, self.eng._stream())
+        split = lambda a: [list(a[i * S:(i + 1) * S]) for i in range(n)]
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            e.needed, e.rows = split(nb), split(nr)
+            raise e
+        return split(nb)
+
+    def work(self, ts, stream=0, slot=0, cap=None, deliver=True):
+        """one stream and slot, host buffers: numpy uint8 packets in -> the delivered datagrams back to back (numpy uint8), or None with
+        deliver=False (rows and counters only)"""
+        import numpy as np
+        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
+        cap = ts.size + 4096 if cap is None else cap
+        out = np.zeros(max(cap, 1), np.uint8) if deliver else None
+        rc = self.lib.dvbs2gpu_ule_work(self.h, int(stream), int(slot), C.c_void_p(ts.ctypes.data), ts.size,
+                                        C.c_void_p(out.ctypes.data) if deliver else None, cap if deliver else 0)
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            nb, nr = C.c_int(), C.c_int()
+            self.lib.dvbs2gpu_ule_get_needed(self.h, int(stream), int(slot), C.byref(nb), C.byref(nr))
+            e.needed, e.rows = nb.value, nr.value
+            raise e
+        return out[:rc].copy() if deliver else None
+
+    def needed(self, stream=0, slot=0):
+        """(bytes, rows) that the slot's last call needed, whether it succeeded or failed for capacity (bytes -1: the rows did not fit)"""
+        nb, nr = C.c_int(), C.c_int()
+        self._check(self.lib.dvbs2gpu_ule_get_needed(self.h, int(stream), int(slot), C.byref(nb), C.byref(nr)))
+        return nb.value, nr.value
+
+    def stats(self, stream=0, slot=-1):
+        st = UleStats()
+        self._check(self.lib.dvbs2gpu_ule_get_stats(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in UleStats._fields_}
+
+    def row_table(self, stream=0, slot=0):
+        """one dict per SNDU of the slot's last call (the fields of dvbs2gpu_ule_row; mac: six bytes), in row order"""
+        rows = self._rows(self.lib.dvbs2gpu_ule_get_row_table, UleRow, int(stream), int(slot))
+        return [{k: bytes(r.mac) if k == 'mac' else int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows]
+
+    def row_table_device(self, stream=0, slot=0):
+        """(device pointer or None, rows): the same table as dvbs2gpu_ule_row records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self.lib.dvbs2gpu_ule_get_row_table_device(self.h, int(stream), int(slot), C.byref(p), C.byref(n)))
         return p.value, n.value
 
 

@@ -2,7 +2,9 @@
 // of a PID of each of `nstreams` transport streams in HBM, reassembled, checked (CRC-32, MAC filter, LLC/SNAP, IP header) and their IP
 // datagrams laid back to back per slot.  Every rule is in mpe_rules.h, whose MpeHostStream is the sequential definition, the host bank
 // and the kernels' yardstick.  How a call's packets are cut into independent pieces is ts_reasm.h with the one-slot format MpeFmt below
-// (the section bank's header and length rule, the T2-MI bank's arrangement); this file holds what is the bank's own.
+// (the section bank's header and length rule, the T2-MI bank's arrangement); what a wave does with one unit in phase D -- the head
+// gather, the source the row rules read it through, the CRC over shares of the pieces -- is reasm_wave.h, shared with ule.hip; this
+// file holds what is the bank's own.
 //
 //   mpe_scan_kernel     one workgroup per (stream, slot); an empty slot returns at once.
 //     A-C  ts_reasm.h: the slot's packets into LDS, one lane for the continuity walk, one lane per PUSI packet and one for the section
@@ -18,7 +20,7 @@
 //     delivered row copies the datagram -- the section's bytes from 12 or 20 on, without the stuffing -- piece by piece to its offset;
 //     then the open section goes to the slot's 4096-byte buffer and the state is stored.
 // Two launches per call and one device-to-host copy, of the call record per (stream, slot).
-#include "ts_reasm.h"
+#include "reasm_wave.h"
 #include "mpe_rules.h"
 
 #include <memory>
@@ -29,7 +31,7 @@ using namespace s2;
 namespace s2 {
 
 constexpr int MPE_MAX_PACKETS = 4096;            // per stream and call: 10 bytes of LDS per packet
-constexpr int MPE_WG = 256, MPE_WAVES = MPE_WG / 64, MPE_HEAD = 128;
+constexpr int MPE_WG = 256, MPE_WAVES = MPE_WG / 64, MPE_HEAD = REASM_HEAD;
 static_assert(sizeof(MpeRow) == sizeof(dvbs2gpu_mpe_row) && sizeof(MpeRow) == 48, "row layout");
 static_assert(sizeof(MpeLayout) == sizeof(dvbs2gpu_mpe_layout), "layout layout");
 static_assert(MPE_MAX_PACKETS <= 32 * MPE_WG, "reasm_collect keeps a thread's match flags in one 32-bit mask (ts_thread_run)");
@@ -52,22 +54,6 @@ struct MpeFmt {
 typedef ReasmRec MpeRec;
 typedef ReasmView<MpeFmt> MpeView;
 struct MpeCall { int32_t needed, nrows, watched, ndelivered; MpeCnt cnt; };
-
-// a section's first 128 bytes in a wave, bytes 2 l and 2 l + 1 in lane l; every lane calls every member
-struct MpeWaveSrc {
-    unsigned h; int lane;
-    __device__ unsigned rd(int i) const { return (unsigned)__shfl((int)h, i >> 1) >> (8 * (i & 1)) & 255u; }
-    template <typename Fn> __device__ bool any(int n, Fn f) const {
-        const bool t = f(lane < n ? lane : 0);
-        return __ballot(lane < n && t) != 0;
-    }
-    template <typename Fn> __device__ unsigned sum(int n, Fn f) const {
-        unsigned v = f(lane < n ? lane : 0);
-        if (lane >= n) v = 0;
-        for (int k = 32; k > 0; k >>= 1) v += (unsigned)__shfl_xor((int)v, k);
-        return v;
-    }
-};
 
 // dynamic LDS: wa[max_packets] (dwords), rc[max_packets] (dwords), wb[max_packets] (16 bits each).  only >= 0: the one (stream, slot)
 // that receives its stream's packets (the single-slot entry point); the others take an empty call
@@ -134,48 +120,10 @@ __global__ void __launch_bounds__(MPE_WG) mpe_scan_kernel(const uint8_t* const* 
         for (int r = wave; r < nrows; r += MPE_WAVES) {
             const MpeRec q = rec[r];
             const int total = q.total;
-            // the head: lane l keeps bytes 2 l and 2 l + 1 of the section.  The walk is the same in every lane; a piece is read by the lanes it holds
-            unsigned h = 0;
-            reasm_pieces(q, v, MPE_HEAD, [&](int pos, const uint8_t* src, int len) {
-                const int a = 2 * lane - pos;
-                if (a >= 0 && a < len) h |= src[a];
-                if (a + 1 >= 0 && a + 1 < len) h |= (unsigned)src[a + 1] << 8;
-            });
-            const MpeWaveSrc hd = {h, lane};
+            // the head (lane l keeps bytes 2 l and 2 l + 1 of the section) and, where the rules take it, the CRC: reasm_wave.h
+            const ReasmWaveSrc hd = reasm_wave_head(q, v, lane);
             uint32_t x = 0;
-            if (mpe_takes_crc(hd.rd(0), hd.rd(1), total)) {                        // (the same in every lane; a section has three bytes at least)
-                // `sub` lanes per PIECE (the section's bytes in one TS payload), 64 / sub pieces a round.  A section has few pieces (9 at
-                // 1416 bytes, 24 at 4096, without adaptation fields): with a lane per piece most of the wave would wait for the few lanes
-                // that each take 184 bytes, so a piece is cut into `sub` equal shares, as many as the pieces expected of `total` leave room
-                // for; sections of more pieces (adaptation fields) take further rounds
-                int sub = 16;
-                while (sub > 1 && sub * (total / (TSMON_TS - 4) + 2) > 64) sub >>= 1;
-                const int per_round = 64 / sub;
-                x = lane == 0 ? crc32m_mulmod(0xFFFFFFFFu, crc32m_xpow((uint32_t)total)) : 0;
-                for (int base = 0;; base += per_round) {
-                    int idx = 0, ppos = 0, plen = 0;                               // idx: the same in every lane
-                    const uint8_t* psrc = nullptr;
-                    const int mine = base + lane / sub;
-                    reasm_pieces(q, v, total, [&](int pos, const uint8_t* src, int len) {
-                        if (idx == mine) { ppos = pos; psrc = src; plen = len; }
-                        ++idx;
-                    });
-                    {                                                              // my share of the piece
-                        const int share = (plen + sub - 1) / sub, a = min((lane % sub) * share, plen), b = min(a + share, plen);
-                        psrc += a; ppos += a; plen = b - a;
-                    }
-                    uint32_t c = 0;
-                    int i = 0;
-                    for (; i + 4 <= plen; i += 4) {                                // an unaligned dword inside the piece
-                        const unsigned d = *reinterpret_cast<const ts_unaligned_u32*>(psrc + i);
-                        for (int k = 0; k < 4; ++k) c = crc32m_byte(c, d >> (8 * k) & 255);
-                    }
-                    for (; i < plen; ++i) c = crc32m_byte(c, psrc[i]);
-                    if (plen > 0) x ^= crc32m_mulmod(c, crc32m_xpow((uint32_t)(total - ppos - plen)));
-                    if (idx <= base + per_round) break;
-                }
-                for (int k = 32; k > 0; k >>= 1) x ^= __shfl_xor(x, k);
-            }
+            if (mpe_takes_crc(hd.rd(0), hd.rd(1), total)) x = reasm_wave_crc(q, v, total, lane);      // (the same in every lane; a section has three bytes at least)
             const MpeRow row = mpe_row_fields(hd, total, x == 0, w, q.j0 < 0 ? -1 : wa_k(wa[q.j0]), wa_k(wa[q.j1]));
             if (lane == 0) {
                 rows[r] = row;

@@ -1,14 +1,15 @@
 // The rules of the MPE bank (own extension; include/dvbs2gpu.h), each stated once and shared by the kernels
 // (mpe.hip), the native host bank (MpeHostStream below, behind dvbs2gpu_mpe_create_host) and a plain C++ test program: the layout of a
 // DSM-CC datagram_section and of the IP headers behind it as one struct (MpeLayout), what a TS packet of a slot's PID does to the slot,
-// and what an emitted section's row says.
+// and what an emitted section's row says.  The IP header rules behind the MPE header are ip_rules.h, shared with the ULE bank.
 //
 // The sequential form -- MpeHostStream::run, which is ts_reasm_run with this format -- IS the definition; every other form must give
 // its results for every cutting of a stream into calls.  The syntax is written from memory of ETSI EN 301 192 (section 7), RFC 791,
 // RFC 8200 and RFC 1042: every offset and limit the code relies on is a field of MpeLayout, reported through dvbs2gpu_mpe_get_layout
 // and compared with the tests' model.
-// Standard headers only: the host tests compile this file with a plain C++ compiler.
+// Standard headers, ip_rules.h and ts_reasm_rules.h only: the host tests compile this file with a plain C++ compiler.
 #pragma once
+#include "ip_rules.h"
 #include "ts_reasm_rules.h"
 
 #include <cstring>
@@ -37,7 +38,9 @@ struct MpeLayout {                     // the layout of dvbs2gpu_mpe_layout (mpe
     int32_t ipv6_payload_length_at, ipv6_next_header_at;   // 4, 6
     int32_t head_bytes;                // a row is decided from the first 12 + 8 + 60 + 4 = 84 bytes of its section at most
 };
-constexpr MpeLayout MPE = {3, 0x0FFF, 4093, 4096, 0x3E, 12, 4, 16, {11, 10, 9, 8, 4, 3}, 5, 6, 7, 8, 6, 0x0800, 0x86DD, 20, 2, 6, 9, 12, 16, 40, 4, 6, 84};
+constexpr MpeLayout MPE = {3, 0x0FFF, 4093, 4096, 0x3E, 12, 4, 16, {11, 10, 9, 8, 4, 3}, 5, 6, 7, 8, 6, IP.ethertype_ipv4, IP.ethertype_ipv6, IP.ipv4_min_header,
+                           IP.ipv4_total_length_at, IP.ipv4_fragment_at, IP.ipv4_protocol_at, IP.ipv4_src_at, IP.ipv4_dst_at, IP.ipv6_header, IP.ipv6_payload_length_at,
+                           IP.ipv6_next_header_at, 84};
 
 constexpr int MPE_SLOTS = 4, MPE_BUF = 4096;
 // row flags (DVBS2GPU_MPE_*)
@@ -96,37 +99,14 @@ TS_HD inline MpeRow mpe_row_fields(const Src& s, int total, bool crc_ok, const M
             return r;
         }
         r.ethertype = (uint16_t)(s.rd(at + MPE.ethertype_at) << 8 | s.rd(at + MPE.ethertype_at + 1));
-        family = r.ethertype == MPE.ethertype_ipv4 ? 4 : r.ethertype == MPE.ethertype_ipv6 ? 6 : 0;
+        family = r.ethertype == IP.ethertype_ipv4 ? 4 : r.ethertype == IP.ethertype_ipv6 ? 6 : 0;
         at += MPE.llc_snap_bytes;
     } else {
         family = end > at ? (int)(s.rd(at) >> 4) : 0;
     }
-    if (family != 4 && family != 6) { r.flags |= MPE_OTHER_PROTOCOL; return r; }
-    const int avail = end - at;
-    int ports_at = -1;
-    if (family == 4) {
-        const int hl = avail >= MPE.ipv4_min_header ? 4 * (int)(s.rd(at) & 15) : 0;
-        const int tl = hl ? (int)(s.rd(at + MPE.ipv4_total_length_at) << 8 | s.rd(at + MPE.ipv4_total_length_at + 1)) : 0;
-        if (hl < MPE.ipv4_min_header || hl > avail || tl < hl || tl > avail) { r.flags |= MPE_BAD_IP; return r; }
-        unsigned sum = s.sum(hl / 2, [&](int k) { return s.rd(at + 2 * k) << 8 | s.rd(at + 2 * k + 1); });
-        sum = (sum & 0xFFFF) + (sum >> 16); sum = (sum & 0xFFFF) + (sum >> 16);
-        if (sum != 0xFFFF) { r.flags |= MPE_BAD_IP; return r; }
-        auto be32 = [&](int i) { return (uint32_t)(s.rd(i) << 24 | s.rd(i + 1) << 16 | s.rd(i + 2) << 8 | s.rd(i + 3)); };
-        r.bytes = tl; r.protocol = (uint8_t)s.rd(at + MPE.ipv4_protocol_at);
-        r.src4 = be32(at + MPE.ipv4_src_at); r.dst4 = be32(at + MPE.ipv4_dst_at);
-        const unsigned frag = (s.rd(at + MPE.ipv4_fragment_at) << 8 | s.rd(at + MPE.ipv4_fragment_at + 1)) & 0x1FFF;
-        if (frag == 0 && tl >= hl + 4) ports_at = at + hl;
-    } else {
-        const int pl = avail >= MPE.ipv6_header ? (int)(s.rd(at + MPE.ipv6_payload_length_at) << 8 | s.rd(at + MPE.ipv6_payload_length_at + 1)) : 0;
-        if (avail < MPE.ipv6_header || MPE.ipv6_header + pl > avail) { r.flags |= MPE_BAD_IP; return r; }
-        r.bytes = MPE.ipv6_header + pl; r.protocol = (uint8_t)s.rd(at + MPE.ipv6_next_header_at);
-        if (pl >= 4) ports_at = at + MPE.ipv6_header;
-    }
-    r.family = (uint8_t)family; r.stuffing = (uint16_t)(avail - r.bytes);
-    if (ports_at >= 0 && (r.protocol == 6 || r.protocol == 17)) {
-        r.src_port = (uint16_t)(s.rd(ports_at) << 8 | s.rd(ports_at + 1)); r.dst_port = (uint16_t)(s.rd(ports_at + 2) << 8 | s.rd(ports_at + 3));
-    }
-    r.flags |= MPE_DATAGRAM;
+    // the IP header behind it: ip_rules.h, shared with the ULE bank
+    const int ip = ip_row_fields(s, at, end, family, r);
+    r.flags |= ip == IP_IS_DATAGRAM ? MPE_DATAGRAM : ip == IP_IS_BAD ? MPE_BAD_IP : MPE_OTHER_PROTOCOL;
     return r;
 }
 // where the datagram of a DATAGRAM row starts in its section: behind the MPE header, and behind LLC/SNAP where there was one
