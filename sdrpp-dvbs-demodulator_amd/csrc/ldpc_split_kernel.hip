@@ -69,30 +69,40 @@ __device__ __forceinline__ void lds_ready_n(int outstanding, uint32_t& r_lo, uin
 }
 #undef LDS_READY_CASE
 
-// Table / record traffic of the layer loop goes through buffer resources: (uniform base in the descriptor) + (uniform pseudo-layer offset in a scalar
-// register) + (the thread's 32-bit byte offset) -- left to itself the compiler builds a 64-bit address per lane and load (v_lshl_add_u64, a half-rate
+// Table / record traffic of the layer loop goes through STRIDED buffer resources with the add-thread-id flag: both buffers are arrays of fixed-size per-thread entries, so
+// the address is (the wave's base in the descriptor) + (uniform pseudo-layer offset in a scalar register) + (lane x stride, added by the memory unit) -- the instructions carry
+// NO address register ("off") and the layer loop no address arithmetic.  Left to itself the compiler builds a 64-bit address per lane and load (v_lshl_add_u64, a half-rate
 // instruction, and twice the address registers).  The loads stay visible to the compiler, which keeps vmcnt.
+// What gfx950 does with such a descriptor (tools/ubench/buffer_stride_probe.hip, profiles/buffer_stride_probe.txt):
+//   * word 3 holds the flag (bit 23) and NOTHING in bits 18:15: in this mode they are stride bits 17:14 -- the usual 0x00020000 there makes the stride 65 536 + 16
+//   * the lane index that is added is the lane of the WAVE (0..63): wave w's entries start w x 64 x stride behind the array's -- that goes into the descriptor's base
+//   * num_records bounds nothing in this form: the range check looks at an index or offset REGISTER, and there is none (every lane of a wave read with 0 records, with
+//     and without a scalar offset; with an index register the unit is ENTRIES and the scalar offset stays outside the check, as it does for the unstrided form).  It is set to
+//     the entries of the array behind the wave's base.
+constexpr int BUF_ADD_TID = 0x00800000;
+template <int NW>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wave_entries_rsrc(uint32_t* base, const int wave, const int words) {      // entries of NW words, one per thread
+    return __builtin_amdgcn_make_buffer_rsrc(base + wave * (64 * NW), NW * 4, words / NW - wave * 64, BUF_ADD_TID);
+}
 // (the words a thread fetches ahead live in ONE register tuple per fetch -- a vector value -- so that the empty asm statements that pin them in place keep them contiguous: as
 // separate 32-bit values the allocator scatters them and the fetch lands in a second tuple, copied over behind a wait)
 template <int NW> struct FetchWords { typedef uint32_t type __attribute__((ext_vector_type(NW))); };
 template <> struct FetchWords<1> { typedef uint32_t type; };
 template <int NW>
-__device__ __forceinline__ typename FetchWords<NW>::type bload(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff) {
+__device__ __forceinline__ typename FetchWords<NW>::type bload(__amdgpu_buffer_rsrc_t rs, uint32_t soff) {
     static_assert(NW == 1 || NW == 2 || NW == 4, "one buffer load per fetch");
-    if constexpr (NW == 1) return __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0);
-    else if constexpr (NW == 2) return __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0);
-    else return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
+    if constexpr (NW == 1) return __builtin_amdgcn_raw_buffer_load_b32(rs, 0, soff, 0);
+    else if constexpr (NW == 2) return __builtin_amdgcn_raw_buffer_load_b64(rs, 0, soff, 0);
+    else return __builtin_amdgcn_raw_buffer_load_b128(rs, 0, soff, 0);
 }
 template <int NW>
 __device__ __forceinline__ uint32_t fetch_word(const typename FetchWords<NW>::type& v, int i) { if constexpr (NW == 1) return v; else return v[i]; }
 template <int NW>
-__device__ __forceinline__ void bstore(const uint32_t (&w)[NW], __amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff) {
-    if constexpr (NW == 1) { __builtin_amdgcn_raw_buffer_store_b32(w[0], rs, voff, soff, 0); }
-    else if constexpr (NW == 2) { const u32x2 v = {w[0], w[1]}; __builtin_amdgcn_raw_buffer_store_b64(v, rs, voff, soff, 0); }
-    else {
-#pragma unroll
-        for (int i = 0; i < NW; i += 4) { const u32x4 v = {w[i], w[i + 1], w[i + 2], w[i + 3]}; __builtin_amdgcn_raw_buffer_store_b128(v, rs, voff + 4 * i, soff, 0); }
-    }
+__device__ __forceinline__ void bstore(const uint32_t (&w)[NW], __amdgpu_buffer_rsrc_t rs, uint32_t soff) {
+    static_assert(NW == 1 || NW == 2 || NW == 4, "one buffer store per record");
+    if constexpr (NW == 1) { __builtin_amdgcn_raw_buffer_store_b32(w[0], rs, 0, soff, 0); }
+    else if constexpr (NW == 2) { const u32x2 v = {w[0], w[1]}; __builtin_amdgcn_raw_buffer_store_b64(v, rs, 0, soff, 0); }
+    else { const u32x4 v = {w[0], w[1], w[2], w[3]}; __builtin_amdgcn_raw_buffer_store_b128(v, rs, 0, soff, 0); }
 }
 
 #define QUAD_DPP(x_, ctrl) __builtin_amdgcn_update_dpp(0, (int)(x_), (ctrl), 0xf, 0xf, true)
@@ -119,6 +129,10 @@ struct RowState {
             if (2 * p + 1 < S::HS) addr[2 * p + 1] = w >> 16;
             RP[p] = rec_pair_dw(fetch_word<S::REC>(rec, (2 * p) >> 2), 2 * p);
         }
+        // (taken in EVERY pseudo-layer, though the conflict-free ones never read it: it has to leave the fetched words before the next fetch is issued into those registers, i.e.
+        // before the layer's kind is looked at.  Tried: taken only by the kinds that read it, in a block of its own in front of the fetch -- laid out in line the conflict-free
+        // layers jump over it, laid out as a side block the allocator spills the word and the layers with shared bits reload it eight times: <12> 29.5 / 30.0 instead of
+        // 27.1 ms per 4096 frames x 50 iterations on decodable frames either way; with the fetch moved into the kinds' branches it lands in a second register set and is copied)
         rw = (fetch_word<S::NPW>(AD, S::RI_WORD) >> S::RI_SHIFT) & 0xffffu;
     }
     __device__ __forceinline__ void pin() {
@@ -691,8 +705,8 @@ __global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(8)
             const uint32_t cflagb = (uint32_t)npad + 8u * 360u;                            // LDS address of the chain layers' two verdict words (the posteriors start at 0)
             uint32_t* __restrict__ msg = A.msg_ws + (size_t)blockIdx.x * (size_t)A.pent_base;
             uint32_t* __restrict__ sgn = A.sgn_ws + (size_t)blockIdx.x * SGN_WS_DWORDS;
-            const __amdgpu_buffer_rsrc_t rs_tab = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(P->atab), 0, P->tab_words * 4, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rs_msg = __builtin_amdgcn_make_buffer_rsrc(msg, 0, A.pent_base * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_tab = wave_entries_rsrc<NPW>(const_cast<uint32_t*>(P->atab), wave, P->tab_words);
+            const __amdgpu_buffer_rsrc_t rs_msg = wave_entries_rsrc<REC>(msg, wave, A.pent_base);
             const bool check = !A.force || it == A.max_trials;
             if (check) {
 #if defined(LDPC_PROF) && LDPC_PROF == 5
@@ -734,8 +748,8 @@ __global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(8)
             typename FetchWords<NPW>::type pw_n;
             LdpcSplitLayer Lnext = layer_at(layers, 0), Lnext2 = layer_at(layers, npl > 1 ? 1 : 0);
             uint32_t soff_tab = 0;
-            pw_n = bload<NPW>(rs_tab, (uint32_t)t * (NPW * 4), soff_tab);
-            rec_n = bload<REC>(rs_msg, (uint32_t)t * (REC * 4), Lnext.rec_off * 4u);
+            pw_n = bload<NPW>(rs_tab, soff_tab);
+            rec_n = bload<REC>(rs_msg, Lnext.rec_off * 4u);
             // (claimed before the loop: a load still in flight on the loop's entry edge makes the compiler open EVERY pseudo-layer with vmcnt(0) -- which, coming round the
             // back edge, waits for the previous pseudo-layer's record store)
             asm volatile("" : "+v"(rec_n), "+v"(pw_n));
@@ -748,11 +762,6 @@ __global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(8)
                 Lnext = Lnext2;
                 Lnext2 = layer_at(layers, pl + 2 < npl ? pl + 2 : npl - 1);
                 soff_tab += T * NPW * 4;
-                // (everything a layer derives from the thread index is derived HERE, from a copy the compiler cannot see through: hoisted out of the loops these values
-                // stay in registers across the whole kernel, and at 64 / 80 registers they are what gets spilled and reloaded inside the layers)
-                int tt = t;
-                asm volatile("" : "+v"(tt));
-                const uint32_t voff_rec = (uint32_t)tt * (REC * 4), voff_tab = (uint32_t)tt * (NPW * 4);
                 RowState<MAXDEG> RS;
                 RS.unpack(pw_n, rec_n);
                 // (the fetched words end HERE as far as the compiler can tell -- every value taken from them exists, and the registers are free for the fetch below: without
@@ -760,29 +769,34 @@ __global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(8)
                 RS.pin();
                 asm volatile("" : "+v"(pw_n), "+v"(rec_n));
                 if (pl + 1 < npl && !(LDPC_SPLIT_EXP & 2)) {
-                    if (!(LDPC_SPLIT_EXP & 16)) pw_n = bload<NPW>(rs_tab, voff_tab, soff_tab);
-                    if (!(LDPC_SPLIT_EXP & 32)) rec_n = bload<REC>(rs_msg, voff_rec, Lnext.rec_off * 4u);
+                    if (!(LDPC_SPLIT_EXP & 16)) pw_n = bload<NPW>(rs_tab, soff_tab);
+                    if (!(LDPC_SPLIT_EXP & 32)) rec_n = bload<REC>(rs_msg, Lnext.rec_off * 4u);
                 }
+                // (what a layer derives from the thread index is derived inside the layer, from a copy the compiler cannot see through: hoisted out of the loops these values
+                // stay in registers across the whole kernel, and at 64 / 80 registers they are what gets spilled and reloaded inside the layers.  Only the layers that use the
+                // index take the copy: chain and speculative layers, and the tests for the row without a previous parity bit and for the odd slot)
+                auto thread_index = [&]() __attribute__((always_inline)) { int tt = t; asm volatile("" : "+v"(tt)); return tt; };
+                const uint32_t kind = L.kind_nw & 0xffu;
                 uint32_t ro[REC];
-                if (LDPC_SPLIT_SKIP && ((LDPC_SPLIT_SKIP >> (L.kind_nw & 0xffu)) & 1)) {      // (timing / counter experiments: the layers of these kinds do nothing)
+                if (LDPC_SPLIT_SKIP && ((LDPC_SPLIT_SKIP >> kind) & 1)) {      // (timing / counter experiments: the layers of these kinds do nothing)
 #pragma unroll
                     for (int w = 0; w < REC; ++w) ro[w] = RS.rw;
-                } else if ((L.kind_nw & 0xffu) == 0) {
+                } else if (kind == 0) {
                     int M0, M1, SXs;
-                    row_input<MAXDEG, 0>(RS, 0u, 0u, tt, M0, M1, SXs);
+                    row_input<MAXDEG, 0>(RS, 0u, 0u, S::ODD ? thread_index() : t, M0, M1, SXs);
                     if (LDPC_SPLIT_EXP & 8) { ro[0] = (uint32_t)(M0 ^ M1 ^ SXs); ro[REC - 1] = ro[0]; }
                     else row_output<MAXDEG, 0>(RS, M0, M1, SXs, 0u, ro);
-                } else if ((L.kind_nw & 0xffu) == 7) {
+                } else if (kind == 7) {
                     int M0, M1, SXs;
-                    row_input<MAXDEG, 0, 1>(RS, 0u, L.aux, tt, M0, M1, SXs);
+                    row_input<MAXDEG, 0, 1>(RS, 0u, L.aux, thread_index(), M0, M1, SXs);
                     row_output<MAXDEG, 0>(RS, M0, M1, SXs, 0u, ro);
-                } else if ((L.kind_nw & 0xffu) == 1) {
+                } else if (kind == 1) {
                     ++cseq;
-                    chain_layer<MAXDEG>(RS, ro, L, ents[L.ent_off + 1], tt, post, cw, cflagb, cseq, A.dbg != 0);
+                    chain_layer<MAXDEG>(RS, ro, L, ents[L.ent_off + 1], thread_index(), post, cw, cflagb, cseq, A.dbg != 0);
                 } else {
                     ++cseq;
                     // (a half of fewer than four slots has no speculative layers: the plan refuses them, ldpc_split_plan.h)
-                    if constexpr (S::HS >= 4) spec_layer<MAXDEG>(RS, ro, L, P->atab, tt, cw, A.prof, pl, cflagb, cseq, A.dbg != 0);
+                    if constexpr (S::HS >= 4) spec_layer<MAXDEG>(RS, ro, L, P->atab, thread_index(), cw, A.prof, pl, cflagb, cseq, A.dbg != 0);
                 }
                 // the next pseudo-layer's words are claimed HERE, before this one's record store is issued: the wait for them then sits where they have had a whole
                 // pseudo-layer to arrive, and the top of the next pseudo-layer waits for nothing (ldpc_kernel.hip)
@@ -794,7 +808,7 @@ __global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(8)
                 if (A.prof && blockIdx.x == 0 && (t == 0 || t == 384)) A.prof[200 + pl + (t ? 50 : 0)] += clock64() - t_claim;
 #endif
                 if (LDPC_SPLIT_EXP & (2 | 64)) asm volatile("" :: "v"(ro[0]), "v"(ro[REC - 1]));
-                else bstore<REC>(ro, rs_msg, voff_rec, L.rec_off * 4u);
+                else bstore<REC>(ro, rs_msg, L.rec_off * 4u);
                 lds_pairs_wait();
                 if (!(LDPC_SPLIT_EXP & 4)) lds_barrier();
 #if defined(LDPC_PROF)
