@@ -913,44 +913,39 @@ private:
     int status_ = 0;
     std::string error_;
 };
-/* MPE bank for one transport stream (dvbs2gpu_mpe_*, include/dvbs2gpu.h; an extension): the DSM-CC datagram_sections of a PID behind
- * BBFrameTSParser or TSMonitor are reassembled and checked and their IP datagrams laid back to back.  Four slots, each a (PID, MAC
- * value, MAC mask) and a reassembler of its own.  init() (a device bank) or initHost() (the library's host implementation, no device)
- * and the setters throw; work() sits in the data path and does NOT throw: a failing call returns 0 and leaves its code in status() and
- * its text in error(), sticky until clearStatus(). */
-class MpeBank {
+namespace detail {
+/* What MpeBank and UleBank share (the datagram banks: dvbs2gpu_mpe_*, dvbs2gpu_ule_*): everything but setWatch().  A: the bank's C
+ * functions and types --  Handle, Stats, Row;  name ("MpeBank");  create, create_host, destroy, reset, work, get_needed, get_stats,
+ * get_row_table (pointers to the C functions). */
+template <typename A>
+class DatagramBank {
 public:
-    MpeBank() {}
-    ~MpeBank() {
-        if (h) dvbs2gpu_mpe_destroy(h);
+    DatagramBank() {}
+    ~DatagramBank() {
+        if (h) A::destroy(h);
     }
-    MpeBank(const MpeBank&) = delete;
-    MpeBank& operator=(const MpeBank&) = delete;
+    DatagramBank(const DatagramBank&) = delete;
+    DatagramBank& operator=(const DatagramBank&) = delete;
 
     void init(int max_packets, int max_rows, int device = 0) {
         release();
         eng = Engine::get(device);
-        check(dvbs2gpu_mpe_create(eng->ctx, 1, max_packets, max_rows, &h));
+        check(A::create(eng->ctx, 1, max_packets, max_rows, &h));
     }
     void initHost(int max_packets, int max_rows) {
         release();
-        check(dvbs2gpu_mpe_create_host(1, max_packets, max_rows, &h));
+        check(A::create_host(1, max_packets, max_rows, &h));
     }
-    void reset() { check(dvbs2gpu_mpe_reset(need())); }
-    /* slot 0..3; pid -1 empties the slot; mac_value / mac_mask: six bytes each in network order, nullptr: all zero (every address).
-     * The same PID may sit in several slots. */
-    void setWatch(int slot, int pid, const uint8_t* mac_value = nullptr, const uint8_t* mac_mask = nullptr) {
-        check(dvbs2gpu_mpe_set_watch(need(), 0, slot, pid, mac_value, mac_mask));
-    }
+    void reset() { check(A::reset(need())); }
     /* nbytes of whole TS packets in for one slot; datagrams (buffer_outsize bytes; nullptr: rows and counters only) receives the
      * slot's IP datagrams back to back; returns their bytes, 0 on failure (see status(); on DVBS2GPU_ERR_CAPACITY needed() has the
      * sizes and nothing was consumed) */
     int work(int slot, const uint8_t* ts, int nbytes, uint8_t* datagrams, int buffer_outsize) noexcept {
-        const int n = h ? dvbs2gpu_mpe_work(h, 0, slot, ts, nbytes, datagrams, buffer_outsize) : DVBS2GPU_ERR_ARG;
+        const int n = h ? A::work(h, 0, slot, ts, nbytes, datagrams, buffer_outsize) : DVBS2GPU_ERR_ARG;
         if (n >= 0) return n;
         if (status_ == 0) {
             status_ = n;
-            try { error_ = h ? dvbs2gpu_last_error() : "MpeBank used before init()"; } catch (...) {}
+            try { error_ = h ? dvbs2gpu_last_error() : std::string(A::name) + " used before init()"; } catch (...) {}
         }
         return 0;
     }
@@ -960,116 +955,88 @@ public:
     /* {bytes, rows} that the slot's last work() needed */
     std::pair<int, int> needed(int slot) {
         int b = 0, r = 0;
-        check(dvbs2gpu_mpe_get_needed(need(), 0, slot, &b, &r));
+        check(A::get_needed(need(), 0, slot, &b, &r));
         return {b, r};
     }
 
-    dvbs2gpu_mpe_stats stats(int slot = -1) {
-        dvbs2gpu_mpe_stats s;
-        check(dvbs2gpu_mpe_get_stats(need(), 0, slot, &s));
+    typename A::Stats stats(int slot = -1) {
+        typename A::Stats s;
+        check(A::get_stats(need(), 0, slot, &s));
         return s;
     }
-    /* one row per section of the slot's last work(), in row order */
-    std::vector<dvbs2gpu_mpe_row> rowTable(int slot) {
+    /* one row per unit (section, SNDU) of the slot's last work(), in row order */
+    std::vector<typename A::Row> rowTable(int slot) {
         int n = 0;
-        check(dvbs2gpu_mpe_get_row_table(need(), 0, slot, nullptr, 0, &n));
-        std::vector<dvbs2gpu_mpe_row> rows((size_t)n);
-        if (n > 0) check(dvbs2gpu_mpe_get_row_table(h, 0, slot, rows.data(), n, &n));
+        check(A::get_row_table(need(), 0, slot, nullptr, 0, &n));
+        std::vector<typename A::Row> rows((size_t)n);
+        if (n > 0) check(A::get_row_table(h, 0, slot, rows.data(), n, &n));
         return rows;
     }
 
-private:
+protected:
     void release() {
-        if (h) dvbs2gpu_mpe_destroy(h);
+        if (h) A::destroy(h);
         h = nullptr;
     }
-    dvbs2gpu_mpe* need() {
-        if (!h) throw std::runtime_error("dvbs2gpu: MpeBank used before init()");
+    typename A::Handle* need() {
+        if (!h) throw std::runtime_error(std::string("dvbs2gpu: ") + A::name + " used before init()");
         return h;
     }
+
+private:
     std::shared_ptr<Engine> eng;
-    dvbs2gpu_mpe* h = nullptr;
+    typename A::Handle* h = nullptr;
     int status_ = 0;
     std::string error_;
+};
+struct MpeApi {
+    typedef dvbs2gpu_mpe Handle; typedef dvbs2gpu_mpe_stats Stats; typedef dvbs2gpu_mpe_row Row;
+    static constexpr const char* name = "MpeBank";
+    static constexpr auto create = &dvbs2gpu_mpe_create, create_host = &dvbs2gpu_mpe_create_host;
+    static constexpr auto destroy = &dvbs2gpu_mpe_destroy;
+    static constexpr auto reset = &dvbs2gpu_mpe_reset;
+    static constexpr auto work = &dvbs2gpu_mpe_work;
+    static constexpr auto get_needed = &dvbs2gpu_mpe_get_needed;
+    static constexpr auto get_stats = &dvbs2gpu_mpe_get_stats;
+    static constexpr auto get_row_table = &dvbs2gpu_mpe_get_row_table;
+};
+struct UleApi {
+    typedef dvbs2gpu_ule Handle; typedef dvbs2gpu_ule_stats Stats; typedef dvbs2gpu_ule_row Row;
+    static constexpr const char* name = "UleBank";
+    static constexpr auto create = &dvbs2gpu_ule_create, create_host = &dvbs2gpu_ule_create_host;
+    static constexpr auto destroy = &dvbs2gpu_ule_destroy;
+    static constexpr auto reset = &dvbs2gpu_ule_reset;
+    static constexpr auto work = &dvbs2gpu_ule_work;
+    static constexpr auto get_needed = &dvbs2gpu_ule_get_needed;
+    static constexpr auto get_stats = &dvbs2gpu_ule_get_stats;
+    static constexpr auto get_row_table = &dvbs2gpu_ule_get_row_table;
+};
+}   // namespace detail
+/* MPE bank for one transport stream (dvbs2gpu_mpe_*, include/dvbs2gpu.h; an extension): the DSM-CC datagram_sections of a PID behind
+ * BBFrameTSParser or TSMonitor are reassembled and checked and their IP datagrams laid back to back.  Four slots, each a (PID, MAC
+ * value, MAC mask) and a reassembler of its own.  init() (a device bank) or initHost() (the library's host implementation, no device)
+ * and the setters throw; work() sits in the data path and does NOT throw: a failing call returns 0 and leaves its code in status() and
+ * its text in error(), sticky until clearStatus(). */
+class MpeBank : public detail::DatagramBank<detail::MpeApi> {
+public:
+    /* slot 0..3; pid -1 empties the slot; mac_value / mac_mask: six bytes each in network order, nullptr: all zero (every address).
+     * The same PID may sit in several slots. */
+    void setWatch(int slot, int pid, const uint8_t* mac_value = nullptr, const uint8_t* mac_mask = nullptr) {
+        check(dvbs2gpu_mpe_set_watch(need(), 0, slot, pid, mac_value, mac_mask));
+    }
 };
 /* ULE bank for one transport stream (dvbs2gpu_ule_*, include/dvbs2gpu.h; an extension): the ULE SNDUs (RFC 4326) of a PID behind
  * BBFrameTSParser or TSMonitor are reassembled and checked and their IP datagrams laid back to back.  Four slots, each a (PID, NPA
  * value, NPA mask, accept_unaddressed) and a reassembler of its own.  init() (a device bank) or initHost() (the library's host
  * implementation, no device) and the setters throw; work() sits in the data path and does NOT throw: a failing call returns 0 and
  * leaves its code in status() and its text in error(), sticky until clearStatus(). */
-class UleBank {
+class UleBank : public detail::DatagramBank<detail::UleApi> {
 public:
-    UleBank() {}
-    ~UleBank() {
-        if (h) dvbs2gpu_ule_destroy(h);
-    }
-    UleBank(const UleBank&) = delete;
-    UleBank& operator=(const UleBank&) = delete;
-
-    void init(int max_packets, int max_rows, int device = 0) {
-        release();
-        eng = Engine::get(device);
-        check(dvbs2gpu_ule_create(eng->ctx, 1, max_packets, max_rows, &h));
-    }
-    void initHost(int max_packets, int max_rows) {
-        release();
-        check(dvbs2gpu_ule_create_host(1, max_packets, max_rows, &h));
-    }
-    void reset() { check(dvbs2gpu_ule_reset(need())); }
     /* slot 0..3; pid -1 empties the slot; npa_value / npa_mask: six bytes each, nullptr: all zero (every address); accept_unaddressed:
      * SNDUs without a destination address pass.  The same PID may sit in several slots. */
     void setWatch(int slot, int pid, const uint8_t* npa_value = nullptr, const uint8_t* npa_mask = nullptr, bool accept_unaddressed = false) {
         check(dvbs2gpu_ule_set_watch(need(), 0, slot, pid, npa_value, npa_mask, accept_unaddressed ? 1 : 0));
     }
-    /* nbytes of whole TS packets in for one slot; datagrams (buffer_outsize bytes; nullptr: rows and counters only) receives the
-     * slot's IP datagrams back to back; returns their bytes, 0 on failure (see status(); on DVBS2GPU_ERR_CAPACITY needed() has the
-     * sizes and nothing was consumed) */
-    int work(int slot, const uint8_t* ts, int nbytes, uint8_t* datagrams, int buffer_outsize) noexcept {
-        const int n = h ? dvbs2gpu_ule_work(h, 0, slot, ts, nbytes, datagrams, buffer_outsize) : DVBS2GPU_ERR_ARG;
-        if (n >= 0) return n;
-        if (status_ == 0) {
-            status_ = n;
-            try { error_ = h ? dvbs2gpu_last_error() : "UleBank used before init()"; } catch (...) {}
-        }
-        return 0;
-    }
-    int status() const { return status_; }
-    const std::string& error() const { return error_; }
-    void clearStatus() { status_ = 0; error_.clear(); }
-    /* {bytes, rows} that the slot's last work() needed */
-    std::pair<int, int> needed(int slot) {
-        int b = 0, r = 0;
-        check(dvbs2gpu_ule_get_needed(need(), 0, slot, &b, &r));
-        return {b, r};
-    }
-
-    dvbs2gpu_ule_stats stats(int slot = -1) {
-        dvbs2gpu_ule_stats s;
-        check(dvbs2gpu_ule_get_stats(need(), 0, slot, &s));
-        return s;
-    }
-    /* one row per SNDU of the slot's last work(), in row order */
-    std::vector<dvbs2gpu_ule_row> rowTable(int slot) {
-        int n = 0;
-        check(dvbs2gpu_ule_get_row_table(need(), 0, slot, nullptr, 0, &n));
-        std::vector<dvbs2gpu_ule_row> rows((size_t)n);
-        if (n > 0) check(dvbs2gpu_ule_get_row_table(h, 0, slot, rows.data(), n, &n));
-        return rows;
-    }
-
-private:
-    void release() {
-        if (h) dvbs2gpu_ule_destroy(h);
-        h = nullptr;
-    }
-    dvbs2gpu_ule* need() {
-        if (!h) throw std::runtime_error("dvbs2gpu: UleBank used before init()");
-        return h;
-    }
-    std::shared_ptr<Engine> eng;
-    dvbs2gpu_ule* h = nullptr;
-    int status_ = 0;
-    std::string error_;
 };
 }   // namespace dvbs2gpu_host
 #endif

@@ -459,31 +459,23 @@ PROTOTYPES = {
     'dvbs2gpu_t2mi_get_row_table': (_i, [_vp, _i, _i, C.POINTER(T2miRow), _i, C.POINTER(_i)]),
     'dvbs2gpu_t2mi_get_row_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
     'dvbs2gpu_t2mi_get_frame_bytes': (_i, [_vp, _i, _i, C.POINTER(_i), _i, C.POINTER(_i)]),
-    'dvbs2gpu_mpe_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
-    'dvbs2gpu_mpe_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
-    'dvbs2gpu_mpe_reset': (_i, [_vp]),
-    'dvbs2gpu_mpe_destroy': (None, [_vp]),
-    'dvbs2gpu_mpe_get_layout': (_i, [C.POINTER(MpeLayout)]),
-    'dvbs2gpu_mpe_set_watch': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
-    'dvbs2gpu_mpe_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _vp]),
-    'dvbs2gpu_mpe_work': (_i, [_vp, _i, _i, _vp, _i, _vp, _i]),
-    'dvbs2gpu_mpe_get_needed': (_i, [_vp, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
-    'dvbs2gpu_mpe_get_stats': (_i, [_vp, _i, _i, C.POINTER(MpeStats)]),
-    'dvbs2gpu_mpe_get_row_table': (_i, [_vp, _i, _i, C.POINTER(MpeRow), _i, C.POINTER(_i)]),
-    'dvbs2gpu_mpe_get_row_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
-    'dvbs2gpu_ule_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
-    'dvbs2gpu_ule_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
-    'dvbs2gpu_ule_reset': (_i, [_vp]),
-    'dvbs2gpu_ule_destroy': (None, [_vp]),
-    'dvbs2gpu_ule_get_layout': (_i, [C.POINTER(UleLayout)]),
-    'dvbs2gpu_ule_set_watch': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _i]),
-    'dvbs2gpu_ule_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _vp]),
-    'dvbs2gpu_ule_work': (_i, [_vp, _i, _i, _vp, _i, _vp, _i]),
-    'dvbs2gpu_ule_get_needed': (_i, [_vp, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
-    'dvbs2gpu_ule_get_stats': (_i, [_vp, _i, _i, C.POINTER(UleStats)]),
-    'dvbs2gpu_ule_get_row_table': (_i, [_vp, _i, _i, C.POINTER(UleRow), _i, C.POINTER(_i)]),
-    'dvbs2gpu_ule_get_row_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
 }
+# the two datagram banks (csrc/dgram_bank.h): the same functions but for the prefix, the structures and what set_watch takes behind the mask
+for _p, _Lay, _St, _Row, _watch in (('mpe', MpeLayout, MpeStats, MpeRow, []), ('ule', UleLayout, UleStats, UleRow, [_i])):
+    PROTOTYPES.update({'dvbs2gpu_%s_%s' % (_p, _k): _v for _k, _v in {
+        'create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+        'create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
+        'reset': (_i, [_vp]),
+        'destroy': (None, [_vp]),
+        'get_layout': (_i, [C.POINTER(_Lay)]),
+        'set_watch': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)] + _watch),
+        'process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+        'work': (_i, [_vp, _i, _i, _vp, _i, _vp, _i]),
+        'get_needed': (_i, [_vp, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+        'get_stats': (_i, [_vp, _i, _i, C.POINTER(_St)]),
+        'get_row_table': (_i, [_vp, _i, _i, C.POINTER(_Row), _i, C.POINTER(_i)]),
+        'get_row_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
+    }.items()})
 
 _lib = None
 
@@ -1896,11 +1888,97 @@ class T2miBank(_TsBank):
         return [int(v) for v in self._rows(self.lib.dvbs2gpu_t2mi_get_frame_bytes, C.c_int, int(stream), int(slot))]
 
 
-class MpeBank(_TsBank):
+class _DatagramBank(_TsBank):
+    """what the banks share that deliver IP datagrams from the units of a PID (csrc/dgram_bank.h; MpeBank: sections, UleBank: SNDUs): four
+    slots per stream, each a watch and a reassembler of its own, one table row per unit, the datagrams back to back.  A bank names its C
+    prefix (_c) and its row and statistics structures (_Row, _Stats) and adds layout() and set_watch()."""
+    SLOTS = 4
+    _c = _Row = _Stats = None
+
+    def _fn(self, name):
+        return getattr(self.lib, '%s_%s' % (self._c, name))
+
+    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=1024):
+        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
+        h = C.c_void_p()
+        engine._check(self._fn('create')(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096, max_rows=1024):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        return cls._host(cls._c + '_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
+
+    def reset(self):
+        self._check(self._fn('reset')(self.h))
+
+    def process(self, ts_tensors, out_tensors=None, nbytes=None):
+        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors: None for rows and counters
+        only, else out_tensors[i][k]: the uint8 CUDA buffer that receives the datagrams of slot k of stream i (None for an empty slot)
+        -> byte counts [i][k].  Dvbs2GpuError -5 carries .needed and .rows ([i][k] each) when a buffer or max_rows is too small
+        (nothing has advanced then)."""
+        n, S = self.nstreams, self.SLOTS
+        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
+        pout, cap = None, 0
+        if out_tensors is not None:
+            flat = [t for per in out_tensors for t in (list(per) + [None] * S)[:S]]
+            pout = (C.c_void_p * (n * S))(*[None if t is None else t.data_ptr() for t in flat])
+            cap = min([int(t.numel()) for t in flat if t is not None] or [0])
+        nb, nr = (C.c_int * (n * S))(), (C.c_int * (n * S))()
+        rc = self._fn('process_batch')(self.h, pin, cnt, pout, cap, nb, nr, self.eng._stream())
+        split = lambda a: [list(a[i * S:(i + 1) * S]) for i in range(n)]
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            e.needed, e.rows = split(nb), split(nr)
+            raise e
+        return split(nb)
+
+    def work(self, ts, stream=0, slot=0, cap=None, deliver=True):
+        """one stream and slot, host buffers: numpy uint8 packets in -> the delivered datagrams back to back (numpy uint8), or None with
+        deliver=False (rows and counters only)"""
+        import numpy as np
+        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
+        cap = ts.size + 4096 if cap is None else cap
+        out = np.zeros(max(cap, 1), np.uint8) if deliver else None
+        rc = self._fn('work')(self.h, int(stream), int(slot), C.c_void_p(ts.ctypes.data), ts.size,
+                              C.c_void_p(out.ctypes.data) if deliver else None, cap if deliver else 0)
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            nb, nr = C.c_int(), C.c_int()
+            self._fn('get_needed')(self.h, int(stream), int(slot), C.byref(nb), C.byref(nr))
+            e.needed, e.rows = nb.value, nr.value
+            raise e
+        return out[:rc].copy() if deliver else None
+
+    def needed(self, stream=0, slot=0):
+        """(bytes, rows) that the slot's last call needed, whether it succeeded or failed for capacity (bytes -1: the rows did not fit)"""
+        nb, nr = C.c_int(), C.c_int()
+        self._check(self._fn('get_needed')(self.h, int(stream), int(slot), C.byref(nb), C.byref(nr)))
+        return nb.value, nr.value
+
+    def stats(self, stream=0, slot=-1):
+        st = self._Stats()
+        self._check(self._fn('get_stats')(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in self._Stats._fields_}
+
+    def row_table(self, stream=0, slot=0):
+        """one dict per unit (section, SNDU) of the slot's last call (the fields of the bank's row structure; mac: six bytes), in row order"""
+        rows = self._rows(self._fn('get_row_table'), self._Row, int(stream), int(slot))
+        return [{k: bytes(r.mac) if k == 'mac' else int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows]
+
+    def row_table_device(self, stream=0, slot=0):
+        """(device pointer or None, rows): the same table as the bank's row records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self._fn('get_row_table_device')(self.h, int(stream), int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+
+class MpeBank(_DatagramBank):
     """MPE bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, MPE bank): the DSM-CC datagram_sections of a PID are
     reassembled, their CRC-32 checked, a MAC filter applied and the IPv4 / IPv6 header behind the MPE header (and LLC/SNAP) checked, one
     table row per section, and the IP datagrams laid back to back in a device buffer.  Four slots per stream, each a (PID, MAC value,
     MAC mask) and a reassembler of its own: the same PID may sit in several slots."""
+    _c, _Row, _Stats = 'dvbs2gpu_mpe', MpeRow, MpeStats
     _destroy = 'dvbs2gpu_mpe_destroy'
     SLOTS = 4
     OTHER_TABLE, MALFORMED, CRC_ERROR, UNCHECKED, SCRAMBLED, FILTERED, FRAGMENT, OTHER_PROTOCOL, BAD_IP, DATAGRAM = (1 << k for k in range(10))
@@ -1908,16 +1986,13 @@ class MpeBank(_TsBank):
     ROW_KEYS = tuple(k for k, _ in MpeRow._fields_)
 
     def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=1024):
-        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
-        h = C.c_void_p()
-        engine._check(self.lib.dvbs2gpu_mpe_create(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
-        self.h = h
+        super().__init__(engine, nstreams, max_packets, max_rows)
         self._watched = [{} for _ in range(nstreams)]               # per stream: slot -> PID, as set_watch left them
 
     @classmethod
     def host(cls, nstreams=1, max_packets=4096, max_rows=1024):
         """a bank without a device: the library's host implementation of the same rules, behind work()"""
-        self = cls._host('dvbs2gpu_mpe_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
+        self = super().host(nstreams, max_packets, max_rows)
         self._watched = [{} for _ in range(nstreams)]
         return self
 
@@ -1927,9 +2002,6 @@ class MpeBank(_TsBank):
         lay = MpeLayout()
         load_library().dvbs2gpu_mpe_get_layout(C.byref(lay))
         return {k: [int(v) for v in getattr(lay, k)] if k == 'mac_at' else int(getattr(lay, k)) for k, _ in MpeLayout._fields_}
-
-    def reset(self):
-        self._check(self.lib.dvbs2gpu_mpe_reset(self.h))
 
     def set_watch(self, stream, slot, pid, mac=None, mask=None):
         """pid -1 empties the slot; mac / mask: six bytes each in network order (None: all zero; an all-zero mask takes every address);
@@ -1963,89 +2035,19 @@ class MpeBank(_TsBank):
                     left.append(pid)
         return left
 
-    def process(self, ts_tensors, out_tensors=None, nbytes=None):
-        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors: None for rows and counters
-        only, else out_tensors[i][k]: the uint8 CUDA buffer that receives the datagrams of slot k of stream i (None for an empty slot)
-        -> byte counts [i][k].  Dvbs2GpuError -5 carries .needed and .rows ([i][k] each) when a buffer or max_rows is too small
-        (nothing has advanced then)."""
-        n, S = self.nstreams, self.SLOTS
-        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
-        pout, cap = None, 0
-        if out_tensors is not None:
-            flat = [t for per in out_tensors for t in (list(per) + [None] * S)[:S]]
-            pout = (C.c_void_p * (n * S))(*[None if t is None else t.data_ptr() for t in flat])
-            cap = min([int(t.numel()) for t in flat if t is not None] or [0])
-        nb, nr = (C.c_int * (n * S))(), (C.c_int * (n * S))()
-        rc = self.lib.dvbs2gpu_mpe_process_batch(self.h, pin, cnt, pout, cap, nb, nr, self.eng._stream())
-        split = lambda a: [list(a[i * S:(i + 1) * S]) for i in range(n)]
-        if rc < 0:
-            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
-            e.needed, e.rows = split(nb), split(nr)
-            raise e
-        return split(nb)
 
-    def work(self, ts, stream=0, slot=0, cap=None, deliver=True):
-        """one stream and slot, host buffers: numpy uint8 packets in -> the delivered datagrams back to back (numpy uint8), or None with
-        deliver=False (rows and counters only)"""
-        import numpy as np
-        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
-        cap = ts.size + 4096 if cap is None else cap
-        out = np.zeros(max(cap, 1), np.uint8) if deliver else None
-        rc = self.lib.dvbs2gpu_mpe_work(self.h, int(stream), int(slot), C.c_void_p(ts.ctypes.data), ts.size,
-                                        C.c_void_p(out.ctypes.data) if deliver else None, cap if deliver else 0)
-        if rc < 0:
-            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
-            nb, nr = C.c_int(), C.c_int()
-            self.lib.dvbs2gpu_mpe_get_needed(self.h, int(stream), int(slot), C.byref(nb), C.byref(nr))
-            e.needed, e.rows = nb.value, nr.value
-            raise e
-        return out[:rc].copy() if deliver else None
-
-    def needed(self, stream=0, slot=0):
-        """(bytes, rows) that the slot's last call needed, whether it succeeded or failed for capacity (bytes -1: the rows did not fit)"""
-        nb, nr = C.c_int(), C.c_int()
-        self._check(self.lib.dvbs2gpu_mpe_get_needed(self.h, int(stream), int(slot), C.byref(nb), C.byref(nr)))
-        return nb.value, nr.value
-
-    def stats(self, stream=0, slot=-1):
-        st = MpeStats()
-        self._check(self.lib.dvbs2gpu_mpe_get_stats(self.h, int(stream), int(slot), C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in MpeStats._fields_}
-
-    def row_table(self, stream=0, slot=0):
-        """one dict per section of the slot's last call (the fields of dvbs2gpu_mpe_row; mac: six bytes), in row order"""
-        rows = self._rows(self.lib.dvbs2gpu_mpe_get_row_table, MpeRow, int(stream), int(slot))
-        return [{k: bytes(r.mac) if k == 'mac' else int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows]
-
-    def row_table_device(self, stream=0, slot=0):
-        """(device pointer or None, rows): the same table as dvbs2gpu_mpe_row records in HBM, valid until the next call"""
-        p, n = C.c_void_p(), C.c_int()
-        self._check(self.lib.dvbs2gpu_mpe_get_row_table_device(self.h, int(stream), int(slot), C.byref(p), C.byref(n)))
-        return p.value, n.value
-
-
-class UleBank(_TsBank):
+class UleBank(_DatagramBank):
     """ULE bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, ULE bank): the SNDUs of a PID (Unidirectional
     Lightweight Encapsulation, RFC 4326) are reassembled, their CRC-32 checked, a filter on the destination NPA address applied,
     optional extension headers and a bridged frame's MAC header followed and the IPv4 / IPv6 header behind them checked, one table row
     per SNDU, and the IP datagrams laid back to back in a device buffer.  Four slots per stream, each a (PID, NPA value, NPA mask,
     accept_unaddressed) and a reassembler of its own: the same PID may sit in several slots.  There is no follow_pmts: ULE has no
     dependable PMT signalling, the caller names the PID."""
+    _c, _Row, _Stats = 'dvbs2gpu_ule', UleRow, UleStats
     _destroy = 'dvbs2gpu_ule_destroy'
     SLOTS = 4
     MALFORMED, CRC_ERROR, FILTERED, NO_ADDRESS, TEST, BRIDGED, EXTENSION, OTHER_PROTOCOL, BAD_IP, DATAGRAM = (1 << k for k in range(10))
     ROW_KEYS = tuple(k for k, _ in UleRow._fields_)
-
-    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=1024):
-        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
-        h = C.c_void_p()
-        engine._check(self.lib.dvbs2gpu_ule_create(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
-        self.h = h
-
-    @classmethod
-    def host(cls, nstreams=1, max_packets=4096, max_rows=1024):
-        """a bank without a device: the library's host implementation of the same rules, behind work()"""
-        return cls._host('dvbs2gpu_ule_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
 
     @staticmethod
     def layout():
@@ -2054,9 +2056,6 @@ class UleBank(_TsBank):
         load_library().dvbs2gpu_ule_get_layout(C.byref(lay))
         return {k: int(getattr(lay, k)) for k, _ in UleLayout._fields_}
 
-    def reset(self):
-        self._check(self.lib.dvbs2gpu_ule_reset(self.h))
-
     def set_watch(self, stream, slot, pid, npa=None, mask=None, accept_unaddressed=False):
         """pid -1 empties the slot; npa / mask: six bytes each (None: all zero; an all-zero mask takes every address);
         accept_unaddressed: SNDUs without a destination address (D = 1) pass the filter; the slot starts afresh"""
@@ -2064,66 +2063,6 @@ class UleBank(_TsBank):
         if any(v is not None and len(bytes(v)) != 6 for v in (npa, mask)):
             raise ValueError('an NPA address or mask has six bytes')
         self._check(self.lib.dvbs2gpu_ule_set_watch(self.h, int(stream), int(slot), int(pid), six(npa), six(mask), int(bool(accept_unaddressed))))
-
-    def process(self, ts_tensors, out_tensors=None, nbytes=None):
-        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors: None for rows and counters
-        only, else out_tensors[i][k]: the uint8 CUDA buffer that receives the datagrams of slot k of stream i (None for an empty slot)
-        -> byte counts [i][k].  Dvbs2GpuError -5 carries .needed and .rows ([i][k] each) when a buffer or max_rows is too small
-        (nothing has advanced then)."""
-        n, S = self.nstreams, self.SLOTS
-        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
-        pout, cap = None, 0
-        if out_tensors is not None:
-            flat = [t for per in out_tensors for t in (list(per) + [None] * S)[:S]]
-            pout = (C.c_void_p * (n * S))(*[None if t is None else t.data_ptr() for t in flat])
-            cap = min([int(t.numel()) for t in flat if t is not None] or [0])
-        nb, nr = (C.c_int * (n * S))(), (C.c_int * (n * S))()
-        rc = self.lib.dvbs2gpu_ule_process_batch(self.h, pin, cnt, pout, cap, nb, nr, self.eng._stream())
-        split = lambda a: [list(a[i * S:(i + 1) * S]) for i in range(n)]
-        if rc < 0:
-            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
-            e.needed, e.rows = split(nb), split(nr)
-            raise e
-        return split(nb)
-
-    def work(self, ts, stream=0, slot=0, cap=None, deliver=True):
-        """one stream and slot, host buffers: numpy uint8 packets in -> the delivered datagrams back to back (numpy uint8), or None with
-        deliver=False (rows and counters only)"""
-        import numpy as np
-        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
-        cap = ts.size + 4096 if cap is None else cap
-        out = np.zeros(max(cap, 1), np.uint8) if deliver else None
-        rc = self.lib.dvbs2gpu_ule_work(self.h, int(stream), int(slot), C.c_void_p(ts.ctypes.data), ts.size,
-                                        C.c_void_p(out.ctypes.data) if deliver else None, cap if deliver else 0)
-        if rc < 0:
-            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
-            nb, nr = C.c_int(), C.c_int()
-            self.lib.dvbs2gpu_ule_get_needed(self.h, int(stream), int(slot), C.byref(nb), C.byref(nr))
-            e.needed, e.rows = nb.value, nr.value
-            raise e
-        return out[:rc].copy() if deliver else None
-
-    def needed(self, stream=0, slot=0):
-        """(bytes, rows) that the slot's last call needed, whether it succeeded or failed for capacity (bytes -1: the rows did not fit)"""
-        nb, nr = C.c_int(), C.c_int()
-        self._check(self.lib.dvbs2gpu_ule_get_needed(self.h, int(stream), int(slot), C.byref(nb), C.byref(nr)))
-        return nb.value, nr.value
-
-    def stats(self, stream=0, slot=-1):
-        st = UleStats()
-        self._check(self.lib.dvbs2gpu_ule_get_stats(self.h, int(stream), int(slot), C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in UleStats._fields_}
-
-    def row_table(self, stream=0, slot=0):
-        """one dict per SNDU of the slot's last call (the fields of dvbs2gpu_ule_row; mac: six bytes), in row order"""
-        rows = self._rows(self.lib.dvbs2gpu_ule_get_row_table, UleRow, int(stream), int(slot))
-        return [{k: bytes(r.mac) if k == 'mac' else int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows]
-
-    def row_table_device(self, stream=0, slot=0):
-        """(device pointer or None, rows): the same table as dvbs2gpu_ule_row records in HBM, valid until the next call"""
-        p, n = C.c_void_p(), C.c_int()
-        self._check(self.lib.dvbs2gpu_ule_get_row_table_device(self.h, int(stream), int(slot), C.byref(p), C.byref(n)))
-        return p.value, n.value
 
 
 class SegmentReceiver(_Handle):

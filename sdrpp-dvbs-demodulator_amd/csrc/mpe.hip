@@ -1,328 +1,35 @@
 // MPE bank (own extension; include/dvbs2gpu.h): the DSM-CC datagram_sections (Multi-Protocol Encapsulation, EN 301 192)
 // of a PID of each of `nstreams` transport streams in HBM, reassembled, checked (CRC-32, MAC filter, LLC/SNAP, IP header) and their IP
 // datagrams laid back to back per slot.  Every rule is in mpe_rules.h, whose MpeHostStream is the sequential definition, the host bank
-// and the kernels' yardstick.  How a call's packets are cut into independent pieces is ts_reasm.h with the one-slot format MpeFmt below
-// (the section bank's header and length rule, the T2-MI bank's arrangement); what a wave does with one unit in phase D -- the head
-// gather, the source the row rules read it through, the CRC over shares of the pieces -- is reasm_wave.h, shared with ule.hip; this
-// file holds what is the bank's own.
-//
-//   mpe_scan_kernel     one workgroup per (stream, slot); an empty slot returns at once.
-//     A-C  ts_reasm.h: the slot's packets into LDS, one lane for the continuity walk, one lane per PUSI packet and one for the section
-//        carried in, one record per row.
-//     D  one wave per row.  The wave gathers the section's first 128 bytes, two per lane, from the TS payloads where they lie (up to 84
-//        decide a row: MPE header, LLC/SNAP, an IPv4 header with options, the ports; behind adaptation fields they may lie a byte per
-//        TS packet), and every lane evaluates mpe_row_fields on them, a byte read being a shuffle, the MAC compare a ballot and the
-//        header checksum a wave sum; lane 0 writes the row.  Where the rules take the CRC-32 each lane takes that of its share of one
-//        PIECE from a zero register, shifted to the section's end and summed, as in t2mi_scan_kernel, but with 2 to 16 lanes to a piece:
-//        a section has 24 pieces at most where a T2-MI packet has 46, and a lane per piece left most of the wave waiting (DESIGN).
-//     E  the rows do not depend on each other: one prefix sum over the delivered rows' bytes gives their offsets.
-//   mpe_commit_kernel   (once the host has seen that every slot's bytes and rows fit) one workgroup per (stream, slot): a wave per
-//     delivered row copies the datagram -- the section's bytes from 12 or 20 on, without the stuffing -- piece by piece to its offset;
-//     then the open section goes to the slot's 4096-byte buffer and the state is stored.
-// Two launches per call and one device-to-host copy, of the call record per (stream, slot).
-#include "reasm_wave.h"
+// and the kernels' yardstick.  The kernels, the handle and the call are the datagram bank's (dgram_bank.h, shared with ule.hip), here
+// instantiated with MpeRules: a 3-byte header with section_length in bytes 1 and 2, and in phase D up to 84 bytes decide a row (MPE
+// header, LLC/SNAP, an IPv4 header with options, the ports) and the CRC-32 is taken only where mpe_takes_crc says so; the datagram is
+// the section's bytes from 12 or 20 on.  This file holds what is the bank's own: the layout checks, the description and the watch.
+#include "dgram_bank.h"
 #include "mpe_rules.h"
 
-#include <memory>
-
 using namespace s2;
-#define g_err last_error()
 
-namespace s2 {
-
-constexpr int MPE_MAX_PACKETS = 4096;            // per stream and call: 10 bytes of LDS per packet
-constexpr int MPE_WG = 256, MPE_WAVES = MPE_WG / 64, MPE_HEAD = REASM_HEAD;
 static_assert(sizeof(MpeRow) == sizeof(dvbs2gpu_mpe_row) && sizeof(MpeRow) == 48, "row layout");
 static_assert(sizeof(MpeLayout) == sizeof(dvbs2gpu_mpe_layout), "layout layout");
-static_assert(MPE_MAX_PACKETS <= 32 * MPE_WG, "reasm_collect keeps a thread's match flags in one 32-bit mask (ts_thread_run)");
 static_assert(sizeof(MpeCnt) == MPE_NCNT * sizeof(int32_t), "counter order");
 static_assert(sizeof(dvbs2gpu_mpe_stats) == MPE_NCNT * sizeof(int64_t), "stats order");
 static_assert(sizeof(MpeWatch) == 16, "watch layout");
 static_assert(MPE.max_section_bytes <= MPE_BUF && MPE.max_section_bytes < (1 << 17), "crc32m_xpow takes 17 bits of length");
-static_assert(MPE.head_bytes <= MPE_HEAD && MPE.head_bytes == MPE.mpe_header_bytes + MPE.llc_snap_bytes + 60 + 4, "the head gather holds what a row reads");
+static_assert(MPE.head_bytes <= REASM_HEAD && MPE.head_bytes == MPE.mpe_header_bytes + MPE.llc_snap_bytes + 60 + 4, "the head gather holds what a row reads");
 
-struct MpeDevSlot { int32_t fill; uint8_t cont, pad[3]; };
-// the section format of ts_reasm.h with one slot per workgroup: a 3-byte header with section_length in bytes 1 and 2, a length beyond
-// 4093 is bad, 0xFF in a section's first place is stuffing, every finished section a row
-struct MpeFmt {
-    typedef MpeDevSlot State;
-    static constexpr int WG = MPE_WG, SLOTS = 1, BUF = MPE_BUF, HEADER = MPE.header_bytes, LEN_A = 1, LEN_B = 2, STUFFING = 0xFF;
-    static constexpr int NCNT = MPE_NCNT, C_DROPPED = MPC_DROPPED, C_BAD_UNIT = MPC_MALSEC, C_SLACK = -1;
-    __device__ static int total(unsigned b1, unsigned b2) { return mpe_total(b1, b2); }
-    __device__ static bool is_row(unsigned, int) { return true; }
+struct MpeBankDesc : MpeRules {
+    typedef dvbs2gpu_mpe_stats Stats;
+    static constexpr const char *BANK = "MPE bank: ", *CNAME = "dvbs2gpu_mpe", *ALLOC = "hipMalloc(mpe)";
 };
-typedef ReasmRec MpeRec;
-typedef ReasmView<MpeFmt> MpeView;
-struct MpeCall { int32_t needed, nrows, watched, ndelivered; MpeCnt cnt; };
-
-// dynamic LDS: wa[max_packets] (dwords), rc[max_packets] (dwords), wb[max_packets] (16 bits each).  only >= 0: the one (stream, slot)
-// that receives its stream's packets (the single-slot entry point); the others take an empty call
-__global__ void __launch_bounds__(MPE_WG) mpe_scan_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nbytes, int max_packets, int max_rows, int only,
-                                                          const MpeWatch* __restrict__ watch, const MpeDevSlot* __restrict__ state, MpeDevSlot* __restrict__ newst,
-                                                          const uint8_t* __restrict__ bufs, unsigned* __restrict__ wa_g, uint16_t* __restrict__ wb_g,
-                                                          MpeRec* __restrict__ recs, MpeRec* __restrict__ opens, MpeRow* __restrict__ rows_g, MpeCall* __restrict__ call,
-                                                          int have_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned mpe_lds[];
-    __shared__ int cnt[MPE_NCNT], wsum[MPE_WAVES];
-    __shared__ MpeDevSlot nss;
-    const int g = blockIdx.x, s = g / MPE_SLOTS, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const MpeWatch& w = watch[g];
-    const int pid = w.pid;
-    if (pid < 0) {                                   // an empty slot: nothing carried, nothing to do
-        if (tid == 0) {
-            MpeCall c = {};
-            call[g] = c;
-            const MpeRec none = {-2, 0, 0, 0, 0};
-            opens[g] = none;
-            newst[g] = state[g];
-        }
-        return;
-    }
-    unsigned* wa = mpe_lds;
-    int* rc = reinterpret_cast<int*>(mpe_lds + max_packets);
-    uint16_t* wb = reinterpret_cast<uint16_t*>(mpe_lds + 2 * (size_t)max_packets);
-    int n = (only >= 0 && only != g) ? 0 : nbytes[s] / TSMON_TS;
-    if (n > max_packets) n = max_packets;            // (the host has refused such a call)
-    const MpeDevSlot ss = state[g];
-    if (tid == 0) {
-        nss = ss;
-        const MpeRec none = {-2, 0, 0, 0, 0};
-        opens[g] = none;
-    }
-    if (tid < MPE_NCNT) cnt[tid] = 0;
-    __syncthreads();
-    const uint8_t* ts = in[s];
-    const int W = n > 0 ? reasm_collect<MPE_WG>(ts, n, [&](const TsmonHdr& h) { return h.cls == TSMON_DATA && h.pid == pid ? 0 : -1; }, wa, wb, wsum) : 0;
-    // B: the continuity walk, one lane
-    if (tid == 0) {
-        uint8_t st = ss.cont;
-        const ReasmWalk c = reasm_classify<MpeFmt>(wa, wb, W, 0, &st);
-        nss.cont = st;
-        nss.fill = 0;
-        cnt[MPC_PACKETS] = c.packets; cnt[MPC_SCR] = c.scrambled; cnt[MPC_MALPKT] = c.malformed;
-    }
-    for (int j = tid; j < W; j += MPE_WG) rc[j] = 0;
-    __syncthreads();
-    // C: sections
-    const MpeView v = {ts, wa, wb, W, bufs + (size_t)g * MPE_BUF, state + g};
-    MpeRec* rec = recs + (size_t)g * max_rows;
-    const ReasmOut<MpeFmt> o = {rc, rec, opens + g, &nss, &cnt, max_rows};
-    reasm_jobs<false>(v, o);
-    __syncthreads();
-    const int nrows = reasm_number_rows<MPE_WG>(rc, W, wsum);
-    const bool fits = nrows <= max_rows;
-    MpeRow* rows = rows_g + (size_t)g * max_rows;
-    int needed = fits ? 0 : -1, ndelivered = 0;
-    if (fits) {
-        reasm_jobs<true>(v, o);
-        __syncthreads();
-        // D: a wave per row
-        for (int r = wave; r < nrows; r += MPE_WAVES) {
-            const MpeRec q = rec[r];
-            const int total = q.total;
-            // the head (lane l keeps bytes 2 l and 2 l + 1 of the section) and, where the rules take it, the CRC: reasm_wave.h
-            const ReasmWaveSrc hd = reasm_wave_head(q, v, lane);
-            uint32_t x = 0;
-            if (mpe_takes_crc(hd.rd(0), hd.rd(1), total)) x = reasm_wave_crc(q, v, total, lane);      // (the same in every lane; a section has three bytes at least)
-            const MpeRow row = mpe_row_fields(hd, total, x == 0, w, q.j0 < 0 ? -1 : wa_k(wa[q.j0]), wa_k(wa[q.j1]));
-            if (lane == 0) {
-                rows[r] = row;
-                mpe_account(row.flags, [&](int c) { atomicAdd(&cnt[c], 1); });
-            }
-        }
-        __syncthreads();
-        // E: the offsets of the delivered rows
-        {
-            int r0, r1; ts_thread_run(nrows, MPE_WG, &r0, &r1);
-            auto bytes_of = [&](int r) { return have_out && (rows[r].flags & MPE_DATAGRAM) ? rows[r].bytes : 0; };
-            int mine = 0, mine_n = 0;
-            for (int r = r0; r < r1; ++r) { const int b = bytes_of(r); mine += b; mine_n += b > 0; }
-            int at = ts_block_scan<MPE_WG>(mine, wsum, &needed);
-            ts_block_scan<MPE_WG>(mine_n, wsum, &ndelivered);
-            for (int r = r0; r < r1; ++r) {
-                const int b = bytes_of(r);
-                if (b) rows[r].offset = at;
-                at += b;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) { cnt[MPC_DELIVERED] = ndelivered; cnt[MPC_BYTES] = needed; }
-    }
-    for (int j = tid; j < W; j += MPE_WG) { wa_g[(size_t)g * max_packets + j] = wa[j]; wb_g[(size_t)g * max_packets + j] = wb[j]; }
-    __syncthreads();
-    if (tid == 0) {
-        newst[g] = nss;
-        MpeCall c;
-        c.needed = needed; c.nrows = nrows; c.watched = W; c.ndelivered = ndelivered;
-        int32_t* dst = reinterpret_cast<int32_t*>(&c.cnt);
-        for (int k = 0; k < MPE_NCNT; ++k) dst[k] = cnt[k];
-        call[g] = c;
-    }
-}
-
-__global__ void __launch_bounds__(MPE_WG) mpe_commit_kernel(const uint8_t* const* __restrict__ in, uint8_t* const* __restrict__ out, int max_packets, int max_rows, int cap,
-                                                            MpeDevSlot* __restrict__ state, const MpeDevSlot* __restrict__ newst, uint8_t* __restrict__ bufs,
-                                                            const unsigned* __restrict__ wa_g, const uint16_t* __restrict__ wb_g, const MpeRec* __restrict__ recs,
-                                                            const MpeRec* __restrict__ opens, const MpeRow* __restrict__ rows_g, const MpeCall* __restrict__ call) {
-    const int g = blockIdx.x, s = g / MPE_SLOTS, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int W = call[g].watched, nrows = call[g].nrows;
-    if (W > max_packets) W = max_packets;
-    if (nrows > max_rows) nrows = max_rows;
-    const MpeRec q = opens[g];
-    if (nrows == 0 && q.j0 == -2 && W == 0) return;  // (an empty slot, or an empty call with nothing open: the state is what it was)
-    uint8_t* sbuf = bufs + (size_t)g * MPE_BUF;
-    const MpeView v = {in[s], wa_g + (size_t)g * max_packets, wb_g + (size_t)g * max_packets, W, sbuf, state + g};
-    const MpeRec* rec = recs + (size_t)g * max_rows;
-    const MpeRow* rows = rows_g + (size_t)g * max_rows;
-    uint8_t* o = out ? out[g] : nullptr;
-    for (int r = wave; o && r < nrows; r += MPE_WAVES) {
-        const int off = rows[r].offset, nb = rows[r].bytes;
-        if (off < 0 || nb <= 0 || off + nb > cap) continue;
-        const int skip = mpe_ip_at(rows[r]);         // the datagram is the section's bytes [skip, skip + nb)
-        reasm_pieces(rec[r], v, skip + nb, [&](int pos, const uint8_t* src, int len) {
-            const int a = pos > skip ? pos : skip, b = pos + len;
-            if (b > a) ts_wave_copy(o + off + (a - skip), TsBytes{src + (a - pos)}, b - a, lane);
-        });
-    }
-    __syncthreads();                                 // the carried rows have read the buffer
-    if (wave == 0 && q.j0 > -2)                      // the open section: what the buffer holds already (a section carried in and on) stays where it is
-        reasm_pieces(q, v, MPE_BUF, [&](int pos, const uint8_t* src, int len) {
-            if (src != sbuf) for (int i = lane; i < len; i += 64) sbuf[pos + i] = src[i];
-        });
-    if (tid == 0) state[g] = newst[g];
-}
-
-}  // namespace s2
-
-struct dvbs2gpu_mpe {
-    dvbs2gpu_ctx* ctx = nullptr;                   // null: a host-only bank (dvbs2gpu_mpe_create_host)
-    int nstreams = 0, max_packets = 0, max_rows = 0;
-    std::vector<MpeWatch> watch;                   // nstreams x 4
-    std::vector<dvbs2gpu_mpe_stats> stats;         // nstreams x 4, since reset; the kernels report each call's share (MpeCall)
-    std::vector<int> nrows, need_bytes, need_rows; // of the last call per (stream, slot)
-    std::vector<MpeCall> h_call;
-    std::vector<char> h_args;
-    // device banks
-    DevBuf<MpeWatch> d_watch;
-    DevBuf<MpeDevSlot> d_state, d_newst;
-    DevBuf<uint8_t> d_bufs;                        // nstreams x 4 x 4096
-    DevBuf<unsigned> d_wa;                         // nstreams x 4 x max_packets: the slots' packets of the last call
-    DevBuf<uint16_t> d_wb;
-    DevBuf<MpeRec> d_recs, d_opens;
-    DevBuf<MpeRow> d_rows;                         // nstreams x 4 x max_rows
-    DevBuf<MpeCall> d_call;
-    DevBuf<uint8_t> d_args;                        // TsBankArgsN<4>(nstreams)
-    TsHostStage stage;                             // of the host-buffer entry point
-    // host-only banks
-    std::vector<MpeHostStream> host;               // nstreams x 4
-};
-
-namespace s2 {
-constexpr MpeWatch MPE_NO_WATCH = {-1, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
-static void mpe_account_call(dvbs2gpu_mpe* b, int g, const MpeCnt& c) {
-    int64_t* d = reinterpret_cast<int64_t*>(&b->stats[g]);
-    const int32_t* a = reinterpret_cast<const int32_t*>(&c);
-    for (int k = 0; k < MPE_NCNT; ++k) d[k] += a[k];
-}
-static bool mpe_create_args_ok(int nstreams, int max_packets, int max_rows, dvbs2gpu_mpe** out) {
-    if (!out || nstreams <= 0 || max_packets <= 0 || max_rows <= 0) return false;
-    if (max_packets > MPE_MAX_PACKETS) { g_err = "MPE bank: max_packets is at most 4096 per stream and call"; return false; }
-    return true;
-}
-static std::unique_ptr<dvbs2gpu_mpe> mpe_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows) {
-    std::unique_ptr<dvbs2gpu_mpe> b(new dvbs2gpu_mpe());
-    const size_t ns = (size_t)nstreams * MPE_SLOTS;
-    b->ctx = ctx; b->nstreams = nstreams; b->max_packets = max_packets; b->max_rows = max_rows;
-    b->watch.assign(ns, MPE_NO_WATCH);
-    b->stats.assign(ns, dvbs2gpu_mpe_stats{});
-    b->nrows.assign(ns, 0); b->need_bytes.assign(ns, 0); b->need_rows.assign(ns, 0);
-    b->h_call.resize(ns);
-    return b;
-}
-static bool mpe_slot_ok(const dvbs2gpu_mpe* b, int stream, int slot) { return b && stream >= 0 && stream < b->nstreams && slot >= 0 && slot < MPE_SLOTS; }
-
-// the device call: d_out 4 pointers per stream or null; only: the one (stream, slot) index that is served, -1: all
-static int mpe_batch(dvbs2gpu_mpe* b, const uint8_t* const* d_ts, const int* nbytes, uint8_t* const* d_out, int cap, int* out_bytes, int* out_rows, int only,
-                     hipStream_t st) {
-    const int n = b->nstreams, ns = n * MPE_SLOTS;
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    const TsBankArgsN<MPE_SLOTS> a(n);
-    a.fill(b->h_args.data(), n, d_ts, d_out, nbytes);
-    HIP_TRY(hipMemcpyAsync(b->d_args, b->h_args.data(), b->h_args.size(), hipMemcpyHostToDevice, st));
-    const size_t lds = (size_t)b->max_packets * 10 + 16;               // <= 40 KiB
-    hipLaunchKernelGGL(mpe_scan_kernel, dim3(ns), dim3(MPE_WG), lds, st, a.in(b->d_args), a.nbytes(b->d_args), b->max_packets, b->max_rows, only, b->d_watch, b->d_state,
-                       b->d_newst, b->d_bufs, b->d_wa, b->d_wb, b->d_recs, b->d_opens, b->d_rows, b->d_call, d_out ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_call.data(), b->d_call, sizeof(MpeCall) * ns, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    bool fits = true;
-    for (int g = 0; g < ns; ++g) {
-        const MpeCall& c = b->h_call[g];
-        fits &= c.nrows <= b->max_rows && (!d_out || c.needed <= cap);
-        b->need_bytes[g] = c.needed; b->need_rows[g] = c.nrows;
-        if (out_bytes) out_bytes[g] = c.needed;
-        if (out_rows) out_rows[g] = c.nrows;
-    }
-    if (!fits) {                                       // nothing has been stored: the same call may come again with more room
-        std::fill(b->nrows.begin(), b->nrows.end(), 0);
-        g_err = "MPE bank: the datagrams of a slot do not fit cap, or its rows max_rows (out_bytes / out_rows hold the sizes)";
-        return DVBS2GPU_ERR_CAPACITY;
-    }
-    hipLaunchKernelGGL(mpe_commit_kernel, dim3(ns), dim3(MPE_WG), 0, st, a.in(b->d_args), d_out ? a.out(b->d_args) : nullptr, b->max_packets, b->max_rows, cap, b->d_state,
-                       b->d_newst, b->d_bufs, b->d_wa, b->d_wb, b->d_recs, b->d_opens, b->d_rows, b->d_call);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int g = 0; g < ns; ++g) { mpe_account_call(b, g, b->h_call[g].cnt); b->nrows[g] = b->h_call[g].nrows; }
-    return 0;
-}
-}  // namespace s2
+struct dvbs2gpu_mpe : DgramBank<MpeBankDesc> {};
 
 extern "C" {
 
 void dvbs2gpu_mpe_destroy(dvbs2gpu_mpe* b) { delete b; }
-
-int dvbs2gpu_mpe_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_mpe** out) {
-    if (!ctx || !mpe_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    auto b = mpe_new(ctx, nstreams, max_packets, max_rows);
-    const size_t n = (size_t)nstreams, ns = n * MPE_SLOTS;
-    const char* what = "hipMalloc(mpe)";               // (zero-filled: the slots' states; the kernels write the rest before it is read)
-    RC_TRY(b->d_watch.alloc(ns, false, what));
-    HIP_TRY(hipMemcpy(b->d_watch, b->watch.data(), ns * sizeof(MpeWatch), hipMemcpyHostToDevice));
-    RC_TRY(b->d_state.alloc(ns, true, what));
-    RC_TRY(b->d_newst.alloc(ns, false, what));
-    RC_TRY(b->d_bufs.alloc(ns * MPE_BUF, false, what));
-    RC_TRY(b->d_wa.alloc(ns * max_packets, false, what));
-    RC_TRY(b->d_wb.alloc(ns * max_packets, false, what));
-    RC_TRY(b->d_recs.alloc(ns * max_rows, false, what));
-    RC_TRY(b->d_opens.alloc(ns, false, what));
-    RC_TRY(b->d_rows.alloc(ns * max_rows, false, what));
-    RC_TRY(b->d_call.alloc(ns, false, what));
-    RC_TRY(b->d_args.alloc(TsBankArgsN<MPE_SLOTS>(n).L.bytes(), false, what));
-    b->h_args.resize(TsBankArgsN<MPE_SLOTS>(n).L.bytes());
-    *out = b.release();
-    return 0;
-}
-
-int dvbs2gpu_mpe_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_mpe** out) {
-    if (!mpe_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
-    auto b = mpe_new(nullptr, nstreams, max_packets, max_rows);
-    b->host.resize((size_t)nstreams * MPE_SLOTS);
-    *out = b.release();
-    return 0;
-}
-
-int dvbs2gpu_mpe_reset(dvbs2gpu_mpe* b) {
-    if (!b) return DVBS2GPU_ERR_ARG;
-    if (b->ctx) {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        HIP_TRY(hipMemset(b->d_state, 0, (size_t)b->nstreams * MPE_SLOTS * sizeof(MpeDevSlot)));
-    }
-    for (auto& h : b->host) h.clear();
-    std::fill(b->stats.begin(), b->stats.end(), dvbs2gpu_mpe_stats{});
-    std::fill(b->nrows.begin(), b->nrows.end(), 0);
-    return 0;
-}
+int dvbs2gpu_mpe_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_mpe** out) { return dgram_create(true, ctx, nstreams, max_packets, max_rows, out); }
+int dvbs2gpu_mpe_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_mpe** out) { return dgram_create(false, nullptr, nstreams, max_packets, max_rows, out); }
+int dvbs2gpu_mpe_reset(dvbs2gpu_mpe* b) { return dgram_reset(b); }
 
 int dvbs2gpu_mpe_get_layout(dvbs2gpu_mpe_layout* h_out) {
     if (!h_out) return DVBS2GPU_ERR_ARG;
@@ -331,103 +38,29 @@ int dvbs2gpu_mpe_get_layout(dvbs2gpu_mpe_layout* h_out) {
 }
 
 int dvbs2gpu_mpe_set_watch(dvbs2gpu_mpe* b, int stream, int slot, int pid, const uint8_t mac_value[6], const uint8_t mac_mask[6]) {
-    if (!mpe_slot_ok(b, stream, slot)) return DVBS2GPU_ERR_ARG;
-    if (pid < -1 || pid >= TSMON_NULL_PID) {
-        g_err = "MPE bank: a slot's PID is 0..0x1FFE (-1 empties the slot)";
-        return DVBS2GPU_ERR_ARG;
-    }
-    const size_t at = (size_t)stream * MPE_SLOTS + slot;
-    MpeWatch w = MPE_NO_WATCH;
+    size_t at;
+    if (!dgram_watch_args_ok(b, stream, slot, pid, &at)) return DVBS2GPU_ERR_ARG;
+    MpeWatch w = MpeRules::NO_WATCH;
     w.pid = pid;
     if (pid >= 0 && mac_value) memcpy(w.mac_value, mac_value, 6);
     if (pid >= 0 && mac_mask) memcpy(w.mac_mask, mac_mask, 6);
-    b->watch[at] = w;
-    b->stats[at] = dvbs2gpu_mpe_stats{};
-    b->nrows[at] = 0;
-    if (b->ctx) {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        HIP_TRY(hipMemcpy(b->d_watch + at, &b->watch[at], sizeof(MpeWatch), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(b->d_state + at, 0, sizeof(MpeDevSlot)));
-    } else {
-        b->host[at].clear();
-        b->host[at].watch = b->watch[at];
-    }
-    return 0;
+    return b->set_watch(at, w);
 }
 
 int dvbs2gpu_mpe_process_batch(dvbs2gpu_mpe* b, const uint8_t* const* d_ts, const int* nbytes, uint8_t* const* d_out, int cap, int* out_bytes, int* out_rows,
                                void* stream) {
-    if (!b || !d_ts || !nbytes || cap < 0 || (d_out && !out_bytes)) return DVBS2GPU_ERR_ARG;
-    if (!b->ctx) { g_err = "MPE bank: a host bank takes host buffers (dvbs2gpu_mpe_work)"; return DVBS2GPU_ERR_ARG; }
-    for (int i = 0; i < b->nstreams; ++i) {
-        if (!ts_bank_check_counts("MPE bank: ", nbytes + i, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
-        bool bad = nbytes[i] > 0 && !d_ts[i];
-        // once d_out is given every watching slot needs its output pointer, one of an empty stream too
-        for (int k = 0; d_out && k < MPE_SLOTS; ++k) {
-            uint8_t* o = d_out[i * MPE_SLOTS + k];
-            bad |= (b->watch[(size_t)i * MPE_SLOTS + k].pid >= 0 && !o) || (o && o == d_ts[i]);
-        }
-        if (bad) { g_err = "MPE bank: null buffer, or an output buffer that is its stream's input"; return DVBS2GPU_ERR_ARG; }
-    }
-    return mpe_batch(b, d_ts, nbytes, d_out, cap, out_bytes, out_rows, -1, (hipStream_t)stream);
+    return dgram_process_batch(b, d_ts, nbytes, d_out, cap, out_bytes, out_rows, stream);
 }
-
 int dvbs2gpu_mpe_work(dvbs2gpu_mpe* b, int stream, int slot, const uint8_t* h_ts, int nbytes, uint8_t* h_out, int cap) {
-    if (!mpe_slot_ok(b, stream, slot) || nbytes < 0 || cap < 0 || (nbytes > 0 && !h_ts)) return DVBS2GPU_ERR_ARG;
-    if (!ts_bank_check_counts("MPE bank: ", &nbytes, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
-    if (h_out && h_out == h_ts) { g_err = "MPE bank: the output buffer is the input"; return DVBS2GPU_ERR_ARG; }
-    const int g = stream * MPE_SLOTS + slot;
-    if (!b->ctx) {
-        MpeHostStream& h = b->host[g];
-        // The tables are of the LAST call, which brought the others nothing.  An empty call changes no state (run() with no packet
-        // is the identity), so the other slots are not run: their tables are emptied by count alone.
-        std::fill(b->nrows.begin(), b->nrows.end(), 0);
-        const std::unique_ptr<MpeState> before(new MpeState(h.st));    // what a capacity failure has to put back
-        h.run(h_ts, nbytes / TSMON_TS, h_out != nullptr);
-        const bool rows_fit = (int)h.rows.size() <= b->max_rows;
-        b->need_rows[g] = (int)h.rows.size();
-        b->need_bytes[g] = rows_fit ? (int)h.bytes.size() : -1;
-        if (!rows_fit || (h_out && (int)h.bytes.size() > cap)) {
-            h.st = *before;
-            h.rows.clear(); h.bytes.clear();
-            g_err = "MPE bank: the datagrams do not fit cap, or the rows max_rows (dvbs2gpu_mpe_get_needed holds the sizes)";
-            return DVBS2GPU_ERR_CAPACITY;
-        }
-        mpe_account_call(b, g, h.cnt);
-        b->nrows[g] = (int)h.rows.size();
-        if (h_out && !h.bytes.empty()) memcpy(h_out, h.bytes.data(), h.bytes.size());
-        return (int)h.bytes.size();
-    }
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    return ts_bank_work<MPE_SLOTS>(b->stage, b->nstreams, stream, h_ts, nbytes, b->max_packets, h_out, cap, false, [&](const uint8_t* const* in, const int* nb, uint8_t* const* out, int* ob) {
-        return mpe_batch(b, in, nb, out, cap, ob, nullptr, g, nullptr);
-    }, slot);
+    return dgram_work(b, stream, slot, h_ts, nbytes, h_out, cap);
 }
-
-/* the byte and row sizes the slot's last call needed, whether it succeeded or failed for capacity (bytes -1: the rows did not fit) */
-int dvbs2gpu_mpe_get_needed(dvbs2gpu_mpe* b, int stream, int slot, int* bytes, int* rows) {
-    if (!mpe_slot_ok(b, stream, slot) || !bytes || !rows) return DVBS2GPU_ERR_ARG;
-    *bytes = b->need_bytes[stream * MPE_SLOTS + slot]; *rows = b->need_rows[stream * MPE_SLOTS + slot];
-    return 0;
-}
-
-int dvbs2gpu_mpe_get_stats(dvbs2gpu_mpe* b, int stream, int slot, dvbs2gpu_mpe_stats* h_out) {
-    if (!b || stream < 0 || stream >= b->nstreams || slot < -1 || slot >= MPE_SLOTS || !h_out) return DVBS2GPU_ERR_ARG;
-    *h_out = dvbs2gpu_mpe_stats{};
-    int64_t* d = reinterpret_cast<int64_t*>(h_out);
-    for (int s = slot < 0 ? 0 : slot; s < (slot < 0 ? MPE_SLOTS : slot + 1); ++s) {
-        const int64_t* a = reinterpret_cast<const int64_t*>(&b->stats[(size_t)stream * MPE_SLOTS + s]);
-        for (int k = 0; k < MPE_NCNT; ++k) d[k] += a[k];
-    }
-    return 0;
-}
-
+int dvbs2gpu_mpe_get_needed(dvbs2gpu_mpe* b, int stream, int slot, int* bytes, int* rows) { return dgram_get_needed(b, stream, slot, bytes, rows); }
+int dvbs2gpu_mpe_get_stats(dvbs2gpu_mpe* b, int stream, int slot, dvbs2gpu_mpe_stats* h_out) { return dgram_get_stats(b, stream, slot, h_out); }
 int dvbs2gpu_mpe_get_row_table(dvbs2gpu_mpe* b, int stream, int slot, dvbs2gpu_mpe_row* h_rows, int cap, int* n) {
-    return ts_bank_rows<MPE_SLOTS>(b, &dvbs2gpu_mpe::max_rows, stream, h_rows, cap, n, slot);
+    return dgram_get_row_table(b, stream, slot, h_rows, cap, n);
 }
-
 int dvbs2gpu_mpe_get_row_table_device(dvbs2gpu_mpe* b, int stream, int slot, const dvbs2gpu_mpe_row** d_rows, int* n) {
-    return ts_bank_rows_device<MPE_SLOTS>(b, &dvbs2gpu_mpe::max_rows, stream, d_rows, n, slot);
+    return dgram_get_row_table_device(b, stream, slot, d_rows, n);
 }
 
 }  // extern "C"

@@ -1,19 +1,16 @@
 // The rules of the MPE bank (own extension; include/dvbs2gpu.h), each stated once and shared by the kernels
-// (mpe.hip), the native host bank (MpeHostStream below, behind dvbs2gpu_mpe_create_host) and a plain C++ test program: the layout of a
+// (mpe.hip), the native host bank (MpeHostStream, behind dvbs2gpu_mpe_create_host) and a plain C++ test program: the layout of a
 // DSM-CC datagram_section and of the IP headers behind it as one struct (MpeLayout), what a TS packet of a slot's PID does to the slot,
 // and what an emitted section's row says.  The IP header rules behind the MPE header are ip_rules.h, shared with the ULE bank.
 //
-// The sequential form -- MpeHostStream::run, which is ts_reasm_run with this format -- IS the definition; every other form must give
+// The sequential form -- MpeHostStream::run, which is DgramHostStream (dgram_rules.h) with these rules -- IS the definition; every other form must give
 // its results for every cutting of a stream into calls.  The syntax is written from memory of ETSI EN 301 192 (section 7), RFC 791,
 // RFC 8200 and RFC 1042: every offset and limit the code relies on is a field of MpeLayout, reported through dvbs2gpu_mpe_get_layout
 // and compared with the tests' model.
-// Standard headers, ip_rules.h and ts_reasm_rules.h only: the host tests compile this file with a plain C++ compiler.
+// Standard headers, ip_rules.h, dgram_rules.h and ts_reasm_rules.h only: the host tests compile this file with a plain C++ compiler.
 #pragma once
+#include "dgram_rules.h"
 #include "ip_rules.h"
-#include "ts_reasm_rules.h"
-
-#include <cstring>
-#include <vector>
 
 namespace s2 {
 
@@ -120,90 +117,25 @@ TS_HD inline void mpe_account(unsigned flags, Add add) {
     for (int k = 0; k < 10; ++k) if (flags >> k & 1) add(of_flag[k]);
 }
 
-// ------------------------------------------------------------------------------------------------- the sequential definition
-struct MpeState {
-    uint8_t cont = 0;                                      // tsmon_step's byte
-    int fill = 0;                                          // bytes buffered; 0: no section is open
-    uint8_t buf[MPE_BUF];
+// ------------------------------------------------------------------------------------------------- what the shared code asks of the bank
+// (dgram_rules.h: the sequential stream; dgram_bank.h: the kernels and the handle)
+struct MpeRules {
+    typedef MpeRow Row; typedef MpeWatch Watch; typedef MpeCnt Cnt;
+    static constexpr MpeWatch NO_WATCH = {-1, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
+    static constexpr int SLOTS = MPE_SLOTS, BUF = MPE_BUF, NCNT = MPE_NCNT, DATAGRAM = MPE_DATAGRAM;
+    // a 3-byte header with section_length in bytes 1 and 2, a length beyond 4093 is bad
+    static constexpr int HEADER = MPE.header_bytes, LEN_A = 1, LEN_B = 2;
+    static constexpr int C_PACKETS = MPC_PACKETS, C_SCR = MPC_SCR, C_MALPKT = MPC_MALPKT, C_DELIVERED = MPC_DELIVERED, C_BYTES = MPC_BYTES;
+    static constexpr int C_DROPPED = MPC_DROPPED, C_BAD_UNIT = MPC_MALSEC, C_SLACK = -1;
+    // the rules above under the names the shared code calls them by: constant function pointers, not forwarding members (a row returned through one
+    // more call level costs the scan kernel registers: profiles/ts_reasm_resources.txt)
+    static constexpr auto total = &mpe_total;
+    static constexpr auto takes_crc = &mpe_takes_crc;
+    static constexpr auto ip_at = &mpe_ip_at;
+    template <typename Src> static constexpr auto row_fields = &mpe_row_fields<Src>;
+    template <typename Add> TS_HD static void account(unsigned flags, Add add) { mpe_account(flags, add); }
 };
-// a section's bytes in memory, the reductions as loops
-struct MpeHostSrc {
-    const uint8_t* b;
-    unsigned rd(int i) const { return b[i]; }
-    template <typename Fn> bool any(int n, Fn f) const { for (int k = 0; k < n; ++k) if (f(k)) return true; return false; }
-    template <typename Fn> unsigned sum(int n, Fn f) const { unsigned v = 0; for (int k = 0; k < n; ++k) v += f(k); return v; }
-};
-
-// one slot of one stream: a complete reassembler
-struct MpeHostStream {
-    MpeWatch watch = {-1, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
-    MpeState st;
-    int first_packet = -1;                                 // of the open section, in this call
-    // of the last call
-    std::vector<MpeRow> rows;
-    std::vector<uint8_t> bytes;
-    MpeCnt cnt = {};
-
-    void clear() { st = MpeState(); rows.clear(); bytes.clear(); }
-
-    void drop() {
-        if (st.fill > 0) ++cnt.dropped_sections;
-        st.fill = 0;
-    }
-    void emit(int k, bool want_bytes) {
-        const uint8_t* b = st.buf;
-        const int total = st.fill;
-        const bool crc_ok = !mpe_takes_crc(b[0], b[1], total) || ts_crc32(b, total) == 0;
-        MpeRow r = mpe_row_fields(MpeHostSrc{b}, total, crc_ok, watch, first_packet, k);
-        mpe_account(r.flags, [&](int c) { ++reinterpret_cast<int32_t*>(&cnt)[c]; });
-        if (want_bytes && (r.flags & MPE_DATAGRAM)) {
-            const uint8_t* d = b + mpe_ip_at(r);
-            r.offset = (int32_t)bytes.size();
-            bytes.insert(bytes.end(), d, d + r.bytes);
-            ++cnt.datagrams_delivered; cnt.bytes_delivered += r.bytes;
-        }
-        rows.push_back(r);
-    }
-    // n bytes for the slot's section (open, or starting with them): stops behind the section's last byte.  true: it was emitted; a bad
-    // length forgets the header and is false too
-    bool feed(const uint8_t* b, int n, int* used, int k, bool want_bytes) {
-        int i = 0;
-        bool done = false;
-        while (i < n) {
-            if (st.fill < MPE.header_bytes) {
-                st.buf[st.fill++] = b[i++];
-                if (st.fill < MPE.header_bytes) continue;
-                if (mpe_total(st.buf[1], st.buf[2]) < 0) { ++cnt.malformed_sections; st.fill = 0; break; }
-            } else {
-                const int total = mpe_total(st.buf[1], st.buf[2]);
-                const int take = n - i < total - st.fill ? n - i : total - st.fill;
-                memcpy(st.buf + st.fill, b + i, (size_t)take);
-                st.fill += take; i += take;
-            }
-            if (st.fill == mpe_total(st.buf[1], st.buf[2])) { emit(k, want_bytes); st.fill = 0; done = true; break; }
-        }
-        *used = i;
-        return done;
-    }
-    // what the shared packet loop asks of a format (ts_reasm_rules.h): one slot, the section bank's stuffing byte
-    struct Format {
-        MpeHostStream& h;
-        int slot_of(int pid) const { return pid == h.watch.pid ? 0 : -1; }
-        MpeState& state(int) { return h.st; }
-        MpeCnt& cnt(int) { return h.cnt; }
-        void drop(int) { h.drop(); }
-        bool feed(int, const uint8_t* b, int n, int* used, int k, bool want_bytes) { return h.feed(b, n, used, k, want_bytes); }
-        void begin(int, int k) { h.first_packet = k; }
-        void slack(int) {}
-        bool stuffing(uint8_t b) const { return b == 0xFF; }
-    };
-    // one call: n packets.  The caller keeps a copy of `st` if the call may have to be undone.
-    void run(const uint8_t* ts, int n, bool want_bytes) {
-        rows.clear(); bytes.clear();
-        cnt = MpeCnt{};
-        first_packet = -1;
-        if (watch.pid >= 0) ts_reasm_run(Format{*this}, ts, n, want_bytes);
-    }
-};
+// the sequential definition: one slot of one stream
+typedef DgramHostStream<MpeRules> MpeHostStream;
 
 }  // namespace s2

@@ -1,10 +1,10 @@
 // The rules of the ULE bank (own extension; include/dvbs2gpu.h), each stated once and shared by the kernels
-// (ule.hip), the native host bank (UleHostStream below, behind dvbs2gpu_ule_create_host) and a plain C++ test program: the layout of a
+// (ule.hip), the native host bank (UleHostStream, behind dvbs2gpu_ule_create_host) and a plain C++ test program: the layout of a
 // ULE SNDU (Unidirectional Lightweight Encapsulation), of its extension headers and of a bridged frame as one struct (UleLayout), what
 // a TS packet of a slot's PID does to the slot, and what an emitted SNDU's row says.  The IP header rules behind them are ip_rules.h,
 // shared with the MPE bank.
 //
-// The sequential form -- UleHostStream::run, which is ts_reasm_run with this format -- IS the definition; every other form must give
+// The sequential form -- UleHostStream::run, which is DgramHostStream (dgram_rules.h) with these rules -- IS the definition; every other form must give
 // its results for every cutting of a stream into calls.  The syntax is written from memory of RFC 4326 and RFC 5163 and is pinned to
 // no test vector of theirs: every offset and limit the code relies on is a field of UleLayout, reported through dvbs2gpu_ule_get_layout
 // and compared with the tests' model.
@@ -12,13 +12,10 @@
 // the open SNDU emits the SNDU and counts `slack` where the RFC discards it and waits for the next PUSI; a TS packet without PUSI
 // ignores what is left of its payload behind the open SNDU's end (the RFC requires PUSI in a packet in which an SNDU starts, so nothing
 // legal is lost); SNDUs above 4096 bytes are the bad length.
-// Standard headers, ip_rules.h and ts_reasm_rules.h only: the host tests compile this file with a plain C++ compiler.
+// Standard headers, ip_rules.h, dgram_rules.h and ts_reasm_rules.h only: the host tests compile this file with a plain C++ compiler.
 #pragma once
+#include "dgram_rules.h"
 #include "ip_rules.h"
-#include "ts_reasm_rules.h"
-
-#include <cstring>
-#include <vector>
 
 namespace s2 {
 
@@ -140,90 +137,25 @@ TS_HD inline void ule_account(unsigned flags, Add add) {
     for (int k = 0; k < 10; ++k) if (flags >> k & 1) add(of_flag[k]);
 }
 
-// ------------------------------------------------------------------------------------------------- the sequential definition
-struct UleState {
-    uint8_t cont = 0;                                      // tsmon_step's byte
-    int fill = 0;                                          // bytes buffered; 0: no SNDU is open
-    uint8_t buf[ULE_BUF];
+// ------------------------------------------------------------------------------------------------- what the shared code asks of the bank
+// (dgram_rules.h: the sequential stream; dgram_bank.h: the kernels and the handle)
+struct UleRules {
+    typedef UleRow Row; typedef UleWatch Watch; typedef UleCnt Cnt;
+    static constexpr UleWatch NO_WATCH = {-1, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}, 0};
+    static constexpr int SLOTS = ULE_SLOTS, BUF = ULE_BUF, NCNT = ULE_NCNT, DATAGRAM = ULE_DATAGRAM;
+    // the length is known from the first two bytes (D and the 15-bit Length), a Length beyond 4092 is bad
+    static constexpr int HEADER = ULE.length_bytes, LEN_A = 0, LEN_B = 1;
+    static constexpr int C_PACKETS = ULC_PACKETS, C_SCR = ULC_SCR, C_MALPKT = ULC_MALPKT, C_DELIVERED = ULC_DELIVERED, C_BYTES = ULC_BYTES;
+    static constexpr int C_DROPPED = ULC_DROPPED, C_BAD_UNIT = ULC_MALSNDU, C_SLACK = ULC_SLACK;
+    // the rules above under the names the shared code calls them by: constant function pointers, not forwarding members (a row returned through one
+    // more call level costs the scan kernel registers: profiles/ts_reasm_resources.txt)
+    static constexpr auto total = &ule_total;
+    static constexpr auto ip_at = &ule_ip_at;
+    template <typename Src> static constexpr auto row_fields = &ule_row_fields<Src>;
+    template <typename Add> TS_HD static void account(unsigned flags, Add add) { ule_account(flags, add); }
+    TS_HD static bool takes_crc(unsigned, unsigned, int) { return true; }      // there is no unchecked SNDU
 };
-// an SNDU's bytes in memory, the reductions as loops
-struct UleHostSrc {
-    const uint8_t* b;
-    unsigned rd(int i) const { return b[i]; }
-    template <typename Fn> bool any(int n, Fn f) const { for (int k = 0; k < n; ++k) if (f(k)) return true; return false; }
-    template <typename Fn> unsigned sum(int n, Fn f) const { unsigned v = 0; for (int k = 0; k < n; ++k) v += f(k); return v; }
-};
-
-// one slot of one stream: a complete reassembler
-struct UleHostStream {
-    UleWatch watch = {-1, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}, 0};
-    UleState st;
-    int first_packet = -1;                                 // of the open SNDU, in this call
-    // of the last call
-    std::vector<UleRow> rows;
-    std::vector<uint8_t> bytes;
-    UleCnt cnt = {};
-
-    void clear() { st = UleState(); rows.clear(); bytes.clear(); }
-
-    void drop() {
-        if (st.fill > 0) ++cnt.dropped_sndus;
-        st.fill = 0;
-    }
-    void emit(int k, bool want_bytes) {
-        const uint8_t* b = st.buf;
-        const int total = st.fill;
-        UleRow r = ule_row_fields(UleHostSrc{b}, total, ts_crc32(b, total) == 0, watch, first_packet, k);
-        ule_account(r.flags, [&](int c) { ++reinterpret_cast<int32_t*>(&cnt)[c]; });
-        if (want_bytes && (r.flags & ULE_DATAGRAM)) {
-            const uint8_t* d = b + ule_ip_at(r);
-            r.offset = (int32_t)bytes.size();
-            bytes.insert(bytes.end(), d, d + r.bytes);
-            ++cnt.datagrams_delivered; cnt.bytes_delivered += r.bytes;
-        }
-        rows.push_back(r);
-    }
-    // n bytes for the slot's SNDU (open, or starting with them): stops behind the SNDU's last byte.  true: it was emitted; a bad length
-    // forgets the header and is false too
-    bool feed(const uint8_t* b, int n, int* used, int k, bool want_bytes) {
-        int i = 0;
-        bool done = false;
-        while (i < n) {
-            if (st.fill < ULE.length_bytes) {
-                st.buf[st.fill++] = b[i++];
-                if (st.fill < ULE.length_bytes) continue;
-                if (ule_total(st.buf[0], st.buf[1]) < 0) { ++cnt.malformed_sndus; st.fill = 0; break; }
-            } else {
-                const int total = ule_total(st.buf[0], st.buf[1]);
-                const int take = n - i < total - st.fill ? n - i : total - st.fill;
-                memcpy(st.buf + st.fill, b + i, (size_t)take);
-                st.fill += take; i += take;
-            }
-            if (st.fill == ule_total(st.buf[0], st.buf[1])) { emit(k, want_bytes); st.fill = 0; done = true; break; }
-        }
-        *used = i;
-        return done;
-    }
-    // what the shared packet loop asks of a format (ts_reasm_rules.h): one slot; 0xFF in an SNDU's first place -- the End Indicator
-    // 0xFFFF and 0xFF padding alike -- ends the packet's chain
-    struct Format {
-        UleHostStream& h;
-        int slot_of(int pid) const { return pid == h.watch.pid ? 0 : -1; }
-        UleState& state(int) { return h.st; }
-        UleCnt& cnt(int) { return h.cnt; }
-        void drop(int) { h.drop(); }
-        bool feed(int, const uint8_t* b, int n, int* used, int k, bool want_bytes) { return h.feed(b, n, used, k, want_bytes); }
-        void begin(int, int k) { h.first_packet = k; }
-        void slack(int) { ++h.cnt.slack; }
-        bool stuffing(uint8_t b) const { return b == 0xFF; }
-    };
-    // one call: n packets.  The caller keeps a copy of `st` if the call may have to be undone.
-    void run(const uint8_t* ts, int n, bool want_bytes) {
-        rows.clear(); bytes.clear();
-        cnt = UleCnt{};
-        first_packet = -1;
-        if (watch.pid >= 0) ts_reasm_run(Format{*this}, ts, n, want_bytes);
-    }
-};
+// the sequential definition: one slot of one stream
+typedef DgramHostStream<UleRules> UleHostStream;
 
 }  // namespace s2

@@ -332,3 +332,47 @@ def test_end_to_end_chained_on_the_device(pkg, eng):
     assert np.array_equal(got, want) and bank.row_table(0, 0) == model.table
     k = len(model.table)
     assert k >= 36 and bytes(got) == b''.join(sent[:k]) and bank.stats(0)['crc_errors'] == 0 and bank.stats(0)['datagrams_delivered'] == k
+
+
+def test_an_mpe_and_a_ule_bank_side_by_side(pkg, eng):
+    """the two banks are two instantiations of one core (csrc/dgram_bank.h) in one process and share no state: on one engine an MpeBank
+    and a UleBank take the same two streams, each carrying an MPE PID and a ULE PID interleaved, in calls of 1, 64 and 65 packets,
+    turn and turn about.  Every call of either bank equals its model and its host bank in bytes, rows, needed sizes and counters and
+    costs two launches (Rig.call, here and in test_gpu_mpe.py).  The call of 64 packets first goes to a pair of banks with max_rows = 2
+    that took the first call too: it fails for capacity in both, advances nothing, and is repeated on the banks with room.  The last
+    call has deliver=False in the ULE bank.  Each bank watches the other's PID in a further slot and finds no unit of its own there."""
+    import test_gpu_mpe as TM
+    MP, UP, sizes = 0x0300, 0x0301, [28, 100, 700]
+    rng = np.random.default_rng(21)
+    ts = [S.interleave(rng, [TM.feed(rng, MP, 65, sizes, cc=i), feed(rng, UP, 65, sizes, cc=3 + i)]) for i in range(2)]
+    wm = [[(0, MP, None, None)], [(1, MP, None, None), (2, UP, None, None)]]
+    wu = [[(0, UP, None, None, True)], [(3, UP, None, None, True), (1, MP, None, None, True)]]
+    mpe, ule = TM.Rig(pkg, eng, 2, 65, 64, watches=wm), Rig(pkg, eng, 2, 65, 64, watches=wu)
+    tight = [pkg.MpeBank(eng, 2, 65, 2), pkg.UleBank(eng, 2, 65, 2)]
+    for bank, watches in zip(tight, (wm, wu)):
+        for i in range(2):
+            for w in watches[i]:
+                bank.set_watch(i, *w)
+    calls = [[t[a:b] for t in ts] for a, b in ((0, 1), (1, 65), (65, 130))]
+    mpe.call(calls[0]), ule.call(calls[0], shift=1)
+    undelivered = lambda st: {n: v for n, v in st.items() if n not in ('datagrams_delivered', 'bytes_delivered')}   # (they take rows only)
+    failed, was = [], []
+    for bank, rig in zip(tight, (mpe, ule)):
+        bank.process([_dev(t) for t in calls[0]], None, nbytes=[t.size for t in calls[0]])
+        was.append([[bank.stats(i, k) for k in range(4)] for i in range(2)])
+        assert all(was[-1][i][k] == undelivered(rig.dv.stats(i, k)) | {'datagrams_delivered': 0, 'bytes_delivered': 0} for i in range(2) for k in range(4))
+    for bank, before in zip(tight, was):
+        with pytest.raises(pkg.Dvbs2GpuError) as e:
+            bank.process([_dev(t) for t in calls[1]], None, nbytes=[t.size for t in calls[1]])
+        assert e.value.code == -5 and all(bank.stats(i, k) == before[i][k] and bank.row_table(i, k) == [] for i in range(2) for k in range(4))
+        failed.append(e.value)
+    mpe.call(calls[1], shift=2), ule.call(calls[1], shift=3)         # the repeat, with room
+    for e, bank, rig in zip(failed, tight, (mpe, ule)):
+        rows = [[rig.dv.needed(i, k)[1] for k in range(4)] for i in range(2)]
+        assert e.rows == rows and max(max(r) for r in rows) > 2 and e.needed == [[-1 if n > 2 else 0 for n in r] for r in rows]
+        assert [[bank.needed(i, k) for k in range(4)] for i in range(2)] == [[(b, n) for b, n in zip(e.needed[i], rows[i])] for i in range(2)]
+    mpe.call(calls[2], shift=1), ule.call(calls[2], deliver=False)
+    assert all(bank.stats(i, k) == before[i][k] for bank, before in zip(tight, was) for i in range(2) for k in range(4))     # untouched by the others' calls
+    assert mpe.models[1].stats(1)['datagrams_delivered'] > 10 and mpe.models[1].stats(2)['dropped_sections'] > 0 and mpe.models[1].stats(2)['sections'] == 0
+    assert ule.models[1].stats(3)['datagrams'] > 10 and ule.models[1].stats(3)['datagrams_delivered'] < ule.models[1].stats(3)['datagrams']
+    assert ule.models[1].stats(1)['sndus'] + ule.models[1].stats(1)['malformed_sndus'] > 0 and ule.models[1].stats(1)['datagrams'] == 0
