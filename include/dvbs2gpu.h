@@ -1557,6 +1557,159 @@ int dvbs2gpu_ule_get_row_table(dvbs2gpu_ule* b, int stream, int slot, dvbs2gpu_u
 /* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
 int dvbs2gpu_ule_get_row_table_device(dvbs2gpu_ule* b, int stream, int slot, const dvbs2gpu_ule_row** d_rows, int* n);
 
+/* ------------------------------------------------------------------ IP-TS bank (own extension)
+ * Nothing in the reference does this.  The IP datagrams that the MPE bank, the ULE bank and the GSE paths leave in HBM, one table row
+ * each, usually carry television again: an MPTS or SPTS in UDP or in RTP (RFC 2250, payload type 33), normally 7 x 188 bytes per
+ * datagram, to a multicast group and port.  For `nstreams` streams a bank reads such a table where it lies, picks the UDP datagrams of
+ * up to 4 flow slots per stream, verifies their UDP checksum, recognises raw TS or RTP/MP2T payloads, applies an RTP sequence rule per
+ * slot, writes one row per input row and lays the TS packets of each slot back to back in a device buffer: a d_ts[i] / nbytes[i] of
+ * dvbs2gpu_tsmon_process_batch and of the PSI, PCR, PES and T2-MI banks.  The sequential form below is the definition
+ * (csrc/ipts_rules.h, IptsHostStream::run); the kernels give its results for every cutting of a datagram sequence into calls.  The
+ * syntax is written from memory of RFC 768, RFC 791, RFC 8200, RFC 3550 and RFC 2250 and pinned to no vector of theirs; it is one
+ * struct, dvbs2gpu_ipts_layout.
+ *   Input: one view per stream and call (dvbs2gpu_ipts_view, below), the same for device and host banks: the datagram bytes, a table of
+ *     n rows (0 <= n <= max_rows) of `stride` bytes, and where a row keeps its int32 offset into the bytes and its int32 byte count (a
+ *     count below 0 is read as 0).  kind RAW_IP: a datagram starts at its IP header (MPE and ULE rows); kind GRE: it starts with the
+ *     GRE header that the GSE paths write (dvbs2gpu_gse_pdu rows).  The bank writes exactly one row per input row, at the same index.
+ *   Flows: 4 slots per stream, each empty (family 0) or (family 4 | 6, destination address, destination UDP port); an IPv4 address
+ *     is the first four of the sixteen address bytes, in network order.  The match is exact on all three; where several slots match,
+ *     the lowest wins.  A new bank has no flow.  set_flow clears the slot's counters and its RTP state.
+ *   Rules per row, in table order; the first rule that fires ends the list, except where it says that the list goes on, and the
+ *   fields of the row that later rules would set are 0 (slot and offset: -1):
+ *     1. offset < 0 (its source did not deliver it): flag NOT_DELIVERED.
+ *     2. Kind GRE: the row needs the 4 bytes 00 00 08 00 (family 4) or 00 00 86 DD (family 6), else flag NOT_IP; the IP header
+ *        follows them (its version nibble is not looked at).  Kind RAW_IP: the family is the high nibble of the first byte, 4 or 6,
+ *        else (or with no byte) NOT_IP.
+ *     3. The IP header by the rules 9 and 10 of the MPE bank (csrc/ip_rules.h, shared), avail = the row's bytes from the IP header
+ *        on: what is BAD_IP there is flag BAD_IP here.  Else `family` is set.  Bytes behind the IP length are ignored.
+ *     4. IPv4 with MF set or a fragment offset != 0 ((i6 << 8 | i7) & 0x3FFF): flag FRAGMENT.  Protocol (IPv6: next_header) != 17:
+ *        flag OTHER_PROTOCOL; IPv6 extension headers are not followed.
+ *     5. The IP payload (behind 4 IHL or 40 header bytes, up to the IP length) needs 8 bytes, and the UDP length L = u4 << 8 | u5
+ *        must be 8 <= L <= the IP payload bytes, else flag BAD_UDP.  src_port = u0 << 8 | u1, dst_port = u2 << 8 | u3; the payload
+ *        is the L - 8 bytes from u8.
+ *     6. No slot of the stream matches (family, destination address, dst_port): flag UNWATCHED; nothing more is read of the
+ *        datagram.  Else `slot`.
+ *     7. The transmitted checksum u6 << 8 | u7 of 0 means not computed on IPv4: flag NO_CHECKSUM, nothing is verified, the list goes
+ *        on; on IPv6 it is flag BAD_CHECKSUM.  Else the ones'-complement sum, carries folded in, of the pseudo-header (IPv4: source,
+ *        destination, 0, 17, L; IPv6: source, destination, L as 32 bits, 0 0 0 17) and of the L UDP bytes as big-endian 16-bit
+ *        words, an odd last byte padded with a zero byte, must be 0xFFFF, else flag BAD_CHECKSUM.
+ *     8. A payload whose length is a positive multiple of 188 with 0x47 at every k * 188 is raw TS: flag RAW, ts_at = where it
+ *        starts in the row's bytes.  Any other payload is read as RTP (bytes p0 ..): fewer than 12 bytes or a version p0 >> 6 != 2:
+ *        flag BAD_PAYLOAD.  The header is 12 + 4 CC (p0 & 15) bytes; with X (p0 >> 4 & 1) 4 more bytes follow, plus 4 x the 16-bit
+ *        number in their last two; with P (p0 >> 5 & 1) the last payload byte is the pad count, which must be >= 1; any of these
+ *        running beyond the payload: BAD_PAYLOAD.  payload_type = p1 & 127; != 33: flag OTHER_PAYLOAD.  What is left between header
+ *        and padding must be a positive multiple of 188 with 0x47 at every k * 188, else BAD_PAYLOAD.  Flag RTP; rtp_seq = p2 << 8 |
+ *        p3, rtp_timestamp = p4..p7, rtp_ssrc = p8..p11 as big-endian numbers; ts_at as above.  The marker bit is not looked at.
+ *     9. RTP rows only; per slot the state (has, last_seq, ssrc) survives calls.  Nothing stored: accept.  Another SSRC than the
+ *        stored one: flag NEW_SOURCE, accept.  Else d = (rtp_seq - last_seq - 1) mod 65536: 0: accept; 1 <= d < 0x8000: flag LOSS,
+ *        lost = d, accept; d >= 0x8000 (a duplicate or a reordered packet): flag LATE, not delivered, the state unchanged.  Accepting
+ *        stores (rtp_seq, rtp_ssrc).  RAW rows neither read nor write the state.
+ *    10. A RAW row and an accepted RTP row have flag TS, packets = their TS packets and bytes = 188 packets.  When the call has output
+ *        buffers the packets go to the slot's buffer, back to back in row order, and row.offset names them.  Every other row has
+ *        offset -1.
+ *   Counters: one per flag; those of rules 1 to 6 and `rows` per stream, those of rules 7 to 10 and `matched` per slot, with ts_packets
+ *     (the packets of TS rows), bytes_delivered (of calls with output buffers), lost (the sum of row.lost) and loss_events (the rows with
+ *     LOSS).  Kept on the host in 64 bits.
+ *   Capacity: sizes first.  If a slot's bytes exceed cap the call returns DVBS2GPU_ERR_CAPACITY, out_bytes[] holds the needed sizes; no
+ *     state or counter of any stream has advanced, the tables of the call are empty, the call can be repeated.  A view of more than
+ *     max_rows rows is an argument error.
+ *   State survives from call to call.  reset forgets state and counters; the flows stay.
+ *   Limits: max_rows <= 16384 per stream and call.  Memory (device banks): 40 bytes per row of max_rows and 0.5 KB per stream.
+ *   NOT done: RFC 2733 / SMPTE 2022-1 FEC; reordering of LATE packets; IPv4 reassembly; IPv6 extension headers; address masks and
+ *     source filters; RTCP. */
+typedef struct dvbs2gpu_ipts dvbs2gpu_ipts;
+#define DVBS2GPU_IPTS_KIND_RAW_IP 0
+#define DVBS2GPU_IPTS_KIND_GRE 1
+typedef struct dvbs2gpu_ipts_view {            /* 40 bytes */
+    const uint8_t* bytes;            /* the datagram bytes, of any alignment (process_batch: a DEVICE pointer; work: a host pointer) */
+    const void* rows;                /* n rows of `stride` bytes, at a multiple of 4 (device / host like bytes) */
+    int32_t stride;                  /* a multiple of 4 */
+    int32_t offset_at, bytes_at;     /* where a row keeps its int32 offset into `bytes` and its int32 byte count: multiples of 4 */
+    int32_t kind;                    /* DVBS2GPU_IPTS_KIND_* */
+    int32_t n;                       /* rows, 0 .. max_rows (with 0 the pointers may be NULL) */
+    int32_t reserved;
+} dvbs2gpu_ipts_view;
+/* built with offsetof from the calls that name a table in HBM and the buffer the rows point into:
+ *   dvbs2gpu_mpe_get_row_table_device / dvbs2gpu_ule_get_row_table_device (kind RAW_IP; dvbs2gpu_mpe_row / dvbs2gpu_ule_row: offset, bytes;
+ *     bytes = the slot's d_out), dvbs2gpu_bbts_get_pdu_table_device / dvbs2gpu_bbts_ma_get_pdu_table_device (kind GRE; dvbs2gpu_gse_pdu:
+ *     offset, bytes; bytes = the stream's or the ISI lane's output buffer). */
+typedef struct dvbs2gpu_ipts_layout {
+    int32_t gre_header_bytes, ipv4_src_at, ipv6_src_at, ipv6_dst_at, ipv4_more_fragments, udp_protocol, udp_header_bytes, udp_length_at, udp_checksum_at;
+    int32_t ts_packet_bytes, ts_sync, rtp_min_header, rtp_version, rtp_payload_type_mp2t, rtp_seq_at, rtp_timestamp_at, rtp_ssrc_at, late_from;
+    int32_t head_bytes;              /* rules 2 to 6 read the first 72 bytes of a row at most; a wave keeps 128 */
+    int32_t slots, row_bytes, view_bytes;
+} dvbs2gpu_ipts_layout;
+int dvbs2gpu_ipts_create(dvbs2gpu_ctx* ctx, int nstreams, int max_rows, dvbs2gpu_ipts** out);
+/* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_ipts_work only */
+int dvbs2gpu_ipts_create_host(int nstreams, int max_rows, dvbs2gpu_ipts** out);
+int dvbs2gpu_ipts_reset(dvbs2gpu_ipts* b);
+void dvbs2gpu_ipts_destroy(dvbs2gpu_ipts* b);
+int dvbs2gpu_ipts_get_layout(dvbs2gpu_ipts_layout* h_out);
+/* slot 0..3; family 4, 6, or 0: the slot is empty (dst_addr may be NULL then); dst_addr: sixteen bytes, an IPv4 address in the first four */
+int dvbs2gpu_ipts_set_flow(dvbs2gpu_ipts* b, int stream, int slot, int family, const uint8_t dst_addr[16], int dst_port);
+/* views[i] (a host array of views with DEVICE pointers): the datagrams of stream i.  d_out NULL: rows and counters only (never a
+ * capacity failure; out_bytes may be NULL).  Else d_out[i*4 + k]: DEVICE buffer of cap bytes, of any alignment, for the TS packets of
+ * slot k of stream i (NULL for an empty slot); out_bytes[i*4 + k] (host) their bytes.  out_rows[i] (host, may be NULL): the rows
+ * written, views[i].n.  Two kernel launches.  Synchronous on `stream`; chained behind the call that wrote the datagrams and in front
+ * of a TS bank's call on the same stream, no packet visits the host. */
+int dvbs2gpu_ipts_process_batch(dvbs2gpu_ipts* b, const dvbs2gpu_ipts_view* views, uint8_t* const* d_out, int cap, int* out_bytes, int* out_rows,
+                                void* stream);
+/* one stream of any bank with HOST pointers in the view and HOST buffers h_out[k] of cap bytes (h_out NULL: rows and counters only);
+ * out_bytes[4] (may be NULL): the bytes of each slot.  0 or a negative error.  Every other stream of the bank receives an empty call. */
+int dvbs2gpu_ipts_work(dvbs2gpu_ipts* b, int stream, const dvbs2gpu_ipts_view* h_view, uint8_t* const* h_out, int cap, int* out_bytes);
+/* the bytes that the slot's last call needed, whether it succeeded or failed for capacity (0 of a call without output buffers) */
+int dvbs2gpu_ipts_get_needed(dvbs2gpu_ipts* b, int stream, int slot, int* bytes);
+typedef struct dvbs2gpu_ipts_stats {           /* since creation or reset; a slot's since its last set_flow; kept on the host */
+    /* the stream's own (0 when a slot >= 0 is asked for) */
+    int64_t rows;
+    int64_t not_delivered, not_ip, bad_ip, fragments, other_protocol, bad_udp, unwatched;
+    /* a slot's */
+    int64_t matched;                 /* rows of the slot's flow */
+    int64_t bad_checksum, no_checksum, bad_payload, other_payload, raw, rtp, new_source, loss_events, late;
+    int64_t ts;                      /* rows with TS, delivered or not */
+    int64_t ts_packets;              /* their TS packets */
+    int64_t bytes_delivered;
+    int64_t lost;                    /* RTP packets missing before rows with LOSS */
+} dvbs2gpu_ipts_stats;
+/* slot 0..3: the slot's counters; slot -1: the stream's own counters and the sum over its slots */
+int dvbs2gpu_ipts_get_stats(dvbs2gpu_ipts* b, int stream, int slot, dvbs2gpu_ipts_stats* h_out);
+#define DVBS2GPU_IPTS_NOT_DELIVERED 1
+#define DVBS2GPU_IPTS_NOT_IP 2
+#define DVBS2GPU_IPTS_BAD_IP 4
+#define DVBS2GPU_IPTS_FRAGMENT 8
+#define DVBS2GPU_IPTS_OTHER_PROTOCOL 16
+#define DVBS2GPU_IPTS_BAD_UDP 32
+#define DVBS2GPU_IPTS_UNWATCHED 64
+#define DVBS2GPU_IPTS_BAD_CHECKSUM 128
+#define DVBS2GPU_IPTS_NO_CHECKSUM 256
+#define DVBS2GPU_IPTS_BAD_PAYLOAD 512
+#define DVBS2GPU_IPTS_OTHER_PAYLOAD 1024
+#define DVBS2GPU_IPTS_RAW 2048
+#define DVBS2GPU_IPTS_RTP 4096
+#define DVBS2GPU_IPTS_NEW_SOURCE 8192
+#define DVBS2GPU_IPTS_LOSS 16384
+#define DVBS2GPU_IPTS_LATE 32768
+#define DVBS2GPU_IPTS_TS 65536
+typedef struct dvbs2gpu_ipts_row {             /* 40 bytes */
+    uint32_t flags;
+    int8_t slot;                     /* of a row that matched a flow, else -1 */
+    uint8_t family;                  /* 4 or 6 of a row that passed rule 3, else 0 */
+    uint8_t payload_type;            /* of an RTP header that passed its length checks */
+    uint8_t reserved;
+    uint16_t src_port, dst_port;     /* of a row that passed rule 5 */
+    uint16_t rtp_seq;                /* of a row with RTP */
+    uint16_t ts_at;                  /* of a row with RAW or RTP: where its TS packets start in the input row's bytes */
+    uint32_t rtp_timestamp, rtp_ssrc;
+    int32_t packets;                 /* TS packets of a TS row, delivered or not; else 0 */
+    int32_t lost;                    /* of a row with LOSS */
+    int32_t offset;                  /* of the TS packets in the slot's output buffer; -1: not delivered */
+    int32_t bytes;                   /* 188 packets */
+} dvbs2gpu_ipts_row;
+/* h_rows[cap] (host); *n = rows of the stream's last call, of which min(*n, cap) are written */
+int dvbs2gpu_ipts_get_row_table(dvbs2gpu_ipts* b, int stream, dvbs2gpu_ipts_row* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_ipts_get_row_table_device(dvbs2gpu_ipts* b, int stream, const dvbs2gpu_ipts_row** d_rows, int* n);
+
 #ifdef __cplusplus
 }
 #endif

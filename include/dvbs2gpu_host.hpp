@@ -1038,5 +1038,87 @@ public:
         check(dvbs2gpu_ule_set_watch(need(), 0, slot, pid, npa_value, npa_mask, accept_unaddressed ? 1 : 0));
     }
 };
+/* IP-TS bank for one stream (dvbs2gpu_ipts_*, include/dvbs2gpu.h; an extension): the UDP / RTP datagrams of up to four flows among the
+ * IP datagrams that MpeBank::work or UleBank::work delivered (or a GSE path's GRE packets) are checked and their TS packets laid back to
+ * back per flow slot, for TSMonitor and the banks behind it.  init() (a device bank) or initHost() (the library's host implementation,
+ * no device) and the setters throw; work() sits in the data path and does NOT throw: a failing call returns false and leaves its code
+ * in status() and its text in error(), sticky until clearStatus(). */
+class IpTsBank {
+public:
+    IpTsBank() {}
+    ~IpTsBank() { release(); }
+    IpTsBank(const IpTsBank&) = delete;
+    IpTsBank& operator=(const IpTsBank&) = delete;
+
+    void init(int max_rows, int device = 0) {
+        release();
+        eng = Engine::get(device);
+        check(dvbs2gpu_ipts_create(eng->ctx, 1, max_rows, &h));
+    }
+    void initHost(int max_rows) {
+        release();
+        check(dvbs2gpu_ipts_create_host(1, max_rows, &h));
+    }
+    void reset() { check(dvbs2gpu_ipts_reset(need())); }
+    /* slot 0..3; family 4 or 6 with the destination address (sixteen bytes, an IPv4 address in the first four) and UDP port; family 0
+     * empties the slot.  The slot's counters and RTP state start afresh. */
+    void setFlow(int slot, int family, const uint8_t* dst_addr = nullptr, int dst_port = 0) { check(dvbs2gpu_ipts_set_flow(need(), 0, slot, family, dst_addr, dst_port)); }
+    /* The view of the rows of a bank's last work() over the host buffer that call filled: Row is dvbs2gpu_mpe_row, dvbs2gpu_ule_row
+     * (kind RAW_IP) or dvbs2gpu_gse_pdu (kind GRE).  `rows` must outlive the work() call that takes the view. */
+    template <typename Row>
+    static dvbs2gpu_ipts_view view(const uint8_t* bytes, const std::vector<Row>& rows, int kind = DVBS2GPU_IPTS_KIND_RAW_IP) {
+        return dvbs2gpu_ipts_view{rows.empty() ? nullptr : bytes, rows.empty() ? nullptr : rows.data(), (int32_t)sizeof(Row), (int32_t)offsetof(Row, offset),
+                                  (int32_t)offsetof(Row, bytes), kind, (int32_t)rows.size(), 0};
+    }
+    /* ts[k] (buffer_outsize bytes each; nullptr for a slot without a flow; ts == nullptr: rows and counters only) receives the TS
+     * packets of slot k, bytes[k] (may be nullptr) their byte counts; false on failure (see status(); on DVBS2GPU_ERR_CAPACITY
+     * needed() has the sizes and nothing was consumed) */
+    bool work(const dvbs2gpu_ipts_view& v, uint8_t* const ts[4], int buffer_outsize, int bytes[4]) noexcept {
+        const int rc = h ? dvbs2gpu_ipts_work(h, 0, &v, ts, buffer_outsize, bytes) : DVBS2GPU_ERR_ARG;
+        if (rc >= 0) return true;
+        if (status_ == 0) {
+            status_ = rc;
+            try { error_ = h ? dvbs2gpu_last_error() : std::string("IpTsBank used before init()"); } catch (...) {}
+        }
+        return false;
+    }
+    int status() const { return status_; }
+    const std::string& error() const { return error_; }
+    void clearStatus() { status_ = 0; error_.clear(); }
+    /* the bytes that the slot's last work() needed */
+    int needed(int slot) {
+        int b = 0;
+        check(dvbs2gpu_ipts_get_needed(need(), 0, slot, &b));
+        return b;
+    }
+    /* a slot's counters; -1: the stream's own and the sum over its slots */
+    dvbs2gpu_ipts_stats stats(int slot = -1) {
+        dvbs2gpu_ipts_stats s;
+        check(dvbs2gpu_ipts_get_stats(need(), 0, slot, &s));
+        return s;
+    }
+    /* one row per input row of the last work(), in row order */
+    std::vector<dvbs2gpu_ipts_row> rowTable() {
+        int n = 0;
+        check(dvbs2gpu_ipts_get_row_table(need(), 0, nullptr, 0, &n));
+        std::vector<dvbs2gpu_ipts_row> rows((size_t)n);
+        if (n > 0) check(dvbs2gpu_ipts_get_row_table(h, 0, rows.data(), n, &n));
+        return rows;
+    }
+
+private:
+    void release() {
+        if (h) dvbs2gpu_ipts_destroy(h);
+        h = nullptr;
+    }
+    dvbs2gpu_ipts* need() {
+        if (!h) throw std::runtime_error("dvbs2gpu: IpTsBank used before init()");
+        return h;
+    }
+    std::shared_ptr<Engine> eng;
+    dvbs2gpu_ipts* h = nullptr;
+    int status_ = 0;
+    std::string error_;
+};
 }   // namespace dvbs2gpu_host
 #endif

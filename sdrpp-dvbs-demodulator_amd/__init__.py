@@ -251,6 +251,33 @@ class UleRow(C.Structure):
                 ('bytes', C.c_int32), ('first_packet', C.c_int32), ('last_packet', C.c_int32), ('ethertype', C.c_uint16), ('stuffing', C.c_uint16)]
 
 
+class IptsView(C.Structure):
+    """dvbs2gpu_ipts_view"""
+    _fields_ = [('bytes', C.c_void_p), ('rows', C.c_void_p), ('stride', C.c_int32), ('offset_at', C.c_int32), ('bytes_at', C.c_int32), ('kind', C.c_int32),
+                ('n', C.c_int32), ('reserved', C.c_int32)]
+
+
+class IptsLayout(C.Structure):
+    """dvbs2gpu_ipts_layout"""
+    _fields_ = [(k, C.c_int32) for k in ('gre_header_bytes', 'ipv4_src_at', 'ipv6_src_at', 'ipv6_dst_at', 'ipv4_more_fragments', 'udp_protocol', 'udp_header_bytes',
+                                         'udp_length_at', 'udp_checksum_at', 'ts_packet_bytes', 'ts_sync', 'rtp_min_header', 'rtp_version', 'rtp_payload_type_mp2t',
+                                         'rtp_seq_at', 'rtp_timestamp_at', 'rtp_ssrc_at', 'late_from', 'head_bytes', 'slots', 'row_bytes', 'view_bytes')]
+
+
+class IptsStats(C.Structure):
+    """dvbs2gpu_ipts_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('rows', 'not_delivered', 'not_ip', 'bad_ip', 'fragments', 'other_protocol', 'bad_udp', 'unwatched', 'matched', 'bad_checksum',
+                                         'no_checksum', 'bad_payload', 'other_payload', 'raw', 'rtp', 'new_source', 'loss_events', 'late', 'ts', 'ts_packets',
+                                         'bytes_delivered', 'lost')]
+
+
+class IptsRow(C.Structure):
+    """dvbs2gpu_ipts_row"""
+    _fields_ = [('flags', C.c_uint32), ('slot', C.c_int8), ('family', C.c_uint8), ('payload_type', C.c_uint8), ('reserved', C.c_uint8), ('src_port', C.c_uint16),
+                ('dst_port', C.c_uint16), ('rtp_seq', C.c_uint16), ('ts_at', C.c_uint16), ('rtp_timestamp', C.c_uint32), ('rtp_ssrc', C.c_uint32),
+                ('packets', C.c_int32), ('lost', C.c_int32), ('offset', C.c_int32), ('bytes', C.c_int32)]
+
+
 class FrameQuality(C.Structure):
     """dvbs2gpu_frame_quality"""
     _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('gain', C.c_float), ('phase', C.c_float), ('known_symbols', C.c_int32),
@@ -476,6 +503,20 @@ for _p, _Lay, _St, _Row, _watch in (('mpe', MpeLayout, MpeStats, MpeRow, []), ('
         'get_row_table': (_i, [_vp, _i, _i, C.POINTER(_Row), _i, C.POINTER(_i)]),
         'get_row_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
     }.items()})
+PROTOTYPES.update({
+    'dvbs2gpu_ipts_create': (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_ipts_create_host': (_i, [_i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_ipts_reset': (_i, [_vp]),
+    'dvbs2gpu_ipts_destroy': (None, [_vp]),
+    'dvbs2gpu_ipts_get_layout': (_i, [C.POINTER(IptsLayout)]),
+    'dvbs2gpu_ipts_set_flow': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint8), _i]),
+    'dvbs2gpu_ipts_process_batch': (_i, [_vp, C.POINTER(IptsView), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    'dvbs2gpu_ipts_work': (_i, [_vp, _i, C.POINTER(IptsView), C.POINTER(_vp), _i, C.POINTER(_i)]),
+    'dvbs2gpu_ipts_get_needed': (_i, [_vp, _i, _i, C.POINTER(_i)]),
+    'dvbs2gpu_ipts_get_stats': (_i, [_vp, _i, _i, C.POINTER(IptsStats)]),
+    'dvbs2gpu_ipts_get_row_table': (_i, [_vp, _i, C.POINTER(IptsRow), _i, C.POINTER(_i)]),
+    'dvbs2gpu_ipts_get_row_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
+})
 
 _lib = None
 
@@ -2063,6 +2104,147 @@ class UleBank(_DatagramBank):
         if any(v is not None and len(bytes(v)) != 6 for v in (npa, mask)):
             raise ValueError('an NPA address or mask has six bytes')
         self._check(self.lib.dvbs2gpu_ule_set_watch(self.h, int(stream), int(slot), int(pid), six(npa), six(mask), int(bool(accept_unaddressed))))
+
+
+class IpTsBank(_TsBank):
+    """IP-TS bank for `nstreams` streams (own extension; include/dvbs2gpu.h, IP-TS bank): among the IP datagrams that an MpeBank, a
+    UleBank or a GSE path left in HBM with one table row each, the UDP datagrams of up to four flows (family, destination address,
+    destination port) per stream have their UDP checksum verified, their payload recognised as raw TS or RTP/MP2T and an RTP sequence
+    rule applied; one row per input row, and the TS packets of each flow slot back to back in a device buffer that TsMonitorBank,
+    PsiBank, PcrBank, PesBank and T2miBank take as input.  The input is a view (IptsView): view_from_mpe / view_from_ule /
+    view_from_pdu_table / view_from_ma_pdu_table build it from the source bank's table in HBM."""
+    _destroy = 'dvbs2gpu_ipts_destroy'
+    SLOTS = 4
+    KIND_RAW_IP, KIND_GRE = 0, 1
+    (NOT_DELIVERED, NOT_IP, BAD_IP, FRAGMENT, OTHER_PROTOCOL, BAD_UDP, UNWATCHED, BAD_CHECKSUM, NO_CHECKSUM, BAD_PAYLOAD, OTHER_PAYLOAD, RAW, RTP, NEW_SOURCE, LOSS,
+     LATE, TS) = (1 << k for k in range(17))
+    ROW_KEYS = tuple(k for k, _ in IptsRow._fields_ if k != 'reserved')
+
+    def __init__(self, engine, nstreams=1, max_rows=1024):
+        self.eng, self.lib, self.nstreams, self.max_rows = engine, engine.lib, nstreams, max_rows
+        h = C.c_void_p()
+        engine._check(self.lib.dvbs2gpu_ipts_create(engine.h, nstreams, max_rows, C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def host(cls, nstreams=1, max_rows=1024):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        return cls._host('dvbs2gpu_ipts_create_host', nstreams=nstreams, max_rows=max_rows)
+
+    @staticmethod
+    def layout():
+        """the UDP, RTP and TS syntax the library relies on (dvbs2gpu_ipts_layout) as a dict"""
+        lay = IptsLayout()
+        load_library().dvbs2gpu_ipts_get_layout(C.byref(lay))
+        return {k: int(getattr(lay, k)) for k, _ in IptsLayout._fields_}
+
+    def reset(self):
+        self._check(self.lib.dvbs2gpu_ipts_reset(self.h))
+
+    def set_flow(self, stream, slot, family, addr=None, port=0):
+        """family 4 or 6 with the destination address (4 or 16 bytes, network order) and UDP port; family 0 empties the slot; the slot's
+        counters and RTP state start afresh"""
+        a = None
+        if family:
+            if addr is None or len(bytes(addr)) != (4 if family == 4 else 16):
+                raise ValueError('an IPv4 address has four bytes, an IPv6 address sixteen')
+            a = (C.c_uint8 * 16)(*bytes(addr))
+        self._check(self.lib.dvbs2gpu_ipts_set_flow(self.h, int(stream), int(slot), int(family), a, int(port)))
+
+    # ---- views
+    @staticmethod
+    def _view(data_ptr, rows_ptr, n, Row, kind):
+        return IptsView(data_ptr if n else None, rows_ptr if n else None, C.sizeof(Row), getattr(Row, 'offset').offset, getattr(Row, 'bytes').offset, kind, n, 0)
+
+    @classmethod
+    def _view_from_datagram_bank(cls, bank, out_tensor, stream, slot):
+        p, n = bank.row_table_device(stream, slot)
+        return cls._view(out_tensor.data_ptr(), p, n, bank._Row, cls.KIND_RAW_IP), out_tensor
+
+    @classmethod
+    def view_from_mpe(cls, bank, out_tensor, stream=0, slot=0):
+        """(view, out_tensor): the datagrams of (stream, slot) of an MpeBank's last process() call, which wrote them into out_tensor"""
+        return cls._view_from_datagram_bank(bank, out_tensor, stream, slot)
+
+    @classmethod
+    def view_from_ule(cls, bank, out_tensor, stream=0, slot=0):
+        """(view, out_tensor): the datagrams of (stream, slot) of a UleBank's last process() call, which wrote them into out_tensor"""
+        return cls._view_from_datagram_bank(bank, out_tensor, stream, slot)
+
+    @classmethod
+    def view_from_pdu_table(cls, bank, out_tensor, stream=0):
+        """(view, out_tensor): the GRE packets of a stream of a BbTsParserBank's last process_batch() call (GSE frames), kind GRE"""
+        p, n = bank.pdu_table_device(stream)
+        return cls._view(out_tensor.data_ptr(), p, n, GsePdu, cls.KIND_GRE), out_tensor
+
+    @classmethod
+    def view_from_ma_pdu_table(cls, bank, out_tensor, stream=0, slot=0):
+        """(view, out_tensor): the GRE packets of an ISI lane of a BbTsParserBank's last mode-adaptation call (GSE frames), kind GRE"""
+        p, n = bank.ma_pdu_table_device(stream, slot)
+        return cls._view(out_tensor.data_ptr(), p, n, GsePdu, cls.KIND_GRE), out_tensor
+
+    # ---- calls
+    def process(self, views, out_tensors=None):
+        """views[i]: the IptsView of stream i (None: no row), device pointers; out_tensors: None for rows and counters only, else
+        out_tensors[i][k]: the uint8 CUDA buffer that receives the TS packets of slot k of stream i (None for an empty slot) -> byte
+        counts [i][k].  Dvbs2GpuError -5 carries .needed ([i][k]) when a buffer is too small (nothing has advanced then)."""
+        n, S = self.nstreams, self.SLOTS
+        va = (IptsView * n)(*[IptsView() if v is None else v for v in views])
+        pout, cap = None, 0
+        if out_tensors is not None:
+            flat = [t for per in out_tensors for t in (list(per) + [None] * S)[:S]]
+            pout = (C.c_void_p * (n * S))(*[None if t is None else t.data_ptr() for t in flat])
+            cap = min([int(t.numel()) for t in flat if t is not None] or [0])
+        nb, nr = (C.c_int * (n * S))(), (C.c_int * n)()
+        rc = self.lib.dvbs2gpu_ipts_process_batch(self.h, va, pout, cap, nb, nr, self.eng._stream())
+        split = lambda a: [list(a[i * S:(i + 1) * S]) for i in range(n)]
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            e.needed = split(nb)
+            raise e
+        return split(nb)
+
+    def work(self, data, table, kind=0, stream=0, cap=None, deliver=True):
+        """one stream, host buffers: data: numpy uint8 datagram bytes; table: (offset, bytes) per datagram -> the TS packets of the four
+        slots (a list of numpy uint8), or None with deliver=False (rows and counters only)"""
+        import numpy as np
+        data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+        tab = np.ascontiguousarray(np.asarray(table, np.int32).reshape(-1, 2))
+        v = IptsView(C.c_void_p(data.ctypes.data) if len(tab) else None, C.c_void_p(tab.ctypes.data) if len(tab) else None, 8, 0, 4, int(kind), len(tab), 0)
+        S = self.SLOTS
+        cap = data.size if cap is None else cap
+        outs = [np.zeros(max(cap, 1), np.uint8) for _ in range(S)] if deliver else None
+        pout = (C.c_void_p * S)(*[o.ctypes.data for o in outs]) if deliver else None
+        nb = (C.c_int * S)()
+        rc = self.lib.dvbs2gpu_ipts_work(self.h, int(stream), C.byref(v), pout, cap if deliver else 0, nb)
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            e.needed = list(nb)
+            raise e
+        return [o[:k].copy() for o, k in zip(outs, nb)] if deliver else None
+
+    def needed(self, stream=0, slot=0):
+        """the bytes that the slot's last call needed, whether it succeeded or failed for capacity"""
+        nb = C.c_int()
+        self._check(self.lib.dvbs2gpu_ipts_get_needed(self.h, int(stream), int(slot), C.byref(nb)))
+        return nb.value
+
+    def stats(self, stream=0, slot=-1):
+        """a slot's counters; slot -1: the stream's own counters and the sum over its slots"""
+        st = IptsStats()
+        self._check(self.lib.dvbs2gpu_ipts_get_stats(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in IptsStats._fields_}
+
+    def row_table(self, stream=0):
+        """one dict per input row of the stream's last call (the fields of dvbs2gpu_ipts_row), in row order"""
+        rows = self._rows(self.lib.dvbs2gpu_ipts_get_row_table, IptsRow, int(stream))
+        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows]
+
+    def row_table_device(self, stream=0):
+        """(device pointer or None, rows): the same table as dvbs2gpu_ipts_row records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self.lib.dvbs2gpu_ipts_get_row_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
+        return p.value, n.value
 
 
 class SegmentReceiver(_Handle):
