@@ -1151,6 +1151,125 @@ int dvbs2gpu_pes_get_row_table(dvbs2gpu_pes* b, int stream, dvbs2gpu_pes_row* h_
 /* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
 int dvbs2gpu_pes_get_row_table_device(dvbs2gpu_pes* b, int stream, const dvbs2gpu_pes_row** d_rows, int* n);
 
+/* ------------------------------------------------------------------ ES bank (own extension)
+ * Nothing in the reference does this.  For `nstreams` transport streams in HBM a bank reads every payload byte of up to 16 watched video
+ * PIDs per stream and writes an index of what they hold: one table row per PES packet start and one per reported start code -- pictures
+ * with their type, sequence headers / SPS, GOP headers, parameter sets, access unit delimiters, sequence ends -- with the position of
+ * each in the elementary stream, so that picture sizes are differences of positions and the PTS of a picture is that of the PES row in
+ * front of it.  The sequential form below is the definition (csrc/es_rules.h, EsHostStream::run); no result depends on how a stream is
+ * cut into calls or on the alignment of the input.  The syntax is written from memory of ISO/IEC 13818-1, 13818-2, 14496-10 and
+ * 23008-2 and pinned to no vector of theirs.
+ *   Watches: 16 slots per stream, each empty or a PID 0..0x1FFE with a codec: DVBS2GPU_ES_MPEG2 (also MPEG-1 video), _H264, _H265.  A
+ *     new bank watches nothing.  The same PID in two slots of a stream is an argument error.  Setting a watch starts the slot afresh,
+ *     state and counters: UNSYNCED, have = 0.
+ *   Packet: 188 bytes at offset 188 k, classified as the TS monitor does; only trusted packets of watched PIDs are looked at.  Such a
+ *     packet counts in `packets` and, in this order:
+ *     1. takes the TS monitor's continuity step.  DUPLICATE: counted in duplicates, nothing more of the packet is used.  CC_ERROR
+ *        (counted in cc_errors) or an announced discontinuity: a RESET.
+ *     2. No payload (AFC&1 clear): done.
+ *     3. AFC = 3 and b4 (adaptation_field_length) > 182: malformed_packets, a reset, done.
+ *     4. The payload is L bytes at 188 - L (184, or 183 - b4).  L adds to payload_bytes.
+ *     5. TSC != 0: scrambled_packets, a reset, and the payload is not read.  With PUSI the packet still takes the start rule (kind
+ *        SCRAMBLED); without, it is done.
+ *     6. PUSI set: a START.
+ *     7. Otherwise, if the slot is synced, the whole payload is the packet's SEGMENT of ES bytes; if not, L adds to bytes_unsynced.
+ *     A reset: have := 0 and the slot's `lost` bit is set.  It does not unsync the slot.  `resets` counts the packets that reset (once
+ *     each, whatever the number of reasons).
+ *   Start: the kind, stream_id, PES_packet_length, PTS and DTS are those of the PES bank's start rule (above), not restated.  The start
+ *     is VALID when its kind is HEADER and 9 + PES_header_data_length <= L: its segment is payload[9 + hdl .. L), which may be empty, and
+ *     the slot is synced.  A valid start does NOT reset: the ES is contiguous across PES packets and a start code may straddle them.
+ *     Every other start is invalid (pes_invalid): the slot is UNSYNCED, the scanner is reset and nothing of the payload is scanned; a
+ *     HEADER whose header runs beyond the packet (legal and rare) has the flag SPLIT_HEADER (split_headers).  One row with unit PES per
+ *     start, valid or not; the invalid start's reset comes behind its row.
+ *   Scanner: per slot es_count (64 bits: the ES bytes accepted since the watch was set), the last 7 accepted bytes and have = min(7,
+ *     bytes accepted since the last reset).  For every accepted byte in order: if have = 7, the 8-byte window is the 7 kept bytes plus
+ *     this one, w0..w7; if w0 w1 w2 = 00 00 01 a CODE has been found with code = w3 and head = w4 w5 w6 w7 (w4 in the high byte), at
+ *     es_offset = es_count - 7, the position of w0; `codes` counts it.  Then the byte is appended.  So whether a code is found is a
+ *     pure function of the last 8 ES bytes: a code whose four head bytes never arrive (reset, end of stream) is never reported,
+ *     emulation-prevention bytes inside the head are not removed, the leading zero of a 4-byte start code is not looked at.
+ *   Classification by the slot's codec; a code without a row is only counted:
+ *     MPEG2  code 00: PICTURE, detail from head >> 19 & 7 (1 I, 2 P, 3 B, else 0), KEY when I; B3: SEQUENCE; B8: GOP; B7: END; 01..AF:
+ *            slices; anything else: other_codes.
+ *     H264   code & 0x80: bad_codes.  t = code & 31: 1 or 5 with head >> 31 set (first_mb_in_slice = 0): PICTURE, KEY when t = 5, detail
+ *            from slice_type, the ue(v) in the 7 bits behind that bit (0 to 3 leading zeros, values 0..14): mod 5 = 0 P, 1 B, 2 I; SP, SI,
+ *            values above 9 and more leading zeros give 0.  1 or 5 with the bit clear: slices.  7: SEQUENCE; 8: PARAM; 9: AUD; 10 or 11:
+ *            END; anything else: other_codes.
+ *     H265   code & 0x80, or head >> 24 & 7 = 0 (nuh_temporal_id_plus1): bad_codes.  t = code >> 1 & 63: 0..9 or 16..21 with head >> 23 & 1
+ *            set (first_slice_segment_in_pic_flag): PICTURE, t >= 16: KEY and detail I, else detail 0; with the bit clear: slices.
+ *            33: SEQUENCE; 32 or 34: PARAM; 35: AUD; 36 or 37: END; anything else: other_codes.
+ *   Row: `packet` of a code row is the packet that holds the window's LAST byte.  RESYNC is set on the first row a slot issues after
+ *     `lost` was set, and clears it.  Order: by packet in input order across the slots; within a packet the PES row first, then the code
+ *     rows by the completing byte's place.  The join: a code belongs to the last PES row of its slot, in row order, whose es_offset is <=
+ *     its own -- per-picture PTS and picture sizes (differences of es_offset) without any carried timestamp.  The table holds the first
+ *     max_rows rows of a call; out_rows[] carries the true count, rows_dropped accumulates the excess, the counters cover everything.
+ *   State survives from call to call.  reset forgets it (positions and counters too; the watches stay).
+ *   Limits: max_packets <= 4096 per stream and call, as in the PES bank: the banks chain on the same buffers.  Memory (device banks) per
+ *     stream: 384 bytes of state, 128 of watches, 48 bytes per row of max_rows and a call record of 1680 bytes.
+ *   NOT done: reassembly of split PES headers; parsing behind the four head bytes (SPS sizes, slice types of H.265, SEI); removal of
+ *     emulation-prevention bytes; audio; copying pictures out. */
+typedef struct dvbs2gpu_es dvbs2gpu_es;
+int dvbs2gpu_es_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_es** out);
+/* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_es_work only */
+int dvbs2gpu_es_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_es** out);
+int dvbs2gpu_es_reset(dvbs2gpu_es* b);
+void dvbs2gpu_es_destroy(dvbs2gpu_es* b);
+#define DVBS2GPU_ES_MPEG2 1
+#define DVBS2GPU_ES_H264 2
+#define DVBS2GPU_ES_H265 3
+/* slot 0..15; pid 0..0x1FFE with a codec, or -1: the slot watches nothing (the codec is ignored) */
+int dvbs2gpu_es_set_watch(dvbs2gpu_es* b, int stream, int slot, int pid, int codec);
+/* d_ts[i]: DEVICE pointer to nbytes[i] bytes (a multiple of 188, at most 188*max_packets) of stream i, of any alignment.  out_rows
+ * (host, may be NULL): the rows of the call per stream, of which the table holds the first max_rows.  One kernel launch.
+ * Synchronous on `stream`; chained behind a packetiser or monitor call on the same stream, no packet visits the host. */
+int dvbs2gpu_es_process_batch(dvbs2gpu_es* b, const uint8_t* const* d_ts, const int* nbytes, int* out_rows, void* stream);
+/* one stream of any bank with a HOST buffer: returns the rows of the call or a negative error.  The other streams of the bank receive
+ * an empty call. */
+int dvbs2gpu_es_work(dvbs2gpu_es* b, int stream, const uint8_t* h_ts, int nbytes);
+typedef struct dvbs2gpu_es_stats {             /* of a slot, since creation, reset or the slot's last set_watch; kept on the host */
+    int64_t packets;                 /* trusted packets of the watched PID, duplicates among them */
+    int64_t payload_bytes, es_bytes, bytes_unsynced, duplicates, cc_errors, scrambled_packets, malformed_packets, resets;
+    int64_t pes_starts, pes_invalid, split_headers;
+    int64_t codes;                   /* every code found; the sum of the counters from `pictures` on but the four picture kinds */
+    int64_t pictures, pictures_i, pictures_p, pictures_b, key_pictures;
+    int64_t sequences, gops, params, auds, ends, slices, other_codes, bad_codes;
+} dvbs2gpu_es_stats;
+/* slot -1: the sum over the stream's slots */
+int dvbs2gpu_es_get_stats(dvbs2gpu_es* b, int stream, int slot, dvbs2gpu_es_stats* h_out);
+typedef struct dvbs2gpu_es_stream_stats {
+    int64_t packets;                 /* every 188 bytes handed in: the position of the next packet */
+    int64_t rows_dropped;
+} dvbs2gpu_es_stream_stats;
+int dvbs2gpu_es_get_stream_stats(dvbs2gpu_es* b, int stream, dvbs2gpu_es_stream_stats* h_out);
+#define DVBS2GPU_ES_UNIT_PES 0
+#define DVBS2GPU_ES_UNIT_PICTURE 1
+#define DVBS2GPU_ES_UNIT_SEQUENCE 2
+#define DVBS2GPU_ES_UNIT_GOP 3
+#define DVBS2GPU_ES_UNIT_PARAM 4
+#define DVBS2GPU_ES_UNIT_AUD 5
+#define DVBS2GPU_ES_UNIT_END 6
+#define DVBS2GPU_ES_KEY 1
+#define DVBS2GPU_ES_RESYNC 2
+#define DVBS2GPU_ES_UNSYNCED 4
+#define DVBS2GPU_ES_SPLIT_HEADER 8
+#pragma pack(push, 4)
+typedef struct dvbs2gpu_es_row {               /* 48 bytes */
+    uint16_t pid;                    /* offset 0 */
+    uint8_t slot, unit;              /* 2, 3: DVBS2GPU_ES_UNIT_PES .. DVBS2GPU_ES_UNIT_END */
+    uint8_t code;                    /* 4: the code byte; PES rows: stream_id */
+    uint8_t detail;                  /* 5: the picture type (1 I, 2 P, 3 B, 0 unknown); PES rows: the PES bank's kind */
+    uint16_t flags;                  /* 6 */
+    int32_t packet;                  /* 8: index in this call of the packet that holds the window's last byte; PES rows: the start */
+    uint32_t head;                   /* 12: the four bytes behind the code byte; PES rows: PES_packet_length */
+    uint64_t es_offset;              /* 16: of the code's first byte; PES rows: es_count before the start's segment */
+    uint64_t pts, dts;               /* 24, 32: PES rows; all ones: absent, and in code rows */
+    uint64_t reserved;               /* 40 */
+} dvbs2gpu_es_row;
+#pragma pack(pop)
+/* h_rows[cap] (host); *n = rows of the last call in the table, of which min(*n, cap) are written */
+int dvbs2gpu_es_get_row_table(dvbs2gpu_es* b, int stream, dvbs2gpu_es_row* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_es_get_row_table_device(dvbs2gpu_es* b, int stream, const dvbs2gpu_es_row** d_rows, int* n);
+
 /* ------------------------------------------------------------------ T2-MI bank (own extension)
  * Nothing in the reference does this.  A DVB-S2 carrier may carry a T2-MI stream (ETSI TS 102 773, the DVB-T2 modulator interface) on
  * one PID of an otherwise empty transport stream; the services lie one level down, in the DVB-T2 BBFRAMEs that the T2-MI packets hold.

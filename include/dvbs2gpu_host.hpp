@@ -823,6 +823,107 @@ private:
     int status_ = 0;
     std::string error_;
 };
+/* ES bank for one transport stream (dvbs2gpu_es_*, include/dvbs2gpu.h; an extension): a picture, GOP and parameter-set index of up to
+ * 16 watched video PIDs (MPEG-2, H.264, H.265) behind BBFrameTSParser, DVBSDemod or TSMonitor, one row per PES packet start and per
+ * reported start code.  init() (a device bank) or initHost() (the library's host implementation, no device) and the setters throw;
+ * work() sits in the data path and does NOT throw: a failing call returns 0 and leaves its code in status() and its text in error(),
+ * sticky until clearStatus(). */
+class EsBank {
+public:
+    EsBank() {}
+    ~EsBank() {
+        if (h) dvbs2gpu_es_destroy(h);
+    }
+    EsBank(const EsBank&) = delete;
+    EsBank& operator=(const EsBank&) = delete;
+
+    void init(int max_packets, int max_rows, int device = 0) {
+        release();
+        eng = Engine::get(device);
+        check(dvbs2gpu_es_create(eng->ctx, 1, max_packets, max_rows, &h));
+    }
+    void initHost(int max_packets, int max_rows) {
+        release();
+        check(dvbs2gpu_es_create_host(1, max_packets, max_rows, &h));
+    }
+    void reset() { check(dvbs2gpu_es_reset(need())); }
+    /* slot 0..15; pid -1 clears the slot; codec DVBS2GPU_ES_MPEG2, _H264 or _H265 */
+    void setWatch(int slot, int pid, int codec = 0) {
+        check(dvbs2gpu_es_set_watch(need(), 0, slot, pid, codec));
+        watched[slot] = pid;
+    }
+    /* the codec of a PMT stream_type: 0x01 / 0x02 MPEG2, 0x1B H264, 0x24 H265, 0: none of them */
+    static int codecOf(int stream_type) {
+        return stream_type == 0x01 || stream_type == 0x02 ? DVBS2GPU_ES_MPEG2 : stream_type == 0x1B ? DVBS2GPU_ES_H264 : stream_type == 0x24 ? DVBS2GPU_ES_H265 : 0;
+    }
+    /* watches the video PIDs of the PMTs that `psi` holds decoded, in free slots, in the order of its slots and then of each PMT's
+     * elementary streams; other stream types and PIDs watched already are skipped; returns the PIDs that found no free slot */
+    std::vector<int> followPmts(PsiBank& psi) {
+        std::vector<int> left;
+        for (int slot = 0; slot < 16; ++slot) {
+            dvbs2gpu_psi_pmt pmt;
+            const std::vector<dvbs2gpu_psi_es> es = psi.programMap(slot, &pmt);
+            if (pmt.program_number < 0) continue;
+            for (const dvbs2gpu_psi_es& e : es) {
+                const int pid = e.elementary_pid, codec = codecOf(e.stream_type);
+                if (!codec || pid >= 0x1FFF || std::find(watched, watched + 16, pid) != watched + 16 || std::find(left.begin(), left.end(), pid) != left.end())
+                    continue;
+                int* free_slot = std::find(watched, watched + 16, -1);
+                if (free_slot == watched + 16) left.push_back(pid);
+                else setWatch((int)(free_slot - watched), pid, codec);
+            }
+        }
+        return left;
+    }
+    /* nbytes of whole TS packets in; returns the rows of the call, 0 on failure (see status()) */
+    int work(const uint8_t* ts, int nbytes) noexcept {
+        const int n = h ? dvbs2gpu_es_work(h, 0, ts, nbytes) : DVBS2GPU_ERR_ARG;
+        if (n >= 0) return n;
+        if (status_ == 0) {
+            status_ = n;
+            try { error_ = h ? dvbs2gpu_last_error() : "EsBank used before init()"; } catch (...) {}
+        }
+        return 0;
+    }
+    int status() const { return status_; }
+    const std::string& error() const { return error_; }
+    void clearStatus() { status_ = 0; error_.clear(); }
+
+    dvbs2gpu_es_stats stats(int slot = -1) {
+        dvbs2gpu_es_stats s;
+        check(dvbs2gpu_es_get_stats(need(), 0, slot, &s));
+        return s;
+    }
+    dvbs2gpu_es_stream_stats streamStats() {
+        dvbs2gpu_es_stream_stats s;
+        check(dvbs2gpu_es_get_stream_stats(need(), 0, &s));
+        return s;
+    }
+    /* the rows of the last work(), in row order (the first max_rows) */
+    std::vector<dvbs2gpu_es_row> rows() {
+        int n = 0;
+        check(dvbs2gpu_es_get_row_table(need(), 0, nullptr, 0, &n));
+        std::vector<dvbs2gpu_es_row> r((size_t)n);
+        if (n > 0) check(dvbs2gpu_es_get_row_table(h, 0, r.data(), n, &n));
+        return r;
+    }
+
+private:
+    void release() {
+        if (h) dvbs2gpu_es_destroy(h);
+        h = nullptr;
+        std::fill(watched, watched + 16, -1);
+    }
+    dvbs2gpu_es* need() {
+        if (!h) throw std::runtime_error("dvbs2gpu: EsBank used before init()");
+        return h;
+    }
+    std::shared_ptr<Engine> eng;
+    dvbs2gpu_es* h = nullptr;
+    int watched[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // slot -> PID, as setWatch left them
+    int status_ = 0;
+    std::string error_;
+};
 /* T2-MI bank for one transport stream (dvbs2gpu_t2mi_*, include/dvbs2gpu.h; an extension): the T2-MI packets of a PID behind
  * BBFrameTSParser or TSMonitor are reassembled and checked, and the DVB-T2 BBFRAMEs of the chosen PLP laid back to back for a second
  * BBFrameTSParser in mode-adaptation mode (feed()).  Four slots, each a (PID, PLP) pair and a reassembler of its own.  init() (a device

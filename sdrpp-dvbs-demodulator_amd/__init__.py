@@ -185,6 +185,26 @@ class PesRow(C.Structure):
                 ('closed_packets', C.c_uint32), ('delta_packets', C.c_uint32), ('delta_ts', C.c_int32)]
 
 
+class EsStats(C.Structure):
+    """dvbs2gpu_es_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('packets', 'payload_bytes', 'es_bytes', 'bytes_unsynced', 'duplicates', 'cc_errors', 'scrambled_packets',
+                                         'malformed_packets', 'resets', 'pes_starts', 'pes_invalid', 'split_headers', 'codes', 'pictures', 'pictures_i',
+                                         'pictures_p', 'pictures_b', 'key_pictures', 'sequences', 'gops', 'params', 'auds', 'ends', 'slices', 'other_codes',
+                                         'bad_codes')]
+
+
+class EsStreamStats(C.Structure):
+    """dvbs2gpu_es_stream_stats"""
+    _fields_ = [('packets', C.c_int64), ('rows_dropped', C.c_int64)]
+
+
+class EsRow(C.Structure):
+    """dvbs2gpu_es_row"""
+    _pack_ = 4
+    _fields_ = [('pid', C.c_uint16), ('slot', C.c_uint8), ('unit', C.c_uint8), ('code', C.c_uint8), ('detail', C.c_uint8), ('flags', C.c_uint16),
+                ('packet', C.c_int32), ('head', C.c_uint32), ('es_offset', C.c_uint64), ('pts', C.c_uint64), ('dts', C.c_uint64), ('reserved', C.c_uint64)]
+
+
 class T2miLayout(C.Structure):
     """dvbs2gpu_t2mi_layout"""
     _fields_ = [(k, C.c_int32) for k in ('header_bytes', 'crc_bytes', 'min_packet_bytes', 'max_packet_bytes', 'bbframe_type', 'bbframe_prefix_bytes',
@@ -473,6 +493,17 @@ PROTOTYPES = {
     'dvbs2gpu_pes_get_stream_stats': (_i, [_vp, _i, C.POINTER(PesStreamStats)]),
     'dvbs2gpu_pes_get_row_table': (_i, [_vp, _i, C.POINTER(PesRow), _i, C.POINTER(_i)]),
     'dvbs2gpu_pes_get_row_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
+    'dvbs2gpu_es_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_es_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_es_reset': (_i, [_vp]),
+    'dvbs2gpu_es_destroy': (None, [_vp]),
+    'dvbs2gpu_es_set_watch': (_i, [_vp, _i, _i, _i, _i]),
+    'dvbs2gpu_es_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _vp]),
+    'dvbs2gpu_es_work': (_i, [_vp, _i, _vp, _i]),
+    'dvbs2gpu_es_get_stats': (_i, [_vp, _i, _i, C.POINTER(EsStats)]),
+    'dvbs2gpu_es_get_stream_stats': (_i, [_vp, _i, C.POINTER(EsStreamStats)]),
+    'dvbs2gpu_es_get_row_table': (_i, [_vp, _i, C.POINTER(EsRow), _i, C.POINTER(_i)]),
+    'dvbs2gpu_es_get_row_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
     'dvbs2gpu_t2mi_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
     'dvbs2gpu_t2mi_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
     'dvbs2gpu_t2mi_reset': (_i, [_vp]),
@@ -1831,6 +1862,102 @@ class PesBank(_TsBank):
         """(device pointer or None, rows): the same table as dvbs2gpu_pes_row records in HBM, valid until the next call"""
         p, n = C.c_void_p(), C.c_int()
         self._check(self.lib.dvbs2gpu_pes_get_row_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+
+class EsBank(_TsBank):
+    """ES bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, ES bank): every payload byte of up to 16 watched video
+    PIDs per stream is scanned for start codes; one table row per PES packet start and per picture, sequence header / SPS, GOP header,
+    parameter set, access unit delimiter and sequence end, with its position in the elementary stream."""
+    _destroy = 'dvbs2gpu_es_destroy'
+    SLOTS = 16
+    MPEG2, H264, H265 = 1, 2, 3
+    PES, PICTURE, SEQUENCE, GOP, PARAM, AUD, END = range(7)
+    PIC_I, PIC_P, PIC_B = 1, 2, 3
+    KEY, RESYNC, UNSYNCED, SPLIT_HEADER = 1, 2, 4, 8
+    NO_TS = (1 << 64) - 1
+    STREAM_TYPE_CODECS = {0x01: 1, 0x02: 1, 0x1B: 2, 0x24: 3}       # PMT stream_type -> codec
+    ROW_KEYS = tuple(k for k, _ in EsRow._fields_)
+
+    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=4096):
+        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
+        h = C.c_void_p()
+        engine._check(self.lib.dvbs2gpu_es_create(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
+        self.h = h
+        self._watched = [{} for _ in range(nstreams)]               # per stream: slot -> (PID, codec), as set_watch left them
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096, max_rows=4096):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        self = cls._host('dvbs2gpu_es_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
+        self._watched = [{} for _ in range(nstreams)]
+        return self
+
+    def reset(self):
+        """forgets states, positions and counters; the watches stay"""
+        self._check(self.lib.dvbs2gpu_es_reset(self.h))
+
+    def set_watch(self, stream, slot, pid, codec=0):
+        """pid -1 clears the slot; the slot starts afresh"""
+        self._check(self.lib.dvbs2gpu_es_set_watch(self.h, int(stream), int(slot), int(pid), int(codec)))
+        self._watched[int(stream)].pop(int(slot), None)
+        if pid >= 0:
+            self._watched[int(stream)][int(slot)] = (int(pid), int(codec))
+
+    def follow_pmts(self, psi_bank, stream=0):
+        """watches the video PIDs of the PMTs that `psi_bank` (a PsiBank that read the same stream) holds decoded -- stream types 0x01 and
+        0x02 as MPEG2, 0x1B as H264, 0x24 as H265, everything else skipped -- in free slots, in the order of its slots and then of each
+        PMT's elementary streams; PIDs watched already are skipped -> the PIDs that found no free slot"""
+        watched = self._watched[int(stream)]
+        left = []
+        for slot in range(psi_bank.SLOTS):
+            hdr, es = psi_bank.program_map(stream, slot)
+            if hdr['program_number'] < 0:
+                continue
+            for stream_type, pid in es:
+                codec = self.STREAM_TYPE_CODECS.get(stream_type)
+                if codec is None or pid >= 0x1FFF or pid in [p for p, _ in watched.values()] or pid in left:
+                    continue
+                free = [s for s in range(self.SLOTS) if s not in watched]
+                if free:
+                    self.set_watch(stream, free[0], pid, codec)
+                else:
+                    left.append(pid)
+        return left
+
+    def process(self, ts_tensors, nbytes=None):
+        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all), of any alignment -> the rows of the
+        call per stream (the table holds the first max_rows of them)"""
+        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
+        nr = (C.c_int * self.nstreams)()
+        self._check(self.lib.dvbs2gpu_es_process_batch(self.h, pin, cnt, nr, self.eng._stream()))
+        return list(nr)
+
+    def work(self, ts, stream=0):
+        """one stream, a host buffer: numpy uint8 packets in -> the rows of the call"""
+        import numpy as np
+        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
+        return self._check(self.lib.dvbs2gpu_es_work(self.h, int(stream), C.c_void_p(ts.ctypes.data), ts.size))
+
+    def stats(self, stream=0, slot=-1):
+        st = EsStats()
+        self._check(self.lib.dvbs2gpu_es_get_stats(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in EsStats._fields_}
+
+    def stream_stats(self, stream=0):
+        st = EsStreamStats()
+        self._check(self.lib.dvbs2gpu_es_get_stream_stats(self.h, int(stream), C.byref(st)))
+        return dict(packets=int(st.packets), rows_dropped=int(st.rows_dropped))
+
+    def rows(self, stream=0):
+        """one dict per row of the last call (the fields of dvbs2gpu_es_row but `reserved`), in row order"""
+        rows = self._rows(self.lib.dvbs2gpu_es_get_row_table, EsRow, int(stream))
+        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS if k != 'reserved'} for r in rows]
+
+    def rows_device(self, stream=0):
+        """(device pointer or None, rows): the same table as dvbs2gpu_es_row records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self.lib.dvbs2gpu_es_get_row_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
         return p.value, n.value
 
 

@@ -1,0 +1,526 @@
+// ES bank (own extension; include/dvbs2gpu.h): picture, GOP and parameter-set index of up to 16 watched video PIDs
+// (MPEG-2, H.264, H.265) of each of `nstreams` transport streams in HBM -- the first TS bank that reads every payload byte.  Every rule
+// is in es_rules.h, whose EsHostStream is the sequential definition, the host bank and the kernel's yardstick; this file says how a
+// call's packets and their bytes are taken in parallel.
+//
+// What makes the parallel form possible: whether a slot is synced in front of a packet is the validity of its last start; with it every
+// packet's segment of ES bytes is known from its own bytes, so a segment's ES position is a prefix sum and the bytes since the last
+// reset a difference of two prefix values; and a code is a pure function of the last 8 ES bytes, so the lane of a packet needs, beside
+// its own segment, only the 7 bytes in front of it, which lie at the END of the slot's previous non-empty segments.
+//
+//   es_kernel  one workgroup per stream, one launch per call.
+//     A-C  ts_watch.h, shared with the PES bank: the trusted packets of watched PIDs as one word each, sorted by slot, with the
+//        continuity verdict.
+//     D  the lanes that own starts read the first payload bytes (pw_load_start) and apply es_packet_plan: valid or not into the word,
+//        the segment's length into LDS.
+//     E  a maximum scan gives every packet its slot's last start (synced = that start was valid, or the carried bit), so every packet's
+//        segment length is known; one prefix sum over them gives the ES positions; two more maximum scans give the last packet with a
+//        reset mark and the last non-empty segment before a packet.
+//     F  every lane rolls the 64-bit window over its packets' segments (dwords at fixed places inside the packet), starting from the 7
+//        bytes in front: at most 7 hops back over non-empty segments (a payload may be one byte), then the carried tail.  Codes are
+//        counted and classified, rows counted per packet.
+//     G  a prefix sum over the rows per packet in INPUT order gives every packet its place in the table; a maximum scan the slot's last
+//        row-bearing packet before one (RESYNC: a reset mark behind it).  The PES rows are written; a packet with code rows is scanned
+//        once more to write them.  The lane of the slot's last packet writes the slot's new state.
+// No lane walks over packets of other lanes beyond the 7 hops: the cost of a call does not depend on what the packets say, but for the
+// second scan of packets that hold codes with rows.  One device-to-host copy of the per-stream call record (EsCall).
+// Vector stores and plain C++ only.
+#include "ts_watch.h"
+#include "es_rules.h"
+
+using namespace s2;
+#define g_err last_error()
+
+namespace s2 {
+
+constexpr int ES_MAX_PACKETS = PW_MAX_PACKETS;             // per stream and call: 10 bytes of LDS per packet
+constexpr int ES_WG = 256;
+static_assert(sizeof(EsRow) == sizeof(dvbs2gpu_es_row) && sizeof(EsRow) == 48, "row layout");
+static_assert(sizeof(EsCnt) * 2 == sizeof(dvbs2gpu_es_stats), "stats order");
+static_assert(sizeof(EsState) == 24, "state layout");
+static_assert(ES_MAX_PACKETS <= 16 * ES_WG, "a thread's verdicts are 16 bits of a mask, its slot counts 16-bit words (ts_thread_run)");
+static_assert(ES_MAX_PACKETS * (TSMON_TS - 4) < (1 << 20), "the prefix sum of segment bytes in an int");
+static_assert(ES_MPEG2 == DVBS2GPU_ES_MPEG2 && ES_H264 == DVBS2GPU_ES_H264 && ES_H265 == DVBS2GPU_ES_H265, "public values");
+static_assert(ES_PES == DVBS2GPU_ES_UNIT_PES && ES_PICTURE == DVBS2GPU_ES_UNIT_PICTURE && ES_END == DVBS2GPU_ES_UNIT_END, "public values");
+static_assert(ES_KEY == DVBS2GPU_ES_KEY && ES_RESYNC == DVBS2GPU_ES_RESYNC && ES_UNSYNCED == DVBS2GPU_ES_UNSYNCED && ES_SPLIT_HEADER == DVBS2GPU_ES_SPLIT_HEADER, "public values");
+
+struct EsCall { EsCallHead head; EsCnt cnt[ES_SLOTS]; };
+
+// behind phase D bit 18 of a start's word says that the start is valid
+constexpr uint32_t PW_VALID = 1u << 18;
+__device__ inline bool es_invalid_start(uint32_t e) { return pw_start(e) && !(e & PW_VALID); }
+// the packet's reset in front of its row and segment; its reset mark (an invalid start resets once more, behind its row)
+__device__ inline bool es_reset_front(uint32_t e) { return (e & PW_GAP) || (pw_counts(e) && pw_scr(e)); }
+__device__ inline bool es_reset_mark(uint32_t e) { return es_reset_front(e) || es_invalid_start(e); }
+constexpr uint16_t ES_NO_PREV = 0xFFFF;
+
+// what the kernel keeps in LDS beside the packets; a multiple of 16 bytes in front of them
+struct alignas(16) EsShared {
+    EsCnt cnt[ES_SLOTS];
+    EsState ss[ES_SLOTS];                        // the slots' states before the call
+    uint16_t place[ES_SLOTS][ES_WG];             // the counting sort's counts, then places; behind the sort the last non-empty segment before each sorted packet
+    int32_t tbase[ES_WG];                        // the rows in front of a thread's run of input packets
+    int32_t w[ES_SLOTS], codec[ES_SLOTS];
+    int32_t start[ES_SLOTS + 1];                 // the slots' runs in sorted order
+    int32_t wsum[ES_WG / 64];
+    uint8_t ncc[ES_SLOTS];                       // the slots' continuity bytes behind the call
+    int64_t pos0;
+};
+static_assert(sizeof(EsShared) % 16 == 0 && sizeof(EsShared::place) == ES_MAX_PACKETS * sizeof(uint16_t), "the packets behind it; an index per packet");
+// dynamic LDS: EsShared, srt[max_packets], exs[max_packets + 1] (32 bits each), rc[max_packets] (16 bits)
+constexpr size_t es_lds_bytes(int max_packets) { return sizeof(EsShared) + ((size_t)max_packets * 2 + 2) * sizeof(uint32_t) + (((size_t)max_packets + 1) & ~(size_t)1) * sizeof(uint16_t); }
+static_assert(es_lds_bytes(ES_MAX_PACKETS) <= 64 * 1024, "dynamic LDS of a workgroup");
+
+__device__ inline void es_flush(EsCnt* d, const EsCnt& a) {
+#define ES_ADD(f) if (a.f) atomicAdd(&d->f, a.f)
+    ES_ADD(es_bytes); ES_ADD(bytes_unsynced); ES_ADD(resets); ES_ADD(pes_starts); ES_ADD(pes_invalid); ES_ADD(split_headers);
+    ES_ADD(codes); ES_ADD(pictures); ES_ADD(pictures_i); ES_ADD(pictures_p); ES_ADD(pictures_b); ES_ADD(key_pictures); ES_ADD(sequences); ES_ADD(gops);
+    ES_ADD(params); ES_ADD(auds); ES_ADD(ends); ES_ADD(slices); ES_ADD(other_codes); ES_ADD(bad_codes);
+#undef ES_ADD
+}
+// the packet counters of phase C, per thread and slot run
+__device__ inline void es_flush_pk(EsCnt* d, const PwPk& a) {
+    atomicAdd(&d->packets, a.packets);
+    if (a.payload_bytes) atomicAdd(&d->payload_bytes, a.payload_bytes);
+    if (a.duplicates) atomicAdd(&d->duplicates, a.duplicates);
+    if (a.cc_errors) atomicAdd(&d->cc_errors, a.cc_errors);
+    if (a.scrambled) atomicAdd(&d->scrambled_packets, a.scrambled);
+    if (a.malformed) atomicAdd(&d->malformed_packets, a.malformed);
+}
+// counters summed per thread and slot run
+struct EsAcc {
+    EsCnt c; int slot; EsCnt* dst;
+    __device__ EsAcc(EsCnt* d) : c(es_cnt_zero()), slot(-1), dst(d) {}
+    __device__ void at(int s) { if (s != slot) { done(); c = es_cnt_zero(); slot = s; } }
+    __device__ void done() { if (slot >= 0) es_flush(&dst[slot], c); slot = -1; }
+};
+
+// the last 8 bytes of packet k, the packet's last byte in the low byte: two dwords that lie inside the packet
+__device__ inline uint64_t es_packet_end(const uint8_t* __restrict__ ts, int k) {
+    const uint8_t* p = ts + (size_t)k * TSMON_TS + TSMON_TS - 8;
+    const uint32_t lo = *reinterpret_cast<const ts_unaligned_u32*>(p), hi = *reinterpret_cast<const ts_unaligned_u32*>(p + 4);
+    return (uint64_t)__builtin_bswap32(lo) << 32 | __builtin_bswap32(hi);
+}
+__device__ inline uint64_t es_low_bytes(uint64_t v, int t) { return t >= 8 ? v : v & ((1ull << (8 * t)) - 1); }
+
+// The segment of the packet k: its last `len` bytes, at ES position `pos`, scanned from the window (win, since) in front of it.  The
+// dwords are read at multiples of 4 inside the packet.  ROWS false: the codes are counted into *c -> the codes with a row.  ROWS
+// true: the rows are written at rows[rank ..] below max_rows, the first with RESYNC if `lost` -> the codes with a row
+template <bool ROWS>
+__device__ inline int es_scan_segment(const uint8_t* __restrict__ ts, int k, int len, uint64_t pos, uint64_t win, uint32_t since, int codec, EsCnt* c, int pid, int slot,
+                                      bool lost, EsRow* rows, int rank, int max_rows) {
+    const uint8_t* p = ts + (size_t)k * TSMON_TS;
+    const int a = TSMON_TS - len;
+    int nrows = 0;
+    for (int d = a >> 2; d < TSMON_TS / 4; ++d) {
+        const uint32_t v = *reinterpret_cast<const ts_unaligned_u32*>(p + 4 * d);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int idx = 4 * d + b;
+            if (idx < a) continue;
+            uint32_t code, head;
+            if (!es_scan_byte(&win, &since, v >> (8 * b) & 255, &code, &head)) continue;
+            const EsCode e = es_classify(codec, code, head);
+            if (!ROWS) es_cnt_code(c, e);
+            if (e.unit >= ES_UNITS) continue;
+            if (ROWS) {
+                if (rank + nrows < max_rows) rows[rank + nrows] = es_code_row(pid, slot, k, e, code, head, pos + (uint64_t)(idx - a) - 7, lost);
+                lost = false;
+            }
+            ++nrows;
+        }
+    }
+    return nrows;
+}
+
+__global__ void __launch_bounds__(ES_WG) es_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nbytes, int max_packets, int max_rows,
+                                                   const int32_t* __restrict__ watch, const int32_t* __restrict__ codec, EsState* __restrict__ state,
+                                                   int64_t* __restrict__ pos, EsRow* __restrict__ rows_g, EsCall* __restrict__ call) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char es_lds[];
+    EsShared& sh = *reinterpret_cast<EsShared*>(es_lds);
+    uint32_t* srt = reinterpret_cast<uint32_t*>(es_lds + sizeof(EsShared));
+    uint32_t* exs = srt + max_packets;               // a segment's length, then the exclusive prefix: the ES bytes of the call in front of it
+    uint16_t* rc = reinterpret_cast<uint16_t*>(exs + max_packets + 2);   // rows per INPUT packet
+    uint32_t* rec = exs;
+    uint16_t* prevne = &sh.place[0][0];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    int n = nbytes[s] / TSMON_TS;
+    if (n > max_packets) n = max_packets;            // (the host has refused such a call)
+    if (tid < ES_SLOTS) {
+        sh.w[tid] = watch[(size_t)s * ES_SLOTS + tid];
+        sh.codec[tid] = codec[(size_t)s * ES_SLOTS + tid];
+        sh.ss[tid] = state[(size_t)s * ES_SLOTS + tid];
+        sh.cnt[tid] = es_cnt_zero();
+    }
+    for (int k = tid; k < n; k += ES_WG) rc[k] = 0;
+    if (tid == 0) sh.pos0 = pos[s];
+    __syncthreads();
+    const uint8_t* ts = in[s];
+    // A: the watched packets, compacted in input order
+    const int W = pw_compact<ES_WG>(ts, n, sh.w, sh.wsum, rec);
+    int nrows = 0;
+    if (W > 0) {
+        // B: the stable counting sort by slot
+        int j0, j1;
+        pw_sort<ES_WG>(rec, srt, W, sh.place, sh.start, sh.wsum, &j0, &j1);
+        // C: the continuity verdicts
+        unsigned dupm, gapm;
+        pw_verdicts(srt, j0, j1, sh.start, [&](int slot) { return sh.ss[slot].cc; }, sh.wsum, sh.ncc,
+                    [&](int slot, const PwPk& pk) { es_flush_pk(&sh.cnt[slot], pk); }, &dupm, &gapm);
+        __syncthreads();                                         // every counter has been read: the verdicts take their bits
+        EsAcc acc(sh.cnt);
+        // D: the starts: valid or not, and their segments
+        int last_start = -1;
+        for (int j = j0; j < j1; ++j) {
+            uint32_t e = pw_with_verdict(srt[j], dupm >> (j - j0) & 1, gapm >> (j - j0) & 1);
+            if (pw_start(e)) {
+                uint32_t w5[5];
+                pw_load_start(ts, e, w5);
+                const EsPlan pl = es_packet_plan(w5, pw_len(e), pw_scr(e), 1, false, false);
+                if (pl.valid) e |= PW_VALID;
+                exs[j] = (uint32_t)pl.seg_len;
+                acc.at(pw_slot(e));
+                es_cnt_start(&acc.c, pl);
+                last_start = j;
+            }
+            srt[j] = e;
+        }
+        __syncthreads();
+        const int ls0 = ts_block_scan_max(last_start, sh.wsum);   // the last sorted start before the thread's run
+        // the slot's synced bit behind its start ls (or none in this call)
+        auto synced_at = [&](int slot, int ls) { return ls >= sh.start[slot] ? (srt[ls] & PW_VALID) != 0 : sh.ss[slot].synced != 0; };
+        // E: the segment lengths, the reset marks
+        int lr0 = -1, ne0 = -1;
+        {
+            int ls = ls0, sum = 0, lr = -1, ne = -1;
+            for (int j = j0; j < j1; ++j) {
+                const uint32_t e = srt[j];
+                const int slot = pw_slot(e);
+                acc.at(slot);
+                int len = 0;
+                if (pw_start(e)) { len = (int)exs[j]; ls = j; }
+                else if (pw_counts(e) && !pw_scr(e)) {
+                    if (synced_at(slot, ls)) len = pw_len(e); else acc.c.bytes_unsynced += pw_len(e);
+                }
+                exs[j] = (uint32_t)len;
+                sum += len;
+                acc.c.es_bytes += len;
+                if (es_reset_mark(e)) { lr = j; ++acc.c.resets; }
+                if (len > 0) ne = j;
+            }
+            int total;
+            int at = ts_block_scan<ES_WG>(sum, sh.wsum, &total);
+            lr0 = ts_block_scan_max(lr, sh.wsum);                // the last sorted packet with a reset mark before the run,
+            ne0 = ts_block_scan_max(ne, sh.wsum);                // and the last one with a non-empty segment
+            ne = ne0;
+            for (int j = j0; j < j1; ++j) {
+                const int len = (int)exs[j];
+                exs[j] = (uint32_t)at; at += len;
+                prevne[j] = ne >= 0 ? (uint16_t)ne : ES_NO_PREV;
+                if (len > 0) ne = j;
+            }
+            if (tid == 0) exs[W] = (uint32_t)total;
+        }
+        __syncthreads();
+        // the window in front of sorted place j of `slot` (j may be the end of the slot's run): lr the last reset mark before or at j,
+        // pne the last non-empty segment before j
+        auto window = [&](int slot, int j, int lr, int pne, uint64_t* win, uint32_t* since) {
+            const int head = sh.start[slot];
+            const uint32_t sn = lr >= head ? exs[j] - exs[lr] : (uint32_t)sh.ss[slot].have + (exs[j] - exs[head]);
+            const int need = sn < 7 ? (int)sn : 7;
+            uint64_t v = 0;
+            int got = 0, jj = pne;
+            for (int hop = 0; hop < 7 && got < need; ++hop) {
+                if (jj < head) break;
+                const int len = (int)(exs[jj + 1] - exs[jj]), t = len < need - got ? len : need - got;
+                v |= es_low_bytes(es_packet_end(ts, pw_k(srt[jj])), t) << (8 * got);
+                got += t;
+                jj = prevne[jj] == ES_NO_PREV ? -1 : (int)prevne[jj];
+            }
+            if (got < need) v |= es_low_bytes(sh.ss[slot].tail, need - got) << (8 * got);
+            *win = v; *since = (uint32_t)need;
+        };
+        // F: the codes, counted; the rows per packet
+        int last_row = -1;
+        {
+            int lr = lr0, ne = ne0;
+            for (int j = j0; j < j1; ++j) {
+                const uint32_t e = srt[j];
+                const int slot = pw_slot(e), k = pw_k(e), len = (int)(exs[j + 1] - exs[j]);
+                acc.at(slot);
+                if (es_reset_mark(e)) lr = j;
+                int nr = pw_start(e);
+                if (len > 0) {
+                    uint64_t win; uint32_t since;
+                    window(slot, j, lr, ne, &win, &since);
+                    nr += es_scan_segment<false>(ts, k, len, 0, win, since, sh.codec[slot], &acc.c, 0, 0, false, nullptr, 0, 0);
+                    ne = j;
+                }
+                if (nr) { rc[k] = (uint16_t)nr; last_row = j; }
+            }
+        }
+        acc.done();
+        __syncthreads();
+        // G: the rows' places in input order, the slot's last row-bearing packet, the rows and the new states
+        const int chunk = (n + ES_WG - 1) / ES_WG;
+        {
+            int k0, k1; ts_thread_run(n, ES_WG, &k0, &k1);
+            int sum = 0;
+            for (int k = k0; k < k1; ++k) sum += rc[k];
+            sh.tbase[tid] = ts_block_scan<ES_WG>(sum, sh.wsum, &nrows);
+        }
+        int lp = ts_block_scan_max(last_row, sh.wsum);
+        __syncthreads();
+        EsRow* rows = rows_g + (size_t)s * max_rows;
+        int lr = lr0, ne = ne0, ls = ls0;
+        // the slot's lost bit where its last row-bearing packet is p and its last reset mark r (both before the place, -1 or another slot's: none)
+        auto lost_behind = [&](int slot, int p, int r) {
+            const int head = sh.start[slot];
+            if (p >= head) return r > p || (r == p && es_invalid_start(srt[p]));
+            return sh.ss[slot].lost != 0 || r >= head;
+        };
+        for (int j = j0; j < j1; ++j) {
+            const uint32_t e = srt[j];
+            const int slot = pw_slot(e), k = pw_k(e), head = sh.start[slot], len = (int)(exs[j + 1] - exs[j]);
+            const uint64_t es_pos = sh.ss[slot].es_count + (exs[j] - exs[head]);
+            const int nr = rc[k];
+            if (nr) {
+                bool lost = es_reset_front(e) || lost_behind(slot, lp, lr);
+                int rank = sh.tbase[k / chunk];
+                for (int q = (k / chunk) * chunk; q < k; ++q) rank += rc[q];
+                if (pw_start(e)) {
+                    uint32_t w5[5];
+                    pw_load_start(ts, e, w5);
+                    const EsPlan pl = es_packet_plan(w5, pw_len(e), pw_scr(e), 1, false, false);
+                    if (rank < max_rows) rows[rank] = es_pes_row(sh.w[slot], slot, k, pl, es_pos, lost);
+                    lost = false;
+                    ++rank;
+                }
+                if (nr > pw_start(e)) {
+                    uint64_t win; uint32_t since;
+                    window(slot, j, es_reset_mark(e) ? j : lr, ne, &win, &since);
+                    es_scan_segment<true>(ts, k, len, es_pos, win, since, sh.codec[slot], nullptr, sh.w[slot], slot, lost, rows, rank, max_rows);
+                }
+                lp = j;
+            }
+            if (es_reset_mark(e)) lr = j;
+            if (len > 0) ne = j;
+            if (pw_start(e)) ls = j;
+            if (j == sh.start[slot + 1] - 1) {
+                EsState nx = sh.ss[slot];
+                uint64_t win; uint32_t since;
+                window(slot, j + 1, lr, ne, &win, &since);
+                nx.es_count += exs[j + 1] - exs[head];
+                nx.tail = win; nx.have = (uint8_t)since;
+                nx.cc = sh.ncc[slot];
+                nx.synced = synced_at(slot, ls);
+                nx.lost = lost_behind(slot, lp, lr);
+                state[(size_t)s * ES_SLOTS + slot] = nx;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < ES_SLOTS) call[s].cnt[tid] = sh.cnt[tid];
+    if (tid == 0) {
+        call[s].head = EsCallHead{nrows, {0, 0, 0}};
+        pos[s] = sh.pos0 + n;
+    }
+}
+
+}  // namespace s2
+
+struct dvbs2gpu_es {
+    dvbs2gpu_ctx* ctx = nullptr;                   // null: a host-only bank (dvbs2gpu_es_create_host)
+    int nstreams = 0, max_packets = 0, max_rows = 0;
+    std::vector<int32_t> watch, codec;             // nstreams x 16
+    std::vector<dvbs2gpu_es_stats> stats;          // nstreams x 16, since reset; the kernel reports each call's share (EsCall)
+    std::vector<dvbs2gpu_es_stream_stats> sstats;
+    std::vector<int> nrows, total;                 // of the last call per stream: rows in the table, rows in all
+    std::vector<EsCall> h_call;
+    std::vector<char> h_args;
+    // device banks
+    DevBuf<int32_t> d_watch, d_codec;
+    DevBuf<EsState> d_state;
+    DevBuf<int64_t> d_pos;
+    DevBuf<EsRow> d_rows;                          // nstreams x max_rows
+    DevBuf<EsCall> d_call;
+    DevBuf<uint8_t> d_args;                        // TsBankArgs(nstreams)
+    TsHostStage stage;                             // of the host-buffer entry point
+    // host-only banks
+    std::vector<EsHostStream> host;
+};
+
+namespace s2 {
+// one stream's call into its statistics; `n` packets came
+static void es_account(dvbs2gpu_es* b, int i, int n, const EsCallHead& head, const EsCnt* c) {
+    dvbs2gpu_es_stream_stats& ss = b->sstats[i];
+    for (int s = 0; s < ES_SLOTS; ++s) {
+        if (!c[s].packets) continue;                   // (no packet of the slot's PID came: every counter is 0)
+        const int32_t* a = reinterpret_cast<const int32_t*>(&c[s]);
+        int64_t* d = reinterpret_cast<int64_t*>(&b->stats[(size_t)i * ES_SLOTS + s]);
+        for (int k = 0; k < ES_COUNTERS; ++k) d[k] += a[k];
+    }
+    ss.packets += n;
+    if (head.rows > b->max_rows) ss.rows_dropped += head.rows - b->max_rows;
+    b->total[i] = head.rows;
+    b->nrows[i] = head.rows < b->max_rows ? head.rows : b->max_rows;
+}
+static bool es_create_args_ok(int nstreams, int max_packets, int max_rows, dvbs2gpu_es** out) {
+    if (!out || nstreams <= 0 || max_packets <= 0 || max_rows <= 0) return false;
+    if (max_packets > ES_MAX_PACKETS) { g_err = "ES bank: max_packets is at most 4096 per stream and call"; return false; }
+    return true;
+}
+static std::unique_ptr<dvbs2gpu_es> es_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows) {
+    std::unique_ptr<dvbs2gpu_es> b(new dvbs2gpu_es());
+    b->ctx = ctx; b->nstreams = nstreams; b->max_packets = max_packets; b->max_rows = max_rows;
+    b->watch.assign((size_t)nstreams * ES_SLOTS, -1);
+    b->codec.assign((size_t)nstreams * ES_SLOTS, ES_NONE);
+    b->stats.assign((size_t)nstreams * ES_SLOTS, dvbs2gpu_es_stats{});
+    b->sstats.assign(nstreams, dvbs2gpu_es_stream_stats{});
+    b->nrows.assign(nstreams, 0); b->total.assign(nstreams, 0);
+    b->h_call.resize(nstreams);
+    return b;
+}
+}  // namespace s2
+
+extern "C" {
+
+void dvbs2gpu_es_destroy(dvbs2gpu_es* b) { delete b; }
+
+int dvbs2gpu_es_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_es** out) {
+    if (!ctx || !es_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    auto b = es_new(ctx, nstreams, max_packets, max_rows);
+    const size_t n = (size_t)nstreams, ns = n * ES_SLOTS;
+    const char* what = "hipMalloc(es)";                // (zero-filled: the slots' states and the positions; the kernel writes rows and call records before they are read)
+    RC_TRY(b->d_watch.alloc(ns, false, what));
+    HIP_TRY(hipMemcpy(b->d_watch, b->watch.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice));
+    RC_TRY(b->d_codec.alloc(ns, true, what));
+    RC_TRY(b->d_state.alloc(ns, true, what));
+    RC_TRY(b->d_pos.alloc(n, true, what));
+    RC_TRY(b->d_rows.alloc(n * max_rows, false, what));
+    RC_TRY(b->d_call.alloc(n, false, what));
+    RC_TRY(b->d_args.alloc(TsBankArgs(n).L.bytes(), false, what));
+    b->h_args.resize(TsBankArgs(n).L.bytes());
+    *out = b.release();
+    return 0;
+}
+
+int dvbs2gpu_es_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_es** out) {
+    if (!es_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
+    auto b = es_new(nullptr, nstreams, max_packets, max_rows);
+    b->host.resize(nstreams);
+    *out = b.release();
+    return 0;
+}
+
+int dvbs2gpu_es_reset(dvbs2gpu_es* b) {
+    if (!b) return DVBS2GPU_ERR_ARG;
+    if (b->ctx) {
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        HIP_TRY(hipMemset(b->d_state, 0, (size_t)b->nstreams * ES_SLOTS * sizeof(EsState)));
+        HIP_TRY(hipMemset(b->d_pos, 0, (size_t)b->nstreams * sizeof(int64_t)));
+    }
+    for (auto& h : b->host) h.reset();
+    std::fill(b->stats.begin(), b->stats.end(), dvbs2gpu_es_stats{});
+    std::fill(b->sstats.begin(), b->sstats.end(), dvbs2gpu_es_stream_stats{});
+    std::fill(b->nrows.begin(), b->nrows.end(), 0);
+    std::fill(b->total.begin(), b->total.end(), 0);
+    return 0;
+}
+
+int dvbs2gpu_es_set_watch(dvbs2gpu_es* b, int stream, int slot, int pid, int codec) {
+    if (!b || stream < 0 || stream >= b->nstreams || slot < 0 || slot >= ES_SLOTS) return DVBS2GPU_ERR_ARG;
+    if (pid < -1 || pid >= TSMON_NULL_PID) { g_err = "ES bank: a watched PID is 0..0x1FFE (-1 clears the slot)"; return DVBS2GPU_ERR_ARG; }
+    if (pid >= 0 && (codec < ES_MPEG2 || codec > ES_H265)) { g_err = "ES bank: the codec is DVBS2GPU_ES_MPEG2, _H264 or _H265"; return DVBS2GPU_ERR_ARG; }
+    int32_t* w = b->watch.data() + (size_t)stream * ES_SLOTS;
+    for (int s = 0; s < ES_SLOTS; ++s)
+        if (pid >= 0 && s != slot && w[s] == pid) { g_err = "ES bank: the PID is watched in another slot of the stream"; return DVBS2GPU_ERR_ARG; }
+    const size_t at = (size_t)stream * ES_SLOTS + slot;
+    w[slot] = pid;
+    b->codec[at] = pid >= 0 ? codec : ES_NONE;
+    b->stats[at] = dvbs2gpu_es_stats{};
+    if (b->ctx) {
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        HIP_TRY(hipMemcpy(b->d_watch + at, &w[slot], sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b->d_codec + at, &b->codec[at], sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(b->d_state + at, 0, sizeof(EsState)));
+    } else {
+        b->host[stream].watch[slot] = pid;
+        b->host[stream].codec[slot] = b->codec[at];
+        b->host[stream].clear_slot(slot);
+    }
+    return 0;
+}
+
+int dvbs2gpu_es_process_batch(dvbs2gpu_es* b, const uint8_t* const* d_ts, const int* nbytes, int* out_rows, void* stream) {
+    if (!b || !d_ts || !nbytes) return DVBS2GPU_ERR_ARG;
+    if (!b->ctx) { g_err = "ES bank: a host bank takes host buffers (dvbs2gpu_es_work)"; return DVBS2GPU_ERR_ARG; }
+    const int n = b->nstreams;
+    for (int i = 0; i < n; ++i) {
+        if (!ts_bank_check_counts("ES bank: ", nbytes + i, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
+        if (nbytes[i] > 0 && !d_ts[i]) { g_err = "ES bank: null buffer"; return DVBS2GPU_ERR_ARG; }
+    }
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const TsBankArgs a(n);
+    a.fill(b->h_args.data(), n, d_ts, nullptr, nbytes);
+    HIP_TRY(hipMemcpyAsync(b->d_args, b->h_args.data(), b->h_args.size(), hipMemcpyHostToDevice, st));
+    const size_t lds = es_lds_bytes(b->max_packets);       // <= 51.3 KiB
+    hipLaunchKernelGGL(es_kernel, dim3(n), dim3(ES_WG), lds, st, a.in(b->d_args), a.nbytes(b->d_args), b->max_packets, b->max_rows, b->d_watch, b->d_codec, b->d_state,
+                       b->d_pos, b->d_rows, b->d_call);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_call.data(), b->d_call, sizeof(EsCall) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) {
+        es_account(b, i, nbytes[i] / TSMON_TS, b->h_call[i].head, b->h_call[i].cnt);
+        if (out_rows) out_rows[i] = b->total[i];
+    }
+    return 0;
+}
+
+int dvbs2gpu_es_work(dvbs2gpu_es* b, int stream, const uint8_t* h_ts, int nbytes) {
+    if (!b || stream < 0 || stream >= b->nstreams || nbytes < 0 || (nbytes > 0 && !h_ts)) return DVBS2GPU_ERR_ARG;
+    if (!ts_bank_check_counts("ES bank: ", &nbytes, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
+    if (!b->ctx) {
+        for (int i = 0; i < b->nstreams; ++i) {        // the other streams receive an empty call
+            EsHostStream& h = b->host[i];
+            const int np = i == stream ? nbytes / TSMON_TS : 0;
+            h.run(h_ts, np, b->max_rows);
+            es_account(b, i, np, h.head, h.cnt);
+        }
+        return b->total[stream];
+    }
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    const int rc = ts_bank_work(b->stage, b->nstreams, stream, h_ts, nbytes, b->max_packets, nullptr, 0, false, [&](const uint8_t* const* in, const int* nb, uint8_t* const*, int*) {
+        return dvbs2gpu_es_process_batch(b, in, nb, nullptr, nullptr);
+    });
+    return rc < 0 ? rc : b->total[stream];
+}
+
+int dvbs2gpu_es_get_stats(dvbs2gpu_es* b, int stream, int slot, dvbs2gpu_es_stats* h_out) {
+    if (!b || stream < 0 || stream >= b->nstreams || slot < -1 || slot >= ES_SLOTS || !h_out) return DVBS2GPU_ERR_ARG;
+    *h_out = dvbs2gpu_es_stats{};
+    for (int s = slot < 0 ? 0 : slot; s < (slot < 0 ? ES_SLOTS : slot + 1); ++s) {
+        const int64_t* src = reinterpret_cast<const int64_t*>(&b->stats[(size_t)stream * ES_SLOTS + s]);
+        int64_t* d = reinterpret_cast<int64_t*>(h_out);
+        for (int k = 0; k < ES_COUNTERS; ++k) d[k] += src[k];
+    }
+    return 0;
+}
+
+int dvbs2gpu_es_get_stream_stats(dvbs2gpu_es* b, int stream, dvbs2gpu_es_stream_stats* h_out) {
+    if (!b || stream < 0 || stream >= b->nstreams || !h_out) return DVBS2GPU_ERR_ARG;
+    *h_out = b->sstats[stream];
+    return 0;
+}
+
+int dvbs2gpu_es_get_row_table(dvbs2gpu_es* b, int stream, dvbs2gpu_es_row* h_rows, int cap, int* n) {
+    return ts_bank_rows(b, &dvbs2gpu_es::max_rows, stream, h_rows, cap, n);
+}
+
+int dvbs2gpu_es_get_row_table_device(dvbs2gpu_es* b, int stream, const dvbs2gpu_es_row** d_rows, int* n) {
+    return ts_bank_rows_device(b, &dvbs2gpu_es::max_rows, stream, d_rows, n);
+}
+
+}  // extern "C"

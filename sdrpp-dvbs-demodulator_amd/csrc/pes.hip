@@ -7,15 +7,9 @@
 // packets between two starts; and a start's timestamp step needs only the slot's previous start that had a PTS.
 //
 //   pes_kernel  one workgroup per stream, one launch per call.
-//     A  every packet's header is read once (ts_load_header, ts_bank.h) and its PID matched against the 16 watches.  The trusted
-//        packets of watched PIDs are compacted in input order into LDS, one 32-bit word each (packet, slot, counter, payload length,
-//        payload, PUSI, scrambled, DI): flags in a mask, ts_block_scan, scatter.
-//     B  the PCR bank's stable counting sort by slot; the words themselves are placed.
-//     C  every thread takes a contiguous run of the sorted words.  The word before one in sorted order is its slot's previous packet,
-//        or the word is its slot's first of the call and takes the carried continuity byte.  A packet is "eligible" when it could be
-//        a duplicate (payload, no DI, the counter of the packet before it); an exclusive maximum scan over the threads
-//        (ts_block_scan_max) gives every packet the last one before it that is not eligible, the distance to it is its place in the
-//        run of equal counters and the parity of that place is dup_used.  With it tsmon_step's verdict follows per packet.
+//     A-C  ts_watch.h, shared with the ES bank: the trusted packets of watched PIDs compacted into LDS as one 32-bit word each
+//        (packet, slot, counter, payload length, payload, PUSI, scrambled, DI), sorted by slot, and tsmon_step's verdict per packet
+//        from the parity of its place in a run of equal counters.
 //     D  two prefix sums over the accepted packets in sorted order -- payload bytes; packets and GAP marks -- make every PES
 //        packet's byte count, packet count and GAP a difference of two prefix values.
 //     E  the lanes that own starts read the first payload bytes (five unaligned dwords that stay inside the packet) and apply
@@ -26,15 +20,14 @@
 //        summed per thread and slot run, then into LDS.  The lane of the slot's last packet writes the slot's new state.
 // No lane walks over packets of other lanes: the cost of a call does not depend on what the packets say.  One device-to-host copy of
 // the per-stream call record (PesCall).
-#include "ts_bank.h"
-#include "pes_rules.h"
+#include "ts_watch.h"
 
 using namespace s2;
 #define g_err last_error()
 
 namespace s2 {
 
-constexpr int PES_MAX_PACKETS = 4096;            // per stream and call: 12 bytes of LDS per packet
+constexpr int PES_MAX_PACKETS = PW_MAX_PACKETS;           // per stream and call: 12 bytes of LDS per packet
 constexpr int PES_WG = 256;
 constexpr int PES_BM_WORDS = PES_MAX_PACKETS / 32;
 static_assert(sizeof(PesRow) == sizeof(dvbs2gpu_pes_row) && sizeof(PesRow) == 48, "row layout");
@@ -46,21 +39,8 @@ static_assert(PES_CLOSED == DVBS2GPU_PES_CLOSED && PES_UNBOUNDED_NONVIDEO == DVB
 
 struct PesCall { PesCallHead head; PesCnt cnt[PES_SLOTS]; };
 
-// a packet in LDS: packet k bits 0-11, slot 12-15, continuity counter 16-19, payload bytes L 20-27 (0 with payload: malformed),
-// payload 28, PUSI 29, scrambled 30, DI 31.  Behind phase C the counter's bits hold the verdict: DUPLICATE 16, a GAP mark 17; behind
-// phase E's first pass bit 18 says that a start has a PTS
-__device__ inline int pw_k(uint32_t e) { return (int)(e & 4095); }
-__device__ inline int pw_slot(uint32_t e) { return (int)(e >> 12 & 15); }
-__device__ inline int pw_cc(uint32_t e) { return (int)(e >> 16 & 15); }
-__device__ inline int pw_len(uint32_t e) { return (int)(e >> 20 & 255); }
-__device__ inline int pw_pay(uint32_t e) { return (int)(e >> 28 & 1); }
-__device__ inline int pw_pusi(uint32_t e) { return (int)(e >> 29 & 1); }
-__device__ inline int pw_scr(uint32_t e) { return (int)(e >> 30 & 1); }
-__device__ inline int pw_di(uint32_t e) { return (int)(e >> 31); }
-constexpr uint32_t PW_VERDICT = 15u << 16, PW_DUP = 1u << 16, PW_GAP = 1u << 17, PW_PTS = 1u << 18;
-// behind phase C: an accepted packet with payload bytes; a start
-__device__ inline bool pw_counts(uint32_t e) { return !(e & PW_DUP) && pw_len(e) > 0; }
-__device__ inline bool pw_start(uint32_t e) { return pw_counts(e) && pw_pusi(e); }
+// the packet words, their verdict bits and phases A-C: ts_watch.h.  Behind phase E's first pass bit 18 says that a start has a PTS
+constexpr uint32_t PW_PTS = 1u << 18;
 
 // what the kernel keeps in LDS beside the packets; a multiple of 16 bytes in front of them
 struct alignas(16) PesShared {
@@ -80,35 +60,11 @@ static_assert(sizeof(PesShared) % 16 == 0 && sizeof(PesShared::place) == PES_MAX
 constexpr size_t pes_lds_bytes(int max_packets) { return sizeof(PesShared) + ((size_t)max_packets * 3 + 2) * sizeof(uint32_t); }
 static_assert(pes_lds_bytes(PES_MAX_PACKETS) <= 64 * 1024, "dynamic LDS of a workgroup");
 
-// packet k of the stream: false, or a trusted packet of a watched PID as its word
-__device__ inline bool pes_look(const uint8_t* __restrict__ ts, int k, const int32_t* w, uint32_t* word) {
-    unsigned b4;
-    const TsmonHdr h = ts_load_header(ts, k, &b4);
-    if (h.cls != TSMON_DATA) return false;
-    int slot = -1;
-    for (int s = 0; s < PES_SLOTS; ++s) if (w[s] == h.pid) slot = s;
-    if (slot < 0) return false;
-    const int L = pes_payload_len(h.afc, b4);
-    *word = (uint32_t)k | (uint32_t)slot << 12 | (uint32_t)h.cc << 16 | (uint32_t)(L > 0 ? L : 0) << 20 | (uint32_t)(L >= 0) << 28 | (uint32_t)h.pusi << 29 |
-            (uint32_t)(h.tsc != 0) << 30 | (uint32_t)h.di << 31;
-    return true;
-}
-
-// the start in packet word e: its first payload bytes as five dwords, each read where it still lies inside the packet and shifted
-// down; bytes behind the packet's end read as 0 (pes_start looks at none of them).  A scrambled payload is not read
+// the start in packet word e (pw_load_start: five dwords that stay inside the packet; pes_start looks at no byte behind its end)
 __device__ inline PesHead pes_load_start(const uint8_t* __restrict__ ts, uint32_t e) {
-    const int L = pw_len(e), o = TSMON_TS - L;
-    uint32_t w[5] = {0, 0, 0, 0, 0};
-    if (!pw_scr(e)) {
-        const uint8_t* p = ts + (size_t)pw_k(e) * TSMON_TS;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int a = o + 4 * i, c = a > TSMON_TS - 4 ? TSMON_TS - 4 : a;
-            const uint32_t v = *reinterpret_cast<const ts_unaligned_u32*>(p + c);
-            w[i] = a - c >= 4 ? 0u : v >> (8 * (a - c));
-        }
-    }
-    return pes_start(w, L, pw_scr(e));
+    uint32_t w[5];
+    pw_load_start(ts, e, w);
+    return pes_start(w, pw_len(e), pw_scr(e));
 }
 
 __device__ inline void pes_flush(PesCnt* d, const PesCnt& a) {
@@ -122,8 +78,7 @@ __device__ inline void pes_flush(PesCnt* d, const PesCnt& a) {
 }
 
 // the packet counters of phase C, per thread and slot run
-struct PesPk { int packets, payload_bytes, duplicates, cc_errors, scrambled, malformed; };
-__device__ inline void pes_flush_pk(PesCnt* d, const PesPk& a) {
+__device__ inline void pes_flush_pk(PesCnt* d, const PwPk& a) {
     atomicAdd(&d->packets, a.packets);
     if (a.payload_bytes) atomicAdd(&d->payload_bytes, a.payload_bytes);
     if (a.duplicates) atomicAdd(&d->duplicates, a.duplicates);
@@ -157,96 +112,22 @@ __global__ void __launch_bounds__(PES_WG) pes_kernel(const uint8_t* const* __res
     __syncthreads();
     const uint8_t* ts = in[s];
     // A: the watched packets, compacted in input order
-    int W = 0;
-    if (n > 0) {
-        int k0, k1; ts_thread_run(n, PES_WG, &k0, &k1);          // <= 16 packets per thread
-        unsigned mask = 0;
-        uint32_t word;
-        for (int k = k0; k < k1; ++k) if (pes_look(ts, k, sh.w, &word)) mask |= 1u << (k - k0);
-        int at = ts_block_scan<PES_WG>(__popc(mask), sh.wsum, &W);
-        for (int k = k0; k < k1; ++k) {
-            if (!(mask >> (k - k0) & 1)) continue;
-            pes_look(ts, k, sh.w, &word);
-            rec[at++] = word;
-        }
-    }
-    __syncthreads();
+    const int W = pw_compact<PES_WG>(ts, n, sh.w, sh.wsum, rec);
     int nstarts = 0;
     if (W > 0) {
         // B: the stable counting sort by slot
-        int j0, j1; ts_thread_run(W, PES_WG, &j0, &j1);
-        for (int q = 0; q < PES_SLOTS; ++q) sh.place[q][tid] = 0;
-        for (int r = j0; r < j1; ++r) ++sh.place[pw_slot(rec[r])][tid];
-        __syncthreads();
-        {
-            uint16_t* flat = &sh.place[0][0] + PES_SLOTS * tid;    // slot-major: 16 threads' counts of one slot
-            int sum = 0, total;
-            for (int i = 0; i < PES_SLOTS; ++i) sum += flat[i];
-            int at = ts_block_scan<PES_WG>(sum, sh.wsum, &total);
-            for (int i = 0; i < PES_SLOTS; ++i) { const int c = flat[i]; flat[i] = (uint16_t)at; at += c; }
-        }
-        __syncthreads();
-        if (tid < PES_SLOTS) sh.start[tid] = sh.place[tid][0];
-        if (tid == PES_SLOTS) sh.start[PES_SLOTS] = W;
-        __syncthreads();
-        for (int r = j0; r < j1; ++r) { const uint32_t e = rec[r]; srt[sh.place[pw_slot(e)][tid]++] = e; }
-        __syncthreads();
-        // C: the continuity verdicts.  seen / last: the continuity state in front of sorted packet j
-        auto front_cc = [&](int j, uint32_t e, bool* seen) {
-            const int slot = pw_slot(e);
-            if (j != sh.start[slot]) { *seen = true; return pw_cc(srt[j - 1]); }
-            *seen = (sh.ss[slot].cc & TSMON_ST_SEEN) != 0;
-            return sh.ss[slot].cc & 15;
-        };
-        auto eligible = [&](uint32_t e, bool seen, int last) { return seen && !pw_di(e) && pw_pay(e) && pw_cc(e) == last; };
-        int mine = -1;
-        for (int j = j0; j < j1; ++j) {
-            const uint32_t e = srt[j];
-            bool seen;
-            const int last = front_cc(j, e, &seen);
-            if (!eligible(e, seen, last)) mine = j;
-        }
-        int brk = ts_block_scan_max(mine, sh.wsum);              // the last sorted packet before j that is not eligible
-        unsigned dupm = 0, gapm = 0;
-        {
-            PesPk pk = {0, 0, 0, 0, 0, 0};
-            int pk_slot = -1;
-            for (int j = j0; j < j1; ++j) {
-                const uint32_t e = srt[j];
-                const int slot = pw_slot(e), head = sh.start[slot], cc = pw_cc(e);
-                bool seen;
-                const int last = front_cc(j, e, &seen);
-                int v = TSMON_CC_ERROR;
-                if (!seen) v = TSMON_FIRST;
-                else if (pw_di(e)) v = TSMON_DISC;
-                else if (!pw_pay(e)) v = cc != last ? TSMON_CC_ERROR : TSMON_OK;
-                else if (cc == ((last + 1) & 15)) v = TSMON_OK;
-                else if (cc == last) {
-                    // its place in the run of equal counters; a run that reaches the slot's head goes on from the carried dup_used
-                    const int dup = brk >= head ? (j - brk) & 1 : ((sh.ss[slot].cc & TSMON_ST_DUP) != 0) ^ ((j - head + 1) & 1);
-                    v = dup ? TSMON_DUPLICATE : TSMON_CC_ERROR;
-                }
-                if (!eligible(e, seen, last)) brk = j;
-                if (slot != pk_slot) {
-                    if (pk_slot >= 0) pes_flush_pk(&sh.cnt[pk_slot], pk);
-                    pk = PesPk{0, 0, 0, 0, 0, 0}; pk_slot = slot;
-                }
-                ++pk.packets;
-                const bool dup = v == TSMON_DUPLICATE, malformed = !dup && pw_pay(e) && pw_len(e) == 0;
-                pk.duplicates += dup; pk.cc_errors += v == TSMON_CC_ERROR; pk.malformed += malformed;
-                if (!dup) { pk.payload_bytes += pw_len(e); pk.scrambled += pw_len(e) > 0 && pw_scr(e); }
-                if (dup) dupm |= 1u << (j - j0);
-                if (v == TSMON_CC_ERROR || v == TSMON_DISC || malformed) gapm |= 1u << (j - j0);
-                if (j == sh.start[slot + 1] - 1) sh.ncc[slot] = (uint8_t)(TSMON_ST_SEEN | (dup ? TSMON_ST_DUP : 0) | cc);
-            }
-            if (pk_slot >= 0) pes_flush_pk(&sh.cnt[pk_slot], pk);
-        }
+        int j0, j1;
+        pw_sort<PES_WG>(rec, srt, W, sh.place, sh.start, sh.wsum, &j0, &j1);
+        // C: the continuity verdicts
+        unsigned dupm, gapm;
+        pw_verdicts(srt, j0, j1, sh.start, [&](int slot) { return sh.ss[slot].cc; }, sh.wsum, sh.ncc,
+                    [&](int slot, const PwPk& pk) { pes_flush_pk(&sh.cnt[slot], pk); }, &dupm, &gapm);
         __syncthreads();                                         // every counter has been read: the verdicts take their bits
         // D: the prefix sums over the accepted packets
         {
             int sb = 0, sc = 0;
             for (int j = j0; j < j1; ++j) {
-                const uint32_t e = (srt[j] & ~PW_VERDICT) | (dupm >> (j - j0) & 1 ? PW_DUP : 0) | (gapm >> (j - j0) & 1 ? PW_GAP : 0);
+                const uint32_t e = pw_with_verdict(srt[j], dupm >> (j - j0) & 1, gapm >> (j - j0) & 1);
                 srt[j] = e;
                 if (pw_counts(e)) { sb += pw_len(e); sc += 1 << 13; }
                 sc += (e & PW_GAP) != 0;

@@ -1,5 +1,5 @@
 // Shared by the banks that work on transport streams in HBM (tsmon.hip: the TS monitor; psi.hip: the PSI sections; pcr.hip: the PCRs; pes.hip: the PES packets;
-// t2mi.hip: the T2-MI packets):
+// es.hip: the elementary streams; t2mi.hip: the T2-MI packets):
 // what a "packet bank" does around its rules.  On the device: the one header read, the one workgroup prefix sum and the contiguous
 // run of items a thread takes ("flags in a mask, scan, scatter").  On the host: the argument table of a call, the count checks,
 // the staging of the single-stream host-buffer entry point and the table getters.  The rules stay in tsmon_rules.h / psi_rules.h / pcr_rules.h / pes_rules.h /
