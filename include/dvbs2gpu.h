@@ -500,7 +500,11 @@ long long dvbs2gpu_dvbs_segrx_find_join(const uint8_t* h_tail, long long ntail, 
  * d_bits[i]: DEVICE pointer to counts[i] decoded bits (one per byte, the Viterbi output); d_ts[i]: DEVICE buffer of cap bytes that
  * receives the 188-byte TS packets of every frame found; out_bytes[i] (host).  Frame k of a call is taken at byte offset
  * 1632*k of the deframer output (the reference indexes 204*k, SURVEY Q5: wrong for k >= 1).  On a failed RS decode the
- * reference's wrapper emits the previous packet's message; so does this.  Synchronous on `stream`. */
+ * reference's wrapper emits the previous packet's message; so does this.  Synchronous on `stream`.
+ * CAPACITY: a handle holds max_bits / 13056 + 3 frames per stream and call.  A stream of real traffic has at most one frame per
+ * 13 056 bits, so it never gets there; a stream with more sync-pattern hits than that in one call (the reference's deframer delivers
+ * every one) has the first max_bits / 13056 + 3 of them delivered, in order, and the rest counted: dvbs2gpu_dvbs_tail_get_dropped.
+ * The deframer's history and errors_nor / errors_inv (those of the true last hit) are what they would be had nothing been dropped. */
 typedef struct dvbs2gpu_dvbs_tail dvbs2gpu_dvbs_tail;
 int dvbs2gpu_dvbs_tail_create(dvbs2gpu_ctx* ctx, int nstreams, int max_bits, dvbs2gpu_dvbs_tail** out);
 int dvbs2gpu_dvbs_tail_reset(dvbs2gpu_dvbs_tail* t);
@@ -509,6 +513,9 @@ int dvbs2gpu_dvbs_tail_process_batch(dvbs2gpu_dvbs_tail* t, const uint8_t* const
                                      int* out_bytes, void* stream);
 /* h_out11 = {frames of the last call, errors_nor, errors_inv, RS error counts of the last frame's 8 packets} */
 int dvbs2gpu_dvbs_tail_get_stats(dvbs2gpu_dvbs_tail* t, int stream, int32_t* h_out11);
+/* *h_dropped = sync-pattern hits of the last process_batch call that this stream found beyond the handle's capacity (see CAPACITY
+ * above) and did not deliver; 0 for every call that fits, after dvbs2gpu_dvbs_tail_reset and after dvbs2gpu_dvbs_tail_rs_stage */
+int dvbs2gpu_dvbs_tail_get_dropped(dvbs2gpu_dvbs_tail* t, int stream, int32_t* h_dropped);
 /* Stage taps of the last call for one stream (host copies; returns the byte count, h_dst may be NULL to query it):
  *   0  frames found by the deframer, 1632 bytes each (DVBS_TS_Deframer::work output, dvbs_ts_deframer.cpp:37-92)
  *   1  the same frames after the Forney de-interleaver and the in-place RS correction, 8 x 204 bytes each

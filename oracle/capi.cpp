@@ -315,6 +315,13 @@ int orc_tsdef_work(void* h, const uint8_t* bits, int size, uint8_t* out, int* er
     if (errs2) { errs2[0] = d->errors_nor; errs2[1] = d->errors_inv; }
     return n;
 }
+// as orc_tsdef_work for an output buffer of cap_frames frames: every hit is counted, the frames beyond the buffer are not written
+int orc_tsdef_work_cap(void* h, const uint8_t* bits, int size, uint8_t* out, int cap_frames, int* errs2) {
+    TsDeframer* d = (TsDeframer*)h;
+    int n = d->work(bits, size, out, cap_frames);
+    if (errs2) { errs2[0] = d->errors_nor; errs2[1] = d->errors_inv; }
+    return n;
+}
 void* orc_dvbsrs_create() { return new DvbsRs(); }
 void orc_dvbsrs_destroy(void* h) { delete (DvbsRs*)h; }
 int orc_dvbsrs_decode(void* h, uint8_t* data204) { return ((DvbsRs*)h)->decode(data204); }

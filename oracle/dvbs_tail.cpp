@@ -16,7 +16,7 @@ static inline uint8_t pack_8(const uint8_t* bits) {
 }
 static inline int compare_8(uint8_t a, uint8_t b) { return __builtin_popcount((unsigned)(a ^ b)); }
 
-int TsDeframer::work(const uint8_t* input, int size, uint8_t* output) {
+int TsDeframer::work(const uint8_t* input, int size, uint8_t* output, int max_frames) {
     int frame_count = 0;
     for (int ibit = 0; ibit < size; ibit++) {
         memmove(&shifter[0], &shifter[1], TS_SIZE - 1);
@@ -28,16 +28,20 @@ int TsDeframer::work(const uint8_t* input, int size, uint8_t* output) {
             t_inv += compare_8(i == 0 ? 0x47 : 0xB8, sb);
         }
         if (t_nor <= 8) {
-            uint8_t* o = &output[(size_t)frame_count * 204 * 8];
-            memset(o, 0, 204 * 8);
-            for (int i = 0; i < 204 * 8 * 8; i++) o[i / 8] = (uint8_t)(o[i / 8] << 1 | shifter[i]);
+            if (frame_count < max_frames) {
+                uint8_t* o = &output[(size_t)frame_count * 204 * 8];
+                memset(o, 0, 204 * 8);
+                for (int i = 0; i < 204 * 8 * 8; i++) o[i / 8] = (uint8_t)(o[i / 8] << 1 | shifter[i]);
+            }
             frame_count++;
             errors_nor = t_nor; errors_inv = 0;
         }
         if (t_inv <= 8) {
-            uint8_t* o = &output[(size_t)frame_count * 204 * 8];
-            memset(o, 0, 204 * 8);
-            for (int i = 0; i < 204 * 8 * 8; i++) o[i / 8] = (uint8_t)(o[i / 8] << 1 | !shifter[i]);
+            if (frame_count < max_frames) {
+                uint8_t* o = &output[(size_t)frame_count * 204 * 8];
+                memset(o, 0, 204 * 8);
+                for (int i = 0; i < 204 * 8 * 8; i++) o[i / 8] = (uint8_t)(o[i / 8] << 1 | !shifter[i]);
+            }
             frame_count++;
             errors_nor = 0; errors_inv = t_inv;
         }

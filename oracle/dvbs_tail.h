@@ -10,7 +10,9 @@ struct TsDeframer {                 // deframing::DVBS_TS_Deframer (dvbs/dvbs_ts
     std::vector<uint8_t> shifter;   // TS_SIZE unpacked bits (the reference's starts uninitialised; zero here)
     int errors_nor = 0, errors_inv = 0;
     TsDeframer() : shifter(TS_SIZE, 0) {}
-    int work(const uint8_t* input, int size, uint8_t* output);   // returns frame count, 1632 bytes each
+    // returns the frame count, 1632 bytes each; frames beyond max_frames are counted and not written (the reference has no such bound:
+    // its caller sizes the buffer)
+    int work(const uint8_t* input, int size, uint8_t* output, int max_frames = 0x7fffffff);
 };
 
 struct Gf256 {                      // common/correct/reed-solomon/field.h, primitive polynomial 0x11d

@@ -165,9 +165,11 @@ void ref_rotate_soft(int8_t* soft, int size, int phase, int iqswap) { rotate_sof
 extern "C" {
 void* ref_tsdef_create() {
     auto* d = new deframing::DVBS_TS_Deframer();
-    // the reference leaves its 13 056-bit shifter uninitialised; feed zeros so that runs are reproducible
-    std::vector<uint8_t> z(1632 * 8, 0), o(16 * 1632);
-    d->work(z.data(), (int)z.size(), o.data());
+    // the reference leaves its 13 056-bit shifter uninitialised; feed zeros so that runs are reproducible.  One bit per call: what the
+    // shifter held may be anything, a recycled bit stream full of sync patterns included, and a bit brings at most one frame
+    std::vector<uint8_t> o(2 * 1632);
+    uint8_t z = 0;
+    for (int i = 0; i < 1632 * 8; ++i) d->work(&z, 1, o.data());
     return d;
 }
 int ref_tsdef_work(void* h, uint8_t* bits, int size, uint8_t* out) { return ((deframing::DVBS_TS_Deframer*)h)->work(bits, size, out); }

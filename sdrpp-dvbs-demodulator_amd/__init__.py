@@ -396,6 +396,7 @@ PROTOTYPES = {
     'dvbs2gpu_dvbs_tail_destroy': (None, [_vp]),
     'dvbs2gpu_dvbs_tail_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i), _vp]),
     'dvbs2gpu_dvbs_tail_get_stats': (_i, [_vp, _i, C.POINTER(C.c_int32)]),
+    'dvbs2gpu_dvbs_tail_get_dropped': (_i, [_vp, _i, C.POINTER(C.c_int32)]),
     'dvbs2gpu_dvbs_tail_get_tap': (_i, [_vp, _i, _i, _vp, _i]),
     'dvbs2gpu_dvbs_tail_rs_stage': (_i, [_vp, _vp, _i, _i, _vp, _i]),
     'dvbs2gpu_dvbs_depuncture': (_i, [_vp, _i, _i, _vp, _i, _vp, _i, C.POINTER(C.c_int32)]),
@@ -1198,6 +1199,17 @@ class DvbsTailBank(_Handle):
         a = (C.c_int32 * 11)()
         self.eng._check(self.lib.dvbs2gpu_dvbs_tail_get_stats(self.h, stream, a))
         return {'frames': a[0], 'errors_nor': a[1], 'errors_inv': a[2], 'rs_errors': list(a[3:11])}
+
+    @property
+    def max_frames(self):
+        """frames one call can deliver per stream: the handle's capacity (include/dvbs2gpu.h)"""
+        return self.max_bits // 13056 + 3
+
+    def dropped(self, stream=0):
+        """sync-pattern hits of the last process_batch call found beyond max_frames and not delivered"""
+        a = C.c_int32()
+        self.eng._check(self.lib.dvbs2gpu_dvbs_tail_get_dropped(self.h, stream, C.byref(a)))
+        return a.value
 
     def tap(self, which, stream=0):
         """stage taps of the last call: 0 deframed frames, 1 packets after Forney + RS, 2 RS status, 3 RS error counts (int32)"""

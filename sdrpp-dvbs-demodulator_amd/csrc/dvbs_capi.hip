@@ -124,6 +124,7 @@ struct dvbs2gpu_dvbs_tail {
     DevBuf<uint8_t> d_v;
     DevBuf<int> d_hit;
     DevBuf<int> d_nframes;
+    DevBuf<int> d_dropped;                     // per stream: hits of the last call beyond max_frames (found, not delivered)
     DevBuf<int> d_errs;
     DevBuf<uint8_t> d_frames;
     DevBuf<uint8_t> d_deint;
@@ -175,6 +176,7 @@ int dvbs2gpu_dvbs_tail_create(dvbs2gpu_ctx* ctx, int nstreams, int max_bits, dvb
     RC_TRY(t->d_v.alloc(n * (size_t)t->v_stride, true, what));
     RC_TRY(t->d_hit.alloc(nf, true, what));
     RC_TRY(t->d_nframes.alloc(n, true, what));
+    RC_TRY(t->d_dropped.alloc(n, true, what));
     RC_TRY(t->d_errs.alloc(n * 2, true, what));
     RC_TRY(t->d_frames.alloc(n * (size_t)t->frames_stride, true, what));
     RC_TRY(t->d_deint.alloc(n * (size_t)t->frames_stride, true, what));
@@ -198,6 +200,7 @@ int dvbs2gpu_dvbs_tail_reset(dvbs2gpu_dvbs_tail* t) {
     HIP_TRY(hipMemset(t->d_hist[0], 0, n * 1632 * 8)); HIP_TRY(hipMemset(t->d_hist[1], 0, n * 1632 * 8));
     HIP_TRY(hipMemset(t->d_forney, 0, n * DVBS_FORNEY_HIST));
     HIP_TRY(hipMemset(t->d_errs, 0, n * 2 * sizeof(int)));
+    HIP_TRY(hipMemset(t->d_dropped, 0, n * sizeof(int)));
     std::vector<DvbsTailState> st(n);
     memset(st.data(), 0, n * sizeof(DvbsTailState));
     for (auto& s : st) s.prbs_pos = -1;
@@ -223,7 +226,7 @@ int dvbs2gpu_dvbs_tail_process_batch(dvbs2gpu_dvbs_tail* t, const uint8_t* const
     HIP_TRY(hipMemcpyAsync(d_out, d_ts, sizeof(void*) * n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_cnt, counts, sizeof(int) * n, hipMemcpyHostToDevice, st));
     HIP_TRY(dvbs_tail_launch(d_in, d_cnt, n, t->max_bits, t->d_hist[t->cur], t->d_hist[t->cur ^ 1], t->d_v, t->v_stride, t->max_frames, t->d_hit,
-                             t->d_nframes, t->d_errs, t->d_frames, t->d_deint, t->frames_stride, t->d_forney, t->d_status, t->d_gf, t->d_prbs,
+                             t->d_nframes, t->d_dropped, t->d_errs, t->d_frames, t->d_deint, t->frames_stride, t->d_forney, t->d_status, t->d_gf, t->d_prbs,
                              t->d_state, d_out, cap, d_ob, t->d_rs_err, st));
     t->cur ^= 1;
     HIP_TRY(hipMemcpyAsync(out_bytes, d_ob, sizeof(int) * n, hipMemcpyDeviceToHost, st));
@@ -241,6 +244,14 @@ int dvbs2gpu_dvbs_tail_get_stats(dvbs2gpu_dvbs_tail* t, int stream, int32_t* h_o
     h_out11[0] = nf; h_out11[1] = er[0]; h_out11[2] = er[1];
     for (int i = 0; i < 8; ++i) h_out11[3 + i] = 0;
     if (nf > 0) HIP_TRY(hipMemcpy(h_out11 + 3, t->d_rs_err + (size_t)stream * t->max_frames * 8 + (size_t)(nf - 1) * 8, 8 * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* hits the deframer found in the last call beyond the handle's max_bits / 13056 + 3 frames: counted, not delivered (include/dvbs2gpu.h) */
+int dvbs2gpu_dvbs_tail_get_dropped(dvbs2gpu_dvbs_tail* t, int stream, int32_t* h_dropped) {
+    if (!t || stream < 0 || stream >= t->nstreams || !h_dropped) return DVBS2GPU_ERR_ARG;
+    HIP_TRY(hipSetDevice(t->ctx->device));
+    HIP_TRY(hipMemcpy(h_dropped, t->d_dropped + stream, sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -273,6 +284,7 @@ int dvbs2gpu_dvbs_tail_rs_stage(dvbs2gpu_dvbs_tail* t, const uint8_t* h_packets,
     std::vector<int> nfr(n, 0);
     nfr[0] = nf;
     HIP_TRY(hipMemcpy(t->d_nframes, nfr.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(t->d_dropped, 0, sizeof(int) * n));
     HIP_TRY(hipMemcpy(t->d_deint, h_packets, (size_t)npackets * 204, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(t->d_status, 1, (size_t)n * t->max_frames * 8));
     HIP_TRY(hipMemset(t->d_rs_err, 0, (size_t)n * t->max_frames * 8 * sizeof(int)));

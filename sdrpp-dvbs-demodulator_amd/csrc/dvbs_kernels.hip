@@ -592,10 +592,12 @@ __global__ __launch_bounds__(256) void dvbs_tsdef_pack_kernel(const uint8_t* con
         vo[p] = (uint8_t)b;
     }
 }
-// one workgroup per stream: test every window end position t (window start = t in the v[] indexing), ordered compaction of hits
+// one workgroup per stream: test every window end position t (window start = t in the v[] indexing), ordered compaction of hits.
+// The first max_frames hits of a call are kept, in order; ndropped[s] counts the later ones (the reference delivers every hit), and
+// errors_nor / errors_inv follow the true last hit, kept or not.
 __global__ __launch_bounds__(256) void dvbs_tsdef_find_kernel(const int* __restrict__ counts, const uint8_t* __restrict__ v, long v_stride,
                                                               int max_frames, int* __restrict__ hit_pos, int* __restrict__ nframes,
-                                                              int* __restrict__ errs) {
+                                                              int* __restrict__ ndropped, int* __restrict__ errs) {
     __shared__ int s_base, s_wave[4], s_last[2];
     const int s = blockIdx.x, n = counts[s], tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint8_t* __restrict__ vv = v + (long)s * v_stride;
@@ -631,7 +633,7 @@ __global__ __launch_bounds__(256) void dvbs_tsdef_find_kernel(const int* __restr
         if (tid == 0) s_base += tot;
         __syncthreads();
     }
-    if (tid == 0) { nframes[s] = min(s_base, max_frames); errs[2 * s] = s_last[0]; errs[2 * s + 1] = s_last[1]; }
+    if (tid == 0) { nframes[s] = min(s_base, max_frames); ndropped[s] = max(s_base - max_frames, 0); errs[2 * s] = s_last[0]; errs[2 * s + 1] = s_last[1]; }
 }
 // frames out (byte k of a frame = v[start + 8k], inverted for an inverted hit) + new history; grid (max_frames + 1, nstreams)
 __global__ __launch_bounds__(256) void dvbs_tsdef_emit_kernel(const uint8_t* const* __restrict__ in_ptrs, const int* __restrict__ counts,
@@ -876,13 +878,14 @@ hipError_t dvbs_tail_rs_finish_launch(int nstreams, int max_frames, const int* d
 }
 
 hipError_t dvbs_tail_launch(const uint8_t* const* d_in_ptrs, const int* d_counts, int nstreams, int max_bits, uint8_t* d_hist, uint8_t* d_hist_next,
-                            uint8_t* d_v, long v_stride, int max_frames, int* d_hit_pos, int* d_nframes, int* d_errs, uint8_t* d_frames,
-                            uint8_t* d_deint, long frames_stride, uint8_t* d_forney_hist, uint8_t* d_status, const uint8_t* d_gf, const uint8_t* d_prbs,
+                            uint8_t* d_v, long v_stride, int max_frames, int* d_hit_pos, int* d_nframes, int* d_ndropped, int* d_errs,
+                            uint8_t* d_frames, uint8_t* d_deint, long frames_stride, uint8_t* d_forney_hist, uint8_t* d_status, const uint8_t* d_gf, const uint8_t* d_prbs,
                             DvbsTailState* d_state, uint8_t* const* d_out_ptrs, int cap, int* d_out_bytes, int* d_rs_err, hipStream_t st) {
     int gx = (max_bits + TSD_WIN + 255) / 256;
     gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
     hipLaunchKernelGGL(dvbs_tsdef_pack_kernel, dim3(gx, nstreams), dim3(256), 0, st, d_in_ptrs, d_counts, d_hist, d_v, v_stride);
-    hipLaunchKernelGGL(dvbs_tsdef_find_kernel, dim3(nstreams), dim3(256), 0, st, d_counts, d_v, v_stride, max_frames, d_hit_pos, d_nframes, d_errs);
+    hipLaunchKernelGGL(dvbs_tsdef_find_kernel, dim3(nstreams), dim3(256), 0, st, d_counts, d_v, v_stride, max_frames, d_hit_pos, d_nframes, d_ndropped,
+                       d_errs);
     hipLaunchKernelGGL(dvbs_tsdef_emit_kernel, dim3(max_frames + 1, nstreams), dim3(256), 0, st, d_in_ptrs, d_counts, d_v, v_stride, max_frames,
                        d_hit_pos, d_nframes, d_frames, frames_stride, d_hist, d_hist_next);
     int gd = (max_frames * 1632 + 255) / 256;

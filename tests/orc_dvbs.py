@@ -211,6 +211,82 @@ def viterbi_case_streams(nb):
     return cases
 
 
+# the leading softs to drop from a stream of each rate so that the search ends on each (rate, phase, shift) it can end on: drop -> shift
+LOCK_DROPS = {0: {0: 0, 1: 1}, 1: {0: 0, 1: 4, 2: 5}, 2: {0: 0, 2: 1}, 3: {0: 0, 3: 3, 4: 4, 5: 5, 1: 7, 2: 8}, 4: {0: 0, 2: 1, 4: 2, 6: 3}}
+VITERBI_LOCK_BLOCKS = 8
+VITERBI_LOCK_WATCHDOG = 2          # max_outsync of the decoders these streams are made for
+RELOCK_BLOCK = 5                   # the block in which a 'relock' stream locks for the second time
+
+
+def viterbi_lock_streams():
+    """streams for the lock search of Viterbi_DVBS (ST_IDLE: 2 phases x 26 (rate, shift) hypotheses in the order 1/2 x 2, 2/3 x 6, 3/4 x 2,
+    5/6 x 12, 7/8 x 4; the LAST one under the threshold wins), for decoders with max_outsync = VITERBI_LOCK_WATCHDOG.
+    List of (name, soft int8 [VITERBI_LOCK_BLOCKS, 8192], kind, lock): lock = (rate, phase, shift) the oracle is to end on, None for 'idle'.
+
+      'lock'    one stream per final lock that a coded stream can produce: 34 of the 52 hypotheses.  A sweep over dvbs_tx(rate, drop = 0 .. 27,
+                both rotations, sigma 8) on the oracle ends on exactly these and on nothing else; LOCK_DROPS lists the smallest drop for each.
+                The other 18 never end a search: rate 2/3 shifts 1, 2, 3 and rate 5/6 shifts 1, 2, 6, 9, 10, 11, each in both phases.  Shifts s
+                and s + period stand for the same puncturing phase of the first soft, without and with one erasure in front of it
+                (depunc_static, depunc.h:16-38,108-137), so one of the two starts the de-punctured stream on the first half of a mother-code
+                pair and the other on the second half.  A stream received at that puncturing phase locks on the pair-aligned one -- 0, 4, 5
+                of 2/3 and 0, 3, 4, 5, 7, 8 of 5/6 -- which shadows its twin; six phases of the first soft are all a 5/6 stream can have,
+                three all a 2/3 stream can.  Should a sweep ever end on one of the 18, it belongs into LOCK_DROPS and REACHABLE_LOCKS.
+      'idle'    coded streams that never lock: rates 3/4 and 7/8 with an odd number of dropped softs (their hypotheses move by whole I/Q
+                pairs, viterbi_all.h:92-150): state 0 and count 0 in every block
+      'late'    2 blocks of noise, then rate 2/3 / 5/6 at a shift > period - 1: the lock and the de-puncturer's leading erasure come in the middle of a call
+      'relock'  signal, 3 blocks of noise (the watchdog gives up in the third), the same rate again at another drop and rotation.  Depunc23/56::set_shift
+                resets neither got_extra nor buf (depunc.h), so the continuous de-puncturer starts the second lock with what the noise left in them:
+                the counts from RELOCK_BLOCK on differ from those of a fresh decoder fed the same blocks."""
+    nb = VITERBI_LOCK_BLOCKS
+    rng = np.random.default_rng(78)
+    out = []
+    for rate, drops in LOCK_DROPS.items():
+        for rot in (False, True):
+            for drop, shift in drops.items():
+                soft, _ = dvbs_tx(rate, nb * 8192, seed=7000 + 100 * rate + 20 * rot + drop, drop=drop, rot90=rot)
+                out.append((f'lock_r{rate}_p{int(rot)}_s{shift}', soft.reshape(nb, 8192), 'lock', (rate, int(rot), shift)))
+    for rate, drop, rot in ((2, 1, False), (2, 3, True), (4, 1, True), (4, 3, False), (4, 5, False), (4, 7, True)):
+        soft, _ = dvbs_tx(rate, nb * 8192, seed=7600 + 10 * rate + drop, drop=drop, rot90=rot)
+        out.append((f'idle_r{rate}_d{drop}_p{int(rot)}', soft.reshape(nb, 8192), 'idle', None))
+    for rate, drop, rot in ((1, 1, True), (1, 2, False), (3, 1, False), (3, 2, True)):
+        soft, _ = dvbs_tx(rate, (nb - 2) * 8192, seed=7700 + 10 * rate + drop, drop=drop, rot90=rot)
+        x = np.concatenate([rng.integers(-70, 71, (2, 8192)).astype(np.int8), soft.reshape(nb - 2, 8192)])
+        out.append((f'late_r{rate}_p{int(rot)}_s{LOCK_DROPS[rate][drop]}', x, 'late', (rate, int(rot), LOCK_DROPS[rate][drop])))
+    for rate, (da, db) in ((1, (1, 0)), (3, (3, 5))):
+        a, _ = dvbs_tx(rate, 2 * 8192, seed=7800 + rate, drop=da, rot90=False)
+        b, _ = dvbs_tx(rate, (nb - RELOCK_BLOCK) * 8192, seed=7810 + rate, drop=db, rot90=True)
+        x = np.concatenate([a.reshape(2, 8192), rng.integers(-70, 71, (RELOCK_BLOCK - 2, 8192)).astype(np.int8), b.reshape(-1, 8192)])
+        out.append((f'relock_r{rate}_d{da}_d{db}', x, 'relock', (rate, 1, LOCK_DROPS[rate][db])))
+    return out
+
+
+REACHABLE_LOCKS = {(r, p, s) for r, shifts in ((0, (0, 1)), (1, (0, 4, 5)), (2, (0, 1)), (3, (0, 3, 4, 5, 7, 8)), (4, (0, 1, 2, 3))) for p in (0, 1) for s in shifts}
+
+
+def check_viterbi_lock_streams(streams, results):
+    """the preconditions of viterbi_lock_streams() on the oracle's (or the reference's) own results [(bits, counts, stats)] -- what makes the
+    streams worth comparing: the 34 final locks, the streams that stay IDLE, the late locks, and the stale de-puncturer state after a re-lock"""
+    locks = set()
+    for (name, soft, kind, lock), (_, n, st) in zip(streams, results):
+        if kind == 'lock':
+            assert (st[:, 1] == 1).all() and (n > 0).all(), (name, st[:, 1], n)
+            assert tuple(st[-1, 2:5]) == lock and (st[:, 2:5] == st[-1, 2:5]).all(), (name, st[:, 2:5])
+            locks.add(tuple(int(v) for v in st[-1, 2:5]))
+        elif kind == 'idle':
+            assert (st[:, 1] == 0).all() and (n == 0).all(), (name, st[:, 1], n)
+        elif kind == 'late':
+            assert (st[:2, 1] == 0).all() and (n[:2] == 0).all() and (st[2:, 1] == 1).all() and (n[2:] > 0).all(), (name, st[:, 1], n)
+            assert (st[2:, 2:5] == np.asarray(lock)).all() and lock[2] > (2 if lock[0] == 1 else 5), (name, st[:, 2:5])
+        else:
+            k = RELOCK_BLOCK
+            assert list(st[:k, 1]) == [1] * (k - 1) + [0] and st[k, 1] == 1, (name, st[:, 1])               # locked, watchdog, IDLE after block k - 1, locked again in block k
+            assert tuple(st[0, 2:5]) != tuple(st[k, 2:5]) and tuple(st[k, 2:5]) == lock and st[0, 2] == lock[0], (name, st[:, 2:5])
+            fresh = OracleViterbi(0.15, VITERBI_LOCK_WATCHDOG).work(soft[k:])
+            assert tuple(fresh[2][0, 1:5]) == (1,) + lock, (name, fresh[2])
+            assert list(n[k:]) != list(fresh[1]), (name, n[k:], fresh[1])                                    # the stale got_extra / buf shows in the counts
+    assert locks == REACHABLE_LOCKS and len(locks) == 34, sorted(REACHABLE_LOCKS ^ locks)
+
+
 CCDEC_FRAMES = [54, 56, 57, 59, 114, 1024, 1366, 1699, 4096, 6799]     # (frame + 6 steps in chunks of 60 = 10 rotations of the state layout: every remainder 0..5, a chunk that is exactly full)
 
 

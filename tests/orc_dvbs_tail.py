@@ -20,6 +20,7 @@ def L():
             getattr(l, n).restype = None
             getattr(l, n).argtypes = [VP]
         l.orc_tsdef_work.argtypes = [VP, VP, C.c_int, VP, VP]
+        l.orc_tsdef_work_cap.argtypes = [VP, VP, C.c_int, VP, C.c_int, VP]
         l.orc_dvbsrs_decode.argtypes = [VP, VP]
         l.orc_rs255_decode.argtypes = [VP, VP]
         l.orc_rs255_locator.argtypes = [VP, VP, VP]
@@ -132,11 +133,22 @@ class OracleTail:
         self.last_rs = [0] * 8
         self.errs = np.zeros(2, np.int32)
         self.call_status, self.call_rs = [], []          # per packet of the last call: rs255_decode produced a message, the wrapper's return value
+        self.call_hits, self.call_frames = 0, np.zeros((0, 1632), np.uint8)      # of the last call: hits of the deframer, the frames handed on
 
-    def process(self, bits):
+    def process(self, bits, capacity=None, keep=None):
+        """one call: -> (TS bytes, frames).  capacity: frames the deframer's output buffer holds (default: bits // 13056 + 4, one more than
+        a stream of real traffic can bring; a stream with more sync-pattern hits than that needs it stated).  keep: hand only the first
+        `keep` frames on to the de-interleaver, RS and descrambler, as an engine handle of that capacity does -- the deframer itself still
+        sees every bit and counts every hit (self.call_hits, self.errs)."""
         bits = np.ascontiguousarray(bits, np.uint8)
-        frames = np.zeros(1632 * (bits.size // 13056 + 4), np.uint8)
-        nf = self.o.orc_tsdef_work(self.hd, P(bits), bits.size, P(frames), P(self.errs)) if bits.size else 0
+        capacity = bits.size // 13056 + 4 if capacity is None else capacity
+        frames = np.zeros(1632 * capacity, np.uint8)
+        nf = self.o.orc_tsdef_work_cap(self.hd, P(bits), bits.size, P(frames), capacity, P(self.errs)) if bits.size else 0
+        assert nf <= capacity, (nf, capacity)                     # (the oracle counted them and wrote no further than the buffer)
+        self.call_hits = nf
+        if keep is not None:
+            nf = min(nf, keep)
+        self.call_frames = frames[:1632 * nf].reshape(nf, 1632)
         out = []
         self.call_status, self.call_rs = [], []
         for k in range(nf):
@@ -153,6 +165,28 @@ class OracleTail:
             for i in range(8):
                 out.append(d[204 * i:204 * i + 188].copy())
         return (np.concatenate(out) if out else np.zeros(0, np.uint8)), nf
+
+
+class OracleDeframer:
+    """the deframer alone, call by call: work(bits, capacity) -> (frames uint8 [n, 1632], (errors_nor, errors_inv) after the call)"""
+
+    def __init__(self):
+        self.o = L()
+        self.h = VP(self.o.orc_tsdef_create())
+        self.errs = np.zeros(2, np.int32)
+
+    def __del__(self):
+        try:
+            self.o.orc_tsdef_destroy(self.h)
+        except Exception:
+            pass
+
+    def work(self, bits, capacity):
+        bits = np.ascontiguousarray(bits, np.uint8)
+        frames = np.zeros(1632 * capacity, np.uint8)
+        nf = self.o.orc_tsdef_work_cap(self.h, P(bits), bits.size, P(frames), capacity, P(self.errs)) if bits.size else 0
+        assert nf <= capacity, (nf, capacity)
+        return frames[:1632 * nf].reshape(nf, 1632), (int(self.errs[0]), int(self.errs[1]))
 
 
 def rs_decodes(o, pkt204):

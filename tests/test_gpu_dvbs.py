@@ -44,10 +44,10 @@ def test_ccdec_chained_blocks_bit_exact(engine, pkg, frame):
     dec.close()
 
 
-def _check_viterbi(names, soft, gb, gn, gs, thr, max_outsync):
+def _check_viterbi(names, soft, gb, gn, gs, thr, max_outsync, want=None):
+    """want: the oracle's (bits, counts, stats) per stream where the caller has them already"""
     for s, name in enumerate(names):
-        v = od.OracleViterbi(thr, max_outsync)
-        eb, en, es = v.work(soft[s])
+        eb, en, es = want[s] if want is not None else od.OracleViterbi(thr, max_outsync).work(soft[s])
         assert (gn[s] == en).all(), (name, gn[s], en)
         assert (gs[s] == es).all(), (name, gs[s], es)
         for b in range(soft.shape[1]):
@@ -82,6 +82,28 @@ def test_viterbi_dvbs_bit_exact(engine, pkg):
     gb3, gn3, gs3 = vit.work(d[:, :3].contiguous())
     assert (gn3.cpu().numpy() == gn[:, :3]).all() and (gs3.cpu().numpy() == gs[:, :3]).all()
     vit.close()
+
+
+def test_viterbi_lock_search_every_reachable_lock(engine, pkg):
+    """the ST_IDLE search on od.viterbi_lock_streams(): one stream per final lock a coded stream can produce (34 of the 52 hypotheses), coded streams
+    that stay IDLE, locks in the middle of a call at shifts with a leading erasure, and re-locks at the same punctured rate (the de-puncturer's
+    stale got_extra / buf) -- all in one batch, as calls of 3 + 5 blocks; the streams' own preconditions are asserted on the oracle alone"""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    streams = od.viterbi_lock_streams()
+    names = [s[0] for s in streams]
+    soft = np.stack([s[1] for s in streams])
+    wd = od.VITERBI_LOCK_WATCHDOG
+    od.L()
+    with ThreadPoolExecutor(max_workers=16) as ex:
+        want = list(ex.map(lambda x: od.OracleViterbi(0.15, wd).work(x), [s[1] for s in streams]))
+    od.check_viterbi_lock_streams(streams, want)
+    vit = pkg.ViterbiBatch(engine, len(streams), 0.15, wd)
+    d = torch.from_numpy(soft).cuda()
+    parts = [vit.work(d[:, :3].contiguous()), vit.work(d[:, 3:].contiguous())]
+    gb, gn, gs = [torch.cat([p[k] for p in parts], 1).cpu().numpy() for k in range(3)]
+    vit.close()
+    _check_viterbi(names, soft, gb, gn, gs, 0.15, wd, want)
 
 
 def test_viterbi_dvbs_default_watchdog(engine, pkg):

@@ -228,6 +228,38 @@ def test_viterbi_dvbs_matches_reference(thr, max_outsync):
     assert set(locked[:, 2]) == set(range(5)) and set(locked[:, 3]) == {0, 1} and (locked[:, 4] > 1).any() and (seen[:, 1] == 0).any()
 
 
+def _oracle_lock_results(streams):
+    from concurrent.futures import ThreadPoolExecutor
+    od.L()                                                        # (bind the library before the pool starts)
+    with ThreadPoolExecutor(max_workers=16) as ex:
+        return list(ex.map(lambda x: od.OracleViterbi(0.15, od.VITERBI_LOCK_WATCHDOG).work(x, fill=0xA5), [s[1] for s in streams]))
+
+
+def test_viterbi_lock_streams_reach_what_they_are_for():
+    """on the oracle alone: the final locks of the 'lock' streams are the 34 reachable ones, the odd-drop 3/4 and 7/8 streams stay IDLE with count 0,
+    the late streams lock in block 2 at a shift with a leading erasure, and a same-rate re-lock yields other counts than a fresh decoder"""
+    streams = od.viterbi_lock_streams()
+    kinds = [s[2] for s in streams]
+    assert kinds.count('lock') == 34 and kinds.count('idle') >= 4 and kinds.count('late') == 4 and kinds.count('relock') == 2
+    assert {s[3][0] for s in streams if s[2] == 'relock'} == {1, 3} and {s[0][:7] for s in streams if s[2] == 'idle'} == {'idle_r2', 'idle_r4'}
+    od.check_viterbi_lock_streams(streams, _oracle_lock_results(streams))
+
+
+def test_viterbi_lock_streams_match_reference():
+    """the same list through the reference's Viterbi_DVBS: counts, stats rows and the written bits (viterbi_written_bits); rate, phase and shift read 0
+    before the first lock on both sides"""
+    _ref_inner()
+    streams = od.viterbi_lock_streams()
+    wd = od.VITERBI_LOCK_WATCHDOG
+    for (name, soft, kind, lock), (ob, on, os_) in zip(streams, _oracle_lock_results(streams)):
+        eb, en, es = od.RefViterbi(0.15, wd).work(soft, fill=0xA5)
+        assert (on == en).all(), (name, on, en)
+        assert (os_ == es).all(), (name, os_, es)
+        assert np.array_equal(od.viterbi_written_bits(ob, on, os_), od.viterbi_written_bits(eb, en, es)), name
+        first = int(np.argmax(es[:, 1] == 1)) if (es[:, 1] == 1).any() else len(es)
+        assert (es[:first, 2:5] == 0).all() and (os_[:first, 2:5] == 0).all(), name
+
+
 @pytest.mark.parametrize('frame', od.CCDEC_FRAMES)
 def test_ccdec_chained_blocks_match_reference(frame):
     """CCDecoder::work, 4 chained blocks twice over, six input kinds (noise levels, erasures, garbage)"""
