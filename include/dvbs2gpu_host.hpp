@@ -448,22 +448,59 @@ private:
     int nt = 0, cap = 0;
 };
 
+namespace detail {
+/* What the bank classes below share: the engine, the handle and its destruction, need() for the calls that throw, and the sticky
+ * status of the work() that does not.  A: the bank's  Handle,  name ("PsiBank")  and  destroy (a pointer to the C function). */
+template <typename A>
+class Bank {
+public:
+    Bank() {}
+    ~Bank() { release(); }
+    Bank(const Bank&) = delete;
+    Bank& operator=(const Bank&) = delete;
+
+    int status() const { return status_; }
+    const std::string& error() const { return error_; }
+    void clearStatus() { status_ = 0; error_.clear(); }
+
+protected:
+    void release() {
+        if (h) A::destroy(h);
+        h = nullptr;
+    }
+    typename A::Handle* need() {
+        if (!h) throw std::runtime_error(std::string("dvbs2gpu: ") + A::name + " used before init()");
+        return h;
+    }
+    /* a work() that failed with rc: the first failure is kept; returns 0 */
+    int fail(int rc) noexcept {
+        if (status_ == 0) {
+            status_ = rc;
+            try { error_ = h ? dvbs2gpu_last_error() : std::string(A::name) + " used before init()"; } catch (...) {}
+        }
+        return 0;
+    }
+    std::shared_ptr<Engine> eng;
+    typename A::Handle* h = nullptr;
+
+private:
+    int status_ = 0;
+    std::string error_;
+};
+struct TsmonApi { typedef dvbs2gpu_tsmon Handle; static constexpr const char* name = "TSMonitor"; static constexpr auto destroy = &dvbs2gpu_tsmon_destroy; };
+struct PsiApi { typedef dvbs2gpu_psi Handle; static constexpr const char* name = "PsiBank"; static constexpr auto destroy = &dvbs2gpu_psi_destroy; };
+struct T2miApi { typedef dvbs2gpu_t2mi Handle; static constexpr const char* name = "T2miBank"; static constexpr auto destroy = &dvbs2gpu_t2mi_destroy; };
+struct IptsApi { typedef dvbs2gpu_ipts Handle; static constexpr const char* name = "IpTsBank"; static constexpr auto destroy = &dvbs2gpu_ipts_destroy; };
+}   // namespace detail
+
 /* TS monitor for one transport stream (dvbs2gpu_tsmon_*, include/dvbs2gpu.h; an extension, the reference has no counterpart): a block
  * behind BBFrameTSParser or DVBSDemod in a sink handler.  init() and the setters throw like everything above.  work() sits in the
  * data path and does NOT throw: a failing call returns 0 bytes and leaves its code in status() and its text in error(), where they
  * stay (sticky: the first failure is kept, later calls still run) until clearStatus(). */
-class TSMonitor {
+class TSMonitor : public detail::Bank<detail::TsmonApi> {
 public:
-    TSMonitor() {}
-    ~TSMonitor() {
-        if (h) dvbs2gpu_tsmon_destroy(h);
-    }
-    TSMonitor(const TSMonitor&) = delete;
-    TSMonitor& operator=(const TSMonitor&) = delete;
-
     void init(int max_packets, int device = 0) {
-        if (h) dvbs2gpu_tsmon_destroy(h);
-        h = nullptr;
+        release();
         eng = Engine::get(device);
         check(dvbs2gpu_tsmon_create(eng->ctx, 1, max_packets, &h));
     }
@@ -477,16 +514,8 @@ public:
      * 0 on failure (see status()) */
     int work(const uint8_t* ts, int nbytes, uint8_t* out, int buffer_outsize) noexcept {
         const int n = h ? dvbs2gpu_tsmon_work(h, 0, ts, nbytes, out, buffer_outsize) : DVBS2GPU_ERR_ARG;
-        if (n >= 0) return n;
-        if (status_ == 0) {
-            status_ = n;
-            try { error_ = h ? dvbs2gpu_last_error() : "TSMonitor used before init()"; } catch (...) {}
-        }
-        return 0;
+        return n >= 0 ? n : fail(n);
     }
-    int status() const { return status_; }
-    const std::string& error() const { return error_; }
-    void clearStatus() { status_ = 0; error_.clear(); }
 
     dvbs2gpu_tsmon_stats stats() {
         dvbs2gpu_tsmon_stats s;
@@ -501,31 +530,14 @@ public:
         if (n > 0) check(dvbs2gpu_tsmon_get_pid_table(h, 0, rows.data(), n, &n));
         return rows;
     }
-
-private:
-    dvbs2gpu_tsmon* need() {
-        if (!h) throw std::runtime_error("dvbs2gpu: TSMonitor used before init()");
-        return h;
-    }
-    std::shared_ptr<Engine> eng;
-    dvbs2gpu_tsmon* h = nullptr;
-    int status_ = 0;
-    std::string error_;
 };
 
 /* PSI section bank for one transport stream (dvbs2gpu_psi_*, include/dvbs2gpu.h; an extension): PAT / PMT / SI sections of up to 16
  * watched PIDs behind BBFrameTSParser, DVBSDemod or TSMonitor.  init() (a device bank) or initHost() (the library's host
  * implementation, no device) and the setters throw; work() sits in the data path and does NOT throw: a failing call returns 0 bytes
  * and leaves its code in status() and its text in error(), sticky until clearStatus(). */
-class PsiBank {
+class PsiBank : public detail::Bank<detail::PsiApi> {
 public:
-    PsiBank() {}
-    ~PsiBank() {
-        if (h) dvbs2gpu_psi_destroy(h);
-    }
-    PsiBank(const PsiBank&) = delete;
-    PsiBank& operator=(const PsiBank&) = delete;
-
     void init(int max_packets, int max_sections, int device = 0) {
         release();
         eng = Engine::get(device);
@@ -562,16 +574,8 @@ public:
      * 0 on failure (see status(); after DVBS2GPU_ERR_CAPACITY needed() holds the sizes) */
     int work(const uint8_t* ts, int nbytes, uint8_t* out, int buffer_outsize) noexcept {
         const int n = h ? dvbs2gpu_psi_work(h, 0, ts, nbytes, out, buffer_outsize) : DVBS2GPU_ERR_ARG;
-        if (n >= 0) return n;
-        if (status_ == 0) {
-            status_ = n;
-            try { error_ = h ? dvbs2gpu_last_error() : "PsiBank used before init()"; } catch (...) {}
-        }
-        return 0;
+        return n >= 0 ? n : fail(n);
     }
-    int status() const { return status_; }
-    const std::string& error() const { return error_; }
-    void clearStatus() { status_ = 0; error_.clear(); }
     void needed(int* bytes, int* rows) { check(dvbs2gpu_psi_get_needed(need(), 0, bytes, rows)); }
 
     dvbs2gpu_psi_stats stats(int slot = -1) {
@@ -604,45 +608,125 @@ public:
 
 private:
     void release() {
-        if (h) dvbs2gpu_psi_destroy(h);
-        h = nullptr;
+        Bank::release();
         std::fill(watched, watched + 16, -1);
         watched[0] = 0;                                    // a new bank watches the PAT in slot 0
     }
-    dvbs2gpu_psi* need() {
-        if (!h) throw std::runtime_error("dvbs2gpu: PsiBank used before init()");
-        return h;
-    }
-    std::shared_ptr<Engine> eng;
-    dvbs2gpu_psi* h = nullptr;
     int watched[16] = {0, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // slot -> PID, as setWatch left them
-    int status_ = 0;
-    std::string error_;
 };
 
+namespace detail {
+/* What PcrBank, PesBank and EsBank share (the watched-PID banks: dvbs2gpu_pcr_*, dvbs2gpu_pes_*, dvbs2gpu_es_*): everything but
+ * setWatch(), the rate and which PIDs of a PMT followPmts() takes.  A: the bank's C functions and types --  Handle, Stats, StreamStats,
+ * Row;  name ("PcrBank");  create, create_host, destroy, reset, work, get_stats, get_stream_stats, get_row_table (pointers to the C
+ * functions). */
+template <typename A>
+class WatchBank : public Bank<A> {
+public:
+    void init(int max_packets, int max_rows, int device = 0) {
+        release();
+        this->eng = Engine::get(device);
+        check(A::create(this->eng->ctx, 1, max_packets, max_rows, &this->h));
+    }
+    void initHost(int max_packets, int max_rows) {
+        release();
+        check(A::create_host(1, max_packets, max_rows, &this->h));
+    }
+    void reset() { check(A::reset(this->need())); }
+    /* nbytes of whole TS packets in; returns the rows of the call (PcrBank: the records, PCR packets of watched PIDs; PesBank: the
+     * starts, PES packet starts on watched PIDs), 0 on failure (see status()) */
+    int work(const uint8_t* ts, int nbytes) noexcept {
+        const int n = this->h ? A::work(this->h, 0, ts, nbytes) : DVBS2GPU_ERR_ARG;
+        return n >= 0 ? n : this->fail(n);
+    }
+
+    typename A::Stats stats(int slot = -1) {
+        typename A::Stats s;
+        check(A::get_stats(this->need(), 0, slot, &s));
+        return s;
+    }
+    typename A::StreamStats streamStats() {
+        typename A::StreamStats s;
+        check(A::get_stream_stats(this->need(), 0, &s));
+        return s;
+    }
+
+protected:
+    /* the rows of the last work() (the first max_rows) */
+    std::vector<typename A::Row> table() {
+        int n = 0;
+        check(A::get_row_table(this->need(), 0, nullptr, 0, &n));
+        std::vector<typename A::Row> rows((size_t)n);
+        if (n > 0) check(A::get_row_table(this->h, 0, rows.data(), n, &n));
+        return rows;
+    }
+    /* followPmts(): for every PMT that `psi` holds decoded, in the order of its slots, pick(pmt, es, offer) calls offer(pid, extra) for
+     * the PIDs the bank would watch; 0x1FFF and above and PIDs watched already are skipped, the others go to free slots through
+     * set(slot, pid, extra); returns the PIDs that found no free slot */
+    template <typename Pick, typename Set>
+    std::vector<int> followWith(PsiBank& psi, Pick pick, Set set) {
+        std::vector<int> left;
+        for (int slot = 0; slot < 16; ++slot) {
+            dvbs2gpu_psi_pmt pmt;
+            const std::vector<dvbs2gpu_psi_es> es = psi.programMap(slot, &pmt);
+            if (pmt.program_number < 0) continue;
+            pick(pmt, es, [&](int pid, int extra) {
+                if (pid >= 0x1FFF || std::find(watched, watched + 16, pid) != watched + 16 || std::find(left.begin(), left.end(), pid) != left.end()) return;
+                int* free_slot = std::find(watched, watched + 16, -1);
+                if (free_slot == watched + 16) left.push_back(pid);
+                else set((int)(free_slot - watched), pid, extra);
+            });
+        }
+        return left;
+    }
+    int watched[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // slot -> PID, as setWatch left them
+
+private:
+    void release() {
+        Bank<A>::release();
+        std::fill(watched, watched + 16, -1);
+    }
+};
+struct PcrApi {
+    typedef dvbs2gpu_pcr Handle; typedef dvbs2gpu_pcr_stats Stats; typedef dvbs2gpu_pcr_stream_stats StreamStats; typedef dvbs2gpu_pcr_row Row;
+    static constexpr const char* name = "PcrBank";
+    static constexpr auto create = &dvbs2gpu_pcr_create, create_host = &dvbs2gpu_pcr_create_host;
+    static constexpr auto destroy = &dvbs2gpu_pcr_destroy;
+    static constexpr auto reset = &dvbs2gpu_pcr_reset;
+    static constexpr auto work = &dvbs2gpu_pcr_work;
+    static constexpr auto get_stats = &dvbs2gpu_pcr_get_stats;
+    static constexpr auto get_stream_stats = &dvbs2gpu_pcr_get_stream_stats;
+    static constexpr auto get_row_table = &dvbs2gpu_pcr_get_row_table;
+};
+struct PesApi {
+    typedef dvbs2gpu_pes Handle; typedef dvbs2gpu_pes_stats Stats; typedef dvbs2gpu_pes_stream_stats StreamStats; typedef dvbs2gpu_pes_row Row;
+    static constexpr const char* name = "PesBank";
+    static constexpr auto create = &dvbs2gpu_pes_create, create_host = &dvbs2gpu_pes_create_host;
+    static constexpr auto destroy = &dvbs2gpu_pes_destroy;
+    static constexpr auto reset = &dvbs2gpu_pes_reset;
+    static constexpr auto work = &dvbs2gpu_pes_work;
+    static constexpr auto get_stats = &dvbs2gpu_pes_get_stats;
+    static constexpr auto get_stream_stats = &dvbs2gpu_pes_get_stream_stats;
+    static constexpr auto get_row_table = &dvbs2gpu_pes_get_row_table;
+};
+struct EsApi {
+    typedef dvbs2gpu_es Handle; typedef dvbs2gpu_es_stats Stats; typedef dvbs2gpu_es_stream_stats StreamStats; typedef dvbs2gpu_es_row Row;
+    static constexpr const char* name = "EsBank";
+    static constexpr auto create = &dvbs2gpu_es_create, create_host = &dvbs2gpu_es_create_host;
+    static constexpr auto destroy = &dvbs2gpu_es_destroy;
+    static constexpr auto reset = &dvbs2gpu_es_reset;
+    static constexpr auto work = &dvbs2gpu_es_work;
+    static constexpr auto get_stats = &dvbs2gpu_es_get_stats;
+    static constexpr auto get_stream_stats = &dvbs2gpu_es_get_stream_stats;
+    static constexpr auto get_row_table = &dvbs2gpu_es_get_row_table;
+};
+}   // namespace detail
 /* PCR bank for one transport stream (dvbs2gpu_pcr_*, include/dvbs2gpu.h; an extension): PCR repetition, discontinuity and accuracy
  * checks on up to 16 watched PIDs behind BBFrameTSParser, DVBSDemod or TSMonitor.  init() (a device bank) or initHost() (the
  * library's host implementation, no device) and the setters throw; work() sits in the data path and does NOT throw: a failing call
  * returns 0 and leaves its code in status() and its text in error(), sticky until clearStatus(). */
-class PcrBank {
+class PcrBank : public detail::WatchBank<detail::PcrApi> {
 public:
-    PcrBank() {}
-    ~PcrBank() {
-        if (h) dvbs2gpu_pcr_destroy(h);
-    }
-    PcrBank(const PcrBank&) = delete;
-    PcrBank& operator=(const PcrBank&) = delete;
-
-    void init(int max_packets, int max_rows, int device = 0) {
-        release();
-        eng = Engine::get(device);
-        check(dvbs2gpu_pcr_create(eng->ctx, 1, max_packets, max_rows, &h));
-    }
-    void initHost(int max_packets, int max_rows) {
-        release();
-        check(dvbs2gpu_pcr_create_host(1, max_packets, max_rows, &h));
-    }
-    void reset() { check(dvbs2gpu_pcr_reset(need())); }
     /* slot 0..15; pid -1 clears the slot */
     void setWatch(int slot, int pid) {
         check(dvbs2gpu_pcr_set_watch(need(), 0, slot, pid));
@@ -653,43 +737,8 @@ public:
     /* watches the PCR PIDs of the PMTs that `psi` holds decoded, in free slots, in the order of its slots; 0x1FFF and PIDs watched
      * already are skipped; returns the PIDs that found no free slot */
     std::vector<int> followPmts(PsiBank& psi) {
-        std::vector<int> left;
-        for (int slot = 0; slot < 16; ++slot) {
-            dvbs2gpu_psi_pmt pmt;
-            psi.programMap(slot, &pmt);
-            const int pid = pmt.pcr_pid;
-            if (pmt.program_number < 0 || pid < 0 || pid == 0x1FFF || std::find(watched, watched + 16, pid) != watched + 16 ||
-                std::find(left.begin(), left.end(), pid) != left.end())
-                continue;
-            int* free_slot = std::find(watched, watched + 16, -1);
-            if (free_slot == watched + 16) left.push_back(pid);
-            else setWatch((int)(free_slot - watched), pid);
-        }
-        return left;
-    }
-    /* nbytes of whole TS packets in; returns the records (PCR packets of watched PIDs) of the call, 0 on failure (see status()) */
-    int work(const uint8_t* ts, int nbytes) noexcept {
-        const int n = h ? dvbs2gpu_pcr_work(h, 0, ts, nbytes) : DVBS2GPU_ERR_ARG;
-        if (n >= 0) return n;
-        if (status_ == 0) {
-            status_ = n;
-            try { error_ = h ? dvbs2gpu_last_error() : "PcrBank used before init()"; } catch (...) {}
-        }
-        return 0;
-    }
-    int status() const { return status_; }
-    const std::string& error() const { return error_; }
-    void clearStatus() { status_ = 0; error_.clear(); }
-
-    dvbs2gpu_pcr_stats stats(int slot = -1) {
-        dvbs2gpu_pcr_stats s;
-        check(dvbs2gpu_pcr_get_stats(need(), 0, slot, &s));
-        return s;
-    }
-    dvbs2gpu_pcr_stream_stats streamStats() {
-        dvbs2gpu_pcr_stream_stats s;
-        check(dvbs2gpu_pcr_get_stream_stats(need(), 0, &s));
-        return s;
+        return followWith(psi, [](const dvbs2gpu_psi_pmt& pmt, const std::vector<dvbs2gpu_psi_es>&, auto offer) { if (pmt.pcr_pid >= 0) offer(pmt.pcr_pid, 0); },
+                          [this](int slot, int pid, int) { setWatch(slot, pid); });
     }
     /* bit/s as the slot's PCRs give it; 0 with no pairs */
     double rate(int slot = -1) {
@@ -698,54 +747,15 @@ public:
         return v;
     }
     /* one row per PCR of the last work(), in input order (the first max_rows) */
-    std::vector<dvbs2gpu_pcr_row> rowTable() {
-        int n = 0;
-        check(dvbs2gpu_pcr_get_row_table(need(), 0, nullptr, 0, &n));
-        std::vector<dvbs2gpu_pcr_row> rows((size_t)n);
-        if (n > 0) check(dvbs2gpu_pcr_get_row_table(h, 0, rows.data(), n, &n));
-        return rows;
-    }
-
-private:
-    void release() {
-        if (h) dvbs2gpu_pcr_destroy(h);
-        h = nullptr;
-        std::fill(watched, watched + 16, -1);
-    }
-    dvbs2gpu_pcr* need() {
-        if (!h) throw std::runtime_error("dvbs2gpu: PcrBank used before init()");
-        return h;
-    }
-    std::shared_ptr<Engine> eng;
-    dvbs2gpu_pcr* h = nullptr;
-    int watched[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // slot -> PID, as setWatch left them
-    int status_ = 0;
-    std::string error_;
+    std::vector<dvbs2gpu_pcr_row> rowTable() { return table(); }
 };
 
 /* PES bank for one transport stream (dvbs2gpu_pes_*, include/dvbs2gpu.h; an extension): PES packet starts, PES length checks and
  * PTS / DTS checks on up to 16 watched PIDs behind BBFrameTSParser, DVBSDemod or TSMonitor.  init() (a device bank) or initHost() (the
  * library's host implementation, no device) and the setters throw; work() sits in the data path and does NOT throw: a failing call
  * returns 0 and leaves its code in status() and its text in error(), sticky until clearStatus(). */
-class PesBank {
+class PesBank : public detail::WatchBank<detail::PesApi> {
 public:
-    PesBank() {}
-    ~PesBank() {
-        if (h) dvbs2gpu_pes_destroy(h);
-    }
-    PesBank(const PesBank&) = delete;
-    PesBank& operator=(const PesBank&) = delete;
-
-    void init(int max_packets, int max_rows, int device = 0) {
-        release();
-        eng = Engine::get(device);
-        check(dvbs2gpu_pes_create(eng->ctx, 1, max_packets, max_rows, &h));
-    }
-    void initHost(int max_packets, int max_rows) {
-        release();
-        check(dvbs2gpu_pes_create_host(1, max_packets, max_rows, &h));
-    }
-    void reset() { check(dvbs2gpu_pes_reset(need())); }
     /* slot 0..15; pid -1 clears the slot */
     void setWatch(int slot, int pid) {
         check(dvbs2gpu_pes_set_watch(need(), 0, slot, pid));
@@ -757,96 +767,21 @@ public:
      * PMT's elementary streams; stream types that carry sections and PIDs watched already are skipped; returns the PIDs that found
      * no free slot */
     std::vector<int> followPmts(PsiBank& psi, const std::vector<int>& skip_types = {0x05, 0x0A, 0x0B, 0x0C, 0x0D, 0x86}) {
-        std::vector<int> left;
-        for (int slot = 0; slot < 16; ++slot) {
-            dvbs2gpu_psi_pmt pmt;
-            const std::vector<dvbs2gpu_psi_es> es = psi.programMap(slot, &pmt);
-            if (pmt.program_number < 0) continue;
-            for (const dvbs2gpu_psi_es& e : es) {
-                const int pid = e.elementary_pid;
-                if (std::find(skip_types.begin(), skip_types.end(), (int)e.stream_type) != skip_types.end() || pid >= 0x1FFF ||
-                    std::find(watched, watched + 16, pid) != watched + 16 || std::find(left.begin(), left.end(), pid) != left.end())
-                    continue;
-                int* free_slot = std::find(watched, watched + 16, -1);
-                if (free_slot == watched + 16) left.push_back(pid);
-                else setWatch((int)(free_slot - watched), pid);
-            }
-        }
-        return left;
-    }
-    /* nbytes of whole TS packets in; returns the starts (PES packet starts on watched PIDs) of the call, 0 on failure (see status()) */
-    int work(const uint8_t* ts, int nbytes) noexcept {
-        const int n = h ? dvbs2gpu_pes_work(h, 0, ts, nbytes) : DVBS2GPU_ERR_ARG;
-        if (n >= 0) return n;
-        if (status_ == 0) {
-            status_ = n;
-            try { error_ = h ? dvbs2gpu_last_error() : "PesBank used before init()"; } catch (...) {}
-        }
-        return 0;
-    }
-    int status() const { return status_; }
-    const std::string& error() const { return error_; }
-    void clearStatus() { status_ = 0; error_.clear(); }
-
-    dvbs2gpu_pes_stats stats(int slot = -1) {
-        dvbs2gpu_pes_stats s;
-        check(dvbs2gpu_pes_get_stats(need(), 0, slot, &s));
-        return s;
-    }
-    dvbs2gpu_pes_stream_stats streamStats() {
-        dvbs2gpu_pes_stream_stats s;
-        check(dvbs2gpu_pes_get_stream_stats(need(), 0, &s));
-        return s;
+        return followWith(psi, [&](const dvbs2gpu_psi_pmt&, const std::vector<dvbs2gpu_psi_es>& es, auto offer) {
+            for (const dvbs2gpu_psi_es& e : es)
+                if (std::find(skip_types.begin(), skip_types.end(), (int)e.stream_type) == skip_types.end()) offer(e.elementary_pid, 0);
+        }, [this](int slot, int pid, int) { setWatch(slot, pid); });
     }
     /* one row per start of the last work(), in input order (the first max_rows) */
-    std::vector<dvbs2gpu_pes_row> rowTable() {
-        int n = 0;
-        check(dvbs2gpu_pes_get_row_table(need(), 0, nullptr, 0, &n));
-        std::vector<dvbs2gpu_pes_row> rows((size_t)n);
-        if (n > 0) check(dvbs2gpu_pes_get_row_table(h, 0, rows.data(), n, &n));
-        return rows;
-    }
-
-private:
-    void release() {
-        if (h) dvbs2gpu_pes_destroy(h);
-        h = nullptr;
-        std::fill(watched, watched + 16, -1);
-    }
-    dvbs2gpu_pes* need() {
-        if (!h) throw std::runtime_error("dvbs2gpu: PesBank used before init()");
-        return h;
-    }
-    std::shared_ptr<Engine> eng;
-    dvbs2gpu_pes* h = nullptr;
-    int watched[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // slot -> PID, as setWatch left them
-    int status_ = 0;
-    std::string error_;
+    std::vector<dvbs2gpu_pes_row> rowTable() { return table(); }
 };
 /* ES bank for one transport stream (dvbs2gpu_es_*, include/dvbs2gpu.h; an extension): a picture, GOP and parameter-set index of up to
  * 16 watched video PIDs (MPEG-2, H.264, H.265) behind BBFrameTSParser, DVBSDemod or TSMonitor, one row per PES packet start and per
  * reported start code.  init() (a device bank) or initHost() (the library's host implementation, no device) and the setters throw;
  * work() sits in the data path and does NOT throw: a failing call returns 0 and leaves its code in status() and its text in error(),
  * sticky until clearStatus(). */
-class EsBank {
+class EsBank : public detail::WatchBank<detail::EsApi> {
 public:
-    EsBank() {}
-    ~EsBank() {
-        if (h) dvbs2gpu_es_destroy(h);
-    }
-    EsBank(const EsBank&) = delete;
-    EsBank& operator=(const EsBank&) = delete;
-
-    void init(int max_packets, int max_rows, int device = 0) {
-        release();
-        eng = Engine::get(device);
-        check(dvbs2gpu_es_create(eng->ctx, 1, max_packets, max_rows, &h));
-    }
-    void initHost(int max_packets, int max_rows) {
-        release();
-        check(dvbs2gpu_es_create_host(1, max_packets, max_rows, &h));
-    }
-    void reset() { check(dvbs2gpu_es_reset(need())); }
     /* slot 0..15; pid -1 clears the slot; codec DVBS2GPU_ES_MPEG2, _H264 or _H265 */
     void setWatch(int slot, int pid, int codec = 0) {
         check(dvbs2gpu_es_set_watch(need(), 0, slot, pid, codec));
@@ -859,85 +794,21 @@ public:
     /* watches the video PIDs of the PMTs that `psi` holds decoded, in free slots, in the order of its slots and then of each PMT's
      * elementary streams; other stream types and PIDs watched already are skipped; returns the PIDs that found no free slot */
     std::vector<int> followPmts(PsiBank& psi) {
-        std::vector<int> left;
-        for (int slot = 0; slot < 16; ++slot) {
-            dvbs2gpu_psi_pmt pmt;
-            const std::vector<dvbs2gpu_psi_es> es = psi.programMap(slot, &pmt);
-            if (pmt.program_number < 0) continue;
-            for (const dvbs2gpu_psi_es& e : es) {
-                const int pid = e.elementary_pid, codec = codecOf(e.stream_type);
-                if (!codec || pid >= 0x1FFF || std::find(watched, watched + 16, pid) != watched + 16 || std::find(left.begin(), left.end(), pid) != left.end())
-                    continue;
-                int* free_slot = std::find(watched, watched + 16, -1);
-                if (free_slot == watched + 16) left.push_back(pid);
-                else setWatch((int)(free_slot - watched), pid, codec);
-            }
-        }
-        return left;
-    }
-    /* nbytes of whole TS packets in; returns the rows of the call, 0 on failure (see status()) */
-    int work(const uint8_t* ts, int nbytes) noexcept {
-        const int n = h ? dvbs2gpu_es_work(h, 0, ts, nbytes) : DVBS2GPU_ERR_ARG;
-        if (n >= 0) return n;
-        if (status_ == 0) {
-            status_ = n;
-            try { error_ = h ? dvbs2gpu_last_error() : "EsBank used before init()"; } catch (...) {}
-        }
-        return 0;
-    }
-    int status() const { return status_; }
-    const std::string& error() const { return error_; }
-    void clearStatus() { status_ = 0; error_.clear(); }
-
-    dvbs2gpu_es_stats stats(int slot = -1) {
-        dvbs2gpu_es_stats s;
-        check(dvbs2gpu_es_get_stats(need(), 0, slot, &s));
-        return s;
-    }
-    dvbs2gpu_es_stream_stats streamStats() {
-        dvbs2gpu_es_stream_stats s;
-        check(dvbs2gpu_es_get_stream_stats(need(), 0, &s));
-        return s;
+        return followWith(psi, [](const dvbs2gpu_psi_pmt&, const std::vector<dvbs2gpu_psi_es>& es, auto offer) {
+            for (const dvbs2gpu_psi_es& e : es)
+                if (const int codec = codecOf(e.stream_type)) offer(e.elementary_pid, codec);
+        }, [this](int slot, int pid, int codec) { setWatch(slot, pid, codec); });
     }
     /* the rows of the last work(), in row order (the first max_rows) */
-    std::vector<dvbs2gpu_es_row> rows() {
-        int n = 0;
-        check(dvbs2gpu_es_get_row_table(need(), 0, nullptr, 0, &n));
-        std::vector<dvbs2gpu_es_row> r((size_t)n);
-        if (n > 0) check(dvbs2gpu_es_get_row_table(h, 0, r.data(), n, &n));
-        return r;
-    }
-
-private:
-    void release() {
-        if (h) dvbs2gpu_es_destroy(h);
-        h = nullptr;
-        std::fill(watched, watched + 16, -1);
-    }
-    dvbs2gpu_es* need() {
-        if (!h) throw std::runtime_error("dvbs2gpu: EsBank used before init()");
-        return h;
-    }
-    std::shared_ptr<Engine> eng;
-    dvbs2gpu_es* h = nullptr;
-    int watched[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // slot -> PID, as setWatch left them
-    int status_ = 0;
-    std::string error_;
+    std::vector<dvbs2gpu_es_row> rows() { return table(); }
 };
 /* T2-MI bank for one transport stream (dvbs2gpu_t2mi_*, include/dvbs2gpu.h; an extension): the T2-MI packets of a PID behind
  * BBFrameTSParser or TSMonitor are reassembled and checked, and the DVB-T2 BBFRAMEs of the chosen PLP laid back to back for a second
  * BBFrameTSParser in mode-adaptation mode (feed()).  Four slots, each a (PID, PLP) pair and a reassembler of its own.  init() (a device
  * bank) or initHost() (the library's host implementation, no device) and the setters throw; work() sits in the data path and does NOT
  * throw: a failing call returns 0 and leaves its code in status() and its text in error(), sticky until clearStatus(). */
-class T2miBank {
+class T2miBank : public detail::Bank<detail::T2miApi> {
 public:
-    T2miBank() {}
-    ~T2miBank() {
-        if (h) dvbs2gpu_t2mi_destroy(h);
-    }
-    T2miBank(const T2miBank&) = delete;
-    T2miBank& operator=(const T2miBank&) = delete;
-
     void init(int max_packets, int max_rows, int device = 0) {
         release();
         eng = Engine::get(device);
@@ -955,16 +826,8 @@ public:
      * and nothing was consumed) */
     int work(int slot, const uint8_t* ts, int nbytes, uint8_t* bbframes, int buffer_outsize) noexcept {
         const int n = h ? dvbs2gpu_t2mi_work(h, 0, slot, ts, nbytes, bbframes, buffer_outsize) : DVBS2GPU_ERR_ARG;
-        if (n >= 0) return n;
-        if (status_ == 0) {
-            status_ = n;
-            try { error_ = h ? dvbs2gpu_last_error() : "T2miBank used before init()"; } catch (...) {}
-        }
-        return 0;
+        return n >= 0 ? n : fail(n);
     }
-    int status() const { return status_; }
-    const std::string& error() const { return error_; }
-    void clearStatus() { status_ = 0; error_.clear(); }
     /* {bytes, rows} that the slot's last work() needed */
     std::pair<int, int> needed(int slot) {
         int b = 0, r = 0;
@@ -999,35 +862,20 @@ public:
         const std::vector<int> sizes = frameBytes(slot);
         return parser.work(bbframes, sizes.data(), (int)sizes.size(), tsframes, buffer_outsize, out_bytes, needed8);
     }
-
-private:
-    void release() {
-        if (h) dvbs2gpu_t2mi_destroy(h);
-        h = nullptr;
-    }
-    dvbs2gpu_t2mi* need() {
-        if (!h) throw std::runtime_error("dvbs2gpu: T2miBank used before init()");
-        return h;
-    }
-    std::shared_ptr<Engine> eng;
-    dvbs2gpu_t2mi* h = nullptr;
-    int status_ = 0;
-    std::string error_;
 };
 namespace detail {
 /* What MpeBank and UleBank share (the datagram banks: dvbs2gpu_mpe_*, dvbs2gpu_ule_*): everything but setWatch().  A: the bank's C
  * functions and types --  Handle, Stats, Row;  name ("MpeBank");  create, create_host, destroy, reset, work, get_needed, get_stats,
  * get_row_table (pointers to the C functions). */
 template <typename A>
-class DatagramBank {
-public:
-    DatagramBank() {}
-    ~DatagramBank() {
-        if (h) A::destroy(h);
-    }
-    DatagramBank(const DatagramBank&) = delete;
-    DatagramBank& operator=(const DatagramBank&) = delete;
+class DatagramBank : public Bank<A> {
+protected:
+    using Bank<A>::eng;
+    using Bank<A>::h;
+    using Bank<A>::need;
+    using Bank<A>::release;
 
+public:
     void init(int max_packets, int max_rows, int device = 0) {
         release();
         eng = Engine::get(device);
@@ -1043,16 +891,8 @@ public:
      * sizes and nothing was consumed) */
     int work(int slot, const uint8_t* ts, int nbytes, uint8_t* datagrams, int buffer_outsize) noexcept {
         const int n = h ? A::work(h, 0, slot, ts, nbytes, datagrams, buffer_outsize) : DVBS2GPU_ERR_ARG;
-        if (n >= 0) return n;
-        if (status_ == 0) {
-            status_ = n;
-            try { error_ = h ? dvbs2gpu_last_error() : std::string(A::name) + " used before init()"; } catch (...) {}
-        }
-        return 0;
+        return n >= 0 ? n : this->fail(n);
     }
-    int status() const { return status_; }
-    const std::string& error() const { return error_; }
-    void clearStatus() { status_ = 0; error_.clear(); }
     /* {bytes, rows} that the slot's last work() needed */
     std::pair<int, int> needed(int slot) {
         int b = 0, r = 0;
@@ -1073,22 +913,6 @@ public:
         if (n > 0) check(A::get_row_table(h, 0, slot, rows.data(), n, &n));
         return rows;
     }
-
-protected:
-    void release() {
-        if (h) A::destroy(h);
-        h = nullptr;
-    }
-    typename A::Handle* need() {
-        if (!h) throw std::runtime_error(std::string("dvbs2gpu: ") + A::name + " used before init()");
-        return h;
-    }
-
-private:
-    std::shared_ptr<Engine> eng;
-    typename A::Handle* h = nullptr;
-    int status_ = 0;
-    std::string error_;
 };
 struct MpeApi {
     typedef dvbs2gpu_mpe Handle; typedef dvbs2gpu_mpe_stats Stats; typedef dvbs2gpu_mpe_row Row;
@@ -1144,13 +968,8 @@ public:
  * back per flow slot, for TSMonitor and the banks behind it.  init() (a device bank) or initHost() (the library's host implementation,
  * no device) and the setters throw; work() sits in the data path and does NOT throw: a failing call returns false and leaves its code
  * in status() and its text in error(), sticky until clearStatus(). */
-class IpTsBank {
+class IpTsBank : public detail::Bank<detail::IptsApi> {
 public:
-    IpTsBank() {}
-    ~IpTsBank() { release(); }
-    IpTsBank(const IpTsBank&) = delete;
-    IpTsBank& operator=(const IpTsBank&) = delete;
-
     void init(int max_rows, int device = 0) {
         release();
         eng = Engine::get(device);
@@ -1176,16 +995,8 @@ public:
      * needed() has the sizes and nothing was consumed) */
     bool work(const dvbs2gpu_ipts_view& v, uint8_t* const ts[4], int buffer_outsize, int bytes[4]) noexcept {
         const int rc = h ? dvbs2gpu_ipts_work(h, 0, &v, ts, buffer_outsize, bytes) : DVBS2GPU_ERR_ARG;
-        if (rc >= 0) return true;
-        if (status_ == 0) {
-            status_ = rc;
-            try { error_ = h ? dvbs2gpu_last_error() : std::string("IpTsBank used before init()"); } catch (...) {}
-        }
-        return false;
+        return rc >= 0 || fail(rc);
     }
-    int status() const { return status_; }
-    const std::string& error() const { return error_; }
-    void clearStatus() { status_ = 0; error_.clear(); }
     /* the bytes that the slot's last work() needed */
     int needed(int slot) {
         int b = 0;
@@ -1206,20 +1017,6 @@ public:
         if (n > 0) check(dvbs2gpu_ipts_get_row_table(h, 0, rows.data(), n, &n));
         return rows;
     }
-
-private:
-    void release() {
-        if (h) dvbs2gpu_ipts_destroy(h);
-        h = nullptr;
-    }
-    dvbs2gpu_ipts* need() {
-        if (!h) throw std::runtime_error("dvbs2gpu: IpTsBank used before init()");
-        return h;
-    }
-    std::shared_ptr<Engine> eng;
-    dvbs2gpu_ipts* h = nullptr;
-    int status_ = 0;
-    std::string error_;
 };
 }   // namespace dvbs2gpu_host
 #endif

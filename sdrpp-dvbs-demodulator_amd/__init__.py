@@ -469,42 +469,28 @@ PROTOTYPES = {
     'dvbs2gpu_psi_get_section_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
     'dvbs2gpu_psi_get_programs': (_i, [_vp, _i, C.POINTER(PsiPat), C.POINTER(PsiProgram), _i, C.POINTER(_i)]),
     'dvbs2gpu_psi_get_program_map': (_i, [_vp, _i, _i, C.POINTER(PsiPmt), C.POINTER(PsiEs), _i, C.POINTER(_i)]),
-    'dvbs2gpu_pcr_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
-    'dvbs2gpu_pcr_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
-    'dvbs2gpu_pcr_reset': (_i, [_vp]),
-    'dvbs2gpu_pcr_destroy': (None, [_vp]),
-    'dvbs2gpu_pcr_set_watch': (_i, [_vp, _i, _i, _i]),
-    'dvbs2gpu_pcr_set_rate': (_i, [_vp, _i, C.c_uint64, _i]),
-    'dvbs2gpu_pcr_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _vp]),
-    'dvbs2gpu_pcr_work': (_i, [_vp, _i, _vp, _i]),
-    'dvbs2gpu_pcr_get_stats': (_i, [_vp, _i, _i, C.POINTER(PcrStats)]),
-    'dvbs2gpu_pcr_get_stream_stats': (_i, [_vp, _i, C.POINTER(PcrStreamStats)]),
-    'dvbs2gpu_pcr_get_rate': (_i, [_vp, _i, _i, C.POINTER(C.c_double)]),
-    'dvbs2gpu_pcr_get_row_table': (_i, [_vp, _i, C.POINTER(PcrRow), _i, C.POINTER(_i)]),
-    'dvbs2gpu_pcr_get_row_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
-    'dvbs2gpu_pes_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
-    'dvbs2gpu_pes_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
-    'dvbs2gpu_pes_reset': (_i, [_vp]),
-    'dvbs2gpu_pes_destroy': (None, [_vp]),
-    'dvbs2gpu_pes_set_watch': (_i, [_vp, _i, _i, _i]),
-    'dvbs2gpu_pes_set_rate': (_i, [_vp, _i, C.c_uint64]),
-    'dvbs2gpu_pes_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _vp]),
-    'dvbs2gpu_pes_work': (_i, [_vp, _i, _vp, _i]),
-    'dvbs2gpu_pes_get_stats': (_i, [_vp, _i, _i, C.POINTER(PesStats)]),
-    'dvbs2gpu_pes_get_stream_stats': (_i, [_vp, _i, C.POINTER(PesStreamStats)]),
-    'dvbs2gpu_pes_get_row_table': (_i, [_vp, _i, C.POINTER(PesRow), _i, C.POINTER(_i)]),
-    'dvbs2gpu_pes_get_row_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
-    'dvbs2gpu_es_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
-    'dvbs2gpu_es_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
-    'dvbs2gpu_es_reset': (_i, [_vp]),
-    'dvbs2gpu_es_destroy': (None, [_vp]),
-    'dvbs2gpu_es_set_watch': (_i, [_vp, _i, _i, _i, _i]),
-    'dvbs2gpu_es_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _vp]),
-    'dvbs2gpu_es_work': (_i, [_vp, _i, _vp, _i]),
-    'dvbs2gpu_es_get_stats': (_i, [_vp, _i, _i, C.POINTER(EsStats)]),
-    'dvbs2gpu_es_get_stream_stats': (_i, [_vp, _i, C.POINTER(EsStreamStats)]),
-    'dvbs2gpu_es_get_row_table': (_i, [_vp, _i, C.POINTER(EsRow), _i, C.POINTER(_i)]),
-    'dvbs2gpu_es_get_row_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
+}
+# the three watched-PID banks (csrc/watch_bank.h): the same functions but for the prefix, the structures, what set_watch takes behind the
+# PID and the rate functions
+for _p, _St, _SSt, _Row, _watch, _own in (
+        ('pcr', PcrStats, PcrStreamStats, PcrRow, [], {'set_rate': (_i, [_vp, _i, C.c_uint64, _i]), 'get_rate': (_i, [_vp, _i, _i, C.POINTER(C.c_double)])}),
+        ('pes', PesStats, PesStreamStats, PesRow, [], {'set_rate': (_i, [_vp, _i, C.c_uint64])}),
+        ('es', EsStats, EsStreamStats, EsRow, [_i], {})):
+    PROTOTYPES.update({'dvbs2gpu_%s_%s' % (_p, _k): _v for _k, _v in {
+        'create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+        'create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
+        'reset': (_i, [_vp]),
+        'destroy': (None, [_vp]),
+        'set_watch': (_i, [_vp, _i, _i, _i] + _watch),
+        'process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _vp]),
+        'work': (_i, [_vp, _i, _vp, _i]),
+        'get_stats': (_i, [_vp, _i, _i, C.POINTER(_St)]),
+        'get_stream_stats': (_i, [_vp, _i, C.POINTER(_SSt)]),
+        'get_row_table': (_i, [_vp, _i, C.POINTER(_Row), _i, C.POINTER(_i)]),
+        'get_row_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
+        **_own,
+    }.items()})
+PROTOTYPES.update({
     'dvbs2gpu_t2mi_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
     'dvbs2gpu_t2mi_create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
     'dvbs2gpu_t2mi_reset': (_i, [_vp]),
@@ -518,7 +504,7 @@ PROTOTYPES = {
     'dvbs2gpu_t2mi_get_row_table': (_i, [_vp, _i, _i, C.POINTER(T2miRow), _i, C.POINTER(_i)]),
     'dvbs2gpu_t2mi_get_row_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
     'dvbs2gpu_t2mi_get_frame_bytes': (_i, [_vp, _i, _i, C.POINTER(_i), _i, C.POINTER(_i)]),
-}
+})
 # the two datagram banks (csrc/dgram_bank.h): the same functions but for the prefix, the structures and what set_watch takes behind the mask
 for _p, _Lay, _St, _Row, _watch in (('mpe', MpeLayout, MpeStats, MpeRow, []), ('ule', UleLayout, UleStats, UleRow, [_i])):
     PROTOTYPES.update({'dvbs2gpu_%s_%s' % (_p, _k): _v for _k, _v in {
@@ -1681,40 +1667,107 @@ class PsiBank(_TsBank):
         return {k: int(getattr(hdr, k)) for k, _ in PsiPmt._fields_}, [(r.stream_type, r.elementary_pid) for r in rows]
 
 
-class PcrBank(_TsBank):
+class _WatchBank(_TsBank):
+    """what the banks share that judge up to 16 watched PIDs per stream and write one row table per stream (csrc/watch_bank.h; PcrBank,
+    PesBank, EsBank).  A bank names its C prefix (_c) and its row and statistics structures (_Row, _Stats, _StreamStats), gives the row
+    table its public names and adds stream_stats(), follow_pmts() and what it is told beyond the watch list."""
+    SLOTS = 16
+    _c = _Row = _Stats = _StreamStats = None
+
+    def _fn(self, name):
+        return getattr(self.lib, '%s_%s' % (self._c, name))
+
+    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=1024):
+        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
+        h = C.c_void_p()
+        engine._check(self._fn('create')(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
+        self.h = h
+        self._watched = [{} for _ in range(nstreams)]               # per stream: slot -> PID (EsBank: (PID, codec)), as set_watch left them
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096, max_rows=1024):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        self = cls._host(cls._c + '_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
+        self._watched = [{} for _ in range(nstreams)]
+        return self
+
+    def reset(self):
+        """forgets states, positions and counters; watches, rates and codecs stay"""
+        self._check(self._fn('reset')(self.h))
+
+    def set_watch(self, stream, slot, pid, *extra):
+        """pid -1 clears the slot; the slot starts afresh"""
+        self._check(self._fn('set_watch')(self.h, int(stream), int(slot), int(pid), *[int(x) for x in extra]))
+        self._watched[int(stream)].pop(int(slot), None)
+        if pid >= 0:
+            self._watched[int(stream)][int(slot)] = (int(pid), *[int(x) for x in extra]) if extra else int(pid)
+
+    def _follow(self, psi_bank, stream, pick):
+        """watches, in free slots, the PIDs that pick(hdr, es) yields as (pid, what set_watch takes behind it) for each PMT that `psi_bank`
+        holds decoded, in the order of its slots; 0x1FFF and above and PIDs watched already are skipped -> the PIDs that found no free slot"""
+        watched = self._watched[int(stream)]
+        left = []
+        for slot in range(psi_bank.SLOTS):
+            hdr, es = psi_bank.program_map(stream, slot)
+            if hdr['program_number'] < 0:
+                continue
+            for pid, *extra in pick(hdr, es):
+                if pid >= 0x1FFF or pid in [w[0] if extra else w for w in watched.values()] or pid in left:
+                    continue
+                free = [s for s in range(self.SLOTS) if s not in watched]
+                if free:
+                    self.set_watch(stream, free[0], pid, *extra)
+                else:
+                    left.append(pid)
+        return left
+
+    def process(self, ts_tensors, nbytes=None):
+        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all), of any alignment -> the rows (PCR records,
+        PES starts, ES rows) of the call per stream (the table holds the first max_rows of them)"""
+        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
+        nr = (C.c_int * self.nstreams)()
+        self._check(self._fn('process_batch')(self.h, pin, cnt, nr, self.eng._stream()))
+        return list(nr)
+
+    def work(self, ts, stream=0):
+        """one stream, a host buffer: numpy uint8 packets in -> the rows of the call"""
+        import numpy as np
+        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
+        return self._check(self._fn('work')(self.h, int(stream), C.c_void_p(ts.ctypes.data), ts.size))
+
+    def stats(self, stream=0, slot=-1):
+        st = self._Stats()
+        self._check(self._fn('get_stats')(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in self._Stats._fields_}
+
+    def _stream_stats(self, stream):
+        st = self._StreamStats()
+        self._check(self._fn('get_stream_stats')(self.h, int(stream), C.byref(st)))
+        return st
+
+    def _table(self, stream=0):
+        """one dict per row of the last call (the fields of the bank's row structure but `reserved`), in row order"""
+        rows = self._rows(self._fn('get_row_table'), self._Row, int(stream))
+        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS if k != 'reserved'} for r in rows]
+
+    def _table_device(self, stream=0):
+        """(device pointer or None, rows): the same table as the bank's row records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self._fn('get_row_table_device')(self.h, int(stream), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+
+class PcrBank(_WatchBank):
     """PCR bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, PCR bank): PCR repetition, discontinuity and
     accuracy checks on up to 16 watched PIDs per stream, one table row per PCR, in integers on (PCR value, packet position)."""
+    _c, _Row, _Stats, _StreamStats = 'dvbs2gpu_pcr', PcrRow, PcrStats, PcrStreamStats
     _destroy = 'dvbs2gpu_pcr_destroy'
     SLOTS = 16
     FIRST, ANNOUNCED, REPEATED, OK, LATE, JUMP = range(6)
     ACCURACY_ERROR, SATURATED = 1, 2
     DEFAULT_LIMIT_Q6 = 864
     ROW_KEYS = tuple(k for k, _ in PcrRow._fields_)
-
-    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=1024):
-        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
-        h = C.c_void_p()
-        engine._check(self.lib.dvbs2gpu_pcr_create(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
-        self.h = h
-        self._watched = [{} for _ in range(nstreams)]               # per stream: slot -> PID, as set_watch left them
-
-    @classmethod
-    def host(cls, nstreams=1, max_packets=4096, max_rows=1024):
-        """a bank without a device: the library's host implementation of the same rules, behind work()"""
-        self = cls._host('dvbs2gpu_pcr_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
-        self._watched = [{} for _ in range(nstreams)]
-        return self
-
-    def reset(self):
-        """forgets states, positions and counters; watches and rates stay"""
-        self._check(self.lib.dvbs2gpu_pcr_reset(self.h))
-
-    def set_watch(self, stream, slot, pid):
-        """pid -1 clears the slot; the slot starts afresh"""
-        self._check(self.lib.dvbs2gpu_pcr_set_watch(self.h, int(stream), int(slot), int(pid)))
-        self._watched[int(stream)].pop(int(slot), None)
-        if pid >= 0:
-            self._watched[int(stream)][int(slot)] = int(pid)
+    row_table, row_table_device = _WatchBank._table, _WatchBank._table_device
 
     def set_rate(self, stream, ticks_per_packet_q24, limit_q6=DEFAULT_LIMIT_Q6):
         """27 MHz ticks per 188-byte packet in Q24.24 (0: no accuracy check) and the accuracy limit in 1/64 tick"""
@@ -1723,42 +1776,10 @@ class PcrBank(_TsBank):
     def follow_pmts(self, psi_bank, stream=0):
         """watches the PCR PIDs of the PMTs that `psi_bank` (a PsiBank that read the same stream) holds decoded, in free slots, in the
         order of its slots; 0x1FFF (a programme without a PCR) and PIDs watched already are skipped -> the PIDs that found no free slot"""
-        watched = self._watched[int(stream)]
-        left = []
-        for slot in range(psi_bank.SLOTS):
-            hdr = psi_bank.program_map(stream, slot)[0]
-            pid = hdr['pcr_pid']
-            if hdr['program_number'] < 0 or pid < 0 or pid == 0x1FFF or pid in watched.values() or pid in left:
-                continue
-            free = [s for s in range(self.SLOTS) if s not in watched]
-            if free:
-                self.set_watch(stream, free[0], pid)
-            else:
-                left.append(pid)
-        return left
-
-    def process(self, ts_tensors, nbytes=None):
-        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all), of any alignment -> the records of the
-        call per stream (the table holds the first max_rows of them)"""
-        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
-        nr = (C.c_int * self.nstreams)()
-        self._check(self.lib.dvbs2gpu_pcr_process_batch(self.h, pin, cnt, nr, self.eng._stream()))
-        return list(nr)
-
-    def work(self, ts, stream=0):
-        """one stream, a host buffer: numpy uint8 packets in -> the records of the call"""
-        import numpy as np
-        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
-        return self._check(self.lib.dvbs2gpu_pcr_work(self.h, int(stream), C.c_void_p(ts.ctypes.data), ts.size))
-
-    def stats(self, stream=0, slot=-1):
-        st = PcrStats()
-        self._check(self.lib.dvbs2gpu_pcr_get_stats(self.h, int(stream), int(slot), C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in PcrStats._fields_}
+        return self._follow(psi_bank, stream, lambda hdr, es: [(hdr['pcr_pid'],)] if hdr['pcr_pid'] >= 0 else [])
 
     def stream_stats(self, stream=0):
-        st = PcrStreamStats()
-        self._check(self.lib.dvbs2gpu_pcr_get_stream_stats(self.h, int(stream), C.byref(st)))
+        st = self._stream_stats(stream)
         return dict(packets=int(st.packets), unwatched_pcr_packets=int(st.unwatched_pcr_packets), rows_dropped=int(st.rows_dropped),
                     first_unwatched_pid=int(st.first_unwatched_pid), packets_since_pcr=[int(v) for v in st.packets_since_pcr])
 
@@ -1768,21 +1789,11 @@ class PcrBank(_TsBank):
         self._check(self.lib.dvbs2gpu_pcr_get_rate(self.h, int(stream), int(slot), C.byref(v)))
         return v.value
 
-    def row_table(self, stream=0):
-        """one dict per row of the last call (the fields of dvbs2gpu_pcr_row but `reserved`), in input order"""
-        rows = self._rows(self.lib.dvbs2gpu_pcr_get_row_table, PcrRow, int(stream))
-        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS if k != 'reserved'} for r in rows]
 
-    def row_table_device(self, stream=0):
-        """(device pointer or None, rows): the same table as dvbs2gpu_pcr_row records in HBM, valid until the next call"""
-        p, n = C.c_void_p(), C.c_int()
-        self._check(self.lib.dvbs2gpu_pcr_get_row_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
-        return p.value, n.value
-
-
-class PesBank(_TsBank):
+class PesBank(_WatchBank):
     """PES bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, PES bank): PES packet starts, PES length checks and
     PTS / DTS checks on up to 16 watched PIDs per stream, one table row per PES packet start."""
+    _c, _Row, _Stats, _StreamStats = 'dvbs2gpu_pes', PesRow, PesStats, PesStreamStats
     _destroy = 'dvbs2gpu_pes_destroy'
     SLOTS = 16
     SCRAMBLED, SHORT, BAD_START, PLAIN, MALFORMED, HEADER = range(6)
@@ -1791,31 +1802,7 @@ class PesBank(_TsBank):
     NO_TS = (1 << 64) - 1
     SECTION_STREAM_TYPES = (0x05, 0x0A, 0x0B, 0x0C, 0x0D, 0x86)     # private sections, DSM-CC (four types), SCTE 35: they carry sections
     ROW_KEYS = tuple(k for k, _ in PesRow._fields_)
-
-    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=1024):
-        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
-        h = C.c_void_p()
-        engine._check(self.lib.dvbs2gpu_pes_create(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
-        self.h = h
-        self._watched = [{} for _ in range(nstreams)]               # per stream: slot -> PID, as set_watch left them
-
-    @classmethod
-    def host(cls, nstreams=1, max_packets=4096, max_rows=1024):
-        """a bank without a device: the library's host implementation of the same rules, behind work()"""
-        self = cls._host('dvbs2gpu_pes_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
-        self._watched = [{} for _ in range(nstreams)]
-        return self
-
-    def reset(self):
-        """forgets states, positions and counters; watches and rates stay"""
-        self._check(self.lib.dvbs2gpu_pes_reset(self.h))
-
-    def set_watch(self, stream, slot, pid):
-        """pid -1 clears the slot; the slot starts afresh"""
-        self._check(self.lib.dvbs2gpu_pes_set_watch(self.h, int(stream), int(slot), int(pid)))
-        self._watched[int(stream)].pop(int(slot), None)
-        if pid >= 0:
-            self._watched[int(stream)][int(slot)] = int(pid)
+    row_table, row_table_device = _WatchBank._table, _WatchBank._table_device
 
     def set_rate(self, stream, ticks_per_packet_q24):
         """27 MHz ticks per 188-byte packet in Q24.24, the PCR bank's quantity (0: no PTS_LATE)"""
@@ -1825,62 +1812,18 @@ class PesBank(_TsBank):
         """watches the elementary PIDs of the PMTs that `psi_bank` (a PsiBank that read the same stream) holds decoded, in free slots, in
         the order of its slots and then of each PMT's elementary streams; stream types that carry sections (skip_types) and PIDs watched
         already are skipped -> the PIDs that found no free slot"""
-        watched = self._watched[int(stream)]
-        left = []
-        for slot in range(psi_bank.SLOTS):
-            hdr, es = psi_bank.program_map(stream, slot)
-            if hdr['program_number'] < 0:
-                continue
-            for stream_type, pid in es:
-                if stream_type in skip_types or pid >= 0x1FFF or pid in watched.values() or pid in left:
-                    continue
-                free = [s for s in range(self.SLOTS) if s not in watched]
-                if free:
-                    self.set_watch(stream, free[0], pid)
-                else:
-                    left.append(pid)
-        return left
-
-    def process(self, ts_tensors, nbytes=None):
-        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all), of any alignment -> the starts of the
-        call per stream (the table holds the first max_rows of them)"""
-        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
-        nr = (C.c_int * self.nstreams)()
-        self._check(self.lib.dvbs2gpu_pes_process_batch(self.h, pin, cnt, nr, self.eng._stream()))
-        return list(nr)
-
-    def work(self, ts, stream=0):
-        """one stream, a host buffer: numpy uint8 packets in -> the starts of the call"""
-        import numpy as np
-        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
-        return self._check(self.lib.dvbs2gpu_pes_work(self.h, int(stream), C.c_void_p(ts.ctypes.data), ts.size))
-
-    def stats(self, stream=0, slot=-1):
-        st = PesStats()
-        self._check(self.lib.dvbs2gpu_pes_get_stats(self.h, int(stream), int(slot), C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in PesStats._fields_}
+        return self._follow(psi_bank, stream, lambda hdr, es: [(pid,) for stream_type, pid in es if stream_type not in skip_types])
 
     def stream_stats(self, stream=0):
-        st = PesStreamStats()
-        self._check(self.lib.dvbs2gpu_pes_get_stream_stats(self.h, int(stream), C.byref(st)))
+        st = self._stream_stats(stream)
         return dict(packets=int(st.packets), rows_dropped=int(st.rows_dropped), packets_since_start=[int(v) for v in st.packets_since_start])
 
-    def row_table(self, stream=0):
-        """one dict per row of the last call (the fields of dvbs2gpu_pes_row but `reserved`), in input order"""
-        rows = self._rows(self.lib.dvbs2gpu_pes_get_row_table, PesRow, int(stream))
-        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS if k != 'reserved'} for r in rows]
 
-    def row_table_device(self, stream=0):
-        """(device pointer or None, rows): the same table as dvbs2gpu_pes_row records in HBM, valid until the next call"""
-        p, n = C.c_void_p(), C.c_int()
-        self._check(self.lib.dvbs2gpu_pes_get_row_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
-        return p.value, n.value
-
-
-class EsBank(_TsBank):
+class EsBank(_WatchBank):
     """ES bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, ES bank): every payload byte of up to 16 watched video
     PIDs per stream is scanned for start codes; one table row per PES packet start and per picture, sequence header / SPS, GOP header,
     parameter set, access unit delimiter and sequence end, with its position in the elementary stream."""
+    _c, _Row, _Stats, _StreamStats = 'dvbs2gpu_es', EsRow, EsStats, EsStreamStats
     _destroy = 'dvbs2gpu_es_destroy'
     SLOTS = 16
     MPEG2, H264, H265 = 1, 2, 3
@@ -1890,87 +1833,30 @@ class EsBank(_TsBank):
     NO_TS = (1 << 64) - 1
     STREAM_TYPE_CODECS = {0x01: 1, 0x02: 1, 0x1B: 2, 0x24: 3}       # PMT stream_type -> codec
     ROW_KEYS = tuple(k for k, _ in EsRow._fields_)
+    rows, rows_device = _WatchBank._table, _WatchBank._table_device
 
     def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=4096):
-        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
-        h = C.c_void_p()
-        engine._check(self.lib.dvbs2gpu_es_create(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
-        self.h = h
-        self._watched = [{} for _ in range(nstreams)]               # per stream: slot -> (PID, codec), as set_watch left them
+        super().__init__(engine, nstreams, max_packets, max_rows)
 
     @classmethod
     def host(cls, nstreams=1, max_packets=4096, max_rows=4096):
         """a bank without a device: the library's host implementation of the same rules, behind work()"""
-        self = cls._host('dvbs2gpu_es_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
-        self._watched = [{} for _ in range(nstreams)]
-        return self
-
-    def reset(self):
-        """forgets states, positions and counters; the watches stay"""
-        self._check(self.lib.dvbs2gpu_es_reset(self.h))
+        return super().host(nstreams, max_packets, max_rows)
 
     def set_watch(self, stream, slot, pid, codec=0):
         """pid -1 clears the slot; the slot starts afresh"""
-        self._check(self.lib.dvbs2gpu_es_set_watch(self.h, int(stream), int(slot), int(pid), int(codec)))
-        self._watched[int(stream)].pop(int(slot), None)
-        if pid >= 0:
-            self._watched[int(stream)][int(slot)] = (int(pid), int(codec))
+        super().set_watch(stream, slot, pid, codec)
 
     def follow_pmts(self, psi_bank, stream=0):
         """watches the video PIDs of the PMTs that `psi_bank` (a PsiBank that read the same stream) holds decoded -- stream types 0x01 and
         0x02 as MPEG2, 0x1B as H264, 0x24 as H265, everything else skipped -- in free slots, in the order of its slots and then of each
         PMT's elementary streams; PIDs watched already are skipped -> the PIDs that found no free slot"""
-        watched = self._watched[int(stream)]
-        left = []
-        for slot in range(psi_bank.SLOTS):
-            hdr, es = psi_bank.program_map(stream, slot)
-            if hdr['program_number'] < 0:
-                continue
-            for stream_type, pid in es:
-                codec = self.STREAM_TYPE_CODECS.get(stream_type)
-                if codec is None or pid >= 0x1FFF or pid in [p for p, _ in watched.values()] or pid in left:
-                    continue
-                free = [s for s in range(self.SLOTS) if s not in watched]
-                if free:
-                    self.set_watch(stream, free[0], pid, codec)
-                else:
-                    left.append(pid)
-        return left
-
-    def process(self, ts_tensors, nbytes=None):
-        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all), of any alignment -> the rows of the
-        call per stream (the table holds the first max_rows of them)"""
-        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
-        nr = (C.c_int * self.nstreams)()
-        self._check(self.lib.dvbs2gpu_es_process_batch(self.h, pin, cnt, nr, self.eng._stream()))
-        return list(nr)
-
-    def work(self, ts, stream=0):
-        """one stream, a host buffer: numpy uint8 packets in -> the rows of the call"""
-        import numpy as np
-        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
-        return self._check(self.lib.dvbs2gpu_es_work(self.h, int(stream), C.c_void_p(ts.ctypes.data), ts.size))
-
-    def stats(self, stream=0, slot=-1):
-        st = EsStats()
-        self._check(self.lib.dvbs2gpu_es_get_stats(self.h, int(stream), int(slot), C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in EsStats._fields_}
+        codecs = self.STREAM_TYPE_CODECS
+        return self._follow(psi_bank, stream, lambda hdr, es: [(pid, codecs[stream_type]) for stream_type, pid in es if stream_type in codecs])
 
     def stream_stats(self, stream=0):
-        st = EsStreamStats()
-        self._check(self.lib.dvbs2gpu_es_get_stream_stats(self.h, int(stream), C.byref(st)))
+        st = self._stream_stats(stream)
         return dict(packets=int(st.packets), rows_dropped=int(st.rows_dropped))
-
-    def rows(self, stream=0):
-        """one dict per row of the last call (the fields of dvbs2gpu_es_row but `reserved`), in row order"""
-        rows = self._rows(self.lib.dvbs2gpu_es_get_row_table, EsRow, int(stream))
-        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS if k != 'reserved'} for r in rows]
-
-    def rows_device(self, stream=0):
-        """(device pointer or None, rows): the same table as dvbs2gpu_es_row records in HBM, valid until the next call"""
-        p, n = C.c_void_p(), C.c_int()
-        self._check(self.lib.dvbs2gpu_es_get_row_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
-        return p.value, n.value
 
 
 class T2miBank(_TsBank):

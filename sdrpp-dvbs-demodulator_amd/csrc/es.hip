@@ -26,6 +26,7 @@
 // second scan of packets that hold codes with rows.  One device-to-host copy of the per-stream call record (EsCall).
 // Vector stores and plain C++ only.
 #include "ts_watch.h"
+#include "watch_bank.h"
 #include "es_rules.h"
 
 using namespace s2;
@@ -329,198 +330,66 @@ __global__ void __launch_bounds__(ES_WG) es_kernel(const uint8_t* const* __restr
 
 }  // namespace s2
 
-struct dvbs2gpu_es {
-    dvbs2gpu_ctx* ctx = nullptr;                   // null: a host-only bank (dvbs2gpu_es_create_host)
-    int nstreams = 0, max_packets = 0, max_rows = 0;
-    std::vector<int32_t> watch, codec;             // nstreams x 16
-    std::vector<dvbs2gpu_es_stats> stats;          // nstreams x 16, since reset; the kernel reports each call's share (EsCall)
-    std::vector<dvbs2gpu_es_stream_stats> sstats;
-    std::vector<int> nrows, total;                 // of the last call per stream: rows in the table, rows in all
-    std::vector<EsCall> h_call;
-    std::vector<char> h_args;
-    // device banks
-    DevBuf<int32_t> d_watch, d_codec;
-    DevBuf<EsState> d_state;
-    DevBuf<int64_t> d_pos;
-    DevBuf<EsRow> d_rows;                          // nstreams x max_rows
-    DevBuf<EsCall> d_call;
-    DevBuf<uint8_t> d_args;                        // TsBankArgs(nstreams)
-    TsHostStage stage;                             // of the host-buffer entry point
-    // host-only banks
-    std::vector<EsHostStream> host;
-};
+// the host half is the watched-PID bank's (watch_bank.h); here what is the bank's own
+struct EsBankD {
+    static constexpr int SLOTS = ES_SLOTS, MAX_PACKETS = ES_MAX_PACKETS;
+    typedef EsState State; typedef EsRow Row; typedef EsCall Call; typedef EsHostStream HostStream;
+    typedef dvbs2gpu_es_stats Stats; typedef dvbs2gpu_es_stream_stats StreamStats;
+    static constexpr int SUMS = ES_COUNTERS;           // every word of dvbs2gpu_es_stats is a counter
+    static constexpr StreamStats NO_STREAM_STATS = {};
+    typedef int32_t Config;                            // the codec, per slot
+    static constexpr int CONFIGS = ES_SLOTS;
+    static constexpr Config NO_CONFIG = ES_NONE;
+    static constexpr const char *BANK = "ES bank: ", *CNAME = "dvbs2gpu_es", *ALLOC = "hipMalloc(es)";
 
-namespace s2 {
-// one stream's call into its statistics; `n` packets came
-static void es_account(dvbs2gpu_es* b, int i, int n, const EsCallHead& head, const EsCnt* c) {
-    dvbs2gpu_es_stream_stats& ss = b->sstats[i];
-    for (int s = 0; s < ES_SLOTS; ++s) {
-        if (!c[s].packets) continue;                   // (no packet of the slot's PID came: every counter is 0)
-        const int32_t* a = reinterpret_cast<const int32_t*>(&c[s]);
-        int64_t* d = reinterpret_cast<int64_t*>(&b->stats[(size_t)i * ES_SLOTS + s]);
-        for (int k = 0; k < ES_COUNTERS; ++k) d[k] += a[k];
+    // one stream's call into its statistics; `n` packets came
+    static void account(WatchBank<EsBankD>& b, int i, int n, const EsCallHead& head, const EsCnt* c) {
+        dvbs2gpu_es_stream_stats& ss = b.sstats[i];
+        for (int s = 0; s < ES_SLOTS; ++s) {
+            if (!c[s].packets) continue;                   // (no packet of the slot's PID came: every counter is 0)
+            const int32_t* a = reinterpret_cast<const int32_t*>(&c[s]);
+            int64_t* d = reinterpret_cast<int64_t*>(&b.stats[(size_t)i * ES_SLOTS + s]);
+            for (int k = 0; k < ES_COUNTERS; ++k) d[k] += a[k];
+        }
+        ss.packets += n;
+        if (head.rows > b.max_rows) ss.rows_dropped += head.rows - b.max_rows;
+        b.total[i] = head.rows;
+        b.nrows[i] = head.rows < b.max_rows ? head.rows : b.max_rows;
     }
-    ss.packets += n;
-    if (head.rows > b->max_rows) ss.rows_dropped += head.rows - b->max_rows;
-    b->total[i] = head.rows;
-    b->nrows[i] = head.rows < b->max_rows ? head.rows : b->max_rows;
-}
-static bool es_create_args_ok(int nstreams, int max_packets, int max_rows, dvbs2gpu_es** out) {
-    if (!out || nstreams <= 0 || max_packets <= 0 || max_rows <= 0) return false;
-    if (max_packets > ES_MAX_PACKETS) { g_err = "ES bank: max_packets is at most 4096 per stream and call"; return false; }
-    return true;
-}
-static std::unique_ptr<dvbs2gpu_es> es_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows) {
-    std::unique_ptr<dvbs2gpu_es> b(new dvbs2gpu_es());
-    b->ctx = ctx; b->nstreams = nstreams; b->max_packets = max_packets; b->max_rows = max_rows;
-    b->watch.assign((size_t)nstreams * ES_SLOTS, -1);
-    b->codec.assign((size_t)nstreams * ES_SLOTS, ES_NONE);
-    b->stats.assign((size_t)nstreams * ES_SLOTS, dvbs2gpu_es_stats{});
-    b->sstats.assign(nstreams, dvbs2gpu_es_stream_stats{});
-    b->nrows.assign(nstreams, 0); b->total.assign(nstreams, 0);
-    b->h_call.resize(nstreams);
-    return b;
-}
-}  // namespace s2
+    static void launch(WatchBank<EsBankD>& b, const TsBankArgs& a, hipStream_t st) {
+        const size_t lds = es_lds_bytes(b.max_packets);        // <= 51.3 KiB
+        hipLaunchKernelGGL(es_kernel, dim3(b.nstreams), dim3(ES_WG), lds, st, a.in(b.d_args), a.nbytes(b.d_args), b.max_packets, b.max_rows, b.d_watch, b.d_cfg, b.d_state,
+                           b.d_pos, b.d_rows, b.d_call);
+    }
+    static void fix_stream_stats(StreamStats*) {}
+};
+struct dvbs2gpu_es : WatchBank<EsBankD> {};
 
 extern "C" {
 
 void dvbs2gpu_es_destroy(dvbs2gpu_es* b) { delete b; }
-
-int dvbs2gpu_es_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_es** out) {
-    if (!ctx || !es_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    auto b = es_new(ctx, nstreams, max_packets, max_rows);
-    const size_t n = (size_t)nstreams, ns = n * ES_SLOTS;
-    const char* what = "hipMalloc(es)";                // (zero-filled: the slots' states and the positions; the kernel writes rows and call records before they are read)
-    RC_TRY(b->d_watch.alloc(ns, false, what));
-    HIP_TRY(hipMemcpy(b->d_watch, b->watch.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice));
-    RC_TRY(b->d_codec.alloc(ns, true, what));
-    RC_TRY(b->d_state.alloc(ns, true, what));
-    RC_TRY(b->d_pos.alloc(n, true, what));
-    RC_TRY(b->d_rows.alloc(n * max_rows, false, what));
-    RC_TRY(b->d_call.alloc(n, false, what));
-    RC_TRY(b->d_args.alloc(TsBankArgs(n).L.bytes(), false, what));
-    b->h_args.resize(TsBankArgs(n).L.bytes());
-    *out = b.release();
-    return 0;
-}
-
-int dvbs2gpu_es_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_es** out) {
-    if (!es_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
-    auto b = es_new(nullptr, nstreams, max_packets, max_rows);
-    b->host.resize(nstreams);
-    *out = b.release();
-    return 0;
-}
-
-int dvbs2gpu_es_reset(dvbs2gpu_es* b) {
-    if (!b) return DVBS2GPU_ERR_ARG;
-    if (b->ctx) {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        HIP_TRY(hipMemset(b->d_state, 0, (size_t)b->nstreams * ES_SLOTS * sizeof(EsState)));
-        HIP_TRY(hipMemset(b->d_pos, 0, (size_t)b->nstreams * sizeof(int64_t)));
-    }
-    for (auto& h : b->host) h.reset();
-    std::fill(b->stats.begin(), b->stats.end(), dvbs2gpu_es_stats{});
-    std::fill(b->sstats.begin(), b->sstats.end(), dvbs2gpu_es_stream_stats{});
-    std::fill(b->nrows.begin(), b->nrows.end(), 0);
-    std::fill(b->total.begin(), b->total.end(), 0);
-    return 0;
-}
+int dvbs2gpu_es_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_es** out) { return watch_create(true, ctx, nstreams, max_packets, max_rows, out); }
+int dvbs2gpu_es_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_es** out) { return watch_create(false, nullptr, nstreams, max_packets, max_rows, out); }
+int dvbs2gpu_es_reset(dvbs2gpu_es* b) { return watch_reset(b); }
 
 int dvbs2gpu_es_set_watch(dvbs2gpu_es* b, int stream, int slot, int pid, int codec) {
-    if (!b || stream < 0 || stream >= b->nstreams || slot < 0 || slot >= ES_SLOTS) return DVBS2GPU_ERR_ARG;
-    if (pid < -1 || pid >= TSMON_NULL_PID) { g_err = "ES bank: a watched PID is 0..0x1FFE (-1 clears the slot)"; return DVBS2GPU_ERR_ARG; }
+    if (!watch_slot_ok(b, stream, slot, pid)) return DVBS2GPU_ERR_ARG;
     if (pid >= 0 && (codec < ES_MPEG2 || codec > ES_H265)) { g_err = "ES bank: the codec is DVBS2GPU_ES_MPEG2, _H264 or _H265"; return DVBS2GPU_ERR_ARG; }
-    int32_t* w = b->watch.data() + (size_t)stream * ES_SLOTS;
-    for (int s = 0; s < ES_SLOTS; ++s)
-        if (pid >= 0 && s != slot && w[s] == pid) { g_err = "ES bank: the PID is watched in another slot of the stream"; return DVBS2GPU_ERR_ARG; }
+    if (const int e = watch_set_watch(b, stream, slot, pid)) return e;
     const size_t at = (size_t)stream * ES_SLOTS + slot;
-    w[slot] = pid;
-    b->codec[at] = pid >= 0 ? codec : ES_NONE;
-    b->stats[at] = dvbs2gpu_es_stats{};
-    if (b->ctx) {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        HIP_TRY(hipMemcpy(b->d_watch + at, &w[slot], sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b->d_codec + at, &b->codec[at], sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(b->d_state + at, 0, sizeof(EsState)));
-    } else {
-        b->host[stream].watch[slot] = pid;
-        b->host[stream].codec[slot] = b->codec[at];
-        b->host[stream].clear_slot(slot);
-    }
+    b->cfg[at] = pid >= 0 ? codec : ES_NONE;
+    if (b->ctx) return watch_upload_config(b, at);
+    b->host[stream].codec[slot] = b->cfg[at];
     return 0;
 }
 
 int dvbs2gpu_es_process_batch(dvbs2gpu_es* b, const uint8_t* const* d_ts, const int* nbytes, int* out_rows, void* stream) {
-    if (!b || !d_ts || !nbytes) return DVBS2GPU_ERR_ARG;
-    if (!b->ctx) { g_err = "ES bank: a host bank takes host buffers (dvbs2gpu_es_work)"; return DVBS2GPU_ERR_ARG; }
-    const int n = b->nstreams;
-    for (int i = 0; i < n; ++i) {
-        if (!ts_bank_check_counts("ES bank: ", nbytes + i, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
-        if (nbytes[i] > 0 && !d_ts[i]) { g_err = "ES bank: null buffer"; return DVBS2GPU_ERR_ARG; }
-    }
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const TsBankArgs a(n);
-    a.fill(b->h_args.data(), n, d_ts, nullptr, nbytes);
-    HIP_TRY(hipMemcpyAsync(b->d_args, b->h_args.data(), b->h_args.size(), hipMemcpyHostToDevice, st));
-    const size_t lds = es_lds_bytes(b->max_packets);       // <= 51.3 KiB
-    hipLaunchKernelGGL(es_kernel, dim3(n), dim3(ES_WG), lds, st, a.in(b->d_args), a.nbytes(b->d_args), b->max_packets, b->max_rows, b->d_watch, b->d_codec, b->d_state,
-                       b->d_pos, b->d_rows, b->d_call);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_call.data(), b->d_call, sizeof(EsCall) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int i = 0; i < n; ++i) {
-        es_account(b, i, nbytes[i] / TSMON_TS, b->h_call[i].head, b->h_call[i].cnt);
-        if (out_rows) out_rows[i] = b->total[i];
-    }
-    return 0;
+    return watch_process_batch(b, d_ts, nbytes, out_rows, stream);
 }
-
-int dvbs2gpu_es_work(dvbs2gpu_es* b, int stream, const uint8_t* h_ts, int nbytes) {
-    if (!b || stream < 0 || stream >= b->nstreams || nbytes < 0 || (nbytes > 0 && !h_ts)) return DVBS2GPU_ERR_ARG;
-    if (!ts_bank_check_counts("ES bank: ", &nbytes, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
-    if (!b->ctx) {
-        for (int i = 0; i < b->nstreams; ++i) {        // the other streams receive an empty call
-            EsHostStream& h = b->host[i];
-            const int np = i == stream ? nbytes / TSMON_TS : 0;
-            h.run(h_ts, np, b->max_rows);
-            es_account(b, i, np, h.head, h.cnt);
-        }
-        return b->total[stream];
-    }
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    const int rc = ts_bank_work(b->stage, b->nstreams, stream, h_ts, nbytes, b->max_packets, nullptr, 0, false, [&](const uint8_t* const* in, const int* nb, uint8_t* const*, int*) {
-        return dvbs2gpu_es_process_batch(b, in, nb, nullptr, nullptr);
-    });
-    return rc < 0 ? rc : b->total[stream];
-}
-
-int dvbs2gpu_es_get_stats(dvbs2gpu_es* b, int stream, int slot, dvbs2gpu_es_stats* h_out) {
-    if (!b || stream < 0 || stream >= b->nstreams || slot < -1 || slot >= ES_SLOTS || !h_out) return DVBS2GPU_ERR_ARG;
-    *h_out = dvbs2gpu_es_stats{};
-    for (int s = slot < 0 ? 0 : slot; s < (slot < 0 ? ES_SLOTS : slot + 1); ++s) {
-        const int64_t* src = reinterpret_cast<const int64_t*>(&b->stats[(size_t)stream * ES_SLOTS + s]);
-        int64_t* d = reinterpret_cast<int64_t*>(h_out);
-        for (int k = 0; k < ES_COUNTERS; ++k) d[k] += src[k];
-    }
-    return 0;
-}
-
-int dvbs2gpu_es_get_stream_stats(dvbs2gpu_es* b, int stream, dvbs2gpu_es_stream_stats* h_out) {
-    if (!b || stream < 0 || stream >= b->nstreams || !h_out) return DVBS2GPU_ERR_ARG;
-    *h_out = b->sstats[stream];
-    return 0;
-}
-
-int dvbs2gpu_es_get_row_table(dvbs2gpu_es* b, int stream, dvbs2gpu_es_row* h_rows, int cap, int* n) {
-    return ts_bank_rows(b, &dvbs2gpu_es::max_rows, stream, h_rows, cap, n);
-}
-
-int dvbs2gpu_es_get_row_table_device(dvbs2gpu_es* b, int stream, const dvbs2gpu_es_row** d_rows, int* n) {
-    return ts_bank_rows_device(b, &dvbs2gpu_es::max_rows, stream, d_rows, n);
-}
+int dvbs2gpu_es_work(dvbs2gpu_es* b, int stream, const uint8_t* h_ts, int nbytes) { return watch_work(b, stream, h_ts, nbytes); }
+int dvbs2gpu_es_get_stats(dvbs2gpu_es* b, int stream, int slot, dvbs2gpu_es_stats* h_out) { return watch_get_stats(b, stream, slot, h_out); }
+int dvbs2gpu_es_get_stream_stats(dvbs2gpu_es* b, int stream, dvbs2gpu_es_stream_stats* h_out) { return watch_get_stream_stats(b, stream, h_out); }
+int dvbs2gpu_es_get_row_table(dvbs2gpu_es* b, int stream, dvbs2gpu_es_row* h_rows, int cap, int* n) { return watch_get_row_table(b, stream, h_rows, cap, n); }
+int dvbs2gpu_es_get_row_table_device(dvbs2gpu_es* b, int stream, const dvbs2gpu_es_row** d_rows, int* n) { return watch_get_row_table_device(b, stream, d_rows, n); }
 
 }  // extern "C"

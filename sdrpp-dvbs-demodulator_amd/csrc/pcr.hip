@@ -24,6 +24,7 @@
 // copy of the per-stream call record (PcrCall).
 #include "ts_bank.h"
 #include "pcr_rules.h"
+#include "watch_bank.h"
 
 using namespace s2;
 #define g_err last_error()
@@ -197,136 +198,64 @@ __global__ void __launch_bounds__(PCR_WG) pcr_kernel(const uint8_t* const* __res
 
 }  // namespace s2
 
-struct dvbs2gpu_pcr {
-    dvbs2gpu_ctx* ctx = nullptr;                   // null: a host-only bank (dvbs2gpu_pcr_create_host)
-    int nstreams = 0, max_packets = 0, max_rows = 0;
-    std::vector<int32_t> watch;                    // nstreams x 16
-    std::vector<PcrRate> rate;
-    std::vector<dvbs2gpu_pcr_stats> stats;         // nstreams x 16, since reset; the kernel reports each call's share (PcrCall)
-    std::vector<dvbs2gpu_pcr_stream_stats> sstats; // packets_since_pcr holds the position of the slot's last record, -1: none
-    std::vector<int> nrows, records;               // of the last call per stream: rows in the table, records in all
-    std::vector<PcrCall> h_call;
-    std::vector<char> h_args;
-    // device banks
-    DevBuf<int32_t> d_watch;
-    DevBuf<PcrRate> d_rate;
-    DevBuf<PcrState> d_state;
-    DevBuf<int64_t> d_pos;
-    DevBuf<PcrRow> d_rows;                         // nstreams x max_rows
-    DevBuf<PcrCall> d_call;
-    DevBuf<uint8_t> d_args;                        // TsBankArgs(nstreams)
-    TsHostStage stage;                             // of the host-buffer entry point
-    // host-only banks
-    std::vector<PcrHostStream> host;
-};
+// the host half is the watched-PID bank's (watch_bank.h); here what is the bank's own
+struct PcrBankD {
+    static constexpr int SLOTS = PCR_SLOTS, MAX_PACKETS = PCR_MAX_PACKETS;
+    typedef PcrState State; typedef PcrRow Row; typedef PcrCall Call; typedef PcrHostStream HostStream;
+    typedef dvbs2gpu_pcr_stats Stats; typedef dvbs2gpu_pcr_stream_stats StreamStats;
+    static constexpr int SUMS = 12;                    // of dvbs2gpu_pcr_stats: the two maxima are the last two words
+    // packets_since_pcr holds the position of the slot's last record, -1: none
+    static constexpr StreamStats NO_STREAM_STATS = {0, 0, 0, -1, 0, {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1}};
+    typedef PcrRate Config;                            // per stream
+    static constexpr int CONFIGS = 1;
+    static constexpr Config NO_CONFIG = {0, PCR_DEFAULT_LIMIT_Q6, 0};
+    static constexpr const char *BANK = "PCR bank: ", *CNAME = "dvbs2gpu_pcr", *ALLOC = "hipMalloc(pcr)";
 
-namespace s2 {
-static_assert(sizeof(dvbs2gpu_pcr_stats) == 14 * sizeof(int64_t), "stats order");
-// one stream's call into its statistics; `n` packets came
-static void pcr_account(dvbs2gpu_pcr* b, int i, int n, const PcrCallHead& head, const PcrCnt* c) {
-    dvbs2gpu_pcr_stream_stats& ss = b->sstats[i];
-    for (int s = 0; s < PCR_SLOTS; ++s) {
-        dvbs2gpu_pcr_stats& d = b->stats[(size_t)i * PCR_SLOTS + s];
-        const PcrCnt& a = c[s];
-        int64_t* dk[PCR_KINDS] = {&d.first, &d.announced, &d.repeated, &d.ok, &d.late, &d.jumps};
-        for (int k = 0; k < PCR_KINDS; ++k) { *dk[k] += a.kind[k]; d.pcr_packets += a.kind[k]; }
-        d.malformed += a.malformed; d.accuracy_measured += a.accuracy_measured; d.accuracy_errors += a.accuracy_errors;
-        d.sum_ticks += (int64_t)a.sum_ticks; d.sum_packets += (int64_t)a.sum_packets;
-        if ((int64_t)a.max_delta_ticks > d.max_delta_ticks) d.max_delta_ticks = a.max_delta_ticks;
-        if ((int64_t)a.max_abs_accuracy > d.max_abs_accuracy) d.max_abs_accuracy = a.max_abs_accuracy;
-        if (a.last_k >= 0) ss.packets_since_pcr[s] = ss.packets + a.last_k;
+    // one stream's call into its statistics; `n` packets came
+    static void account(WatchBank<PcrBankD>& b, int i, int n, const PcrCallHead& head, const PcrCnt* c) {
+        dvbs2gpu_pcr_stream_stats& ss = b.sstats[i];
+        for (int s = 0; s < PCR_SLOTS; ++s) {
+            dvbs2gpu_pcr_stats& d = b.stats[(size_t)i * PCR_SLOTS + s];
+            const PcrCnt& a = c[s];
+            int64_t* dk[PCR_KINDS] = {&d.first, &d.announced, &d.repeated, &d.ok, &d.late, &d.jumps};
+            for (int k = 0; k < PCR_KINDS; ++k) { *dk[k] += a.kind[k]; d.pcr_packets += a.kind[k]; }
+            d.malformed += a.malformed; d.accuracy_measured += a.accuracy_measured; d.accuracy_errors += a.accuracy_errors;
+            d.sum_ticks += (int64_t)a.sum_ticks; d.sum_packets += (int64_t)a.sum_packets;
+            if ((int64_t)a.max_delta_ticks > d.max_delta_ticks) d.max_delta_ticks = a.max_delta_ticks;
+            if ((int64_t)a.max_abs_accuracy > d.max_abs_accuracy) d.max_abs_accuracy = a.max_abs_accuracy;
+            if (a.last_k >= 0) ss.packets_since_pcr[s] = ss.packets + a.last_k;
+        }
+        ss.packets += n;
+        ss.unwatched_pcr_packets += head.unwatched;
+        ss.first_unwatched_pid = head.first_unwatched_pid;
+        if (head.records > b.max_rows) ss.rows_dropped += head.records - b.max_rows;
+        b.total[i] = head.records;
+        b.nrows[i] = head.records < b.max_rows ? head.records : b.max_rows;
     }
-    ss.packets += n;
-    ss.unwatched_pcr_packets += head.unwatched;
-    ss.first_unwatched_pid = head.first_unwatched_pid;
-    if (head.records > b->max_rows) ss.rows_dropped += head.records - b->max_rows;
-    b->records[i] = head.records;
-    b->nrows[i] = head.records < b->max_rows ? head.records : b->max_rows;
-}
-static const dvbs2gpu_pcr_stream_stats PCR_NO_STREAM_STATS = {0, 0, 0, -1, 0, {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1}};
-static bool pcr_create_args_ok(int nstreams, int max_packets, int max_rows, dvbs2gpu_pcr** out) {
-    if (!out || nstreams <= 0 || max_packets <= 0 || max_rows <= 0) return false;
-    if (max_packets > PCR_MAX_PACKETS) { g_err = "PCR bank: max_packets is at most 4096 per stream and call"; return false; }
-    return true;
-}
-static std::unique_ptr<dvbs2gpu_pcr> pcr_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows) {
-    std::unique_ptr<dvbs2gpu_pcr> b(new dvbs2gpu_pcr());
-    b->ctx = ctx; b->nstreams = nstreams; b->max_packets = max_packets; b->max_rows = max_rows;
-    b->watch.assign((size_t)nstreams * PCR_SLOTS, -1);
-    b->rate.assign(nstreams, PcrRate{0, PCR_DEFAULT_LIMIT_Q6, 0});
-    b->stats.assign((size_t)nstreams * PCR_SLOTS, dvbs2gpu_pcr_stats{});
-    b->sstats.assign(nstreams, PCR_NO_STREAM_STATS);
-    b->nrows.assign(nstreams, 0); b->records.assign(nstreams, 0);
-    b->h_call.resize(nstreams);
-    return b;
-}
-}  // namespace s2
+    static void launch(WatchBank<PcrBankD>& b, const TsBankArgs& a, hipStream_t st) {
+        const size_t lds = sizeof(PcrShared) + (size_t)b.max_packets * 10;      // <= 51 KiB
+        hipLaunchKernelGGL(pcr_kernel, dim3(b.nstreams), dim3(PCR_WG), lds, st, a.in(b.d_args), a.nbytes(b.d_args), b.max_packets, b.max_rows, b.d_watch, b.d_cfg, b.d_state,
+                           b.d_pos, b.d_rows, b.d_call);
+    }
+    static void fix_stream_stats(StreamStats* o) {
+        for (int s = 0; s < PCR_SLOTS; ++s)
+            if (o->packets_since_pcr[s] >= 0) o->packets_since_pcr[s] = o->packets - o->packets_since_pcr[s];
+    }
+};
+static_assert(sizeof(dvbs2gpu_pcr_stats) == (PcrBankD::SUMS + 2) * sizeof(int64_t), "stats order");
+struct dvbs2gpu_pcr : WatchBank<PcrBankD> {};
 
 extern "C" {
 
 void dvbs2gpu_pcr_destroy(dvbs2gpu_pcr* b) { delete b; }
-
-int dvbs2gpu_pcr_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_pcr** out) {
-    if (!ctx || !pcr_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    auto b = pcr_new(ctx, nstreams, max_packets, max_rows);
-    const size_t n = (size_t)nstreams, ns = n * PCR_SLOTS;
-    const char* what = "hipMalloc(pcr)";               // (zero-filled: the slots' states and the positions; the kernel writes rows and call records before they are read)
-    RC_TRY(b->d_watch.alloc(ns, false, what));
-    HIP_TRY(hipMemcpy(b->d_watch, b->watch.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice));
-    RC_TRY(b->d_rate.alloc(n, false, what));
-    HIP_TRY(hipMemcpy(b->d_rate, b->rate.data(), n * sizeof(PcrRate), hipMemcpyHostToDevice));
-    RC_TRY(b->d_state.alloc(ns, true, what));
-    RC_TRY(b->d_pos.alloc(n, true, what));
-    RC_TRY(b->d_rows.alloc(n * max_rows, false, what));
-    RC_TRY(b->d_call.alloc(n, false, what));
-    RC_TRY(b->d_args.alloc(TsBankArgs(n).L.bytes(), false, what));
-    b->h_args.resize(TsBankArgs(n).L.bytes());
-    *out = b.release();
-    return 0;
-}
-
-int dvbs2gpu_pcr_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_pcr** out) {
-    if (!pcr_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
-    auto b = pcr_new(nullptr, nstreams, max_packets, max_rows);
-    b->host.resize(nstreams);
-    *out = b.release();
-    return 0;
-}
-
-int dvbs2gpu_pcr_reset(dvbs2gpu_pcr* b) {
-    if (!b) return DVBS2GPU_ERR_ARG;
-    if (b->ctx) {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        HIP_TRY(hipMemset(b->d_state, 0, (size_t)b->nstreams * PCR_SLOTS * sizeof(PcrState)));
-        HIP_TRY(hipMemset(b->d_pos, 0, (size_t)b->nstreams * sizeof(int64_t)));
-    }
-    for (auto& h : b->host) h.reset();
-    std::fill(b->stats.begin(), b->stats.end(), dvbs2gpu_pcr_stats{});
-    std::fill(b->sstats.begin(), b->sstats.end(), PCR_NO_STREAM_STATS);
-    std::fill(b->nrows.begin(), b->nrows.end(), 0);
-    std::fill(b->records.begin(), b->records.end(), 0);
-    return 0;
-}
+int dvbs2gpu_pcr_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_pcr** out) { return watch_create(true, ctx, nstreams, max_packets, max_rows, out); }
+int dvbs2gpu_pcr_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_pcr** out) { return watch_create(false, nullptr, nstreams, max_packets, max_rows, out); }
+int dvbs2gpu_pcr_reset(dvbs2gpu_pcr* b) { return watch_reset(b); }
 
 int dvbs2gpu_pcr_set_watch(dvbs2gpu_pcr* b, int stream, int slot, int pid) {
-    if (!b || stream < 0 || stream >= b->nstreams || slot < 0 || slot >= PCR_SLOTS) return DVBS2GPU_ERR_ARG;
-    if (pid < -1 || pid >= TSMON_NULL_PID) { g_err = "PCR bank: a watched PID is 0..0x1FFE (-1 clears the slot)"; return DVBS2GPU_ERR_ARG; }
-    int32_t* w = b->watch.data() + (size_t)stream * PCR_SLOTS;
-    for (int s = 0; s < PCR_SLOTS; ++s)
-        if (pid >= 0 && s != slot && w[s] == pid) { g_err = "PCR bank: the PID is watched in another slot of the stream"; return DVBS2GPU_ERR_ARG; }
-    const size_t at = (size_t)stream * PCR_SLOTS + slot;
-    w[slot] = pid;
-    b->stats[at] = dvbs2gpu_pcr_stats{};
+    if (!watch_slot_ok(b, stream, slot, pid)) return DVBS2GPU_ERR_ARG;
+    if (const int e = watch_set_watch(b, stream, slot, pid)) return e;
     b->sstats[stream].packets_since_pcr[slot] = -1;
-    if (b->ctx) {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        HIP_TRY(hipMemcpy(b->d_watch + at, &w[slot], sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(b->d_state + at, 0, sizeof(PcrState)));
-    } else {
-        b->host[stream].watch[slot] = pid;
-        b->host[stream].clear_slot(slot);
-    }
     return 0;
 }
 
@@ -336,80 +265,18 @@ int dvbs2gpu_pcr_set_rate(dvbs2gpu_pcr* b, int stream, uint64_t ticks_per_packet
         g_err = "PCR bank: ticks per packet (Q24.24) stay below 2^48, the accuracy limit is not negative";
         return DVBS2GPU_ERR_ARG;
     }
-    b->rate[stream] = PcrRate{ticks_per_packet_q24, limit_q6, 0};
-    if (b->ctx) {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        HIP_TRY(hipMemcpy(b->d_rate + stream, &b->rate[stream], sizeof(PcrRate), hipMemcpyHostToDevice));
-    } else b->host[stream].rate = b->rate[stream];
+    b->cfg[stream] = PcrRate{ticks_per_packet_q24, limit_q6, 0};
+    if (b->ctx) return watch_upload_config(b, stream);
+    b->host[stream].rate = b->cfg[stream];
     return 0;
 }
 
 int dvbs2gpu_pcr_process_batch(dvbs2gpu_pcr* b, const uint8_t* const* d_ts, const int* nbytes, int* out_rows, void* stream) {
-    if (!b || !d_ts || !nbytes) return DVBS2GPU_ERR_ARG;
-    if (!b->ctx) { g_err = "PCR bank: a host bank takes host buffers (dvbs2gpu_pcr_work)"; return DVBS2GPU_ERR_ARG; }
-    const int n = b->nstreams;
-    for (int i = 0; i < n; ++i) {
-        if (!ts_bank_check_counts("PCR bank: ", nbytes + i, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
-        if (nbytes[i] > 0 && !d_ts[i]) { g_err = "PCR bank: null buffer"; return DVBS2GPU_ERR_ARG; }
-    }
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const TsBankArgs a(n);
-    a.fill(b->h_args.data(), n, d_ts, nullptr, nbytes);
-    HIP_TRY(hipMemcpyAsync(b->d_args, b->h_args.data(), b->h_args.size(), hipMemcpyHostToDevice, st));
-    const size_t lds = sizeof(PcrShared) + (size_t)b->max_packets * 10;      // <= 51 KiB
-    hipLaunchKernelGGL(pcr_kernel, dim3(n), dim3(PCR_WG), lds, st, a.in(b->d_args), a.nbytes(b->d_args), b->max_packets, b->max_rows, b->d_watch, b->d_rate, b->d_state,
-                       b->d_pos, b->d_rows, b->d_call);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_call.data(), b->d_call, sizeof(PcrCall) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int i = 0; i < n; ++i) {
-        pcr_account(b, i, nbytes[i] / TSMON_TS, b->h_call[i].head, b->h_call[i].cnt);
-        if (out_rows) out_rows[i] = b->records[i];
-    }
-    return 0;
+    return watch_process_batch(b, d_ts, nbytes, out_rows, stream);
 }
-
-int dvbs2gpu_pcr_work(dvbs2gpu_pcr* b, int stream, const uint8_t* h_ts, int nbytes) {
-    if (!b || stream < 0 || stream >= b->nstreams || nbytes < 0 || (nbytes > 0 && !h_ts)) return DVBS2GPU_ERR_ARG;
-    if (!ts_bank_check_counts("PCR bank: ", &nbytes, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
-    if (!b->ctx) {
-        for (int i = 0; i < b->nstreams; ++i) {        // the other streams receive an empty call
-            PcrHostStream& h = b->host[i];
-            const int np = i == stream ? nbytes / TSMON_TS : 0;
-            h.run(h_ts, np, b->max_rows);
-            pcr_account(b, i, np, h.head, h.cnt);
-        }
-        return b->records[stream];
-    }
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    const int rc = ts_bank_work(b->stage, b->nstreams, stream, h_ts, nbytes, b->max_packets, nullptr, 0, false, [&](const uint8_t* const* in, const int* nb, uint8_t* const*, int*) {
-        return dvbs2gpu_pcr_process_batch(b, in, nb, nullptr, nullptr);
-    });
-    return rc < 0 ? rc : b->records[stream];
-}
-
-int dvbs2gpu_pcr_get_stats(dvbs2gpu_pcr* b, int stream, int slot, dvbs2gpu_pcr_stats* h_out) {
-    if (!b || stream < 0 || stream >= b->nstreams || slot < -1 || slot >= PCR_SLOTS || !h_out) return DVBS2GPU_ERR_ARG;
-    *h_out = dvbs2gpu_pcr_stats{};
-    for (int s = slot < 0 ? 0 : slot; s < (slot < 0 ? PCR_SLOTS : slot + 1); ++s) {
-        const dvbs2gpu_pcr_stats& a = b->stats[(size_t)stream * PCR_SLOTS + s];
-        const int64_t* src = reinterpret_cast<const int64_t*>(&a);
-        int64_t* d = reinterpret_cast<int64_t*>(h_out);
-        for (int k = 0; k < 12; ++k) d[k] += src[k];   // the two maxima are the last two words
-        if (a.max_delta_ticks > h_out->max_delta_ticks) h_out->max_delta_ticks = a.max_delta_ticks;
-        if (a.max_abs_accuracy > h_out->max_abs_accuracy) h_out->max_abs_accuracy = a.max_abs_accuracy;
-    }
-    return 0;
-}
-
-int dvbs2gpu_pcr_get_stream_stats(dvbs2gpu_pcr* b, int stream, dvbs2gpu_pcr_stream_stats* h_out) {
-    if (!b || stream < 0 || stream >= b->nstreams || !h_out) return DVBS2GPU_ERR_ARG;
-    *h_out = b->sstats[stream];
-    for (int s = 0; s < PCR_SLOTS; ++s)
-        if (h_out->packets_since_pcr[s] >= 0) h_out->packets_since_pcr[s] = h_out->packets - h_out->packets_since_pcr[s];
-    return 0;
-}
+int dvbs2gpu_pcr_work(dvbs2gpu_pcr* b, int stream, const uint8_t* h_ts, int nbytes) { return watch_work(b, stream, h_ts, nbytes); }
+int dvbs2gpu_pcr_get_stats(dvbs2gpu_pcr* b, int stream, int slot, dvbs2gpu_pcr_stats* h_out) { return watch_get_stats(b, stream, slot, h_out); }
+int dvbs2gpu_pcr_get_stream_stats(dvbs2gpu_pcr* b, int stream, dvbs2gpu_pcr_stream_stats* h_out) { return watch_get_stream_stats(b, stream, h_out); }
 
 int dvbs2gpu_pcr_get_rate(dvbs2gpu_pcr* b, int stream, int slot, double* bits_per_s) {
     dvbs2gpu_pcr_stats st;
@@ -419,12 +286,7 @@ int dvbs2gpu_pcr_get_rate(dvbs2gpu_pcr* b, int stream, int slot, double* bits_pe
     return 0;
 }
 
-int dvbs2gpu_pcr_get_row_table(dvbs2gpu_pcr* b, int stream, dvbs2gpu_pcr_row* h_rows, int cap, int* n) {
-    return ts_bank_rows(b, &dvbs2gpu_pcr::max_rows, stream, h_rows, cap, n);
-}
-
-int dvbs2gpu_pcr_get_row_table_device(dvbs2gpu_pcr* b, int stream, const dvbs2gpu_pcr_row** d_rows, int* n) {
-    return ts_bank_rows_device(b, &dvbs2gpu_pcr::max_rows, stream, d_rows, n);
-}
+int dvbs2gpu_pcr_get_row_table(dvbs2gpu_pcr* b, int stream, dvbs2gpu_pcr_row* h_rows, int cap, int* n) { return watch_get_row_table(b, stream, h_rows, cap, n); }
+int dvbs2gpu_pcr_get_row_table_device(dvbs2gpu_pcr* b, int stream, const dvbs2gpu_pcr_row** d_rows, int* n) { return watch_get_row_table_device(b, stream, d_rows, n); }
 
 }  // extern "C"

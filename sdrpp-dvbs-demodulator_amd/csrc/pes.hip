@@ -21,6 +21,7 @@
 // No lane walks over packets of other lanes: the cost of a call does not depend on what the packets say.  One device-to-host copy of
 // the per-stream call record (PesCall).
 #include "ts_watch.h"
+#include "watch_bank.h"
 
 using namespace s2;
 #define g_err last_error()
@@ -223,223 +224,84 @@ __global__ void __launch_bounds__(PES_WG) pes_kernel(const uint8_t* const* __res
 
 }  // namespace s2
 
-struct dvbs2gpu_pes {
-    dvbs2gpu_ctx* ctx = nullptr;                   // null: a host-only bank (dvbs2gpu_pes_create_host)
-    int nstreams = 0, max_packets = 0, max_rows = 0;
-    std::vector<int32_t> watch;                    // nstreams x 16
-    std::vector<PesRate> rate;
-    std::vector<dvbs2gpu_pes_stats> stats;         // nstreams x 16, since reset; the kernel reports each call's share (PesCall)
-    std::vector<dvbs2gpu_pes_stream_stats> sstats; // packets_since_start holds the position of the slot's last start, -1: none
-    std::vector<int> nrows, starts;                // of the last call per stream: rows in the table, starts in all
-    std::vector<PesCall> h_call;
-    std::vector<char> h_args;
-    // device banks
-    DevBuf<int32_t> d_watch;
-    DevBuf<PesRate> d_rate;
-    DevBuf<PesState> d_state;
-    DevBuf<int64_t> d_pos;
-    DevBuf<PesRow> d_rows;                         // nstreams x max_rows
-    DevBuf<PesCall> d_call;
-    DevBuf<uint8_t> d_args;                        // TsBankArgs(nstreams)
-    TsHostStage stage;                             // of the host-buffer entry point
-    // host-only banks
-    std::vector<PesHostStream> host;
-};
+// the host half is the watched-PID bank's (watch_bank.h); here what is the bank's own
+struct PesBankD {
+    static constexpr int SLOTS = PES_SLOTS, MAX_PACKETS = PES_MAX_PACKETS;
+    typedef PesState State; typedef PesRow Row; typedef PesCall Call; typedef PesHostStream HostStream;
+    typedef dvbs2gpu_pes_stats Stats; typedef dvbs2gpu_pes_stream_stats StreamStats;
+    static constexpr int SUMS = 23;                    // of dvbs2gpu_pes_stats: the counters in front of the maximum
+    // packets_since_start holds the position of the slot's last start, -1: none
+    static constexpr StreamStats NO_STREAM_STATS = {0, 0, {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1}};
+    typedef PesRate Config;                            // per stream
+    static constexpr int CONFIGS = 1;
+    static constexpr Config NO_CONFIG = {0, 0};
+    static constexpr const char *BANK = "PES bank: ", *CNAME = "dvbs2gpu_pes", *ALLOC = "hipMalloc(pes)";
 
-namespace s2 {
-constexpr int PES_STATS_SUMS = 23;                 // of dvbs2gpu_pes_stats: the counters in front of the maximum
-static_assert(sizeof(dvbs2gpu_pes_stats) == (PES_STATS_SUMS + 1) * sizeof(int64_t), "stats order");
-// one stream's call into its statistics; `n` packets came
-static void pes_account(dvbs2gpu_pes* b, int i, int n, const PesCallHead& head, const PesCnt* c) {
-    dvbs2gpu_pes_stream_stats& ss = b->sstats[i];
-    for (int s = 0; s < PES_SLOTS; ++s) {
-        const PesCnt& a = c[s];
-        if (!a.packets) continue;                      // (no packet of the slot's PID came: every counter is 0)
-        dvbs2gpu_pes_stats& d = b->stats[(size_t)i * PES_SLOTS + s];
-        d.packets += a.packets; d.payload_bytes += a.payload_bytes; d.duplicates += a.duplicates; d.cc_errors += a.cc_errors;
-        d.scrambled_packets += a.scrambled_packets; d.malformed_packets += a.malformed_packets;
-        int64_t* dk[PES_KINDS] = {&d.starts_scrambled, &d.starts_short, &d.starts_bad_start, &d.starts_plain, &d.starts_malformed, &d.starts_header};
-        for (int k = 0; k < PES_KINDS; ++k) { *dk[k] += a.kind[k]; d.starts += a.kind[k]; }
-        d.with_pts += a.with_pts; d.with_dts += a.with_dts;
-        d.closed_ok += a.closed_ok; d.closed_mismatch += a.closed_mismatch; d.closed_gap += a.closed_gap; d.closed_unchecked += a.closed_unchecked;
-        d.ts_backward += a.ts_backward; d.ts_gap += a.ts_gap; d.pts_late += a.pts_late; d.dts_after_pts += a.dts_after_pts;
-        if ((int64_t)a.max_delta_packets > d.max_delta_packets) d.max_delta_packets = a.max_delta_packets;
-        if (a.last_k >= 0) ss.packets_since_start[s] = ss.packets + a.last_k;
+    // one stream's call into its statistics; `n` packets came
+    static void account(WatchBank<PesBankD>& b, int i, int n, const PesCallHead& head, const PesCnt* c) {
+        dvbs2gpu_pes_stream_stats& ss = b.sstats[i];
+        for (int s = 0; s < PES_SLOTS; ++s) {
+            const PesCnt& a = c[s];
+            if (!a.packets) continue;                      // (no packet of the slot's PID came: every counter is 0)
+            dvbs2gpu_pes_stats& d = b.stats[(size_t)i * PES_SLOTS + s];
+            d.packets += a.packets; d.payload_bytes += a.payload_bytes; d.duplicates += a.duplicates; d.cc_errors += a.cc_errors;
+            d.scrambled_packets += a.scrambled_packets; d.malformed_packets += a.malformed_packets;
+            int64_t* dk[PES_KINDS] = {&d.starts_scrambled, &d.starts_short, &d.starts_bad_start, &d.starts_plain, &d.starts_malformed, &d.starts_header};
+            for (int k = 0; k < PES_KINDS; ++k) { *dk[k] += a.kind[k]; d.starts += a.kind[k]; }
+            d.with_pts += a.with_pts; d.with_dts += a.with_dts;
+            d.closed_ok += a.closed_ok; d.closed_mismatch += a.closed_mismatch; d.closed_gap += a.closed_gap; d.closed_unchecked += a.closed_unchecked;
+            d.ts_backward += a.ts_backward; d.ts_gap += a.ts_gap; d.pts_late += a.pts_late; d.dts_after_pts += a.dts_after_pts;
+            if ((int64_t)a.max_delta_packets > d.max_delta_packets) d.max_delta_packets = a.max_delta_packets;
+            if (a.last_k >= 0) ss.packets_since_start[s] = ss.packets + a.last_k;
+        }
+        ss.packets += n;
+        if (head.starts > b.max_rows) ss.rows_dropped += head.starts - b.max_rows;
+        b.total[i] = head.starts;
+        b.nrows[i] = head.starts < b.max_rows ? head.starts : b.max_rows;
     }
-    ss.packets += n;
-    if (head.starts > b->max_rows) ss.rows_dropped += head.starts - b->max_rows;
-    b->starts[i] = head.starts;
-    b->nrows[i] = head.starts < b->max_rows ? head.starts : b->max_rows;
-}
-static const dvbs2gpu_pes_stream_stats PES_NO_STREAM_STATS = {0, 0, {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1}};
-static bool pes_create_args_ok(int nstreams, int max_packets, int max_rows, dvbs2gpu_pes** out) {
-    if (!out || nstreams <= 0 || max_packets <= 0 || max_rows <= 0) return false;
-    if (max_packets > PES_MAX_PACKETS) { g_err = "PES bank: max_packets is at most 4096 per stream and call"; return false; }
-    return true;
-}
-static std::unique_ptr<dvbs2gpu_pes> pes_new(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows) {
-    std::unique_ptr<dvbs2gpu_pes> b(new dvbs2gpu_pes());
-    b->ctx = ctx; b->nstreams = nstreams; b->max_packets = max_packets; b->max_rows = max_rows;
-    b->watch.assign((size_t)nstreams * PES_SLOTS, -1);
-    b->rate.assign(nstreams, PesRate{0, 0});
-    b->stats.assign((size_t)nstreams * PES_SLOTS, dvbs2gpu_pes_stats{});
-    b->sstats.assign(nstreams, PES_NO_STREAM_STATS);
-    b->nrows.assign(nstreams, 0); b->starts.assign(nstreams, 0);
-    b->h_call.resize(nstreams);
-    return b;
-}
-}  // namespace s2
+    static void launch(WatchBank<PesBankD>& b, const TsBankArgs& a, hipStream_t st) {
+        const size_t lds = pes_lds_bytes(b.max_packets);       // <= 59.2 KiB
+        hipLaunchKernelGGL(pes_kernel, dim3(b.nstreams), dim3(PES_WG), lds, st, a.in(b.d_args), a.nbytes(b.d_args), b.max_packets, b.max_rows, b.d_watch, b.d_cfg, b.d_state,
+                           b.d_pos, b.d_rows, b.d_call);
+    }
+    static void fix_stream_stats(StreamStats* o) {
+        for (int s = 0; s < PES_SLOTS; ++s)
+            if (o->packets_since_start[s] >= 0) o->packets_since_start[s] = o->packets - o->packets_since_start[s];
+    }
+};
+static_assert(sizeof(dvbs2gpu_pes_stats) == (PesBankD::SUMS + 1) * sizeof(int64_t), "stats order");
+struct dvbs2gpu_pes : WatchBank<PesBankD> {};
 
 extern "C" {
 
 void dvbs2gpu_pes_destroy(dvbs2gpu_pes* b) { delete b; }
-
-int dvbs2gpu_pes_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_pes** out) {
-    if (!ctx || !pes_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    auto b = pes_new(ctx, nstreams, max_packets, max_rows);
-    const size_t n = (size_t)nstreams, ns = n * PES_SLOTS;
-    const char* what = "hipMalloc(pes)";               // (zero-filled: the slots' states, the positions and the rates; the kernel writes rows and call records before they are read)
-    RC_TRY(b->d_watch.alloc(ns, false, what));
-    HIP_TRY(hipMemcpy(b->d_watch, b->watch.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice));
-    RC_TRY(b->d_rate.alloc(n, true, what));
-    RC_TRY(b->d_state.alloc(ns, true, what));
-    RC_TRY(b->d_pos.alloc(n, true, what));
-    RC_TRY(b->d_rows.alloc(n * max_rows, false, what));
-    RC_TRY(b->d_call.alloc(n, false, what));
-    RC_TRY(b->d_args.alloc(TsBankArgs(n).L.bytes(), false, what));
-    b->h_args.resize(TsBankArgs(n).L.bytes());
-    *out = b.release();
-    return 0;
-}
-
-int dvbs2gpu_pes_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_pes** out) {
-    if (!pes_create_args_ok(nstreams, max_packets, max_rows, out)) return DVBS2GPU_ERR_ARG;
-    auto b = pes_new(nullptr, nstreams, max_packets, max_rows);
-    b->host.resize(nstreams);
-    *out = b.release();
-    return 0;
-}
-
-int dvbs2gpu_pes_reset(dvbs2gpu_pes* b) {
-    if (!b) return DVBS2GPU_ERR_ARG;
-    if (b->ctx) {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        HIP_TRY(hipMemset(b->d_state, 0, (size_t)b->nstreams * PES_SLOTS * sizeof(PesState)));
-        HIP_TRY(hipMemset(b->d_pos, 0, (size_t)b->nstreams * sizeof(int64_t)));
-    }
-    for (auto& h : b->host) h.reset();
-    std::fill(b->stats.begin(), b->stats.end(), dvbs2gpu_pes_stats{});
-    std::fill(b->sstats.begin(), b->sstats.end(), PES_NO_STREAM_STATS);
-    std::fill(b->nrows.begin(), b->nrows.end(), 0);
-    std::fill(b->starts.begin(), b->starts.end(), 0);
-    return 0;
-}
+int dvbs2gpu_pes_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_pes** out) { return watch_create(true, ctx, nstreams, max_packets, max_rows, out); }
+int dvbs2gpu_pes_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_pes** out) { return watch_create(false, nullptr, nstreams, max_packets, max_rows, out); }
+int dvbs2gpu_pes_reset(dvbs2gpu_pes* b) { return watch_reset(b); }
 
 int dvbs2gpu_pes_set_watch(dvbs2gpu_pes* b, int stream, int slot, int pid) {
-    if (!b || stream < 0 || stream >= b->nstreams || slot < 0 || slot >= PES_SLOTS) return DVBS2GPU_ERR_ARG;
-    if (pid < -1 || pid >= TSMON_NULL_PID) { g_err = "PES bank: a watched PID is 0..0x1FFE (-1 clears the slot)"; return DVBS2GPU_ERR_ARG; }
-    int32_t* w = b->watch.data() + (size_t)stream * PES_SLOTS;
-    for (int s = 0; s < PES_SLOTS; ++s)
-        if (pid >= 0 && s != slot && w[s] == pid) { g_err = "PES bank: the PID is watched in another slot of the stream"; return DVBS2GPU_ERR_ARG; }
-    const size_t at = (size_t)stream * PES_SLOTS + slot;
-    w[slot] = pid;
-    b->stats[at] = dvbs2gpu_pes_stats{};
+    if (!watch_slot_ok(b, stream, slot, pid)) return DVBS2GPU_ERR_ARG;
+    if (const int e = watch_set_watch(b, stream, slot, pid)) return e;
     b->sstats[stream].packets_since_start[slot] = -1;
-    if (b->ctx) {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        HIP_TRY(hipMemcpy(b->d_watch + at, &w[slot], sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(b->d_state + at, 0, sizeof(PesState)));
-    } else {
-        b->host[stream].watch[slot] = pid;
-        b->host[stream].clear_slot(slot);
-    }
     return 0;
 }
 
 int dvbs2gpu_pes_set_rate(dvbs2gpu_pes* b, int stream, uint64_t ticks_per_packet_q24) {
     if (!b || stream < 0 || stream >= b->nstreams) return DVBS2GPU_ERR_ARG;
     if (ticks_per_packet_q24 >= PES_MAX_TPP) { g_err = "PES bank: ticks per packet (Q24.24) stay below 2^48"; return DVBS2GPU_ERR_ARG; }
-    b->rate[stream] = pes_rate(ticks_per_packet_q24);
-    if (b->ctx) {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        HIP_TRY(hipMemcpy(b->d_rate + stream, &b->rate[stream], sizeof(PesRate), hipMemcpyHostToDevice));
-    } else b->host[stream].rate = b->rate[stream];
+    b->cfg[stream] = pes_rate(ticks_per_packet_q24);
+    if (b->ctx) return watch_upload_config(b, stream);
+    b->host[stream].rate = b->cfg[stream];
     return 0;
 }
 
 int dvbs2gpu_pes_process_batch(dvbs2gpu_pes* b, const uint8_t* const* d_ts, const int* nbytes, int* out_rows, void* stream) {
-    if (!b || !d_ts || !nbytes) return DVBS2GPU_ERR_ARG;
-    if (!b->ctx) { g_err = "PES bank: a host bank takes host buffers (dvbs2gpu_pes_work)"; return DVBS2GPU_ERR_ARG; }
-    const int n = b->nstreams;
-    for (int i = 0; i < n; ++i) {
-        if (!ts_bank_check_counts("PES bank: ", nbytes + i, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
-        if (nbytes[i] > 0 && !d_ts[i]) { g_err = "PES bank: null buffer"; return DVBS2GPU_ERR_ARG; }
-    }
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const TsBankArgs a(n);
-    a.fill(b->h_args.data(), n, d_ts, nullptr, nbytes);
-    HIP_TRY(hipMemcpyAsync(b->d_args, b->h_args.data(), b->h_args.size(), hipMemcpyHostToDevice, st));
-    const size_t lds = pes_lds_bytes(b->max_packets);      // <= 59.2 KiB
-    hipLaunchKernelGGL(pes_kernel, dim3(n), dim3(PES_WG), lds, st, a.in(b->d_args), a.nbytes(b->d_args), b->max_packets, b->max_rows, b->d_watch, b->d_rate, b->d_state,
-                       b->d_pos, b->d_rows, b->d_call);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_call.data(), b->d_call, sizeof(PesCall) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int i = 0; i < n; ++i) {
-        pes_account(b, i, nbytes[i] / TSMON_TS, b->h_call[i].head, b->h_call[i].cnt);
-        if (out_rows) out_rows[i] = b->starts[i];
-    }
-    return 0;
+    return watch_process_batch(b, d_ts, nbytes, out_rows, stream);
 }
-
-int dvbs2gpu_pes_work(dvbs2gpu_pes* b, int stream, const uint8_t* h_ts, int nbytes) {
-    if (!b || stream < 0 || stream >= b->nstreams || nbytes < 0 || (nbytes > 0 && !h_ts)) return DVBS2GPU_ERR_ARG;
-    if (!ts_bank_check_counts("PES bank: ", &nbytes, 1, b->max_packets)) return DVBS2GPU_ERR_ARG;
-    if (!b->ctx) {
-        for (int i = 0; i < b->nstreams; ++i) {        // the other streams receive an empty call
-            PesHostStream& h = b->host[i];
-            const int np = i == stream ? nbytes / TSMON_TS : 0;
-            h.run(h_ts, np, b->max_rows);
-            pes_account(b, i, np, h.head, h.cnt);
-        }
-        return b->starts[stream];
-    }
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    const int rc = ts_bank_work(b->stage, b->nstreams, stream, h_ts, nbytes, b->max_packets, nullptr, 0, false, [&](const uint8_t* const* in, const int* nb, uint8_t* const*, int*) {
-        return dvbs2gpu_pes_process_batch(b, in, nb, nullptr, nullptr);
-    });
-    return rc < 0 ? rc : b->starts[stream];
-}
-
-int dvbs2gpu_pes_get_stats(dvbs2gpu_pes* b, int stream, int slot, dvbs2gpu_pes_stats* h_out) {
-    if (!b || stream < 0 || stream >= b->nstreams || slot < -1 || slot >= PES_SLOTS || !h_out) return DVBS2GPU_ERR_ARG;
-    *h_out = dvbs2gpu_pes_stats{};
-    for (int s = slot < 0 ? 0 : slot; s < (slot < 0 ? PES_SLOTS : slot + 1); ++s) {
-        const dvbs2gpu_pes_stats& a = b->stats[(size_t)stream * PES_SLOTS + s];
-        const int64_t* src = reinterpret_cast<const int64_t*>(&a);
-        int64_t* d = reinterpret_cast<int64_t*>(h_out);
-        for (int k = 0; k < PES_STATS_SUMS; ++k) d[k] += src[k];   // the maximum is the last word
-        if (a.max_delta_packets > h_out->max_delta_packets) h_out->max_delta_packets = a.max_delta_packets;
-    }
-    return 0;
-}
-
-int dvbs2gpu_pes_get_stream_stats(dvbs2gpu_pes* b, int stream, dvbs2gpu_pes_stream_stats* h_out) {
-    if (!b || stream < 0 || stream >= b->nstreams || !h_out) return DVBS2GPU_ERR_ARG;
-    *h_out = b->sstats[stream];
-    for (int s = 0; s < PES_SLOTS; ++s)
-        if (h_out->packets_since_start[s] >= 0) h_out->packets_since_start[s] = h_out->packets - h_out->packets_since_start[s];
-    return 0;
-}
-
-int dvbs2gpu_pes_get_row_table(dvbs2gpu_pes* b, int stream, dvbs2gpu_pes_row* h_rows, int cap, int* n) {
-    return ts_bank_rows(b, &dvbs2gpu_pes::max_rows, stream, h_rows, cap, n);
-}
-
-int dvbs2gpu_pes_get_row_table_device(dvbs2gpu_pes* b, int stream, const dvbs2gpu_pes_row** d_rows, int* n) {
-    return ts_bank_rows_device(b, &dvbs2gpu_pes::max_rows, stream, d_rows, n);
-}
+int dvbs2gpu_pes_work(dvbs2gpu_pes* b, int stream, const uint8_t* h_ts, int nbytes) { return watch_work(b, stream, h_ts, nbytes); }
+int dvbs2gpu_pes_get_stats(dvbs2gpu_pes* b, int stream, int slot, dvbs2gpu_pes_stats* h_out) { return watch_get_stats(b, stream, slot, h_out); }
+int dvbs2gpu_pes_get_stream_stats(dvbs2gpu_pes* b, int stream, dvbs2gpu_pes_stream_stats* h_out) { return watch_get_stream_stats(b, stream, h_out); }
+int dvbs2gpu_pes_get_row_table(dvbs2gpu_pes* b, int stream, dvbs2gpu_pes_row* h_rows, int cap, int* n) { return watch_get_row_table(b, stream, h_rows, cap, n); }
+int dvbs2gpu_pes_get_row_table_device(dvbs2gpu_pes* b, int stream, const dvbs2gpu_pes_row** d_rows, int* n) { return watch_get_row_table_device(b, stream, d_rows, n); }
 
 }  // extern "C"

@@ -3,7 +3,8 @@
 // what a "packet bank" does around its rules.  On the device: the one header read, the one workgroup prefix sum and the contiguous
 // run of items a thread takes ("flags in a mask, scan, scatter").  On the host: the argument table of a call, the count checks,
 // the staging of the single-stream host-buffer entry point and the table getters.  The rules stay in tsmon_rules.h / psi_rules.h / pcr_rules.h / pes_rules.h /
-// t2mi_rules.h; what the two reassembling banks (PSI, T2-MI) share beyond this is ts_reasm.h.
+// t2mi_rules.h; what the two reassembling banks (PSI, T2-MI) share beyond this is ts_reasm.h, what the three watched-PID banks (PCR, PES,
+// ES) share is watch_bank.h (the host half) and, PES and ES, ts_watch.h (device phases A-C); the two datagram banks are dgram_bank.h.
 #pragma once
 #include "bbts_common.h"
 #include "tsmon_rules.h"
