@@ -489,7 +489,6 @@ private:
 };
 struct TsmonApi { typedef dvbs2gpu_tsmon Handle; static constexpr const char* name = "TSMonitor"; static constexpr auto destroy = &dvbs2gpu_tsmon_destroy; };
 struct PsiApi { typedef dvbs2gpu_psi Handle; static constexpr const char* name = "PsiBank"; static constexpr auto destroy = &dvbs2gpu_psi_destroy; };
-struct T2miApi { typedef dvbs2gpu_t2mi Handle; static constexpr const char* name = "T2miBank"; static constexpr auto destroy = &dvbs2gpu_t2mi_destroy; };
 struct IptsApi { typedef dvbs2gpu_ipts Handle; static constexpr const char* name = "IpTsBank"; static constexpr auto destroy = &dvbs2gpu_ipts_destroy; };
 }   // namespace detail
 
@@ -802,69 +801,9 @@ public:
     /* the rows of the last work(), in row order (the first max_rows) */
     std::vector<dvbs2gpu_es_row> rows() { return table(); }
 };
-/* T2-MI bank for one transport stream (dvbs2gpu_t2mi_*, include/dvbs2gpu.h; an extension): the T2-MI packets of a PID behind
- * BBFrameTSParser or TSMonitor are reassembled and checked, and the DVB-T2 BBFRAMEs of the chosen PLP laid back to back for a second
- * BBFrameTSParser in mode-adaptation mode (feed()).  Four slots, each a (PID, PLP) pair and a reassembler of its own.  init() (a device
- * bank) or initHost() (the library's host implementation, no device) and the setters throw; work() sits in the data path and does NOT
- * throw: a failing call returns 0 and leaves its code in status() and its text in error(), sticky until clearStatus(). */
-class T2miBank : public detail::Bank<detail::T2miApi> {
-public:
-    void init(int max_packets, int max_rows, int device = 0) {
-        release();
-        eng = Engine::get(device);
-        check(dvbs2gpu_t2mi_create(eng->ctx, 1, max_packets, max_rows, &h));
-    }
-    void initHost(int max_packets, int max_rows) {
-        release();
-        check(dvbs2gpu_t2mi_create_host(1, max_packets, max_rows, &h));
-    }
-    void reset() { check(dvbs2gpu_t2mi_reset(need())); }
-    /* slot 0..3; pid -1 empties the slot; plp -1: every PLP.  The same PID may sit in several slots. */
-    void setWatch(int slot, int pid, int plp = -1) { check(dvbs2gpu_t2mi_set_watch(need(), 0, slot, pid, plp)); }
-    /* nbytes of whole TS packets in for one slot; bbframes (buffer_outsize bytes; nullptr: rows and counters only) receives the
-     * slot's BBFRAMEs back to back; returns their bytes, 0 on failure (see status(); on DVBS2GPU_ERR_CAPACITY needed() has the sizes
-     * and nothing was consumed) */
-    int work(int slot, const uint8_t* ts, int nbytes, uint8_t* bbframes, int buffer_outsize) noexcept {
-        const int n = h ? dvbs2gpu_t2mi_work(h, 0, slot, ts, nbytes, bbframes, buffer_outsize) : DVBS2GPU_ERR_ARG;
-        return n >= 0 ? n : fail(n);
-    }
-    /* {bytes, rows} that the slot's last work() needed */
-    std::pair<int, int> needed(int slot) {
-        int b = 0, r = 0;
-        check(dvbs2gpu_t2mi_get_needed(need(), 0, slot, &b, &r));
-        return {b, r};
-    }
-
-    dvbs2gpu_t2mi_stats stats(int slot = -1) {
-        dvbs2gpu_t2mi_stats s;
-        check(dvbs2gpu_t2mi_get_stats(need(), 0, slot, &s));
-        return s;
-    }
-    /* one row per T2-MI packet of the slot's last work(), in row order */
-    std::vector<dvbs2gpu_t2mi_row> rowTable(int slot) {
-        int n = 0;
-        check(dvbs2gpu_t2mi_get_row_table(need(), 0, slot, nullptr, 0, &n));
-        std::vector<dvbs2gpu_t2mi_row> rows((size_t)n);
-        if (n > 0) check(dvbs2gpu_t2mi_get_row_table(h, 0, slot, rows.data(), n, &n));
-        return rows;
-    }
-    /* the sizes of the BBFRAMEs that the slot's last work() delivered, in order */
-    std::vector<int> frameBytes(int slot) {
-        int n = 0;
-        check(dvbs2gpu_t2mi_get_frame_bytes(need(), 0, slot, nullptr, 0, &n));
-        std::vector<int> sizes((size_t)n);
-        if (n > 0) check(dvbs2gpu_t2mi_get_frame_bytes(h, 0, slot, sizes.data(), n, &n));
-        return sizes;
-    }
-    /* the BBFRAMEs that the slot's last work() wrote to `bbframes` into the mode-adaptation work() of `parser` (after its
-     * setFrameSize() and setModeAdaptation()): tsframes[8], out_bytes[8], needed[8] as there; false: buffer_outsize was too small */
-    bool feed(int slot, dvbs2::BBFrameTSParser& parser, uint8_t* bbframes, uint8_t* const* tsframes, int buffer_outsize, int* out_bytes, int* needed8 = nullptr) {
-        const std::vector<int> sizes = frameBytes(slot);
-        return parser.work(bbframes, sizes.data(), (int)sizes.size(), tsframes, buffer_outsize, out_bytes, needed8);
-    }
-};
 namespace detail {
-/* What MpeBank and UleBank share (the datagram banks: dvbs2gpu_mpe_*, dvbs2gpu_ule_*): everything but setWatch().  A: the bank's C
+/* What MpeBank, UleBank and T2miBank share (the datagram banks: dvbs2gpu_mpe_*, dvbs2gpu_ule_*, dvbs2gpu_t2mi_*): everything but
+ * setWatch() and what T2miBank has for the mode-adaptation packetiser.  A: the bank's C
  * functions and types --  Handle, Stats, Row;  name ("MpeBank");  create, create_host, destroy, reset, work, get_needed, get_stats,
  * get_row_table (pointers to the C functions). */
 template <typename A>
@@ -887,8 +826,8 @@ public:
     }
     void reset() { check(A::reset(need())); }
     /* nbytes of whole TS packets in for one slot; datagrams (buffer_outsize bytes; nullptr: rows and counters only) receives the
-     * slot's IP datagrams back to back; returns their bytes, 0 on failure (see status(); on DVBS2GPU_ERR_CAPACITY needed() has the
-     * sizes and nothing was consumed) */
+     * slot's IP datagrams (T2miBank: BBFRAMEs) back to back; returns their bytes, 0 on failure (see status(); on
+     * DVBS2GPU_ERR_CAPACITY needed() has the sizes and nothing was consumed) */
     int work(int slot, const uint8_t* ts, int nbytes, uint8_t* datagrams, int buffer_outsize) noexcept {
         const int n = h ? A::work(h, 0, slot, ts, nbytes, datagrams, buffer_outsize) : DVBS2GPU_ERR_ARG;
         return n >= 0 ? n : this->fail(n);
@@ -905,7 +844,7 @@ public:
         check(A::get_stats(need(), 0, slot, &s));
         return s;
     }
-    /* one row per unit (section, SNDU) of the slot's last work(), in row order */
+    /* one row per unit (section, SNDU, T2-MI packet) of the slot's last work(), in row order */
     std::vector<typename A::Row> rowTable(int slot) {
         int n = 0;
         check(A::get_row_table(need(), 0, slot, nullptr, 0, &n));
@@ -936,7 +875,42 @@ struct UleApi {
     static constexpr auto get_stats = &dvbs2gpu_ule_get_stats;
     static constexpr auto get_row_table = &dvbs2gpu_ule_get_row_table;
 };
+struct T2miApi {
+    typedef dvbs2gpu_t2mi Handle; typedef dvbs2gpu_t2mi_stats Stats; typedef dvbs2gpu_t2mi_row Row;
+    static constexpr const char* name = "T2miBank";
+    static constexpr auto create = &dvbs2gpu_t2mi_create, create_host = &dvbs2gpu_t2mi_create_host;
+    static constexpr auto destroy = &dvbs2gpu_t2mi_destroy;
+    static constexpr auto reset = &dvbs2gpu_t2mi_reset;
+    static constexpr auto work = &dvbs2gpu_t2mi_work;
+    static constexpr auto get_needed = &dvbs2gpu_t2mi_get_needed;
+    static constexpr auto get_stats = &dvbs2gpu_t2mi_get_stats;
+    static constexpr auto get_row_table = &dvbs2gpu_t2mi_get_row_table;
+};
 }   // namespace detail
+/* T2-MI bank for one transport stream (dvbs2gpu_t2mi_*, include/dvbs2gpu.h; an extension): the T2-MI packets of a PID behind
+ * BBFrameTSParser or TSMonitor are reassembled and checked, and the DVB-T2 BBFRAMEs of the chosen PLP laid back to back for a second
+ * BBFrameTSParser in mode-adaptation mode (feed()).  Four slots, each a (PID, PLP) pair and a reassembler of its own.  init() (a device
+ * bank) or initHost() (the library's host implementation, no device) and the setters throw; work() sits in the data path and does NOT
+ * throw: a failing call returns 0 and leaves its code in status() and its text in error(), sticky until clearStatus(). */
+class T2miBank : public detail::DatagramBank<detail::T2miApi> {
+public:
+    /* slot 0..3; pid -1 empties the slot; plp -1: every PLP.  The same PID may sit in several slots. */
+    void setWatch(int slot, int pid, int plp = -1) { check(dvbs2gpu_t2mi_set_watch(need(), 0, slot, pid, plp)); }
+    /* the sizes of the BBFRAMEs that the slot's last work() delivered, in order */
+    std::vector<int> frameBytes(int slot) {
+        int n = 0;
+        check(dvbs2gpu_t2mi_get_frame_bytes(need(), 0, slot, nullptr, 0, &n));
+        std::vector<int> sizes((size_t)n);
+        if (n > 0) check(dvbs2gpu_t2mi_get_frame_bytes(h, 0, slot, sizes.data(), n, &n));
+        return sizes;
+    }
+    /* the BBFRAMEs that the slot's last work() wrote to `bbframes` into the mode-adaptation work() of `parser` (after its
+     * setFrameSize() and setModeAdaptation()): tsframes[8], out_bytes[8], needed[8] as there; false: buffer_outsize was too small */
+    bool feed(int slot, dvbs2::BBFrameTSParser& parser, uint8_t* bbframes, uint8_t* const* tsframes, int buffer_outsize, int* out_bytes, int* needed8 = nullptr) {
+        const std::vector<int> sizes = frameBytes(slot);
+        return parser.work(bbframes, sizes.data(), (int)sizes.size(), tsframes, buffer_outsize, out_bytes, needed8);
+    }
+};
 /* MPE bank for one transport stream (dvbs2gpu_mpe_*, include/dvbs2gpu.h; an extension): the DSM-CC datagram_sections of a PID behind
  * BBFrameTSParser or TSMonitor are reassembled and checked and their IP datagrams laid back to back.  Four slots, each a (PID, MAC
  * value, MAC mask) and a reassembler of its own.  init() (a device bank) or initHost() (the library's host implementation, no device)

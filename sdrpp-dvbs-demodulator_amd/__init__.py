@@ -1859,107 +1859,14 @@ class EsBank(_WatchBank):
         return dict(packets=int(st.packets), rows_dropped=int(st.rows_dropped))
 
 
-class T2miBank(_TsBank):
-    """T2-MI bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, T2-MI bank): the T2-MI packets of a PID are
-    reassembled, their CRC-32 and packet count checked, one table row per T2-MI packet, and the BBFRAMEs of the chosen PLP laid back
-    to back in a device buffer for BbTsParserBank.process_ma.  Four slots per stream, each a (PID, PLP) pair and a reassembler of its
-    own: the same PID may sit in several slots."""
-    _destroy = 'dvbs2gpu_t2mi_destroy'
-    SLOTS = 4
-    CRC_ERROR, COUNT_ERROR, BBFRAME, INTL_FRAME_START, BAD_PAYLOAD = 1, 2, 4, 8, 16
-    ROW_KEYS = tuple(k for k, _ in T2miRow._fields_)
-
-    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=1024):
-        self.eng, self.lib, self.nstreams, self.max_packets, self.max_rows = engine, engine.lib, nstreams, max_packets, max_rows
-        h = C.c_void_p()
-        engine._check(self.lib.dvbs2gpu_t2mi_create(engine.h, nstreams, max_packets, max_rows, C.byref(h)))
-        self.h = h
-
-    @classmethod
-    def host(cls, nstreams=1, max_packets=4096, max_rows=1024):
-        """a bank without a device: the library's host implementation of the same rules, behind work()"""
-        return cls._host('dvbs2gpu_t2mi_create_host', nstreams=nstreams, max_packets=max_packets, max_rows=max_rows)
-
-    @staticmethod
-    def layout():
-        """the T2-MI syntax the library relies on (dvbs2gpu_t2mi_layout) as a dict"""
-        lay = T2miLayout()
-        load_library().dvbs2gpu_t2mi_get_layout(C.byref(lay))
-        return {k: int(getattr(lay, k)) for k, _ in T2miLayout._fields_}
-
-    def reset(self):
-        self._check(self.lib.dvbs2gpu_t2mi_reset(self.h))
-
-    def set_watch(self, stream, slot, pid, plp=-1):
-        """pid -1 empties the slot; plp -1: every PLP; the slot starts afresh"""
-        self._check(self.lib.dvbs2gpu_t2mi_set_watch(self.h, int(stream), int(slot), int(pid), int(plp)))
-
-    def process(self, ts_tensors, out_tensors=None, nbytes=None):
-        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors: None for rows and counters
-        only, else out_tensors[i][k]: the uint8 CUDA buffer that receives the BBFRAMEs of slot k of stream i (None for an empty slot)
-        -> byte counts [i][k].  Dvbs2GpuError -5 carries .needed and .rows ([i][k] each) when a buffer or max_rows is too small
-        (nothing has advanced then)."""
-        n, S = self.nstreams, self.SLOTS
-        pin, cnt, _, _ = self._marshal(ts_tensors, None, nbytes)
-        pout, cap = None, 0
-        if out_tensors is not None:
-            flat = [t for per in out_tensors for t in (list(per) + [None] * S)[:S]]
-            pout = (C.c_void_p * (n * S))(*[None if t is None else t.data_ptr() for t in flat])
-            cap = min([int(t.numel()) for t in flat if t is not None] or [0])
-        nb, nr = (C.c_int * (n * S))(), (C.c_int * (n * S))()
-        rc = self.lib.dvbs2gpu_t2mi_process_batch(self.h, pin, cnt, pout, cap, nb, nr, self.eng._stream())
-        split = lambda a: [list(a[i * S:(i + 1) * S]) for i in range(n)]
-        if rc < 0:
-            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
-            e.needed, e.rows = split(nb), split(nr)
-            raise e
-        return split(nb)
-
-    def work(self, ts, stream=0, slot=0, cap=None, deliver=True):
-        """one stream and slot, host buffers: numpy uint8 packets in -> the delivered BBFRAMEs back to back (numpy uint8), or None with
-        deliver=False (rows and counters only)"""
-        import numpy as np
-        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
-        cap = ts.size + 8208 if cap is None else cap
-        out = np.zeros(max(cap, 1), np.uint8) if deliver else None
-        rc = self.lib.dvbs2gpu_t2mi_work(self.h, int(stream), int(slot), C.c_void_p(ts.ctypes.data), ts.size,
-                                         C.c_void_p(out.ctypes.data) if deliver else None, cap if deliver else 0)
-        if rc < 0:
-            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
-            nb, nr = C.c_int(), C.c_int()
-            self.lib.dvbs2gpu_t2mi_get_needed(self.h, int(stream), int(slot), C.byref(nb), C.byref(nr))
-            e.needed, e.rows = nb.value, nr.value
-            raise e
-        return out[:rc].copy() if deliver else None
-
-    def stats(self, stream=0, slot=-1):
-        st = T2miStats()
-        self._check(self.lib.dvbs2gpu_t2mi_get_stats(self.h, int(stream), int(slot), C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in T2miStats._fields_}
-
-    def row_table(self, stream=0, slot=0):
-        """one dict per T2-MI packet of the slot's last call (the fields of dvbs2gpu_t2mi_row), in row order"""
-        rows = self._rows(self.lib.dvbs2gpu_t2mi_get_row_table, T2miRow, int(stream), int(slot))
-        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows]
-
-    def row_table_device(self, stream=0, slot=0):
-        """(device pointer or None, rows): the same table as dvbs2gpu_t2mi_row records in HBM, valid until the next call"""
-        p, n = C.c_void_p(), C.c_int()
-        self._check(self.lib.dvbs2gpu_t2mi_get_row_table_device(self.h, int(stream), int(slot), C.byref(p), C.byref(n)))
-        return p.value, n.value
-
-    def frame_bytes(self, stream=0, slot=0):
-        """the sizes of the BBFRAMEs that the slot's last call delivered, in order: with the slot's output buffer, the frame_bytes and
-        nframes of BbTsParserBank.process_ma"""
-        return [int(v) for v in self._rows(self.lib.dvbs2gpu_t2mi_get_frame_bytes, C.c_int, int(stream), int(slot))]
-
-
 class _DatagramBank(_TsBank):
-    """what the banks share that deliver IP datagrams from the units of a PID (csrc/dgram_bank.h; MpeBank: sections, UleBank: SNDUs): four
-    slots per stream, each a watch and a reassembler of its own, one table row per unit, the datagrams back to back.  A bank names its C
-    prefix (_c) and its row and statistics structures (_Row, _Stats) and adds layout() and set_watch()."""
+    """what the banks share that deliver the payloads of the units of a PID (csrc/dgram_bank.h; MpeBank: the IP datagrams of sections,
+    UleBank: of SNDUs, T2miBank: the BBFRAMEs of T2-MI packets): four slots per stream, each a watch and a reassembler of its own, one
+    table row per unit, the payloads back to back.  A bank names its C prefix (_c), its row and statistics structures (_Row, _Stats)
+    and the longest payload (_WORK_SLACK: what work() allows beyond the input's size) and adds layout() and set_watch()."""
     SLOTS = 4
     _c = _Row = _Stats = None
+    _WORK_SLACK = 4096
 
     def _fn(self, name):
         return getattr(self.lib, '%s_%s' % (self._c, name))
@@ -1980,7 +1887,7 @@ class _DatagramBank(_TsBank):
 
     def process(self, ts_tensors, out_tensors=None, nbytes=None):
         """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors: None for rows and counters
-        only, else out_tensors[i][k]: the uint8 CUDA buffer that receives the datagrams of slot k of stream i (None for an empty slot)
+        only, else out_tensors[i][k]: the uint8 CUDA buffer that receives the datagrams (BBFRAMEs) of slot k of stream i (None for an empty slot)
         -> byte counts [i][k].  Dvbs2GpuError -5 carries .needed and .rows ([i][k] each) when a buffer or max_rows is too small
         (nothing has advanced then)."""
         n, S = self.nstreams, self.SLOTS
@@ -2000,11 +1907,11 @@ class _DatagramBank(_TsBank):
         return split(nb)
 
     def work(self, ts, stream=0, slot=0, cap=None, deliver=True):
-        """one stream and slot, host buffers: numpy uint8 packets in -> the delivered datagrams back to back (numpy uint8), or None with
+        """one stream and slot, host buffers: numpy uint8 packets in -> the delivered datagrams (BBFRAMEs) back to back (numpy uint8), or None with
         deliver=False (rows and counters only)"""
         import numpy as np
         ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
-        cap = ts.size + 4096 if cap is None else cap
+        cap = ts.size + self._WORK_SLACK if cap is None else cap
         out = np.zeros(max(cap, 1), np.uint8) if deliver else None
         rc = self._fn('work')(self.h, int(stream), int(slot), C.c_void_p(ts.ctypes.data), ts.size,
                               C.c_void_p(out.ctypes.data) if deliver else None, cap if deliver else 0)
@@ -2028,7 +1935,7 @@ class _DatagramBank(_TsBank):
         return {k: int(getattr(st, k)) for k, _ in self._Stats._fields_}
 
     def row_table(self, stream=0, slot=0):
-        """one dict per unit (section, SNDU) of the slot's last call (the fields of the bank's row structure; mac: six bytes), in row order"""
+        """one dict per unit (section, SNDU, T2-MI packet) of the slot's last call (the fields of the bank's row structure; mac: six bytes), in row order"""
         rows = self._rows(self._fn('get_row_table'), self._Row, int(stream), int(slot))
         return [{k: bytes(r.mac) if k == 'mac' else int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows]
 
@@ -2037,6 +1944,35 @@ class _DatagramBank(_TsBank):
         p, n = C.c_void_p(), C.c_int()
         self._check(self._fn('get_row_table_device')(self.h, int(stream), int(slot), C.byref(p), C.byref(n)))
         return p.value, n.value
+
+
+class T2miBank(_DatagramBank):
+    """T2-MI bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, T2-MI bank): the T2-MI packets of a PID are
+    reassembled, their CRC-32 and packet count checked, one table row per T2-MI packet, and the BBFRAMEs of the chosen PLP laid back
+    to back in a device buffer for BbTsParserBank.process_ma.  Four slots per stream, each a (PID, PLP) pair and a reassembler of its
+    own: the same PID may sit in several slots."""
+    _c, _Row, _Stats = 'dvbs2gpu_t2mi', T2miRow, T2miStats
+    _destroy = 'dvbs2gpu_t2mi_destroy'
+    _WORK_SLACK = 8208
+    SLOTS = 4
+    CRC_ERROR, COUNT_ERROR, BBFRAME, INTL_FRAME_START, BAD_PAYLOAD = 1, 2, 4, 8, 16
+    ROW_KEYS = tuple(k for k, _ in T2miRow._fields_)
+
+    @staticmethod
+    def layout():
+        """the T2-MI syntax the library relies on (dvbs2gpu_t2mi_layout) as a dict"""
+        lay = T2miLayout()
+        load_library().dvbs2gpu_t2mi_get_layout(C.byref(lay))
+        return {k: int(getattr(lay, k)) for k, _ in T2miLayout._fields_}
+
+    def set_watch(self, stream, slot, pid, plp=-1):
+        """pid -1 empties the slot; plp -1: every PLP; the slot starts afresh"""
+        self._check(self.lib.dvbs2gpu_t2mi_set_watch(self.h, int(stream), int(slot), int(pid), int(plp)))
+
+    def frame_bytes(self, stream=0, slot=0):
+        """the sizes of the BBFRAMEs that the slot's last call delivered, in order: with the slot's output buffer, the frame_bytes and
+        nframes of BbTsParserBank.process_ma"""
+        return [int(v) for v in self._rows(self.lib.dvbs2gpu_t2mi_get_frame_bytes, C.c_int, int(stream), int(slot))]
 
 
 class MpeBank(_DatagramBank):

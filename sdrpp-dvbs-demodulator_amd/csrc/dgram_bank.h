@@ -1,24 +1,31 @@
-// The datagram bank: what the banks that deliver IP datagrams from length-prefixed units of a TS PID (mpe.hip: MPE sections; ule.hip:
-// ULE SNDUs) are around their rules, stated once.  How a call's packets are cut into independent pieces is ts_reasm.h
-// with the one-slot format DgramFmt below; what a wave does with one unit in phase D -- the head gather, the source the row rules read
-// it through, the CRC over shares of the pieces -- is reasm_wave.h; this file holds the two kernels, the call record, the handle and the
-// bodies of the C functions.  A bank supplies a description D: its rules (MpeRules, UleRules: dgram_rules.h lists the members) and
+// The datagram bank: what the banks that deliver the payloads of length-prefixed units of a TS PID -- IP datagrams (mpe.hip: MPE
+// sections; ule.hip: ULE SNDUs) or BBFRAMEs (t2mi.hip: T2-MI packets) -- are around their rules, stated once.  How a
+// call's packets are cut into independent pieces is ts_reasm.h with the one-slot format DgramFmt below; what a wave does with one unit
+// in phase D -- the head gather, the source the row rules read it through, the CRC over shares of the pieces -- is reasm_wave.h; this
+// file holds the two kernels, the call record, the handle and the bodies of the C functions.  A bank supplies a description D: its
+// rules (MpeRules, UleRules, T2miRules: dgram_rules.h lists the members) and
 //   Stats                             the public statistics, NCNT 64-bit counters in the order of Cnt
-//   BANK, CNAME, ALLOC                "MPE bank: ", "dvbs2gpu_mpe", "hipMalloc(mpe)": the bank in error texts, its C prefix, its allocations
+//   BANK, CNAME, ALLOC, NOUN          "MPE bank: ", "dvbs2gpu_mpe", "hipMalloc(mpe)", "datagrams": the bank in error texts, its C prefix,
+//                                     its allocations, what it delivers
+//   OWN_ROWS, SIZE_LIST               the bank brings phases D and D' below as wave_row(q, v, lane, row) and sequence_pass(rows, nrows,
+//                                     ss, nss, cnt, wsum); it keeps the list of the delivered sizes.  DgramIpBank: neither (MPE, ULE)
 // and a handle `struct dvbs2gpu_x : DgramBank<D> {}`; the C functions pass the handle and forward.
 //
 //   dgram_scan_kernel<D>    one workgroup per (stream, slot); an empty slot returns at once.
 //     A-C  ts_reasm.h: the slot's packets into LDS, one lane for the continuity walk, one lane per PUSI packet and one for the unit
 //        carried in, one record per row.
-//     D  one wave per row.  The wave gathers the unit's first 128 bytes, two per lane, from the TS payloads where they lie (behind
-//        adaptation fields they may lie a byte per TS packet), and every lane evaluates D::row_fields on them, a byte read being a
-//        shuffle, the address compare a ballot and the header checksum a wave sum; lane 0 writes the row.  Where D::takes_crc says so
-//        each lane takes the CRC-32 of its share of one PIECE from a zero register, shifted to the unit's end and summed, as in
-//        t2mi_scan_kernel, but with 2 to 16 lanes to a piece: a unit has 24 pieces at most where a T2-MI packet has 46, and a lane per
-//        piece left most of the wave waiting (DESIGN).
-//     E  the rows do not depend on each other: one prefix sum over the delivered rows' bytes gives their offsets.
+//     D  one wave per row.  Without D::OWN_ROWS the wave gathers the unit's first 128 bytes, two per lane, from the TS payloads
+//        where they lie (behind adaptation fields they may lie a byte per TS packet), and every lane evaluates D::row_fields on them, a
+//        byte read being a shuffle, the address compare a ballot and the header checksum a wave sum; lane 0 writes the row and steps its
+//        counters.  Where D::takes_crc says so each lane takes the CRC-32 of its share of one PIECE from a zero register, shifted to the
+//        unit's end and summed, with 2 to 16 lanes to a piece: a unit has 24 pieces at most where a T2-MI packet has 46, and a lane per
+//        piece left most of the wave waiting (DESIGN).  With it, D::wave_row: t2mi.hip.
+//     D' D::sequence_pass: what the finished rows, in order, do to the bytes the bank carries from unit to unit (DgramDevSlot::own) and
+//        they to the rows.  Only T2-MI has one (COUNT_ERROR).
+//     E  the rows do not depend on each other any more: one prefix sum over the delivered rows' bytes gives their offsets, and where
+//        D::SIZE_LIST a second one their places in the list of delivered sizes.
 //   dgram_commit_kernel<D>  (once the host has seen that every slot's bytes and rows fit) one workgroup per (stream, slot): a wave per
-//     delivered row copies the datagram -- the unit's bytes from D::ip_at(row) on, without the stuffing -- piece by piece to its
+//     delivered row copies the payload -- the unit's bytes from D::ip_at(row) on, without the stuffing -- piece by piece to its
 //     offset; then the open unit goes to the slot's buffer and the state is stored.
 // Two launches per call and one device-to-host copy, of the call record per (stream, slot).
 #pragma once
@@ -33,18 +40,34 @@ constexpr int DGRAM_MAX_PACKETS = 4096;          // per stream and call: 10 byte
 constexpr int DGRAM_WG = 256, DGRAM_WAVES = DGRAM_WG / 64;
 static_assert(DGRAM_MAX_PACKETS <= 32 * DGRAM_WG, "reasm_collect keeps a thread's match flags in one 32-bit mask (ts_thread_run)");
 
-struct DgramDevSlot { int32_t fill; uint8_t cont, pad[3]; };
-// the format of ts_reasm.h with one slot per workgroup: the bank's header and length rule, 0xFF in a unit's first place is stuffing,
-// every finished unit a row
+struct DgramDevSlot { int32_t fill; uint8_t cont, own[DGRAM_OWN]; };      // own: DgramState::own
+static_assert(sizeof(DgramDevSlot) == 8, "reset and set_watch clear a slot's eight bytes");
+// the format of ts_reasm.h with one slot per workgroup: the bank's header, length rule and stuffing byte, every finished unit a row
 template <typename D>
 struct DgramFmt {
     typedef DgramDevSlot State;
-    static constexpr int WG = DGRAM_WG, SLOTS = 1, BUF = D::BUF, HEADER = D::HEADER, LEN_A = D::LEN_A, LEN_B = D::LEN_B, STUFFING = 0xFF;
+    static constexpr int WG = DGRAM_WG, SLOTS = 1, BUF = D::BUF, HEADER = D::HEADER, LEN_A = D::LEN_A, LEN_B = D::LEN_B, STUFFING = D::STUFFING;
     static constexpr int NCNT = D::NCNT, C_DROPPED = D::C_DROPPED, C_BAD_UNIT = D::C_BAD_UNIT, C_SLACK = D::C_SLACK;
     __device__ static int total(unsigned a, unsigned b) { return D::total(a, b); }
     __device__ static bool is_row(unsigned, int) { return true; }
 };
 template <typename D> struct DgramCall { int32_t needed, nrows, watched, ndelivered; typename D::Cnt cnt; };
+
+// what a description says that decides a row from the unit's head, carries nothing from unit to unit and keeps no size list (MPE, ULE)
+struct DgramIpBank {
+    static constexpr const char* NOUN = "datagrams";
+    static constexpr bool OWN_ROWS = false, SIZE_LIST = false;
+};
+
+// Where D::SIZE_LIST, the sizes of slot g's delivered payloads in order: max_rows ints per slot, behind the rows of all `ns` slots in the
+// rows' buffer (the list has no kernel argument of its own, so that the kernels of the banks without one are what they were)
+template <typename Row>
+__host__ __device__ inline int* dgram_size_list(Row* rows_g, size_t ns, int max_rows, size_t g) {
+    return reinterpret_cast<int*>(rows_g + ns * max_rows) + g * max_rows;
+}
+template <typename D> inline size_t dgram_row_slots(size_t ns, int max_rows) {          // the rows' buffer in rows
+    return ns * max_rows + (D::SIZE_LIST ? (ns * max_rows * sizeof(int) + sizeof(typename D::Row) - 1) / sizeof(typename D::Row) : 0);
+}
 
 // dynamic LDS: wa[max_packets] (dwords), rc[max_packets] (dwords), wb[max_packets] (16 bits each).  only >= 0: the one (stream, slot)
 // that receives its stream's packets (the single-slot entry point); the others take an empty call
@@ -112,29 +135,37 @@ __global__ void __launch_bounds__(DGRAM_WG) dgram_scan_kernel(const uint8_t* con
         // D: a wave per row
         for (int r = wave; r < nrows; r += DGRAM_WAVES) {
             const ReasmRec q = rec[r];
-            const int total = q.total;
-            // the head (lane l keeps bytes 2 l and 2 l + 1 of the unit) and, where the rules take it, the CRC: reasm_wave.h
-            const ReasmWaveSrc hd = reasm_wave_head(q, v, lane);
-            uint32_t x = 0;
-            if (D::takes_crc(hd.rd(0), hd.rd(1), total)) x = reasm_wave_crc(q, v, total, lane);       // (the same in every lane; a unit has two bytes at least)
-            const typename D::Row row = D::template row_fields<ReasmWaveSrc>(hd, total, x == 0, w, q.j0 < 0 ? -1 : wa_k(wa[q.j0]), wa_k(wa[q.j1]));
-            if (lane == 0) {
-                rows[r] = row;
-                D::account(row.flags, [&](int c) { atomicAdd(&cnt[c], 1); });
+            if constexpr (D::OWN_ROWS) D::wave_row(q, v, lane, &rows[r]);
+            else {
+                const int total = q.total;
+                // the head (lane l keeps bytes 2 l and 2 l + 1 of the unit) and, where the rules take it, the CRC: reasm_wave.h
+                const ReasmWaveSrc hd = reasm_wave_head(q, v, lane);
+                uint32_t x = 0;
+                if (D::takes_crc(hd.rd(0), hd.rd(1), total)) x = reasm_wave_crc(q, v, total, lane);   // (the same in every lane; a unit has two bytes at least)
+                const typename D::Row row = D::template row_fields<ReasmWaveSrc>(hd, total, x == 0, w, q.j0 < 0 ? -1 : wa_k(wa[q.j0]), wa_k(wa[q.j1]));
+                if (lane == 0) {
+                    rows[r] = row;
+                    D::account(row.flags, [&](int c) { atomicAdd(&cnt[c], 1); });
+                }
             }
         }
         __syncthreads();
+        // D': the rows in order and the bytes the bank carries from unit to unit
+        if constexpr (D::OWN_ROWS) D::sequence_pass(rows, nrows, ss, &nss, cnt, wsum);
         // E: the offsets of the delivered rows
         {
             int r0, r1; ts_thread_run(nrows, DGRAM_WG, &r0, &r1);
-            auto bytes_of = [&](int r) { return have_out && (rows[r].flags & D::DATAGRAM) ? rows[r].bytes : 0; };
+            // (the watch as an argument: a lambda that captures it costs the MPE kernel its instruction stream)
+            auto bytes_of = [&](int r, const typename D::Watch& of) { return have_out && D::delivers(rows[r], of) ? D::bytes_of(rows[r]) : 0; };
             int mine = 0, mine_n = 0;
-            for (int r = r0; r < r1; ++r) { const int b = bytes_of(r); mine += b; mine_n += b > 0; }
+            for (int r = r0; r < r1; ++r) { const int b = bytes_of(r, w); mine += b; mine_n += b > 0; }
             int at = ts_block_scan<DGRAM_WG>(mine, wsum, &needed);
-            ts_block_scan<DGRAM_WG>(mine_n, wsum, &ndelivered);
+            int idx = ts_block_scan<DGRAM_WG>(mine_n, wsum, &ndelivered);
+            int* sizes = D::SIZE_LIST ? dgram_size_list(rows_g, gridDim.x, max_rows, g) : nullptr;
             for (int r = r0; r < r1; ++r) {
-                const int b = bytes_of(r);
+                const int b = bytes_of(r, w);
                 if (b) rows[r].offset = at;
+                if (D::SIZE_LIST && b) sizes[idx++] = b;
                 at += b;
             }
         }
@@ -171,9 +202,9 @@ __global__ void __launch_bounds__(DGRAM_WG) dgram_commit_kernel(const uint8_t* c
     const typename D::Row* rows = rows_g + (size_t)g * max_rows;
     uint8_t* o = out ? out[g] : nullptr;
     for (int r = wave; o && r < nrows; r += DGRAM_WAVES) {
-        const int off = rows[r].offset, nb = rows[r].bytes;
+        const int off = rows[r].offset, nb = D::bytes_of(rows[r]);
         if (off < 0 || nb <= 0 || off + nb > cap) continue;
-        const int skip = D::ip_at(rows[r]);          // the datagram is the unit's bytes [skip, skip + nb)
+        const int skip = D::ip_at(rows[r]);          // the payload is the unit's bytes [skip, skip + nb)
         reasm_pieces(rec[r], v, skip + nb, [&](int pos, const uint8_t* src, int len) {
             const int a = pos > skip ? pos : skip, b = pos + len;
             if (b > a) ts_wave_copy(o + off + (a - skip), TsBytes{src + (a - pos)}, b - a, lane);
@@ -197,6 +228,7 @@ struct DgramBank {
     std::vector<typename D::Watch> watch;          // nstreams x 4
     std::vector<typename D::Stats> stats;          // nstreams x 4, since reset; the kernels report each call's share (DgramCall)
     std::vector<int> nrows, need_bytes, need_rows; // of the last call per (stream, slot)
+    std::vector<int> ndelivered;                   // where D::SIZE_LIST (else empty): the entries of its size list
     std::vector<DgramCall<D>> h_call;
     std::vector<char> h_args;
     // device banks
@@ -206,7 +238,7 @@ struct DgramBank {
     DevBuf<unsigned> d_wa;                         // nstreams x 4 x max_packets: the slots' packets of the last call
     DevBuf<uint16_t> d_wb;
     DevBuf<ReasmRec> d_recs, d_opens;
-    DevBuf<typename D::Row> d_rows;                // nstreams x 4 x max_rows
+    DevBuf<typename D::Row> d_rows;                // nstreams x 4 x max_rows, and where D::SIZE_LIST the size lists (dgram_size_list)
     DevBuf<DgramCall<D>> d_call;
     DevBuf<uint8_t> d_args;                        // TsBankArgsN<4>(nstreams)
     TsHostStage stage;                             // of the host-buffer entry point
@@ -224,6 +256,7 @@ struct DgramBank {
         watch[at] = w;
         stats[at] = typename D::Stats{};
         nrows[at] = 0;
+        if (D::SIZE_LIST) ndelivered[at] = 0;
         if (ctx) {
             HIP_TRY(hipSetDevice(ctx->device));
             HIP_TRY(hipMemcpy(d_watch + at, &watch[at], sizeof(w), hipMemcpyHostToDevice));
@@ -238,7 +271,7 @@ struct DgramBank {
 
 // ------------------------------------------------------------------------------------------------- the bodies of the C functions
 // H: the handle, a DgramBank<D>
-inline std::string dgram_text(const char* bank, const char* a, const char* cname = "", const char* b = "") { return std::string(bank) + a + cname + b; }
+template <typename... T> inline std::string dgram_text(T... parts) { std::string s; ((s += parts), ...); return s; }
 
 // the device call: d_out 4 pointers per stream or null; only: the one (stream, slot) index that is served, -1: all
 template <typename H>
@@ -265,14 +298,19 @@ int dgram_batch(H* b, const uint8_t* const* d_ts, const int* nbytes, uint8_t* co
     }
     if (!fits) {                                       // nothing has been stored: the same call may come again with more room
         std::fill(b->nrows.begin(), b->nrows.end(), 0);
-        last_error() = dgram_text(D::BANK, "the datagrams of a slot do not fit cap, or its rows max_rows (out_bytes / out_rows hold the sizes)");
+        std::fill(b->ndelivered.begin(), b->ndelivered.end(), 0);
+        last_error() = dgram_text(D::BANK, "the ", D::NOUN, " of a slot do not fit cap, or its rows max_rows (out_bytes / out_rows hold the sizes)");
         return DVBS2GPU_ERR_CAPACITY;
     }
     hipLaunchKernelGGL(dgram_commit_kernel<D>, dim3(ns), dim3(DGRAM_WG), 0, st, a.in(b->d_args), d_out ? a.out(b->d_args) : nullptr, b->max_packets, b->max_rows, cap,
                        b->d_state, b->d_newst, b->d_bufs, b->d_wa, b->d_wb, b->d_recs, b->d_opens, b->d_rows, b->d_call);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    for (int g = 0; g < ns; ++g) { b->account_call(g, b->h_call[g].cnt); b->nrows[g] = b->h_call[g].nrows; }
+    for (int g = 0; g < ns; ++g) {
+        b->account_call(g, b->h_call[g].cnt);
+        b->nrows[g] = b->h_call[g].nrows;
+        if (D::SIZE_LIST) b->ndelivered[g] = b->h_call[g].ndelivered;
+    }
     return 0;
 }
 
@@ -288,7 +326,7 @@ int dgram_create(bool device, dvbs2gpu_ctx* ctx, int nstreams, int max_packets, 
     b->ctx = ctx; b->nstreams = nstreams; b->max_packets = max_packets; b->max_rows = max_rows;
     b->watch.assign(ns, D::NO_WATCH);
     b->stats.assign(ns, typename D::Stats{});
-    b->nrows.assign(ns, 0); b->need_bytes.assign(ns, 0); b->need_rows.assign(ns, 0);
+    b->nrows.assign(ns, 0); b->need_bytes.assign(ns, 0); b->need_rows.assign(ns, 0); b->ndelivered.assign(D::SIZE_LIST ? ns : 0, 0);
     b->h_call.resize(ns);
     if (!ctx) {
         b->host.resize(ns);
@@ -305,7 +343,7 @@ int dgram_create(bool device, dvbs2gpu_ctx* ctx, int nstreams, int max_packets, 
     RC_TRY(b->d_wb.alloc(ns * max_packets, false, what));
     RC_TRY(b->d_recs.alloc(ns * max_rows, false, what));
     RC_TRY(b->d_opens.alloc(ns, false, what));
-    RC_TRY(b->d_rows.alloc(ns * max_rows, false, what));
+    RC_TRY(b->d_rows.alloc(dgram_row_slots<D>(ns, max_rows), false, what));
     RC_TRY(b->d_call.alloc(ns, false, what));
     RC_TRY(b->d_args.alloc(TsBankArgsN<D::SLOTS>(n).L.bytes(), false, what));
     b->h_args.resize(TsBankArgsN<D::SLOTS>(n).L.bytes());
@@ -323,6 +361,7 @@ int dgram_reset(H* b) {
     for (auto& h : b->host) h.clear();
     std::fill(b->stats.begin(), b->stats.end(), typename H::D::Stats{});
     std::fill(b->nrows.begin(), b->nrows.end(), 0);
+    std::fill(b->ndelivered.begin(), b->ndelivered.end(), 0);
     return 0;
 }
 
@@ -363,8 +402,10 @@ int dgram_work(H* b, int stream, int slot, const uint8_t* h_ts, int nbytes, uint
     if (!b->ctx) {
         typename H::HostStream& h = b->host[g];
         // The tables are of the LAST call, which brought the others nothing.  An empty call changes no state (run() with no packet
-        // is the identity), so the other slots are not run: their tables are emptied by count alone.
+        // is the identity), so the other slots are not run: their tables are emptied by count alone.  host[].rows and .bytes of those
+        // slots keep what their own last call left; every getter reads them through nrows / ndelivered, which are 0.
         std::fill(b->nrows.begin(), b->nrows.end(), 0);
+        std::fill(b->ndelivered.begin(), b->ndelivered.end(), 0);
         const std::unique_ptr<typename H::HostStream::State> before(new typename H::HostStream::State(h.st));    // what a capacity failure has to put back
         h.run(h_ts, nbytes / TSMON_TS, h_out != nullptr);
         const bool rows_fit = (int)h.rows.size() <= b->max_rows;
@@ -373,11 +414,12 @@ int dgram_work(H* b, int stream, int slot, const uint8_t* h_ts, int nbytes, uint
         if (!rows_fit || (h_out && (int)h.bytes.size() > cap)) {
             h.st = *before;
             h.rows.clear(); h.bytes.clear();
-            last_error() = dgram_text(D::BANK, "the datagrams do not fit cap, or the rows max_rows (", D::CNAME, "_get_needed holds the sizes)");
+            last_error() = dgram_text(D::BANK, "the ", D::NOUN, " do not fit cap, or the rows max_rows (", D::CNAME, "_get_needed holds the sizes)");
             return DVBS2GPU_ERR_CAPACITY;
         }
         b->account_call(g, h.cnt);
         b->nrows[g] = (int)h.rows.size();
+        if (D::SIZE_LIST) b->ndelivered[g] = h.counter(D::C_DELIVERED);
         if (h_out && !h.bytes.empty()) memcpy(h_out, h.bytes.data(), h.bytes.size());
         return (int)h.bytes.size();
     }

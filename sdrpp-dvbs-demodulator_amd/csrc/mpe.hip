@@ -1,10 +1,11 @@
 // MPE bank (own extension; include/dvbs2gpu.h): the DSM-CC datagram_sections (Multi-Protocol Encapsulation, EN 301 192)
 // of a PID of each of `nstreams` transport streams in HBM, reassembled, checked (CRC-32, MAC filter, LLC/SNAP, IP header) and their IP
 // datagrams laid back to back per slot.  Every rule is in mpe_rules.h, whose MpeHostStream is the sequential definition, the host bank
-// and the kernels' yardstick.  The kernels, the handle and the call are the datagram bank's (dgram_bank.h, shared with ule.hip), here
-// instantiated with MpeRules: a 3-byte header with section_length in bytes 1 and 2, and in phase D up to 84 bytes decide a row (MPE
-// header, LLC/SNAP, an IPv4 header with options, the ports) and the CRC-32 is taken only where mpe_takes_crc says so; the datagram is
-// the section's bytes from 12 or 20 on.  This file holds what is the bank's own: the layout checks, the description and the watch.
+// and the kernels' yardstick.  The kernels, the handle and the call are the datagram bank's (dgram_bank.h, shared with ule.hip and
+// t2mi.hip), here instantiated with MpeRules: a 3-byte header with section_length in bytes 1 and 2, and in phase D up to 84 bytes
+// decide a row (MPE header, LLC/SNAP, an IPv4 header with options, the ports) and the CRC-32 is taken only where mpe_takes_crc says
+// so; the datagram is the section's bytes from 12 or 20 on.  This file holds what is the bank's own: the layout checks, the description
+// and the watch.
 #include "dgram_bank.h"
 #include "mpe_rules.h"
 
@@ -18,7 +19,7 @@ static_assert(sizeof(MpeWatch) == 16, "watch layout");
 static_assert(MPE.max_section_bytes <= MPE_BUF && MPE.max_section_bytes < (1 << 17), "crc32m_xpow takes 17 bits of length");
 static_assert(MPE.head_bytes <= REASM_HEAD && MPE.head_bytes == MPE.mpe_header_bytes + MPE.llc_snap_bytes + 60 + 4, "the head gather holds what a row reads");
 
-struct MpeBankDesc : MpeRules {
+struct MpeBankDesc : MpeRules, DgramIpBank {
     typedef dvbs2gpu_mpe_stats Stats;
     static constexpr const char *BANK = "MPE bank: ", *CNAME = "dvbs2gpu_mpe", *ALLOC = "hipMalloc(mpe)";
 };

@@ -122,9 +122,9 @@ TS_HD inline void mpe_account(unsigned flags, Add add) {
 struct MpeRules {
     typedef MpeRow Row; typedef MpeWatch Watch; typedef MpeCnt Cnt;
     static constexpr MpeWatch NO_WATCH = {-1, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
-    static constexpr int SLOTS = MPE_SLOTS, BUF = MPE_BUF, NCNT = MPE_NCNT, DATAGRAM = MPE_DATAGRAM;
-    // a 3-byte header with section_length in bytes 1 and 2, a length beyond 4093 is bad
-    static constexpr int HEADER = MPE.header_bytes, LEN_A = 1, LEN_B = 2;
+    static constexpr int SLOTS = MPE_SLOTS, BUF = MPE_BUF, NCNT = MPE_NCNT;
+    // a 3-byte header with section_length in bytes 1 and 2, a length beyond 4093 is bad; 0xFF in a section's first place is stuffing
+    static constexpr int HEADER = MPE.header_bytes, LEN_A = 1, LEN_B = 2, STUFFING = 0xFF;
     static constexpr int C_PACKETS = MPC_PACKETS, C_SCR = MPC_SCR, C_MALPKT = MPC_MALPKT, C_DELIVERED = MPC_DELIVERED, C_BYTES = MPC_BYTES;
     static constexpr int C_DROPPED = MPC_DROPPED, C_BAD_UNIT = MPC_MALSEC, C_SLACK = -1;
     // the rules above under the names the shared code calls them by: constant function pointers, not forwarding members (a row returned through one
@@ -134,6 +134,10 @@ struct MpeRules {
     static constexpr auto ip_at = &mpe_ip_at;
     template <typename Src> static constexpr auto row_fields = &mpe_row_fields<Src>;
     template <typename Add> TS_HD static void account(unsigned flags, Add add) { mpe_account(flags, add); }
+    // nothing is carried from section to section; a DATAGRAM row's datagram is delivered
+    TS_HD static void sequence(MpeRow&, uint8_t*) {}
+    TS_HD static bool delivers(const MpeRow& r, const MpeWatch&) { return r.flags & MPE_DATAGRAM; }
+    TS_HD static int bytes_of(const MpeRow& r) { return r.bytes; }
 };
 // the sequential definition: one slot of one stream
 typedef DgramHostStream<MpeRules> MpeHostStream;

@@ -1,8 +1,8 @@
 // PSI section bank (own extension; include/dvbs2gpu.h): PAT / PMT / SI section reassembly with CRC-32 on up to 16
 // watched PIDs of each of `nstreams` transport streams in HBM.  Every rule is in psi_rules.h, whose PsiHostStream is the sequential
 // definition, the host bank and the kernels' yardstick.  How a call's packets are cut into independent pieces -- why that is possible,
-// the packet list, the section walkers and the row numbering -- is ts_reasm.h with the format PsiFmt below (the T2-MI bank, t2mi.hip,
-// is its other user); this file holds what is the bank's own.
+// the packet list, the section walkers and the row numbering -- is ts_reasm.h with the format PsiFmt below (the datagram banks, dgram_bank.h,
+// are its other users); this file holds what is the bank's own.
 //
 //   psi_scan_kernel    one workgroup per stream.
 //     A-C  ts_reasm.h: the packets of the 16 watched PIDs into LDS, one lane per slot for the continuity walk, one lane per PUSI packet

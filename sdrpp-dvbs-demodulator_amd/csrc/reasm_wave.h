@@ -1,6 +1,7 @@
 // What a wave does with ONE unit of a reassembling bank that decides a row from the unit's leading bytes and takes the CRC-32/MPEG over
-// all of them (mpe.hip: sections; ule.hip: SNDUs), stated once on top of reasm_pieces (ts_reasm.h): the head gather,
-// the source that the row rules read it through, and the CRC over shares of the pieces.  Every lane of the wave calls every function.
+// all of them, stated once on top of reasm_pieces (ts_reasm.h): the head gather and the source that the row rules
+// read it through (mpe.hip: sections; ule.hip: SNDUs), and the CRC over shares of the pieces (those two and t2mi.hip: T2-MI packets,
+// a lane per piece).  Every lane of the wave calls every function.
 #pragma once
 #include "ts_reasm.h"
 
@@ -41,10 +42,11 @@ __device__ inline ReasmWaveSrc reasm_wave_head(const ReasmRec& q, const ReasmVie
 // CRC of its share of one PIECE (the unit's bytes in one TS payload) from a zero register, shifted to the unit's end, and the wave sums.
 // `sub` lanes per piece, 64 / sub pieces a round.  A unit has few pieces (9 at 1416 bytes, 24 at 4096, without adaptation fields): with
 // a lane per piece most of the wave would wait for the few lanes that each take 184 bytes, so a piece is cut into `sub` equal shares, as
-// many as the pieces expected of `total` leave room for; units of more pieces (adaptation fields) take further rounds
-template <typename F>
+// many as the pieces expected of `total` leave room for and at most SUB_MAX; units of more pieces (adaptation fields) take further
+// rounds.  SUB_MAX 1, a lane per piece, is for units of up to 46 pieces (t2mi.hip)
+template <int SUB_MAX = 16, typename F>
 __device__ inline uint32_t reasm_wave_crc(const ReasmRec& q, const ReasmView<F>& v, int total, int lane) {
-    int sub = 16;
+    int sub = SUB_MAX;
     while (sub > 1 && sub * (total / (TSMON_TS - 4) + 2) > 64) sub >>= 1;
     const int per_round = 64 / sub;
     uint32_t x = lane == 0 ? crc32m_mulmod(0xFFFFFFFFu, crc32m_xpow((uint32_t)total)) : 0;

@@ -1,16 +1,14 @@
 // The rules of the T2-MI bank (own extension; include/dvbs2gpu.h), each stated once and shared by the kernels
 // (t2mi.hip), the native host bank (T2miHostStream below, behind dvbs2gpu_t2mi_create_host) and a plain C++ test program: the T2-MI
-// packet layout as one struct (T2miLayout), what a TS packet of a slot's PID does to the slot, and what an emitted packet's row says.
+// packet layout as one struct (T2miLayout), what an emitted packet's row says and the packet-count rule.  What a TS packet of a slot's
+// PID does to the slot is the datagram banks' sequential stream (dgram_rules.h, shared with mpe_rules.h and ule_rules.h) with T2miRules.
 //
 // The sequential form -- T2miHostStream::run, packet by packet -- IS the definition; every other form must give its results for every
 // cutting of a stream into calls.  The packet syntax is written from memory of ETSI TS 102 773: every offset and limit the code relies
 // on is a field of T2miLayout, reported through dvbs2gpu_t2mi_get_layout and compared with the tests' model.
 // Standard headers only: the host tests compile this file with a plain C++ compiler.
 #pragma once
-#include "ts_reasm_rules.h"
-
-#include <cstring>
-#include <vector>
+#include "dgram_rules.h"
 
 namespace s2 {
 
@@ -65,84 +63,49 @@ TS_HD inline T2miRow t2mi_row_fields(Rd rd, int total, bool valid, int first_pac
 // does the slot deliver the BBFRAME of this row
 TS_HD inline bool t2mi_delivers(const T2miRow& r, int plp) { return (r.flags & T2MI_BBFRAME) && (plp < 0 || plp == r.plp_id); }
 
-// ------------------------------------------------------------------------------------------------- the sequential definition
-struct T2miState {
-    uint8_t cont = 0, has_count = 0, last_count = 0;       // tsmon_step's byte; there has been a valid packet; its packet_count
-    int fill = 0;                                          // bytes buffered; 0: no packet is open
-    uint8_t buf[T2MI_BUF];
+// the packet-count rule on what a slot carries from packet to packet -- own[0]: there has been a valid packet, own[1]: its packet_count:
+// a valid packet whose count is not the last one's plus one has COUNT_ERROR, and steps the pair
+enum { T2S_HAS_COUNT = 0, T2S_LAST_COUNT = 1 };
+TS_HD inline void t2mi_sequence(T2miRow& r, uint8_t* own) {
+    if (r.flags & T2MI_CRC_ERROR) return;
+    if (own[T2S_HAS_COUNT] && r.packet_count != ((own[T2S_LAST_COUNT] + 1) & 255)) r.flags |= T2MI_COUNT_ERROR;
+    own[T2S_HAS_COUNT] = 1; own[T2S_LAST_COUNT] = r.packet_count;
+}
+// the counters that a row steps, but for the delivery's: add(index into T2miCnt)
+enum { T2C_PACKETS = 0, T2C_T2MI, T2C_CRC, T2C_COUNT, T2C_BB, T2C_BADPAY, T2C_DELIVERED, T2C_BYTES, T2C_DROPPED, T2C_MALPKT, T2C_SCR, T2C_SLACK };
+template <typename Add>
+TS_HD inline void t2mi_account(unsigned flags, Add add) {
+    add(T2C_T2MI);
+    if (flags & T2MI_CRC_ERROR) add(T2C_CRC);
+    if (flags & T2MI_COUNT_ERROR) add(T2C_COUNT);
+    if (flags & T2MI_BBFRAME) add(T2C_BB);
+    if (flags & T2MI_BAD_PAYLOAD) add(T2C_BADPAY);
+}
+
+// ------------------------------------------------------------------------------------------------- what the shared code asks of the bank
+// (dgram_rules.h: the sequential stream; dgram_bank.h: the kernels and the handle)
+struct T2miRules {
+    typedef T2miRow Row; typedef T2miWatch Watch; typedef T2miCnt Cnt;
+    static constexpr T2miWatch NO_WATCH = {-1, -1};
+    static constexpr int SLOTS = T2MI_SLOTS, BUF = T2MI_BUF, NCNT = T2MI_NCNT;
+    // a 6-byte header with payload_bits in bytes 4 and 5; no stuffing and no bad length; what a PUSI packet's pointer bytes hold beyond
+    // the open packet's end is counted
+    static constexpr int HEADER = T2MI.header_bytes, LEN_A = 4, LEN_B = 5, STUFFING = -1;
+    static constexpr int C_PACKETS = T2C_PACKETS, C_SCR = T2C_SCR, C_MALPKT = T2C_MALPKT, C_DELIVERED = T2C_DELIVERED, C_BYTES = T2C_BYTES;
+    static constexpr int C_DROPPED = T2C_DROPPED, C_BAD_UNIT = -1, C_SLACK = T2C_SLACK;
+    static constexpr auto total = &t2mi_total;
+    static constexpr auto sequence = &t2mi_sequence;
+    TS_HD static bool takes_crc(unsigned, unsigned, int) { return true; }      // there is no unchecked packet
+    template <typename Src> TS_HD static T2miRow row_fields(const Src& s, int total, bool crc_ok, const T2miWatch&, int first_packet, int last_packet) {
+        return t2mi_row_fields([&](int i) { return s.rd(i); }, total, crc_ok, first_packet, last_packet);
+    }
+    template <typename Add> TS_HD static void account(unsigned flags, Add add) { t2mi_account(flags, add); }
+    // the BBFRAME of a row lies behind the packet's header and the BBFRAME prefix
+    TS_HD static bool delivers(const T2miRow& r, const T2miWatch& w) { return t2mi_delivers(r, w.plp); }
+    TS_HD static int bytes_of(const T2miRow& r) { return r.bbframe_bytes; }
+    TS_HD static int ip_at(const T2miRow&) { return T2MI.header_bytes + T2MI.bbframe_prefix_bytes; }
 };
-
-// one slot of one stream: a complete reassembler
-struct T2miHostStream {
-    T2miWatch watch = {-1, -1};
-    T2miState st;
-    int first_packet = -1;                                 // of the open packet, in this call
-    // of the last call
-    std::vector<T2miRow> rows;
-    std::vector<uint8_t> bytes;
-    T2miCnt cnt = {};
-
-    void clear() { st = T2miState(); rows.clear(); bytes.clear(); }
-
-    void drop() {
-        if (st.fill > 0) ++cnt.dropped_packets;
-        st.fill = 0;
-    }
-    void emit(int k, bool want_bytes) {
-        const uint8_t* b = st.buf;
-        const int total = st.fill;
-        ++cnt.t2mi_packets;
-        const bool valid = ts_crc32(b, total) == 0;
-        T2miRow r = t2mi_row_fields([&](int i) { return (unsigned)b[i]; }, total, valid, first_packet, k);
-        if (!valid) ++cnt.crc_errors;
-        else {
-            if (st.has_count && r.packet_count != ((st.last_count + 1) & 255)) { r.flags |= T2MI_COUNT_ERROR; ++cnt.count_errors; }
-            st.has_count = 1; st.last_count = r.packet_count;
-            if (r.flags & T2MI_BAD_PAYLOAD) ++cnt.bad_payload;
-            if (r.flags & T2MI_BBFRAME) ++cnt.bbframes;
-            if (want_bytes && t2mi_delivers(r, watch.plp)) {
-                const uint8_t* f = b + T2MI.header_bytes + T2MI.bbframe_prefix_bytes;
-                r.offset = (int32_t)bytes.size();
-                bytes.insert(bytes.end(), f, f + r.bbframe_bytes);
-                ++cnt.bbframes_delivered; cnt.bytes_delivered += r.bbframe_bytes;
-            }
-        }
-        rows.push_back(r);
-    }
-    // n bytes for the slot's packet (open, or starting with them): stops behind the packet's last byte.  true: it was emitted
-    bool feed(const uint8_t* b, int n, int* used, int k, bool want_bytes) {
-        int i = 0;
-        bool done = false;
-        while (i < n) {
-            if (st.fill < T2MI.header_bytes) { st.buf[st.fill++] = b[i++]; continue; }
-            const int total = t2mi_total(st.buf[4], st.buf[5]);
-            const int take = n - i < total - st.fill ? n - i : total - st.fill;
-            memcpy(st.buf + st.fill, b + i, (size_t)take);
-            st.fill += take; i += take;
-            if (st.fill == total) { emit(k, want_bytes); st.fill = 0; done = true; break; }
-        }
-        *used = i;
-        return done;
-    }
-    // what the shared packet loop asks of a format (ts_reasm_rules.h): one slot, no stuffing, the pointer slack counted
-    struct Format {
-        T2miHostStream& h;
-        int slot_of(int pid) const { return pid == h.watch.pid ? 0 : -1; }
-        T2miState& state(int) { return h.st; }
-        T2miCnt& cnt(int) { return h.cnt; }
-        void drop(int) { h.drop(); }
-        bool feed(int, const uint8_t* b, int n, int* used, int k, bool want_bytes) { return h.feed(b, n, used, k, want_bytes); }
-        void begin(int, int k) { h.first_packet = k; }
-        void slack(int) { ++h.cnt.pointer_slack; }
-        bool stuffing(uint8_t) const { return false; }
-    };
-    // one call: n packets.  The caller keeps a copy of `st` if the call may have to be undone.
-    void run(const uint8_t* ts, int n, bool want_bytes) {
-        rows.clear(); bytes.clear();
-        cnt = T2miCnt{};
-        first_packet = -1;
-        if (watch.pid >= 0) ts_reasm_run(Format{*this}, ts, n, want_bytes);
-    }
-};
+// the sequential definition: one slot of one stream
+typedef DgramHostStream<T2miRules> T2miHostStream;
 
 }  // namespace s2

@@ -1,10 +1,11 @@
 // Shared by the banks that work on transport streams in HBM (tsmon.hip: the TS monitor; psi.hip: the PSI sections; pcr.hip: the PCRs; pes.hip: the PES packets;
-// es.hip: the elementary streams; t2mi.hip: the T2-MI packets):
+// es.hip: the elementary streams; t2mi.hip, mpe.hip, ule.hip: T2-MI packets, MPE sections, ULE SNDUs):
 // what a "packet bank" does around its rules.  On the device: the one header read, the one workgroup prefix sum and the contiguous
 // run of items a thread takes ("flags in a mask, scan, scatter").  On the host: the argument table of a call, the count checks,
 // the staging of the single-stream host-buffer entry point and the table getters.  The rules stay in tsmon_rules.h / psi_rules.h / pcr_rules.h / pes_rules.h /
-// t2mi_rules.h; what the two reassembling banks (PSI, T2-MI) share beyond this is ts_reasm.h, what the three watched-PID banks (PCR, PES,
-// ES) share is watch_bank.h (the host half) and, PES and ES, ts_watch.h (device phases A-C); the two datagram banks are dgram_bank.h.
+// t2mi_rules.h / mpe_rules.h / ule_rules.h; what the four reassembling banks (PSI, T2-MI, MPE, ULE) share beyond this is ts_reasm.h, what
+// the three watched-PID banks (PCR, PES, ES) share is watch_bank.h (the host half) and, PES and ES, ts_watch.h (device phases A-C); the
+// three datagram banks (T2-MI, MPE, ULE) are dgram_bank.h.
 #pragma once
 #include "bbts_common.h"
 #include "tsmon_rules.h"
@@ -66,7 +67,7 @@ __device__ inline void ts_thread_run(int n, int wg, int* k0, int* k1) {
 }
 #endif
 
-// the argument table of a call for n streams: input pointers | output pointers, SLOTS per stream (the T2-MI bank: 4) | byte counts
+// the argument table of a call for n streams: input pointers | output pointers, SLOTS per stream (the datagram banks: 4) | byte counts
 template <int SLOTS>
 struct TsBankArgsN {
     ScratchLayout L;

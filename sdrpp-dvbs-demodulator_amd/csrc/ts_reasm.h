@@ -1,5 +1,6 @@
-// The device side of the banks that reassemble length-prefixed units from the payloads of a PID (psi.hip: PSI sections; t2mi.hip:
-// T2-MI packets; rules and sequential definition in ts_reasm_rules.h), stated once.
+// The device side of the banks that reassemble length-prefixed units from the payloads of a PID (psi.hip: PSI sections; dgram_bank.h:
+// the datagram banks -- T2-MI packets, MPE sections, ULE SNDUs; rules and sequential definition in ts_reasm_rules.h; DESIGN section
+// 9), stated once.
 //
 // What makes the parallel form possible: a unit STARTS only behind the pointer field of a PUSI packet, so the chain of unit headers of
 // a TS packet starts at its own pointer and never leaves the packet; only the LAST unit begun in a PUSI packet can reach into the

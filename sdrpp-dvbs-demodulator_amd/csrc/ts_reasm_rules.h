@@ -1,9 +1,9 @@
 // The rules that the banks share which reassemble length-prefixed units from the payloads of one PID (psi_rules.h: PSI sections;
-// t2mi_rules.h: T2-MI packets), each stated once for the kernels (ts_reasm.h), the host banks and the plain C++ test
+// dgram_rules.h: the datagram banks -- T2-MI packets, MPE sections, ULE SNDUs), each stated once for the kernels (ts_reasm.h), the host banks and the plain C++ test
 // programs.  A unit STARTS only behind the pointer field of a PUSI packet; a packet without PUSI only continues the open unit and
 // ignores what is left of its payload; scrambling, a continuity break or a malformed packet drops the open unit.
 //
-// ts_reasm_run, packet by packet, IS the definition.  A format supplies to it (F below; PsiHostStream and T2miHostStream each wrap
+// ts_reasm_run, packet by packet, IS the definition.  A format supplies to it (F below; PsiHostStream and DgramHostStream each wrap
 // themselves in one):
 //   slot_of(pid)                      the slot that takes the PID, -1: none
 //   state(s)  .cont .fill             tsmon_step's byte; the bytes of the open unit, 0: none is open

@@ -2,8 +2,8 @@
 // PID of each of `nstreams` transport streams in HBM, reassembled, checked (CRC-32, NPA filter, extension headers, bridged frames, IP
 // header) and their IP datagrams laid back to back per slot.  Every rule is in ule_rules.h, whose UleHostStream is the sequential
 // definition, the host bank and the kernels' yardstick.  The kernels, the handle and the call are the datagram bank's (dgram_bank.h,
-// shared with mpe.hip), here instantiated with UleRules: the length is known from the first two bytes, and in phase D all 128 leading
-// bytes can decide a row (base header, NPA, 40 bytes of optional headers, a bridged MAC header, an IPv4 header with options, the ports)
+// shared with mpe.hip and t2mi.hip), here instantiated with UleRules: the length is known from the first two bytes, and in phase D all
+// 128 leading bytes can decide a row (base header, NPA, 40 bytes of optional headers, a bridged MAC header, an IPv4 header with options, the ports)
 // and the CRC-32 is always taken: there is no unchecked SNDU.  The extension-header walk of ule_row_fields is data dependent, but every
 // lane walks the same chain from the same shuffled bytes: no divergence.  The datagram is the SNDU's bytes from ule_ip_at(row) on.
 // This file holds what is the bank's own: the layout checks, the description and the watch.
@@ -20,7 +20,7 @@ static_assert(sizeof(UleWatch) == 20, "watch layout");
 static_assert(ULE.max_sndu_bytes <= ULE_BUF && ULE.max_sndu_bytes < (1 << 17), "crc32m_xpow takes 17 bits of length");
 static_assert(ULE.head_bytes == REASM_HEAD && REASM_HEAD == 2 * 64, "the head gather, two bytes per lane, holds exactly what a row reads");
 
-struct UleBankDesc : UleRules {
+struct UleBankDesc : UleRules, DgramIpBank {
     typedef dvbs2gpu_ule_stats Stats;
     static constexpr const char *BANK = "ULE bank: ", *CNAME = "dvbs2gpu_ule", *ALLOC = "hipMalloc(ule)";
 };

@@ -142,9 +142,10 @@ TS_HD inline void ule_account(unsigned flags, Add add) {
 struct UleRules {
     typedef UleRow Row; typedef UleWatch Watch; typedef UleCnt Cnt;
     static constexpr UleWatch NO_WATCH = {-1, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}, 0};
-    static constexpr int SLOTS = ULE_SLOTS, BUF = ULE_BUF, NCNT = ULE_NCNT, DATAGRAM = ULE_DATAGRAM;
-    // the length is known from the first two bytes (D and the 15-bit Length), a Length beyond 4092 is bad
-    static constexpr int HEADER = ULE.length_bytes, LEN_A = 0, LEN_B = 1;
+    static constexpr int SLOTS = ULE_SLOTS, BUF = ULE_BUF, NCNT = ULE_NCNT;
+    // the length is known from the first two bytes (D and the 15-bit Length), a Length beyond 4092 is bad; 0xFF in an SNDU's first place
+    // is the End Indicator or padding
+    static constexpr int HEADER = ULE.length_bytes, LEN_A = 0, LEN_B = 1, STUFFING = 0xFF;
     static constexpr int C_PACKETS = ULC_PACKETS, C_SCR = ULC_SCR, C_MALPKT = ULC_MALPKT, C_DELIVERED = ULC_DELIVERED, C_BYTES = ULC_BYTES;
     static constexpr int C_DROPPED = ULC_DROPPED, C_BAD_UNIT = ULC_MALSNDU, C_SLACK = ULC_SLACK;
     // the rules above under the names the shared code calls them by: constant function pointers, not forwarding members (a row returned through one
@@ -154,6 +155,10 @@ struct UleRules {
     template <typename Src> static constexpr auto row_fields = &ule_row_fields<Src>;
     template <typename Add> TS_HD static void account(unsigned flags, Add add) { ule_account(flags, add); }
     TS_HD static bool takes_crc(unsigned, unsigned, int) { return true; }      // there is no unchecked SNDU
+    // nothing is carried from SNDU to SNDU; a DATAGRAM row's datagram is delivered
+    TS_HD static void sequence(UleRow&, uint8_t*) {}
+    TS_HD static bool delivers(const UleRow& r, const UleWatch&) { return r.flags & ULE_DATAGRAM; }
+    TS_HD static int bytes_of(const UleRow& r) { return r.bytes; }
 };
 // the sequential definition: one slot of one stream
 typedef DgramHostStream<UleRules> UleHostStream;
