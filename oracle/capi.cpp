@@ -145,6 +145,8 @@ int orc_s2rx_tap(void* h, int which, void* dst) {
     return -1;
 }
 float orc_s2rx_nco_freq(void* h) { return ((S2Rx*)h)->nco_freq(); }
+// S2Rx::timing_events: arm 0, arm 127, 0-sample steps, >= 2-sample steps, clamped errors, steps at the frequency limit -- since creation
+void orc_s2rx_timing_events(void* h, long long out[6]) { for (int i = 0; i < 6; ++i) out[i] = ((S2Rx*)h)->timing_events[i]; }
 // tools/pll_tile_study.py: passes-per-tile histogram of the parallel-in-time form of the payload PLL (34 bins) + tiles whose fixed point differed from the serial loop
 void orc_s2rx_pll_study(void* h, int tile, long long* hist34, long long* mismatch) {
     S2Rx* r = (S2Rx*)h;

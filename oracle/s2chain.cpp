@@ -471,9 +471,11 @@ int S2Rx::gardner(int n, const cf* in, cf* out) {   // gardner.cpp:89-152, omega
         if (g_spsctr == 0) {
             cf dfdt;
             if (phase == 0) {
+                timing_events[0]++;
                 cf fT1 = dot8(&buf[g_offset], &bank[(size_t)(phase + 1) * 8]);
                 dfdt = csub(fT1, outVal);
             } else if (phase == 127) {
+                timing_events[1]++;
                 cf fT_1 = dot8(&buf[g_offset], &bank[(size_t)(phase - 1) * 8]);
                 dfdt = csub(outVal, fT_1);
             } else {
@@ -487,11 +489,19 @@ int S2Rx::gardner(int n, const cf* in, cf* out) {   // gardner.cpp:89-152, omega
         }
         g_spsctr++;
         if (g_spsctr >= 2) g_spsctr = 0;
+        if (error > 1.0f || error < -1.0f) timing_events[4]++;
         if (error > 1.0f) error = 1.0f;
         if (error < -1.0f) error = -1.0f;
         g_pcl.advance(error);
+        if (g_pcl.freq == g_pcl.minFreq || g_pcl.freq == g_pcl.maxFreq) timing_events[5]++;
         float delta = floorf(g_pcl.phase);
-        g_offset = (int)((float)g_offset + delta);
+        // a poisoned loop (a NaN error passes both clamps above and makes freq and phase NaN; (int) of a NaN or huge float is INT_MIN or undefined) must not
+        // index buf with it: the call ends here, as the engine's bounded loops do.  What such a call delivers is unspecified; reset() brings the receiver back.
+        const float next = (float)g_offset + delta;
+        if (!std::isfinite(g_pcl.phase) || !(next >= 0.0f && next < 1.0e9f)) { g_offset = n; break; }
+        if (delta == 0.0f) timing_events[2]++;
+        if (delta >= 2.0f) timing_events[3]++;
+        g_offset = (int)next;
         g_pcl.phase -= delta;
     }
     g_offset -= n;

@@ -132,6 +132,9 @@ public:
     void gardner_tile_study(int n, const cf* in);   // the same tiles with the replay restarted at the first symbol whose table cell changed: replay steps, symbols, evaluation passes
     std::vector<int8_t> dbg_llr;        // deinterleaved LLRs per frame
     std::vector<FrameStats> dbg_stats;
+    // what the timing recovery met since this receiver was created (counting only; tests use it to show that a signal drives the loop where they say it does):
+    // on-symbol outputs at arm 0, at arm 127, steps that consumed 0 samples, 2 or more, steps whose error was clamped, steps that left freq at minFreq or maxFreq
+    long long timing_events[6] = {};
     float nco_freq() const { return nco_freq_; }
     float agc_gain_now() const { return agc_gain; }
     s2::ModcodParams mp;

@@ -164,6 +164,8 @@ def _bind_chain():
     L.orc_s2rx_tap.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.orc_s2rx_nco_freq.argtypes = [C.c_void_p]
     L.orc_s2rx_nco_freq.restype = C.c_float
+    L.orc_s2rx_timing_events.argtypes = [C.c_void_p, np.ctypeslib.ndpointer(np.int64, flags='C_CONTIGUOUS')]
+    L.orc_s2rx_timing_events.restype = None
     for name in ('orc_s2rx_agc', 'orc_s2rx_nco', 'orc_s2rx_rrc'):
         getattr(L, name).argtypes = [C.c_void_p, C.c_int, _f32p, _f32p]
         getattr(L, name).restype = None
@@ -243,13 +245,14 @@ def pls_info(pls):
     return mp['plframe'], mp['kbch'] // 8
 
 
-def transmit_vcm(pls_list, nframes, seed=1, esn0_db=200.0, cfo=0.0, timing=0.0, phase0=0.0, lead_symbols=0):
-    """ACM/VCM stream: frame f carries PLS code pls_list[f % len] -> (iq, [bbframe bytes per frame or None for dummy frames])"""
+def transmit_vcm(pls_list, nframes, seed=1, esn0_db=200.0, cfo=0.0, timing=0.0, phase0=0.0, lead_symbols=0, nsamples=0):
+    """ACM/VCM stream: frame f carries PLS code pls_list[f % len] -> (iq, [bbframe bytes per frame or None for dummy frames]);
+    nsamples as in transmit()"""
     L = _bind_chain()
-    t = TxCfg(0, 0, 0, nframes, seed, esn0_db, cfo, timing, phase0, lead_symbols, 0, 0, len(pls_list), (C.c_int * 64)(*pls_list))
+    t = TxCfg(0, 0, 0, nframes, seed, esn0_db, cfo, timing, phase0, lead_symbols, 0, nsamples, len(pls_list), (C.c_int * 64)(*pls_list))
     sizes = [pls_info(pls_list[f % len(pls_list)]) for f in range(nframes)]
     nsym = lead_symbols + sum(s[0] for s in sizes)
-    iq = np.zeros(2 * nsym, np.complex64)
+    iq = np.zeros(nsamples if nsamples else 2 * nsym, np.complex64)
     bb = np.zeros(sum(s[1] for s in sizes) + 8, np.uint8)
     n = L.orc_s2_transmit(C.byref(t), iq.ctypes.data, iq.size, bb.ctypes.data, None, 0)
     assert n == iq.size, (n, iq.size)
@@ -310,6 +313,19 @@ class OracleRx:
                 pos += st.bbframe_bytes
         assert pos == n, (pos, n)
         return frames
+
+    def reset(self):
+        self.L.orc_s2rx_reset(self.h)
+
+    def nco_freq(self):
+        return self.L.orc_s2rx_nco_freq(self.h)
+
+    def timing_events(self):
+        """what the timing recovery met since creation -> dict: on-symbol outputs at arm 0 / arm 127, steps of 0 / of 2 or more samples,
+        steps whose error was clamped, steps that left the loop frequency at its limit"""
+        out = np.zeros(6, np.int64)
+        self.L.orc_s2rx_timing_events(self.h, out)
+        return dict(zip(('arm0', 'arm127', 'step0', 'step2', 'clamped', 'freq_limit'), (int(x) for x in out)))
 
     def tap(self, which):
         n = self.L.orc_s2rx_tap(self.h, which, None)

@@ -179,6 +179,51 @@ def test_dvbs_bank_kernels_equal_the_wave_per_stream_kernels(engine, pkg, slices
     e2.close()
 
 
+def _resample(iq0, ppm):
+    """the signal on a sampling clock that is off by ppm (linear interpolation, as in test_timing_phase_sweeping_through_the_whole_bank_bit_exact: any
+    resampler will do, both sides get the same samples)"""
+    t = np.arange(int(iq0.size / (1 + ppm * 1e-6)) - 2) * (1 + ppm * 1e-6)
+    k = t.astype(np.int64)
+    f = (t - k).astype(np.float32)
+    return (iq0[k] * (1 - f) + iq0[k + 1] * f).astype(np.complex64)
+
+
+@pytest.mark.parametrize('slices', ['1', '3'])
+def test_dvbs_bank_kernels_equal_the_wave_per_stream_kernels_under_clock_drift(engine, pkg, slices):
+    """the bank kernels (several streams per wave, context option dvbs_bank_min = 1) with three of the six carriers on a sampling clock that is off by +1500,
+    -1200 and +300 ppm: the clock error drags their timing phases along the interpolator bank and across its ends at different rates (the oracle shows the one at
+    +1500 ppm hovering around the wrap between row 255 and row 0 for thousands of symbols) while their neighbours in the wave stay put -- symbols, loop state and decoded bits must equal the wave-per-stream path's (which the sweep test above holds to the oracle), call by call"""
+    import torch
+    S = 6
+    ppm = {1: 1500.0, 3: -1200.0, 4: 300.0}
+    iqs = [od.dvbs_iq(r % 5, 30000, seed=60 + r, esn0_db=11.0, cfo=(r - 2) * 6e-4, timing=0.13 * r, phase0=0.2 * r)[0] for r in range(S)]
+    iqs = [_resample(x, ppm[r]) if r in ppm else x for r, x in enumerate(iqs)]
+    counts = [[24576, 20001, 24576, 777, 16384, 9000], [1000, 24576, 63, 24576, 130, 24576], [24576, 4575, 24576, 24576, 8192, 15576]]
+    assert all(sum(c[i] for c in counts) < iqs[i].size for i in range(S))
+    single = [pkg.DvbsDemodBank(engine, 1, max_samples=24576) for _ in range(S)]
+    e2 = pkg.Engine(0, options={'dvbs_bank_min': 1, 'dvbs_fe_slices': int(slices)})
+    bank = pkg.DvbsDemodBank(e2, S, max_samples=24576)
+    pos, nsym = [0] * S, [0] * S
+    try:
+        for rep in range(3):
+            tin = [torch.from_numpy(iqs[i][pos[i]:pos[i] + counts[rep][i]]).cuda() for i in range(S)]
+            tout = [torch.zeros(4 * 8192 + 24576, dtype=torch.uint8, device='cuda') for _ in range(S)]
+            nb = bank.process_batch(tin, tout)
+            for i in range(S):
+                ref = single[i].process(iqs[i][pos[i]:pos[i] + counts[rep][i]])
+                pos[i] += counts[rep][i]
+                nsym[i] += single[i].symbols().size
+                assert np.array_equal(bank.symbols(i).view(np.uint32), single[i].symbols().view(np.uint32)), (rep, i)
+                assert np.array_equal(bank.loop_state(i).view(np.uint32), single[i].loop_state().view(np.uint32)), (rep, i)
+                assert nb[i] == ref.size and np.array_equal(tout[i][:nb[i]].cpu().numpy(), ref), (rep, i)
+        assert min(nsym) > 12000
+    finally:
+        for b in single:
+            b.close()
+        bank.close()
+        e2.close()
+
+
 def test_time_sliced_dvbs_front_end_changes_nothing(engine, pkg):
     """small banks run AGC / FLL + RRC / timing recovery / Costas + soft FIFO + Viterbi as time-sliced stages on three streams (every stage keeps
     its state in the stream record); 1 slice (what a GPU-filling bank uses), 3, 8, the maximum 32 and the default 24 must give the same symbols,
