@@ -1213,7 +1213,7 @@ int dvbs2gpu_pes_get_row_table_device(dvbs2gpu_pes* b, int stream, const dvbs2gp
  *   Limits: max_packets <= 4096 per stream and call, as in the PES bank: the banks chain on the same buffers.  Memory (device banks) per
  *     stream: 384 bytes of state, 128 of watches, 48 bytes per row of max_rows and a call record of 1680 bytes.
  *   NOT done: reassembly of split PES headers; parsing behind the four head bytes (SPS sizes, slice types of H.265, SEI); removal of
- *     emulation-prevention bytes; audio; copying pictures out. */
+ *     emulation-prevention bytes; copying pictures out.  Audio PIDs are the audio bank's (below). */
 typedef struct dvbs2gpu_es dvbs2gpu_es;
 int dvbs2gpu_es_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_es** out);
 /* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_es_work only */
@@ -1276,6 +1276,129 @@ typedef struct dvbs2gpu_es_row {               /* 48 bytes */
 int dvbs2gpu_es_get_row_table(dvbs2gpu_es* b, int stream, dvbs2gpu_es_row* h_rows, int cap, int* n);
 /* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
 int dvbs2gpu_es_get_row_table_device(dvbs2gpu_es* b, int stream, const dvbs2gpu_es_row** d_rows, int* n);
+
+/* ------------------------------------------------------------------ Audio bank (own extension)
+ * Nothing in the reference does this.  For `nstreams` transport streams in HBM a bank follows the frames of up to 16 watched audio PIDs
+ * per stream -- MPEG-1/2/2.5 audio layers I-III, AAC in ADTS, AC-3 and E-AC-3 -- and writes one table row per PES packet start, one
+ * per frame (codec sub-kind, channel mode, sample rate, samples, bitrate, size, position in the elementary stream) and one per loss of
+ * framing, so that a frame's PTS is that of the PES row in front of it and "is the framing intact" is a counter.  The sequential form
+ * below is the definition (csrc/aud_rules.h, AudHostStream::run); no result depends on how a stream is cut into calls or on the
+ * alignment of the input.  The header syntax is written from memory of ISO/IEC 11172-3, 13818-3, 13818-7 and ETSI TS 102 366 and
+ * pinned to no vector of theirs.
+ *   Watches: 16 slots per stream, each empty or a PID 0..0x1FFE with a codec: DVBS2GPU_AUD_MPA, _ADTS, _AC3 (E-AC-3 too: told apart by
+ *     bsid).  A new bank watches nothing.  The same PID in two slots of a stream is an argument error.  Setting a watch starts the slot
+ *     afresh, state and counters.
+ *   Packet, start and segment: exactly steps 1-7 and the start rule of the ES bank (above), not restated: trusted packets of watched
+ *     PIDs, the continuity step, duplicates ignored, CC_ERROR / DISC / malformed / scrambled -> a RESET, a valid PES start opens a
+ *     segment and does not reset, an invalid start unsyncs the slot, SPLIT_HEADER, one PES row per start, bytes_unsynced.
+ *   Accepted bytes: es_count, the last 7 accepted bytes and have as in the ES bank.  For every accepted byte with have = 7 the window
+ *     w0..w7 lies at ES position q = es_count - 7.
+ *   Framer: per slot `locked`, `next` (a 64-bit ES position) and `params` (the previous frame's parameter word; none since the
+ *     acquisition).
+ *     Acquire: a VALID start that finds the slot not locked sets locked, next := the ES position of its segment's first byte
+ *       (acquisitions), and the coming FRAME or LOSS row is marked ACQUIRED.  Nothing is acquired elsewhere: lock is taken at PES payload
+ *       starts only -- a departure from a free-running sync search, and what PES-aligned broadcast audio needs -- so that sync words
+ *       inside payloads never count and no result depends on the cut into calls.
+ *     Check: when locked and q = next, the window is parsed (below).  Valid: a FRAME row at es_offset = q, next += frame_bytes, and
+ *       CHANGE if the parameter word differs from params (never on the first frame after an acquisition; param_changes).  Invalid: a LOSS
+ *       row (es_offset = q, head = w0..w3), locked := 0, sync_losses.  A byte accepted while not locked adds to bytes_unlocked (the byte
+ *       that completes a failing window was accepted while locked).
+ *     A reset and an invalid start unlock without a row (and set `lost`: RESYNC on the next row, as in the ES bank).  A valid start
+ *       while locked whose segment does not begin at next counts unaligned_starts and changes nothing: frames may straddle PES packets.
+ *     A frame is reported by the packet that holds w7; a frame whose 8th byte never arrives is never reported.  next may lie any
+ *       distance beyond the bytes received.  frame_bytes >= 7 and a LOSS unlocks: a packet yields at most 27 FRAME / LOSS rows.
+ *   Parse, a pure function of the 8 bytes and the slot's codec:
+ *     MPA   w0..w3 as the 32-bit header: 11 sync bits; version 3 MPEG-1, 2 MPEG-2, 0 MPEG-2.5, 1 invalid; layer 3 I, 2 II, 1 III, 0
+ *           invalid; bitrate index 0 (free format) and 15 invalid, sampling index 3 invalid.  kbps by index 1..14 -- V1 L1 32..448 in
+ *           steps of 32; V1 L2 32 48 56 64 80 96 112 128 160 192 224 256 320 384; V1 L3 32 40 48 56 64 80 96 112 128 160 192 224 256
+ *           320; V2/2.5 L1 32 48 56 64 80 96 112 128 144 160 176 192 224 256; V2/2.5 L2, L3 8 16 24 32 40 48 56 64 80 96 112 128 144
+ *           160.  fs 44100 / 48000 / 32000, halved for V2, quartered for V2.5.  Bytes (integer floor): L1 (12 br / fs + pad) 4; L2 and
+ *           L3 of V1 144 br / fs + pad; L3 of V2/2.5 72 br / fs + pad.  Samples 384 / 1152 / 576 likewise.  code = version << 2 | layer
+ *           (the header's bits), detail = mode (0 stereo, 1 joint, 2 dual, 3 mono).
+ *     ADTS  12 sync bits, layer bits 0, sampling_frequency_index <= 12 (96000 88200 64000 48000 44100 32000 24000 22050 16000 12000
+ *           11025 8000 7350); aac_frame_length: 13 bits, the low 2 of w3, w4, the top 3 of w5, valid when >= 7 (>= 9 with
+ *           protection_absent = 0); samples 1024 (blocks + 1), blocks the low 2 bits of w6.  code = ID << 2 | profile, detail =
+ *           channel_configuration.
+ *     AC3   w0 w1 = 0B 77; bsid the top 5 bits of w5.  bsid <= 10, AC-3: fscod (top 2 bits of w4) 3 invalid, frmsizecod (the low 6)
+ *           > 37 invalid; br = 32 40 48 56 64 80 96 112 128 160 192 224 256 320 384 448 512 576 640 [frmsizecod >> 1]; 16-bit words:
+ *           2 br at 48 k, 3 br at 32 k, floor(320 br / 147) + (frmsizecod & 1) at 44.1 k; bytes twice that, samples 1536; detail =
+ *           acmod.  bsid 11..16, E-AC-3: bytes 2 (frmsiz + 1), frmsiz the 11 bits behind strmtyp and substreamid, invalid under 7;
+ *           fscod 3 selects fscod2 (24000 22050 16000, 6 blocks, 3 invalid), else numblkscod 1 2 3 6 blocks; samples 256 blocks;
+ *           detail = acmod | lfeon << 3.  Any other bsid: invalid.  code = bsid.
+ *     kbps of ADTS and E-AC-3, whose headers name none: floor(8 frame_bytes fs / (1000 samples)).  The parameter word holds everything
+ *     named here but padding and length (the MPA mode extension, private and copyright bits are not parameters).
+ *   Row: `packet` of a FRAME or LOSS row is the packet that holds w7.  Order: by packet in input order across the slots; within a
+ *     packet the PES row first, then by the completing byte's place.  The joins are the ES bank's: a frame belongs to the last PES row
+ *     of its slot whose es_offset is <= its own (its PTS; the first frame of an aligned PES packet has exactly that offset), and a
+ *     frame's size is also the difference of neighbouring offsets.  The table holds the first max_rows rows of a call; out_rows[]
+ *     carries the true count, rows_dropped accumulates the excess, the counters cover everything.
+ *   State (32 bytes per slot) survives from call to call.  reset forgets it (positions and counters too; the watches stay).
+ *   Limits: max_packets <= 4096 per stream and call, as in the ES bank: the banks chain on the same buffers.  Memory (device banks) per
+ *     stream: 512 bytes of state, 128 of watches, 48 bytes per row of max_rows and a call record of 1296 bytes.
+ *   NOT done: a sync search outside PES starts (a PID whose PES packets never begin with a frame is never locked); LATM/LOAS, DTS,
+ *     AC-4; free-format MPA; CRC checks of frames; a check of the PTS step against the frames' duration; copying frames out.  DVB's AC-3
+ *     in private stream type 0x06 is told by a descriptor, which the PSI bank's PMT view does not carry: the caller names such a PID
+ *     with set_watch. */
+typedef struct dvbs2gpu_aud dvbs2gpu_aud;
+int dvbs2gpu_aud_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, int max_rows, dvbs2gpu_aud** out);
+/* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_aud_work only */
+int dvbs2gpu_aud_create_host(int nstreams, int max_packets, int max_rows, dvbs2gpu_aud** out);
+int dvbs2gpu_aud_reset(dvbs2gpu_aud* b);
+void dvbs2gpu_aud_destroy(dvbs2gpu_aud* b);
+#define DVBS2GPU_AUD_MPA 1
+#define DVBS2GPU_AUD_ADTS 2
+#define DVBS2GPU_AUD_AC3 3
+/* slot 0..15; pid 0..0x1FFE with a codec, or -1: the slot watches nothing (the codec is ignored) */
+int dvbs2gpu_aud_set_watch(dvbs2gpu_aud* b, int stream, int slot, int pid, int codec);
+/* d_ts[i]: DEVICE pointer to nbytes[i] bytes (a multiple of 188, at most 188*max_packets) of stream i, of any alignment.  out_rows
+ * (host, may be NULL): the rows of the call per stream, of which the table holds the first max_rows.  One kernel launch.
+ * Synchronous on `stream`; chained behind a packetiser or monitor call on the same stream, no packet visits the host. */
+int dvbs2gpu_aud_process_batch(dvbs2gpu_aud* b, const uint8_t* const* d_ts, const int* nbytes, int* out_rows, void* stream);
+/* one stream of any bank with a HOST buffer: returns the rows of the call or a negative error.  The other streams of the bank receive
+ * an empty call. */
+int dvbs2gpu_aud_work(dvbs2gpu_aud* b, int stream, const uint8_t* h_ts, int nbytes);
+typedef struct dvbs2gpu_aud_stats {            /* of a slot, since creation, reset or the slot's last set_watch; kept on the host */
+    int64_t packets;                 /* trusted packets of the watched PID, duplicates among them */
+    int64_t payload_bytes, es_bytes, bytes_unsynced, duplicates, cc_errors, scrambled_packets, malformed_packets, resets;
+    int64_t pes_starts, pes_invalid, split_headers;
+    int64_t frames, frame_bytes_total, samples_total;   /* FRAME rows, and the sums of their frame_bytes and samples */
+    int64_t acquisitions, sync_losses, param_changes, unaligned_starts, bytes_unlocked;
+} dvbs2gpu_aud_stats;
+/* slot -1: the sum over the stream's slots */
+int dvbs2gpu_aud_get_stats(dvbs2gpu_aud* b, int stream, int slot, dvbs2gpu_aud_stats* h_out);
+typedef struct dvbs2gpu_aud_stream_stats {
+    int64_t packets;                 /* every 188 bytes handed in: the position of the next packet */
+    int64_t rows_dropped;
+} dvbs2gpu_aud_stream_stats;
+int dvbs2gpu_aud_get_stream_stats(dvbs2gpu_aud* b, int stream, dvbs2gpu_aud_stream_stats* h_out);
+#define DVBS2GPU_AUD_UNIT_PES 0
+#define DVBS2GPU_AUD_UNIT_FRAME 1
+#define DVBS2GPU_AUD_UNIT_LOSS 2
+#define DVBS2GPU_AUD_ACQUIRED 1
+#define DVBS2GPU_AUD_RESYNC 2
+#define DVBS2GPU_AUD_UNSYNCED 4
+#define DVBS2GPU_AUD_SPLIT_HEADER 8
+#define DVBS2GPU_AUD_CHANGE 16
+#pragma pack(push, 4)
+typedef struct dvbs2gpu_aud_row {              /* 48 bytes, laid out like dvbs2gpu_es_row (packet in 16 bits: it is below 4096) */
+    uint16_t pid;                    /* offset 0 */
+    uint8_t slot, unit;              /* 2, 3: DVBS2GPU_AUD_UNIT_PES, _FRAME, _LOSS */
+    uint8_t code;                    /* 4: the codec's sub-kind (see Parse); PES rows: stream_id */
+    uint8_t detail;                  /* 5: the channel mode (see Parse); PES rows: the PES bank's kind */
+    uint16_t flags;                  /* 6 */
+    uint16_t packet;                 /* 8: index in this call of the packet that holds w7; PES rows: the start */
+    uint16_t kbps;                   /* 10: FRAME rows */
+    uint32_t head;                   /* 12: w0..w3, w0 in the high byte; PES rows: PES_packet_length */
+    uint64_t es_offset;              /* 16: of w0; PES rows: es_count before the start's segment */
+    uint64_t pts, dts;               /* 24, 32: PES rows; all ones: absent, and in FRAME and LOSS rows */
+    uint32_t sample_rate;            /* 40: FRAME rows, Hz */
+    uint16_t frame_bytes, samples;   /* 44, 46: FRAME rows */
+} dvbs2gpu_aud_row;
+#pragma pack(pop)
+/* h_rows[cap] (host); *n = rows of the last call in the table, of which min(*n, cap) are written */
+int dvbs2gpu_aud_get_row_table(dvbs2gpu_aud* b, int stream, dvbs2gpu_aud_row* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_aud_get_row_table_device(dvbs2gpu_aud* b, int stream, const dvbs2gpu_aud_row** d_rows, int* n);
 
 /* ------------------------------------------------------------------ T2-MI bank (own extension)
  * Nothing in the reference does this.  A DVB-S2 carrier may carry a T2-MI stream (ETSI TS 102 773, the DVB-T2 modulator interface) on

@@ -615,7 +615,7 @@ private:
 };
 
 namespace detail {
-/* What PcrBank, PesBank and EsBank share (the watched-PID banks: dvbs2gpu_pcr_*, dvbs2gpu_pes_*, dvbs2gpu_es_*): everything but
+/* What PcrBank, PesBank, EsBank and AudBank share (the watched-PID banks: dvbs2gpu_pcr_*, dvbs2gpu_pes_*, dvbs2gpu_es_*, dvbs2gpu_aud_*): everything but
  * setWatch(), the rate and which PIDs of a PMT followPmts() takes.  A: the bank's C functions and types --  Handle, Stats, StreamStats,
  * Row;  name ("PcrBank");  create, create_host, destroy, reset, work, get_stats, get_stream_stats, get_row_table (pointers to the C
  * functions). */
@@ -719,6 +719,17 @@ struct EsApi {
     static constexpr auto get_stream_stats = &dvbs2gpu_es_get_stream_stats;
     static constexpr auto get_row_table = &dvbs2gpu_es_get_row_table;
 };
+struct AudApi {
+    typedef dvbs2gpu_aud Handle; typedef dvbs2gpu_aud_stats Stats; typedef dvbs2gpu_aud_stream_stats StreamStats; typedef dvbs2gpu_aud_row Row;
+    static constexpr const char* name = "AudBank";
+    static constexpr auto create = &dvbs2gpu_aud_create, create_host = &dvbs2gpu_aud_create_host;
+    static constexpr auto destroy = &dvbs2gpu_aud_destroy;
+    static constexpr auto reset = &dvbs2gpu_aud_reset;
+    static constexpr auto work = &dvbs2gpu_aud_work;
+    static constexpr auto get_stats = &dvbs2gpu_aud_get_stats;
+    static constexpr auto get_stream_stats = &dvbs2gpu_aud_get_stream_stats;
+    static constexpr auto get_row_table = &dvbs2gpu_aud_get_row_table;
+};
 }   // namespace detail
 /* PCR bank for one transport stream (dvbs2gpu_pcr_*, include/dvbs2gpu.h; an extension): PCR repetition, discontinuity and accuracy
  * checks on up to 16 watched PIDs behind BBFrameTSParser, DVBSDemod or TSMonitor.  init() (a device bank) or initHost() (the
@@ -800,6 +811,35 @@ public:
     }
     /* the rows of the last work(), in row order (the first max_rows) */
     std::vector<dvbs2gpu_es_row> rows() { return table(); }
+};
+/* Audio bank for one transport stream (dvbs2gpu_aud_*, include/dvbs2gpu.h; an extension): a frame index of up to 16 watched audio PIDs
+ * (MPEG audio, ADTS, AC-3 / E-AC-3) behind BBFrameTSParser, DVBSDemod or TSMonitor, one row per PES packet start, per frame and per
+ * loss of framing.  init() (a device bank) or initHost() (the library's host implementation, no device) and the setters throw;
+ * work() sits in the data path and does NOT throw: a failing call returns 0 and leaves its code in status() and its text in error(),
+ * sticky until clearStatus(). */
+class AudBank : public detail::WatchBank<detail::AudApi> {
+public:
+    /* slot 0..15; pid -1 clears the slot; codec DVBS2GPU_AUD_MPA, _ADTS or _AC3 */
+    void setWatch(int slot, int pid, int codec = 0) {
+        check(dvbs2gpu_aud_set_watch(need(), 0, slot, pid, codec));
+        watched[slot] = pid;
+    }
+    /* the codec of a PMT stream_type: 0x03 / 0x04 MPA, 0x0F ADTS, 0x81 / 0x87 AC3, 0: none of them.  The PMT views carry no
+     * descriptors: DVB's AC-3 in private stream type 0x06 cannot be told, the caller names such a PID with setWatch() */
+    static int codecOf(int stream_type) {
+        return stream_type == 0x03 || stream_type == 0x04 ? DVBS2GPU_AUD_MPA : stream_type == 0x0F ? DVBS2GPU_AUD_ADTS
+             : stream_type == 0x81 || stream_type == 0x87 ? DVBS2GPU_AUD_AC3 : 0;
+    }
+    /* watches the audio PIDs of the PMTs that `psi` holds decoded, in free slots, in the order of its slots and then of each PMT's
+     * elementary streams; other stream types and PIDs watched already are skipped; returns the PIDs that found no free slot */
+    std::vector<int> followPmts(PsiBank& psi) {
+        return followWith(psi, [](const dvbs2gpu_psi_pmt&, const std::vector<dvbs2gpu_psi_es>& es, auto offer) {
+            for (const dvbs2gpu_psi_es& e : es)
+                if (const int codec = codecOf(e.stream_type)) offer(e.elementary_pid, codec);
+        }, [this](int slot, int pid, int codec) { setWatch(slot, pid, codec); });
+    }
+    /* the rows of the last work(), in row order (the first max_rows) */
+    std::vector<dvbs2gpu_aud_row> rows() { return table(); }
 };
 namespace detail {
 /* What MpeBank, UleBank and T2miBank share (the datagram banks: dvbs2gpu_mpe_*, dvbs2gpu_ule_*, dvbs2gpu_t2mi_*): everything but

@@ -205,6 +205,26 @@ class EsRow(C.Structure):
                 ('packet', C.c_int32), ('head', C.c_uint32), ('es_offset', C.c_uint64), ('pts', C.c_uint64), ('dts', C.c_uint64), ('reserved', C.c_uint64)]
 
 
+class AudStats(C.Structure):
+    """dvbs2gpu_aud_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('packets', 'payload_bytes', 'es_bytes', 'bytes_unsynced', 'duplicates', 'cc_errors', 'scrambled_packets',
+                                         'malformed_packets', 'resets', 'pes_starts', 'pes_invalid', 'split_headers', 'frames', 'frame_bytes_total',
+                                         'samples_total', 'acquisitions', 'sync_losses', 'param_changes', 'unaligned_starts', 'bytes_unlocked')]
+
+
+class AudStreamStats(C.Structure):
+    """dvbs2gpu_aud_stream_stats"""
+    _fields_ = [('packets', C.c_int64), ('rows_dropped', C.c_int64)]
+
+
+class AudRow(C.Structure):
+    """dvbs2gpu_aud_row"""
+    _pack_ = 4
+    _fields_ = [('pid', C.c_uint16), ('slot', C.c_uint8), ('unit', C.c_uint8), ('code', C.c_uint8), ('detail', C.c_uint8), ('flags', C.c_uint16),
+                ('packet', C.c_uint16), ('kbps', C.c_uint16), ('head', C.c_uint32), ('es_offset', C.c_uint64), ('pts', C.c_uint64), ('dts', C.c_uint64),
+                ('sample_rate', C.c_uint32), ('frame_bytes', C.c_uint16), ('samples', C.c_uint16)]
+
+
 class T2miLayout(C.Structure):
     """dvbs2gpu_t2mi_layout"""
     _fields_ = [(k, C.c_int32) for k in ('header_bytes', 'crc_bytes', 'min_packet_bytes', 'max_packet_bytes', 'bbframe_type', 'bbframe_prefix_bytes',
@@ -470,12 +490,13 @@ PROTOTYPES = {
     'dvbs2gpu_psi_get_programs': (_i, [_vp, _i, C.POINTER(PsiPat), C.POINTER(PsiProgram), _i, C.POINTER(_i)]),
     'dvbs2gpu_psi_get_program_map': (_i, [_vp, _i, _i, C.POINTER(PsiPmt), C.POINTER(PsiEs), _i, C.POINTER(_i)]),
 }
-# the three watched-PID banks (csrc/watch_bank.h): the same functions but for the prefix, the structures, what set_watch takes behind the
+# the four watched-PID banks (csrc/watch_bank.h): the same functions but for the prefix, the structures, what set_watch takes behind the
 # PID and the rate functions
 for _p, _St, _SSt, _Row, _watch, _own in (
         ('pcr', PcrStats, PcrStreamStats, PcrRow, [], {'set_rate': (_i, [_vp, _i, C.c_uint64, _i]), 'get_rate': (_i, [_vp, _i, _i, C.POINTER(C.c_double)])}),
         ('pes', PesStats, PesStreamStats, PesRow, [], {'set_rate': (_i, [_vp, _i, C.c_uint64])}),
-        ('es', EsStats, EsStreamStats, EsRow, [_i], {})):
+        ('es', EsStats, EsStreamStats, EsRow, [_i], {}),
+        ('aud', AudStats, AudStreamStats, AudRow, [_i], {})):
     PROTOTYPES.update({'dvbs2gpu_%s_%s' % (_p, _k): _v for _k, _v in {
         'create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
         'create_host': (_i, [_i, _i, _i, C.POINTER(_vp)]),
@@ -1669,7 +1690,7 @@ class PsiBank(_TsBank):
 
 class _WatchBank(_TsBank):
     """what the banks share that judge up to 16 watched PIDs per stream and write one row table per stream (csrc/watch_bank.h; PcrBank,
-    PesBank, EsBank).  A bank names its C prefix (_c) and its row and statistics structures (_Row, _Stats, _StreamStats), gives the row
+    PesBank, EsBank, AudBank).  A bank names its C prefix (_c) and its row and statistics structures (_Row, _Stats, _StreamStats), gives the row
     table its public names and adds stream_stats(), follow_pmts() and what it is told beyond the watch list."""
     SLOTS = 16
     _c = _Row = _Stats = _StreamStats = None
@@ -1851,6 +1872,47 @@ class EsBank(_WatchBank):
         """watches the video PIDs of the PMTs that `psi_bank` (a PsiBank that read the same stream) holds decoded -- stream types 0x01 and
         0x02 as MPEG2, 0x1B as H264, 0x24 as H265, everything else skipped -- in free slots, in the order of its slots and then of each
         PMT's elementary streams; PIDs watched already are skipped -> the PIDs that found no free slot"""
+        codecs = self.STREAM_TYPE_CODECS
+        return self._follow(psi_bank, stream, lambda hdr, es: [(pid, codecs[stream_type]) for stream_type, pid in es if stream_type in codecs])
+
+    def stream_stats(self, stream=0):
+        st = self._stream_stats(stream)
+        return dict(packets=int(st.packets), rows_dropped=int(st.rows_dropped))
+
+
+class AudBank(_WatchBank):
+    """Audio bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, audio bank): the frames of up to 16 watched audio
+    PIDs per stream (MPEG audio, ADTS, AC-3 / E-AC-3) are followed header by header from PES payload starts on; one table row per PES
+    packet start, per frame (codec sub-kind, channel mode, sample rate, samples, bitrate, size, position in the elementary stream) and
+    per loss of framing."""
+    _c, _Row, _Stats, _StreamStats = 'dvbs2gpu_aud', AudRow, AudStats, AudStreamStats
+    _destroy = 'dvbs2gpu_aud_destroy'
+    SLOTS = 16
+    MPA, ADTS, AC3 = 1, 2, 3
+    PES, FRAME, LOSS = range(3)
+    ACQUIRED, RESYNC, UNSYNCED, SPLIT_HEADER, CHANGE = 1, 2, 4, 8, 16
+    NO_TS = (1 << 64) - 1
+    STREAM_TYPE_CODECS = {0x03: 1, 0x04: 1, 0x0F: 2, 0x81: 3, 0x87: 3}      # PMT stream_type -> codec
+    ROW_KEYS = tuple(k for k, _ in AudRow._fields_)
+    rows, rows_device = _WatchBank._table, _WatchBank._table_device
+
+    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=4096):
+        super().__init__(engine, nstreams, max_packets, max_rows)
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096, max_rows=4096):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        return super().host(nstreams, max_packets, max_rows)
+
+    def set_watch(self, stream, slot, pid, codec=0):
+        """pid -1 clears the slot; the slot starts afresh"""
+        super().set_watch(stream, slot, pid, codec)
+
+    def follow_pmts(self, psi_bank, stream=0):
+        """watches the audio PIDs of the PMTs that `psi_bank` (a PsiBank that read the same stream) holds decoded -- stream types 0x03 and
+        0x04 as MPA, 0x0F as ADTS, 0x81 and 0x87 as AC3, everything else skipped -- in free slots, in the order of its slots and then of
+        each PMT's elementary streams; PIDs watched already are skipped -> the PIDs that found no free slot.  The PMT views carry no
+        descriptors: DVB's AC-3 in private stream type 0x06 cannot be followed, the caller names such a PID with set_watch()"""
         codecs = self.STREAM_TYPE_CODECS
         return self._follow(psi_bank, stream, lambda hdr, es: [(pid, codecs[stream_type]) for stream_type, pid in es if stream_type in codecs])
 
