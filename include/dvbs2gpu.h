@@ -1959,6 +1959,127 @@ int dvbs2gpu_ipts_get_row_table(dvbs2gpu_ipts* b, int stream, dvbs2gpu_ipts_row*
 /* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
 int dvbs2gpu_ipts_get_row_table_device(dvbs2gpu_ipts* b, int stream, const dvbs2gpu_ipts_row** d_rows, int* n);
 
+/* ------------------------------------------------------------------ IP output bank (own extension)
+ * Nothing in the reference does this.  It is the IP-TS bank's direction reversed: a head-end sends every selected service as MPEG-TS in
+ * UDP or in RTP (RFC 2250, payload type 33, normally 7 x 188 bytes per datagram) to a multicast group.  For `nstreams` transport
+ * streams in HBM -- the d_ts[i] / nbytes[i] of every TS bank -- a bank picks the packets of up to 4 flow slots per stream, groups each
+ * slot's packets into datagrams with complete IPv4 / IPv6 + UDP (+ RTP) headers and checksums, lays each slot's datagrams back to back
+ * in a device buffer and writes one table row per datagram: a dvbs2gpu_ipts_view of kind RAW_IP as it stands, which the IP-TS bank
+ * reads back.  The sequential form below is the definition (csrc/ipout_rules.h, IpoutHostStream::run); the kernels give its results for
+ * every cutting of a stream into calls.  The syntax is written from memory of RFC 768, RFC 791, RFC 8200, RFC 3550 and RFC 2250 and
+ * pinned to no vector of theirs; the offsets are those of dvbs2gpu_ipts_layout and dvbs2gpu_mpe_layout, and what they do not name is
+ * dvbs2gpu_ipout_layout.
+ *   Packet: 188 bytes at offset 188 k.  b0 != 0x47: counted as bad_sync, it enters no slot.  Else PID = (b1 & 0x1F) << 8 | b2 as it
+ *     stands; TEI and the scrambling bits are not looked at: the bank forwards, it does not judge.  The stream's position n (64 bits,
+ *     since creation or reset) counts every 188 bytes handed in; it is the counter `packets`.
+ *   Flow slot: 4 per stream, each empty (family 0) or a dvbs2gpu_ipout_flow with a PID list.  pid_mode 0: every PID enters; 1: the
+ *     listed ones; 2: all but the listed ones; drop_null keeps PID 0x1FFF out whatever the list says (the monitor's filter).  The slots
+ *     are independent: one packet may enter several.  A new bank has no flow.  set_flow clears the slot's counters, its held packets and
+ *     its datagram count (the RTP sequence starts at seq_base again); the stream's clock stays.
+ *   Clock: per stream (q, r), both 0 in a new bank and after reset, and the rate tpp of set_rate (0 in a new bank: q never moves), with
+ *     D = 300 << 24.  The tick value of an input packet, good sync byte or not, is q before it; after it r += tpp, q += r / D (q mod
+ *     2^32), r %= D.  So q counts 90 kHz ticks.  A rate change takes effect at the next call; q and r stay.
+ *   Datagrams: a slot's passing packets, in input order, follow the 0 .. P-1 packets it holds from earlier calls; every full group of
+ *     P = packets_per_datagram packets is a datagram, the rest is held with the tick value of its first packet.  With the call's flush
+ *     flag a non-empty rest leaves as one SHORT datagram at the end of the call, also where the call brought the slot nothing.  Without
+ *     flush the output is the same for every cutting of the stream into calls.  A set_flow with another P meets no held packets: it
+ *     dropped them.
+ *   Headers, all numbers big-endian:
+ *     IPv4 (20 bytes): 45, dscp << 2, total length, identification 00 00, 40 00 (DF), ttl, 17, header checksum, source, destination.
+ *     IPv6 (40 bytes): version 6, traffic class dscp << 2, flow label 0, payload length, next header 17, hop limit = ttl, source,
+ *       destination.
+ *     UDP (8): source port, destination port, length L, checksum: the ones' complement of the ones'-complement sum over the
+ *       pseudo-header (as rule 7 of the IP-TS bank) and the L UDP bytes with a zero checksum field; always computed, on IPv4 too; a
+ *       computed 0x0000 is sent as 0xFFFF.
+ *     RTP (mode RTP, 12): 80, 21 (marker 0, payload type 33), seq = seq_base + the slot's datagrams so far (since set_flow or reset)
+ *       mod 65536, timestamp = timestamp_base + the tick value of the datagram's first packet mod 2^32, ssrc.  Mode RAW has no RTP
+ *       header; the row's rtp_seq and rtp_timestamp are 0.
+ *     Then the datagram's packets, 188 bytes each, unchanged.
+ *   Row: one per datagram, per slot, in output order (dvbs2gpu_ipout_row).  Flags RTP (the mode), SHORT (fewer than P packets), CARRIED
+ *     (it begins with packets held from earlier calls).  first_packet: the index in this call's input of the first packet that the
+ *     datagram takes from this call, -1 if it takes none.  udp_checksum: as sent.
+ *   Counters, 64 bits on the host: per stream packets and bad_sync; per slot passed (packets that entered), datagrams, short_datagrams,
+ *     ts_packets (in datagrams), bytes_delivered, and held: what the slot holds now, not a sum over calls.
+ *   Capacity: sizes first.  If a slot's bytes exceed cap the call returns DVBS2GPU_ERR_CAPACITY, out_bytes[] holds the needed sizes; no
+ *     state or counter of any stream has advanced, the clock neither, the tables of the call are empty, the call can be repeated.
+ *   State survives from call to call.  reset forgets state (clock, held packets, datagram counts) and counters; flows and rates stay.
+ *   Limits: max_packets <= 8192 per stream and call; a call makes at most max(1, packets) datagrams per slot.  Memory (device banks)
+ *     per stream: the PID bitmaps, 1 KiB per slot; the held packets, 6 x 188 bytes per slot, not doubled (the commit kernel reads them
+ *     for a slot's first datagram, meets a barrier and only then writes them); the row tables, 24 bytes x max_packets per slot; a
+ *     list of the passing packets' indices, 2 bytes x max_packets per slot; 0.3 KB of flows and state.
+ *   NOT done: FEC (SMPTE 2022-1); RTCP; IPv4 options and fragmentation; IPv6 extension headers; VLAN / Ethernet framing; pacing (the
+ *     rows carry the timestamps a sender paces by); PCR-locked timestamps: the clock is the packet count at the set rate. */
+typedef struct dvbs2gpu_ipout dvbs2gpu_ipout;
+#define DVBS2GPU_IPOUT_MODE_RAW 0
+#define DVBS2GPU_IPOUT_MODE_RTP 1
+typedef struct dvbs2gpu_ipout_flow {           /* 56 bytes */
+    int32_t family;                  /* 4, 6, or 0: the slot is empty and nothing else is read */
+    uint8_t src_addr[16], dst_addr[16];        /* an IPv4 address in the first four bytes, network order */
+    uint16_t src_port, dst_port;
+    uint8_t ttl;                     /* the hop limit on IPv6 */
+    uint8_t dscp;                    /* 0..63 */
+    uint8_t mode;                    /* DVBS2GPU_IPOUT_MODE_* */
+    uint8_t packets_per_datagram;    /* P, 1..7 */
+    uint32_t ssrc, timestamp_base;
+    uint16_t seq_base;
+    uint8_t pid_mode;                /* 0 all, 1 listed, 2 all but listed */
+    uint8_t drop_null;
+} dvbs2gpu_ipout_flow;
+typedef struct dvbs2gpu_ipout_layout {
+    int32_t ipv4_version_ihl, ipv4_tos_at, ipv4_id_at, ipv4_dont_fragment, ipv4_ttl_at, ipv4_checksum_at, ipv6_hop_limit_at, rtp_first_byte;
+    int32_t tick_divisor;            /* 27 MHz ticks per tick of the RTP clock: D = tick_divisor << 24 */
+    int32_t max_packets_per_datagram, held_packets, pid_map_bytes, slots, row_bytes, flow_bytes;
+} dvbs2gpu_ipout_layout;
+int dvbs2gpu_ipout_create(dvbs2gpu_ctx* ctx, int nstreams, int max_packets, dvbs2gpu_ipout** out);
+/* a bank without a device: the library's native host implementation of the same rules, behind dvbs2gpu_ipout_work only */
+int dvbs2gpu_ipout_create_host(int nstreams, int max_packets, dvbs2gpu_ipout** out);
+int dvbs2gpu_ipout_reset(dvbs2gpu_ipout* b);
+void dvbs2gpu_ipout_destroy(dvbs2gpu_ipout* b);
+int dvbs2gpu_ipout_get_layout(dvbs2gpu_ipout_layout* h_out);
+/* slot 0..3; flow->family 0 (or flow NULL) empties the slot; pids[npids] (host, may be NULL with npids 0): the list of pid_mode 1 and 2,
+ * each <= 0x1FFF.  DVBS2GPU_ERR_ARG for another family, P outside 1..7, dscp > 63, a mode or pid_mode out of range or a PID > 0x1FFF;
+ * the slot is unchanged then. */
+int dvbs2gpu_ipout_set_flow(dvbs2gpu_ipout* b, int stream, int slot, const dvbs2gpu_ipout_flow* flow, const uint16_t* pids, int npids);
+/* ticks_per_packet_q24: the quantity of dvbs2gpu_pcr_set_rate (27 MHz ticks per 188-byte packet in Q24.24, < 2^48), 0: not set */
+int dvbs2gpu_ipout_set_rate(dvbs2gpu_ipout* b, int stream, uint64_t ticks_per_packet_q24);
+/* d_ts[i] (DEVICE), nbytes[i] (host): whole 188-byte packets of stream i, at most max_packets (d_ts[i] may be NULL with nbytes[i] 0).
+ * d_out[i*4 + k]: DEVICE buffer of cap bytes, of any alignment, for the datagrams of slot k of stream i (NULL for an empty slot only);
+ * out_bytes[i*4 + k] (host) their bytes; out_rows[i*4 + k] (host, may be NULL) their number.  flush != 0: every slot's held packets
+ * leave (see above).  Two kernel launches.  Synchronous on `stream`; chained behind the call that wrote the TS and in front of
+ * dvbs2gpu_ipts_process_batch on the same stream, no packet visits the host. */
+int dvbs2gpu_ipout_process_batch(dvbs2gpu_ipout* b, const uint8_t* const* d_ts, const int* nbytes, uint8_t* const* d_out, int cap, int* out_bytes,
+                                 int* out_rows, int flush, void* stream);
+/* one stream of any bank with HOST buffers: h_ts[nbytes], h_out[k] of cap bytes (NULL for an empty slot only); out_bytes[4] (may be
+ * NULL): the bytes of each slot.  0 or a negative error.  Every other stream of the bank receives an empty call without flush. */
+int dvbs2gpu_ipout_work(dvbs2gpu_ipout* b, int stream, const uint8_t* h_ts, int nbytes, uint8_t* const* h_out, int cap, int* out_bytes, int flush);
+/* the bytes that the slot's last call needed, whether it succeeded or failed for capacity */
+int dvbs2gpu_ipout_get_needed(dvbs2gpu_ipout* b, int stream, int slot, int* bytes);
+typedef struct dvbs2gpu_ipout_stats {          /* since creation or reset; a slot's since its last set_flow; kept on the host */
+    int64_t packets, bad_sync;       /* the stream's own (0 when a slot >= 0 is asked for) */
+    int64_t passed, datagrams, short_datagrams, ts_packets, bytes_delivered;
+    int64_t held;                    /* now */
+} dvbs2gpu_ipout_stats;
+/* slot 0..3: the slot's counters; slot -1: the stream's own counters and the sum over its slots */
+int dvbs2gpu_ipout_get_stats(dvbs2gpu_ipout* b, int stream, int slot, dvbs2gpu_ipout_stats* h_out);
+#define DVBS2GPU_IPOUT_RTP 1
+#define DVBS2GPU_IPOUT_SHORT 2
+#define DVBS2GPU_IPOUT_CARRIED 4
+typedef struct dvbs2gpu_ipout_row {            /* 24 bytes */
+    int32_t offset;                  /* of the datagram, at its IP header, in the slot's output buffer */
+    int32_t bytes;
+    uint32_t rtp_timestamp;
+    uint16_t rtp_seq;
+    uint8_t packets;
+    uint8_t flags;                   /* DVBS2GPU_IPOUT_* */
+    int32_t first_packet;
+    uint16_t udp_checksum;
+    uint16_t reserved;
+} dvbs2gpu_ipout_row;
+/* h_rows[cap] (host); *n = rows of the slot's last call, of which min(*n, cap) are written */
+int dvbs2gpu_ipout_get_row_table(dvbs2gpu_ipout* b, int stream, int slot, dvbs2gpu_ipout_row* h_rows, int cap, int* n);
+/* the same table in HBM, valid until the bank's next call (device banks only): *d_rows is a DEVICE pointer (NULL when *n == 0) */
+int dvbs2gpu_ipout_get_row_table_device(dvbs2gpu_ipout* b, int stream, int slot, const dvbs2gpu_ipout_row** d_rows, int* n);
+
 #ifdef __cplusplus
 }
 #endif

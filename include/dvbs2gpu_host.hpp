@@ -490,6 +490,7 @@ private:
 struct TsmonApi { typedef dvbs2gpu_tsmon Handle; static constexpr const char* name = "TSMonitor"; static constexpr auto destroy = &dvbs2gpu_tsmon_destroy; };
 struct PsiApi { typedef dvbs2gpu_psi Handle; static constexpr const char* name = "PsiBank"; static constexpr auto destroy = &dvbs2gpu_psi_destroy; };
 struct IptsApi { typedef dvbs2gpu_ipts Handle; static constexpr const char* name = "IpTsBank"; static constexpr auto destroy = &dvbs2gpu_ipts_destroy; };
+struct IpoutApi { typedef dvbs2gpu_ipout Handle; static constexpr const char* name = "IpOutBank"; static constexpr auto destroy = &dvbs2gpu_ipout_destroy; };
 }   // namespace detail
 
 /* TS monitor for one transport stream (dvbs2gpu_tsmon_*, include/dvbs2gpu.h; an extension, the reference has no counterpart): a block
@@ -1029,6 +1030,57 @@ public:
         check(dvbs2gpu_ipts_get_row_table(need(), 0, nullptr, 0, &n));
         std::vector<dvbs2gpu_ipts_row> rows((size_t)n);
         if (n > 0) check(dvbs2gpu_ipts_get_row_table(h, 0, rows.data(), n, &n));
+        return rows;
+    }
+};
+/* IP output bank for one transport stream (dvbs2gpu_ipout_*, include/dvbs2gpu.h; an extension): a block behind TSMonitor's filter or any
+ * TS source; the packets of up to four flows leave as UDP or RTP/MP2T datagrams with complete headers, back to back per flow slot, one
+ * row each -- IpTsBank::view() over rowTable() reads them back.  init() (a device bank) or initHost() (the library's host
+ * implementation, no device) and the setters throw; work() sits in the data path and does NOT throw: a failing call returns false and
+ * leaves its code in status() and its text in error(), sticky until clearStatus(). */
+class IpOutBank : public detail::Bank<detail::IpoutApi> {
+public:
+    void init(int max_packets, int device = 0) {
+        release();
+        eng = Engine::get(device);
+        check(dvbs2gpu_ipout_create(eng->ctx, 1, max_packets, &h));
+    }
+    void initHost(int max_packets) {
+        release();
+        check(dvbs2gpu_ipout_create_host(1, max_packets, &h));
+    }
+    void reset() { check(dvbs2gpu_ipout_reset(need())); }
+    /* slot 0..3; flow.family 0 empties the slot; pids: the list of pid_mode 1 and 2.  The slot's counters, held packets and sequence
+     * start afresh. */
+    void setFlow(int slot, const dvbs2gpu_ipout_flow& flow, const std::vector<uint16_t>& pids = {}) {
+        check(dvbs2gpu_ipout_set_flow(need(), 0, slot, &flow, pids.data(), (int)pids.size()));
+    }
+    /* 27 MHz ticks per packet in Q24.24, the quantity of PCRBank's rate; 0: not set */
+    void setRate(uint64_t ticks_per_packet_q24) { check(dvbs2gpu_ipout_set_rate(need(), 0, ticks_per_packet_q24)); }
+    /* out[k] (buffer_outsize bytes each; nullptr for a slot without a flow) receives the datagrams of slot k, bytes[k] (may be nullptr)
+     * their byte counts; false on failure (see status(); on DVBS2GPU_ERR_CAPACITY needed() has the sizes and nothing was consumed) */
+    bool work(const uint8_t* ts, int nbytes, uint8_t* const out[4], int buffer_outsize, int bytes[4], bool flush = false) noexcept {
+        const int rc = h ? dvbs2gpu_ipout_work(h, 0, ts, nbytes, out, buffer_outsize, bytes, flush ? 1 : 0) : DVBS2GPU_ERR_ARG;
+        return rc >= 0 || fail(rc);
+    }
+    /* the bytes that the slot's last work() needed */
+    int needed(int slot) {
+        int b = 0;
+        check(dvbs2gpu_ipout_get_needed(need(), 0, slot, &b));
+        return b;
+    }
+    /* a slot's counters; -1: the stream's own and the sum over its slots */
+    dvbs2gpu_ipout_stats stats(int slot = -1) {
+        dvbs2gpu_ipout_stats s;
+        check(dvbs2gpu_ipout_get_stats(need(), 0, slot, &s));
+        return s;
+    }
+    /* one row per datagram of the slot's last work(), in output order */
+    std::vector<dvbs2gpu_ipout_row> rowTable(int slot) {
+        int n = 0;
+        check(dvbs2gpu_ipout_get_row_table(need(), 0, slot, nullptr, 0, &n));
+        std::vector<dvbs2gpu_ipout_row> rows((size_t)n);
+        if (n > 0) check(dvbs2gpu_ipout_get_row_table(h, 0, slot, rows.data(), n, &n));
         return rows;
     }
 };

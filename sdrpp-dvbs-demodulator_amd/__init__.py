@@ -318,6 +318,31 @@ class IptsRow(C.Structure):
                 ('packets', C.c_int32), ('lost', C.c_int32), ('offset', C.c_int32), ('bytes', C.c_int32)]
 
 
+class IpoutFlow(C.Structure):
+    """dvbs2gpu_ipout_flow"""
+    _fields_ = [('family', C.c_int32), ('src_addr', C.c_uint8 * 16), ('dst_addr', C.c_uint8 * 16), ('src_port', C.c_uint16), ('dst_port', C.c_uint16),
+                ('ttl', C.c_uint8), ('dscp', C.c_uint8), ('mode', C.c_uint8), ('packets_per_datagram', C.c_uint8), ('ssrc', C.c_uint32),
+                ('timestamp_base', C.c_uint32), ('seq_base', C.c_uint16), ('pid_mode', C.c_uint8), ('drop_null', C.c_uint8)]
+
+
+class IpoutLayout(C.Structure):
+    """dvbs2gpu_ipout_layout"""
+    _fields_ = [(k, C.c_int32) for k in ('ipv4_version_ihl', 'ipv4_tos_at', 'ipv4_id_at', 'ipv4_dont_fragment', 'ipv4_ttl_at', 'ipv4_checksum_at', 'ipv6_hop_limit_at',
+                                         'rtp_first_byte', 'tick_divisor', 'max_packets_per_datagram', 'held_packets', 'pid_map_bytes', 'slots', 'row_bytes',
+                                         'flow_bytes')]
+
+
+class IpoutStats(C.Structure):
+    """dvbs2gpu_ipout_stats"""
+    _fields_ = [(k, C.c_int64) for k in ('packets', 'bad_sync', 'passed', 'datagrams', 'short_datagrams', 'ts_packets', 'bytes_delivered', 'held')]
+
+
+class IpoutRow(C.Structure):
+    """dvbs2gpu_ipout_row"""
+    _fields_ = [('offset', C.c_int32), ('bytes', C.c_int32), ('rtp_timestamp', C.c_uint32), ('rtp_seq', C.c_uint16), ('packets', C.c_uint8), ('flags', C.c_uint8),
+                ('first_packet', C.c_int32), ('udp_checksum', C.c_uint16), ('reserved', C.c_uint16)]
+
+
 class FrameQuality(C.Structure):
     """dvbs2gpu_frame_quality"""
     _fields_ = [('esn0_db', C.c_float), ('mer_db', C.c_float), ('gain', C.c_float), ('phase', C.c_float), ('known_symbols', C.c_int32),
@@ -555,6 +580,19 @@ PROTOTYPES.update({
     'dvbs2gpu_ipts_get_stats': (_i, [_vp, _i, _i, C.POINTER(IptsStats)]),
     'dvbs2gpu_ipts_get_row_table': (_i, [_vp, _i, C.POINTER(IptsRow), _i, C.POINTER(_i)]),
     'dvbs2gpu_ipts_get_row_table_device': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
+    'dvbs2gpu_ipout_create': (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_ipout_create_host': (_i, [_i, _i, C.POINTER(_vp)]),
+    'dvbs2gpu_ipout_reset': (_i, [_vp]),
+    'dvbs2gpu_ipout_destroy': (None, [_vp]),
+    'dvbs2gpu_ipout_get_layout': (_i, [C.POINTER(IpoutLayout)]),
+    'dvbs2gpu_ipout_set_flow': (_i, [_vp, _i, _i, C.POINTER(IpoutFlow), C.POINTER(C.c_uint16), _i]),
+    'dvbs2gpu_ipout_set_rate': (_i, [_vp, _i, C.c_uint64]),
+    'dvbs2gpu_ipout_process_batch': (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _i, _vp]),
+    'dvbs2gpu_ipout_work': (_i, [_vp, _i, _vp, _i, C.POINTER(_vp), _i, C.POINTER(_i), _i]),
+    'dvbs2gpu_ipout_get_needed': (_i, [_vp, _i, _i, C.POINTER(_i)]),
+    'dvbs2gpu_ipout_get_stats': (_i, [_vp, _i, _i, C.POINTER(IpoutStats)]),
+    'dvbs2gpu_ipout_get_row_table': (_i, [_vp, _i, _i, C.POINTER(IpoutRow), _i, C.POINTER(_i)]),
+    'dvbs2gpu_ipout_get_row_table_device': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
 })
 
 _lib = None
@@ -2206,6 +2244,12 @@ class IpTsBank(_TsBank):
         p, n = bank.ma_pdu_table_device(stream, slot)
         return cls._view(out_tensor.data_ptr(), p, n, GsePdu, cls.KIND_GRE), out_tensor
 
+    @classmethod
+    def view_from_ipout(cls, bank, out_tensor, stream=0, slot=0):
+        """(view, out_tensor): the datagrams of (stream, slot) of an IpOutBank's last process() call, which wrote them into out_tensor"""
+        p, n = bank.row_table_device(stream, slot)
+        return cls._view(out_tensor.data_ptr(), p, n, IpoutRow, cls.KIND_RAW_IP), out_tensor
+
     # ---- calls
     def process(self, views, out_tensors=None):
         """views[i]: the IptsView of stream i (None: no row), device pointers; out_tensors: None for rows and counters only, else
@@ -2267,6 +2311,122 @@ class IpTsBank(_TsBank):
         """(device pointer or None, rows): the same table as dvbs2gpu_ipts_row records in HBM, valid until the next call"""
         p, n = C.c_void_p(), C.c_int()
         self._check(self.lib.dvbs2gpu_ipts_get_row_table_device(self.h, int(stream), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+
+class IpOutBank(_TsBank):
+    """IP output bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, IP output bank): the packets of up to four
+    flow slots per stream, selected by PID, leave as UDP or RTP/MP2T datagrams with complete IPv4 / IPv6, UDP and RTP headers and
+    checksums, back to back per slot in a device buffer with one table row each.  It is IpTsBank's direction reversed:
+    IpTsBank.view_from_ipout reads the result back."""
+    _destroy = 'dvbs2gpu_ipout_destroy'
+    SLOTS = 4
+    MODE_RAW, MODE_RTP = 0, 1
+    PASS_ALL, PASS_LISTED, DROP_LISTED = 0, 1, 2
+    RTP, SHORT, CARRIED = 1, 2, 4
+    ROW_KEYS = tuple(k for k, _ in IpoutRow._fields_ if k != 'reserved')
+
+    def __init__(self, engine, nstreams=1, max_packets=4096):
+        self.eng, self.lib, self.nstreams, self.max_packets = engine, engine.lib, nstreams, max_packets
+        h = C.c_void_p()
+        engine._check(self.lib.dvbs2gpu_ipout_create(engine.h, nstreams, max_packets, C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        return cls._host('dvbs2gpu_ipout_create_host', nstreams=nstreams, max_packets=max_packets)
+
+    @staticmethod
+    def layout():
+        """what the library's headers rely on beyond IpTsBank.layout() (dvbs2gpu_ipout_layout) as a dict"""
+        lay = IpoutLayout()
+        load_library().dvbs2gpu_ipout_get_layout(C.byref(lay))
+        return {k: int(getattr(lay, k)) for k, _ in IpoutLayout._fields_}
+
+    def reset(self):
+        self._check(self.lib.dvbs2gpu_ipout_reset(self.h))
+
+    def set_flow(self, stream, slot, family=0, src=None, dst=None, src_port=0, dst_port=0, ttl=64, dscp=0, mode=1, ssrc=0, seq_base=0, timestamp_base=0,
+                 packets_per_datagram=7, pid_mode=0, pids=(), drop_null=False):
+        """family 4 or 6 with source and destination address (4 or 16 bytes, network order); family 0 empties the slot.  pids: the list of
+        pid_mode 1 (pass listed) and 2 (drop listed).  The slot's counters, held packets and RTP sequence start afresh."""
+        f = IpoutFlow()
+        if family:
+            if any(a is None or len(bytes(a)) != (4 if family == 4 else 16) for a in (src, dst)):
+                raise ValueError('an IPv4 address has four bytes, an IPv6 address sixteen')
+            for k, v in (('family', family), ('src_port', src_port), ('dst_port', dst_port), ('ttl', ttl), ('mode', mode), ('ssrc', ssrc), ('seq_base', seq_base),
+                         ('timestamp_base', timestamp_base), ('pid_mode', pid_mode), ('drop_null', bool(drop_null))):
+                setattr(f, k, int(v))
+            # (out of range for their bytes: the library refuses 255)
+            f.dscp, f.packets_per_datagram = min(max(int(dscp), 0), 255), min(max(int(packets_per_datagram), 0), 255)
+            f.src_addr[:len(bytes(src))] = list(bytes(src))
+            f.dst_addr[:len(bytes(dst))] = list(bytes(dst))
+        if any(not 0 <= int(p) <= 0xFFFF for p in pids):
+            raise ValueError('a PID is a 13-bit number')
+        a = (C.c_uint16 * max(len(pids), 1))(*[int(p) for p in pids])
+        self._check(self.lib.dvbs2gpu_ipout_set_flow(self.h, int(stream), int(slot), C.byref(f), a, len(pids)))
+
+    def set_rate(self, stream, ticks_per_packet_q24):
+        """27 MHz ticks per packet in Q24.24 (PcrBank.set_rate's quantity); 0: not set"""
+        self._check(self.lib.dvbs2gpu_ipout_set_rate(self.h, int(stream), int(ticks_per_packet_q24)))
+
+    def process(self, ts_tensors, out_tensors, nbytes=None, flush=False):
+        """ts_tensors[i]: uint8 CUDA, whole 188-byte packets (nbytes[i] of them, default all); out_tensors[i][k]: the uint8 CUDA buffer
+        that receives the datagrams of slot k of stream i (None for an empty slot) -> byte counts [i][k].  Dvbs2GpuError -5 carries
+        .needed ([i][k]) when a buffer is too small (nothing has advanced then)."""
+        n, S = self.nstreams, self.SLOTS
+        pin = (C.c_void_p * n)(*[t.data_ptr() if t is not None and t.numel() else None for t in ts_tensors])
+        cnt = (C.c_int * n)(*[(0 if t is None else int(t.numel())) if nbytes is None else int(nbytes[i]) for i, t in enumerate(ts_tensors)])
+        flat = [t for per in out_tensors for t in (list(per) + [None] * S)[:S]]
+        pout = (C.c_void_p * (n * S))(*[None if t is None else t.data_ptr() for t in flat])
+        cap = min([int(t.numel()) for t in flat if t is not None] or [0])
+        nb, nr = (C.c_int * (n * S))(), (C.c_int * (n * S))()
+        rc = self.lib.dvbs2gpu_ipout_process_batch(self.h, pin, cnt, pout, cap, nb, nr, int(bool(flush)), self.eng._stream())
+        split = lambda a: [list(a[i * S:(i + 1) * S]) for i in range(n)]
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            e.needed = split(nb)
+            raise e
+        return split(nb)
+
+    def work(self, ts, stream=0, cap=None, flush=False):
+        """one stream, host buffers: numpy uint8 packets in -> the datagrams of the four slots (a list of numpy uint8)"""
+        import numpy as np
+        ts = np.ascontiguousarray(ts, np.uint8).reshape(-1)
+        S = self.SLOTS
+        cap = (ts.size // 188 + 7) * (188 + 60) if cap is None else cap
+        outs = [np.zeros(max(cap, 1), np.uint8) for _ in range(S)]
+        pout = (C.c_void_p * S)(*[o.ctypes.data for o in outs])
+        nb = (C.c_int * S)()
+        rc = self.lib.dvbs2gpu_ipout_work(self.h, int(stream), C.c_void_p(ts.ctypes.data) if ts.size else None, ts.size, pout, cap, nb, int(bool(flush)))
+        if rc < 0:
+            e = Dvbs2GpuError(rc, self.lib.dvbs2gpu_last_error().decode())
+            e.needed = list(nb)
+            raise e
+        return [o[:k].copy() for o, k in zip(outs, nb)]
+
+    def needed(self, stream=0, slot=0):
+        """the bytes that the slot's last call needed, whether it succeeded or failed for capacity"""
+        nb = C.c_int()
+        self._check(self.lib.dvbs2gpu_ipout_get_needed(self.h, int(stream), int(slot), C.byref(nb)))
+        return nb.value
+
+    def stats(self, stream=0, slot=-1):
+        """a slot's counters; slot -1: the stream's own counters and the sum over its slots"""
+        st = IpoutStats()
+        self._check(self.lib.dvbs2gpu_ipout_get_stats(self.h, int(stream), int(slot), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in IpoutStats._fields_}
+
+    def row_table(self, stream=0, slot=0):
+        """one dict per datagram of the slot's last call (the fields of dvbs2gpu_ipout_row), in output order"""
+        rows = self._rows(self.lib.dvbs2gpu_ipout_get_row_table, IpoutRow, int(stream), int(slot))
+        return [{k: int(getattr(r, k)) for k in self.ROW_KEYS} for r in rows]
+
+    def row_table_device(self, stream=0, slot=0):
+        """(device pointer or None, rows): the same table as dvbs2gpu_ipout_row records in HBM, valid until the next call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self.lib.dvbs2gpu_ipout_get_row_table_device(self.h, int(stream), int(slot), C.byref(p), C.byref(n)))
         return p.value, n.value
 
 

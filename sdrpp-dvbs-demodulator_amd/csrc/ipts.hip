@@ -18,7 +18,7 @@
 // Two launches per call and one device-to-host copy, of the call record per stream.  The kernels read nothing outside
 // [offset, offset + bytes) of a row: rules 3, 5 and 8 bound every length by the row's byte count before a byte behind it is asked for.
 // Static LDS: 0.4 KB.
-#include "ts_reasm.h"
+#include "ip_wave.h"
 #include "ipts_rules.h"
 
 #include <memory>
@@ -58,28 +58,11 @@ struct IptsWaveSrc {
         for (int k = 32; k > 0; k >>= 1) v += (unsigned)__shfl_xor((int)v, k);
         return v;
     }
-    // even: the sum of the bytes at even places of [at, at + len), odd: at odd places; the words' sum is 256 even + odd.  len < 65536:
-    // even <= 32768 * 255, so the result fits 32 bits, and a lane's share of them all the more
+    // the words' sum of [at, at + len), not folded (ip_wave.h)
     __device__ unsigned wsum(int at, int len) const {
-        const uint8_t* q = p + at;
-        int lead = (int)((16 - (reinterpret_cast<uintptr_t>(q) & 15)) & 15);
-        if (lead > len) lead = len;
-        const int nvec = (len - lead) / 16, tail = lead + 16 * nvec;
-        unsigned a = 0, b = 0;                         // of the 16-byte loads: the bytes at even and at odd ADDRESSES
-        const uint4* qv = reinterpret_cast<const uint4*>(q + lead);
-        for (int i = lane; i < nvec; i += 64) {
-            const uint4 x = qv[i];
-            const unsigned d[4] = {x.x, x.y, x.z, x.w};
-            for (int k = 0; k < 4; ++k) {
-                const unsigned lo = d[k] & 0x00FF00FFu, hi = d[k] >> 8 & 0x00FF00FFu;
-                a += (lo & 0xFFFF) + (lo >> 16); b += (hi & 0xFFFF) + (hi >> 16);
-            }
-        }
-        unsigned even = lead & 1 ? b : a, odd = lead & 1 ? a : b;
-        if (lane < lead) { if (lane & 1) odd += q[lane]; else even += q[lane]; }
-        if (lane < len - tail) { if ((tail + lane) & 1) odd += q[tail + lane]; else even += q[tail + lane]; }
-        for (int k = 32; k > 0; k >>= 1) { even += (unsigned)__shfl_xor((int)even, k); odd += (unsigned)__shfl_xor((int)odd, k); }
-        return (even << 8) + odd;
+        unsigned even = 0, odd = 0;
+        ip_lanes_wsum(p + at, len, lane, 64, &even, &odd);
+        return ip_wave_wsum_reduce(even, odd);
     }
     __device__ bool syncs(int at, int n) const {
         bool ok = true;
@@ -153,17 +136,6 @@ __global__ void __launch_bounds__(IPTS_WG) ipts_scan_kernel(const IptsView* __re
     if (tid < IPTS_NCNT) rec[IPTS_SLOTS + tid] = cnt[tid];
 }
 
-// n bytes from s to d in a wave: where the two agree modulo 16, 16-byte accesses between a byte-wise lead-in and tail
-__device__ inline void ipts_wave_copy(uint8_t* d, const uint8_t* s, int n, int lane) {
-    if ((reinterpret_cast<uintptr_t>(d) ^ reinterpret_cast<uintptr_t>(s)) & 15) { ts_wave_copy(d, TsBytes{s}, n, lane); return; }
-    int lead = (int)((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15);
-    if (lead > n) lead = n;
-    const int nvec = (n - lead) / 16, tail = lead + 16 * nvec;
-    if (lane < lead) d[lane] = s[lane];
-    for (int i = lane; i < nvec; i += 64) reinterpret_cast<uint4*>(d + lead)[i] = reinterpret_cast<const uint4*>(s + lead)[i];
-    if (lane < n - tail) d[tail + lane] = s[tail + lane];
-}
-
 __global__ void __launch_bounds__(IPTS_WG) ipts_commit_kernel(const IptsView* __restrict__ views, uint8_t* const* __restrict__ out, int max_rows, int cap,
                                                               IptsSeq* __restrict__ state, const IptsSeq* __restrict__ newst, const IptsRow* __restrict__ rows_g) {
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -175,7 +147,7 @@ __global__ void __launch_bounds__(IPTS_WG) ipts_commit_kernel(const IptsView* __
         if (!(q.flags & IPTS_TS) || q.offset < 0 || q.bytes <= 0 || q.offset + q.bytes > cap) continue;
         uint8_t* o = out[s * IPTS_SLOTS + q.slot];
         if (!o) continue;
-        ipts_wave_copy(o + q.offset, v.bytes + ipts_row_i32(v, r, v.offset_at) + q.ts_at, q.bytes, lane);
+        ip_lanes_copy(o + q.offset, v.bytes + ipts_row_i32(v, r, v.offset_at) + q.ts_at, q.bytes, lane, 64);
     }
     if (tid < IPTS_SLOTS) state[s * IPTS_SLOTS + tid] = newst[s * IPTS_SLOTS + tid];
 }
