@@ -31,6 +31,10 @@ namespace s2 {
 #define LDPC_SPLIT_SKIP 0           // development switch for counter experiments (results wrong): bit k set = the pseudo-layers of kind k do nothing
 #endif
 
+#ifndef LDPC_SPLIT_SPEC_STATS
+#define LDPC_SPLIT_SPEC_STATS 0      // development aid: prof[512 + 32 * (pseudo-layer % 11) + passes] counts the layers of workgroup 0 by passes taken (tools/ldpc_split_prof.py); prof[900 / 901 / 902]: speculative layers / their attempts / attempts that held, prof[904 / 905]: the chain layers' attempts / attempts that held
+#endif
+
 template <int MAXDEG>
 struct SplitShape {
     // a row has NL = MAXDEG + 2 links; half 0 holds the first HS = ceil(NL / 2), half 1 the rest.  ODD: half 1 has one link less -- its last slot (HS - 1) is a constant
@@ -239,8 +243,9 @@ __device__ __forceinline__ void row_totals(const RowState<MAXDEG>& R, const uint
 }
 
 // output phase: new messages and posteriors of every slot from the row totals (both halves of M0 / M1 equal, sign of the row in bits 15 and 31 of SXs)
-// SKIP: the first SKIP slots, where flagged in `early`, were written ahead (layers with shared links)
-template <int MAXDEG, int SKIP>
+// SKIP: the first SKIP slots, where flagged in `early`, stay unwritten (layers with shared links: a later row owns the bit)
+// WHOLE: an attempt -- the first SKIP slots stay unwritten, all of them, where `early` is not zero: one test for the lot (SKIP even)
+template <int MAXDEG, int SKIP, bool WHOLE = false>
 __device__ __forceinline__ void row_output(const RowState<MAXDEG>& R, const int M0, const int M1, const int SXs, const uint32_t early, uint32_t (&rec_out)[SplitShape<MAXDEG>::REC],
                                            uint32_t* pn0 = nullptr /* [2]: the new posteriors of slots 0 / 1 and 2 / 3: bits 7:0 / 23:16 */, const int npn = 1) {
     using S = SplitShape<MAXDEG>;
@@ -262,6 +267,14 @@ __device__ __forceinline__ void row_output(const RowState<MAXDEG>& R, const int 
         // new posterior: 16-bit saturating add = int8 saturation; >> 8 brings the bytes to bits 7:0 / 23:16 for the stores
         const uint32_t pn = bits2(sat_add2(R.V[p], nm)) >> 8;
         if (p < npn && pn0) pn0[p] = pn;
+        if constexpr (WHOLE) {
+            static_assert(!WHOLE || (SKIP % 2 == 0 && SKIP <= HS), "whole pairs of real slots");
+            if (2 * p < SKIP) {
+                if (!early) { lds_write_lo_i8(R.addr[2 * p], pn); lds_write_hi_i8(R.addr[2 * p + 1], pn); }
+                NM[p] = nm;
+                continue;
+            }
+        }
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
             const int k = 2 * p + hh;
@@ -333,16 +346,17 @@ typedef __attribute__((address_space(3))) u32x2_a4 lds_u2_a4;
 //            the totals with packed operations, handed to half 1, then the output phase -- which leaves out the early slots: a later row's L link owns that bit's final value.
 //   SPECULATION (round 6)  On a frame that has converged no row changes a posterior any more: what a row's late link reads from its bit at the start of the layer IS what
 //            the earlier row will leave there.  A chain layer that finds this -- every slot a later row reads ("early") got back the value it held -- tells the next chain
-//            layer (a flag word behind the records), and that one makes an ATTEMPT: the plain row update with every input taken from its bit, the pair's slots of the rows
-//            of level > 1 held back, the same check; one barrier; where the check held for every row of the workgroup the layer is done after the held-back stores (the
-//            guesses were the values the walk would have carried: induction along the chains) -- no records, no walk, no second output phase: 100 instead of 187 vector
-//            instructions per wave, two barriers instead of three.  Where it did not, the layer goes the long way from the totals on (phase A's stores of the rows of
-//            level 1 stand, everything else is computed again from the inputs in the registers) and the next chain layer does not try.
+//            layer (a flag word behind the records), and that one makes an ATTEMPT: the plain row update of every row with every input taken from its bit and NO store to a
+//            pair slot, and a stricter check that needs no row word: did any row's update change either posterior of its pair?  One barrier.  Where no row did, every
+//            reader of a shared bit read what the sequential order would have given it whichever row ran first (induction along the chains), and the pair slots' new
+//            posteriors are the bytes their bits hold: nothing is owed, the layer is done -- no records, no walk, no second output phase, no held-back stores, and the
+//            vote is the verdict.  Where some row did, the pair's bits are untouched and the layer goes the long way from the totals on: the rows of level 1 finish as they
+//            do without an attempt (their inputs were no guesses), everything else is computed again from the inputs in the registers, and the next chain layer does not try.
 template <int MAXDEG>
 __device__ __forceinline__ void chain_layer(RowState<MAXDEG>& R, uint32_t (&rec_out)[SplitShape<MAXDEG>::REC],
                                             const LdpcSplitLayer L, const uint32_t eL, const int t, int8_t* __restrict__ post, uint32_t* __restrict__ cw,
                                             const uint32_t flagb /* LDS address of the two verdict words */, const uint32_t cseq /* chain layers of this frame so far, this one included */,
-                                            const bool fail_attempts /* tests: every attempt is made to fail */) {
+                                            const bool fail_attempts /* tests: every attempt is made to fail */, [[maybe_unused]] unsigned long long* prof) {
     [[maybe_unused]] constexpr int KIND = 1;
     typedef __attribute__((address_space(3))) uint32_t lds_u1;
     const uint32_t rw = R.rw;
@@ -359,27 +373,39 @@ __device__ __forceinline__ void chain_layer(RowState<MAXDEG>& R, uint32_t (&rec_
     int M0, M1, SXs;
     uint32_t x0, pn0 = 0;
     SPLIT_MARK_DECL;
-    row_input<MAXDEG, -1, SplitShape<MAXDEG>::NOPREV_SHARED>(R, (!attempt && level > 1u && !half1) ? 1u : 0u, 1u /* rows in lane order: row 0's half 1 */, t, M0, M1, SXs, ((L.kind_nw >> 20) & 1u) != 0, &x0);
-    SPLIT_MARK(0);
+    const bool noprev = ((L.kind_nw >> 20) & 1u) != 0;
     if (attempt) {
-        row_output<MAXDEG, 2>(R, M0, M1, SXs, (level > 1u && !half1) ? 3u : 0u, rec_out, &pn0);
-        const bool bad = fail_attempts || ((pn0 ^ (x0 >> 8)) & emask) != 0;
-        if (__builtin_amdgcn_ballot_w64(bad) != 0 && (t & 63) == 0) *(lds_u1*)(uintptr_t)my_flag = cseq;
+        // the plain row update of EVERY row (an input phase of its own: nothing of the row word in it), the pair left unwritten; the question is not the row word's
+        // either: did any row change a posterior of its pair?  `mine`: half 0 of a row -- rows in lane order, 360 of them (half 1's slots 0 / 1 are ordinary links; an
+        // idle lane reads and writes scratch bytes it shares with others: its pair goes there like the rest)
+        const bool mine = __builtin_amdgcn_alignbit((uint32_t)t, (uint32_t)t, 1) < 360u;
+        row_input<MAXDEG, 0, SplitShape<MAXDEG>::NOPREV_SHARED>(R, 0u, 1u /* rows in lane order: row 0's half 1 */, t, M0, M1, SXs, noprev, &x0);
+        SPLIT_MARK(0);
+        row_output<MAXDEG, 2, true>(R, M0, M1, SXs, mine ? 1u : 0u, rec_out, &pn0);
+        // (two ballots joined as masks: each is its compare's result as it stands, the ballot of a joined condition is built again from a select)
+        const uint64_t bad = __builtin_amdgcn_ballot_w64(mine) & __builtin_amdgcn_ballot_w64(((pn0 ^ (x0 >> 8)) & 0x00ff00ffu) != 0);
+        if (bad != 0 || fail_attempts) *(lds_u1*)(uintptr_t)my_flag = cseq;      // (every lane of the wave: the same word, the same value)
         lds_pairs_wait();
         lds_barrier();
+        // no row did: every pair slot's new posterior is the byte its bit holds, every row read what the rows before it leave -- nothing is owed, and the vote is the
+        // verdict for the next layer
+#if LDPC_SPLIT_SPEC_STATS
+        if (prof && blockIdx.x == 0 && t == 0) prof[904] += 1;
+#endif
         if ((uint32_t)__builtin_amdgcn_readfirstlane((int)*(const lds_u1*)(uintptr_t)my_flag) != cseq) {
-            // every guess was right: the held-back stores (a slot a later row touches stays that row's), and the layer is done
-            if (level > 1u && !half1) {
-                if (!(early & 1u)) lds_write_lo_i8(R.addr[0], pn0);
-                if (!(early & 2u)) lds_write_hi_i8(R.addr[1], pn0);
-            }
+#if LDPC_SPLIT_SPEC_STATS
+            if (prof && blockIdx.x == 0 && t == 0) prof[905] += 1;
+#endif
             return;
         }
-        // the long way: the totals again, without the pair where the row has late links (the rows of level 1 are done: their inputs were no guesses)
+        // the long way: the pair's bits are as the layer found them; the totals again, without the pair where the row has late links.  The rows of level 1 -- their inputs
+        // were no guesses -- still owe their pair: they finish below as they do without an attempt
         row_totals<MAXDEG, -1>(R, (level > 1u && !half1) ? 1u : 0u, M0, M1, SXs);
-    } else if (level == 1u) {
-        row_output<MAXDEG, 0>(R, M0, M1, SXs, 0u, rec_out, &pn0);
+    } else {
+        row_input<MAXDEG, -1, SplitShape<MAXDEG>::NOPREV_SHARED>(R, (level > 1u && !half1) ? 1u : 0u, 1u, t, M0, M1, SXs, noprev, &x0);
+        SPLIT_MARK(0);
     }
+    if (level == 1u) row_output<MAXDEG, 0>(R, M0, M1, SXs, 0u, rec_out, &pn0);
     if ((late >> 1) & 1) {
         // totals without the pair: min0 = the smallest magnitude among the row's other links (what the E link's new message takes), sign = their product
         reinterpret_cast<uint2*>(cw)[j] = chain_record_x(R.msg(1), (late & 1u) ? 255 : (M0 >> 24), (int)R.V[0][0] >> 8, SXs >> 31);
@@ -485,9 +511,6 @@ __device__ __forceinline__ LdpcSplitLayer layer_at(const_layer_ptr layers, int i
 //            (a changed input reaches the next row's output only through the min, which mostly ignores it).  Reads race with the same pass's writes: a newer value is as good.
 //   phase C  rows of level > 1: the four inputs of the last pass join the totals, then the output phase; a slot a LATER row touches stays unwritten (that row owns the bit).
 // Bit-exact by construction; the time depends on the data (passes), the result does not.
-#ifndef LDPC_SPLIT_SPEC_STATS
-#define LDPC_SPLIT_SPEC_STATS 0      // development aid: prof[512 + 32 * (pseudo-layer % 11) + passes] counts the layers of workgroup 0 by passes taken (tools/ldpc_split_prof.py)
-#endif
 template <int MAXDEG>
 __device__ __forceinline__ void spec_layer(RowState<MAXDEG>& R, uint32_t (&rec_out)[SplitShape<MAXDEG>::REC], const LdpcSplitLayer L, const uint32_t* __restrict__ tab, const int t,
                                            uint32_t* __restrict__ cw, [[maybe_unused]] unsigned long long* prof, [[maybe_unused]] const int pl,
@@ -502,60 +525,52 @@ __device__ __forceinline__ void spec_layer(RowState<MAXDEG>& R, uint32_t (&rec_o
     const int depth = (int)(L.aux >> 16);
     // the row's side entry {f0 | f1 << 16, f2 | f3 << 16}: f & 0x7ff = distance from the row's own cell back to slot's source cell (0: the bit itself), bit 15: a later row touches the slot
     // (fetched behind the compiler's back and claimed by hand behind the first pass: a load the compiler sees inside ONE kind's branch makes it open the claims of the layer
-    // loop -- every kind's -- with vmcnt(0), which also waits for the previous pseudo-layer's record store: +10 % on the whole kernel when tried)
+    // loop -- every kind's -- with vmcnt(0), which also waits for the previous pseudo-layer's record store: +10 % on the whole kernel when tried.  Asked for where the way
+    // through the passes begins, behind the attempt: an attempt that holds needs no side entry, and a value fetched this way must have ONE place where it is asked for
+    // and ONE where it is claimed -- with two, the compiler moved the registers between them while the load was still on its way)
     u32x2 side;
-    {
-        const uint64_t sbase = (uint64_t)(uintptr_t)(tab + L.ent_off);
-        const uint32_t voff = (uint32_t)j * 8u;
-        asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(side) : "v"(voff), "s"(sbase) : "memory");
-    }
     uint32_t cwb = lds_offset(reinterpret_cast<const int8_t*>(cw));
     asm volatile("" : "+s"(cwb));
     const uint32_t flagb = cwb + 4u * 384u;            // two words behind the cells: flag[p & 1] = p + 1 where a row read something new in pass p
     if (t == 0) { *(lds_u1*)(uintptr_t)flagb = 0u; *(lds_u1*)(uintptr_t)(flagb + 4u) = 0u; }
     // the verdict words the layers with shared bits hand on (chain_layer): where the layer before changed no posterior a later row reads, this one first tries the plain row
-    // update -- every input from its bit, slots 0..3 of the rows of level > 1 held back, one barrier, done if every such posterior got its value back -- and only else the passes
+    // update -- every input from its bit, slots 0..3 of half 0 left unwritten in every row, one barrier, done if no row changed a posterior of those slots (then nothing is
+    // owed to them: chain_layer) -- and only else the passes
     const uint32_t my_flag = vflagb + 4u * (cseq & 1u);
     const bool attempt = (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const lds_u1*)(uintptr_t)(vflagb + 4u * ((cseq - 1u) & 1u))) != cseq - 1u;
-    // (a copy of the side entry of its own for the attempt: a value fetched behind the compiler's back must have ONE place where it is claimed -- with two, the compiler
-    //  moved the registers between them while the load was still on its way)
-    u32x2 side_a = {0u, 0u};
-    if (attempt) {
-        const uint64_t sbase = (uint64_t)(uintptr_t)(tab + L.ent_off);
-        const uint32_t voff = (uint32_t)j * 8u;
-        asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(side_a) : "v"(voff), "s"(sbase) : "memory");
-    }
     int M0, M1, SXs;
     uint32_t xr[2], pn[2] = {0u, 0u};
-    row_input<MAXDEG, -2, SplitShape<MAXDEG>::NOPREV_SHARED>(R, (!attempt && spec) ? 1u : 0u, 1u, t, M0, M1, SXs, ((L.kind_nw >> 20) & 1u) != 0, xr, 2);
+    const bool noprev = ((L.kind_nw >> 20) & 1u) != 0;
     uint32_t em0 = 0, em1 = 0;                         // the bytes of slots 0..3 a later row reads (known once the side entry is in)
 #if LDPC_SPLIT_SPEC_STATS
     if (prof && blockIdx.x == 0 && t == 0) { prof[900] += 1; prof[901] += attempt; prof[910 + (cseq < 40 ? cseq : 40)] += attempt; }
 #endif
     if (attempt) {
-        row_output<MAXDEG, 4>(R, M0, M1, SXs, spec ? 15u : 0u, rec_out, pn, 2);
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(side_a) : : "memory");
-        em0 = (((side_a.x >> 15) & 1u) ? 0xffu : 0u) | (((side_a.x >> 31) & 1u) ? 0xff0000u : 0u);
-        em1 = (((side_a.y >> 15) & 1u) ? 0xffu : 0u) | (((side_a.y >> 31) & 1u) ? 0xff0000u : 0u);
-        const bool bad = fail_attempts || (!half1 && ((((pn[0] ^ (xr[0] >> 8)) & em0) | ((pn[1] ^ (xr[1] >> 8)) & em1)) != 0));
-        if (__builtin_amdgcn_ballot_w64(bad) != 0 && (t & 63) == 0) *(lds_u1*)(uintptr_t)my_flag = cseq;
+        // (chain_layer: an input phase of its own, `mine` = half 0 of a row -- half 1's slots 0..3 are ordinary links, an idle lane works on scratch bytes it shares with others)
+        const bool mine = __builtin_amdgcn_alignbit((uint32_t)t, (uint32_t)t, 1) < 360u;
+        row_input<MAXDEG, 0, SplitShape<MAXDEG>::NOPREV_SHARED>(R, 0u, 1u, t, M0, M1, SXs, noprev, xr, 2);
+        row_output<MAXDEG, 4, true>(R, M0, M1, SXs, mine ? 1u : 0u, rec_out, pn, 2);
+        const uint64_t bad = __builtin_amdgcn_ballot_w64(mine) & __builtin_amdgcn_ballot_w64((((pn[0] ^ (xr[0] >> 8)) | (pn[1] ^ (xr[1] >> 8))) & 0x00ff00ffu) != 0);
+        if (bad != 0 || fail_attempts) *(lds_u1*)(uintptr_t)my_flag = cseq;      // (every lane of the wave: the same word, the same value)
         lds_pairs_wait();
         lds_barrier();
         if ((uint32_t)__builtin_amdgcn_readfirstlane((int)*(const lds_u1*)(uintptr_t)my_flag) != cseq) {
 #if LDPC_SPLIT_SPEC_STATS
             if (prof && blockIdx.x == 0 && t == 0) prof[902] += 1;
 #endif
-            if (spec) {
-                if (!(em0 & 0xffu)) lds_write_lo_i8(R.addr[0], pn[0]);
-                if (!(em0 >> 16)) lds_write_hi_i8(R.addr[1], pn[0]);
-                if (!(em1 & 0xffu)) lds_write_lo_i8(R.addr[2], pn[1]);
-                if (!(em1 >> 16)) lds_write_hi_i8(R.addr[3], pn[1]);
-            }
             return;
         }
-        row_totals<MAXDEG, -2>(R, spec ? 1u : 0u, M0, M1, SXs);          // the long way: the totals without slots 0..3 where the row has predecessors
+        // the long way: the bits of slots 0..3 are as the layer found them; the totals without those slots where the row has predecessors -- the rows of level 1 still owe
+        // theirs and finish below as they do without an attempt
+        row_totals<MAXDEG, -2>(R, spec ? 1u : 0u, M0, M1, SXs);
     } else {
-        if (level == 1u) row_output<MAXDEG, 0>(R, M0, M1, SXs, 0u, rec_out, pn, 2);
+        row_input<MAXDEG, -2, SplitShape<MAXDEG>::NOPREV_SHARED>(R, spec ? 1u : 0u, 1u, t, M0, M1, SXs, noprev, xr, 2);
+    }
+    if (level == 1u) row_output<MAXDEG, 0>(R, M0, M1, SXs, 0u, rec_out, pn, 2);
+    {
+        const uint64_t sbase = (uint64_t)(uintptr_t)(tab + L.ent_off);
+        const uint32_t voff = (uint32_t)j * 8u;
+        asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(side) : "v"(voff), "s"(sbase) : "memory");
     }
     const uint32_t cell = cwb + 4u * (uint32_t)j;
     // (the FIRST pass reads every slot from its bit -- the guess: what the previous layer left there; the later ones from the sources)
@@ -792,7 +807,7 @@ __global__ __launch_bounds__(LDPC_SPLIT_T) __attribute__((amdgpu_waves_per_eu(8)
                     row_output<MAXDEG, 0>(RS, M0, M1, SXs, 0u, ro);
                 } else if (kind == 1) {
                     ++cseq;
-                    chain_layer<MAXDEG>(RS, ro, L, ents[L.ent_off + 1], thread_index(), post, cw, cflagb, cseq, A.dbg != 0);
+                    chain_layer<MAXDEG>(RS, ro, L, ents[L.ent_off + 1], thread_index(), post, cw, cflagb, cseq, A.dbg != 0, A.prof);
                 } else {
                     ++cseq;
                     // (a half of fewer than four slots has no speculative layers: the plan refuses them, ldpc_split_plan.h)
