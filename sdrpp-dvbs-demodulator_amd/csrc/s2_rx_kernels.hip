@@ -96,9 +96,7 @@ __device__ __forceinline__ cf32 dot8(const cf32* x, const float* t) {
 // ------------------------------------------------------------------------------------------------ front end
 // sin/cos on the serial per-sample paths: the shared straight-line definition (~35 instructions for both values, no slow-path
 // branches).  The hardware's v_sin_f32 / v_cos_f32 would be 3 instructions (DVB-S bank +18 %, S2 headline +1.5 % when tried), but
-// their ~1e-6 absolute error has no CPU restatement, and parity with the oracle is the gate: every loop uses the shared definition.
-__device__ __forceinline__ cf32 phasor_fast(float x) { return phasor(x); }
-__device__ __forceinline__ cf32 phasor_hw(float x) { return phasor(x); }
+// their ~1e-6 absolute error has no CPU restatement, and parity with the oracle is the gate: every loop uses the shared definition (phasor).
 
 // The front end is split along its dependency structure:
 //   agc_pc_kernel      LANE = STREAM.  The AGC gain and NCO phase recurrences depend only on the input, are strictly serial in
@@ -413,7 +411,7 @@ __global__ __launch_bounds__(64 * 2 * G2_PAIRS) void s2_gardner2_kernel(const S2
             for (int q = 0; q < G2_SPT; ++q) {
                 const int sj = sj0 + SSTEP * q, idx = t * G2_TILE + si;
                 if (idx < s_n[sj]) {
-                    const cf32 z = cmul(cscale(px[q], pg[q].re), phasor_fast(-pg[q].im));   // FastAGC scaling, FreqShift rotation
+                    const cf32 z = cmul(cscale(px[q], pg[q].re), phasor(-pg[q].im));   // FastAGC scaling, FreqShift rotation
                     const int slot = (idx + GARDNER_TAPS - 1) & (G2_RING - 1);
                     float* rr = &ring[(sj * 2) * G2_PITCH + slot];
                     rr[0] = z.re; rr[G2_PITCH] = z.im;
@@ -770,7 +768,7 @@ __global__ __launch_bounds__(192) void s2_gardner_cand_kernel(const S2StreamWork
         auto commit = [&](int t) {
             const int idx = t * GC_T + smp;
             if (idx < q_n) {
-                const cf32 z = cmul(cscale(px, pg.re), phasor_fast(-pg.im));   // FastAGC scaling, FreqShift rotation
+                const cf32 z = cmul(cscale(px, pg.re), phasor(-pg.im));   // FastAGC scaling, FreqShift rotation
                 const int slot = (idx + GARDNER_TAPS - 1) & (GC_RING - 1);
                 f32x2* rr = &ring[sj * GC_PITCH + slot];
                 rr[0] = f32x2{z.re, z.im};
@@ -1232,6 +1230,8 @@ __device__ __attribute__((noinline)) float soft_phase_err_group(lds_cf32* __rest
 #ifndef S2_PLL_TILES
 #define S2_PLL_TILES 1   // one stream per workgroup: a payload tile of the PLL as a fixed point of (parallel phase-error evaluation, serial replay) instead of the serial loop (A/B switch)
 #endif
+// (where the switch is asked: a LUT constellation's payload tile -- s2_frame_loops_kernel with one stream per workgroup, s2_vcm_loops_kernel always)
+__device__ __forceinline__ bool pll_tile_form(int cbits) { return S2_PLL_TILES && cbits != 5; }
 #ifndef S2_PLL_ASM
 #define S2_PLL_ASM 1     // the PLL's payload-tile loop of s2_frame_loops_kernel written out (A/B switch)
 #endif
@@ -1267,7 +1267,7 @@ __device__ __forceinline__ cf32 pll_payload_tile(const cf32 sym, const bool mine
     for (;;) {
         bool changed = false;
         if (mine_k) {
-            tmp_val = cmul(sym, phasor_fast(-myph));
+            tmp_val = cmul(sym, phasor(-myph));
             const int cell = lut_cell(tmp_val.re, tmp_val.im);
             changed = cell != mycell;
             mycell = cell;
@@ -1351,6 +1351,149 @@ __device__ __forceinline__ cf32 pll_payload_tile(const cf32 sym, const bool mine
     return tmp_val;
 }
 
+// THE FRAME RULES, each stated once for s2_frame_loops_kernel (GSZ = FL_LPS lanes per stream, FL_SYNC) and s2_vcm_loops_kernel (GSZ = 64, __syncthreads),
+// as the oracle states them once for both paths (S2Rx::coarse_fed / pll / plhdr) -- the general PLL step excepted, see pll_symbol.  The serial parts run uniformly in the GSZ lanes of a stream's group; lane `gl`
+// of the group takes every GSZ-th element of the parallel parts.
+//
+// Coarse frequency error detector (dvbs2_fed.h): 88 header terms plus 34 per pilot block, the terms in parallel, summed in the reference's order.
+// fr: the frame, blk: room for a 36-symbol pilot block, terms: room for 88 floats; the caller has synchronised in front.  Returns the estimate.
+template <int GSZ, class Sync>
+__device__ __forceinline__ float coarse_fed(const cf32* __restrict__ fr, const cf32* __restrict__ plsc, const S2PlTablesDev& T, int pilots, int pilot_blocks,
+                                            cf32* blk, float* terms, int gl, Sync sync) {
+    #pragma unroll 1
+    for (int i = gl; i < 88; i += GSZ) {
+        cf32 r2 = (i + 2) < 26 ? T.sof[i + 2] : plsc[i + 2 - 26];
+        cf32 r0 = i < 26 ? T.sof[i] : plsc[i - 26];
+        terms[i] = cmul(cmul(cmul(fr[i + 2], cconj(r2)), cconj(fr[i])), r0).im;
+    }
+    sync();
+    float err = 0.f, symcnt = 90 - 2;
+    for (int i = 0; i < 88; ++i) err += terms[i];
+    if (pilots) {
+        const cf32 p{0.707f, 0.707f};
+        for (int b = 0; b < pilot_blocks; ++b) {
+            int start = pilot_start(b);
+            sync();
+            for (int i = gl; i < 36; i += GSZ) blk[i] = pl_descramble(fr[start + i], T.rn[start - 90 + i]);
+            sync();
+            for (int i = gl; i < 36; i += GSZ)
+                if (i >= 2) terms[i] = cmul(cmul(cmul(blk[i], cconj(p)), cconj(blk[i - 2])), p).im;
+            sync();
+            for (int i = 2; i < 36; ++i) err += terms[i];
+            symcnt += 36 - 2;
+        }
+    }
+    return err / symcnt;
+}
+// ... and its feedback into the NCO (dvbs2_fed.h): a hundredth of the loop bandwidth once the estimate is small, the frequency kept within +-0.3 pi
+__device__ __forceinline__ float nco_feedback(float nco_freq, float est, float fll_bw) {
+    const float PI_F = 3.14159265358979323846f;
+    if (fabsf(est) < 0.02) nco_freq = nco_freq + est * (fll_bw / 100.0f);
+    else nco_freq = nco_freq + est * fll_bw;
+    if (nco_freq > 0.3f * PI_F) nco_freq = 0.3f * PI_F;
+    if (nco_freq < -0.3f * PI_F) nco_freq = -0.3f * PI_F;
+    return nco_freq;
+}
+
+// Where the PLL stands among the frame's pilot blocks: the start of the block at or ahead of the current symbol (-1: none left), its number, and the
+// sum over the known symbols of the running block (pilot-aided mode)
+struct PilotWalk {
+    int next_pilot, pb;
+    cf32 pacc;
+    // no header symbol and no pilot symbol among the symbols base .. base + m - 1
+    __device__ __forceinline__ bool payload_only(int base, int m) const { return base >= 90 && !(next_pilot >= 0 && next_pilot < base + m && next_pilot + 36 > base); }
+};
+// One symbol of the PLL (dvbs2_pll.cpp:34-86): symbol i of the frame (`rn` its Gold-sequence value) is rotated by the loop phase; a header symbol gives the
+// data-aided error against SOF / PLSC, a pilot symbol the reference's sign-sliced error or (pilot_aided) the data-aided one, a payload symbol the
+// decision-directed error of its constellation (table, or the 32APSK search shared by the group's lanes: pts, states, amp, prescale); the loop advances.
+// Returns the output symbol: descrambled, zero for a header symbol (those come from the PLHDR demod).
+// s2_vcm_loops_kernel's step.  s2_frame_loops_kernel keeps the SAME text written out in its tile loop, and a change here has to be made there too: through this
+// function -- the symbol by value or the tile pointers and k, the store outside or inside -- its 32APSK + pilots frame loops took 0.2 .. 0.5 ms of 53.6 longer
+// (profiles/s2_frame_rules_isa.txt).
+template <int GSZ>
+__device__ __forceinline__ cf32 pll_symbol(PclDev& pll, PilotWalk& w, cf32 sym, int i, int rn, const S2LoopCoefs& co, const S2PlTablesDev& T,
+                                           const cf32* __restrict__ plsc, int pilot_blocks, int cbits, const float* lut_err, lds_cf32* pts, int states,
+                                           float amp, float prescale, int gl) {
+    cf32 tmp_val = cmul(sym, phasor(-pll.phase));
+    float error = 0.f;
+    cf32 o;
+    bool block_end = false;
+    if (i >= 90) {
+        cf32 descr = pl_descramble(tmp_val, rn);
+        bool is_pilot = w.next_pilot >= 0 && i >= w.next_pilot && i < w.next_pilot + 36;
+        if (!is_pilot) {
+            if (cbits != 5) error = as_global(lut_err)[lut_cell(tmp_val.re, tmp_val.im)];
+            else error = soft_phase_err_group<GSZ>(pts, states, amp, prescale, tmp_val, gl);
+        } else {
+            if (co.pilot_aided) {
+                // own extension: data-aided on the known (1+j)/sqrt2 pilot, and the block estimate below
+                const cf32 pr = cmul(descr, cf32{0.707f, -0.707f});
+                error = cphase(pr);
+                w.pacc = cadd(w.pacc, pr);
+            } else {
+                // the reference's pilot error: decision-directed on the sign-sliced QPSK point, a tenth of the gain (dvbs2_pll.cpp:58)
+                const cf32 pt{descr.re > 0 ? 0.707f : -0.707f, descr.im > 0 ? 0.707f : -0.707f};
+                error = cphase(cmul(descr, cconj(pt))) / 10.0f;
+            }
+            if (i == w.next_pilot + 35) { ++w.pb; w.next_pilot = w.pb < pilot_blocks ? pilot_start(w.pb) : -1; block_end = true; }
+        }
+        o = descr;
+    } else {
+        const cf32 pr = cmul(tmp_val, cconj(i < 26 ? T.sof[i] : plsc[i - 26]));
+        error = cphase(pr);
+        if (co.pilot_aided) w.pacc = cadd(w.pacc, pr);
+        block_end = i == 89;
+        o = cf32{0.f, 0.f};
+    }
+    pll.advance(error);
+    pll.wrap_pi_once();
+    if (co.pilot_aided && block_end) {
+        // pilot-aided mode (include/dvbs2gpu.h): the block estimate of the residual phase over the known symbols moves the loop phase
+        if (w.pacc.re != 0.f || w.pacc.im != 0.f) {
+            pll.phase += cphase(w.pacc);
+            pll.advance(0.f);
+            pll.wrap_pi();
+        }
+        w.pacc = cf32{0.f, 0.f};
+    }
+    return o;
+}
+
+// PL header demod (dvbs2_plhdr_demod.cpp:33-67): its own loop over the 90 header symbols `hs`, then the jump over the rest of the frame.  emit(i, o) gets
+// header symbol i as demodulated; soft (or nullptr): the soft value (sign = bit) of PLSC symbol p goes to soft[p].re -- `hs` itself will do, slot p = i - 26 < i
+// has been consumed by then.  Returns the 64 hard PLSC bits, first bit highest.
+// (emit comes BEFORE the soft value, as the reference stores before it decides: with the soft value handed to emit s2_frame_loops_kernel came out with the head of
+// its written-out payload loop 24 bytes into a 32-byte fetch window, and the headline's frame loops 0.5 % slower -- profiles/s2_frame_rules_isa.txt.)
+template <class Emit>
+__device__ __forceinline__ unsigned long long plhdr_loop(PclDev& hdr, const cf32* hs, int plframe, cf32* soft, Emit emit) {
+    unsigned long long plheader = 0;
+    const cf32 rot{(float)0.70710678118654757, (float)-0.70710678118654746};   // (cos(-pi/4), sin(-pi/4)) in double, cast
+    for (int i = 0; i < 90; ++i) {
+        cf32 tmp_val = cmul(hs[i], phasor(-hdr.phase));
+        float error = ((tmp_val.re > 0 ? 1.0f : -1.0f) * tmp_val.im) - ((tmp_val.im > 0 ? 1.0f : -1.0f) * tmp_val.re);
+        cf32 o = (i & 1) ? cf32{-tmp_val.re, tmp_val.im} : cf32{tmp_val.im, tmp_val.re};
+        emit(i, o);
+        if (i >= 26) {
+            const float sv = cmul(o, rot).re;
+            plheader = plheader << 1 | (unsigned long long)(!(sv > 0));
+            if (soft) soft[i - 26].re = sv;
+        }
+        hdr.advance(error);
+        hdr.wrap_pi_once();
+    }
+    hdr.phase += hdr.freq * (plframe - 91);
+    hdr.advance(0.f);
+    hdr.wrap_pi();
+    return plheader;
+}
+// Soft PLS decode (include/dvbs2gpu.h), the metric of one codeword: sum_p +-soft[p] over all 64 code bits in index order (soft value p at soft[p * STRIDE])
+template <int STRIDE>
+__device__ __forceinline__ float plsc_soft_metric(unsigned long long code, const float* soft) {
+    float mtr = 0.f;
+    for (int p = 0; p < 64; ++p) { const float sv = soft[p * STRIDE]; mtr += ((code >> (63 - p)) & 1ull) ? -sv : sv; }
+    return mtr;
+}
+
 // SPEC: with the loops ahead of the PL sync (below) compiled in -- small banks only: the plain instantiation has to stay within 128 registers
 // (it shares its SIMDs with three decoder waves in the pipelined mode), and the extra state costs it 14
 // one wave per workgroup, whatever the bank (round 6, same call: a big bank in two-wave workgroups -> decoder in the step 247.8 -> 245.8 ms but frame loops 108-115 -> 123-132
@@ -1395,7 +1538,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     PclDev pll{co.pll_alpha, co.pll_beta, st->pll_phase, st->pll_freq, co.pll_min_freq, co.pll_max_freq};
     PclDev hdr{co.hdr_alpha, co.hdr_beta, st->hdr_phase, st->hdr_freq, co.hdr_min_freq, co.hdr_max_freq};
     float nco_freq = st->nco_freq;
-    const float PI_F = 3.14159265358979323846f;
     const cf32* __restrict__ plsc = T.plsc + (size_t)pls_code * 64;
     const int done = found ? st->loops_done : 0;
     const int f0 = found ? sc * maxf + done : first[sc], nf = !act ? 0 : (found ? st->walk_nf - done : first[sc + 1] - f0);
@@ -1471,12 +1613,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         }
         // ---- PLL (dvbs2_pll.cpp:34-86), 64-symbol tiles
         const int b0 = t0 * FL_TILE, b1 = fin ? plframe : t1 * FL_TILE;
-        int next_pilot = -1, pb = 0;
+        PilotWalk pw{-1, 0, cf32{0.f, 0.f}};
         if (pilots && pilot_blocks > 0) {                   // (the pilot block at or ahead of the first symbol: a pass may start inside the frame)
-            while (pb < pilot_blocks && pilot_start(pb) + 36 <= b0) ++pb;
-            next_pilot = pb < pilot_blocks ? pilot_start(pb) : -1;
+            while (pw.pb < pilot_blocks && pilot_start(pw.pb) + 36 <= b0) ++pw.pb;
+            pw.next_pilot = pw.pb < pilot_blocks ? pilot_start(pw.pb) : -1;
         }
-        cf32 pacc{0.f, 0.f};
         // the next tile's symbols and Gold-sequence values are fetched into registers while the serial loop runs on the current one
         constexpr int NPF = (FL_TILE + FL_LPS - 1) / FL_LPS;
         cf32 pf[NPF];
@@ -1505,9 +1646,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             // A tile of payload symbols only (no header, no pilot symbol: all but a handful of the frame's tiles) takes the short loop: rotate, phase
             // error, advance -- the Gold-sequence rotation of the OUTPUT (descrambling acts on the rotated symbol and feeds nothing back into
             // the loop) is left to the lanes that copy the tile out.  Everything else goes through the general loop below.
-            const bool plain = base >= 90 && !(next_pilot >= 0 && next_pilot < base + m && next_pilot + 36 > base);
+            const bool plain = pw.payload_only(base, m);
             if (plain) {
-                if (S2_PLL_TILES && C.bits != 5 && spw == 1) {
+                if (pll_tile_form(C.bits) && spw == 1) {
                     // one stream per workgroup: the tile as a fixed point over all 64 lanes (pll_payload_tile above)
                     const bool mine_k = lane < m;
                     const cf32 tmp_val = pll_payload_tile(mine_k ? tiles[0][lane] : cf32{0.f, 0.f}, mine_k, lane, m, pll, lut_err_v);
@@ -1623,7 +1764,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                               "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "vcc", "scc", "memory");
                         k = m - (int)left;
                         if (!why) break;
-                        const cf32 tmp_val = cmul(tl[k], phasor_fast(-pll.phase));           // (a cell index that needs the double form)
+                        const cf32 tmp_val = cmul(tl[k], phasor(-pll.phase));           // (a cell index that needs the double form)
                         const float error = as_global(lut_err_v)[lut_cell(tmp_val.re, tmp_val.im)];
                         ot[k] = tmp_val;
                         pll.advance(error);
@@ -1632,7 +1773,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     }
 #else
                     for (int k = 0; k < m; ++k) {
-                        const cf32 tmp_val = cmul(tl[k], phasor_fast(-pll.phase));
+                        const cf32 tmp_val = cmul(tl[k], phasor(-pll.phase));
                         const float error = as_global(lut_err_v)[lut_cell(tmp_val.re, tmp_val.im)];
                         ot[k] = tmp_val;                     // (every lane of the group holds the same value: no predicate in the chain)
                         pll.advance(error);
@@ -1641,7 +1782,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #endif
                 } else {
                     for (int k = 0; k < m; ++k) {
-                        const cf32 tmp_val = cmul(tl[k], phasor_fast(-pll.phase));
+                        const cf32 tmp_val = cmul(tl[k], phasor(-pll.phase));
                         const float error = soft_phase_err_group<FL_LPS>((lds_cf32*)reinterpret_cast<const float*>(s_pts), C.states, C.amp, C.prescale, tmp_val, gl);
                         ot[k] = tmp_val;
                         pll.advance(error);
@@ -1649,15 +1790,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     }
                 }
             } else
-            for (int k = 0; k < m; ++k) {
+            for (int k = 0; k < m; ++k) {                 // (the text of pll_symbol, written out: see there)
                 const int i = base + k;
-                cf32 tmp_val = cmul(tl[k], phasor_fast(-pll.phase));
+                cf32 tmp_val = cmul(tl[k], phasor(-pll.phase));
                 float error = 0.f;
                 cf32 o;
                 bool block_end = false;
                 if (i >= 90) {
                     cf32 descr = pl_descramble(tmp_val, rnt[k]);
-                    bool is_pilot = next_pilot >= 0 && i >= next_pilot && i < next_pilot + 36;
+                    bool is_pilot = pw.next_pilot >= 0 && i >= pw.next_pilot && i < pw.next_pilot + 36;
                     if (!is_pilot) {
                         if (C.bits != 5) error = as_global(lut_err_v)[lut_cell(tmp_val.re, tmp_val.im)];
                         else error = soft_phase_err_group<FL_LPS>((lds_cf32*)reinterpret_cast<const float*>(s_pts), C.states, C.amp, C.prescale, tmp_val, gl);
@@ -1666,19 +1807,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                             // own extension: data-aided on the known (1+j)/sqrt2 pilot, and the block estimate below
                             const cf32 pr = cmul(descr, cf32{0.707f, -0.707f});
                             error = cphase(pr);
-                            pacc = cadd(pacc, pr);
+                            pw.pacc = cadd(pw.pacc, pr);
                         } else {
                             // the reference's pilot error: decision-directed on the sign-sliced QPSK point, a tenth of the gain (dvbs2_pll.cpp:58)
                             const cf32 pt{descr.re > 0 ? 0.707f : -0.707f, descr.im > 0 ? 0.707f : -0.707f};
                             error = cphase(cmul(descr, cconj(pt))) / 10.0f;
                         }
-                        if (i == next_pilot + 35) { ++pb; next_pilot = pb < pilot_blocks ? pilot_start(pb) : -1; block_end = true; }
+                        if (i == pw.next_pilot + 35) { ++pw.pb; pw.next_pilot = pw.pb < pilot_blocks ? pilot_start(pw.pb) : -1; block_end = true; }
                     }
                     o = descr;
                 } else {
                     const cf32 pr = cmul(tmp_val, cconj(i < 26 ? T.sof[i] : plsc[i - 26]));
                     error = cphase(pr);
-                    if (co.pilot_aided) pacc = cadd(pacc, pr);
+                    if (co.pilot_aided) pw.pacc = cadd(pw.pacc, pr);
                     block_end = i == 89;
                     o = cf32{0.f, 0.f};   // header symbols come from the PLHDR demod below
                 }
@@ -1687,12 +1828,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 pll.wrap_pi_once();
                 if (co.pilot_aided && block_end) {
                     // pilot-aided mode (include/dvbs2gpu.h): the block estimate of the residual phase over the known symbols moves the loop phase
-                    if (pacc.re != 0.f || pacc.im != 0.f) {
-                        pll.phase += cphase(pacc);
+                    if (pw.pacc.re != 0.f || pw.pacc.im != 0.f) {
+                        pll.phase += cphase(pw.pacc);
                         pll.advance(0.f);
                         pll.wrap_pi();
                     }
-                    pacc = cf32{0.f, 0.f};
+                    pw.pacc = cf32{0.f, 0.f};
                 }
             }
             FL_SYNC();
@@ -1706,59 +1847,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         }
         if (fin) {
         FL_SYNC();
-        // ---- coarse frequency error detector (dvbs2_fed.h): terms in parallel, summed in the reference's order
-        #pragma unroll 1
-        for (int i = gl; i < 88; i += FL_LPS) {
-            cf32 r2 = (i + 2) < 26 ? T.sof[i + 2] : plsc[i + 2 - 26];
-            cf32 r0 = i < 26 ? T.sof[i] : plsc[i - 26];
-            fd[i] = cmul(cmul(cmul(fr[i + 2], cconj(r2)), cconj(fr[i])), r0).im;
-        }
-        FL_SYNC();
-        float err = 0.f, symcnt = 90 - 2;
-        for (int i = 0; i < 88; ++i) err += fd[i];
-        if (pilots) {
-            const cf32 p{0.707f, 0.707f};
-            for (int b = 0; b < pilot_blocks; ++b) {
-                int start = pilot_start(b);
-                FL_SYNC();
-                for (int i = gl; i < 36; i += FL_LPS) tl[i] = pl_descramble(fr[start + i], T.rn[start - 90 + i]);
-                FL_SYNC();
-                for (int i = gl; i < 36; i += FL_LPS)
-                    if (i >= 2) fd[i] = cmul(cmul(cmul(tl[i], cconj(p)), cconj(tl[i - 2])), p).im;
-                FL_SYNC();
-                for (int i = 2; i < 36; ++i) err += fd[i];
-                symcnt += 36 - 2;
-            }
-        }
-        float est = err / symcnt;
-        if (fabsf(est) < 0.02) nco_freq = nco_freq + est * (co.fll_bw / 100.0f);
-        else nco_freq = nco_freq + est * co.fll_bw;
-        if (nco_freq > 0.3f * PI_F) nco_freq = 0.3f * PI_F;
-        if (nco_freq < -0.3f * PI_F) nco_freq = -0.3f * PI_F;
+        // ---- coarse frequency error detector (dvbs2_fed.h)
+        const float est = coarse_fed<FL_LPS>(fr, plsc, T, pilots, pilot_blocks, tl, fd, gl, [] { FL_SYNC(); });
+        nco_freq = nco_feedback(nco_freq, est, co.fll_bw);
         // ---- PL header demod (dvbs2_plhdr_demod.cpp:33-67)
         // (the 90 header symbols are staged now, over the input + output tiles the PLL loop is through with)
         FL_SYNC();
         #pragma unroll 1
         for (int i = gl; i < 90; i += FL_LPS) tl[i] = fr[i];
-        unsigned long long plheader = 0;
-        const cf32 rot{(float)0.70710678118654757, (float)-0.70710678118654746};   // (cos(-pi/4), sin(-pi/4)) in double, cast
         FL_SYNC();
-        for (int i = 0; i < 90; ++i) {
-            cf32 tmp_val = cmul(tl[i], phasor_fast(-hdr.phase));
-            float error = ((tmp_val.re > 0 ? 1.0f : -1.0f) * tmp_val.im) - ((tmp_val.im > 0 ? 1.0f : -1.0f) * tmp_val.re);
-            cf32 o = (i & 1) ? cf32{-tmp_val.re, tmp_val.im} : cf32{tmp_val.im, tmp_val.re};
-            if (gl == 0 && fact) out[i] = o;
-            if (i >= 26) {
-                const float sv = cmul(o, rot).re;
-                plheader = plheader << 1 | (unsigned long long)(!(sv > 0));
-                if (co.soft_plsc && gl == 0) tl[i - 26].re = sv;      // (slot i - 26 < i has been consumed: reuse it for the soft value)
-            }
-            hdr.advance(error);
-            hdr.wrap_pi_once();
-        }
-        hdr.phase += hdr.freq * (plframe - 91);
-        hdr.advance(0.f);
-        hdr.wrap_pi();
+        const unsigned long long plheader = plhdr_loop(hdr, tl, plframe, co.soft_plsc && gl == 0 ? tl : nullptr, [&](int i, cf32 o) { if (gl == 0 && fact) out[i] = o; });
         // codeword search: minimum distance, lowest index among the minima (the reference scans 0..127 with strict '<')
         int key = 0x7fffffff;
         if (!co.soft_plsc) {
@@ -1776,9 +1874,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             int bc = 0x7fffffff;
             #pragma unroll 1
             for (int c = gl; c < 128; c += FL_LPS) {
-                const unsigned long long code = T.plsc_code[c];
-                float mtr = 0.f;
-                for (int p = 0; p < 64; ++p) { const float sv = tl[p].re; mtr += ((code >> (63 - p)) & 1ull) ? -sv : sv; }
+                const float mtr = plsc_soft_metric<2>(T.plsc_code[c], &tl[0].re);
                 if (bc == 0x7fffffff || mtr > bm) { bm = mtr; bc = c; }
             }
 #pragma unroll
@@ -1822,6 +1918,17 @@ __device__ __forceinline__ int deint_pos(int constel, int rate, int bits, int ro
     if (bits == 2) return 2 * j + (1 - c);
     const int col = (constel == C_8PSK && rate == R3_5) ? (2 - c) : c;
     return col * rows + j;
+}
+// the LLRs of payload symbol j (value v): the constellation's table cell, or constellation_t::demod_soft_calc for 32APSK; each goes to its de-interleaved place
+__device__ __forceinline__ void demap_symbol(const S2ConstelDev& C, cf32 v, int constel, int rate, int bits, int rows, int j, int8_t* __restrict__ out) {
+    int8_t b[5];
+    if (bits != 5) {
+        const int8_t* __restrict__ e = C.lut_bits + (size_t)lut_cell(v.re, v.im) * bits;
+        for (int c = 0; c < bits; ++c) b[c] = e[c];
+    } else {
+        soft_calc_dev(C, v, b, nullptr);
+    }
+    for (int c = 0; c < bits; ++c) out[deint_pos(constel, rate, bits, rows, j, c)] = b[c];
 }
 // grid (x: symbol tiles, y: frame).  LUT fetch + bit de-interleave fused: LLR c of payload symbol j goes to
 // column c (8PSK 3/5: columns reversed), QPSK just swaps the pair.
@@ -1880,15 +1987,7 @@ __global__ __launch_bounds__(256) void s2_demap_kernel(S2ConstelDev C_arg, int r
     for (int j = j0 + blockIdx.x * 256 + threadIdx.x; j < nsym; j += gridDim.x * 256) {
         int pos = 90 + j;
         if (pilots) pos += 36 * (j / 1440);   // pilot blocks already passed (one after every 16 slots)
-        cf32 v = fr[pos];
-        int8_t b[5];
-        if (bits != 5) {
-            const int8_t* __restrict__ e = C.lut_bits + (size_t)lut_cell(v.re, v.im) * bits;
-            for (int c = 0; c < bits; ++c) b[c] = e[c];
-        } else {
-            soft_calc_dev(C, v, b, nullptr);
-        }
-        for (int c = 0; c < bits; ++c) out[deint_pos(C.constel, rate, bits, rows, j, c)] = b[c];
+        demap_symbol(C, fr[pos], C.constel, rate, bits, rows, j, out);
     }
 }
 // S2Deinterleaver::deinterleave alone (s2_deinterleaver.cpp:72-136) on caller-supplied int8 frames: the same index function as the
@@ -1900,11 +1999,67 @@ __global__ __launch_bounds__(256) void s2_deinterleave_kernel(int constel, int r
         out[(size_t)f * N + deint_pos(constel, rate, bits, rows, i / bits, i % bits)] = in[(size_t)f * N + i];
 }
 
+// The reference's PL-sync correlator (dvbs2_pl_sync.cpp:111-143) by the 256 threads of a workgroup, brute force over the offsets 0 .. noff - 1 of x (noff + 90
+// symbols are read): 90 differential products, signed sums over the SOF and the odd PLSC positions, c = max |csof +- cplsc|, arg-max with strict '>' and
+// d.im > 0 = the lowest offset wins ties.  d (256 + 96), r_val, r_idx (256): the workgroup's LDS.  Returns the best offset, `best` its correlation (0: none qualified);
+// ends behind a barrier.
+__device__ __forceinline__ int pl_sync_correlate(const cf32* __restrict__ x, int noff, cf32* d, float* r_val, int* r_idx, int tid, float& best) {
+    const uint32_t dsof = 0x18d2e82u ^ (0x18d2e82u >> 1);
+    const unsigned long long SCR = 0x719d83c953422dfaull;
+    const unsigned long long dscr = SCR ^ (SCR >> 1);
+    float bestv = 0.f;
+    int besti = 0;
+    for (int base = 0; base < noff; base += 256) {
+        __syncthreads();
+        for (int k = tid; k < 256 + 90; k += 256) {
+            const int a = base + k;
+            cf32 v{0.f, 0.f};
+            if (k >= 1 && a < noff + 90) v = cmul(cconj(x[a - 1]), x[a]);
+            d[k] = v;
+        }
+        __syncthreads();
+        const int ss = base + tid;
+        if (ss < noff) {
+            const cf32* dd = &d[tid];
+            cf32 csof{0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < 26; ++i) {
+                cf32 v = (i == 0) ? cf32{0.f, 0.f} : dd[i];
+                if (((dsof >> (25 - i)) ^ i) & 1) csof = cadd(csof, v);
+                else csof = csub(csof, v);
+            }
+            cf32 cpl{0.f, 0.f};
+#pragma unroll
+            for (int i = 1; i < 64; i += 2) {
+                if ((dscr >> (63 - i)) & 1) cpl = csub(cpl, dd[26 + i]);
+                else cpl = cadd(cpl, dd[26 + i]);
+            }
+            cf32 c0 = cadd(csof, cpl), c1 = csub(csof, cpl);
+            cf32 c = camp(c0) > camp(c1) ? c0 : c1;
+            cf32 dv = cscale(c, 1.0f / (26 - 1 + 64 / 2));
+            float diff = camp(dv);
+            if (diff > bestv && dv.im > 0) { bestv = diff; besti = ss; }
+        }
+    }
+    r_val[tid] = bestv; r_idx[tid] = besti;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+            float v2 = r_val[tid + o]; int i2 = r_idx[tid + o];
+            float v1 = r_val[tid]; int i1 = r_idx[tid];
+            if (v2 > v1 || (v2 == v1 && v2 > 0.f && i2 < i1)) { r_val[tid] = v2; r_idx[tid] = i2; }
+        }
+        __syncthreads();
+    }
+    best = r_val[0];
+    const int at = r_idx[0];
+    __syncthreads();
+    return at;
+}
+
 // ------------------------------------------------------------------------------------------------ PL sync walk (CCM)
 // S2PLSyncBlock::process / internal_process (dvbs2_pl_sync.cpp:81-165) for one stream per workgroup, on the stream's symbol FIFO: every
-// complete window of `raw` symbols from the FIFO head on is correlated -- brute force at every offset (dvbs2_pl_sync.cpp:111-143): 90
-// differential products, signed sums over the SOF and the odd PLSC positions, c = max |csof +- cplsc|, arg-max with strict '>' and
-// d.im > 0 = the lowest offset wins ties; best_pos == 0: the window is the frame; best_pos != 0 (state 0 -> 1): the frame is
+// complete window of `raw` symbols from the FIFO head on is correlated (pl_sync_correlate); best_pos == 0: the window is the frame; best_pos != 0 (state 0 -> 1): the frame is
 // window[pos:] plus `pos` more symbols -- taken if they are in, else the window stays at the FIFO head and the stream waits in state 1
 // (pl_pending) for the next call.  A frame carries the best_match of the correlation that placed it (the reference's member
 // variable).  Per stream out: the frames' FIFO offsets, consumed symbols, symbols available, symbols this call added.
@@ -1929,9 +2084,6 @@ __global__ __launch_bounds__(256) void s2_ccm_walk_kernel(const S2StreamWork* __
     float lastbm = st->pl_last_bm;
     // a window the frame loops of the previous call were ahead in: the FIFO has lost the walk_cur symbols in front of it since
     if (sub == 0 && tid == 0 && st->spec_on) { st->spec_off -= st->walk_cur; st->spec_carried = st->spec_tiles; }
-    const uint32_t dsof = 0x18d2e82u ^ (0x18d2e82u >> 1);
-    const unsigned long long SCR = 0x719d83c953422dfaull;
-    const unsigned long long dscr = SCR ^ (SCR >> 1);
     const int noff = raw - 90;
     bool waiting = false;
     if (pend > 0) {                 // (the window the realigned frame starts in lies at `cur`: the FIFO head at the start of a call)
@@ -1945,54 +2097,9 @@ __global__ __launch_bounds__(256) void s2_ccm_walk_kernel(const S2StreamWork* __
         }
     }
     while (!waiting && cur + raw <= avail && nf < maxf) {
-        const cf32* __restrict__ x = fifo + cur;
-        float bestv = 0.f;
-        int besti = 0;
-        for (int base = 0; base < noff; base += 256) {
-            __syncthreads();
-            for (int k = tid; k < 256 + 90; k += 256) {
-                const int a = base + k;
-                cf32 v{0.f, 0.f};
-                if (k >= 1 && a < raw) v = cmul(cconj(x[a - 1]), x[a]);
-                d[k] = v;
-            }
-            __syncthreads();
-            const int ss = base + tid;
-            if (ss < noff) {
-                const cf32* dd = &d[tid];
-                cf32 csof{0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < 26; ++i) {
-                    cf32 v = (i == 0) ? cf32{0.f, 0.f} : dd[i];
-                    if (((dsof >> (25 - i)) ^ i) & 1) csof = cadd(csof, v);
-                    else csof = csub(csof, v);
-                }
-                cf32 cpl{0.f, 0.f};
-#pragma unroll
-                for (int i = 1; i < 64; i += 2) {
-                    if ((dscr >> (63 - i)) & 1) cpl = csub(cpl, dd[26 + i]);
-                    else cpl = cadd(cpl, dd[26 + i]);
-                }
-                cf32 c0 = cadd(csof, cpl), c1 = csub(csof, cpl);
-                cf32 c = camp(c0) > camp(c1) ? c0 : c1;
-                cf32 dv = cscale(c, 1.0f / (26 - 1 + 64 / 2));
-                float diff = camp(dv);
-                if (diff > bestv && dv.im > 0) { bestv = diff; besti = ss; }
-            }
-        }
-        r_val[tid] = bestv; r_idx[tid] = besti;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o) {
-                float v2 = r_val[tid + o]; int i2 = r_idx[tid + o];
-                float v1 = r_val[tid]; int i1 = r_idx[tid];
-                if (v2 > v1 || (v2 == v1 && v2 > 0.f && i2 < i1)) { r_val[tid] = v2; r_idx[tid] = i2; }
-            }
-            __syncthreads();
-        }
-        const float bm = r_val[0];
-        const int pos = bm > 0.f ? r_idx[0] : 0;
-        __syncthreads();
+        float bm;
+        const int at = pl_sync_correlate(fifo + cur, noff, d, r_val, r_idx, tid, bm);
+        const int pos = bm > 0.f ? at : 0;
         lastbm = bm;
         if (pos == 0) {
             if (tid == 0) found[(size_t)s * maxf + nf] = S2VcmFound{cur, 0, bm, 0};
@@ -2021,8 +2128,8 @@ __global__ __launch_bounds__(256) void s2_ccm_walk_kernel(const S2StreamWork* __
 // code of every frame.  The CPU oracle (oracle/s2chain.cpp, S2Rx::vcm_walk / pls_at / soft_plsc_decode) states the same rules.
 //
 // s2_vcm_walk_kernel -- ONE WORKGROUP PER STREAM walks the stream's symbol FIFO:
-//   not locked: the reference's differential SOF + PLSC correlator (it does not depend on the MODCOD) over the next VCM_ACQ_WINDOW
-//               offsets, same arg-max rule (strict '>', d.im > 0, lowest offset wins ties); the best offset becomes the frame start.
+//   not locked: the reference's differential SOF + PLSC correlator (pl_sync_correlate: it does not depend on the MODCOD) over the next VCM_ACQ_WINDOW
+//               offsets; the best offset becomes the frame start.
 //   locked:     soft PLS decode at the frame start: phase reference z = sum x[k] conj(sof[k]) over the 26 SOF symbols, soft value of
 //               PLSC symbol p = (w.re + w.im) for even p, (w.im - w.re) for odd p with w = x[26+p] conj(z) (pi/2-BPSK, s2_defs.h:60-80),
 //               metric of codeword c = sum_p +-soft[p] in index order, highest metric wins (lowest c on ties), ratio = metric /
@@ -2046,61 +2153,12 @@ __global__ __launch_bounds__(256) void s2_vcm_walk_kernel(const S2StreamWork* __
     const int avail_total = w.fifo_fill + nsym;
     int synced = st->vcm_synced;
     int cur = 0, nf = 0;
-    const uint32_t dsof = 0x18d2e82u ^ (0x18d2e82u >> 1);
-    const unsigned long long SCR = 0x719d83c953422dfaull;
-    const unsigned long long dscr = SCR ^ (SCR >> 1);
     while (true) {
         const int avail = avail_total - cur;
         if (!synced) {
             if (avail < VCM_ACQ_WINDOW + 90) break;
-            const cf32* __restrict__ x = fifo + cur;
-            float bestv = 0.f;
-            int besti = 0;
-            for (int base = 0; base < VCM_ACQ_WINDOW; base += 256) {
-                __syncthreads();
-                for (int k = tid; k < 256 + 90; k += 256) {
-                    const int a = base + k;
-                    cf32 v{0.f, 0.f};
-                    if (k >= 1 && a < VCM_ACQ_WINDOW + 90) v = cmul(cconj(x[a - 1]), x[a]);
-                    d[k] = v;
-                }
-                __syncthreads();
-                const int ss = base + tid;
-                if (ss < VCM_ACQ_WINDOW) {
-                    const cf32* dd = &d[tid];
-                    cf32 csof{0.f, 0.f};
-#pragma unroll
-                    for (int i = 0; i < 26; ++i) {
-                        cf32 v = (i == 0) ? cf32{0.f, 0.f} : dd[i];
-                        if (((dsof >> (25 - i)) ^ i) & 1) csof = cadd(csof, v);
-                        else csof = csub(csof, v);
-                    }
-                    cf32 cpl{0.f, 0.f};
-#pragma unroll
-                    for (int i = 1; i < 64; i += 2) {
-                        if ((dscr >> (63 - i)) & 1) cpl = csub(cpl, dd[26 + i]);
-                        else cpl = cadd(cpl, dd[26 + i]);
-                    }
-                    cf32 c0 = cadd(csof, cpl), c1 = csub(csof, cpl);
-                    cf32 c = camp(c0) > camp(c1) ? c0 : c1;
-                    cf32 dv = cscale(c, 1.0f / (26 - 1 + 64 / 2));
-                    float diff = camp(dv);
-                    if (diff > bestv && dv.im > 0) { bestv = diff; besti = ss; }
-                }
-            }
-            r_val[tid] = bestv; r_idx[tid] = besti;
-            __syncthreads();
-            for (int o = 128; o > 0; o >>= 1) {
-                if (tid < o) {
-                    float v2 = r_val[tid + o]; int i2 = r_idx[tid + o];
-                    float v1 = r_val[tid]; int i1 = r_idx[tid];
-                    if (v2 > v1 || (v2 == v1 && v2 > 0.f && i2 < i1)) { r_val[tid] = v2; r_idx[tid] = i2; }
-                }
-                __syncthreads();
-            }
-            const float bv = r_val[0];
-            const int bi = r_idx[0];
-            __syncthreads();
+            float bv;
+            const int bi = pl_sync_correlate(fifo + cur, VCM_ACQ_WINDOW, d, r_val, r_idx, tid, bv);
             if (bv > 0.f) { cur += bi; synced = 1; }
             else cur += VCM_ACQ_WINDOW;
             continue;
@@ -2118,11 +2176,7 @@ __global__ __launch_bounds__(256) void s2_vcm_walk_kernel(const S2StreamWork* __
             soft[tid] = (tid & 1) ? (wv.im - wv.re) : (wv.re + wv.im);
         }
         __syncthreads();
-        float mtr = 0.f;
-        if (tid < 128) {
-            const unsigned long long code = T.plsc_code[tid];
-            for (int p = 0; p < 64; ++p) mtr += ((code >> (63 - p)) & 1ull) ? -soft[p] : soft[p];
-        }
+        const float mtr = tid < 128 ? plsc_soft_metric<1>(T.plsc_code[tid], soft) : 0.f;
         r_val[tid] = mtr; r_idx[tid] = tid;
         __syncthreads();
         for (int o = 64; o > 0; o >>= 1) {        // over the 128 codewords: highest metric, lowest index on ties
@@ -2158,8 +2212,8 @@ __global__ __launch_bounds__(256) void s2_vcm_walk_kernel(const S2StreamWork* __
 }
 
 // s2_vcm_loops_kernel -- ONE WAVE PER STREAM, its frames in order, every frame with the parameters of ITS PLS code: coarse FED + NCO
-// feedback, PLL, PLHDR demod exactly as in s2_frame_loops_kernel (same operation order), in the plain one-wave-per-stream form: the
-// serial recurrences run uniformly in all lanes, the lanes share the loads / stores and the parallel parts.
+// feedback, PLL, PLHDR demod through the functions s2_frame_loops_kernel uses (coarse_fed, nco_feedback, pll_symbol, plhdr_loop, pll_payload_tile), in the
+// plain one-wave-per-stream form: the serial recurrences run uniformly in all lanes, the lanes share the loads / stores and the parallel parts.
 __global__ __launch_bounds__(64) void s2_vcm_loops_kernel(const S2StreamWork* __restrict__ work, const S2VcmFrame* __restrict__ frames,
                                                           const int* __restrict__ first, S2LoopCoefs co, S2PlTablesDev T,
                                                           const S2VcmMod* __restrict__ mods, const S2ConstelDev* __restrict__ cons,
@@ -2169,14 +2223,12 @@ __global__ __launch_bounds__(64) void s2_vcm_loops_kernel(const S2StreamWork* __
     __shared__ uint8_t rnt[64];
     __shared__ float fedt[96];
     __shared__ cf32 hdr_sym[90];
-    __shared__ float hsoft[64];
     __shared__ cf32 v_pts[32];
     const int lane = threadIdx.x, s = blockIdx.x;
     S2StreamState* st = work[s].st;
     PclDev pll{co.pll_alpha, co.pll_beta, st->pll_phase, st->pll_freq, co.pll_min_freq, co.pll_max_freq};
     PclDev hdr{co.hdr_alpha, co.hdr_beta, st->hdr_phase, st->hdr_freq, co.hdr_min_freq, co.hdr_max_freq};
     float nco_freq = st->nco_freq;
-    const float PI_F = 3.14159265358979323846f;
     for (int f = first[s]; f < first[s + 1]; ++f) {
         const S2VcmFrame F = frames[f];
         const S2VcmMod M = mods[F.pls];
@@ -2193,40 +2245,15 @@ __global__ __launch_bounds__(64) void s2_vcm_loops_kernel(const S2StreamWork* __
         const int plframe = M.plframe, pilots = M.pilots, pilot_blocks = M.pilot_blocks;
         const S2ConstelDev* __restrict__ C = cons + M.con;
         const int cbits = C->bits;
-        // ---- coarse frequency error detector (dvbs2_fed.h): terms in parallel, summed in the reference's order
+        // ---- coarse frequency error detector (dvbs2_fed.h)
         __syncthreads();
         if (cbits == 5 && lane < 32) v_pts[lane] = lane < C->states ? C->pts_g[lane] : cf32{0.f, 0.f};   // (this frame's 32APSK points, see soft_phase_err_group)
-        for (int i = lane; i < 88; i += 64) {
-            cf32 r2 = (i + 2) < 26 ? T.sof[i + 2] : plsc[i + 2 - 26];
-            cf32 r0 = i < 26 ? T.sof[i] : plsc[i - 26];
-            fedt[i] = cmul(cmul(cmul(fr[i + 2], cconj(r2)), cconj(fr[i])), r0).im;
-        }
         for (int i = lane; i < 90; i += 64) hdr_sym[i] = fr[i];
-        __syncthreads();
-        float err = 0.f, symcnt = 90 - 2;
-        for (int i = 0; i < 88; ++i) err += fedt[i];
-        if (pilots) {
-            const cf32 p{0.707f, 0.707f};
-            for (int b = 0; b < pilot_blocks; ++b) {
-                const int start = pilot_start(b);
-                __syncthreads();
-                if (lane < 36) tile[lane] = pl_descramble(fr[start + lane], T.rn[start - 90 + lane]);
-                __syncthreads();
-                if (lane >= 2 && lane < 36) fedt[lane] = cmul(cmul(cmul(tile[lane], cconj(p)), cconj(tile[lane - 2])), p).im;
-                __syncthreads();
-                for (int i = 2; i < 36; ++i) err += fedt[i];
-                symcnt += 36 - 2;
-            }
-        }
-        const float est = err / symcnt;
-        if (fabsf(est) < 0.02) nco_freq = nco_freq + est * (co.fll_bw / 100.0f);
-        else nco_freq = nco_freq + est * co.fll_bw;
-        if (nco_freq > 0.3f * PI_F) nco_freq = 0.3f * PI_F;
-        if (nco_freq < -0.3f * PI_F) nco_freq = -0.3f * PI_F;
+        const float est = coarse_fed<64>(fr, plsc, T, pilots, pilot_blocks, tile, fedt, lane, [] { __syncthreads(); });
+        nco_freq = nco_feedback(nco_freq, est, co.fll_bw);
         stt.fed_err = est;
         // ---- PLL (dvbs2_pll.cpp:34-86)
-        int next_pilot = (pilots && pilot_blocks > 0) ? pilot_start(0) : -1, pb = 0;
-        cf32 pacc{0.f, 0.f};
+        PilotWalk pw{(pilots && pilot_blocks > 0) ? pilot_start(0) : -1, 0, cf32{0.f, 0.f}};
         for (int base = 0; base < plframe; base += 64) {
             const int m = min(64, plframe - base);
             __syncthreads();
@@ -2237,75 +2264,21 @@ __global__ __launch_bounds__(64) void s2_vcm_loops_kernel(const S2StreamWork* __
             __syncthreads();
             // a tile of payload symbols only (no header, no pilot symbol) of a LUT constellation: the fixed-point form (pll_payload_tile) -- the general loop below is
             // ~100 instructions and a table round trip per symbol
-            const bool plain = S2_PLL_TILES && cbits != 5 && base >= 90 && !(next_pilot >= 0 && next_pilot < base + m && next_pilot + 36 > base);
+            const bool plain = pll_tile_form(cbits) && pw.payload_only(base, m);
             if (plain) {
                 const bool mine_k = lane < m;
                 const cf32 tmp_val = pll_payload_tile(mine_k ? tile[lane] : cf32{0.f, 0.f}, mine_k, lane, m, pll, C->lut_err);
                 if (mine_k) otile[lane] = pl_descramble(tmp_val, rnt[lane]);
             } else
-            for (int k = 0; k < m; ++k) {
-                const int i = base + k;
-                cf32 tmp_val = cmul(tile[k], phasor(-pll.phase));
-                float error = 0.f;
-                cf32 o;
-                bool block_end = false;
-                if (i >= 90) {
-                    cf32 descr = pl_descramble(tmp_val, rnt[k]);
-                    bool is_pilot = next_pilot >= 0 && i >= next_pilot && i < next_pilot + 36;
-                    if (!is_pilot) {
-                        if (cbits != 5) error = as_global(C->lut_err)[lut_cell(tmp_val.re, tmp_val.im)];
-                        else error = soft_phase_err_group<64>((lds_cf32*)reinterpret_cast<const float*>(v_pts), C->states, C->amp, C->prescale, tmp_val, lane);
-                    } else {
-                        if (co.pilot_aided) {
-                            // own extension: data-aided on the known (1+j)/sqrt2 pilot, and the block estimate below
-                            const cf32 pr = cmul(descr, cf32{0.707f, -0.707f});
-                            error = cphase(pr);
-                            pacc = cadd(pacc, pr);
-                        } else {
-                            // the reference's pilot error: decision-directed on the sign-sliced QPSK point, a tenth of the gain (dvbs2_pll.cpp:58)
-                            const cf32 pt{descr.re > 0 ? 0.707f : -0.707f, descr.im > 0 ? 0.707f : -0.707f};
-                            error = cphase(cmul(descr, cconj(pt))) / 10.0f;
-                        }
-                        if (i == next_pilot + 35) { ++pb; next_pilot = pb < pilot_blocks ? pilot_start(pb) : -1; block_end = true; }
-                    }
-                    o = descr;
-                } else {
-                    const cf32 pr = cmul(tmp_val, cconj(i < 26 ? T.sof[i] : plsc[i - 26]));
-                    error = cphase(pr);
-                    if (co.pilot_aided) pacc = cadd(pacc, pr);
-                    block_end = i == 89;
-                    o = cf32{0.f, 0.f};
-                }
-                otile[k] = o;                             // (uniform value)
-                pll.advance(error);
-                pll.wrap_pi_once();
-                if (co.pilot_aided && block_end) {
-                    if (pacc.re != 0.f || pacc.im != 0.f) {
-                        pll.phase += cphase(pacc);
-                        pll.advance(0.f);
-                        pll.wrap_pi();
-                    }
-                    pacc = cf32{0.f, 0.f};
-                }
-            }
+            for (int k = 0; k < m; ++k)                   // (uniform value)
+                otile[k] = pll_symbol<64>(pll, pw, tile[k], base + k, rnt[k], co, T, plsc, pilot_blocks, cbits, C->lut_err,
+                                          (lds_cf32*)reinterpret_cast<const float*>(v_pts), C->states, C->amp, C->prescale, lane);
             __syncthreads();
             if (lane < m && base + lane >= 90) out[base + lane] = otile[lane];
         }
         // ---- PL header demod (dvbs2_plhdr_demod.cpp:33-67): loop + header symbols; the frame's PLS code is the one the framing decoded
-        const cf32 rot{(float)0.70710678118654757, (float)-0.70710678118654746};
         __syncthreads();
-        for (int i = 0; i < 90; ++i) {
-            cf32 tmp_val = cmul(hdr_sym[i], phasor(-hdr.phase));
-            float error = ((tmp_val.re > 0 ? 1.0f : -1.0f) * tmp_val.im) - ((tmp_val.im > 0 ? 1.0f : -1.0f) * tmp_val.re);
-            cf32 o = (i & 1) ? cf32{-tmp_val.re, tmp_val.im} : cf32{tmp_val.im, tmp_val.re};
-            if (lane == 0) out[i] = o;
-            hdr.advance(error);
-            hdr.wrap_pi_once();
-        }
-        hdr.phase += hdr.freq * (plframe - 91);
-        hdr.advance(0.f);
-        hdr.wrap_pi();
-        (void)hsoft; (void)rot;
+        plhdr_loop(hdr, hdr_sym, plframe, nullptr, [&](int i, cf32 o) { if (lane == 0) out[i] = o; });
         if (lane == 0) stats[f] = stt;
     }
     if (lane == 0) {
@@ -2329,15 +2302,7 @@ __global__ __launch_bounds__(256) void s2_vcm_demap_kernel(const S2VcmFrame* __r
     for (int j = blockIdx.x * 256 + threadIdx.x; j < nsym; j += gridDim.x * 256) {
         int pos = 90 + j;
         if (M.pilots) pos += 36 * (j / 1440);
-        const cf32 v = fr[pos];
-        int8_t b[5];
-        if (bits != 5) {
-            const int8_t* __restrict__ e = C.lut_bits + (size_t)lut_cell(v.re, v.im) * bits;
-            for (int c = 0; c < bits; ++c) b[c] = e[c];
-        } else {
-            soft_calc_dev(C, v, b, nullptr);
-        }
-        for (int c = 0; c < bits; ++c) out[deint_pos(M.constel, M.rate, bits, rows, j, c)] = b[c];
+        demap_symbol(C, fr[pos], M.constel, M.rate, bits, rows, j, out);
     }
 }
 // frames of one FEC group -> contiguous LLR block (the decoder takes [frames][N]); grid (x: tiles, y: frame of the group)
@@ -2661,7 +2626,7 @@ __global__ __launch_bounds__(64) void dvbs_fll4_kernel(const DvbsStreamWork* __r
         __syncthreads();
         for (int k = 0; k < mmax; ++k) {
             if (k < m) {                                     // (whole lane groups: the shifts and the swizzle stay inside a stream)
-                const cf32 x = cmul_pk3(ytile[row][k], phasor_hw(-phase));
+                const cf32 x = cmul_pk3(ytile[row][k], phasor(-phase));
                 // this sample's two outputs: the sum leaving the last tap position + newest sample * tap 64 (the stream's last lane)
                 const cf32 lo = cadd(al[TPL - 1], cmul_pk3(x, tl_last)), hi = cadd(ah[TPL - 1], cmul_pk3(x, th_last));
                 float err = fast_amplitude(hi) - fast_amplitude(lo);
@@ -3030,7 +2995,7 @@ __global__ __launch_bounds__(64) void dvbs_costas_kernel(const DvbsStreamWork* _
     const int first = (nsub > 1 && sub) ? st->n_sym_slice[sub - 1] : 0, last = nsub > 1 ? st->n_sym_slice[sub] : st->n_sym;
     PclDev cos{co.cos_alpha, co.cos_beta, st->costas_phase, st->costas_freq, co.cos_min_freq, co.cos_max_freq};
     auto one = [&](cf32 x) -> cf32 {
-        const cf32 v = cmul(x, phasor_hw(-cos.phase));
+        const cf32 v = cmul(x, phasor(-cos.phase));
         float cerr = ((v.re > 0 ? 1.0f : -1.0f) * v.im) - ((v.im > 0 ? 1.0f : -1.0f) * v.re);
         cerr = clamp_med3(cerr, -1.0f, 1.0f);
         cos.advance(cerr);

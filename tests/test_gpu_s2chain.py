@@ -846,6 +846,41 @@ def test_acm_vcm_stream_cycling_modcods_equals_oracle(engine, esn0, cfo, chunk):
     dm.close()
 
 
+VCM_PILOT_PLS = [(14 << 2) | 3, (6 << 2) | 3, 0, (4 << 2) | 2, (27 << 2) | 3, (19 << 2) | 3]
+
+
+def test_acm_vcm_pilot_aided_equals_oracle(engine):
+    """The pilot-aided PLL (data-aided pilot error, block phase estimate after the header and after every pilot block) on the ACM/VCM
+    path: short frames of four pilot-carrying MODCODs (8PSK, QPSK, 32APSK, 16APSK), one without pilots and a dummy PLFRAME.  Same
+    equality bar as the cycling test above: taps, per-frame statistics and BBFRAMEs call by call.  (The oracle alone delivers 10 frames
+    on this input, the last 8 of them the transmitted frames 6..13.)"""
+    iq, bbs = orc.transmit_vcm(VCM_PILOT_PLS, 18, seed=3, esn0_db=22.0, cfo=1e-3, timing=0.3, phase0=0.2, lead_symbols=500)
+    chunk = 30011
+    rx = orc.OracleRx(orc.default_cfg(4, 1, 0, acm_vcm=1, max_ldpc_trials=25, pilot_aided=1))
+    dm = engine.demod(engine.default_cfg(4, True, False, acm_vcm=1, max_ldpc_trials=25, pilot_aided=1), max_samples=chunk)
+    got_all = []
+    for ncall, a in enumerate(range(0, iq.size, chunk)):
+        part = iq[a:a + chunk]
+        o = rx.process(part)
+        g = dm.process(part)
+        for t in range(4):
+            assert same_bits(rx.tap(t), dm.tap(t)), ('tap', t, ncall)
+        st_o, st_g = rx.tap(4), dm.stats()
+        assert len(st_o) == len(st_g), ncall
+        for a_, b_ in zip(st_o, st_g):
+            assert np.float32(a_.best_match).view(np.uint32) == np.float32(b_.pl_sync_best_match).view(np.uint32)
+            assert np.float32(a_.fed_err).view(np.uint32) == np.float32(b_.coarse_freq_err).view(np.uint32)
+            assert (a_.detect_modcod, a_.detect_short, a_.detect_pilots, a_.ldpc_trials, a_.bch_corr, a_.bbframe_bytes) == \
+                   (b_.detected_modcod, b_.detected_shortframes, b_.detected_pilots, b_.ldpc_trials, b_.bch_corrections, b_.bbframe_bytes)
+        assert len(o) == len(g) and all(np.array_equal(x, y) for x, y in zip(o, g)), ('BBFRAMEs', ncall)
+        got_all += g
+    sent = [bytes(b) for b in bbs if b is not None]
+    idx = [sent.index(bytes(x)) if bytes(x) in sent else -1 for x in got_all]
+    good = [k for k in idx if k >= 0]
+    assert len(good) >= 8 and good == list(range(good[0], good[0] + len(good))), idx
+    dm.close()
+
+
 def test_acm_vcm_batch_of_streams_and_error_paths(engine, pkg):
     """several ACM/VCM streams and a CCM stream in one process_batch call == each on its own handle"""
     import torch
