@@ -687,49 +687,63 @@ private:
         std::fill(watched, watched + 16, -1);
     }
 };
-struct PcrApi {
-    typedef dvbs2gpu_pcr Handle; typedef dvbs2gpu_pcr_stats Stats; typedef dvbs2gpu_pcr_stream_stats StreamStats; typedef dvbs2gpu_pcr_row Row;
-    static constexpr const char* name = "PcrBank";
-    static constexpr auto create = &dvbs2gpu_pcr_create, create_host = &dvbs2gpu_pcr_create_host;
-    static constexpr auto destroy = &dvbs2gpu_pcr_destroy;
-    static constexpr auto reset = &dvbs2gpu_pcr_reset;
-    static constexpr auto work = &dvbs2gpu_pcr_work;
-    static constexpr auto get_stats = &dvbs2gpu_pcr_get_stats;
-    static constexpr auto get_stream_stats = &dvbs2gpu_pcr_get_stream_stats;
-    static constexpr auto get_row_table = &dvbs2gpu_pcr_get_row_table;
+/* the A of a watched-PID bank: its types and C functions by prefix */
+#define DVBS2GPU_WATCH_API(Api, cls, p)                                                                                                  \
+    struct Api {                                                                                                                         \
+        typedef dvbs2gpu_##p Handle; typedef dvbs2gpu_##p##_stats Stats; typedef dvbs2gpu_##p##_stream_stats StreamStats;                \
+        typedef dvbs2gpu_##p##_row Row;                                                                                                  \
+        static constexpr const char* name = cls;                                                                                         \
+        static constexpr auto create = &dvbs2gpu_##p##_create, create_host = &dvbs2gpu_##p##_create_host;                                \
+        static constexpr auto destroy = &dvbs2gpu_##p##_destroy;                                                                         \
+        static constexpr auto reset = &dvbs2gpu_##p##_reset;                                                                             \
+        static constexpr auto work = &dvbs2gpu_##p##_work;                                                                               \
+        static constexpr auto get_stats = &dvbs2gpu_##p##_get_stats;                                                                     \
+        static constexpr auto get_stream_stats = &dvbs2gpu_##p##_get_stream_stats;                                                       \
+        static constexpr auto get_row_table = &dvbs2gpu_##p##_get_row_table;                                                             \
+        static constexpr auto set_watch = &dvbs2gpu_##p##_set_watch;                                                                     \
+    }
+DVBS2GPU_WATCH_API(PcrApi, "PcrBank", pcr);
+DVBS2GPU_WATCH_API(PesApi, "PesBank", pes);
+DVBS2GPU_WATCH_API(EsWatchApi, "EsBank", es);
+DVBS2GPU_WATCH_API(AudWatchApi, "AudBank", aud);
+#undef DVBS2GPU_WATCH_API
+struct EsApi : EsWatchApi {
+    /* the codec of a PMT stream_type: 0x01 / 0x02 MPEG2, 0x1B H264, 0x24 H265, 0: none of them */
+    static int codecOf(int stream_type) {
+        return stream_type == 0x01 || stream_type == 0x02 ? DVBS2GPU_ES_MPEG2 : stream_type == 0x1B ? DVBS2GPU_ES_H264 : stream_type == 0x24 ? DVBS2GPU_ES_H265 : 0;
+    }
 };
-struct PesApi {
-    typedef dvbs2gpu_pes Handle; typedef dvbs2gpu_pes_stats Stats; typedef dvbs2gpu_pes_stream_stats StreamStats; typedef dvbs2gpu_pes_row Row;
-    static constexpr const char* name = "PesBank";
-    static constexpr auto create = &dvbs2gpu_pes_create, create_host = &dvbs2gpu_pes_create_host;
-    static constexpr auto destroy = &dvbs2gpu_pes_destroy;
-    static constexpr auto reset = &dvbs2gpu_pes_reset;
-    static constexpr auto work = &dvbs2gpu_pes_work;
-    static constexpr auto get_stats = &dvbs2gpu_pes_get_stats;
-    static constexpr auto get_stream_stats = &dvbs2gpu_pes_get_stream_stats;
-    static constexpr auto get_row_table = &dvbs2gpu_pes_get_row_table;
+struct AudApi : AudWatchApi {
+    /* the codec of a PMT stream_type: 0x03 / 0x04 MPA, 0x0F ADTS, 0x81 / 0x87 AC3, 0: none of them.  The PMT views carry no
+     * descriptors: DVB's AC-3 in private stream type 0x06 cannot be told, the caller names such a PID with setWatch() */
+    static int codecOf(int stream_type) {
+        return stream_type == 0x03 || stream_type == 0x04 ? DVBS2GPU_AUD_MPA : stream_type == 0x0F ? DVBS2GPU_AUD_ADTS
+             : stream_type == 0x81 || stream_type == 0x87 ? DVBS2GPU_AUD_AC3 : 0;
+    }
 };
-struct EsApi {
-    typedef dvbs2gpu_es Handle; typedef dvbs2gpu_es_stats Stats; typedef dvbs2gpu_es_stream_stats StreamStats; typedef dvbs2gpu_es_row Row;
-    static constexpr const char* name = "EsBank";
-    static constexpr auto create = &dvbs2gpu_es_create, create_host = &dvbs2gpu_es_create_host;
-    static constexpr auto destroy = &dvbs2gpu_es_destroy;
-    static constexpr auto reset = &dvbs2gpu_es_reset;
-    static constexpr auto work = &dvbs2gpu_es_work;
-    static constexpr auto get_stats = &dvbs2gpu_es_get_stats;
-    static constexpr auto get_stream_stats = &dvbs2gpu_es_get_stream_stats;
-    static constexpr auto get_row_table = &dvbs2gpu_es_get_row_table;
-};
-struct AudApi {
-    typedef dvbs2gpu_aud Handle; typedef dvbs2gpu_aud_stats Stats; typedef dvbs2gpu_aud_stream_stats StreamStats; typedef dvbs2gpu_aud_row Row;
-    static constexpr const char* name = "AudBank";
-    static constexpr auto create = &dvbs2gpu_aud_create, create_host = &dvbs2gpu_aud_create_host;
-    static constexpr auto destroy = &dvbs2gpu_aud_destroy;
-    static constexpr auto reset = &dvbs2gpu_aud_reset;
-    static constexpr auto work = &dvbs2gpu_aud_work;
-    static constexpr auto get_stats = &dvbs2gpu_aud_get_stats;
-    static constexpr auto get_stream_stats = &dvbs2gpu_aud_get_stream_stats;
-    static constexpr auto get_row_table = &dvbs2gpu_aud_get_row_table;
+/* What EsBank and AudBank share beyond WatchBank (the banks that are told a codec per slot): setWatch() with the codec, codecOf(),
+ * followPmts() by it and rows().  A adds set_watch and codecOf to what WatchBank asks for. */
+template <typename A>
+class CodecBank : public WatchBank<A> {
+public:
+    /* slot 0..15; pid -1 clears the slot; codec: one of the bank's DVBS2GPU_ES_* / DVBS2GPU_AUD_* codecs */
+    void setWatch(int slot, int pid, int codec = 0) {
+        check(A::set_watch(this->need(), 0, slot, pid, codec));
+        this->watched[slot] = pid;
+    }
+    /* the codec of a PMT stream_type, 0: none of the bank's */
+    static int codecOf(int stream_type) { return A::codecOf(stream_type); }
+    /* watches the PIDs of the PMTs that `psi` holds decoded whose stream type codecOf() knows, in free slots, in the order of its
+     * slots and then of each PMT's elementary streams; other stream types and PIDs watched already are skipped; returns the PIDs
+     * that found no free slot */
+    std::vector<int> followPmts(PsiBank& psi) {
+        return this->followWith(psi, [](const dvbs2gpu_psi_pmt&, const std::vector<dvbs2gpu_psi_es>& es, auto offer) {
+            for (const dvbs2gpu_psi_es& e : es)
+                if (const int codec = A::codecOf(e.stream_type)) offer(e.elementary_pid, codec);
+        }, [this](int slot, int pid, int codec) { setWatch(slot, pid, codec); });
+    }
+    /* the rows of the last work(), in row order (the first max_rows) */
+    std::vector<typename A::Row> rows() { return this->table(); }
 };
 }   // namespace detail
 /* PCR bank for one transport stream (dvbs2gpu_pcr_*, include/dvbs2gpu.h; an extension): PCR repetition, discontinuity and accuracy
@@ -790,58 +804,14 @@ public:
  * 16 watched video PIDs (MPEG-2, H.264, H.265) behind BBFrameTSParser, DVBSDemod or TSMonitor, one row per PES packet start and per
  * reported start code.  init() (a device bank) or initHost() (the library's host implementation, no device) and the setters throw;
  * work() sits in the data path and does NOT throw: a failing call returns 0 and leaves its code in status() and its text in error(),
- * sticky until clearStatus(). */
-class EsBank : public detail::WatchBank<detail::EsApi> {
-public:
-    /* slot 0..15; pid -1 clears the slot; codec DVBS2GPU_ES_MPEG2, _H264 or _H265 */
-    void setWatch(int slot, int pid, int codec = 0) {
-        check(dvbs2gpu_es_set_watch(need(), 0, slot, pid, codec));
-        watched[slot] = pid;
-    }
-    /* the codec of a PMT stream_type: 0x01 / 0x02 MPEG2, 0x1B H264, 0x24 H265, 0: none of them */
-    static int codecOf(int stream_type) {
-        return stream_type == 0x01 || stream_type == 0x02 ? DVBS2GPU_ES_MPEG2 : stream_type == 0x1B ? DVBS2GPU_ES_H264 : stream_type == 0x24 ? DVBS2GPU_ES_H265 : 0;
-    }
-    /* watches the video PIDs of the PMTs that `psi` holds decoded, in free slots, in the order of its slots and then of each PMT's
-     * elementary streams; other stream types and PIDs watched already are skipped; returns the PIDs that found no free slot */
-    std::vector<int> followPmts(PsiBank& psi) {
-        return followWith(psi, [](const dvbs2gpu_psi_pmt&, const std::vector<dvbs2gpu_psi_es>& es, auto offer) {
-            for (const dvbs2gpu_psi_es& e : es)
-                if (const int codec = codecOf(e.stream_type)) offer(e.elementary_pid, codec);
-        }, [this](int slot, int pid, int codec) { setWatch(slot, pid, codec); });
-    }
-    /* the rows of the last work(), in row order (the first max_rows) */
-    std::vector<dvbs2gpu_es_row> rows() { return table(); }
-};
+ * sticky until clearStatus().  setWatch(slot, pid, codec) takes DVBS2GPU_ES_MPEG2, _H264 or _H265; followPmts() the video PIDs. */
+class EsBank : public detail::CodecBank<detail::EsApi> {};
 /* Audio bank for one transport stream (dvbs2gpu_aud_*, include/dvbs2gpu.h; an extension): a frame index of up to 16 watched audio PIDs
  * (MPEG audio, ADTS, AC-3 / E-AC-3) behind BBFrameTSParser, DVBSDemod or TSMonitor, one row per PES packet start, per frame and per
  * loss of framing.  init() (a device bank) or initHost() (the library's host implementation, no device) and the setters throw;
  * work() sits in the data path and does NOT throw: a failing call returns 0 and leaves its code in status() and its text in error(),
- * sticky until clearStatus(). */
-class AudBank : public detail::WatchBank<detail::AudApi> {
-public:
-    /* slot 0..15; pid -1 clears the slot; codec DVBS2GPU_AUD_MPA, _ADTS or _AC3 */
-    void setWatch(int slot, int pid, int codec = 0) {
-        check(dvbs2gpu_aud_set_watch(need(), 0, slot, pid, codec));
-        watched[slot] = pid;
-    }
-    /* the codec of a PMT stream_type: 0x03 / 0x04 MPA, 0x0F ADTS, 0x81 / 0x87 AC3, 0: none of them.  The PMT views carry no
-     * descriptors: DVB's AC-3 in private stream type 0x06 cannot be told, the caller names such a PID with setWatch() */
-    static int codecOf(int stream_type) {
-        return stream_type == 0x03 || stream_type == 0x04 ? DVBS2GPU_AUD_MPA : stream_type == 0x0F ? DVBS2GPU_AUD_ADTS
-             : stream_type == 0x81 || stream_type == 0x87 ? DVBS2GPU_AUD_AC3 : 0;
-    }
-    /* watches the audio PIDs of the PMTs that `psi` holds decoded, in free slots, in the order of its slots and then of each PMT's
-     * elementary streams; other stream types and PIDs watched already are skipped; returns the PIDs that found no free slot */
-    std::vector<int> followPmts(PsiBank& psi) {
-        return followWith(psi, [](const dvbs2gpu_psi_pmt&, const std::vector<dvbs2gpu_psi_es>& es, auto offer) {
-            for (const dvbs2gpu_psi_es& e : es)
-                if (const int codec = codecOf(e.stream_type)) offer(e.elementary_pid, codec);
-        }, [this](int slot, int pid, int codec) { setWatch(slot, pid, codec); });
-    }
-    /* the rows of the last work(), in row order (the first max_rows) */
-    std::vector<dvbs2gpu_aud_row> rows() { return table(); }
-};
+ * sticky until clearStatus().  setWatch(slot, pid, codec) takes DVBS2GPU_AUD_MPA, _ADTS or _AC3; followPmts() the audio PIDs. */
+class AudBank : public detail::CodecBank<detail::AudApi> {};
 namespace detail {
 /* What MpeBank, UleBank and T2miBank share (the datagram banks: dvbs2gpu_mpe_*, dvbs2gpu_ule_*, dvbs2gpu_t2mi_*): everything but
  * setWatch() and what T2miBank has for the mode-adaptation packetiser.  A: the bank's C

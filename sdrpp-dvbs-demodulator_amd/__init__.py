@@ -1728,7 +1728,7 @@ class PsiBank(_TsBank):
 
 class _WatchBank(_TsBank):
     """what the banks share that judge up to 16 watched PIDs per stream and write one row table per stream (csrc/watch_bank.h; PcrBank,
-    PesBank, EsBank, AudBank).  A bank names its C prefix (_c) and its row and statistics structures (_Row, _Stats, _StreamStats), gives the row
+    PesBank, and under _CodecBank EsBank and AudBank).  A bank names its C prefix (_c) and its row and statistics structures (_Row, _Stats, _StreamStats), gives the row
     table its public names and adds stream_stats(), follow_pmts() and what it is told beyond the watch list."""
     SLOTS = 16
     _c = _Row = _Stats = _StreamStats = None
@@ -1878,10 +1878,42 @@ class PesBank(_WatchBank):
         return dict(packets=int(st.packets), rows_dropped=int(st.rows_dropped), packets_since_start=[int(v) for v in st.packets_since_start])
 
 
-class EsBank(_WatchBank):
+class _CodecBank(_WatchBank):
+    """what the watched-PID banks share that read the elementary streams of their PIDs and are told a codec per slot (csrc/es_stream.h;
+    EsBank, AudBank): a larger row table by default, set_watch() with the codec, follow_pmts() by the bank's STREAM_TYPE_CODECS (PMT
+    stream_type -> codec) and the row table as rows() / rows_device()."""
+    STREAM_TYPE_CODECS = {}
+    rows, rows_device = _WatchBank._table, _WatchBank._table_device
+
+    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=4096):
+        super().__init__(engine, nstreams, max_packets, max_rows)
+
+    @classmethod
+    def host(cls, nstreams=1, max_packets=4096, max_rows=4096):
+        """a bank without a device: the library's host implementation of the same rules, behind work()"""
+        return super().host(nstreams, max_packets, max_rows)
+
+    def set_watch(self, stream, slot, pid, codec=0):
+        """pid -1 clears the slot; the slot starts afresh"""
+        super().set_watch(stream, slot, pid, codec)
+
+    def follow_pmts(self, psi_bank, stream=0):
+        """watches the PIDs of the PMTs that `psi_bank` (a PsiBank that read the same stream) holds decoded whose stream type the bank's
+        STREAM_TYPE_CODECS names, with that codec, everything else skipped -- in free slots, in the order of its slots and then of each
+        PMT's elementary streams; PIDs watched already are skipped -> the PIDs that found no free slot"""
+        codecs = self.STREAM_TYPE_CODECS
+        return self._follow(psi_bank, stream, lambda hdr, es: [(pid, codecs[stream_type]) for stream_type, pid in es if stream_type in codecs])
+
+    def stream_stats(self, stream=0):
+        st = self._stream_stats(stream)
+        return dict(packets=int(st.packets), rows_dropped=int(st.rows_dropped))
+
+
+class EsBank(_CodecBank):
     """ES bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, ES bank): every payload byte of up to 16 watched video
     PIDs per stream is scanned for start codes; one table row per PES packet start and per picture, sequence header / SPS, GOP header,
-    parameter set, access unit delimiter and sequence end, with its position in the elementary stream."""
+    parameter set, access unit delimiter and sequence end, with its position in the elementary stream.  follow_pmts() takes stream
+    types 0x01 and 0x02 as MPEG2, 0x1B as H264, 0x24 as H265."""
     _c, _Row, _Stats, _StreamStats = 'dvbs2gpu_es', EsRow, EsStats, EsStreamStats
     _destroy = 'dvbs2gpu_es_destroy'
     SLOTS = 16
@@ -1892,37 +1924,14 @@ class EsBank(_WatchBank):
     NO_TS = (1 << 64) - 1
     STREAM_TYPE_CODECS = {0x01: 1, 0x02: 1, 0x1B: 2, 0x24: 3}       # PMT stream_type -> codec
     ROW_KEYS = tuple(k for k, _ in EsRow._fields_)
-    rows, rows_device = _WatchBank._table, _WatchBank._table_device
-
-    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=4096):
-        super().__init__(engine, nstreams, max_packets, max_rows)
-
-    @classmethod
-    def host(cls, nstreams=1, max_packets=4096, max_rows=4096):
-        """a bank without a device: the library's host implementation of the same rules, behind work()"""
-        return super().host(nstreams, max_packets, max_rows)
-
-    def set_watch(self, stream, slot, pid, codec=0):
-        """pid -1 clears the slot; the slot starts afresh"""
-        super().set_watch(stream, slot, pid, codec)
-
-    def follow_pmts(self, psi_bank, stream=0):
-        """watches the video PIDs of the PMTs that `psi_bank` (a PsiBank that read the same stream) holds decoded -- stream types 0x01 and
-        0x02 as MPEG2, 0x1B as H264, 0x24 as H265, everything else skipped -- in free slots, in the order of its slots and then of each
-        PMT's elementary streams; PIDs watched already are skipped -> the PIDs that found no free slot"""
-        codecs = self.STREAM_TYPE_CODECS
-        return self._follow(psi_bank, stream, lambda hdr, es: [(pid, codecs[stream_type]) for stream_type, pid in es if stream_type in codecs])
-
-    def stream_stats(self, stream=0):
-        st = self._stream_stats(stream)
-        return dict(packets=int(st.packets), rows_dropped=int(st.rows_dropped))
 
 
-class AudBank(_WatchBank):
+class AudBank(_CodecBank):
     """Audio bank for `nstreams` transport streams (own extension; include/dvbs2gpu.h, audio bank): the frames of up to 16 watched audio
     PIDs per stream (MPEG audio, ADTS, AC-3 / E-AC-3) are followed header by header from PES payload starts on; one table row per PES
     packet start, per frame (codec sub-kind, channel mode, sample rate, samples, bitrate, size, position in the elementary stream) and
-    per loss of framing."""
+    per loss of framing.  follow_pmts() takes stream types 0x03 and 0x04 as MPA, 0x0F as ADTS, 0x81 and 0x87 as AC3; the PMT views
+    carry no descriptors: DVB's AC-3 in private stream type 0x06 cannot be followed, the caller names such a PID with set_watch()."""
     _c, _Row, _Stats, _StreamStats = 'dvbs2gpu_aud', AudRow, AudStats, AudStreamStats
     _destroy = 'dvbs2gpu_aud_destroy'
     SLOTS = 16
@@ -1932,31 +1941,6 @@ class AudBank(_WatchBank):
     NO_TS = (1 << 64) - 1
     STREAM_TYPE_CODECS = {0x03: 1, 0x04: 1, 0x0F: 2, 0x81: 3, 0x87: 3}      # PMT stream_type -> codec
     ROW_KEYS = tuple(k for k, _ in AudRow._fields_)
-    rows, rows_device = _WatchBank._table, _WatchBank._table_device
-
-    def __init__(self, engine, nstreams=1, max_packets=4096, max_rows=4096):
-        super().__init__(engine, nstreams, max_packets, max_rows)
-
-    @classmethod
-    def host(cls, nstreams=1, max_packets=4096, max_rows=4096):
-        """a bank without a device: the library's host implementation of the same rules, behind work()"""
-        return super().host(nstreams, max_packets, max_rows)
-
-    def set_watch(self, stream, slot, pid, codec=0):
-        """pid -1 clears the slot; the slot starts afresh"""
-        super().set_watch(stream, slot, pid, codec)
-
-    def follow_pmts(self, psi_bank, stream=0):
-        """watches the audio PIDs of the PMTs that `psi_bank` (a PsiBank that read the same stream) holds decoded -- stream types 0x03 and
-        0x04 as MPA, 0x0F as ADTS, 0x81 and 0x87 as AC3, everything else skipped -- in free slots, in the order of its slots and then of
-        each PMT's elementary streams; PIDs watched already are skipped -> the PIDs that found no free slot.  The PMT views carry no
-        descriptors: DVB's AC-3 in private stream type 0x06 cannot be followed, the caller names such a PID with set_watch()"""
-        codecs = self.STREAM_TYPE_CODECS
-        return self._follow(psi_bank, stream, lambda hdr, es: [(pid, codecs[stream_type]) for stream_type, pid in es if stream_type in codecs])
-
-    def stream_stats(self, stream=0):
-        st = self._stream_stats(stream)
-        return dict(packets=int(st.packets), rows_dropped=int(st.rows_dropped))
 
 
 class _DatagramBank(_TsBank):

@@ -8,10 +8,11 @@
 // is known from the start alone, and for PES-aligned audio the chain before a start ends exactly where the start's own begins.
 //
 //   aud_kernel  one workgroup per stream, one launch per call.
-//     A-E  as in the ES bank (ts_watch.h; es.hip): the trusted packets of watched PIDs sorted by slot with their verdicts, the starts'
+//     A-E  es_stream.h, shared with the ES bank: the trusted packets of watched PIDs sorted by slot with their verdicts, the starts'
 //        plans, every packet's segment of ES bytes and its ES position by one prefix sum (exs), the last reset mark before a packet.
-//        An EVENT is a packet that is a start or carries a reset mark; link[] chains a slot's events, and the packets from an event up
-//        to the next one are its TERRITORY.  Only an event changes the lock from outside; inside a territory the chain alone does.
+//        This bank's hook adds the events: an EVENT is a packet that is a start or carries a reset mark; link[] chains a slot's events,
+//        and the packets from an event up to the next one are its TERRITORY.  Only an event changes the lock from outside; inside a
+//        territory the chain alone does.
 //     S  speculate: the lane of every valid start walks the chain through its territory as if the start acquired: hop by hop, a binary
 //        search over exs maps the header's last byte to its packet, the 8 bytes are read (two dwords where they lie in one packet).
 //        It writes every packet of the territory its ENTRY, 16 bits: the framer's state in front of the packet -- UNLOCKED, CARRY (the
@@ -26,40 +27,32 @@
 //        and walks its territory frame by frame, writing the entries anew.  Only then does one lane's work grow with the frames.
 //     F  every lane takes its packets' entries and checks the headers whose last byte lies in the packet (at most 27): the frames and
 //        losses are counted, rows counted per packet.
-//     G  the ES bank's: a prefix sum over the rows per packet in INPUT order, the PES rows, a second walk of each row-bearing packet
-//        that writes its rows; the lane of the slot's last packet writes the slot's new state.
+//     G  es_stream.h: a prefix sum over the rows per packet in INPUT order, the PES rows, a second walk of each row-bearing packet
+//        that writes its rows; the lane of the slot's last packet writes the slot's new state: here the tail and the framer's lock.
 // Every loop is bounded by a size: positions strictly increase along a chain, a territory of B bytes has at most B / 7 + 2 hops.
 // Vector stores and plain C++ only.
-#include "ts_watch.h"
-#include "watch_bank.h"
+#include "es_stream.h"
 #include "aud_rules.h"
 
 using namespace s2;
-#define g_err last_error()
 
 namespace s2 {
 
-constexpr int AUD_MAX_PACKETS = PW_MAX_PACKETS;
-constexpr int AUD_WG = 256;
+constexpr int AUD_MAX_PACKETS = ES_MAX_PACKETS;
+constexpr int AUD_WG = ES_WG;
 static_assert(sizeof(AudRow) == sizeof(dvbs2gpu_aud_row) && sizeof(AudRow) == 48, "row layout");
 static_assert(sizeof(AudCnt) * 2 == sizeof(dvbs2gpu_aud_stats), "stats order");
 static_assert(sizeof(AudState) == 32, "state layout");
-static_assert(AUD_MAX_PACKETS <= 16 * AUD_WG, "a thread's verdicts are 16 bits of a mask, its slot counts 16-bit words (ts_thread_run)");
-static_assert(AUD_MAX_PACKETS * (TSMON_TS - 4) < (1 << 20), "the prefix sum of segment bytes in an int");
+static_assert(AUD_SLOTS == ES_SLOTS && AUD_NONE == 0, "es_stream.h");
 static_assert(AUD_MPA == DVBS2GPU_AUD_MPA && AUD_ADTS == DVBS2GPU_AUD_ADTS && AUD_AC3 == DVBS2GPU_AUD_AC3, "public values");
 static_assert(AUD_PES == DVBS2GPU_AUD_UNIT_PES && AUD_FRAME == DVBS2GPU_AUD_UNIT_FRAME && AUD_LOSS == DVBS2GPU_AUD_UNIT_LOSS, "public values");
 static_assert(AUD_ACQUIRED == DVBS2GPU_AUD_ACQUIRED && AUD_RESYNC == DVBS2GPU_AUD_RESYNC && AUD_UNSYNCED == DVBS2GPU_AUD_UNSYNCED &&
               AUD_SPLIT_HEADER == DVBS2GPU_AUD_SPLIT_HEADER && AUD_CHANGE == DVBS2GPU_AUD_CHANGE, "public values");
 static_assert(AUD_PACKET_ROWS == 28 && AUD_MAX_FRAME + AUD_WINDOW < (1 << 14), "rows per packet in a byte; a distance inside a frame in an entry");
 
-struct AudCall { AudCallHead head; AudCnt cnt[AUD_SLOTS]; };
-
-// behind phase D bit 18 of a start's word says that the start is valid; behind phase J bit 19 that it continues a chain
-constexpr uint32_t AW_VALID = 1u << 18, AW_CONT = 1u << 19;
-__device__ inline bool aud_invalid_start(uint32_t e) { return pw_start(e) && !(e & AW_VALID); }
-__device__ inline bool aud_reset_front(uint32_t e) { return (e & PW_GAP) || (pw_counts(e) && pw_scr(e)); }
-__device__ inline bool aud_reset_mark(uint32_t e) { return aud_reset_front(e) || aud_invalid_start(e); }
-__device__ inline bool aud_event(uint32_t e) { return pw_start(e) || aud_reset_mark(e); }
+// bits 18 and 19 of a word are the bank's (ts_watch.h): VALID is es_stream.h's; behind phase J bit 19 says that a start continues a chain
+constexpr uint32_t AW_CONT = 1u << 19;
+__device__ inline bool aud_event(uint32_t e) { return pw_start(e) || es_reset_mark(e); }
 constexpr uint16_t AUD_NO_LINK = 0xFFFF;
 // an entry: the kind in bits 14-15, d or v below
 constexpr int AE_UNLOCKED = 0, AE_CARRY = 1, AE_PREV = 2, AE_ACQ = 3;
@@ -68,51 +61,49 @@ constexpr int AE_UNLOCKED = 0, AE_CARRY = 1, AE_PREV = 2, AE_ACQ = 3;
 // PREV, the last frame's position; ACQ, the start's sorted place
 struct AudSt { bool locked; int64_t next; uint32_t params; int kind, ref; };
 
-// what the kernel keeps in LDS beside the packets; a multiple of 16 bytes in front of them
-struct alignas(16) AudShared {
-    AudCnt cnt[AUD_SLOTS];
-    AudState ss[AUD_SLOTS];                      // the slots' states before the call
-    uint16_t place[AUD_SLOTS][AUD_WG];           // the counting sort's counts, then places; behind the sort link[]: an event's next event in sorted order
-    int32_t tbase[AUD_WG];                       // the rows in front of a thread's run of input packets
+// what the kernel keeps in LDS beside the packets: es_stream.h's (place[]: behind the sort link[], an event's next event in sorted
+// order) and the framer's
+struct alignas(16) AudShared : EsStreamShared<AudCnt, AudState> {
     int64_t x0_next[AUD_SLOTS];                  // the exit of the walk in front of a slot's first event
-    int32_t w[AUD_SLOTS], codec[AUD_SLOTS];
-    int32_t start[AUD_SLOTS + 1];                // the slots' runs in sorted order
     int32_t first_ev[AUD_SLOTS];                 // a slot's first event, -1: none
     int32_t x0_locked[AUD_SLOTS];
-    int32_t wsum[AUD_WG / 64];
-    uint8_t ncc[AUD_SLOTS];                      // the slots' continuity bytes behind the call
-    int64_t pos0;
 };
+// what the bank is to es_stream.h
+struct AudT {
+    typedef AudState State; typedef AudCnt Cnt; typedef AudRow Row; typedef AudShared Shared;
+    __device__ static void flush(AudCnt* d, const AudCnt& a) {
+#define AUD_ADD(f) if (a.f) atomicAdd(&d->f, a.f)
+        AUD_ADD(es_bytes); AUD_ADD(bytes_unsynced); AUD_ADD(resets); AUD_ADD(pes_starts); AUD_ADD(pes_invalid); AUD_ADD(split_headers);
+        AUD_ADD(frames); AUD_ADD(frame_bytes_total); AUD_ADD(samples_total); AUD_ADD(acquisitions); AUD_ADD(sync_losses); AUD_ADD(param_changes);
+        AUD_ADD(unaligned_starts); AUD_ADD(bytes_unlocked);
+#undef AUD_ADD
+    }
+    __device__ static bool synced(const AudState& st) { return (st.bits & AUD_SYNCED) != 0; }
+    __device__ static bool lost(const AudState& st) { return (st.bits & AUD_LOST) != 0; }
+    // (LOCKED is the kernel's to set behind it)
+    __device__ static void set_synced_lost(AudState& st, bool synced, bool lost) { st.bits = (uint8_t)((synced ? AUD_SYNCED : 0) | (lost ? AUD_LOST : 0)); }
+    __device__ static AudRow pes_row(int pid, int slot, int k, const EsPlan& pl, uint64_t es_pos, bool lost) { return aud_pes_row(pid, slot, k, pl, es_pos, lost); }
+};
+typedef EsStreamCall<AudCnt> AudCall;
 static_assert(sizeof(AudShared) % 16 == 0 && sizeof(AudShared::place) == AUD_MAX_PACKETS * sizeof(uint16_t), "the packets behind it; an index per packet");
 // dynamic LDS: AudShared, srt[max_packets], exs[max_packets + 2] (32 bits each), ent[], xit[] (16 bits per packet), rc[] (8 bits)
 constexpr size_t aud_even(int max_packets) { return ((size_t)max_packets + 1) & ~(size_t)1; }
 constexpr size_t aud_lds_bytes(int max_packets) {
     return sizeof(AudShared) + ((size_t)max_packets * 2 + 2) * sizeof(uint32_t) + 2 * aud_even(max_packets) * sizeof(uint16_t) + (((size_t)max_packets + 15) & ~(size_t)15);
 }
-static_assert(aud_lds_bytes(AUD_MAX_PACKETS) < 64 * 1024, "dynamic LDS of a workgroup");
+static_assert(aud_lds_bytes(AUD_MAX_PACKETS) < 64 * 1024, "dynamic LDS of a workgroup");        // 63.3 KiB
 
-__device__ inline void aud_flush(AudCnt* d, const AudCnt& a) {
-#define AUD_ADD(f) if (a.f) atomicAdd(&d->f, a.f)
-    AUD_ADD(es_bytes); AUD_ADD(bytes_unsynced); AUD_ADD(resets); AUD_ADD(pes_starts); AUD_ADD(pes_invalid); AUD_ADD(split_headers);
-    AUD_ADD(frames); AUD_ADD(frame_bytes_total); AUD_ADD(samples_total); AUD_ADD(acquisitions); AUD_ADD(sync_losses); AUD_ADD(param_changes);
-    AUD_ADD(unaligned_starts); AUD_ADD(bytes_unlocked);
-#undef AUD_ADD
-}
-// the packet counters of phase C, per thread and slot run
-__device__ inline void aud_flush_pk(AudCnt* d, const PwPk& a) {
-    atomicAdd(&d->packets, a.packets);
-    if (a.payload_bytes) atomicAdd(&d->payload_bytes, a.payload_bytes);
-    if (a.duplicates) atomicAdd(&d->duplicates, a.duplicates);
-    if (a.cc_errors) atomicAdd(&d->cc_errors, a.cc_errors);
-    if (a.scrambled) atomicAdd(&d->scrambled_packets, a.scrambled);
-    if (a.malformed) atomicAdd(&d->malformed_packets, a.malformed);
-}
-// counters summed per thread and slot run
-struct AudAcc {
-    AudCnt c; int slot; AudCnt* dst;
-    __device__ AudAcc(AudCnt* d) : c(aud_cnt_zero()), slot(-1), dst(d) {}
-    __device__ __forceinline__ void at(int s) { if (s != slot) { done(); c = aud_cnt_zero(); slot = s; } }
-    __device__ __forceinline__ void done() { if (slot >= 0) aud_flush(&dst[slot], c); slot = -1; }
+// the front's hook: the entries cleared, and the events chained: link[] and the slots' first events
+struct AudEvents {
+    AudShared& sh; uint16_t *ent, *xit, *link; int le;
+    __device__ __forceinline__ void placed(int j) { ent[j] = 0; xit[j] = 0; link[j] = AUD_NO_LINK; }
+    __device__ __forceinline__ void first(int j, uint32_t e, int) { if (aud_event(e)) le = j; }
+    __device__ __forceinline__ void between(int* wsum) { le = ts_block_scan_max(le, wsum); }                 // the last event before the thread's run
+    __device__ __forceinline__ void second(int j, uint32_t e, int) {
+        if (!aud_event(e)) return;
+        if (le >= sh.start[pw_slot(e)]) link[le] = (uint16_t)j; else sh.first_ev[pw_slot(e)] = j;
+        le = j;
+    }
 };
 
 // One slot's packets of the call as the walks see them: the sorted run [head, end), their words and prefix values, and the ES bytes at
@@ -164,98 +155,27 @@ __global__ void __launch_bounds__(AUD_WG) aud_kernel(const uint8_t* const* __res
                                                      const int32_t* __restrict__ watch, const int32_t* __restrict__ codec, AudState* __restrict__ state,
                                                      int64_t* __restrict__ pos, AudRow* __restrict__ rows_g, AudCall* __restrict__ call) {
     extern __shared__ __attribute__((aligned(16))) unsigned char aud_lds[];
-    AudShared& sh = *reinterpret_cast<AudShared*>(aud_lds);
-    uint32_t* srt = reinterpret_cast<uint32_t*>(aud_lds + sizeof(AudShared));
-    uint32_t* exs = srt + max_packets;               // a segment's length, then the exclusive prefix: the ES bytes of the call in front of it
-    uint16_t* ent = reinterpret_cast<uint16_t*>(exs + max_packets + 2);     // the entries, per sorted packet
+    EsStream<AudT> f(aud_lds, in, nbytes, max_packets, max_rows);
+    AudShared& sh = f.sh;
+    uint32_t* srt = f.srt;
+    const uint32_t* exs = f.exs;
+    const uint8_t* ts = f.ts;
+    uint16_t* ent = reinterpret_cast<uint16_t*>(f.exs + max_packets + 2);   // the entries, per sorted packet
     uint16_t* xit = ent + aud_even(max_packets);                            // a valid start's exit: 0 unlocked, else 8 + next - the territory's end
     uint8_t* rc = reinterpret_cast<uint8_t*>(xit + aud_even(max_packets));  // rows per INPUT packet
-    uint32_t* rec = exs;
     uint16_t* link = &sh.place[0][0];
-    const int s = blockIdx.x, tid = threadIdx.x;
-    int n = nbytes[s] / TSMON_TS;
-    if (n > max_packets) n = max_packets;            // (the host has refused such a call)
+    const int tid = f.tid;
     if (tid < AUD_SLOTS) {
-        sh.w[tid] = watch[(size_t)s * AUD_SLOTS + tid];
-        sh.codec[tid] = codec[(size_t)s * AUD_SLOTS + tid];
-        sh.ss[tid] = state[(size_t)s * AUD_SLOTS + tid];
-        sh.cnt[tid] = aud_cnt_zero();
         sh.first_ev[tid] = -1;
         sh.x0_locked[tid] = 0; sh.x0_next[tid] = 0;
     }
-    for (int k = tid; k < n; k += AUD_WG) rc[k] = 0;
-    if (tid == 0) sh.pos0 = pos[s];
-    __syncthreads();
-    const uint8_t* ts = in[s];
-    // A: the watched packets, compacted in input order
-    const int W = pw_compact<AUD_WG>(ts, n, sh.w, sh.wsum, rec);
+    for (int k = tid; k < f.n; k += AUD_WG) rc[k] = 0;
+    EsStreamAcc<AudT> acc(sh.cnt);
+    AudEvents hook = {sh, ent, xit, link, -1};
     int nrows = 0;
-    if (W > 0) {
-        // B: the stable counting sort by slot
-        int j0, j1;
-        pw_sort<AUD_WG>(rec, srt, W, sh.place, sh.start, sh.wsum, &j0, &j1);
-        // C: the continuity verdicts
-        unsigned dupm, gapm;
-        pw_verdicts(srt, j0, j1, sh.start, [&](int slot) { return sh.ss[slot].cc; }, sh.wsum, sh.ncc,
-                    [&](int slot, const PwPk& pk) { aud_flush_pk(&sh.cnt[slot], pk); }, &dupm, &gapm);
-        __syncthreads();                                         // every counter has been read: the verdicts take their bits
-        AudAcc acc(sh.cnt);
-        // D: the starts: valid or not, and their segments
-        int last_start = -1;
-        for (int j = j0; j < j1; ++j) {
-            uint32_t e = pw_with_verdict(srt[j], dupm >> (j - j0) & 1, gapm >> (j - j0) & 1);
-            if (pw_start(e)) {
-                uint32_t w5[5];
-                pw_load_start(ts, e, w5);
-                const EsPlan pl = es_packet_plan(w5, pw_len(e), pw_scr(e), 1, false, false);
-                if (pl.valid) e |= AW_VALID;
-                exs[j] = (uint32_t)pl.seg_len;
-                acc.at(pw_slot(e));
-                aud_cnt_start(&acc.c, pl);
-                last_start = j;
-            }
-            srt[j] = e;
-            ent[j] = 0; xit[j] = 0; link[j] = AUD_NO_LINK;
-        }
-        __syncthreads();
-        const int ls0 = ts_block_scan_max(last_start, sh.wsum);   // the last sorted start before the thread's run
-        // the slot's synced bit behind its start ls (or none in this call)
-        auto synced_at = [&](int slot, int ls) { return ls >= sh.start[slot] ? (srt[ls] & AW_VALID) != 0 : (sh.ss[slot].bits & AUD_SYNCED) != 0; };
-        // E: the segment lengths, the reset marks, the events
-        int lr0 = -1;
-        {
-            int ls = ls0, sum = 0, lr = -1, le = -1;
-            for (int j = j0; j < j1; ++j) {
-                const uint32_t e = srt[j];
-                const int slot = pw_slot(e);
-                acc.at(slot);
-                int len = 0;
-                if (pw_start(e)) { len = (int)exs[j]; ls = j; }
-                else if (pw_counts(e) && !pw_scr(e)) {
-                    if (synced_at(slot, ls)) len = pw_len(e); else acc.c.bytes_unsynced += pw_len(e);
-                }
-                exs[j] = (uint32_t)len;
-                sum += len;
-                acc.c.es_bytes += len;
-                if (aud_reset_mark(e)) { lr = j; ++acc.c.resets; }
-                if (aud_event(e)) le = j;
-            }
-            int total;
-            int at = ts_block_scan<AUD_WG>(sum, sh.wsum, &total);
-            lr0 = ts_block_scan_max(lr, sh.wsum);                // the last sorted packet with a reset mark before the run,
-            le = ts_block_scan_max(le, sh.wsum);                 // and the last event
-            for (int j = j0; j < j1; ++j) {
-                const int len = (int)exs[j];
-                exs[j] = (uint32_t)at; at += len;
-                const uint32_t e = srt[j];
-                if (aud_event(e)) {
-                    if (le >= sh.start[pw_slot(e)]) link[le] = (uint16_t)j; else sh.first_ev[pw_slot(e)] = j;
-                    le = j;
-                }
-            }
-            if (tid == 0) exs[W] = (uint32_t)total;
-        }
-        __syncthreads();
+    // A-E: es_stream.h
+    if (f.front(watch, codec, state, pos, acc, hook)) {
+        const int j0 = f.j0, j1 = f.j1;
         auto run_of = [&](int slot) { return AudRun{ts, srt, exs, sh.ss[slot].tail, sh.start[slot], sh.start[slot + 1]}; };
         auto carried = [&](int slot) {
             const AudState& c = sh.ss[slot];
@@ -356,7 +276,7 @@ __global__ void __launch_bounds__(AUD_WG) aud_kernel(const uint8_t* const* __res
                 const AudSt st = walk_territory(r, slot, j, fe >= 0 ? fe : r.end, carried(slot));
                 sh.x0_locked[slot] = st.locked; sh.x0_next[slot] = st.next;
             }
-            if (pw_start(e) && (e & AW_VALID)) {
+            if (pw_start(e) && (e & PW_VALID)) {
                 const int jb = link[j] != AUD_NO_LINK && link[j] < r.end ? link[j] : r.end;
                 const AudSt st = walk_territory(r, slot, j, jb, AudSt{true, r.pos(j), 0, AE_ACQ, j});
                 xit[j] = st.locked ? (uint16_t)(8 + st.next - r.pos(jb)) : (uint16_t)0;
@@ -373,8 +293,8 @@ __global__ void __launch_bounds__(AUD_WG) aud_kernel(const uint8_t* const* __res
             for (int it = r.head; it < r.end && ev >= 0; ++it) {
                 const uint32_t e = srt[ev];
                 const int jb = link[ev] != AUD_NO_LINK && link[ev] < r.end ? link[ev] : r.end;
-                if (aud_reset_mark(e)) st.locked = false;                                 // (a reset in front of a valid start: it acquires)
-                if (pw_start(e) && (e & AW_VALID)) {
+                if (es_reset_mark(e)) st.locked = false;                                 // (a reset in front of a valid start: it acquires)
+                if (pw_start(e) && (e & PW_VALID)) {
                     if (!st.locked || st.next == r.pos(ev)) {                             // the speculation holds
                         if (!st.locked) ++acquisitions; else srt[ev] = e | AW_CONT;
                         st.locked = xit[ev] != 0; st.next = r.pos(jb) + (int)xit[ev] - 8;
@@ -417,109 +337,38 @@ __global__ void __launch_bounds__(AUD_WG) aud_kernel(const uint8_t* const* __res
         }
         acc.done();
         __syncthreads();
-        // G: the rows' places in input order, the slot's last row-bearing packet, the rows and the new states
-        const int chunk = (n + AUD_WG - 1) / AUD_WG;
-        {
-            int k0, k1; ts_thread_run(n, AUD_WG, &k0, &k1);
-            int sum = 0;
-            for (int k = k0; k < k1; ++k) sum += rc[k];
-            sh.tbase[tid] = ts_block_scan<AUD_WG>(sum, sh.wsum, &nrows);
-        }
-        int lp = ts_block_scan_max(last_row, sh.wsum);
-        __syncthreads();
-        AudRow* rows = rows_g + (size_t)s * max_rows;
-        int lr = lr0, ls = ls0;
-        // the slot's lost bit where its last row-bearing packet is p and its last reset mark r (both before the place, -1 or another slot's: none)
-        auto lost_behind = [&](int slot, int p, int r) {
-            const int head = sh.start[slot];
-            if (p >= head) return r > p || (r == p && aud_invalid_start(srt[p]));
-            return (sh.ss[slot].bits & AUD_LOST) != 0 || r >= head;
-        };
-        for (int j = j0; j < j1; ++j) {
-            const uint32_t e = srt[j];
-            const int slot = pw_slot(e), k = pw_k(e), head = sh.start[slot];
-            const AudRun r = run_of(slot);
-            const int nr = rc[k];
-            if (nr) {
-                bool lost = aud_reset_front(e) || lost_behind(slot, lp, lr);
-                int rank = sh.tbase[k / chunk];
-                for (int q = (k / chunk) * chunk; q < k; ++q) rank += rc[q];
-                if (pw_start(e)) {
-                    uint32_t w5[5];
-                    pw_load_start(ts, e, w5);
-                    const EsPlan pl = es_packet_plan(w5, pw_len(e), pw_scr(e), 1, false, false);
-                    if (rank < max_rows) rows[rank] = aud_pes_row(sh.w[slot], slot, k, pl, sh.ss[slot].es_count + (uint64_t)r.pos(j), lost);
-                    lost = false;
-                    ++rank;
-                }
-                if (nr > pw_start(e)) {
-                    AudSt st = state_in(r, slot, j);
-                    AudCnt none = aud_cnt_zero();
-                    walk_packet(r, slot, j, st, &none, rows, rank, max_rows, lost, nullptr);
-                }
-                lp = j;
-            }
-            if (aud_reset_mark(e)) lr = j;
-            if (pw_start(e)) ls = j;
-            if (j == r.end - 1) {
-                AudState nx = sh.ss[slot];
+        // G: es_stream.h; a second walk of each row-bearing packet writes its rows
+        AudRow* rows = rows_g + (size_t)f.s * max_rows;
+        nrows = f.rows(rc, last_row, rows_g, state,
+            [&](int j, uint32_t e, uint64_t, int, int rank, bool lost) {
+                const int slot = pw_slot(e);
+                const AudRun r = run_of(slot);
+                AudSt st = state_in(r, slot, j);
+                AudCnt none = aud_cnt_zero();
+                walk_packet(r, slot, j, st, &none, rows, rank, max_rows, lost, nullptr);
+            },
+            [&](AudState& nx, int slot, int j, int lr) {
+                const AudRun r = run_of(slot);
                 AudSt st = state_in(r, slot, j);
                 AudCnt none = aud_cnt_zero();
                 walk_packet(r, slot, j, st, &none, nullptr, 0, 0, false, nullptr);
                 const int total = r.pos(r.end);
-                const uint32_t sn = lr >= head ? (uint32_t)(total - r.pos(lr)) : (uint32_t)nx.have + (uint32_t)total;
+                const uint32_t sn = lr >= r.head ? (uint32_t)(total - r.pos(lr)) : (uint32_t)nx.have + (uint32_t)total;
                 const int have = sn < 7 ? (int)sn : 7;
                 nx.tail = r.bytes(total - have, have); nx.have = (uint8_t)have;
-                nx.es_count += (uint64_t)total;
-                nx.cc = sh.ncc[slot];
-                nx.bits = (uint8_t)((synced_at(slot, ls) ? AUD_SYNCED : 0) | (lost_behind(slot, lp, lr) ? AUD_LOST : 0) | (st.locked ? AUD_LOCKED : 0));
-                if (st.locked) { nx.next = sh.ss[slot].es_count + (uint64_t)st.next; nx.params = st.params; }
-                state[(size_t)s * AUD_SLOTS + slot] = nx;
-            }
-        }
-        __syncthreads();
+                if (st.locked) { nx.bits |= AUD_LOCKED; nx.next = sh.ss[slot].es_count + (uint64_t)st.next; nx.params = st.params; }
+            });
     }
-    if (tid < AUD_SLOTS) call[s].cnt[tid] = sh.cnt[tid];
-    if (tid == 0) {
-        call[s].head = AudCallHead{nrows, {0, 0, 0}};
-        pos[s] = sh.pos0 + n;
-    }
+    f.finish(call, pos, nrows);
 }
 
 }  // namespace s2
 
-// the host half is the watched-PID bank's (watch_bank.h); here what is the bank's own
-struct AudBankD {
-    static constexpr int SLOTS = AUD_SLOTS, MAX_PACKETS = AUD_MAX_PACKETS;
-    typedef AudState State; typedef AudRow Row; typedef AudCall Call; typedef AudHostStream HostStream;
-    typedef dvbs2gpu_aud_stats Stats; typedef dvbs2gpu_aud_stream_stats StreamStats;
-    static constexpr int SUMS = AUD_COUNTERS;          // every word of dvbs2gpu_aud_stats is a counter
+// the host half is the watched-PID bank's (watch_bank.h) with what es_stream.h adds for a bank with a codec per slot; here what is the bank's own
+struct AudBankD : EsStreamBankD<AudBankD, AudT, aud_kernel, aud_lds_bytes, AUD_COUNTERS> {
+    typedef AudHostStream HostStream; typedef dvbs2gpu_aud_stats Stats; typedef dvbs2gpu_aud_stream_stats StreamStats;
     static constexpr StreamStats NO_STREAM_STATS = {};
-    typedef int32_t Config;                            // the codec, per slot
-    static constexpr int CONFIGS = AUD_SLOTS;
-    static constexpr Config NO_CONFIG = AUD_NONE;
     static constexpr const char *BANK = "audio bank: ", *CNAME = "dvbs2gpu_aud", *ALLOC = "hipMalloc(aud)";
-
-    // one stream's call into its statistics; `n` packets came
-    static void account(WatchBank<AudBankD>& b, int i, int n, const AudCallHead& head, const AudCnt* c) {
-        dvbs2gpu_aud_stream_stats& ss = b.sstats[i];
-        for (int s = 0; s < AUD_SLOTS; ++s) {
-            if (!c[s].packets) continue;                   // (no packet of the slot's PID came: every counter is 0)
-            const int32_t* a = reinterpret_cast<const int32_t*>(&c[s]);
-            int64_t* d = reinterpret_cast<int64_t*>(&b.stats[(size_t)i * AUD_SLOTS + s]);
-            for (int k = 0; k < AUD_COUNTERS; ++k) d[k] += a[k];
-        }
-        ss.packets += n;
-        if (head.rows > b.max_rows) ss.rows_dropped += head.rows - b.max_rows;
-        b.total[i] = head.rows;
-        b.nrows[i] = head.rows < b.max_rows ? head.rows : b.max_rows;
-    }
-    static void launch(WatchBank<AudBankD>& b, const TsBankArgs& a, hipStream_t st) {
-        const size_t lds = aud_lds_bytes(b.max_packets);       // <= 63.3 KiB
-        hipLaunchKernelGGL(aud_kernel, dim3(b.nstreams), dim3(AUD_WG), lds, st, a.in(b.d_args), a.nbytes(b.d_args), b.max_packets, b.max_rows, b.d_watch, b.d_cfg, b.d_state,
-                           b.d_pos, b.d_rows, b.d_call);
-    }
-    static void fix_stream_stats(StreamStats*) {}
 };
 struct dvbs2gpu_aud : WatchBank<AudBankD> {};
 
@@ -531,14 +380,7 @@ int dvbs2gpu_aud_create_host(int nstreams, int max_packets, int max_rows, dvbs2g
 int dvbs2gpu_aud_reset(dvbs2gpu_aud* b) { return watch_reset(b); }
 
 int dvbs2gpu_aud_set_watch(dvbs2gpu_aud* b, int stream, int slot, int pid, int codec) {
-    if (!watch_slot_ok(b, stream, slot, pid)) return DVBS2GPU_ERR_ARG;
-    if (pid >= 0 && (codec < AUD_MPA || codec > AUD_AC3)) { g_err = "audio bank: the codec is DVBS2GPU_AUD_MPA, _ADTS or _AC3"; return DVBS2GPU_ERR_ARG; }
-    if (const int e = watch_set_watch(b, stream, slot, pid)) return e;
-    const size_t at = (size_t)stream * AUD_SLOTS + slot;
-    b->cfg[at] = pid >= 0 ? codec : AUD_NONE;
-    if (b->ctx) return watch_upload_config(b, at);
-    b->host[stream].codec[slot] = b->cfg[at];
-    return 0;
+    return es_stream_set_watch(b, stream, slot, pid, codec, AUD_AC3, "audio bank: the codec is DVBS2GPU_AUD_MPA, _ADTS or _AC3");
 }
 
 int dvbs2gpu_aud_process_batch(dvbs2gpu_aud* b, const uint8_t* const* d_ts, const int* nbytes, int* out_rows, void* stream) {

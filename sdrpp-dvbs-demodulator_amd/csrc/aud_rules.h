@@ -124,17 +124,14 @@ AUD_HD inline AudParse aud_parse(int codec, uint64_t win) {
 constexpr int AUD_SYNCED = 1, AUD_LOST = 2, AUD_LOCKED = 4;
 struct AudState { uint64_t es_count, tail, next; uint32_t params; uint8_t cc, have, bits, pad; };
 
-// what one call adds to a slot's statistics, in the order of dvbs2gpu_aud_stats
-struct AudCnt {
-    int32_t packets, payload_bytes, es_bytes, bytes_unsynced, duplicates, cc_errors, scrambled_packets, malformed_packets, resets, pes_starts, pes_invalid,
-            split_headers, frames, frame_bytes_total, samples_total, acquisitions, sync_losses, param_changes, unaligned_starts, bytes_unlocked;
+// what one call adds to a slot's statistics, in the order of dvbs2gpu_aud_stats: the ES bank's twelve (EsStreamCnt, with es_cnt_start
+// for a start) and the framer's
+struct AudCnt : EsStreamCnt {
+    int32_t frames, frame_bytes_total, samples_total, acquisitions, sync_losses, param_changes, unaligned_starts, bytes_unlocked;
 };
 constexpr int AUD_COUNTERS = 20;
 static_assert(sizeof(AudCnt) == AUD_COUNTERS * sizeof(int32_t), "counter order");
-AUD_HD inline AudCnt aud_cnt_zero() { return AudCnt{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; }
-AUD_HD inline void aud_cnt_start(AudCnt* c, const EsPlan& p) {
-    ++c->pes_starts; c->pes_invalid += !p.valid; c->split_headers += (p.row_flags & ES_SPLIT_HEADER) != 0;
-}
+AUD_HD inline AudCnt aud_cnt_zero() { return AudCnt{}; }
 
 // The framer's check of the header at `next`: the window w0..w7 against the frame before it (params; 0: the first since the
 // acquisition).  A valid header: a FRAME row, params and the next header's place follow it, true.  Else a LOSS row, false: the lock is lost
@@ -159,97 +156,39 @@ AUD_HD inline AudRow aud_pes_row(int pid, int slot, int k, const EsPlan& p, uint
     return AudRow{(uint16_t)pid, (uint8_t)slot, AUD_PES, (uint8_t)p.hd.stream_id, (uint8_t)p.hd.kind, (uint16_t)(p.row_flags | (lost ? AUD_RESYNC : 0)), (uint16_t)k, 0,
                   p.hd.declared, es_count, p.hd.pts, p.hd.dts, 0, 0, 0};
 }
-// the header of a stream's call record; the slots' AudCnt follow it (AudCall in aud.hip)
-struct AudCallHead { int32_t rows, pad[3]; };
-
 // ------------------------------------------------------------------------------------------------- the sequential definition
-struct AudHostStream {
-    int32_t watch[AUD_SLOTS];                               // -1: the slot watches nothing
-    int32_t codec[AUD_SLOTS];
-    AudState slot[AUD_SLOTS];
-    int64_t packets = 0;                                    // the position of the next call's first packet
-    // of the last call
-    std::vector<AudRow> rows;                               // the first max_rows
-    AudCnt cnt[AUD_SLOTS];
-    AudCallHead head = {0, {0, 0, 0}};
-
-    AudHostStream() {
-        for (int s = 0; s < AUD_SLOTS; ++s) { watch[s] = -1; codec[s] = AUD_NONE; clear_slot(s); cnt[s] = aud_cnt_zero(); }
-    }
-    void clear_slot(int s) { slot[s] = AudState{0, 0, 0, 0, 0, 0, 0, 0}; }
-    void reset() {
-        for (int s = 0; s < AUD_SLOTS; ++s) clear_slot(s);
-        packets = 0; rows.clear(); head = {0, {0, 0, 0}};
-    }
+// the packet walk is the ES bank's (EsHostWalk, es_rules.h); here what the framer does with a reset, a start and a segment's bytes
+struct AudHostStream : EsHostWalk<AudHostStream, AudState, AudCnt, AudRow> {
     void emit(AudRow r, AudState& st, int max_rows) {
         if (st.bits & AUD_LOST) r.flags |= AUD_RESYNC;
         st.bits &= (uint8_t)~AUD_LOST;
-        if (head.rows++ < max_rows) rows.push_back(r);
+        EsHostWalk::emit(r, max_rows);
     }
+    static bool synced(const AudState& st) { return (st.bits & AUD_SYNCED) != 0; }
     // a reset: the window is forgotten, the lock is lost without a row
-    static void framer_reset(AudState& st) { st.have = 0; st.tail = 0; st.bits = (uint8_t)((st.bits | AUD_LOST) & ~AUD_LOCKED); }
-    // one call: n packets
-    void run(const uint8_t* ts, int n, int max_rows) {
-        rows.clear();
-        head = {0, {0, 0, 0}};
-        for (int s = 0; s < AUD_SLOTS; ++s) cnt[s] = aud_cnt_zero();
-        for (int k = 0; k < n; ++k) {
-            const uint8_t* p = ts + (size_t)k * TSMON_TS;
-            const TsmonHdr h = tsmon_parse(p);
-            if (h.cls != TSMON_DATA) continue;
-            int s = 0;
-            while (s < AUD_SLOTS && watch[s] != h.pid) ++s;
-            if (s == AUD_SLOTS) continue;
-            AudState& st = slot[s];
-            AudCnt& c = cnt[s];
-            ++c.packets;
-            const int v = tsmon_step(&st.cc, h.afc, h.cc, h.di);
-            if (v == TSMON_DUPLICATE) { ++c.duplicates; continue; }
-            c.cc_errors += v == TSMON_CC_ERROR;
-            const bool cont = v == TSMON_CC_ERROR || v == TSMON_DISC;
-            const int L = pes_payload_len(h.afc, h.afc == 3 ? p[4] : 0);
-            if (L <= 0) {
-                const bool malformed = L == 0;
-                c.malformed_packets += malformed;
-                if (cont || malformed) { ++c.resets; framer_reset(st); }
-                continue;
-            }
-            c.payload_bytes += L;
-            c.scrambled_packets += h.tsc != 0;
-            uint32_t w[5] = {0, 0, 0, 0, 0};
-            const uint8_t* pay = p + TSMON_TS - L;
-            if (h.pusi && !h.tsc) for (int i = 0; i < L && i < PES_HEAD_BYTES; ++i) w[i >> 2] |= (uint32_t)pay[i] << (8 * (i & 3));
-            const EsPlan pl = es_packet_plan(w, L, h.tsc, h.pusi, cont, (st.bits & AUD_SYNCED) != 0);
-            if (pl.reset) framer_reset(st);
-            if (pl.start) {
-                emit(aud_pes_row(h.pid, s, k, pl, st.es_count, false), st, max_rows);
-                aud_cnt_start(&c, pl);
-                st.bits = (uint8_t)(pl.valid ? st.bits | AUD_SYNCED : st.bits & ~AUD_SYNCED);
-                if (!pl.valid) framer_reset(st);
-                else if (!(st.bits & AUD_LOCKED)) { st.bits |= AUD_LOCKED; st.next = st.es_count; st.params = 0; ++c.acquisitions; }
-                else if (st.next != st.es_count) ++c.unaligned_starts;
-            }
-            c.resets += pl.reset || (pl.start && !pl.valid);
-            c.bytes_unsynced += pl.unsynced_bytes;
-            c.es_bytes += pl.seg_len;
-            uint64_t win = st.tail;
-            uint32_t since = st.have;
-            for (int i = 0; i < pl.seg_len; ++i) {
-                c.bytes_unlocked += !(st.bits & AUD_LOCKED);        // (the byte that completes a failing window was accepted while locked)
-                win = win << 8 | pay[pl.seg_off + i];
-                ++since;
-                if (since < (uint32_t)AUD_WINDOW || !(st.bits & AUD_LOCKED) || st.es_count + i - 7 != st.next) continue;
-                AudLock lk = {st.next, st.params};
-                AudRow r = {(uint16_t)h.pid, (uint8_t)s, 0, 0, 0, 0, (uint16_t)k, 0, 0, 0, 0, 0, 0, 0, 0};
-                if (!aud_check(codec[s], win, &lk, &c, &r)) st.bits &= (uint8_t)~AUD_LOCKED;
-                st.next = lk.next; st.params = lk.params;
-                emit(r, st, max_rows);
-            }
-            st.es_count += pl.seg_len;
-            st.have = (uint8_t)(since < 7 ? since : 7);
-            st.tail = st.have == 7 ? win & ES_TAIL_MASK : win & ((1ull << (8 * st.have)) - 1);
+    static void stream_reset(AudState& st) { st.have = 0; st.tail = 0; st.bits = (uint8_t)((st.bits | AUD_LOST) & ~AUD_LOCKED); }
+    void start(int k, int s, const EsPlan& pl, int max_rows) {
+        AudState& st = slot[s];
+        emit(aud_pes_row(watch[s], s, k, pl, st.es_count, false), st, max_rows);
+        st.bits = (uint8_t)(pl.valid ? st.bits | AUD_SYNCED : st.bits & ~AUD_SYNCED);
+        if (!pl.valid) return;
+        if (!(st.bits & AUD_LOCKED)) { st.bits |= AUD_LOCKED; st.next = st.es_count; st.params = 0; ++cnt[s].acquisitions; }
+        else if (st.next != st.es_count) ++cnt[s].unaligned_starts;
+    }
+    void segment(int k, int s, const EsPlan& pl, const uint8_t* pay, uint64_t* win, uint32_t* since, int max_rows) {
+        AudState& st = slot[s];
+        AudCnt& c = cnt[s];
+        for (int i = 0; i < pl.seg_len; ++i) {
+            c.bytes_unlocked += !(st.bits & AUD_LOCKED);        // (the byte that completes a failing window was accepted while locked)
+            *win = *win << 8 | pay[pl.seg_off + i];
+            ++*since;
+            if (*since < (uint32_t)AUD_WINDOW || !(st.bits & AUD_LOCKED) || st.es_count + i - 7 != st.next) continue;
+            AudLock lk = {st.next, st.params};
+            AudRow r = {(uint16_t)watch[s], (uint8_t)s, 0, 0, 0, 0, (uint16_t)k, 0, 0, 0, 0, 0, 0, 0, 0};
+            if (!aud_check(codec[s], *win, &lk, &c, &r)) st.bits &= (uint8_t)~AUD_LOCKED;
+            st.next = lk.next; st.params = lk.params;
+            emit(r, st, max_rows);
         }
-        packets += n;
     }
 };
 

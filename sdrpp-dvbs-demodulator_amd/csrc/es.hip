@@ -9,92 +9,57 @@
 // its own segment, only the 7 bytes in front of it, which lie at the END of the slot's previous non-empty segments.
 //
 //   es_kernel  one workgroup per stream, one launch per call.
-//     A-C  ts_watch.h, shared with the PES bank: the trusted packets of watched PIDs as one word each, sorted by slot, with the
-//        continuity verdict.
-//     D  the lanes that own starts read the first payload bytes (pw_load_start) and apply es_packet_plan: valid or not into the word,
-//        the segment's length into LDS.
-//     E  a maximum scan gives every packet its slot's last start (synced = that start was valid, or the carried bit), so every packet's
-//        segment length is known; one prefix sum over them gives the ES positions; two more maximum scans give the last packet with a
-//        reset mark and the last non-empty segment before a packet.
+//     A-E  es_stream.h, shared with the audio bank (A-C: ts_watch.h, shared with the PES bank too): the trusted packets of watched PIDs
+//        as one word each, sorted by slot, with the continuity verdict; the starts' plans (es_packet_plan: valid or not into the word);
+//        every packet's segment of ES bytes from its slot's last start (synced = that start was valid, or the carried bit), the ES
+//        positions by one prefix sum, the last packet with a reset mark before a packet.  This bank's hook adds the last non-empty
+//        segment before a packet.
 //     F  every lane rolls the 64-bit window over its packets' segments (dwords at fixed places inside the packet), starting from the 7
 //        bytes in front: at most 7 hops back over non-empty segments (a payload may be one byte), then the carried tail.  Codes are
 //        counted and classified, rows counted per packet.
-//     G  a prefix sum over the rows per packet in INPUT order gives every packet its place in the table; a maximum scan the slot's last
-//        row-bearing packet before one (RESYNC: a reset mark behind it).  The PES rows are written; a packet with code rows is scanned
-//        once more to write them.  The lane of the slot's last packet writes the slot's new state.
+//     G  es_stream.h: a prefix sum over the rows per packet in INPUT order gives every packet its place in the table; a maximum scan
+//        the slot's last row-bearing packet before one (RESYNC: a reset mark behind it).  The PES rows are written; a packet with code
+//        rows is scanned once more to write them.  The lane of the slot's last packet writes the slot's new state: here its window.
 // No lane walks over packets of other lanes beyond the 7 hops: the cost of a call does not depend on what the packets say, but for the
 // second scan of packets that hold codes with rows.  One device-to-host copy of the per-stream call record (EsCall).
 // Vector stores and plain C++ only.
-#include "ts_watch.h"
-#include "watch_bank.h"
-#include "es_rules.h"
+#include "es_stream.h"
 
 using namespace s2;
-#define g_err last_error()
 
 namespace s2 {
 
-constexpr int ES_MAX_PACKETS = PW_MAX_PACKETS;             // per stream and call: 10 bytes of LDS per packet
-constexpr int ES_WG = 256;
 static_assert(sizeof(EsRow) == sizeof(dvbs2gpu_es_row) && sizeof(EsRow) == 48, "row layout");
 static_assert(sizeof(EsCnt) * 2 == sizeof(dvbs2gpu_es_stats), "stats order");
 static_assert(sizeof(EsState) == 24, "state layout");
-static_assert(ES_MAX_PACKETS <= 16 * ES_WG, "a thread's verdicts are 16 bits of a mask, its slot counts 16-bit words (ts_thread_run)");
-static_assert(ES_MAX_PACKETS * (TSMON_TS - 4) < (1 << 20), "the prefix sum of segment bytes in an int");
-static_assert(ES_MPEG2 == DVBS2GPU_ES_MPEG2 && ES_H264 == DVBS2GPU_ES_H264 && ES_H265 == DVBS2GPU_ES_H265, "public values");
+static_assert(ES_NONE == 0 && ES_MPEG2 == DVBS2GPU_ES_MPEG2 && ES_H264 == DVBS2GPU_ES_H264 && ES_H265 == DVBS2GPU_ES_H265, "public values");
 static_assert(ES_PES == DVBS2GPU_ES_UNIT_PES && ES_PICTURE == DVBS2GPU_ES_UNIT_PICTURE && ES_END == DVBS2GPU_ES_UNIT_END, "public values");
 static_assert(ES_KEY == DVBS2GPU_ES_KEY && ES_RESYNC == DVBS2GPU_ES_RESYNC && ES_UNSYNCED == DVBS2GPU_ES_UNSYNCED && ES_SPLIT_HEADER == DVBS2GPU_ES_SPLIT_HEADER, "public values");
 
-struct EsCall { EsCallHead head; EsCnt cnt[ES_SLOTS]; };
-
-// behind phase D bit 18 of a start's word says that the start is valid
-constexpr uint32_t PW_VALID = 1u << 18;
-__device__ inline bool es_invalid_start(uint32_t e) { return pw_start(e) && !(e & PW_VALID); }
-// the packet's reset in front of its row and segment; its reset mark (an invalid start resets once more, behind its row)
-__device__ inline bool es_reset_front(uint32_t e) { return (e & PW_GAP) || (pw_counts(e) && pw_scr(e)); }
-__device__ inline bool es_reset_mark(uint32_t e) { return es_reset_front(e) || es_invalid_start(e); }
-constexpr uint16_t ES_NO_PREV = 0xFFFF;
-
-// what the kernel keeps in LDS beside the packets; a multiple of 16 bytes in front of them
-struct alignas(16) EsShared {
-    EsCnt cnt[ES_SLOTS];
-    EsState ss[ES_SLOTS];                        // the slots' states before the call
-    uint16_t place[ES_SLOTS][ES_WG];             // the counting sort's counts, then places; behind the sort the last non-empty segment before each sorted packet
-    int32_t tbase[ES_WG];                        // the rows in front of a thread's run of input packets
-    int32_t w[ES_SLOTS], codec[ES_SLOTS];
-    int32_t start[ES_SLOTS + 1];                 // the slots' runs in sorted order
-    int32_t wsum[ES_WG / 64];
-    uint8_t ncc[ES_SLOTS];                       // the slots' continuity bytes behind the call
-    int64_t pos0;
-};
-static_assert(sizeof(EsShared) % 16 == 0 && sizeof(EsShared::place) == ES_MAX_PACKETS * sizeof(uint16_t), "the packets behind it; an index per packet");
-// dynamic LDS: EsShared, srt[max_packets], exs[max_packets + 1] (32 bits each), rc[max_packets] (16 bits)
-constexpr size_t es_lds_bytes(int max_packets) { return sizeof(EsShared) + ((size_t)max_packets * 2 + 2) * sizeof(uint32_t) + (((size_t)max_packets + 1) & ~(size_t)1) * sizeof(uint16_t); }
-static_assert(es_lds_bytes(ES_MAX_PACKETS) <= 64 * 1024, "dynamic LDS of a workgroup");
-
-__device__ inline void es_flush(EsCnt* d, const EsCnt& a) {
+// what the bank is to es_stream.h
+struct EsT {
+    typedef EsState State; typedef EsCnt Cnt; typedef EsRow Row;
+    typedef EsStreamShared<EsCnt, EsState> Shared;   // place[]: behind the sort the last non-empty segment before each sorted packet
+    __device__ static void flush(EsCnt* d, const EsCnt& a) {
 #define ES_ADD(f) if (a.f) atomicAdd(&d->f, a.f)
-    ES_ADD(es_bytes); ES_ADD(bytes_unsynced); ES_ADD(resets); ES_ADD(pes_starts); ES_ADD(pes_invalid); ES_ADD(split_headers);
-    ES_ADD(codes); ES_ADD(pictures); ES_ADD(pictures_i); ES_ADD(pictures_p); ES_ADD(pictures_b); ES_ADD(key_pictures); ES_ADD(sequences); ES_ADD(gops);
-    ES_ADD(params); ES_ADD(auds); ES_ADD(ends); ES_ADD(slices); ES_ADD(other_codes); ES_ADD(bad_codes);
+        ES_ADD(es_bytes); ES_ADD(bytes_unsynced); ES_ADD(resets); ES_ADD(pes_starts); ES_ADD(pes_invalid); ES_ADD(split_headers);
+        ES_ADD(codes); ES_ADD(pictures); ES_ADD(pictures_i); ES_ADD(pictures_p); ES_ADD(pictures_b); ES_ADD(key_pictures); ES_ADD(sequences); ES_ADD(gops);
+        ES_ADD(params); ES_ADD(auds); ES_ADD(ends); ES_ADD(slices); ES_ADD(other_codes); ES_ADD(bad_codes);
 #undef ES_ADD
-}
-// the packet counters of phase C, per thread and slot run
-__device__ inline void es_flush_pk(EsCnt* d, const PwPk& a) {
-    atomicAdd(&d->packets, a.packets);
-    if (a.payload_bytes) atomicAdd(&d->payload_bytes, a.payload_bytes);
-    if (a.duplicates) atomicAdd(&d->duplicates, a.duplicates);
-    if (a.cc_errors) atomicAdd(&d->cc_errors, a.cc_errors);
-    if (a.scrambled) atomicAdd(&d->scrambled_packets, a.scrambled);
-    if (a.malformed) atomicAdd(&d->malformed_packets, a.malformed);
-}
-// counters summed per thread and slot run
-struct EsAcc {
-    EsCnt c; int slot; EsCnt* dst;
-    __device__ EsAcc(EsCnt* d) : c(es_cnt_zero()), slot(-1), dst(d) {}
-    __device__ void at(int s) { if (s != slot) { done(); c = es_cnt_zero(); slot = s; } }
-    __device__ void done() { if (slot >= 0) es_flush(&dst[slot], c); slot = -1; }
+    }
+    __device__ static bool synced(const EsState& st) { return st.synced != 0; }
+    __device__ static bool lost(const EsState& st) { return st.lost != 0; }
+    __device__ static void set_synced_lost(EsState& st, bool synced, bool lost) { st.synced = synced; st.lost = lost; }
+    __device__ static EsRow pes_row(int pid, int slot, int k, const EsPlan& pl, uint64_t es_pos, bool lost) { return es_pes_row(pid, slot, k, pl, es_pos, lost); }
 };
+typedef EsT::Shared EsShared;
+typedef EsStreamCall<EsCnt> EsCall;
+static_assert(sizeof(EsShared) % 16 == 0 && sizeof(EsShared::place) == ES_MAX_PACKETS * sizeof(uint16_t), "the packets behind it; an index per packet");
+// dynamic LDS: EsShared, srt[max_packets], exs[max_packets + 1] (32 bits each), rc[max_packets] (16 bits): 10 bytes per packet
+constexpr size_t es_lds_bytes(int max_packets) { return sizeof(EsShared) + ((size_t)max_packets * 2 + 2) * sizeof(uint32_t) + (((size_t)max_packets + 1) & ~(size_t)1) * sizeof(uint16_t); }
+static_assert(es_lds_bytes(ES_MAX_PACKETS) <= 64 * 1024, "dynamic LDS of a workgroup");        // 51.3 KiB
+
+constexpr uint16_t ES_NO_PREV = 0xFFFF;
 
 // the last 8 bytes of packet k, the packet's last byte in the low byte: two dwords that lie inside the packet
 __device__ inline uint64_t es_packet_end(const uint8_t* __restrict__ ts, int k) {
@@ -134,6 +99,10 @@ __device__ inline int es_scan_segment(const uint8_t* __restrict__ ts, int k, int
     return nrows;
 }
 
+// The kernel keeps its own text of the set-up, phases A-E and the skeleton of G, which aud_kernel takes from es_stream.h (EsStream):
+// written on EsStream, with all but identical instructions, this kernel took 0.80 ms where this text takes 0.70 ms (4096 streams x 309
+// packets), and the cause was not found.  A change to either text belongs in the other too; the word predicates,
+// the accumulator, the LDS struct, the call record and the host half are es_stream.h's
 __global__ void __launch_bounds__(ES_WG) es_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nbytes, int max_packets, int max_rows,
                                                    const int32_t* __restrict__ watch, const int32_t* __restrict__ codec, EsState* __restrict__ state,
                                                    int64_t* __restrict__ pos, EsRow* __restrict__ rows_g, EsCall* __restrict__ call) {
@@ -167,9 +136,9 @@ __global__ void __launch_bounds__(ES_WG) es_kernel(const uint8_t* const* __restr
         // C: the continuity verdicts
         unsigned dupm, gapm;
         pw_verdicts(srt, j0, j1, sh.start, [&](int slot) { return sh.ss[slot].cc; }, sh.wsum, sh.ncc,
-                    [&](int slot, const PwPk& pk) { es_flush_pk(&sh.cnt[slot], pk); }, &dupm, &gapm);
+                    [&](int slot, const PwPk& pk) { pw_flush_pk(&sh.cnt[slot], pk); }, &dupm, &gapm);
         __syncthreads();                                         // every counter has been read: the verdicts take their bits
-        EsAcc acc(sh.cnt);
+        EsStreamAcc<EsT> acc(sh.cnt);
         // D: the starts: valid or not, and their segments
         int last_start = -1;
         for (int j = j0; j < j1; ++j) {
@@ -330,38 +299,11 @@ __global__ void __launch_bounds__(ES_WG) es_kernel(const uint8_t* const* __restr
 
 }  // namespace s2
 
-// the host half is the watched-PID bank's (watch_bank.h); here what is the bank's own
-struct EsBankD {
-    static constexpr int SLOTS = ES_SLOTS, MAX_PACKETS = ES_MAX_PACKETS;
-    typedef EsState State; typedef EsRow Row; typedef EsCall Call; typedef EsHostStream HostStream;
-    typedef dvbs2gpu_es_stats Stats; typedef dvbs2gpu_es_stream_stats StreamStats;
-    static constexpr int SUMS = ES_COUNTERS;           // every word of dvbs2gpu_es_stats is a counter
+// the host half is the watched-PID bank's (watch_bank.h) with what es_stream.h adds for a bank with a codec per slot; here what is the bank's own
+struct EsBankD : EsStreamBankD<EsBankD, EsT, es_kernel, es_lds_bytes, ES_COUNTERS> {
+    typedef EsHostStream HostStream; typedef dvbs2gpu_es_stats Stats; typedef dvbs2gpu_es_stream_stats StreamStats;
     static constexpr StreamStats NO_STREAM_STATS = {};
-    typedef int32_t Config;                            // the codec, per slot
-    static constexpr int CONFIGS = ES_SLOTS;
-    static constexpr Config NO_CONFIG = ES_NONE;
     static constexpr const char *BANK = "ES bank: ", *CNAME = "dvbs2gpu_es", *ALLOC = "hipMalloc(es)";
-
-    // one stream's call into its statistics; `n` packets came
-    static void account(WatchBank<EsBankD>& b, int i, int n, const EsCallHead& head, const EsCnt* c) {
-        dvbs2gpu_es_stream_stats& ss = b.sstats[i];
-        for (int s = 0; s < ES_SLOTS; ++s) {
-            if (!c[s].packets) continue;                   // (no packet of the slot's PID came: every counter is 0)
-            const int32_t* a = reinterpret_cast<const int32_t*>(&c[s]);
-            int64_t* d = reinterpret_cast<int64_t*>(&b.stats[(size_t)i * ES_SLOTS + s]);
-            for (int k = 0; k < ES_COUNTERS; ++k) d[k] += a[k];
-        }
-        ss.packets += n;
-        if (head.rows > b.max_rows) ss.rows_dropped += head.rows - b.max_rows;
-        b.total[i] = head.rows;
-        b.nrows[i] = head.rows < b.max_rows ? head.rows : b.max_rows;
-    }
-    static void launch(WatchBank<EsBankD>& b, const TsBankArgs& a, hipStream_t st) {
-        const size_t lds = es_lds_bytes(b.max_packets);        // <= 51.3 KiB
-        hipLaunchKernelGGL(es_kernel, dim3(b.nstreams), dim3(ES_WG), lds, st, a.in(b.d_args), a.nbytes(b.d_args), b.max_packets, b.max_rows, b.d_watch, b.d_cfg, b.d_state,
-                           b.d_pos, b.d_rows, b.d_call);
-    }
-    static void fix_stream_stats(StreamStats*) {}
 };
 struct dvbs2gpu_es : WatchBank<EsBankD> {};
 
@@ -373,14 +315,7 @@ int dvbs2gpu_es_create_host(int nstreams, int max_packets, int max_rows, dvbs2gp
 int dvbs2gpu_es_reset(dvbs2gpu_es* b) { return watch_reset(b); }
 
 int dvbs2gpu_es_set_watch(dvbs2gpu_es* b, int stream, int slot, int pid, int codec) {
-    if (!watch_slot_ok(b, stream, slot, pid)) return DVBS2GPU_ERR_ARG;
-    if (pid >= 0 && (codec < ES_MPEG2 || codec > ES_H265)) { g_err = "ES bank: the codec is DVBS2GPU_ES_MPEG2, _H264 or _H265"; return DVBS2GPU_ERR_ARG; }
-    if (const int e = watch_set_watch(b, stream, slot, pid)) return e;
-    const size_t at = (size_t)stream * ES_SLOTS + slot;
-    b->cfg[at] = pid >= 0 ? codec : ES_NONE;
-    if (b->ctx) return watch_upload_config(b, at);
-    b->host[stream].codec[slot] = b->cfg[at];
-    return 0;
+    return es_stream_set_watch(b, stream, slot, pid, codec, ES_H265, "ES bank: the codec is DVBS2GPU_ES_MPEG2, _H264 or _H265");
 }
 
 int dvbs2gpu_es_process_batch(dvbs2gpu_es* b, const uint8_t* const* d_ts, const int* nbytes, int* out_rows, void* stream) {

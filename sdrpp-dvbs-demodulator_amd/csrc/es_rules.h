@@ -5,8 +5,9 @@
 // (es_classify) and what a row adds to its slot's counters.  The PES start itself is pes_start() of pes_rules.h, not restated here.
 //
 // The sequential form -- EsHostStream::run, packet by packet and byte by byte -- IS the definition; every other form must give its
-// rows, counters and state for every cut of a stream into calls.  Start-code and header syntax as remembered from ISO/IEC 13818-1,
-// 13818-2, 14496-10 and 23008-2; pinned to no vector of theirs.
+// rows, counters and state for every cut of a stream into calls.  Its packet walk (EsHostWalk) and the twelve counters in front of
+// the bank's own (EsStreamCnt) are stated here for the audio bank too (aud_rules.h).  Start-code and header syntax as remembered from
+// ISO/IEC 13818-1, 13818-2, 14496-10 and 23008-2; pinned to no vector of theirs.
 // Standard headers only: the host tests compile this file with a plain C++ compiler.
 #pragma once
 #include "pes_rules.h"
@@ -113,14 +114,19 @@ ES_HD inline EsPlan es_packet_plan(const uint32_t* w, int L, int tsc, int pusi, 
     return p;
 }
 
-// what one call adds to a slot's statistics, in the order of dvbs2gpu_es_stats
-struct EsCnt {
+// what one call adds to a slot's statistics.  The twelve counters that every bank over an elementary stream begins with (the ES bank
+// here, the audio bank in aud_rules.h), in the order of dvbs2gpu_es_stats and dvbs2gpu_aud_stats
+struct EsStreamCnt {
     int32_t packets, payload_bytes, es_bytes, bytes_unsynced, duplicates, cc_errors, scrambled_packets, malformed_packets, resets, pes_starts, pes_invalid,
-            split_headers, codes, pictures, pictures_i, pictures_p, pictures_b, key_pictures, sequences, gops, params, auds, ends, slices, other_codes, bad_codes;
+            split_headers;
 };
-constexpr int ES_COUNTERS = 26;
-static_assert(sizeof(EsCnt) == ES_COUNTERS * sizeof(int32_t), "counter order");
-ES_HD inline EsCnt es_cnt_zero() { return EsCnt{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; }
+// behind them the ES bank's own, in the order of dvbs2gpu_es_stats
+struct EsCnt : EsStreamCnt {
+    int32_t codes, pictures, pictures_i, pictures_p, pictures_b, key_pictures, sequences, gops, params, auds, ends, slices, other_codes, bad_codes;
+};
+constexpr int ES_STREAM_COUNTERS = 12, ES_COUNTERS = 26;
+static_assert(sizeof(EsStreamCnt) == ES_STREAM_COUNTERS * sizeof(int32_t) && sizeof(EsCnt) == ES_COUNTERS * sizeof(int32_t), "counter order");
+ES_HD inline EsCnt es_cnt_zero() { return EsCnt{}; }
 // a code into its slot's counters (no run-time index: the kernel keeps *c in registers)
 ES_HD inline void es_cnt_code(EsCnt* c, const EsCode& e) {
     ++c->codes;
@@ -130,7 +136,7 @@ ES_HD inline void es_cnt_code(EsCnt* c, const EsCode& e) {
     c->pictures_b += e.unit == ES_PICTURE && e.detail == ES_PIC_B; c->key_pictures += e.key;
 }
 // a start into its slot's counters
-ES_HD inline void es_cnt_start(EsCnt* c, const EsPlan& p) {
+ES_HD inline void es_cnt_start(EsStreamCnt* c, const EsPlan& p) {
     ++c->pes_starts; c->pes_invalid += !p.valid; c->split_headers += (p.row_flags & ES_SPLIT_HEADER) != 0;
 }
 ES_HD inline EsRow es_pes_row(int pid, int slot, int k, const EsPlan& p, uint64_t es_count, bool lost) {
@@ -141,35 +147,44 @@ ES_HD inline EsRow es_code_row(int pid, int slot, int k, const EsCode& e, uint32
     return EsRow{(uint16_t)pid, (uint8_t)slot, (uint8_t)e.unit, (uint8_t)code, (uint8_t)e.detail, (uint16_t)((e.key ? ES_KEY : 0) | (lost ? ES_RESYNC : 0)), k, head,
                  es_offset, PES_NO_TS, PES_NO_TS, 0};
 }
-// the header of a stream's call record; the slots' EsCnt follow it (EsCall in es.hip)
+// the header of a stream's call record; the slots' counters follow it (EsStreamCall in es_stream.h)
 struct EsCallHead { int32_t rows, pad[3]; };
 
 // ------------------------------------------------------------------------------------------------- the sequential definition
-struct EsHostStream {
+// The packet walk of a bank over the elementary streams of watched PIDs, stated once for EsHostStream below and AudHostStream
+// (aud_rules.h): everything around what the bank does with a reset, a start and the bytes of a segment.  State has es_count, tail,
+// have and cc; Cnt begins with EsStreamCnt.  Self supplies
+//   static bool synced(const State&)                 the slot's synced bit in front of the packet
+//   static void stream_reset(State&)                 a reset: the window is forgotten, the slot is lost (and what the bank forgets with it)
+//   void start(k, s, pl, max_rows)                   a start: its PES row, the synced bit, what a valid start does to the bank's own state
+//                                                    (an invalid one is followed by a reset)
+//   void segment(k, s, pl, pay, &win, &since, max_rows)   the segment pay[pl.seg_off ..], byte by byte into the window (win, since)
+template <typename Self, typename State, typename Cnt, typename Row>
+struct EsHostWalk {
     int32_t watch[ES_SLOTS];                                // -1: the slot watches nothing
     int32_t codec[ES_SLOTS];
-    EsState slot[ES_SLOTS];
+    State slot[ES_SLOTS];
     int64_t packets = 0;                                    // the position of the next call's first packet
     // of the last call
-    std::vector<EsRow> rows;                                // the first max_rows
-    EsCnt cnt[ES_SLOTS];
+    std::vector<Row> rows;                                  // the first max_rows
+    Cnt cnt[ES_SLOTS];
     EsCallHead head = {0, {0, 0, 0}};
 
-    EsHostStream() {
-        for (int s = 0; s < ES_SLOTS; ++s) { watch[s] = -1; codec[s] = ES_NONE; clear_slot(s); cnt[s] = es_cnt_zero(); }
+    EsHostWalk() {
+        for (int s = 0; s < ES_SLOTS; ++s) { watch[s] = -1; codec[s] = 0; clear_slot(s); cnt[s] = Cnt{}; }
     }
-    void clear_slot(int s) { slot[s] = EsState{0, 0, 0, 0, 0, 0, {0, 0, 0, 0}}; }
+    void clear_slot(int s) { slot[s] = State{}; }
     void reset() {
         for (int s = 0; s < ES_SLOTS; ++s) clear_slot(s);
         packets = 0; rows.clear(); head = {0, {0, 0, 0}};
     }
-    void emit(const EsRow& r, int max_rows) { if (head.rows++ < max_rows) rows.push_back(r); }
-    static void scanner_reset(EsState& st) { st.have = 0; st.tail = 0; st.lost = 1; }
+    void emit(const Row& r, int max_rows) { if (head.rows++ < max_rows) rows.push_back(r); }
     // one call: n packets
     void run(const uint8_t* ts, int n, int max_rows) {
+        Self& self = static_cast<Self&>(*this);
         rows.clear();
         head = {0, {0, 0, 0}};
-        for (int s = 0; s < ES_SLOTS; ++s) cnt[s] = es_cnt_zero();
+        for (int s = 0; s < ES_SLOTS; ++s) cnt[s] = Cnt{};
         for (int k = 0; k < n; ++k) {
             const uint8_t* p = ts + (size_t)k * TSMON_TS;
             const TsmonHdr h = tsmon_parse(p);
@@ -177,8 +192,8 @@ struct EsHostStream {
             int s = 0;
             while (s < ES_SLOTS && watch[s] != h.pid) ++s;
             if (s == ES_SLOTS) continue;
-            EsState& st = slot[s];
-            EsCnt& c = cnt[s];
+            State& st = slot[s];
+            Cnt& c = cnt[s];
             ++c.packets;
             const int v = tsmon_step(&st.cc, h.afc, h.cc, h.di);
             if (v == TSMON_DUPLICATE) { ++c.duplicates; continue; }
@@ -188,7 +203,7 @@ struct EsHostStream {
             if (L <= 0) {
                 const bool malformed = L == 0;
                 c.malformed_packets += malformed;
-                if (cont || malformed) { ++c.resets; scanner_reset(st); }
+                if (cont || malformed) { ++c.resets; Self::stream_reset(st); }
                 continue;
             }
             c.payload_bytes += L;
@@ -196,33 +211,46 @@ struct EsHostStream {
             uint32_t w[5] = {0, 0, 0, 0, 0};
             const uint8_t* pay = p + TSMON_TS - L;
             if (h.pusi && !h.tsc) for (int i = 0; i < L && i < PES_HEAD_BYTES; ++i) w[i >> 2] |= (uint32_t)pay[i] << (8 * (i & 3));
-            const EsPlan pl = es_packet_plan(w, L, h.tsc, h.pusi, cont, st.synced != 0);
-            if (pl.reset) scanner_reset(st);
+            const EsPlan pl = es_packet_plan(w, L, h.tsc, h.pusi, cont, Self::synced(st));
+            if (pl.reset) Self::stream_reset(st);
             if (pl.start) {
-                emit(es_pes_row(h.pid, s, k, pl, st.es_count, st.lost != 0), max_rows);
-                st.lost = 0;
+                self.start(k, s, pl, max_rows);
                 es_cnt_start(&c, pl);
-                st.synced = pl.valid;
-                if (!pl.valid) scanner_reset(st);
+                if (!pl.valid) Self::stream_reset(st);
             }
             c.resets += pl.reset || (pl.start && !pl.valid);
             c.bytes_unsynced += pl.unsynced_bytes;
             c.es_bytes += pl.seg_len;
             uint64_t win = st.tail;
             uint32_t since = st.have;
-            for (int i = 0; i < pl.seg_len; ++i) {
-                uint32_t code, hd;
-                if (es_scan_byte(&win, &since, pay[pl.seg_off + i], &code, &hd)) {
-                    const EsCode e = es_classify(codec[s], code, hd);
-                    es_cnt_code(&c, e);
-                    if (e.unit < ES_UNITS) { emit(es_code_row(h.pid, s, k, e, code, hd, st.es_count + i - 7, st.lost != 0), max_rows); st.lost = 0; }
-                }
-            }
+            self.segment(k, s, pl, pay, &win, &since, max_rows);
             st.es_count += pl.seg_len;
             st.have = (uint8_t)(since < 7 ? since : 7);
             st.tail = st.have == 7 ? win & ES_TAIL_MASK : win & ((1ull << (8 * st.have)) - 1);
         }
         packets += n;
+    }
+};
+
+struct EsHostStream : EsHostWalk<EsHostStream, EsState, EsCnt, EsRow> {
+    static bool synced(const EsState& st) { return st.synced != 0; }
+    static void stream_reset(EsState& st) { st.have = 0; st.tail = 0; st.lost = 1; }
+    void start(int k, int s, const EsPlan& pl, int max_rows) {
+        EsState& st = slot[s];
+        emit(es_pes_row(watch[s], s, k, pl, st.es_count, st.lost != 0), max_rows);
+        st.lost = 0;
+        st.synced = pl.valid;
+    }
+    void segment(int k, int s, const EsPlan& pl, const uint8_t* pay, uint64_t* win, uint32_t* since, int max_rows) {
+        EsState& st = slot[s];
+        for (int i = 0; i < pl.seg_len; ++i) {
+            uint32_t code, hd;
+            if (es_scan_byte(win, since, pay[pl.seg_off + i], &code, &hd)) {
+                const EsCode e = es_classify(codec[s], code, hd);
+                es_cnt_code(&cnt[s], e);
+                if (e.unit < ES_UNITS) { emit(es_code_row(watch[s], s, k, e, code, hd, st.es_count + i - 7, st.lost != 0), max_rows); st.lost = 0; }
+            }
+        }
     }
 };
 

@@ -7,7 +7,7 @@
 // packets between two starts; and a start's timestamp step needs only the slot's previous start that had a PTS.
 //
 //   pes_kernel  one workgroup per stream, one launch per call.
-//     A-C  ts_watch.h, shared with the ES bank: the trusted packets of watched PIDs compacted into LDS as one 32-bit word each
+//     A-C  ts_watch.h, shared with the ES and audio banks: the trusted packets of watched PIDs compacted into LDS as one 32-bit word each
 //        (packet, slot, counter, payload length, payload, PUSI, scrambled, DI), sorted by slot, and tsmon_step's verdict per packet
 //        from the parity of its place in a run of equal counters.
 //     D  two prefix sums over the accepted packets in sorted order -- payload bytes; packets and GAP marks -- make every PES
@@ -78,16 +78,6 @@ __device__ inline void pes_flush(PesCnt* d, const PesCnt& a) {
     if (a.last_k >= 0) d->last_k = a.last_k;      // one lane per slot has it
 }
 
-// the packet counters of phase C, per thread and slot run
-__device__ inline void pes_flush_pk(PesCnt* d, const PwPk& a) {
-    atomicAdd(&d->packets, a.packets);
-    if (a.payload_bytes) atomicAdd(&d->payload_bytes, a.payload_bytes);
-    if (a.duplicates) atomicAdd(&d->duplicates, a.duplicates);
-    if (a.cc_errors) atomicAdd(&d->cc_errors, a.cc_errors);
-    if (a.scrambled) atomicAdd(&d->scrambled_packets, a.scrambled);
-    if (a.malformed) atomicAdd(&d->malformed_packets, a.malformed);
-}
-
 // dynamic LDS: PesShared, srt[max_packets], exb[max_packets + 1], exc[max_packets + 1] (32 bits each).  The compacted words lie in exb
 // until they are sorted into srt
 __global__ void __launch_bounds__(PES_WG) pes_kernel(const uint8_t* const* __restrict__ in, const int* __restrict__ nbytes, int max_packets, int max_rows,
@@ -122,7 +112,7 @@ __global__ void __launch_bounds__(PES_WG) pes_kernel(const uint8_t* const* __res
         // C: the continuity verdicts
         unsigned dupm, gapm;
         pw_verdicts(srt, j0, j1, sh.start, [&](int slot) { return sh.ss[slot].cc; }, sh.wsum, sh.ncc,
-                    [&](int slot, const PwPk& pk) { pes_flush_pk(&sh.cnt[slot], pk); }, &dupm, &gapm);
+                    [&](int slot, const PwPk& pk) { pw_flush_pk(&sh.cnt[slot], pk); }, &dupm, &gapm);
         __syncthreads();                                         // every counter has been read: the verdicts take their bits
         // D: the prefix sums over the accepted packets
         {

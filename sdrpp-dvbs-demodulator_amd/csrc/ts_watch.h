@@ -1,6 +1,7 @@
 // Shared by the banks that follow up to 16 watched PIDs per stream packet by packet with one workgroup per stream (pes.hip: the PES
-// packets; es.hip: the elementary streams): the first three phases of their kernels, which turn a call's packets into
-// one 32-bit word per trusted packet of a watched PID, sorted by slot, with the TS monitor's continuity verdict in it.
+// packets; es.hip and aud.hip through es_stream.h: the elementary streams): the first three phases of their kernels,
+// which turn a call's packets into one 32-bit word per trusted packet of a watched PID, sorted by slot, with the TS monitor's
+// continuity verdict in it.
 //     A  every packet's header is read once (ts_load_header, ts_bank.h) and its PID matched against the 16 watches.  The trusted
 //        packets of watched PIDs are compacted in input order into LDS, one word each: flags in a mask, ts_block_scan, scatter.
 //     B  the PCR bank's stable counting sort by slot; the words themselves are placed.
@@ -69,6 +70,16 @@ __device__ inline void pw_load_start(const uint8_t* __restrict__ ts, uint32_t e,
 
 // the packet counters of phase C, per thread and slot run
 struct PwPk { int packets, payload_bytes, duplicates, cc_errors, scrambled, malformed; };
+// into the slot's counters in LDS (Cnt: PesCnt, EsCnt, AudCnt: each has the six fields)
+template <typename Cnt>
+__device__ inline void pw_flush_pk(Cnt* d, const PwPk& a) {
+    atomicAdd(&d->packets, a.packets);
+    if (a.payload_bytes) atomicAdd(&d->payload_bytes, a.payload_bytes);
+    if (a.duplicates) atomicAdd(&d->duplicates, a.duplicates);
+    if (a.cc_errors) atomicAdd(&d->cc_errors, a.cc_errors);
+    if (a.scrambled) atomicAdd(&d->scrambled_packets, a.scrambled);
+    if (a.malformed) atomicAdd(&d->malformed_packets, a.malformed);
+}
 
 // A: the watched packets of ts[0 .. n), compacted in input order into rec -> how many.  w: the 16 watches (LDS).  Every thread of the
 // workgroup calls it, whatever n is

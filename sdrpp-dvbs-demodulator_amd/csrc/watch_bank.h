@@ -1,7 +1,8 @@
 // The watched-PID bank: what the banks that judge up to 16 watched PIDs per stream and write one row table per stream (pcr.hip: the
 // PCRs; pes.hip: the PES packets; es.hip: the video elementary streams; aud.hip: the audio frames) are on the host
-// around their kernels and rules, stated once: the handle's members and the bodies of the C functions.  The kernels stay in the .hip files (the device phases that
-// PES and ES share are ts_watch.h), the rules and the sequential host streams in *_rules.h.  A bank supplies a description D:
+// around their kernels and rules, stated once: the handle's members and the bodies of the C functions.  The kernels stay in the .hip
+// files (the device phases that PES, ES and audio share are ts_watch.h; what ES and audio share beyond them, on the device and in
+// their descriptions here, is es_stream.h), the rules and the sequential host streams in *_rules.h.  A bank supplies a description D:
 //   SLOTS, MAX_PACKETS                watched PIDs per stream; packets per stream and call (4096: the text of create)
 //   State, Row, Call, HostStream      the slot's carried state, the row, the call record (head + cnt[SLOTS]), the sequential stream
 //   Stats, StreamStats, SUMS          the public statistics; the first SUMS 64-bit words of Stats add up over slots, the rest are maxima
