@@ -209,14 +209,24 @@ int dvbs2gpu_get_stage_times(dvbs2gpu_ctx* ctx, dvbs2gpu_stage_times* out);
  * Gardner delay line + PCL, RRC delay line, /2 decimator phase, PL-sync buffer and state machine, PLL and
  * PLHDR loops).  Not re-entrant per handle (the reference guards process() with ctrlMtx the same way).
  *
- * cfg mirrors the arguments of DVBS2Demod::init (module_dvbs2_demod.cpp:7-30) in the same units. */
+ * cfg mirrors the arguments of DVBS2Demod::init (module_dvbs2_demod.cpp:7-30) in the same units.
+ *
+ * ACCEPTED CONFIGURATIONS (one rule, csrc/rx_cfg_rules.h; everything else is DVBS2GPU_ERR_ARG from create, with a message that names the bound):
+ *   rrc_taps 1 .. 129;  rrc_alpha within [0, 1] (0 = sinc);  samplerate, symbolrate positive and finite, their ratio positive and finite, and every
+ *   RRC tap they yield finite;
+ *   clock_mu_gain, clock_omega_gain, agc_rate, loop_bw, fll_bw finite;
+ *   0 <= omega_rel_limit <= 0.05  and  1 - omega_rel_limit - |clock_mu_gain| / 2 >= 16/17 + 1e-6.
+ * The last bound is the timing recovery's: of the two outputs per symbol one moves the loop by freq + clock_mu_gain * e (|e| <= 1), the other by freq, freq
+ * within 1 -+ omega_rel_limit, so n samples yield fewer than n / (1 - omega_rel_limit - |clock_mu_gain| / 2) + 2 outputs, and the engine holds n + n/16 + 128
+ * of them; it also keeps every step at 0, 1 or 2 samples and every period's outputs inside the resolvers' lists.  The plugin's gains (0.0176) pass up to
+ * omega_rel_limit 0.05; at the plugin's 0.02, |clock_mu_gain| up to 0.0776. */
 typedef struct dvbs2gpu_demod_cfg {
     double symbolrate, samplerate;       /* only their ratio matters (RRC taps); the plugin uses samplerate = 2*symbolrate */
     float agc_rate, rrc_alpha;
     int32_t rrc_taps;
     float loop_bw, fll_bw;
-    float clock_omega_gain, clock_mu_gain, omega_rel_limit;   /* gains, agc_rate and the bandwidths must be finite (DVBS2GPU_ERR_ARG otherwise):
-                                          * the timing-recovery kernels evaluate PCL::advance(0) as "frequency unchanged" */
+    float clock_omega_gain, clock_mu_gain, omega_rel_limit;   /* (see ACCEPTED CONFIGURATIONS above; finite gains: the timing-recovery kernels
+                                          * evaluate PCL::advance(0) as "frequency unchanged") */
     int32_t modcod, shortframes, pilots;
     float sof_threshold;                 /* stored, unused in CCM mode -- as in the reference (dvbs2_pl_sync.cpp:140-142); ACM/VCM mode:
                                           * minimum SOF quality of a frame start */
@@ -298,7 +308,10 @@ int dvbs2gpu_demod_get_frame_positions(dvbs2gpu_demod* d, int64_t* h_out, int ca
 /* Debug taps of the last process call (device->host copies; for parity tests and the constellation
  * display callback d_handler, module_dvbs2_demod.cpp:337).  which: 0 = 1-sps symbols entering PL sync,
  * 1 = aligned raw PLFRAMEs, 2 = PLL output, (complex64, count in complex samples); 3 = LLRs (int8).
- * Returns the element count; copies at most cap elements when h_dst != NULL. */
+ * Returns the element count; copies at most cap elements when h_dst != NULL.
+ * Taps 2 and 3 lie in the context's per-call scratch: they are valid until the next call on the context, and in a batch whose configuration
+ * groups run one after another (streams that differ in their front-end settings) they are those of the LAST group only -- the handles of
+ * the other groups report 0 elements for them.  Taps 0 and 1, the statistics and the output are every handle's own. */
 int dvbs2gpu_demod_get_tap(dvbs2gpu_demod* d, int which, void* h_dst, int cap);
 
 /* Signal quality per frame (own extension; off by default).  With quality on, every frame the handle's front end
@@ -429,7 +442,14 @@ int dvbs2gpu_forney_deinterleave_batch(dvbs2gpu_forney* h, const uint8_t* d_in, 
  * including vit.process: demod::QPSK_ALT (FastAGC, band-edge FLL, RRC, COMPLEX_FD timing recovery, Costas<4>;
  * common/dsp/demod/qpsk_alt.cpp:136-144), DVBSymToSoftBlock and Viterbi_DVBS, for `nstreams` independent streams.
  * The output of a call is what DVBSVitBlock::process hands to the TS deframer: decoded bits, one per byte (0 bytes while
- * the decoder is not locked).  cfg mirrors the arguments of DVBSDemod::init (module_dvbs_demod.cpp:9) in the same units. */
+ * the decoder is not locked).  cfg mirrors the arguments of DVBSDemod::init (module_dvbs_demod.cpp:9) in the same units.
+ *
+ * ACCEPTED CONFIGURATIONS (csrc/rx_cfg_rules.h; everything else is DVBS2GPU_ERR_ARG from create), with sps = samplerate / symbolrate:
+ *   rrc_taps 65;  rrc_alpha within [0, 1];  samplerate and symbolrate within [1, 2^31) (the FLL's band-edge filters take them as ints);
+ *   all gains and bandwidths finite;  sps <= 64;  0 <= omega_rel_limit <= 0.25;  sps * (1 - omega_rel_limit) >= 1.5;
+ *   sps * (1 - omega_rel_limit) - |clock_mu_gain| >= 1.3.
+ * The timing loop takes one symbol per freq + clock_mu_gain * e samples (|e| <= 1, freq within sps * (1 -+ omega_rel_limit)): the last bound keeps a
+ * 256-sample tile of the kernel at 198 symbols or fewer (it stages 200), and the symbol and soft-bit buffers are sized from the same smallest step. */
 typedef struct dvbs2gpu_dvbs_cfg {
     double symbolrate, samplerate;       /* the plugin uses samplerate = 2*symbolrate (main.cpp:139) */
     float agc_rate, rrc_alpha;

@@ -921,7 +921,9 @@ void S2Rx::vcm_walk(uint8_t* out, int out_cap, int* outcnt) {
 
 int S2Rx::process(int count, const cf* in, uint8_t* out, int out_cap) {
     dbg_symbols.clear(); dbg_frames.clear(); dbg_pll.clear(); dbg_llr.clear(); dbg_stats.clear();
-    work1.resize(count + 16); work2.resize(count + 1024);
+    // (the timing loop's outputs: fewer than count / (1 - omega_rel_limit - |clock_mu_gain| / 2) + 2 -- up to count * 17/16 in a configuration the engine
+    //  accepts, csrc/rx_cfg_rules.h; an error held at its clamp gets there, count + 1024 was the default gains' bound)
+    work1.resize(count + 16); work2.resize(2 * (size_t)count + 1024);
     agc(count, in, work1.data());
     nco(count, work1.data(), work1.data());
     int n = gardner(count, work1.data(), work2.data());

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "s2_rx.h"
 #include "scratch_layout.h"
+#include "rx_cfg_rules.h"
 #include "dev_buf.h"
 #include <type_traits>
 
@@ -165,7 +166,7 @@ struct dvbs2gpu_ctx {
     s2::DevBuf<float> d_gardner_bank;
     s2::PlTables pl{};
     std::map<int, s2::ConstelTables> constel; // by modcod (gammas depend on it)
-    std::map<int, s2::DevBuf<float>> rrc;           // by ntaps*1000 + round(alpha*100) (Ts = 2)
+    std::map<s2::rxcfg::RrcKey, s2::DevBuf<float>> rrc;   // by the exact (ntaps, alpha, Ts) of make_rrc_taps (rx_cfg_rules.h)
     // (ws_rx.slot_stats also holds frontend_prepass's work table -- a pre-passed group is never staged; ws_rx.deliver also collects the jobs left in slots without a group)
     s2::GroupWs ws_rx;
     // ACM/VCM mode (s2_demod.hip): what every PLS code means + the constellations it points to, on the device; per-call scratch
@@ -266,7 +267,6 @@ int get_bch(dvbs2gpu_ctx* ctx, int m, int t, BchDeviceCode** out);
 int get_prbs(dvbs2gpu_ctx* ctx);
 // LLR -> BBFRAME for nframes frames of one code; all pointers device
 std::vector<float> make_polyphase_bank(int phases, int taps_per_phase);
-std::vector<float> make_rrc_taps(int count, double beta, double Ts);
 int get_rrc(dvbs2gpu_ctx* ctx, int ntaps, float alpha, double Ts, float** out);
 void critically_damped(float bw, float* alpha, float* beta);
 int fec_run(dvbs2gpu_ctx* ctx, const FecParams& f, const int8_t* d_llr, int nframes, int max_trials, int force, uint8_t* d_bbframes,

@@ -93,21 +93,18 @@ void dvbs2gpu_dvbs_demod_default_cfg(dvbs2gpu_dvbs_cfg* c) {   // main.cpp:64-73
 
 int dvbs2gpu_dvbs_demod_create(dvbs2gpu_ctx* ctx, const dvbs2gpu_dvbs_cfg* cfg, int nstreams, int max_samples, dvbs2gpu_dvbs_demod** out) {
     if (!ctx || !cfg || !out || nstreams <= 0 || max_samples <= 0) return DVBS2GPU_ERR_ARG;
-    if (cfg->rrc_taps != 65) { last_error() = "the DVB-S front end is built for the reference's 65-tap filters (RRC_TAP_COUNT)"; return DVBS2GPU_ERR_ARG; }
-    if (!(cfg->samplerate > 0) || !(cfg->symbolrate > 0)) return DVBS2GPU_ERR_ARG;
-    // the timing loop writes one symbol per `freq` input samples, freq >= omega * (1 - omega_rel_limit): the symbol / soft buffers are
-    // sized from that bound, and the kernel stages at most FD_TILE/2 + 72 symbols per 256-sample tile (omega_min >= 1.5 keeps it at 171)
+    // what a configuration may be: rx_cfg_rules.h.  The timing loop writes one symbol per a >= a_min = omega (1 - omega_rel_limit) - |clock_mu_gain| input
+    // samples: the symbol / soft buffers are sized from that bound, and the kernel stages at most FD_TILE/2 + 72 symbols per 256-sample tile
     {
-        const double omega_min = (cfg->samplerate / cfg->symbolrate) * (1.0 - (double)cfg->omega_rel_limit);
-        if (!(cfg->omega_rel_limit >= 0.f) || !(cfg->omega_rel_limit <= 0.25f) || !(omega_min >= 1.5) || !(cfg->samplerate / cfg->symbolrate <= 64.0)) {
-            last_error() = "samplerate/symbolrate * (1 - omega_rel_limit) must be >= 1.5 (and the ratio <= 64, omega_rel_limit in [0, 0.25])";
-            return DVBS2GPU_ERR_ARG;
-        }
+        const char* why = rxcfg::dvbs_loop_refusal(cfg->samplerate, cfg->symbolrate, cfg->rrc_taps, cfg->omega_rel_limit, cfg->clock_mu_gain, cfg->clock_omega_gain,
+                                                   cfg->agc_rate, cfg->loop_bw, cfg->fll_bw);
+        if (!why) why = rxcfg::rrc_refusal(cfg->rrc_taps, cfg->rrc_alpha, cfg->samplerate, cfg->symbolrate);
+        if (why) { last_error() = why; return DVBS2GPU_ERR_ARG; }
     }
     HIP_TRY(hipSetDevice(ctx->device));
     std::unique_ptr<dvbs2gpu_dvbs_demod> d(new dvbs2gpu_dvbs_demod());
     d->ctx = ctx; d->cfg = *cfg; d->nstreams = nstreams; d->max_samples = max_samples;
-    d->sym_cap = (size_t)((double)max_samples / ((cfg->samplerate / cfg->symbolrate) * (1.0 - (double)cfg->omega_rel_limit))) + 130;
+    d->sym_cap = rxcfg::dvbs_sym_cap(max_samples, rxcfg::dvbs_a_min(cfg->samplerate / cfg->symbolrate, cfg->omega_rel_limit, cfg->clock_mu_gain));
     d->soft_cap = (size_t)2 * d->sym_cap + 2 * DVBS_SOFT_BLOCK + 128;
     d->max_blocks = (int)(d->soft_cap / DVBS_SOFT_BLOCK);
     const float PI_F = 3.14159265358979323846f;

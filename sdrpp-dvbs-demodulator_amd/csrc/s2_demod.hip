@@ -34,22 +34,7 @@ namespace {
 //  oracle builds the same tables independently in oracle/s2chain.cpp)
 }  // namespace
 namespace s2 {
-std::vector<float> make_rrc_taps(int count, double beta, double Ts) {
-    const double PI = 3.14159265358979323846, SQ2 = 1.41421356237309504880;
-    double limit = Ts / (4.0 * beta), half = (double)count / 2.0;
-    std::vector<float> taps(count);
-    for (int i = 0; i < count; i++) {
-        double t = (double)i - half + 0.5, v;
-        if (t == 0.0) v = (1.0 + beta * (4.0 / PI - 1.0)) / Ts;
-        else if (t == limit || t == -limit)
-            v = ((1.0 + 2.0 / PI) * sin(PI / (4.0 * beta)) + (1.0 - 2.0 / PI) * cos(PI / (4.0 * beta))) * beta / (Ts * SQ2);
-        else
-            v = ((sin((1.0 - beta) * PI * t / Ts) + cos((1.0 + beta) * PI * t / Ts) * 4.0 * beta * t / Ts) /
-                 ((1.0 - (4.0 * beta * t / Ts) * (4.0 * beta * t / Ts)) * PI * t / Ts)) / Ts;
-        taps[i] = (float)v;
-    }
-    return taps;
-}
+// (make_rrc_taps: rx_cfg_rules.h)
 
 // gardner.cpp:154-159 (128 phases x 8 taps) and complex_fd.cpp:152-157 (256 x 256): Nuttall-windowed sinc, polyphase bank
 std::vector<float> make_polyphase_bank(int phases, int tpp) {
@@ -238,11 +223,12 @@ int get_constel(dvbs2gpu_ctx* ctx, const ModcodParams& mp, ConstelTables** out) 
 namespace s2 {
 int get_rrc(dvbs2gpu_ctx* ctx, int ntaps, float alpha, double Ts, float** out) {
     std::lock_guard<std::mutex> l(ctx->mtx);
-    int key = ntaps * 100000 + (int)lround(alpha * 1000) * 10 + (int)lround(Ts);
+    // the exact arguments of make_rrc_taps (rx_cfg_rules.h): a key that rounds them hands one configuration the taps of another
+    const rxcfg::RrcKey key = rxcfg::rrc_key(ntaps, alpha, Ts);
     auto it = ctx->rrc.find(key);
     if (it == ctx->rrc.end()) {
         DevBuf<float> d;
-        int rc = upload(make_rrc_taps(ntaps, alpha, Ts), d);
+        int rc = upload(rxcfg::make_rrc_taps(ntaps, alpha, Ts), d);
         if (rc) return rc;
         it = ctx->rrc.emplace(key, std::move(d)).first;
     }
@@ -288,6 +274,7 @@ struct dvbs2gpu_demod {
     const cf32* tap_pll = nullptr;           // into ctx workspace, valid until the next call on this context
     int tap_pll_stride = 0;                  // elements between the frames behind tap_pll (0: one frame behind the other; mixed batches keep every stream's frames in slots of the batch's longest PLFRAME)
     const int8_t* tap_llr = nullptr;
+    bool taps_gone = false;                  // a later configuration group of the same batch call has reused the workspace tap_pll / tap_llr point into: taps 2 and 3 report nothing
     std::vector<int> frame_len;              // ACM/VCM: PLFRAME length of each frame of the last call (CCM: empty = mp.plframe)
     long long tap_pll_count = -1, tap_llr_count = -1;   // ACM/VCM: element counts of the taps (frames differ in size)
     float nco_freq_host = 0.f;
@@ -302,15 +289,11 @@ constexpr int S2_SMALL_BANK = 256;       // streams up to which a batch is treat
 int demod_configure(dvbs2gpu_demod* d) {
     const dvbs2gpu_demod_cfg& c = d->cfg;
     if (!modcod_params(c.modcod, c.shortframes, c.pilots, &d->mp)) { last_error() = "unsupported MODCOD"; return DVBS2GPU_ERR_MODCOD; }
-    if (c.rrc_taps < 1 || c.rrc_taps > RRC_MAX_TAPS) { last_error() = "rrc_taps out of range"; return DVBS2GPU_ERR_ARG; }
-    if (!(c.samplerate > 0) || !(c.symbolrate > 0)) { last_error() = "samplerate and symbolrate must be positive"; return DVBS2GPU_ERR_ARG; }
-    // the Gardner loop (omega = 1 sample per output, module_dvbs2_demod.cpp:49) emits at most count / (1 - omega_rel_limit) samples; the
-    // timing-recovery scratch (count + count/16 + 128) and the symbol FIFO are sized for a limit of a few percent (main.cpp:73: 0.02)
-    if (!(c.omega_rel_limit >= 0.f) || !(c.omega_rel_limit <= 0.05f)) { last_error() = "omega_rel_limit must be within [0, 0.05]"; return DVBS2GPU_ERR_ARG; }
-    // (the kernels evaluate PCL::advance(0) as "freq unchanged" -- exact for finite gains only)
-    if (!std::isfinite(c.clock_mu_gain) || !std::isfinite(c.clock_omega_gain) || !std::isfinite(c.agc_rate) || !std::isfinite(c.loop_bw) || !std::isfinite(c.fll_bw)) {
-        last_error() = "loop gains must be finite"; return DVBS2GPU_ERR_ARG;
-    }
+    // what a configuration may be: rx_cfg_rules.h (the filter; the timing loop against the timing-recovery scratch, the resolvers' lists and rings)
+    static_assert(rxcfg::RRC_TAPS_MAX == RRC_MAX_TAPS, "rx_cfg_rules.h states the kernels' tap limit");
+    const char* why = rxcfg::rrc_refusal(c.rrc_taps, c.rrc_alpha, c.samplerate, c.symbolrate);
+    if (!why) why = rxcfg::s2_loop_refusal(c.omega_rel_limit, c.clock_mu_gain, c.clock_omega_gain, c.agc_rate, c.loop_bw, c.fll_bw);
+    if (why) { last_error() = why; return DVBS2GPU_ERR_ARG; }
     S2LoopCoefs& co = d->co;
     co.g_prio_duty = 0; co.post_prio = 0;       // (scheduling hints: set per call by the pipelined mode's balancer)
     co.g_form = 0; co.g_cand_skew = 0;            // (context options, set per call)
@@ -1476,8 +1459,9 @@ int frontend_prepass(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const 
 bool same_frontend(const dvbs2gpu_demod* a, const dvbs2gpu_demod* b) {
     const S2LoopCoefs &x = a->co, &y = b->co;
     return x.agc_rate == y.agc_rate && x.g_alpha == y.g_alpha && x.g_beta == y.g_beta && x.g_min_freq == y.g_min_freq && x.g_max_freq == y.g_max_freq &&
-           a->cfg.rrc_taps == b->cfg.rrc_taps && a->cfg.rrc_alpha == b->cfg.rrc_alpha && a->cfg.samplerate == b->cfg.samplerate &&
-           a->cfg.symbolrate == b->cfg.symbolrate;
+           // (the same filter = the same entry of the tap cache: one decision, get_rrc's)
+           rxcfg::rrc_key(a->cfg.rrc_taps, a->cfg.rrc_alpha, a->cfg.samplerate / a->cfg.symbolrate) ==
+               rxcfg::rrc_key(b->cfg.rrc_taps, b->cfg.rrc_alpha, b->cfg.samplerate / b->cfg.symbolrate);
 }
 
 // one configuration group of a batch: its streams' arguments in the group's order, how it runs, and (groups side by side) how it ended
@@ -1656,6 +1640,9 @@ int dvbs2gpu_demod_process_batch(dvbs2gpu_demod* const* demods, int n, const flo
             groups.push_back(std::move(idx));
         }
     }
+    for (int i = 0; i < n; ++i) demods[i]->taps_gone = false;
+    // groups that run one after another share the context's per-call scratch: the PLL output and the LLRs behind taps 2 and 3 are those of the LAST group only
+    auto taps_of_last_group_only = [&]() { for (size_t g = 0; g + 1 < groups.size(); ++g) for (int k : groups[g]) demods[k]->taps_gone = true; };
     const bool pipe = ctx->pipeline_fec != 0;
     bool any_vcm = false;
     for (int i = 0; i < n; ++i) any_vcm = any_vcm || demods[i]->cfg.acm_vcm != 0;
@@ -1706,6 +1693,7 @@ int dvbs2gpu_demod_process_batch(dvbs2gpu_demod* const* demods, int n, const flo
             if (!pipe) J.copy_out(out_bytes);
             ++slot;
         }
+        taps_of_last_group_only();
         return pipe ? collect_leftovers(slot) : 0;
     }
     // a small mixed batch with one front-end and loop configuration: ONE stage pipeline for all MODCODs (process_mixed)
@@ -1752,6 +1740,7 @@ int dvbs2gpu_demod_process_batch(dvbs2gpu_demod* const* demods, int n, const flo
         jobs.pop_back();                // (run in order, here)
         ++group_no;
     }
+    if (!side_by_side) taps_of_last_group_only();
     if (side_by_side) {
         // the MODCOD-dependent stages (PL sync, frame loops, demapper, FEC hand-over, delivery) of the groups are independent and
         // latency-bound: one host thread and HIP stream per group (the pre-pass above has completed; every group ends synchronised)
@@ -1806,6 +1795,7 @@ int dvbs2gpu_demod_process(dvbs2gpu_demod* d, int count, const float* h_iq, uint
     CallGuard guard(d->ctx);                    // the per-call workspaces are context-wide: one call at a time per context
     HIP_TRY(hipSetDevice(d->ctx->device));
     { int rq = ws_quiesce(d->ctx); if (rq) return rq; }
+    d->taps_gone = false;
     // staging buffers of the host-pointer entry point, allocated on first use
     if (!d->d_in) RC_TRY(d->d_in.alloc((size_t)d->max_samples, false, "hipMalloc(demod staging)"));
     if (!d->d_out) RC_TRY(d->d_out.alloc((size_t)(d->fifo_cap / 3330 + 2) * 8100, false, "hipMalloc(demod staging)"));
@@ -1886,6 +1876,7 @@ int dvbs2gpu_demod_get_tap(dvbs2gpu_demod* d, int which, void* h_dst, int cap) {
             return n;
         }
         case 2: {
+            if (d->taps_gone) return 0;
             if (d->tap_pll_count >= 0 && d->cfg.acm_vcm) {
                 int n = (int)d->tap_pll_count;
                 if (h_dst && n && d->tap_pll) HIP_TRY(hipMemcpy(h_dst, d->tap_pll, sizeof(cf32) * std::min(n, cap), hipMemcpyDeviceToHost));
@@ -1903,6 +1894,7 @@ int dvbs2gpu_demod_get_tap(dvbs2gpu_demod* d, int which, void* h_dst, int cap) {
             return n;
         }
         case 3: {
+            if (d->taps_gone) return 0;
             if (d->tap_llr_count >= 0 && d->cfg.acm_vcm) {
                 int n = (int)d->tap_llr_count;
                 if (h_dst && n && d->tap_llr) HIP_TRY(hipMemcpy(h_dst, d->tap_llr, (size_t)std::min(n, cap), hipMemcpyDeviceToHost));

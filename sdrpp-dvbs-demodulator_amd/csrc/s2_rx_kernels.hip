@@ -24,6 +24,7 @@
 #include "s2_rx.h"
 #include "../../include/dvbs2gpu_math.h"
 #include "s2_params.h"
+#include "rx_cfg_rules.h"
 
 namespace s2 {
 
@@ -148,6 +149,7 @@ constexpr int G_TILE = 64;     // samples per stream per staging tile
 constexpr int G_SPW = 8;       // streams per wave (8 lanes each)
 
 __device__ __forceinline__ size_t fe_scratch_offset(int n) { return (size_t)n + n / 16 + 128; }
+static_assert(s2::rxcfg::s2_fe_out_capacity(1000003) == 1000003 + 1000003 / 16 + 128, "rx_cfg_rules.h admits configurations against this capacity");
 
 // ---- serial per-sample recurrences, LANE = STREAM, with the memory traffic on a second wave ------------------------------
 // Workgroup = 2 waves for 64 streams.  Wave 0 runs the recurrences of its 64 streams out of LDS tiles (in place: the result
@@ -333,6 +335,7 @@ constexpr int G2_RING = 4 * G2_TILE;
 constexpr int G2_PITCH = G2_RING + 8 + 1;     // ring + mirror of its first 8 slots; odd pitch
 constexpr int G2_LIST = G2_TILE + 8;          // outputs of a stream per period: <= (G2_TILE + 3) / 0.96 (list entries beyond are refused by the loop bounds)
 constexpr int G2_SPT = (G_SPW * G2_TILE) / 64; // samples each producer lane stages per period
+static_assert(G2_TILE == s2::rxcfg::S2_PERIOD && G2_LIST == s2::rxcfg::S2_LIST, "rx_cfg_rules.h admits configurations against these sizes");
 
 __device__ __forceinline__ void lds_only_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
@@ -698,6 +701,7 @@ constexpr int GC_NR = GC_T + GC_LB;           // table rows: offsets base-2 .. b
 constexpr int GC_WN = 8;                      // arms per row: (reported arm - 3) .. (reported arm + 4), kept inside 0 .. 127
 constexpr int GC_LIST = GC_T + 8;             // outputs of a stream per period (bounded by the loops below)
 static_assert(GC_CS * GC_T == 64 && GC_RING == 128, "stager layout; a list word holds slot << 7 | arm in 14 bits");
+static_assert(GC_T == s2::rxcfg::S2_PERIOD && GC_LIST == s2::rxcfg::S2_LIST, "rx_cfg_rules.h admits configurations against these sizes");
 
 // pred_skew: added to the reported arm before the table's window is laid around it -- 0 in production; the tests skew the prediction so
 // that the resolver leaves its tables (partly, or with every symbol) and has to get the same bits from the fall-back path
@@ -2766,6 +2770,7 @@ __device__ __forceinline__ void fd_dot3_wave(const cf32 (&x)[4], const float* t0
 // phase moves slowly, so a window of FD_WROWS consecutive bank rows is kept in LDS and re-centred when the phase leaves it.
 constexpr int FD_TILE = 256;
 constexpr int FD_WROWS = 4;
+static_assert(FD_TILE == s2::rxcfg::FD_TILE_SAMPLES && FD_TILE / 2 + 72 == s2::rxcfg::FD_OCAP, "rx_cfg_rules.h admits configurations against these sizes");
 __global__ __launch_bounds__(64) void dvbs_fd_kernel(const DvbsStreamWork* __restrict__ work, DvbsLoopCoefs co,
                                                             const float* __restrict__ bank, int sub, int nsub) {
     __shared__ cf32 win[FD_TILE + FD_TAPS];      // [255 history][tile]
@@ -2785,7 +2790,7 @@ __global__ __launch_bounds__(64) void dvbs_fd_kernel(const DvbsStreamWork* __res
     for (int i = lane; i < FD_TAPS - 1; i += 64) win[i] = st->fd_hist[i];
     __syncthreads();
     __builtin_amdgcn_s_setprio(FE_PRIO);               // latency-critical serial loop (see agc_pc_kernel)
-    constexpr int OCAP = FD_TILE / 2 + 72;             // symbols a tile can produce at most (samples per symbol x (1 - limit) >= 1.5, checked on the host: <= 171)
+    constexpr int OCAP = FD_TILE / 2 + 72;             // symbols a tile can produce at most (rx_cfg_rules.h, checked on the host: <= 198)
     const uint32_t win_a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) cf32*)win;
     const uint32_t ost_a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) cf32*)ostage;
     const uint32_t brow_a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)brow;

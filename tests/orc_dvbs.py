@@ -380,7 +380,8 @@ class OracleQpskAlt:
 
     def process(self, iq):
         iq = np.ascontiguousarray(iq, np.complex64)
-        out = np.zeros(iq.size // 2 + 64, np.complex64)
+        # (one symbol per `freq + mu_gain * e` samples, any ratio: a configuration the engine accepts never steps by less than a sample -- csrc/rx_cfg_rules.h)
+        out = np.zeros(iq.size + 64, np.complex64)
         n = self.l.orc_qpskalt_process(self.h, iq.size, P(iq), P(out))
         return out[:n]
 

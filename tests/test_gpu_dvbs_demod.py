@@ -268,6 +268,11 @@ def test_dvbs_demod_error_codes(engine, pkg):
         assert e.value.code == pkg.ERR_ARG, kw
     ok = pkg.DvbsDemodBank(engine, 1, max_samples=1000, samplerate=3.2e6, symbolrate=2e6)      # 1.6 samples per symbol: accepted
     ok.close()
+    # the timing gain enters the bound the buffers are sized with (csrc/rx_cfg_rules.h; every bound from both sides: test_gpu_rx_cfg.py)
+    for kw, word in ((dict(clock_mu_gain=0.7), '1.3'), (dict(clock_mu_gain=float('nan')), 'finite'), (dict(rrc_alpha=-0.1), 'rrc_alpha'), (dict(symbolrate=0.5, samplerate=1.0), '2^31')):
+        with pytest.raises(pkg.Dvbs2GpuError) as e:
+            pkg.DvbsDemodBank(engine, 1, max_samples=1000, **kw)
+        assert e.value.code == pkg.ERR_ARG and word in str(e.value), (kw, str(e.value))
     bank = pkg.DvbsDemodBank(engine, 2, max_samples=1000)
     assert engine.lib.dvbs2gpu_dvbs_demod_process(bank.h, 10, None, None, 0) == pkg.ERR_ARG      # host entry needs a 1-stream bank
     iq = np.zeros(2000, np.complex64)

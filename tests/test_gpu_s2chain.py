@@ -257,6 +257,14 @@ def test_demod_error_codes(engine, pkg):
         with pytest.raises(pkg.Dvbs2GpuError) as e:
             engine.demod(engine.default_cfg(14, **kw))
         assert e.value.code == pkg.ERR_ARG, kw
+    # the rule of csrc/rx_cfg_rules.h (every bound from both sides: test_gpu_rx_cfg.py): the timing gain against the timing recovery's output buffer,
+    # the roll-off, non-finite rates; the message names the bound
+    for kw, word in ((dict(clock_mu_gain=0.2), '16/17'), (dict(clock_mu_gain=-1.0), '16/17'), (dict(rrc_alpha=1.5), 'rrc_alpha'), (dict(rrc_taps=130), 'rrc_taps'),
+                     (dict(samplerate=float('inf')), 'samplerate'), (dict(omega_rel_limit=0.0500001), 'omega_rel_limit')):
+        with pytest.raises(pkg.Dvbs2GpuError) as e:
+            engine.demod(engine.default_cfg(14, **kw))
+        assert e.value.code == pkg.ERR_ARG and word in str(e.value), (kw, str(e.value))
+    engine.demod(engine.default_cfg(14, omega_rel_limit=0.05), max_samples=4096).close()      # the plugin's gains pass up to the largest limit
 
 
 def test_pipelined_batch_delivers_the_same_frames_one_call_later(engine, pkg):
