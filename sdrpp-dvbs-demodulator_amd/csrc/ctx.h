@@ -96,20 +96,19 @@ struct GroupWs {        // a CCM group (process_group)
               slot_stats,   // stage pipeline: per-slot frame stats
               quality;      // signal-quality descriptors + records (quality.hip)
 };
+// the buffers of one FEC job: LLRs | BBFRAMEs | frame refs + first[] + results (a CCM group's job), results + index list + destination table (a job in
+// parts, fec_parts.h: ACM/VCM, mixed).  One set per slot and parity for the jobs of the throughput mode; a job in parts of a synchronous call uses its flow's own set
+struct FecJobBufs { Workspace llr, bb, job; };
 struct VcmWs {          // a group of ACM/VCM streams (process_vcm_group)
     Workspace work,     // stream-work table + first[] + counts + FIFO cur/fill + symbol counts + NCO
-              found, frames /* frames + stats + destinations + index lists */, pll, llr,
-              fec_llr, fec_bb, fec_res,     // synchronous FEC parts: LLRs | BBFRAMEs | results + index lists + destinations
-              deliver, quality;
+              found, frames /* frames + stats */, pll, llr, deliver, quality;
+    FecJobBufs fec;     // the synchronous call's job
 };
 struct MixWs {          // a mixed CCM batch (process_mixed)
     Workspace work,     // stream-work table + per-stream configurations + symbol counts + NCO + FIFO cur/fill
-              found, llr_of /* per-frame LLR pointers + slot indices */, pll, slot_stats,
-              fec_llr, fec_bb, fec_res,     // synchronous FEC parts, as VcmWs
-              deliver, quality;
+              found, llr_of /* per-frame LLR pointers + slot indices */, pll, slot_stats, deliver, quality;
+    FecJobBufs fec;     // the synchronous call's job
 };
-// the buffers of one pipelined FEC job (per slot and parity): LLRs | BBFRAMEs | frame refs + first[] + results (CCM), results + index lists + destinations (ACM/VCM, mixed)
-struct FecJobBufs { Workspace llr, bb, job; };
 
 // the argument table of a bank call for n streams (dvbs_capi.hip, bbts.hip): input pointers | output pointers | counts in | bytes out
 struct BankArgs {

@@ -14,10 +14,10 @@
 //   7 D2H (or D2D for the batch entry point) of BBFRAMEs + stats; FIFO remainder moved to the spare buffer (sync 2)
 // ACM/VCM streams (cfg.acm_vcm): 3 = s2_vcm_walk_kernel, 4-5 with per-frame MODCOD tables, 6 = one FEC job per LDPC code present.
 #include "ctx.h"
+#include "fec_parts.h"
 #include "../../include/dvbs2gpu_math.h"
 #include <list>
 #include <unordered_map>
-#include <tuple>
 #include <thread>
 #include <cmath>
 #include <algorithm>
@@ -322,8 +322,9 @@ int demod_reset_state(dvbs2gpu_demod* d) {
 }
 
 // The FEC job of a pipelined call, collected by the next call (or by a later one, or dropped when the mode is switched off).
-// CCM groups: one job = one LDPC code, frames stream-major, every BBFRAME kb bytes.  ACM/VCM groups: one part per LDPC code present in the
-// call (frames of a part = pooled frame indices idx[]), BBFRAMEs of different sizes at per-frame byte offsets inside their stream's output.
+// CCM groups: one job = one LDPC code, frames stream-major, every BBFRAME kb bytes.  ACM/VCM groups and mixed batches: a job in parts (fec_parts.h,
+// build_parts_job; frames of a part = pooled frame indices idx[]), BBFRAMEs of different sizes at per-frame byte offsets inside their stream's output.
+// A synchronous call of those two flows builds the same job and collects it itself.
 struct PendingFec {
     int n = 0, nf = 0, kb = 0;
     std::vector<dvbs2gpu_demod*> dm;    // the streams of the call that started the job (its stream indices are positions in this list)
@@ -335,17 +336,17 @@ struct PendingFec {
     const uint8_t* d_bb = nullptr;
     const int8_t* d_llr = nullptr;      // (CCM jobs: what the decoder read; kept for dvbs2gpu_debug_last_fec_job)
     int N = 0, rate = -1, shortframe = 0, max_trials = 0, force = 0, slot = -1;
-    const int32_t* d_trials = nullptr;  // CCM: [nf]; ACM/VCM: per part trials[cnt] ++ corrections[cnt] at part.to
+    const int32_t* d_trials = nullptr;  // CCM: [nf]; in parts: [n_results], per part trials[cnt] ++ corrections[cnt]
     const int32_t* d_corr = nullptr;
-    // ACM/VCM
-    struct Part { int kb, cnt; const uint8_t* d_bb; const int* d_idx; size_t to; };
-    bool vcm = false;
+    // a job in parts
+    struct Part { int kb, cnt; const uint8_t* d_bb; const int* d_idx; };
+    bool in_parts = false;
     std::vector<Part> parts;
     std::vector<int> frame_off;         // [nf] byte offset of the frame's BBFRAME inside its stream's output, -1: none (dummy PLFRAME)
     std::vector<int> frame_tr, frame_co;   // [nf] index of the frame's trial count / correction count in the job's result array, -1: none
     std::vector<int> stream_bytes;      // [n]
     uint8_t** d_dst = nullptr;          // [nf] device table of the frames' destinations, filled by the delivery
-    size_t n_results = 0;               // int32 words in d_trials (ACM/VCM)
+    size_t n_results = 0;               // int32 words in d_trials (a job in parts)
     hipEvent_t done = nullptr;          // recorded on the FEC stream behind the job
     hipEvent_t t0 = nullptr;            // ... and in front of it (big CCM jobs: the job's duration, for the priority balancer)
     std::vector<hipEvent_t> done_more;  // (a job whose parts ran on several streams: one event per stream)
@@ -370,7 +371,7 @@ struct BatchMap {
 
 // results of a finished (or finishing) job -> the callers' output buffers and the per-frame stats of its streams.  `wo`: a scratch workspace of the caller's
 static int deliver_job(dvbs2gpu_ctx* ctx, PendingFec* job, hipStream_t st, Workspace& wo, const BatchMap& bm) {
-    if (!job->vcm && job->slot >= 0 && job->d_llr) {       // (bench.py's decoder self-check reads the job's buffers back through dvbs2gpu_debug_last_fec_job)
+    if (!job->in_parts && job->slot >= 0 && job->d_llr) {       // (bench.py's decoder self-check reads the job's buffers back through dvbs2gpu_debug_last_fec_job)
         dvbs2gpu_ctx::LastFecJob& lj = ctx->last_fec[job->slot];
         lj.d_llr = job->d_llr; lj.d_bb = job->d_bb; lj.nf = job->nf; lj.n = job->n; lj.N = job->N; lj.kb = job->kb;
         lj.rate = job->rate; lj.shortframe = job->shortframe; lj.max_trials = job->max_trials; lj.force = job->force;
@@ -385,7 +386,7 @@ static int deliver_job(dvbs2gpu_ctx* ctx, PendingFec* job, hipStream_t st, Works
         if (it != bm.pos.end()) where[i] = it->second;
     }
     std::vector<int32_t> res;
-    if (!job->vcm) {
+    if (!job->in_parts) {
         std::vector<uint8_t*> outs(job->n, nullptr);
         for (int i = 0; i < job->n; ++i) {
             if (where[i] < 0) continue;
@@ -415,7 +416,7 @@ static int deliver_job(dvbs2gpu_ctx* ctx, PendingFec* job, hipStream_t st, Works
         }
         return 0;
     }
-    // ACM/VCM: per-frame destinations
+    // a job in parts: per-frame destinations
     std::vector<uint8_t*> dst(job->nf, nullptr);
     for (int i = 0; i < job->n; ++i) {
         if (where[i] < 0) continue;
@@ -681,6 +682,58 @@ struct SlotHandOver {
     int park_and_deliver(std::unique_ptr<PendingFec> job) { park(std::move(job)); return prev ? deliver(prev.get()) : 0; }
 };
 
+// What the PL-sync walk reports of every stream (cnts, four per stream: frames, symbols consumed, FIFO fill, symbols appended) -> the handles' symbol tap and FIFO
+// fill, and cur[]: the symbols each stream's call consumed.  Every fill is checked against its FIFO before any handle is written, so a refused call leaves the host
+// side of all its streams where it was.  (The device side has advanced all the same -- the walk has run --, and a handle of a refused call needs a reset either way.)
+int pool_walk_counts(dvbs2gpu_demod* const* dm, int n, const std::vector<int>& cnts, std::vector<int>* cur) {
+    for (int i = 0; i < n; ++i)
+        if (cnts[4 * i + 2] > dm[i]->fifo_cap) { last_error() = "symbol FIFO overflow"; return DVBS2GPU_ERR_CAPACITY; }
+    cur->assign(n, 0);
+    for (int i = 0; i < n; ++i) {
+        dvbs2gpu_demod* d = dm[i];
+        d->tap_sym_off = d->fifo_fill; d->tap_sym_cnt = cnts[4 * i + 3]; d->tap_fifo = d->fifo_cur;
+        d->fifo_fill = cnts[4 * i + 2];
+        (*cur)[i] = cnts[4 * i + 1];
+    }
+    return 0;
+}
+
+// The FEC job of a call whose pooled frames go to the decoders in parts (fec_parts.h: ACM/VCM groups, mixed batches).  build_parts_job selects the job's buffers --
+// the slot's of this parity in the throughput mode (the next call reuses the flow's scratch while the job runs), the flow's `own` set for a job the call collects
+// itself --, sizes them, lays out the job buffer (results | index list | destination table), uploads the index list on `st` and fills the PendingFec but for what
+// the call learns later: the frames' stats and quality records, and the events behind the parts.  Where the parts run is the flow's: run() enqueues one.
+struct PartsJob {
+    std::unique_ptr<PendingFec> job;
+    const FecParts* plan = nullptr;
+    int8_t* llr = nullptr; uint8_t* bb = nullptr; int32_t* res = nullptr; int* idx = nullptr;
+    int par = 0;        // the parity of the slot's buffers in use (the flow flips fec_parity once the job is enqueued)
+    int run(dvbs2gpu_ctx* ctx, size_t pi, const FecParams& f, hipStream_t s, FecWs* ws = nullptr) const {
+        const FecParts::Part& P = plan->parts[pi];
+        int32_t* tr = res + P.to;
+        return fec_run(ctx, f, llr + P.lo, P.cnt(), P.max_trials, P.force, bb + P.bo, tr, tr + P.cnt(), s, ws);
+    }
+};
+int build_parts_job(dvbs2gpu_ctx* ctx, const FecParts& plan, dvbs2gpu_demod* const* dm, int n, const std::vector<int>& first, const std::vector<int>& frame_off,
+                    const std::vector<int>& stream_bytes, bool pipelined, int slot, FecJobBufs& own, hipStream_t st, PartsJob* out) {
+    const int nf = plan.nf();
+    out->plan = &plan;
+    out->par = pipelined ? ctx->fec_parity[slot] : 0;
+    FecJobBufs& B = pipelined ? ctx->ws_fecbuf[slot][out->par] : own;
+    ScratchLayout lt;   // B.job
+    const auto l_res = lt.add<int32_t>(plan.n_results); const auto l_idx = lt.add<int>(plan.idx.size()); const auto l_dst = lt.add<uint8_t*>(nf);
+    int rc;
+    if ((rc = B.llr.ensure(plan.llr_bytes + 64)) || (rc = B.bb.ensure(plan.bb_bytes + 64)) || (rc = B.job.ensure(lt.bytes()))) return rc;
+    out->llr = (int8_t*)B.llr.p; out->bb = (uint8_t*)B.bb.p; out->res = l_res(B.job.p); out->idx = l_idx(B.job.p);
+    if (!plan.idx.empty()) HIP_TRY(hipMemcpyAsync(out->idx, plan.idx.data(), sizeof(int) * plan.idx.size(), hipMemcpyHostToDevice, st));
+    out->job.reset(new PendingFec());
+    PendingFec& J = *out->job;
+    J.in_parts = true; J.n = n; J.nf = nf; J.dm.assign(dm, dm + n); J.first = first; J.frame_off = frame_off; J.stream_bytes = stream_bytes;
+    J.frame_tr = plan.frame_tr; J.frame_co = plan.frame_co;
+    J.d_trials = out->res; J.n_results = plan.n_results; J.d_dst = l_dst(B.job.p);
+    for (const FecParts::Part& P : plan.parts) J.parts.push_back(PendingFec::Part{P.kb, P.cnt(), out->bb + P.bo, out->idx + P.io});
+    return 0;
+}
+
 // Balance of the two streams of the pipelined mode: did this call have to wait for the previous call's FEC job `prev` (the decoder is the critical path: the timing
 // loop should yield more) or was the job long done (the front end is: it should yield less)?  One step of the priority duty per two consistent calls.
 // `job_was_done`: asked before the delivery, which began at t_d0.
@@ -813,18 +866,12 @@ int process_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     hm.mark("fe_enqueued");
     HIP_TRY(hipStreamSynchronize(st));
     hm.mark("fe_done");
-    std::vector<int> cur(n, 0);
+    std::vector<int> cur;
+    if ((rc = pool_walk_counts(dm, n, cnts, &cur))) return rc;
     std::vector<std::vector<int>> frame_start(n);
     std::vector<std::vector<float>> frame_bm(n);
-    for (int i = 0; i < n; ++i) {
-        dvbs2gpu_demod* d = dm[i];
-        const int nfi = cnts[4 * i], nsym_i = cnts[4 * i + 3];
-        d->tap_sym_off = d->fifo_fill; d->tap_sym_cnt = nsym_i; d->tap_fifo = d->fifo_cur;
-        d->fifo_fill = cnts[4 * i + 2];
-        if (d->fifo_fill > d->fifo_cap) { last_error() = "symbol FIFO overflow"; return DVBS2GPU_ERR_CAPACITY; }
-        cur[i] = cnts[4 * i + 1];
-        for (int k = 0; k < nfi; ++k) { frame_start[i].push_back(found[(size_t)i * maxf + k].offset); frame_bm[i].push_back(found[(size_t)i * maxf + k].sofq); }
-    }
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < cnts[4 * i]; ++k) { frame_start[i].push_back(found[(size_t)i * maxf + k].offset); frame_bm[i].push_back(found[(size_t)i * maxf + k].sofq); }
     hm.mark("plsync_done");
     // ---- 4..6 on the pooled frames
     std::vector<S2FrameRef> frames;
@@ -1040,9 +1087,9 @@ int get_vcm_tables(dvbs2gpu_ctx* ctx) {
     return 0;
 }
 
-// One group of ACM/VCM streams (same loop settings), synchronous: front end -> framing walk on the device -> [frame tables to the host:
-// pooling, grouping by LDPC code] -> per-frame-MODCOD loops + demapper -> one FEC job per code present -> BBFRAMEs of differing size
-// into the streams' output buffers in frame order.
+// One group of ACM/VCM streams (same loop settings): front end -> framing walk on the device -> [frame tables to the host: pooling, one FEC part per
+// LDPC code present (fec_parts.h)] -> per-frame-MODCOD loops + demapper -> the job in parts -> BBFRAMEs of differing size into the streams' output
+// buffers in frame order, by the delivery of this call (synchronous) or of the next one (throughput mode).
 int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf32* const* d_iq, const int* counts, uint8_t* const* d_out,
                       int out_cap, int* out_bytes, hipStream_t st, bool pipelined = false, int slot = 0, const BatchMap* bm = nullptr) {
     dvbs2gpu_demod* d0 = dm[0];
@@ -1071,189 +1118,99 @@ int process_vcm_group(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const
     HIP_TRY(hipMemcpyAsync(cnts.data(), d_counts, sizeof(int) * 4 * n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(found.data(), d_found, sizeof(S2VcmFound) * found.size(), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    // ---- pool the frames (stream-major, stream order), group them by LDPC code, lay out PLL output / LLRs / output bytes
+    // ---- pool the frames (stream-major, stream order), one FEC part per LDPC code present, lay out PLL output / LLRs / output bytes
+    std::vector<int> cur;
+    if ((rc = pool_walk_counts(dm, n, cnts, &cur))) return rc;
     std::vector<S2VcmFrame> frames;
     std::vector<int> first(n + 1, 0);
-    std::vector<uint8_t*> dst;                     // per pooled frame: where its BBFRAME goes
-    std::vector<int> frame_off, stream_bytes(n, 0);   // (pipelined: the same as offsets -- the buffers are those of the call that collects the job)
-    std::map<int, std::vector<int>> groups;        // PLS-independent FEC identity (code index * 2 + frame size is implied by the index) -> pooled frame indices
-    std::map<int, int> group_pls;                  // a PLS code of the group (its FEC parameters)
+    std::vector<int> frame_off, stream_bytes(n, 0);   // where a frame's BBFRAME goes, as an offset: the buffers are those of the call that collects the job
+    FecParts plan;
+    const int force = d0->cfg.force_ldpc_iters > 0;
+    const int mt = force ? d0->cfg.force_ldpc_iters : d0->cfg.max_ldpc_trials;
     long long pll_off = 0, llr_off = 0;
     for (int i = 0; i < n; ++i) {
         dvbs2gpu_demod* d = dm[i];
-        const int nf = cnts[4 * i], avail = cnts[4 * i + 2], nsym = cnts[4 * i + 3];
         first[i] = (int)frames.size();
-        d->tap_sym_off = d->fifo_fill; d->tap_sym_cnt = nsym; d->tap_fifo = d->fifo_cur;
-        d->fifo_fill = avail;
-        if (d->fifo_fill > d->fifo_cap) { last_error() = "symbol FIFO overflow"; return DVBS2GPU_ERR_CAPACITY; }
         const cf32* base = d->d_fifo[d->fifo_cur];
         int obytes = 0;
-        for (int k = 0; k < nf; ++k) {
+        for (int k = 0; k < cnts[4 * i]; ++k) {
             const S2VcmFound& F = found[(size_t)i * maxf + k];
             const S2VcmMod& M = ctx->h_vcm_mods[F.pls];
             S2VcmFrame fr;
             fr.sym = base + F.offset; fr.stream = i; fr.pls = F.pls; fr.pll_off = pll_off; fr.llr_off = llr_off; fr.sofq = F.sofq; fr.dst_index = 0;
             if (M.valid == 1) {
-                auto& g = groups[M.code_index];
-                fr.dst_index = (int)g.size();
-                g.push_back((int)frames.size());
-                group_pls[M.code_index] = F.pls;
+                plan.add(M.code_index, mt, force, M.N, M.kb);
+                fr.dst_index = plan.parts[plan.part_of.back()].cnt() - 1;
                 if (obytes + M.kb > out_cap) { last_error() = "output buffer too small"; return DVBS2GPU_ERR_CAPACITY; }
-                dst.push_back(d_out[i] + obytes);
                 frame_off.push_back(obytes);
                 obytes += M.kb;
                 pll_off += M.plframe; llr_off += M.N;
                 d->tap_pll_count += M.plframe; d->tap_llr_count += M.N;
             } else {
-                dst.push_back(nullptr);
+                plan.add_none();
                 frame_off.push_back(-1);
             }
             d->frame_ptrs.push_back(fr.sym); d->frame_len.push_back(M.plframe); d->frame_pos.push_back(d->sym_base + F.offset);
             frames.push_back(fr);
         }
         stream_bytes[i] = obytes;
-        if (!pipelined) out_bytes[i] = obytes;
     }
     first[n] = (int)frames.size();
+    plan.layout();
     const int nf = (int)frames.size();
     QualityCall qc(dm, n);
     std::vector<S2FrameStats> hstats(nf);
-    std::vector<int32_t> trials(nf, 0), corr(nf, 0);
-    std::unique_ptr<PendingFec> job_started;
+    PartsJob pj;
     if (nf > 0) {
-        static_assert(sizeof(S2VcmFrame) == 40 && sizeof(S2FrameStats) == 32, "tests/cpp/scratch_layout_host.cpp mirrors these sizes");
         ScratchLayout lr;   // W.frames
-        const auto l_frames = lr.add<S2VcmFrame>(nf); const auto l_stats = lr.add<S2FrameStats>(nf); const auto l_dst = lr.add<uint8_t*>(nf); const auto l_idx = lr.add<int>(nf);
+        const auto l_frames = lr.add<S2VcmFrame>(nf); const auto l_stats = lr.add<S2FrameStats>(nf);
         if ((rc = W.frames.ensure(lr.bytes()))) return rc;
         S2VcmFrame* d_frames = l_frames(W.frames.p); S2FrameStats* d_stats = l_stats(W.frames.p);
-        uint8_t** d_dst = l_dst(W.frames.p); int* d_idx = l_idx(W.frames.p);
         if ((rc = W.pll.ensure((size_t)std::max<long long>(pll_off, 1) * sizeof(cf32)))) return rc;
         if ((rc = W.llr.ensure((size_t)std::max<long long>(llr_off, 4)))) return rc;
         cf32* d_pll = (cf32*)W.pll.p;
         int8_t* d_llr = (int8_t*)W.llr.p;
         HIP_TRY(hipMemcpyAsync(d_frames, frames.data(), sizeof(S2VcmFrame) * nf, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_first, first.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_dst, dst.data(), sizeof(uint8_t*) * nf, hipMemcpyHostToDevice, st));
         { StageSpan sp(ctx->timers, ST_LOOPS, st); HIP_TRY(s2_vcm_loops_launch(d_work, n, d_frames, d_first, d0->co, ctx->pl, ctx->d_vcm_mods, ctx->d_vcm_cons, d_pll, d_stats, st)); }
         { StageSpan sp(ctx->timers, ST_DEMAP, st); HIP_TRY(s2_vcm_demap_launch(d_frames, nf, ctx->d_vcm_mods, ctx->d_vcm_cons, d_pll, d_llr, st)); }
-        for (int f = 0; f < nf; ++f)      // (a dummy PLFRAME has no PLL output; launched behind the LLR gathers below, so that no decoder waits for it)
+        for (int f = 0; f < nf; ++f)      // (a dummy PLFRAME has no PLL output; launched behind the LLR gathers below, so that no decoder of the throughput mode waits for it)
             qc.add(frames[f].stream, f, ctx->h_vcm_mods[frames[f].pls].valid == 1 ? d_pll + frames[f].pll_off : nullptr, frames[f].pls);
-        const int force = d0->cfg.force_ldpc_iters > 0;
-        const int mt = force ? d0->cfg.force_ldpc_iters : d0->cfg.max_ldpc_trials;
-        // one FEC job per LDPC code present in the call; group buffers: LLRs | BBFRAMEs | trials + corrections
-        std::vector<std::pair<int, std::vector<int32_t>>> results;     // (code, trials ++ corrections) filled after the sync
-        size_t off_idx = 0;
-        std::vector<int> all_idx;
-        for (auto& kv : groups) all_idx.insert(all_idx.end(), kv.second.begin(), kv.second.end());
-        HIP_TRY(hipMemcpyAsync(d_idx, all_idx.data(), sizeof(int) * all_idx.size(), hipMemcpyHostToDevice, st));
-        size_t llr_need = 0, bb_need = 0;
-        for (auto& kv : groups) {
-            const FecParams& f = ctx->h_vcm_fec[group_pls[kv.first]];
-            llr_need += (size_t)kv.second.size() * f.N; bb_need += (size_t)kv.second.size() * (f.kbch / 8 + 8);
-        }
-        // pipelined: the job's buffers are the slot's double-buffered FEC workspaces (the next call reuses ws_vcm while the job runs):
-        // LLR groups | BBFRAME groups | results (trials ++ corrections per part) + the parts' frame index lists + the destination table
-        const int par = pipelined ? ctx->fec_parity[slot] : 0;
-        Workspace& ws_gl = pipelined ? ctx->ws_fecbuf[slot][par].llr : W.fec_llr;
-        Workspace& ws_gb = pipelined ? ctx->ws_fecbuf[slot][par].bb : W.fec_bb;
-        Workspace& ws_gt = pipelined ? ctx->ws_fecbuf[slot][par].job : W.fec_res;
-        const size_t nall = all_idx.size();
-        ScratchLayout lt;   // ws_gt
-        const auto l_res = lt.add<int32_t>(2 * nall); const auto l_jidx = lt.add<int>(nall); const auto l_jdst = lt.add<uint8_t*>(nf);
-        if ((rc = ws_gl.ensure(llr_need + 64)) || (rc = ws_gb.ensure(bb_need + 64)) || (rc = ws_gt.ensure(lt.bytes()))) return rc;
-        int32_t* d_res = l_res(ws_gt.p); int* j_idx = l_jidx(ws_gt.p);
-        if (pipelined) {
-            HIP_TRY(hipMemcpyAsync(j_idx, all_idx.data(), sizeof(int) * nall, hipMemcpyHostToDevice, st));
-            if (!ctx->ev_llr) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_llr, hipEventDisableTiming));
-        }
-        size_t lo = 0, bo = 0, to = 0;
-        struct Out { int code; size_t to; int cnt; };
-        std::vector<Out> outs;
-        std::vector<PendingFec::Part> parts;
-        struct Run { FecParams f; int8_t* llr; int cnt; uint8_t* bb; int32_t* tr; };
-        std::vector<Run> runs;
-        for (auto& kv : groups) {
-            const FecParams& f = ctx->h_vcm_fec[group_pls[kv.first]];
-            const int cnt = (int)kv.second.size(), kb = f.kbch / 8;
-            int8_t* g_llr = (int8_t*)ws_gl.p + lo;
-            uint8_t* g_bb = (uint8_t*)ws_gb.p + bo;
-            int32_t* g_tr = d_res + to;
-            HIP_TRY(s2_vcm_gather_launch(d_frames, d_idx + off_idx, cnt, f.N, d_llr, g_llr, st));
-            if (!pipelined) {
-                if ((rc = fec_run(ctx, f, g_llr, cnt, mt, force, g_bb, g_tr, g_tr + cnt, st))) return rc;
-                // the group's index list, re-based onto the per-frame destination table
-                { StageSpan sp(ctx->timers, ST_DELIVER, st); HIP_TRY(s2_vcm_scatter_launch(d_idx + off_idx, cnt, kb, g_bb, d_dst, st)); }
-            } else {
-                runs.push_back(Run{f, g_llr, cnt, g_bb, g_tr});
-                parts.push_back(PendingFec::Part{kb, cnt, g_bb, j_idx + off_idx, to});
-            }
-            outs.push_back(Out{kv.first, to, cnt});
-            off_idx += cnt; lo += (size_t)cnt * f.N; bo += (size_t)cnt * kb; bo = (bo + 7) & ~(size_t)7; to += 2 * (size_t)cnt;
-        }
-        if (pipelined) {
-            // the decoders of this call's codes go onto the FEC stream, behind the gathers; the call that follows collects them
-            hipStream_t sf = ctx->fec_stream;
-            HIP_TRY(hipEventRecord(ctx->ev_llr, st));
-            if ((rc = qc.launch(ctx, W.quality, st, 0))) return rc;
-            {
-                std::lock_guard<std::mutex> fl(ctx->fec_mtx);
+        // one FEC part per LDPC code present in the call: its LLRs gathered on the call's stream, its decoder in sequence on the call's stream (synchronous: this
+        // call collects the job) or, behind the gathers, on the FEC stream (throughput mode: the call that follows collects it)
+        if ((rc = build_parts_job(ctx, plan, dm, n, first, frame_off, stream_bytes, pipelined, slot, W.fec, st, &pj))) return rc;
+        for (const FecParts::Part& P : plan.parts) HIP_TRY(s2_vcm_gather_launch(d_frames, pj.idx + P.io, P.cnt(), P.N, d_llr, pj.llr + P.lo, st));
+        {
+            hipStream_t sf = pipelined ? ctx->fec_stream : st;
+            std::lock_guard<std::mutex> fl(ctx->fec_mtx);
+            if (pipelined) {
+                if (!ctx->ev_llr) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_llr, hipEventDisableTiming));
+                HIP_TRY(hipEventRecord(ctx->ev_llr, st));
                 HIP_TRY(hipStreamWaitEvent(sf, ctx->ev_llr, 0));
-                for (const Run& r : runs)
-                    if ((rc = fec_run(ctx, r.f, r.llr, r.cnt, mt, force, r.bb, r.tr, r.tr + r.cnt, sf))) return rc;
-                if (!ctx->ev_fec[slot][par]) HIP_TRY(hipEventCreate(&ctx->ev_fec[slot][par]));
-                HIP_TRY(hipEventRecord(ctx->ev_fec[slot][par], sf));
             }
-            ctx->fec_parity[slot] ^= 1;
-            HIP_TRY(hipMemcpyAsync(hstats.data(), d_stats, sizeof(S2FrameStats) * nf, hipMemcpyDeviceToHost, st));
-            job_started.reset(new PendingFec());
-            PendingFec& J = *job_started;
-            J.vcm = true; J.n = n; J.nf = nf; J.dm.assign(dm, dm + n); J.first = first;
-            J.parts = std::move(parts); J.frame_off = frame_off; J.stream_bytes = stream_bytes;
-            J.frame_tr.assign(nf, -1); J.frame_co.assign(nf, -1);
-            for (const Out& o : outs) {
-                const std::vector<int>& idx = groups[o.code];
-                for (int k = 0; k < o.cnt; ++k) { J.frame_tr[idx[k]] = (int)(o.to + k); J.frame_co[idx[k]] = (int)(o.to + o.cnt + k); }
-            }
-            J.d_trials = d_res; J.n_results = 2 * nall;
-            J.d_dst = l_jdst(ws_gt.p);
-            J.done = ctx->ev_fec[slot][par];
-        } else {
-            if ((rc = qc.launch(ctx, W.quality, st, 0))) return rc;
-            std::vector<int32_t> tc(2 * all_idx.size());
-            HIP_TRY(hipMemcpyAsync(tc.data(), d_res, sizeof(int32_t) * tc.size(), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(hstats.data(), d_stats, sizeof(S2FrameStats) * nf, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            for (const Out& o : outs) {
-                const std::vector<int>& idx = groups[o.code];
-                for (int k = 0; k < o.cnt; ++k) { trials[idx[k]] = tc[o.to + k]; corr[idx[k]] = tc[o.to + o.cnt + k]; }
+            for (size_t pi = 0; pi < plan.parts.size(); ++pi)
+                if ((rc = pj.run(ctx, pi, ctx->h_vcm_fec[frames[plan.parts[pi].frames[0]].pls], sf))) return rc;
+            if (pipelined) {
+                hipEvent_t& done = ctx->ev_fec[slot][pj.par];
+                if (!done) HIP_TRY(hipEventCreate(&done));
+                HIP_TRY(hipEventRecord(done, sf));
+                pj.job->done = done;
+                ctx->fec_parity[slot] ^= 1;
             }
         }
-        for (int i = 0; i < n; ++i)
-            if (first[i + 1] > first[i]) {
-                // taps: PLL output and LLRs of this stream's data frames are contiguous, in frame order
-                for (int f = first[i]; f < first[i + 1]; ++f)
-                    if (ctx->h_vcm_mods[frames[f].pls].valid == 1) { dm[i]->tap_pll = d_pll + frames[f].pll_off; dm[i]->tap_llr = d_llr + frames[f].llr_off; break; }
-            }
+        if ((rc = qc.launch(ctx, W.quality, st, 0))) return rc;
+        HIP_TRY(hipMemcpyAsync(hstats.data(), d_stats, sizeof(S2FrameStats) * nf, hipMemcpyDeviceToHost, st));
+        for (int i = 0; i < n; ++i)     // taps: PLL output and LLRs of this stream's data frames are contiguous, in frame order
+            for (int f = first[i]; f < first[i + 1]; ++f)
+                if (ctx->h_vcm_mods[frames[f].pls].valid == 1) { dm[i]->tap_pll = d_pll + frames[f].pll_off; dm[i]->tap_llr = d_llr + frames[f].llr_off; break; }
     }
-    std::vector<int> cur(n);
-    for (int i = 0; i < n; ++i) cur[i] = cnts[4 * i + 1];
     if ((rc = finish_call(dm, n, cur, d_work, d_curfill, d_nsym, d_nco, st))) return rc;
-    std::vector<S2FrameQuality> qrec = qc.by_frame(nf);
-    if (pipelined) {
-        // the job of the previous call of this slot is collected AFTER this call's job has gone onto the FEC stream (process_group does the same)
-        if (job_started) { job_started->hstats = hstats; job_started->qual_on = qc.on; job_started->hquality = std::move(qrec); }
-        SlotHandOver h(ctx, slot, st, W.deliver, bm, true, dm, n, d_out, out_cap, out_bytes);
-        return h.park_and_deliver(std::move(job_started));
-    }
-    for (int i = 0; i < n; ++i) {
-        for (int f = first[i]; f < first[i + 1]; ++f) {
-            S2FrameStats s = hstats[f];
-            s.ldpc_trials = trials[f]; s.bch_corr = corr[f];
-            dm[i]->stats.push_back(s);
-        }
-        publish_quality(dm[i], qc.on, qrec, i, first[i], first[i + 1]);
-    }
-    return 0;
+    if (pj.job) { pj.job->hstats = std::move(hstats); pj.job->qual_on = qc.on; pj.job->hquality = qc.by_frame(nf); }
+    // throughput mode: the job of the previous call of this slot is collected AFTER this call's job has gone onto the FEC stream (process_group does the same);
+    // synchronous: this call collects its own
+    SlotHandOver h(ctx, slot, st, W.deliver, bm, pipelined, dm, n, d_out, out_cap, out_bytes);
+    if (!pipelined) return pj.job ? h.deliver(pj.job.get()) : 0;
+    return h.park_and_deliver(std::move(pj.job));
 }
 
 // ---------------------------------------------------------------------------------------------------- mixed CCM batches, one launch per stage
@@ -1320,27 +1277,19 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
     HIP_TRY(hipMemcpyAsync(found.data(), d_found, sizeof(S2VcmFound) * nslot, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     // ---- pool the frames (stream-major), one FEC part per (LDPC code, iteration setting)
-    struct PartH { FecParams f; int mt, force; std::vector<int> frames; size_t lo = 0, bo = 0, to = 0; };
-    std::vector<PartH> parts;
-    std::map<std::tuple<int, int, int>, int> part_of;
-    std::vector<int> first(n + 1, 0), fslot, frame_off, cur(n, 0), stream_bytes(n, 0);
+    FecParts plan;
+    std::vector<const FecParams*> part_fec;
+    std::vector<int> first(n + 1, 0), fslot, frame_off, cur, stream_bytes(n, 0);
     std::vector<S2FrameStats> hstats;
     // (every capacity is checked before any handle's state is touched: a refused call leaves all receivers where they were)
-    for (int i = 0; i < n; ++i) {
-        if (cnts[4 * i + 2] > dm[i]->fifo_cap) { last_error() = "symbol FIFO overflow"; return DVBS2GPU_ERR_CAPACITY; }
+    for (int i = 0; i < n; ++i)
         if (cnts[4 * i] * (dm[i]->mp.fec.kbch / 8) > out_cap) { last_error() = "output buffer too small"; return DVBS2GPU_ERR_CAPACITY; }
-    }
+    if ((rc = pool_walk_counts(dm, n, cnts, &cur))) return rc;
     for (int i = 0; i < n; ++i) {
         dvbs2gpu_demod* d = dm[i];
         const int nfi = cnts[4 * i], kb = d->mp.fec.kbch / 8;
-        d->tap_sym_off = d->fifo_fill; d->tap_sym_cnt = cnts[4 * i + 3]; d->tap_fifo = d->fifo_cur;
-        d->fifo_fill = cnts[4 * i + 2];
-        cur[i] = cnts[4 * i + 1];
         first[i] = (int)fslot.size();
         const int force = d->cfg.force_ldpc_iters > 0, mt = force ? d->cfg.force_ldpc_iters : d->cfg.max_ldpc_trials;
-        const auto key = std::make_tuple(d->mp.fec.code_index, mt, force);
-        auto it = part_of.find(key);
-        if (nfi > 0 && it == part_of.end()) { it = part_of.emplace(key, (int)parts.size()).first; parts.push_back(PartH{d->mp.fec, mt, force, {}}); }     // (a part exists only with frames in it)
         const cf32* base = d->d_fifo[d->fifo_cur];
         for (int k = 0; k < nfi; ++k) {
             const S2VcmFound& F = found[(size_t)i * maxf + k];
@@ -1349,7 +1298,8 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
             s.best_match = F.sofq; s.bbframe_bytes = kb;
             hstats.push_back(s);
             frame_off.push_back(k * kb);
-            parts[it->second].frames.push_back((int)fslot.size());
+            plan.add(d->mp.fec.code_index, mt, force, d->mp.fec.N, kb);
+            if (plan.parts.size() > part_fec.size()) part_fec.push_back(&d->mp.fec);
             fslot.push_back(i * maxf + k);
         }
         stream_bytes[i] = nfi * kb;
@@ -1358,72 +1308,47 @@ int process_mixed(dvbs2gpu_ctx* ctx, dvbs2gpu_demod* const* dm, int n, const cf3
         d->tap_llr = nullptr;
     }
     first[n] = (int)fslot.size();
+    plan.layout();
     const int nf = (int)fslot.size();
     QualityCall qc(dm, n);
-    std::unique_ptr<PendingFec> job;
+    PartsJob pj;
     if (nf > 0) {
-        const int par = pipelined ? ctx->fec_parity[0] : 0;
-        Workspace& ws_gl = pipelined ? ctx->ws_fecbuf[0][par].llr : W.fec_llr;
-        Workspace& ws_gb = pipelined ? ctx->ws_fecbuf[0][par].bb : W.fec_bb;
-        Workspace& ws_gt = pipelined ? ctx->ws_fecbuf[0][par].job : W.fec_res;
-        size_t lo = 0, bo = 0, to = 0;
-        for (PartH& P : parts) {
-            P.lo = lo; P.bo = bo; P.to = to;
-            lo += (size_t)P.frames.size() * P.f.N; bo += ((size_t)P.frames.size() * (P.f.kbch / 8) + 63) & ~(size_t)63; to += 2 * P.frames.size();
-        }
-        ScratchLayout lt, ll;   // ws_gt, W.llr_of
-        const auto l_res = lt.add<int32_t>(to); const auto l_jidx = lt.add<int>(nf); const auto l_jdst = lt.add<uint8_t*>(nf);
+        if ((rc = build_parts_job(ctx, plan, dm, n, first, frame_off, stream_bytes, pipelined, 0, W.fec, st, &pj))) return rc;
+        ScratchLayout ll;   // W.llr_of
         const auto l_llr_of = ll.add<int8_t*>(nf); const auto l_slot = ll.add<int>(nf);
-        if ((rc = ws_gl.ensure(lo + 64)) || (rc = ws_gb.ensure(bo + 64)) || (rc = ws_gt.ensure(lt.bytes())) || (rc = W.llr_of.ensure(ll.bytes()))) return rc;
+        if ((rc = W.llr_of.ensure(ll.bytes()))) return rc;
         int8_t** d_llr_of = l_llr_of(W.llr_of.p); int* d_slot = l_slot(W.llr_of.p);
-        int32_t* d_res = l_res(ws_gt.p); int* j_idx = l_jidx(ws_gt.p);
         std::vector<int8_t*> llr_of(nf);
-        std::vector<int> all_idx;
-        for (const PartH& P : parts)
-            for (size_t k = 0; k < P.frames.size(); ++k) { llr_of[P.frames[k]] = (int8_t*)ws_gl.p + P.lo + k * P.f.N; all_idx.push_back(P.frames[k]); }
+        for (int f = 0; f < nf; ++f) llr_of[f] = pj.llr + plan.frame_llr[f];
         for (int i = 0; i < n; ++i)
             if (first[i + 1] > first[i]) dm[i]->tap_llr = llr_of[first[i]];      // (a stream's frames are consecutive inside its part)
         HIP_TRY(hipMemcpyAsync(d_llr_of, llr_of.data(), sizeof(int8_t*) * nf, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_slot, fslot.data(), sizeof(int) * nf, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(j_idx, all_idx.data(), sizeof(int) * nf, hipMemcpyHostToDevice, st));
         { StageSpan sp(ctx->timers, ST_DEMAP, st); HIP_TRY(s2_demap_mixed_launch(d_cfgs, max_slots, maxf, raw_max, d_pll, nf, d_llr_of, st, d_slot)); }
         if (!ctx->ev_llr) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_llr, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(ctx->ev_llr, st));
         for (int i = 0; i < n; ++i)
             for (int f = first[i]; f < first[i + 1]; ++f) qc.add(i, f, d_pll + (size_t)fslot[f] * raw_max, cfgs[i].pls_code);
         if ((rc = qc.launch(ctx, W.quality, st, 0))) return rc;
-        // the FEC jobs, side by side
-        job.reset(new PendingFec());
-        PendingFec& J = *job;
-        J.vcm = true; J.n = n; J.nf = nf; J.dm.assign(dm, dm + n); J.first = first; J.hstats = hstats;
-        J.frame_off = frame_off; J.stream_bytes = stream_bytes;
-        J.frame_tr.assign(nf, -1); J.frame_co.assign(nf, -1);
-        J.d_trials = d_res; J.n_results = to;
-        J.d_dst = l_jdst(ws_gt.p);
-        const int nside = std::min<int>((int)parts.size(), dvbs2gpu_ctx::MIX_FEC_STREAMS);
-        size_t off_idx = 0;
-        for (size_t pi = 0; pi < parts.size(); ++pi) {
-            const PartH& P = parts[pi];
-            const int k = (int)(pi % nside), cnt = (int)P.frames.size();
+        // the parts, side by side: part pi on side stream pi % nside with that stream's FEC workspaces, one event per side stream behind its parts
+        const int nside = std::min<int>((int)plan.parts.size(), dvbs2gpu_ctx::MIX_FEC_STREAMS);
+        for (size_t pi = 0; pi < plan.parts.size(); ++pi) {
+            const int k = (int)(pi % nside);
             if (!ctx->grp_stream[k]) HIP_TRY(hipStreamCreateWithFlags(&ctx->grp_stream[k], hipStreamNonBlocking));
-            hipStream_t sk = ctx->grp_stream[k];
-            if ((int)pi < nside) HIP_TRY(hipStreamWaitEvent(sk, ctx->ev_llr, 0));
-            int32_t* g_tr = d_res + P.to;
-            uint8_t* g_bb = (uint8_t*)ws_gb.p + P.bo;
-            if ((rc = fec_run(ctx, P.f, (const int8_t*)ws_gl.p + P.lo, cnt, P.mt, P.force, g_bb, g_tr, g_tr + cnt, sk, &ctx->fws_grp[k]))) return rc;
-            J.parts.push_back(PendingFec::Part{P.f.kbch / 8, cnt, g_bb, j_idx + off_idx, P.to});
-            for (int q = 0; q < cnt; ++q) { J.frame_tr[P.frames[q]] = (int)(P.to + q); J.frame_co[P.frames[q]] = (int)(P.to + cnt + q); }
-            off_idx += cnt;
+            if ((int)pi < nside) HIP_TRY(hipStreamWaitEvent(ctx->grp_stream[k], ctx->ev_llr, 0));
+            if ((rc = pj.run(ctx, pi, *part_fec[pi], ctx->grp_stream[k], &ctx->fws_grp[k]))) return rc;
         }
         for (int k = 0; k < nside; ++k) {
-            if (!ctx->ev_mix[k][par]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_mix[k][par], hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ctx->ev_mix[k][par], ctx->grp_stream[k]));
-            J.done_more.push_back(ctx->ev_mix[k][par]);
+            hipEvent_t& done = ctx->ev_mix[k][pj.par];
+            if (!done) HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(done, ctx->grp_stream[k]));
+            pj.job->done_more.push_back(done);
         }
         if (pipelined) ctx->fec_parity[0] ^= 1;
     }
     if ((rc = finish_call(dm, n, cur, d_work, d_curfill, d_nsym, d_nco, st))) return rc;
-    if (job) { job->qual_on = qc.on; job->hquality = qc.by_frame(nf); }
+    std::unique_ptr<PendingFec> job = std::move(pj.job);
+    if (job) { job->hstats = std::move(hstats); job->qual_on = qc.on; job->hquality = qc.by_frame(nf); }
     // (synchronous: the job is collected by this call)
     SlotHandOver h(ctx, 0, st, W.deliver, bm, pipelined, dm, n, d_out, out_cap, out_bytes);
     if (!pipelined) return job ? h.deliver(job.get()) : 0;

@@ -73,24 +73,17 @@ static void mix(const char* what) {
             }
 }
 
-// The frame buffer of the ACM/VCM flow (s2_demod.hip, process_vcm_group): frame records, frame stats, a table of POINTERS, ints.  Carved by hand
-// the table's 8-byte alignment rested on the two struct sizes and on the parity of nf.  The real S2VcmFrame (40 bytes) and S2FrameStats (32 bytes)
-// of csrc/s2_rx.h are multiples of 8 (s2_demod.hip asserts these sizes), so the real layout was never at risk; Frame44 / Stats36 are the
-// synthetic case, sizes that are 4 mod 8, where nf = 1 and nf = 3 put the table at an odd multiple of 4 unless the layout aligns it.
-struct Frame40 { const void* sym; int stream, pls; long long pll_off, llr_off; float sofq; int dst_index; };
-struct Stats32 { float best_match; int modcod, shortf, pilots; float fed_err; int trials, corr, bytes; };
-struct Frame44 { int w[11]; };
-struct Stats36 { int w[9]; };
-static_assert(sizeof(Frame40) == 40 && sizeof(Stats32) == 32, "mirrors of S2VcmFrame / S2FrameStats");
-static_assert(sizeof(Frame44) % 8 == 4 && sizeof(Stats36) % 8 == 4 && alignof(Frame44) == 4, "the synthetic sizes are 4 mod 8");
-
-template <typename F, typename S>
-static void vcm_frames(size_t nf, const char* what) {
+// The job buffer of a FEC job in parts (s2_demod.hip, build_parts_job; the ACM/VCM and the mixed flow): int32 results[2 * nall] | int indices[nall] | a table
+// of nf POINTERS, nall <= nf the frames that have a part.  Carved by hand the table would sit behind 3 * nall four-byte words: at an odd multiple of 4 for
+// every odd nall (nf = 1 and nf = 3 among them) unless the layout aligns it.
+static void vcm_frames(size_t nall, size_t nf, const char* what) {
     ScratchLayout L;
     std::vector<Span> spans;
-    add<F>(L, spans, nf, what); add<S>(L, spans, nf, what); add<uint8_t*>(L, spans, nf, what); add<int>(L, spans, nf, what);
+    add<int32_t>(L, spans, 2 * nall, what); add<int>(L, spans, nall, what); add<uint8_t*>(L, spans, nf, what);
     check_disjoint(spans, L.bytes(), what);
-    CHECK(spans.size() == 4 && spans[2].off % alignof(uint8_t*) == 0, "%s, nf = %zu: pointer table at offset %zu", what, nf, spans.size() == 4 ? spans[2].off : 0);
+    // (an empty array leaves no span: the table is the last one)
+    const bool all_there = spans.size() == (nall ? 3u : 1u);
+    CHECK(all_there && spans.back().off % alignof(uint8_t*) == 0, "%s, nall = %zu, nf = %zu: pointer table at offset %zu", what, nall, nf, all_there ? spans.back().off : 0);
 }
 
 int main() {
@@ -100,8 +93,9 @@ int main() {
     mix<Vec16, uint8_t, double>("vectors | bytes | doubles");
     mix<uint8_t, Block256, uint32_t>("bytes | a 256-byte-aligned block | words");
     for (size_t nf : {(size_t)1, (size_t)3, (size_t)4, (size_t)1001}) {
-        vcm_frames<Frame40, Stats32>(nf, "frame buffer, real sizes");
-        vcm_frames<Frame44, Stats36>(nf, "frame buffer, sizes 4 mod 8");
+        vcm_frames(nf, nf, "job buffer, every frame in a part");
+        vcm_frames(nf | 1, (nf | 1) + 2, "job buffer, an odd count of frames in parts among dummy PLFRAMEs");
+        vcm_frames(0, nf, "job buffer, dummy PLFRAMEs only");
     }
     if (failures) fprintf(stderr, "%d checks failed\n", failures);
     return failures ? 1 : 0;

@@ -1,7 +1,7 @@
 """Calls whose pooled frame count is ODD, in the two flows that keep a table of device pointers behind per-frame arrays in one scratch buffer
-(csrc/scratch_layout.h): an ACM/VCM bank (process_vcm_group: frames | stats | destinations | indices; its pipelined job: results | indices |
-destinations) and a mixed-MODCOD bank (process_mixed: LLR pointers | slot indices).  Three streams each, one call with the whole signal,
-synchronous and pipelined; BBFRAMEs, trial counts and per-frame stats equal the oracle's."""
+(csrc/scratch_layout.h): the job buffer of a FEC job in parts, which an ACM/VCM bank (process_vcm_group) and a mixed-MODCOD bank (process_mixed) build
+in either mode (build_parts_job: results | indices | destinations), and the mixed bank's per-frame table (LLR pointers | slot indices).  Three streams
+each, one call with the whole signal, synchronous and pipelined; BBFRAMEs, trial counts and per-frame stats equal the oracle's."""
 import numpy as np
 import pytest
 import orc

@@ -964,6 +964,50 @@ def test_acm_vcm_streams_in_the_pipelined_mode_equal_synchronous_one_call_later(
     assert total > 20000
 
 
+def test_acm_vcm_job_without_parts_and_stream_without_bbframes_equal_oracle(engine, pkg):
+    """The FEC job of an ACM/VCM call at its empty edges: stream (a) carries dummy PLFRAMEs only -- alone on a handle its call pools frames and no FEC part --,
+    stream (b) a few data frames among dummies, stream (c) three LDPC codes, two of them with odd BBFRAME sizes.  (a) through Demod.process, then (a), (b), (c) as
+    one batch, synchronous and in the throughput mode (the frames arrive with the next, empty call): BBFRAME bytes and per-frame stats equal the oracle's."""
+    import torch
+    from test_gpu_odd_frame_counts import stats_key
+    S = 2
+    common = dict(esn0_db=18.0, cfo=1e-4, timing=0.1, phase0=0.1, lead_symbols=300)
+    streams = []
+    for pls, nframes, seed in [([0], 14, 71), ([0, 0, 0, (4 << 2) | S], 16, 72), ([(6 << 2) | S, 0, (9 << 2) | S, (4 << 2) | S], 16, 73)]:
+        iq, _ = orc.transmit_vcm(pls, nframes, seed=seed, **common)
+        rx = orc.OracleRx(orc.default_cfg(4, 1, 0, acm_vcm=1))
+        frames = [np.asarray(f).reshape(-1) for f in rx.process(iq)]
+        streams.append((iq, np.concatenate(frames + [np.zeros(0, np.uint8)]), [stats_key(x, 'vcm') for x in rx.tap(4)], sorted({f.size for f in frames})))
+    print('oracle: frames per stream', [len(s[2]) for s in streams], 'BBFRAME sizes', [s[3] for s in streams])
+    # what makes the case: (a) has frames and no BBFRAME, (c) BBFRAMEs of at least two sizes
+    assert len(streams[0][2]) >= 1 and streams[0][1].size == 0 and len(streams[2][3]) >= 2, [(len(s[2]), s[3]) for s in streams]
+    assert all(s[0].size < 250000 for s in streams)
+    cfg = lambda: engine.default_cfg(4, True, False, acm_vcm=1)
+    dm = engine.demod(cfg(), max_samples=streams[0][0].size)
+    try:
+        got = dm.process(streams[0][0])
+        assert len(got) == 0 and [stats_key(x, 'vcm') for x in dm.stats()] == streams[0][2]
+    finally:
+        dm.close()
+    cap = max(s[0].size for s in streams) // 2 + 100000
+    for pipelined in (False, True):
+        dms = [engine.demod(cfg(), max_samples=s[0].size) for s in streams]
+        tout = [torch.zeros(cap, dtype=torch.uint8, device='cuda') for _ in streams]
+        engine.set_pipelined(pipelined)
+        try:
+            nb = engine.process_batch(dms, [torch.from_numpy(s[0]).cuda() for s in streams], tout)
+            if pipelined:       # the call's job is delivered by the next call
+                assert sum(nb) == 0 and all(len(d.stats()) == 0 for d in dms)
+                nb = engine.process_batch(dms, [torch.empty(0, dtype=torch.complex64, device='cuda') for _ in streams], tout)
+            for i, (d, s) in enumerate(zip(dms, streams)):
+                assert np.array_equal(tout[i][:nb[i]].cpu().numpy(), s[1]), (pipelined, i)
+                assert [stats_key(x, 'vcm') for x in d.stats()] == s[2], (pipelined, i)
+        finally:
+            engine.set_pipelined(False)
+            for d in dms:
+                d.close()
+
+
 def test_pipelined_batch_whose_streams_come_and_go(engine, pkg):
     """throughput mode with a stream set that changes from call to call: a stream that joins starts with nothing pending, the streams that stay get the
     frames of the previous call whatever their new position in the batch, a stream that is absent from the call after its own loses that call's
