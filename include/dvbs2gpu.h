@@ -154,6 +154,45 @@ int dvbs2gpu_fec_decode_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, cons
                               int max_trials, int force, uint8_t* d_bbframes, int32_t* d_trials, int32_t* d_corrections,
                               void* stream);
 
+/* ------------------------------------------------------------------ FEC encoder and per-frame channel BER
+ * The transmit-side FEC of ETSI EN 302 307-1 on the device, stage by stage and as one call.  The reference has no usable counterpart (its
+ * BBFrameLDPC::encode produces non-codewords for some rates), so each entry cites the clause of the standard it implements.  Frames are packed
+ * bits, MSB first; a code word's bit order is the order dvbs2gpu_ldpc_decode_batch reads its d_llr in.  Errors: an unknown (rate, shortframes), a NULL
+ * pointer, a negative frame count or a bad amplitude return DVBS2GPU_ERR_ARG with a dvbs2gpu_last_error() text, before anything is enqueued;
+ * nframes == 0 succeeds without a launch. */
+
+/* BB scrambling, clause 5.2.2: the inverse of dvbs2gpu_bb_descramble_batch (the same PRBS, XOR).
+ * d_bbframes [nframes][kbch/8] -> d_out [nframes][K/8], the BCH parity area zeroed. */
+int dvbs2gpu_bb_scramble_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, const uint8_t* d_bbframes, int nframes, uint8_t* d_out, void* stream);
+
+/* BCH encoding, clause 5.3.1: the inverse of dvbs2gpu_bch_decode_batch.  d_frames [nframes][K/8]: the first kbch bits are the message,
+ * the K - kbch parity bits m(x) x^(K - kbch) mod g(x) are written behind them in place. */
+int dvbs2gpu_bch_encode_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, uint8_t* d_frames, int nframes, void* stream);
+
+/* LDPC encoding, clause 5.3.2: the inverse of dvbs2gpu_ldpc_decode_batch's hard output.  d_info [nframes][K/8] -> d_code [nframes][N/8]:
+ * the K information bits, then the parity bits. */
+int dvbs2gpu_ldpc_encode_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, const uint8_t* d_info, int nframes, uint8_t* d_code, void* stream);
+
+/* All three (clauses 5.2.2, 5.3.1, 5.3.2): the inverse of dvbs2gpu_fec_decode_batch.  d_bbframes [nframes][kbch/8] -> d_code [nframes][N/8].
+ * With d_llr non-NULL also [nframes][N] int8: +amplitude for bit 0, -amplitude for bit 1 (1 <= amplitude <= 127) -- the decoder's input
+ * with no host in between. */
+int dvbs2gpu_fec_encode_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, const uint8_t* d_bbframes, int nframes, uint8_t* d_code,
+                              int8_t* d_llr, int amplitude, void* stream);
+
+/* Channel bit errors per frame: the BBFRAMEs a decoder delivered are encoded again (clauses 5.2.2, 5.3.1, 5.3.2 -- the inverse of the
+ * dvbs2gpu_fec_decode_batch call that made them) and compared with the hard decisions of the LLRs that decoder read (bit 1 <=> negative).
+ * d_llr [nframes][N], d_bbframes [nframes][kbch/8] -> d_counted [nframes]: LLRs that are not 0 (a 0 is an erasure and left out);
+ * d_errors [nframes]: those among them whose sign is not the code bit.  d_corrections [nframes] or NULL: the decoder's BCH results; a frame
+ * with a negative entry gets errors -1, counted 0 (its BBFRAME is not the transmitted one). */
+int dvbs2gpu_fec_channel_ber_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, const int8_t* d_llr, const uint8_t* d_bbframes,
+                                   const int32_t* d_corrections, int nframes, int32_t* d_errors, int32_t* d_counted, void* stream);
+
+/* Host-only dump of the encoder's rules (csrc/fec_encode_rules.h; no GPU needed).  bch_generator (or NULL): the K - kbch + 1 coefficients of
+ * g(x), x^0 first.  counts: int32 [80] = {BCH parity bits, BCH chunks per frame, bytes per chunk, frames per workgroup of the BCH kernel, of the
+ * LDPC kernel, LDPC layers, information-bit links, workgroups per launch at the most, frames per pass of the channel BER, number of chunk seams,
+ * 0 .. [16 + k]: frame bit at which the k-th chunk seam lies}. */
+int dvbs2gpu_fec_encode_plan_dump(int rate, int shortframes, uint8_t* bch_generator, int32_t* counts);
+
 /* ------------------------------------------------------------------ soft demap + bit de-interleave
  * replaces S2BBToSoft::process (dvbs2_bb_to_soft.cpp:7-33): constellation_t::demod_soft_lut per payload
  * symbol (constellation.cpp:293-322) followed by S2Deinterleaver::deinterleave (s2_deinterleaver.cpp:72-136).

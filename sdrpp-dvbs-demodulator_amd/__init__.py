@@ -394,6 +394,12 @@ PROTOTYPES = {
     'dvbs2gpu_bch_decode_batch': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     'dvbs2gpu_bb_descramble_batch': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     'dvbs2gpu_fec_decode_batch': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'dvbs2gpu_bb_scramble_batch': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    'dvbs2gpu_bch_encode_batch': (_i, [_vp, _i, _i, _vp, _i, _vp]),
+    'dvbs2gpu_ldpc_encode_batch': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    'dvbs2gpu_fec_encode_batch': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
+    'dvbs2gpu_fec_channel_ber_batch': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    'dvbs2gpu_fec_encode_plan_dump': (_i, [_i, _i, _vp, C.POINTER(C.c_int32)]),
     'dvbs2gpu_demap_batch': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'dvbs2gpu_deinterleave_batch': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     'dvbs2gpu_set_stage_timing': (_i, [_vp, _i]),
@@ -662,6 +668,27 @@ def ldpc_split_plan(rate, shortframes=False):
             'ent_off': layers[:, 3].astype(int), 'table': table[:npl * 768 * npw].reshape(npl, 768, npw), 'words': table, 'row_of': row_of, 'layer': layer_of}
 
 
+def fec_encode_plan(rate, shortframes=False):
+    """Host-only: the FEC encoder's rules for one code (csrc/fec_encode_rules.h) -> dict: 'generator' the BCH generator polynomial as uint8 coefficients, x^0
+    first; 'parity_bits', 'bch_chunks', 'chunk_bytes', 'bch_frames_per_workgroup', 'ldpc_frames_per_workgroup', 'layers', 'links', 'max_workgroups',
+    'ber_chunk_frames'; 'seams': the frame bits at which a chunk of the BCH kernel begins inside the message"""
+    import numpy as np
+    lib = load_library()
+    cnt = (C.c_int32 * 80)()
+    rc = lib.dvbs2gpu_fec_encode_plan_dump(int(rate), int(bool(shortframes)), None, cnt)
+    if rc != 0:
+        raise Dvbs2GpuError(rc, lib.dvbs2gpu_last_error().decode())
+    gen = np.zeros(cnt[0] + 1, np.uint8)
+    rc = lib.dvbs2gpu_fec_encode_plan_dump(int(rate), int(bool(shortframes)), gen.ctypes.data, cnt)
+    if rc != 0:
+        raise Dvbs2GpuError(rc, lib.dvbs2gpu_last_error().decode())
+    keys = ['parity_bits', 'bch_chunks', 'chunk_bytes', 'bch_frames_per_workgroup', 'ldpc_frames_per_workgroup', 'layers', 'links', 'max_workgroups', 'ber_chunk_frames']
+    d = dict(zip(keys, list(cnt)[:9]))
+    d['generator'] = gen
+    d['seams'] = [int(x) for x in list(cnt)[16:16 + cnt[9]]]
+    return d
+
+
 class FleetEntry(C.Structure):
     """dvbs2gpu_fleet_entry"""
     _fields_ = [('cfg', DemodCfg), ('weight', C.c_double), ('max_samples', C.c_int32), ('reserved', C.c_int32)]
@@ -863,6 +890,68 @@ class Engine:
         self._check(self.lib.dvbs2gpu_fec_decode_batch(self.h, int(rate), int(bool(shortframes)), _ptr(llr), F, int(max_trials),
                                                        int(bool(force)), _ptr(out), _ptr(trials), _ptr(corr), self._stream()))
         return out, trials, corr
+
+    # ---- FEC encoder: the inverses of the stages above, and the per-frame channel BER made from them
+    def bb_scramble(self, bbframes, rate, shortframes=False):
+        """bbframes uint8 [F, kbch/8] -> scrambled frames uint8 [F, K/8], the BCH parity area zeroed"""
+        t = self.torch
+        fi = fec_info(rate, shortframes)
+        assert bbframes.dtype == t.uint8 and bbframes.is_cuda and bbframes.is_contiguous() and bbframes.shape[1] == fi['kbch'] // 8
+        out = t.empty((bbframes.shape[0], fi['ldpc_k'] // 8), dtype=t.uint8, device=bbframes.device)
+        self._check(self.lib.dvbs2gpu_bb_scramble_batch(self.h, int(rate), int(bool(shortframes)), _ptr(bbframes), bbframes.shape[0], _ptr(out), self._stream()))
+        return out
+
+    def bch_encode(self, frames, rate, shortframes=False):
+        """frames uint8 [F, K/8]: the BCH parity of the first kbch bits is written behind them in place -> frames"""
+        t = self.torch
+        fi = fec_info(rate, shortframes)
+        assert frames.dtype == t.uint8 and frames.is_cuda and frames.is_contiguous() and frames.shape[1] == fi['ldpc_k'] // 8
+        self._check(self.lib.dvbs2gpu_bch_encode_batch(self.h, int(rate), int(bool(shortframes)), _ptr(frames), frames.shape[0], self._stream()))
+        return frames
+
+    def ldpc_encode(self, info, rate, shortframes=False, out=None):
+        """info uint8 [F, K/8] -> code words uint8 [F, N/8]"""
+        t = self.torch
+        fi = fec_info(rate, shortframes)
+        assert info.dtype == t.uint8 and info.is_cuda and info.is_contiguous() and info.shape[1] == fi['ldpc_k'] // 8
+        if out is None:
+            out = t.empty((info.shape[0], fi['ldpc_n'] // 8), dtype=t.uint8, device=info.device)
+        assert out.dtype == t.uint8 and out.is_cuda and out.is_contiguous() and out.shape[1] == fi['ldpc_n'] // 8 and out.shape[0] >= info.shape[0]
+        self._check(self.lib.dvbs2gpu_ldpc_encode_batch(self.h, int(rate), int(bool(shortframes)), _ptr(info), info.shape[0], _ptr(out), self._stream()))
+        return out
+
+    def fec_encode(self, bbframes, rate, shortframes=False, amplitude=None, out=None, llr=None):
+        """bbframes uint8 [F, kbch/8] -> (code words uint8 [F, N/8], LLRs int8 [F, N] of +-amplitude, or None without an amplitude)"""
+        t = self.torch
+        fi = fec_info(rate, shortframes)
+        assert bbframes.dtype == t.uint8 and bbframes.is_cuda and bbframes.is_contiguous() and bbframes.shape[1] == fi['kbch'] // 8
+        F = bbframes.shape[0]
+        if out is None:
+            out = t.empty((F, fi['ldpc_n'] // 8), dtype=t.uint8, device=bbframes.device)
+        assert out.dtype == t.uint8 and out.is_cuda and out.is_contiguous() and out.shape[1] == fi['ldpc_n'] // 8 and out.shape[0] >= F
+        if amplitude is not None and llr is None:
+            llr = t.empty((F, fi['ldpc_n']), dtype=t.int8, device=bbframes.device)
+        if amplitude is not None:
+            assert llr.dtype == t.int8 and llr.is_cuda and llr.is_contiguous() and llr.shape[1] == fi['ldpc_n'] and llr.shape[0] >= F
+        self._check(self.lib.dvbs2gpu_fec_encode_batch(self.h, int(rate), int(bool(shortframes)), _ptr(bbframes), F, _ptr(out),
+                                                       _ptr(llr) if amplitude is not None else None, int(amplitude or 0), self._stream()))
+        return out, (llr if amplitude is not None else None)
+
+    def channel_ber(self, llr, bbframes, rate, shortframes=False, corrections=None):
+        """llr int8 [F, N] (what the decoder read), bbframes uint8 [F, kbch/8] (what it delivered), corrections int32 [F] (its BCH results) or None
+        -> (errors int32 [F], counted int32 [F]); a frame with a negative correction count gives (-1, 0)"""
+        t = self.torch
+        fi = fec_info(rate, shortframes)
+        assert llr.dtype == t.int8 and llr.is_cuda and llr.is_contiguous() and llr.shape[1] == fi['ldpc_n']
+        F = llr.shape[0]
+        assert bbframes.dtype == t.uint8 and bbframes.is_cuda and bbframes.is_contiguous() and bbframes.shape == (F, fi['kbch'] // 8)
+        if corrections is not None:
+            assert corrections.dtype == t.int32 and corrections.is_cuda and corrections.is_contiguous() and corrections.shape == (F,)
+        errors = t.empty((F,), dtype=t.int32, device=llr.device)
+        counted = t.empty((F,), dtype=t.int32, device=llr.device)
+        self._check(self.lib.dvbs2gpu_fec_channel_ber_batch(self.h, int(rate), int(bool(shortframes)), _ptr(llr), _ptr(bbframes), _ptr(corrections), F,
+                                                            _ptr(errors), _ptr(counted), self._stream()))
+        return errors, counted
 
     def demap(self, frames, modcod, shortframes=False, pilots=False):
         """frames complex64 [F, plframe] (PLL output) -> LLR int8 [F, N]"""

@@ -2,6 +2,7 @@
 // Host-side only logic here; kernels live in *_kernel.hip.  No CPU fallback: without a HIP device
 // dvbs2gpu_create fails with DVBS2GPU_ERR_NODEVICE.
 #include "ctx.h"
+#include "fec_encode_rules.h"
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
@@ -208,6 +209,28 @@ int get_prbs(dvbs2gpu_ctx* ctx) {
         if (b) sr |= 0x4000;
     }
     return upload(seq, ctx->d_prbs);
+}
+
+// the encoder's tables of one code (fec_encode_rules.h)
+int get_fec_enc(dvbs2gpu_ctx* ctx, const FecParams& f, FecEncDeviceCode** out) {
+    std::lock_guard<std::mutex> l(ctx->mtx);
+    auto it = ctx->fec_enc.find(f.code_index);
+    if (it == ctx->fec_enc.end()) {
+        const fecenc::BchRules B = fecenc::build_bch_rules(f.bch_m, f.bch_t);
+        if (B.P != f.K - f.kbch) { last_error() = "BCH generator polynomial: wrong degree"; return DVBS2GPU_ERR_ARG; }
+        const fecenc::BchChunkPlan CP = fecenc::build_bch_chunk_plan(B, f.kbch);
+        const fecenc::LdpcEncodePlan LP = fecenc::build_ldpc_encode_plan(f.code_index);
+        FecEncCode D;
+        D.N = f.N; D.K = f.K; D.kbch = f.kbch; D.P = B.P; D.q = LP.q; D.blocks = LP.blocks; D.chunk_bytes = CP.chunk_bytes;
+        int rc;
+        if ((rc = upload(B.byte_tab, D.byte_tab, &D.d_byte_tab))) return rc;
+        if ((rc = upload(CP.rows, D.rows, &D.d_rows))) return rc;
+        if ((rc = upload(LP.layer_off, D.layer_off, &D.d_layer_off))) return rc;
+        if ((rc = upload(LP.ent, D.ent, &D.d_ent))) return rc;
+        it = ctx->fec_enc.emplace(f.code_index, std::move(D)).first;
+    }
+    *out = &it->second;
+    return 0;
 }
 }  // namespace s2
 
@@ -626,6 +649,116 @@ int dvbs2gpu_fec_decode_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, cons
     rc = fec_run(ctx, f, d_llr, nframes, max_trials, force, d_bbframes, d_trials, d_corrections, (hipStream_t)stream, nullptr);
     int rc2 = ws_release(ctx, (hipStream_t)stream);
     return rc ? rc : rc2;
+}
+
+// ---- the FEC encoder (fec_encode.hip): every argument is looked at before anything is enqueued
+static int enc_bad(const char* who, const char* what) { g_err = std::string(who) + ": " + what; return DVBS2GPU_ERR_ARG; }
+static int enc_args(const char* who, dvbs2gpu_ctx* ctx, int rate, int shortframes, int nframes, FecParams* f) {
+    if (!ctx) return enc_bad(who, "no context");
+    if (nframes < 0) return enc_bad(who, "negative frame count");
+    if (!fec_params(rate, shortframes, f)) return enc_bad(who, "no such code (rate 0..10; short frames have no rate 9/10)");
+    return 0;
+}
+// BBFRAMEs -> code words at d_code (rows `stride` bytes apart): the scrambled frame and its BCH parity are made in the row itself, the LDPC parity behind them
+static int fec_encode_run(dvbs2gpu_ctx* ctx, const FecParams& f, const uint8_t* d_bbframes, int nframes, uint8_t* d_code, hipStream_t st) {
+    FecEncDeviceCode* E;
+    RC_TRY(get_fec_enc(ctx, f, &E));
+    RC_TRY(get_prbs(ctx));
+    const size_t stride = (size_t)f.N / 8;
+    HIP_TRY(bb_scramble_launch(d_bbframes, f.kbch / 8, ctx->d_prbs, nframes, d_code, stride, f.K / 8, st));
+    HIP_TRY(bch_encode_launch(*E, d_code, stride, nframes, st));
+    HIP_TRY(ldpc_encode_launch(*E, d_code, stride, d_code, stride, nframes, st));
+    return 0;
+}
+
+int dvbs2gpu_bb_scramble_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, const uint8_t* d_bbframes, int nframes, uint8_t* d_out, void* stream) {
+    FecParams f;
+    RC_TRY(enc_args("bb_scramble_batch", ctx, rate, shortframes, nframes, &f));
+    if (nframes == 0) return 0;
+    if (!d_bbframes || !d_out) return enc_bad("bb_scramble_batch", "null pointer");
+    CallGuard guard(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    RC_TRY(get_prbs(ctx));
+    HIP_TRY(bb_scramble_launch(d_bbframes, f.kbch / 8, ctx->d_prbs, nframes, d_out, (size_t)f.K / 8, f.K / 8, (hipStream_t)stream));
+    return 0;
+}
+
+int dvbs2gpu_bch_encode_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, uint8_t* d_frames, int nframes, void* stream) {
+    FecParams f;
+    RC_TRY(enc_args("bch_encode_batch", ctx, rate, shortframes, nframes, &f));
+    if (nframes == 0) return 0;
+    if (!d_frames) return enc_bad("bch_encode_batch", "null pointer");
+    CallGuard guard(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    FecEncDeviceCode* E;
+    RC_TRY(get_fec_enc(ctx, f, &E));
+    HIP_TRY(bch_encode_launch(*E, d_frames, (size_t)f.K / 8, nframes, (hipStream_t)stream));
+    return 0;
+}
+
+int dvbs2gpu_ldpc_encode_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, const uint8_t* d_info, int nframes, uint8_t* d_code, void* stream) {
+    FecParams f;
+    RC_TRY(enc_args("ldpc_encode_batch", ctx, rate, shortframes, nframes, &f));
+    if (nframes == 0) return 0;
+    if (!d_info || !d_code) return enc_bad("ldpc_encode_batch", "null pointer");
+    if ((const uint8_t*)d_code == d_info) return enc_bad("ldpc_encode_batch", "d_info and d_code are the same buffer (their rows differ in length)");
+    CallGuard guard(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    FecEncDeviceCode* E;
+    RC_TRY(get_fec_enc(ctx, f, &E));
+    HIP_TRY(ldpc_encode_launch(*E, d_info, (size_t)f.K / 8, d_code, (size_t)f.N / 8, nframes, (hipStream_t)stream));
+    return 0;
+}
+
+int dvbs2gpu_fec_encode_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, const uint8_t* d_bbframes, int nframes, uint8_t* d_code, int8_t* d_llr,
+                              int amplitude, void* stream) {
+    FecParams f;
+    RC_TRY(enc_args("fec_encode_batch", ctx, rate, shortframes, nframes, &f));
+    if (d_llr && (amplitude < 1 || amplitude > 127)) return enc_bad("fec_encode_batch", "amplitude outside 1..127");
+    if (nframes == 0) return 0;
+    if (!d_bbframes || !d_code) return enc_bad("fec_encode_batch", "null pointer");
+    CallGuard guard(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    RC_TRY(fec_encode_run(ctx, f, d_bbframes, nframes, d_code, (hipStream_t)stream));
+    if (d_llr) HIP_TRY(fec_llr_launch(d_code, f.N, nframes, amplitude, d_llr, (hipStream_t)stream));
+    return 0;
+}
+
+int dvbs2gpu_fec_channel_ber_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes, const int8_t* d_llr, const uint8_t* d_bbframes,
+                                   const int32_t* d_corrections, int nframes, int32_t* d_errors, int32_t* d_counted, void* stream) {
+    FecParams f;
+    RC_TRY(enc_args("fec_channel_ber_batch", ctx, rate, shortframes, nframes, &f));
+    if (nframes == 0) return 0;
+    if (!d_llr || !d_bbframes || !d_errors || !d_counted) return enc_bad("fec_channel_ber_batch", "null pointer");
+    CallGuard guard(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    int rc = stage_enter(ctx, st);      // the re-encoded code words take the hard-decision scratch of the context
+    if (rc) return rc;
+    const int chunk = std::min(nframes, fecenc::BER_CHUNK_FRAMES);
+    rc = ctx->fws.hard.ensure((size_t)chunk * (f.N / 8));
+    uint8_t* code = (uint8_t*)ctx->fws.hard.p;
+    for (int a = 0; a < nframes && !rc; a += chunk) {
+        const int n = std::min(chunk, nframes - a);
+        rc = fec_encode_run(ctx, f, d_bbframes + (size_t)a * (f.kbch / 8), n, code, st);
+        if (!rc) {
+            hipError_t e = fec_channel_ber_launch(d_llr + (size_t)a * f.N, code, f.N, d_corrections ? d_corrections + a : nullptr, n, d_errors + a, d_counted + a, st);
+            if (e != hipSuccess) rc = fail_hip(e, "fec_channel_ber_launch");
+        }
+    }
+    int rc2 = ws_release(ctx, st);
+    return rc ? rc : rc2;
+}
+
+int dvbs2gpu_fec_encode_plan_dump(int rate, int shortframes, uint8_t* bch_generator, int32_t* counts) {
+    FecParams f;
+    if (!fec_params(rate, shortframes, &f)) return enc_bad("fec_encode_plan_dump", "no such code (rate 0..10; short frames have no rate 9/10)");
+    if (!counts) return enc_bad("fec_encode_plan_dump", "null pointer");
+    const fecenc::BchRules B = fecenc::build_bch_rules(f.bch_m, f.bch_t);
+    if (B.P != f.K - f.kbch) return enc_bad("fec_encode_plan_dump", "BCH generator polynomial: wrong degree");
+    fecenc::plan_counts(f, fecenc::bch_chunk_cut(f.kbch), fecenc::build_ldpc_encode_plan(f.code_index), counts);      // (the cut alone: the chunk-shift rows are the device's business)
+    if (bch_generator) memcpy(bch_generator, B.gen.data(), B.gen.size());
+    return 0;
 }
 
 }  // extern "C"

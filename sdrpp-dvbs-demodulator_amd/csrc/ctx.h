@@ -119,7 +119,7 @@ struct BankArgs {
 
 // What a kernel reads is a plain struct of raw pointers, passed by value or copied to the device; the context's caches hold it together
 // with the owners of the tables it points to (a launch takes the plain part: `*C` slices to it).
-static_assert(std::is_trivially_copyable_v<LdpcDeviceCode> && std::is_trivially_copyable_v<BchDeviceCode>, "kernel-visible structs stay plain");
+static_assert(std::is_trivially_copyable_v<LdpcDeviceCode> && std::is_trivially_copyable_v<BchDeviceCode> && std::is_trivially_copyable_v<FecEncDeviceCode>, "kernel-visible structs stay plain");
 static_assert(std::is_trivially_copyable_v<S2ConstelDev> && std::is_trivially_copyable_v<S2PlTablesDev>, "kernel-visible structs stay plain");
 struct LdpcCode : LdpcDeviceCode {
     DevBuf<LdpcLayerDesc> layers;
@@ -128,6 +128,7 @@ struct LdpcCode : LdpcDeviceCode {
     DevBuf<LdpcSplitLayer> split_layers;
 };
 struct BchCode : BchDeviceCode { DevBuf<uint16_t> log, exp, imap, syn_tab; };
+struct FecEncCode : FecEncDeviceCode { DevBuf<uint32_t> byte_tab, rows, layer_off, ent; };     // the encoder's tables of one code (fec_encode_rules.h)
 struct ConstelTables {          // device tables of one constellation (type, gamma1, gamma2)
     S2ConstelDev dev;
     DevBuf<int8_t> bits;
@@ -248,6 +249,8 @@ struct dvbs2gpu_ctx {
     s2::DevBuf<float> d_fd_bank;              // COMPLEX_FD interpolator bank, 256 x 256
     std::map<int, s2::DevBuf<s2::cf32>> bandedge;    // FLL band-edge taps [2][ntaps] by ntaps*100000 + round(alpha*1000)*10 + sps
     s2::Workspace ws_dvbs[4];
+    // FEC encoder (fec_encode.hip): the tables of a code, by code_index
+    std::map<int, s2::FecEncCode> fec_enc;
 };
 
 namespace s2 {
@@ -264,6 +267,7 @@ int apply_option(dvbs2gpu_ctx* ctx, const char* name, int value);   // 0, or -1:
 int get_ldpc(dvbs2gpu_ctx* ctx, int code_index, LdpcDeviceCode** out);
 int get_bch(dvbs2gpu_ctx* ctx, int m, int t, BchDeviceCode** out);
 int get_prbs(dvbs2gpu_ctx* ctx);
+int get_fec_enc(dvbs2gpu_ctx* ctx, const FecParams& f, FecEncDeviceCode** out);
 // LLR -> BBFRAME for nframes frames of one code; all pointers device
 std::vector<float> make_polyphase_bank(int phases, int taps_per_phase);
 int get_rrc(dvbs2gpu_ctx* ctx, int ntaps, float alpha, double Ts, float** out);

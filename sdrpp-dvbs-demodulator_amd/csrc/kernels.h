@@ -80,6 +80,26 @@ hipError_t bch_correct_launch(const BchDeviceCode& C, uint8_t* frames, int frame
 hipError_t bb_descramble_launch(const uint8_t* frames, int frame_stride, const uint8_t* prbs, int out_bytes, int nframes,
                                 uint8_t* out, hipStream_t stream);
 
+// ------------------------------------------------------------------ FEC encoder and channel-error count (fec_encode.hip, rules: fec_encode_rules.h)
+struct FecEncDeviceCode {               // one (rate, frame kind)
+    int N = 0, K = 0, kbch = 0, P = 0;  // P = K - kbch, the BCH parity bits
+    int q = 0, blocks = 0;              // LDPC layers, 360-bit information blocks
+    int chunk_bytes = 0;                // BCH: message bytes per lane
+    const uint32_t* d_byte_tab = nullptr;   // [256][6]  v(x) x^P mod g
+    const uint32_t* d_rows = nullptr;       // [64][P][6] chunk-shift rows
+    const uint32_t* d_layer_off = nullptr;  // [q + 1]
+    const uint32_t* d_ent = nullptr;        // links r << 16 | sp
+};
+// frames lie `stride` bytes apart; every launch takes at most `max_wg` workgroups, which share the frames between them
+hipError_t bb_scramble_launch(const uint8_t* bbframes, int kb_bytes, const uint8_t* prbs, int nframes, uint8_t* out, size_t out_stride, int out_bytes,
+                              hipStream_t stream);       // out[f][0, kb_bytes) = bbframes[f] ^ prbs, [kb_bytes, out_bytes) = 0
+hipError_t bch_encode_launch(const FecEncDeviceCode& C, uint8_t* frames, size_t stride, int nframes, hipStream_t stream);     // parity into [kbch / 8, K / 8)
+hipError_t ldpc_encode_launch(const FecEncDeviceCode& C, const uint8_t* info, size_t info_stride, uint8_t* code, size_t code_stride, int nframes,
+                              hipStream_t stream);       // info == code (same stride): the parity is written behind the information bits in place
+hipError_t fec_llr_launch(const uint8_t* code, int N, int nframes, int amplitude, int8_t* llr, hipStream_t stream);
+hipError_t fec_channel_ber_launch(const int8_t* llr, const uint8_t* code, int N, const int32_t* corrections, int nframes, int32_t* errors, int32_t* counted,
+                                  hipStream_t stream);
+
 // ------------------------------------------------------------------ DVB-S inner code (dvbs_kernels.hip)
 // One Viterbi_DVBS object (viterbi_all.h:33-160) per stream; decoders 0-4 = BER-test decoders (rates 1/2,2/3,3/4,5/6,7/8),
 // 5-9 = main decoders; dep[0] = Depunc23, dep[1] = Depunc56.

@@ -41,12 +41,12 @@ struct ModcodParams {
 };
 
 // kbch for normal frames, indexed by Rate (ETSI table 5a), and BCH t.
-static const int KBCH_NORMAL[RATE_COUNT] = {16008, 21408, 25728, 32208, 38688, 43040, 48408, 51648, 53840, 57472, 58192};
-static const int NBCH_NORMAL[RATE_COUNT] = {16200, 21600, 25920, 32400, 38880, 43200, 48600, 51840, 54000, 57600, 58320};
+static constexpr int KBCH_NORMAL[RATE_COUNT] = {16008, 21408, 25728, 32208, 38688, 43040, 48408, 51648, 53840, 57472, 58192};
+static constexpr int NBCH_NORMAL[RATE_COUNT] = {16200, 21600, 25920, 32400, 38880, 43200, 48600, 51840, 54000, 57600, 58320};
 static const int BCH_T_NORMAL[RATE_COUNT] = {12, 12, 12, 12, 12, 10, 12, 12, 10, 8, 8};
 // short frames (ETSI table 5b); 9/10 does not exist for short frames
-static const int KBCH_SHORT[RATE_COUNT] = {3072, 5232, 6312, 7032, 9552, 10632, 11712, 12432, 13152, 14232, 0};
-static const int NBCH_SHORT[RATE_COUNT] = {3240, 5400, 6480, 7200, 9720, 10800, 11880, 12600, 13320, 14400, 0};
+static constexpr int KBCH_SHORT[RATE_COUNT] = {3072, 5232, 6312, 7032, 9552, 10632, 11712, 12432, 13152, 14232, 0};
+static constexpr int NBCH_SHORT[RATE_COUNT] = {3240, 5400, 6480, 7200, 9720, 10800, 11880, 12600, 13320, 14400, 0};
 
 inline bool fec_params(int rate, int shortframe, FecParams* out) {
     if (rate < 0 || rate >= RATE_COUNT) return false;
