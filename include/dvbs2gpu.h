@@ -193,6 +193,65 @@ int dvbs2gpu_fec_channel_ber_batch(dvbs2gpu_ctx* ctx, int rate, int shortframes,
  * 0 .. [16 + k]: frame bit at which the k-th chunk seam lies}. */
 int dvbs2gpu_fec_encode_plan_dump(int rate, int shortframes, uint8_t* bch_generator, int32_t* counts);
 
+/* ------------------------------------------------------------------ modulator: code words -> PLFRAME symbols -> 2-sps IQ -> channel
+ * The transmit side behind the FEC encoder (ETSI EN 302 307-1 clauses 5.3.3 bit interleaver, 5.4 mapping, 5.5 PL framing with pilots and PL
+ * scrambling, 5.6 root-raised-cosine shaping) and a small channel stage, so that a test signal is made where the receiver reads it.  The rules
+ * are stated once in csrc/s2_tx_rules.h and run unchanged in the kernels and in dvbs2gpu_s2_tx_host.
+ * A frame is named by its PLS code, pls = modcod << 2 | short << 1 | pilots; modcod 0 is the dummy PLFRAME (3330 symbols, no BBFRAME, no code
+ * word).  The PLS list `pls` (host, [nframes]) is shared by the streams of a call.  Symbols and IQ are interleaved (re, im) float pairs.
+ * Errors: a PLS code that names no frame (MODCODs 29..31, short 9/10, outside 0..127), a NULL pointer, a negative count, a roll-off other than
+ * 0.35 / 0.25 / 0.20, a timing outside -2..2, an output that is not 16-byte aligned return DVBS2GPU_ERR_ARG with a dvbs2gpu_last_error() text
+ * before anything is enqueued; a count of 0 succeeds without a launch. */
+
+/* Host-only: the sizes of one stream's block for a PLS list.  Any output may be NULL. */
+int dvbs2gpu_s2_tx_sizes(const int32_t* pls, int nframes, long long* symbols, long long* bbframe_bytes, long long* code_bytes);
+
+/* Code words -> PL symbols, d_symbols [nstreams][symbols] (16-byte aligned).  The code word (N/8 bytes, packed MSB first, the bit order of
+ * dvbs2gpu_fec_encode_batch) of frame f, stream s is read at d_code + code_off[f] + s * code_stride[f] (host arrays [nframes], bytes; entries of
+ * dummy frames are ignored), so stream-major and frame-major buffers both work.  Both NULL: [nstreams][code_bytes], a stream's code words one
+ * behind the other.  A code word may lie at any byte alignment: the kernel loads the aligned 32-bit words that hold it, so up to 3 bytes in
+ * front of its first byte and up to 3 behind its last, inside those words, are read and discarded (never a word that holds no code byte). */
+int dvbs2gpu_pl_frame_batch(dvbs2gpu_ctx* ctx, const int32_t* pls, int nframes, const uint8_t* d_code, const long long* code_off,
+                            const long long* code_stride, int nstreams, float* d_symbols, void* stream);
+
+/* Symbols [nstreams][symbols] -> IQ at 2 samples per symbol, d_iq [nstreams][2 * symbols] (16-byte aligned, not d_symbols).  Sample n sits at
+ * symbol time (n - timing) / 2; the pulse is the unit-energy RRC of the given roll-off cut at +-16 symbols.  Symbols outside the block count
+ * as 0, or wrap around with circular != 0 (the block can then be repeated as a seamless stream). */
+int dvbs2gpu_pulse_shape_batch(dvbs2gpu_ctx* ctx, const float* d_symbols, int nstreams, long long symbols, double rolloff, double timing,
+                               int circular, float* d_iq, void* stream);
+
+/* Channel, in place on d_iq [nstreams][nsamples]: sample n of stream s is rotated by phase0[s] + cfo[s] * n (rad, rad/sample) and gets white
+ * Gaussian noise of per-dimension sigma sqrt(10^(-esn0_db[s] / 10)) -- Es/N0 behind a unit-energy matched filter at 2 samples per symbol;
+ * esn0_db >= 100: none; esn0_db >= -50, |cfo| <= 4, |phase0| <= 1e6 -- from a counter-based generator: the noise is a function of (seed[s], s, n) alone, the same for every launch shape.
+ * The four arrays are host arrays [nstreams]. */
+int dvbs2gpu_channel_batch(dvbs2gpu_ctx* ctx, float* d_iq, int nstreams, long long nsamples, const double* esn0_db, const double* cfo,
+                           const double* phase0, const uint64_t* seed, void* stream);
+
+typedef struct dvbs2gpu_tx_channel {    /* the channel's host arrays, [nstreams] each */
+    const double* esn0_db;
+    const double* cfo;
+    const double* phase0;
+    const uint64_t* seed;
+} dvbs2gpu_tx_channel;
+
+/* BBFRAMEs -> IQ in one call: dvbs2gpu_fec_encode_batch's stages, PL framing, shaping, and the channel when `channel` is not NULL.
+ * d_bbframes is frame-major, [frame][stream][kbch_f / 8] (dummy frames take no bytes); d_iq [nstreams][2 * symbols].  Frames of one code that
+ * follow one another share one set of encoder launches (a CCM call makes one).  The code words and symbols in between live in buffers of the
+ * context. */
+int dvbs2gpu_s2_modulate_batch(dvbs2gpu_ctx* ctx, const int32_t* pls, int nframes, const uint8_t* d_bbframes, int nstreams, double rolloff,
+                               double timing, int circular, const dvbs2gpu_tx_channel* channel, float* d_iq, void* stream);
+
+/* Host-only, no GPU: the same rules on the CPU for one stream, every pointer a host pointer.  code: the frames' code words one behind the
+ * other (code_bytes of dvbs2gpu_s2_tx_sizes).  symbols [2 * symbols] floats and iq [4 * symbols] floats may each be NULL; channel (one entry
+ * per array) may be NULL; stream_index is the s of dvbs2gpu_channel_batch. */
+int dvbs2gpu_s2_tx_host(const int32_t* pls, int nframes, const uint8_t* code, double rolloff, double timing, int circular,
+                        const dvbs2gpu_tx_channel* channel, long long stream_index, float* symbols, float* iq);
+
+/* Host-only: the last two stages of dvbs2gpu_s2_tx_host on their own, for any block (host pointers).  Shaping: symbols [2 * nsymbols] floats
+ * -> iq [4 * nsymbols] floats.  Channel: iq [2 * nsamples] floats in place, one entry per array of `channel`. */
+int dvbs2gpu_pulse_shape_host(const float* symbols, long long nsymbols, double rolloff, double timing, int circular, float* iq);
+int dvbs2gpu_channel_host(float* iq, long long nsamples, const dvbs2gpu_tx_channel* channel, long long stream_index);
+
 /* ------------------------------------------------------------------ soft demap + bit de-interleave
  * replaces S2BBToSoft::process (dvbs2_bb_to_soft.cpp:7-33): constellation_t::demod_soft_lut per payload
  * symbol (constellation.cpp:293-322) followed by S2Deinterleaver::deinterleave (s2_deinterleaver.cpp:72-136).

@@ -400,6 +400,14 @@ PROTOTYPES = {
     'dvbs2gpu_fec_encode_batch': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
     'dvbs2gpu_fec_channel_ber_batch': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'dvbs2gpu_fec_encode_plan_dump': (_i, [_i, _i, _vp, C.POINTER(C.c_int32)]),
+    'dvbs2gpu_s2_tx_sizes': (_i, [_vp, _i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    'dvbs2gpu_pl_frame_batch': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    'dvbs2gpu_pulse_shape_batch': (_i, [_vp, _vp, _i, C.c_longlong, C.c_double, C.c_double, _i, _vp, _vp]),
+    'dvbs2gpu_channel_batch': (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp]),
+    'dvbs2gpu_s2_modulate_batch': (_i, [_vp, _vp, _i, _vp, _i, C.c_double, C.c_double, _i, _vp, _vp, _vp]),
+    'dvbs2gpu_s2_tx_host': (_i, [_vp, _i, _vp, C.c_double, C.c_double, _i, _vp, C.c_longlong, _vp, _vp]),
+    'dvbs2gpu_pulse_shape_host': (_i, [_vp, C.c_longlong, C.c_double, C.c_double, _i, _vp]),
+    'dvbs2gpu_channel_host': (_i, [_vp, C.c_longlong, _vp, C.c_longlong]),
     'dvbs2gpu_demap_batch': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'dvbs2gpu_deinterleave_batch': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     'dvbs2gpu_set_stage_timing': (_i, [_vp, _i]),
@@ -689,6 +697,79 @@ def fec_encode_plan(rate, shortframes=False):
     return d
 
 
+class TxChannel(C.Structure):
+    """dvbs2gpu_tx_channel: pointers to the channel's host arrays"""
+    _fields_ = [('esn0_db', _vp), ('cfo', _vp), ('phase0', _vp), ('seed', _vp)]
+
+
+def _tx_channel(esn0_db, cfo, phase0, seed, nstreams):
+    """-> (TxChannel, the numpy arrays it points to); scalars are repeated for every stream"""
+    import numpy as np
+    arrs = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dt), (nstreams,))) for v, dt in
+            ((esn0_db, np.float64), (cfo, np.float64), (phase0, np.float64), (seed, np.uint64))]
+    return TxChannel(*[a.ctypes.data for a in arrs]), arrs
+
+
+def _pls_array(pls):
+    import numpy as np
+    return np.ascontiguousarray(np.asarray(pls, np.int32).reshape(-1))
+
+
+def s2_tx_sizes(pls):
+    """Host-only: the sizes of one stream's block for a PLS list (pls = modcod << 2 | short << 1 | pilots, modcod 0 = dummy PLFRAME)
+    -> dict 'symbols', 'bbframe_bytes', 'code_bytes'"""
+    lib = load_library()
+    a = _pls_array(pls)
+    o = [C.c_longlong() for _ in range(3)]
+    rc = lib.dvbs2gpu_s2_tx_sizes(a.ctypes.data, a.size, C.byref(o[0]), C.byref(o[1]), C.byref(o[2]))
+    if rc != 0:
+        raise Dvbs2GpuError(rc, lib.dvbs2gpu_last_error().decode())
+    return {'symbols': int(o[0].value), 'bbframe_bytes': int(o[1].value), 'code_bytes': int(o[2].value)}
+
+
+def s2_tx_host(pls, code, rolloff=0.35, timing=0.0, circular=False, esn0_db=None, cfo=0.0, phase0=0.0, seed=0, stream=0, want_iq=True):
+    """Host-only: the modulator's rules (csrc/s2_tx_rules.h) on the CPU for one stream.  code: uint8, the frames' code words one behind the other.
+    -> (symbols complex64 [symbols], iq complex64 [2 * symbols] or None); the channel is applied when esn0_db is given"""
+    import numpy as np
+    lib = load_library()
+    a = _pls_array(pls)
+    sz = s2_tx_sizes(a)
+    code = np.ascontiguousarray(np.asarray(code, np.uint8).reshape(-1))
+    assert code.size == sz['code_bytes'], (code.size, sz['code_bytes'])
+    sym = np.zeros(sz['symbols'], np.complex64)
+    iq = np.zeros(2 * sz['symbols'], np.complex64) if want_iq else None
+    ch, keep = (None, None) if esn0_db is None else _tx_channel(esn0_db, cfo, phase0, seed, 1)
+    rc = lib.dvbs2gpu_s2_tx_host(a.ctypes.data, a.size, code.ctypes.data if code.size else None, float(rolloff), float(timing), int(bool(circular)),
+                                 C.addressof(ch) if ch is not None else None, int(stream), sym.ctypes.data, iq.ctypes.data if want_iq else None)
+    if rc != 0:
+        raise Dvbs2GpuError(rc, lib.dvbs2gpu_last_error().decode())
+    return sym, iq
+
+
+def pulse_shape_host(symbols, rolloff=0.35, timing=0.0, circular=False):
+    """Host-only: the shaping stage of s2_tx_host for any block of symbols, complex64 [n] -> iq complex64 [2 n]"""
+    import numpy as np
+    lib = load_library()
+    symbols = np.ascontiguousarray(np.asarray(symbols, np.complex64).reshape(-1))
+    iq = np.zeros(2 * symbols.size, np.complex64)
+    rc = lib.dvbs2gpu_pulse_shape_host(symbols.ctypes.data, symbols.size, float(rolloff), float(timing), int(bool(circular)), iq.ctypes.data)
+    if rc != 0:
+        raise Dvbs2GpuError(rc, lib.dvbs2gpu_last_error().decode())
+    return iq
+
+
+def channel_host(iq, esn0_db=200.0, cfo=0.0, phase0=0.0, seed=0, stream=0):
+    """Host-only: the channel stage of s2_tx_host for any block, complex64 [n] -> a changed copy; `stream` is the stream's index in a device call"""
+    import numpy as np
+    lib = load_library()
+    out = np.array(np.asarray(iq, np.complex64).reshape(-1), copy=True, order='C')
+    ch, keep = _tx_channel(esn0_db, cfo, phase0, seed, 1)
+    rc = lib.dvbs2gpu_channel_host(out.ctypes.data, out.size, C.addressof(ch), int(stream))
+    if rc != 0:
+        raise Dvbs2GpuError(rc, lib.dvbs2gpu_last_error().decode())
+    return out
+
+
 class FleetEntry(C.Structure):
     """dvbs2gpu_fleet_entry"""
     _fields_ = [('cfg', DemodCfg), ('weight', C.c_double), ('max_samples', C.c_int32), ('reserved', C.c_int32)]
@@ -952,6 +1033,68 @@ class Engine:
         self._check(self.lib.dvbs2gpu_fec_channel_ber_batch(self.h, int(rate), int(bool(shortframes)), _ptr(llr), _ptr(bbframes), _ptr(corrections), F,
                                                             _ptr(errors), _ptr(counted), self._stream()))
         return errors, counted
+
+    # ---- modulator: code words -> PL symbols -> 2-sps IQ -> channel (csrc/s2_tx.hip)
+    def pl_frame(self, code, pls, nstreams=None, code_off=None, code_stride=None, out=None):
+        """code uint8: the code words of the PLS list `pls`, by default [nstreams, code_bytes] (a stream's code words one behind the other); with code_off /
+        code_stride (bytes, one per frame) frame f of stream s is read at code_off[f] + s * code_stride[f] -> symbols complex64 [nstreams, symbols]"""
+        import numpy as np
+        t = self.torch
+        a = _pls_array(pls)
+        sz = s2_tx_sizes(a)
+        assert code.dtype == t.uint8 and code.is_cuda and code.is_contiguous()
+        if code_off is None:
+            assert code.dim() == 2 and code.shape[1] == sz['code_bytes']
+            nstreams = code.shape[0]
+            off = stride = None
+        else:
+            off = np.ascontiguousarray(np.asarray(code_off, np.int64))
+            stride = np.ascontiguousarray(np.asarray(code_stride, np.int64))
+            assert off.shape == (a.size,) and stride.shape == (a.size,) and nstreams is not None
+            for f in range(a.size):     # the last byte read lies inside `code`
+                if a[f] >> 2:
+                    assert off[f] >= 0 and stride[f] >= 0 and off[f] + (nstreams - 1) * stride[f] + s2_tx_sizes([a[f]])['code_bytes'] <= code.numel()
+        if out is None:
+            out = t.empty((nstreams, sz['symbols']), dtype=t.complex64, device=code.device)
+        assert out.dtype == t.complex64 and out.is_cuda and out.is_contiguous() and out.shape == (nstreams, sz['symbols'])
+        self._check(self.lib.dvbs2gpu_pl_frame_batch(self.h, a.ctypes.data, a.size, _ptr(code), off.ctypes.data if off is not None else None,
+                                                     stride.ctypes.data if stride is not None else None, int(nstreams), _ptr(out), self._stream()))
+        return out
+
+    def pulse_shape(self, symbols, rolloff=0.35, timing=0.0, circular=False, out=None):
+        """symbols complex64 [nstreams, symbols] -> IQ complex64 [nstreams, 2 * symbols]"""
+        t = self.torch
+        assert symbols.dtype == t.complex64 and symbols.is_cuda and symbols.is_contiguous() and symbols.dim() == 2
+        S, n = symbols.shape
+        if out is None:
+            out = t.empty((S, 2 * n), dtype=t.complex64, device=symbols.device)
+        assert out.dtype == t.complex64 and out.is_cuda and out.is_contiguous() and out.shape == (S, 2 * n)
+        self._check(self.lib.dvbs2gpu_pulse_shape_batch(self.h, _ptr(symbols), S, n, float(rolloff), float(timing), int(bool(circular)), _ptr(out), self._stream()))
+        return out
+
+    def channel(self, iq, esn0_db=200.0, cfo=0.0, phase0=0.0, seed=0):
+        """iq complex64 [nstreams, nsamples], changed in place: rotation by phase0 + cfo * n, AWGN at esn0_db (>= 100: none); each parameter a scalar or one
+        value per stream -> iq"""
+        t = self.torch
+        assert iq.dtype == t.complex64 and iq.is_cuda and iq.is_contiguous() and iq.dim() == 2
+        ch, keep = _tx_channel(esn0_db, cfo, phase0, seed, iq.shape[0])
+        self._check(self.lib.dvbs2gpu_channel_batch(self.h, _ptr(iq), iq.shape[0], iq.shape[1], ch.esn0_db, ch.cfo, ch.phase0, ch.seed, self._stream()))
+        return iq
+
+    def modulate(self, bbframes, pls, nstreams, rolloff=0.35, timing=0.0, circular=False, esn0_db=None, cfo=0.0, phase0=0.0, seed=0, out=None):
+        """bbframes uint8, frame-major: for every frame of the PLS list its nstreams BBFRAMEs of kbch/8 bytes (dummy frames take none), one flat tensor of
+        nstreams * bbframe_bytes -> IQ complex64 [nstreams, 2 * symbols]; the channel is applied when esn0_db is given"""
+        t = self.torch
+        a = _pls_array(pls)
+        sz = s2_tx_sizes(a)
+        assert bbframes.dtype == t.uint8 and bbframes.is_cuda and bbframes.is_contiguous() and bbframes.numel() == nstreams * sz['bbframe_bytes']
+        if out is None:
+            out = t.empty((nstreams, 2 * sz['symbols']), dtype=t.complex64, device=bbframes.device)
+        assert out.dtype == t.complex64 and out.is_cuda and out.is_contiguous() and out.shape == (nstreams, 2 * sz['symbols'])
+        ch, keep = (None, None) if esn0_db is None else _tx_channel(esn0_db, cfo, phase0, seed, nstreams)
+        self._check(self.lib.dvbs2gpu_s2_modulate_batch(self.h, a.ctypes.data, a.size, _ptr(bbframes), int(nstreams), float(rolloff), float(timing),
+                                                        int(bool(circular)), C.addressof(ch) if ch is not None else None, _ptr(out), self._stream()))
+        return out
 
     def demap(self, frames, modcod, shortframes=False, pilots=False):
         """frames complex64 [F, plframe] (PLL output) -> LLR int8 [F, N]"""

@@ -761,4 +761,174 @@ int dvbs2gpu_fec_encode_plan_dump(int rate, int shortframes, uint8_t* bch_genera
     return 0;
 }
 
+// ---- the modulator (s2_tx.hip, rules: s2_tx_rules.h): every argument is looked at before anything is enqueued
+static int tx_list(const char* who, const int32_t* pls, int nframes, s2tx::ListSizes* total, std::vector<long long>* sym_off = nullptr,
+                   std::vector<long long>* bb_off = nullptr, std::vector<long long>* code_off = nullptr) {
+    if (nframes < 0) return enc_bad(who, "negative frame count");
+    if (nframes > 0 && !pls) return enc_bad(who, "null pointer");
+    int bad = 0;
+    if (!s2tx::list_sizes(pls, nframes, total, &bad, sym_off, bb_off, code_off)) {
+        g_err = std::string(who) + ": frame " + std::to_string(bad) + " has no valid PLS code (" + std::to_string(pls[bad]) + ": reserved MODCOD, or short 9/10)";
+        return DVBS2GPU_ERR_ARG;
+    }
+    return 0;
+}
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static const char* shape_refusal(double rolloff, double timing) {
+    if (!s2tx::rolloff_ok(rolloff)) return "roll-off is none of 0.35, 0.25, 0.20";
+    if (!(timing >= -2.0 && timing <= 2.0)) return "timing outside -2..2 samples";
+    return nullptr;
+}
+static const char* channel_refusal(const dvbs2gpu_tx_channel* ch, int nstreams) {
+    if (!ch->esn0_db || !ch->cfo || !ch->phase0 || !ch->seed) return "null pointer (channel arrays)";
+    for (int s = 0; s < nstreams; ++s)
+        if (!(ch->esn0_db[s] >= -50.0) || !(std::fabs(ch->cfo[s]) <= 4.0) || !(std::fabs(ch->phase0[s]) <= 1e6))
+            return "channel parameter not finite or out of range (esn0_db >= -50, |cfo| <= 4, |phase0| <= 1e6)";
+    return nullptr;
+}
+
+int dvbs2gpu_s2_tx_sizes(const int32_t* pls, int nframes, long long* symbols, long long* bbframe_bytes, long long* code_bytes) {
+    s2tx::ListSizes total;
+    RC_TRY(tx_list("s2_tx_sizes", pls, nframes, &total));
+    if (symbols) *symbols = total.symbols;
+    if (bbframe_bytes) *bbframe_bytes = total.bb_bytes;
+    if (code_bytes) *code_bytes = total.code_bytes;
+    return 0;
+}
+
+int dvbs2gpu_pl_frame_batch(dvbs2gpu_ctx* ctx, const int32_t* pls, int nframes, const uint8_t* d_code, const long long* code_off, const long long* code_stride,
+                            int nstreams, float* d_symbols, void* stream) {
+    if (!ctx) return enc_bad("pl_frame_batch", "no context");
+    if (nstreams < 0) return enc_bad("pl_frame_batch", "negative stream count");
+    s2tx::ListSizes total;
+    std::vector<long long> packed_off;
+    RC_TRY(tx_list("pl_frame_batch", pls, nframes, &total, nullptr, nullptr, &packed_off));
+    if ((code_off == nullptr) != (code_stride == nullptr)) return enc_bad("pl_frame_batch", "code_off and code_stride are given together or not at all");
+    if (nframes == 0 || nstreams == 0) return 0;
+    if (!d_symbols || (total.code_bytes > 0 && !d_code)) return enc_bad("pl_frame_batch", "null pointer");
+    if (!aligned16(d_symbols)) return enc_bad("pl_frame_batch", "d_symbols is not 16-byte aligned");
+    std::vector<long long> packed_stride;
+    if (!code_off) {        // stream-major, a stream's code words one behind the other
+        packed_stride.assign((size_t)nframes, total.code_bytes);
+        code_off = packed_off.data(); code_stride = packed_stride.data();
+    }
+    for (int f = 0; f < nframes; ++f)
+        if ((pls[f] >> 2) != 0 && (code_off[f] < 0 || code_stride[f] < 0)) return enc_bad("pl_frame_batch", "negative code-word offset or stride");
+    CallGuard guard(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    return tx_pl_frame(ctx, pls, nframes, d_code, code_off, code_stride, nstreams, (cf32*)d_symbols, (hipStream_t)stream);
+}
+
+int dvbs2gpu_pulse_shape_batch(dvbs2gpu_ctx* ctx, const float* d_symbols, int nstreams, long long symbols, double rolloff, double timing, int circular,
+                               float* d_iq, void* stream) {
+    if (!ctx) return enc_bad("pulse_shape_batch", "no context");
+    if (nstreams < 0 || symbols < 0) return enc_bad("pulse_shape_batch", "negative count");
+    if (const char* why = shape_refusal(rolloff, timing)) return enc_bad("pulse_shape_batch", why);
+    if (nstreams == 0 || symbols == 0) return 0;
+    if (!d_symbols || !d_iq) return enc_bad("pulse_shape_batch", "null pointer");
+    if ((const float*)d_iq == d_symbols) return enc_bad("pulse_shape_batch", "d_symbols and d_iq are the same buffer");
+    if (!aligned16(d_iq)) return enc_bad("pulse_shape_batch", "d_iq is not 16-byte aligned");
+    CallGuard guard(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    return tx_pulse_shape(ctx, (const cf32*)d_symbols, nstreams, symbols, rolloff, timing, circular, (cf32*)d_iq, (hipStream_t)stream);
+}
+
+int dvbs2gpu_channel_batch(dvbs2gpu_ctx* ctx, float* d_iq, int nstreams, long long nsamples, const double* esn0_db, const double* cfo, const double* phase0,
+                           const uint64_t* seed, void* stream) {
+    if (!ctx) return enc_bad("channel_batch", "no context");
+    if (nstreams < 0 || nsamples < 0) return enc_bad("channel_batch", "negative count");
+    const dvbs2gpu_tx_channel ch{esn0_db, cfo, phase0, seed};
+    if (nstreams > 0) if (const char* why = channel_refusal(&ch, nstreams)) return enc_bad("channel_batch", why);
+    if (nstreams == 0 || nsamples == 0) return 0;
+    if (!d_iq) return enc_bad("channel_batch", "null pointer");
+    CallGuard guard(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    RC_TRY(tx_buffers_enter(ctx, st));
+    const int rc = tx_channel(ctx, (cf32*)d_iq, nstreams, nsamples, esn0_db, cfo, phase0, seed, st);
+    const int rc2 = tx_buffers_leave(ctx, st);
+    return rc ? rc : rc2;
+}
+
+int dvbs2gpu_s2_modulate_batch(dvbs2gpu_ctx* ctx, const int32_t* pls, int nframes, const uint8_t* d_bbframes, int nstreams, double rolloff, double timing,
+                               int circular, const dvbs2gpu_tx_channel* channel, float* d_iq, void* stream) {
+    if (!ctx) return enc_bad("s2_modulate_batch", "no context");
+    if (nstreams < 0) return enc_bad("s2_modulate_batch", "negative stream count");
+    s2tx::ListSizes total;
+    std::vector<long long> bb_off, code_off;
+    RC_TRY(tx_list("s2_modulate_batch", pls, nframes, &total, nullptr, &bb_off, &code_off));
+    if (const char* why = shape_refusal(rolloff, timing)) return enc_bad("s2_modulate_batch", why);
+    if (channel && nstreams > 0) if (const char* why = channel_refusal(channel, nstreams)) return enc_bad("s2_modulate_batch", why);
+    if (nframes == 0 || nstreams == 0) return 0;
+    if (!d_iq || (total.bb_bytes > 0 && !d_bbframes)) return enc_bad("s2_modulate_batch", "null pointer");
+    if (!aligned16(d_iq)) return enc_bad("s2_modulate_batch", "d_iq is not 16-byte aligned");
+    if ((long long)nstreams * nframes > 0x7fffffffLL) return enc_bad("s2_modulate_batch", "more than 2^31 - 1 frames");
+    CallGuard guard(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    RC_TRY(tx_buffers_enter(ctx, st));
+    int rc = ctx->tx.code.ensure((size_t)nstreams * (size_t)total.code_bytes + 16);
+    if (!rc) rc = ctx->tx.sym.ensure((size_t)nstreams * (size_t)total.symbols * sizeof(cf32));
+    uint8_t* code = (uint8_t*)ctx->tx.code.p;
+    // frame-major code words, [frame][stream][N / 8]: the frames of one code that follow one another (dummy frames between them take no bytes) are one
+    // fec_encode launch set over (frames x streams) rows
+    std::vector<long long> off((size_t)nframes, 0), stride((size_t)nframes, 0);
+    for (int a = 0; a < nframes && !rc;) {
+        s2tx::FrameRule R;
+        s2tx::frame_rule(pls[a], &R);
+        if (R.dummy) { ++a; continue; }
+        int b = a, rows = 0;
+        for (; b < nframes; ++b) {
+            s2tx::FrameRule Q;
+            s2tx::frame_rule(pls[b], &Q);
+            if (Q.dummy) continue;
+            if (Q.fec_rate != R.fec_rate || Q.shortframe != R.shortframe) break;
+            off[b] = (long long)nstreams * code_off[b]; stride[b] = Q.code_bytes;
+            ++rows;
+        }
+        FecParams f;
+        fec_params(R.fec_rate, R.shortframe, &f);
+        rc = fec_encode_run(ctx, f, d_bbframes + (size_t)nstreams * bb_off[a], rows * nstreams, code + (size_t)nstreams * code_off[a], st);
+        a = b;
+    }
+    if (!rc) rc = tx_pl_frame(ctx, pls, nframes, code, off.data(), stride.data(), nstreams, (cf32*)ctx->tx.sym.p, st);
+    if (!rc) rc = tx_pulse_shape(ctx, (const cf32*)ctx->tx.sym.p, nstreams, total.symbols, rolloff, timing, circular, (cf32*)d_iq, st);
+    if (!rc && channel) rc = tx_channel(ctx, (cf32*)d_iq, nstreams, 2 * total.symbols, channel->esn0_db, channel->cfo, channel->phase0, channel->seed, st);
+    const int rc2 = tx_buffers_leave(ctx, st);
+    return rc ? rc : rc2;
+}
+
+int dvbs2gpu_s2_tx_host(const int32_t* pls, int nframes, const uint8_t* code, double rolloff, double timing, int circular, const dvbs2gpu_tx_channel* channel,
+                        long long stream_index, float* symbols, float* iq) {
+    s2tx::ListSizes total;
+    RC_TRY(tx_list("s2_tx_host", pls, nframes, &total));
+    if (iq) if (const char* why = shape_refusal(rolloff, timing)) return enc_bad("s2_tx_host", why);
+    if (iq && channel) if (const char* why = channel_refusal(channel, 1)) return enc_bad("s2_tx_host", why);
+    if (stream_index < 0) return enc_bad("s2_tx_host", "negative stream index");
+    if (nframes == 0) return 0;
+    if (total.code_bytes > 0 && !code) return enc_bad("s2_tx_host", "null pointer");
+    tx_host(pls, nframes, code, rolloff, timing, circular, channel ? channel->esn0_db : nullptr, channel ? channel->cfo : nullptr,
+            channel ? channel->phase0 : nullptr, channel ? channel->seed : nullptr, stream_index, (cf32*)symbols, (cf32*)iq);
+    return 0;
+}
+
+int dvbs2gpu_pulse_shape_host(const float* symbols, long long nsymbols, double rolloff, double timing, int circular, float* iq) {
+    if (nsymbols < 0) return enc_bad("pulse_shape_host", "negative count");
+    if (const char* why = shape_refusal(rolloff, timing)) return enc_bad("pulse_shape_host", why);
+    if (nsymbols == 0) return 0;
+    if (!symbols || !iq) return enc_bad("pulse_shape_host", "null pointer");
+    tx_shape_host((const cf32*)symbols, nsymbols, rolloff, timing, circular, (cf32*)iq);
+    return 0;
+}
+
+int dvbs2gpu_channel_host(float* iq, long long nsamples, const dvbs2gpu_tx_channel* channel, long long stream_index) {
+    if (nsamples < 0 || stream_index < 0) return enc_bad("channel_host", "negative count");
+    if (!channel) return enc_bad("channel_host", "null pointer");
+    if (const char* why = channel_refusal(channel, 1)) return enc_bad("channel_host", why);
+    if (nsamples == 0) return 0;
+    if (!iq) return enc_bad("channel_host", "null pointer");
+    tx_channel_host((cf32*)iq, nsamples, *channel->esn0_db, *channel->cfo, *channel->phase0, *channel->seed, stream_index);
+    return 0;
+}
+
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include "scratch_layout.h"
 #include "rx_cfg_rules.h"
 #include "dev_buf.h"
+#include "s2_tx.h"
 #include <type_traits>
 
 namespace s2 {
@@ -251,6 +252,8 @@ struct dvbs2gpu_ctx {
     s2::Workspace ws_dvbs[4];
     // FEC encoder (fec_encode.hip): the tables of a code, by code_index
     std::map<int, s2::FecEncCode> fec_enc;
+    // modulator (s2_tx.hip): constellation tables, the buffers of dvbs2gpu_s2_modulate_batch, the channel's table
+    s2::TxState tx;
 };
 
 namespace s2 {
@@ -270,6 +273,7 @@ int get_prbs(dvbs2gpu_ctx* ctx);
 int get_fec_enc(dvbs2gpu_ctx* ctx, const FecParams& f, FecEncDeviceCode** out);
 // LLR -> BBFRAME for nframes frames of one code; all pointers device
 std::vector<float> make_polyphase_bank(int phases, int taps_per_phase);
+int get_rx_tables(dvbs2gpu_ctx* ctx);                // ctx->pl (and the timing recovery's bank), built on first use
 int get_rrc(dvbs2gpu_ctx* ctx, int ntaps, float alpha, double Ts, float** out);
 void critically_damped(float bw, float* alpha, float* beta);
 int fec_run(dvbs2gpu_ctx* ctx, const FecParams& f, const int8_t* d_llr, int nframes, int max_trials, int force, uint8_t* d_bbframes,

@@ -4,10 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "launch_count.h"
+#include "s2_pl_tables.h"   // cf32
 
 namespace s2 {
-
-struct cf32 { float re, im; };
 
 constexpr int RRC_MAX_TAPS = 129;
 constexpr int GARDNER_PHASES = 128;

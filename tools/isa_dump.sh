@@ -6,7 +6,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 SRC=$ROOT/sdrpp-dvbs-demodulator_amd/csrc
 mkdir -p /tmp/isa
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$ROOT/include"
-case "$1" in s2_rx_kernels|s2_demod|dvbs_demod) FLAGS="$FLAGS -ffp-contract=off";; esac
+case "$1" in s2_rx_kernels|s2_demod|dvbs_demod|s2_tx) FLAGS="$FLAGS -ffp-contract=off";; esac
 /opt/rocm/bin/hipcc $FLAGS -S --cuda-device-only -o /tmp/isa/$1.s $SRC/$1.hip 2>&1 | grep -v "argument unused" || true
 if [ -n "$2" ]; then
   awk -v pat="$2" '$0 ~ "^_Z.*" pat ".*:" {p=1} p{print} /^\.Lfunc_end/{if(p)exit}' /tmp/isa/$1.s > /tmp/isa/$1.kernel.s
